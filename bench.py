@@ -2,7 +2,7 @@
 """bench.py - BASELINE.json metric: 2-ch 512x512 slices/sec on N MI355X (config 2: synthetic batch=64, one ts2d-v2
 sub-model (K=18), fp32).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: either under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`, or plain
      `python bench.py --gpus N`: with no WORLD_SIZE in the environment the script starts that launcher itself as a CHILD process -
      one rank per GPU, the reference's counterpart being its `mp.Pool` of workers, ts2d/core/inference/predictor.py:79-86 -
@@ -12,7 +12,9 @@ sub-model (K=18), fp32).
 One "step" = one forward pass of the hot path (the whole PlainConvUNet, input NCHW -> fp32 logits NCHW + packed masks)
 over one batch of 64 synthetic slices per GPU, inputs already resident in HBM.  Slices shard over ranks with no
 data-path collective (weak scaling); weights are broadcast once from rank 0 with RCCL before the timed region.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  The inputs come from a fixed seed, so the same arguments give the same batch in every run;
+`--dump-outputs DIR` writes what the last timed step left in the caller's buffers (rank 0: DIR/logits.npy, DIR/mask.npy; see
+dump_outputs), so that two builds of the library can be compared output for output.
 
 Other BASELINE configurations (same contract, ONE JSON line each; `config.workload` names the configuration):
     python bench.py --workload config3          five ts2d-v2 sub-models (117 labels) on one batch of 128, 16-bit mode
@@ -34,8 +36,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-PEAK_FP32_MFMA_TFLOPS = 157.3     # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
-PEAK_F16_MFMA_TFLOPS = 2500.0     # dense fp16/bf16 MFMA peak (same guide); the split path issues 3 fp16 MFMA products per MAC
+PEAK_FP32_MFMA_TFLOPS = 157.3     # v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
+PEAK_F16_MFMA_TFLOPS = 2500.0     # dense fp16/bf16 MFMA peak; the split path issues 3 fp16 MFMA products per MAC
 MEASURED_F16_PIPE_TFLOPS = 32768 * 1024 / 20.8e-9 / 1e12      # 32x32x16 MFMA = 32768 FLOP, 1024 SIMDs, 20.8 ns each (probe): ~1613
 PEAK_HBM_GBS = 8000.0
 MEASURED_HBM_MIXED_GBS = 4700.0   # copy / 4:3 read:write streaming rate measured on this pool (scripts/probes/hbm_probe.hip)
@@ -129,6 +131,26 @@ def oracle_check(arch, sd, x4, logits4, mask4, emulate=None):
                 worst = max(worst, dist)
                 all_tol = all_tol and dist <= errs[-1]
     return errs, flips, bits, worst, all_tol
+
+
+DUMP_ELEMS = 1 << 22              # --dump-outputs: elements kept per array (16 MB as float32, 32 MB for the two arrays)
+
+
+def dump_outputs(torch, d, logits, mask):
+    """`--dump-outputs d`: the two arrays a caller of the timed step receives, as d/logits.npy (fp32 logits) and d/mask.npy (the packed
+    mask words unpacked to 0.0 / 1.0 per pixel, float32).  Arrays of more than DUMP_ELEMS elements are sampled: the same positions
+    of both, DUMP_ELEMS flat indices into the B x K x H x W logits drawn from a fixed seed (sorted, repeats dropped) - every slice, label and
+    image region is covered, and the files of two runs with the same arguments line up element for element."""
+    n = logits.numel()
+    if n > DUMP_ELEMS:
+        idx = torch.from_numpy(np.unique(np.random.default_rng(0).integers(0, n, DUMP_ELEMS))).to(logits.device)
+    else:
+        idx = torch.arange(n, device=logits.device)
+    # bit w % 32 of word w // 32 of a row is pixel w (engine.unpack_mask); W is a multiple of 32, so the same holds for flat indices
+    bits = (mask.reshape(-1)[idx // 32] >> (idx % 32)) & 1
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'logits.npy'), logits.reshape(-1)[idx].cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(d, 'mask.npy'), bits.cpu().numpy().astype(np.float32))
 
 
 def timed_forward(torch, dev, fn, rounds=3, reps=3):
@@ -367,11 +389,15 @@ def main():
     ap.add_argument('--precision', choices=('split', 'exact', 'f16'), default=None,
                     help="split: fp16 hi/lo x3 MFMA with fp32 accumulation (fp32-equivalent accuracy, default); exact: fp32 MFMA; "
                          "f16: fp16 storage + one fp16 MFMA product (BASELINE configs 3/5, outside the fp32 parity tolerance)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='config 2: after the timed steps rank 0 writes the logits and masks of the last one (a fixed sample) as DIR/<name>.npy')
     args = ap.parse_args()
     if args.stream is not None and args.workload == 'config2':
         args.workload = 'config4'
     if args.precision is None:
         args.precision = 'f16' if args.workload == 'config3' else 'split'
+    if args.dump_outputs is not None and (args.workload != 'config2' or os.environ.get('TS2D_BENCH_DRYRUN')):
+        ap.error('--dump-outputs is implemented for the config-2 workload on a GPU only')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # not under a launcher: start one (child process), relay its exit code; nothing below runs in this process
@@ -501,6 +527,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = parallel.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs is not None and rank == 0:                        # before the legs below run other modes into the same buffers
+        dump_outputs(torch, args.dump_outputs, logits, mask)
 
     stream_res = None
     if world > 1:            # config 4 on the same ranks (outside the timed region above): 10k-slice stream, contiguous blocks

@@ -1,5 +1,5 @@
 import time, sys, os
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from totalsegmentator2d_amd.arch import UNetArch
 from totalsegmentator2d_amd import weights
 from totalsegmentator2d_amd.engine import Engine

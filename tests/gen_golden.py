@@ -9,7 +9,6 @@ from __future__ import annotations
 
 import hashlib
 import os
-import shutil
 import sys
 
 import numpy as np
@@ -81,13 +80,8 @@ def main():
     np.savez_compressed(os.path.join(OUT, 'sliding_window.npz'), g512_diag=np.diag(g).copy(), g512_row0=g[0].copy(),
                         g512_centre=g[256].copy(), g64x96=g2, **{f'steps/{k}': v for k, v in steps.items()})
     sliding_window_goldens()
-    # (v) real-data plumbing: the reference's own sample assets (data files) + z-scored checksums
+    # (v) real-data plumbing: z-scored checksums of the reference's own sample assets (data files, kept in golden/assets)
     adir = os.path.join(OUT, 'assets')
-    os.makedirs(adir, exist_ok=True)
-    ref_assets = '/root/reference/assets'
-    for f in ('sample_s0616.nrrd', 'sample_s0332.nrrd', 'sample_s0521.nrrd', 'sample_chexpert.nrrd'):
-        if os.path.exists(os.path.join(ref_assets, f)):
-            shutil.copyfile(os.path.join(ref_assets, f), os.path.join(adir, f))
     from totalsegmentator2d_amd import nrrd
     img = nrrd.read(os.path.join(adir, 'sample_s0616.nrrd'))
     a = np.moveaxis(np.asarray(img.array), -1, 0).astype(np.float32)
