@@ -153,6 +153,44 @@ int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp
                               const int32_t* tile_y, const int32_t* tile_x, int mirror_mask, const uint16_t* gaussian_f16,
                               uint16_t* logits_f16, uint8_t* seg_u8);
 
+/* Sliding-window inference of N preprocessed 2-D images as ONE engine batch (ABI 8).  Replaces the reference's way of driving several
+ * inputs at once - `apply` submits every input to its worker pool before it waits for any (ts2d/core/inference/nnu.py:194-216) and each
+ * worker runs predict_logits_from_preprocessed_data per input (ts2d/core/inference/prediction_worker.py:209) - by one call: the rows
+ * (tile x mirror variant) of all images travel through the network together, so a folder of cases, or the z slices of a stack, pay one
+ * stream synchronise per call and run at the large-batch rate of the kernels.
+ *   images         n_images descriptors.  Extents and tile counts may differ per image; patch, mirror_mask, gaussian_f16 and the tile
+ *                  dtype (ts2d_engine_set_tile_dtype) are shared.  Per image: `image`, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16 and
+ *                  seg_u8 mean what they mean in ts2d_engine_predict_tiled (at least one output non-NULL); inf_flag is written by the
+ *                  call: 1 if this image's aggregated logits hold an inf.  ts2d_engine_tiled_inf_flag() is the OR over the images.
+ *   n_images == 0  returns TS2D_OK and does nothing.
+ * Every argument is validated before any device work; an error names the image ("image 3: tile 1 at (..) leaves ..") and nothing is written.
+ * Determinism rule: inside ts2d_engine_predict_tiled_batch the network always takes the full-batch dispatch (no "sbk" split-K, composed
+ * decoder entries stay composed), whatever the size of a chunk.  A row's logits are then a function of its own pixels and the weights
+ * only: a case's logits_f16 / seg_u8 bytes are identical whatever its batch-mates, its position in the batch and the batch size, and
+ * identical, bit for bit, to ts2d_engine_predict_tiled on an engine with option "sbk" = 0.  Against the default single-case path ("sbk"
+ * on) they agree to fp32 summation order: a few float16 ulps at most on the aggregated logits (each rounding into the half buffer may flip).  The handle's options are not touched.
+ * (A batch of ONE small case is slower this way than ts2d_engine_predict_tiled - 4.3 against 4.0 ms at 8 rows of the canonical net.)
+ * Row packing: the n_tiles x V rows of an image are consecutive; chunks of at most 64 rows are filled greedily with whole images; an
+ * image with more than 64 rows takes chunks of its own, split in 64s.  Per chunk: one gather launch, one forward, one aggregate launch.
+ * Device scratch (grown before the first launch, kept by the handle): R x (K + C) x patch_h x patch_w x 4 bytes with
+ * R = max(rows of the fullest chunk <= 64, rows of the largest image) - NOT n_images x rows - plus, summed over the images,
+ * C x Hp x Wp x 4 (inputs) and K x Hp x Wp x 3 (half + uint8 outputs, each only if some image asks for it), plus 64 bytes per
+ * (image, chunk) pair and 8 per tile.  Canonical net (K = 26, C = 2, 512 x 512 patch), 8 cases of 512 x 768: 64 rows -> 1.88 GB of tile
+ * logits + batch, 0.27 GB of inputs and outputs.  Synchronous: one stream synchronise per call, then ts2d_engine_check. */
+typedef struct {
+    const float*   image;        /* host [C, Hp, Wp] fp32, already padded to at least the patch */
+    int32_t        Hp, Wp;
+    int32_t        n_tiles;
+    const int32_t* tile_y;       /* host, n_tiles origins in upstream order */
+    const int32_t* tile_x;
+    uint16_t*      logits_f16;   /* host [K, Hp, Wp] half bits, or NULL */
+    uint8_t*       seg_u8;       /* host [K, Hp, Wp], or NULL */
+    int32_t        inf_flag;     /* out: this image's aggregated logits hold an inf */
+} ts2d_tiled_image;
+
+int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int patch_h, int patch_w,
+                                    int mirror_mask, const uint16_t* gaussian_f16);
+
 /* Blend order of ts2d_engine_predict_tiled (upstream `prediction *= gaussian; predicted_logits[sl] += prediction` with
  * float16 `predicted_logits`; reached from ts2d/core/inference/prediction_worker.py:209):
  *   TS2D_TILE_F32 (default) the reference's CPU path (nnu.py:161-163: device=cpu when torch.cuda.is_available() is false - no autocast): the tile prediction is
@@ -171,7 +209,8 @@ int ts2d_engine_set_tile_dtype(ts2d_engine* e, int mode);
  * forward does: ts2d/core/inference/prediction_worker.py:209.) */
 int ts2d_engine_set_keep_activations(ts2d_engine* e, int enable);
 
-/* 1 if the last ts2d_engine_predict_tiled call produced an infinite aggregated float16 logit - upstream's
+/* 1 if the last ts2d_engine_predict_tiled / ts2d_engine_predict_tiled_batch call (the OR over its images) produced an infinite
+ * aggregated float16 logit - upstream's
  * "Encountered inf in predicted array" check of predict_sliding_window_return_logits (reached from
  * ts2d/core/inference/prediction_worker.py:209), evaluated on the device instead of a host pass over the array. */
 int ts2d_engine_tiled_inf_flag(const ts2d_engine* e);

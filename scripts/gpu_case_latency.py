@@ -53,3 +53,40 @@ with TS2D(models=models) as ts:
         ts.concurrent_models = conc
         best = min(_timed(lambda: ts.predict(img)) for _ in range(5))
         print(f'image in memory, sub-models {"concurrent" if conc else "serial    "}: best of 5: {best * 1e3:.1f} ms per case', flush=True)
+    # ---- several cases at once: TS2D.predict_many (one engine batch per sub-model, ts2d_engine_predict_tiled_batch) against one predict per case,
+    # in-memory copies of the sample, split and 16-bit modes, alternated in one process, best of 5 after warm-up.  Stage times are host-clock
+    # spans summed over the sub-models (the cases of a batch share the `predicted` stamp: the predict span of a batched case is the batch's).
+    def _stages(results):
+        st = {}
+        for res in results:
+            for r in res.data['models'].values():
+                t_ = r['timestamps']
+                for a, b in (('start', 'preprocessed'), ('preprocessed', 'predicted'), ('predicted', 'exported')):
+                    st[b] = st.get(b, 0) + t_[b] - t_[a]
+        return st
+
+    ts.concurrent_models = True
+    for mode in ('split', 'f16'):
+        for m in ts.models.values():
+            for e in m._predictor.engines:
+                e.set_precision(mode)
+                e.set_tile_dtype('half' if mode == 'f16' else 'float')
+        for n in (8, 16):
+            imgs = [img] * n
+            many = ts.predict_many(imgs)                                   # warm-up of both paths at this size
+            single = [ts.predict(img) for _ in range(n)]
+            flips = np.mean([(a.get_segmentation().array != b.get_segmentation().array).mean() for a, b in zip(many, single)])
+            same = all(np.array_equal(many[0].get_segmentation().array, r.get_segmentation().array) for r in many[1:])
+            tb = ts_ = None
+            for _ in range(5):
+                t = time.time(); many = ts.predict_many(imgs); dt = time.time() - t
+                if tb is None or dt < tb[0]:
+                    tb = (dt, _stages(many))
+                t = time.time(); single = [ts.predict(x) for x in imgs]; dt = time.time() - t
+                if ts_ is None or dt < ts_[0]:
+                    ts_ = (dt, _stages(single))
+            for label, (dt, st) in (('predict_many', tb), ('predict x n  ', ts_)):
+                print(f'{mode:5s} {n:2d} cases {label}: best of 5: {dt * 1e3:7.1f} ms = {n / dt:6.1f} cases/s  (summed over cases and sub-models: preprocess '
+                      f'{st["preprocessed"] * 1e3:.1f}, predict {st["predicted"] * 1e3:.1f}, export {st["exported"] * 1e3:.1f} ms)', flush=True)
+            print(f'{mode:5s} {n:2d} cases: predict_many / predict = {ts_[0] / tb[0]:.2f}x cases/s; every case of the batch identical: {same}; '
+                  f'mask bits differing from predict: {flips:.2e}', flush=True)

@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libts2d_engine.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'ts2d_engine.h')
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_STAGES = 16
 PRECISION_F32_EXACT = 0
 PRECISION_F32_SPLIT_F16X3 = 1
@@ -20,7 +20,7 @@ PRECISION_F16 = 2
 
 # every symbol include/ts2d_engine.h declares
 SYMBOLS = ('ts2d_engine_create', 'ts2d_engine_load_weights', 'ts2d_engine_weight_buffer', 'ts2d_engine_weights_ready',
-           'ts2d_engine_forward', 'ts2d_engine_check', 'ts2d_engine_predict_tiled', 'ts2d_engine_tiled_inf_flag', 'ts2d_engine_set_tile_dtype', 'ts2d_engine_set_keep_activations', 'ts2d_project_coronal', 'ts2d_project_coronal_zscore', 'ts2d_synth_slices', 'ts2d_engine_reserve', 'ts2d_engine_workspace_bytes', 'ts2d_engine_set_workspace', 'ts2d_engine_set_precision', 'ts2d_engine_set_option', 'ts2d_engine_set_profiling', 'ts2d_engine_num_ops',
+           'ts2d_engine_forward', 'ts2d_engine_check', 'ts2d_engine_predict_tiled', 'ts2d_engine_predict_tiled_batch', 'ts2d_engine_tiled_inf_flag', 'ts2d_engine_set_tile_dtype', 'ts2d_engine_set_keep_activations', 'ts2d_project_coronal', 'ts2d_project_coronal_zscore', 'ts2d_synth_slices', 'ts2d_engine_reserve', 'ts2d_engine_workspace_bytes', 'ts2d_engine_set_workspace', 'ts2d_engine_set_precision', 'ts2d_engine_set_option', 'ts2d_engine_set_profiling', 'ts2d_engine_num_ops',
            'ts2d_engine_op_name', 'ts2d_engine_op_kernel', 'ts2d_engine_op_times', 'ts2d_engine_debug_tensor', 'ts2d_engine_device_bytes', 'ts2d_engine_destroy',
            'ts2d_last_error', 'ts2d_abi_version')
 
@@ -31,6 +31,13 @@ class ArchDesc(ctypes.Structure):
                 ('features', ctypes.c_int32 * MAX_STAGES), ('n_conv_enc', ctypes.c_int32 * MAX_STAGES),
                 ('n_conv_dec', ctypes.c_int32 * MAX_STAGES), ('norm_eps', ctypes.c_float), ('leaky_slope', ctypes.c_float),
                 ('strides', (ctypes.c_int32 * 2) * MAX_STAGES)]
+
+
+class TiledImage(ctypes.Structure):
+    """``ts2d_tiled_image``: one image of ``ts2d_engine_predict_tiled_batch``."""
+    _fields_ = [('image', ctypes.c_void_p), ('Hp', ctypes.c_int32), ('Wp', ctypes.c_int32), ('n_tiles', ctypes.c_int32),
+                ('tile_y', ctypes.c_void_p), ('tile_x', ctypes.c_void_p), ('logits_f16', ctypes.c_void_p), ('seg_u8', ctypes.c_void_p),
+                ('inf_flag', ctypes.c_int32)]
 
 
 class EngineLibraryError(RuntimeError):
@@ -83,6 +90,8 @@ def load():
     lib.ts2d_engine_predict_tiled.restype = c.c_int
     lib.ts2d_engine_predict_tiled.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
                                               c.c_int, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.ts2d_engine_predict_tiled_batch.restype = c.c_int
+    lib.ts2d_engine_predict_tiled_batch.argtypes = [c.c_void_p, c.POINTER(TiledImage), c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p]
     lib.ts2d_project_coronal.restype = c.c_int
     lib.ts2d_project_coronal.argtypes = [c.c_int, c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.c_int, c.c_longlong, c.c_longlong,
                                          c.c_longlong, c.c_longlong, c.c_void_p, c.c_void_p]

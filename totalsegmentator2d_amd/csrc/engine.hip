@@ -191,8 +191,10 @@ struct ts2d_engine {
     uint32_t ws_token = 0;        // ... token this engine's last run wrote into its header (g_ws_generation)
     // the kernel choices of the last (B, H, W, precision, options): a forward of the same shape does not search tile shapes again
     // (62 launches per forward: at B = 1 the host side is a visible part of the 2.5 ms)
-    std::vector<Choice> plan; int planB = 0, planH = 0, planW = 0, plan_prec = -1; unsigned plan_gen = 0, opt_gen = 1;
+    std::vector<Choice> plan; int planB = 0, planH = 0, planW = 0, plan_prec = -1; unsigned plan_gen = 0, opt_gen = 1; bool plan_full = false;
     char* d_stage = nullptr; size_t stage_bytes = 0;      // host-buffer forwards only (ensure_staging)
+    bool ws_full = false;         // the activation plan of the workspace is the full-batch dispatch's (ensure_workspace)
+    bool last_full = false;       // the last run took the full-batch dispatch (ts2d_engine_check re-runs it the same way)
     int ws_precision = -1; bool ws_keep = false;      // the activation plan of the workspace was made for this mode (composition depends on it)
     bool keep_activations = false;                    // ts2d_engine_set_keep_activations: one buffer per tensor (debug access, full diagnosis)
     float* d_part = nullptr;
@@ -994,8 +996,9 @@ int choose_ksplit(const Op& op, const TileGeom& g) {
 // Measured (profiles/r06_small_batch.txt, wall time of a forward, split mode): B = 1 2.51 -> 1.90 ms, B = 2 2.77 -> 2.15, B = 4 3.27 -> 2.82, B = 8 4.32 -> 3.98;
 // filling to TWO workgroups per CU instead of one: equal (the reduction pass of each further split op costs what its conv gains).
 constexpr size_t kSbkElems = (size_t)2 * 256 * 256 * 64;      // S x B x HW x Cout of any op this rule splits (n_wgs S < 2 x 256 CUs, <= 256 pixels x 64 columns each)
-int fill_ksplit(const ts2d_engine* e, long long n_wgs, int nchunks) {
-    if (!e->use_sbk || e->num_cus > 256) return 1;            // (the bound above assumes <= 256 CUs)
+// `full`: the run asks for the full-batch dispatch whatever its size (ts2d_engine_predict_tiled_batch: a row's bits must not depend on its batch)
+int fill_ksplit(const ts2d_engine* e, long long n_wgs, int nchunks, bool full = false) {
+    if (!e->use_sbk || full || e->num_cus > 256) return 1;            // (the bound above assumes <= 256 CUs)
     int S = 1;
     while (S < 8 && n_wgs * S < e->num_cus && nchunks / (S * 2) >= 4) S *= 2;
     return S;
@@ -1025,7 +1028,7 @@ bool fuse0_applies(const ts2d_engine* e, int H, int W) {
 }
 
 // The decoder block `op` (3x3 conv over cat(up, skip)) as ONE kernel together with its transposed conv (kernels_upc.h ...), or K_NONE.
-Kern composed_kernel(const ts2d_engine* e, const Op& op, int B, int H, int W) {
+Kern composed_kernel(const ts2d_engine* e, const Op& op, int B, int H, int W, bool full = false) {
     if (!op.upc_ok || !e->use_upc || !e->use_one || e->precision == TS2D_PRECISION_F32_EXACT || B < 1) return K_NONE;
     const bool f16 = e->precision == TS2D_PRECISION_F16;
     const Op& up = e->ops[op.up_idx];
@@ -1038,7 +1041,7 @@ Kern composed_kernel(const ts2d_engine* e, const Op& op, int B, int H, int W) {
         const TileGeom g1 = tile_geom(B, Ht, Wt, 1, 1, 9);
         const int chunk = f16 ? 32 : 16, bn1 = op.cout % 64 == 0 ? 64 : 32;
         const bool two_ok = up.split_ok && (f16 ? op.h32_ok : op.split_ok) && g1.NIMG == 1 && (size_t)B * Ht * Wt * up.cout <= kSbkElems / 2;
-        if (two_ok && fill_ksplit(e, (long long)g1.n_mtiles * (op.cout / bn1), ct_total(op) / chunk) > 1) return K_NONE;
+        if (two_ok && fill_ksplit(e, (long long)g1.n_mtiles * (op.cout / bn1), ct_total(op) / chunk, full) > 1) return K_NONE;
     }
     if (Ht % 8 || Wt % 32) {                                            // no complete 8 x 32 tiles: tiles that follow the extent (FLEX instances)
         bool ok = false;
@@ -1056,7 +1059,7 @@ Kern composed_kernel(const ts2d_engine* e, const Op& op, int B, int H, int W) {
     return upq ? K_UPQ : K_UPC;           // (Cb = 128: conv3x3_upq no faster than conv3x3_upc, measured)
 }
 
-Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W) {
+Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W, bool full = false) {
     const Op& op = e->ops[oi];
     Choice c;
     const bool f16 = e->precision == TS2D_PRECISION_F16, exact = e->precision == TS2D_PRECISION_F32_EXACT;
@@ -1077,7 +1080,7 @@ Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W) {
     const Tensor& src = e->tensors[op.src];
     const int Hin = H >> src.ly, Win = W >> src.lx;
     if (op.type == OP_CONVT) {
-        if (oi + 1 < e->ops.size() && e->ops[oi + 1].up_idx == (int)oi && composed_kernel(e, e->ops[oi + 1], B, H, W) != K_NONE) {
+        if (oi + 1 < e->ops.size() && e->ops[oi + 1].up_idx == (int)oi && composed_kernel(e, e->ops[oi + 1], B, H, W, full) != K_NONE) {
             c.k = K_FUSED_AWAY;             // composed into the next block: the upsampled tensor is never materialised
             return c;
         }
@@ -1094,7 +1097,7 @@ Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W) {
     }
     const int Ht = H >> op.ly, Wt = W >> op.lx, ct = ct_total(op);
     if (op.up_idx >= 0) {
-        const Kern ck = composed_kernel(e, op, B, H, W);
+        const Kern ck = composed_kernel(e, op, B, H, W, full);
         if (ck != K_NONE) {
             c.k = ck; c.fused_stats = true;
             if (ck == K_UP0 && f16) c.ppt = 4;
@@ -1119,7 +1122,7 @@ Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W) {
         {
             const TileGeom g1 = tile_geom(B, Ht, Wt, 2, 2, 9);
             const int P1 = g1.PH * g1.PW * g1.NIMG;
-            if (e->use_one && g1.NIMG == 1 && P1 <= 5 * kBlock && img32) s2k = fill_ksplit(e, (long long)g1.n_mtiles * (op.cout / c.bn), op.cin / 8);
+            if (e->use_one && g1.NIMG == 1 && P1 <= 5 * kBlock && img32) s2k = fill_ksplit(e, (long long)g1.n_mtiles * (op.cout / c.bn), op.cin / 8, full);
         }
         if (s2k == 1 && op.s2v2_ok && e->use_s2v2 && e->use_one && Ht % 8 == 0 && Wt % 32 == 0 && img32 && magic_ok(tile_fixed(B, Ht, Wt, 8, 32, 2, 2))) {
             // stride-2 block on complete 8 x 32 output tiles: one 512-thread workgroup per CU, up to 128 output columns
@@ -1156,7 +1159,7 @@ Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W) {
     // small batch: split-K on the one-image kernels where they leave most CUs idle (fill_ksplit) - ahead of the 512-thread kernels, which have no split-K form
     if (c.g.NIMG == 1 && img32 && op.cout % c.bn == 0) {
         const bool can = f16 ? (op.h32_ok && e->use_h32 && P * 4 <= 6 * kBlock) : (e->use_one && P * 2 <= 3 * kBlock);
-        const int sk = can ? fill_ksplit(e, (long long)c.g.n_mtiles * (op.cout / c.bn), ct / (f16 ? 32 : 16)) : 1;
+        const int sk = can ? fill_ksplit(e, (long long)c.g.n_mtiles * (op.cout / c.bn), ct / (f16 ? 32 : 16), full) : 1;
         if (sk > 1) {
             c.ksplit = sk; c.fused_stats = false;
             c.k = f16 ? K_S1_H32 : K_S1_ONE;
@@ -1185,21 +1188,22 @@ Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W) {
     return c;
 }
 
-// choose() for every op, cached per (B, H, W, precision, option generation)
-const std::vector<Choice>& planned(ts2d_engine* e, int B, int H, int W) {
-    if (e->plan.size() != e->ops.size() || e->planB != B || e->planH != H || e->planW != W || e->plan_prec != e->precision || e->plan_gen != e->opt_gen) {
+// choose() for every op, cached per (B, H, W, precision, option generation, full-batch dispatch of the run)
+const std::vector<Choice>& planned(ts2d_engine* e, int B, int H, int W, bool full = false) {
+    if (e->plan.size() != e->ops.size() || e->planB != B || e->planH != H || e->planW != W || e->plan_prec != e->precision || e->plan_gen != e->opt_gen ||
+        e->plan_full != full) {
         e->plan.resize(e->ops.size());
-        for (size_t i = 0; i < e->ops.size(); ++i) e->plan[i] = choose(e, i, B, H, W);
-        e->planB = B; e->planH = H; e->planW = W; e->plan_prec = e->precision; e->plan_gen = e->opt_gen;
+        for (size_t i = 0; i < e->ops.size(); ++i) e->plan[i] = choose(e, i, B, H, W, full);
+        e->planB = B; e->planH = H; e->planW = W; e->plan_prec = e->precision; e->plan_gen = e->opt_gen; e->plan_full = full;
     }
     return e->plan;
 }
 
-size_t partial_floats_needed(const ts2d_engine* e, int B, int H, int W) {
+size_t partial_floats_needed(const ts2d_engine* e, int B, int H, int W, bool full) {
     size_t mx = 0;
     for (size_t i = 0; i < e->ops.size(); ++i) {
         const Op& op = e->ops[i];
-        const Choice c = choose(e, i, B, H, W);
+        const Choice c = choose(e, i, B, H, W, full);
         if (c.ksplit > 1) mx = std::max(mx, (size_t)c.ksplit * B * (H >> op.ly) * (W >> op.lx) * op.cout);
     }
     // a workspace sized for B also serves every smaller batch, whose ops may split K further (fill_ksplit): the bound of that rule
@@ -1207,12 +1211,12 @@ size_t partial_floats_needed(const ts2d_engine* e, int B, int H, int W) {
     return mx;
 }
 
-size_t part_floats_needed(const ts2d_engine* e, int B, int H, int W) {
+size_t part_floats_needed(const ts2d_engine* e, int B, int H, int W, bool full) {
     size_t mx = 0;
     for (size_t i = 0; i < e->ops.size(); ++i) {
         const Op& op = e->ops[i];
         if (op.type != OP_CONV) continue;
-        const Choice c = choose(e, i, B, H, W);
+        const Choice c = choose(e, i, B, H, W, full);
         if (c.fused_stats) mx = std::max(mx, (size_t)B * c.g.tiles_x * c.g.tiles_y * c.ppt * op.cout * 4);      // (S, Q, K, n) per (tile, channel)
         if (e->use_sbk) mx = std::max(mx, kSbkElems / 256 * 4);      // small-batch split-K (any smaller batch in this workspace): a partial per 256 pixels and channel
     }
@@ -1227,7 +1231,7 @@ size_t part_floats_needed(const ts2d_engine* e, int B, int H, int W) {
 // keep_activations: no reuse (every tensor keeps its own buffer for ts2d_engine_debug_tensor / the non-finite diagnosis).
 struct ActPlan { std::vector<size_t> off; std::vector<char> used, reused; size_t bytes = 0; };
 
-ActPlan plan_activations(const ts2d_engine* e, int B, int H, int W, bool keep) {
+ActPlan plan_activations(const ts2d_engine* e, int B, int H, int W, bool keep, bool full) {
     const size_t nt = e->tensors.size(), no = e->ops.size();
     ActPlan p; p.off.assign(nt, 0); p.used.assign(nt, 0); p.reused.assign(nt, 0);
     auto bytes_of = [&](size_t t) { const Tensor& x = e->tensors[t]; return align_up((size_t)B * (H >> x.ly) * (W >> x.lx) * x.C * sizeof(float), 256); };
@@ -1238,7 +1242,7 @@ ActPlan plan_activations(const ts2d_engine* e, int B, int H, int W, bool keep) {
     for (size_t i = 0; i < no; ++i) {
         const Op& op = e->ops[i];
         if (fused0 && i == 1) continue;                    // (reads the network input, which is not part of the arena)
-        if (op.type == OP_CONVT && choose(e, i, B, H, W).k == K_FUSED_AWAY) { skipped[i] = 1; continue; }
+        if (op.type == OP_CONVT && choose(e, i, B, H, W, full).k == K_FUSED_AWAY) { skipped[i] = 1; continue; }
         if (op.type == OP_CONV && op.up_idx >= 0 && skipped[op.up_idx]) { reads[i] = {e->ops[op.up_idx].src, op.skip}; continue; }
         if (!(op.first_direct)) reads[i].push_back(op.src);
         if (op.skip >= 0) reads[i].push_back(op.skip);
@@ -1294,9 +1298,9 @@ ActPlan plan_activations(const ts2d_engine* e, int B, int H, int W, bool keep) {
 // Layout of the activation workspace for (B, H, W) under the engine's current precision mode, options and keep flag.
 struct WsLayout { ActPlan plan; std::vector<size_t> o_sc, o_sh; size_t o_part = 0, o_pk = 0, o_up = 0, bytes = 0; };
 
-WsLayout workspace_layout(const ts2d_engine* e, int B, int H, int W) {
+WsLayout workspace_layout(const ts2d_engine* e, int B, int H, int W, bool full = false) {
     WsLayout L;
-    L.plan = plan_activations(e, B, H, W, e->keep_activations);
+    L.plan = plan_activations(e, B, H, W, e->keep_activations, full);
     for (size_t& o : L.plan.off) o += kWsHeader;          // (the header: owner token of a shared workspace)
     size_t off = align_up(kWsHeader + L.plan.bytes, 256);
     L.o_sc.assign(e->tensors.size(), 0); L.o_sh.assign(e->tensors.size(), 0);
@@ -1307,20 +1311,26 @@ WsLayout workspace_layout(const ts2d_engine* e, int B, int H, int W) {
             L.o_sh[i] = off; off = align_up(off + (size_t)B * t.C * sizeof(float), 256);
         }
     }
-    L.o_part = off; off = align_up(off + part_floats_needed(e, B, H, W) * sizeof(float) + 256, 256);
-    L.o_pk = off; off = align_up(off + partial_floats_needed(e, B, H, W) * sizeof(float) + 256, 256);   // split-K partials
+    L.o_part = off; off = align_up(off + part_floats_needed(e, B, H, W, full) * sizeof(float) + 256, 256);
+    L.o_pk = off; off = align_up(off + partial_floats_needed(e, B, H, W, full) * sizeof(float) + 256, 256);   // split-K partials
     // one upsampled tensor of a small batch's two-kernel decoder entry (composed_kernel): the plan above is the reserved batch's, where that entry is composed
     L.o_up = off; if (e->use_sbk) off = align_up(off + kSbkElems / 2 * sizeof(float) + 256, 256);
     L.bytes = off;
     return L;
 }
 
-int ensure_workspace(ts2d_engine* e, int B, int H, int W) {
+// `full`: the run takes the full-batch dispatch whatever its size (ts2d_engine_predict_tiled_batch).  Its activation plan keeps the coarse
+// tensor of every composed decoder entry alive until that entry has run; the plan of a small batch under "sbk" (transposed conv + conv)
+// releases it one op earlier, so a layout made for such a batch cannot serve a full-dispatch run and is re-made here - inside the same
+// memory when it fits (checked below, never assumed).  The reverse holds: a full-dispatch layout serves every "sbk" run of the same or a
+// smaller batch (the upsampled tensor of its two-kernel entries goes to the d_up scratch, as for any batch below the reserved one), so
+// the layout stays and a following predict_tiled / forward finds it unchanged.
+int ensure_workspace(ts2d_engine* e, int B, int H, int W, bool full = false) {
     const bool keep = e->keep_activations;
-    if (e->d_ws && e->wsB >= B && e->wsH == H && e->wsW == W && e->ws_precision == e->precision && e->ws_keep == keep) return TS2D_OK;
+    if (e->d_ws && e->wsB >= B && e->wsH == H && e->wsW == W && e->ws_precision == e->precision && e->ws_keep == keep && (e->ws_full || !full)) return TS2D_OK;
     HIP_TRY(hipSetDevice(e->device));
     if (e->d_ws && e->wsH == H && e->wsW == W && e->wsB > B && !e->ws_external) B = e->wsB;      // same geometry, another mode: keep the larger batch capacity
-    const WsLayout L = workspace_layout(e, B, H, W);
+    const WsLayout L = workspace_layout(e, B, H, W, full);
     if (e->d_ws) {      // the old workspace may still be in use by a run on ANY stream: wait for its end-of-run event
         if (e->ws_busy) { HIP_TRY(hipEventSynchronize(e->ws_event)); e->ws_busy = false; }
         HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1333,7 +1343,7 @@ int ensure_workspace(ts2d_engine* e, int B, int H, int W) {
         if (e->d_ws && e->ws_bytes < L.bytes) { HIP_TRY(hipFree(e->d_ws)); e->d_ws = nullptr; e->ws_bytes = 0; }      // (a mode change that fits re-maps the same memory)
         if (!e->d_ws) { HIP_TRY(hipMalloc(reinterpret_cast<void**>(&e->d_ws), L.bytes)); e->ws_bytes = L.bytes; }
     }
-    e->wsB = B; e->wsH = H; e->wsW = W; e->ws_precision = e->precision; e->ws_keep = keep;
+    e->wsB = B; e->wsH = H; e->wsW = W; e->ws_precision = e->precision; e->ws_keep = keep; e->ws_full = full;
     for (size_t i = 0; i < e->tensors.size(); ++i) {
         Tensor& t = e->tensors[i];
         t.data = L.plan.used[i] ? reinterpret_cast<float*>(e->d_ws + L.plan.off[i]) : nullptr;
@@ -1394,7 +1404,7 @@ int prof_end(ts2d_engine* e, hipStream_t st) {
 
 #define TRY(expr) do { int _rc = (expr); if (_rc != TS2D_OK) return _rc; } while (0)
 
-int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st);
+int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st, bool full);
 
 // Order this run after the previous user of the workspace if that one ran on a different stream.
 int workspace_acquire(ts2d_engine* e, hipStream_t st) {
@@ -1424,7 +1434,8 @@ bool workspace_is_mine(ts2d_engine* e) {
     return tok == e->ws_token;
 }
 
-int run_forward(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st, bool clear_flags = true) {
+int run_forward(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st, bool clear_flags = true,
+                bool full = false) {
     TRY(workspace_acquire(e, st));
     if (e->ws_external) {           // stamp the shared workspace: whatever another engine of the set left in it is gone after this run
         e->ws_token = ++g_ws_generation;
@@ -1432,7 +1443,7 @@ int run_forward(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->d_ws), (int)e->ws_token, 1, st));
     }
     if (clear_flags) HIP_TRY(hipMemsetAsync(e->d_flags, 0, 2 * sizeof(int), st));
-    const int rc = run_forward_impl(e, d_in, B, H, W, d_logits, d_mask, st);
+    const int rc = run_forward_impl(e, d_in, B, H, W, d_logits, d_mask, st, full);
     const int rc2 = workspace_release(e, st);       // also after a failed launch: earlier kernels of the run may be in flight
     return rc != TS2D_OK ? rc : rc2;
 }
@@ -1447,14 +1458,14 @@ inline void set_tiling(ConvArgs& ca, const TileGeom& g, int n_ctiles) {
     ca.PH = g.PH; ca.PW = g.PW;
 }
 
-int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st) {
+int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st, bool full) {
     const ts2d_arch_desc& a = e->arch;
     e->n_launched = 0;
     e->fused_away.assign(e->ops.size(), 0);
     // (the input is scanned by ts2d_engine_check only when it lives in the engine's own staging memory)
     e->last_input = ((e->d_in_stage && d_in == e->d_in_stage) || (e->d_sw && reinterpret_cast<const char*>(d_in) >= e->d_sw &&
                                                reinterpret_cast<const char*>(d_in) < e->d_sw + e->sw_bytes)) ? d_in : nullptr;
-    e->lastB = B; e->lastH = H; e->lastW = W; e->last_stream = st;
+    e->lastB = B; e->lastH = H; e->lastW = W; e->last_stream = st; e->last_full = full;
     const bool f16 = e->precision == TS2D_PRECISION_F16;      // fp16 storage, one fp16 MFMA product, fp32 accumulate/statistics
     e->last_f16 = f16;
     if (f16 && !e->ops[0].first_direct) return fail(TS2D_ERR_INVALID, "fp16 mode needs <= 4 input channels");
@@ -1468,7 +1479,7 @@ int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, flo
         TRY(prof_end(e, st));
     }
     const float* wts = e->d_weights;
-    const std::vector<Choice>& plan = planned(e, B, H, W);
+    const std::vector<Choice>& plan = planned(e, B, H, W, full);
     // a transposed conv that runs on its own although the workspace's plan (made for the reserved batch) composed it away: its output goes to the
     // scratch region (small batches, composed_kernel; one such tensor is alive at a time - it is read by the very next op only)
     for (size_t oi = 0; oi < e->ops.size(); ++oi) {
@@ -1871,7 +1882,7 @@ int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, flo
 // ------------------------------------------------------------------------------------------------- C-ABI
 extern "C" {
 
-int ts2d_abi_version(void) { return 7; }
+int ts2d_abi_version(void) { return 8; }
 
 const char* ts2d_last_error(void) { return g_err.c_str(); }
 
@@ -1973,15 +1984,19 @@ int ts2d_engine_weights_ready(ts2d_engine* e) {
     return TS2D_OK;
 }
 
-int ts2d_engine_reserve(ts2d_engine* e, int B, int H, int W) {
-    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_reserve: null engine");
+static int reserve_checked(ts2d_engine* e, int B, int H, int W, bool full) {
     const int divy = 1 << e->lvl_y[e->arch.n_stages - 1], divx = 1 << e->lvl_x[e->arch.n_stages - 1];
     if (B < 1 || H < divy || W < divx || H % divy || W % divx)
         return fail(TS2D_ERR_INVALID, "shape B=%d H=%d W=%d: H and W must be positive multiples of %d and %d", B, H, W, divy, divx);
     if ((H / divy) * (W / divx) <= 1)   // torch InstanceNorm2d raises "Expected more than 1 spatial element" here too
         return fail(TS2D_ERR_INVALID, "shape %dx%d leaves a single bottleneck pixel: InstanceNorm needs more than 1 spatial element", H, W);
     if ((long long)B * H * W >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "B*H*W = %lld exceeds 2^31 pixels per call", (long long)B * H * W);
-    return ensure_workspace(e, B, H, W);
+    return ensure_workspace(e, B, H, W, full);
+}
+
+int ts2d_engine_reserve(ts2d_engine* e, int B, int H, int W) {
+    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_reserve: null engine");
+    return reserve_checked(e, B, H, W, false);
 }
 
 int ts2d_engine_workspace_bytes(ts2d_engine* e, int B, int H, int W, size_t* n_bytes) {
@@ -2096,6 +2111,160 @@ int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp
     return ts2d_engine_check(e);
 }
 
+// N images through the sliding window as ONE engine batch (include/ts2d_engine.h).  Host side: validate everything, pack the rows
+// (tile x mirror variant) of the images into chunks of at most kSwChunkRows, lay the scratch out, enqueue every host-to-device copy,
+// then per chunk one sw_gather_batch, one full-batch-dispatch forward and (where an image ends in the chunk) one sw_aggregate_batch,
+// then every device-to-host copy, ONE stream synchronise and the result check.
+constexpr int kSwChunkRows = 64;
+
+int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
+                                    const uint16_t* gaussian_f16) {
+    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: null engine");
+    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
+    if (n_images == 0) return TS2D_OK;
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
+    if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: bad patch %dx%d", ph, pw);
+    const int C = e->arch.input_channels, K = e->arch.num_classes;
+    int vflip[4] = {0, 0, 0, 0}, V = 1;
+    if ((mirror_mask & 3) == 3) { vflip[1] = 1; vflip[2] = 2; vflip[3] = 3; V = 4; }
+    else if (mirror_mask & 1) { vflip[1] = 1; V = 2; }
+    else if (mirror_mask & 2) { vflip[1] = 2; V = 2; }
+    const int vflips = vflip[0] | (vflip[1] << 8) | (vflip[2] << 16) | (vflip[3] << 24);
+    long long n_tiles_all = 0;
+    bool any16 = false, anyseg = false;
+    for (int i = 0; i < n_images; ++i) {
+        const ts2d_tiled_image& im = images[i];
+        if (!im.image || !im.tile_y || !im.tile_x) return fail(TS2D_ERR_INVALID, "image %d: null image or tile pointer", i);
+        if (!im.logits_f16 && !im.seg_u8) return fail(TS2D_ERR_INVALID, "image %d: both outputs are null", i);
+        if (im.n_tiles < 1 || im.n_tiles > (1 << 20) || im.Hp < 1 || im.Wp < 1 || ph > im.Hp || pw > im.Wp)
+            return fail(TS2D_ERR_INVALID, "image %d: bad tiling: %d tiles of %dx%d on %dx%d", i, im.n_tiles, ph, pw, im.Hp, im.Wp);
+        if ((long long)K * im.Hp * im.Wp >= (1LL << 31) || (long long)C * im.Hp * im.Wp >= (1LL << 31))
+            return fail(TS2D_ERR_INVALID, "image %d: %dx%d exceeds 2^31 elements per image", i, im.Hp, im.Wp);
+        for (int t = 0; t < im.n_tiles; ++t)
+            if (im.tile_y[t] < 0 || im.tile_x[t] < 0 || im.tile_y[t] + ph > im.Hp || im.tile_x[t] + pw > im.Wp)
+                return fail(TS2D_ERR_INVALID, "image %d: tile %d at (%d,%d) leaves the %dx%d image", i, t, im.tile_y[t], im.tile_x[t], im.Hp, im.Wp);
+        n_tiles_all += im.n_tiles;
+        any16 |= im.logits_f16 != nullptr; anyseg |= im.seg_u8 != nullptr;
+    }
+    if (n_tiles_all * V >= (1LL << 28)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %lld network rows in one call", n_tiles_all * V);
+    // ---- row packing: whole images, greedily, into chunks of at most kSwChunkRows rows; a larger image takes chunks of its own
+    struct Chunk { int seg0, n_segs, rows, log_row; bool aggregate; unsigned gblocks, ablocks; };
+    std::vector<SwSeg> segs;
+    std::vector<Chunk> chunks;
+    std::vector<size_t> o_img(n_images);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+    const int pwq = (pw + 3) / 4;
+    auto blocks_of = [](long long lanes) { return (lanes + 255) / 256; };
+    long long out_elems = 0, img_floats = 0;
+    int tile0 = 0, cap_rows = 0;
+    long long log_rows = 0;
+    Chunk cur{0, 0, 0, 0, true, 0, 0};
+    auto flush = [&]() { if (cur.n_segs) chunks.push_back(cur); cur = Chunk{(int)segs.size(), 0, 0, 0, true, 0, 0}; };
+    for (int i = 0; i < n_images; ++i) {
+        const ts2d_tiled_image& im = images[i];
+        const int rows = im.n_tiles * V;
+        SwSeg sg{};
+        sg.img_off = img_floats; sg.out_off = out_elems; sg.Hp = im.Hp; sg.Wp = im.Wp; sg.tile0 = tile0; sg.n_tiles = im.n_tiles; sg.image = i;
+        const long long ablocks = blocks_of((long long)K * im.Hp * ((im.Wp + 3) / 4));
+        if (rows > kSwChunkRows) {
+            flush();
+            for (int r0 = 0; r0 < rows; r0 += kSwChunkRows) {
+                const int nb = std::min(kSwChunkRows, rows - r0);
+                sg.row0 = r0; sg.n_rows = nb; sg.batch_row = 0; sg.log_row = 0; sg.gblock0 = 0; sg.ablock0 = 0;
+                segs.push_back(sg);
+                cur.n_segs = 1; cur.rows = nb; cur.log_row = r0; cur.aggregate = r0 + nb == rows;
+                cur.gblocks = (unsigned)blocks_of((long long)nb * C * ph * pwq); cur.ablocks = (unsigned)ablocks;
+                flush();
+            }
+        } else {
+            if (cur.rows + rows > kSwChunkRows) flush();
+            sg.row0 = 0; sg.n_rows = rows; sg.batch_row = cur.rows; sg.log_row = cur.rows; sg.gblock0 = cur.gblocks; sg.ablock0 = cur.ablocks;
+            segs.push_back(sg);
+            cur.n_segs++; cur.rows += rows;
+            cur.gblocks += (unsigned)blocks_of((long long)rows * C * ph * pwq); cur.ablocks += (unsigned)ablocks;
+        }
+        cap_rows = std::max(cap_rows, std::min(rows, kSwChunkRows)); log_rows = std::max<long long>(log_rows, rows);
+        tile0 += im.n_tiles;
+        img_floats += (long long)align_up((size_t)C * im.Hp * im.Wp, 64);
+        out_elems += (long long)align_up((size_t)K * im.Hp * im.Wp, 256);
+    }
+    flush();
+    for (const Chunk& c : chunks) {
+        cap_rows = std::max(cap_rows, c.rows);
+        if ((long long)c.gblocks >= (1LL << 31) || (long long)c.ablocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: a chunk exceeds 2^31 blocks");
+    }
+    log_rows = std::max<long long>(log_rows, cap_rows);
+    TRY(reserve_checked(e, cap_rows, ph, pw, true));
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    // ---- the descriptor table and every tile origin: one host blob, one copy
+    const size_t tab_segs = segs.size() * sizeof(SwSeg), tab_bytes = tab_segs + 2 * (size_t)n_tiles_all * 4;
+    std::vector<char> tab(tab_bytes);
+    memcpy(tab.data(), segs.data(), tab_segs);
+    {
+        int32_t* ty = reinterpret_cast<int32_t*>(tab.data() + tab_segs); int32_t* tx = ty + n_tiles_all;
+        for (int i = 0; i < n_images; ++i) {
+            memcpy(ty, images[i].tile_y, (size_t)images[i].n_tiles * 4); memcpy(tx, images[i].tile_x, (size_t)images[i].n_tiles * 4);
+            ty += images[i].n_tiles; tx += images[i].n_tiles;
+        }
+    }
+    // ---- scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs | uint8 outputs | flags]
+    const size_t o_tab = take(tab_bytes), o_g = take((size_t)ph * pw * 2), o_imgs = take((size_t)img_floats * 4);
+    const size_t o_batch = take((size_t)cap_rows * C * ph * pw * 4), o_log = take((size_t)log_rows * K * ph * pw * 4);
+    const size_t o_o16 = take(any16 ? (size_t)out_elems * 2 : 0), o_seg = take(anyseg ? (size_t)out_elems : 0), o_flag = take((size_t)n_images * 4);
+    if (off > e->sw_bytes) {                                  // grown before the first launch only
+        HIP_TRY(hipStreamSynchronize(st));
+        if (e->d_sw) { HIP_TRY(hipFree(e->d_sw)); e->d_sw = nullptr; e->sw_bytes = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&e->d_sw), off));
+        e->sw_bytes = off;
+    }
+    char* b = e->d_sw;
+    const SwSeg* d_segs = reinterpret_cast<const SwSeg*>(b + o_tab);
+    const int* d_ty = reinterpret_cast<const int*>(b + o_tab + tab_segs); const int* d_tx = d_ty + n_tiles_all;
+    __half* d_g = reinterpret_cast<__half*>(b + o_g); float* d_imgs = reinterpret_cast<float*>(b + o_imgs);
+    float* d_batch = reinterpret_cast<float*>(b + o_batch); float* d_log = reinterpret_cast<float*>(b + o_log);
+    __half* d_o16 = any16 ? reinterpret_cast<__half*>(b + o_o16) : nullptr; uint8_t* d_seg = anyseg ? reinterpret_cast<uint8_t*>(b + o_seg) : nullptr;
+    int* d_flag = reinterpret_cast<int*>(b + o_flag);
+    for (int i = 0; i < n_images; ++i) images[i].inf_flag = 0;
+    HIP_TRY(hipMemcpyAsync(b + o_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
+    if (gaussian_f16) HIP_TRY(hipMemcpyAsync(d_g, gaussian_f16, (size_t)ph * pw * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)n_images * 4, st));
+    {
+        long long io = 0;
+        for (int i = 0; i < n_images; ++i) {
+            const size_t nf = (size_t)C * images[i].Hp * images[i].Wp;
+            HIP_TRY(hipMemcpyAsync(d_imgs + io, images[i].image, nf * 4, hipMemcpyHostToDevice, st));
+            io += (long long)align_up(nf, 64);
+        }
+    }
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        const Chunk& c = chunks[ci];
+        hipLaunchKernelGGL(sw_gather_batch, dim3(c.gblocks), dim3(256), 0, st, d_imgs, d_segs + c.seg0, c.n_segs, C, ph, pw, V, vflips, d_ty, d_tx, d_batch);
+        HIP_TRY(hipGetLastError());
+        TRY(run_forward(e, d_batch, c.rows, ph, pw, d_log + (size_t)c.log_row * K * ph * pw, nullptr, st, ci == 0, true));
+        if (!c.aggregate) continue;
+        hipLaunchKernelGGL(sw_aggregate_batch, dim3(c.ablocks), dim3(256), 0, st, d_log, d_segs + c.seg0, c.n_segs, K, ph, pw, V, vflips, d_ty, d_tx,
+                           gaussian_f16 ? d_g : nullptr, d_o16, d_seg, kSigmoidHalfThreshold, d_flag, e->tile_half);
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<int> flags(n_images, 0);
+    HIP_TRY(hipMemcpyAsync(flags.data(), d_flag, (size_t)n_images * 4, hipMemcpyDeviceToHost, st));
+    {
+        long long oo = 0;
+        for (int i = 0; i < n_images; ++i) {
+            const size_t ne = (size_t)K * images[i].Hp * images[i].Wp;
+            if (images[i].logits_f16) HIP_TRY(hipMemcpyAsync(images[i].logits_f16, d_o16 + oo, ne * 2, hipMemcpyDeviceToHost, st));
+            if (images[i].seg_u8) HIP_TRY(hipMemcpyAsync(images[i].seg_u8, d_seg + oo, ne, hipMemcpyDeviceToHost, st));
+            oo += (long long)align_up(ne, 256);
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    e->tiled_inf = 0;
+    for (int i = 0; i < n_images; ++i) { images[i].inf_flag = flags[i] != 0; e->tiled_inf |= flags[i] != 0; }
+    return ts2d_engine_check(e);
+}
+
 int ts2d_engine_check(ts2d_engine* e) {
     if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_check: null engine");
     if (!e->lastB) return TS2D_OK;
@@ -2139,7 +2308,7 @@ int ts2d_engine_check(ts2d_engine* e) {
             e->use_fuse0 = false; ++e->opt_gen;      // (the first block as its own kernel: its output can be scanned and named)
             hipStream_t st = e->last_stream ? e->last_stream : e->stream;
             const bool prof = e->profiling; e->profiling = false;
-            if (ensure_workspace(e, B, H, W) != TS2D_OK || run_forward(e, d_copy, B, H, W, nullptr, nullptr, st, false) != TS2D_OK ||
+            if (ensure_workspace(e, B, H, W, e->last_full) != TS2D_OK || run_forward(e, d_copy, B, H, W, nullptr, nullptr, st, false, e->last_full) != TS2D_OK ||
                 hipStreamSynchronize(st) != hipSuccess) { /* keep the generic message */ }
             e->profiling = prof;
             e->use_fuse0 = was_fuse0; ++e->opt_gen;

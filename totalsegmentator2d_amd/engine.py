@@ -238,6 +238,52 @@ class Engine:
         self.last_tiled_inf = bool(self.lib.ts2d_engine_tiled_inf_flag(self._h))     # upstream's inf check, done on the device
         return out16, seg
 
+    def predict_tiled_batch(self, images, patch, tiles, mirror_axes=None, gaussian: Optional[np.ndarray] = None,
+                            want_logits: bool = True, want_seg: bool = False):
+        """Device-side sliding window for N padded 2-D images as ONE engine batch (C-ABI ts2d_engine_predict_tiled_batch).
+        images: list of [C,Hp,Wp] arrays (extents may differ); tiles: one [(y, x), ...] list per image, upstream order.  Patch, mirror
+        axes and gaussian are shared.  Returns (list of float16 [K,Hp,Wp] or None, list of uint8 [K,Hp,Wp] or None).
+        The network takes the full-batch dispatch whatever the batch: an image's bytes do not depend on its batch-mates, its position
+        or the batch size, and equal :meth:`predict_tiled` on an engine with ``options={'sbk': 0}`` bit for bit.
+        Sets ``last_tiled_inf`` (the OR over the images) and ``last_tiled_inf_per_image``."""
+        if len(images) != len(tiles):
+            raise RuntimeError(f"{len(images)} images but {len(tiles)} tile lists")
+        if not (want_logits or want_seg):
+            raise RuntimeError("predict_tiled_batch: neither logits nor segmentation requested")
+        K = self.arch.num_classes
+        keep = []                    # every array the descriptors point into stays alive until the call returns
+        desc = (_lib.TiledImage * max(len(images), 1))()
+        out16, seg = [], []
+        for i, (image, tl) in enumerate(zip(images, tiles)):
+            image = np.ascontiguousarray(image, dtype=np.float32)
+            if image.ndim != 3:
+                raise RuntimeError(f"image {i}: expected [C,Hp,Wp], found shape {image.shape}")
+            C, Hp, Wp = image.shape
+            if C != self.arch.input_channels:
+                raise RuntimeError(f"image {i}: input has {C} channels, the model expects {self.arch.input_channels}")
+            ty = np.ascontiguousarray([t[0] for t in tl], dtype=np.int32)
+            tx = np.ascontiguousarray([t[1] for t in tl], dtype=np.int32)
+            o16 = np.empty((K, Hp, Wp), dtype=np.float16) if want_logits else None
+            sg = np.empty((K, Hp, Wp), dtype=np.uint8) if want_seg else None
+            keep += [image, ty, tx]
+            out16.append(o16)
+            seg.append(sg)
+            d = desc[i]
+            d.image, d.Hp, d.Wp, d.n_tiles = image.ctypes.data, Hp, Wp, len(tl)
+            d.tile_y, d.tile_x = ty.ctypes.data, tx.ctypes.data
+            d.logits_f16 = None if o16 is None else o16.ctypes.data
+            d.seg_u8 = None if sg is None else sg.ctypes.data
+        mask = 0
+        for a in (mirror_axes or ()):
+            mask |= 1 << int(a)
+        g = None if gaussian is None else np.ascontiguousarray(gaussian, dtype=np.float16)
+        _lib.check(self.lib.ts2d_engine_predict_tiled_batch(self._h, desc, len(images), int(patch[0]), int(patch[1]), mask,
+                                                            None if g is None else g.ctypes.data), 'ts2d_engine_predict_tiled_batch')
+        self.last_tiled_inf_per_image = [bool(desc[i].inf_flag) for i in range(len(images))]
+        self.last_tiled_inf = any(self.last_tiled_inf_per_image)
+        del keep
+        return (out16 if want_logits else None), (seg if want_seg else None)
+
     def _check_shape(self, C, W, mask):
         if C != self.arch.input_channels:
             raise RuntimeError(f"input has {C} channels, the model expects {self.arch.input_channels}")

@@ -43,7 +43,7 @@ def _enumerate_cases(src: str):
 
 
 def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fetch_remote: bool = True, collapse: bool = False,
-             visualize: bool = True, save_all: bool = False, silent: bool = False, models=None):
+             visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1):
     model = DEFAULT_MODEL if model is None else model
     content = 'all' if visualize else 'file'
     which = 'all' if save_all else 'final'
@@ -52,6 +52,15 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
     with TS2D(key=model, use_remote=use_remote, fetch_remote=fetch_remote, models=models) as ts:
         cases = list(_enumerate_cases(src))
         log(f"Predicting {len(cases)} case{'s' if len(cases) != 1 else ''}")
+        if batch_cases > 1:
+            # groups of `batch_cases` cases share one engine batch per sub-model (TS2D.predict_many); same files, same log lines per case
+            for g0 in range(0, len(cases), batch_cases):
+                group = cases[g0:g0 + batch_cases]
+                for i, (name, _) in enumerate(group):
+                    log(f"[{g0 + i + 1}/{len(cases)}] Processing: {name}")
+                for (name, _), res in zip(group, ts.predict_many([path for _, path in group], collapse=collapse, max_cases=batch_cases)):
+                    res.save(dest=dest, name=name, models=which, content=content, targets=['segmentation', 'projection'])
+            return
         for i, (name, path) in enumerate(cases):
             log(f"[{i + 1}/{len(cases)}] Processing: {name}")
             res = ts.predict(path, collapse=collapse)
@@ -70,9 +79,13 @@ def ts2d_entry_point(argv=None):
     p.add_argument("--visualize", action="store_true", help="Visualize the results as PNG images (not implemented).")
     p.add_argument("--save-all", action="store_true", help="Also save results for each individual model.")
     p.add_argument("--silent", action="store_true", help="Hides any unnecessary output.")
+    p.add_argument("--batch-cases", type=int, default=1, help="Cases of a directory that share one engine batch per sub-model (1: one case at a time). "
+                   "A case's result does not depend on the other cases of its batch.")
     a = p.parse_args(argv)
+    if a.batch_cases < 1:
+        p.error("--batch-cases must be at least 1")
     ts2d_run(src=a.src, dest=a.dest, model=a.model, use_remote=not a.no_remote, fetch_remote=not a.no_fetch, collapse=a.collapse,
-             visualize=a.visualize, save_all=a.save_all, silent=a.silent)
+             visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases)
 
 
 if __name__ == '__main__':

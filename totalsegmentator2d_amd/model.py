@@ -145,6 +145,30 @@ class HIPModel:
                      (getattr(pm, 'plans', None) or {}).get('foreground_intensity_properties_per_channel', {}),
                      None if dz is None else tuple(dz.get('order', ()))))
 
+    def _preprocess_input(self, img):
+        """Stage 1 of :meth:`_apply_one` / :meth:`apply_batch`: read, to array, preprocess (the case's shared ``preprocess_cache`` is honoured).
+        Returns (reference image, preprocessed data, properties)."""
+        p = self._predictor
+        ref = nrrd.read(img) if isinstance(img, str) else img
+        from .preprocess import image_to_array
+        data, props = image_to_array(ref)
+        if getattr(ref, 'device_zscore', None) is not None:
+            props['device_zscore'] = ref.device_zscore      # z-score done on the device behind the projection (image.py)
+        pre = p.configuration_manager.preprocessor_class(verbose=p.verbose)
+        shared = getattr(ref, 'preprocess_cache', None)      # set by TS2D.predict: the sub-models of one case mostly share channels and plan
+        if shared is None:
+            data, _, props = pre.run_case_npy(data, None, props, p.plans_manager, p.configuration_manager, p.dataset_json)
+        else:
+            key = self._preprocess_key(p, props)
+            with shared['lock']:                             # (the first sub-model computes, its siblings wait for the result instead of repeating it)
+                hit = shared['items'].get(key)
+                if hit is None:
+                    d2, _, p2 = pre.run_case_npy(data, None, props, p.plans_manager, p.configuration_manager, p.dataset_json)
+                    d2.setflags(write=False)
+                    hit = shared['items'][key] = (d2, p2)
+            data, props = hit[0], dict(hit[1])
+        return ref, data, props
+
     def _apply_one(self, name, img, result_dir, override):
         """The reference worker's four stages (``prediction_worker.py:177-242``), each failing under its own name -
         ``"<Stage> failed for <name>: <cause>"`` - so that a HIP error (``ts2d_last_error``) tells which stage raised it."""
@@ -160,24 +184,7 @@ class HIPModel:
         except Exception as ex:
             raise RuntimeError(f"Could not create output directory: {ex}") from ex
         try:
-            ref = nrrd.read(img) if isinstance(img, str) else img
-            from .preprocess import image_to_array
-            data, props = image_to_array(ref)
-            if getattr(ref, 'device_zscore', None) is not None:
-                props['device_zscore'] = ref.device_zscore      # z-score done on the device behind the projection (image.py)
-            pre = p.configuration_manager.preprocessor_class(verbose=p.verbose)
-            shared = getattr(ref, 'preprocess_cache', None)      # set by TS2D.predict: the sub-models of one case mostly share channels and plan
-            if shared is None:
-                data, _, props = pre.run_case_npy(data, None, props, p.plans_manager, p.configuration_manager, p.dataset_json)
-            else:
-                key = self._preprocess_key(p, props)
-                with shared['lock']:                             # (the first sub-model computes, its siblings wait for the result instead of repeating it)
-                    hit = shared['items'].get(key)
-                    if hit is None:
-                        d2, _, p2 = pre.run_case_npy(data, None, props, p.plans_manager, p.configuration_manager, p.dataset_json)
-                        d2.setflags(write=False)
-                        hit = shared['items'][key] = (d2, p2)
-                data, props = hit[0], dict(hit[1])
+            ref, data, props = self._preprocess_input(img)
             ts['preprocessed'] = time.time()
         except Exception as ex:
             raise RuntimeError(f"Preprocessing failed for {name}: {ex}") from ex
@@ -205,3 +212,79 @@ class HIPModel:
         except Exception as ex:
             raise RuntimeError(f"Export failed for {name}: {ex}") from ex
         return (ofile + '.nrrd') if result_dir is not None else seg
+
+    # ------------------------------------------------------------------ apply_batch: N inputs, one predictor batch call
+    def _wants_device_threshold(self, data, props) -> bool:
+        """The fast-path decision of :meth:`_apply_one`: a multilabel case whose export needs no logits gets its segmentation from the device."""
+        p = self._predictor
+        if not (self.device_threshold and bool(p.dataset_json.get('multilabel', p.dataset_json.get('multiclass', False)))
+                and hasattr(p, 'predict_segmentation_from_preprocessed_data_batch')):
+            return False
+        from .export import needs_logits
+        return not needs_logits(props, np.asarray(data).shape[1:])
+
+    def apply_batch(self, inputs: Union[List, Dict], result_dir: Optional[str] = None, override: bool = True) -> dict:
+        """:meth:`apply` for several inputs with ONE engine batch (the reference's ``apply`` submits every input to its worker pool before
+        it waits, ``ts2d/core/inference/nnu.py:194-216``).  Stage 1 preprocesses every input, stage 2 is one predictor batch call over
+        the inputs that share the fast-path decision (device-thresholded segmentation / logits: at most two calls), stage 3 exports
+        each.  Inside the batched engine call the network always takes the full-batch dispatch, so an input's result does not depend
+        on the other inputs of the call.  Errors: ``"<Stage> failed for <name>: <cause>"``.  ``batch_timestamps[name]`` holds
+        ``start / preprocessed / predicted / exported / done`` per input (the inputs of one batch share ``predicted``);
+        ``timestamps`` is left at the last input's values.  ``override=False`` skips existing outputs before any device work."""
+        if self._predictor is None:
+            raise RuntimeError("model is not started")
+        if isinstance(inputs, (list, tuple)):
+            inputs = {f'image{i + 1}': img for i, img in enumerate(inputs)}
+        p = self._predictor
+        results: dict = {}
+        self.batch_timestamps = {}
+        todo = []
+        for name, img in inputs.items():
+            ts = self.batch_timestamps[name] = {'start': time.time()}
+            ofile = None
+            try:
+                if result_dir is not None:
+                    os.makedirs(result_dir, exist_ok=True)
+                    ofile = os.path.join(result_dir, name)
+                    if not override and os.path.exists(ofile + '.nrrd'):
+                        results[name] = ofile + '.nrrd'
+                        continue
+            except Exception as ex:
+                raise RuntimeError(f"Could not create output directory: {ex}") from ex
+            try:
+                ref, data, props = self._preprocess_input(img)
+                ts['preprocessed'] = time.time()
+            except Exception as ex:
+                raise RuntimeError(f"Preprocessing failed for {name}: {ex}") from ex
+            todo.append([name, ofile, ref, data, props, None])
+        fast = [t for t in todo if self._wants_device_threshold(t[3], t[4])]
+        for group, use_seg in ((fast, True), ([t for t in todo if not any(t is f for f in fast)], False)):
+            if not group:
+                continue
+            try:
+                out = p.predict_segmentation_from_preprocessed_data_batch([t[3] for t in group]) if use_seg else None
+                if out is None:
+                    out = p.predict_logits_from_preprocessed_data_batch([t[3] for t in group])
+                    out = [o.cpu().numpy() if hasattr(o, 'cpu') else o for o in out]
+            except Exception as ex:
+                names = ', '.join(t[0] for t in group)
+                m = re.match(r'input (\d+): ', str(ex))          # the predictor names the offending input of the batch by index
+                if m and int(m.group(1)) < len(group):
+                    names = group[int(m.group(1))][0]
+                raise RuntimeError(f"Prediction failed for {names}: {ex}") from ex
+            now = time.time()
+            for t, o in zip(group, out):
+                t[5] = o
+                self.batch_timestamps[t[0]]['predicted'] = now
+        for name, ofile, ref, data, props, logits in todo:
+            ts = self.batch_timestamps[name]
+            try:
+                seg = export_prediction_from_logits(logits, props, p.configuration_manager, p.plans_manager, p.dataset_json, ofile,
+                                                    ref_image=ref, labels=self.labels,
+                                                    colors=self.colors if isinstance(self.colors, dict) else None)
+                ts['exported'] = ts['done'] = time.time()
+            except Exception as ex:
+                raise RuntimeError(f"Export failed for {name}: {ex}") from ex
+            results[name] = (ofile + '.nrrd') if result_dir is not None else seg
+            self.timestamps = ts
+        return {name: results[name] for name in inputs}

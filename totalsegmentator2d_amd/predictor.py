@@ -225,3 +225,75 @@ class HIPnnUNetPredictor:
             return torch.from_numpy(np.ascontiguousarray(pred))
         except ImportError:
             return pred
+
+    # ------------------------------------------------------------------ batched inference (N cases, one engine batch per fold)
+    _INF_MESSAGE = ('Encountered inf in predicted array. Aborting... If this problem persists, reduce '
+                    'value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32')
+
+    def _sliding_window_batch(self, list_of_data, fold: int = 0, want_seg: bool = False):
+        """One fold, N inputs, ONE engine call (C-ABI ts2d_engine_predict_tiled_batch): every z slice of every [C,Z,H,W] input is one
+        image of the batch, padded and tiled with the helpers :meth:`predict_sliding_window_return_logits` uses.  Returns one array per
+        input in the input's geometry: float16 [K,Z,H,W] logits, or the device-thresholded uint8 segmentation when ``want_seg``.
+        Inside the call the network always takes the full-batch dispatch: an input's bytes do not depend on its batch-mates.
+        (The one method that touches the engine on the batched path: the CPU tests override it with a loop over the host restatement.)"""
+        patch = tuple(self.configuration_manager.patch_size)
+        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
+            raise AssertionError('mirror_axes does not match the dimension of the input!')
+        images, tiles, owner, reverts, shapes = [], [], [], [], []
+        for i, data in enumerate(list_of_data):
+            data = np.asarray(data, dtype=np.float32)
+            if data.ndim != 4:
+                raise AssertionError('input_image must be a 4D np.ndarray or torch.Tensor (c, x, y, z)')
+            padded, revert = sw.pad_nd_image(data, patch)
+            C, Z, H, W = padded.shape
+            slicers = sw.tile_slicers((H, W), patch, self.tile_step_size, Z)
+            for d in range(Z):
+                images.append(padded[:, d])
+                tiles.append([(sx, sy) for (dd, sx, sy) in slicers if dd == d])
+                owner.append(i)
+            reverts.append(revert)
+            shapes.append((Z, H, W))
+        g = sw.compute_gaussian(patch) if self.use_gaussian else None
+        axes = self.allowed_mirroring_axes if self.use_mirroring else None
+        e = self.engines[fold]
+        out16, seg = e.predict_tiled_batch(images, patch, tiles, axes, g, want_logits=not want_seg, want_seg=want_seg)
+        planes = seg if want_seg else out16
+        bad = sorted({owner[j] for j, f in enumerate(e.last_tiled_inf_per_image) if f})
+        if bad:
+            raise RuntimeError(f'input {bad[0]}: ' + self._INF_MESSAGE)
+        results, j = [], 0
+        for (Z, H, W), revert in zip(shapes, reverts):
+            full = np.stack(planes[j:j + Z], axis=1) if Z != 1 else planes[j][:, None]
+            j += Z
+            results.append(full[(slice(None),) + revert[1:]])
+        return results
+
+    def predict_logits_from_preprocessed_data_batch(self, list_of_data):
+        """:meth:`predict_logits_from_preprocessed_data` for a list of inputs: one batched engine call per fold (a [C,Z,H,W] input
+        contributes Z images - a z-stack is one engine call, not Z), folds averaged as there.  Returns a list (torch CPU tensors when
+        torch is importable)."""
+        datas = [d.detach().cpu().numpy() if hasattr(d, 'detach') else d for d in list_of_data]
+        if not datas:
+            return []
+        n = max(1, len(self.list_of_parameters))
+        preds = None
+        for f in range(n):
+            ps = self._sliding_window_batch(datas, f)
+            preds = ps if preds is None else [a + b for a, b in zip(preds, ps)]
+        if n > 1:
+            preds = [p / np.float16(n) for p in preds]
+        try:
+            import torch
+            return [torch.from_numpy(np.ascontiguousarray(p)) for p in preds]
+        except ImportError:
+            return preds
+
+    def predict_segmentation_from_preprocessed_data_batch(self, list_of_data):
+        """:meth:`predict_segmentation_from_preprocessed_data` for a list of inputs: uint8 [K,1,H,W] per input from ONE engine call,
+        or None when the predictor needs the logits (a fold ensemble) or an input is no single z slice."""
+        datas = [np.asarray(d.detach().cpu().numpy() if hasattr(d, 'detach') else d, dtype=np.float32) for d in list_of_data]
+        if len(self.list_of_parameters) != 1 or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
+            return None
+        if not datas:
+            return []
+        return self._sliding_window_batch(datas, 0, want_seg=True)

@@ -123,6 +123,79 @@ class TS2D:
             result['projections'] = cache['projections']
         return TS2D.Result(result)
 
+    def predict_many(self, inputs, collapse: bool = False, merge: bool = True, max_cases: int = 8) -> List["TS2D.Result"]:
+        """:meth:`predict` for several cases: per sub-model ONE engine batch over groups of at most ``max_cases`` cases
+        (``HIPModel.apply_batch``) instead of one small batch per case; the sub-models run concurrently on their own threads and streams as
+        in :meth:`predict`.  Inside a batched engine call the network always takes the full-batch dispatch, so a case's result does not
+        depend on which other cases travel with it, on their order or on ``max_cases``; against :meth:`predict` (small-batch dispatch)
+        it agrees to fp32 summation order (a few float16 ulps at most on the aggregated logits: each rounding into the half buffer may flip).
+        ``max_cases=8`` makes 64 network rows for the default case of 2 tiles x 4 mirror passes.  Host memory: every case of a group holds
+        its K result planes of Hp x Wp bytes per sub-model until the group is exported (float16 planes where an export resamples)."""
+        images = []
+        for inp in inputs:
+            if isinstance(inp, str):
+                inp = nrrd.read(inp)
+            if not isinstance(inp, nrrd.Image):
+                raise RuntimeError(f"input must be a string path or an image, found: {type(inp).__name__}")
+            images.append(inp)
+        max_cases = max(1, int(max_cases))
+        order = sorted(self.models)
+        caches = [dict() for _ in images]
+        prepared = [{mid: self._prepare_model_input(mid, img, cache) for mid in order} for img, cache in zip(images, caches)]
+
+        def run_model(mid):
+            out = []
+            for g0 in range(0, len(images), max_cases):
+                out += self._apply_model_batch(mid, [pr[mid] for pr in prepared[g0:g0 + max_cases]], collapse, first=g0)
+            return out
+        if self.concurrent_models and len(order) > 1 and images:
+            pool = self._executor(len(order))
+            futs = {mid: pool.submit(run_model, mid) for mid in order}
+            done, failure = {}, None
+            for mid in order:                                            # every running sub-model is waited for before a failure is re-raised
+                try:
+                    done[mid] = futs[mid].result()
+                except BaseException as ex:
+                    if failure is None:
+                        failure = ex
+                        for f in futs.values():
+                            f.cancel()
+            if failure is not None:
+                raise failure
+        else:
+            done = {mid: run_model(mid) for mid in order}
+        results = []
+        for i, (img, cache) in enumerate(zip(images, caches)):
+            result: dict = {}
+            for mid in order:
+                result.setdefault('models', {})[mid] = done[mid][i]
+            if merge:
+                segs = [r['segmentation'] for _, r in sorted(result['models'].items())]
+                result['segmentation'] = segs[0] if len(segs) == 1 else combine_segmentations(segs)
+            result['input'] = img
+            if cache.get('projections'):
+                result['projections'] = cache['projections']
+            results.append(TS2D.Result(result))
+        return results
+
+    def _apply_model_batch(self, mid: str, prepared: list, collapse: bool, first: int = 0) -> List[dict]:
+        """:meth:`_apply_model` for a group of cases: one ``model.apply_batch`` + restoring each case's 3-D geometry."""
+        model = self.models[mid]
+        names = [f'case{first + i + 1}' for i in range(len(prepared))]
+        segs = model.apply_batch({n: pr[1] for n, pr in zip(names, prepared)})
+        out = []
+        for n, (input, input2d, native_2d) in zip(names, prepared):
+            res = {'id': mid, 'revision': model.revision}
+            res['model'], res['group'] = decompose_model_key(mid)
+            seg = segs[n]
+            if not (collapse or native_2d):
+                seg = restore_dimension(seg, input)
+            res['input'] = input2d if collapse else input
+            res['segmentation'] = seg
+            res['timestamps'] = dict(model.batch_timestamps[n])
+            out.append(res)
+        return out
+
     def _predict_model(self, mid: str, input: nrrd.Image, collapse: bool, cache: dict) -> dict:
         return self._apply_model(mid, self._prepare_model_input(mid, input, cache), collapse)
 
