@@ -148,7 +148,9 @@ int ts2d_engine_check(ts2d_engine* e);
  *   logits_f16     host [K, Hp, Wp] half bits: aggregated logits / n_predictions in upstream's float16 buffers (rounding
  *                  order: ts2d_engine_set_tile_dtype; equal bit for bit to the repo's ATen-pinned oracle); may be NULL
  *   seg_u8         host [K, Hp, Wp]: sigmoid(float(logit)) > 0.5 of the aggregated logits (multilabel export); may be NULL
- * All tiles x mirror variants go through the network as one batch (chunks of at most 64 rows).  Synchronous. */
+ * All tiles x mirror variants go through the network as one batch (chunks of at most 64 rows).  Synchronous.
+ * This is ts2d_engine_predict_tiled_batch with one image - the same host code and kernels - except for the dispatch of the network:
+ * here it depends on the batch size (option "sbk"), there it never does (the determinism rule below). */
 int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp, int patch_h, int patch_w, int n_tiles,
                               const int32_t* tile_y, const int32_t* tile_x, int mirror_mask, const uint16_t* gaussian_f16,
                               uint16_t* logits_f16, uint8_t* seg_u8);

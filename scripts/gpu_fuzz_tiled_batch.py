@@ -1,5 +1,7 @@
-"""Randomised check of the batched sliding window (ts2d_engine_predict_tiled_batch: segment table, row packing, sw_gather_batch,
-sw_aggregate_batch, per-image inf flag) against ts2d_engine_predict_tiled on an engine with 'sbk': 0, image by image, bit for bit.  Each case
+"""Randomised check of the packing and the dispatch of the batched sliding window (ts2d_engine_predict_tiled_batch: segment table with
+several images per launch, row packing into chunks, per-image inf flag, full-batch dispatch) against ts2d_engine_predict_tiled on an engine
+with 'sbk': 0, image by image, bit for bit.  Both entries run the same kernel pair and host code (a single image is a batch of one), so this
+does not check the aggregation arithmetic - scripts/gpu_fuzz_sliding_window.py does, against the host restatement.  Each case
 draws one network, patch, step, mirror axes and tile dtype and 1 ... 9 images of mixed extents (smaller and larger than the patch, pitches
 that are and are not multiples of 4) that travel in ONE call on an engine with default options.
     python scripts/gpu_fuzz_tiled_batch.py SEED N"""

@@ -1,8 +1,8 @@
 """One batched sliding-window call beside the per-case calls it replaces, for a kernel trace: the canonical K = 26 net, 8 copies of the
 preprocessed extent of sample_s0616 (644 x 512 padded, 2 tiles x 4 mirror passes each = 64 rows).
     rocprofv3 --kernel-trace --memory-copy-trace --stats -d OUT -- python scripts/gpu_tiled_batch_trace.py
-In the trace: sw_gather / sw_aggregate run 8 times each (ts2d_engine_predict_tiled), sw_gather_batch / sw_aggregate_batch once
-(ts2d_engine_predict_tiled_batch).  Bytes the pair moves for these 8 cases (computed from the shapes, printed below): gather reads and writes
+In the trace, per round (two rounds, the second one warm): sw_gather / sw_aggregate run 9 times each - 8 launches over one image
+(ts2d_engine_predict_tiled, one segment) and then one launch over all 8 (ts2d_engine_predict_tiled_batch, 8 segments).  Bytes the pair moves for these 8 cases (computed from the shapes, printed below): gather reads and writes
 rows x C x ph x pw floats; aggregate reads rows x K x ph x pw floats and writes K x Hp x Wp halves + bytes per case."""
 import os, sys
 import numpy as np

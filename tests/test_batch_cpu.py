@@ -4,6 +4,7 @@ import ctypes
 import os
 import re
 import shutil
+import threading
 
 import numpy as np
 import pytest
@@ -63,6 +64,58 @@ def test_predict_many_names_the_case_with_the_wrong_channel_count(two_models):
             ts.predict_many([CT[1], os.path.join(A, 'sample_chexpert.nrrd')])
         with pytest.raises(RuntimeError, match='input must be a string path or an image'):
             ts.predict_many([CT[1], 5])
+
+
+class _StubModel:
+    """The members TS2D touches, around an ``apply`` the test controls."""
+    channels, multilabel, revision, colors = {0: 'mean', 1: 'max'}, True, 'r000', {}
+
+    def __init__(self, apply):
+        self.apply, self.timestamps = apply, {}
+
+    def start(self, wait=True):
+        pass
+
+    await_startup = stop = lambda self: None
+
+
+def test_predict_waits_for_every_running_sub_model_before_it_raises():
+    """A sub-model fails at once while another is still at work: predict() raises that failure, but not before the other has finished
+    (C-ABI: one caller thread per engine - the caller may start the next case on the same handles as soon as it has control)."""
+    running, release, finished = threading.Event(), threading.Event(), threading.Event()
+
+    def failing(img):
+        running.wait(10)                      # (the other sub-model has started: it cannot be cancelled any more)
+        raise ValueError('device lost')
+
+    def slow(img):
+        running.set()
+        release.wait(10)
+        finished.set()
+        return img
+
+    img = nrrd.Image(np.zeros((8, 8, 2), np.float32), (1.5, 1.5), (0.0, 0.0), (1.0, 0.0, 0.0, 1.0), components=2)
+    outcome = []
+
+    def call(ts):
+        try:
+            ts.predict(img)
+        except BaseException as ex:
+            outcome.append((ex, finished.is_set()))
+
+    with TS2D(models={'a_fails': _StubModel(failing), 'b_slow': _StubModel(slow)}) as ts:
+        t = threading.Thread(target=call, args=(ts,))
+        t.start()
+        try:
+            assert running.wait(10)
+            t.join(0.3)
+            assert t.is_alive() and not outcome        # the failure is there, the second sub-model still runs: predict() holds on
+        finally:
+            release.set()
+            t.join(10)
+    assert not t.is_alive() and len(outcome) == 1
+    ex, second_had_finished = outcome[0]
+    assert isinstance(ex, ValueError) and str(ex) == 'device lost' and second_had_finished
 
 
 def test_apply_batch_stage_errors_timestamps_and_override(tmp_path, two_models):

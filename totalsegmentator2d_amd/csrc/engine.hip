@@ -996,8 +996,10 @@ int choose_ksplit(const Op& op, const TileGeom& g) {
 // Measured (profiles/r06_small_batch.txt, wall time of a forward, split mode): B = 1 2.51 -> 1.90 ms, B = 2 2.77 -> 2.15, B = 4 3.27 -> 2.82, B = 8 4.32 -> 3.98;
 // filling to TWO workgroups per CU instead of one: equal (the reduction pass of each further split op costs what its conv gains).
 constexpr size_t kSbkElems = (size_t)2 * 256 * 256 * 64;      // S x B x HW x Cout of any op this rule splits (n_wgs S < 2 x 256 CUs, <= 256 pixels x 64 columns each)
-// `full`: the run asks for the full-batch dispatch whatever its size (ts2d_engine_predict_tiled_batch: a row's bits must not depend on its batch)
-int fill_ksplit(const ts2d_engine* e, long long n_wgs, int nchunks, bool full = false) {
+// `full`: the run asks for the full-batch dispatch whatever its size (ts2d_engine_predict_tiled_batch: a row's bits must not depend on its batch).
+// No default anywhere below: every caller names the dispatch it means.
+constexpr bool kBySize = false, kFullBatch = true;
+int fill_ksplit(const ts2d_engine* e, long long n_wgs, int nchunks, bool full) {
     if (!e->use_sbk || full || e->num_cus > 256) return 1;            // (the bound above assumes <= 256 CUs)
     int S = 1;
     while (S < 8 && n_wgs * S < e->num_cus && nchunks / (S * 2) >= 4) S *= 2;
@@ -1028,7 +1030,7 @@ bool fuse0_applies(const ts2d_engine* e, int H, int W) {
 }
 
 // The decoder block `op` (3x3 conv over cat(up, skip)) as ONE kernel together with its transposed conv (kernels_upc.h ...), or K_NONE.
-Kern composed_kernel(const ts2d_engine* e, const Op& op, int B, int H, int W, bool full = false) {
+Kern composed_kernel(const ts2d_engine* e, const Op& op, int B, int H, int W, bool full) {
     if (!op.upc_ok || !e->use_upc || !e->use_one || e->precision == TS2D_PRECISION_F32_EXACT || B < 1) return K_NONE;
     const bool f16 = e->precision == TS2D_PRECISION_F16;
     const Op& up = e->ops[op.up_idx];
@@ -1059,7 +1061,7 @@ Kern composed_kernel(const ts2d_engine* e, const Op& op, int B, int H, int W, bo
     return upq ? K_UPQ : K_UPC;           // (Cb = 128: conv3x3_upq no faster than conv3x3_upc, measured)
 }
 
-Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W, bool full = false) {
+Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W, bool full) {
     const Op& op = e->ops[oi];
     Choice c;
     const bool f16 = e->precision == TS2D_PRECISION_F16, exact = e->precision == TS2D_PRECISION_F32_EXACT;
@@ -1189,7 +1191,7 @@ Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W, bool full = 
 }
 
 // choose() for every op, cached per (B, H, W, precision, option generation, full-batch dispatch of the run)
-const std::vector<Choice>& planned(ts2d_engine* e, int B, int H, int W, bool full = false) {
+const std::vector<Choice>& planned(ts2d_engine* e, int B, int H, int W, bool full) {
     if (e->plan.size() != e->ops.size() || e->planB != B || e->planH != H || e->planW != W || e->plan_prec != e->precision || e->plan_gen != e->opt_gen ||
         e->plan_full != full) {
         e->plan.resize(e->ops.size());
@@ -1298,7 +1300,7 @@ ActPlan plan_activations(const ts2d_engine* e, int B, int H, int W, bool keep, b
 // Layout of the activation workspace for (B, H, W) under the engine's current precision mode, options and keep flag.
 struct WsLayout { ActPlan plan; std::vector<size_t> o_sc, o_sh; size_t o_part = 0, o_pk = 0, o_up = 0, bytes = 0; };
 
-WsLayout workspace_layout(const ts2d_engine* e, int B, int H, int W, bool full = false) {
+WsLayout workspace_layout(const ts2d_engine* e, int B, int H, int W, bool full) {
     WsLayout L;
     L.plan = plan_activations(e, B, H, W, e->keep_activations, full);
     for (size_t& o : L.plan.off) o += kWsHeader;          // (the header: owner token of a shared workspace)
@@ -1325,7 +1327,7 @@ WsLayout workspace_layout(const ts2d_engine* e, int B, int H, int W, bool full =
 // memory when it fits (checked below, never assumed).  The reverse holds: a full-dispatch layout serves every "sbk" run of the same or a
 // smaller batch (the upsampled tensor of its two-kernel entries goes to the d_up scratch, as for any batch below the reserved one), so
 // the layout stays and a following predict_tiled / forward finds it unchanged.
-int ensure_workspace(ts2d_engine* e, int B, int H, int W, bool full = false) {
+int ensure_workspace(ts2d_engine* e, int B, int H, int W, bool full) {
     const bool keep = e->keep_activations;
     if (e->d_ws && e->wsB >= B && e->wsH == H && e->wsW == W && e->ws_precision == e->precision && e->ws_keep == keep && (e->ws_full || !full)) return TS2D_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1434,8 +1436,7 @@ bool workspace_is_mine(ts2d_engine* e) {
     return tok == e->ws_token;
 }
 
-int run_forward(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st, bool clear_flags = true,
-                bool full = false) {
+int run_forward(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st, bool clear_flags, bool full) {
     TRY(workspace_acquire(e, st));
     if (e->ws_external) {           // stamp the shared workspace: whatever another engine of the set left in it is gone after this run
         e->ws_token = ++g_ws_generation;
@@ -1996,7 +1997,7 @@ static int reserve_checked(ts2d_engine* e, int B, int H, int W, bool full) {
 
 int ts2d_engine_reserve(ts2d_engine* e, int B, int H, int W) {
     if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_reserve: null engine");
-    return reserve_checked(e, B, H, W, false);
+    return reserve_checked(e, B, H, W, kBySize);
 }
 
 int ts2d_engine_workspace_bytes(ts2d_engine* e, int B, int H, int W, size_t* n_bytes) {
@@ -2004,7 +2005,7 @@ int ts2d_engine_workspace_bytes(ts2d_engine* e, int B, int H, int W, size_t* n_b
     const int divy = 1 << e->lvl_y[e->arch.n_stages - 1], divx = 1 << e->lvl_x[e->arch.n_stages - 1];
     if (B < 1 || H < divy || W < divx || H % divy || W % divx)
         return fail(TS2D_ERR_INVALID, "shape B=%d H=%d W=%d: H and W must be positive multiples of %d and %d", B, H, W, divy, divx);
-    *n_bytes = workspace_layout(e, B, H, W).bytes;
+    *n_bytes = workspace_layout(e, B, H, W, kBySize).bytes;
     return TS2D_OK;
 }
 
@@ -2032,98 +2033,29 @@ int ts2d_engine_forward(ts2d_engine* e, const float* input, int B, int H, int W,
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : e->stream;
     const int K = e->arch.num_classes;
-    if (on_device) return run_forward(e, input, B, H, W, logits, mask_packed, st);
+    if (on_device) return run_forward(e, input, B, H, W, logits, mask_packed, st, true, kBySize);
     // host buffers: staged on the device, synchronous
     TRY(ensure_staging(e, B, H, W));
     HIP_TRY(hipMemcpyAsync(e->d_in_stage, input, (size_t)B * e->arch.input_channels * H * W * sizeof(float), hipMemcpyHostToDevice, st));
-    TRY(run_forward(e, e->d_in_stage, B, H, W, logits ? e->d_logit_stage : nullptr, mask_packed ? e->d_mask_stage : nullptr, st));
+    TRY(run_forward(e, e->d_in_stage, B, H, W, logits ? e->d_logit_stage : nullptr, mask_packed ? e->d_mask_stage : nullptr, st, true, kBySize));
     if (logits) HIP_TRY(hipMemcpyAsync(logits, e->d_logit_stage, (size_t)B * K * H * W * sizeof(float), hipMemcpyDeviceToHost, st));
     if (mask_packed) HIP_TRY(hipMemcpyAsync(mask_packed, e->d_mask_stage, (size_t)B * K * H * (W / 32) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return ts2d_engine_check(e);          // never a silent inf / NaN (asynchronous device-pointer calls: the caller runs the check)
 }
 
-int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp, int ph, int pw, int n_tiles,
-                              const int32_t* tile_y, const int32_t* tile_x, int mirror_mask, const uint16_t* gaussian_f16,
-                              uint16_t* logits_f16, uint8_t* seg_u8) {
-    if (!e || !image || !tile_y || !tile_x) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: null argument");
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
-    if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
-    if (n_tiles < 1 || ph > Hp || pw > Wp) return fail(TS2D_ERR_INVALID, "bad tiling: %d tiles of %dx%d on %dx%d", n_tiles, ph, pw, Hp, Wp);
-    for (int t = 0; t < n_tiles; ++t)
-        if (tile_y[t] < 0 || tile_x[t] < 0 || tile_y[t] + ph > Hp || tile_x[t] + pw > Wp)
-            return fail(TS2D_ERR_INVALID, "tile %d at (%d,%d) leaves the %dx%d image", t, tile_y[t], tile_x[t], Hp, Wp);
-    const int C = e->arch.input_channels, K = e->arch.num_classes;
-    int vflip[4] = {0, 0, 0, 0}, V = 1;
-    if ((mirror_mask & 3) == 3) { vflip[1] = 1; vflip[2] = 2; vflip[3] = 3; V = 4; }
-    else if (mirror_mask & 1) { vflip[1] = 1; V = 2; }
-    else if (mirror_mask & 2) { vflip[1] = 2; V = 2; }
-    const int rows = n_tiles * V, chunk = std::min(rows, 64);
-    TRY(ts2d_engine_reserve(e, chunk, ph, pw));
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t st = e->stream;
-    // scratch layout
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_img = take((size_t)C * Hp * Wp * 4), o_batch = take((size_t)rows * C * ph * pw * 4);
-    const size_t o_log = take((size_t)rows * K * ph * pw * 4), o_g = take((size_t)ph * pw * 2);
-    const size_t o_o16 = take((size_t)K * Hp * Wp * 2), o_seg = take((size_t)K * Hp * Wp);
-    const size_t o_ty = take((size_t)n_tiles * 4), o_tx = take((size_t)n_tiles * 4), o_vf = take(16), o_flag = take(4);
-    if (off > e->sw_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (e->d_sw) { HIP_TRY(hipFree(e->d_sw)); e->d_sw = nullptr; e->sw_bytes = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&e->d_sw), off));
-        e->sw_bytes = off;
-    }
-    char* b = e->d_sw;
-    float* d_img = reinterpret_cast<float*>(b + o_img); float* d_batch = reinterpret_cast<float*>(b + o_batch);
-    float* d_log = reinterpret_cast<float*>(b + o_log); __half* d_g = reinterpret_cast<__half*>(b + o_g);
-    __half* d_o16 = reinterpret_cast<__half*>(b + o_o16); uint8_t* d_seg = reinterpret_cast<uint8_t*>(b + o_seg);
-    int* d_ty = reinterpret_cast<int*>(b + o_ty); int* d_tx = reinterpret_cast<int*>(b + o_tx); int* d_vf = reinterpret_cast<int*>(b + o_vf);
-    HIP_TRY(hipMemcpyAsync(d_img, image, (size_t)C * Hp * Wp * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_ty, tile_y, (size_t)n_tiles * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_tx, tile_x, (size_t)n_tiles * 4, hipMemcpyHostToDevice, st));
-    int* d_flag = reinterpret_cast<int*>(b + o_flag);
-    HIP_TRY(hipMemsetAsync(d_flag, 0, 4, st));
-    HIP_TRY(hipMemcpyAsync(d_vf, vflip, 16, hipMemcpyHostToDevice, st));
-    if (gaussian_f16) HIP_TRY(hipMemcpyAsync(d_g, gaussian_f16, (size_t)ph * pw * 2, hipMemcpyHostToDevice, st));
-    {
-        const long long total = (long long)rows * C * ph * pw;
-        hipLaunchKernelGGL(sw_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_img, C, Hp, Wp, ph, pw, V, d_ty, d_tx, d_vf, d_batch, total);
-        HIP_TRY(hipGetLastError());
-    }
-    for (int r0 = 0; r0 < rows; r0 += chunk) {
-        const int nb = std::min(chunk, rows - r0);
-        TRY(run_forward(e, d_batch + (size_t)r0 * C * ph * pw, nb, ph, pw, d_log + (size_t)r0 * K * ph * pw, nullptr, st, r0 == 0));
-    }
-    {
-        const long long total = (long long)K * Hp * Wp;
-        hipLaunchKernelGGL(sw_aggregate, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_log, K, Hp, Wp, ph, pw, n_tiles, V,
-                           d_ty, d_tx, d_vf, gaussian_f16 ? d_g : nullptr, logits_f16 ? d_o16 : nullptr, seg_u8 ? d_seg : nullptr,
-                           kSigmoidHalfThreshold, total, d_flag, e->tile_half);
-        HIP_TRY(hipGetLastError());
-    }
-    e->tiled_inf = 0;
-    HIP_TRY(hipMemcpyAsync(&e->tiled_inf, d_flag, 4, hipMemcpyDeviceToHost, st));
-    if (logits_f16) HIP_TRY(hipMemcpyAsync(logits_f16, d_o16, (size_t)K * Hp * Wp * 2, hipMemcpyDeviceToHost, st));
-    if (seg_u8) HIP_TRY(hipMemcpyAsync(seg_u8, d_seg, (size_t)K * Hp * Wp, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return ts2d_engine_check(e);
-}
-
-// N images through the sliding window as ONE engine batch (include/ts2d_engine.h).  Host side: validate everything, pack the rows
-// (tile x mirror variant) of the images into chunks of at most kSwChunkRows, lay the scratch out, enqueue every host-to-device copy,
-// then per chunk one sw_gather_batch, one full-batch-dispatch forward and (where an image ends in the chunk) one sw_aggregate_batch,
-// then every device-to-host copy, ONE stream synchronise and the result check.
+// The sliding window of both C entries (include/ts2d_engine.h): N images as ONE engine batch; ts2d_engine_predict_tiled is N = 1.
+// Host side: validate everything, pack the rows (tile x mirror variant) of the images into chunks of at most kSwChunkRows, lay the
+// scratch out, enqueue every host-to-device copy, then per chunk one sw_gather, one forward and (where an image ends in the chunk)
+// one sw_aggregate, then every device-to-host copy, ONE stream synchronise and the result check.
+// `full` is the whole difference between the entries' results: the batch entry asks for the full-batch dispatch (a row's bits must not
+// depend on its batch-mates), the single-image entry for the size-dependent one.  `name_images`: a message names the image it is about.
 constexpr int kSwChunkRows = 64;
 
-int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
-                                    const uint16_t* gaussian_f16) {
-    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: null engine");
-    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
-    if (n_images == 0) return TS2D_OK;
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
-    if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: bad patch %dx%d", ph, pw);
+static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
+                              const uint16_t* gaussian_f16, bool full, bool name_images) {
+    const char* entry = name_images ? "ts2d_engine_predict_tiled_batch" : "ts2d_engine_predict_tiled";
+    if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "%s: bad patch %dx%d", entry, ph, pw);
     const int C = e->arch.input_channels, K = e->arch.num_classes;
     int vflip[4] = {0, 0, 0, 0}, V = 1;
     if ((mirror_mask & 3) == 3) { vflip[1] = 1; vflip[2] = 2; vflip[3] = 3; V = 4; }
@@ -2134,19 +2066,21 @@ int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, in
     bool any16 = false, anyseg = false;
     for (int i = 0; i < n_images; ++i) {
         const ts2d_tiled_image& im = images[i];
-        if (!im.image || !im.tile_y || !im.tile_x) return fail(TS2D_ERR_INVALID, "image %d: null image or tile pointer", i);
-        if (!im.logits_f16 && !im.seg_u8) return fail(TS2D_ERR_INVALID, "image %d: both outputs are null", i);
+        char pre[24] = "";
+        if (name_images) snprintf(pre, sizeof(pre), "image %d: ", i);
+        if (!im.image || !im.tile_y || !im.tile_x) return fail(TS2D_ERR_INVALID, "%snull image or tile pointer", pre);
+        if (!im.logits_f16 && !im.seg_u8) return fail(TS2D_ERR_INVALID, "%sboth outputs are null", pre);
         if (im.n_tiles < 1 || im.n_tiles > (1 << 20) || im.Hp < 1 || im.Wp < 1 || ph > im.Hp || pw > im.Wp)
-            return fail(TS2D_ERR_INVALID, "image %d: bad tiling: %d tiles of %dx%d on %dx%d", i, im.n_tiles, ph, pw, im.Hp, im.Wp);
+            return fail(TS2D_ERR_INVALID, "%sbad tiling: %d tiles of %dx%d on %dx%d", pre, im.n_tiles, ph, pw, im.Hp, im.Wp);
         if ((long long)K * im.Hp * im.Wp >= (1LL << 31) || (long long)C * im.Hp * im.Wp >= (1LL << 31))
-            return fail(TS2D_ERR_INVALID, "image %d: %dx%d exceeds 2^31 elements per image", i, im.Hp, im.Wp);
+            return fail(TS2D_ERR_INVALID, "%s%dx%d exceeds 2^31 elements per image", pre, im.Hp, im.Wp);
         for (int t = 0; t < im.n_tiles; ++t)
             if (im.tile_y[t] < 0 || im.tile_x[t] < 0 || im.tile_y[t] + ph > im.Hp || im.tile_x[t] + pw > im.Wp)
-                return fail(TS2D_ERR_INVALID, "image %d: tile %d at (%d,%d) leaves the %dx%d image", i, t, im.tile_y[t], im.tile_x[t], im.Hp, im.Wp);
+                return fail(TS2D_ERR_INVALID, "%stile %d at (%d,%d) leaves the %dx%d image", pre, t, im.tile_y[t], im.tile_x[t], im.Hp, im.Wp);
         n_tiles_all += im.n_tiles;
         any16 |= im.logits_f16 != nullptr; anyseg |= im.seg_u8 != nullptr;
     }
-    if (n_tiles_all * V >= (1LL << 28)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %lld network rows in one call", n_tiles_all * V);
+    if (n_tiles_all * V >= (1LL << 28)) return fail(TS2D_ERR_INVALID, "%s: %lld network rows in one call", entry, n_tiles_all * V);
     // ---- row packing: whole images, greedily, into chunks of at most kSwChunkRows rows; a larger image takes chunks of its own
     struct Chunk { int seg0, n_segs, rows, log_row; bool aggregate; unsigned gblocks, ablocks; };
     std::vector<SwSeg> segs;
@@ -2192,10 +2126,10 @@ int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, in
     flush();
     for (const Chunk& c : chunks) {
         cap_rows = std::max(cap_rows, c.rows);
-        if ((long long)c.gblocks >= (1LL << 31) || (long long)c.ablocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: a chunk exceeds 2^31 blocks");
+        if ((long long)c.gblocks >= (1LL << 31) || (long long)c.ablocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: a chunk exceeds 2^31 blocks", entry);
     }
     log_rows = std::max<long long>(log_rows, cap_rows);
-    TRY(reserve_checked(e, cap_rows, ph, pw, true));
+    TRY(reserve_checked(e, cap_rows, ph, pw, full));
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = e->stream;
     // ---- the descriptor table and every tile origin: one host blob, one copy
@@ -2240,11 +2174,11 @@ int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, in
     }
     for (size_t ci = 0; ci < chunks.size(); ++ci) {
         const Chunk& c = chunks[ci];
-        hipLaunchKernelGGL(sw_gather_batch, dim3(c.gblocks), dim3(256), 0, st, d_imgs, d_segs + c.seg0, c.n_segs, C, ph, pw, V, vflips, d_ty, d_tx, d_batch);
+        hipLaunchKernelGGL(sw_gather, dim3(c.gblocks), dim3(256), 0, st, d_imgs, d_segs + c.seg0, c.n_segs, C, ph, pw, V, vflips, d_ty, d_tx, d_batch);
         HIP_TRY(hipGetLastError());
-        TRY(run_forward(e, d_batch, c.rows, ph, pw, d_log + (size_t)c.log_row * K * ph * pw, nullptr, st, ci == 0, true));
+        TRY(run_forward(e, d_batch, c.rows, ph, pw, d_log + (size_t)c.log_row * K * ph * pw, nullptr, st, ci == 0, full));
         if (!c.aggregate) continue;
-        hipLaunchKernelGGL(sw_aggregate_batch, dim3(c.ablocks), dim3(256), 0, st, d_log, d_segs + c.seg0, c.n_segs, K, ph, pw, V, vflips, d_ty, d_tx,
+        hipLaunchKernelGGL(sw_aggregate, dim3(c.ablocks), dim3(256), 0, st, d_log, d_segs + c.seg0, c.n_segs, K, ph, pw, V, vflips, d_ty, d_tx,
                            gaussian_f16 ? d_g : nullptr, d_o16, d_seg, kSigmoidHalfThreshold, d_flag, e->tile_half);
         HIP_TRY(hipGetLastError());
     }
@@ -2263,6 +2197,25 @@ int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, in
     e->tiled_inf = 0;
     for (int i = 0; i < n_images; ++i) { images[i].inf_flag = flags[i] != 0; e->tiled_inf |= flags[i] != 0; }
     return ts2d_engine_check(e);
+}
+
+int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp, int ph, int pw, int n_tiles,
+                              const int32_t* tile_y, const int32_t* tile_x, int mirror_mask, const uint16_t* gaussian_f16,
+                              uint16_t* logits_f16, uint8_t* seg_u8) {
+    if (!e || !image || !tile_y || !tile_x) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: null argument");
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
+    if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
+    ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
+    return predict_tiled_impl(e, &one, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false);
+}
+
+int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
+                                    const uint16_t* gaussian_f16) {
+    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: null engine");
+    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
+    if (n_images == 0) return TS2D_OK;
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
+    return predict_tiled_impl(e, images, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true);
 }
 
 int ts2d_engine_check(ts2d_engine* e) {

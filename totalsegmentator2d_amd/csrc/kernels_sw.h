@@ -7,6 +7,13 @@
 //   tile_half != 0 (the CUDA autocast path): the tile is cast to half first, the product and the sum each round to half.
 // Tiles are accumulated in upstream order per output pixel, so the result is bit-identical to the host implementation in
 // predictor.py (tests/test_gpu_predictor.py).
+//
+// One kernel pair serves ts2d_engine_predict_tiled (one image) and ts2d_engine_predict_tiled_batch: ONE gather and ONE aggregate launch
+// per chunk of network rows, whatever the number of images in it.  A chunk is described by a device table of segments (one per image
+// that has rows in the chunk); a block belongs to exactly one segment, found by a search over the `first block` prefix with the block
+// index - wave-uniform, so no lane diverges on it.  Both kernels are pure HBM traffic: each lane owns 4 consecutive X, reads 16 bytes
+// where the tile origin and the row pitch allow (a W-mirrored variant reads the 16 bytes at the mirrored position and reverses them)
+// and stores 16 / 8 / 4 bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -14,70 +21,6 @@
 
 namespace ts2d {
 
-// batch row (t * V + v) = tile t, mirror variant v; variant flips: bit0 = flip H (tensor dim 2), bit1 = flip W (dim 3)
-__global__ void sw_gather(const float* __restrict__ img, int C, int Hp, int Wp, int ph, int pw, int V,
-                          const int* __restrict__ tile_y, const int* __restrict__ tile_x, const int* __restrict__ vflip,
-                          float* __restrict__ batch, long long total) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int x = (int)(i % pw); long long r = i / pw;
-    const int y = (int)(r % ph); r /= ph;
-    const int c = (int)(r % C); const int row = (int)(r / C);
-    const int t = row / V, f = vflip[row % V];
-    const int sy = (f & 1) ? ph - 1 - y : y, sx = (f & 2) ? pw - 1 - x : x;
-    batch[i] = img[((size_t)c * Hp + tile_y[t] + sy) * Wp + tile_x[t] + sx];
-}
-
-__device__ __forceinline__ __half h_mul(__half a, __half b) { return __float2half_rn(__half2float(a) * __half2float(b)); }
-__device__ __forceinline__ __half h_add(__half a, __half b) { return __float2half_rn(__half2float(a) + __half2float(b)); }
-__device__ __forceinline__ __half h_div(__half a, __half b) { return __float2half_rn(__half2float(a) / __half2float(b)); }
-
-// one thread per output element (k, Y, X) of the padded image
-__global__ void sw_aggregate(const float* __restrict__ logits, int K, int Hp, int Wp, int ph, int pw, int T, int V,
-                             const int* __restrict__ tile_y, const int* __restrict__ tile_x, const int* __restrict__ vflip,
-                             const __half* __restrict__ gauss, __half* __restrict__ out16, uint8_t* __restrict__ seg,
-                             float thr, long long total, int* __restrict__ inf_flag, int tile_half) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int X = (int)(i % Wp); long long r = i / Wp;
-    const int Y = (int)(r % Hp); const int k = (int)(r / Hp);
-    __half acc = __float2half_rn(0.f), n = __float2half_rn(0.f);
-    for (int t = 0; t < T; ++t) {
-        const int yy = Y - tile_y[t], xx = X - tile_x[t];
-        if (yy < 0 || yy >= ph || xx < 0 || xx >= pw) continue;
-        const size_t plane = (size_t)ph * pw;
-        float y = logits[((size_t)(t * V) * K + k) * plane + (size_t)yy * pw + xx];
-        for (int v = 1; v < V; ++v) {                      // y += flip(net(flip(x)), axes): read the un-flipped position
-            const int f = vflip[v];
-            const int sy = (f & 1) ? ph - 1 - yy : yy, sx = (f & 2) ? pw - 1 - xx : xx;
-            y += logits[((size_t)(t * V + v) * K + k) * plane + (size_t)sy * pw + sx];
-        }
-        if (V > 1) y /= (float)V;
-        const __half g = gauss ? gauss[(size_t)yy * pw + xx] : __float2half_rn(1.f);
-        if (tile_half) {
-            __half p = __float2half_rn(y);
-            if (gauss) p = h_mul(p, g);
-            acc = h_add(acc, p);
-        } else {      // (explicit _rn intrinsics: the product must round to fp32 before the add - no FMA contraction)
-            const float pf = gauss ? __fmul_rn(y, __half2float(g)) : y;
-            acc = __float2half_rn(__fadd_rn(__half2float(acc), pf));
-        }
-        n = h_add(n, g);
-    }
-    const __half res = h_div(acc, n);
-    if ((__half_as_ushort(res) & 0x7FFFu) == 0x7C00u) *inf_flag = 1;      // upstream's "Encountered inf in predicted array" check
-    if (out16) out16[i] = res;
-    if (seg) seg[i] = __half2float(res) > thr ? 1 : 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------ batched form
-// ts2d_engine_predict_tiled_batch: ONE gather and ONE aggregate launch per chunk of network rows, whatever the number of images in it.
-// A chunk is described by a device table of segments (one per image that has rows in the chunk); a block belongs to exactly one
-// segment, found by a search over the `first block` prefix with the block index - wave-uniform, so no lane diverges on it.
-// Both kernels are pure HBM traffic: each lane owns 4 consecutive X, reads 16 bytes where the tile origin and the row pitch allow
-// (a W-mirrored variant reads the 16 bytes at the mirrored position and reverses them) and stores 16 / 8 / 4 bytes.
-// The per-pixel arithmetic of sw_aggregate_batch is that of sw_aggregate, operation for operation (sw_blend below repeats its
-// statements): the two kernels give the same bits, which is what makes a batched case equal to ts2d_engine_predict_tiled.
 struct SwSeg {
     long long img_off;      // floats from the image area to this image's [C, Hp, Wp] (a multiple of 4)
     long long out_off;      // elements from the output areas to this image's [K, Hp, Wp] (a multiple of 8)
@@ -105,12 +48,12 @@ __device__ __forceinline__ int sw_find_seg(const SwSeg* __restrict__ segs, int n
     return lo;
 }
 
-// vflip of variant v, packed 8 bits per variant
+// batch row (t * V + v) = tile t, mirror variant v; variant flips: bit0 = flip H (tensor dim 2), bit1 = flip W (dim 3), packed 8 bits per variant
 __device__ __forceinline__ int sw_vflip(int packed, int v) { return (packed >> (8 * v)) & 3; }
 
-__global__ __launch_bounds__(256) void sw_gather_batch(const float* __restrict__ images, const SwSeg* __restrict__ segs, int n_segs,
-                                                       int C, int ph, int pw, int V, int vflips, const int* __restrict__ tile_y,
-                                                       const int* __restrict__ tile_x, float* __restrict__ batch) {
+__global__ __launch_bounds__(256) void sw_gather(const float* __restrict__ images, const SwSeg* __restrict__ segs, int n_segs,
+                                                 int C, int ph, int pw, int V, int vflips, const int* __restrict__ tile_y,
+                                                 const int* __restrict__ tile_x, float* __restrict__ batch) {
     const SwSeg sg = segs[sw_find_seg<false>(segs, n_segs, blockIdx.x)];
     const int pwq = (pw + 3) >> 2;
     const long long q = (long long)(blockIdx.x - sg.gblock0) * 256 + threadIdx.x;
@@ -136,14 +79,18 @@ __global__ __launch_bounds__(256) void sw_gather_batch(const float* __restrict__
     }
 }
 
-// one tile's contribution to one pixel: the statements of sw_aggregate's loop body
+__device__ __forceinline__ __half h_mul(__half a, __half b) { return __float2half_rn(__half2float(a) * __half2float(b)); }
+__device__ __forceinline__ __half h_add(__half a, __half b) { return __float2half_rn(__half2float(a) + __half2float(b)); }
+__device__ __forceinline__ __half h_div(__half a, __half b) { return __float2half_rn(__half2float(a) / __half2float(b)); }
+
+// one tile's contribution to one pixel (y: the sum over the mirror variants), shared by the 16-byte and the per-pixel path of sw_aggregate
 __device__ __forceinline__ void sw_blend(__half& acc, __half& n, float y, int V, bool has_gauss, __half g, int tile_half) {
     if (V > 1) y /= (float)V;
     if (tile_half) {
         __half p = __float2half_rn(y);
         if (has_gauss) p = h_mul(p, g);
         acc = h_add(acc, p);
-    } else {
+    } else {      // (explicit _rn intrinsics: the product must round to fp32 before the add - no FMA contraction)
         const float pf = has_gauss ? __fmul_rn(y, __half2float(g)) : y;
         acc = __float2half_rn(__fadd_rn(__half2float(acc), pf));
     }
@@ -151,11 +98,11 @@ __device__ __forceinline__ void sw_blend(__half& acc, __half& n, float y, int V,
 }
 
 // one lane per 4 consecutive X of one (k, Y) row of one image's padded extent
-__global__ __launch_bounds__(256) void sw_aggregate_batch(const float* __restrict__ logits, const SwSeg* __restrict__ segs, int n_segs,
-                                                          int K, int ph, int pw, int V, int vflips, const int* __restrict__ tile_y,
-                                                          const int* __restrict__ tile_x, const __half* __restrict__ gauss,
-                                                          __half* __restrict__ out16, uint8_t* __restrict__ seg, float thr,
-                                                          int* __restrict__ inf_flags, int tile_half) {
+__global__ __launch_bounds__(256) void sw_aggregate(const float* __restrict__ logits, const SwSeg* __restrict__ segs, int n_segs,
+                                                    int K, int ph, int pw, int V, int vflips, const int* __restrict__ tile_y,
+                                                    const int* __restrict__ tile_x, const __half* __restrict__ gauss,
+                                                    __half* __restrict__ out16, uint8_t* __restrict__ seg, float thr,
+                                                    int* __restrict__ inf_flags, int tile_half) {
     const SwSeg sg = segs[sw_find_seg<true>(segs, n_segs, blockIdx.x)];
     const int Hp = sg.Hp, Wp = sg.Wp, Wq = (Wp + 3) >> 2;
     const long long total = (long long)K * Hp * Wq;
@@ -173,7 +120,7 @@ __global__ __launch_bounds__(256) void sw_aggregate_batch(const float* __restric
     const __half one = __float2half_rn(1.f);
     __half acc[4], n[4];
     for (int j = 0; j < 4; ++j) { acc[j] = __float2half_rn(0.f); n[j] = __float2half_rn(0.f); }
-    for (int t = 0; t < sg.n_tiles; ++t) {                // tiles in ascending order, as sw_aggregate
+    for (int t = 0; t < sg.n_tiles; ++t) {                // tiles in ascending (upstream) order
         const int ty = tile_y[sg.tile0 + t], tx = tile_x[sg.tile0 + t];
         if (Yhi < ty || Ylo >= ty + ph) continue;         // (wave-uniform)
         const int yy = Y - ty, xx0 = X0 - tx;
@@ -239,6 +186,5 @@ __global__ __launch_bounds__(256) void sw_aggregate_batch(const float* __restric
         }
     }
 }
-
 
 }  // namespace ts2d

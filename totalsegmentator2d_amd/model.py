@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Union
 import numpy as np
 
 from . import nrrd
-from .export import export_prediction_from_logits
+from .export import export_prediction_from_logits, needs_logits
 from .predictor import HIPnnUNetPredictor
 
 
@@ -37,7 +37,7 @@ class HIPModel:
         self.labels: Optional[Dict[int, str]] = None
         self.colors = self._param.get('nnu.result.colors')
         self._dataset_json: Optional[dict] = None
-        self.device_threshold = True     # thresholded segmentation straight from the device where the export needs no logits (_apply_one)
+        self.device_threshold = True     # thresholded segmentation straight from the device where the export needs no logits (_run)
         self._discover()
 
     # ------------------------------------------------------------------ configuration (reference wrapper.py:113-162)
@@ -128,9 +128,9 @@ class HIPModel:
         if isinstance(inputs, (list, tuple)):
             inputs = {f'image{i + 1}': img for i, img in enumerate(inputs)}
         results = {}
-        for name, img in inputs.items():
+        for name, img in inputs.items():          # one input at a time through all four stages, as the reference's worker
             try:
-                results[name] = self._apply_one(name, img, result_dir, override)
+                results.update(self._run({name: img}, result_dir, override, batched=False, stamps={}))
             except Exception as ex:
                 raise RuntimeError(f"Prediction failed for: {name}: {ex}") from ex
         return next(iter(results.values())) if single else results
@@ -146,7 +146,7 @@ class HIPModel:
                      None if dz is None else tuple(dz.get('order', ()))))
 
     def _preprocess_input(self, img):
-        """Stage 1 of :meth:`_apply_one` / :meth:`apply_batch`: read, to array, preprocess (the case's shared ``preprocess_cache`` is honoured).
+        """Stage 1 of :meth:`_run`: read, to array, preprocess (the case's shared ``preprocess_cache`` is honoured).
         Returns (reference image, preprocessed data, properties)."""
         p = self._predictor
         ref = nrrd.read(img) if isinstance(img, str) else img
@@ -169,78 +169,33 @@ class HIPModel:
             data, props = hit[0], dict(hit[1])
         return ref, data, props
 
-    def _apply_one(self, name, img, result_dir, override):
-        """The reference worker's four stages (``prediction_worker.py:177-242``), each failing under its own name -
-        ``"<Stage> failed for <name>: <cause>"`` - so that a HIP error (``ts2d_last_error``) tells which stage raised it."""
+    def _predict(self, datas, use_seg: bool, batched: bool):
+        """Stage 2 of :meth:`_run`, the one stage that differs between :meth:`apply` and :meth:`apply_batch`: ONE predictor batch call
+        over ``datas``, or the predictor's single-case methods per input - the reference's duck-typed seam
+        (``predict_logits_from_preprocessed_data``, prediction_worker.py:206-209), which a foreign predictor without the batch methods
+        serves too.  ``use_seg``: ask for the device-thresholded segmentation first (it answers None when the case needs the logits)."""
         p = self._predictor
-        ts = self.timestamps = {'start': time.time()}
-        ofile = None
-        try:
-            if result_dir is not None:
-                os.makedirs(result_dir, exist_ok=True)
-                ofile = os.path.join(result_dir, name)
-                if not override and os.path.exists(ofile + '.nrrd'):
-                    return ofile + '.nrrd'
-        except Exception as ex:
-            raise RuntimeError(f"Could not create output directory: {ex}") from ex
-        try:
-            ref, data, props = self._preprocess_input(img)
-            ts['preprocessed'] = time.time()
-        except Exception as ex:
-            raise RuntimeError(f"Preprocessing failed for {name}: {ex}") from ex
-        try:
-            logits = None
-            # product fast path: a multilabel 2-D case whose export does not resample gets its segmentation thresholded on the device
-            # (K uint8 planes to the host instead of K float16 ones; the predicate is the export step's, bit for bit) - the reference's seam
-            # (predict_logits_from_preprocessed_data + export_prediction_from_logits) stays as it is and serves every other case
-            if self.device_threshold and bool(p.dataset_json.get('multilabel', p.dataset_json.get('multiclass', False))) \
-                    and hasattr(p, 'predict_segmentation_from_preprocessed_data'):
-                from .export import needs_logits
-                if not needs_logits(props, np.asarray(data).shape[1:]):
-                    logits = p.predict_segmentation_from_preprocessed_data(data)
-            if logits is None:
-                logits = p.predict_logits_from_preprocessed_data(data)
-                logits = logits.cpu().numpy() if hasattr(logits, 'cpu') else logits
-            ts['predicted'] = time.time()
-        except Exception as ex:
-            raise RuntimeError(f"Prediction failed for {name}: {ex}") from ex
-        try:
-            seg = export_prediction_from_logits(logits, props, p.configuration_manager, p.plans_manager, p.dataset_json, ofile,
-                                                ref_image=ref, labels=self.labels,
-                                                colors=self.colors if isinstance(self.colors, dict) else None)
-            ts['exported'] = ts['done'] = time.time()
-        except Exception as ex:
-            raise RuntimeError(f"Export failed for {name}: {ex}") from ex
-        return (ofile + '.nrrd') if result_dir is not None else seg
+        if batched:
+            out = p.predict_segmentation_from_preprocessed_data_batch(datas) if use_seg else None
+            if out is None:
+                out = p.predict_logits_from_preprocessed_data_batch(datas)
+        else:
+            out = [p.predict_segmentation_from_preprocessed_data(d) if use_seg else None for d in datas]
+            out = [p.predict_logits_from_preprocessed_data(d) if o is None else o for d, o in zip(datas, out)]
+        return [o.cpu().numpy() if hasattr(o, 'cpu') else o for o in out]
 
-    # ------------------------------------------------------------------ apply_batch: N inputs, one predictor batch call
-    def _wants_device_threshold(self, data, props) -> bool:
-        """The fast-path decision of :meth:`_apply_one`: a multilabel case whose export needs no logits gets its segmentation from the device."""
-        p = self._predictor
-        if not (self.device_threshold and bool(p.dataset_json.get('multilabel', p.dataset_json.get('multiclass', False)))
-                and hasattr(p, 'predict_segmentation_from_preprocessed_data_batch')):
-            return False
-        from .export import needs_logits
-        return not needs_logits(props, np.asarray(data).shape[1:])
-
-    def apply_batch(self, inputs: Union[List, Dict], result_dir: Optional[str] = None, override: bool = True) -> dict:
-        """:meth:`apply` for several inputs with ONE engine batch (the reference's ``apply`` submits every input to its worker pool before
-        it waits, ``ts2d/core/inference/nnu.py:194-216``).  Stage 1 preprocesses every input, stage 2 is one predictor batch call over
-        the inputs that share the fast-path decision (device-thresholded segmentation / logits: at most two calls), stage 3 exports
-        each.  Inside the batched engine call the network always takes the full-batch dispatch, so an input's result does not depend
-        on the other inputs of the call.  Errors: ``"<Stage> failed for <name>: <cause>"``.  ``batch_timestamps[name]`` holds
-        ``start / preprocessed / predicted / exported / done`` per input (the inputs of one batch share ``predicted``);
-        ``timestamps`` is left at the last input's values.  ``override=False`` skips existing outputs before any device work."""
-        if self._predictor is None:
-            raise RuntimeError("model is not started")
-        if isinstance(inputs, (list, tuple)):
-            inputs = {f'image{i + 1}': img for i, img in enumerate(inputs)}
+    def _run(self, inputs: dict, result_dir, override, batched: bool, stamps: dict) -> dict:
+        """The reference worker's four stages (``prediction_worker.py:177-242``) over ``inputs``: output file, preprocessing of every
+        input, prediction (:meth:`_predict`, per group of inputs that share the fast-path decision: at most two groups), export of each.
+        Each stage fails under its own name - ``"<Stage> failed for <name>: <cause>"`` - so that a HIP error (``ts2d_last_error``)
+        tells which stage raised it.  ``stamps[name]`` receives ``start / preprocessed / predicted / exported / done`` per input (the
+        inputs of one group share ``predicted``); ``timestamps`` follows the input at work.  ``override=False`` skips existing outputs
+        before any device work."""
         p = self._predictor
         results: dict = {}
-        self.batch_timestamps = {}
         todo = []
         for name, img in inputs.items():
-            ts = self.batch_timestamps[name] = {'start': time.time()}
+            ts = self.timestamps = stamps[name] = {'start': time.time()}
             ofile = None
             try:
                 if result_dir is not None:
@@ -257,15 +212,17 @@ class HIPModel:
             except Exception as ex:
                 raise RuntimeError(f"Preprocessing failed for {name}: {ex}") from ex
             todo.append([name, ofile, ref, data, props, None])
-        fast = [t for t in todo if self._wants_device_threshold(t[3], t[4])]
+        # product fast path: a multilabel 2-D case whose export does not resample gets its segmentation thresholded on the device
+        # (K uint8 planes to the host instead of K float16 ones; the predicate is the export step's, bit for bit) - the reference's seam
+        # (predict_logits_from_preprocessed_data + export_prediction_from_logits) stays as it is and serves every other case
+        can_seg = self.device_threshold and bool(p.dataset_json.get('multilabel', p.dataset_json.get('multiclass', False))) \
+            and hasattr(p, 'predict_segmentation_from_preprocessed_data' + ('_batch' if batched else ''))
+        fast = [t for t in todo if can_seg and not needs_logits(t[4], np.asarray(t[3]).shape[1:])]
         for group, use_seg in ((fast, True), ([t for t in todo if not any(t is f for f in fast)], False)):
             if not group:
                 continue
             try:
-                out = p.predict_segmentation_from_preprocessed_data_batch([t[3] for t in group]) if use_seg else None
-                if out is None:
-                    out = p.predict_logits_from_preprocessed_data_batch([t[3] for t in group])
-                    out = [o.cpu().numpy() if hasattr(o, 'cpu') else o for o in out]
+                out = self._predict([t[3] for t in group], use_seg, batched)
             except Exception as ex:
                 names = ', '.join(t[0] for t in group)
                 m = re.match(r'input (\d+): ', str(ex))          # the predictor names the offending input of the batch by index
@@ -275,9 +232,9 @@ class HIPModel:
             now = time.time()
             for t, o in zip(group, out):
                 t[5] = o
-                self.batch_timestamps[t[0]]['predicted'] = now
+                stamps[t[0]]['predicted'] = now
         for name, ofile, ref, data, props, logits in todo:
-            ts = self.batch_timestamps[name]
+            ts = self.timestamps = stamps[name]
             try:
                 seg = export_prediction_from_logits(logits, props, p.configuration_manager, p.plans_manager, p.dataset_json, ofile,
                                                     ref_image=ref, labels=self.labels,
@@ -286,5 +243,17 @@ class HIPModel:
             except Exception as ex:
                 raise RuntimeError(f"Export failed for {name}: {ex}") from ex
             results[name] = (ofile + '.nrrd') if result_dir is not None else seg
-            self.timestamps = ts
         return {name: results[name] for name in inputs}
+
+    def apply_batch(self, inputs: Union[List, Dict], result_dir: Optional[str] = None, override: bool = True) -> dict:
+        """:meth:`apply` for several inputs with ONE engine batch (the reference's ``apply`` submits every input to its worker pool before
+        it waits, ``ts2d/core/inference/nnu.py:194-216``): the stages of :meth:`_run` over all inputs, the prediction one predictor
+        batch call per fast-path group.  Inside the batched engine call the network always takes the full-batch dispatch, so an
+        input's result does not depend on the other inputs of the call.  Errors: ``"<Stage> failed for <name>: <cause>"``.
+        ``batch_timestamps[name]`` holds the stamps per input; ``timestamps`` is left at the last input's values."""
+        if self._predictor is None:
+            raise RuntimeError("model is not started")
+        if isinstance(inputs, (list, tuple)):
+            inputs = {f'image{i + 1}': img for i, img in enumerate(inputs)}
+        self.batch_timestamps = {}
+        return self._run(inputs, result_dir, override, batched=True, stamps=self.batch_timestamps)

@@ -151,36 +151,61 @@ class HIPnnUNetPredictor:
         self.engines = []
 
     # ------------------------------------------------------------------ inference
-    def predict_sliding_window_return_logits(self, data: np.ndarray, fold: int = 0) -> np.ndarray:
-        """One fold: tiles x mirror variants -> one engine batch -> upstream's fp16 Gaussian aggregation.
-        data [C,Z,H,W] float32 -> float16 [K,Z,H,W]."""
+    _INF_MESSAGE = ('Encountered inf in predicted array. Aborting... If this problem persists, reduce '
+                    'value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32')
+
+    def _sliding_window_batch(self, list_of_data, fold: int = 0, want_seg: bool = False, one_call: bool = True):
+        """One fold, N inputs [C,Z,H,W]: pad, tile, tiles x mirror variants through the engine, upstream's fp16 Gaussian aggregation
+        on the device.  Every z slice of every input is one image.  ``one_call``: all images in ONE engine call (C-ABI
+        ts2d_engine_predict_tiled_batch: the network takes the full-batch dispatch, an input's bytes do not depend on its batch-mates,
+        an error names the input); otherwise one ts2d_engine_predict_tiled call per image (size-dependent dispatch).  Returns one
+        array per input in the input's geometry: float16 [K,Z,H,W] logits, or the device-thresholded uint8 segmentation when ``want_seg``.
+        A single case is a batch of one: the single-case methods below are this method on ``[data]`` with ``one_call=False``.
+        (The one method that touches the engine, under the name the test infrastructure overrides: tests/batch_util.py replaces it, and
+        tests/host_predictor.py predict_sliding_window_return_logits, with the host restatement.)"""
         patch = tuple(self.configuration_manager.patch_size)
-        data = np.asarray(data, dtype=np.float32)
-        if data.ndim != 4:
-            raise AssertionError('input_image must be a 4D np.ndarray or torch.Tensor (c, x, y, z)')
-        padded, revert = sw.pad_nd_image(data, patch)
-        C, Z, H, W = padded.shape
-        slicers = sw.tile_slicers((H, W), patch, self.tile_step_size, Z)
+        images, tiles, owner, reverts, shapes = [], [], [], [], []
+        for i, data in enumerate(list_of_data):
+            data = np.asarray(data, dtype=np.float32)
+            if data.ndim != 4:
+                raise AssertionError('input_image must be a 4D np.ndarray or torch.Tensor (c, x, y, z)')
+            padded, revert = sw.pad_nd_image(data, patch)
+            C, Z, H, W = padded.shape
+            slicers = sw.tile_slicers((H, W), patch, self.tile_step_size, Z)
+            for d in range(Z):
+                images.append(padded[:, d])
+                tiles.append([(sx, sy) for (dd, sx, sy) in slicers if dd == d])
+                owner.append(i)
+            reverts.append(revert)
+            shapes.append((Z, H, W))
         if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
             raise AssertionError('mirror_axes does not match the dimension of the input!')
-        # gather (with mirroring), network, mirror-average and fp16 Gaussian aggregation all on the device
         g = sw.compute_gaussian(patch) if self.use_gaussian else None
-        K = self.arch.num_classes
-        logits = np.empty((K, Z, H, W), dtype=np.float16)
         axes = self.allowed_mirroring_axes if self.use_mirroring else None
-        any_inf = False
-        for d in range(Z):
-            tiles = [(sx, sy) for (dd, sx, sy) in slicers if dd == d]
-            # (Z == 1, the 2-D case: logits[:, d] is contiguous and the engine writes into it directly)
-            out16, _ = self.engines[fold].predict_tiled(padded[:, d], patch, tiles, axes, g, want_logits=True,
-                                                        out_logits=logits[:, d] if Z == 1 else None)
-            if Z != 1:
-                logits[:, d] = out16
-            any_inf = any_inf or self.engines[fold].last_tiled_inf
-        if any_inf:
-            raise RuntimeError('Encountered inf in predicted array. Aborting... If this problem persists, reduce '
-                               'value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32')
-        return logits[(slice(None),) + revert[1:]]
+        e = self.engines[fold]
+        if one_call:
+            out16, seg = e.predict_tiled_batch(images, patch, tiles, axes, g, want_logits=not want_seg, want_seg=want_seg)
+            planes, inf = (seg if want_seg else out16), e.last_tiled_inf_per_image
+        else:
+            planes, inf = [], []
+            for image, tl in zip(images, tiles):
+                out16, seg = e.predict_tiled(image, patch, tl, axes, g, want_logits=not want_seg, want_seg=want_seg)
+                planes.append(seg if want_seg else out16)
+                inf.append(e.last_tiled_inf)
+        bad = sorted({owner[j] for j, f in enumerate(inf) if f})
+        if bad:
+            raise RuntimeError((f'input {bad[0]}: ' if one_call else '') + self._INF_MESSAGE)
+        results, j = [], 0
+        for (Z, H, W), revert in zip(shapes, reverts):
+            full = np.stack(planes[j:j + Z], axis=1) if Z != 1 else planes[j][:, None]
+            j += Z
+            results.append(full[(slice(None),) + revert[1:]])
+        return results
+
+    def predict_sliding_window_return_logits(self, data: np.ndarray, fold: int = 0) -> np.ndarray:
+        """One fold: tiles x mirror variants -> one engine batch per z slice -> upstream's fp16 Gaussian aggregation.
+        data [C,Z,H,W] float32 -> float16 [K,Z,H,W]."""
+        return self._sliding_window_batch([data], fold, one_call=False)[0]
 
     def predict_segmentation_from_preprocessed_data(self, data):
         """Fast path of the product surface (not part of the reference's duck-typed seam): the multilabel segmentation
@@ -193,20 +218,7 @@ class HIPnnUNetPredictor:
         data = np.asarray(data, dtype=np.float32)
         if len(self.list_of_parameters) != 1 or len(self.engines) != 1 or data.ndim != 4 or data.shape[1] != 1:
             return None
-        patch = tuple(self.configuration_manager.patch_size)
-        padded, revert = sw.pad_nd_image(data, patch)
-        C, Z, H, W = padded.shape
-        slicers = sw.tile_slicers((H, W), patch, self.tile_step_size, Z)
-        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
-            raise AssertionError('mirror_axes does not match the dimension of the input!')
-        g = sw.compute_gaussian(patch) if self.use_gaussian else None
-        axes = self.allowed_mirroring_axes if self.use_mirroring else None
-        tiles = [(sx, sy) for (dd, sx, sy) in slicers if dd == 0]
-        _, seg = self.engines[0].predict_tiled(padded[:, 0], patch, tiles, axes, g, want_logits=False, want_seg=True)
-        if self.engines[0].last_tiled_inf:
-            raise RuntimeError('Encountered inf in predicted array. Aborting... If this problem persists, reduce '
-                               'value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32')
-        return seg[:, None][(slice(None),) + revert[1:]]
+        return self._sliding_window_batch([data], 0, want_seg=True, one_call=False)[0]
 
     def predict_logits_from_preprocessed_data(self, data):
         """Fold ensemble (upstream: sum over ``list_of_parameters`` then ``/= n``).  Accepts numpy or torch [C,1,H,W];
@@ -227,47 +239,6 @@ class HIPnnUNetPredictor:
             return pred
 
     # ------------------------------------------------------------------ batched inference (N cases, one engine batch per fold)
-    _INF_MESSAGE = ('Encountered inf in predicted array. Aborting... If this problem persists, reduce '
-                    'value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32')
-
-    def _sliding_window_batch(self, list_of_data, fold: int = 0, want_seg: bool = False):
-        """One fold, N inputs, ONE engine call (C-ABI ts2d_engine_predict_tiled_batch): every z slice of every [C,Z,H,W] input is one
-        image of the batch, padded and tiled with the helpers :meth:`predict_sliding_window_return_logits` uses.  Returns one array per
-        input in the input's geometry: float16 [K,Z,H,W] logits, or the device-thresholded uint8 segmentation when ``want_seg``.
-        Inside the call the network always takes the full-batch dispatch: an input's bytes do not depend on its batch-mates.
-        (The one method that touches the engine on the batched path: the CPU tests override it with a loop over the host restatement.)"""
-        patch = tuple(self.configuration_manager.patch_size)
-        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
-            raise AssertionError('mirror_axes does not match the dimension of the input!')
-        images, tiles, owner, reverts, shapes = [], [], [], [], []
-        for i, data in enumerate(list_of_data):
-            data = np.asarray(data, dtype=np.float32)
-            if data.ndim != 4:
-                raise AssertionError('input_image must be a 4D np.ndarray or torch.Tensor (c, x, y, z)')
-            padded, revert = sw.pad_nd_image(data, patch)
-            C, Z, H, W = padded.shape
-            slicers = sw.tile_slicers((H, W), patch, self.tile_step_size, Z)
-            for d in range(Z):
-                images.append(padded[:, d])
-                tiles.append([(sx, sy) for (dd, sx, sy) in slicers if dd == d])
-                owner.append(i)
-            reverts.append(revert)
-            shapes.append((Z, H, W))
-        g = sw.compute_gaussian(patch) if self.use_gaussian else None
-        axes = self.allowed_mirroring_axes if self.use_mirroring else None
-        e = self.engines[fold]
-        out16, seg = e.predict_tiled_batch(images, patch, tiles, axes, g, want_logits=not want_seg, want_seg=want_seg)
-        planes = seg if want_seg else out16
-        bad = sorted({owner[j] for j, f in enumerate(e.last_tiled_inf_per_image) if f})
-        if bad:
-            raise RuntimeError(f'input {bad[0]}: ' + self._INF_MESSAGE)
-        results, j = [], 0
-        for (Z, H, W), revert in zip(shapes, reverts):
-            full = np.stack(planes[j:j + Z], axis=1) if Z != 1 else planes[j][:, None]
-            j += Z
-            results.append(full[(slice(None),) + revert[1:]])
-        return results
-
     def predict_logits_from_preprocessed_data_batch(self, list_of_data):
         """:meth:`predict_logits_from_preprocessed_data` for a list of inputs: one batched engine call per fold (a [C,Z,H,W] input
         contributes Z images - a z-stack is one engine call, not Z), folds averaged as there.  Returns a list (torch CPU tensors when

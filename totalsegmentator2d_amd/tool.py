@@ -88,40 +88,55 @@ class TS2D:
             pool = self._pool = ThreadPoolExecutor(max_workers=n, thread_name_prefix='ts2d-submodel')
         return pool
 
-    def predict(self, input: Union[nrrd.Image, str], collapse: bool = False, merge: bool = True) -> "TS2D.Result":
+    @staticmethod
+    def _as_image(input) -> nrrd.Image:
         if isinstance(input, str):
             input = nrrd.read(input)
         if not isinstance(input, nrrd.Image):
             raise RuntimeError(f"input must be a string path or an image, found: {type(input).__name__}")
-        result: dict = {}
-        cache: dict = {}
+        return input
+
+    def _fan_out(self, run) -> dict:
+        """``{mid: run(mid)}`` over the sub-models - concurrently: the C-ABI's handles are independent (include/ts2d_engine.h: one
+        caller thread per engine), every engine runs on its own stream, and ctypes releases the interpreter lock for the duration of a
+        call.  On a failure the sub-models that have not started are cancelled and EVERY running one is waited for before the first
+        failure (in sub-model order) is raised: no engine is still at work on a worker thread when the caller gets control back."""
         order = sorted(self.models)
-        # input side per sub-model (projections are computed once and cached), then the networks - concurrently: the C-ABI's handles
-        # are independent (include/ts2d_engine.h: one caller thread per engine), every engine runs on its own stream, and ctypes
-        # releases the interpreter lock for the duration of a call
-        prepared = {mid: self._prepare_model_input(mid, input, cache) for mid in order}
-        if self.concurrent_models and len(order) > 1:
-            pool = self._executor(len(order))
-            futs = {mid: pool.submit(self._apply_model, mid, prepared[mid], collapse) for mid in order}
-            done = {}
-            try:
-                for mid in order:
-                    done[mid] = futs[mid].result()                       # (the first failure is raised, in sub-model order)
-            except BaseException:
-                for f in futs.values():                                  # sub-models that have not started yet are not run for a failed case
-                    f.cancel()
-                raise
-        else:
-            done = {mid: self._apply_model(mid, prepared[mid], collapse) for mid in order}
+        if not (self.concurrent_models and len(order) > 1):
+            return {mid: run(mid) for mid in order}
+        pool = self._executor(len(order))
+        futs = {mid: pool.submit(run, mid) for mid in order}
+        done, failure = {}, None
         for mid in order:
-            result.setdefault('models', {})[mid] = done[mid]
+            try:
+                done[mid] = futs[mid].result()
+            except BaseException as ex:
+                if failure is None:
+                    failure = ex
+                    for f in futs.values():
+                        f.cancel()
+        if failure is not None:
+            raise failure
+        return done
+
+    @staticmethod
+    def _result(input: nrrd.Image, cache: dict, models: dict, merge: bool) -> "TS2D.Result":
+        result: dict = {'models': models}
         if merge:
-            segs = [r['segmentation'] for _, r in sorted(result['models'].items())]
+            segs = [r['segmentation'] for _, r in sorted(models.items())]
             result['segmentation'] = segs[0] if len(segs) == 1 else combine_segmentations(segs)
         result['input'] = input
         if cache.get('projections'):
             result['projections'] = cache['projections']
         return TS2D.Result(result)
+
+    def predict(self, input: Union[nrrd.Image, str], collapse: bool = False, merge: bool = True) -> "TS2D.Result":
+        input = self._as_image(input)
+        cache: dict = {}
+        # input side per sub-model (projections are computed once and cached), then the networks
+        prepared = {mid: self._prepare_model_input(mid, input, cache) for mid in sorted(self.models)}
+        done = self._fan_out(lambda mid: self._apply_model(mid, prepared[mid], collapse))
+        return self._result(input, cache, done, merge)
 
     def predict_many(self, inputs, collapse: bool = False, merge: bool = True, max_cases: int = 8) -> List["TS2D.Result"]:
         """:meth:`predict` for several cases: per sub-model ONE engine batch over groups of at most ``max_cases`` cases
@@ -131,13 +146,7 @@ class TS2D:
         it agrees to fp32 summation order (a few float16 ulps at most on the aggregated logits: each rounding into the half buffer may flip).
         ``max_cases=8`` makes 64 network rows for the default case of 2 tiles x 4 mirror passes.  Host memory: every case of a group holds
         its K result planes of Hp x Wp bytes per sub-model until the group is exported (float16 planes where an export resamples)."""
-        images = []
-        for inp in inputs:
-            if isinstance(inp, str):
-                inp = nrrd.read(inp)
-            if not isinstance(inp, nrrd.Image):
-                raise RuntimeError(f"input must be a string path or an image, found: {type(inp).__name__}")
-            images.append(inp)
+        images = [self._as_image(inp) for inp in inputs]
         max_cases = max(1, int(max_cases))
         order = sorted(self.models)
         caches = [dict() for _ in images]
@@ -148,53 +157,32 @@ class TS2D:
             for g0 in range(0, len(images), max_cases):
                 out += self._apply_model_batch(mid, [pr[mid] for pr in prepared[g0:g0 + max_cases]], collapse, first=g0)
             return out
-        if self.concurrent_models and len(order) > 1 and images:
-            pool = self._executor(len(order))
-            futs = {mid: pool.submit(run_model, mid) for mid in order}
-            done, failure = {}, None
-            for mid in order:                                            # every running sub-model is waited for before a failure is re-raised
-                try:
-                    done[mid] = futs[mid].result()
-                except BaseException as ex:
-                    if failure is None:
-                        failure = ex
-                        for f in futs.values():
-                            f.cancel()
-            if failure is not None:
-                raise failure
-        else:
-            done = {mid: run_model(mid) for mid in order}
-        results = []
-        for i, (img, cache) in enumerate(zip(images, caches)):
-            result: dict = {}
-            for mid in order:
-                result.setdefault('models', {})[mid] = done[mid][i]
-            if merge:
-                segs = [r['segmentation'] for _, r in sorted(result['models'].items())]
-                result['segmentation'] = segs[0] if len(segs) == 1 else combine_segmentations(segs)
-            result['input'] = img
-            if cache.get('projections'):
-                result['projections'] = cache['projections']
-            results.append(TS2D.Result(result))
-        return results
+        done = self._fan_out(run_model)
+        return [self._result(img, cache, {mid: done[mid][i] for mid in order}, merge) for i, (img, cache) in enumerate(zip(images, caches))]
+
+    def _model_result(self, mid: str, prepared, collapse: bool, seg, timestamps: dict) -> dict:
+        """What one sub-model contributes to a ``Result``: the segmentation ``model.apply`` returned for ``prepared``, its 3-D geometry restored."""
+        input, input2d, native_2d = prepared
+        res = {'id': mid, 'revision': self.models[mid].revision}
+        res['model'], res['group'] = decompose_model_key(mid)
+        if not (collapse or native_2d):
+            seg = restore_dimension(seg, input)
+        res['input'] = input2d if collapse else input
+        res['segmentation'] = seg
+        res['timestamps'] = dict(timestamps)
+        return res
+
+    def _apply_model(self, mid: str, prepared, collapse: bool) -> dict:
+        """Reference tool.py:172-174: ``model.apply`` + restoring the 3-D geometry."""
+        model = self.models[mid]
+        return self._model_result(mid, prepared, collapse, model.apply(prepared[1]), model.timestamps)
 
     def _apply_model_batch(self, mid: str, prepared: list, collapse: bool, first: int = 0) -> List[dict]:
-        """:meth:`_apply_model` for a group of cases: one ``model.apply_batch`` + restoring each case's 3-D geometry."""
+        """:meth:`_apply_model` for a group of cases: one ``model.apply_batch``."""
         model = self.models[mid]
         names = [f'case{first + i + 1}' for i in range(len(prepared))]
         segs = model.apply_batch({n: pr[1] for n, pr in zip(names, prepared)})
-        out = []
-        for n, (input, input2d, native_2d) in zip(names, prepared):
-            res = {'id': mid, 'revision': model.revision}
-            res['model'], res['group'] = decompose_model_key(mid)
-            seg = segs[n]
-            if not (collapse or native_2d):
-                seg = restore_dimension(seg, input)
-            res['input'] = input2d if collapse else input
-            res['segmentation'] = seg
-            res['timestamps'] = dict(model.batch_timestamps[n])
-            out.append(res)
-        return out
+        return [self._model_result(mid, pr, collapse, segs[n], model.batch_timestamps[n]) for n, pr in zip(names, prepared)]
 
     def _predict_model(self, mid: str, input: nrrd.Image, collapse: bool, cache: dict) -> dict:
         return self._apply_model(mid, self._prepare_model_input(mid, input, cache), collapse)
@@ -237,20 +225,6 @@ class TS2D:
         import threading
         input2d.preprocess_cache = cache.setdefault('preprocessed', {'lock': threading.Lock(), 'items': {}})
         return input, input2d, native_2d
-
-    def _apply_model(self, mid: str, prepared, collapse: bool) -> dict:
-        """Reference tool.py:172-174: ``model.apply`` + restoring the 3-D geometry."""
-        model = self.models[mid]
-        input, input2d, native_2d = prepared
-        res = {'id': mid, 'revision': model.revision}
-        res['model'], res['group'] = decompose_model_key(mid)
-        seg = model.apply(input2d)
-        if not (collapse or native_2d):
-            seg = restore_dimension(seg, input)
-        res['input'] = input2d if collapse else input
-        res['segmentation'] = seg
-        res['timestamps'] = dict(model.timestamps)
-        return res
 
     class Result:
         def __init__(self, data: dict):
