@@ -272,6 +272,11 @@ const char* ts2d_engine_op_name(ts2d_engine* e, int op);
 /* The kernel that served entry `op` of the last profiled forward ("conv3x3_f16x3_q", "conv3x3_upc<64>", "finalize_stats", ...):
  * the dispatch depends on precision mode, channel counts and tile geometry, bench.py groups its roofline blocks by this. */
 const char* ts2d_engine_op_kernel(ts2d_engine* e, int op);
+/* Test accessor (ABI 9): the split-K factor entry `op` of the last profiled forward ran with - S > 1: the conv wrote S fp32 partial
+ * sums that the entry "<name>.stats" behind it reduced; 1: it did not split (every ".stats" entry, every kernel without a split-K
+ * form).  0: no such entry - an op that was composed into its consumer launches nothing and has none.  The factor depends on the
+ * batch size and the CU count (option "sbk"), so a test that means to address the split-K arithmetic asserts it here first. */
+int ts2d_engine_op_ksplit(ts2d_engine* e, int op);
 int ts2d_engine_op_times(ts2d_engine* e, float* ms, int n_ops);
 
 /* Test/debug accessor (not on the product path): copies activation tensor `name` ("enc0.c1", "dec3.up", ... - the

@@ -41,7 +41,7 @@ def _h(t):
     return t.to(torch.float16).to(torch.float32)
 
 
-def conv_block(x, w, b, g, be, stride, eps=1e-5, slope=0.01, emulate=None, round_w=True, storage_view=False):
+def conv_block(x, w, b, g, be, stride, eps=1e-5, slope=0.01, emulate=None, round_w=True, storage_view=False, dtype=None):
     """``ConvDropoutNormReLU``: Conv2d(3x3, pad 1, stride = int or (sy, sx)) -> InstanceNorm2d(affine, eps, biased var) -> LeakyReLU.
 
     ``emulate='f16'`` restates the arithmetic CONTRACT of the engine's 16-bit mode (include/ts2d_engine.h, TS2D_PRECISION_F16; to first
@@ -52,7 +52,12 @@ def conv_block(x, w, b, g, be, stride, eps=1e-5, slope=0.01, emulate=None, round
     block, which the engine computes from the fp32 network input with fp32 weights (exact fp32 MFMA) and only stores as fp16.
     ``storage_view=True``: the block's output as the engine's debug accessor shows it - the STORED fp16 conv output normalised and
     activated in fp32, without the operand rounding of the consumer - so that a per-layer comparison is not blurred by half an fp16
-    ulp on every element."""
+    ulp on every element.
+    ``dtype=torch.float64`` (without ``emulate``): the same block evaluated in double precision from the given fp32 values, returned as
+    float64 - a reference whose own rounding is not part of a per-layer bound."""
+    if dtype is not None:
+        assert emulate is None, 'dtype is for the fp32-contract modes; the 16-bit emulation defines its own roundings'
+        x, w, b, g, be = (t.to(dtype) for t in (x, w, b, g, be))
     if emulate is None:
         y = F.conv2d(x, w, b, stride=stride, padding=1)
         y = F.instance_norm(y, None, None, g, be, use_input_stats=True, momentum=0.1, eps=eps)
@@ -106,15 +111,20 @@ def unet_forward(arch, sd: Dict[str, np.ndarray], x, return_intermediates: bool 
     return (x, inter) if return_intermediates else x
 
 
-def layer_forward(arch, sd: Dict[str, np.ndarray], name: str, src, skip=None, emulate=None, storage_view=False):
+def layer_forward(arch, sd: Dict[str, np.ndarray], name: str, src, skip=None, emulate=None, storage_view=False, dtype=None):
     """ONE block of :func:`unet_forward` in isolation, from the activated tensors it reads (as torch holds them after the previous
     block): ``encS.cI`` / ``decL.cI`` (I > 0) from ``src``; ``decL.c0`` from ``src`` = the COARSE tensor the transposed conv reads and
     ``skip`` (transpconv -> cat((up, skip), 1) -> conv block); ``head`` from ``src``.  Per-layer parity tests feed it the engine's own
     inputs of that layer, so that an error cannot hide behind the accumulated difference of the layers in front of it.
     With ``emulate='f16'`` the given inputs are rounded to fp16 first (the operand rounding of the consumer);
-    ``storage_view``: see :func:`conv_block`."""
+    ``storage_view``: see :func:`conv_block`.  ``dtype=torch.float64`` (split / exact mode only): every operation of the block in
+    double precision, result float64."""
     sd = {k: _t(v) for k, v in sd.items()}
     x = _t(src).to(torch.float32)
+    if dtype is not None:
+        assert emulate is None, 'dtype is for the fp32-contract modes'
+        sd = {k: v.to(dtype) for k, v in sd.items()}
+        x = x.to(dtype)
     f16 = emulate == 'f16'
     if f16 and name != 'enc0.c0':
         # the engine's debug accessor returns activations BEFORE the consumer's operand rounding: round them here (a no-op for
@@ -140,9 +150,9 @@ def layer_forward(arch, sd: Dict[str, np.ndarray], name: str, src, skip=None, em
                 kt = f'decoder.transpconvs.{j}'
                 up = F.conv_transpose2d(x, _h(sd[f'{kt}.weight']) if f16 else sd[f'{kt}.weight'], sd[f'{kt}.bias'],
                                         stride=tuple(arch.strides[lvl + 1]))
-                x = torch.cat((_h(up) if f16 else up, _t(skip).to(torch.float32)), 1)
+                x = torch.cat((_h(up) if f16 else up, _t(skip).to(x.dtype)), 1)
         return conv_block(x, sd[f'{k}.conv.weight'], sd[f'{k}.conv.bias'], sd[f'{k}.norm.weight'], sd[f'{k}.norm.bias'],
-                          stride, arch.norm_eps, arch.leaky_slope, emulate=emulate, round_w=rw, storage_view=storage_view)
+                          stride, arch.norm_eps, arch.leaky_slope, emulate=emulate, round_w=rw, storage_view=storage_view, dtype=dtype)
 
 
 # ----------------------------------------------------------------------------- A7

@@ -207,7 +207,7 @@ def test_tiled_image_binding_matches_the_header_layout():
     assert ctypes.sizeof(_lib.TiledImage) == (off + 7) // 8 * 8 == 64
     assert [f[0] for f in _lib.TiledImage._fields_] == [n for n, _ in fields]
     lib = _lib.load()
-    assert 'ts2d_engine_predict_tiled_batch' in _lib.SYMBOLS and lib.ts2d_abi_version() == _lib.ABI_VERSION == 8
+    assert 'ts2d_engine_predict_tiled_batch' in _lib.SYMBOLS and lib.ts2d_abi_version() == _lib.ABI_VERSION == 9
     desc = (_lib.TiledImage * 1)()
     assert lib.ts2d_engine_predict_tiled_batch(None, desc, 1, 64, 64, 0, None) == -1
     assert 'null engine' in _lib.last_error()

@@ -238,3 +238,39 @@ def test_preprocessor_properties_carry_the_sitk_geometry():
     assert props['spacing'] == (999.0, img.spacing[1], img.spacing[0])            # nnU-Net order beside it
     _, p2 = preprocess.image_to_array(img)
     assert p2['sitk_stuff']['direction'] == tuple(img.direction) and p2['sitk_stuff']['files'] == []
+
+
+@pytest.mark.parametrize('name', ['k_two3', 'xr_1ch', 'aniso_21'])
+def test_float64_layer_oracle_agrees_with_the_float32_one(name):
+    """``layer_forward(dtype=torch.float64)`` (the reference of the per-layer GPU checks, tests/layer_check.py) is the same block as the
+    fp32 one: fed with the fp32 oracle's own intermediates it reproduces every block of ``unet_forward`` to fp32 rounding, returns
+    float64, and tests/layer_check.py names the right inputs for every op (a wrong source would be off by O(1))."""
+    import torch
+    from tests import layer_check as LC
+    arch, B, H, W, seed = cases.SMALL_CASES[name]
+    sd, _ = blob_for(arch, seed)
+    x = cases.make_input(arch, B, H, W, seed)
+    _, inter = O.unet_forward(arch, sd, x, return_intermediates=True)
+    _, inter16 = O.unet_forward(arch, sd, x, return_intermediates=True, emulate='f16')
+    for n, want in inter.items():
+        if n == 'enc0.c0':
+            continue
+        srcs = [inter[s].numpy() for s in LC.op_sources(arch, n)]
+        got = LC.reference_block(arch, sd, n, srcs, 'split')
+        assert got.dtype == np.float64 and got.shape == tuple(want.shape), n
+        scale = max(1.0, float(want.abs().max()))
+        assert np.abs(got - want.numpy()).max() <= 2e-5 * scale, n
+        if not n.endswith('.up'):
+            w64 = O.layer_forward(arch, sd, n, *srcs, dtype=torch.float64)
+            w32 = O.layer_forward(arch, sd, n, *srcs)
+            assert w64.dtype == torch.float64 and w32.dtype == torch.float32 and np.array_equal(w64.numpy(), got)
+            assert float((w64 - w32.double()).abs().max()) <= 2e-5
+        ok, worst, text = LC.layer_error(n, want.numpy(), got, 'split')
+        assert ok or n.endswith('.up'), text                  # (the fp32 oracle itself lies within the split-mode bound of the fp64 block)
+    with pytest.raises(AssertionError):
+        O.layer_forward(arch, sd, 'enc1.c0', inter['enc0.c1'].numpy(), emulate='f16', dtype=torch.float64)
+    # the 16-bit reference block: identical to the 16-bit oracle's own intermediates wherever the storage view is the stored value
+    for n, want in inter16.items():
+        if n.endswith('.up'):
+            srcs = [inter16[s].numpy() for s in LC.op_sources(arch, n)]
+            assert np.array_equal(LC.reference_block(arch, sd, n, srcs, 'f16'), want.numpy().astype(np.float64)), n

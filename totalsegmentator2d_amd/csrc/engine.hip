@@ -65,6 +65,7 @@ struct Tensor {            // an activation tensor of the program (NHWC fp32)
     int ly = 0, lx = 0;    // log2 of the cumulative stride along H / W: extent (H >> ly, W >> lx) (per-axis strides, ABI 7)
     bool normed = false;   // raw conv output that carries InstanceNorm scale/shift
     float* data = nullptr; float* scale = nullptr; float* shift = nullptr;
+    size_t bytes = 0;      // of its buffer in the workspace plan (0: none)
     bool resident = false; // its buffer still holds the values of the last run (no later tensor of the run was placed on it)
 };
 
@@ -103,7 +104,7 @@ struct Op {
     size_t dev_wraw = 0;
 };
 
-struct Launch { std::string name, kernel; hipEvent_t e0 = nullptr, e1 = nullptr; };
+struct Launch { std::string name, kernel; int ksplit = 1; hipEvent_t e0 = nullptr, e1 = nullptr; };
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: one process may drive engines on several GPUs
 // (include/ts2d_engine.h: handles are independent), so the "already set" state is a bit per device, not one flag per process.
@@ -1231,11 +1232,11 @@ size_t part_floats_needed(const ts2d_engine* e, int B, int H, int W, bool full) 
 // simulating the program.  Canonical net: 340 -> ~110 MB per slice.  A composed decoder entry (kernels_upc.h) reads the COARSE tensor
 // and never materialises `decN.up`, so the plan depends on the precision mode - it is remade when that changes.
 // keep_activations: no reuse (every tensor keeps its own buffer for ts2d_engine_debug_tensor / the non-finite diagnosis).
-struct ActPlan { std::vector<size_t> off; std::vector<char> used, reused; size_t bytes = 0; };
+struct ActPlan { std::vector<size_t> off, size; std::vector<char> used, reused; size_t bytes = 0; };
 
 ActPlan plan_activations(const ts2d_engine* e, int B, int H, int W, bool keep, bool full) {
     const size_t nt = e->tensors.size(), no = e->ops.size();
-    ActPlan p; p.off.assign(nt, 0); p.used.assign(nt, 0); p.reused.assign(nt, 0);
+    ActPlan p; p.off.assign(nt, 0); p.size.assign(nt, 0); p.used.assign(nt, 0); p.reused.assign(nt, 0);
     auto bytes_of = [&](size_t t) { const Tensor& x = e->tensors[t]; return align_up((size_t)B * (H >> x.ly) * (W >> x.lx) * x.C * sizeof(float), 256); };
     // which ops run, what they read
     std::vector<char> skipped(no, 0);
@@ -1271,14 +1272,25 @@ ActPlan plan_activations(const ts2d_engine* e, int B, int H, int W, bool keep, b
         if (k > 0 && freel[k - 1].off + freel[k - 1].size == freel[k].off) { freel[k - 1].size += freel[k].size; freel.erase(freel.begin() + k); }
     };
     std::vector<std::pair<size_t, size_t>> live(nt, {0, 0});
-    if (!e->ops[0].first_direct) { bool r; p.off[0] = alloc(bytes_of(0), r); p.used[0] = 1; live[0] = {p.off[0], bytes_of(0)}; }
+    if (!e->ops[0].first_direct) { bool r; p.off[0] = alloc(bytes_of(0), r); p.size[0] = bytes_of(0); p.used[0] = 1; live[0] = {p.off[0], bytes_of(0)}; }
     for (size_t i = 0; i < no; ++i) {
-        if (skipped[i]) continue;
+        if (skipped[i]) {
+            // keep_activations: a smaller batch inside this workspace may run the entry as two kernels ("sbk", composed_kernel) - its upsampled
+            // tensor then gets a buffer of its own instead of the one shared scratch region, so that it is still there after the run
+            // (ts2d_engine_debug_tensor, the non-finite diagnosis).  The two-kernel rule bounds the tensor by the scratch region's size.
+            if (keep && e->use_sbk) {
+                const Op& op = e->ops[i];
+                const size_t sz = std::min(bytes_of(op.dst), align_up(kSbkElems / 2 * sizeof(float), 256));
+                bool r = false;
+                p.off[op.dst] = alloc(sz, r); p.size[op.dst] = sz; p.used[op.dst] = 1; live[op.dst] = {p.off[op.dst], sz};
+            }
+            continue;
+        }
         const Op& op = e->ops[i];
         if (fused0 && i == 0) continue;                      // statistics only: no output tensor
         if (op.dst >= 0) {                                   // the output is placed while the inputs are still allocated: never on top of them
             bool r = false;
-            p.off[op.dst] = alloc(bytes_of(op.dst), r); p.used[op.dst] = 1; live[op.dst] = {p.off[op.dst], bytes_of(op.dst)};
+            p.off[op.dst] = alloc(bytes_of(op.dst), r); p.size[op.dst] = bytes_of(op.dst); p.used[op.dst] = 1; live[op.dst] = {p.off[op.dst], bytes_of(op.dst)};
             if (last[op.dst] < 0 && !keep) release(live[op.dst].first, live[op.dst].second);       // (never read: e.g. a net whose last tensor feeds nothing)
         }
         if (!keep)
@@ -1290,7 +1302,7 @@ ActPlan plan_activations(const ts2d_engine* e, int B, int H, int W, bool keep, b
         for (size_t b2 = 0; b2 < nt; ++b2) {
             if (!p.used[b2] || a == b2) continue;
             const bool later = b2 > a;                       // tensors are numbered in program order of their producers
-            if (later && p.off[b2] < p.off[a] + bytes_of(a) && p.off[a] < p.off[b2] + bytes_of(b2)) p.reused[a] = 1;
+            if (later && p.off[b2] < p.off[a] + p.size[a] && p.off[a] < p.off[b2] + p.size[b2]) p.reused[a] = 1;
         }
     }
     p.bytes = top;
@@ -1350,6 +1362,7 @@ int ensure_workspace(ts2d_engine* e, int B, int H, int W, bool full) {
         Tensor& t = e->tensors[i];
         t.data = L.plan.used[i] ? reinterpret_cast<float*>(e->d_ws + L.plan.off[i]) : nullptr;
         t.resident = L.plan.used[i] && !L.plan.reused[i];
+        t.bytes = L.plan.used[i] ? L.plan.size[i] : 0;
         t.scale = t.normed ? reinterpret_cast<float*>(e->d_ws + L.o_sc[i]) : nullptr;
         t.shift = t.normed ? reinterpret_cast<float*>(e->d_ws + L.o_sh[i]) : nullptr;
     }
@@ -1390,12 +1403,17 @@ int prof_begin(ts2d_engine* e, const std::string& name, hipStream_t st) {
     }
     e->launches[e->n_launched].name = name;
     e->launches[e->n_launched].kernel.clear();
+    e->launches[e->n_launched].ksplit = 1;
     HIP_TRY(hipEventRecord(e->launches[e->n_launched].e0, st));
     return TS2D_OK;
 }
 // which kernel served the op being profiled (ts2d_engine_op_kernel): called between prof_begin and prof_end
 void prof_kernel(ts2d_engine* e, const std::string& kernel) {
     if (e->profiling && e->n_launched < e->launches.size()) e->launches[e->n_launched].kernel = kernel;
+}
+// ... and the split-K factor it ran with (ts2d_engine_op_ksplit)
+void prof_ksplit(ts2d_engine* e, int ksplit) {
+    if (e->profiling && e->n_launched < e->launches.size()) e->launches[e->n_launched].ksplit = ksplit;
 }
 int prof_end(ts2d_engine* e, hipStream_t st) {
     if (!e->profiling) return TS2D_OK;
@@ -1487,7 +1505,11 @@ int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, flo
         const Op& op = e->ops[oi];
         if (op.type != OP_CONVT || plan[oi].k == K_FUSED_AWAY) continue;
         Tensor& t = e->tensors[op.dst];
-        if (t.data != nullptr && t.data != e->d_up) continue;
+        if (t.data != nullptr && t.data != e->d_up) {
+            if ((size_t)B * (H >> t.ly) * (W >> t.lx) * t.C * sizeof(float) > t.bytes)
+                return fail(TS2D_ERR_STATE, "internal: op %s writes more than its buffer in the workspace plan holds", op.name.c_str());
+            continue;
+        }
         if (!e->d_up || (size_t)B * (H >> t.ly) * (W >> t.lx) * t.C > kSbkElems / 2)
             return fail(TS2D_ERR_STATE, "internal: op %s has no output buffer in the workspace plan", op.name.c_str());
         t.data = e->d_up; t.resident = false;
@@ -1814,6 +1836,7 @@ int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, flo
                 if (c.ksplit > 1) {
                     ca.ksplit = c.ksplit; ca.kslice_stride = (long long)B * Ht * Wt * op.cout;
                     ca.dst = e->d_partial; ca.part = nullptr;
+                    prof_ksplit(e, c.ksplit);
                 }
                 if (smem > 160 * 1024) return fail(TS2D_ERR_INVALID, "op %s: LDS tile of %zu bytes exceeds 160 KiB", op.name.c_str(), smem);
                 if (c.k == K_S1_ONE) {     // tile inside one image: lean staging path
@@ -1883,7 +1906,7 @@ int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, flo
 // ------------------------------------------------------------------------------------------------- C-ABI
 extern "C" {
 
-int ts2d_abi_version(void) { return 8; }
+int ts2d_abi_version(void) { return 9; }
 
 const char* ts2d_last_error(void) { return g_err.c_str(); }
 
@@ -2018,7 +2041,7 @@ int ts2d_engine_set_workspace(ts2d_engine* e, void* dev_ptr, size_t n_bytes) {
     if (e->d_ws && !e->ws_external) HIP_TRY(hipFree(e->d_ws));
     e->d_ws = reinterpret_cast<char*>(dev_ptr); e->ws_bytes = dev_ptr ? n_bytes : 0; e->ws_external = dev_ptr != nullptr;
     e->ws_precision = -1; e->wsB = 0;           // re-plan inside the new memory at the next reserve / forward
-    for (Tensor& t : e->tensors) { t.data = nullptr; t.resident = false; }
+    for (Tensor& t : e->tensors) { t.data = nullptr; t.bytes = 0; t.resident = false; }
     e->lastB = 0;
     return TS2D_OK;
 }
@@ -2261,9 +2284,10 @@ int ts2d_engine_check(ts2d_engine* e) {
             e->use_fuse0 = false; ++e->opt_gen;      // (the first block as its own kernel: its output can be scanned and named)
             hipStream_t st = e->last_stream ? e->last_stream : e->stream;
             const bool prof = e->profiling; e->profiling = false;
+            const size_t n_launched = e->n_launched;      // (the launch table keeps describing the caller's run: ts2d_engine_op_kernel / _op_ksplit after the error)
             if (ensure_workspace(e, B, H, W, e->last_full) != TS2D_OK || run_forward(e, d_copy, B, H, W, nullptr, nullptr, st, false, e->last_full) != TS2D_OK ||
                 hipStreamSynchronize(st) != hipSuccess) { /* keep the generic message */ }
-            e->profiling = prof;
+            e->profiling = prof; e->n_launched = n_launched;
             e->use_fuse0 = was_fuse0; ++e->opt_gen;
             e->last_input = nullptr;
         }
@@ -2286,7 +2310,7 @@ int ts2d_engine_check(ts2d_engine* e) {
         if (e->ws_busy) { (void)hipEventSynchronize(e->ws_event); e->ws_busy = false; }
         if (e->d_ws && !e->ws_external) { (void)hipFree(e->d_ws); e->d_ws = nullptr; e->ws_bytes = 0; }
         e->ws_precision = -1;     // (re-plan at the next forward)
-        for (Tensor& t : e->tensors) { t.data = nullptr; t.resident = false; }
+        for (Tensor& t : e->tensors) { t.data = nullptr; t.bytes = 0; t.resident = false; }
         e->lastB = 0;             // (nothing of that run is readable any more)
     }
     e->keep_activations = was_keep;
@@ -2400,6 +2424,11 @@ int ts2d_engine_num_ops(ts2d_engine* e) { return e ? (int)e->n_launched : 0; }
 const char* ts2d_engine_op_kernel(ts2d_engine* e, int op) {
     if (!e || op < 0 || (size_t)op >= e->n_launched) return "";
     return e->launches[op].kernel.c_str();
+}
+
+int ts2d_engine_op_ksplit(ts2d_engine* e, int op) {
+    if (!e || op < 0 || (size_t)op >= e->n_launched) return 0;
+    return e->launches[op].ksplit;
 }
 
 const char* ts2d_engine_op_name(ts2d_engine* e, int op) {

@@ -304,6 +304,11 @@ class Engine:
         n = self.lib.ts2d_engine_num_ops(self._h)
         return {self.lib.ts2d_engine_op_name(self._h, i).decode(): self.lib.ts2d_engine_op_kernel(self._h, i).decode() for i in range(n)}
 
+    def op_ksplit(self) -> dict:
+        """op name -> split-K factor it ran with in the last profiled forward (1: no split; an op composed into its consumer has no entry)."""
+        n = self.lib.ts2d_engine_num_ops(self._h)
+        return {self.lib.ts2d_engine_op_name(self._h, i).decode(): int(self.lib.ts2d_engine_op_ksplit(self._h, i)) for i in range(n)}
+
     def debug_tensor(self, name: str, capacity: int = 1 << 26) -> np.ndarray:
         """Test accessor: activation `name` of the last forward as torch would hold it (NCHW, norm+act applied).  Activations
         share buffers by liveness: the first call switches the engine to private buffers and runs the last forward again - on the
