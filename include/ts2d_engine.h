@@ -193,6 +193,44 @@ typedef struct {
 int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int patch_h, int patch_w,
                                     int mirror_mask, const uint16_t* gaussian_f16);
 
+/* The sliding window of ts2d_engine_predict_tiled_batch followed, on the device, by the export's resample-back and threshold.  Replaces
+ * `export_prediction_from_logits` (reference call site ts2d/core/inference/prediction_worker.py:215-221) up to the crop-insert: nnU-Net
+ * resamples the logits of a case whose spacing is not the plan's back to the extent the case had before preprocessing
+ * (`resampling_fn_probabilities`: skimage resize, order 1, mode 'edge', per plane for the 2-D configurations) and thresholds them
+ * (multilabel: sigmoid(float(logit)) > 0.5).  Here one kernel (csrc/kernels_resample.h) does both where the aggregation left the half
+ * logits, so K uint8 planes of the ORIGINAL extent travel to the host instead of K float16 planes of the network's extent that the host
+ * widens, interpolates and thresholds.
+ *   exports        n_images descriptors, one per image.  (src_y, src_x, src_h, src_w): the rectangle of the aggregated [K, Hp, Wp] logits
+ *                  that is the prediction - what pad_nd_image's revert slices cut out; (out_h, out_w): the extent after resampling
+ *                  (`shape_after_cropping_and_before_resampling`, in plane).  seg_u8 [K, out_h, out_w]: float32(value) > 1.5 * 2^-24, the
+ *                  predicate of seg_u8 in ts2d_engine_predict_tiled; logits_f32 [K, out_h, out_w]: the resampled logits themselves.  At least
+ *                  one of the two is non-NULL.  Arithmetic: per axis cc = (o + 0.5) * (n_in / n_out) - 0.5, i0 = floor(cc), w1 = cc - i0,
+ *                  w0 = 1 - w1 in float64 on the host, the two indices i0 and i0 + 1 clamped to [0, n_in - 1] (not the coordinate); per
+ *                  pixel (((a00*wy0)*wx0 + (a01*wy0)*wx1) + (a10*wy1)*wx0) + (a11*wy1)*wx1 in float64 without FMA, ONE rounding to
+ *                  float32 - bit for bit what scipy's zoom(order=1, mode='nearest', grid_mode=True) returns (skimage's resize calls it),
+ *                  +-inf samples included; restated in numpy as totalsegmentator2d_amd.preprocess.resize_linear_f64.  With out extent
+ *                  == src extent the taps degenerate to weights 1 / 0 and seg_u8 equals the un-resampled seg_u8 of the rectangle.
+ *   images         as in ts2d_engine_predict_tiled_batch, except that logits_f16 and seg_u8 of an image may both be NULL: the half
+ *                  buffer then lives in the scratch only.  inf_flag is written as there.
+ *   full_batch     0: the size-dependent dispatch of ts2d_engine_predict_tiled; nonzero: the full-batch dispatch and with it the
+ *                  determinism rule of ts2d_engine_predict_tiled_batch (an image's bytes do not depend on its batch-mates).
+ * Every argument is validated before any device work, the image named in the message (an empty source rectangle or one that leaves
+ * the image, a non-positive output extent, both export outputs NULL, 2^31 or more output elements, 2^26 or more output rows + columns
+ * in one call); nothing is written then.
+ * Device scratch: that of ts2d_engine_predict_tiled_batch (the half outputs always) plus, summed over the images,
+ * K x out_h x out_w bytes (x 5 with logits_f32 asked for) and 24 bytes per output row and column (the tap tables) + 40 per image.
+ * Synchronous: ONE stream synchronise per call, then ts2d_engine_check.  n_images == 0 returns TS2D_OK and does nothing.
+ * (Added under ABI 9: new symbols only, no existing signature or structure changes, so ts2d_abi_version() stays 9.) */
+typedef struct {
+    int32_t  src_y, src_x, src_h, src_w;   /* rectangle of the aggregated [K, Hp, Wp] logits that is the prediction (un-padded) */
+    int32_t  out_h, out_w;                 /* extent after resampling back */
+    uint8_t* seg_u8;                       /* host [K, out_h, out_w], or NULL */
+    float*   logits_f32;                   /* host [K, out_h, out_w], or NULL */
+} ts2d_tiled_export;
+
+int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images,
+                                     int patch_h, int patch_w, int mirror_mask, const uint16_t* gaussian_f16, int full_batch);
+
 /* Blend order of ts2d_engine_predict_tiled (upstream `prediction *= gaussian; predicted_logits[sl] += prediction` with
  * float16 `predicted_logits`; reached from ts2d/core/inference/prediction_worker.py:209):
  *   TS2D_TILE_F32 (default) the reference's CPU path (nnu.py:161-163: device=cpu when torch.cuda.is_available() is false - no autocast): the tile prediction is
@@ -211,7 +249,7 @@ int ts2d_engine_set_tile_dtype(ts2d_engine* e, int mode);
  * forward does: ts2d/core/inference/prediction_worker.py:209.) */
 int ts2d_engine_set_keep_activations(ts2d_engine* e, int enable);
 
-/* 1 if the last ts2d_engine_predict_tiled / ts2d_engine_predict_tiled_batch call (the OR over its images) produced an infinite
+/* 1 if the last ts2d_engine_predict_tiled / ts2d_engine_predict_tiled_batch / ts2d_engine_predict_tiled_export call (the OR over its images) produced an infinite
  * aggregated float16 logit - upstream's
  * "Encountered inf in predicted array" check of predict_sliding_window_return_logits (reached from
  * ts2d/core/inference/prediction_worker.py:209), evaluated on the device instead of a host pass over the array. */

@@ -20,7 +20,7 @@ PRECISION_F16 = 2
 
 # every symbol include/ts2d_engine.h declares
 SYMBOLS = ('ts2d_engine_create', 'ts2d_engine_load_weights', 'ts2d_engine_weight_buffer', 'ts2d_engine_weights_ready',
-           'ts2d_engine_forward', 'ts2d_engine_check', 'ts2d_engine_predict_tiled', 'ts2d_engine_predict_tiled_batch', 'ts2d_engine_tiled_inf_flag', 'ts2d_engine_set_tile_dtype', 'ts2d_engine_set_keep_activations', 'ts2d_project_coronal', 'ts2d_project_coronal_zscore', 'ts2d_synth_slices', 'ts2d_engine_reserve', 'ts2d_engine_workspace_bytes', 'ts2d_engine_set_workspace', 'ts2d_engine_set_precision', 'ts2d_engine_set_option', 'ts2d_engine_set_profiling', 'ts2d_engine_num_ops',
+           'ts2d_engine_forward', 'ts2d_engine_check', 'ts2d_engine_predict_tiled', 'ts2d_engine_predict_tiled_batch', 'ts2d_engine_predict_tiled_export', 'ts2d_engine_tiled_inf_flag', 'ts2d_engine_set_tile_dtype', 'ts2d_engine_set_keep_activations', 'ts2d_project_coronal', 'ts2d_project_coronal_zscore', 'ts2d_synth_slices', 'ts2d_engine_reserve', 'ts2d_engine_workspace_bytes', 'ts2d_engine_set_workspace', 'ts2d_engine_set_precision', 'ts2d_engine_set_option', 'ts2d_engine_set_profiling', 'ts2d_engine_num_ops',
            'ts2d_engine_op_name', 'ts2d_engine_op_kernel', 'ts2d_engine_op_ksplit', 'ts2d_engine_op_times', 'ts2d_engine_debug_tensor', 'ts2d_engine_device_bytes', 'ts2d_engine_destroy',
            'ts2d_last_error', 'ts2d_abi_version')
 
@@ -38,6 +38,12 @@ class TiledImage(ctypes.Structure):
     _fields_ = [('image', ctypes.c_void_p), ('Hp', ctypes.c_int32), ('Wp', ctypes.c_int32), ('n_tiles', ctypes.c_int32),
                 ('tile_y', ctypes.c_void_p), ('tile_x', ctypes.c_void_p), ('logits_f16', ctypes.c_void_p), ('seg_u8', ctypes.c_void_p),
                 ('inf_flag', ctypes.c_int32)]
+
+
+class TiledExport(ctypes.Structure):
+    """``ts2d_tiled_export``: the resample-back of one image of ``ts2d_engine_predict_tiled_export``."""
+    _fields_ = [('src_y', ctypes.c_int32), ('src_x', ctypes.c_int32), ('src_h', ctypes.c_int32), ('src_w', ctypes.c_int32),
+                ('out_h', ctypes.c_int32), ('out_w', ctypes.c_int32), ('seg_u8', ctypes.c_void_p), ('logits_f32', ctypes.c_void_p)]
 
 
 class EngineLibraryError(RuntimeError):
@@ -92,6 +98,9 @@ def load():
                                               c.c_int, c.c_void_p, c.c_void_p, c.c_void_p]
     lib.ts2d_engine_predict_tiled_batch.restype = c.c_int
     lib.ts2d_engine_predict_tiled_batch.argtypes = [c.c_void_p, c.POINTER(TiledImage), c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p]
+    lib.ts2d_engine_predict_tiled_export.restype = c.c_int
+    lib.ts2d_engine_predict_tiled_export.argtypes = [c.c_void_p, c.POINTER(TiledImage), c.POINTER(TiledExport), c.c_int, c.c_int, c.c_int, c.c_int,
+                                                     c.c_void_p, c.c_int]
     lib.ts2d_project_coronal.restype = c.c_int
     lib.ts2d_project_coronal.argtypes = [c.c_int, c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.c_int, c.c_longlong, c.c_longlong,
                                          c.c_longlong, c.c_longlong, c.c_void_p, c.c_void_p]

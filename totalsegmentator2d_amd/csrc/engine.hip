@@ -18,6 +18,7 @@
 #include "kernels_upc_h.h"
 #include "kernels_upc_h2.h"
 #include "kernels_sw.h"
+#include "kernels_resample.h"
 #include "kernels_project.h"
 
 #include <atomic>
@@ -2073,11 +2074,30 @@ int ts2d_engine_forward(ts2d_engine* e, const float* input, int B, int H, int W,
 // one sw_aggregate, then every device-to-host copy, ONE stream synchronise and the result check.
 // `full` is the whole difference between the entries' results: the batch entry asks for the full-batch dispatch (a row's bits must not
 // depend on its batch-mates), the single-image entry for the size-dependent one.  `name_images`: a message names the image it is about.
+// `exports` (ts2d_engine_predict_tiled_export; else null): one descriptor per image - behind the last aggregate ONE sw_resample_threshold
+// launch resamples every image's half logits to its export extent where they lie in the scratch.
 constexpr int kSwChunkRows = 64;
 
-static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
-                              const uint16_t* gaussian_f16, bool full, bool name_images) {
-    const char* entry = name_images ? "ts2d_engine_predict_tiled_batch" : "ts2d_engine_predict_tiled";
+// Taps of one axis of the order-1 resample (n_in -> n_out samples; preprocess.linear_axis_taps is the same statement in numpy, pinned
+// to scipy): cc = (o + 0.5) * (n_in / n_out) - 0.5, i0 = floor(cc), w1 = cc - i0, all in float64; the coordinate is not clamped, the
+// two INDICES are (scipy extends the array by its edge samples).  `origin` shifts the indices to the padded plane.
+// No contraction: a fused (o + 0.5) * zoom - 0.5 would round differently from numpy on a host build that has FMA (-march=native).
+static void rs_axis_taps(int n_in, int n_out, int origin, RsTap* t) {
+#pragma clang fp contract(off)
+    const double zoom = (double)n_in / (double)n_out;
+    for (int o = 0; o < n_out; ++o) {
+        const double prod = ((double)o + 0.5) * zoom;
+        const double cc = prod - 0.5;
+        const double f = std::floor(cc);
+        const long long i0 = (long long)f;
+        t[o].w1 = cc - f; t[o].w0 = 1.0 - t[o].w1;
+        t[o].i0 = origin + (int)std::min<long long>(std::max<long long>(i0, 0), n_in - 1);
+        t[o].i1 = origin + (int)std::min<long long>(std::max<long long>(i0 + 1, 0), n_in - 1);
+    }
+}
+
+static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
+                              int mirror_mask, const uint16_t* gaussian_f16, bool full, bool name_images, const char* entry) {
     if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "%s: bad patch %dx%d", entry, ph, pw);
     const int C = e->arch.input_channels, K = e->arch.num_classes;
     int vflip[4] = {0, 0, 0, 0}, V = 1;
@@ -2085,14 +2105,14 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, int n_im
     else if (mirror_mask & 1) { vflip[1] = 1; V = 2; }
     else if (mirror_mask & 2) { vflip[1] = 2; V = 2; }
     const int vflips = vflip[0] | (vflip[1] << 8) | (vflip[2] << 16) | (vflip[3] << 24);
-    long long n_tiles_all = 0;
-    bool any16 = false, anyseg = false;
+    long long n_tiles_all = 0, n_taps_all = 0;
+    bool any16 = false, anyseg = false, any_rs8 = false, any_rs32 = false;
     for (int i = 0; i < n_images; ++i) {
         const ts2d_tiled_image& im = images[i];
         char pre[24] = "";
         if (name_images) snprintf(pre, sizeof(pre), "image %d: ", i);
         if (!im.image || !im.tile_y || !im.tile_x) return fail(TS2D_ERR_INVALID, "%snull image or tile pointer", pre);
-        if (!im.logits_f16 && !im.seg_u8) return fail(TS2D_ERR_INVALID, "%sboth outputs are null", pre);
+        if (!exports && !im.logits_f16 && !im.seg_u8) return fail(TS2D_ERR_INVALID, "%sboth outputs are null", pre);
         if (im.n_tiles < 1 || im.n_tiles > (1 << 20) || im.Hp < 1 || im.Wp < 1 || ph > im.Hp || pw > im.Wp)
             return fail(TS2D_ERR_INVALID, "%sbad tiling: %d tiles of %dx%d on %dx%d", pre, im.n_tiles, ph, pw, im.Hp, im.Wp);
         if ((long long)K * im.Hp * im.Wp >= (1LL << 31) || (long long)C * im.Hp * im.Wp >= (1LL << 31))
@@ -2102,6 +2122,18 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, int n_im
                 return fail(TS2D_ERR_INVALID, "%stile %d at (%d,%d) leaves the %dx%d image", pre, t, im.tile_y[t], im.tile_x[t], im.Hp, im.Wp);
         n_tiles_all += im.n_tiles;
         any16 |= im.logits_f16 != nullptr; anyseg |= im.seg_u8 != nullptr;
+        if (!exports) continue;
+        const ts2d_tiled_export& ex = exports[i];
+        if (!ex.seg_u8 && !ex.logits_f32) return fail(TS2D_ERR_INVALID, "%sexport: both outputs are null", pre);
+        if (ex.src_h < 1 || ex.src_w < 1 || ex.src_y < 0 || ex.src_x < 0 || ex.src_h > im.Hp - ex.src_y || ex.src_w > im.Wp - ex.src_x)
+            return fail(TS2D_ERR_INVALID, "%sexport: source rectangle %dx%d at (%d,%d) is empty or leaves the %dx%d image", pre, ex.src_h, ex.src_w,
+                        ex.src_y, ex.src_x, im.Hp, im.Wp);
+        if (ex.out_h < 1 || ex.out_w < 1) return fail(TS2D_ERR_INVALID, "%sexport: bad output extent %dx%d", pre, ex.out_h, ex.out_w);
+        if ((long long)K * ex.out_h * ex.out_w >= (1LL << 31))
+            return fail(TS2D_ERR_INVALID, "%sexport: %dx%d exceeds 2^31 output elements", pre, ex.out_h, ex.out_w);
+        n_taps_all += (long long)ex.out_h + ex.out_w;         // (each < 2^31 by the check above; bounded before any table is allocated)
+        if (n_taps_all >= (1LL << 26)) return fail(TS2D_ERR_INVALID, "%sexport: more than 2^26 output rows + columns in one call", pre);
+        any16 = true; any_rs8 |= ex.seg_u8 != nullptr; any_rs32 |= ex.logits_f32 != nullptr;
     }
     if (n_tiles_all * V >= (1LL << 28)) return fail(TS2D_ERR_INVALID, "%s: %lld network rows in one call", entry, n_tiles_all * V);
     // ---- row packing: whole images, greedily, into chunks of at most kSwChunkRows rows; a larger image takes chunks of its own
@@ -2152,13 +2184,36 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, int n_im
         if ((long long)c.gblocks >= (1LL << 31) || (long long)c.ablocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: a chunk exceeds 2^31 blocks", entry);
     }
     log_rows = std::max<long long>(log_rows, cap_rows);
+    // ---- the export: one segment per image (its half logits are segs' out_off), the taps of its rows then of its columns
+    std::vector<RsSeg> rsegs;
+    std::vector<RsTap> rtaps;
+    long long rs_elems = 0, rs_blocks = 0;
+    if (exports) {
+        long long oo = 0;
+        for (int i = 0; i < n_images; ++i) {
+            const ts2d_tiled_image& im = images[i]; const ts2d_tiled_export& ex = exports[i];
+            RsSeg rs{};
+            rs.src_off = oo; rs.dst_off = rs_elems; rs.Hp = im.Hp; rs.Wp = im.Wp; rs.out_h = ex.out_h; rs.out_w = ex.out_w;
+            rs.tap0 = (int)rtaps.size(); rs.block0 = (unsigned)rs_blocks;
+            rsegs.push_back(rs);
+            rtaps.resize(rtaps.size() + ex.out_h + ex.out_w);
+            rs_axis_taps(ex.src_h, ex.out_h, ex.src_y, rtaps.data() + rs.tap0);
+            rs_axis_taps(ex.src_w, ex.out_w, ex.src_x, rtaps.data() + rs.tap0 + ex.out_h);
+            rs_blocks += blocks_of((long long)K * ex.out_h * ((ex.out_w + 3) / 4));
+            rs_elems += (long long)align_up((size_t)K * ex.out_h * ex.out_w, 256);
+            oo += (long long)align_up((size_t)K * im.Hp * im.Wp, 256);
+        }
+        if (rs_blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the export exceeds 2^31 blocks", entry);
+    }
     TRY(reserve_checked(e, cap_rows, ph, pw, full));
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = e->stream;
     // ---- the descriptor table and every tile origin: one host blob, one copy
-    const size_t tab_segs = segs.size() * sizeof(SwSeg), tab_bytes = tab_segs + 2 * (size_t)n_tiles_all * 4;
+    const size_t tab_segs = segs.size() * sizeof(SwSeg), tab_rsegs = align_up(tab_segs + 2 * (size_t)n_tiles_all * 4, 8);
+    const size_t tab_rtaps = tab_rsegs + rsegs.size() * sizeof(RsSeg), tab_bytes = tab_rtaps + rtaps.size() * sizeof(RsTap);
     std::vector<char> tab(tab_bytes);
     memcpy(tab.data(), segs.data(), tab_segs);
+    if (exports) { memcpy(tab.data() + tab_rsegs, rsegs.data(), rsegs.size() * sizeof(RsSeg)); memcpy(tab.data() + tab_rtaps, rtaps.data(), rtaps.size() * sizeof(RsTap)); }
     {
         int32_t* ty = reinterpret_cast<int32_t*>(tab.data() + tab_segs); int32_t* tx = ty + n_tiles_all;
         for (int i = 0; i < n_images; ++i) {
@@ -2166,10 +2221,11 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, int n_im
             ty += images[i].n_tiles; tx += images[i].n_tiles;
         }
     }
-    // ---- scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs | uint8 outputs | flags]
+    // ---- scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs | uint8 outputs | flags | resampled uint8 | resampled float]
     const size_t o_tab = take(tab_bytes), o_g = take((size_t)ph * pw * 2), o_imgs = take((size_t)img_floats * 4);
     const size_t o_batch = take((size_t)cap_rows * C * ph * pw * 4), o_log = take((size_t)log_rows * K * ph * pw * 4);
     const size_t o_o16 = take(any16 ? (size_t)out_elems * 2 : 0), o_seg = take(anyseg ? (size_t)out_elems : 0), o_flag = take((size_t)n_images * 4);
+    const size_t o_rs8 = take(any_rs8 ? (size_t)rs_elems : 0), o_rs32 = take(any_rs32 ? (size_t)rs_elems * 4 : 0);
     if (off > e->sw_bytes) {                                  // grown before the first launch only
         HIP_TRY(hipStreamSynchronize(st));
         if (e->d_sw) { HIP_TRY(hipFree(e->d_sw)); e->d_sw = nullptr; e->sw_bytes = 0; }
@@ -2205,6 +2261,17 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, int n_im
                            gaussian_f16 ? d_g : nullptr, d_o16, d_seg, kSigmoidHalfThreshold, d_flag, e->tile_half);
         HIP_TRY(hipGetLastError());
     }
+    uint8_t* d_rs8 = any_rs8 ? reinterpret_cast<uint8_t*>(b + o_rs8) : nullptr; float* d_rs32 = any_rs32 ? reinterpret_cast<float*>(b + o_rs32) : nullptr;
+    if (exports) {
+        hipLaunchKernelGGL(sw_resample_threshold, dim3((unsigned)rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + o_tab + tab_rsegs),
+                           n_images, K, reinterpret_cast<const RsTap*>(b + o_tab + tab_rtaps), d_rs8, d_rs32, kSigmoidHalfThreshold);
+        HIP_TRY(hipGetLastError());
+        for (int i = 0; i < n_images; ++i) {
+            const size_t ne = (size_t)K * exports[i].out_h * exports[i].out_w;
+            if (exports[i].seg_u8) HIP_TRY(hipMemcpyAsync(exports[i].seg_u8, d_rs8 + rsegs[i].dst_off, ne, hipMemcpyDeviceToHost, st));
+            if (exports[i].logits_f32) HIP_TRY(hipMemcpyAsync(exports[i].logits_f32, d_rs32 + rsegs[i].dst_off, ne * 4, hipMemcpyDeviceToHost, st));
+        }
+    }
     std::vector<int> flags(n_images, 0);
     HIP_TRY(hipMemcpyAsync(flags.data(), d_flag, (size_t)n_images * 4, hipMemcpyDeviceToHost, st));
     {
@@ -2229,7 +2296,7 @@ int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
     if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
     ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
-    return predict_tiled_impl(e, &one, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false);
+    return predict_tiled_impl(e, &one, nullptr, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, "ts2d_engine_predict_tiled");
 }
 
 int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
@@ -2238,7 +2305,18 @@ int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, in
     if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
     if (n_images == 0) return TS2D_OK;
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
-    return predict_tiled_impl(e, images, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true);
+    return predict_tiled_impl(e, images, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, "ts2d_engine_predict_tiled_batch");
+}
+
+int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
+                                     int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
+    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: null engine");
+    if (n_images < 0 || (n_images > 0 && !(images && exports)))
+        return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: %d images at a null pointer", n_images);
+    if (n_images == 0) return TS2D_OK;
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_export: weights not loaded");
+    return predict_tiled_impl(e, images, exports, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true,
+                              "ts2d_engine_predict_tiled_export");
 }
 
 int ts2d_engine_check(ts2d_engine* e) {

@@ -282,6 +282,62 @@ class Engine:
         del keep
         return (out16 if want_logits else None), (seg if want_seg else None)
 
+    def predict_tiled_export(self, images, patch, tiles, exports, mirror_axes=None, gaussian: Optional[np.ndarray] = None,
+                             want_seg: bool = True, want_f32: bool = False, want_logits: bool = False, want_padded_seg: bool = False,
+                             full_batch: bool = True):
+        """:meth:`predict_tiled_batch` followed, on the device, by the export's order-1 resample-back and threshold (C-ABI
+        ts2d_engine_predict_tiled_export).  exports: one ``(src_y, src_x, src_h, src_w, out_h, out_w)`` per image - the rectangle of the
+        padded prediction that is the case, and the extent it is resampled to.  Returns ``(seg, f32, logits, padded_seg)``: lists of
+        uint8 [K,out_h,out_w] (``float32(value) > 1.5 * 2^-24`` of the resampled logits), float32 [K,out_h,out_w] (those logits),
+        float16 [K,Hp,Wp] and uint8 [K,Hp,Wp] (what :meth:`predict_tiled_batch` returns), each None unless asked for.
+        ``full_batch``: the full-batch dispatch of :meth:`predict_tiled_batch` (an image's bytes do not depend on its batch-mates);
+        False: the size-dependent dispatch of :meth:`predict_tiled`.  The resampled values equal
+        ``preprocess.resize_linear_f64`` of the float16 logits bit for bit.  Sets ``last_tiled_inf`` / ``last_tiled_inf_per_image``."""
+        if not (len(images) == len(tiles) == len(exports)):
+            raise RuntimeError(f"{len(images)} images but {len(tiles)} tile lists and {len(exports)} exports")
+        if not (want_seg or want_f32):
+            raise RuntimeError("predict_tiled_export: neither the resampled segmentation nor the resampled logits requested")
+        K = self.arch.num_classes
+        keep = []                    # every array the descriptors point into stays alive until the call returns
+        n = max(len(images), 1)
+        desc, exd = (_lib.TiledImage * n)(), (_lib.TiledExport * n)()
+        seg, f32, out16, pseg = [], [], [], []
+        for i, (image, tl, ex) in enumerate(zip(images, tiles, exports)):
+            image = np.ascontiguousarray(image, dtype=np.float32)
+            if image.ndim != 3:
+                raise RuntimeError(f"image {i}: expected [C,Hp,Wp], found shape {image.shape}")
+            C, Hp, Wp = image.shape
+            if C != self.arch.input_channels:
+                raise RuntimeError(f"image {i}: input has {C} channels, the model expects {self.arch.input_channels}")
+            sy, sx, sh, sw_, oh, ow = (int(v) for v in ex)
+            ty = np.ascontiguousarray([t[0] for t in tl], dtype=np.int32)
+            tx = np.ascontiguousarray([t[1] for t in tl], dtype=np.int32)
+            shape = (K, max(oh, 0), max(ow, 0))          # (a bad extent is the library's to reject, by name)
+            seg.append(np.empty(shape, dtype=np.uint8) if want_seg else None)
+            f32.append(np.empty(shape, dtype=np.float32) if want_f32 else None)
+            out16.append(np.empty((K, Hp, Wp), dtype=np.float16) if want_logits else None)
+            pseg.append(np.empty((K, Hp, Wp), dtype=np.uint8) if want_padded_seg else None)
+            keep += [image, ty, tx]
+            d, x = desc[i], exd[i]
+            d.image, d.Hp, d.Wp, d.n_tiles = image.ctypes.data, Hp, Wp, len(tl)
+            d.tile_y, d.tile_x = ty.ctypes.data, tx.ctypes.data
+            d.logits_f16 = out16[i].ctypes.data if want_logits else None
+            d.seg_u8 = pseg[i].ctypes.data if want_padded_seg else None
+            x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w = sy, sx, sh, sw_, oh, ow
+            x.seg_u8 = seg[i].ctypes.data if want_seg else None
+            x.logits_f32 = f32[i].ctypes.data if want_f32 else None
+        mask = 0
+        for a in (mirror_axes or ()):
+            mask |= 1 << int(a)
+        g = None if gaussian is None else np.ascontiguousarray(gaussian, dtype=np.float16)
+        _lib.check(self.lib.ts2d_engine_predict_tiled_export(self._h, desc, exd, len(images), int(patch[0]), int(patch[1]), mask,
+                                                             None if g is None else g.ctypes.data, int(bool(full_batch))),
+                   'ts2d_engine_predict_tiled_export')
+        self.last_tiled_inf_per_image = [bool(desc[i].inf_flag) for i in range(len(images))]
+        self.last_tiled_inf = any(self.last_tiled_inf_per_image)
+        del keep
+        return (seg if want_seg else None), (f32 if want_f32 else None), (out16 if want_logits else None), (pseg if want_padded_seg else None)
+
     def _check_shape(self, C, W, mask):
         if C != self.arch.input_channels:
             raise RuntimeError(f"input has {C} channels, the model expects {self.arch.input_channels}")

@@ -6,6 +6,7 @@ apply / stop``, ``channels``, ``multilabel``, ``revision`` - but no worker proce
 """
 from __future__ import annotations
 
+import inspect
 import json
 import os
 import re
@@ -169,18 +170,30 @@ class HIPModel:
             data, props = hit[0], dict(hit[1])
         return ref, data, props
 
-    def _predict(self, datas, use_seg: bool, batched: bool):
+    @staticmethod
+    def _takes(fn, name: str) -> bool:
+        """Does callable `fn` accept the keyword `name`?"""
+        try:
+            params = inspect.signature(fn).parameters
+        except (TypeError, ValueError):
+            return False
+        return name in params or any(q.kind is q.VAR_KEYWORD for q in params.values())
+
+    def _predict(self, datas, use_seg: bool, batched: bool, out_shapes=None):
         """Stage 2 of :meth:`_run`, the one stage that differs between :meth:`apply` and :meth:`apply_batch`: ONE predictor batch call
         over ``datas``, or the predictor's single-case methods per input - the reference's duck-typed seam
         (``predict_logits_from_preprocessed_data``, prediction_worker.py:206-209), which a foreign predictor without the batch methods
-        serves too.  ``use_seg``: ask for the device-thresholded segmentation first (it answers None when the case needs the logits)."""
+        serves too.  ``use_seg``: ask for the device-thresholded segmentation first (it answers None when the case needs the logits);
+        ``out_shapes``: per input the extent its export resamples to, or None - passed on only when some input has one."""
         p = self._predictor
+        shapes = out_shapes if out_shapes is not None and any(s is not None for s in out_shapes) else None
         if batched:
-            out = p.predict_segmentation_from_preprocessed_data_batch(datas) if use_seg else None
+            out = p.predict_segmentation_from_preprocessed_data_batch(datas, **({} if shapes is None else {'out_shapes': shapes})) if use_seg else None
             if out is None:
                 out = p.predict_logits_from_preprocessed_data_batch(datas)
         else:
-            out = [p.predict_segmentation_from_preprocessed_data(d) if use_seg else None for d in datas]
+            out = [p.predict_segmentation_from_preprocessed_data(d, **({} if shapes is None or s is None else {'out_shape': s})) if use_seg else None
+                   for d, s in zip(datas, shapes or [None] * len(datas))]
             out = [p.predict_logits_from_preprocessed_data(d) if o is None else o for d, o in zip(datas, out)]
         return [o.cpu().numpy() if hasattr(o, 'cpu') else o for o in out]
 
@@ -212,17 +225,33 @@ class HIPModel:
             except Exception as ex:
                 raise RuntimeError(f"Preprocessing failed for {name}: {ex}") from ex
             todo.append([name, ofile, ref, data, props, None])
-        # product fast path: a multilabel 2-D case whose export does not resample gets its segmentation thresholded on the device
-        # (K uint8 planes to the host instead of K float16 ones; the predicate is the export step's, bit for bit) - the reference's seam
+        # product fast path: a multilabel 2-D case gets its segmentation thresholded on the device (K uint8 planes to the host instead
+        # of K float16 ones; the predicate is the export step's, bit for bit).  A case whose export resamples (its spacing is not the
+        # plan's) joins with the extent it had before resampling: the device resamples the logits back (order 1) in front of the
+        # threshold and the export step receives uint8 planes already in that extent.  The reference's seam
         # (predict_logits_from_preprocessed_data + export_prediction_from_logits) stays as it is and serves every other case
         can_seg = self.device_threshold and bool(p.dataset_json.get('multilabel', p.dataset_json.get('multiclass', False))) \
             and hasattr(p, 'predict_segmentation_from_preprocessed_data' + ('_batch' if batched else ''))
-        fast = [t for t in todo if can_seg and not needs_logits(t[4], np.asarray(t[3]).shape[1:])]
+        # (a foreign predictor, or a double of the engine method, that knows the fast path but not its `out_shape(s)` keyword keeps
+        #  the host route for resampled cases, as before the device export existed)
+        fast_fn = getattr(p, 'predict_segmentation_from_preprocessed_data' + ('_batch' if batched else ''), None)
+        can_export = can_seg and self._takes(fast_fn, 'out_shapes' if batched else 'out_shape') \
+            and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, 'out_shapes'))
+
+        def target(t):
+            """The extent the device export resamples case `t` to: None = none needed, False = not a case for it (a stack, a 3-D plan,
+            a predictor without the export)."""
+            shape = tuple(np.asarray(t[3]).shape[1:])
+            if not needs_logits(t[4], shape):
+                return None
+            tgt = tuple(t[4]['shape_after_cropping_and_before_resampling'])
+            return tgt if can_export and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] == 1 else False
+        fast = [t for t in todo if can_seg and target(t) is not False]
         for group, use_seg in ((fast, True), ([t for t in todo if not any(t is f for f in fast)], False)):
             if not group:
                 continue
             try:
-                out = self._predict([t[3] for t in group], use_seg, batched)
+                out = self._predict([t[3] for t in group], use_seg, batched, [target(t) for t in group] if use_seg else None)
             except Exception as ex:
                 names = ', '.join(t[0] for t in group)
                 m = re.match(r'input (\d+): ', str(ex))          # the predictor names the offending input of the batch by index

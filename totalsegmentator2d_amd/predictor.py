@@ -154,13 +154,16 @@ class HIPnnUNetPredictor:
     _INF_MESSAGE = ('Encountered inf in predicted array. Aborting... If this problem persists, reduce '
                     'value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32')
 
-    def _sliding_window_batch(self, list_of_data, fold: int = 0, want_seg: bool = False, one_call: bool = True):
+    def _sliding_window_batch(self, list_of_data, fold: int = 0, want_seg: bool = False, one_call: bool = True, out_shapes=None):
         """One fold, N inputs [C,Z,H,W]: pad, tile, tiles x mirror variants through the engine, upstream's fp16 Gaussian aggregation
         on the device.  Every z slice of every input is one image.  ``one_call``: all images in ONE engine call (C-ABI
         ts2d_engine_predict_tiled_batch: the network takes the full-batch dispatch, an input's bytes do not depend on its batch-mates,
         an error names the input); otherwise one ts2d_engine_predict_tiled call per image (size-dependent dispatch).  Returns one
         array per input in the input's geometry: float16 [K,Z,H,W] logits, or the device-thresholded uint8 segmentation when ``want_seg``.
         A single case is a batch of one: the single-case methods below are this method on ``[data]`` with ``one_call=False``.
+        ``out_shapes`` (with ``want_seg``, Z = 1): one in-plane extent ``(h, w)`` or None per input - the device resamples every input's
+        logits (order 1) to its extent, None = the input's own, and thresholds them there (C-ABI ts2d_engine_predict_tiled_export, the
+        export's ``resampling_fn_probabilities`` + threshold): uint8 [K,1,h,w] per input.
         (The one method that touches the engine, under the name the test infrastructure overrides: tests/batch_util.py replaces it, and
         tests/host_predictor.py predict_sliding_window_return_logits, with the host restatement.)"""
         patch = tuple(self.configuration_manager.patch_size)
@@ -183,6 +186,24 @@ class HIPnnUNetPredictor:
         g = sw.compute_gaussian(patch) if self.use_gaussian else None
         axes = self.allowed_mirroring_axes if self.use_mirroring else None
         e = self.engines[fold]
+        if out_shapes is not None:
+            if not want_seg or len(out_shapes) != len(list_of_data) or any(Z != 1 for Z, _, _ in shapes):
+                raise AssertionError('out_shapes needs want_seg, one extent (or None) per input and single-slice inputs')
+            exports = []
+            for data, revert, hw in zip(list_of_data, reverts, out_shapes):
+                H, W = np.shape(data)[2:]
+                exports.append((revert[2].start, revert[3].start, H, W) + (tuple(int(v) for v in hw) if hw is not None else (H, W)))
+            groups = [range(len(images))] if one_call else [[j] for j in range(len(images))]
+            planes, inf = [], []
+            for grp in groups:
+                seg = e.predict_tiled_export([images[j] for j in grp], patch, [tiles[j] for j in grp], [exports[j] for j in grp], axes, g,
+                                             full_batch=one_call)[0]
+                planes += seg
+                inf += e.last_tiled_inf_per_image
+            bad = sorted(j for j, f in enumerate(inf) if f)
+            if bad:
+                raise RuntimeError((f'input {bad[0]}: ' if one_call else '') + self._INF_MESSAGE)
+            return [p[:, None] for p in planes]
         if one_call:
             out16, seg = e.predict_tiled_batch(images, patch, tiles, axes, g, want_logits=not want_seg, want_seg=want_seg)
             planes, inf = (seg if want_seg else out16), e.last_tiled_inf_per_image
@@ -207,18 +228,38 @@ class HIPnnUNetPredictor:
         data [C,Z,H,W] float32 -> float16 [K,Z,H,W]."""
         return self._sliding_window_batch([data], fold, one_call=False)[0]
 
-    def predict_segmentation_from_preprocessed_data(self, data):
+    @staticmethod
+    def _in_plane(out_shape, data):
+        """``out_shape`` of the fast-path methods -> in-plane ``(h, w)``, None (no resampling) or False (not a case for the device export).
+        Accepts (h, w) or, as ``properties['shape_after_cropping_and_before_resampling']`` holds it, (1, h, w)."""
+        if out_shape is None:
+            return None
+        hw = tuple(int(v) for v in out_shape)
+        if len(hw) == 3 and hw[0] == 1:
+            hw = hw[1:]
+        if len(hw) != 2 or min(hw) < 1:
+            return False
+        return None if hw == tuple(data.shape[2:]) else hw
+
+    def predict_segmentation_from_preprocessed_data(self, data, out_shape=None):
         """Fast path of the product surface (not part of the reference's duck-typed seam): the multilabel segmentation
         ``sigmoid(float(half logits)) > 0.5`` thresholded ON THE DEVICE by the aggregation kernel (kernels_sw.h: the same predicate as
         export.py's bit-pattern test, verified on all 65 536 half values), so that K uint8 planes travel to the host instead of K float16
         ones and the host never thresholds.  One fold, one z-slice (the 2-D models of ts2d); returns uint8 [K, 1, H, W] in the
-        preprocessed geometry, or None when the case needs the logits (fold ensembles average logits first; 3-D stacks)."""
+        preprocessed geometry, or None when the case needs the logits (fold ensembles average logits first; 3-D stacks).
+        ``out_shape`` (the case's ``shape_after_cropping_and_before_resampling``, (h, w) or (1, h, w)): the export's order-1
+        resample-back runs on the device in front of the threshold (kernels_resample.h; bit for bit the host route's
+        ``resample_data_to_shape(order=1)`` + threshold) and the result is uint8 [K, 1, h, w] in THAT extent."""
         if hasattr(data, 'detach'):
             data = data.detach().cpu().numpy()
         data = np.asarray(data, dtype=np.float32)
         if len(self.list_of_parameters) != 1 or len(self.engines) != 1 or data.ndim != 4 or data.shape[1] != 1:
             return None
-        return self._sliding_window_batch([data], 0, want_seg=True, one_call=False)[0]
+        hw = self._in_plane(out_shape, data)
+        if hw is False:
+            return None
+        kw = {} if hw is None else {'out_shapes': [hw]}
+        return self._sliding_window_batch([data], 0, want_seg=True, one_call=False, **kw)[0]
 
     def predict_logits_from_preprocessed_data(self, data):
         """Fold ensemble (upstream: sum over ``list_of_parameters`` then ``/= n``).  Accepts numpy or torch [C,1,H,W];
@@ -259,12 +300,17 @@ class HIPnnUNetPredictor:
         except ImportError:
             return preds
 
-    def predict_segmentation_from_preprocessed_data_batch(self, list_of_data):
+    def predict_segmentation_from_preprocessed_data_batch(self, list_of_data, out_shapes=None):
         """:meth:`predict_segmentation_from_preprocessed_data` for a list of inputs: uint8 [K,1,H,W] per input from ONE engine call,
-        or None when the predictor needs the logits (a fold ensemble) or an input is no single z slice."""
+        or None when the predictor needs the logits (a fold ensemble) or an input is no single z slice.  ``out_shapes``: one
+        ``out_shape`` (or None) per input; inputs that resample and inputs that do not travel in the same call."""
         datas = [np.asarray(d.detach().cpu().numpy() if hasattr(d, 'detach') else d, dtype=np.float32) for d in list_of_data]
         if len(self.list_of_parameters) != 1 or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
             return None
         if not datas:
             return []
-        return self._sliding_window_batch(datas, 0, want_seg=True)
+        hws = [self._in_plane(s, d) for s, d in zip(out_shapes, datas)] if out_shapes is not None else [None] * len(datas)
+        if (out_shapes is not None and len(out_shapes) != len(datas)) or any(hw is False for hw in hws):
+            return None
+        kw = {} if all(hw is None for hw in hws) else {'out_shapes': hws}
+        return self._sliding_window_batch(datas, 0, want_seg=True, **kw)

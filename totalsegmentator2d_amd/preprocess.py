@@ -149,6 +149,39 @@ def resize_like_skimage(img2d: np.ndarray, new_shape, order: int) -> np.ndarray:
     return out.astype(img2d.dtype, copy=False)
 
 
+def linear_axis_taps(n_in: int, n_out: int):
+    """Taps of one axis of :func:`resize_linear_f64` (``n_in`` -> ``n_out`` samples), all in float64: the two source indices and their
+    weights per output sample, ``(i0, i1, w0, w1)``.  As scipy does it for ``mode='nearest'``: the coordinate is NOT clamped - the array
+    is extended by its edge samples, so the tap INDICES are clamped and a coordinate outside the array weighs the same edge sample twice.
+    The C entry ts2d_engine_predict_tiled_export computes the same table on the host."""
+    cc = (np.arange(n_out, dtype=np.float64) + 0.5) * (np.float64(n_in) / np.float64(n_out)) - 0.5
+    f = np.floor(cc)
+    w1 = cc - f
+    i0 = f.astype(np.int64)
+    return np.clip(i0, 0, n_in - 1), np.clip(i0 + 1, 0, n_in - 1), 1.0 - w1, w1
+
+
+def resize_linear_f64(img2d: np.ndarray, new_shape) -> np.ndarray:
+    """:func:`resize_like_skimage` with ``order=1`` as a closed form in float64, bit for bit what scipy returns (tests/test_resample_cpu.py:
+    every float32 value, half-valued and full float32 input, and the same non-finite outputs for +-inf samples): four taps in the order
+    (y0,x0), (y0,x1), (y1,x0), (y1,x1), each sample multiplied by its row weight and then by its column weight, the four products summed
+    left to right, every product and sum rounded to float64 (no FMA), ONE rounding to the input's dtype.  The clip to the input's
+    value range that follows in ``resize_like_skimage`` never changes an order-1 result (a convex combination, rounded once).  A zero
+    weight on an infinite sample gives NaN, as in scipy.  This is the statement the device kernel ``sw_resample_threshold``
+    (csrc/kernels_resample.h) reproduces bit for bit."""
+    img2d = np.asarray(img2d)
+    y0, y1, wy0, wy1 = linear_axis_taps(img2d.shape[0], int(new_shape[0]))
+    x0, x1, wx0, wx1 = linear_axis_taps(img2d.shape[1], int(new_shape[1]))
+    a = img2d.astype(np.float64)
+    wy0, wy1, wx0, wx1 = wy0[:, None], wy1[:, None], wx0[None], wx1[None]
+    with np.errstate(invalid='ignore'):                                   # (0 x inf = NaN is the pinned result, not a warning)
+        r = (a[y0][:, x0] * wy0) * wx0
+        r = r + (a[y0][:, x1] * wy0) * wx1
+        r = r + (a[y1][:, x0] * wy1) * wx0
+        r = r + (a[y1][:, x1] * wy1) * wx1
+    return r.astype(img2d.dtype)
+
+
 def resample_data_to_shape(data: np.ndarray, new_shape, order: int = 3) -> np.ndarray:
     """``resample_data_or_seg_to_shape(data, new_shape, current_spacing, new_spacing, is_seg=False, order=3, order_z=0)`` for the
     2-D configurations ts2d uses ([C, 1, H, W] with the 999 pseudo-spacing): upstream finds the 999 axis anisotropic and
