@@ -278,6 +278,24 @@ int ts2d_project_coronal_zscore(int device, const void* volume, size_t n_elems, 
                                 long long sy, long long sx, long long base, float* out_max, float* out_mean, float* out_norm,
                                 double* out_stats, int32_t* out_box);
 
+/* nnU-Net's input resample for the 2-D configurations on the device: every plane of src [n_planes][in_h][in_w] float32 resampled to
+ * dst [n_planes][out_h][out_w] float32 as skimage.transform.resize(plane, (out_h, out_w), order=3, mode='edge', anti_aliasing=False,
+ * clip=True) does it (reference flow DefaultPreprocessor.run_case, ts2d/core/inference/prediction_worker.py:194-199, for a case whose
+ * spacing is not the plan's).  Host pointers in and out, synchronous, scratch of the call's own, freed on every path.
+ * Arithmetic contract = preprocess.resize_cubic_f64, bit for bit, which is bit for bit scipy's zoom(order=3, mode='nearest',
+ * grid_mode=True) and the clip that follows it: the plane padded by 12 edge samples, widened to float64, cubic B-spline prefilter along
+ * axis 0 and then along axis 1 exactly as scipy's line filter runs it (pole = the float64 nearest to sqrt(3) - 2, the boundary sum with
+ * its running products of the pole and its accumulator read back in the last term, sequential recursions), 16 taps per output pixel in
+ * row-major order, each (c * wy) * wx, summed left to right from 0, every product and sum rounded to float64 (no FMA), ONE rounding
+ * to float32, then x < lo ? lo : x and x > hi ? hi : x.  Taps and line constants are computed on the host in float64.
+ *   lo_hi      [n_planes][2]: the float32 minimum and maximum of each source plane (the caller has them from numpy).  They must be
+ *              finite and ordered: a plane with a non-finite sample is outside the contract (its minimum or maximum says so).
+ * TS2D_ERR_INVALID, by name, before any device work: null pointers, n_planes < 1, an extent below 2 or above 8192, more than 2^28
+ * padded or output samples in one call, a zoom whose taps would leave the padded plane, non-finite or inverted lo_hi.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+int ts2d_resample_cubic(int device, const float* src, int n_planes, int in_h, int in_w, int out_h, int out_w, const float* lo_hi,
+                        float* dst);
+
 /* Synthetic slice stream on the device (BASELINE config 4: "synthetic 10k-slice stream", generated per rank from (seed, slice
  * index) so that no host transfer skews the timing).  Writes n_elements fp32 values, approximately N(0,1), to device memory:
  * element i of the call = element (first_element + i) of the stream identified by `key`; a value depends on (key, element index)

@@ -1,13 +1,15 @@
 """Per-case wall time of cases whose spacing is NOT the plan's (1.5 mm): the host route of the export (float16 logits to the host,
 scipy order 1 per plane, threshold) against the device export (csrc/kernels_resample.h: resample-back + threshold behind the sliding
-window).  Five canonical sub-models (K = 18/23/24/26/26, synthetic weights) as in scripts/gpu_case_latency.py; synthetic two-channel
+window) and against the device export with the order-3 INPUT resample on the device as well (csrc/kernels_resample_in.h, the product
+default).  Five canonical sub-models (K = 18/23/24/26/26, synthetic weights) as in scripts/gpu_case_latency.py; synthetic two-channel
 images of the three geometries of the issue (original extent at its spacing -> network extent), every case its OWN image object with
 its own pixels (the sub-models of one case share a preprocessing cache that hangs on the image: aliases of one image would share it
 across cases).  TS2D.predict: median of N cases after warm-up; predict_many(max_cases=8): cases/s over 3 groups of 8 distinct cases.
 Stage spans (host clock, summed over the five sub-models, which run concurrently - they add up to more than the wall time) and the
-host order-3 input resample timed on its own say where the time over an un-resampled case of the same network geometry goes.
+order-3 input resample of one case timed on its own, on the host and on the device (the whole synchronous call: allocation, copies in,
+three kernels, copy out), say where the time over an un-resampled case of the same network geometry goes.
 
-    timeout -k 10 600 python scripts/gpu_resampled_case.py [N=20] > profiles/r09_resampled_case.txt     # exit status 0 = complete"""
+    timeout -k 10 600 python scripts/gpu_resampled_case.py [N=20] > profiles/r10_resampled_case.txt     # exit status 0 = complete"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -39,9 +41,10 @@ def images(hw, spacing, n, seed0):
                        (1.0, 0.0, 0.0, 1.0), 2, {}, None) for s in range(n)]
 
 
-def route(ts, device):
+def route(ts, device, device_input):
     for m in ts.models.values():
         m.device_threshold = device
+        m.device_input_resample = device_input
 
 
 def stages(results):
@@ -65,9 +68,17 @@ with TS2D(models=models) as ts:
         for _ in range(5):
             P.resample_data_to_shape(z, (1,) + net, order=3)
         t_in = (time.perf_counter() - t0) / 5
+        ref = P.resample_data_to_shape(z, (1,) + net, order=3)
+        got = P.resample_data_to_shape(z, (1,) + net, order=3, device=0)                 # (warm-up of the three kernels as well)
+        same_in = np.array_equal(ref.view(np.uint32), got.view(np.uint32))
+        t0 = time.perf_counter()
+        for _ in range(20):
+            P.resample_data_to_shape(z, (1,) + net, order=3, device=0)
+        t_dev = (time.perf_counter() - t0) / 20
         res = {}
-        for name, dev, ehw, esp in (('host route', False, hw, sp), ('device export', True, hw, sp), ('un-resampled', True, net, (1.5, 1.5))):
-            route(ts, dev)
+        for name, dev, dev_in, ehw, esp in (('host route', False, False, hw, sp), ('device export', True, False, hw, sp),
+                                            ('device in + export', True, True, hw, sp), ('un-resampled', True, True, net, (1.5, 1.5))):
+            route(ts, dev, dev_in)
             cases = images(ehw, esp, N, 100)                     # the same N cases for both routes
             many_in = [images(ehw, esp, 8, 1000 + 8 * g) for g in range(GROUPS)]
             for im in images(ehw, esp, 3, 500):
@@ -81,12 +92,15 @@ with TS2D(models=models) as ts:
             rate = 8 * GROUPS / (time.perf_counter() - t0)
             res[name] = (float(np.median(t)), rate, [r.get_segmentation().array for r in out],
                          [r.get_segmentation().array for g in many for r in g], stages(out), stages([r for g in many for r in g]))
-        h, d, u = (res[k] for k in ('host route', 'device export', 'un-resampled'))
-        eq = all(np.array_equal(a, b) for a, b in zip(h[2], d[2])), all(np.array_equal(a, b) for a, b in zip(h[3], d[3]))
+        h, d, di, u = (res[k] for k in ('host route', 'device export', 'device in + export', 'un-resampled'))
+        eq = (all(np.array_equal(a, b) and np.array_equal(a, c) for a, b, c in zip(h[2], d[2], di[2])),
+              all(np.array_equal(a, b) and np.array_equal(a, c) for a, b, c in zip(h[3], d[3], di[3])))
         print(f'{hw[0]} x {hw[1]} at {sp[1]} x {sp[0]} mm -> {net[0]} x {net[1]}: masks of all {N} + {8 * GROUPS} cases equal (predict, predict_many): {eq}')
         for name, (med, rate, _, _, s1, s8) in res.items():
-            print(f'    {name:14s} predict median of {N}: {med * 1e3:6.1f} ms per case   [{s1}]')
-            print(f'    {"":14s} predict_many(max_cases=8), {8 * GROUPS} distinct cases: {rate:5.1f} cases/s   [{s8}]')
-        print(f'    host order-3 input resample of one case, on its own: {t_in * 1e3:.1f} ms')
+            print(f'    {name:18s} predict median of {N}: {med * 1e3:6.1f} ms per case   [{s1}]')
+            print(f'    {"":18s} predict_many(max_cases=8), {8 * GROUPS} distinct cases: {rate:5.1f} cases/s   [{s8}]')
+        print(f'    order-3 input resample of one case, on its own: host {t_in * 1e3:.1f} ms, device {t_dev * 1e3:.2f} ms (whole call), same bits: {same_in}')
+        print(f'    device in + export: {d[0] / di[0]:.2f}x the device export per case ({(d[0] - di[0]) * 1e3:.1f} ms less; {di[1] / d[1]:.2f}x in cases/s), '
+              f'{di[0] / u[0]:.2f}x an un-resampled case ({(di[0] - u[0]) * 1e3:.1f} ms more)')
         print(f'    device export: {h[0] / d[0]:.1f}x the host route per case ({d[1] / h[1]:.1f}x in cases/s), {d[0] / u[0]:.2f}x an un-resampled case '
               f'of the same network geometry ({(d[0] - u[0]) * 1e3:.1f} ms more, of which the input resample is {t_in * 1e3:.1f} ms)', flush=True)

@@ -19,6 +19,7 @@
 #include "kernels_upc_h2.h"
 #include "kernels_sw.h"
 #include "kernels_resample.h"
+#include "kernels_resample_in.h"
 #include "kernels_project.h"
 
 #include <atomic>
@@ -2475,6 +2476,111 @@ int ts2d_project_coronal_zscore(int device, const void* volume, size_t n_elems, 
     if (!out_norm) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal_zscore: null argument");
     return project_coronal_impl(device, volume, n_elems, dtype, nz, ny, nx, sz, sy, sx, base, out_max, out_mean, out_norm, out_stats, out_box);
 }
+// Taps of one axis of the order-3 resample (n_in -> n_out samples; preprocess.cubic_axis_taps is the same statement in numpy, pinned to
+// scipy): cc = ((o + 0.5) * (n_in / n_out) - 0.5) + 12 clamped to the padded extent, start = floor(cc) - 1, y = cc - floor(cc), t = 1 - y,
+// w1 = (y*y*(y-2)*3 + 4) / 6, w2 = (t*t*(t-2)*3 + 4) / 6, w0 = t*t*t / 6, w3 = 1 - w0 - w1 - w2, one rounding per step.  False if a tap
+// would leave the padded line (with this map it cannot: cc lies in [11.5, n_in + 11.5]; checked because the kernel reads where it points).
+static bool rsin_axis_taps(int n_in, int n_out, RsInTap* t) {
+#pragma clang fp contract(off)
+    const int n_pad = n_in + 2 * kRsInPad;
+    const double zoom = (double)n_in / (double)n_out;
+    for (int o = 0; o < n_out; ++o) {
+        const double prod = ((double)o + 0.5) * zoom;
+        const double shifted = prod - 0.5;
+        double cc = shifted + (double)kRsInPad;
+        cc = std::min(std::max(cc, 0.0), (double)(n_pad - 1));
+        const double f = std::floor(cc);
+        const long long start = (long long)f - 1;
+        if (start < 0 || start + 3 > n_pad - 1) return false;
+        const double y = cc - f, u = 1.0 - y;
+        const double yy = y * y, uu = u * u;
+        const double a1 = yy * (y - 2.0), a2 = uu * (u - 2.0);
+        const double b1 = a1 * 3.0, b2 = a2 * 3.0;
+        t[o].w[1] = (b1 + 4.0) / 6.0;
+        t[o].w[2] = (b2 + 4.0) / 6.0;
+        const double u3 = uu * u;
+        t[o].w[0] = u3 / 6.0;
+        const double r0 = 1.0 - t[o].w[0], r1 = r0 - t[o].w[1];
+        t[o].w[3] = r1 - t[o].w[2];
+        t[o].start = (int)start; t[o].pad_ = 0;
+    }
+    return true;
+}
+
+// The float64 nearest to sqrt(3) - 2: what scipy's binary holds for the pole of the cubic prefilter (its compiler folds the constant
+// in extended precision).  std::sqrt(3.0) - 2.0 is two units in the last place away and would cost the bit identity.
+static const double kRsInPole = -0x1.126145e9ecd56p-2;
+constexpr int kRsInMaxExtent = 8192;          // preprocess.CUBIC_MAX_EXTENT
+
+static RsInAxis rsin_axis_constants(int n_pad) {
+#pragma clang fp contract(off)
+    RsInAxis a;
+    a.z = kRsInPole;
+    const double inv = 1.0 / a.z;
+    a.gain = (1.0 - a.z) * (1.0 - inv);
+    a.zn = std::pow(a.z, (double)n_pad);
+    const double zn2 = a.zn * a.zn;
+    a.k0 = a.z / (1.0 - zn2);
+    a.k1 = a.z / (a.z - 1.0);
+    return a;
+}
+
+int ts2d_resample_cubic(int device, const float* src, int n_planes, int in_h, int in_w, int out_h, int out_w, const float* lo_hi, float* dst) {
+    if (!src || !lo_hi || !dst) return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: null argument");
+    if (n_planes < 1) return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: %d planes", n_planes);
+    if (in_h < 2 || in_w < 2 || out_h < 2 || out_w < 2 || in_h > kRsInMaxExtent || in_w > kRsInMaxExtent || out_h > kRsInMaxExtent || out_w > kRsInMaxExtent)
+        return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: extents %d x %d -> %d x %d outside 2 ... %d", in_h, in_w, out_h, out_w, kRsInMaxExtent);
+    const int Hp = in_h + 2 * kRsInPad, Wp = in_w + 2 * kRsInPad;
+    if ((long long)n_planes * Hp * Wp > (1ll << 28) || (long long)n_planes * out_h * out_w > (1ll << 28))
+        return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: %d planes of %d x %d -> %d x %d are more than one call takes (2^28 samples)", n_planes, in_h, in_w, out_h, out_w);
+    for (int p = 0; p < n_planes; ++p)
+        if (!std::isfinite(lo_hi[2 * p]) || !std::isfinite(lo_hi[2 * p + 1]) || lo_hi[2 * p] > lo_hi[2 * p + 1])
+            return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: plane %d has non-finite or inverted clip bounds [%g, %g] (a plane with a non-finite sample is not computed here)",
+                        p, (double)lo_hi[2 * p], (double)lo_hi[2 * p + 1]);
+    std::vector<RsInTap> taps((size_t)out_h + out_w);
+    if (!rsin_axis_taps(in_h, out_h, taps.data()) || !rsin_axis_taps(in_w, out_w, taps.data() + out_h))
+        return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: zoom %d x %d -> %d x %d puts a tap outside the padded plane", in_h, in_w, out_h, out_w);
+    std::vector<double> zpow((size_t)std::max(Hp, Wp));
+    {
+#pragma clang fp contract(off)
+        zpow[0] = 1.0; zpow[1] = kRsInPole;                                    // running products, as scipy forms them (z_i *= z)
+        for (size_t i = 2; i < zpow.size(); ++i) zpow[i] = zpow[i - 1] * kRsInPole;
+    }
+    const RsInAxis ax_h = rsin_axis_constants(Hp), ax_w = rsin_axis_constants(Wp);
+    HIP_TRY(hipSetDevice(device));
+    const size_t n_src = (size_t)n_planes * in_h * in_w, n_coef = (size_t)n_planes * Hp * Wp, n_dst = (size_t)n_planes * out_h * out_w;
+    // [coefficients | powers | taps | source | clip bounds | result]
+    const size_t o_pow = align_up(n_coef * sizeof(double), 256), o_taps = align_up(o_pow + zpow.size() * sizeof(double), 256);
+    const size_t o_src = align_up(o_taps + taps.size() * sizeof(RsInTap), 256), o_lh = align_up(o_src + n_src * sizeof(float), 256);
+    const size_t o_dst = align_up(o_lh + (size_t)n_planes * 2 * sizeof(float), 256);
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), o_dst + n_dst * sizeof(float)));
+    double* d_coef = reinterpret_cast<double*>(d);
+    const double* d_pow = reinterpret_cast<const double*>(d + o_pow);
+    const RsInTap* d_taps = reinterpret_cast<const RsInTap*>(d + o_taps);
+    const float* d_src = reinterpret_cast<const float*>(d + o_src);
+    const float* d_lh = reinterpret_cast<const float*>(d + o_lh);
+    float* d_dst = reinterpret_cast<float*>(d + o_dst);
+    hipError_t he = hipMemcpy(d + o_pow, zpow.data(), zpow.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d + o_taps, taps.data(), taps.size() * sizeof(RsInTap), hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d + o_src, src, n_src * sizeof(float), hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d + o_lh, lo_hi, (size_t)n_planes * 2 * sizeof(float), hipMemcpyHostToDevice);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(rsin_prefilter_cols, dim3((unsigned)(((long long)n_planes * Wp + 63) / 64)), dim3(64), 0, 0,
+                           d_src, n_planes, in_h, in_w, ax_h, d_pow, d_coef);
+        hipLaunchKernelGGL(rsin_prefilter_rows, dim3((unsigned)(((long long)n_planes * Hp + 63) / 64)), dim3(64), 0, 0,
+                           d_coef, n_planes, Hp, Wp, ax_w, d_pow);
+        const long long quads = (long long)n_planes * out_h * ((out_w + 3) / 4);
+        hipLaunchKernelGGL(rsin_interp_clip, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, 0,
+                           d_coef, n_planes, Hp, Wp, out_h, out_w, d_taps, d_lh, d_dst);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipMemcpy(dst, d_dst, n_dst * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (he != hipSuccess) return fail(TS2D_ERR_HIP, "ts2d_resample_cubic failed: %s", hipGetErrorString(he));
+    return TS2D_OK;
+}
+
 int ts2d_synth_slices(int device, unsigned long long key, unsigned long long first_element, unsigned long long n_elements,
                       float* out_device, void* stream) {
     if (!out_device) return fail(TS2D_ERR_INVALID, "ts2d_synth_slices: null output");

@@ -8,6 +8,7 @@ crop_to_nonzero -> per-channel normalisation (channel names ``mean`` / ``max`` a
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -182,15 +183,166 @@ def resize_linear_f64(img2d: np.ndarray, new_shape) -> np.ndarray:
     return r.astype(img2d.dtype)
 
 
-def resample_data_to_shape(data: np.ndarray, new_shape, order: int = 3) -> np.ndarray:
+CUBIC_PAD = 12                                         # scipy's _prepad_for_spline_filter: edge samples per side for mode='nearest'
+CUBIC_POLE = float.fromhex('-0x1.126145e9ecd56p-2')    # the float64 nearest to sqrt(3) - 2 (see resize_cubic_f64: NOT math.sqrt(3.0) - 2.0)
+CUBIC_GAIN = (1.0 - CUBIC_POLE) * (1.0 - 1.0 / CUBIC_POLE)
+CUBIC_MAX_EXTENT = 8192                                # per axis, input and output: the device entry's index arithmetic is sized for it
+
+
+class CubicResampleLimit(ValueError):
+    """A plane :func:`resize_cubic_f64` (and the device entry ts2d_resample_cubic) does not compute: the callers keep the scipy route."""
+
+
+def cubic_axis_taps(n_in: int, n_out: int):
+    """Taps of one axis of :func:`resize_cubic_f64` (``n_in`` -> ``n_out`` samples), all in float64: per output sample the index of
+    the first of four consecutive samples of the PADDED line (``n_in + 2 * CUBIC_PAD`` coefficients) and their four weights,
+    ``(start[n_out] int64, w[n_out, 4] float64)``.  As scipy's NI_ZoomShift does it for ``grid_mode=True``, ``mode='nearest'``, order 3, one
+    rounding per step: ``cc = ((o + 0.5) * (n_in / n_out) - 0.5) + 12``, clamped to the padded extent, ``start = floor(cc) - 1``, and with
+    ``y = cc - floor(cc)``, ``t = 1 - y``: ``w1 = (y*y*(y-2)*3 + 4) / 6``, ``w2 = (t*t*(t-2)*3 + 4) / 6``, ``w0 = t*t*t / 6``, ``w3 = 1 - w0 - w1 - w2``.
+    With this map ``cc`` lies in ``[11.5, n_in + 11.5]`` for every pair of extents, so the four taps stay inside the padded line and scipy's
+    re-mapping of edge taps never runs; that is checked all the same (:class:`CubicResampleLimit`), as are the extents (2 ... CUBIC_MAX_EXTENT).
+    The C entry ts2d_resample_cubic computes the same table on the host."""
+    n_in, n_out = int(n_in), int(n_out)
+    if min(n_in, n_out) < 2 or max(n_in, n_out) > CUBIC_MAX_EXTENT:
+        raise CubicResampleLimit(f"cubic_axis_taps: extent {n_in} -> {n_out} outside 2 ... {CUBIC_MAX_EXTENT}")
+    n_pad = n_in + 2 * CUBIC_PAD
+    cc = np.arange(n_out, dtype=np.float64) + 0.5
+    cc = cc * (np.float64(n_in) / np.float64(n_out))
+    cc = cc - 0.5
+    cc = cc + np.float64(CUBIC_PAD)
+    cc = np.clip(cc, 0.0, np.float64(n_pad - 1))
+    f = np.floor(cc)
+    start = f.astype(np.int64) - 1
+    if start.min() < 0 or start.max() + 3 > n_pad - 1:
+        raise CubicResampleLimit(f"cubic_axis_taps: zoom {n_in} -> {n_out} puts a tap outside the padded line")
+    y = cc - f
+    t = 1.0 - y
+    w = np.empty((n_out, 4), np.float64)
+    w[:, 1] = (y * y * (y - 2.0) * 3.0 + 4.0) / 6.0
+    w[:, 2] = (t * t * (t - 2.0) * 3.0 + 4.0) / 6.0
+    w[:, 0] = t * t * t / 6.0
+    w[:, 3] = 1.0 - w[:, 0] - w[:, 1] - w[:, 2]
+    return start, w
+
+
+def cubic_prefilter_axis0(c: np.ndarray) -> np.ndarray:
+    """scipy's cubic B-spline prefilter (``ni_splines.c: apply_filter``, the initialisation of modes 'nearest' / 'reflect') along axis 0
+    of a float64 ``[n, m]`` array, in place and bit for bit, one rounding per product / sum / quotient:
+    the gain on every sample; ``c[0]``: ``acc = c[0] + z^n * c[n-1]``, then for i = 1 ... n-1 ``acc += z_i * (c[i] + z^n * c[n-1-i])`` with the
+    running product ``z_i`` (``z, z*z, ...``), ``c[0] = acc * (z / (1 - z^n * z^n)) + c[0]``; ``c[i] += z * c[i-1]``; ``c[n-1] *= z / (z - 1)``;
+    ``c[i] = z * (c[i+1] - c[i])``.  scipy accumulates ``acc`` IN ``c[0]``, so the last term of the sum (i = n-1, which reads ``c[0]``) sees the
+    accumulator and not the sample: that is reproduced here, it is worth 6e-4 of an impulse on a line of 2 and 6e-7 on a padded line of 26."""
+    n = c.shape[0]
+    z = CUBIC_POLE
+    c *= CUBIC_GAIN
+    z_n = math.pow(z, float(n))
+    c0 = c[0].copy()
+    acc = c[0] + z_n * c[n - 1]
+    z_i = z
+    for i in range(1, n):
+        acc = acc + z_i * (c[i] + z_n * (acc if i == n - 1 else c[n - 1 - i]))
+        z_i = z_i * z
+    c[0] = acc * (z / (1.0 - z_n * z_n)) + c0
+    for i in range(1, n):
+        c[i] = c[i] + z * c[i - 1]
+    c[n - 1] = c[n - 1] * (z / (z - 1.0))
+    for i in range(n - 2, -1, -1):
+        c[i] = z * (c[i + 1] - c[i])
+    return c
+
+
+def cubic_coefficients_f64(img2d: np.ndarray) -> np.ndarray:
+    """The float64 B-spline coefficients ``[H + 24, W + 24]`` scipy's zoom interpolates: the plane padded by its edge samples, filtered
+    along axis 0 and then along axis 1 (``ndi.spline_filter(np.pad(a, 12, 'edge'), 3, output=float64, mode='nearest')``, bit for bit)."""
+    c = np.pad(np.asarray(img2d), CUBIC_PAD, mode='edge').astype(np.float64)
+    c = cubic_prefilter_axis0(c)
+    return np.ascontiguousarray(cubic_prefilter_axis0(np.ascontiguousarray(c.T)).T)
+
+
+def resize_cubic_f64(img2d: np.ndarray, new_shape) -> np.ndarray:
+    """:func:`resize_like_skimage` with ``order=3`` as a closed form in float64 - nnU-Net's input resample for one float32 plane: pad by 12 edge
+    samples, prefilter both axes (:func:`cubic_coefficients_f64`), per output pixel 16 taps in row-major order (row tap outer, column tap
+    inner), each ``(c * wy) * wx``, summed left to right from 0, every product and sum rounded to float64 (no FMA), ONE rounding to float32,
+    then the clip to the plane's float32 ``[min, max]``.  This is the statement the device entry ts2d_resample_cubic
+    (csrc/kernels_resample_in.h) reproduces bit for bit.
+
+    Compared with scipy 1.15.3 (tests/test_resample_cubic_cpu.py: seeded shapes from 8 x 8 to 1000 x 512, up- and down-sampling, N(0,1),
+    integer-valued, high-dynamic-range and constant planes): every float32 result is equal bit for bit.  Two things had to be found for
+    that, both in the prefilter.  The pole: scipy's binary holds ``sqrt(3.0) - 2.0`` folded by its compiler in extended precision, the
+    float64 nearest to the real number, which is two units in the last place away from Python's ``math.sqrt(3.0) - 2.0``.  And the
+    boundary sum accumulates in ``c[0]`` (:func:`cubic_prefilter_axis0`).  A scipy built by a compiler that folds the constant differently
+    would differ by about one float32 ulp on a few pixels in a million; the CPU test would show it.
+
+    Limits, raised as :class:`CubicResampleLimit`: an extent below 2 or above CUBIC_MAX_EXTENT, a plane with a non-finite sample (scipy
+    computes NaN-polluted lines there; the callers hand such a plane to scipy), a tap outside the padded plane (unreachable, see
+    :func:`cubic_axis_taps`)."""
+    img2d = np.asarray(img2d)
+    if img2d.ndim != 2:
+        raise CubicResampleLimit(f"resize_cubic_f64: a 2-D plane is needed, got {img2d.ndim} axes")
+    sy, wy = cubic_axis_taps(img2d.shape[0], int(new_shape[0]))
+    sx, wx = cubic_axis_taps(img2d.shape[1], int(new_shape[1]))
+    if not np.isfinite(img2d).all():
+        raise CubicResampleLimit("resize_cubic_f64: the plane has a non-finite sample")
+    c = cubic_coefficients_f64(img2d)
+    r = np.zeros((len(sy), len(sx)), np.float64)
+    for i in range(4):
+        rows = c[sy + i]
+        for j in range(4):
+            r = r + (rows[:, sx + j] * wy[:, i, None]) * wx[None, :, j]
+    out = r.astype(img2d.dtype)
+    lo, hi = img2d.min(), img2d.max()
+    out[out < lo] = lo                      # numpy's clip spelled out: a result equal to a bound keeps its own sign of zero
+    out[out > hi] = hi
+    return out
+
+
+def cubic_device_entry():
+    """``ts2d_resample_cubic`` of the engine library, or None where there is none to call (no library built, or one built before the
+    entry existed): the callers then keep the host route, silently - the result is the same."""
+    from . import _lib
+    try:
+        lib = _lib.load()
+    except _lib.EngineLibraryError:
+        return None
+    return getattr(lib, 'ts2d_resample_cubic', None)
+
+
+def resample_planes_cubic_device(data: np.ndarray, new_hw, device: int) -> Optional[np.ndarray]:
+    """All (channel, slice) planes of ``data`` [C, Z, H, W] float32 through ONE ``ts2d_resample_cubic`` call on ``device``: bit for bit
+    :func:`resize_cubic_f64`, hence scipy, per plane.  None when this is no case for the entry - no entry, not float32, an extent outside
+    2 ... CUBIC_MAX_EXTENT, a plane with a non-finite sample (its min / max say so) - and the caller runs scipy.  A call that FAILS raises."""
+    from . import _lib
+    entry = cubic_device_entry()
+    c, z, h, w = data.shape
+    oh, ow = int(new_hw[0]), int(new_hw[1])
+    if entry is None or data.dtype != np.float32 or c * z < 1 or min(h, w, oh, ow) < 2 or max(h, w, oh, ow) > CUBIC_MAX_EXTENT:
+        return None
+    if c * z * (h + 2 * CUBIC_PAD) * (w + 2 * CUBIC_PAD) > 1 << 28 or c * z * oh * ow > 1 << 28:
+        return None
+    src = np.ascontiguousarray(data).reshape(c * z, h, w)
+    lo_hi = np.stack([src.min(axis=(1, 2)), src.max(axis=(1, 2))], axis=1).astype(np.float32)
+    if not np.isfinite(lo_hi).all():
+        return None
+    out = np.empty((c, z, oh, ow), np.float32)
+    _lib.check(entry(int(device), src.ctypes.data, c * z, h, w, oh, ow, lo_hi.ctypes.data, out.ctypes.data), 'ts2d_resample_cubic')
+    return out
+
+
+def resample_data_to_shape(data: np.ndarray, new_shape, order: int = 3, device: Optional[int] = None) -> np.ndarray:
     """``resample_data_or_seg_to_shape(data, new_shape, current_spacing, new_spacing, is_seg=False, order=3, order_z=0)`` for the
     2-D configurations ts2d uses ([C, 1, H, W] with the 999 pseudo-spacing): upstream finds the 999 axis anisotropic and
-    resamples every (channel, slice) in-plane with ``resize``; the slice count does not change [UPSTREAM-RECALL]."""
+    resamples every (channel, slice) in-plane with ``resize``; the slice count does not change [UPSTREAM-RECALL].
+    ``device``: index of the GPU that resamples order 3 (:func:`resample_planes_cubic_device`, the same float32 values bit for bit);
+    None, another order or a plane outside that entry's limits: scipy on the host."""
     new_shape = tuple(int(v) for v in new_shape)
     if tuple(data.shape[1:]) == new_shape:
         return data
     if data.shape[1] != new_shape[0]:
         raise NotImplementedError(f"resampling along the slice axis ({data.shape[1]} -> {new_shape[0]} slices) is not implemented (2-D configurations only)")
+    if device is not None and order == 3:
+        out = resample_planes_cubic_device(data, new_shape[1:], device)
+        if out is not None:
+            return out
     out = np.empty((data.shape[0],) + new_shape, dtype=data.dtype)
     for c in range(data.shape[0]):
         for z in range(data.shape[1]):
@@ -228,6 +380,7 @@ class DefaultPreprocessor:
         schemes = getattr(configuration_manager, 'normalization_schemes', None) or ['ZScoreNormalization'] * data.shape[0]
         use_mask = getattr(configuration_manager, 'use_mask_for_norm', None) or [False] * data.shape[0]
         dz = properties.pop('device_zscore', None)
+        device_resample = properties.pop('device_resample', None)     # GPU index for the order-3 resample below (HIPModel sets it), None: host
         if dz is not None and not _device_zscore_applies(dz, data, bbox, tf, schemes, use_mask):
             dz = None
         fip = (getattr(plans_manager, 'plans', None) or {}).get('foreground_intensity_properties_per_channel', {})
@@ -237,7 +390,7 @@ class DefaultPreprocessor:
                 continue
             data[c] = normalize_channel(data[c], schemes[c], bool(c < len(use_mask) and use_mask[c]), nzmask, fip.get(str(c)))
         if list(new_shape) != list(data.shape[1:]):       # the plan's spacing differs from the image's: resample (order 3), AFTER normalising
-            data = resample_data_to_shape(data, new_shape, order=3)
+            data = resample_data_to_shape(data, new_shape, order=3, device=device_resample)
         return data, None, properties
 
     def run_case(self, image_files: List[str], seg_file: Optional[str], plans_manager, configuration_manager, dataset_json):
