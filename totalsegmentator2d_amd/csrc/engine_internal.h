@@ -1,0 +1,206 @@
+// Host-side internals of libts2d_engine.so, shared by program.cpp, pack_weights.cpp, dispatch.cpp and engine.hip: the program (tensors, ops),
+// the kernel choice of an op, the workspace layout and the engine handle.  Not installed, not part of the ABI (include/ts2d_engine.h is).
+// No device code here or in the .cpp files: they build without an offload pass.  engine.hip is the one file that holds kernels.
+#pragma once
+#include "../../include/ts2d_engine.h"
+#include <hip/hip_runtime_api.h>
+
+#include <atomic>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)      // (the library exports the C-ABI only)
+namespace ts2d {
+
+// thread-local last error (ts2d_last_error): ONE definition for every object of the library (program.cpp)
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+const char* last_error();
+
+constexpr size_t kWsHeader = 256;         // bytes in front of the activation plan: [0] = token of the last run inside this memory
+
+enum OpType { OP_CONV = 0, OP_CONVT = 1, OP_HEAD = 2 };
+
+struct Tensor {            // an activation tensor of the program (NHWC fp32)
+    std::string name;
+    int C = 0, level = 0;
+    int Cu = 0;            // channels of the CALLER's architecture (C is the width the kernels run: rounded up to 32 - pad_arch)
+    int ly = 0, lx = 0;    // log2 of the cumulative stride along H / W: extent (H >> ly, W >> lx) (per-axis strides, ABI 7)
+    bool normed = false;   // raw conv output that carries InstanceNorm scale/shift
+    float* data = nullptr; float* scale = nullptr; float* shift = nullptr;
+    size_t bytes = 0;      // of its buffer in the workspace plan (0: none)
+    bool resident = false; // its buffer still holds the values of the last run (no later tensor of the run was placed on it)
+};
+
+struct Op {
+    OpType type; std::string name;
+    int src, skip, dst;           // tensor indices (skip = -1 if none)
+    int cin, cin_skip, cout, stride, level;      // stride: 1 = (1, 1), 2 = (2, 2) - the dedicated kernels; 3 = anisotropic (generic kernel only)
+    int sy = 1, sx = 1;           // stride along H / W (conv: of the conv; transposed conv: kernel = stride of the upsampling)
+    int ly = 0, lx = 0;           // shifts of the op's level (= of its output tensor; the head: level 0)
+    int ck;                       // Cin chunk of the packed weight layout
+    size_t blob_w, blob_b, blob_g, blob_be;     // offsets (floats) into the PyTorch-layout blob
+    size_t dev_w, dev_b, dev_g, dev_be;         // offsets (floats) into the device weight arena
+    size_t dev_w_floats;
+    bool split_ok = false;        // eligible for the split-fp16 kernel (3x3, stride 1, Cin % 16 == 0, not the net input)
+    size_t dev_wh = 0;            // offset (floats) of the split-fp16 weights in the arena
+    size_t dev_wh32 = 0;          // offset (floats) of the fp16 weights in 32-channel chunks (precision mode f16, kernels_h32.h)
+    bool h32_ok = false;
+    size_t dev_ws = 0;            // offset (floats) of 1 / (power-of-two pre-scale of the split weights)
+    size_t dev_wp = 0;            // offset (floats) of the split-fp16 weights in plane order [chunk16][column tile][tap][hi,lo][h][column][8 halves]
+                                  // (conv3x3_f16x3_qp; stride-1 split_ok convs)
+    bool s2v2_ok = false;         // stride-2 block: 512-thread kernel of kernels_s2v2.h
+    size_t dev_w2 = 0;            // offset (floats) of its weight image [chunk16][column tile][tap][hi,lo][h][column][8 halves]
+    int bn2 = 0;                  // its column tile (128 or 64)
+    bool res_ok = false;          // 32 -> 32 stride-1 block: resident-weight persistent kernel (kernels_res32.h)
+    size_t dev_wres = 0;          // offset (floats) of its weight image [tap][hi,lo][g][cout][8 halves]
+    bool upc_ok = false;          // decoder c0 block whose "up" half is composed with the preceding ConvTranspose2d (kernels_upc.h)
+    int up_idx = -1;              // ... index of that transposed conv in the program
+    size_t dev_wc = 0;            // composed weights [chunk Cb/16][column tile][16 = (A,B,dI,dJ)][hi,lo][h][column][8 halves]
+    size_t dev_wk = 0;            // skip half of the 3x3 weights [chunk Cs/16][column tile][tap][hi,lo][h][column][8 halves]
+    size_t dev_wcs = 0;           // 1 / (their common power-of-two pre-scale)
+    size_t dev_bvar = 0;          // [9 = (ry, rx)][Cout] bias variants
+    bool up0_ok = false;          // ... with 64 coarse, 32 skip and 32 output channels (level 0 of the canonical net): kernels_up0.h
+    size_t dev_w0c = 0;           // composed weights in fragment order [parity 4][k-step 8][hi,lo][cb 2][lane 64][8 halves]
+    size_t dev_w0k = 0;           // skip half, resident image [tap 9][hi,lo][g 4][cout 32][8 halves]
+    bool first_direct = false;    // first conv block handled by conv3x3_first (reads the NCHW boundary tensor)
+    size_t dev_wraw = 0;
+};
+
+struct Launch { std::string name, kernel; int ksplit = 1; hipEvent_t e0 = nullptr, e1 = nullptr; };
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Pixel tiling of one level: tile = NIMG images x TH x TW pixels, NIMG * TH * TW <= 256 (a workgroup's 256 GEMM rows).
+struct TileGeom { int TH, TW, NIMG, lgTH, lgTW, tiles_x, tiles_y, n_mtiles, PH, PW; };
+
+enum Kern { K_NONE = 0, K_FUSED_AWAY, K_FIRST, K_FIRST_STATS, K_EXACT, K_S1_GENERIC, K_S1_ONE, K_S1_QP, K_S1_H32, K_S1_H2, K_S1_RES32, K_S1_RES32F,
+            K_S2_V2, K_S2_ONE, K_S2_GENERIC, K_T_ONE, K_T_GENERIC, K_UP0, K_UPQ, K_UPC, K_UPC_H, K_UPC_H2, K_HEAD_MFMA, K_HEAD_1X1 };
+
+struct Choice {
+    Kern k = K_NONE;
+    TileGeom g{};               // the pixel tiling the kernel walks
+    int bn = 0;                 // output columns per workgroup
+    int ksplit = 1;
+    bool fused_stats = false;   // per-tile partial statistics come out of the kernel's epilogue (else stats_direct / splitk_reduce_stats)
+    int ppt = 1;                // ... partials per tile and channel (conv3x3_up0: one per wave)
+    bool first_full = false;    // (K_FIRST*) complete one-image 256-pixel tiles: the persistent variant
+    bool flex = false;          // (K_UPC / K_UPC_H / K_S2_V2) the level is no multiple of 8 x 32: the FLEX instance on the tile c.g
+    bool first_split = false;   // (K_FIRST*) the K = 9 C contraction as one fp16 hi / lo split product (kernels_first.h SPLIT; else the exact fp32 MFMA)
+    bool k32 = false;           // (K_S2_V2) 16-bit mode: chunks of 32 channels (kernels_s2v2.h K32)
+    int npp = 0, nch = 0;       // (K_S2_V2) LDS planes per (tap, k half), channel chunks
+    int seg = 0;                // (K_UP0 / K_S1_RES32*) tiles per workgroup segment (segment_tiles)
+    int ks = 0;                 // (K_UPC_H / K_UPC_H2) coarse k-steps per staged chunk
+    const char* name = "";      // what ts2d_engine_op_kernel reports for the op (tests and scripts/pmc_traffic.py key on these strings)
+};
+
+inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+inline int ct_total(const Op& op) { return op.cin + op.cin_skip; }
+
+}  // namespace ts2d
+
+#pragma GCC visibility pop
+
+struct ts2d_engine {
+    ts2d_arch_desc arch{};
+    int lvl_y[TS2D_MAX_STAGES] = {0}, lvl_x[TS2D_MAX_STAGES] = {0};      // per stage: log2 of the cumulative stride along H / W
+    int device = 0;
+    int cin_pad = 8;
+    std::vector<ts2d::Tensor> tensors;
+    std::vector<ts2d::Op> ops;
+    size_t blob_floats = 0;
+    ts2d_arch_desc user_arch{};        // the descriptor the caller gave; `arch` is what the kernels run (pad_arch)
+    bool padded = false;
+    size_t user_blob_floats = 0;       // floats of the caller's blob (== blob_floats unless padded)
+    float* d_weights = nullptr; size_t weight_floats = 0;
+    bool weights_ready = false;
+    int precision = TS2D_PRECISION_F32_SPLIT_F16X3;
+    int num_cus = 256;
+    int tile_half = 0;            // sliding-window blend order (ts2d_engine_set_tile_dtype): 0 = fp32 tile (reference CPU path)
+    int tiled_inf = 0;            // the last predict_tiled produced an infinite aggregated logit (ts2d_engine_tiled_inf_flag)
+    // Kernel-dispatch options (ts2d_engine_set_option; ABI 6).  Each selects between two complete, parity-tested kernels for the ops it
+    // names; the defaults are the measured-fastest ones.  They are per-HANDLE state set through the C-ABI - the caller's environment
+    // never changes which kernel runs.
+    bool use_one = true;          // "one": one-image-tile kernels (0: the generic ones; also switches every kernel built on them off)
+    bool use_s2v2 = true;         // "s2v2": 512-thread stride-2 kernel
+    bool use_q = true;            // "q": persistent 512-thread double-buffered stride-1 kernel on 16 x 32 tiles (0: conv3x3_f16x3_one)
+    bool use_h2 = true;           // "h2": 16-bit plain C -> C blocks on 16 x 32 tiles (0: conv3x3_h32)
+    bool use_uh2 = true;          // "uh2": 16-bit composed block on 16 x 32 tiles (0: conv3x3_upc_h)
+    bool use_s2k32 = true;        // "s2k32": 16-bit mode - the 512-thread stride-2 kernel on 32-channel chunks (0: 16-channel chunks)
+    bool use_sbk = true;          // "sbk": small batches - split-K (and the two-kernel decoder entry) where the preferred kernel would leave most CUs idle (fill_ksplit)
+    bool use_first_split = true;  // "first_split": the first block's contraction as one fp16 hi / lo split product (kernels_first.h SPLIT; 0: exact fp32 MFMA)
+    bool use_up0 = true;          // "up0": dedicated persistent kernel of the level-0 composed block (0: conv3x3_upc<32>)
+    int u0seg = 0;                // "u0seg": tiles per workgroup segment of conv3x3_up0 (0: chosen from the grid; tests force segments that end inside an image)
+    bool use_upc = true;          // "upc": decoder c0 blocks composed with their transposed conv (0: two kernels)
+    bool use_res = true;          // "res": resident-weight kernel of the 32 -> 32 blocks
+    bool use_fuse0 = true;        // "fuse0": first block recomputed inside the second (statistics-only pre-pass + conv3x3_res32 fused variant)
+    bool diagnosing = false;      // the re-run of ts2d_engine_check: the first block as its own kernel whatever "fuse0" says (its output can be scanned and named)
+    int use_flex2 = 2;            // "flex2": conv3x3s2_v2 on level-dividing tiles where the level is no multiple of 8 x 32 (0: off, 1: 16-bit mode only, 2: both)
+    bool use_flex = true;         // "flex": the composed decoder entry on extent-following tiles at levels that are no multiple of 8 x 32 (0: two kernels there)
+    int dbg = 0;                  // TS2D_DBG (the one environment switch left): timing ablations / in-kernel phase stamps of diagnostic runs
+    unsigned long long* d_prof = nullptr;     // TS2D_DBG=256: in-kernel phase counters, 8 per op (diagnostic)
+    std::vector<char> fused_away; // per op of the last run: 1 = its output tensor was not materialised (composed into the next op)
+    // workspace
+    char* d_ws = nullptr; size_t ws_bytes = 0; int wsB = 0, wsH = 0, wsW = 0;
+    bool ws_external = false;     // d_ws is the caller's memory (ts2d_engine_set_workspace): shared by the engines of a sub-model set
+    uint32_t ws_token = 0;        // ... token this engine's last run wrote into its header (g_ws_generation)
+    // the kernel choices of the last (B, H, W, precision, options): a forward of the same shape does not search tile shapes again
+    // (62 launches per forward: at B = 1 the host side is a visible part of the 2.5 ms)
+    std::vector<ts2d::Choice> plan; int planB = 0, planH = 0, planW = 0, plan_prec = -1; unsigned plan_gen = 0, opt_gen = 1; bool plan_full = false;
+    char* d_stage = nullptr; size_t stage_bytes = 0;      // host-buffer forwards only (ensure_staging)
+    bool ws_full = false;         // the activation plan of the workspace is the full-batch dispatch's (ensure_workspace)
+    bool last_full = false;       // the last run took the full-batch dispatch (ts2d_engine_check re-runs it the same way)
+    int ws_precision = -1; bool ws_keep = false;      // the activation plan of the workspace was made for this mode (composition depends on it)
+    bool keep_activations = false;                    // ts2d_engine_set_keep_activations: one buffer per tensor (debug access, full diagnosis)
+    float* d_part = nullptr;
+    float* d_partial = nullptr;   // split-K partial outputs
+    float* d_up = nullptr;        // scratch for ONE upsampled tensor (small batches: a decoder entry that the reserved batch's plan composes runs as two kernels)
+    float* d_in_stage = nullptr; float* d_logit_stage = nullptr; uint32_t* d_mask_stage = nullptr;
+    hipStream_t stream = nullptr;
+    bool profiling = false;
+    std::vector<ts2d::Launch> launches; size_t n_launched = 0;
+    int lastB = 0, lastH = 0, lastW = 0; hipStream_t last_stream = nullptr; bool last_f16 = false;
+    char* d_sw = nullptr; size_t sw_bytes = 0;     // sliding-window scratch (image, batch, tile logits, outputs)
+    // The activation workspace is shared by every call on this handle, whatever stream the caller passes: the end of each run
+    // is marked with an event, and a run issued on ANOTHER stream first waits for it (no host synchronisation).
+    hipEvent_t ws_event = nullptr; hipStream_t ws_stream = nullptr; bool ws_busy = false;
+    int* d_flags = nullptr;       // [0]: a logit of the last run was inf / NaN (set by the head kernels); [1]: scratch of the diagnosis
+    bool checked_input = false; const float* last_input = nullptr;      // (synchronous paths: the staged input can be scanned too)
+};
+
+#pragma GCC visibility push(hidden)
+namespace ts2d {
+
+// ---- program.cpp: the descriptor as a program of ops over tensors, and the device weight arena's layout
+ts2d_arch_desc pad_arch(const ts2d_arch_desc& a, bool& padded);
+void expand_blob(const ts2d_arch_desc& ua, const ts2d_arch_desc& pa, const float* ub, std::vector<float>& pb);
+int build_program(ts2d_engine* e);
+int tensor_index(ts2d_engine* e, const std::string& name);      // -1: no such tensor
+
+// ---- pack_weights.cpp: PyTorch-layout blob -> packed device layouts (host staging buffer `out`, weight_floats long)
+void pack_weights(const ts2d_engine* e, const float* blob, float* out);
+float f16_to_f32(uint16_t hb);
+
+// ---- dispatch.cpp: which kernel serves an op, and the workspace that follows from it
+// Small-batch split-K (fill_ksplit): S x B x HW x Cout of any op the rule splits (n_wgs S < 2 x 256 CUs, <= 256 pixels x 64 columns each)
+constexpr size_t kSbkElems = (size_t)2 * 256 * 256 * 64;
+// `full`: the run asks for the full-batch dispatch whatever its size (ts2d_engine_predict_tiled_batch: a row's bits must not depend on its batch).
+// No default anywhere: every caller names the dispatch it means.
+constexpr bool kBySize = false, kFullBatch = true;
+
+Choice choose(const ts2d_engine* e, size_t oi, int B, int H, int W, bool full);
+std::vector<Choice> choose_all(const ts2d_engine* e, int B, int H, int W, bool full);
+const std::vector<Choice>& planned(ts2d_engine* e, int B, int H, int W, bool full);
+
+struct ActPlan { std::vector<size_t> off, size; std::vector<char> used, reused; size_t bytes = 0; };
+// Layout of the activation workspace for (B, H, W) under the engine's current precision mode, options and keep flag.
+struct WsLayout {
+    ActPlan plan; std::vector<size_t> o_sc, o_sh; size_t o_part = 0, o_pk = 0, o_up = 0, bytes = 0;
+    bool has_up = false;      // the scratch of one upsampled tensor exists at o_up (small batches: a decoder entry the reserved batch's plan composes)
+};
+WsLayout workspace_layout(const ts2d_engine* e, int B, int H, int W, bool full);
+
+}  // namespace ts2d
+#pragma GCC visibility pop

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "tile_dims.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -68,8 +69,7 @@ __device__ __forceinline__ void stat_tile_store(const float* red, int nwaves, in
 #define TS2D_PACKED_F32      // (the host pass of hipcc parses the kernels too and does not know the feature)
 #endif
 
-constexpr int kBlock = 256;   // threads per workgroup (4 waves, one per SIMD)
-constexpr int kBM = 256;      // output pixels per workgroup tile
+// (kBlock, kBM - threads and output pixels per workgroup tile: tile_dims.h)
 
 // n / d for 0 <= n < 2^22 by the float reciprocal inv_d = 1.0f / d (correctly rounded, computed on the host): exact, because
 // (n + 0.5) / d is at least 0.5 / d away from an integer and the two roundings move it by less than (n + 0.5) 2^-23 / d.
