@@ -2,7 +2,7 @@
 """bench.py - BASELINE.json metric: 2-ch 512x512 slices/sec on N MI355X (config 2: synthetic batch=64, one ts2d-v2
 sub-model (K=18), fp32).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: either under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`, or plain
      `python bench.py --gpus N`: with no WORLD_SIZE in the environment the script starts that launcher itself as a CHILD process -
      one rank per GPU, the reference's counterpart being its `mp.Pool` of workers, ts2d/core/inference/predictor.py:79-86 -
@@ -16,11 +16,17 @@ Rank 0 prints ONE JSON line.  The inputs come from a fixed seed, so the same arg
 `--dump-outputs DIR` writes what the last timed step left in the caller's buffers (rank 0: DIR/logits.npy, DIR/mask.npy; see
 dump_outputs), so that two builds of the library can be compared output for output.
 
+A plain run does what the headline needs and no more: set-up, warm-up, the timed steps, the dump if asked for, the line.  The
+per-kernel HIP events sampled inside the timed steps are part of the step definition, so the roofline blocks computed from them
+come with every line at no cost.  `--full` adds what takes runs of its own, outside the timed region: the other precision modes
+with their oracle errors and roofline blocks, the other extents (`geometry`), BASELINE configurations 3 and 5, the live oracle
+check of the timed batch and the CPU baseline; on N > 1 GPUs also the config-4 stream as `stream_10k`.  `--no-cpu-baseline`,
+`--no-other-modes` and `--no-extra-legs` take single legs out of a `--full` run again.
+
 Other BASELINE configurations (same contract, ONE JSON line each; `config.workload` names the configuration):
     python bench.py --workload config3          five ts2d-v2 sub-models (117 labels) on one batch of 128, 16-bit mode
     python bench.py --workload config4 [--stream 10000]   (N ranks) contiguous blocks of a 10k-slice stream generated on the
                                                 device from (seed, slice index); strong scaling; weight broadcast reported
-The default (config 2) line of an N > 1 run also carries the config-4 result as `stream_10k`.
 """
 from __future__ import annotations
 
@@ -374,16 +380,19 @@ def dry_run(args, backend: str):
     dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--batch', type=int, default=64, help='slices per GPU per step (config 2: 64)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='config 2: after the timed steps also run every leg the headline does not need (other precision modes, other extents, '
+                         'configs 3 and 5, oracle check of the timed batch, CPU baseline; N > 1: the config-4 stream); off by default')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the oracle checks and the CPU baseline')
     ap.add_argument('--no-profile', action='store_true', help='do not bracket kernels with HIP events')
-    ap.add_argument('--no-other-modes', action='store_true', help='skip the exact / f16 legs (profiling runs: only the timed mode launches kernels)')
-    ap.add_argument('--no-extra-legs', action='store_true', help='skip the geometry / config3 / config5 legs of the default line')
+    ap.add_argument('--no-other-modes', action='store_true', help='--full without the exact / f16 legs (and without the legs of --no-extra-legs)')
+    ap.add_argument('--no-extra-legs', action='store_true', help='--full without the geometry / config3 / config5 legs')
     ap.add_argument('--workload', choices=('config2', 'config3', 'config4'), default='config2')
     ap.add_argument('--stream', type=int, default=None, help='config 4: total slices of the synthetic stream (default 10000)')
     ap.add_argument('--precision', choices=('split', 'exact', 'f16'), default=None,
@@ -391,14 +400,20 @@ def main():
                          "f16: fp16 storage + one fp16 MFMA product (BASELINE configs 3/5, outside the fp32 parity tolerance)")
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='config 2: after the timed steps rank 0 writes the logits and masks of the last one (a fixed sample) as DIR/<name>.npy')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.stream is not None and args.workload == 'config2':
         args.workload = 'config4'
     if args.precision is None:
         args.precision = 'f16' if args.workload == 'config3' else 'split'
     if args.dump_outputs is not None and (args.workload != 'config2' or os.environ.get('TS2D_BENCH_DRYRUN')):
         ap.error('--dump-outputs is implemented for the config-2 workload on a GPU only')
+    if not args.full:                 # a plain run: no leg besides the timed steps
+        args.no_cpu_baseline = args.no_other_modes = args.no_extra_legs = True
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # not under a launcher: start one (child process), relay its exit code; nothing below runs in this process
         raise SystemExit(self_launch(args.gpus))
@@ -531,7 +546,7 @@ def main():
         dump_outputs(torch, args.dump_outputs, logits, mask)
 
     stream_res = None
-    if world > 1:            # config 4 on the same ranks (outside the timed region above): 10k-slice stream, contiguous blocks
+    if world > 1 and args.full:            # config 4 on the same ranks (outside the timed region above): 10k-slice stream, contiguous blocks
         if profile:
             engine.set_profiling(False)
         # Isolated from the primary result: a failure on ANY rank is agreed on by all ranks (one max-reduce of a flag, so no rank

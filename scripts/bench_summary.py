@@ -1,4 +1,4 @@
-"""One-paragraph summary of a bench.py JSON line (profiles/rNN_bench_runs.txt): python scripts/bench_summary.py <bench.json> [label]"""
+"""One-paragraph summary of a `bench.py --full` JSON line (profiles/rNN_bench_runs.txt): python scripts/bench_summary.py <bench.json> [label]"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 lab = sys.argv[2] if len(sys.argv) > 2 else ''

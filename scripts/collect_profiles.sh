@@ -7,7 +7,7 @@ set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/${1:-gpurun_out/prof}
 mkdir -p "$O"
-python3 "$R/bench.py" > "$O/bench.json" 2> "$O/bench.err"
+python3 "$R/bench.py" --full > "$O/bench.json" 2> "$O/bench.err"
 cd /tmp && export TMPDIR=/tmp
 A="--steps 10 --warmup 3 --no-cpu-baseline --no-other-modes --no-profile"      # (13 forwards: one cold launch no longer carries 4-8 % of a kernel's average - VERDICT r4 weak #11)
 F="--output-format csv"
