@@ -230,6 +230,40 @@ typedef struct {
 int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images,
                                      int patch_h, int patch_w, int mirror_mask, const uint16_t* gaussian_f16, int full_batch);
 
+/* ts2d_engine_predict_tiled_export for a FOLD ENSEMBLE: the folds of a model folder (reference: `folds` of model.json go straight into the
+ * predictor, ts2d/core/inference/nnu.py:31-33,146-165) as one call, the mean of their logits taken on the device.  Replaces upstream's
+ * predict_logits_from_preprocessed_data (reached from ts2d/core/inference/prediction_worker.py:209) - per fold load the parameters and
+ * `prediction += predict_sliding_window_return_logits(data)`, then `prediction /= n` when n > 1, in the float16 of the aggregated
+ * logits - and the export behind it, so that neither F x K half planes per case travel to the host nor numpy adds halves there.
+ *   engines        n_engines handles (1..32), one per fold, in fold order; all on one device, with the same input channels, num_classes,
+ *                  precision mode and tile dtype, weights ready.  The other layers may differ.
+ *   per fold f     exactly the sliding window ts2d_engine_predict_tiled_export(engines[f], ...) runs: the same row packing, the same
+ *                  chunks of at most 64 rows, the same dispatch (`full_batch` and its determinism rule mean what they mean there), so
+ *                  fold f's aggregated half logits are byte for byte what the single-engine entries give for that engine.
+ *   the mean       one kernel (csrc/kernels_fold.h) over the F half buffers, per element and in fold order:
+ *                  acc = x[0]; acc = half(float(acc) + float(x[f])) for f = 1 .. F-1; acc = half(float(acc) / float(half(F))) - the fp32
+ *                  add and the correctly rounded fp32 division of numpy's float16 `+` and `/`, each rounded to nearest even, bit for bit
+ *                  (+-inf, subnormals and signed zeros as IEEE has them; a NaN stays a NaN).  n_engines == 1: no mean kernel - the
+ *                  call is byte-identical to ts2d_engine_predict_tiled_export on that engine (`exports` NULL, full_batch != 0: to
+ *                  ts2d_engine_predict_tiled_batch); upstream divides only when n > 1.
+ *   outputs        of the MEAN: images[i].logits_f16 and seg_u8 (the predicate on the mean), exports[i].seg_u8 and logits_f32 (the mean
+ *                  resampled back) as in the single-engine entry.  `exports` may be NULL: every image then names at least one output.
+ *   inf_flag       images[i].inf_flag is the OR over the folds of fold f's flag for image i - upstream looks at every fold's aggregated
+ *                  array, not at the mean; ts2d_engine_tiled_inf_flag(engines[f]) is fold f's own OR over the images.
+ * Every argument is validated before any device work and nothing is written on an error: a null array, n_engines outside 1..32, a
+ * null handle ("engine 2 is null"), a fold whose weights are not ready (TS2D_ERR_STATE, "fold 1: weights not loaded"), folds on
+ * different devices or differing in input channels, num_classes, precision mode or tile dtype (the fold and the property named), and
+ * per image everything ts2d_engine_predict_tiled_export rejects, in the same words.  n_images == 0 returns TS2D_OK and does nothing.
+ * The folds run one after the other on the FIRST engine's stream, and engines[0] holds all scratch: that of
+ * ts2d_engine_predict_tiled_export ONCE (tile logits and gathered batch, R x (K + C) x patch_h x patch_w x 4 bytes, the uploaded inputs,
+ * the export's outputs) - only the half outputs exist per fold: n_engines x K x Hp x Wp x 2 bytes summed over the images, plus
+ * 4 bytes per (fold, image).  Each fold keeps its own activation workspace; the caller may give the folds a shared one with
+ * ts2d_engine_set_workspace, which is legal here because they run on one stream.
+ * Synchronous: ONE stream synchronise per call, then ts2d_engine_check for every fold; a failure is reported as "fold <f>: <message>".
+ * (Added under ABI 9: a new symbol only, so ts2d_abi_version() stays 9.) */
+int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_export* exports,
+                                       int n_images, int patch_h, int patch_w, int mirror_mask, const uint16_t* gaussian_f16, int full_batch);
+
 /* Blend order of ts2d_engine_predict_tiled (upstream `prediction *= gaussian; predicted_logits[sl] += prediction` with
  * float16 `predicted_logits`; reached from ts2d/core/inference/prediction_worker.py:209):
  *   TS2D_TILE_F32 (default) the reference's CPU path (nnu.py:161-163: device=cpu when torch.cuda.is_available() is false - no autocast): the tile prediction is
@@ -248,7 +282,8 @@ int ts2d_engine_set_tile_dtype(ts2d_engine* e, int mode);
  * forward does: ts2d/core/inference/prediction_worker.py:209.) */
 int ts2d_engine_set_keep_activations(ts2d_engine* e, int enable);
 
-/* 1 if the last ts2d_engine_predict_tiled / ts2d_engine_predict_tiled_batch / ts2d_engine_predict_tiled_export call (the OR over its images) produced an infinite
+/* 1 if the last ts2d_engine_predict_tiled / ts2d_engine_predict_tiled_batch / ts2d_engine_predict_tiled_export call (the OR over its images; after
+ * ts2d_ensemble_predict_tiled_export: this fold's own) produced an infinite
  * aggregated float16 logit - upstream's
  * "Encountered inf in predicted array" check of predict_sliding_window_return_logits (reached from
  * ts2d/core/inference/prediction_worker.py:209), evaluated on the device instead of a host pass over the array. */

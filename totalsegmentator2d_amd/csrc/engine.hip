@@ -18,6 +18,7 @@
 #include "kernels_upc_h.h"
 #include "kernels_upc_h2.h"
 #include "kernels_sw.h"
+#include "kernels_fold.h"
 #include "kernels_resample.h"
 #include "kernels_resample_in.h"
 #include "kernels_project.h"
@@ -850,7 +851,18 @@ int ts2d_engine_forward(ts2d_engine* e, const float* input, int B, int H, int W,
 // depend on its batch-mates), the single-image entry for the size-dependent one.  `name_images`: a message names the image it is about.
 // `exports` (ts2d_engine_predict_tiled_export; else null): one descriptor per image - behind the last aggregate ONE sw_resample_threshold
 // launch resamples every image's half logits to its export extent where they lie in the scratch.
+// `engines[0 .. F)` (ts2d_ensemble_predict_tiled_export; the other entries are F = 1): the folds of an ensemble, one after the other on
+// the FIRST engine's stream and in its scratch - the chunk loop once per fold, sw_aggregate into the fold's own half slot and inf
+// flags, then ONE sw_fold_mean (kernels_fold.h) into slot 0, on which the tail below runs as it does on a single fold's logits.  Only
+// the half slots and the flags exist F times.  `name_folds`: a fold's failed reserve or result check is reported as "fold <f>: ...".
 constexpr int kSwChunkRows = 64;
+constexpr int kMaxFolds = 32;
+
+static int name_fold(int rc, bool name_folds, int f) {
+    if (rc == TS2D_OK || !name_folds) return rc;
+    const std::string msg = last_error();
+    return fail(rc, "fold %d: %s", f, msg.c_str());
+}
 
 // Taps of one axis of the order-1 resample (n_in -> n_out samples; preprocess.linear_axis_taps is the same statement in numpy, pinned
 // to scipy): cc = (o + 0.5) * (n_in / n_out) - 0.5, i0 = floor(cc), w1 = cc - i0, all in float64; the coordinate is not clamped, the
@@ -870,8 +882,10 @@ static void rs_axis_taps(int n_in, int n_out, int origin, RsTap* t) {
     }
 }
 
-static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
-                              int mirror_mask, const uint16_t* gaussian_f16, bool full, bool name_images, const char* entry) {
+static int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images,
+                              int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, bool full, bool name_images, bool name_folds,
+                              const char* entry) {
+    ts2d_engine* e = engines[0];
     if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "%s: bad patch %dx%d", entry, ph, pw);
     const int C = e->arch.input_channels, K = e->arch.num_classes;
     int vflip[4] = {0, 0, 0, 0}, V = 1;
@@ -880,7 +894,7 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, const ts
     else if (mirror_mask & 2) { vflip[1] = 2; V = 2; }
     const int vflips = vflip[0] | (vflip[1] << 8) | (vflip[2] << 16) | (vflip[3] << 24);
     long long n_tiles_all = 0, n_taps_all = 0;
-    bool any16 = false, anyseg = false, any_rs8 = false, any_rs32 = false;
+    bool any16 = F > 1, anyseg = false, any_rs8 = false, any_rs32 = false;      // (the mean is taken over the half buffers)
     for (int i = 0; i < n_images; ++i) {
         const ts2d_tiled_image& im = images[i];
         char pre[24] = "";
@@ -958,6 +972,7 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, const ts
         if ((long long)c.gblocks >= (1LL << 31) || (long long)c.ablocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: a chunk exceeds 2^31 blocks", entry);
     }
     log_rows = std::max<long long>(log_rows, cap_rows);
+    if (F > 1 && blocks_of(out_elems >> 3) >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the fold mean exceeds 2^31 blocks", entry);
     // ---- the export: one segment per image (its half logits are segs' out_off), the taps of its rows then of its columns
     std::vector<RsSeg> rsegs;
     std::vector<RsTap> rtaps;
@@ -979,7 +994,7 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, const ts
         }
         if (rs_blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the export exceeds 2^31 blocks", entry);
     }
-    TRY(reserve_checked(e, cap_rows, ph, pw, full));
+    for (int f = 0; f < F; ++f) TRY(name_fold(reserve_checked(engines[f], cap_rows, ph, pw, full), name_folds, f));
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = e->stream;
     // ---- the descriptor table and every tile origin: one host blob, one copy
@@ -995,10 +1010,10 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, const ts
             ty += images[i].n_tiles; tx += images[i].n_tiles;
         }
     }
-    // ---- scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs | uint8 outputs | flags | resampled uint8 | resampled float]
+    // ---- scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs x F | uint8 outputs | flags x F | resampled uint8 | resampled float]
     const size_t o_tab = take(tab_bytes), o_g = take((size_t)ph * pw * 2), o_imgs = take((size_t)img_floats * 4);
     const size_t o_batch = take((size_t)cap_rows * C * ph * pw * 4), o_log = take((size_t)log_rows * K * ph * pw * 4);
-    const size_t o_o16 = take(any16 ? (size_t)out_elems * 2 : 0), o_seg = take(anyseg ? (size_t)out_elems : 0), o_flag = take((size_t)n_images * 4);
+    const size_t o_o16 = take(any16 ? (size_t)F * out_elems * 2 : 0), o_seg = take(anyseg ? (size_t)out_elems : 0), o_flag = take((size_t)F * n_images * 4);
     const size_t o_rs8 = take(any_rs8 ? (size_t)rs_elems : 0), o_rs32 = take(any_rs32 ? (size_t)rs_elems * 4 : 0);
     if (off > e->sw_bytes) {                                  // grown before the first launch only
         HIP_TRY(hipStreamSynchronize(st));
@@ -1016,7 +1031,7 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, const ts
     for (int i = 0; i < n_images; ++i) images[i].inf_flag = 0;
     HIP_TRY(hipMemcpyAsync(b + o_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
     if (gaussian_f16) HIP_TRY(hipMemcpyAsync(d_g, gaussian_f16, (size_t)ph * pw * 2, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)n_images * 4, st));
+    HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)F * n_images * 4, st));
     {
         long long io = 0;
         for (int i = 0; i < n_images; ++i) {
@@ -1025,14 +1040,23 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, const ts
             io += (long long)align_up(nf, 64);
         }
     }
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-        const Chunk& c = chunks[ci];
-        hipLaunchKernelGGL(sw_gather, dim3(c.gblocks), dim3(256), 0, st, d_imgs, d_segs + c.seg0, c.n_segs, C, ph, pw, V, vflips, d_ty, d_tx, d_batch);
-        HIP_TRY(hipGetLastError());
-        TRY(run_forward(e, d_batch, c.rows, ph, pw, d_log + (size_t)c.log_row * K * ph * pw, nullptr, st, ci == 0, full));
-        if (!c.aggregate) continue;
-        hipLaunchKernelGGL(sw_aggregate, dim3(c.ablocks), dim3(256), 0, st, d_log, d_segs + c.seg0, c.n_segs, K, ph, pw, V, vflips, d_ty, d_tx,
-                           gaussian_f16 ? d_g : nullptr, d_o16, d_seg, kSigmoidHalfThreshold, d_flag, e->tile_half);
+    for (int f = 0; f < F; ++f)
+        for (size_t ci = 0; ci < chunks.size(); ++ci) {
+            const Chunk& c = chunks[ci];
+            hipLaunchKernelGGL(sw_gather, dim3(c.gblocks), dim3(256), 0, st, d_imgs, d_segs + c.seg0, c.n_segs, C, ph, pw, V, vflips, d_ty, d_tx, d_batch);
+            HIP_TRY(hipGetLastError());
+            TRY(run_forward(engines[f], d_batch, c.rows, ph, pw, d_log + (size_t)c.log_row * K * ph * pw, nullptr, st, ci == 0, full));
+            if (!c.aggregate) continue;
+            // (an ensemble's uint8 output is the predicate on the MEAN: sw_fold_mean writes it)
+            hipLaunchKernelGGL(sw_aggregate, dim3(c.ablocks), dim3(256), 0, st, d_log, d_segs + c.seg0, c.n_segs, K, ph, pw, V, vflips, d_ty, d_tx,
+                               gaussian_f16 ? d_g : nullptr, d_o16 ? d_o16 + (size_t)f * out_elems : nullptr, F > 1 ? nullptr : d_seg,
+                               kSigmoidHalfThreshold, d_flag + (size_t)f * n_images, e->tile_half);
+            HIP_TRY(hipGetLastError());
+        }
+    if (F > 1) {          // every slot up to the end of the last image (the alignment gaps between the images ride along unread)
+        const long long n_mean = segs.back().out_off + (long long)K * segs.back().Hp * segs.back().Wp;
+        hipLaunchKernelGGL(sw_fold_mean, dim3((unsigned)blocks_of((n_mean >> 3) + (n_mean & 7))), dim3(256), 0, st, d_o16, out_elems, F, n_mean,
+                           d_seg, kSigmoidHalfThreshold);
         HIP_TRY(hipGetLastError());
     }
     uint8_t* d_rs8 = any_rs8 ? reinterpret_cast<uint8_t*>(b + o_rs8) : nullptr; float* d_rs32 = any_rs32 ? reinterpret_cast<float*>(b + o_rs32) : nullptr;
@@ -1046,8 +1070,8 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, const ts
             if (exports[i].logits_f32) HIP_TRY(hipMemcpyAsync(exports[i].logits_f32, d_rs32 + rsegs[i].dst_off, ne * 4, hipMemcpyDeviceToHost, st));
         }
     }
-    std::vector<int> flags(n_images, 0);
-    HIP_TRY(hipMemcpyAsync(flags.data(), d_flag, (size_t)n_images * 4, hipMemcpyDeviceToHost, st));
+    std::vector<int> flags((size_t)F * n_images, 0);
+    HIP_TRY(hipMemcpyAsync(flags.data(), d_flag, (size_t)F * n_images * 4, hipMemcpyDeviceToHost, st));
     {
         long long oo = 0;
         for (int i = 0; i < n_images; ++i) {
@@ -1058,9 +1082,16 @@ static int predict_tiled_impl(ts2d_engine* e, ts2d_tiled_image* images, const ts
         }
     }
     HIP_TRY(hipStreamSynchronize(st));
-    e->tiled_inf = 0;
-    for (int i = 0; i < n_images; ++i) { images[i].inf_flag = flags[i] != 0; e->tiled_inf |= flags[i] != 0; }
-    return ts2d_engine_check(e);
+    for (int f = 0; f < F; ++f) {         // upstream looks for inf in every fold's aggregated array, not in the mean
+        engines[f]->tiled_inf = 0;
+        for (int i = 0; i < n_images; ++i) {
+            const int inf = flags[(size_t)f * n_images + i] != 0;
+            images[i].inf_flag = f ? (images[i].inf_flag | inf) : inf;
+            engines[f]->tiled_inf |= inf;
+        }
+    }
+    for (int f = 0; f < F; ++f) TRY(name_fold(ts2d_engine_check(engines[f]), name_folds, f));
+    return TS2D_OK;
 }
 
 int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp, int ph, int pw, int n_tiles,
@@ -1070,7 +1101,7 @@ int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
     if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
     ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
-    return predict_tiled_impl(e, &one, nullptr, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, "ts2d_engine_predict_tiled");
+    return predict_tiled_impl(&e, 1, &one, nullptr, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
 }
 
 int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
@@ -1079,7 +1110,7 @@ int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, in
     if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
     if (n_images == 0) return TS2D_OK;
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
-    return predict_tiled_impl(e, images, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, "ts2d_engine_predict_tiled_batch");
+    return predict_tiled_impl(&e, 1, images, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
 }
 
 int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
@@ -1089,8 +1120,35 @@ int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, c
         return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: %d images at a null pointer", n_images);
     if (n_images == 0) return TS2D_OK;
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_export: weights not loaded");
-    return predict_tiled_impl(e, images, exports, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true,
+    return predict_tiled_impl(&e, 1, images, exports, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
                               "ts2d_engine_predict_tiled_export");
+}
+
+int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_export* exports,
+                                       int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
+    static const char* entry = "ts2d_ensemble_predict_tiled_export";
+    if (!engines) return fail(TS2D_ERR_INVALID, "%s: %d engines at a null pointer", entry, n_engines);
+    if (n_engines < 1 || n_engines > kMaxFolds) return fail(TS2D_ERR_INVALID, "%s: n_engines = %d is outside 1..%d", entry, n_engines, kMaxFolds);
+    for (int f = 0; f < n_engines; ++f)
+        if (!engines[f]) return fail(TS2D_ERR_INVALID, "%s: engine %d is null", entry, f);
+    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
+    if (n_images == 0) return TS2D_OK;
+    const ts2d_engine* e0 = engines[0];
+    for (int f = 0; f < n_engines; ++f) {
+        const ts2d_engine* e = engines[f];
+        if (!e->weights_ready) return fail(TS2D_ERR_STATE, "%s: fold %d: weights not loaded", entry, f);
+        if (e->device != e0->device) return fail(TS2D_ERR_INVALID, "%s: fold %d is on device %d, fold 0 on device %d", entry, f, e->device, e0->device);
+        if (e->arch.input_channels != e0->arch.input_channels)
+            return fail(TS2D_ERR_INVALID, "%s: fold %d has %d input channels, fold 0 has %d", entry, f, e->arch.input_channels, e0->arch.input_channels);
+        if (e->arch.num_classes != e0->arch.num_classes)
+            return fail(TS2D_ERR_INVALID, "%s: fold %d has num_classes %d, fold 0 has %d", entry, f, e->arch.num_classes, e0->arch.num_classes);
+        if (e->precision != e0->precision)
+            return fail(TS2D_ERR_INVALID, "%s: fold %d runs precision mode %d, fold 0 mode %d", entry, f, e->precision, e0->precision);
+        if (e->tile_half != e0->tile_half)
+            return fail(TS2D_ERR_INVALID, "%s: fold %d blends with tile dtype %d, fold 0 with %d", entry, f, e->tile_half, e0->tile_half);
+    }
+    return predict_tiled_impl(engines, n_engines, images, exports, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
+                              true, true, entry);
 }
 
 int ts2d_engine_check(ts2d_engine* e) {

@@ -293,36 +293,58 @@ class Engine:
         ``full_batch``: the full-batch dispatch of :meth:`predict_tiled_batch` (an image's bytes do not depend on its batch-mates);
         False: the size-dependent dispatch of :meth:`predict_tiled`.  The resampled values equal
         ``preprocess.resize_linear_f64`` of the float16 logits bit for bit.  Sets ``last_tiled_inf`` / ``last_tiled_inf_per_image``."""
-        if not (len(images) == len(tiles) == len(exports)):
-            raise RuntimeError(f"{len(images)} images but {len(tiles)} tile lists and {len(exports)} exports")
-        if not (want_seg or want_f32):
-            raise RuntimeError("predict_tiled_export: neither the resampled segmentation nor the resampled logits requested")
+        desc, exd, mask, g, keep, outs = self._tiled_export_args('predict_tiled_export', images, tiles, exports, mirror_axes, gaussian,
+                                                                 want_seg, want_f32, want_logits, want_padded_seg)
+        _lib.check(self.lib.ts2d_engine_predict_tiled_export(self._h, desc, exd, len(images), int(patch[0]), int(patch[1]), mask,
+                                                             None if g is None else g.ctypes.data, int(bool(full_batch))),
+                   'ts2d_engine_predict_tiled_export')
+        self.last_tiled_inf_per_image = [bool(desc[i].inf_flag) for i in range(len(images))]
+        self.last_tiled_inf = any(self.last_tiled_inf_per_image)
+        del keep
+        return outs
+
+    def _tiled_export_args(self, what, images, tiles, exports, mirror_axes, gaussian, want_seg, want_f32, want_logits, want_padded_seg):
+        """Argument preparation of :meth:`predict_tiled_export` and :func:`predict_tiled_export_ensemble` (`what` names the caller in a
+        message): the descriptor arrays, the mirror mask, the half gaussian, the arrays the descriptors point into, and the output lists
+        ``(seg, f32, logits, padded_seg)`` the call fills.  ``exports`` None (the ensemble only): no resample-back, no export descriptors."""
+        if len(images) != len(tiles) or (exports is not None and len(exports) != len(images)):
+            raise RuntimeError(f"{len(images)} images but {len(tiles)} tile lists" + ("" if exports is None else f" and {len(exports)} exports"))
+        if exports is None:
+            if want_seg or want_f32:
+                raise RuntimeError(f"{what}: the resampled outputs need exports")
+            if not (want_logits or want_padded_seg):
+                raise RuntimeError(f"{what}: neither logits nor segmentation requested")
+        elif not (want_seg or want_f32):
+            raise RuntimeError(f"{what}: neither the resampled segmentation nor the resampled logits requested")
         K = self.arch.num_classes
         keep = []                    # every array the descriptors point into stays alive until the call returns
         n = max(len(images), 1)
-        desc, exd = (_lib.TiledImage * n)(), (_lib.TiledExport * n)()
+        desc, exd = (_lib.TiledImage * n)(), (None if exports is None else (_lib.TiledExport * n)())
         seg, f32, out16, pseg = [], [], [], []
-        for i, (image, tl, ex) in enumerate(zip(images, tiles, exports)):
+        for i, (image, tl) in enumerate(zip(images, tiles)):
             image = np.ascontiguousarray(image, dtype=np.float32)
             if image.ndim != 3:
                 raise RuntimeError(f"image {i}: expected [C,Hp,Wp], found shape {image.shape}")
             C, Hp, Wp = image.shape
             if C != self.arch.input_channels:
                 raise RuntimeError(f"image {i}: input has {C} channels, the model expects {self.arch.input_channels}")
-            sy, sx, sh, sw_, oh, ow = (int(v) for v in ex)
             ty = np.ascontiguousarray([t[0] for t in tl], dtype=np.int32)
             tx = np.ascontiguousarray([t[1] for t in tl], dtype=np.int32)
-            shape = (K, max(oh, 0), max(ow, 0))          # (a bad extent is the library's to reject, by name)
-            seg.append(np.empty(shape, dtype=np.uint8) if want_seg else None)
-            f32.append(np.empty(shape, dtype=np.float32) if want_f32 else None)
             out16.append(np.empty((K, Hp, Wp), dtype=np.float16) if want_logits else None)
             pseg.append(np.empty((K, Hp, Wp), dtype=np.uint8) if want_padded_seg else None)
             keep += [image, ty, tx]
-            d, x = desc[i], exd[i]
+            d = desc[i]
             d.image, d.Hp, d.Wp, d.n_tiles = image.ctypes.data, Hp, Wp, len(tl)
             d.tile_y, d.tile_x = ty.ctypes.data, tx.ctypes.data
             d.logits_f16 = out16[i].ctypes.data if want_logits else None
             d.seg_u8 = pseg[i].ctypes.data if want_padded_seg else None
+            if exports is None:
+                continue
+            sy, sx, sh, sw_, oh, ow = (int(v) for v in exports[i])
+            shape = (K, max(oh, 0), max(ow, 0))          # (a bad extent is the library's to reject, by name)
+            seg.append(np.empty(shape, dtype=np.uint8) if want_seg else None)
+            f32.append(np.empty(shape, dtype=np.float32) if want_f32 else None)
+            x = exd[i]
             x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w = sy, sx, sh, sw_, oh, ow
             x.seg_u8 = seg[i].ctypes.data if want_seg else None
             x.logits_f32 = f32[i].ctypes.data if want_f32 else None
@@ -330,13 +352,8 @@ class Engine:
         for a in (mirror_axes or ()):
             mask |= 1 << int(a)
         g = None if gaussian is None else np.ascontiguousarray(gaussian, dtype=np.float16)
-        _lib.check(self.lib.ts2d_engine_predict_tiled_export(self._h, desc, exd, len(images), int(patch[0]), int(patch[1]), mask,
-                                                             None if g is None else g.ctypes.data, int(bool(full_batch))),
-                   'ts2d_engine_predict_tiled_export')
-        self.last_tiled_inf_per_image = [bool(desc[i].inf_flag) for i in range(len(images))]
-        self.last_tiled_inf = any(self.last_tiled_inf_per_image)
-        del keep
-        return (seg if want_seg else None), (f32 if want_f32 else None), (out16 if want_logits else None), (pseg if want_padded_seg else None)
+        outs = (seg if want_seg else None), (f32 if want_f32 else None), (out16 if want_logits else None), (pseg if want_padded_seg else None)
+        return desc, exd, mask, g, keep, outs
 
     def _check_shape(self, C, W, mask):
         if C != self.arch.input_channels:
@@ -408,6 +425,33 @@ class Engine:
 
     def device_bytes(self) -> int:
         return int(self.lib.ts2d_engine_device_bytes(self._h))
+
+
+def predict_tiled_export_ensemble(engines, images, patch, tiles, exports, mirror_axes=None, gaussian: Optional[np.ndarray] = None,
+                                  want_seg: bool = True, want_f32: bool = False, want_logits: bool = False, want_padded_seg: bool = False,
+                                  full_batch: bool = True):
+    """:meth:`Engine.predict_tiled_export` for a fold ensemble (C-ABI ts2d_ensemble_predict_tiled_export): ``engines`` are the folds, in
+    fold order; each runs the sliding window that method runs, the device takes the mean of their float16 logits (upstream's
+    ``prediction += fold; prediction /= n`` bit for bit - :func:`predictor.fold_mean_f16` is the statement in numpy) and every output is
+    that of the mean.  Same arguments and the same ``(seg, f32, logits, padded_seg)`` as there; ``exports`` may be None (no
+    resample-back: ``want_seg`` / ``want_f32`` must be off and ``want_logits`` or ``want_padded_seg`` on).  One engine: that method's
+    bytes.  Sets ``last_tiled_inf_per_image`` on the first engine (per image the OR over the folds: upstream checks every fold's
+    array) and ``last_tiled_inf`` on every engine (that fold's own)."""
+    engines = list(engines)
+    if not engines:
+        raise RuntimeError("predict_tiled_export_ensemble: no engines")
+    e0 = engines[0]
+    desc, exd, mask, g, keep, outs = e0._tiled_export_args('predict_tiled_export_ensemble', images, tiles, exports, mirror_axes, gaussian,
+                                                           want_seg, want_f32, want_logits, want_padded_seg)
+    handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
+    _lib.check(e0.lib.ts2d_ensemble_predict_tiled_export(handles, len(engines), desc, exd, len(images), int(patch[0]), int(patch[1]), mask,
+                                                         None if g is None else g.ctypes.data, int(bool(full_batch))),
+               'ts2d_ensemble_predict_tiled_export')
+    e0.last_tiled_inf_per_image = [bool(desc[i].inf_flag) for i in range(len(images))]
+    for e in engines:
+        e.last_tiled_inf = bool(e.lib.ts2d_engine_tiled_inf_flag(e._h))
+    del keep
+    return outs
 
 
 def unpack_mask(packed: np.ndarray, W: int) -> np.ndarray:

@@ -29,6 +29,19 @@ from . import sliding_window as sw
 from .arch import UNetArch
 
 
+def fold_mean_f16(folds) -> np.ndarray:
+    """The fold ensemble's mean as upstream's ``predict_logits_from_preprocessed_data`` takes it (``prediction += fold`` per fold, then
+    ``prediction /= n`` when n > 1), in the float16 of the aggregated logits: numpy's half ``+`` and ``/`` are the fp32 operation
+    rounded to nearest even - what the device kernel sw_fold_mean computes, bit for bit (csrc/kernels_fold.h)."""
+    folds = [np.asarray(f, dtype=np.float16) for f in folds]
+    pred = folds[0]
+    for p in folds[1:]:
+        pred = pred + p
+    if len(folds) > 1:
+        pred = pred / np.float16(len(folds))
+    return pred
+
+
 class _Device:
     """``torch.device``-like (``.type``) without importing torch."""
     def __init__(self, index: int):
@@ -223,6 +236,46 @@ class HIPnnUNetPredictor:
             results.append(full[(slice(None),) + revert[1:]])
         return results
 
+    def _sliding_window_ensemble(self, list_of_data, want_seg: bool = True, one_call: bool = True, out_shapes=None):
+        """Every fold, N single-slice inputs [C,1,H,W], ONE engine call (C-ABI ts2d_ensemble_predict_tiled_export): per fold the sliding
+        window of :meth:`_sliding_window_batch`, the mean of the folds' float16 logits on the device (:func:`fold_mean_f16`, bit for
+        bit), then that method's export: the order-1 resample to ``out_shapes[i]`` (None: the input's own extent, where the taps are
+        1 / 0) and the threshold.  Returns uint8 [K,1,h,w] per input, or the float16 [K,1,H,W] mean logits without ``want_seg``.
+        ``one_call`` False (the single-case methods): the size-dependent dispatch, so the bytes are those of
+        :meth:`predict_logits_from_preprocessed_data`; True: the full-batch dispatch of the ``_batch`` methods."""
+        from .engine import predict_tiled_export_ensemble
+        patch = tuple(self.configuration_manager.patch_size)
+        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
+            raise AssertionError('mirror_axes does not match the dimension of the input!')
+        out_shapes = [None] * len(list_of_data) if out_shapes is None else out_shapes
+        if len(out_shapes) != len(list_of_data):
+            raise AssertionError('out_shapes needs one extent (or None) per input')
+        images, tiles, exports = [], [], []
+        for data, hw in zip(list_of_data, out_shapes):
+            data = np.asarray(data, dtype=np.float32)
+            if data.ndim != 4 or data.shape[1] != 1:
+                raise AssertionError('the fold ensemble on the device takes single-slice inputs (c, 1, y, z)')
+            padded, revert = sw.pad_nd_image(data, patch)
+            H, W = data.shape[2:]
+            images.append(padded[:, 0])
+            tiles.append([(sx, sy) for (_, sx, sy) in sw.tile_slicers(padded.shape[2:], patch, self.tile_step_size, 1)])
+            exports.append((revert[2].start, revert[3].start, H, W) + (tuple(int(v) for v in hw) if hw is not None else (H, W)))
+        g = sw.compute_gaussian(patch) if self.use_gaussian else None
+        axes = self.allowed_mirroring_axes if self.use_mirroring else None
+        seg, _, out16, _ = predict_tiled_export_ensemble(self.engines, images, patch, tiles, exports if want_seg else None, axes, g,
+                                                         want_seg=want_seg, want_logits=not want_seg, full_batch=one_call)
+        bad = sorted(j for j, f in enumerate(self.engines[0].last_tiled_inf_per_image) if f)
+        if bad:
+            raise RuntimeError((f'input {bad[0]}: ' if one_call else '') + self._INF_MESSAGE)
+        if want_seg:
+            return [p[:, None] for p in seg]
+        return [p[:, ex[0]:ex[0] + ex[2], ex[1]:ex[1] + ex[3]][:, None] for p, ex in zip(out16, exports)]
+
+    def _device_ensemble(self) -> bool:
+        """Is this a fold ensemble whose folds are all real engines?  (The host doubles of the tests have none: they keep the logits route.)"""
+        from .engine import Engine
+        return len(self.engines) == len(self.list_of_parameters) > 1 and all(isinstance(e, Engine) for e in self.engines)
+
     def predict_sliding_window_return_logits(self, data: np.ndarray, fold: int = 0) -> np.ndarray:
         """One fold: tiles x mirror variants -> one engine batch per z slice -> upstream's fp16 Gaussian aggregation.
         data [C,Z,H,W] float32 -> float16 [K,Z,H,W]."""
@@ -245,19 +298,24 @@ class HIPnnUNetPredictor:
         """Fast path of the product surface (not part of the reference's duck-typed seam): the multilabel segmentation
         ``sigmoid(float(half logits)) > 0.5`` thresholded ON THE DEVICE by the aggregation kernel (kernels_sw.h: the same predicate as
         export.py's bit-pattern test, verified on all 65 536 half values), so that K uint8 planes travel to the host instead of K float16
-        ones and the host never thresholds.  One fold, one z-slice (the 2-D models of ts2d); returns uint8 [K, 1, H, W] in the
-        preprocessed geometry, or None when the case needs the logits (fold ensembles average logits first; 3-D stacks).
+        ones and the host never thresholds.  One z-slice (the 2-D models of ts2d); returns uint8 [K, 1, H, W] in the
+        preprocessed geometry, or None when the case needs the logits (3-D stacks; a predictor without engines).  A fold ensemble runs
+        every fold in one engine call and the device takes the mean of the folds' logits in front of the threshold
+        (:meth:`_sliding_window_ensemble`): the bytes are those of :meth:`predict_logits_from_preprocessed_data` + the host export.
         ``out_shape`` (the case's ``shape_after_cropping_and_before_resampling``, (h, w) or (1, h, w)): the export's order-1
         resample-back runs on the device in front of the threshold (kernels_resample.h; bit for bit the host route's
         ``resample_data_to_shape(order=1)`` + threshold) and the result is uint8 [K, 1, h, w] in THAT extent."""
         if hasattr(data, 'detach'):
             data = data.detach().cpu().numpy()
         data = np.asarray(data, dtype=np.float32)
-        if len(self.list_of_parameters) != 1 or len(self.engines) != 1 or data.ndim != 4 or data.shape[1] != 1:
+        ensemble = self._device_ensemble()
+        if not (ensemble or len(self.list_of_parameters) == len(self.engines) == 1) or data.ndim != 4 or data.shape[1] != 1:
             return None
         hw = self._in_plane(out_shape, data)
         if hw is False:
             return None
+        if ensemble:
+            return self._sliding_window_ensemble([data], want_seg=True, one_call=False, out_shapes=[hw])[0]
         kw = {} if hw is None else {'out_shapes': [hw]}
         return self._sliding_window_batch([data], 0, want_seg=True, one_call=False, **kw)[0]
 
@@ -302,15 +360,19 @@ class HIPnnUNetPredictor:
 
     def predict_segmentation_from_preprocessed_data_batch(self, list_of_data, out_shapes=None):
         """:meth:`predict_segmentation_from_preprocessed_data` for a list of inputs: uint8 [K,1,H,W] per input from ONE engine call,
-        or None when the predictor needs the logits (a fold ensemble) or an input is no single z slice.  ``out_shapes``: one
-        ``out_shape`` (or None) per input; inputs that resample and inputs that do not travel in the same call."""
+        or None when the predictor needs the logits (a fold ensemble without engines) or an input is no single z slice.  ``out_shapes``:
+        one ``out_shape`` (or None) per input; inputs that resample and inputs that do not travel in the same call.  A fold ensemble:
+        every fold and every input in ONE engine call, the mean of the folds on the device (:meth:`_sliding_window_ensemble`)."""
         datas = [np.asarray(d.detach().cpu().numpy() if hasattr(d, 'detach') else d, dtype=np.float32) for d in list_of_data]
-        if len(self.list_of_parameters) != 1 or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
+        ensemble = self._device_ensemble()
+        if not (ensemble or len(self.list_of_parameters) == 1) or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
             return None
         if not datas:
             return []
         hws = [self._in_plane(s, d) for s, d in zip(out_shapes, datas)] if out_shapes is not None else [None] * len(datas)
         if (out_shapes is not None and len(out_shapes) != len(datas)) or any(hw is False for hw in hws):
             return None
+        if ensemble:
+            return self._sliding_window_ensemble(datas, want_seg=True, one_call=True, out_shapes=hws)
         kw = {} if all(hw is None for hw in hws) else {'out_shapes': hws}
         return self._sliding_window_batch(datas, 0, want_seg=True, **kw)
