@@ -330,6 +330,47 @@ int ts2d_project_coronal_zscore(int device, const void* volume, size_t n_elems, 
 int ts2d_resample_cubic(int device, const float* src, int n_planes, int in_h, int in_w, int out_h, int out_w, const float* lo_hi,
                         float* dst);
 
+/* nnU-Net's preprocessing of an input that is 2-D when it arrives - an X-ray image, a pre-projected multi-channel image - on planes that
+ * stay on the device: crop_to_nonzero, ZScoreNormalization without mask per channel, the resample to the plan spacing (reference flow
+ * DefaultPreprocessor.run_case, ts2d/core/inference/prediction_worker.py:194-199).  The planes are uploaded once and downloaded once.
+ * Every entry validates its arguments before any device work and names itself in ts2d_last_error, frees its scratch on every path and
+ * is synchronous.  (New symbols of ABI 9: nothing that existed changed.) */
+typedef struct ts2d_planes ts2d_planes;
+
+/* Upload src [n_planes][h][w] float32 (the channels of one case, prediction_worker.py:194-199: the array run_case reads) to HIP device
+ * `device`.  TS2D_ERR_INVALID: null pointers, n_planes outside 1 ... 65535, an extent outside 1 ... 8192, more than 2^28 samples. */
+int ts2d_planes_create(int device, const float* src, int n_planes, int h, int w, ts2d_planes** out);
+
+/* crop_to_nonzero and the per-plane z-score of run_case (prediction_worker.py:194-199), in place on the handle:
+ *   box    {first row, one past the last row, first column, one past the last column} of the pixels that are non-zero in ANY plane
+ *          (`!= 0` as numpy has it: a NaN is not zero; planes of zeros keep their whole extent); the planes are compacted to it, so the
+ *          handle's extent becomes (box[1] - box[0]) x (box[3] - box[2]).
+ *   stats  [n_planes][2]: float32 mean and standard deviation of each cropped plane.
+ * Arithmetic contract = preprocess.zscore_f32_statement, bit for bit, which is bit for bit numpy's img.mean(), img.std(), img -= mean,
+ * img /= max(std, 1e-8) on the C-contiguous float32 plane: the float32 sum in chunks of 8192 elements added in index order from +0, each
+ * chunk summed pairwise (runs of at most 128 elements in eight strided accumulators combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then
+ * the last len % 8 elements; a longer run split at n/2 - (n/2) % 8), sum / n in float64 rounded once to float32, the second sum over
+ * fl32(fl32(x - mean)^2), the float32 square root, and per element fl32(fl32(x - mean) / max(std, 1e-8)) with a correctly rounded
+ * division.  No fused multiply-add, no atomics on floats: two calls give the same bits.  The float32 minimum and maximum of each
+ * normalised plane stay on the handle: they are the clip bounds of ts2d_planes_resample_cubic.
+ *   nonfinite  set to 1 when a mean, a variance or a normalised sample is not finite (a non-finite sample, or float32 sums that
+ *          overflow): the planes are then cropped but NOT a normalisation the caller may use; it drops the handle and runs numpy. */
+int ts2d_planes_crop_zscore(ts2d_planes* p, int32_t box[4], float* stats, int* nonfinite);
+
+/* The order-3 resample of run_case (prediction_worker.py:194-199, a case whose spacing is not the plan's) of every plane of the handle to
+ * out_h x out_w, clipped to the bounds ts2d_planes_crop_zscore left: the arithmetic, the limits and the messages of ts2d_resample_cubic.
+ * The handle's extent becomes out_h x out_w and its clip bounds are used up (TS2D_ERR_STATE without them). */
+int ts2d_planes_resample_cubic(ts2d_planes* p, int out_h, int out_w);
+
+/* The current extent of the planes (prediction_worker.py:194-199: the shape of the array run_case returns). */
+int ts2d_planes_extent(const ts2d_planes* p, int* h, int* w);
+
+/* Copy the planes [n_planes][h][w] (current extent) back to the host (prediction_worker.py:194-199: the array run_case returns). */
+int ts2d_planes_download(const ts2d_planes* p, float* dst);
+
+/* Free the handle and its device memory (NULL is fine).  Reference: the preprocessed array going out of scope (prediction_worker.py:194-199). */
+int ts2d_planes_destroy(ts2d_planes* p);
+
 /* Synthetic slice stream on the device (BASELINE config 4: "synthetic 10k-slice stream", generated per rank from (seed, slice
  * index) so that no host transfer skews the timing).  Writes n_elements fp32 values, approximately N(0,1), to device memory:
  * element i of the call = element (first_element + i) of the stream identified by `key`; a value depends on (key, element index)

@@ -20,7 +20,7 @@ PRECISION_F16 = 2
 
 # every symbol include/ts2d_engine.h declares
 SYMBOLS = ('ts2d_engine_create', 'ts2d_engine_load_weights', 'ts2d_engine_weight_buffer', 'ts2d_engine_weights_ready',
-           'ts2d_engine_forward', 'ts2d_engine_check', 'ts2d_engine_predict_tiled', 'ts2d_engine_predict_tiled_batch', 'ts2d_engine_predict_tiled_export', 'ts2d_ensemble_predict_tiled_export', 'ts2d_engine_tiled_inf_flag', 'ts2d_engine_set_tile_dtype', 'ts2d_engine_set_keep_activations', 'ts2d_project_coronal', 'ts2d_project_coronal_zscore', 'ts2d_resample_cubic', 'ts2d_synth_slices', 'ts2d_engine_reserve', 'ts2d_engine_workspace_bytes', 'ts2d_engine_set_workspace', 'ts2d_engine_set_precision', 'ts2d_engine_set_option', 'ts2d_engine_set_profiling', 'ts2d_engine_num_ops',
+           'ts2d_engine_forward', 'ts2d_engine_check', 'ts2d_engine_predict_tiled', 'ts2d_engine_predict_tiled_batch', 'ts2d_engine_predict_tiled_export', 'ts2d_ensemble_predict_tiled_export', 'ts2d_engine_tiled_inf_flag', 'ts2d_engine_set_tile_dtype', 'ts2d_engine_set_keep_activations', 'ts2d_project_coronal', 'ts2d_project_coronal_zscore', 'ts2d_resample_cubic', 'ts2d_planes_create', 'ts2d_planes_crop_zscore', 'ts2d_planes_resample_cubic', 'ts2d_planes_extent', 'ts2d_planes_download', 'ts2d_planes_destroy', 'ts2d_synth_slices', 'ts2d_engine_reserve', 'ts2d_engine_workspace_bytes', 'ts2d_engine_set_workspace', 'ts2d_engine_set_precision', 'ts2d_engine_set_option', 'ts2d_engine_set_profiling', 'ts2d_engine_num_ops',
            'ts2d_engine_op_name', 'ts2d_engine_op_kernel', 'ts2d_engine_op_ksplit', 'ts2d_engine_op_times', 'ts2d_engine_debug_tensor', 'ts2d_engine_device_bytes', 'ts2d_engine_destroy',
            'ts2d_last_error', 'ts2d_abi_version')
 
@@ -113,6 +113,19 @@ def load():
     if hasattr(lib, 'ts2d_resample_cubic'):        # added under ABI 9: a library built before it lacks the symbol and the callers keep the host route
         lib.ts2d_resample_cubic.restype = c.c_int
         lib.ts2d_resample_cubic.argtypes = [c.c_int, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p]
+    if hasattr(lib, 'ts2d_planes_create'):         # the device-resident planes of preprocess.DevicePlanes, added under ABI 9 like the entry above
+        lib.ts2d_planes_create.restype = c.c_int
+        lib.ts2d_planes_create.argtypes = [c.c_int, c.c_void_p, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
+        lib.ts2d_planes_crop_zscore.restype = c.c_int
+        lib.ts2d_planes_crop_zscore.argtypes = [c.c_void_p, c.POINTER(c.c_int32 * 4), c.c_void_p, c.POINTER(c.c_int)]
+        lib.ts2d_planes_resample_cubic.restype = c.c_int
+        lib.ts2d_planes_resample_cubic.argtypes = [c.c_void_p, c.c_int, c.c_int]
+        lib.ts2d_planes_extent.restype = c.c_int
+        lib.ts2d_planes_extent.argtypes = [c.c_void_p, c.POINTER(c.c_int), c.POINTER(c.c_int)]
+        lib.ts2d_planes_download.restype = c.c_int
+        lib.ts2d_planes_download.argtypes = [c.c_void_p, c.c_void_p]
+        lib.ts2d_planes_destroy.restype = c.c_int
+        lib.ts2d_planes_destroy.argtypes = [c.c_void_p]
     lib.ts2d_synth_slices.restype = c.c_int
     lib.ts2d_synth_slices.argtypes = [c.c_int, c.c_ulonglong, c.c_ulonglong, c.c_ulonglong, c.c_void_p, c.c_void_p]
     lib.ts2d_engine_reserve.restype = c.c_int

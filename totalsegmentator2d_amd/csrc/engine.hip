@@ -22,6 +22,7 @@
 #include "kernels_resample.h"
 #include "kernels_resample_in.h"
 #include "kernels_project.h"
+#include "kernels_prep.h"
 
 #include <atomic>
 #include <cstdio>
@@ -1354,6 +1355,54 @@ static RsInAxis rsin_axis_constants(int n_pad) {
     return a;
 }
 
+// The device part of the order-3 resample, shared by ts2d_resample_cubic (host planes in and out) and ts2d_planes_resample_cubic (planes that
+// live on the device): the host tables of one (in_h, in_w) -> (out_h, out_w) zoom and the layout of the scratch they go to,
+// [coefficients | powers | taps], then the three rsin_* launches over device pointers.
+struct RsInPlan {
+    int Hp = 0, Wp = 0;
+    std::vector<RsInTap> taps;          // rows at [0, out_h), columns at [out_h, out_h + out_w)
+    std::vector<double> zpow;           // running products of the pole, as scipy forms them (z_i *= z)
+    RsInAxis ax_h, ax_w;
+    size_t o_pow = 0, o_taps = 0, bytes = 0;
+};
+
+// false: a tap would leave the padded plane
+static bool rsin_plan(int n_planes, int in_h, int in_w, int out_h, int out_w, RsInPlan* pl) {
+    pl->Hp = in_h + 2 * kRsInPad; pl->Wp = in_w + 2 * kRsInPad;
+    pl->taps.resize((size_t)out_h + out_w);
+    if (!rsin_axis_taps(in_h, out_h, pl->taps.data()) || !rsin_axis_taps(in_w, out_w, pl->taps.data() + out_h)) return false;
+    pl->zpow.resize((size_t)std::max(pl->Hp, pl->Wp));
+    {
+#pragma clang fp contract(off)
+        pl->zpow[0] = 1.0; pl->zpow[1] = kRsInPole;
+        for (size_t i = 2; i < pl->zpow.size(); ++i) pl->zpow[i] = pl->zpow[i - 1] * kRsInPole;
+    }
+    pl->ax_h = rsin_axis_constants(pl->Hp); pl->ax_w = rsin_axis_constants(pl->Wp);
+    pl->o_pow = align_up((size_t)n_planes * pl->Hp * pl->Wp * sizeof(double), 256);
+    pl->o_taps = align_up(pl->o_pow + pl->zpow.size() * sizeof(double), 256);
+    pl->bytes = align_up(pl->o_taps + pl->taps.size() * sizeof(RsInTap), 256);
+    return true;
+}
+
+// d_scratch: pl.bytes; d_src [n_planes][in_h][in_w], d_lh [n_planes][2], d_dst [n_planes][out_h][out_w], all on the device
+static hipError_t rsin_run(const RsInPlan& pl, char* d_scratch, const float* d_src, const float* d_lh, float* d_dst, int n_planes, int in_h,
+                           int in_w, int out_h, int out_w) {
+    double* d_coef = reinterpret_cast<double*>(d_scratch);
+    const double* d_pow = reinterpret_cast<const double*>(d_scratch + pl.o_pow);
+    const RsInTap* d_taps = reinterpret_cast<const RsInTap*>(d_scratch + pl.o_taps);
+    hipError_t he = hipMemcpy(d_scratch + pl.o_pow, pl.zpow.data(), pl.zpow.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d_scratch + pl.o_taps, pl.taps.data(), pl.taps.size() * sizeof(RsInTap), hipMemcpyHostToDevice);
+    if (he != hipSuccess) return he;
+    hipLaunchKernelGGL(rsin_prefilter_cols, dim3((unsigned)(((long long)n_planes * pl.Wp + 63) / 64)), dim3(64), 0, 0,
+                       d_src, n_planes, in_h, in_w, pl.ax_h, d_pow, d_coef);
+    hipLaunchKernelGGL(rsin_prefilter_rows, dim3((unsigned)(((long long)n_planes * pl.Hp + 63) / 64)), dim3(64), 0, 0,
+                       d_coef, n_planes, pl.Hp, pl.Wp, pl.ax_w, d_pow);
+    const long long quads = (long long)n_planes * out_h * ((out_w + 3) / 4);
+    hipLaunchKernelGGL(rsin_interp_clip, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, 0,
+                       d_coef, n_planes, pl.Hp, pl.Wp, out_h, out_w, d_taps, d_lh, d_dst);
+    return hipGetLastError();
+}
+
 int ts2d_resample_cubic(int device, const float* src, int n_planes, int in_h, int in_w, int out_h, int out_w, const float* lo_hi, float* dst) {
     if (!src || !lo_hi || !dst) return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: null argument");
     if (n_planes < 1) return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: %d planes", n_planes);
@@ -1366,50 +1415,237 @@ int ts2d_resample_cubic(int device, const float* src, int n_planes, int in_h, in
         if (!std::isfinite(lo_hi[2 * p]) || !std::isfinite(lo_hi[2 * p + 1]) || lo_hi[2 * p] > lo_hi[2 * p + 1])
             return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: plane %d has non-finite or inverted clip bounds [%g, %g] (a plane with a non-finite sample is not computed here)",
                         p, (double)lo_hi[2 * p], (double)lo_hi[2 * p + 1]);
-    std::vector<RsInTap> taps((size_t)out_h + out_w);
-    if (!rsin_axis_taps(in_h, out_h, taps.data()) || !rsin_axis_taps(in_w, out_w, taps.data() + out_h))
+    RsInPlan pl;
+    if (!rsin_plan(n_planes, in_h, in_w, out_h, out_w, &pl))
         return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: zoom %d x %d -> %d x %d puts a tap outside the padded plane", in_h, in_w, out_h, out_w);
-    std::vector<double> zpow((size_t)std::max(Hp, Wp));
-    {
-#pragma clang fp contract(off)
-        zpow[0] = 1.0; zpow[1] = kRsInPole;                                    // running products, as scipy forms them (z_i *= z)
-        for (size_t i = 2; i < zpow.size(); ++i) zpow[i] = zpow[i - 1] * kRsInPole;
-    }
-    const RsInAxis ax_h = rsin_axis_constants(Hp), ax_w = rsin_axis_constants(Wp);
     HIP_TRY(hipSetDevice(device));
-    const size_t n_src = (size_t)n_planes * in_h * in_w, n_coef = (size_t)n_planes * Hp * Wp, n_dst = (size_t)n_planes * out_h * out_w;
-    // [coefficients | powers | taps | source | clip bounds | result]
-    const size_t o_pow = align_up(n_coef * sizeof(double), 256), o_taps = align_up(o_pow + zpow.size() * sizeof(double), 256);
-    const size_t o_src = align_up(o_taps + taps.size() * sizeof(RsInTap), 256), o_lh = align_up(o_src + n_src * sizeof(float), 256);
+    const size_t n_src = (size_t)n_planes * in_h * in_w, n_dst = (size_t)n_planes * out_h * out_w;
+    // [scratch of the plan | source | clip bounds | result]
+    const size_t o_src = pl.bytes, o_lh = align_up(o_src + n_src * sizeof(float), 256);
     const size_t o_dst = align_up(o_lh + (size_t)n_planes * 2 * sizeof(float), 256);
     char* d = nullptr;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), o_dst + n_dst * sizeof(float)));
-    double* d_coef = reinterpret_cast<double*>(d);
-    const double* d_pow = reinterpret_cast<const double*>(d + o_pow);
-    const RsInTap* d_taps = reinterpret_cast<const RsInTap*>(d + o_taps);
-    const float* d_src = reinterpret_cast<const float*>(d + o_src);
-    const float* d_lh = reinterpret_cast<const float*>(d + o_lh);
     float* d_dst = reinterpret_cast<float*>(d + o_dst);
-    hipError_t he = hipMemcpy(d + o_pow, zpow.data(), zpow.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d + o_taps, taps.data(), taps.size() * sizeof(RsInTap), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d + o_src, src, n_src * sizeof(float), hipMemcpyHostToDevice);
+    hipError_t he = hipMemcpy(d + o_src, src, n_src * sizeof(float), hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(d + o_lh, lo_hi, (size_t)n_planes * 2 * sizeof(float), hipMemcpyHostToDevice);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(rsin_prefilter_cols, dim3((unsigned)(((long long)n_planes * Wp + 63) / 64)), dim3(64), 0, 0,
-                           d_src, n_planes, in_h, in_w, ax_h, d_pow, d_coef);
-        hipLaunchKernelGGL(rsin_prefilter_rows, dim3((unsigned)(((long long)n_planes * Hp + 63) / 64)), dim3(64), 0, 0,
-                           d_coef, n_planes, Hp, Wp, ax_w, d_pow);
-        const long long quads = (long long)n_planes * out_h * ((out_w + 3) / 4);
-        hipLaunchKernelGGL(rsin_interp_clip, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, 0,
-                           d_coef, n_planes, Hp, Wp, out_h, out_w, d_taps, d_lh, d_dst);
-        he = hipGetLastError();
-    }
+    if (he == hipSuccess)
+        he = rsin_run(pl, d, reinterpret_cast<const float*>(d + o_src), reinterpret_cast<const float*>(d + o_lh), d_dst, n_planes, in_h, in_w, out_h, out_w);
     if (he == hipSuccess) he = hipMemcpy(dst, d_dst, n_dst * sizeof(float), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (he != hipSuccess) return fail(TS2D_ERR_HIP, "ts2d_resample_cubic failed: %s", hipGetErrorString(he));
     return TS2D_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- ts2d_planes
+// Planes that stay on the device between the steps of nnU-Net's preprocessing of a native 2-D input (kernels_prep.h): uploaded once,
+// cropped, z-scored and resampled where they lie, downloaded once.
+struct ts2d_planes {
+    int device = 0;
+    int n = 0, h = 0, w = 0;
+    float* d = nullptr;         // [n][h][w]
+    float* d_lh = nullptr;      // [n][2]: float32 minimum and maximum of each plane, valid while has_bounds
+    bool has_bounds = false;
+};
+
+constexpr int kPrepMaxPlanes = 65535;           // (a grid dimension)
+constexpr long long kPrepMaxSamples = 1ll << 28;
+
+// leaves of numpy's pairwise sum over a run of n elements (the partial chunk of a plane), in the order the recursion visits them
+static void prep_leaves(int off, int n, std::vector<PrepLeaf>* out) {
+    if (n <= kPrepLeaf) { out->push_back(PrepLeaf{off, n}); return; }
+    int n2 = n / 2; n2 -= n2 % 8;
+    prep_leaves(off, n2, out);
+    prep_leaves(off + n2, n - n2, out);
+}
+
+// the same recursion over the leaves' sums: every inner node adds its two halves, rounded to float32
+static float prep_fold(const float*& leaf, int n) {
+#pragma clang fp contract(off)
+    if (n <= kPrepLeaf) return *leaf++;
+    int n2 = n / 2; n2 -= n2 % 8;
+    const float a = prep_fold(leaf, n2);
+    const float b = prep_fold(leaf, n - n2);
+    return a + b;
+}
+
+// numpy's add.reduce of one plane from what prep_chunk_sums wrote: +0, plus each chunk's pairwise sum in index order
+static float prep_plane_sum(const float* sums, long long n) {
+#pragma clang fp contract(off)
+    const long long n_full = n / kPrepChunk;
+    float acc = 0.f;
+    for (long long c = 0; c < n_full; ++c) acc = acc + sums[c];
+    if (n % kPrepChunk) { const float* leaf = sums + n_full; const float tail = prep_fold(leaf, (int)(n % kPrepChunk)); acc = acc + tail; }
+    return acc;
+}
+
+static float prep_unkey(int key) { const int b = key < 0 ? key ^ 0x7FFFFFFF : key; float f; std::memcpy(&f, &b, 4); return f; }
+
+int ts2d_planes_create(int device, const float* src, int n_planes, int h, int w, ts2d_planes** out) {
+    if (!src || !out) return fail(TS2D_ERR_INVALID, "ts2d_planes_create: null argument");
+    *out = nullptr;
+    if (n_planes < 1 || n_planes > kPrepMaxPlanes) return fail(TS2D_ERR_INVALID, "ts2d_planes_create: %d planes outside 1 ... %d", n_planes, kPrepMaxPlanes);
+    if (h < 1 || w < 1 || h > kRsInMaxExtent || w > kRsInMaxExtent)
+        return fail(TS2D_ERR_INVALID, "ts2d_planes_create: extents %d x %d outside 1 ... %d", h, w, kRsInMaxExtent);
+    if ((long long)n_planes * h * w > kPrepMaxSamples)
+        return fail(TS2D_ERR_INVALID, "ts2d_planes_create: %d planes of %d x %d are more than one handle takes (2^28 samples)", n_planes, h, w);
+    HIP_TRY(hipSetDevice(device));
+    const size_t bytes = (size_t)n_planes * h * w * sizeof(float);
+    float* d = nullptr; float* d_lh = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), bytes));
+    hipError_t he = hipMalloc(reinterpret_cast<void**>(&d_lh), (size_t)n_planes * 2 * sizeof(float));
+    if (he == hipSuccess) he = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+        (void)hipFree(d); if (d_lh) (void)hipFree(d_lh);
+        return fail(he == hipErrorOutOfMemory ? TS2D_ERR_NOMEM : TS2D_ERR_HIP, "ts2d_planes_create failed: %s", hipGetErrorString(he));
+    }
+    ts2d_planes* p = new ts2d_planes();
+    p->device = device; p->n = n_planes; p->h = h; p->w = w; p->d = d; p->d_lh = d_lh;
+    *out = p;
+    return TS2D_OK;
+}
+
+int ts2d_planes_crop_zscore(ts2d_planes* p, int32_t box[4], float* stats, int* nonfinite) {
+    if (!p || !box || !stats || !nonfinite) return fail(TS2D_ERR_INVALID, "ts2d_planes_crop_zscore: null argument");
+    *nonfinite = 0;
+    HIP_TRY(hipSetDevice(p->device));
+    const int n = p->n;
+    // scratch, sized for the uncropped extent: [box | min / max keys | mean, divisor | leaves of the partial chunk | chunk and leaf sums]
+    const size_t per_plane = (size_t)((long long)p->h * p->w / kPrepChunk) + kPrepMaxTailLeaves;
+    const size_t o_keys = 256, o_norm = align_up(o_keys + (size_t)n * 2 * sizeof(int), 256), o_leaves = align_up(o_norm + (size_t)n * sizeof(PrepNorm), 256);
+    const size_t o_sums = align_up(o_leaves + kPrepMaxTailLeaves * sizeof(PrepLeaf), 256);
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), o_sums + (size_t)n * per_plane * sizeof(float)));
+    int* d_box = reinterpret_cast<int*>(d); int* d_keys = reinterpret_cast<int*>(d + o_keys);
+    PrepNorm* d_norm = reinterpret_cast<PrepNorm*>(d + o_norm); PrepLeaf* d_leaves = reinterpret_cast<PrepLeaf*>(d + o_leaves);
+    float* d_sums = reinterpret_cast<float*>(d + o_sums);
+    float* d_new = nullptr;                                     // the compacted planes, until the handle owns them
+    auto done = [&](hipError_t he) {
+        (void)hipFree(d); if (d_new) (void)hipFree(d_new);
+        if (he != hipSuccess) return fail(he == hipErrorOutOfMemory ? TS2D_ERR_NOMEM : TS2D_ERR_HIP, "ts2d_planes_crop_zscore failed: %s", hipGetErrorString(he));
+        return (int)TS2D_OK;
+    };
+    // 1. crop_to_nonzero's box over all planes
+    int hb[4] = {p->h, -1, p->w, -1};
+    hipError_t he = hipMemcpy(d_box, hb, sizeof(hb), hipMemcpyHostToDevice);
+    if (he != hipSuccess) return done(he);
+    hipLaunchKernelGGL(prep_nonzero_box, dim3((unsigned)(((long long)p->h * p->w + 255) / 256)), dim3(256), 0, 0, p->d, n, p->h, p->w, d_box);
+    he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpy(hb, d_box, sizeof(hb), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return done(he);
+    if (hb[1] < 0) { hb[0] = 0; hb[1] = p->h - 1; hb[2] = 0; hb[3] = p->w - 1; }            // nothing but zeros: the whole extent stays
+    if (hb[0] < 0 || hb[1] >= p->h || hb[0] > hb[1] || hb[2] < 0 || hb[3] >= p->w || hb[2] > hb[3]) {
+        (void)done(hipSuccess);
+        return fail(TS2D_ERR_HIP, "ts2d_planes_crop_zscore: the device returned the box rows %d ... %d, columns %d ... %d of %d x %d", hb[0], hb[1], hb[2], hb[3], p->h, p->w);
+    }
+    const int bh = hb[1] - hb[0] + 1, bw = hb[3] - hb[2] + 1;
+    // 2. compaction: the flattened index of the dense [n][bh][bw] buffer is numpy's
+    if (bh != p->h || bw != p->w) {
+        he = hipMalloc(reinterpret_cast<void**>(&d_new), (size_t)n * bh * bw * sizeof(float));
+        for (int c = 0; c < n && he == hipSuccess; ++c)
+            he = hipMemcpy2D(d_new + (size_t)c * bh * bw, (size_t)bw * sizeof(float), p->d + ((size_t)c * p->h + hb[0]) * p->w + hb[2],
+                             (size_t)p->w * sizeof(float), (size_t)bw * sizeof(float), (size_t)bh, hipMemcpyDeviceToDevice);
+        if (he != hipSuccess) return done(he);
+        (void)hipFree(p->d);
+        p->d = d_new; d_new = nullptr; p->h = bh; p->w = bw;
+    }
+    p->has_bounds = false;
+    box[0] = hb[0]; box[1] = hb[1] + 1; box[2] = hb[2]; box[3] = hb[3] + 1;
+    // 3. the two sums of every plane: chunk and leaf sums on the device, their fold and the float32 statistics here
+    const long long N = (long long)bh * bw, n_full = N / kPrepChunk;
+    std::vector<PrepLeaf> leaves;
+    if (N % kPrepChunk) prep_leaves(0, (int)(N % kPrepChunk), &leaves);
+    if ((int)leaves.size() > kPrepMaxTailLeaves) { (void)done(hipSuccess); return fail(TS2D_ERR_INVALID, "ts2d_planes_crop_zscore: %zu leaves in a partial chunk", leaves.size()); }
+    const size_t n_out = (size_t)n_full + leaves.size();
+    const dim3 grid_sums((unsigned)(n_full + (leaves.empty() ? 0 : 1)), (unsigned)n);
+    std::vector<float> sums((size_t)n * n_out);
+    std::vector<PrepNorm> norm((size_t)n, PrepNorm{0.f, 1.f});
+    if (!leaves.empty()) he = hipMemcpy(d_leaves, leaves.data(), leaves.size() * sizeof(PrepLeaf), hipMemcpyHostToDevice);
+    if (he != hipSuccess) return done(he);
+    bool bad = false;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 0) hipLaunchKernelGGL(prep_chunk_sums<0>, grid_sums, dim3(512), 0, 0, p->d, N, d_norm, d_leaves, (int)leaves.size(), d_sums);
+        else hipLaunchKernelGGL(prep_chunk_sums<1>, grid_sums, dim3(512), 0, 0, p->d, N, d_norm, d_leaves, (int)leaves.size(), d_sums);
+        he = hipGetLastError();
+        if (he == hipSuccess) he = hipMemcpy(sums.data(), d_sums, sums.size() * sizeof(float), hipMemcpyDeviceToHost);
+        if (he != hipSuccess) return done(he);
+        for (int c = 0; c < n; ++c) {
+            // numpy divides the float32 sum by the count in float64 and rounds once to float32 (`ret / rcount` with an intp count)
+            const float q = (float)((double)prep_plane_sum(sums.data() + (size_t)c * n_out, N) / (double)N);
+            if (!std::isfinite(q)) bad = true;
+            if (pass == 0) { norm[c].mean = q; stats[2 * c] = q; }
+            else { const float sd = std::sqrt(q); stats[2 * c + 1] = sd; norm[c].div = 1e-8 > (double)sd ? (float)1e-8 : sd; }   // max(std, 1e-8)
+        }
+        if (bad) { *nonfinite = 1; return done(hipSuccess); }      // a non-finite sample (or an overflowing sum): nothing is normalised
+        he = hipMemcpy(d_norm, norm.data(), norm.size() * sizeof(PrepNorm), hipMemcpyHostToDevice);
+        if (he != hipSuccess) return done(he);
+    }
+    // 4. normalise in place; the minimum and maximum of the result are the clip bounds of the resample
+    std::vector<int> keys((size_t)n * 2);
+    for (int c = 0; c < n; ++c) { keys[2 * c] = 0x7FFFFFFF; keys[2 * c + 1] = (int)0x80000000; }
+    he = hipMemcpy(d_keys, keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (he != hipSuccess) return done(he);
+    hipLaunchKernelGGL(prep_normalise, dim3((unsigned)((N + 256 * kPrepNormPerLane - 1) / (256 * kPrepNormPerLane)), (unsigned)n), dim3(256), 0, 0, p->d, N, d_norm, d_keys);
+    he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpy(keys.data(), d_keys, keys.size() * sizeof(int), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return done(he);
+    std::vector<float> lh((size_t)n * 2);
+    for (size_t i = 0; i < lh.size(); ++i) { lh[i] = prep_unkey(keys[i]); if (!std::isfinite(lh[i])) bad = true; }
+    if (bad) { *nonfinite = 1; return done(hipSuccess); }          // (a quotient overflowed: the planes hold it, the caller drops the handle)
+    he = hipMemcpy(p->d_lh, lh.data(), lh.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (he != hipSuccess) return done(he);
+    p->has_bounds = true;
+    return done(hipSuccess);
+}
+
+int ts2d_planes_resample_cubic(ts2d_planes* p, int out_h, int out_w) {
+    if (!p) return fail(TS2D_ERR_INVALID, "ts2d_planes_resample_cubic: null argument");
+    const int in_h = p->h, in_w = p->w, n = p->n;
+    if (in_h < 2 || in_w < 2 || out_h < 2 || out_w < 2 || in_h > kRsInMaxExtent || in_w > kRsInMaxExtent || out_h > kRsInMaxExtent || out_w > kRsInMaxExtent)
+        return fail(TS2D_ERR_INVALID, "ts2d_planes_resample_cubic: extents %d x %d -> %d x %d outside 2 ... %d", in_h, in_w, out_h, out_w, kRsInMaxExtent);
+    if ((long long)n * (in_h + 2 * kRsInPad) * (in_w + 2 * kRsInPad) > (1ll << 28) || (long long)n * out_h * out_w > (1ll << 28))
+        return fail(TS2D_ERR_INVALID, "ts2d_planes_resample_cubic: %d planes of %d x %d -> %d x %d are more than one call takes (2^28 samples)", n, in_h, in_w, out_h, out_w);
+    if (!p->has_bounds)
+        return fail(TS2D_ERR_STATE, "ts2d_planes_resample_cubic: the planes carry no clip bounds (ts2d_planes_crop_zscore computes them; a resample uses them up)");
+    RsInPlan pl;
+    if (!rsin_plan(n, in_h, in_w, out_h, out_w, &pl))
+        return fail(TS2D_ERR_INVALID, "ts2d_planes_resample_cubic: zoom %d x %d -> %d x %d puts a tap outside the padded plane", in_h, in_w, out_h, out_w);
+    HIP_TRY(hipSetDevice(p->device));
+    char* d_scratch = nullptr; float* d_dst = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_scratch), pl.bytes));
+    hipError_t he = hipMalloc(reinterpret_cast<void**>(&d_dst), (size_t)n * out_h * out_w * sizeof(float));
+    if (he == hipSuccess) he = rsin_run(pl, d_scratch, p->d, p->d_lh, d_dst, n, in_h, in_w, out_h, out_w);
+    if (he == hipSuccess) he = hipDeviceSynchronize();
+    (void)hipFree(d_scratch);
+    if (he != hipSuccess) {
+        if (d_dst) (void)hipFree(d_dst);
+        return fail(he == hipErrorOutOfMemory ? TS2D_ERR_NOMEM : TS2D_ERR_HIP, "ts2d_planes_resample_cubic failed: %s", hipGetErrorString(he));
+    }
+    (void)hipFree(p->d);
+    p->d = d_dst; p->h = out_h; p->w = out_w; p->has_bounds = false;
+    return TS2D_OK;
+}
+
+int ts2d_planes_extent(const ts2d_planes* p, int* h, int* w) {
+    if (!p || !h || !w) return fail(TS2D_ERR_INVALID, "ts2d_planes_extent: null argument");
+    *h = p->h; *w = p->w;
+    return TS2D_OK;
+}
+
+int ts2d_planes_download(const ts2d_planes* p, float* dst) {
+    if (!p || !dst) return fail(TS2D_ERR_INVALID, "ts2d_planes_download: null argument");
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipMemcpy(dst, p->d, (size_t)p->n * p->h * p->w * sizeof(float), hipMemcpyDeviceToHost));
+    return TS2D_OK;
+}
+
+int ts2d_planes_destroy(ts2d_planes* p) {
+    if (!p) return TS2D_OK;
+    (void)hipSetDevice(p->device);
+    if (p->d) (void)hipFree(p->d);
+    if (p->d_lh) (void)hipFree(p->d_lh);
+    delete p;
+    return TS2D_OK;
+}
 int ts2d_synth_slices(int device, unsigned long long key, unsigned long long first_element, unsigned long long n_elements,
                       float* out_device, void* stream) {
     if (!out_device) return fail(TS2D_ERR_INVALID, "ts2d_synth_slices: null output");

@@ -40,6 +40,7 @@ class HIPModel:
         self._dataset_json: Optional[dict] = None
         self.device_threshold = True     # thresholded segmentation straight from the device where the export needs no logits (_run)
         self.device_input_resample = True   # order-3 resample of an off-spacing case's input on the device: the same float32 values as scipy, bit for bit (preprocess.resize_cubic_f64)
+        self.device_input_normalize = True  # crop box, z-score (and that resample) of a native 2-D input on device-resident planes: the same float32 values as numpy, bit for bit (preprocess.zscore_f32_statement)
         self._discover()
 
     # ------------------------------------------------------------------ configuration (reference wrapper.py:113-162)
@@ -142,19 +143,27 @@ class HIPModel:
         """Everything DefaultPreprocessor.run_case_npy reads besides the image itself: two sub-models with the same key preprocess identically."""
         cm, pm = p.configuration_manager, p.plans_manager
         dz = props.get('device_zscore')
-        return repr((props.get('device_resample'),) + (list(getattr(pm, 'transpose_forward', [0, 1, 2])), list(cm.spacing), list(getattr(cm, 'normalization_schemes', None) or []),
+        return repr((props.get('device_resample'), props.get('device_normalize')) + (list(getattr(pm, 'transpose_forward', [0, 1, 2])), list(cm.spacing), list(getattr(cm, 'normalization_schemes', None) or []),
                      list(getattr(cm, 'use_mask_for_norm', None) or []), sorted((p.dataset_json.get('channel_names') or {}).items()),
                      (getattr(pm, 'plans', None) or {}).get('foreground_intensity_properties_per_channel', {}),
                      None if dz is None else tuple(dz.get('order', ()))))
 
-    def _resample_device(self) -> Optional[int]:
-        """GPU index for the input resample: the device of the predictor's engines.  None - the host route - with the switch off and for a
-        predictor that holds no engine of this library (a foreign or host-only predictor: there may be no GPU at all)."""
+    def _input_device(self, switch: bool) -> Optional[int]:
+        """GPU index for a device stage of the input side: the device of the predictor's engines.  None - the host route - with the stage's switch
+        off and for a predictor that holds no engine of this library (a foreign or host-only predictor: there may be no GPU at all)."""
         from .engine import Engine
         engines = getattr(self._predictor, 'engines', None) or []
-        if not self.device_input_resample or not engines or not isinstance(engines[0], Engine):
+        if not switch or not engines or not isinstance(engines[0], Engine):
             return None
         return int(engines[0].device)
+
+    def _resample_device(self) -> Optional[int]:
+        """GPU index for the input resample (``device_input_resample``), or None: the host route."""
+        return self._input_device(self.device_input_resample)
+
+    def _normalize_device(self) -> Optional[int]:
+        """GPU index for crop box and z-score of a native 2-D input (``device_input_normalize``), or None: the host route."""
+        return self._input_device(getattr(self, 'device_input_normalize', False))
 
     def _preprocess_input(self, img):
         """Stage 1 of :meth:`_run`: read, to array, preprocess (the case's shared ``preprocess_cache`` is honoured).
@@ -167,6 +176,8 @@ class HIPModel:
             props['device_zscore'] = ref.device_zscore      # z-score done on the device behind the projection (image.py)
         if self._resample_device() is not None:
             props['device_resample'] = self._resample_device()   # an off-spacing case is resampled to the plan spacing on the device (preprocess.py)
+        if self._normalize_device() is not None:
+            props['device_normalize'] = self._normalize_device()  # a native 2-D input is cropped and z-scored on the device, on planes that stay there for the resample (preprocess.py)
         pre = p.configuration_manager.preprocessor_class(verbose=p.verbose)
         shared = getattr(ref, 'preprocess_cache', None)      # set by TS2D.predict: the sub-models of one case mostly share channels and plan
         if shared is None:

@@ -309,12 +309,17 @@ def cubic_device_entry():
 
 def resample_planes_cubic_device(data: np.ndarray, new_hw, device: int) -> Optional[np.ndarray]:
     """All (channel, slice) planes of ``data`` [C, Z, H, W] float32 through ONE ``ts2d_resample_cubic`` call on ``device``: bit for bit
-    :func:`resize_cubic_f64`, hence scipy, per plane.  None when this is no case for the entry - no entry, not float32, an extent outside
+    :func:`resize_cubic_f64`, hence scipy, per plane.  ``data`` may be a :class:`DevicePlanes` that :meth:`DevicePlanes.crop_zscore` has
+    normalised: its planes are resampled where they lie.  None when this is no case for the entry - no entry, not float32, an extent outside
     2 ... CUBIC_MAX_EXTENT, a plane with a non-finite sample (its min / max say so) - and the caller runs scipy.  A call that FAILS raises."""
     from . import _lib
-    entry = cubic_device_entry()
     c, z, h, w = data.shape
     oh, ow = int(new_hw[0]), int(new_hw[1])
+    if isinstance(data, DevicePlanes):          # z-scored on the device: resampled there, with the clip bounds it kept, and downloaded once
+        if min(h, w, oh, ow) < 2 or max(h, w, oh, ow) > CUBIC_MAX_EXTENT or c * (h + 2 * CUBIC_PAD) * (w + 2 * CUBIC_PAD) > 1 << 28 or c * oh * ow > 1 << 28:
+            return None
+        return data.resample((oh, ow)).download()
+    entry = cubic_device_entry()
     if entry is None or data.dtype != np.float32 or c * z < 1 or min(h, w, oh, ow) < 2 or max(h, w, oh, ow) > CUBIC_MAX_EXTENT:
         return None
     if c * z * (h + 2 * CUBIC_PAD) * (w + 2 * CUBIC_PAD) > 1 << 28 or c * z * oh * ow > 1 << 28:
@@ -343,11 +348,232 @@ def resample_data_to_shape(data: np.ndarray, new_shape, order: int = 3, device: 
         out = resample_planes_cubic_device(data, new_shape[1:], device)
         if out is not None:
             return out
+    if isinstance(data, DevicePlanes):
+        data = data.download()
     out = np.empty((data.shape[0],) + new_shape, dtype=data.dtype)
     for c in range(data.shape[0]):
         for z in range(data.shape[1]):
             out[c, z] = resize_like_skimage(data[c, z], new_shape[1:], order)
     return out
+
+
+SUM_CHUNK = 8192             # numpy's default buffer size in elements (np.getbufsize()): the run add.reduce hands to its pairwise sum
+SUM_LEAF = 128               # numpy's PW_BLOCKSIZE: the longest run summed in eight strided accumulators
+PLANES_MAX_SAMPLES = 1 << 28  # samples one device handle takes (ts2d_planes_create)
+
+
+def pairwise_leaves(n: int):
+    """The leaves of numpy's pairwise sum over a run of ``n`` elements, ``(offset, length)`` in the order the recursion visits them: a run of
+    at most SUM_LEAF elements is a leaf, a longer one splits at ``n2 = n // 2 - (n // 2) % 8``.  The C entry ts2d_planes_crop_zscore walks
+    the same recursion for the partial chunk of a plane."""
+    out = []
+
+    def walk(off, n):
+        if n <= SUM_LEAF:
+            out.append((off, n))
+        else:
+            n2 = n // 2
+            n2 -= n2 % 8
+            walk(off, n2)
+            walk(off + n2, n - n2)
+    walk(0, int(n))
+    return out
+
+
+def _leaf_sums_f32(a: np.ndarray, offs: np.ndarray, length: int) -> np.ndarray:
+    """The float32 sums of the leaves ``a[o : o + length]``, all of one length: fewer than 8 elements one by one from +0, else eight strided
+    accumulators combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) and the ``length % 8`` last elements one by one."""
+    blk = a[offs[:, None] + np.arange(length)[None]]
+    if length < 8:
+        r = np.zeros(len(offs), np.float32)
+        for i in range(length):
+            r = r + blk[:, i]
+        return r
+    m = length - length % 8
+    r8 = blk[:, :8].copy()
+    for i in range(8, m, 8):
+        r8 = r8 + blk[:, i:i + 8]
+    r = ((r8[:, 0] + r8[:, 1]) + (r8[:, 2] + r8[:, 3])) + ((r8[:, 4] + r8[:, 5]) + (r8[:, 6] + r8[:, 7]))
+    for i in range(m, length):
+        r = r + blk[:, i]
+    return r
+
+
+def sum_f32_statement(a: np.ndarray) -> np.float32:
+    """``a.sum()`` of a C-contiguous float32 array as numpy 2.2 computes it, written out: the flattened array goes to add.reduce's inner loop in
+    chunks of SUM_CHUNK elements; the result starts at +0 (so a sum of -0.0 alone is +0.0) and receives the PAIRWISE sum of each chunk in
+    index order (:func:`pairwise_leaves`, the leaves' sums added along the recursion's tree).  A full chunk is 64 leaves of 128 under a
+    perfect binary tree.  Every addition is rounded to float32."""
+    a = np.ascontiguousarray(a, np.float32).reshape(-1)
+    n_full, tail = divmod(a.size, SUM_CHUNK)
+    acc = np.float32(0.0)
+    with np.errstate(over='ignore', invalid='ignore'):
+        if n_full:
+            lv = _leaf_sums_f32(a, np.arange(n_full * (SUM_CHUNK // SUM_LEAF), dtype=np.int64) * SUM_LEAF, SUM_LEAF).reshape(n_full, -1)
+            while lv.shape[1] > 1:
+                lv = lv[:, 0::2] + lv[:, 1::2]
+            for v in lv[:, 0]:
+                acc = np.float32(acc + v)
+        if tail:
+            leaves = pairwise_leaves(tail)
+            offs = np.array([o for o, _ in leaves], np.int64) + n_full * SUM_CHUNK
+            lens = np.array([l for _, l in leaves], np.int64)
+            sums = np.empty(len(leaves), np.float32)
+            for length in np.unique(lens):
+                sel = lens == length
+                sums[sel] = _leaf_sums_f32(a, offs[sel], int(length))
+            it = iter(sums)
+
+            def fold(n):
+                if n <= SUM_LEAF:
+                    return next(it)
+                n2 = n // 2
+                n2 -= n2 % 8
+                left = fold(n2)
+                return np.float32(left + fold(n - n2))
+            acc = np.float32(acc + fold(tail))
+    return acc
+
+
+def zscore_stats_f32_statement(plane: np.ndarray):
+    """``(mean, std, divisor)`` of :func:`zscore_f32_statement`, each a float32."""
+    x = np.ascontiguousarray(plane, np.float32)
+    n = np.float64(x.size)
+    with np.errstate(over='ignore', invalid='ignore'):
+        mean = np.float32(np.float64(sum_f32_statement(x)) / n)         # numpy: float32 sum / intp count, in float64, rounded once
+        d = x - mean
+        var = np.float32(np.float64(sum_f32_statement(d * d)) / n)
+        std = np.sqrt(var)
+    return mean, std, (np.float32(1e-8) if 1e-8 > std else std)         # max(std, 1e-8): the divisor is std unless 1e-8 > std
+
+
+def zscore_f32_statement(plane: np.ndarray) -> np.ndarray:
+    """:func:`zscore` (nnU-Net's ``ZScoreNormalization.run`` without mask) of one C-contiguous float32 plane with numpy's reductions written out,
+    bit for bit what numpy 2.2 returns (tests/test_prep_cpu.py: every float32 value over run lengths that cross every branch, N(0,1),
+    integer-valued, constant, all-zero and high-dynamic-range planes): ``sum`` = :func:`sum_f32_statement`; ``mean = fl32(f64(sum) / n)``;
+    ``d = fl32(x - mean)``; the second sum runs over ``fl32(d * d)``; ``var = fl32(f64(sum) / n)``; ``std = sqrt(var)`` in float32; per element
+    ``fl32(d / div)`` with ``div = std`` unless ``1e-8 > std``, then ``float32(1e-8)``.  For n below 2^24 the two float64 quotients equal the
+    float32 ones.  What had to be found: numpy sums in chunks of its buffer size, so the pairwise tree never spans more than 8192 elements
+    and the chunk sums are added one after the other; and the reduction starts from +0, not from the first element.  This is the statement
+    the device entry ts2d_planes_crop_zscore (csrc/kernels_prep.h) reproduces bit for bit."""
+    x = np.ascontiguousarray(plane, np.float32)
+    mean, _, div = zscore_stats_f32_statement(x)
+    with np.errstate(over='ignore', invalid='ignore'):
+        return (x - mean) / div
+
+
+def crop_box_statement(data: np.ndarray):
+    """:func:`crop_to_nonzero`'s box for ``[C, 1, H, W]`` data: ``[[0, 1], [r0, r1], [c0, c1]]``, half open, over the pixels that are non-zero in
+    any channel; an all-zero image keeps its whole extent.  The device entry ts2d_planes_crop_zscore returns ``(r0, r1, c0, c1)``."""
+    c, z, h, w = data.shape
+    if z != 1:
+        raise ValueError(f"crop_box_statement: one slice per channel is needed, got {z}")
+    nz = (data[:, 0] != 0).any(axis=0)
+    rows, cols = np.flatnonzero(nz.any(axis=1)), np.flatnonzero(nz.any(axis=0))
+    if not len(rows):
+        return [[0, 1], [0, h], [0, w]]
+    return [[0, 1], [int(rows[0]), int(rows[-1]) + 1], [int(cols[0]), int(cols[-1]) + 1]]
+
+
+def planes_device_entries():
+    """The engine library when it has the ``ts2d_planes_*`` entries, or None (no library built, or one built before they existed): the callers
+    then keep the host route, silently - the result is the same."""
+    from . import _lib
+    try:
+        lib = _lib.load()
+    except _lib.EngineLibraryError:
+        return None
+    return lib if hasattr(lib, 'ts2d_planes_create') else None
+
+
+class DevicePlanes:
+    """The planes ``[C, 1, h, w]`` float32 of one native 2-D case on the device, behind a ``ts2d_planes`` handle: uploaded once here, cropped
+    and z-scored (:meth:`crop_zscore`) and resampled (:meth:`resample`) where they lie, downloaded once (:meth:`download`).  Every float32
+    that comes back is the host route's, bit for bit (:func:`zscore_f32_statement`, :func:`resize_cubic_f64`).  A context manager;
+    :meth:`close` destroys the handle and may be called twice."""
+
+    def __init__(self, data: np.ndarray, device: int, lib=None):
+        import ctypes
+        self._lib = lib if lib is not None else planes_device_entries()
+        if self._lib is None:
+            raise RuntimeError("DevicePlanes: the engine library has no ts2d_planes_* entries")
+        data = np.asarray(data)
+        if data.ndim != 4 or data.shape[1] != 1 or data.dtype != np.float32:
+            raise ValueError(f"DevicePlanes: float32 [C, 1, H, W] is needed, got {data.dtype} {data.shape}")
+        src = np.ascontiguousarray(data)
+        self.device, self.channels = int(device), int(data.shape[0])
+        self.stats = None                                   # [C, 2] float32 (mean, std) after crop_zscore
+        self._h = ctypes.c_void_p()
+        self._check(self._lib.ts2d_planes_create(self.device, src.ctypes.data, self.channels, int(data.shape[2]), int(data.shape[3]),
+                                                 ctypes.byref(self._h)), 'ts2d_planes_create')
+
+    @staticmethod
+    def _check(rc, what):
+        from . import _lib
+        _lib.check(rc, what)
+
+    @property
+    def shape(self):
+        import ctypes
+        h, w = ctypes.c_int(), ctypes.c_int()
+        self._check(self._lib.ts2d_planes_extent(self._h, ctypes.byref(h), ctypes.byref(w)), 'ts2d_planes_extent')
+        return (self.channels, 1, h.value, w.value)
+
+    def crop_zscore(self):
+        """crop_to_nonzero and the per-channel z-score on the device.  Returns the box ``[[0, 1], [r0, r1], [c0, c1]]`` the planes now span, or None
+        when the device met a non-finite mean, variance or result: nothing usable was normalised and the caller takes the host route."""
+        import ctypes
+        box, bad = (ctypes.c_int32 * 4)(), ctypes.c_int(0)
+        stats = np.zeros((self.channels, 2), np.float32)
+        self._check(self._lib.ts2d_planes_crop_zscore(self._h, ctypes.byref(box), stats.ctypes.data, ctypes.byref(bad)), 'ts2d_planes_crop_zscore')
+        if bad.value:
+            return None
+        self.stats = stats
+        return [[0, 1], [int(box[0]), int(box[1])], [int(box[2]), int(box[3])]]
+
+    def resample(self, hw):
+        """Order-3 resample of every plane to ``hw`` on the device, clipped to the bounds :meth:`crop_zscore` left."""
+        self._check(self._lib.ts2d_planes_resample_cubic(self._h, int(hw[0]), int(hw[1])), 'ts2d_planes_resample_cubic')
+        return self
+
+    def download(self) -> np.ndarray:
+        out = np.empty(self.shape, np.float32)
+        self._check(self._lib.ts2d_planes_download(self._h, out.ctypes.data), 'ts2d_planes_download')
+        return out
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None and h.value is not None:
+            self._lib.ts2d_planes_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# C * H * W from which the device route of run_case_npy is taken.  Below it the handle's fixed cost (three allocations, a dozen small copies
+# and synchronisations: 0.25 ms) is more than numpy's passes over the planes; measured on two-channel square planes the routes cross between
+# 2 x 128^2 (0.89x) and 2 x 192^2 (1.34x) samples (profiles/r12_native2d_case.txt, DESIGN.md section 7 item 2).
+DEVICE_NORMALIZE_MIN_SAMPLES = 1 << 16
+
+
+def _device_normalize_applies(data, tf, schemes, use_mask, dz) -> bool:
+    """The handle computes nnU-Net's result only for the plain case: identity transpose, one slice per channel, ZScoreNormalization without
+    mask on every channel, no z-score from the projection, extents and sample count inside the handle's limits (and above the size from
+    which it pays), the entries present."""
+    c, z, h, w = data.shape
+    return (list(tf) == [0, 1, 2] and z == 1 and c >= 1 and dz is None
+            and all(s == 'ZScoreNormalization' for s in schemes[:c]) and len(schemes) >= c and not any(use_mask[:c])
+            and 1 <= min(h, w) and max(h, w) <= CUBIC_MAX_EXTENT and DEVICE_NORMALIZE_MIN_SAMPLES <= c * h * w <= PLANES_MAX_SAMPLES
+            and planes_device_entries() is not None)
 
 
 def _device_zscore_applies(dz, data, bbox, tf, schemes, use_mask) -> bool:
@@ -370,17 +596,28 @@ class DefaultPreprocessor:
         data = data.transpose([0] + [i + 1 for i in tf])
         original_spacing = [properties['spacing'][i] for i in tf]
         properties['shape_before_cropping'] = data.shape[1:]
-        data, bbox, nzmask = crop_to_nonzero(data, return_mask=True)
-        properties['bbox_used_for_cropping'] = bbox
-        properties['shape_after_cropping_and_before_resampling'] = data.shape[1:]
-        target_spacing = list(configuration_manager.spacing)
-        if len(target_spacing) < len(data.shape[1:]):
-            target_spacing = [original_spacing[0]] + target_spacing
-        new_shape = [int(round(i / j * k)) for i, j, k in zip(original_spacing, target_spacing, data.shape[1:])]
         schemes = getattr(configuration_manager, 'normalization_schemes', None) or ['ZScoreNormalization'] * data.shape[0]
         use_mask = getattr(configuration_manager, 'use_mask_for_norm', None) or [False] * data.shape[0]
         dz = properties.pop('device_zscore', None)
         device_resample = properties.pop('device_resample', None)     # GPU index for the order-3 resample below (HIPModel sets it), None: host
+        device_normalize = properties.pop('device_normalize', None)   # GPU index for crop box + z-score (+ that resample) on device-resident planes
+        target_spacing = list(configuration_manager.spacing)
+        if len(target_spacing) < len(data.shape[1:]):
+            target_spacing = [original_spacing[0]] + target_spacing
+        if device_normalize is not None and _device_normalize_applies(data, tf, schemes, use_mask, dz):
+            with DevicePlanes(data, device_normalize) as planes:
+                bbox = planes.crop_zscore()
+                if bbox is not None:            # (None: a non-finite sample or sum - numpy below computes what numpy computes of it)
+                    properties['bbox_used_for_cropping'] = bbox
+                    shape = properties['shape_after_cropping_and_before_resampling'] = planes.shape[1:]
+                    new_shape = [int(round(i / j * k)) for i, j, k in zip(original_spacing, target_spacing, shape)]
+                    if list(new_shape) != list(shape):
+                        return resample_data_to_shape(planes, new_shape, order=3, device=device_resample), None, properties
+                    return planes.download(), None, properties
+        data, bbox, nzmask = crop_to_nonzero(data, return_mask=True)
+        properties['bbox_used_for_cropping'] = bbox
+        properties['shape_after_cropping_and_before_resampling'] = data.shape[1:]
+        new_shape = [int(round(i / j * k)) for i, j, k in zip(original_spacing, target_spacing, data.shape[1:])]
         if dz is not None and not _device_zscore_applies(dz, data, bbox, tf, schemes, use_mask):
             dz = None
         fip = (getattr(plans_manager, 'plans', None) or {}).get('foreground_intensity_properties_per_channel', {})
