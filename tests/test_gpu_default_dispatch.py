@@ -39,7 +39,7 @@ from totalsegmentator2d_amd.engine import Engine, unpack_mask
 
 pytestmark = pytest.mark.gpu
 
-CHUNK_ROWS = 64          # kSwChunkRows of csrc/engine.hip (predict_tiled_impl), restated
+CHUNK_ROWS = 64          # kSwChunkRows of csrc/device_tables.h (tiled_plan.cpp packs the rows), restated
 
 
 # ------------------------------------------------------------------------------------------------------------------ helpers
@@ -319,7 +319,7 @@ def test_overflowing_stand_alone_transposed_conv_is_named():
 
 # ------------------------------------------------------------------------------------------------------------------ d. sliding window
 def _chunked_network(engines, rows_per_image):
-    """The network of the host restatement, called as ``predict_tiled_impl`` (csrc/engine.hip) calls it for ONE image per call: the rows of
+    """The network of the host restatement, called as ``predict_tiled_impl`` (csrc/tiled.hip) calls it for ONE image per call: the rows of
     an image (tile-major, mirror variants inside) in chunks of at most kSwChunkRows = 64, in row order, each chunk one forward."""
     def net(batch, fold):
         out = []

@@ -335,7 +335,7 @@ def test_per_axis_strides_in_every_precision_mode(name):
 def test_stage_widths_that_are_not_multiples_of_32(feats, strides):
     """A plans.json may name any features_per_stage (the reference builds whatever arch_kwargs say: ts2d/core/inference/nnu.py:164-165).
     The engine runs such a stage rounded up to a multiple of 32 with zero weights / bias / gamma / beta in the added channels
-    (csrc/engine.hip pad_arch / expand_blob) - exact, so the tolerance is the usual one; the weight blob and every tensor read back
+    (csrc/program.cpp pad_arch / expand_blob) - exact, so the tolerance is the usual one; the weight blob and every tensor read back
     keep the caller's widths."""
     from oracle import torch_oracle as O
     arch = cases.unet(len(feats), feats, 5, cin=2, nconv=2, strides=strides)

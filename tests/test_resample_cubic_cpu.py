@@ -136,6 +136,65 @@ def test_entry_refuses_bad_arguments_by_name_before_any_device_work():
         bad = np.array([bounds], np.float32)
         rc, msg = call(lh=bad.ctypes.data)
         assert rc == -1 and 'ts2d_resample_cubic' in msg and 'clip bounds' in msg, (bounds, rc, msg)
+    # every refusal of the input-side entries that is reached before the device is selected, word for word (the strings were
+    # recorded from the library as it was before the entries moved to their own unit and shared one extent / size check)
+    for entry, args, want in _input_side_refusals():
+        rc = getattr(lib, entry)(*args)
+        assert (rc, _lib.last_error()) == (-1, want), (entry, args, rc, _lib.last_error())
+    handle = ctypes.c_void_p(1234)                        # a refused ts2d_planes_create leaves no handle behind
+    assert lib.ts2d_planes_create(0, src.ctypes.data, 0, 8, 8, ctypes.byref(handle)) == -1 and handle.value is None
+
+
+_SMALL = np.zeros(64, np.float32)
+
+
+def _input_side_refusals():
+    """(entry, arguments, message) - the buffers are small: every call is refused before it reads one."""
+    p = _SMALL.ctypes.data
+    out = ctypes.pointer(ctypes.c_void_p())
+    R, C, J = 'ts2d_resample_cubic', 'ts2d_planes_create', 'ts2d_project_coronal'
+    ext = 'ts2d_resample_cubic: extents %d x %d -> %d x %d outside 2 ... 8192'
+    big = 'ts2d_resample_cubic: %d planes of %d x %d -> %d x %d are more than one call takes (2^28 samples)'
+    view = 'ts2d_project_coronal: the strided view leaves the buffer'
+    return [
+        (R, (0, None, 1, 8, 8, 5, 5, p, p), 'ts2d_resample_cubic: null argument'),
+        (R, (0, p, 1, 8, 8, 5, 5, None, p), 'ts2d_resample_cubic: null argument'),
+        (R, (0, p, 1, 8, 8, 5, 5, p, None), 'ts2d_resample_cubic: null argument'),
+        (R, (0, p, 0, 8, 8, 5, 5, p, p), 'ts2d_resample_cubic: 0 planes'),
+        (R, (0, p, -3, 8, 8, 5, 5, p, p), 'ts2d_resample_cubic: -3 planes'),
+        (R, (0, p, 1, 1, 8, 5, 5, p, p), ext % (1, 8, 5, 5)),
+        (R, (0, p, 1, 8, 1, 5, 5, p, p), ext % (8, 1, 5, 5)),
+        (R, (0, p, 1, 8, 8, 1, 5, p, p), ext % (8, 8, 1, 5)),
+        (R, (0, p, 1, 8, 8, 5, 1, p, p), ext % (8, 8, 5, 1)),
+        (R, (0, p, 1, 8193, 8, 5, 5, p, p), ext % (8193, 8, 5, 5)),
+        (R, (0, p, 1, 8, 8193, 5, 5, p, p), ext % (8, 8193, 5, 5)),
+        (R, (0, p, 1, 8, 8, 8193, 5, p, p), ext % (8, 8, 8193, 5)),
+        (R, (0, p, 1, 8, 8, 5, 8193, p, p), ext % (8, 8, 5, 8193)),
+        (R, (0, p, 1, 0, -4, 5, 5, p, p), ext % (0, -4, 5, 5)),
+        (R, (0, p, 4, 8192, 8192, 5, 5, p, p), big % (4, 8192, 8192, 5, 5)),                  # 4 x 8216 x 8216 padded samples in
+        (R, (0, p, 5, 8, 8, 8192, 8192, p, p), big % (5, 8, 8, 8192, 8192)),                  # 5 x 8192 x 8192 samples out
+        (C, (0, None, 1, 8, 8, out), 'ts2d_planes_create: null argument'),
+        (C, (0, p, 1, 8, 8, None), 'ts2d_planes_create: null argument'),
+        (C, (0, p, 0, 8, 8, out), 'ts2d_planes_create: 0 planes outside 1 ... 65535'),
+        (C, (0, p, 65536, 8, 8, out), 'ts2d_planes_create: 65536 planes outside 1 ... 65535'),
+        (C, (0, p, 1, 0, 8, out), 'ts2d_planes_create: extents 0 x 8 outside 1 ... 8192'),
+        (C, (0, p, 1, 8, 0, out), 'ts2d_planes_create: extents 8 x 0 outside 1 ... 8192'),
+        (C, (0, p, 1, 8193, 8, out), 'ts2d_planes_create: extents 8193 x 8 outside 1 ... 8192'),
+        (C, (0, p, 1, 8, 8193, out), 'ts2d_planes_create: extents 8 x 8193 outside 1 ... 8192'),
+        (C, (0, p, 5, 8192, 8192, out), 'ts2d_planes_create: 5 planes of 8192 x 8192 are more than one handle takes (2^28 samples)'),
+        (J, (0, None, 64, 2, 4, 4, 4, 16, 4, 1, 0, p, p), 'ts2d_project_coronal: null argument'),
+        (J, (0, p, 64, 2, 4, 4, 4, 16, 4, 1, 0, None, p), 'ts2d_project_coronal: null argument'),
+        (J, (0, p, 64, 2, 4, 4, 4, 16, 4, 1, 0, p, None), 'ts2d_project_coronal: null argument'),
+        (J, (0, p, 64, -1, 4, 4, 4, 16, 4, 1, 0, p, p), 'ts2d_project_coronal: bad dtype / extents'),
+        (J, (0, p, 64, 5, 4, 4, 4, 16, 4, 1, 0, p, p), 'ts2d_project_coronal: bad dtype / extents'),
+        (J, (0, p, 64, 2, 0, 4, 4, 16, 4, 1, 0, p, p), 'ts2d_project_coronal: bad dtype / extents'),
+        (J, (0, p, 64, 2, 4, 4, 0, 16, 4, 1, 0, p, p), 'ts2d_project_coronal: bad dtype / extents'),
+        (J, (0, p, 63, 2, 4, 4, 4, 16, 4, 1, 0, p, p), view),                                 # the last element is number 63
+        (J, (0, p, 64, 2, 4, 4, 4, 16, 4, 1, 1, p, p), view),                                 # ... shifted past the end by the base
+        (J, (0, p, 64, 2, 4, 4, 4, 16, 4, 1, -1, p, p), view),                                # a base in front of the buffer
+        (J, (0, p, 64, 2, 4, 4, 4, 16, 4, -1, 2, p, p), view),                                # a negative stride that walks in front of it
+        (J, (0, p, 0, 2, 1, 1, 1, 0, 0, 0, 0, p, p), view),                                   # an empty buffer
+    ]
 
 
 # ------------------------------------------------------------------------------------------------ emitted code

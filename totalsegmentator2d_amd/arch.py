@@ -109,7 +109,7 @@ class UNetArch:
             raise NotImplementedError("conv_bias=False / affine=False are not supported")
         if self.input_channels < 1 or self.num_classes < 1:
             raise ValueError("input_channels and num_classes must be positive")
-        # (any width: the engine rounds a stage up to a multiple of 32 with zero weights in the added channels - exact, csrc/engine.hip pad_arch;
+        # (any width: the engine rounds a stage up to a multiple of 32 with zero weights in the added channels - exact, csrc/program.cpp pad_arch;
         #  the head kernel reads at most 64 channels)
         if any(f < 1 for f in self.features_per_stage):
             raise ValueError("features_per_stage must be positive")

@@ -1,6 +1,7 @@
 // libts2d_engine.so - host side of the MI355X-native 2-D U-Net engine + the C-ABI of include/ts2d_engine.h.
 // Replaces the network-forward part of nnUNetPredictor (reference seam: ts2d/core/inference/prediction_worker.py:209,
 // network built at ts2d/core/inference/nnu.py:164-165).  gfx950 only; no CPU fallback exists in this library.
+// This unit is the network: workspace, launchers, forward, result check.  The sliding window around it is tiled.hip, the input side prep.hip.
 #include "engine_internal.h"
 #include "kernels.h"
 #include "kernels_f16x3.h"
@@ -17,12 +18,6 @@
 #include "kernels_upq.h"
 #include "kernels_upc_h.h"
 #include "kernels_upc_h2.h"
-#include "kernels_sw.h"
-#include "kernels_fold.h"
-#include "kernels_resample.h"
-#include "kernels_resample_in.h"
-#include "kernels_project.h"
-#include "kernels_prep.h"
 
 #include <atomic>
 #include <cstdio>
@@ -41,15 +36,6 @@ namespace {
 // and remembers it; an engine whose token is no longer in the header knows that ANOTHER engine of the set has overwritten its
 // activations since (ts2d_engine_debug_tensor / ts2d_engine_check must not read them as its own - ADVICE r4).
 std::atomic<uint32_t> g_ws_generation{0};
-
-#define HIP_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess)                                                                             \
-            return fail(_e == hipErrorOutOfMemory ? TS2D_ERR_NOMEM : TS2D_ERR_HIP, "%s failed: %s (%s:%d)", \
-                        #expr, hipGetErrorString(_e), __FILE__, __LINE__);                                \
-    } while (0)
-#define TRY(expr) do { int _rc = (expr); if (_rc != TS2D_OK) return _rc; } while (0)
 
 int upload_weights(ts2d_engine* e, const float* blob, size_t n_floats) {
     // (pack_weights also records the per-layer split scale in the op table)
@@ -665,7 +651,9 @@ bool workspace_is_mine(ts2d_engine* e) {
     return tok == e->ws_token;
 }
 
-int run_forward(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st, bool clear_flags, bool full) {
+}  // namespace
+
+int ts2d::run_forward(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st, bool clear_flags, bool full) {
     TRY(workspace_acquire(e, st));
     if (e->ws_external) {           // stamp the shared workspace: whatever another engine of the set left in it is gone after this run
         e->ws_token = ++g_ws_generation;
@@ -678,7 +666,15 @@ int run_forward(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d
     return rc != TS2D_OK ? rc : rc2;
 }
 
-}  // namespace
+int ts2d::reserve_checked(ts2d_engine* e, int B, int H, int W, bool full) {
+    const int divy = 1 << e->lvl_y[e->arch.n_stages - 1], divx = 1 << e->lvl_x[e->arch.n_stages - 1];
+    if (B < 1 || H < divy || W < divx || H % divy || W % divx)
+        return fail(TS2D_ERR_INVALID, "shape B=%d H=%d W=%d: H and W must be positive multiples of %d and %d", B, H, W, divy, divx);
+    if ((H / divy) * (W / divx) <= 1)   // torch InstanceNorm2d raises "Expected more than 1 spatial element" here too
+        return fail(TS2D_ERR_INVALID, "shape %dx%d leaves a single bottleneck pixel: InstanceNorm needs more than 1 spatial element", H, W);
+    if ((long long)B * H * W >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "B*H*W = %lld exceeds 2^31 pixels per call", (long long)B * H * W);
+    return ensure_workspace(e, B, H, W, full);
+}
 
 // ------------------------------------------------------------------------------------------------- C-ABI
 extern "C" {
@@ -785,16 +781,6 @@ int ts2d_engine_weights_ready(ts2d_engine* e) {
     return TS2D_OK;
 }
 
-static int reserve_checked(ts2d_engine* e, int B, int H, int W, bool full) {
-    const int divy = 1 << e->lvl_y[e->arch.n_stages - 1], divx = 1 << e->lvl_x[e->arch.n_stages - 1];
-    if (B < 1 || H < divy || W < divx || H % divy || W % divx)
-        return fail(TS2D_ERR_INVALID, "shape B=%d H=%d W=%d: H and W must be positive multiples of %d and %d", B, H, W, divy, divx);
-    if ((H / divy) * (W / divx) <= 1)   // torch InstanceNorm2d raises "Expected more than 1 spatial element" here too
-        return fail(TS2D_ERR_INVALID, "shape %dx%d leaves a single bottleneck pixel: InstanceNorm needs more than 1 spatial element", H, W);
-    if ((long long)B * H * W >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "B*H*W = %lld exceeds 2^31 pixels per call", (long long)B * H * W);
-    return ensure_workspace(e, B, H, W, full);
-}
-
 int ts2d_engine_reserve(ts2d_engine* e, int B, int H, int W) {
     if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_reserve: null engine");
     return reserve_checked(e, B, H, W, kBySize);
@@ -842,314 +828,6 @@ int ts2d_engine_forward(ts2d_engine* e, const float* input, int B, int H, int W,
     if (mask_packed) HIP_TRY(hipMemcpyAsync(mask_packed, e->d_mask_stage, (size_t)B * K * H * (W / 32) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return ts2d_engine_check(e);          // never a silent inf / NaN (asynchronous device-pointer calls: the caller runs the check)
-}
-
-// The sliding window of both C entries (include/ts2d_engine.h): N images as ONE engine batch; ts2d_engine_predict_tiled is N = 1.
-// Host side: validate everything, pack the rows (tile x mirror variant) of the images into chunks of at most kSwChunkRows, lay the
-// scratch out, enqueue every host-to-device copy, then per chunk one sw_gather, one forward and (where an image ends in the chunk)
-// one sw_aggregate, then every device-to-host copy, ONE stream synchronise and the result check.
-// `full` is the whole difference between the entries' results: the batch entry asks for the full-batch dispatch (a row's bits must not
-// depend on its batch-mates), the single-image entry for the size-dependent one.  `name_images`: a message names the image it is about.
-// `exports` (ts2d_engine_predict_tiled_export; else null): one descriptor per image - behind the last aggregate ONE sw_resample_threshold
-// launch resamples every image's half logits to its export extent where they lie in the scratch.
-// `engines[0 .. F)` (ts2d_ensemble_predict_tiled_export; the other entries are F = 1): the folds of an ensemble, one after the other on
-// the FIRST engine's stream and in its scratch - the chunk loop once per fold, sw_aggregate into the fold's own half slot and inf
-// flags, then ONE sw_fold_mean (kernels_fold.h) into slot 0, on which the tail below runs as it does on a single fold's logits.  Only
-// the half slots and the flags exist F times.  `name_folds`: a fold's failed reserve or result check is reported as "fold <f>: ...".
-constexpr int kSwChunkRows = 64;
-constexpr int kMaxFolds = 32;
-
-static int name_fold(int rc, bool name_folds, int f) {
-    if (rc == TS2D_OK || !name_folds) return rc;
-    const std::string msg = last_error();
-    return fail(rc, "fold %d: %s", f, msg.c_str());
-}
-
-// Taps of one axis of the order-1 resample (n_in -> n_out samples; preprocess.linear_axis_taps is the same statement in numpy, pinned
-// to scipy): cc = (o + 0.5) * (n_in / n_out) - 0.5, i0 = floor(cc), w1 = cc - i0, all in float64; the coordinate is not clamped, the
-// two INDICES are (scipy extends the array by its edge samples).  `origin` shifts the indices to the padded plane.
-// No contraction: a fused (o + 0.5) * zoom - 0.5 would round differently from numpy on a host build that has FMA (-march=native).
-static void rs_axis_taps(int n_in, int n_out, int origin, RsTap* t) {
-#pragma clang fp contract(off)
-    const double zoom = (double)n_in / (double)n_out;
-    for (int o = 0; o < n_out; ++o) {
-        const double prod = ((double)o + 0.5) * zoom;
-        const double cc = prod - 0.5;
-        const double f = std::floor(cc);
-        const long long i0 = (long long)f;
-        t[o].w1 = cc - f; t[o].w0 = 1.0 - t[o].w1;
-        t[o].i0 = origin + (int)std::min<long long>(std::max<long long>(i0, 0), n_in - 1);
-        t[o].i1 = origin + (int)std::min<long long>(std::max<long long>(i0 + 1, 0), n_in - 1);
-    }
-}
-
-static int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images,
-                              int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, bool full, bool name_images, bool name_folds,
-                              const char* entry) {
-    ts2d_engine* e = engines[0];
-    if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "%s: bad patch %dx%d", entry, ph, pw);
-    const int C = e->arch.input_channels, K = e->arch.num_classes;
-    int vflip[4] = {0, 0, 0, 0}, V = 1;
-    if ((mirror_mask & 3) == 3) { vflip[1] = 1; vflip[2] = 2; vflip[3] = 3; V = 4; }
-    else if (mirror_mask & 1) { vflip[1] = 1; V = 2; }
-    else if (mirror_mask & 2) { vflip[1] = 2; V = 2; }
-    const int vflips = vflip[0] | (vflip[1] << 8) | (vflip[2] << 16) | (vflip[3] << 24);
-    long long n_tiles_all = 0, n_taps_all = 0;
-    bool any16 = F > 1, anyseg = false, any_rs8 = false, any_rs32 = false;      // (the mean is taken over the half buffers)
-    for (int i = 0; i < n_images; ++i) {
-        const ts2d_tiled_image& im = images[i];
-        char pre[24] = "";
-        if (name_images) snprintf(pre, sizeof(pre), "image %d: ", i);
-        if (!im.image || !im.tile_y || !im.tile_x) return fail(TS2D_ERR_INVALID, "%snull image or tile pointer", pre);
-        if (!exports && !im.logits_f16 && !im.seg_u8) return fail(TS2D_ERR_INVALID, "%sboth outputs are null", pre);
-        if (im.n_tiles < 1 || im.n_tiles > (1 << 20) || im.Hp < 1 || im.Wp < 1 || ph > im.Hp || pw > im.Wp)
-            return fail(TS2D_ERR_INVALID, "%sbad tiling: %d tiles of %dx%d on %dx%d", pre, im.n_tiles, ph, pw, im.Hp, im.Wp);
-        if ((long long)K * im.Hp * im.Wp >= (1LL << 31) || (long long)C * im.Hp * im.Wp >= (1LL << 31))
-            return fail(TS2D_ERR_INVALID, "%s%dx%d exceeds 2^31 elements per image", pre, im.Hp, im.Wp);
-        for (int t = 0; t < im.n_tiles; ++t)
-            if (im.tile_y[t] < 0 || im.tile_x[t] < 0 || im.tile_y[t] + ph > im.Hp || im.tile_x[t] + pw > im.Wp)
-                return fail(TS2D_ERR_INVALID, "%stile %d at (%d,%d) leaves the %dx%d image", pre, t, im.tile_y[t], im.tile_x[t], im.Hp, im.Wp);
-        n_tiles_all += im.n_tiles;
-        any16 |= im.logits_f16 != nullptr; anyseg |= im.seg_u8 != nullptr;
-        if (!exports) continue;
-        const ts2d_tiled_export& ex = exports[i];
-        if (!ex.seg_u8 && !ex.logits_f32) return fail(TS2D_ERR_INVALID, "%sexport: both outputs are null", pre);
-        if (ex.src_h < 1 || ex.src_w < 1 || ex.src_y < 0 || ex.src_x < 0 || ex.src_h > im.Hp - ex.src_y || ex.src_w > im.Wp - ex.src_x)
-            return fail(TS2D_ERR_INVALID, "%sexport: source rectangle %dx%d at (%d,%d) is empty or leaves the %dx%d image", pre, ex.src_h, ex.src_w,
-                        ex.src_y, ex.src_x, im.Hp, im.Wp);
-        if (ex.out_h < 1 || ex.out_w < 1) return fail(TS2D_ERR_INVALID, "%sexport: bad output extent %dx%d", pre, ex.out_h, ex.out_w);
-        if ((long long)K * ex.out_h * ex.out_w >= (1LL << 31))
-            return fail(TS2D_ERR_INVALID, "%sexport: %dx%d exceeds 2^31 output elements", pre, ex.out_h, ex.out_w);
-        n_taps_all += (long long)ex.out_h + ex.out_w;         // (each < 2^31 by the check above; bounded before any table is allocated)
-        if (n_taps_all >= (1LL << 26)) return fail(TS2D_ERR_INVALID, "%sexport: more than 2^26 output rows + columns in one call", pre);
-        any16 = true; any_rs8 |= ex.seg_u8 != nullptr; any_rs32 |= ex.logits_f32 != nullptr;
-    }
-    if (n_tiles_all * V >= (1LL << 28)) return fail(TS2D_ERR_INVALID, "%s: %lld network rows in one call", entry, n_tiles_all * V);
-    // ---- row packing: whole images, greedily, into chunks of at most kSwChunkRows rows; a larger image takes chunks of its own
-    struct Chunk { int seg0, n_segs, rows, log_row; bool aggregate; unsigned gblocks, ablocks; };
-    std::vector<SwSeg> segs;
-    std::vector<Chunk> chunks;
-    std::vector<size_t> o_img(n_images);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const int pwq = (pw + 3) / 4;
-    auto blocks_of = [](long long lanes) { return (lanes + 255) / 256; };
-    long long out_elems = 0, img_floats = 0;
-    int tile0 = 0, cap_rows = 0;
-    long long log_rows = 0;
-    Chunk cur{0, 0, 0, 0, true, 0, 0};
-    auto flush = [&]() { if (cur.n_segs) chunks.push_back(cur); cur = Chunk{(int)segs.size(), 0, 0, 0, true, 0, 0}; };
-    for (int i = 0; i < n_images; ++i) {
-        const ts2d_tiled_image& im = images[i];
-        const int rows = im.n_tiles * V;
-        SwSeg sg{};
-        sg.img_off = img_floats; sg.out_off = out_elems; sg.Hp = im.Hp; sg.Wp = im.Wp; sg.tile0 = tile0; sg.n_tiles = im.n_tiles; sg.image = i;
-        const long long ablocks = blocks_of((long long)K * im.Hp * ((im.Wp + 3) / 4));
-        if (rows > kSwChunkRows) {
-            flush();
-            for (int r0 = 0; r0 < rows; r0 += kSwChunkRows) {
-                const int nb = std::min(kSwChunkRows, rows - r0);
-                sg.row0 = r0; sg.n_rows = nb; sg.batch_row = 0; sg.log_row = 0; sg.gblock0 = 0; sg.ablock0 = 0;
-                segs.push_back(sg);
-                cur.n_segs = 1; cur.rows = nb; cur.log_row = r0; cur.aggregate = r0 + nb == rows;
-                cur.gblocks = (unsigned)blocks_of((long long)nb * C * ph * pwq); cur.ablocks = (unsigned)ablocks;
-                flush();
-            }
-        } else {
-            if (cur.rows + rows > kSwChunkRows) flush();
-            sg.row0 = 0; sg.n_rows = rows; sg.batch_row = cur.rows; sg.log_row = cur.rows; sg.gblock0 = cur.gblocks; sg.ablock0 = cur.ablocks;
-            segs.push_back(sg);
-            cur.n_segs++; cur.rows += rows;
-            cur.gblocks += (unsigned)blocks_of((long long)rows * C * ph * pwq); cur.ablocks += (unsigned)ablocks;
-        }
-        cap_rows = std::max(cap_rows, std::min(rows, kSwChunkRows)); log_rows = std::max<long long>(log_rows, rows);
-        tile0 += im.n_tiles;
-        img_floats += (long long)align_up((size_t)C * im.Hp * im.Wp, 64);
-        out_elems += (long long)align_up((size_t)K * im.Hp * im.Wp, 256);
-    }
-    flush();
-    for (const Chunk& c : chunks) {
-        cap_rows = std::max(cap_rows, c.rows);
-        if ((long long)c.gblocks >= (1LL << 31) || (long long)c.ablocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: a chunk exceeds 2^31 blocks", entry);
-    }
-    log_rows = std::max<long long>(log_rows, cap_rows);
-    if (F > 1 && blocks_of(out_elems >> 3) >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the fold mean exceeds 2^31 blocks", entry);
-    // ---- the export: one segment per image (its half logits are segs' out_off), the taps of its rows then of its columns
-    std::vector<RsSeg> rsegs;
-    std::vector<RsTap> rtaps;
-    long long rs_elems = 0, rs_blocks = 0;
-    if (exports) {
-        long long oo = 0;
-        for (int i = 0; i < n_images; ++i) {
-            const ts2d_tiled_image& im = images[i]; const ts2d_tiled_export& ex = exports[i];
-            RsSeg rs{};
-            rs.src_off = oo; rs.dst_off = rs_elems; rs.Hp = im.Hp; rs.Wp = im.Wp; rs.out_h = ex.out_h; rs.out_w = ex.out_w;
-            rs.tap0 = (int)rtaps.size(); rs.block0 = (unsigned)rs_blocks;
-            rsegs.push_back(rs);
-            rtaps.resize(rtaps.size() + ex.out_h + ex.out_w);
-            rs_axis_taps(ex.src_h, ex.out_h, ex.src_y, rtaps.data() + rs.tap0);
-            rs_axis_taps(ex.src_w, ex.out_w, ex.src_x, rtaps.data() + rs.tap0 + ex.out_h);
-            rs_blocks += blocks_of((long long)K * ex.out_h * ((ex.out_w + 3) / 4));
-            rs_elems += (long long)align_up((size_t)K * ex.out_h * ex.out_w, 256);
-            oo += (long long)align_up((size_t)K * im.Hp * im.Wp, 256);
-        }
-        if (rs_blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the export exceeds 2^31 blocks", entry);
-    }
-    for (int f = 0; f < F; ++f) TRY(name_fold(reserve_checked(engines[f], cap_rows, ph, pw, full), name_folds, f));
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t st = e->stream;
-    // ---- the descriptor table and every tile origin: one host blob, one copy
-    const size_t tab_segs = segs.size() * sizeof(SwSeg), tab_rsegs = align_up(tab_segs + 2 * (size_t)n_tiles_all * 4, 8);
-    const size_t tab_rtaps = tab_rsegs + rsegs.size() * sizeof(RsSeg), tab_bytes = tab_rtaps + rtaps.size() * sizeof(RsTap);
-    std::vector<char> tab(tab_bytes);
-    memcpy(tab.data(), segs.data(), tab_segs);
-    if (exports) { memcpy(tab.data() + tab_rsegs, rsegs.data(), rsegs.size() * sizeof(RsSeg)); memcpy(tab.data() + tab_rtaps, rtaps.data(), rtaps.size() * sizeof(RsTap)); }
-    {
-        int32_t* ty = reinterpret_cast<int32_t*>(tab.data() + tab_segs); int32_t* tx = ty + n_tiles_all;
-        for (int i = 0; i < n_images; ++i) {
-            memcpy(ty, images[i].tile_y, (size_t)images[i].n_tiles * 4); memcpy(tx, images[i].tile_x, (size_t)images[i].n_tiles * 4);
-            ty += images[i].n_tiles; tx += images[i].n_tiles;
-        }
-    }
-    // ---- scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs x F | uint8 outputs | flags x F | resampled uint8 | resampled float]
-    const size_t o_tab = take(tab_bytes), o_g = take((size_t)ph * pw * 2), o_imgs = take((size_t)img_floats * 4);
-    const size_t o_batch = take((size_t)cap_rows * C * ph * pw * 4), o_log = take((size_t)log_rows * K * ph * pw * 4);
-    const size_t o_o16 = take(any16 ? (size_t)F * out_elems * 2 : 0), o_seg = take(anyseg ? (size_t)out_elems : 0), o_flag = take((size_t)F * n_images * 4);
-    const size_t o_rs8 = take(any_rs8 ? (size_t)rs_elems : 0), o_rs32 = take(any_rs32 ? (size_t)rs_elems * 4 : 0);
-    if (off > e->sw_bytes) {                                  // grown before the first launch only
-        HIP_TRY(hipStreamSynchronize(st));
-        if (e->d_sw) { HIP_TRY(hipFree(e->d_sw)); e->d_sw = nullptr; e->sw_bytes = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&e->d_sw), off));
-        e->sw_bytes = off;
-    }
-    char* b = e->d_sw;
-    const SwSeg* d_segs = reinterpret_cast<const SwSeg*>(b + o_tab);
-    const int* d_ty = reinterpret_cast<const int*>(b + o_tab + tab_segs); const int* d_tx = d_ty + n_tiles_all;
-    __half* d_g = reinterpret_cast<__half*>(b + o_g); float* d_imgs = reinterpret_cast<float*>(b + o_imgs);
-    float* d_batch = reinterpret_cast<float*>(b + o_batch); float* d_log = reinterpret_cast<float*>(b + o_log);
-    __half* d_o16 = any16 ? reinterpret_cast<__half*>(b + o_o16) : nullptr; uint8_t* d_seg = anyseg ? reinterpret_cast<uint8_t*>(b + o_seg) : nullptr;
-    int* d_flag = reinterpret_cast<int*>(b + o_flag);
-    for (int i = 0; i < n_images; ++i) images[i].inf_flag = 0;
-    HIP_TRY(hipMemcpyAsync(b + o_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
-    if (gaussian_f16) HIP_TRY(hipMemcpyAsync(d_g, gaussian_f16, (size_t)ph * pw * 2, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)F * n_images * 4, st));
-    {
-        long long io = 0;
-        for (int i = 0; i < n_images; ++i) {
-            const size_t nf = (size_t)C * images[i].Hp * images[i].Wp;
-            HIP_TRY(hipMemcpyAsync(d_imgs + io, images[i].image, nf * 4, hipMemcpyHostToDevice, st));
-            io += (long long)align_up(nf, 64);
-        }
-    }
-    for (int f = 0; f < F; ++f)
-        for (size_t ci = 0; ci < chunks.size(); ++ci) {
-            const Chunk& c = chunks[ci];
-            hipLaunchKernelGGL(sw_gather, dim3(c.gblocks), dim3(256), 0, st, d_imgs, d_segs + c.seg0, c.n_segs, C, ph, pw, V, vflips, d_ty, d_tx, d_batch);
-            HIP_TRY(hipGetLastError());
-            TRY(run_forward(engines[f], d_batch, c.rows, ph, pw, d_log + (size_t)c.log_row * K * ph * pw, nullptr, st, ci == 0, full));
-            if (!c.aggregate) continue;
-            // (an ensemble's uint8 output is the predicate on the MEAN: sw_fold_mean writes it)
-            hipLaunchKernelGGL(sw_aggregate, dim3(c.ablocks), dim3(256), 0, st, d_log, d_segs + c.seg0, c.n_segs, K, ph, pw, V, vflips, d_ty, d_tx,
-                               gaussian_f16 ? d_g : nullptr, d_o16 ? d_o16 + (size_t)f * out_elems : nullptr, F > 1 ? nullptr : d_seg,
-                               kSigmoidHalfThreshold, d_flag + (size_t)f * n_images, e->tile_half);
-            HIP_TRY(hipGetLastError());
-        }
-    if (F > 1) {          // every slot up to the end of the last image (the alignment gaps between the images ride along unread)
-        const long long n_mean = segs.back().out_off + (long long)K * segs.back().Hp * segs.back().Wp;
-        hipLaunchKernelGGL(sw_fold_mean, dim3((unsigned)blocks_of((n_mean >> 3) + (n_mean & 7))), dim3(256), 0, st, d_o16, out_elems, F, n_mean,
-                           d_seg, kSigmoidHalfThreshold);
-        HIP_TRY(hipGetLastError());
-    }
-    uint8_t* d_rs8 = any_rs8 ? reinterpret_cast<uint8_t*>(b + o_rs8) : nullptr; float* d_rs32 = any_rs32 ? reinterpret_cast<float*>(b + o_rs32) : nullptr;
-    if (exports) {
-        hipLaunchKernelGGL(sw_resample_threshold, dim3((unsigned)rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + o_tab + tab_rsegs),
-                           n_images, K, reinterpret_cast<const RsTap*>(b + o_tab + tab_rtaps), d_rs8, d_rs32, kSigmoidHalfThreshold);
-        HIP_TRY(hipGetLastError());
-        for (int i = 0; i < n_images; ++i) {
-            const size_t ne = (size_t)K * exports[i].out_h * exports[i].out_w;
-            if (exports[i].seg_u8) HIP_TRY(hipMemcpyAsync(exports[i].seg_u8, d_rs8 + rsegs[i].dst_off, ne, hipMemcpyDeviceToHost, st));
-            if (exports[i].logits_f32) HIP_TRY(hipMemcpyAsync(exports[i].logits_f32, d_rs32 + rsegs[i].dst_off, ne * 4, hipMemcpyDeviceToHost, st));
-        }
-    }
-    std::vector<int> flags((size_t)F * n_images, 0);
-    HIP_TRY(hipMemcpyAsync(flags.data(), d_flag, (size_t)F * n_images * 4, hipMemcpyDeviceToHost, st));
-    {
-        long long oo = 0;
-        for (int i = 0; i < n_images; ++i) {
-            const size_t ne = (size_t)K * images[i].Hp * images[i].Wp;
-            if (images[i].logits_f16) HIP_TRY(hipMemcpyAsync(images[i].logits_f16, d_o16 + oo, ne * 2, hipMemcpyDeviceToHost, st));
-            if (images[i].seg_u8) HIP_TRY(hipMemcpyAsync(images[i].seg_u8, d_seg + oo, ne, hipMemcpyDeviceToHost, st));
-            oo += (long long)align_up(ne, 256);
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int f = 0; f < F; ++f) {         // upstream looks for inf in every fold's aggregated array, not in the mean
-        engines[f]->tiled_inf = 0;
-        for (int i = 0; i < n_images; ++i) {
-            const int inf = flags[(size_t)f * n_images + i] != 0;
-            images[i].inf_flag = f ? (images[i].inf_flag | inf) : inf;
-            engines[f]->tiled_inf |= inf;
-        }
-    }
-    for (int f = 0; f < F; ++f) TRY(name_fold(ts2d_engine_check(engines[f]), name_folds, f));
-    return TS2D_OK;
-}
-
-int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp, int ph, int pw, int n_tiles,
-                              const int32_t* tile_y, const int32_t* tile_x, int mirror_mask, const uint16_t* gaussian_f16,
-                              uint16_t* logits_f16, uint8_t* seg_u8) {
-    if (!e || !image || !tile_y || !tile_x) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: null argument");
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
-    if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
-    ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
-    return predict_tiled_impl(&e, 1, &one, nullptr, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
-}
-
-int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
-                                    const uint16_t* gaussian_f16) {
-    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: null engine");
-    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
-    if (n_images == 0) return TS2D_OK;
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
-    return predict_tiled_impl(&e, 1, images, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
-}
-
-int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
-                                     int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
-    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: null engine");
-    if (n_images < 0 || (n_images > 0 && !(images && exports)))
-        return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: %d images at a null pointer", n_images);
-    if (n_images == 0) return TS2D_OK;
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_export: weights not loaded");
-    return predict_tiled_impl(&e, 1, images, exports, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
-                              "ts2d_engine_predict_tiled_export");
-}
-
-int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_export* exports,
-                                       int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
-    static const char* entry = "ts2d_ensemble_predict_tiled_export";
-    if (!engines) return fail(TS2D_ERR_INVALID, "%s: %d engines at a null pointer", entry, n_engines);
-    if (n_engines < 1 || n_engines > kMaxFolds) return fail(TS2D_ERR_INVALID, "%s: n_engines = %d is outside 1..%d", entry, n_engines, kMaxFolds);
-    for (int f = 0; f < n_engines; ++f)
-        if (!engines[f]) return fail(TS2D_ERR_INVALID, "%s: engine %d is null", entry, f);
-    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
-    if (n_images == 0) return TS2D_OK;
-    const ts2d_engine* e0 = engines[0];
-    for (int f = 0; f < n_engines; ++f) {
-        const ts2d_engine* e = engines[f];
-        if (!e->weights_ready) return fail(TS2D_ERR_STATE, "%s: fold %d: weights not loaded", entry, f);
-        if (e->device != e0->device) return fail(TS2D_ERR_INVALID, "%s: fold %d is on device %d, fold 0 on device %d", entry, f, e->device, e0->device);
-        if (e->arch.input_channels != e0->arch.input_channels)
-            return fail(TS2D_ERR_INVALID, "%s: fold %d has %d input channels, fold 0 has %d", entry, f, e->arch.input_channels, e0->arch.input_channels);
-        if (e->arch.num_classes != e0->arch.num_classes)
-            return fail(TS2D_ERR_INVALID, "%s: fold %d has num_classes %d, fold 0 has %d", entry, f, e->arch.num_classes, e0->arch.num_classes);
-        if (e->precision != e0->precision)
-            return fail(TS2D_ERR_INVALID, "%s: fold %d runs precision mode %d, fold 0 mode %d", entry, f, e->precision, e0->precision);
-        if (e->tile_half != e0->tile_half)
-            return fail(TS2D_ERR_INVALID, "%s: fold %d blends with tile dtype %d, fold 0 with %d", entry, f, e->tile_half, e0->tile_half);
-    }
-    return predict_tiled_impl(engines, n_engines, images, exports, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
-                              true, true, entry);
 }
 
 int ts2d_engine_check(ts2d_engine* e) {
@@ -1233,433 +911,6 @@ int ts2d_engine_check(ts2d_engine* e) {
                 e->precision == TS2D_PRECISION_F32_EXACT ? "" :
                 " (the fp16 products of this precision mode need |activation| < 65504 at every conv input: "
                 "an overflowing activation - e.g. an un-normalised transposed-conv output - becomes inf; use TS2D_PRECISION_F32_EXACT for such weights)");
-}
-
-int ts2d_engine_tiled_inf_flag(const ts2d_engine* e) { return e ? (e->tiled_inf != 0) : 0; }
-
-static int project_coronal_impl(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz,
-                                long long sy, long long sx, long long base, float* out_max, float* out_mean, float* out_norm, double* out_stats, int* out_box) {
-    if (!volume || !out_max || !out_mean) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal: null argument");
-    static const int esize[5] = {2, 1, 4, 2, 4};
-    if (dtype < 0 || dtype > 4 || nz < 1 || ny < 1 || nx < 1) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal: bad dtype / extents");
-    {   // every element the view can touch must lie inside the buffer
-        long long lo = base, hi = base;
-        const long long ext[3] = {(long long)(nz - 1) * sz, (long long)(ny - 1) * sy, (long long)(nx - 1) * sx};
-        for (int k = 0; k < 3; ++k) { if (ext[k] < 0) lo += ext[k]; else hi += ext[k]; }
-        if (lo < 0 || hi >= (long long)n_elems) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal: the strided view leaves the buffer");
-    }
-    HIP_TRY(hipSetDevice(device));
-    const size_t vbytes = n_elems * esize[dtype], obytes = (size_t)nz * nx * sizeof(float);
-    char* d = nullptr;
-    // [volume | max | mean (contiguous: the two channels of the z-score) | normalised x 2 | partial sums | stats | box]
-    const size_t o_proj = align_up(vbytes, 256), o_norm = align_up(o_proj + 2 * obytes, 256), o_part = align_up(o_norm + 2 * obytes, 256);
-    const size_t o_stats = o_part + 2 * kZBlocks * sizeof(double), o_box = o_stats + 4 * sizeof(double);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), o_box + 4 * sizeof(int)));
-    float* d_max = reinterpret_cast<float*>(d + o_proj);
-    float* d_mean = d_max + (size_t)nz * nx;
-    hipError_t he = hipMemcpy(d, volume, vbytes, hipMemcpyHostToDevice);
-    if (he == hipSuccess) {
-        const unsigned grid = (unsigned)(((long long)nz * nx + 255) / 256);
-        switch (dtype) {
-            case 0: hipLaunchKernelGGL(project_coronal<int16_t>, dim3(grid), dim3(256), 0, 0, reinterpret_cast<const int16_t*>(d), nz, ny, nx, sz, sy, sx, base, d_max, d_mean); break;
-            case 1: hipLaunchKernelGGL(project_coronal<uint8_t>, dim3(grid), dim3(256), 0, 0, reinterpret_cast<const uint8_t*>(d), nz, ny, nx, sz, sy, sx, base, d_max, d_mean); break;
-            case 2: hipLaunchKernelGGL(project_coronal<float>, dim3(grid), dim3(256), 0, 0, reinterpret_cast<const float*>(d), nz, ny, nx, sz, sy, sx, base, d_max, d_mean); break;
-            case 3: hipLaunchKernelGGL(project_coronal<uint16_t>, dim3(grid), dim3(256), 0, 0, reinterpret_cast<const uint16_t*>(d), nz, ny, nx, sz, sy, sx, base, d_max, d_mean); break;
-            default: hipLaunchKernelGGL(project_coronal<int32_t>, dim3(grid), dim3(256), 0, 0, reinterpret_cast<const int32_t*>(d), nz, ny, nx, sz, sy, sx, base, d_max, d_mean); break;
-        }
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess && out_norm) {          // per-channel z-score of (max, mean): float64 two-pass statistics, deterministic
-        const long long n = (long long)nz * nx;
-        float* d_norm = reinterpret_cast<float*>(d + o_norm);
-        double* d_part = reinterpret_cast<double*>(d + o_part); double* d_stats = reinterpret_cast<double*>(d + o_stats);
-        int* d_box = reinterpret_cast<int*>(d + o_box);
-        const int box0[4] = {nz, -1, nx, -1};
-        he = hipMemcpy(d_box, box0, sizeof(box0), hipMemcpyHostToDevice);
-        if (he == hipSuccess) {
-            hipLaunchKernelGGL(zs_partial<0>, dim3(kZBlocks, 2), dim3(256), 0, 0, d_max, n, d_stats, d_part);
-            hipLaunchKernelGGL(zs_combine<0>, dim3(1), dim3(2), 0, 0, d_part, n, d_stats);
-            hipLaunchKernelGGL(zs_partial<1>, dim3(kZBlocks, 2), dim3(256), 0, 0, d_max, n, d_stats, d_part);
-            hipLaunchKernelGGL(zs_combine<1>, dim3(1), dim3(2), 0, 0, d_part, n, d_stats);
-            hipLaunchKernelGGL(zs_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_max, n, nx, 2, d_stats, d_norm, d_box);
-            he = hipGetLastError();
-        }
-        if (he == hipSuccess) he = hipMemcpy(out_norm, d_norm, 2 * obytes, hipMemcpyDeviceToHost);
-        if (he == hipSuccess && out_stats) he = hipMemcpy(out_stats, d_stats, 4 * sizeof(double), hipMemcpyDeviceToHost);
-        if (he == hipSuccess && out_box) he = hipMemcpy(out_box, d_box, 4 * sizeof(int), hipMemcpyDeviceToHost);
-    }
-    if (he == hipSuccess) he = hipMemcpy(out_max, d_max, obytes, hipMemcpyDeviceToHost);
-    if (he == hipSuccess) he = hipMemcpy(out_mean, d_mean, obytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (he != hipSuccess) return fail(TS2D_ERR_HIP, "ts2d_project_coronal failed: %s", hipGetErrorString(he));
-    return TS2D_OK;
-}
-
-int ts2d_project_coronal(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz,
-                         long long sy, long long sx, long long base, float* out_max, float* out_mean) {
-    return project_coronal_impl(device, volume, n_elems, dtype, nz, ny, nx, sz, sy, sx, base, out_max, out_mean, nullptr, nullptr, nullptr);
-}
-
-int ts2d_project_coronal_zscore(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz,
-                                long long sy, long long sx, long long base, float* out_max, float* out_mean, float* out_norm,
-                                double* out_stats, int32_t* out_box) {
-    if (!out_norm) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal_zscore: null argument");
-    return project_coronal_impl(device, volume, n_elems, dtype, nz, ny, nx, sz, sy, sx, base, out_max, out_mean, out_norm, out_stats, out_box);
-}
-// Taps of one axis of the order-3 resample (n_in -> n_out samples; preprocess.cubic_axis_taps is the same statement in numpy, pinned to
-// scipy): cc = ((o + 0.5) * (n_in / n_out) - 0.5) + 12 clamped to the padded extent, start = floor(cc) - 1, y = cc - floor(cc), t = 1 - y,
-// w1 = (y*y*(y-2)*3 + 4) / 6, w2 = (t*t*(t-2)*3 + 4) / 6, w0 = t*t*t / 6, w3 = 1 - w0 - w1 - w2, one rounding per step.  False if a tap
-// would leave the padded line (with this map it cannot: cc lies in [11.5, n_in + 11.5]; checked because the kernel reads where it points).
-static bool rsin_axis_taps(int n_in, int n_out, RsInTap* t) {
-#pragma clang fp contract(off)
-    const int n_pad = n_in + 2 * kRsInPad;
-    const double zoom = (double)n_in / (double)n_out;
-    for (int o = 0; o < n_out; ++o) {
-        const double prod = ((double)o + 0.5) * zoom;
-        const double shifted = prod - 0.5;
-        double cc = shifted + (double)kRsInPad;
-        cc = std::min(std::max(cc, 0.0), (double)(n_pad - 1));
-        const double f = std::floor(cc);
-        const long long start = (long long)f - 1;
-        if (start < 0 || start + 3 > n_pad - 1) return false;
-        const double y = cc - f, u = 1.0 - y;
-        const double yy = y * y, uu = u * u;
-        const double a1 = yy * (y - 2.0), a2 = uu * (u - 2.0);
-        const double b1 = a1 * 3.0, b2 = a2 * 3.0;
-        t[o].w[1] = (b1 + 4.0) / 6.0;
-        t[o].w[2] = (b2 + 4.0) / 6.0;
-        const double u3 = uu * u;
-        t[o].w[0] = u3 / 6.0;
-        const double r0 = 1.0 - t[o].w[0], r1 = r0 - t[o].w[1];
-        t[o].w[3] = r1 - t[o].w[2];
-        t[o].start = (int)start; t[o].pad_ = 0;
-    }
-    return true;
-}
-
-// The float64 nearest to sqrt(3) - 2: what scipy's binary holds for the pole of the cubic prefilter (its compiler folds the constant
-// in extended precision).  std::sqrt(3.0) - 2.0 is two units in the last place away and would cost the bit identity.
-static const double kRsInPole = -0x1.126145e9ecd56p-2;
-constexpr int kRsInMaxExtent = 8192;          // preprocess.CUBIC_MAX_EXTENT
-
-static RsInAxis rsin_axis_constants(int n_pad) {
-#pragma clang fp contract(off)
-    RsInAxis a;
-    a.z = kRsInPole;
-    const double inv = 1.0 / a.z;
-    a.gain = (1.0 - a.z) * (1.0 - inv);
-    a.zn = std::pow(a.z, (double)n_pad);
-    const double zn2 = a.zn * a.zn;
-    a.k0 = a.z / (1.0 - zn2);
-    a.k1 = a.z / (a.z - 1.0);
-    return a;
-}
-
-// The device part of the order-3 resample, shared by ts2d_resample_cubic (host planes in and out) and ts2d_planes_resample_cubic (planes that
-// live on the device): the host tables of one (in_h, in_w) -> (out_h, out_w) zoom and the layout of the scratch they go to,
-// [coefficients | powers | taps], then the three rsin_* launches over device pointers.
-struct RsInPlan {
-    int Hp = 0, Wp = 0;
-    std::vector<RsInTap> taps;          // rows at [0, out_h), columns at [out_h, out_h + out_w)
-    std::vector<double> zpow;           // running products of the pole, as scipy forms them (z_i *= z)
-    RsInAxis ax_h, ax_w;
-    size_t o_pow = 0, o_taps = 0, bytes = 0;
-};
-
-// false: a tap would leave the padded plane
-static bool rsin_plan(int n_planes, int in_h, int in_w, int out_h, int out_w, RsInPlan* pl) {
-    pl->Hp = in_h + 2 * kRsInPad; pl->Wp = in_w + 2 * kRsInPad;
-    pl->taps.resize((size_t)out_h + out_w);
-    if (!rsin_axis_taps(in_h, out_h, pl->taps.data()) || !rsin_axis_taps(in_w, out_w, pl->taps.data() + out_h)) return false;
-    pl->zpow.resize((size_t)std::max(pl->Hp, pl->Wp));
-    {
-#pragma clang fp contract(off)
-        pl->zpow[0] = 1.0; pl->zpow[1] = kRsInPole;
-        for (size_t i = 2; i < pl->zpow.size(); ++i) pl->zpow[i] = pl->zpow[i - 1] * kRsInPole;
-    }
-    pl->ax_h = rsin_axis_constants(pl->Hp); pl->ax_w = rsin_axis_constants(pl->Wp);
-    pl->o_pow = align_up((size_t)n_planes * pl->Hp * pl->Wp * sizeof(double), 256);
-    pl->o_taps = align_up(pl->o_pow + pl->zpow.size() * sizeof(double), 256);
-    pl->bytes = align_up(pl->o_taps + pl->taps.size() * sizeof(RsInTap), 256);
-    return true;
-}
-
-// d_scratch: pl.bytes; d_src [n_planes][in_h][in_w], d_lh [n_planes][2], d_dst [n_planes][out_h][out_w], all on the device
-static hipError_t rsin_run(const RsInPlan& pl, char* d_scratch, const float* d_src, const float* d_lh, float* d_dst, int n_planes, int in_h,
-                           int in_w, int out_h, int out_w) {
-    double* d_coef = reinterpret_cast<double*>(d_scratch);
-    const double* d_pow = reinterpret_cast<const double*>(d_scratch + pl.o_pow);
-    const RsInTap* d_taps = reinterpret_cast<const RsInTap*>(d_scratch + pl.o_taps);
-    hipError_t he = hipMemcpy(d_scratch + pl.o_pow, pl.zpow.data(), pl.zpow.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d_scratch + pl.o_taps, pl.taps.data(), pl.taps.size() * sizeof(RsInTap), hipMemcpyHostToDevice);
-    if (he != hipSuccess) return he;
-    hipLaunchKernelGGL(rsin_prefilter_cols, dim3((unsigned)(((long long)n_planes * pl.Wp + 63) / 64)), dim3(64), 0, 0,
-                       d_src, n_planes, in_h, in_w, pl.ax_h, d_pow, d_coef);
-    hipLaunchKernelGGL(rsin_prefilter_rows, dim3((unsigned)(((long long)n_planes * pl.Hp + 63) / 64)), dim3(64), 0, 0,
-                       d_coef, n_planes, pl.Hp, pl.Wp, pl.ax_w, d_pow);
-    const long long quads = (long long)n_planes * out_h * ((out_w + 3) / 4);
-    hipLaunchKernelGGL(rsin_interp_clip, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, 0,
-                       d_coef, n_planes, pl.Hp, pl.Wp, out_h, out_w, d_taps, d_lh, d_dst);
-    return hipGetLastError();
-}
-
-int ts2d_resample_cubic(int device, const float* src, int n_planes, int in_h, int in_w, int out_h, int out_w, const float* lo_hi, float* dst) {
-    if (!src || !lo_hi || !dst) return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: null argument");
-    if (n_planes < 1) return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: %d planes", n_planes);
-    if (in_h < 2 || in_w < 2 || out_h < 2 || out_w < 2 || in_h > kRsInMaxExtent || in_w > kRsInMaxExtent || out_h > kRsInMaxExtent || out_w > kRsInMaxExtent)
-        return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: extents %d x %d -> %d x %d outside 2 ... %d", in_h, in_w, out_h, out_w, kRsInMaxExtent);
-    const int Hp = in_h + 2 * kRsInPad, Wp = in_w + 2 * kRsInPad;
-    if ((long long)n_planes * Hp * Wp > (1ll << 28) || (long long)n_planes * out_h * out_w > (1ll << 28))
-        return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: %d planes of %d x %d -> %d x %d are more than one call takes (2^28 samples)", n_planes, in_h, in_w, out_h, out_w);
-    for (int p = 0; p < n_planes; ++p)
-        if (!std::isfinite(lo_hi[2 * p]) || !std::isfinite(lo_hi[2 * p + 1]) || lo_hi[2 * p] > lo_hi[2 * p + 1])
-            return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: plane %d has non-finite or inverted clip bounds [%g, %g] (a plane with a non-finite sample is not computed here)",
-                        p, (double)lo_hi[2 * p], (double)lo_hi[2 * p + 1]);
-    RsInPlan pl;
-    if (!rsin_plan(n_planes, in_h, in_w, out_h, out_w, &pl))
-        return fail(TS2D_ERR_INVALID, "ts2d_resample_cubic: zoom %d x %d -> %d x %d puts a tap outside the padded plane", in_h, in_w, out_h, out_w);
-    HIP_TRY(hipSetDevice(device));
-    const size_t n_src = (size_t)n_planes * in_h * in_w, n_dst = (size_t)n_planes * out_h * out_w;
-    // [scratch of the plan | source | clip bounds | result]
-    const size_t o_src = pl.bytes, o_lh = align_up(o_src + n_src * sizeof(float), 256);
-    const size_t o_dst = align_up(o_lh + (size_t)n_planes * 2 * sizeof(float), 256);
-    char* d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), o_dst + n_dst * sizeof(float)));
-    float* d_dst = reinterpret_cast<float*>(d + o_dst);
-    hipError_t he = hipMemcpy(d + o_src, src, n_src * sizeof(float), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d + o_lh, lo_hi, (size_t)n_planes * 2 * sizeof(float), hipMemcpyHostToDevice);
-    if (he == hipSuccess)
-        he = rsin_run(pl, d, reinterpret_cast<const float*>(d + o_src), reinterpret_cast<const float*>(d + o_lh), d_dst, n_planes, in_h, in_w, out_h, out_w);
-    if (he == hipSuccess) he = hipMemcpy(dst, d_dst, n_dst * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (he != hipSuccess) return fail(TS2D_ERR_HIP, "ts2d_resample_cubic failed: %s", hipGetErrorString(he));
-    return TS2D_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- ts2d_planes
-// Planes that stay on the device between the steps of nnU-Net's preprocessing of a native 2-D input (kernels_prep.h): uploaded once,
-// cropped, z-scored and resampled where they lie, downloaded once.
-struct ts2d_planes {
-    int device = 0;
-    int n = 0, h = 0, w = 0;
-    float* d = nullptr;         // [n][h][w]
-    float* d_lh = nullptr;      // [n][2]: float32 minimum and maximum of each plane, valid while has_bounds
-    bool has_bounds = false;
-};
-
-constexpr int kPrepMaxPlanes = 65535;           // (a grid dimension)
-constexpr long long kPrepMaxSamples = 1ll << 28;
-
-// leaves of numpy's pairwise sum over a run of n elements (the partial chunk of a plane), in the order the recursion visits them
-static void prep_leaves(int off, int n, std::vector<PrepLeaf>* out) {
-    if (n <= kPrepLeaf) { out->push_back(PrepLeaf{off, n}); return; }
-    int n2 = n / 2; n2 -= n2 % 8;
-    prep_leaves(off, n2, out);
-    prep_leaves(off + n2, n - n2, out);
-}
-
-// the same recursion over the leaves' sums: every inner node adds its two halves, rounded to float32
-static float prep_fold(const float*& leaf, int n) {
-#pragma clang fp contract(off)
-    if (n <= kPrepLeaf) return *leaf++;
-    int n2 = n / 2; n2 -= n2 % 8;
-    const float a = prep_fold(leaf, n2);
-    const float b = prep_fold(leaf, n - n2);
-    return a + b;
-}
-
-// numpy's add.reduce of one plane from what prep_chunk_sums wrote: +0, plus each chunk's pairwise sum in index order
-static float prep_plane_sum(const float* sums, long long n) {
-#pragma clang fp contract(off)
-    const long long n_full = n / kPrepChunk;
-    float acc = 0.f;
-    for (long long c = 0; c < n_full; ++c) acc = acc + sums[c];
-    if (n % kPrepChunk) { const float* leaf = sums + n_full; const float tail = prep_fold(leaf, (int)(n % kPrepChunk)); acc = acc + tail; }
-    return acc;
-}
-
-static float prep_unkey(int key) { const int b = key < 0 ? key ^ 0x7FFFFFFF : key; float f; std::memcpy(&f, &b, 4); return f; }
-
-int ts2d_planes_create(int device, const float* src, int n_planes, int h, int w, ts2d_planes** out) {
-    if (!src || !out) return fail(TS2D_ERR_INVALID, "ts2d_planes_create: null argument");
-    *out = nullptr;
-    if (n_planes < 1 || n_planes > kPrepMaxPlanes) return fail(TS2D_ERR_INVALID, "ts2d_planes_create: %d planes outside 1 ... %d", n_planes, kPrepMaxPlanes);
-    if (h < 1 || w < 1 || h > kRsInMaxExtent || w > kRsInMaxExtent)
-        return fail(TS2D_ERR_INVALID, "ts2d_planes_create: extents %d x %d outside 1 ... %d", h, w, kRsInMaxExtent);
-    if ((long long)n_planes * h * w > kPrepMaxSamples)
-        return fail(TS2D_ERR_INVALID, "ts2d_planes_create: %d planes of %d x %d are more than one handle takes (2^28 samples)", n_planes, h, w);
-    HIP_TRY(hipSetDevice(device));
-    const size_t bytes = (size_t)n_planes * h * w * sizeof(float);
-    float* d = nullptr; float* d_lh = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), bytes));
-    hipError_t he = hipMalloc(reinterpret_cast<void**>(&d_lh), (size_t)n_planes * 2 * sizeof(float));
-    if (he == hipSuccess) he = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        (void)hipFree(d); if (d_lh) (void)hipFree(d_lh);
-        return fail(he == hipErrorOutOfMemory ? TS2D_ERR_NOMEM : TS2D_ERR_HIP, "ts2d_planes_create failed: %s", hipGetErrorString(he));
-    }
-    ts2d_planes* p = new ts2d_planes();
-    p->device = device; p->n = n_planes; p->h = h; p->w = w; p->d = d; p->d_lh = d_lh;
-    *out = p;
-    return TS2D_OK;
-}
-
-int ts2d_planes_crop_zscore(ts2d_planes* p, int32_t box[4], float* stats, int* nonfinite) {
-    if (!p || !box || !stats || !nonfinite) return fail(TS2D_ERR_INVALID, "ts2d_planes_crop_zscore: null argument");
-    *nonfinite = 0;
-    HIP_TRY(hipSetDevice(p->device));
-    const int n = p->n;
-    // scratch, sized for the uncropped extent: [box | min / max keys | mean, divisor | leaves of the partial chunk | chunk and leaf sums]
-    const size_t per_plane = (size_t)((long long)p->h * p->w / kPrepChunk) + kPrepMaxTailLeaves;
-    const size_t o_keys = 256, o_norm = align_up(o_keys + (size_t)n * 2 * sizeof(int), 256), o_leaves = align_up(o_norm + (size_t)n * sizeof(PrepNorm), 256);
-    const size_t o_sums = align_up(o_leaves + kPrepMaxTailLeaves * sizeof(PrepLeaf), 256);
-    char* d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), o_sums + (size_t)n * per_plane * sizeof(float)));
-    int* d_box = reinterpret_cast<int*>(d); int* d_keys = reinterpret_cast<int*>(d + o_keys);
-    PrepNorm* d_norm = reinterpret_cast<PrepNorm*>(d + o_norm); PrepLeaf* d_leaves = reinterpret_cast<PrepLeaf*>(d + o_leaves);
-    float* d_sums = reinterpret_cast<float*>(d + o_sums);
-    float* d_new = nullptr;                                     // the compacted planes, until the handle owns them
-    auto done = [&](hipError_t he) {
-        (void)hipFree(d); if (d_new) (void)hipFree(d_new);
-        if (he != hipSuccess) return fail(he == hipErrorOutOfMemory ? TS2D_ERR_NOMEM : TS2D_ERR_HIP, "ts2d_planes_crop_zscore failed: %s", hipGetErrorString(he));
-        return (int)TS2D_OK;
-    };
-    // 1. crop_to_nonzero's box over all planes
-    int hb[4] = {p->h, -1, p->w, -1};
-    hipError_t he = hipMemcpy(d_box, hb, sizeof(hb), hipMemcpyHostToDevice);
-    if (he != hipSuccess) return done(he);
-    hipLaunchKernelGGL(prep_nonzero_box, dim3((unsigned)(((long long)p->h * p->w + 255) / 256)), dim3(256), 0, 0, p->d, n, p->h, p->w, d_box);
-    he = hipGetLastError();
-    if (he == hipSuccess) he = hipMemcpy(hb, d_box, sizeof(hb), hipMemcpyDeviceToHost);
-    if (he != hipSuccess) return done(he);
-    if (hb[1] < 0) { hb[0] = 0; hb[1] = p->h - 1; hb[2] = 0; hb[3] = p->w - 1; }            // nothing but zeros: the whole extent stays
-    if (hb[0] < 0 || hb[1] >= p->h || hb[0] > hb[1] || hb[2] < 0 || hb[3] >= p->w || hb[2] > hb[3]) {
-        (void)done(hipSuccess);
-        return fail(TS2D_ERR_HIP, "ts2d_planes_crop_zscore: the device returned the box rows %d ... %d, columns %d ... %d of %d x %d", hb[0], hb[1], hb[2], hb[3], p->h, p->w);
-    }
-    const int bh = hb[1] - hb[0] + 1, bw = hb[3] - hb[2] + 1;
-    // 2. compaction: the flattened index of the dense [n][bh][bw] buffer is numpy's
-    if (bh != p->h || bw != p->w) {
-        he = hipMalloc(reinterpret_cast<void**>(&d_new), (size_t)n * bh * bw * sizeof(float));
-        for (int c = 0; c < n && he == hipSuccess; ++c)
-            he = hipMemcpy2D(d_new + (size_t)c * bh * bw, (size_t)bw * sizeof(float), p->d + ((size_t)c * p->h + hb[0]) * p->w + hb[2],
-                             (size_t)p->w * sizeof(float), (size_t)bw * sizeof(float), (size_t)bh, hipMemcpyDeviceToDevice);
-        if (he != hipSuccess) return done(he);
-        (void)hipFree(p->d);
-        p->d = d_new; d_new = nullptr; p->h = bh; p->w = bw;
-    }
-    p->has_bounds = false;
-    box[0] = hb[0]; box[1] = hb[1] + 1; box[2] = hb[2]; box[3] = hb[3] + 1;
-    // 3. the two sums of every plane: chunk and leaf sums on the device, their fold and the float32 statistics here
-    const long long N = (long long)bh * bw, n_full = N / kPrepChunk;
-    std::vector<PrepLeaf> leaves;
-    if (N % kPrepChunk) prep_leaves(0, (int)(N % kPrepChunk), &leaves);
-    if ((int)leaves.size() > kPrepMaxTailLeaves) { (void)done(hipSuccess); return fail(TS2D_ERR_INVALID, "ts2d_planes_crop_zscore: %zu leaves in a partial chunk", leaves.size()); }
-    const size_t n_out = (size_t)n_full + leaves.size();
-    const dim3 grid_sums((unsigned)(n_full + (leaves.empty() ? 0 : 1)), (unsigned)n);
-    std::vector<float> sums((size_t)n * n_out);
-    std::vector<PrepNorm> norm((size_t)n, PrepNorm{0.f, 1.f});
-    if (!leaves.empty()) he = hipMemcpy(d_leaves, leaves.data(), leaves.size() * sizeof(PrepLeaf), hipMemcpyHostToDevice);
-    if (he != hipSuccess) return done(he);
-    bool bad = false;
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 0) hipLaunchKernelGGL(prep_chunk_sums<0>, grid_sums, dim3(512), 0, 0, p->d, N, d_norm, d_leaves, (int)leaves.size(), d_sums);
-        else hipLaunchKernelGGL(prep_chunk_sums<1>, grid_sums, dim3(512), 0, 0, p->d, N, d_norm, d_leaves, (int)leaves.size(), d_sums);
-        he = hipGetLastError();
-        if (he == hipSuccess) he = hipMemcpy(sums.data(), d_sums, sums.size() * sizeof(float), hipMemcpyDeviceToHost);
-        if (he != hipSuccess) return done(he);
-        for (int c = 0; c < n; ++c) {
-            // numpy divides the float32 sum by the count in float64 and rounds once to float32 (`ret / rcount` with an intp count)
-            const float q = (float)((double)prep_plane_sum(sums.data() + (size_t)c * n_out, N) / (double)N);
-            if (!std::isfinite(q)) bad = true;
-            if (pass == 0) { norm[c].mean = q; stats[2 * c] = q; }
-            else { const float sd = std::sqrt(q); stats[2 * c + 1] = sd; norm[c].div = 1e-8 > (double)sd ? (float)1e-8 : sd; }   // max(std, 1e-8)
-        }
-        if (bad) { *nonfinite = 1; return done(hipSuccess); }      // a non-finite sample (or an overflowing sum): nothing is normalised
-        he = hipMemcpy(d_norm, norm.data(), norm.size() * sizeof(PrepNorm), hipMemcpyHostToDevice);
-        if (he != hipSuccess) return done(he);
-    }
-    // 4. normalise in place; the minimum and maximum of the result are the clip bounds of the resample
-    std::vector<int> keys((size_t)n * 2);
-    for (int c = 0; c < n; ++c) { keys[2 * c] = 0x7FFFFFFF; keys[2 * c + 1] = (int)0x80000000; }
-    he = hipMemcpy(d_keys, keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (he != hipSuccess) return done(he);
-    hipLaunchKernelGGL(prep_normalise, dim3((unsigned)((N + 256 * kPrepNormPerLane - 1) / (256 * kPrepNormPerLane)), (unsigned)n), dim3(256), 0, 0, p->d, N, d_norm, d_keys);
-    he = hipGetLastError();
-    if (he == hipSuccess) he = hipMemcpy(keys.data(), d_keys, keys.size() * sizeof(int), hipMemcpyDeviceToHost);
-    if (he != hipSuccess) return done(he);
-    std::vector<float> lh((size_t)n * 2);
-    for (size_t i = 0; i < lh.size(); ++i) { lh[i] = prep_unkey(keys[i]); if (!std::isfinite(lh[i])) bad = true; }
-    if (bad) { *nonfinite = 1; return done(hipSuccess); }          // (a quotient overflowed: the planes hold it, the caller drops the handle)
-    he = hipMemcpy(p->d_lh, lh.data(), lh.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (he != hipSuccess) return done(he);
-    p->has_bounds = true;
-    return done(hipSuccess);
-}
-
-int ts2d_planes_resample_cubic(ts2d_planes* p, int out_h, int out_w) {
-    if (!p) return fail(TS2D_ERR_INVALID, "ts2d_planes_resample_cubic: null argument");
-    const int in_h = p->h, in_w = p->w, n = p->n;
-    if (in_h < 2 || in_w < 2 || out_h < 2 || out_w < 2 || in_h > kRsInMaxExtent || in_w > kRsInMaxExtent || out_h > kRsInMaxExtent || out_w > kRsInMaxExtent)
-        return fail(TS2D_ERR_INVALID, "ts2d_planes_resample_cubic: extents %d x %d -> %d x %d outside 2 ... %d", in_h, in_w, out_h, out_w, kRsInMaxExtent);
-    if ((long long)n * (in_h + 2 * kRsInPad) * (in_w + 2 * kRsInPad) > (1ll << 28) || (long long)n * out_h * out_w > (1ll << 28))
-        return fail(TS2D_ERR_INVALID, "ts2d_planes_resample_cubic: %d planes of %d x %d -> %d x %d are more than one call takes (2^28 samples)", n, in_h, in_w, out_h, out_w);
-    if (!p->has_bounds)
-        return fail(TS2D_ERR_STATE, "ts2d_planes_resample_cubic: the planes carry no clip bounds (ts2d_planes_crop_zscore computes them; a resample uses them up)");
-    RsInPlan pl;
-    if (!rsin_plan(n, in_h, in_w, out_h, out_w, &pl))
-        return fail(TS2D_ERR_INVALID, "ts2d_planes_resample_cubic: zoom %d x %d -> %d x %d puts a tap outside the padded plane", in_h, in_w, out_h, out_w);
-    HIP_TRY(hipSetDevice(p->device));
-    char* d_scratch = nullptr; float* d_dst = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_scratch), pl.bytes));
-    hipError_t he = hipMalloc(reinterpret_cast<void**>(&d_dst), (size_t)n * out_h * out_w * sizeof(float));
-    if (he == hipSuccess) he = rsin_run(pl, d_scratch, p->d, p->d_lh, d_dst, n, in_h, in_w, out_h, out_w);
-    if (he == hipSuccess) he = hipDeviceSynchronize();
-    (void)hipFree(d_scratch);
-    if (he != hipSuccess) {
-        if (d_dst) (void)hipFree(d_dst);
-        return fail(he == hipErrorOutOfMemory ? TS2D_ERR_NOMEM : TS2D_ERR_HIP, "ts2d_planes_resample_cubic failed: %s", hipGetErrorString(he));
-    }
-    (void)hipFree(p->d);
-    p->d = d_dst; p->h = out_h; p->w = out_w; p->has_bounds = false;
-    return TS2D_OK;
-}
-
-int ts2d_planes_extent(const ts2d_planes* p, int* h, int* w) {
-    if (!p || !h || !w) return fail(TS2D_ERR_INVALID, "ts2d_planes_extent: null argument");
-    *h = p->h; *w = p->w;
-    return TS2D_OK;
-}
-
-int ts2d_planes_download(const ts2d_planes* p, float* dst) {
-    if (!p || !dst) return fail(TS2D_ERR_INVALID, "ts2d_planes_download: null argument");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMemcpy(dst, p->d, (size_t)p->n * p->h * p->w * sizeof(float), hipMemcpyDeviceToHost));
-    return TS2D_OK;
-}
-
-int ts2d_planes_destroy(ts2d_planes* p) {
-    if (!p) return TS2D_OK;
-    (void)hipSetDevice(p->device);
-    if (p->d) (void)hipFree(p->d);
-    if (p->d_lh) (void)hipFree(p->d_lh);
-    delete p;
-    return TS2D_OK;
-}
-int ts2d_synth_slices(int device, unsigned long long key, unsigned long long first_element, unsigned long long n_elements,
-                      float* out_device, void* stream) {
-    if (!out_device) return fail(TS2D_ERR_INVALID, "ts2d_synth_slices: null output");
-    if (n_elements == 0) return TS2D_OK;
-    if (n_elements > (1ull << 40)) return fail(TS2D_ERR_INVALID, "ts2d_synth_slices: %llu elements in one call", n_elements);
-    HIP_TRY(hipSetDevice(device));
-    const unsigned long long per = 1ull << 30;                      // <= 2^30 elements per launch (grid of 2^22 blocks)
-    for (unsigned long long o = 0; o < n_elements; o += per) {
-        const unsigned long long m = std::min(per, n_elements - o);
-        hipLaunchKernelGGL(synth_normal, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                           out_device + o, key, first_element + o, m);
-        HIP_TRY(hipGetLastError());
-    }
-    return TS2D_OK;
 }
 
 int ts2d_engine_set_profiling(ts2d_engine* e, int enable) {

@@ -1,9 +1,12 @@
-// Host-side internals of libts2d_engine.so, shared by program.cpp, pack_weights.cpp, dispatch.cpp and engine.hip: the program (tensors, ops),
-// the kernel choice of an op, the workspace layout and the engine handle.  Not installed, not part of the ABI (include/ts2d_engine.h is).
-// No device code here or in the .cpp files: they build without an offload pass.  engine.hip is the one file that holds kernels.
+// Host-side internals of libts2d_engine.so, shared by the plain C++ files (program.cpp, pack_weights.cpp, dispatch.cpp, tiled_plan.cpp,
+// prep_plan.cpp) and the three device units: the program (tensors, ops), the kernel choice of an op, the workspace layout, the engine
+// handle, the plans of the sliding window and of the input side.  Not installed, not part of the ABI (include/ts2d_engine.h is).
+// No device code here or in the .cpp files: they build without an offload pass.  Kernels live in engine.hip (the network), tiled.hip
+// (the sliding window, fold mean and export) and prep.hip (projection, input resample, native 2-D planes), each kernel in exactly one.
 #pragma once
 #include "../../include/ts2d_engine.h"
 #include <hip/hip_runtime_api.h>
+#include "device_tables.h"
 
 #include <atomic>
 #include <cstddef>
@@ -17,6 +20,31 @@ namespace ts2d {
 // thread-local last error (ts2d_last_error): ONE definition for every object of the library (program.cpp)
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 const char* last_error();
+
+#define HIP_TRY(expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t _e = (expr);                                                                           \
+        if (_e != hipSuccess)                                                                             \
+            return fail(_e == hipErrorOutOfMemory ? TS2D_ERR_NOMEM : TS2D_ERR_HIP, "%s failed: %s (%s:%d)", \
+                        #expr, hipGetErrorString(_e), __FILE__, __LINE__);                                \
+    } while (0)
+#define TRY(expr) do { int _rc = (expr); if (_rc != TS2D_OK) return _rc; } while (0)
+
+// Owner of one hipMalloc on the input side (prep.hip): freed when it leaves its scope, so an early HIP_TRY return leaks nothing; a
+// handle (ts2d_planes) takes a buffer over by move.  The engine's long-lived buffers are not these: ts2d_engine_destroy frees them.
+class DevMem {
+public:
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept : p_(o.release()) {}
+    DevMem& operator=(DevMem&& o) noexcept { if (this != &o) { reset(); p_ = o.release(); } return *this; }
+    ~DevMem() { reset(); }
+    hipError_t alloc(size_t bytes) { reset(); return hipMalloc(&p_, bytes); }
+    template <class T> T* as(size_t byte_off = 0) const { return reinterpret_cast<T*>(static_cast<char*>(p_) + byte_off); }
+    void* release() { void* p = p_; p_ = nullptr; return p; }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; }
+private:
+    void* p_ = nullptr;
+};
 
 constexpr size_t kWsHeader = 256;         // bytes in front of the activation plan: [0] = token of the last run inside this memory
 
@@ -201,6 +229,40 @@ struct WsLayout {
     bool has_up = false;      // the scratch of one upsampled tensor exists at o_up (small batches: a decoder entry the reserved batch's plan composes)
 };
 WsLayout workspace_layout(const ts2d_engine* e, int B, int H, int W, bool full);
+
+// ---- engine.hip: what the sliding window (tiled.hip) needs of the engine
+int reserve_checked(ts2d_engine* e, int B, int H, int W, bool full);      // shape checks of a forward, then the workspace for it
+int run_forward(ts2d_engine* e, const float* d_in, int B, int H, int W, float* d_logits, uint32_t* d_mask, hipStream_t st, bool clear_flags, bool full);
+
+// ---- tiled_plan.cpp: everything of a sliding-window call that is decided before the device is touched
+struct SwChunk { int seg0, n_segs, rows, log_row; bool aggregate; unsigned gblocks, ablocks; };      // one gather + forward (+ aggregate)
+struct SwPlan {
+    int V = 1, vflips = 0;                  // mirror variants per tile and their flips, 8 bits each
+    int cap_rows = 0;                       // rows of the largest chunk: the batch every fold reserves
+    long long n_tiles_all = 0, out_elems = 0, rs_blocks = 0;
+    bool any16 = false, anyseg = false, any_rs8 = false, any_rs32 = false;
+    std::vector<SwSeg> segs; std::vector<SwChunk> chunks; std::vector<RsSeg> rsegs;
+    std::vector<char> tab;                  // [segments | tile_y | tile_x | export segments | export taps]: one host blob, one copy
+    size_t tab_segs = 0, tab_rsegs = 0, tab_rtaps = 0;
+    // scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs x F | uint8 outputs | flags x F | resampled uint8 | resampled float]
+    size_t o_tab = 0, o_g = 0, o_imgs = 0, o_batch = 0, o_log = 0, o_o16 = 0, o_seg = 0, o_flag = 0, o_rs8 = 0, o_rs32 = 0, bytes = 0;
+};
+int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
+               int mirror_mask, bool name_images, const char* entry, SwPlan* pl);
+
+// ---- prep_plan.cpp: the host arithmetic of the input side, bit for bit numpy's / scipy's
+// The host tables of one (in_h, in_w) -> (out_h, out_w) order-3 zoom and the layout of the scratch they go to: [coefficients | powers | taps]
+struct RsInPlan {
+    int Hp = 0, Wp = 0;
+    std::vector<RsInTap> taps;          // rows at [0, out_h), columns at [out_h, out_h + out_w)
+    std::vector<double> zpow;           // running products of the pole, as scipy forms them (z_i *= z)
+    RsInAxis ax_h, ax_w;
+    size_t o_pow = 0, o_taps = 0, bytes = 0;
+};
+int rsin_plan(const char* entry, int n_planes, int in_h, int in_w, int out_h, int out_w, RsInPlan* pl);      // fails if a tap would leave the padded plane
+void prep_leaves(int off, int n, std::vector<PrepLeaf>* out);
+float prep_plane_sum(const float* sums, long long n);
+float prep_unkey(int key);
 
 }  // namespace ts2d
 #pragma GCC visibility pop

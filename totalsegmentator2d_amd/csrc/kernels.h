@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "tile_dims.h"
+#include "device_tables.h"      // kSigmoidHalfThreshold
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -551,8 +552,6 @@ __global__ void nchw_to_nhwc_pad(const float* __restrict__ x, int C, int HW, lon
 // The predicate: on the ATen CPU kernels the oracle was pinned with, sigmoid(x) > 0.5  <=>  x > 1.5 * 2^-24
 // (exhaustive fp32 scan, tests/test_oracle.py); NaN compares false on both sides.
 // ------------------------------------------------------------------------------------------------------------
-constexpr float kSigmoidHalfThreshold = 0x1.8p-24f;
-
 struct HeadArgs {
     const float* src; const float* sc; const float* sh;   // raw NHWC [B,H,W,C] + its scale/shift [B,C]
     const float* w; const float* bias;                     // [K][C], [K]

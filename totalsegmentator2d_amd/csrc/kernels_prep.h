@@ -1,6 +1,6 @@
 // Device side of nnU-Net's preprocessing of an input that is 2-D when it arrives (reference flow DefaultPreprocessor.run_case,
 // ts2d/core/inference/prediction_worker.py:194-199): crop_to_nonzero's box, the per-channel ZScoreNormalization without mask, and the clip
-// bounds of the resample that follows.  Four kernels behind the ts2d_planes handle (engine.hip):
+// bounds of the resample that follows.  Four kernels behind the ts2d_planes handle (prep.hip):
 //     prep_nonzero_box      the bounding box of the pixels that are non-zero in ANY plane (integer atomics, one pass over all planes)
 //     prep_chunk_sums<P>    numpy's float32 sum of a plane, chunk by chunk (P = 0: of x; P = 1: of fl32(fl32(x - mean)^2))
 //     prep_normalise        x <- fl32(fl32(x - mean) / div) in place, and the plane's float32 minimum and maximum
@@ -22,7 +22,7 @@
 // lane in the same tree order.  One workgroup per full chunk writes one float.  The LAST, partial chunk of a plane has a tree of its
 // own: the host walks the recursion once per extent and uploads its leaves (offset, length); the workgroup behind the full chunks
 // writes one float per leaf and the host folds them along the recursion.  The host then adds the chunk sums in index order and
-// computes mean, variance, square root and divisor in float32 (engine.hip: prep_*), so no reduction order is left to the device.
+// computes mean, variance, square root and divisor in float32 (prep_plan.cpp: prep_*), so no reduction order is left to the device.
 // No float atomics anywhere; the result does not depend on the launch shape.
 //
 // Every float32 sum, difference and product is a plain operator under `#pragma clang fp contract(off)` (prep_add, prep_term): hipcc contracts
@@ -36,18 +36,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "device_tables.h"      // kPrepChunk, kPrepLeaf, kPrepMaxTailLeaves, PrepLeaf, PrepNorm
 
 namespace ts2d {
-
-constexpr int kPrepChunk = 8192;        // numpy's buffer size in elements: the run its add.reduce hands to the pairwise sum
-constexpr int kPrepLeaf = 128;          // numpy's PW_BLOCKSIZE: the longest run summed in eight accumulators
-constexpr int kPrepMaxTailLeaves = 160; // a partial chunk (< 8192 elements) has fewer leaves than this (each is longer than 56)
-
-struct PrepLeaf { int off, len; };      // a leaf of the partial chunk's tree, `off` counted from the chunk's first element
-static_assert(sizeof(PrepLeaf) == 8, "PrepLeaf is copied to the device as bytes");
-
-struct PrepNorm { float mean, div; };   // per plane: what prep_chunk_sums<1> subtracts and prep_normalise subtracts and divides by
-static_assert(sizeof(PrepNorm) == 8, "PrepNorm is copied to the device as bytes");
 
 __device__ __forceinline__ float prep_add(float a, float b) {
 #pragma clang fp contract(off)

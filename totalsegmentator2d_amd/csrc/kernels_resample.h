@@ -7,7 +7,7 @@
 // what skimage's resize(order=1, mode='edge') calls and the host route of the export computes (tests/test_resample_cpu.py): per output pixel
 //     value = ((((a00*wy0)*wx0 + (a01*wy0)*wx1) + (a10*wy1)*wx0) + (a11*wy1)*wx1      every product and sum rounded to float64, no FMA
 // then ONE rounding to float32 and the export predicate float32(value) > 1.5 * 2^-24.  The per-axis taps (two source indices, two
-// weights per output row / column) are computed in float64 on the host (engine.hip: rs_axis_taps) and uploaded, so the kernel holds
+// weights per output row / column) are computed in float64 on the host (tiled_plan.cpp: rs_axis_taps) and uploaded, so the kernel holds
 // no division and no floor whose device rounding would have to be argued about: it widens four halves, multiplies and adds.
 // Every product and sum is written under `#pragma clang fp contract(off)` (rs_mul / rs_add): hipcc contracts by default, and HIP's
 // __dmul_rn / __dadd_rn are plain operators that it fuses into v_fmac_f64 just the same; tests/test_resample_cpu.py asserts that the
@@ -21,24 +21,10 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include "device_tables.h"      // RsSeg, RsTap
+#include "rs_arith.h"           // rs_mul, rs_add
 
 namespace ts2d {
-
-struct RsSeg {
-    long long src_off;      // elements from the half outputs to this image's aggregated [K, Hp, Wp] (SwSeg::out_off)
-    long long dst_off;      // elements from the resampled outputs to this image's [K, out_h, out_w] (a multiple of 4)
-    int Hp, Wp;
-    int out_h, out_w;
-    int tap0;               // its taps: rows at taps[tap0 ... tap0 + out_h), columns at taps[tap0 + out_h ... tap0 + out_h + out_w)
-    unsigned block0;        // first block of the image in the launch
-};
-static_assert(sizeof(RsSeg) == 40, "RsSeg is copied to the device as bytes");
-
-struct RsTap {
-    double w0, w1;          // weights of the two source samples
-    int i0, i1;             // their row / column in the padded [Hp, Wp] plane (source rectangle origin included)
-};
-static_assert(sizeof(RsTap) == 24, "RsTap is copied to the device as bytes");
 
 __device__ __forceinline__ int rs_find_seg(const RsSeg* __restrict__ segs, int n, unsigned blk) {
     int lo = 0, hi = n - 1;
@@ -50,15 +36,6 @@ __device__ __forceinline__ int rs_find_seg(const RsSeg* __restrict__ segs, int n
 }
 
 __device__ __forceinline__ double rs_widen(const __half* p) { return (double)__half2float(*p); }
-// a float64 product / sum that is rounded on its own: never half of a fused multiply-add
-__device__ __forceinline__ double rs_mul(double a, double b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ double rs_add(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
 
 // one lane per 4 consecutive X of one (k, Y) row of one image's output extent; seg / out32: either may be null
 __global__ __launch_bounds__(256) void sw_resample_threshold(const __half* __restrict__ src16, const RsSeg* __restrict__ segs, int n_segs,

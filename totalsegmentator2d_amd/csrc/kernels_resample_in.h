@@ -1,7 +1,7 @@
 // Device side of the INPUT resample: a case whose spacing is not the plan's has every (channel, slice) plane resampled
 // to the plan spacing with skimage's resize(order=3, mode='edge', anti_aliasing=False, clip=True), which is scipy's
 // zoom(order=3, mode='nearest', grid_mode=True) followed by a clip to the plane's value range.  Three kernels, each ONE launch for all
-// planes of a call (ts2d_resample_cubic, engine.hip):
+// planes of a call (ts2d_resample_cubic, prep.hip):
 //     rsin_prefilter_cols   pad by 12 edge samples, widen to float64, gain, cubic B-spline prefilter along axis 0
 //     rsin_prefilter_rows   the same filter along axis 1, in place
 //     rsin_interp_clip      16 taps per output pixel, one rounding to float32, clip to the plane's [lo, hi]
@@ -18,8 +18,8 @@
 // sequential along a line by nature and is left so: a scan or a truncated sum would change the bits.  Everything that does not depend on
 // the line - z, gain, z^n, the running products zpow[i] = z * z * ... (NOT pow(z, i)), k0, k1 - is computed once on the host in float64
 // and passed in (RsInAxis), so no pow and no division runs on the device; the interpolation taps (start index, four weights per output
-// row / column) come from the host as well (engine.hip: rsin_axis_taps), so the kernels hold no floor either.  Every float64 product and
-// sum is written with rs_mul / rs_add (kernels_resample.h: `#pragma clang fp contract(off)`); tests/test_resample_cubic_cpu.py asserts that
+// row / column) come from the host as well (prep_plan.cpp: rsin_axis_taps), so the kernels hold no floor either.  Every float64 product and
+// sum is written with rs_mul / rs_add (rs_arith.h: `#pragma clang fp contract(off)`); tests/test_resample_cubic_cpu.py asserts that
 // the emitted stream holds v_mul_f64 / v_add_f64 and no fused form, no scratch and no spills.  float64 denormals are kept (the powers
 // zpow[i] pass through them on their way to 0 on lines longer than about 560 samples), as on the host.
 //
@@ -31,24 +31,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "kernels_resample.h"
+#include "device_tables.h"      // kRsInPad, RsInAxis, RsInTap
+#include "rs_arith.h"           // rs_mul, rs_add
 
 namespace ts2d {
 
-constexpr int kRsInPad = 12;        // scipy's _prepad_for_spline_filter for mode='nearest'
 constexpr int kRsInBatch = 16;      // samples of a line whose loads are in flight together
-
-struct RsInAxis {           // line-independent constants of the prefilter along one axis (n = padded extent of that axis)
-    double z, gain, zn;     // pole, gain, z^n (libm pow on the host, as scipy calls it)
-    double k0, k1;          // z / (1 - z^n * z^n),  z / (z - 1)
-};
-static_assert(sizeof(RsInAxis) == 40, "RsInAxis is passed by value");
-
-struct RsInTap {
-    double w[4];            // weights of four consecutive coefficients
-    int start, pad_;        // index of the first one in the padded line
-};
-static_assert(sizeof(RsInTap) == 40, "RsInTap is copied to the device as bytes");
 
 // The line filter of one lane.  `L` gives the line: L.g(i) = sample i times the gain, L.c(i) = reference to coefficient i.  Whole batches
 // first (their loads carry constant offsets and are issued together), then the remainder sample by sample.

@@ -18,23 +18,9 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include "device_tables.h"      // SwSeg
 
 namespace ts2d {
-
-struct SwSeg {
-    long long img_off;      // floats from the image area to this image's [C, Hp, Wp] (a multiple of 4)
-    long long out_off;      // elements from the output areas to this image's [K, Hp, Wp] (a multiple of 8)
-    int Hp, Wp;
-    int tile0, n_tiles;     // its tile origins are tile_y / tile_x[tile0 ... tile0 + n_tiles)
-    int row0, n_rows;       // rows (tile * V + variant) of the image gathered in this chunk: [row0, row0 + n_rows)
-    int batch_row;          // ... they are rows [batch_row, batch_row + n_rows) of the chunk's batch
-    int log_row;            // row of the logit buffer that holds the image's row 0 (aggregate)
-    int image;              // index of the image in the call (its inf flag)
-    int pad_;
-    unsigned gblock0;       // first block of the segment in the gather launch
-    unsigned ablock0;       // ... in the aggregate launch
-};
-static_assert(sizeof(SwSeg) == 64, "SwSeg is copied to the device as bytes");
 
 // the segment that owns block `blk`: the last one whose first block is <= blk (n <= 64: at most 6 steps, all in scalar registers)
 template <bool AGG>

@@ -1,0 +1,187 @@
+// The sliding window of libts2d_engine.so: tile gather, aggregation, the mean of an ensemble's folds and the export's resample-back, around
+// the engine's forward (engine.hip: reserve_checked, run_forward).  The C entries ts2d_engine_predict_tiled* and ts2d_ensemble_predict_tiled_export.
+#include "engine_internal.h"
+#include "kernels_sw.h"
+#include "kernels_fold.h"
+#include "kernels_resample.h"
+
+#include <string>
+#include <vector>
+
+using namespace ts2d;
+
+#pragma GCC visibility push(hidden)
+namespace {
+
+int name_fold(int rc, bool name_folds, int f) {
+    if (rc == TS2D_OK || !name_folds) return rc;
+    const std::string msg = last_error();
+    return fail(rc, "fold %d: %s", f, msg.c_str());
+}
+
+// The sliding window of every C entry (include/ts2d_engine.h): N images as ONE engine batch; ts2d_engine_predict_tiled is N = 1.
+// plan_tiled (tiled_plan.cpp) validates everything, packs the rows (tile x mirror variant) of the images into chunks of at most
+// kSwChunkRows and lays the scratch out; here every host-to-device copy is enqueued, then per chunk one sw_gather, one forward and
+// (where an image ends in the chunk) one sw_aggregate, then every device-to-host copy, ONE stream synchronise and the result check.
+// `full` is the whole difference between the entries' results: the batch entry asks for the full-batch dispatch (a row's bits must not
+// depend on its batch-mates), the single-image entry for the size-dependent one.  `name_images`: a message names the image it is about.
+// `exports` (ts2d_engine_predict_tiled_export; else null): one descriptor per image - behind the last aggregate ONE sw_resample_threshold
+// launch resamples every image's half logits to its export extent where they lie in the scratch.
+// `engines[0 .. F)` (ts2d_ensemble_predict_tiled_export; the other entries are F = 1): the folds of an ensemble, one after the other on
+// the FIRST engine's stream and in its scratch - the chunk loop once per fold, sw_aggregate into the fold's own half slot and inf
+// flags, then ONE sw_fold_mean (kernels_fold.h) into slot 0, on which the tail below runs as it does on a single fold's logits.  Only
+// the half slots and the flags exist F times.  `name_folds`: a fold's failed reserve or result check is reported as "fold <f>: ...".
+int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images,
+                       int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, bool full, bool name_images, bool name_folds,
+                       const char* entry) {
+    ts2d_engine* e = engines[0];
+    SwPlan pl;
+    TRY(plan_tiled(e, F, images, exports, n_images, ph, pw, mirror_mask, name_images, entry, &pl));
+    const int C = e->arch.input_channels, K = e->arch.num_classes, V = pl.V;
+    for (int f = 0; f < F; ++f) TRY(name_fold(reserve_checked(engines[f], pl.cap_rows, ph, pw, full), name_folds, f));
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    if (pl.bytes > e->sw_bytes) {                             // grown before the first launch only
+        HIP_TRY(hipStreamSynchronize(st));
+        if (e->d_sw) { HIP_TRY(hipFree(e->d_sw)); e->d_sw = nullptr; e->sw_bytes = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&e->d_sw), pl.bytes));
+        e->sw_bytes = pl.bytes;
+    }
+    char* b = e->d_sw;
+    const SwSeg* d_segs = reinterpret_cast<const SwSeg*>(b + pl.o_tab);
+    const int* d_ty = reinterpret_cast<const int*>(b + pl.o_tab + pl.tab_segs); const int* d_tx = d_ty + pl.n_tiles_all;
+    __half* d_g = reinterpret_cast<__half*>(b + pl.o_g); float* d_imgs = reinterpret_cast<float*>(b + pl.o_imgs);
+    float* d_batch = reinterpret_cast<float*>(b + pl.o_batch); float* d_log = reinterpret_cast<float*>(b + pl.o_log);
+    __half* d_o16 = pl.any16 ? reinterpret_cast<__half*>(b + pl.o_o16) : nullptr; uint8_t* d_seg = pl.anyseg ? reinterpret_cast<uint8_t*>(b + pl.o_seg) : nullptr;
+    int* d_flag = reinterpret_cast<int*>(b + pl.o_flag);
+    for (int i = 0; i < n_images; ++i) images[i].inf_flag = 0;
+    HIP_TRY(hipMemcpyAsync(b + pl.o_tab, pl.tab.data(), pl.tab.size(), hipMemcpyHostToDevice, st));
+    if (gaussian_f16) HIP_TRY(hipMemcpyAsync(d_g, gaussian_f16, (size_t)ph * pw * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)F * n_images * 4, st));
+    {
+        long long io = 0;
+        for (int i = 0; i < n_images; ++i) {
+            const size_t nf = (size_t)C * images[i].Hp * images[i].Wp;
+            HIP_TRY(hipMemcpyAsync(d_imgs + io, images[i].image, nf * 4, hipMemcpyHostToDevice, st));
+            io += (long long)align_up(nf, 64);
+        }
+    }
+    for (int f = 0; f < F; ++f)
+        for (size_t ci = 0; ci < pl.chunks.size(); ++ci) {
+            const SwChunk& c = pl.chunks[ci];
+            hipLaunchKernelGGL(sw_gather, dim3(c.gblocks), dim3(256), 0, st, d_imgs, d_segs + c.seg0, c.n_segs, C, ph, pw, V, pl.vflips, d_ty, d_tx, d_batch);
+            HIP_TRY(hipGetLastError());
+            TRY(run_forward(engines[f], d_batch, c.rows, ph, pw, d_log + (size_t)c.log_row * K * ph * pw, nullptr, st, ci == 0, full));
+            if (!c.aggregate) continue;
+            // (an ensemble's uint8 output is the predicate on the MEAN: sw_fold_mean writes it)
+            hipLaunchKernelGGL(sw_aggregate, dim3(c.ablocks), dim3(256), 0, st, d_log, d_segs + c.seg0, c.n_segs, K, ph, pw, V, pl.vflips, d_ty, d_tx,
+                               gaussian_f16 ? d_g : nullptr, d_o16 ? d_o16 + (size_t)f * pl.out_elems : nullptr, F > 1 ? nullptr : d_seg,
+                               kSigmoidHalfThreshold, d_flag + (size_t)f * n_images, e->tile_half);
+            HIP_TRY(hipGetLastError());
+        }
+    if (F > 1) {          // every slot up to the end of the last image (the alignment gaps between the images ride along unread)
+        const long long n_mean = pl.segs.back().out_off + (long long)K * pl.segs.back().Hp * pl.segs.back().Wp;
+        hipLaunchKernelGGL(sw_fold_mean, dim3((unsigned)(((n_mean >> 3) + (n_mean & 7) + 255) / 256)), dim3(256), 0, st, d_o16, pl.out_elems, F, n_mean,
+                           d_seg, kSigmoidHalfThreshold);
+        HIP_TRY(hipGetLastError());
+    }
+    uint8_t* d_rs8 = pl.any_rs8 ? reinterpret_cast<uint8_t*>(b + pl.o_rs8) : nullptr; float* d_rs32 = pl.any_rs32 ? reinterpret_cast<float*>(b + pl.o_rs32) : nullptr;
+    if (exports) {
+        hipLaunchKernelGGL(sw_resample_threshold, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
+                           n_images, K, reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps), d_rs8, d_rs32, kSigmoidHalfThreshold);
+        HIP_TRY(hipGetLastError());
+        for (int i = 0; i < n_images; ++i) {
+            const size_t ne = (size_t)K * exports[i].out_h * exports[i].out_w;
+            if (exports[i].seg_u8) HIP_TRY(hipMemcpyAsync(exports[i].seg_u8, d_rs8 + pl.rsegs[i].dst_off, ne, hipMemcpyDeviceToHost, st));
+            if (exports[i].logits_f32) HIP_TRY(hipMemcpyAsync(exports[i].logits_f32, d_rs32 + pl.rsegs[i].dst_off, ne * 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+    std::vector<int> flags((size_t)F * n_images, 0);
+    HIP_TRY(hipMemcpyAsync(flags.data(), d_flag, (size_t)F * n_images * 4, hipMemcpyDeviceToHost, st));
+    {
+        long long oo = 0;
+        for (int i = 0; i < n_images; ++i) {
+            const size_t ne = (size_t)K * images[i].Hp * images[i].Wp;
+            if (images[i].logits_f16) HIP_TRY(hipMemcpyAsync(images[i].logits_f16, d_o16 + oo, ne * 2, hipMemcpyDeviceToHost, st));
+            if (images[i].seg_u8) HIP_TRY(hipMemcpyAsync(images[i].seg_u8, d_seg + oo, ne, hipMemcpyDeviceToHost, st));
+            oo += (long long)align_up(ne, 256);
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int f = 0; f < F; ++f) {         // upstream looks for inf in every fold's aggregated array, not in the mean
+        engines[f]->tiled_inf = 0;
+        for (int i = 0; i < n_images; ++i) {
+            const int inf = flags[(size_t)f * n_images + i] != 0;
+            images[i].inf_flag = f ? (images[i].inf_flag | inf) : inf;
+            engines[f]->tiled_inf |= inf;
+        }
+    }
+    for (int f = 0; f < F; ++f) TRY(name_fold(ts2d_engine_check(engines[f]), name_folds, f));
+    return TS2D_OK;
+}
+
+}  // namespace
+#pragma GCC visibility pop
+
+extern "C" {
+
+int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp, int ph, int pw, int n_tiles,
+                              const int32_t* tile_y, const int32_t* tile_x, int mirror_mask, const uint16_t* gaussian_f16,
+                              uint16_t* logits_f16, uint8_t* seg_u8) {
+    if (!e || !image || !tile_y || !tile_x) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: null argument");
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
+    if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
+    ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
+    return predict_tiled_impl(&e, 1, &one, nullptr, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
+}
+
+int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
+                                    const uint16_t* gaussian_f16) {
+    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: null engine");
+    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
+    if (n_images == 0) return TS2D_OK;
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
+    return predict_tiled_impl(&e, 1, images, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
+}
+
+int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
+                                     int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
+    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: null engine");
+    if (n_images < 0 || (n_images > 0 && !(images && exports)))
+        return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: %d images at a null pointer", n_images);
+    if (n_images == 0) return TS2D_OK;
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_export: weights not loaded");
+    return predict_tiled_impl(&e, 1, images, exports, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
+                              "ts2d_engine_predict_tiled_export");
+}
+
+int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_export* exports,
+                                       int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
+    static const char* entry = "ts2d_ensemble_predict_tiled_export";
+    if (!engines) return fail(TS2D_ERR_INVALID, "%s: %d engines at a null pointer", entry, n_engines);
+    if (n_engines < 1 || n_engines > kMaxFolds) return fail(TS2D_ERR_INVALID, "%s: n_engines = %d is outside 1..%d", entry, n_engines, kMaxFolds);
+    for (int f = 0; f < n_engines; ++f)
+        if (!engines[f]) return fail(TS2D_ERR_INVALID, "%s: engine %d is null", entry, f);
+    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
+    if (n_images == 0) return TS2D_OK;
+    const ts2d_engine* e0 = engines[0];
+    for (int f = 0; f < n_engines; ++f) {
+        const ts2d_engine* e = engines[f];
+        if (!e->weights_ready) return fail(TS2D_ERR_STATE, "%s: fold %d: weights not loaded", entry, f);
+        if (e->device != e0->device) return fail(TS2D_ERR_INVALID, "%s: fold %d is on device %d, fold 0 on device %d", entry, f, e->device, e0->device);
+        if (e->arch.input_channels != e0->arch.input_channels)
+            return fail(TS2D_ERR_INVALID, "%s: fold %d has %d input channels, fold 0 has %d", entry, f, e->arch.input_channels, e0->arch.input_channels);
+        if (e->arch.num_classes != e0->arch.num_classes)
+            return fail(TS2D_ERR_INVALID, "%s: fold %d has num_classes %d, fold 0 has %d", entry, f, e->arch.num_classes, e0->arch.num_classes);
+        if (e->precision != e0->precision)
+            return fail(TS2D_ERR_INVALID, "%s: fold %d runs precision mode %d, fold 0 mode %d", entry, f, e->precision, e0->precision);
+        if (e->tile_half != e0->tile_half)
+            return fail(TS2D_ERR_INVALID, "%s: fold %d blends with tile dtype %d, fold 0 with %d", entry, f, e->tile_half, e0->tile_half);
+    }
+    return predict_tiled_impl(engines, n_engines, images, exports, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
+                              true, true, entry);
+}
+
+int ts2d_engine_tiled_inf_flag(const ts2d_engine* e) { return e ? (e->tiled_inf != 0) : 0; }
+
+}  // extern "C"

@@ -1,0 +1,182 @@
+// The device-free front of the sliding window (tiled.hip: predict_tiled_impl): argument checks, the rows (tile x mirror variant) of the
+// images packed into chunks of at most kSwChunkRows, the export's segments and taps, the table blob and the scratch layout.  Plain C++:
+// the taps must match numpy bit for bit, so this arithmetic is not compiled as HIP code.
+#include "engine_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+namespace ts2d {
+namespace {
+
+long long blocks_of(long long lanes) { return (lanes + 255) / 256; }
+
+// Taps of one axis of the order-1 resample (n_in -> n_out samples; preprocess.linear_axis_taps is the same statement in numpy, pinned
+// to scipy): cc = (o + 0.5) * (n_in / n_out) - 0.5, i0 = floor(cc), w1 = cc - i0, all in float64; the coordinate is not clamped, the
+// two INDICES are (scipy extends the array by its edge samples).  `origin` shifts the indices to the padded plane.
+// No contraction: a fused (o + 0.5) * zoom - 0.5 would round differently from numpy on a host build that has FMA (-march=native).
+void rs_axis_taps(int n_in, int n_out, int origin, RsTap* t) {
+#pragma clang fp contract(off)
+    const double zoom = (double)n_in / (double)n_out;
+    for (int o = 0; o < n_out; ++o) {
+        const double prod = ((double)o + 0.5) * zoom;
+        const double cc = prod - 0.5;
+        const double f = std::floor(cc);
+        const long long i0 = (long long)f;
+        t[o].w1 = cc - f; t[o].w0 = 1.0 - t[o].w1;
+        t[o].i0 = origin + (int)std::min<long long>(std::max<long long>(i0, 0), n_in - 1);
+        t[o].i1 = origin + (int)std::min<long long>(std::max<long long>(i0 + 1, 0), n_in - 1);
+    }
+}
+
+// every image (and its export descriptor) on its own; the totals that bound the tables
+int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
+                 bool name_images, const char* entry, SwPlan* pl) {
+    long long n_taps_all = 0;
+    pl->any16 = F > 1;      // (the mean is taken over the half buffers)
+    for (int i = 0; i < n_images; ++i) {
+        const ts2d_tiled_image& im = images[i];
+        char pre[24] = "";
+        if (name_images) snprintf(pre, sizeof(pre), "image %d: ", i);
+        if (!im.image || !im.tile_y || !im.tile_x) return fail(TS2D_ERR_INVALID, "%snull image or tile pointer", pre);
+        if (!exports && !im.logits_f16 && !im.seg_u8) return fail(TS2D_ERR_INVALID, "%sboth outputs are null", pre);
+        if (im.n_tiles < 1 || im.n_tiles > (1 << 20) || im.Hp < 1 || im.Wp < 1 || ph > im.Hp || pw > im.Wp)
+            return fail(TS2D_ERR_INVALID, "%sbad tiling: %d tiles of %dx%d on %dx%d", pre, im.n_tiles, ph, pw, im.Hp, im.Wp);
+        if ((long long)K * im.Hp * im.Wp >= (1LL << 31) || (long long)C * im.Hp * im.Wp >= (1LL << 31))
+            return fail(TS2D_ERR_INVALID, "%s%dx%d exceeds 2^31 elements per image", pre, im.Hp, im.Wp);
+        for (int t = 0; t < im.n_tiles; ++t)
+            if (im.tile_y[t] < 0 || im.tile_x[t] < 0 || im.tile_y[t] + ph > im.Hp || im.tile_x[t] + pw > im.Wp)
+                return fail(TS2D_ERR_INVALID, "%stile %d at (%d,%d) leaves the %dx%d image", pre, t, im.tile_y[t], im.tile_x[t], im.Hp, im.Wp);
+        pl->n_tiles_all += im.n_tiles;
+        pl->any16 |= im.logits_f16 != nullptr; pl->anyseg |= im.seg_u8 != nullptr;
+        if (!exports) continue;
+        const ts2d_tiled_export& ex = exports[i];
+        if (!ex.seg_u8 && !ex.logits_f32) return fail(TS2D_ERR_INVALID, "%sexport: both outputs are null", pre);
+        if (ex.src_h < 1 || ex.src_w < 1 || ex.src_y < 0 || ex.src_x < 0 || ex.src_h > im.Hp - ex.src_y || ex.src_w > im.Wp - ex.src_x)
+            return fail(TS2D_ERR_INVALID, "%sexport: source rectangle %dx%d at (%d,%d) is empty or leaves the %dx%d image", pre, ex.src_h, ex.src_w,
+                        ex.src_y, ex.src_x, im.Hp, im.Wp);
+        if (ex.out_h < 1 || ex.out_w < 1) return fail(TS2D_ERR_INVALID, "%sexport: bad output extent %dx%d", pre, ex.out_h, ex.out_w);
+        if ((long long)K * ex.out_h * ex.out_w >= (1LL << 31))
+            return fail(TS2D_ERR_INVALID, "%sexport: %dx%d exceeds 2^31 output elements", pre, ex.out_h, ex.out_w);
+        n_taps_all += (long long)ex.out_h + ex.out_w;         // (each < 2^31 by the check above; bounded before any table is allocated)
+        if (n_taps_all >= (1LL << 26)) return fail(TS2D_ERR_INVALID, "%sexport: more than 2^26 output rows + columns in one call", pre);
+        pl->any16 = true; pl->any_rs8 |= ex.seg_u8 != nullptr; pl->any_rs32 |= ex.logits_f32 != nullptr;
+    }
+    if (pl->n_tiles_all * pl->V >= (1LL << 28)) return fail(TS2D_ERR_INVALID, "%s: %lld network rows in one call", entry, pl->n_tiles_all * pl->V);
+    return TS2D_OK;
+}
+
+// Row packing: whole images, greedily, into chunks of at most kSwChunkRows rows; a larger image takes chunks of its own.
+// img_floats / log_rows: floats of the image area, rows of the tile-logit buffer.
+int pack_rows(int F, int C, int K, const ts2d_tiled_image* images, int n_images, int ph, int pw, const char* entry, SwPlan* pl,
+              long long* img_floats, long long* log_rows) {
+    const int pwq = (pw + 3) / 4;
+    int tile0 = 0;
+    SwChunk cur{0, 0, 0, 0, true, 0, 0};
+    auto flush = [&]() { if (cur.n_segs) pl->chunks.push_back(cur); cur = SwChunk{(int)pl->segs.size(), 0, 0, 0, true, 0, 0}; };
+    for (int i = 0; i < n_images; ++i) {
+        const ts2d_tiled_image& im = images[i];
+        const int rows = im.n_tiles * pl->V;
+        SwSeg sg{};
+        sg.img_off = *img_floats; sg.out_off = pl->out_elems; sg.Hp = im.Hp; sg.Wp = im.Wp; sg.tile0 = tile0; sg.n_tiles = im.n_tiles; sg.image = i;
+        const long long ablocks = blocks_of((long long)K * im.Hp * ((im.Wp + 3) / 4));
+        if (rows > kSwChunkRows) {
+            flush();
+            for (int r0 = 0; r0 < rows; r0 += kSwChunkRows) {
+                const int nb = std::min(kSwChunkRows, rows - r0);
+                sg.row0 = r0; sg.n_rows = nb; sg.batch_row = 0; sg.log_row = 0; sg.gblock0 = 0; sg.ablock0 = 0;
+                pl->segs.push_back(sg);
+                cur.n_segs = 1; cur.rows = nb; cur.log_row = r0; cur.aggregate = r0 + nb == rows;
+                cur.gblocks = (unsigned)blocks_of((long long)nb * C * ph * pwq); cur.ablocks = (unsigned)ablocks;
+                flush();
+            }
+        } else {
+            if (cur.rows + rows > kSwChunkRows) flush();
+            sg.row0 = 0; sg.n_rows = rows; sg.batch_row = cur.rows; sg.log_row = cur.rows; sg.gblock0 = cur.gblocks; sg.ablock0 = cur.ablocks;
+            pl->segs.push_back(sg);
+            cur.n_segs++; cur.rows += rows;
+            cur.gblocks += (unsigned)blocks_of((long long)rows * C * ph * pwq); cur.ablocks += (unsigned)ablocks;
+        }
+        pl->cap_rows = std::max(pl->cap_rows, std::min(rows, kSwChunkRows)); *log_rows = std::max<long long>(*log_rows, rows);
+        tile0 += im.n_tiles;
+        *img_floats += (long long)align_up((size_t)C * im.Hp * im.Wp, 64);
+        pl->out_elems += (long long)align_up((size_t)K * im.Hp * im.Wp, 256);
+    }
+    flush();
+    for (const SwChunk& c : pl->chunks) {
+        pl->cap_rows = std::max(pl->cap_rows, c.rows);
+        if ((long long)c.gblocks >= (1LL << 31) || (long long)c.ablocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: a chunk exceeds 2^31 blocks", entry);
+    }
+    *log_rows = std::max<long long>(*log_rows, pl->cap_rows);
+    if (F > 1 && blocks_of(pl->out_elems >> 3) >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the fold mean exceeds 2^31 blocks", entry);
+    return TS2D_OK;
+}
+
+// The export: one segment per image (its half logits are segs' out_off), the taps of its rows then of its columns.
+// rs_elems: elements of the resampled outputs.
+int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, const char* entry, SwPlan* pl,
+                std::vector<RsTap>* rtaps, long long* rs_elems) {
+    long long oo = 0;
+    for (int i = 0; i < n_images; ++i) {
+        const ts2d_tiled_image& im = images[i]; const ts2d_tiled_export& ex = exports[i];
+        RsSeg rs{};
+        rs.src_off = oo; rs.dst_off = *rs_elems; rs.Hp = im.Hp; rs.Wp = im.Wp; rs.out_h = ex.out_h; rs.out_w = ex.out_w;
+        rs.tap0 = (int)rtaps->size(); rs.block0 = (unsigned)pl->rs_blocks;
+        pl->rsegs.push_back(rs);
+        rtaps->resize(rtaps->size() + ex.out_h + ex.out_w);
+        rs_axis_taps(ex.src_h, ex.out_h, ex.src_y, rtaps->data() + rs.tap0);
+        rs_axis_taps(ex.src_w, ex.out_w, ex.src_x, rtaps->data() + rs.tap0 + ex.out_h);
+        pl->rs_blocks += blocks_of((long long)K * ex.out_h * ((ex.out_w + 3) / 4));
+        *rs_elems += (long long)align_up((size_t)K * ex.out_h * ex.out_w, 256);
+        oo += (long long)align_up((size_t)K * im.Hp * im.Wp, 256);
+    }
+    if (pl->rs_blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the export exceeds 2^31 blocks", entry);
+    return TS2D_OK;
+}
+
+}  // namespace
+
+int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
+               int mirror_mask, bool name_images, const char* entry, SwPlan* pl) {
+    if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "%s: bad patch %dx%d", entry, ph, pw);
+    const int C = e->arch.input_channels, K = e->arch.num_classes;
+    int vflip[4] = {0, 0, 0, 0};
+    if ((mirror_mask & 3) == 3) { vflip[1] = 1; vflip[2] = 2; vflip[3] = 3; pl->V = 4; }
+    else if (mirror_mask & 1) { vflip[1] = 1; pl->V = 2; }
+    else if (mirror_mask & 2) { vflip[1] = 2; pl->V = 2; }
+    pl->vflips = vflip[0] | (vflip[1] << 8) | (vflip[2] << 16) | (vflip[3] << 24);
+    long long img_floats = 0, log_rows = 0, rs_elems = 0;
+    std::vector<RsTap> rtaps;
+    TRY(check_images(F, C, K, images, exports, n_images, ph, pw, name_images, entry, pl));
+    TRY(pack_rows(F, C, K, images, n_images, ph, pw, entry, pl, &img_floats, &log_rows));
+    if (exports) TRY(plan_export(K, images, exports, n_images, entry, pl, &rtaps, &rs_elems));
+    // ---- the descriptor table and every tile origin
+    const size_t n_tiles = (size_t)pl->n_tiles_all;
+    pl->tab_segs = pl->segs.size() * sizeof(SwSeg); pl->tab_rsegs = align_up(pl->tab_segs + 2 * n_tiles * 4, 8);
+    pl->tab_rtaps = pl->tab_rsegs + pl->rsegs.size() * sizeof(RsSeg);
+    pl->tab.resize(pl->tab_rtaps + rtaps.size() * sizeof(RsTap));
+    memcpy(pl->tab.data(), pl->segs.data(), pl->tab_segs);
+    if (exports) {
+        memcpy(pl->tab.data() + pl->tab_rsegs, pl->rsegs.data(), pl->rsegs.size() * sizeof(RsSeg));
+        memcpy(pl->tab.data() + pl->tab_rtaps, rtaps.data(), rtaps.size() * sizeof(RsTap));
+    }
+    int32_t* ty = reinterpret_cast<int32_t*>(pl->tab.data() + pl->tab_segs); int32_t* tx = ty + n_tiles;
+    for (int i = 0; i < n_images; ++i) {
+        memcpy(ty, images[i].tile_y, (size_t)images[i].n_tiles * 4); memcpy(tx, images[i].tile_x, (size_t)images[i].n_tiles * 4);
+        ty += images[i].n_tiles; tx += images[i].n_tiles;
+    }
+    // ---- the scratch (SwPlan names its parts)
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+    pl->o_tab = take(pl->tab.size()); pl->o_g = take((size_t)ph * pw * 2); pl->o_imgs = take((size_t)img_floats * 4);
+    pl->o_batch = take((size_t)pl->cap_rows * C * ph * pw * 4); pl->o_log = take((size_t)log_rows * K * ph * pw * 4);
+    pl->o_o16 = take(pl->any16 ? (size_t)F * pl->out_elems * 2 : 0); pl->o_seg = take(pl->anyseg ? (size_t)pl->out_elems : 0);
+    pl->o_flag = take((size_t)F * n_images * 4);
+    pl->o_rs8 = take(pl->any_rs8 ? (size_t)rs_elems : 0); pl->o_rs32 = take(pl->any_rs32 ? (size_t)rs_elems * 4 : 0);
+    pl->bytes = off;
+    return TS2D_OK;
+}
+
+}  // namespace ts2d
