@@ -11,6 +11,7 @@ from tests import cases
 from tests.conftest import blob_for
 from totalsegmentator2d_amd import _lib, export, nrrd, prng, weights
 from totalsegmentator2d_amd import preprocess as P
+from totalsegmentator2d_amd import engine as engine_module
 from totalsegmentator2d_amd import sliding_window as sw
 from totalsegmentator2d_amd.engine import Engine, predict_tiled_export_ensemble
 from totalsegmentator2d_amd.model import HIPModel
@@ -172,7 +173,7 @@ def _host_seg(logits, hw):
 
 
 @pytest.mark.parametrize('mirror', [None, (0, 1)])
-def test_the_predictors_segmentation_of_an_ensemble_equals_the_host_route(mirror):
+def test_the_predictors_segmentation_of_an_ensemble_equals_the_host_route(mirror, monkeypatch):
     arch, shape, patch, step, _, folds, seed = cases.SW_CASES['sw_folds_nomirror']
     assert folds == 2
     blobs = [blob_for(arch, seed + f)[1] for f in range(folds)]
@@ -182,8 +183,9 @@ def test_the_predictors_segmentation_of_an_ensemble_equals_the_host_route(mirror
     p.manual_initialization(arch, blobs, patch, inference_allowed_mirroring_axes=mirror)
     try:
         calls = []
-        orig = p._sliding_window_ensemble
-        p._sliding_window_ensemble = lambda *a, **kw: (calls.append(len(a[0])), orig(*a, **kw))[1]
+        orig = engine_module.predict_tiled_export_ensemble          # the predictor looks it up at call time: calls INTO THE LIBRARY are counted
+        monkeypatch.setattr(engine_module, 'predict_tiled_export_ensemble',
+                            lambda engines, images, *a, **kw: (calls.append(len(images)), orig(engines, images, *a, **kw))[1])
         lg = p.predict_logits_from_preprocessed_data(data)
         for out_shape in (None, (1, 150, 111)):
             seg = p.predict_segmentation_from_preprocessed_data(data, **({} if out_shape is None else {'out_shape': out_shape}))
@@ -239,7 +241,7 @@ def _image(hw, spacing, seed):
                       (1.0, 0.0, 0.0, 1.0), 2, {}, None)
 
 
-def test_apply_and_apply_batch_of_a_two_fold_model_equal_the_host_route():
+def test_apply_and_apply_batch_of_a_two_fold_model_equal_the_host_route(monkeypatch):
     cases_ = [_image((100, 90), (1.5, 1.5), 1), _image((150, 128), (0.8, 1.0), 2), _image((70, 131), (1.5, 1.5), 3)]
     m = _two_fold_model()
     m.start()
@@ -247,8 +249,9 @@ def test_apply_and_apply_batch_of_a_two_fold_model_equal_the_host_route():
         p = m._predictor
         assert len(p.engines) == 2 and p._device_ensemble()
         calls = []
-        orig = p._sliding_window_ensemble
-        p._sliding_window_ensemble = lambda *a, **kw: (calls.append(len(a[0])), orig(*a, **kw))[1]
+        orig = engine_module.predict_tiled_export_ensemble          # the predictor looks it up at call time: calls INTO THE LIBRARY are counted
+        monkeypatch.setattr(engine_module, 'predict_tiled_export_ensemble',
+                            lambda engines, images, *a, **kw: (calls.append(len(images)), orig(engines, images, *a, **kw))[1])
         m.device_threshold = False
         host = [m.apply(c) for c in cases_]
         host_many = m.apply_batch(cases_)

@@ -18,13 +18,6 @@ PRECISION_F32_EXACT = 0
 PRECISION_F32_SPLIT_F16X3 = 1
 PRECISION_F16 = 2
 
-# every symbol include/ts2d_engine.h declares
-SYMBOLS = ('ts2d_engine_create', 'ts2d_engine_load_weights', 'ts2d_engine_weight_buffer', 'ts2d_engine_weights_ready',
-           'ts2d_engine_forward', 'ts2d_engine_check', 'ts2d_engine_predict_tiled', 'ts2d_engine_predict_tiled_batch', 'ts2d_engine_predict_tiled_export', 'ts2d_ensemble_predict_tiled_export', 'ts2d_engine_tiled_inf_flag', 'ts2d_engine_set_tile_dtype', 'ts2d_engine_set_keep_activations', 'ts2d_project_coronal', 'ts2d_project_coronal_zscore', 'ts2d_resample_cubic', 'ts2d_planes_create', 'ts2d_planes_crop_zscore', 'ts2d_planes_resample_cubic', 'ts2d_planes_extent', 'ts2d_planes_download', 'ts2d_planes_destroy', 'ts2d_synth_slices', 'ts2d_engine_reserve', 'ts2d_engine_workspace_bytes', 'ts2d_engine_set_workspace', 'ts2d_engine_set_precision', 'ts2d_engine_set_option', 'ts2d_engine_set_profiling', 'ts2d_engine_num_ops',
-           'ts2d_engine_op_name', 'ts2d_engine_op_kernel', 'ts2d_engine_op_ksplit', 'ts2d_engine_op_times', 'ts2d_engine_debug_tensor', 'ts2d_engine_device_bytes', 'ts2d_engine_destroy',
-           'ts2d_last_error', 'ts2d_abi_version')
-
-
 class ArchDesc(ctypes.Structure):
     """``ts2d_arch_desc``."""
     _fields_ = [('input_channels', ctypes.c_int32), ('num_classes', ctypes.c_int32), ('n_stages', ctypes.c_int32),
@@ -44,6 +37,59 @@ class TiledExport(ctypes.Structure):
     """``ts2d_tiled_export``: the resample-back of one image of ``ts2d_engine_predict_tiled_export``."""
     _fields_ = [('src_y', ctypes.c_int32), ('src_x', ctypes.c_int32), ('src_h', ctypes.c_int32), ('src_w', ctypes.c_int32),
                 ('out_h', ctypes.c_int32), ('out_w', ctypes.c_int32), ('seg_u8', ctypes.c_void_p), ('logits_f32', ctypes.c_void_p)]
+
+
+# shorthands of the table below: int, void *, size_t, long long, unsigned long long, char *; pointers to a void * and to the two descriptors
+_I, _P, _Z, _LL, _ULL, _S = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_char_p
+_PP, _TI, _TE = ctypes.POINTER(_P), ctypes.POINTER(TiledImage), ctypes.POINTER(TiledExport)
+_PROJECT = [_I, _P, _Z, _I, _I, _I, _I, _LL, _LL, _LL, _LL, _P, _P]
+
+# every symbol include/ts2d_engine.h declares: name -> (restype, argtypes)
+SIGNATURES = {
+    'ts2d_abi_version': (_I, []),                 # first: load() checks it before it looks up the rest
+    'ts2d_last_error': (_S, []),
+    'ts2d_engine_create': (_I, [ctypes.POINTER(ArchDesc), _P, _Z, _I, _PP]),
+    'ts2d_engine_load_weights': (_I, [_P, _P, _Z]),
+    'ts2d_engine_weight_buffer': (_I, [_P, _PP, ctypes.POINTER(_Z)]),
+    'ts2d_engine_weights_ready': (_I, [_P]),
+    'ts2d_engine_forward': (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P]),
+    'ts2d_engine_check': (_I, [_P]),
+    'ts2d_engine_predict_tiled': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    'ts2d_engine_predict_tiled_batch': (_I, [_P, _TI, _I, _I, _I, _I, _P]),
+    'ts2d_engine_predict_tiled_export': (_I, [_P, _TI, _TE, _I, _I, _I, _I, _P, _I]),
+    'ts2d_ensemble_predict_tiled_export': (_I, [_PP, _I, _TI, _TE, _I, _I, _I, _I, _P, _I]),
+    'ts2d_project_coronal': (_I, _PROJECT),
+    'ts2d_project_coronal_zscore': (_I, _PROJECT + [_P, _P, _P]),
+    'ts2d_resample_cubic': (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    'ts2d_planes_create': (_I, [_I, _P, _I, _I, _I, _PP]),
+    'ts2d_planes_crop_zscore': (_I, [_P, ctypes.POINTER(ctypes.c_int32 * 4), _P, ctypes.POINTER(_I)]),
+    'ts2d_planes_resample_cubic': (_I, [_P, _I, _I]),
+    'ts2d_planes_extent': (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    'ts2d_planes_download': (_I, [_P, _P]),
+    'ts2d_planes_destroy': (_I, [_P]),
+    'ts2d_synth_slices': (_I, [_I, _ULL, _ULL, _ULL, _P, _P]),
+    'ts2d_engine_reserve': (_I, [_P, _I, _I, _I]),
+    'ts2d_engine_workspace_bytes': (_I, [_P, _I, _I, _I, ctypes.POINTER(_Z)]),
+    'ts2d_engine_set_workspace': (_I, [_P, _P, _Z]),
+    'ts2d_engine_set_precision': (_I, [_P, _I]),
+    'ts2d_engine_set_option': (_I, [_P, _S, _I]),
+    'ts2d_engine_set_tile_dtype': (_I, [_P, _I]),
+    'ts2d_engine_set_keep_activations': (_I, [_P, _I]),
+    'ts2d_engine_set_profiling': (_I, [_P, _I]),
+    'ts2d_engine_num_ops': (_I, [_P]),
+    'ts2d_engine_op_name': (_S, [_P, _I]),
+    'ts2d_engine_op_kernel': (_S, [_P, _I]),
+    'ts2d_engine_op_ksplit': (_I, [_P, _I]),
+    'ts2d_engine_op_times': (_I, [_P, _P, _I]),
+    'ts2d_engine_debug_tensor': (_I, [_P, _S, _P, _Z, ctypes.POINTER(ctypes.c_int32 * 4)]),
+    'ts2d_engine_tiled_inf_flag': (_I, [_P]),
+    'ts2d_engine_device_bytes': (_Z, [_P]),
+    'ts2d_engine_destroy': (_I, [_P]),
+}
+SYMBOLS = tuple(SIGNATURES)
+# added under ABI 9 (the cubic resample; the device-resident planes of preprocess.DevicePlanes): a library built before them lacks the
+# symbols, still loads, and the callers keep the host route
+OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_'))
 
 
 class EngineLibraryError(RuntimeError):
@@ -73,95 +119,13 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as ex:
         raise EngineLibraryError(f"failed to load {LIB_PATH}: {ex}") from ex
-    c = ctypes
-    lib.ts2d_abi_version.restype = c.c_int
-    lib.ts2d_abi_version.argtypes = []
-    if lib.ts2d_abi_version() != ABI_VERSION:
-        raise EngineLibraryError(f"ABI mismatch: library {lib.ts2d_abi_version()}, binding {ABI_VERSION}")
-    lib.ts2d_last_error.restype = c.c_char_p
-    lib.ts2d_last_error.argtypes = []
-    lib.ts2d_engine_create.restype = c.c_int
-    lib.ts2d_engine_create.argtypes = [c.POINTER(ArchDesc), c.c_void_p, c.c_size_t, c.c_int, c.POINTER(c.c_void_p)]
-    lib.ts2d_engine_load_weights.restype = c.c_int
-    lib.ts2d_engine_load_weights.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t]
-    lib.ts2d_engine_weight_buffer.restype = c.c_int
-    lib.ts2d_engine_weight_buffer.argtypes = [c.c_void_p, c.POINTER(c.c_void_p), c.POINTER(c.c_size_t)]
-    lib.ts2d_engine_weights_ready.restype = c.c_int
-    lib.ts2d_engine_weights_ready.argtypes = [c.c_void_p]
-    lib.ts2d_engine_forward.restype = c.c_int
-    lib.ts2d_engine_forward.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
-                                        c.c_int, c.c_void_p]
-    lib.ts2d_engine_check.restype = c.c_int
-    lib.ts2d_engine_check.argtypes = [c.c_void_p]
-    lib.ts2d_engine_predict_tiled.restype = c.c_int
-    lib.ts2d_engine_predict_tiled.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
-                                              c.c_int, c.c_void_p, c.c_void_p, c.c_void_p]
-    lib.ts2d_engine_predict_tiled_batch.restype = c.c_int
-    lib.ts2d_engine_predict_tiled_batch.argtypes = [c.c_void_p, c.POINTER(TiledImage), c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p]
-    lib.ts2d_engine_predict_tiled_export.restype = c.c_int
-    lib.ts2d_engine_predict_tiled_export.argtypes = [c.c_void_p, c.POINTER(TiledImage), c.POINTER(TiledExport), c.c_int, c.c_int, c.c_int, c.c_int,
-                                                     c.c_void_p, c.c_int]
-    lib.ts2d_ensemble_predict_tiled_export.restype = c.c_int
-    lib.ts2d_ensemble_predict_tiled_export.argtypes = [c.POINTER(c.c_void_p), c.c_int, c.POINTER(TiledImage), c.POINTER(TiledExport), c.c_int, c.c_int,
-                                                       c.c_int, c.c_int, c.c_void_p, c.c_int]
-    lib.ts2d_project_coronal.restype = c.c_int
-    lib.ts2d_project_coronal.argtypes = [c.c_int, c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.c_int, c.c_longlong, c.c_longlong,
-                                         c.c_longlong, c.c_longlong, c.c_void_p, c.c_void_p]
-    lib.ts2d_project_coronal_zscore.restype = c.c_int
-    lib.ts2d_project_coronal_zscore.argtypes = [c.c_int, c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.c_int, c.c_longlong, c.c_longlong,
-                                         c.c_longlong, c.c_longlong, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
-    if hasattr(lib, 'ts2d_resample_cubic'):        # added under ABI 9: a library built before it lacks the symbol and the callers keep the host route
-        lib.ts2d_resample_cubic.restype = c.c_int
-        lib.ts2d_resample_cubic.argtypes = [c.c_int, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p]
-    if hasattr(lib, 'ts2d_planes_create'):         # the device-resident planes of preprocess.DevicePlanes, added under ABI 9 like the entry above
-        lib.ts2d_planes_create.restype = c.c_int
-        lib.ts2d_planes_create.argtypes = [c.c_int, c.c_void_p, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
-        lib.ts2d_planes_crop_zscore.restype = c.c_int
-        lib.ts2d_planes_crop_zscore.argtypes = [c.c_void_p, c.POINTER(c.c_int32 * 4), c.c_void_p, c.POINTER(c.c_int)]
-        lib.ts2d_planes_resample_cubic.restype = c.c_int
-        lib.ts2d_planes_resample_cubic.argtypes = [c.c_void_p, c.c_int, c.c_int]
-        lib.ts2d_planes_extent.restype = c.c_int
-        lib.ts2d_planes_extent.argtypes = [c.c_void_p, c.POINTER(c.c_int), c.POINTER(c.c_int)]
-        lib.ts2d_planes_download.restype = c.c_int
-        lib.ts2d_planes_download.argtypes = [c.c_void_p, c.c_void_p]
-        lib.ts2d_planes_destroy.restype = c.c_int
-        lib.ts2d_planes_destroy.argtypes = [c.c_void_p]
-    lib.ts2d_synth_slices.restype = c.c_int
-    lib.ts2d_synth_slices.argtypes = [c.c_int, c.c_ulonglong, c.c_ulonglong, c.c_ulonglong, c.c_void_p, c.c_void_p]
-    lib.ts2d_engine_reserve.restype = c.c_int
-    lib.ts2d_engine_reserve.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_int]
-    lib.ts2d_engine_workspace_bytes.restype = c.c_int
-    lib.ts2d_engine_workspace_bytes.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_size_t)]
-    lib.ts2d_engine_set_workspace.restype = c.c_int
-    lib.ts2d_engine_set_workspace.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t]
-    lib.ts2d_engine_set_precision.restype = c.c_int
-    lib.ts2d_engine_set_precision.argtypes = [c.c_void_p, c.c_int]
-    lib.ts2d_engine_set_option.restype = c.c_int
-    lib.ts2d_engine_set_option.argtypes = [c.c_void_p, c.c_char_p, c.c_int]
-    lib.ts2d_engine_set_tile_dtype.restype = c.c_int
-    lib.ts2d_engine_set_tile_dtype.argtypes = [c.c_void_p, c.c_int]
-    lib.ts2d_engine_set_keep_activations.restype = c.c_int
-    lib.ts2d_engine_set_keep_activations.argtypes = [c.c_void_p, c.c_int]
-    lib.ts2d_engine_set_profiling.restype = c.c_int
-    lib.ts2d_engine_set_profiling.argtypes = [c.c_void_p, c.c_int]
-    lib.ts2d_engine_num_ops.restype = c.c_int
-    lib.ts2d_engine_num_ops.argtypes = [c.c_void_p]
-    lib.ts2d_engine_op_name.restype = c.c_char_p
-    lib.ts2d_engine_op_name.argtypes = [c.c_void_p, c.c_int]
-    lib.ts2d_engine_op_kernel.restype = c.c_char_p
-    lib.ts2d_engine_op_kernel.argtypes = [c.c_void_p, c.c_int]
-    lib.ts2d_engine_op_ksplit.restype = c.c_int
-    lib.ts2d_engine_op_ksplit.argtypes = [c.c_void_p, c.c_int]
-    lib.ts2d_engine_op_times.restype = c.c_int
-    lib.ts2d_engine_op_times.argtypes = [c.c_void_p, c.c_void_p, c.c_int]
-    lib.ts2d_engine_debug_tensor.restype = c.c_int
-    lib.ts2d_engine_debug_tensor.argtypes = [c.c_void_p, c.c_char_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_int32 * 4)]
-    lib.ts2d_engine_tiled_inf_flag.restype = c.c_int
-    lib.ts2d_engine_tiled_inf_flag.argtypes = [c.c_void_p]
-    lib.ts2d_engine_device_bytes.restype = c.c_size_t
-    lib.ts2d_engine_device_bytes.argtypes = [c.c_void_p]
-    lib.ts2d_engine_destroy.restype = c.c_int
-    lib.ts2d_engine_destroy.argtypes = [c.c_void_p]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
+        if name == 'ts2d_abi_version' and fn() != ABI_VERSION:      # the table's first entry: another ABI is refused before its symbols are looked up
+            raise EngineLibraryError(f"ABI mismatch: library {fn()}, binding {ABI_VERSION}")
     _lib = lib
     return lib
 

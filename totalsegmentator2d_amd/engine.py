@@ -216,25 +216,13 @@ class Engine:
         """Device-side sliding window for one padded 2-D image [C,Hp,Wp] (C-ABI ts2d_engine_predict_tiled).
         tiles: [(y, x), ...] in upstream order; gaussian: float16 [ph,pw] or None.  Returns (float16 [K,Hp,Wp] or None,
         uint8 [K,Hp,Wp] or None)."""
-        image = np.ascontiguousarray(image, dtype=np.float32)
-        C, Hp, Wp = image.shape
-        if C != self.arch.input_channels:
-            raise RuntimeError(f"input has {C} channels, the model expects {self.arch.input_channels}")
-        ty = np.ascontiguousarray([t[0] for t in tiles], dtype=np.int32)
-        tx = np.ascontiguousarray([t[1] for t in tiles], dtype=np.int32)
-        mask = 0
-        for a in (mirror_axes or ()):
-            mask |= 1 << int(a)
-        g = None if gaussian is None else np.ascontiguousarray(gaussian, dtype=np.float16)
-        K = self.arch.num_classes
-        out16 = np.empty((K, Hp, Wp), dtype=np.float16) if want_logits else None
-        seg = np.empty((K, Hp, Wp), dtype=np.uint8) if want_seg else None
-        _lib.check(self.lib.ts2d_engine_predict_tiled(
-            self._h, image.ctypes.data, Hp, Wp, int(patch[0]), int(patch[1]), len(tiles), ty.ctypes.data, tx.ctypes.data, mask,
-            None if g is None else g.ctypes.data, None if out16 is None else out16.ctypes.data,
-            None if seg is None else seg.ctypes.data), 'ts2d_engine_predict_tiled')
-        self.last_tiled_inf = bool(self.lib.ts2d_engine_tiled_inf_flag(self._h))     # upstream's inf check, done on the device
-        return out16, seg
+        desc, _, mask, g, keep, outs = self._tiled_args(None, [image], [tiles], None, mirror_axes, gaussian, False, False, want_logits, want_seg)
+        d = desc[0]
+        _lib.check(self.lib.ts2d_engine_predict_tiled(self._h, d.image, d.Hp, d.Wp, int(patch[0]), int(patch[1]), d.n_tiles, d.tile_y, d.tile_x,
+                                                      mask, g, d.logits_f16, d.seg_u8), 'ts2d_engine_predict_tiled')
+        _read_tiled_inf([self], None, 0, engine_flags=True)                          # upstream's inf check, done on the device
+        del keep
+        return (outs[2][0] if want_logits else None), (outs[3][0] if want_seg else None)
 
     def predict_tiled_batch(self, images, patch, tiles, mirror_axes=None, gaussian: Optional[np.ndarray] = None,
                             want_logits: bool = True, want_seg: bool = False):
@@ -244,43 +232,13 @@ class Engine:
         The network takes the full-batch dispatch whatever the batch: an image's bytes do not depend on its batch-mates, its position
         or the batch size, and equal :meth:`predict_tiled` on an engine with ``options={'sbk': 0}`` bit for bit.
         Sets ``last_tiled_inf`` (the OR over the images) and ``last_tiled_inf_per_image``."""
-        if len(images) != len(tiles):
-            raise RuntimeError(f"{len(images)} images but {len(tiles)} tile lists")
-        if not (want_logits or want_seg):
-            raise RuntimeError("predict_tiled_batch: neither logits nor segmentation requested")
-        K = self.arch.num_classes
-        keep = []                    # every array the descriptors point into stays alive until the call returns
-        desc = (_lib.TiledImage * max(len(images), 1))()
-        out16, seg = [], []
-        for i, (image, tl) in enumerate(zip(images, tiles)):
-            image = np.ascontiguousarray(image, dtype=np.float32)
-            if image.ndim != 3:
-                raise RuntimeError(f"image {i}: expected [C,Hp,Wp], found shape {image.shape}")
-            C, Hp, Wp = image.shape
-            if C != self.arch.input_channels:
-                raise RuntimeError(f"image {i}: input has {C} channels, the model expects {self.arch.input_channels}")
-            ty = np.ascontiguousarray([t[0] for t in tl], dtype=np.int32)
-            tx = np.ascontiguousarray([t[1] for t in tl], dtype=np.int32)
-            o16 = np.empty((K, Hp, Wp), dtype=np.float16) if want_logits else None
-            sg = np.empty((K, Hp, Wp), dtype=np.uint8) if want_seg else None
-            keep += [image, ty, tx]
-            out16.append(o16)
-            seg.append(sg)
-            d = desc[i]
-            d.image, d.Hp, d.Wp, d.n_tiles = image.ctypes.data, Hp, Wp, len(tl)
-            d.tile_y, d.tile_x = ty.ctypes.data, tx.ctypes.data
-            d.logits_f16 = None if o16 is None else o16.ctypes.data
-            d.seg_u8 = None if sg is None else sg.ctypes.data
-        mask = 0
-        for a in (mirror_axes or ()):
-            mask |= 1 << int(a)
-        g = None if gaussian is None else np.ascontiguousarray(gaussian, dtype=np.float16)
-        _lib.check(self.lib.ts2d_engine_predict_tiled_batch(self._h, desc, len(images), int(patch[0]), int(patch[1]), mask,
-                                                            None if g is None else g.ctypes.data), 'ts2d_engine_predict_tiled_batch')
-        self.last_tiled_inf_per_image = [bool(desc[i].inf_flag) for i in range(len(images))]
-        self.last_tiled_inf = any(self.last_tiled_inf_per_image)
+        desc, _, mask, g, keep, outs = self._tiled_args('predict_tiled_batch', images, tiles, None, mirror_axes, gaussian,
+                                                        False, False, want_logits, want_seg)
+        _lib.check(self.lib.ts2d_engine_predict_tiled_batch(self._h, desc, len(images), int(patch[0]), int(patch[1]), mask, g),
+                   'ts2d_engine_predict_tiled_batch')
+        _read_tiled_inf([self], desc, len(images), engine_flags=False)
         del keep
-        return (out16 if want_logits else None), (seg if want_seg else None)
+        return outs[2], outs[3]
 
     def predict_tiled_export(self, images, patch, tiles, exports, mirror_axes=None, gaussian: Optional[np.ndarray] = None,
                              want_seg: bool = True, want_f32: bool = False, want_logits: bool = False, want_padded_seg: bool = False,
@@ -293,26 +251,27 @@ class Engine:
         ``full_batch``: the full-batch dispatch of :meth:`predict_tiled_batch` (an image's bytes do not depend on its batch-mates);
         False: the size-dependent dispatch of :meth:`predict_tiled`.  The resampled values equal
         ``preprocess.resize_linear_f64`` of the float16 logits bit for bit.  Sets ``last_tiled_inf`` / ``last_tiled_inf_per_image``."""
-        desc, exd, mask, g, keep, outs = self._tiled_export_args('predict_tiled_export', images, tiles, exports, mirror_axes, gaussian,
-                                                                 want_seg, want_f32, want_logits, want_padded_seg)
-        _lib.check(self.lib.ts2d_engine_predict_tiled_export(self._h, desc, exd, len(images), int(patch[0]), int(patch[1]), mask,
-                                                             None if g is None else g.ctypes.data, int(bool(full_batch))),
-                   'ts2d_engine_predict_tiled_export')
-        self.last_tiled_inf_per_image = [bool(desc[i].inf_flag) for i in range(len(images))]
-        self.last_tiled_inf = any(self.last_tiled_inf_per_image)
+        desc, exd, mask, g, keep, outs = self._tiled_args('predict_tiled_export', images, tiles, exports, mirror_axes, gaussian,
+                                                          want_seg, want_f32, want_logits, want_padded_seg)
+        _lib.check(self.lib.ts2d_engine_predict_tiled_export(self._h, desc, exd, len(images), int(patch[0]), int(patch[1]), mask, g,
+                                                             int(bool(full_batch))), 'ts2d_engine_predict_tiled_export')
+        _read_tiled_inf([self], desc, len(images), engine_flags=False)
         del keep
         return outs
 
-    def _tiled_export_args(self, what, images, tiles, exports, mirror_axes, gaussian, want_seg, want_f32, want_logits, want_padded_seg):
-        """Argument preparation of :meth:`predict_tiled_export` and :func:`predict_tiled_export_ensemble` (`what` names the caller in a
-        message): the descriptor arrays, the mirror mask, the half gaussian, the arrays the descriptors point into, and the output lists
-        ``(seg, f32, logits, padded_seg)`` the call fills.  ``exports`` None (the ensemble only): no resample-back, no export descriptors."""
+    def _tiled_args(self, what, images, tiles, exports, mirror_axes, gaussian, want_seg, want_f32, want_logits, want_padded_seg):
+        """Argument preparation of every tiled call (`what` names the calling method in a message): the ``TiledImage`` array, the
+        ``TiledExport`` array (None without ``exports``: no resample-back), the mirror mask, the address of the half gaussian (or None),
+        the arrays all of these point into - they must outlive the call - and the output lists ``(seg, f32, logits, padded_seg)`` the
+        call fills, each None unless asked for.  ``what`` None is the one image of :meth:`predict_tiled`: its messages carry no
+        ``image i: `` and everything but the channel count is left to the library (or to the unpacking of the shape) to refuse."""
+        one = what is None
         if len(images) != len(tiles) or (exports is not None and len(exports) != len(images)):
             raise RuntimeError(f"{len(images)} images but {len(tiles)} tile lists" + ("" if exports is None else f" and {len(exports)} exports"))
         if exports is None:
             if want_seg or want_f32:
                 raise RuntimeError(f"{what}: the resampled outputs need exports")
-            if not (want_logits or want_padded_seg):
+            if not (want_logits or want_padded_seg or one):
                 raise RuntimeError(f"{what}: neither logits nor segmentation requested")
         elif not (want_seg or want_f32):
             raise RuntimeError(f"{what}: neither the resampled segmentation nor the resampled logits requested")
@@ -322,12 +281,13 @@ class Engine:
         desc, exd = (_lib.TiledImage * n)(), (None if exports is None else (_lib.TiledExport * n)())
         seg, f32, out16, pseg = [], [], [], []
         for i, (image, tl) in enumerate(zip(images, tiles)):
+            at = '' if one else f'image {i}: '
             image = np.ascontiguousarray(image, dtype=np.float32)
-            if image.ndim != 3:
-                raise RuntimeError(f"image {i}: expected [C,Hp,Wp], found shape {image.shape}")
+            if image.ndim != 3 and not one:
+                raise RuntimeError(f"{at}expected [C,Hp,Wp], found shape {image.shape}")
             C, Hp, Wp = image.shape
             if C != self.arch.input_channels:
-                raise RuntimeError(f"image {i}: input has {C} channels, the model expects {self.arch.input_channels}")
+                raise RuntimeError(f"{at}input has {C} channels, the model expects {self.arch.input_channels}")
             ty = np.ascontiguousarray([t[0] for t in tl], dtype=np.int32)
             tx = np.ascontiguousarray([t[1] for t in tl], dtype=np.int32)
             out16.append(np.empty((K, Hp, Wp), dtype=np.float16) if want_logits else None)
@@ -352,8 +312,9 @@ class Engine:
         for a in (mirror_axes or ()):
             mask |= 1 << int(a)
         g = None if gaussian is None else np.ascontiguousarray(gaussian, dtype=np.float16)
+        keep.append(g)
         outs = (seg if want_seg else None), (f32 if want_f32 else None), (out16 if want_logits else None), (pseg if want_padded_seg else None)
-        return desc, exd, mask, g, keep, outs
+        return desc, exd, mask, (None if g is None else g.ctypes.data), keep, outs
 
     def _check_shape(self, C, W, mask):
         if C != self.arch.input_channels:
@@ -440,18 +401,24 @@ def predict_tiled_export_ensemble(engines, images, patch, tiles, exports, mirror
     engines = list(engines)
     if not engines:
         raise RuntimeError("predict_tiled_export_ensemble: no engines")
-    e0 = engines[0]
-    desc, exd, mask, g, keep, outs = e0._tiled_export_args('predict_tiled_export_ensemble', images, tiles, exports, mirror_axes, gaussian,
-                                                           want_seg, want_f32, want_logits, want_padded_seg)
+    desc, exd, mask, g, keep, outs = engines[0]._tiled_args('predict_tiled_export_ensemble', images, tiles, exports, mirror_axes, gaussian,
+                                                            want_seg, want_f32, want_logits, want_padded_seg)
     handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
-    _lib.check(e0.lib.ts2d_ensemble_predict_tiled_export(handles, len(engines), desc, exd, len(images), int(patch[0]), int(patch[1]), mask,
-                                                         None if g is None else g.ctypes.data, int(bool(full_batch))),
-               'ts2d_ensemble_predict_tiled_export')
-    e0.last_tiled_inf_per_image = [bool(desc[i].inf_flag) for i in range(len(images))]
-    for e in engines:
-        e.last_tiled_inf = bool(e.lib.ts2d_engine_tiled_inf_flag(e._h))
+    _lib.check(engines[0].lib.ts2d_ensemble_predict_tiled_export(handles, len(engines), desc, exd, len(images), int(patch[0]), int(patch[1]),
+                                                                 mask, g, int(bool(full_batch))), 'ts2d_ensemble_predict_tiled_export')
+    _read_tiled_inf(engines, desc, len(images), engine_flags=True)
     del keep
     return outs
+
+
+def _read_tiled_inf(engines, desc, n_images, engine_flags: bool):
+    """The inf flags a tiled call left behind (upstream's inf check, done on the device).  With descriptors, ``last_tiled_inf_per_image``
+    of the first engine is their per-image flags; ``last_tiled_inf`` of every engine is its own flag in the library (the flat entry and
+    the ensemble: that fold's own) or, without ``engine_flags``, the OR over its images."""
+    if desc is not None:
+        engines[0].last_tiled_inf_per_image = [bool(desc[i].inf_flag) for i in range(n_images)]
+    for e in engines:
+        e.last_tiled_inf = bool(e.lib.ts2d_engine_tiled_inf_flag(e._h)) if engine_flags else any(e.last_tiled_inf_per_image)
 
 
 def unpack_mask(packed: np.ndarray, W: int) -> np.ndarray:

@@ -42,6 +42,20 @@ def fold_mean_f16(folds) -> np.ndarray:
     return pred
 
 
+def _to_numpy(data) -> np.ndarray:
+    """torch tensor or array-like in -> float32 numpy."""
+    return np.asarray(data.detach().cpu().numpy() if hasattr(data, 'detach') else data, dtype=np.float32)
+
+
+def _to_torch(a: np.ndarray):
+    """numpy out -> torch CPU tensor when torch is importable (so that the caller's ``.cpu()`` works), else the array."""
+    try:
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a))
+    except ImportError:
+        return a
+
+
 class _Device:
     """``torch.device``-like (``.type``) without importing torch."""
     def __init__(self, index: int):
@@ -167,7 +181,7 @@ class HIPnnUNetPredictor:
     _INF_MESSAGE = ('Encountered inf in predicted array. Aborting... If this problem persists, reduce '
                     'value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32')
 
-    def _sliding_window_batch(self, list_of_data, fold: int = 0, want_seg: bool = False, one_call: bool = True, out_shapes=None):
+    def _sliding_window_batch(self, list_of_data, fold: Optional[int] = 0, want_seg: bool = False, one_call: bool = True, out_shapes=None):
         """One fold, N inputs [C,Z,H,W]: pad, tile, tiles x mirror variants through the engine, upstream's fp16 Gaussian aggregation
         on the device.  Every z slice of every input is one image.  ``one_call``: all images in ONE engine call (C-ABI
         ts2d_engine_predict_tiled_batch: the network takes the full-batch dispatch, an input's bytes do not depend on its batch-mates,
@@ -177,12 +191,59 @@ class HIPnnUNetPredictor:
         ``out_shapes`` (with ``want_seg``, Z = 1): one in-plane extent ``(h, w)`` or None per input - the device resamples every input's
         logits (order 1) to its extent, None = the input's own, and thresholds them there (C-ABI ts2d_engine_predict_tiled_export, the
         export's ``resampling_fn_probabilities`` + threshold): uint8 [K,1,h,w] per input.
+        ``fold`` None: EVERY fold, single-slice inputs [C,1,H,W], ONE engine call (C-ABI ts2d_ensemble_predict_tiled_export): per fold
+        the same sliding window, the mean of the folds' float16 logits on the device (:func:`fold_mean_f16`, bit for bit), and every
+        output is that of the mean; ``want_seg`` always goes through the export (at an input's own extent the taps are 1 / 0).
+        ``one_call`` False there: the size-dependent dispatch, so the bytes are those of :meth:`predict_logits_from_preprocessed_data`.
         (The one method that touches the engine, under the name the test infrastructure overrides: tests/batch_util.py replaces it, and
         tests/host_predictor.py predict_sliding_window_return_logits, with the host restatement.)"""
         patch = tuple(self.configuration_manager.patch_size)
+        ensemble = fold is None
+        images, tiles, owner, reverts, shapes = self._pad_and_tile(list_of_data, patch, single_slice=ensemble)
+        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
+            raise AssertionError('mirror_axes does not match the dimension of the input!')
+        g = sw.compute_gaussian(patch) if self.use_gaussian else None
+        axes = self.allowed_mirroring_axes if self.use_mirroring else None
+        e = None if ensemble else self.engines[fold]
+        if ensemble and want_seg and out_shapes is None:
+            out_shapes = [None] * len(list_of_data)
+        exports = None if out_shapes is None else self._export_rects(list_of_data, reverts, shapes, out_shapes, want_seg)
+        want = dict(want_logits=not want_seg, want_seg=want_seg)
+        if ensemble:
+            from .engine import predict_tiled_export_ensemble
+            planes = predict_tiled_export_ensemble(self.engines, images, patch, tiles, exports, axes, g, **want, full_batch=one_call)[0 if want_seg else 2]
+            inf = self.engines[0].last_tiled_inf_per_image
+        elif exports is not None:
+            planes, inf = [], []
+            for grp in ([range(len(images))] if one_call else [[j] for j in range(len(images))]):
+                planes += e.predict_tiled_export([images[j] for j in grp], patch, [tiles[j] for j in grp], [exports[j] for j in grp], axes, g,
+                                                 full_batch=one_call)[0]
+                inf += e.last_tiled_inf_per_image
+        elif one_call:
+            planes, inf = e.predict_tiled_batch(images, patch, tiles, axes, g, **want)[want_seg], e.last_tiled_inf_per_image
+        else:
+            planes, inf = [], []
+            for image, tl in zip(images, tiles):
+                planes.append(e.predict_tiled(image, patch, tl, axes, g, **want)[want_seg])
+                inf.append(e.last_tiled_inf)
+        self._raise_on_inf(inf, owner, one_call)
+        if exports is not None:              # resampled on the device: already the case's own rectangle, one plane per input
+            return [p[:, None] for p in planes]
+        results, j = [], 0
+        for (Z, H, W), revert in zip(shapes, reverts):
+            full = np.stack(planes[j:j + Z], axis=1) if Z != 1 else planes[j][:, None]
+            j += Z
+            results.append(full[(slice(None),) + revert[1:]])
+        return results
+
+    def _pad_and_tile(self, list_of_data, patch, single_slice: bool):
+        """Inputs [C,Z,H,W] -> every z slice of every input, padded up to the patch, as one image with its tile list (upstream order),
+        the input that owns it, and per input the slicer that undoes the padding and the padded ``(Z, H, W)``."""
         images, tiles, owner, reverts, shapes = [], [], [], [], []
         for i, data in enumerate(list_of_data):
             data = np.asarray(data, dtype=np.float32)
+            if single_slice and (data.ndim != 4 or data.shape[1] != 1):
+                raise AssertionError('the fold ensemble on the device takes single-slice inputs (c, 1, y, z)')
             if data.ndim != 4:
                 raise AssertionError('input_image must be a 4D np.ndarray or torch.Tensor (c, x, y, z)')
             padded, revert = sw.pad_nd_image(data, patch)
@@ -194,82 +255,25 @@ class HIPnnUNetPredictor:
                 owner.append(i)
             reverts.append(revert)
             shapes.append((Z, H, W))
-        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
-            raise AssertionError('mirror_axes does not match the dimension of the input!')
-        g = sw.compute_gaussian(patch) if self.use_gaussian else None
-        axes = self.allowed_mirroring_axes if self.use_mirroring else None
-        e = self.engines[fold]
-        if out_shapes is not None:
-            if not want_seg or len(out_shapes) != len(list_of_data) or any(Z != 1 for Z, _, _ in shapes):
-                raise AssertionError('out_shapes needs want_seg, one extent (or None) per input and single-slice inputs')
-            exports = []
-            for data, revert, hw in zip(list_of_data, reverts, out_shapes):
-                H, W = np.shape(data)[2:]
-                exports.append((revert[2].start, revert[3].start, H, W) + (tuple(int(v) for v in hw) if hw is not None else (H, W)))
-            groups = [range(len(images))] if one_call else [[j] for j in range(len(images))]
-            planes, inf = [], []
-            for grp in groups:
-                seg = e.predict_tiled_export([images[j] for j in grp], patch, [tiles[j] for j in grp], [exports[j] for j in grp], axes, g,
-                                             full_batch=one_call)[0]
-                planes += seg
-                inf += e.last_tiled_inf_per_image
-            bad = sorted(j for j, f in enumerate(inf) if f)
-            if bad:
-                raise RuntimeError((f'input {bad[0]}: ' if one_call else '') + self._INF_MESSAGE)
-            return [p[:, None] for p in planes]
-        if one_call:
-            out16, seg = e.predict_tiled_batch(images, patch, tiles, axes, g, want_logits=not want_seg, want_seg=want_seg)
-            planes, inf = (seg if want_seg else out16), e.last_tiled_inf_per_image
-        else:
-            planes, inf = [], []
-            for image, tl in zip(images, tiles):
-                out16, seg = e.predict_tiled(image, patch, tl, axes, g, want_logits=not want_seg, want_seg=want_seg)
-                planes.append(seg if want_seg else out16)
-                inf.append(e.last_tiled_inf)
+        return images, tiles, owner, reverts, shapes
+
+    @staticmethod
+    def _export_rects(list_of_data, reverts, shapes, out_shapes, want_seg):
+        """One ``(src_y, src_x, src_h, src_w, out_h, out_w)`` per input: the rectangle of the padded prediction that is the case, and
+        the extent it is resampled to (None: its own)."""
+        if not want_seg or len(out_shapes) != len(list_of_data) or any(Z != 1 for Z, _, _ in shapes):
+            raise AssertionError('out_shapes needs want_seg, one extent (or None) per input and single-slice inputs')
+        exports = []
+        for data, revert, hw in zip(list_of_data, reverts, out_shapes):
+            H, W = np.shape(data)[2:]
+            exports.append((revert[2].start, revert[3].start, H, W) + (tuple(int(v) for v in hw) if hw is not None else (H, W)))
+        return exports
+
+    def _raise_on_inf(self, inf, owner, one_call):
+        """Upstream's inf check on the flags of the device, one per image; a call that carries several inputs names the first bad one."""
         bad = sorted({owner[j] for j, f in enumerate(inf) if f})
         if bad:
             raise RuntimeError((f'input {bad[0]}: ' if one_call else '') + self._INF_MESSAGE)
-        results, j = [], 0
-        for (Z, H, W), revert in zip(shapes, reverts):
-            full = np.stack(planes[j:j + Z], axis=1) if Z != 1 else planes[j][:, None]
-            j += Z
-            results.append(full[(slice(None),) + revert[1:]])
-        return results
-
-    def _sliding_window_ensemble(self, list_of_data, want_seg: bool = True, one_call: bool = True, out_shapes=None):
-        """Every fold, N single-slice inputs [C,1,H,W], ONE engine call (C-ABI ts2d_ensemble_predict_tiled_export): per fold the sliding
-        window of :meth:`_sliding_window_batch`, the mean of the folds' float16 logits on the device (:func:`fold_mean_f16`, bit for
-        bit), then that method's export: the order-1 resample to ``out_shapes[i]`` (None: the input's own extent, where the taps are
-        1 / 0) and the threshold.  Returns uint8 [K,1,h,w] per input, or the float16 [K,1,H,W] mean logits without ``want_seg``.
-        ``one_call`` False (the single-case methods): the size-dependent dispatch, so the bytes are those of
-        :meth:`predict_logits_from_preprocessed_data`; True: the full-batch dispatch of the ``_batch`` methods."""
-        from .engine import predict_tiled_export_ensemble
-        patch = tuple(self.configuration_manager.patch_size)
-        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
-            raise AssertionError('mirror_axes does not match the dimension of the input!')
-        out_shapes = [None] * len(list_of_data) if out_shapes is None else out_shapes
-        if len(out_shapes) != len(list_of_data):
-            raise AssertionError('out_shapes needs one extent (or None) per input')
-        images, tiles, exports = [], [], []
-        for data, hw in zip(list_of_data, out_shapes):
-            data = np.asarray(data, dtype=np.float32)
-            if data.ndim != 4 or data.shape[1] != 1:
-                raise AssertionError('the fold ensemble on the device takes single-slice inputs (c, 1, y, z)')
-            padded, revert = sw.pad_nd_image(data, patch)
-            H, W = data.shape[2:]
-            images.append(padded[:, 0])
-            tiles.append([(sx, sy) for (_, sx, sy) in sw.tile_slicers(padded.shape[2:], patch, self.tile_step_size, 1)])
-            exports.append((revert[2].start, revert[3].start, H, W) + (tuple(int(v) for v in hw) if hw is not None else (H, W)))
-        g = sw.compute_gaussian(patch) if self.use_gaussian else None
-        axes = self.allowed_mirroring_axes if self.use_mirroring else None
-        seg, _, out16, _ = predict_tiled_export_ensemble(self.engines, images, patch, tiles, exports if want_seg else None, axes, g,
-                                                         want_seg=want_seg, want_logits=not want_seg, full_batch=one_call)
-        bad = sorted(j for j, f in enumerate(self.engines[0].last_tiled_inf_per_image) if f)
-        if bad:
-            raise RuntimeError((f'input {bad[0]}: ' if one_call else '') + self._INF_MESSAGE)
-        if want_seg:
-            return [p[:, None] for p in seg]
-        return [p[:, ex[0]:ex[0] + ex[2], ex[1]:ex[1] + ex[3]][:, None] for p, ex in zip(out16, exports)]
 
     def _device_ensemble(self) -> bool:
         """Is this a fold ensemble whose folds are all real engines?  (The host doubles of the tests have none: they keep the logits route.)"""
@@ -301,69 +305,44 @@ class HIPnnUNetPredictor:
         ones and the host never thresholds.  One z-slice (the 2-D models of ts2d); returns uint8 [K, 1, H, W] in the
         preprocessed geometry, or None when the case needs the logits (3-D stacks; a predictor without engines).  A fold ensemble runs
         every fold in one engine call and the device takes the mean of the folds' logits in front of the threshold
-        (:meth:`_sliding_window_ensemble`): the bytes are those of :meth:`predict_logits_from_preprocessed_data` + the host export.
+        (:meth:`_sliding_window_batch` with ``fold=None``): the bytes are those of :meth:`predict_logits_from_preprocessed_data` + the host export.
         ``out_shape`` (the case's ``shape_after_cropping_and_before_resampling``, (h, w) or (1, h, w)): the export's order-1
         resample-back runs on the device in front of the threshold (kernels_resample.h; bit for bit the host route's
         ``resample_data_to_shape(order=1)`` + threshold) and the result is uint8 [K, 1, h, w] in THAT extent."""
-        if hasattr(data, 'detach'):
-            data = data.detach().cpu().numpy()
-        data = np.asarray(data, dtype=np.float32)
+        data = _to_numpy(data)
         ensemble = self._device_ensemble()
         if not (ensemble or len(self.list_of_parameters) == len(self.engines) == 1) or data.ndim != 4 or data.shape[1] != 1:
             return None
         hw = self._in_plane(out_shape, data)
         if hw is False:
             return None
-        if ensemble:
-            return self._sliding_window_ensemble([data], want_seg=True, one_call=False, out_shapes=[hw])[0]
         kw = {} if hw is None else {'out_shapes': [hw]}
-        return self._sliding_window_batch([data], 0, want_seg=True, one_call=False, **kw)[0]
+        return self._sliding_window_batch([data], None if ensemble else 0, want_seg=True, one_call=False, **kw)[0]
 
     def predict_logits_from_preprocessed_data(self, data):
         """Fold ensemble (upstream: sum over ``list_of_parameters`` then ``/= n``).  Accepts numpy or torch [C,1,H,W];
         returns a torch CPU tensor (float16) when torch is importable so that the caller's ``.cpu()`` works."""
-        if hasattr(data, 'detach'):
-            data = data.detach().cpu().numpy()
-        n = max(1, len(self.list_of_parameters))
-        pred = None
-        for f in range(n):
-            p = self.predict_sliding_window_return_logits(data, f)
-            pred = p if pred is None else pred + p
-        if n > 1:
-            pred = pred / np.float16(n)
-        try:
-            import torch
-            return torch.from_numpy(np.ascontiguousarray(pred))
-        except ImportError:
-            return pred
+        data, n = _to_numpy(data), max(1, len(self.list_of_parameters))
+        return _to_torch(fold_mean_f16([self.predict_sliding_window_return_logits(data, f) for f in range(n)]))
 
     # ------------------------------------------------------------------ batched inference (N cases, one engine batch per fold)
     def predict_logits_from_preprocessed_data_batch(self, list_of_data):
         """:meth:`predict_logits_from_preprocessed_data` for a list of inputs: one batched engine call per fold (a [C,Z,H,W] input
         contributes Z images - a z-stack is one engine call, not Z), folds averaged as there.  Returns a list (torch CPU tensors when
         torch is importable)."""
-        datas = [d.detach().cpu().numpy() if hasattr(d, 'detach') else d for d in list_of_data]
+        datas = [_to_numpy(d) for d in list_of_data]
         if not datas:
             return []
         n = max(1, len(self.list_of_parameters))
-        preds = None
-        for f in range(n):
-            ps = self._sliding_window_batch(datas, f)
-            preds = ps if preds is None else [a + b for a, b in zip(preds, ps)]
-        if n > 1:
-            preds = [p / np.float16(n) for p in preds]
-        try:
-            import torch
-            return [torch.from_numpy(np.ascontiguousarray(p)) for p in preds]
-        except ImportError:
-            return preds
+        per_fold = [self._sliding_window_batch(datas, f) for f in range(n)]
+        return [_to_torch(fold_mean_f16(folds)) for folds in zip(*per_fold)]
 
     def predict_segmentation_from_preprocessed_data_batch(self, list_of_data, out_shapes=None):
         """:meth:`predict_segmentation_from_preprocessed_data` for a list of inputs: uint8 [K,1,H,W] per input from ONE engine call,
         or None when the predictor needs the logits (a fold ensemble without engines) or an input is no single z slice.  ``out_shapes``:
         one ``out_shape`` (or None) per input; inputs that resample and inputs that do not travel in the same call.  A fold ensemble:
-        every fold and every input in ONE engine call, the mean of the folds on the device (:meth:`_sliding_window_ensemble`)."""
-        datas = [np.asarray(d.detach().cpu().numpy() if hasattr(d, 'detach') else d, dtype=np.float32) for d in list_of_data]
+        every fold and every input in ONE engine call, the mean of the folds on the device (:meth:`_sliding_window_batch` with ``fold=None``)."""
+        datas = [_to_numpy(d) for d in list_of_data]
         ensemble = self._device_ensemble()
         if not (ensemble or len(self.list_of_parameters) == 1) or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
             return None
@@ -372,7 +351,5 @@ class HIPnnUNetPredictor:
         hws = [self._in_plane(s, d) for s, d in zip(out_shapes, datas)] if out_shapes is not None else [None] * len(datas)
         if (out_shapes is not None and len(out_shapes) != len(datas)) or any(hw is False for hw in hws):
             return None
-        if ensemble:
-            return self._sliding_window_ensemble(datas, want_seg=True, one_call=True, out_shapes=hws)
         kw = {} if all(hw is None for hw in hws) else {'out_shapes': hws}
-        return self._sliding_window_batch(datas, 0, want_seg=True, **kw)
+        return self._sliding_window_batch(datas, None if ensemble else 0, want_seg=True, **kw)
