@@ -264,6 +264,51 @@ int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, c
 int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_export* exports,
                                        int n_images, int patch_h, int patch_w, int mirror_mask, const uint16_t* gaussian_f16, int full_batch);
 
+/* ts2d_ensemble_predict_tiled_export for a LABEL-MAP model - the ordinary nnU-Net head: len(labels) heads with background at 0, whose export
+ * is "resample the logits back, then take the argmax over the heads" (`export_prediction_from_logits`, reference call site
+ * ts2d/core/inference/prediction_worker.py:215-221, without the multilabel fork's sigmoid).  One kernel (csrc/kernels_labelmap.h) does
+ * both where the aggregation (or the mean of the folds) left the half logits, so ONE uint8 plane of the ORIGINAL extent travels to the
+ * host instead of K float16 planes of the network's extent that the host widens, interpolates and compares.
+ *   engines        as in ts2d_ensemble_predict_tiled_export: n_engines handles (1..32) in fold order, the same sliding window per fold,
+ *                  the same mean.  n_engines == 1 is the single-model case: no mean kernel, as there.
+ *   labelmaps      n_images descriptors, one per image.  (src_y, src_x, src_h, src_w) and (out_h, out_w) mean what they mean in
+ *                  ts2d_tiled_export; label_u8 [out_h, out_w] (not NULL): per pixel the index of the head with the largest value.
+ *                  The value compared per head is that of ts2d_tiled_export.logits_f32, bit for bit (float64 products and sums without
+ *                  FMA, ONE rounding to float32) - except where (out_h, out_w) == (src_h, src_w): the host route does not resample then,
+ *                  and the value is the widened half itself (no taps: an infinite logit stays infinite instead of meeting a zero weight).
+ *                  The comparison is numpy's argmax on float32: the first index of the maximum wins, +0 and -0 are equal, a NaN beats
+ *                  every number and the first NaN wins.  Restated in numpy as totalsegmentator2d_amd.export.labelmap_statement.
+ *   images         as in ts2d_engine_predict_tiled_export: logits_f16 and seg_u8 of an image may both be NULL; logits_f16 asked for in
+ *                  the same call are the (mean) half logits the label map was taken from.  inf_flag is written as in the ensemble entry
+ *                  (the OR over the folds); ts2d_engine_tiled_inf_flag(engines[f]) is fold f's own.
+ *   full_batch     as in ts2d_engine_predict_tiled_export (nonzero: an image's bytes do not depend on its batch-mates).
+ * Every argument is validated before any device work and nothing is written on an error: what ts2d_ensemble_predict_tiled_export
+ * refuses of the engines, in the same words; per image what ts2d_engine_predict_tiled_export refuses, the image named, with "labelmap:"
+ * where it says "export:" (an empty source rectangle or one that leaves the image, a non-positive output extent, a NULL label_u8, 2^31 or
+ * more output elements, 2^26 or more output rows + columns in one call).  n_images == 0 returns TS2D_OK and does nothing.
+ * Device scratch, all held by engines[0]: that of ts2d_ensemble_predict_tiled_export without its resampled outputs (tile logits and
+ * gathered batch once, the half outputs n_engines x K x Hp x Wp x 2 bytes summed over the images, 4 bytes per (fold, image)) plus, summed
+ * over the images, out_h x out_w bytes (the label maps) and 24 bytes per output row and column of an image that resamples + 40 per image.
+ * Synchronous: ONE stream synchronise per call, then ts2d_engine_check for every fold; a failure is reported as "fold <f>: <message>".
+ * (Added under ABI 9: new symbols only, no existing signature or structure changes, so ts2d_abi_version() stays 9.) */
+typedef struct {
+    int32_t  src_y, src_x, src_h, src_w;   /* rectangle of the aggregated [K, Hp, Wp] logits that is the prediction (un-padded) */
+    int32_t  out_h, out_w;                 /* extent after resampling back */
+    uint8_t* label_u8;                     /* host [out_h, out_w] */
+} ts2d_tiled_labelmap;
+
+int ts2d_ensemble_predict_tiled_labelmap(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_labelmap* labelmaps,
+                                         int n_images, int patch_h, int patch_w, int mirror_mask, const uint16_t* gaussian_f16, int full_batch);
+
+/* The label-map kernel of ts2d_ensemble_predict_tiled_labelmap on half planes the CALLER supplies (so that it can be tested on values no
+ * network produces: ties, signed zeros, subnormals, infinities, NaN): logits_f16 host [K, H, W] half bits, rect = {src_y, src_x, src_h,
+ * src_w} inside [H, W], label_u8 host [out_h, out_w].  Same arithmetic, same comparator, same identity rule.  Host pointers in and out,
+ * synchronous, scratch of the call's own, freed on every path.  TS2D_ERR_INVALID, by name, before any device work: null pointers, K
+ * outside 1 ... 256, a non-positive extent or 2^31 or more elements, a rectangle that is empty or leaves the planes, a bad output extent.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+int ts2d_labelmap_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
+                              uint8_t* label_u8);
+
 /* Blend order of ts2d_engine_predict_tiled (upstream `prediction *= gaussian; predicted_logits[sl] += prediction` with
  * float16 `predicted_logits`; reached from ts2d/core/inference/prediction_worker.py:209):
  *   TS2D_TILE_F32 (default) the reference's CPU path (nnu.py:161-163: device=cpu when torch.cuda.is_available() is false - no autocast): the tile prediction is

@@ -39,9 +39,15 @@ class TiledExport(ctypes.Structure):
                 ('out_h', ctypes.c_int32), ('out_w', ctypes.c_int32), ('seg_u8', ctypes.c_void_p), ('logits_f32', ctypes.c_void_p)]
 
 
-# shorthands of the table below: int, void *, size_t, long long, unsigned long long, char *; pointers to a void * and to the two descriptors
+class TiledLabelmap(ctypes.Structure):
+    """``ts2d_tiled_labelmap``: resample-back and argmax of one image of ``ts2d_ensemble_predict_tiled_labelmap``."""
+    _fields_ = [('src_y', ctypes.c_int32), ('src_x', ctypes.c_int32), ('src_h', ctypes.c_int32), ('src_w', ctypes.c_int32),
+                ('out_h', ctypes.c_int32), ('out_w', ctypes.c_int32), ('label_u8', ctypes.c_void_p)]
+
+
+# shorthands of the table below: int, void *, size_t, long long, unsigned long long, char *; pointers to a void * and to the three descriptors
 _I, _P, _Z, _LL, _ULL, _S = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_char_p
-_PP, _TI, _TE = ctypes.POINTER(_P), ctypes.POINTER(TiledImage), ctypes.POINTER(TiledExport)
+_PP, _TI, _TE, _TL = ctypes.POINTER(_P), ctypes.POINTER(TiledImage), ctypes.POINTER(TiledExport), ctypes.POINTER(TiledLabelmap)
 _PROJECT = [_I, _P, _Z, _I, _I, _I, _I, _LL, _LL, _LL, _LL, _P, _P]
 
 # every symbol include/ts2d_engine.h declares: name -> (restype, argtypes)
@@ -58,6 +64,8 @@ SIGNATURES = {
     'ts2d_engine_predict_tiled_batch': (_I, [_P, _TI, _I, _I, _I, _I, _P]),
     'ts2d_engine_predict_tiled_export': (_I, [_P, _TI, _TE, _I, _I, _I, _I, _P, _I]),
     'ts2d_ensemble_predict_tiled_export': (_I, [_PP, _I, _TI, _TE, _I, _I, _I, _I, _P, _I]),
+    'ts2d_ensemble_predict_tiled_labelmap': (_I, [_PP, _I, _TI, _TL, _I, _I, _I, _I, _P, _I]),
+    'ts2d_labelmap_from_logits': (_I, [_I, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32 * 4), _I, _I, _P]),
     'ts2d_project_coronal': (_I, _PROJECT),
     'ts2d_project_coronal_zscore': (_I, _PROJECT + [_P, _P, _P]),
     'ts2d_resample_cubic': (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),

@@ -27,13 +27,14 @@ struct SwSeg {
 };
 static_assert(sizeof(SwSeg) == 64, "SwSeg is copied to the device as bytes");
 
-// ---- the export's order-1 resample (kernels_resample.h)
+// ---- the export's order-1 resample (kernels_resample.h: K planes out; kernels_labelmap.h: the argmax over the K planes, ONE plane out)
 struct RsSeg {
     long long src_off;      // elements from the half outputs to this image's aggregated [K, Hp, Wp] (SwSeg::out_off)
-    long long dst_off;      // elements from the resampled outputs to this image's [K, out_h, out_w] (a multiple of 4)
+    long long dst_off;      // elements from the resampled outputs to this image's [K, out_h, out_w] (a multiple of 4); label map: [out_h, out_w]
     int Hp, Wp;
     int out_h, out_w;
     int tap0;               // its taps: rows at taps[tap0 ... tap0 + out_h), columns at taps[tap0 + out_h ... tap0 + out_h + out_w)
+                            // label map only: -1 = output extent == source rectangle, no taps - src_off then points at the rectangle's first sample
     unsigned block0;        // first block of the image in the launch
 };
 static_assert(sizeof(RsSeg) == 40, "RsSeg is copied to the device as bytes");

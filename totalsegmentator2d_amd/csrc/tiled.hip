@@ -1,9 +1,11 @@
 // The sliding window of libts2d_engine.so: tile gather, aggregation, the mean of an ensemble's folds and the export's resample-back, around
-// the engine's forward (engine.hip: reserve_checked, run_forward).  The C entries ts2d_engine_predict_tiled* and ts2d_ensemble_predict_tiled_export.
+// the engine's forward (engine.hip: reserve_checked, run_forward).  The C entries ts2d_engine_predict_tiled*, ts2d_ensemble_predict_tiled_export,
+// ts2d_ensemble_predict_tiled_labelmap and ts2d_labelmap_from_logits.
 #include "engine_internal.h"
 #include "kernels_sw.h"
 #include "kernels_fold.h"
 #include "kernels_resample.h"
+#include "kernels_labelmap.h"
 
 #include <string>
 #include <vector>
@@ -31,12 +33,14 @@ int name_fold(int rc, bool name_folds, int f) {
 // the FIRST engine's stream and in its scratch - the chunk loop once per fold, sw_aggregate into the fold's own half slot and inf
 // flags, then ONE sw_fold_mean (kernels_fold.h) into slot 0, on which the tail below runs as it does on a single fold's logits.  Only
 // the half slots and the flags exist F times.  `name_folds`: a fold's failed reserve or result check is reported as "fold <f>: ...".
-int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images,
-                       int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, bool full, bool name_images, bool name_folds,
-                       const char* entry) {
+// `labelmap` (ts2d_ensemble_predict_tiled_labelmap): `exports` carry the label-map descriptors (seg_u8 = label_u8) - behind the last
+// aggregate (or the mean) ONE sw_labelmap launch (kernels_labelmap.h) in the place of sw_resample_threshold: ONE uint8 plane per image.
+int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap,
+                       int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, bool full, bool name_images,
+                       bool name_folds, const char* entry) {
     ts2d_engine* e = engines[0];
     SwPlan pl;
-    TRY(plan_tiled(e, F, images, exports, n_images, ph, pw, mirror_mask, name_images, entry, &pl));
+    TRY(plan_tiled(e, F, images, exports, labelmap, n_images, ph, pw, mirror_mask, name_images, entry, &pl));
     const int C = e->arch.input_channels, K = e->arch.num_classes, V = pl.V;
     for (int f = 0; f < F; ++f) TRY(name_fold(reserve_checked(engines[f], pl.cap_rows, ph, pw, full), name_folds, f));
     HIP_TRY(hipSetDevice(e->device));
@@ -86,7 +90,13 @@ int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* ima
         HIP_TRY(hipGetLastError());
     }
     uint8_t* d_rs8 = pl.any_rs8 ? reinterpret_cast<uint8_t*>(b + pl.o_rs8) : nullptr; float* d_rs32 = pl.any_rs32 ? reinterpret_cast<float*>(b + pl.o_rs32) : nullptr;
-    if (exports) {
+    if (labelmap) {
+        hipLaunchKernelGGL(sw_labelmap, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
+                           n_images, K, reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps), d_rs8);
+        HIP_TRY(hipGetLastError());
+        for (int i = 0; i < n_images; ++i)
+            HIP_TRY(hipMemcpyAsync(exports[i].seg_u8, d_rs8 + pl.rsegs[i].dst_off, (size_t)exports[i].out_h * exports[i].out_w, hipMemcpyDeviceToHost, st));
+    } else if (exports) {
         hipLaunchKernelGGL(sw_resample_threshold, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
                            n_images, K, reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps), d_rs8, d_rs32, kSigmoidHalfThreshold);
         HIP_TRY(hipGetLastError());
@@ -120,49 +130,15 @@ int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* ima
     return TS2D_OK;
 }
 
-}  // namespace
-#pragma GCC visibility pop
-
-extern "C" {
-
-int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp, int ph, int pw, int n_tiles,
-                              const int32_t* tile_y, const int32_t* tile_x, int mirror_mask, const uint16_t* gaussian_f16,
-                              uint16_t* logits_f16, uint8_t* seg_u8) {
-    if (!e || !image || !tile_y || !tile_x) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: null argument");
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
-    if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
-    ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
-    return predict_tiled_impl(&e, 1, &one, nullptr, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
-}
-
-int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
-                                    const uint16_t* gaussian_f16) {
-    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: null engine");
-    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
-    if (n_images == 0) return TS2D_OK;
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
-    return predict_tiled_impl(&e, 1, images, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
-}
-
-int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
-                                     int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
-    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: null engine");
-    if (n_images < 0 || (n_images > 0 && !(images && exports)))
-        return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: %d images at a null pointer", n_images);
-    if (n_images == 0) return TS2D_OK;
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_export: weights not loaded");
-    return predict_tiled_impl(&e, 1, images, exports, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
-                              "ts2d_engine_predict_tiled_export");
-}
-
-int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_export* exports,
-                                       int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
-    static const char* entry = "ts2d_ensemble_predict_tiled_export";
+// what the ensemble entries refuse alike before any device work: the handles, the image array, folds that differ where they must agree.
+// *todo: the images to run (0: the call returns TS2D_OK and does nothing)
+int check_folds(const char* entry, ts2d_engine* const* engines, int n_engines, const ts2d_tiled_image* images, int n_images, int* todo) {
     if (!engines) return fail(TS2D_ERR_INVALID, "%s: %d engines at a null pointer", entry, n_engines);
     if (n_engines < 1 || n_engines > kMaxFolds) return fail(TS2D_ERR_INVALID, "%s: n_engines = %d is outside 1..%d", entry, n_engines, kMaxFolds);
     for (int f = 0; f < n_engines; ++f)
         if (!engines[f]) return fail(TS2D_ERR_INVALID, "%s: engine %d is null", entry, f);
     if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
+    *todo = n_images;
     if (n_images == 0) return TS2D_OK;
     const ts2d_engine* e0 = engines[0];
     for (int f = 0; f < n_engines; ++f) {
@@ -178,8 +154,101 @@ int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engine
         if (e->tile_half != e0->tile_half)
             return fail(TS2D_ERR_INVALID, "%s: fold %d blends with tile dtype %d, fold 0 with %d", entry, f, e->tile_half, e0->tile_half);
     }
-    return predict_tiled_impl(engines, n_engines, images, exports, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
+    return TS2D_OK;
+}
+
+}  // namespace
+#pragma GCC visibility pop
+
+extern "C" {
+
+int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp, int ph, int pw, int n_tiles,
+                              const int32_t* tile_y, const int32_t* tile_x, int mirror_mask, const uint16_t* gaussian_f16,
+                              uint16_t* logits_f16, uint8_t* seg_u8) {
+    if (!e || !image || !tile_y || !tile_x) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: null argument");
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
+    if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
+    ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
+    return predict_tiled_impl(&e, 1, &one, nullptr, false, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
+}
+
+int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
+                                    const uint16_t* gaussian_f16) {
+    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: null engine");
+    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
+    if (n_images == 0) return TS2D_OK;
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
+    return predict_tiled_impl(&e, 1, images, nullptr, false, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
+}
+
+int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
+                                     int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
+    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: null engine");
+    if (n_images < 0 || (n_images > 0 && !(images && exports)))
+        return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: %d images at a null pointer", n_images);
+    if (n_images == 0) return TS2D_OK;
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_export: weights not loaded");
+    return predict_tiled_impl(&e, 1, images, exports, false, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
+                              "ts2d_engine_predict_tiled_export");
+}
+
+int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_export* exports,
+                                       int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
+    static const char* entry = "ts2d_ensemble_predict_tiled_export";
+    int todo = 0;
+    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    if (!todo) return TS2D_OK;
+    return predict_tiled_impl(engines, n_engines, images, exports, false, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
                               true, true, entry);
+}
+
+int ts2d_ensemble_predict_tiled_labelmap(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_labelmap* labelmaps,
+                                         int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
+    static const char* entry = "ts2d_ensemble_predict_tiled_labelmap";
+    int todo = 0;
+    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    if (!todo) return TS2D_OK;
+    if (!labelmaps) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
+    std::vector<ts2d_tiled_export> ex((size_t)n_images);      // the geometry of an export, ONE uint8 output
+    for (int i = 0; i < n_images; ++i) {
+        const ts2d_tiled_labelmap& lm = labelmaps[i];
+        ex[i] = ts2d_tiled_export{lm.src_y, lm.src_x, lm.src_h, lm.src_w, lm.out_h, lm.out_w, lm.label_u8, nullptr};
+    }
+    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, n_images, ph, pw, mirror_mask, gaussian_f16,
+                              full_batch ? kFullBatch : kBySize, true, true, entry);
+}
+
+int ts2d_labelmap_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
+                              uint8_t* label_u8) {
+    static const char* entry = "ts2d_labelmap_from_logits";
+    if (!logits_f16 || !rect || !label_u8) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
+    if (K < 1 || K > 256) return fail(TS2D_ERR_INVALID, "%s: %d heads outside 1 ... 256", entry, K);
+    if (H < 1 || W < 1 || (long long)K * H * W >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: bad extent %d x %d x %d (2^31 elements at most)", entry, K, H, W);
+    const ts2d_tiled_export ex{rect[0], rect[1], rect[2], rect[3], out_h, out_w, label_u8, nullptr};
+    if (ex.src_h < 1 || ex.src_w < 1 || ex.src_y < 0 || ex.src_x < 0 || ex.src_h > H - ex.src_y || ex.src_w > W - ex.src_x)
+        return fail(TS2D_ERR_INVALID, "%s: source rectangle %dx%d at (%d,%d) is empty or leaves the %dx%d image", entry, ex.src_h, ex.src_w, ex.src_y,
+                    ex.src_x, H, W);
+    if (out_h < 1 || out_w < 1) return fail(TS2D_ERR_INVALID, "%s: bad output extent %dx%d", entry, out_h, out_w);
+    if ((long long)out_h * out_w >= (1LL << 31) || (long long)out_h + out_w >= (1LL << 26))
+        return fail(TS2D_ERR_INVALID, "%s: %dx%d exceeds 2^31 output elements or 2^26 output rows + columns", entry, out_h, out_w);
+    std::vector<RsSeg> segs; std::vector<RsTap> rtaps;
+    long long blocks = 0, elems = 0;
+    rs_plan_segment(true, K, H, W, ex, 0, &segs, &rtaps, &blocks, &elems);
+    if (blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the labelmap exceeds 2^31 blocks", entry);
+    HIP_TRY(hipSetDevice(device));
+    // [segment | taps | half planes | label map]
+    const size_t n_src = (size_t)K * H * W, n_dst = (size_t)out_h * out_w;
+    const size_t o_taps = align_up(sizeof(RsSeg), 8), o_src = align_up(o_taps + rtaps.size() * sizeof(RsTap), 256), o_dst = align_up(o_src + n_src * 2, 256);
+    DevMem d;
+    HIP_TRY(d.alloc(o_dst + n_dst));
+    HIP_TRY(hipMemcpy(d.as<char>(), segs.data(), sizeof(RsSeg), hipMemcpyHostToDevice));
+    if (!rtaps.empty()) HIP_TRY(hipMemcpy(d.as<char>(o_taps), rtaps.data(), rtaps.size() * sizeof(RsTap), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_src), logits_f16, n_src * 2, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(sw_labelmap, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(), 1, K,
+                       d.as<const RsTap>(o_taps), d.as<uint8_t>(o_dst));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(label_u8, d.as<uint8_t>(o_dst), n_dst, hipMemcpyDeviceToHost));
+    return TS2D_OK;
 }
 
 int ts2d_engine_tiled_inf_flag(const ts2d_engine* e) { return e ? (e->tiled_inf != 0) : 0; }

@@ -32,9 +32,11 @@ void rs_axis_taps(int n_in, int n_out, int origin, RsTap* t) {
 }
 
 // every image (and its export descriptor) on its own; the totals that bound the tables
-int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
-                 bool name_images, const char* entry, SwPlan* pl) {
+// `labelmap`: the descriptors are those of a label-map call (ONE output plane per image: seg_u8 is its label_u8) and are named so
+int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, int n_images, int ph,
+                 int pw, bool name_images, const char* entry, SwPlan* pl) {
     long long n_taps_all = 0;
+    const char* what = labelmap ? "labelmap" : "export";
     pl->any16 = F > 1;      // (the mean is taken over the half buffers)
     for (int i = 0; i < n_images; ++i) {
         const ts2d_tiled_image& im = images[i];
@@ -53,15 +55,15 @@ int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d
         pl->any16 |= im.logits_f16 != nullptr; pl->anyseg |= im.seg_u8 != nullptr;
         if (!exports) continue;
         const ts2d_tiled_export& ex = exports[i];
-        if (!ex.seg_u8 && !ex.logits_f32) return fail(TS2D_ERR_INVALID, "%sexport: both outputs are null", pre);
+        if (!ex.seg_u8 && !ex.logits_f32) return fail(TS2D_ERR_INVALID, labelmap ? "%s%s: the output is null" : "%s%s: both outputs are null", pre, what);
         if (ex.src_h < 1 || ex.src_w < 1 || ex.src_y < 0 || ex.src_x < 0 || ex.src_h > im.Hp - ex.src_y || ex.src_w > im.Wp - ex.src_x)
-            return fail(TS2D_ERR_INVALID, "%sexport: source rectangle %dx%d at (%d,%d) is empty or leaves the %dx%d image", pre, ex.src_h, ex.src_w,
+            return fail(TS2D_ERR_INVALID, "%s%s: source rectangle %dx%d at (%d,%d) is empty or leaves the %dx%d image", pre, what, ex.src_h, ex.src_w,
                         ex.src_y, ex.src_x, im.Hp, im.Wp);
-        if (ex.out_h < 1 || ex.out_w < 1) return fail(TS2D_ERR_INVALID, "%sexport: bad output extent %dx%d", pre, ex.out_h, ex.out_w);
-        if ((long long)K * ex.out_h * ex.out_w >= (1LL << 31))
-            return fail(TS2D_ERR_INVALID, "%sexport: %dx%d exceeds 2^31 output elements", pre, ex.out_h, ex.out_w);
+        if (ex.out_h < 1 || ex.out_w < 1) return fail(TS2D_ERR_INVALID, "%s%s: bad output extent %dx%d", pre, what, ex.out_h, ex.out_w);
+        if ((long long)(labelmap ? 1 : K) * ex.out_h * ex.out_w >= (1LL << 31))
+            return fail(TS2D_ERR_INVALID, "%s%s: %dx%d exceeds 2^31 output elements", pre, what, ex.out_h, ex.out_w);
         n_taps_all += (long long)ex.out_h + ex.out_w;         // (each < 2^31 by the check above; bounded before any table is allocated)
-        if (n_taps_all >= (1LL << 26)) return fail(TS2D_ERR_INVALID, "%sexport: more than 2^26 output rows + columns in one call", pre);
+        if (n_taps_all >= (1LL << 26)) return fail(TS2D_ERR_INVALID, "%s%s: more than 2^26 output rows + columns in one call", pre, what);
         pl->any16 = true; pl->any_rs8 |= ex.seg_u8 != nullptr; pl->any_rs32 |= ex.logits_f32 != nullptr;
     }
     if (pl->n_tiles_all * pl->V >= (1LL << 28)) return fail(TS2D_ERR_INVALID, "%s: %lld network rows in one call", entry, pl->n_tiles_all * pl->V);
@@ -116,30 +118,40 @@ int pack_rows(int F, int C, int K, const ts2d_tiled_image* images, int n_images,
 
 // The export: one segment per image (its half logits are segs' out_off), the taps of its rows then of its columns.
 // rs_elems: elements of the resampled outputs.
-int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, const char* entry, SwPlan* pl,
-                std::vector<RsTap>* rtaps, long long* rs_elems) {
+int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, int n_images, const char* entry,
+                SwPlan* pl, std::vector<RsTap>* rtaps, long long* rs_elems) {
     long long oo = 0;
     for (int i = 0; i < n_images; ++i) {
-        const ts2d_tiled_image& im = images[i]; const ts2d_tiled_export& ex = exports[i];
-        RsSeg rs{};
-        rs.src_off = oo; rs.dst_off = *rs_elems; rs.Hp = im.Hp; rs.Wp = im.Wp; rs.out_h = ex.out_h; rs.out_w = ex.out_w;
-        rs.tap0 = (int)rtaps->size(); rs.block0 = (unsigned)pl->rs_blocks;
-        pl->rsegs.push_back(rs);
-        rtaps->resize(rtaps->size() + ex.out_h + ex.out_w);
-        rs_axis_taps(ex.src_h, ex.out_h, ex.src_y, rtaps->data() + rs.tap0);
-        rs_axis_taps(ex.src_w, ex.out_w, ex.src_x, rtaps->data() + rs.tap0 + ex.out_h);
-        pl->rs_blocks += blocks_of((long long)K * ex.out_h * ((ex.out_w + 3) / 4));
-        *rs_elems += (long long)align_up((size_t)K * ex.out_h * ex.out_w, 256);
-        oo += (long long)align_up((size_t)K * im.Hp * im.Wp, 256);
+        rs_plan_segment(labelmap, K, images[i].Hp, images[i].Wp, exports[i], oo, &pl->rsegs, rtaps, &pl->rs_blocks, rs_elems);
+        oo += (long long)align_up((size_t)K * images[i].Hp * images[i].Wp, 256);
     }
-    if (pl->rs_blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the export exceeds 2^31 blocks", entry);
+    if (pl->rs_blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the %s exceeds 2^31 blocks", entry, labelmap ? "labelmap" : "export");
     return TS2D_OK;
 }
 
 }  // namespace
 
-int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
-               int mirror_mask, bool name_images, const char* entry, SwPlan* pl) {
+void rs_plan_segment(bool labelmap, int K, int Hp, int Wp, const ts2d_tiled_export& ex, long long src_off, std::vector<RsSeg>* rsegs,
+                     std::vector<RsTap>* rtaps, long long* blocks, long long* rs_elems) {
+    const int planes = labelmap ? 1 : K;          // of the output: the label map is ONE plane, its lanes walk the K source planes
+    RsSeg rs{};
+    rs.src_off = src_off; rs.dst_off = *rs_elems; rs.Hp = Hp; rs.Wp = Wp; rs.out_h = ex.out_h; rs.out_w = ex.out_w;
+    rs.block0 = (unsigned)*blocks;
+    if (labelmap && ex.out_h == ex.src_h && ex.out_w == ex.src_w) {      // the host route does not resample then: no taps, no weights
+        rs.tap0 = -1; rs.src_off += (long long)ex.src_y * Wp + ex.src_x;
+    } else {
+        rs.tap0 = (int)rtaps->size();
+        rtaps->resize(rtaps->size() + ex.out_h + ex.out_w);
+        rs_axis_taps(ex.src_h, ex.out_h, ex.src_y, rtaps->data() + rs.tap0);
+        rs_axis_taps(ex.src_w, ex.out_w, ex.src_x, rtaps->data() + rs.tap0 + ex.out_h);
+    }
+    rsegs->push_back(rs);
+    *blocks += blocks_of((long long)planes * ex.out_h * ((ex.out_w + 3) / 4));
+    *rs_elems += (long long)align_up((size_t)planes * ex.out_h * ex.out_w, 256);
+}
+
+int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, int n_images,
+               int ph, int pw, int mirror_mask, bool name_images, const char* entry, SwPlan* pl) {
     if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "%s: bad patch %dx%d", entry, ph, pw);
     const int C = e->arch.input_channels, K = e->arch.num_classes;
     int vflip[4] = {0, 0, 0, 0};
@@ -149,9 +161,9 @@ int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, cons
     pl->vflips = vflip[0] | (vflip[1] << 8) | (vflip[2] << 16) | (vflip[3] << 24);
     long long img_floats = 0, log_rows = 0, rs_elems = 0;
     std::vector<RsTap> rtaps;
-    TRY(check_images(F, C, K, images, exports, n_images, ph, pw, name_images, entry, pl));
+    TRY(check_images(F, C, K, images, exports, labelmap, n_images, ph, pw, name_images, entry, pl));
     TRY(pack_rows(F, C, K, images, n_images, ph, pw, entry, pl, &img_floats, &log_rows));
-    if (exports) TRY(plan_export(K, images, exports, n_images, entry, pl, &rtaps, &rs_elems));
+    if (exports) TRY(plan_export(K, images, exports, labelmap, n_images, entry, pl, &rtaps, &rs_elems));
     // ---- the descriptor table and every tile origin
     const size_t n_tiles = (size_t)pl->n_tiles_all;
     pl->tab_segs = pl->segs.size() * sizeof(SwSeg); pl->tab_rsegs = align_up(pl->tab_segs + 2 * n_tiles * 4, 8);

@@ -259,11 +259,13 @@ class Engine:
         del keep
         return outs
 
-    def _tiled_args(self, what, images, tiles, exports, mirror_axes, gaussian, want_seg, want_f32, want_logits, want_padded_seg):
+    def _tiled_args(self, what, images, tiles, exports, mirror_axes, gaussian, want_seg, want_f32, want_logits, want_padded_seg,
+                    labelmap: bool = False):
         """Argument preparation of every tiled call (`what` names the calling method in a message): the ``TiledImage`` array, the
         ``TiledExport`` array (None without ``exports``: no resample-back), the mirror mask, the address of the half gaussian (or None),
         the arrays all of these point into - they must outlive the call - and the output lists ``(seg, f32, logits, padded_seg)`` the
-        call fills, each None unless asked for.  ``what`` None is the one image of :meth:`predict_tiled`: its messages carry no
+        call fills, each None unless asked for.  ``labelmap``: the descriptors are ``TiledLabelmap`` and ``seg`` holds ONE uint8 plane
+        [out_h,out_w] per image, the label map.  ``what`` None is the one image of :meth:`predict_tiled`: its messages carry no
         ``image i: `` and everything but the channel count is left to the library (or to the unpacking of the shape) to refuse."""
         one = what is None
         if len(images) != len(tiles) or (exports is not None and len(exports) != len(images)):
@@ -278,7 +280,7 @@ class Engine:
         K = self.arch.num_classes
         keep = []                    # every array the descriptors point into stays alive until the call returns
         n = max(len(images), 1)
-        desc, exd = (_lib.TiledImage * n)(), (None if exports is None else (_lib.TiledExport * n)())
+        desc, exd = (_lib.TiledImage * n)(), (None if exports is None else ((_lib.TiledLabelmap if labelmap else _lib.TiledExport) * n)())
         seg, f32, out16, pseg = [], [], [], []
         for i, (image, tl) in enumerate(zip(images, tiles)):
             at = '' if one else f'image {i}: '
@@ -301,11 +303,14 @@ class Engine:
             if exports is None:
                 continue
             sy, sx, sh, sw_, oh, ow = (int(v) for v in exports[i])
-            shape = (K, max(oh, 0), max(ow, 0))          # (a bad extent is the library's to reject, by name)
+            shape = (() if labelmap else (K,)) + (max(oh, 0), max(ow, 0))          # (a bad extent is the library's to reject, by name)
             seg.append(np.empty(shape, dtype=np.uint8) if want_seg else None)
             f32.append(np.empty(shape, dtype=np.float32) if want_f32 else None)
             x = exd[i]
             x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w = sy, sx, sh, sw_, oh, ow
+            if labelmap:
+                x.label_u8 = seg[i].ctypes.data
+                continue
             x.seg_u8 = seg[i].ctypes.data if want_seg else None
             x.logits_f32 = f32[i].ctypes.data if want_f32 else None
         mask = 0
@@ -409,6 +414,42 @@ def predict_tiled_export_ensemble(engines, images, patch, tiles, exports, mirror
     _read_tiled_inf(engines, desc, len(images), engine_flags=True)
     del keep
     return outs
+
+
+def predict_tiled_labelmap_ensemble(engines, images, patch, tiles, rects, mirror_axes=None, gaussian: Optional[np.ndarray] = None,
+                                    want_logits: bool = False, full_batch: bool = True):
+    """:func:`predict_tiled_export_ensemble` for a LABEL-MAP model (C-ABI ts2d_ensemble_predict_tiled_labelmap): the same sliding window
+    per fold and the same mean (one engine: no mean), then per image the resample-back of the half logits to its extent and the argmax
+    over the heads on the device (csrc/kernels_labelmap.h).  rects: one ``(src_y, src_x, src_h, src_w, out_h, out_w)`` per image.
+    Returns ``(labels, logits)``: lists of uint8 [out_h,out_w] - ``export.labelmap_statement`` of the half logits, byte for byte - and
+    of float16 [K,Hp,Wp] (those logits; None unless asked for).  Sets the inf flags as :func:`predict_tiled_export_ensemble` does."""
+    engines = list(engines)
+    if not engines:
+        raise RuntimeError("predict_tiled_labelmap_ensemble: no engines")
+    if rects is None:
+        raise RuntimeError("predict_tiled_labelmap_ensemble: the label maps need their rectangles and extents")
+    desc, lmd, mask, g, keep, outs = engines[0]._tiled_args('predict_tiled_labelmap_ensemble', images, tiles, rects, mirror_axes, gaussian,
+                                                            True, False, want_logits, False, labelmap=True)
+    handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
+    _lib.check(engines[0].lib.ts2d_ensemble_predict_tiled_labelmap(handles, len(engines), desc, lmd, len(images), int(patch[0]), int(patch[1]),
+                                                                   mask, g, int(bool(full_batch))), 'ts2d_ensemble_predict_tiled_labelmap')
+    _read_tiled_inf(engines, desc, len(images), engine_flags=True)
+    del keep
+    return outs[0], outs[2]
+
+
+def labelmap_from_logits(logits_f16: np.ndarray, rect, out_hw, device: int = 0) -> np.ndarray:
+    """The label-map kernel on half planes of the caller's (C-ABI ts2d_labelmap_from_logits): float16 [K,H,W], ``rect = (y, x, h, w)``
+    inside it, resampled to ``out_hw`` and decided over the heads -> uint8 [out_h,out_w] = ``export.labelmap_statement``."""
+    lg = np.ascontiguousarray(logits_f16, dtype=np.float16)
+    if lg.ndim != 3:
+        raise RuntimeError(f"expected [K,H,W], found shape {lg.shape}")
+    oh, ow = (int(v) for v in out_hw)
+    out = np.empty((max(oh, 0), max(ow, 0)), dtype=np.uint8)
+    r = (ctypes.c_int32 * 4)(*[int(v) for v in rect])
+    _lib.check(_lib.load().ts2d_labelmap_from_logits(int(device), lg.ctypes.data, lg.shape[0], lg.shape[1], lg.shape[2], ctypes.byref(r), oh, ow,
+                                                     out.ctypes.data), 'ts2d_labelmap_from_logits')
+    return out
 
 
 def _read_tiled_inf(engines, desc, n_images, engine_flags: bool):

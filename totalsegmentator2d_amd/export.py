@@ -23,6 +23,24 @@ def needs_logits(properties: dict, shape_khw) -> bool:
     return tuple(properties.get('shape_after_cropping_and_before_resampling', tuple(shape_khw))) != tuple(shape_khw)
 
 
+def labelmap_statement(logits_f16, rect, out_hw) -> np.ndarray:
+    """The numpy statement of the device label-map export (csrc/kernels_labelmap.h; C-ABI ts2d_ensemble_predict_tiled_labelmap and
+    ts2d_labelmap_from_logits): the rectangle ``rect = (y, x, h, w)`` of the aggregated half logits [K, Hp, Wp] widened to float32,
+    every plane resampled to ``out_hw`` by :func:`preprocess.resize_linear_f64` (bit for bit scipy's order-1 zoom, the export's
+    ``resampling_fn_probabilities``) - NOT where ``out_hw == (h, w)``: the host route does not resample there, so an infinite logit stays
+    infinite instead of meeting a zero weight - and numpy's argmax over the heads: the first index of the maximum, +0 == -0, the first
+    NaN wins.  uint8 [out_h, out_w].  It is the host route of the export byte for byte (tests/test_labelmap_cpu.py) wherever no SOURCE sample
+    is NaN: skimage's clip to the plane's [min, max] makes such a plane NaN as a whole there; the engine refuses NaN logits long before
+    the export (ts2d_engine_check), so that no such plane arrives."""
+    from .preprocess import resize_linear_f64
+    y, x, h, w = (int(v) for v in rect)
+    out_hw = tuple(int(v) for v in out_hw)
+    lg = np.asarray(logits_f16)[:, y:y + h, x:x + w].astype(np.float32)
+    if out_hw != (h, w):
+        lg = np.stack([resize_linear_f64(pl, out_hw) for pl in lg])
+    return lg.argmax(0).astype(np.uint8)
+
+
 def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties: dict, multilabel: bool = True,
                                                                 transpose_backward=(0, 1, 2)) -> np.ndarray:
     """[K, Z, H, W] logits (any float dtype) -> uint8 segmentation in the ORIGINAL (pre-crop) array shape:
@@ -50,7 +68,13 @@ def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properti
         out = np.zeros((lg.shape[0],) + shape0, dtype=np.uint8)
         out[(slice(None),) + sl] = seg
         return out.transpose([0] + [i + 1 for i in transpose_backward])
-    seg = lg.astype(np.float32).argmax(0).astype(np.uint8)
+    if lg.dtype == np.uint8:
+        # already resampled and decided on the device (HIPnnUNetPredictor.predict_labelmap_from_preprocessed_data): ONE plane of labels
+        if lg.shape[0] != 1:
+            raise ValueError(f"a uint8 prediction of a label-map model is one plane of labels, found {lg.shape[0]}")
+        seg = lg[0]
+    else:
+        seg = lg.astype(np.float32).argmax(0).astype(np.uint8)
     out = np.zeros(shape0, dtype=np.uint8)
     out[sl] = seg
     return out.transpose(list(transpose_backward))

@@ -39,6 +39,7 @@ class HIPModel:
         self.colors = self._param.get('nnu.result.colors')
         self._dataset_json: Optional[dict] = None
         self.device_threshold = True     # thresholded segmentation straight from the device where the export needs no logits (_run)
+        self.device_labelmap = True      # a label-map (non-multilabel) model: resample-back and argmax on the device, ONE uint8 plane to the host (_run); the host route's bytes
         self.device_input_resample = True   # order-3 resample of an off-spacing case's input on the device: the same float32 values as scipy, bit for bit (preprocess.resize_cubic_f64)
         self.device_input_normalize = True  # crop box, z-score (and that resample) of a native 2-D input on device-resident planes: the same float32 values as numpy, bit for bit (preprocess.zscore_f32_statement)
         self._discover()
@@ -202,20 +203,21 @@ class HIPModel:
             return False
         return name in params or any(q.kind is q.VAR_KEYWORD for q in params.values())
 
-    def _predict(self, datas, use_seg: bool, batched: bool, out_shapes=None):
+    def _predict(self, datas, use_seg: bool, batched: bool, out_shapes=None, fast: str = 'predict_segmentation_from_preprocessed_data'):
         """Stage 2 of :meth:`_run`, the one stage that differs between :meth:`apply` and :meth:`apply_batch`: ONE predictor batch call
         over ``datas``, or the predictor's single-case methods per input - the reference's duck-typed seam
         (``predict_logits_from_preprocessed_data``, prediction_worker.py:206-209), which a foreign predictor without the batch methods
         serves too.  ``use_seg``: ask for the device-thresholded segmentation first (it answers None when the case needs the logits);
-        ``out_shapes``: per input the extent its export resamples to, or None - passed on only when some input has one."""
+        ``out_shapes``: per input the extent its export resamples to, or None - passed on only when some input has one.  ``fast``: the
+        name of that fast-path method - the segmentation of a multilabel model or the label map of an ordinary one."""
         p = self._predictor
         shapes = out_shapes if out_shapes is not None and any(s is not None for s in out_shapes) else None
         if batched:
-            out = p.predict_segmentation_from_preprocessed_data_batch(datas, **({} if shapes is None else {'out_shapes': shapes})) if use_seg else None
+            out = getattr(p, fast + '_batch')(datas, **({} if shapes is None else {'out_shapes': shapes})) if use_seg else None
             if out is None:
                 out = p.predict_logits_from_preprocessed_data_batch(datas)
         else:
-            out = [p.predict_segmentation_from_preprocessed_data(d, **({} if shapes is None or s is None else {'out_shape': s})) if use_seg else None
+            out = [getattr(p, fast)(d, **({} if shapes is None or s is None else {'out_shape': s})) if use_seg else None
                    for d, s in zip(datas, shapes or [None] * len(datas))]
             out = [p.predict_logits_from_preprocessed_data(d) if o is None else o for d, o in zip(datas, out)]
         return [o.cpu().numpy() if hasattr(o, 'cpu') else o for o in out]
@@ -253,13 +255,21 @@ class HIPModel:
         # plan's) joins with the extent it had before resampling: the device resamples the logits back (order 1) in front of the
         # threshold and the export step receives uint8 planes already in that extent.  The reference's seam
         # (predict_logits_from_preprocessed_data + export_prediction_from_logits) stays as it is and serves every other case
-        can_seg = self.device_threshold and bool(p.dataset_json.get('multilabel', p.dataset_json.get('multiclass', False))) \
-            and hasattr(p, 'predict_segmentation_from_preprocessed_data' + ('_batch' if batched else ''))
+        multilabel = bool(p.dataset_json.get('multilabel', p.dataset_json.get('multiclass', False)))
+        can_seg = self.device_threshold and multilabel and hasattr(p, 'predict_segmentation_from_preprocessed_data' + ('_batch' if batched else ''))
         # (a foreign predictor, or a double of the engine method, that knows the fast path but not its `out_shape(s)` keyword keeps
         #  the host route for resampled cases, as before the device export existed)
         fast_fn = getattr(p, 'predict_segmentation_from_preprocessed_data' + ('_batch' if batched else ''), None)
         can_export = can_seg and self._takes(fast_fn, 'out_shapes' if batched else 'out_shape') \
             and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, 'out_shapes'))
+        # a label-map model (the ordinary nnU-Net head): the same two host steps - resample-back, then the argmax over the heads - on the
+        # device, ONE uint8 plane per case to the host; the export step receives it as the decided label map.  Only a predictor that has
+        # the method (and, where it is a double of the engine method, its `labelmap` keyword) takes this route
+        lm_name = 'predict_labelmap_from_preprocessed_data'
+        lm_fn = getattr(p, lm_name + ('_batch' if batched else ''), None)
+        can_lm = getattr(self, 'device_labelmap', False) and not multilabel and lm_fn is not None \
+            and self._takes(lm_fn, 'out_shapes' if batched else 'out_shape') \
+            and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, 'labelmap'))
 
         def target(t):
             """The extent the device export resamples case `t` to: None = none needed, False = not a case for it (a stack, a 3-D plan,
@@ -268,13 +278,14 @@ class HIPModel:
             if not needs_logits(t[4], shape):
                 return None
             tgt = tuple(t[4]['shape_after_cropping_and_before_resampling'])
-            return tgt if can_export and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] == 1 else False
-        fast = [t for t in todo if can_seg and target(t) is not False]
+            return tgt if (can_export or can_lm) and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] == 1 else False
+        fast = [t for t in todo if (can_seg or can_lm) and target(t) is not False]
         for group, use_seg in ((fast, True), ([t for t in todo if not any(t is f for f in fast)], False)):
             if not group:
                 continue
             try:
-                out = self._predict([t[3] for t in group], use_seg, batched, [target(t) for t in group] if use_seg else None)
+                out = self._predict([t[3] for t in group], use_seg, batched, [target(t) for t in group] if use_seg else None,
+                                    **({'fast': lm_name} if can_lm else {}))
             except Exception as ex:
                 names = ', '.join(t[0] for t in group)
                 m = re.match(r'input (\d+): ', str(ex))          # the predictor names the offending input of the batch by index

@@ -181,7 +181,8 @@ class HIPnnUNetPredictor:
     _INF_MESSAGE = ('Encountered inf in predicted array. Aborting... If this problem persists, reduce '
                     'value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32')
 
-    def _sliding_window_batch(self, list_of_data, fold: Optional[int] = 0, want_seg: bool = False, one_call: bool = True, out_shapes=None):
+    def _sliding_window_batch(self, list_of_data, fold: Optional[int] = 0, want_seg: bool = False, one_call: bool = True, out_shapes=None,
+                              labelmap: bool = False):
         """One fold, N inputs [C,Z,H,W]: pad, tile, tiles x mirror variants through the engine, upstream's fp16 Gaussian aggregation
         on the device.  Every z slice of every input is one image.  ``one_call``: all images in ONE engine call (C-ABI
         ts2d_engine_predict_tiled_batch: the network takes the full-batch dispatch, an input's bytes do not depend on its batch-mates,
@@ -195,16 +196,31 @@ class HIPnnUNetPredictor:
         the same sliding window, the mean of the folds' float16 logits on the device (:func:`fold_mean_f16`, bit for bit), and every
         output is that of the mean; ``want_seg`` always goes through the export (at an input's own extent the taps are 1 / 0).
         ``one_call`` False there: the size-dependent dispatch, so the bytes are those of :meth:`predict_logits_from_preprocessed_data`.
+        ``labelmap`` (a label-map model; single-slice inputs): ONE engine call (C-ABI ts2d_ensemble_predict_tiled_labelmap) over fold
+        ``fold`` or, with None, every fold and their mean; the device resamples every input's logits to its extent of ``out_shapes``
+        (None = its own: no resampling) and takes the argmax over the heads there (:func:`export.labelmap_statement`, byte for byte):
+        uint8 [1,1,h,w] per input.
         (The one method that touches the engine, under the name the test infrastructure overrides: tests/batch_util.py replaces it, and
         tests/host_predictor.py predict_sliding_window_return_logits, with the host restatement.)"""
         patch = tuple(self.configuration_manager.patch_size)
         ensemble = fold is None
-        images, tiles, owner, reverts, shapes = self._pad_and_tile(list_of_data, patch, single_slice=ensemble)
+        images, tiles, owner, reverts, shapes = self._pad_and_tile(list_of_data, patch, single_slice=ensemble or labelmap)
         if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
             raise AssertionError('mirror_axes does not match the dimension of the input!')
         g = sw.compute_gaussian(patch) if self.use_gaussian else None
         axes = self.allowed_mirroring_axes if self.use_mirroring else None
         e = None if ensemble else self.engines[fold]
+        if labelmap:
+            from .engine import predict_tiled_labelmap_ensemble
+            rects = self._export_rects(list_of_data, reverts, shapes, out_shapes if out_shapes is not None else [None] * len(list_of_data), True)
+            engines = self.engines if ensemble else [e]
+            planes, inf = [], []
+            for grp in ([range(len(images))] if one_call else [[j] for j in range(len(images))]):
+                planes += predict_tiled_labelmap_ensemble(engines, [images[j] for j in grp], patch, [tiles[j] for j in grp], [rects[j] for j in grp],
+                                                          axes, g, full_batch=one_call)[0]
+                inf += engines[0].last_tiled_inf_per_image
+            self._raise_on_inf(inf, owner, one_call)
+            return [p[None, None] for p in planes]
         if ensemble and want_seg and out_shapes is None:
             out_shapes = [None] * len(list_of_data)
         exports = None if out_shapes is None else self._export_rects(list_of_data, reverts, shapes, out_shapes, want_seg)
@@ -318,6 +334,40 @@ class HIPnnUNetPredictor:
             return None
         kw = {} if hw is None else {'out_shapes': [hw]}
         return self._sliding_window_batch([data], None if ensemble else 0, want_seg=True, one_call=False, **kw)[0]
+
+    def predict_labelmap_from_preprocessed_data(self, data, out_shape=None):
+        """The twin of :meth:`predict_segmentation_from_preprocessed_data` for a LABEL-MAP model (the ordinary nnU-Net head: one head per
+        label, background at 0): the export's order-1 resample-back and the argmax over the heads ON THE DEVICE (kernels_labelmap.h), so
+        that ONE uint8 plane travels to the host instead of K float16 ones.  One z-slice; returns uint8 [1, 1, h, w] - the labels in the
+        extent of ``out_shape`` (the case's ``shape_after_cropping_and_before_resampling``, (h, w) or (1, h, w); None: the preprocessed
+        geometry) - or None when the case keeps the logits route (3-D stacks; a predictor without engines; a bad ``out_shape``).  A fold
+        ensemble runs every fold in one engine call, the mean of the folds in front of the argmax.  The bytes are those of
+        :meth:`predict_logits_from_preprocessed_data` + the host export (``resample_data_to_shape(order=1)`` + ``argmax``)."""
+        data = _to_numpy(data)
+        ensemble = self._device_ensemble()
+        if not (ensemble or len(self.list_of_parameters) == len(self.engines) == 1) or data.ndim != 4 or data.shape[1] != 1:
+            return None
+        hw = self._in_plane(out_shape, data)
+        if hw is False:
+            return None
+        return self._sliding_window_batch([data], None if ensemble else 0, one_call=False, out_shapes=[hw], labelmap=True)[0]
+
+    def predict_labelmap_from_preprocessed_data_batch(self, list_of_data, out_shapes=None):
+        """:meth:`predict_labelmap_from_preprocessed_data` for a list of inputs: uint8 [1,1,h,w] per input from ONE engine call (every
+        fold of an ensemble in it), or None when the predictor keeps the logits route (a fold ensemble without engines), an input is no
+        single z slice or an ``out_shapes`` entry is bad.  ``out_shapes``: one ``out_shape`` (or None) per input."""
+        datas = [_to_numpy(d) for d in list_of_data]
+        ensemble = self._device_ensemble()
+        if not (ensemble or len(self.list_of_parameters) == len(self.engines) == 1) or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
+            return None
+        if not datas:
+            return []
+        if out_shapes is not None and len(out_shapes) != len(datas):
+            return None
+        hws = [self._in_plane(s, d) for s, d in zip(out_shapes, datas)] if out_shapes is not None else [None] * len(datas)
+        if any(hw is False for hw in hws):
+            return None
+        return self._sliding_window_batch(datas, None if ensemble else 0, out_shapes=hws, labelmap=True)
 
     def predict_logits_from_preprocessed_data(self, data):
         """Fold ensemble (upstream: sum over ``list_of_parameters`` then ``/= n``).  Accepts numpy or torch [C,1,H,W];
