@@ -376,7 +376,7 @@ int ts2d_resample_cubic(int device, const float* src, int n_planes, int in_h, in
                         float* dst);
 
 /* nnU-Net's preprocessing of an input that is 2-D when it arrives - an X-ray image, a pre-projected multi-channel image - on planes that
- * stay on the device: crop_to_nonzero, ZScoreNormalization without mask per channel, the resample to the plan spacing (reference flow
+ * stay on the device: crop_to_nonzero, the normalisation of each channel, the resample to the plan spacing (reference flow
  * DefaultPreprocessor.run_case, ts2d/core/inference/prediction_worker.py:194-199).  The planes are uploaded once and downloaded once.
  * Every entry validates its arguments before any device work and names itself in ts2d_last_error, frees its scratch on every path and
  * is synchronous.  (New symbols of ABI 9: nothing that existed changed.) */
@@ -401,6 +401,45 @@ int ts2d_planes_create(int device, const float* src, int n_planes, int h, int w,
  *   nonfinite  set to 1 when a mean, a variance or a normalised sample is not finite (a non-finite sample, or float32 sums that
  *          overflow): the planes are then cropped but NOT a normalisation the caller may use; it drops the handle and runs numpy. */
 int ts2d_planes_crop_zscore(ts2d_planes* p, int32_t box[4], float* stats, int* nonfinite);
+
+/* crop_to_nonzero and ANY of nnU-Net's normalisation schemes per plane (run_case, prediction_worker.py:194-199; nnunetv2's
+ * default_normalization_schemes), in place on the handle - what ts2d_planes_crop_zscore does for the plain z-score, for the cases it does
+ * not take: an ordinary CT model, a plan with use_mask_for_norm, a natural-image model, a channel that is not normalised.
+ *   schemes   [n_planes]: TS2D_NORM_* of each plane.
+ *   params    [n_planes][4] float32, read for TS2D_NORM_CT only: {mean, divisor = float32(max(std, 1e-8)), lower bound, upper bound}, each as
+ *             numpy converts the plan's number for a float32 array.  They must be finite.
+ *   use_mask  [n_planes]: non-zero = a TS2D_NORM_ZSCORE plane takes its statistics over, and is normalised only inside, the non-zero mask
+ *             of the case: the pixels of the box that are non-zero in ANY plane (nnU-Net's `seg >= 0` for a single slice; the hole
+ *             filling of create_nonzero_mask changes nothing there).  Ignored for the other schemes, as nnU-Net ignores it.
+ *   box       as ts2d_planes_crop_zscore returns it; the planes are compacted to it.
+ *   stats     [n_planes][2]: (mean, std) of a z-score plane - of its masked samples with use_mask - and the (subtrahend, divisor) actually
+ *             used otherwise: CT (mean, divisor), Rescale (minimum, divisor), RGB (0, 255), none (0, 1).
+ * Arithmetic contract = the statements of preprocess.py, bit for bit, each bit for bit numpy's (preprocess.normalize_channel):
+ *   TS2D_NORM_ZSCORE     zscore_f32_statement; with use_mask masked_zscore_f32_statement: the sums of ts2d_planes_crop_zscore over
+ *                        plane[mask], a compact copy in row-major order (n_m samples: chunks of 8192, the pairwise tree of the last
+ *                        n_m % 8192), fl32(fl32(x - mean) / max(std, 1e-8)) inside the mask, the sample itself outside.
+ *   TS2D_NORM_CT         ct_f32_statement: x < lo ? lo : x, then x > hi ? hi : x (a sample equal to a bound keeps its sign of zero, a NaN
+ *                        stays NaN), then fl32(fl32(x - mean) / divisor).
+ *   TS2D_NORM_RESCALE01  rescale01_f32_statement: fl32(fl32(x - min) / d) with d = fl32(max - min), or float32(1e-8) if that is larger.
+ *   TS2D_NORM_RGB01      rgb01_f32_statement: fl32(x / 255).
+ *   TS2D_NORM_NONE       the sample itself.
+ * No fused multiply-add, correctly rounded divisions, no atomics on floats, a compaction by integer counts: two calls give the same bits.
+ * The float32 minimum and maximum of each resulting plane stay on the handle: the clip bounds of ts2d_planes_resample_cubic.
+ *   status    0, or TS2D_PLANES_* bits: the planes are then cropped but NOT a result the caller may use; it drops the handle and runs numpy,
+ *             which computes (or raises) what numpy computes of such a case.
+ * TS2D_ERR_INVALID, by name, before any device work: null pointers, a scheme outside TS2D_NORM_*, a non-finite CT parameter. */
+#define TS2D_NORM_ZSCORE 0      /* ZScoreNormalization */
+#define TS2D_NORM_CT 1          /* CTNormalization */
+#define TS2D_NORM_RESCALE01 2   /* RescaleTo01Normalization */
+#define TS2D_NORM_RGB01 3       /* RGBTo01Normalization */
+#define TS2D_NORM_NONE 4        /* NoNormalization */
+#define TS2D_PLANES_NONFINITE 1     /* a statistic, a Rescale bound or a resulting sample is not finite */
+#define TS2D_PLANES_RGB_RANGE 2     /* a TS2D_NORM_RGB01 plane holds a sample outside [0, 255]: upstream raises */
+#define TS2D_PLANES_EMPTY_MASK 4    /* use_mask on an image of zeros: there is nothing to take a mean of */
+#define TS2D_PLANES_ZERO_SIGN 8     /* a TS2D_NORM_RESCALE01 plane whose minimum is -0.0: if it holds +0.0 too, numpy's min() may return
+                                     * either, and the sign of every resulting zero hangs on it */
+int ts2d_planes_crop_normalize(ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask, int32_t box[4],
+                               float* stats, int* status);
 
 /* The order-3 resample of run_case (prediction_worker.py:194-199, a case whose spacing is not the plan's) of every plane of the handle to
  * out_h x out_w, clipped to the bounds ts2d_planes_crop_zscore left: the arithmetic, the limits and the messages of ts2d_resample_cubic.

@@ -71,6 +71,7 @@ SIGNATURES = {
     'ts2d_resample_cubic': (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),
     'ts2d_planes_create': (_I, [_I, _P, _I, _I, _I, _PP]),
     'ts2d_planes_crop_zscore': (_I, [_P, ctypes.POINTER(ctypes.c_int32 * 4), _P, ctypes.POINTER(_I)]),
+    'ts2d_planes_crop_normalize': (_I, [_P, _P, _P, _P, ctypes.POINTER(ctypes.c_int32 * 4), _P, ctypes.POINTER(_I)]),
     'ts2d_planes_resample_cubic': (_I, [_P, _I, _I]),
     'ts2d_planes_extent': (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     'ts2d_planes_download': (_I, [_P, _P]),
@@ -95,8 +96,8 @@ SIGNATURES = {
     'ts2d_engine_destroy': (_I, [_P]),
 }
 SYMBOLS = tuple(SIGNATURES)
-# added under ABI 9 (the cubic resample; the device-resident planes of preprocess.DevicePlanes): a library built before them lacks the
-# symbols, still loads, and the callers keep the host route
+# added under ABI 9 (the cubic resample; the device-resident planes of preprocess.DevicePlanes, ts2d_planes_crop_normalize after the others):
+# a library built before them lacks the symbols, still loads, and the callers keep the host route
 OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_'))
 
 

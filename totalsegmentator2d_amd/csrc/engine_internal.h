@@ -267,6 +267,7 @@ struct RsInPlan {
 int rsin_plan(const char* entry, int n_planes, int in_h, int in_w, int out_h, int out_w, RsInPlan* pl);      // fails if a tap would leave the padded plane
 void prep_leaves(int off, int n, std::vector<PrepLeaf>* out);
 float prep_plane_sum(const float* sums, long long n);
+float prep_rescale_div(float mn, float mx);
 float prep_unkey(int key);
 
 }  // namespace ts2d

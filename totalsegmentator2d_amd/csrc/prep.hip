@@ -1,10 +1,11 @@
 // The input side of libts2d_engine.so, none of which needs an engine: coronal projection + z-score of a volume, the order-3 resample to the
-// plan spacing, and the ts2d_planes handle (crop box, z-score and resample of native 2-D inputs where they lie on the device).
+// plan spacing, and the ts2d_planes handle (crop box, every normalisation scheme of nnU-Net and resample of native 2-D inputs where they lie on the device).
 // The host arithmetic behind them is prep_plan.cpp; every device buffer of a call is a DevMem, so HIP_TRY may return wherever it fails.
 #include "engine_internal.h"
 #include "kernels_project.h"
 #include "kernels_resample_in.h"
 #include "kernels_prep.h"
+#include "kernels_prep_schemes.h"
 
 #include <algorithm>
 #include <cmath>
@@ -27,6 +28,8 @@ namespace {
 
 constexpr int kPrepMaxPlanes = 65535;           // (a grid dimension)
 constexpr long long kPrepMaxSamples = 1ll << 28;
+static_assert(kPrepZScore == TS2D_NORM_ZSCORE && kPrepCT == TS2D_NORM_CT && kPrepRescale01 == TS2D_NORM_RESCALE01 && kPrepRGB01 == TS2D_NORM_RGB01 &&
+              kPrepNone == TS2D_NORM_NONE && kPrepStatusRgbRange == TS2D_PLANES_RGB_RANGE, "the scheme table speaks the C header's numbers");
 
 int project_coronal_impl(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz,
                          long long sy, long long sx, long long base, float* out_max, float* out_mean, float* out_norm, double* out_stats, int* out_box) {
@@ -110,6 +113,78 @@ int rsin_run(const RsInPlan& pl, char* d_scratch, const float* d_src, const floa
     return TS2D_OK;
 }
 
+// crop_to_nonzero of both crop entries: the box of the pixels that are non-zero in any plane, and the planes compacted to it.  d_box: four
+// integers of device scratch.  box = {first row, one past the last row, first column, one past the last column}; the handle's clip bounds are dropped.
+int planes_crop(const char* entry, ts2d_planes* p, int* d_box, int32_t box[4]) {
+    const int n = p->n;
+    int hb[4] = {p->h, -1, p->w, -1};
+    HIP_TRY(hipMemcpy(d_box, hb, sizeof(hb), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(prep_nonzero_box, dim3((unsigned)(((long long)p->h * p->w + 255) / 256)), dim3(256), 0, 0, p->d.as<float>(), n, p->h, p->w, d_box);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(hb, d_box, sizeof(hb), hipMemcpyDeviceToHost));
+    if (hb[1] < 0) { hb[0] = 0; hb[1] = p->h - 1; hb[2] = 0; hb[3] = p->w - 1; }            // nothing but zeros: the whole extent stays
+    if (hb[0] < 0 || hb[1] >= p->h || hb[0] > hb[1] || hb[2] < 0 || hb[3] >= p->w || hb[2] > hb[3])
+        return fail(TS2D_ERR_HIP, "%s: the device returned the box rows %d ... %d, columns %d ... %d of %d x %d", entry, hb[0], hb[1], hb[2], hb[3], p->h, p->w);
+    const int bh = hb[1] - hb[0] + 1, bw = hb[3] - hb[2] + 1;
+    // compaction: the flattened index of the dense [n][bh][bw] buffer is numpy's
+    if (bh != p->h || bw != p->w) {
+        DevMem d_new;
+        HIP_TRY(d_new.alloc((size_t)n * bh * bw * sizeof(float)));
+        for (int c = 0; c < n; ++c)
+            HIP_TRY(hipMemcpy2D(d_new.as<float>() + (size_t)c * bh * bw, (size_t)bw * sizeof(float), p->d.as<float>() + ((size_t)c * p->h + hb[0]) * p->w + hb[2],
+                                (size_t)p->w * sizeof(float), (size_t)bw * sizeof(float), (size_t)bh, hipMemcpyDeviceToDevice));
+        p->d = std::move(d_new); p->h = bh; p->w = bw;
+    }
+    p->has_bounds = false;
+    box[0] = hb[0]; box[1] = hb[1] + 1; box[2] = hb[2]; box[3] = hb[3] + 1;
+    return TS2D_OK;
+}
+
+// The z-score statistics of the planes x [n][N] on the device that `want` selects (null: all): the two sums chunk by chunk on the device, their
+// fold and the float32 mean, variance, square root and divisor here.  norm [n] (also left at d_norm) and stats [n][2] = (mean, std) are
+// written for the selected planes only; *bad is set, and nothing more computed, when a mean or a variance of theirs is not finite.
+// d_leaves: kPrepMaxTailLeaves leaves, d_sums: n * (N / kPrepChunk + kPrepMaxTailLeaves) floats of device scratch.
+int planes_stats(const char* entry, const float* x, long long N, int n, const uint8_t* want, PrepNorm* d_norm, PrepLeaf* d_leaves, float* d_sums,
+                 PrepNorm* norm, float* stats, bool* bad) {
+    const long long n_full = N / kPrepChunk;
+    std::vector<PrepLeaf> leaves;
+    if (N % kPrepChunk) prep_leaves(0, (int)(N % kPrepChunk), &leaves);
+    if ((int)leaves.size() > kPrepMaxTailLeaves) return fail(TS2D_ERR_INVALID, "%s: %zu leaves in a partial chunk", entry, leaves.size());
+    const size_t n_out = (size_t)n_full + leaves.size();
+    const dim3 grid_sums((unsigned)(n_full + (leaves.empty() ? 0 : 1)), (unsigned)n);
+    std::vector<float> sums((size_t)n * n_out);
+    if (!leaves.empty()) HIP_TRY(hipMemcpy(d_leaves, leaves.data(), leaves.size() * sizeof(PrepLeaf), hipMemcpyHostToDevice));
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 0) hipLaunchKernelGGL(prep_chunk_sums<0>, grid_sums, dim3(512), 0, 0, x, N, d_norm, d_leaves, (int)leaves.size(), d_sums);
+        else hipLaunchKernelGGL(prep_chunk_sums<1>, grid_sums, dim3(512), 0, 0, x, N, d_norm, d_leaves, (int)leaves.size(), d_sums);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(sums.data(), d_sums, sums.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int c = 0; c < n; ++c) {
+            if (want && !want[c]) continue;
+            // numpy divides the float32 sum by the count in float64 and rounds once to float32 (`ret / rcount` with an intp count)
+            const float q = (float)((double)prep_plane_sum(sums.data() + (size_t)c * n_out, N) / (double)N);
+            if (!std::isfinite(q)) *bad = true;
+            if (pass == 0) { norm[c].mean = q; stats[2 * c] = q; }
+            else { const float sd = std::sqrt(q); stats[2 * c + 1] = sd; norm[c].div = 1e-8 > (double)sd ? (float)1e-8 : sd; }   // max(std, 1e-8)
+        }
+        if (*bad) return TS2D_OK;
+        HIP_TRY(hipMemcpy(d_norm, norm, (size_t)n * sizeof(PrepNorm), hipMemcpyHostToDevice));
+    }
+    return TS2D_OK;
+}
+
+// The keys a normalise kernel left at d_keys [n][2] become the handle's clip bounds; *bad is set instead when one of them is not finite.
+int planes_keep_bounds(ts2d_planes* p, const int* d_keys, std::vector<int>* keys, bool* bad) {
+    const size_t m = (size_t)p->n * 2;
+    HIP_TRY(hipMemcpy(keys->data(), d_keys, m * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<float> lh(m);
+    for (size_t i = 0; i < m; ++i) { lh[i] = prep_unkey((*keys)[i]); if (!std::isfinite(lh[i])) *bad = true; }
+    if (*bad) return TS2D_OK;
+    HIP_TRY(hipMemcpy(p->d_lh.as<float>(), lh.data(), m * sizeof(float), hipMemcpyHostToDevice));
+    p->has_bounds = true;
+    return TS2D_OK;
+}
+
 }  // namespace
 #pragma GCC visibility pop
 
@@ -183,69 +258,131 @@ int ts2d_planes_crop_zscore(ts2d_planes* p, int32_t box[4], float* stats, int* n
     const size_t o_sums = align_up(o_leaves + kPrepMaxTailLeaves * sizeof(PrepLeaf), 256);
     DevMem d;
     HIP_TRY(d.alloc(o_sums + (size_t)n * per_plane * sizeof(float)));
-    int* d_box = d.as<int>(); int* d_keys = d.as<int>(o_keys);
-    PrepNorm* d_norm = d.as<PrepNorm>(o_norm); PrepLeaf* d_leaves = d.as<PrepLeaf>(o_leaves);
-    float* d_sums = d.as<float>(o_sums);
-    // 1. crop_to_nonzero's box over all planes
-    int hb[4] = {p->h, -1, p->w, -1};
-    HIP_TRY(hipMemcpy(d_box, hb, sizeof(hb), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(prep_nonzero_box, dim3((unsigned)(((long long)p->h * p->w + 255) / 256)), dim3(256), 0, 0, p->d.as<float>(), n, p->h, p->w, d_box);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(hb, d_box, sizeof(hb), hipMemcpyDeviceToHost));
-    if (hb[1] < 0) { hb[0] = 0; hb[1] = p->h - 1; hb[2] = 0; hb[3] = p->w - 1; }            // nothing but zeros: the whole extent stays
-    if (hb[0] < 0 || hb[1] >= p->h || hb[0] > hb[1] || hb[2] < 0 || hb[3] >= p->w || hb[2] > hb[3])
-        return fail(TS2D_ERR_HIP, "ts2d_planes_crop_zscore: the device returned the box rows %d ... %d, columns %d ... %d of %d x %d", hb[0], hb[1], hb[2], hb[3], p->h, p->w);
-    const int bh = hb[1] - hb[0] + 1, bw = hb[3] - hb[2] + 1;
-    // 2. compaction: the flattened index of the dense [n][bh][bw] buffer is numpy's
-    if (bh != p->h || bw != p->w) {
-        DevMem d_new;
-        HIP_TRY(d_new.alloc((size_t)n * bh * bw * sizeof(float)));
-        for (int c = 0; c < n; ++c)
-            HIP_TRY(hipMemcpy2D(d_new.as<float>() + (size_t)c * bh * bw, (size_t)bw * sizeof(float), p->d.as<float>() + ((size_t)c * p->h + hb[0]) * p->w + hb[2],
-                                (size_t)p->w * sizeof(float), (size_t)bw * sizeof(float), (size_t)bh, hipMemcpyDeviceToDevice));
-        p->d = std::move(d_new); p->h = bh; p->w = bw;
-    }
+    int* d_keys = d.as<int>(o_keys);
+    PrepNorm* d_norm = d.as<PrepNorm>(o_norm);
+    // 1., 2. crop_to_nonzero's box over all planes and the compaction to it
+    TRY(planes_crop("ts2d_planes_crop_zscore", p, d.as<int>(), box));
     float* const x = p->d.as<float>();
-    p->has_bounds = false;
-    box[0] = hb[0]; box[1] = hb[1] + 1; box[2] = hb[2]; box[3] = hb[3] + 1;
     // 3. the two sums of every plane: chunk and leaf sums on the device, their fold and the float32 statistics here
-    const long long N = (long long)bh * bw, n_full = N / kPrepChunk;
-    std::vector<PrepLeaf> leaves;
-    if (N % kPrepChunk) prep_leaves(0, (int)(N % kPrepChunk), &leaves);
-    if ((int)leaves.size() > kPrepMaxTailLeaves) return fail(TS2D_ERR_INVALID, "ts2d_planes_crop_zscore: %zu leaves in a partial chunk", leaves.size());
-    const size_t n_out = (size_t)n_full + leaves.size();
-    const dim3 grid_sums((unsigned)(n_full + (leaves.empty() ? 0 : 1)), (unsigned)n);
-    std::vector<float> sums((size_t)n * n_out);
+    const long long N = (long long)p->h * p->w;
     std::vector<PrepNorm> norm((size_t)n, PrepNorm{0.f, 1.f});
-    if (!leaves.empty()) HIP_TRY(hipMemcpy(d_leaves, leaves.data(), leaves.size() * sizeof(PrepLeaf), hipMemcpyHostToDevice));
     bool bad = false;
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 0) hipLaunchKernelGGL(prep_chunk_sums<0>, grid_sums, dim3(512), 0, 0, x, N, d_norm, d_leaves, (int)leaves.size(), d_sums);
-        else hipLaunchKernelGGL(prep_chunk_sums<1>, grid_sums, dim3(512), 0, 0, x, N, d_norm, d_leaves, (int)leaves.size(), d_sums);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(sums.data(), d_sums, sums.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (int c = 0; c < n; ++c) {
-            // numpy divides the float32 sum by the count in float64 and rounds once to float32 (`ret / rcount` with an intp count)
-            const float q = (float)((double)prep_plane_sum(sums.data() + (size_t)c * n_out, N) / (double)N);
-            if (!std::isfinite(q)) bad = true;
-            if (pass == 0) { norm[c].mean = q; stats[2 * c] = q; }
-            else { const float sd = std::sqrt(q); stats[2 * c + 1] = sd; norm[c].div = 1e-8 > (double)sd ? (float)1e-8 : sd; }   // max(std, 1e-8)
-        }
-        if (bad) { *nonfinite = 1; return TS2D_OK; }               // a non-finite sample (or an overflowing sum): nothing is normalised
-        HIP_TRY(hipMemcpy(d_norm, norm.data(), norm.size() * sizeof(PrepNorm), hipMemcpyHostToDevice));
-    }
+    TRY(planes_stats("ts2d_planes_crop_zscore", x, N, n, nullptr, d_norm, d.as<PrepLeaf>(o_leaves), d.as<float>(o_sums), norm.data(), stats, &bad));
+    if (bad) { *nonfinite = 1; return TS2D_OK; }                   // a non-finite sample (or an overflowing sum): nothing is normalised
     // 4. normalise in place; the minimum and maximum of the result are the clip bounds of the resample
     std::vector<int> keys((size_t)n * 2);
     for (int c = 0; c < n; ++c) { keys[2 * c] = 0x7FFFFFFF; keys[2 * c + 1] = (int)0x80000000; }
     HIP_TRY(hipMemcpy(d_keys, keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(prep_normalise, dim3((unsigned)((N + 256 * kPrepNormPerLane - 1) / (256 * kPrepNormPerLane)), (unsigned)n), dim3(256), 0, 0, x, N, d_norm, d_keys);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(keys.data(), d_keys, keys.size() * sizeof(int), hipMemcpyDeviceToHost));
-    std::vector<float> lh((size_t)n * 2);
-    for (size_t i = 0; i < lh.size(); ++i) { lh[i] = prep_unkey(keys[i]); if (!std::isfinite(lh[i])) bad = true; }
-    if (bad) { *nonfinite = 1; return TS2D_OK; }                   // (a quotient overflowed: the planes hold it, the caller drops the handle)
-    HIP_TRY(hipMemcpy(p->d_lh.as<float>(), lh.data(), lh.size() * sizeof(float), hipMemcpyHostToDevice));
-    p->has_bounds = true;
+    TRY(planes_keep_bounds(p, d_keys, &keys, &bad));
+    if (bad) *nonfinite = 1;                                       // (a quotient overflowed: the planes hold it, the caller drops the handle)
+    return TS2D_OK;
+}
+
+int ts2d_planes_crop_normalize(ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask, int32_t box[4], float* stats,
+                               int* status) {
+    const char* const entry = "ts2d_planes_crop_normalize";
+    if (!p || !schemes || !params || !use_mask || !box || !stats || !status) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
+    *status = 0;
+    const int n = p->n;
+    bool any_plain = false, any_masked = false, any_rescale = false;
+    for (int c = 0; c < n; ++c) {
+        if (schemes[c] < TS2D_NORM_ZSCORE || schemes[c] > TS2D_NORM_NONE) return fail(TS2D_ERR_INVALID, "%s: plane %d has the unknown scheme %d", entry, c, (int)schemes[c]);
+        if (schemes[c] == TS2D_NORM_CT)
+            for (int k = 0; k < 4; ++k)
+                if (!std::isfinite(params[4 * c + k]))
+                    return fail(TS2D_ERR_INVALID, "%s: plane %d has the non-finite CT parameter %g at [%d] (mean, divisor, lower bound, upper bound)", entry, c, (double)params[4 * c + k], k);
+        const bool masked = schemes[c] == TS2D_NORM_ZSCORE && use_mask[c];
+        any_masked |= masked; any_plain |= schemes[c] == TS2D_NORM_ZSCORE && !masked; any_rescale |= schemes[c] == TS2D_NORM_RESCALE01;
+    }
+    HIP_TRY(hipSetDevice(p->device));
+    // scratch, sized for the uncropped extent: [box, n_m, status | min / max keys, of the result and of the input | mean, divisor | scheme table |
+    //                                           leaves of the partial chunk | chunk and leaf sums]
+    const size_t per_plane = (size_t)((long long)p->h * p->w / kPrepChunk) + kPrepMaxTailLeaves;
+    const size_t o_keys = 256, o_norm = align_up(o_keys + (size_t)n * 4 * sizeof(int), 256), o_table = align_up(o_norm + (size_t)n * sizeof(PrepNorm), 256);
+    const size_t o_leaves = align_up(o_table + (size_t)n * sizeof(PrepScheme), 256), o_sums = align_up(o_leaves + kPrepMaxTailLeaves * sizeof(PrepLeaf), 256);
+    DevMem d, d_mask, d_dense;
+    HIP_TRY(d.alloc(o_sums + (size_t)n * per_plane * sizeof(float)));
+    int* d_total = d.as<int>(4 * sizeof(int)); int* d_status = d_total + 1;
+    int* d_keys = d.as<int>(o_keys); int* d_keys_in = d_keys + 2 * (size_t)n;
+    PrepNorm* d_norm = d.as<PrepNorm>(o_norm); PrepScheme* d_table = d.as<PrepScheme>(o_table);
+    PrepLeaf* d_leaves = d.as<PrepLeaf>(o_leaves); float* d_sums = d.as<float>(o_sums);
+    // 1., 2. crop_to_nonzero's box over all planes and the compaction to it
+    TRY(planes_crop(entry, p, d.as<int>(), box));
+    float* const x = p->d.as<float>();
+    const long long N = (long long)p->h * p->w;
+    const dim3 grid_apply((unsigned)((N + 256 * kPrepNormPerLane - 1) / (256 * kPrepNormPerLane)), (unsigned)n);
+    std::vector<int> keys((size_t)n * 4);
+    for (size_t i = 0; i < keys.size(); i += 2) { keys[i] = 0x7FFFFFFF; keys[i + 1] = (int)0x80000000; }
+    const int zero2[2] = {0, 0};
+    HIP_TRY(hipMemcpy(d_keys, keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_total, zero2, sizeof(zero2), hipMemcpyHostToDevice));
+    // 3. the non-zero mask inside the box (nnU-Net's `seg >= 0` for one slice), shared by all planes, and the masked samples of every plane
+    //    in index order: numpy's `img[m]`
+    long long n_m = 0;
+    const uint8_t* mask = nullptr;
+    if (any_masked) {
+        const int nb = (int)((N + kPrepMaskBlock - 1) / kPrepMaskBlock);
+        const size_t o_counts = align_up((size_t)N, 256), o_offs = align_up(o_counts + (size_t)nb * sizeof(int), 256);
+        HIP_TRY(d_mask.alloc(o_offs + (size_t)nb * sizeof(int)));
+        mask = d_mask.as<uint8_t>();
+        hipLaunchKernelGGL(prep_mask_counts, dim3((unsigned)nb), dim3(256), 0, 0, x, n, N, d_mask.as<uint8_t>(), d_mask.as<int>(o_counts));
+        hipLaunchKernelGGL(prep_mask_scan, dim3(1), dim3(1024), 0, 0, d_mask.as<int>(o_counts), nb, d_mask.as<int>(o_offs), d_total);
+        HIP_TRY(hipGetLastError());
+        int total = 0;
+        HIP_TRY(hipMemcpy(&total, d_total, sizeof(int), hipMemcpyDeviceToHost));
+        if (total < 0 || total > N) return fail(TS2D_ERR_HIP, "%s: the device counted %d masked pixels of %lld", entry, total, N);
+        if (total == 0) { *status = TS2D_PLANES_EMPTY_MASK; return TS2D_OK; }      // an image of zeros: numpy takes the mean of nothing
+        n_m = total;
+        HIP_TRY(d_dense.alloc((size_t)n * n_m * sizeof(float)));
+        hipLaunchKernelGGL(prep_mask_scatter, dim3((unsigned)nb, (unsigned)n), dim3(256), 0, 0, x, N, mask, d_mask.as<int>(o_offs), n_m, d_dense.as<float>());
+        HIP_TRY(hipGetLastError());
+    }
+    // 4. the parameters of every plane: the z-score statistics (of the whole plane, or of its masked samples), the minimum and maximum
+    //    behind Rescale, the caller's for CT
+    std::vector<PrepNorm> norm((size_t)n, PrepNorm{0.f, 1.f});
+    std::vector<uint8_t> want((size_t)n);
+    bool bad = false;
+    if (any_plain) {
+        for (int c = 0; c < n; ++c) want[c] = schemes[c] == TS2D_NORM_ZSCORE && !use_mask[c];
+        TRY(planes_stats(entry, x, N, n, want.data(), d_norm, d_leaves, d_sums, norm.data(), stats, &bad));
+    }
+    if (any_masked && !bad) {
+        for (int c = 0; c < n; ++c) want[c] = schemes[c] == TS2D_NORM_ZSCORE && use_mask[c];
+        TRY(planes_stats(entry, d_dense.as<float>(), n_m, n, want.data(), d_norm, d_leaves, d_sums, norm.data(), stats, &bad));
+    }
+    if (any_rescale && !bad) {
+        hipLaunchKernelGGL(prep_apply_schemes<false>, grid_apply, dim3(256), 0, 0, x, N, nullptr, nullptr, d_keys_in, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(keys.data() + 2 * (size_t)n, d_keys_in, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    std::vector<PrepScheme> table((size_t)n);
+    for (int c = 0; c < n && !bad; ++c) {
+        PrepScheme& s = table[c];
+        s = PrepScheme{(int)schemes[c], 0, 0.f, 1.f, 0.f, 0.f};
+        if (s.id == kPrepZScore) { s.masked = use_mask[c] ? 1 : 0; s.sub = norm[c].mean; s.div = norm[c].div; continue; }      // (stats: mean and std, written above)
+        if (s.id == kPrepCT) { s.sub = params[4 * c]; s.div = params[4 * c + 1]; s.lo = params[4 * c + 2]; s.hi = params[4 * c + 3]; }
+        if (s.id == kPrepRGB01) s.div = 255.f;
+        if (s.id == kPrepRescale01) {
+            const float mn = prep_unkey(keys[2 * (size_t)n + 2 * c]), mx = prep_unkey(keys[2 * (size_t)n + 2 * c + 1]);
+            if (!std::isfinite(mn) || !std::isfinite(mx)) { bad = true; break; }
+            // numpy's min() of a plane that holds zeros of both signs and nothing below them returns either: not decided here
+            if (mn == 0.f && std::signbit(mn)) *status |= TS2D_PLANES_ZERO_SIGN;
+            s.sub = mn; s.div = prep_rescale_div(mn, mx);
+        }
+        stats[2 * c] = s.sub; stats[2 * c + 1] = s.div;
+    }
+    if (bad) *status |= TS2D_PLANES_NONFINITE;                     // a non-finite sample (or an overflowing sum)
+    if (*status) return TS2D_OK;                                   // nothing is normalised
+    // 5. normalise in place; the minimum and maximum of the result are the clip bounds of the resample
+    HIP_TRY(hipMemcpy(d_table, table.data(), table.size() * sizeof(PrepScheme), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(prep_apply_schemes<true>, grid_apply, dim3(256), 0, 0, x, N, d_table, mask, d_keys, d_status);
+    HIP_TRY(hipGetLastError());
+    TRY(planes_keep_bounds(p, d_keys, &keys, &bad));
+    HIP_TRY(hipMemcpy(status, d_status, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad) *status |= TS2D_PLANES_NONFINITE;                     // (a quotient overflowed, or a plane that is not normalised holds a non-finite sample)
+    if (*status) p->has_bounds = false;                            // (an RGB sample out of range: the planes are no result, nothing resamples them)
     return TS2D_OK;
 }
 

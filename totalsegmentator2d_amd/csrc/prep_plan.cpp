@@ -105,6 +105,14 @@ float prep_plane_sum(const float* sums, long long n) {
     return acc;
 }
 
+// RescaleTo01Normalization's divisor from the plane's minimum and maximum: numpy takes `clip(max(img - min), 1e-8, None)`; x -> fl32(x - min)
+// is monotone, so that maximum is fl32(max - min), and the clip is `d < lo ? lo : d` with lo = float32(1e-8) (a NaN stays NaN)
+float prep_rescale_div(float mn, float mx) {
+#pragma clang fp contract(off)
+    const float d = mx - mn, lo = (float)1e-8;
+    return d < lo ? lo : d;
+}
+
 float prep_unkey(int key) { const int b = key < 0 ? key ^ 0x7FFFFFFF : key; float f; std::memcpy(&f, &b, 4); return f; }
 
 }  // namespace ts2d

@@ -42,6 +42,7 @@ class HIPModel:
         self.device_labelmap = True      # a label-map (non-multilabel) model: resample-back and argmax on the device, ONE uint8 plane to the host (_run); the host route's bytes
         self.device_input_resample = True   # order-3 resample of an off-spacing case's input on the device: the same float32 values as scipy, bit for bit (preprocess.resize_cubic_f64)
         self.device_input_normalize = True  # crop box, z-score (and that resample) of a native 2-D input on device-resident planes: the same float32 values as numpy, bit for bit (preprocess.zscore_f32_statement)
+        self.device_input_normalize_schemes = True  # the same for every other nnU-Net scheme (masked z-score, CT, Rescale, RGB, none): the cases device_input_normalize leaves to numpy, the same bits (preprocess.*_f32_statement)
         self._discover()
 
     # ------------------------------------------------------------------ configuration (reference wrapper.py:113-162)
@@ -144,7 +145,7 @@ class HIPModel:
         """Everything DefaultPreprocessor.run_case_npy reads besides the image itself: two sub-models with the same key preprocess identically."""
         cm, pm = p.configuration_manager, p.plans_manager
         dz = props.get('device_zscore')
-        return repr((props.get('device_resample'), props.get('device_normalize')) + (list(getattr(pm, 'transpose_forward', [0, 1, 2])), list(cm.spacing), list(getattr(cm, 'normalization_schemes', None) or []),
+        return repr((props.get('device_resample'), props.get('device_normalize'), props.get('device_normalize_schemes')) + (list(getattr(pm, 'transpose_forward', [0, 1, 2])), list(cm.spacing), list(getattr(cm, 'normalization_schemes', None) or []),
                      list(getattr(cm, 'use_mask_for_norm', None) or []), sorted((p.dataset_json.get('channel_names') or {}).items()),
                      (getattr(pm, 'plans', None) or {}).get('foreground_intensity_properties_per_channel', {}),
                      None if dz is None else tuple(dz.get('order', ()))))
@@ -179,6 +180,8 @@ class HIPModel:
             props['device_resample'] = self._resample_device()   # an off-spacing case is resampled to the plan spacing on the device (preprocess.py)
         if self._normalize_device() is not None:
             props['device_normalize'] = self._normalize_device()  # a native 2-D input is cropped and z-scored on the device, on planes that stay there for the resample (preprocess.py)
+        if self._input_device(getattr(self, 'device_input_normalize_schemes', False)) is not None:
+            props['device_normalize_schemes'] = self._input_device(self.device_input_normalize_schemes)   # ... and normalised there by any other scheme of the plan
         pre = p.configuration_manager.preprocessor_class(verbose=p.verbose)
         shared = getattr(ref, 'preprocess_cache', None)      # set by TS2D.predict: the sub-models of one case mostly share channels and plan
         if shared is None:

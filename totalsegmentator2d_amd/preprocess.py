@@ -309,13 +309,13 @@ def cubic_device_entry():
 
 def resample_planes_cubic_device(data: np.ndarray, new_hw, device: int) -> Optional[np.ndarray]:
     """All (channel, slice) planes of ``data`` [C, Z, H, W] float32 through ONE ``ts2d_resample_cubic`` call on ``device``: bit for bit
-    :func:`resize_cubic_f64`, hence scipy, per plane.  ``data`` may be a :class:`DevicePlanes` that :meth:`DevicePlanes.crop_zscore` has
-    normalised: its planes are resampled where they lie.  None when this is no case for the entry - no entry, not float32, an extent outside
+    :func:`resize_cubic_f64`, hence scipy, per plane.  ``data`` may be a :class:`DevicePlanes` that :meth:`DevicePlanes.crop_zscore` or
+    :meth:`DevicePlanes.crop_normalize` has normalised: its planes are resampled where they lie.  None when this is no case for the entry - no entry, not float32, an extent outside
     2 ... CUBIC_MAX_EXTENT, a plane with a non-finite sample (its min / max say so) - and the caller runs scipy.  A call that FAILS raises."""
     from . import _lib
     c, z, h, w = data.shape
     oh, ow = int(new_hw[0]), int(new_hw[1])
-    if isinstance(data, DevicePlanes):          # z-scored on the device: resampled there, with the clip bounds it kept, and downloaded once
+    if isinstance(data, DevicePlanes):          # normalised on the device: resampled there, with the clip bounds it kept, and downloaded once
         if min(h, w, oh, ow) < 2 or max(h, w, oh, ow) > CUBIC_MAX_EXTENT or c * (h + 2 * CUBIC_PAD) * (w + 2 * CUBIC_PAD) > 1 << 28 or c * oh * ow > 1 << 28:
             return None
         return data.resample((oh, ow)).download()
@@ -475,6 +475,84 @@ def crop_box_statement(data: np.ndarray):
     return [[0, 1], [int(rows[0]), int(rows[-1]) + 1], [int(cols[0]), int(cols[-1]) + 1]]
 
 
+# nnU-Net's default_normalization_schemes -> the TS2D_NORM_* of include/ts2d_engine.h, and the TS2D_PLANES_* status bits of ts2d_planes_crop_normalize
+NORM_SCHEME_IDS = {'ZScoreNormalization': 0, 'CTNormalization': 1, 'RescaleTo01Normalization': 2, 'RGBTo01Normalization': 3, 'NoNormalization': 4}
+PLANES_NONFINITE, PLANES_RGB_RANGE, PLANES_EMPTY_MASK, PLANES_ZERO_SIGN = 1, 2, 4, 8
+RGB_RANGE_MESSAGE = "RGB images are uint 8, for whatever reason I found pixel values outside [0, 255]"
+
+
+def ct_f32_parameters(props: dict) -> np.ndarray:
+    """``(mean, divisor, lower bound, upper bound)`` of :func:`ct_f32_statement`, four float32, from one entry of the plan's
+    ``foreground_intensity_properties_per_channel``: ``float32(mean)``; ``float32(max(std, 1e-8))``, the ``max`` taken in double and rounded once;
+    the two percentiles as numpy 2.2's ``clip`` converts a Python float or int for a float32 array (NEP 50: to float32, round to nearest) - found
+    by letting ``clip`` itself convert them.  A bound float32 cannot hold becomes an infinity (numpy warns of the overflow; silenced here)."""
+    with np.errstate(over='ignore'):
+        lo = np.clip(np.array([-np.inf], np.float32), props['percentile_00_5'], None)[0]
+        hi = np.clip(np.array([np.inf], np.float32), None, props['percentile_99_5'])[0]
+        return np.array([np.float32(props['mean']), np.float32(max(props['std'], 1e-8)), lo, hi], np.float32)
+
+
+def ct_f32_statement(plane: np.ndarray, props: dict) -> np.ndarray:
+    """``CTNormalization.run`` (:func:`normalize_channel`) of one float32 plane with numpy's clip written out, bit for bit what numpy 2.2 returns
+    (tests/test_prep_schemes_cpu.py): with the parameters of :func:`ct_f32_parameters`, ``x < lo ? lo : x``, then ``x > hi ? hi : x``, then
+    ``fl32(fl32(x - mean) / divisor)``.  What clip does at the edges: a NaN SAMPLE stays NaN (both comparisons are false); a sample EQUAL to a
+    bound keeps its own bits, so ``-0.0`` against a bound of ``0.0`` stays ``-0.0`` and only a sample really below ``0.0`` becomes ``+0.0`` (``-0.0`` as the
+    bound gives ``-0.0``); bounds in the wrong order give the upper one everywhere.  A bound that is not finite in float32: an infinity clips
+    nothing on its side, a NaN bound makes every sample NaN (that is the one thing the comparisons do not say: numpy's clip propagates a NaN
+    bound).  The device entry ts2d_planes_crop_normalize takes finite parameters only; the caller keeps the host route for the rest."""
+    x = np.ascontiguousarray(plane, np.float32)
+    mean, div, lo, hi = ct_f32_parameters(props)
+    with np.errstate(over='ignore', invalid='ignore'):
+        if np.isnan(lo) or np.isnan(hi):
+            v = np.full(x.shape, np.nan, np.float32)
+        else:
+            v = np.where(x < lo, lo, x)
+            v = np.where(v > hi, hi, v)
+        return (v - mean) / div
+
+
+def rescale01_f32_statement(plane: np.ndarray) -> np.ndarray:
+    """``RescaleTo01Normalization.run`` of one C-contiguous float32 plane, bit for bit numpy 2.2: ``d = fl32(x - min)``, then ``fl32(d / div)`` with
+    ``div = max(d)`` unless that is below ``float32(1e-8)``, then ``float32(1e-8)`` (``np.clip`` of a float32 scalar with a Python float bound stays
+    float32).  ``x -> fl32(x - min)`` is monotone, so ``max(d) = fl32(max(x) - min(x))``: the device derives the divisor from the plane's two bounds
+    and needs no second pass.  A constant plane gives ``d = +0`` everywhere, the divisor 1e-8 and zeros.  ``min`` and ``max`` are exact, but for one
+    thing: of a plane whose smallest value is zero and that holds zeros of both signs, numpy's ``min()`` returns ``-0.0`` or ``+0.0`` depending on where
+    they lie and how its vector loop runs over them, and ``fl32(-0.0 - min)`` is ``+0.0`` for the one and ``-0.0`` for the other.  This statement takes
+    what numpy returns; the device entry reports a minimum of ``-0.0`` (PLANES_ZERO_SIGN) and leaves such a plane to numpy."""
+    x = np.ascontiguousarray(plane, np.float32)
+    with np.errstate(over='ignore', invalid='ignore'):
+        d = x - x.min()
+        mx, lo = d.max(), np.float32(1e-8)
+        return d / (lo if mx < lo else mx)
+
+
+def rgb01_f32_statement(plane: np.ndarray) -> np.ndarray:
+    """``RGBTo01Normalization.run`` of one float32 plane: upstream's range check (``min() < 0 or max() > 255`` raises; a NaN passes it, a ``-0.0`` too),
+    then ``fl32(x / float32(255))``."""
+    x = np.ascontiguousarray(plane, np.float32)
+    if x.min() < 0 or x.max() > 255:
+        raise RuntimeError(RGB_RANGE_MESSAGE)
+    with np.errstate(invalid='ignore'):
+        return x / np.float32(255.0)
+
+
+def masked_zscore_f32_statement(plane: np.ndarray, mask: np.ndarray) -> np.ndarray:
+    """``ZScoreNormalization.run`` with ``use_mask_for_norm`` of one float32 plane, bit for bit numpy 2.2: ``img[m]`` is a compact 1-D copy of the
+    masked samples in row-major order, so ``img[m].mean()`` and ``img[m].std()`` are :func:`zscore_stats_f32_statement` of a run of ``n_m`` elements
+    (chunks of 8192, the pairwise tree of the last ``n_m % 8192``); inside the mask ``fl32(fl32(x - mean) / max(std, 1e-8))``, outside it the sample
+    itself.  For the single-slice inputs of the device path the mask is "non-zero in ANY channel" inside the crop box (:func:`crop_to_nonzero`).
+    An empty mask (an image of zeros) has no mean: numpy warns and fills NaN; it is no case of this statement, nor of the device."""
+    x = np.ascontiguousarray(plane, np.float32).copy()
+    m = np.asarray(mask).astype(bool)
+    sel = x[m]
+    if not sel.size:
+        raise ValueError("masked_zscore_f32_statement: the mask is empty")
+    mean, _, div = zscore_stats_f32_statement(sel)
+    with np.errstate(over='ignore', invalid='ignore'):
+        x[m] = (sel - mean) / div
+    return x
+
+
 def planes_device_entries():
     """The engine library when it has the ``ts2d_planes_*`` entries, or None (no library built, or one built before they existed): the callers
     then keep the host route, silently - the result is the same."""
@@ -488,8 +566,8 @@ def planes_device_entries():
 
 class DevicePlanes:
     """The planes ``[C, 1, h, w]`` float32 of one native 2-D case on the device, behind a ``ts2d_planes`` handle: uploaded once here, cropped
-    and z-scored (:meth:`crop_zscore`) and resampled (:meth:`resample`) where they lie, downloaded once (:meth:`download`).  Every float32
-    that comes back is the host route's, bit for bit (:func:`zscore_f32_statement`, :func:`resize_cubic_f64`).  A context manager;
+    and normalised (:meth:`crop_zscore`, or :meth:`crop_normalize` for the other schemes) and resampled (:meth:`resample`) where they lie, downloaded once (:meth:`download`).  Every float32
+    that comes back is the host route's, bit for bit (:func:`zscore_f32_statement` and the statements of the other schemes, :func:`resize_cubic_f64`).  A context manager;
     :meth:`close` destroys the handle and may be called twice."""
 
     def __init__(self, data: np.ndarray, device: int, lib=None):
@@ -502,7 +580,8 @@ class DevicePlanes:
             raise ValueError(f"DevicePlanes: float32 [C, 1, H, W] is needed, got {data.dtype} {data.shape}")
         src = np.ascontiguousarray(data)
         self.device, self.channels = int(device), int(data.shape[0])
-        self.stats = None                                   # [C, 2] float32 (mean, std) after crop_zscore
+        self.stats = None                                   # [C, 2] float32 (mean, std) after crop_zscore; what crop_normalize used per channel
+        self.status = 0                                     # PLANES_* bits of the last crop_normalize
         self._h = ctypes.c_void_p()
         self._check(self._lib.ts2d_planes_create(self.device, src.ctypes.data, self.channels, int(data.shape[2]), int(data.shape[3]),
                                                  ctypes.byref(self._h)), 'ts2d_planes_create')
@@ -527,6 +606,26 @@ class DevicePlanes:
         stats = np.zeros((self.channels, 2), np.float32)
         self._check(self._lib.ts2d_planes_crop_zscore(self._h, ctypes.byref(box), stats.ctypes.data, ctypes.byref(bad)), 'ts2d_planes_crop_zscore')
         if bad.value:
+            return None
+        self.stats = stats
+        return [[0, 1], [int(box[0]), int(box[1])], [int(box[2]), int(box[3])]]
+
+    def crop_normalize(self, schemes, use_mask, fip):
+        """crop_to_nonzero and each channel's own scheme on the device (ts2d_planes_crop_normalize): ``schemes`` the plan's names, ``use_mask`` its
+        ``use_mask_for_norm``, ``fip`` its ``foreground_intensity_properties_per_channel`` (read for the CT channels).  Returns the box like
+        :meth:`crop_zscore`, or None with the PLANES_* bits in ``self.status``: nothing usable was normalised and the caller takes the host route."""
+        import ctypes
+        ids = np.array([NORM_SCHEME_IDS[s] for s in schemes[:self.channels]], np.int32)
+        params = np.zeros((self.channels, 4), np.float32)
+        for c in np.flatnonzero(ids == NORM_SCHEME_IDS['CTNormalization']):
+            params[c] = ct_f32_parameters(fip[str(c)])
+        masked = np.array([bool(c < len(use_mask) and use_mask[c]) for c in range(self.channels)], np.uint8)
+        box, status = (ctypes.c_int32 * 4)(), ctypes.c_int(0)
+        stats = np.zeros((self.channels, 2), np.float32)
+        self._check(self._lib.ts2d_planes_crop_normalize(self._h, ids.ctypes.data, params.ctypes.data, masked.ctypes.data, ctypes.byref(box),
+                                                         stats.ctypes.data, ctypes.byref(status)), 'ts2d_planes_crop_normalize')
+        self.status = int(status.value)
+        if self.status:
             return None
         self.stats = stats
         return [[0, 1], [int(box[0]), int(box[1])], [int(box[2]), int(box[3])]]
@@ -561,7 +660,9 @@ class DevicePlanes:
 
 # C * H * W from which the device route of run_case_npy is taken.  Below it the handle's fixed cost (three allocations, a dozen small copies
 # and synchronisations: 0.25 ms) is more than numpy's passes over the planes; measured on two-channel square planes the routes cross between
-# 2 x 128^2 (0.89x) and 2 x 192^2 (1.34x) samples (profiles/r12_native2d_case.txt).
+# 2 x 128^2 (0.89x) and 2 x 192^2 (1.34x) samples (profiles/r12_native2d_case.txt).  The other schemes
+# (DevicePlanes.crop_normalize) cross between the same two sizes - 0.78 ... 0.98x and 1.23 ... 1.65x, quartiles within 3 % of the medians
+# (profiles/r16_normalize_schemes_case.txt) - so this one gate serves them all.
 DEVICE_NORMALIZE_MIN_SAMPLES = 1 << 16
 
 
@@ -574,6 +675,34 @@ def _device_normalize_applies(data, tf, schemes, use_mask, dz) -> bool:
             and all(s == 'ZScoreNormalization' for s in schemes[:c]) and len(schemes) >= c and not any(use_mask[:c])
             and 1 <= min(h, w) and max(h, w) <= CUBIC_MAX_EXTENT and DEVICE_NORMALIZE_MIN_SAMPLES <= c * h * w <= PLANES_MAX_SAMPLES
             and planes_device_entries() is not None)
+
+
+def _device_schemes_apply(data, tf, schemes, use_mask, fip) -> bool:
+    """The cases :func:`_device_normalize_applies` refuses for their schemes and ts2d_planes_crop_normalize computes: identity transpose, one slice
+    per channel, every scheme one of nnU-Net's five and not all of them the plain z-score (that case belongs to the other predicate, its z-score
+    from the projection included - which can never apply here, so it does not bar this route), the plan's intensity properties there for every CT
+    channel as Python numbers that are finite in float32, extents and sample count inside the handle's limits (and above the size from which it
+    pays), the entry present."""
+    c, z, h, w = data.shape
+    if not (list(tf) == [0, 1, 2] and z == 1 and c >= 1 and len(schemes) >= c and all(s in NORM_SCHEME_IDS for s in schemes[:c])):
+        return False
+    masked = [bool(i < len(use_mask) and use_mask[i]) for i in range(c)]
+    if all(s == 'ZScoreNormalization' for s in schemes[:c]) and not any(masked):
+        return False
+    for i in range(c):
+        if schemes[i] == 'CTNormalization':
+            props = (fip or {}).get(str(i))
+            keys = ('mean', 'std', 'percentile_00_5', 'percentile_99_5')
+            if not props or not all(type(props.get(k)) in (int, float) for k in keys):
+                return False
+            try:
+                if not np.isfinite(ct_f32_parameters(props)).all():
+                    return False
+            except OverflowError:
+                return False
+    lib = planes_device_entries()
+    return (1 <= min(h, w) and max(h, w) <= CUBIC_MAX_EXTENT and DEVICE_NORMALIZE_MIN_SAMPLES <= c * h * w <= PLANES_MAX_SAMPLES
+            and lib is not None and hasattr(lib, 'ts2d_planes_crop_normalize'))
 
 
 def _device_zscore_applies(dz, data, bbox, tf, schemes, use_mask) -> bool:
@@ -601,13 +730,20 @@ class DefaultPreprocessor:
         dz = properties.pop('device_zscore', None)
         device_resample = properties.pop('device_resample', None)     # GPU index for the order-3 resample below (HIPModel sets it), None: host
         device_normalize = properties.pop('device_normalize', None)   # GPU index for crop box + z-score (+ that resample) on device-resident planes
+        device_schemes = properties.pop('device_normalize_schemes', None)   # the same for the cases that route refuses for their schemes: masked z-score, CT, Rescale, RGB, none
         target_spacing = list(configuration_manager.spacing)
         if len(target_spacing) < len(data.shape[1:]):
             target_spacing = [original_spacing[0]] + target_spacing
+        fip = (getattr(plans_manager, 'plans', None) or {}).get('foreground_intensity_properties_per_channel', {})
+        planes_device = None
         if device_normalize is not None and _device_normalize_applies(data, tf, schemes, use_mask, dz):
-            with DevicePlanes(data, device_normalize) as planes:
-                bbox = planes.crop_zscore()
-                if bbox is not None:            # (None: a non-finite sample or sum - numpy below computes what numpy computes of it)
+            planes_device, plain = device_normalize, True
+        elif device_schemes is not None and _device_schemes_apply(data, tf, schemes, use_mask, fip):
+            planes_device, plain = device_schemes, False
+        if planes_device is not None:
+            with DevicePlanes(data, planes_device) as planes:
+                bbox = planes.crop_zscore() if plain else planes.crop_normalize(schemes, use_mask, fip)
+                if bbox is not None:            # (None: a non-finite sample or sum, an RGB sample out of range, an empty mask - numpy below computes, or raises, what numpy does)
                     properties['bbox_used_for_cropping'] = bbox
                     shape = properties['shape_after_cropping_and_before_resampling'] = planes.shape[1:]
                     new_shape = [int(round(i / j * k)) for i, j, k in zip(original_spacing, target_spacing, shape)]
@@ -620,7 +756,6 @@ class DefaultPreprocessor:
         new_shape = [int(round(i / j * k)) for i, j, k in zip(original_spacing, target_spacing, data.shape[1:])]
         if dz is not None and not _device_zscore_applies(dz, data, bbox, tf, schemes, use_mask):
             dz = None
-        fip = (getattr(plans_manager, 'plans', None) or {}).get('foreground_intensity_properties_per_channel', {})
         for c in range(data.shape[0]):
             if dz is not None:          # normalised on the device behind the projection (ts2d_project_coronal_zscore): no host pass
                 data[c, 0] = dz['norm'][dz['order'][c]]
