@@ -309,6 +309,36 @@ int ts2d_ensemble_predict_tiled_labelmap(ts2d_engine* const* engines, int n_engi
 int ts2d_labelmap_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
                               uint8_t* label_u8);
 
+/* ts2d_ensemble_predict_tiled_labelmap for a REGION-BASED model - nnU-Net's third label convention: the label values of dataset.json are
+ * lists of labels (nested or overlapping regions, BraTS style), the network has one head per foreground region, and the export is
+ * "resample the logits back, sigmoid in float32, then paint the regions in order" [UPSTREAM-RECALL: LabelManager.has_regions,
+ * convert_probabilities_to_segmentation]:
+ *     seg = 0;  for i, c in enumerate(regions_class_order): seg[prob[i] > 0.5] = c
+ * One kernel (csrc/kernels_regions.h) does all of it where the aggregation (or the mean of the folds) left the half logits, so ONE uint8
+ * plane of the ORIGINAL extent travels to the host.  Everything is as in ts2d_ensemble_predict_tiled_labelmap - engines, images, the
+ * descriptors (`maps`: label_u8 [out_h, out_w], not NULL), the fold mean, inf_flag, full_batch and its determinism rule, logits_f16 of
+ * an image asked for in the same call, the device scratch (+ n_order bytes in the call's table) - except the decision:
+ *   class_order    n_order class values (0 ... 255; they may repeat and may be 0), one per head, n_order == num_classes of the engines.
+ *   label_u8       per pixel class_order[i] of the HIGHEST head i whose value exceeds 1.5 * 2^-24 - the predicate of seg_u8 in
+ *                  ts2d_engine_predict_tiled: sigmoid(float32 v) > 0.5 - or 0 where no head does.  NaN is not above it, +inf is.  The value
+ *                  per head is that of ts2d_tiled_export.logits_f32, bit for bit, except where (out_h, out_w) == (src_h, src_w): the
+ *                  widened half itself, as in the label-map entry (so a zero weight on an infinite sample - NaN, not painted - arises
+ *                  only where the call resamples).  Restated in numpy as totalsegmentator2d_amd.export.regions_statement.
+ * Every argument is validated before any device work and nothing is written on an error: everything the label-map entry refuses, with
+ * "regions:" where that says "labelmap:"; a NULL class_order ("regions: the class order is null"); n_order != num_classes ("regions: 3
+ * class values for a model of 4 heads").  n_images == 0 returns TS2D_OK and does nothing.
+ * (Added under ABI 9: new symbols only, no existing signature or structure changes, so ts2d_abi_version() stays 9.) */
+int ts2d_ensemble_predict_tiled_regions(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_labelmap* maps,
+                                        int n_images, int patch_h, int patch_w, int mirror_mask, const uint16_t* gaussian_f16, int full_batch,
+                                        const uint8_t* class_order, int n_order);
+
+/* The region kernel of ts2d_ensemble_predict_tiled_regions on half planes the CALLER supplies - the twin of ts2d_labelmap_from_logits,
+ * with the same arguments and the same refusals, plus class_order: K class values, one per head (NULL: "regions: the class order is
+ * null"; a NULL label_u8: "regions: the output is null").  Same arithmetic, same predicate, same identity rule.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+int ts2d_regions_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
+                             const uint8_t* class_order, uint8_t* label_u8);
+
 /* Blend order of ts2d_engine_predict_tiled (upstream `prediction *= gaussian; predicted_logits[sl] += prediction` with
  * float16 `predicted_logits`; reached from ts2d/core/inference/prediction_worker.py:209):
  *   TS2D_TILE_F32 (default) the reference's CPU path (nnu.py:161-163: device=cpu when torch.cuda.is_available() is false - no autocast): the tile prediction is

@@ -66,6 +66,8 @@ SIGNATURES = {
     'ts2d_ensemble_predict_tiled_export': (_I, [_PP, _I, _TI, _TE, _I, _I, _I, _I, _P, _I]),
     'ts2d_ensemble_predict_tiled_labelmap': (_I, [_PP, _I, _TI, _TL, _I, _I, _I, _I, _P, _I]),
     'ts2d_labelmap_from_logits': (_I, [_I, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32 * 4), _I, _I, _P]),
+    'ts2d_ensemble_predict_tiled_regions': (_I, [_PP, _I, _TI, _TL, _I, _I, _I, _I, _P, _I, _P, _I]),
+    'ts2d_regions_from_logits': (_I, [_I, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32 * 4), _I, _I, _P, _P]),
     'ts2d_project_coronal': (_I, _PROJECT),
     'ts2d_project_coronal_zscore': (_I, _PROJECT + [_P, _P, _P]),
     'ts2d_resample_cubic': (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),

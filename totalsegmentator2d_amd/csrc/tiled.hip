@@ -1,11 +1,12 @@
 // The sliding window of libts2d_engine.so: tile gather, aggregation, the mean of an ensemble's folds and the export's resample-back, around
 // the engine's forward (engine.hip: reserve_checked, run_forward).  The C entries ts2d_engine_predict_tiled*, ts2d_ensemble_predict_tiled_export,
-// ts2d_ensemble_predict_tiled_labelmap and ts2d_labelmap_from_logits.
+// ts2d_ensemble_predict_tiled_labelmap, ts2d_ensemble_predict_tiled_regions, ts2d_labelmap_from_logits and ts2d_regions_from_logits.
 #include "engine_internal.h"
 #include "kernels_sw.h"
 #include "kernels_fold.h"
 #include "kernels_resample.h"
 #include "kernels_labelmap.h"
+#include "kernels_regions.h"
 
 #include <string>
 #include <vector>
@@ -35,12 +36,14 @@ int name_fold(int rc, bool name_folds, int f) {
 // the half slots and the flags exist F times.  `name_folds`: a fold's failed reserve or result check is reported as "fold <f>: ...".
 // `labelmap` (ts2d_ensemble_predict_tiled_labelmap): `exports` carry the label-map descriptors (seg_u8 = label_u8) - behind the last
 // aggregate (or the mean) ONE sw_labelmap launch (kernels_labelmap.h) in the place of sw_resample_threshold: ONE uint8 plane per image.
+// `class_order` (ts2d_ensemble_predict_tiled_regions; with `labelmap`, else null): the num_classes class values of a region-based model -
+// the label-map plan, the table riding in the call's one table blob, and ONE sw_regions launch (kernels_regions.h) in sw_labelmap's place.
 int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap,
-                       int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, bool full, bool name_images,
-                       bool name_folds, const char* entry) {
+                       const uint8_t* class_order, int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, bool full,
+                       bool name_images, bool name_folds, const char* entry) {
     ts2d_engine* e = engines[0];
     SwPlan pl;
-    TRY(plan_tiled(e, F, images, exports, labelmap, n_images, ph, pw, mirror_mask, name_images, entry, &pl));
+    TRY(plan_tiled(e, F, images, exports, labelmap, class_order, n_images, ph, pw, mirror_mask, name_images, entry, &pl));
     const int C = e->arch.input_channels, K = e->arch.num_classes, V = pl.V;
     for (int f = 0; f < F; ++f) TRY(name_fold(reserve_checked(engines[f], pl.cap_rows, ph, pw, full), name_folds, f));
     HIP_TRY(hipSetDevice(e->device));
@@ -91,8 +94,13 @@ int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* ima
     }
     uint8_t* d_rs8 = pl.any_rs8 ? reinterpret_cast<uint8_t*>(b + pl.o_rs8) : nullptr; float* d_rs32 = pl.any_rs32 ? reinterpret_cast<float*>(b + pl.o_rs32) : nullptr;
     if (labelmap) {
-        hipLaunchKernelGGL(sw_labelmap, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
-                           n_images, K, reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps), d_rs8);
+        const RsSeg* d_rsegs = reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs);
+        const RsTap* d_rtaps = reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps);
+        if (class_order)
+            hipLaunchKernelGGL(sw_regions, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, d_rsegs, n_images, K, d_rtaps,
+                               reinterpret_cast<const uint8_t*>(b + pl.o_tab + pl.tab_order), d_rs8, kSigmoidHalfThreshold);
+        else
+            hipLaunchKernelGGL(sw_labelmap, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, d_rsegs, n_images, K, d_rtaps, d_rs8);
         HIP_TRY(hipGetLastError());
         for (int i = 0; i < n_images; ++i)
             HIP_TRY(hipMemcpyAsync(exports[i].seg_u8, d_rs8 + pl.rsegs[i].dst_off, (size_t)exports[i].out_h * exports[i].out_w, hipMemcpyDeviceToHost, st));
@@ -157,71 +165,20 @@ int check_folds(const char* entry, ts2d_engine* const* engines, int n_engines, c
     return TS2D_OK;
 }
 
-}  // namespace
-#pragma GCC visibility pop
-
-extern "C" {
-
-int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp, int ph, int pw, int n_tiles,
-                              const int32_t* tile_y, const int32_t* tile_x, int mirror_mask, const uint16_t* gaussian_f16,
-                              uint16_t* logits_f16, uint8_t* seg_u8) {
-    if (!e || !image || !tile_y || !tile_x) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: null argument");
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
-    if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
-    ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
-    return predict_tiled_impl(&e, 1, &one, nullptr, false, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
-}
-
-int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
-                                    const uint16_t* gaussian_f16) {
-    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: null engine");
-    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
-    if (n_images == 0) return TS2D_OK;
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
-    return predict_tiled_impl(&e, 1, images, nullptr, false, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
-}
-
-int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
-                                     int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
-    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: null engine");
-    if (n_images < 0 || (n_images > 0 && !(images && exports)))
-        return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: %d images at a null pointer", n_images);
-    if (n_images == 0) return TS2D_OK;
-    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_export: weights not loaded");
-    return predict_tiled_impl(&e, 1, images, exports, false, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
-                              "ts2d_engine_predict_tiled_export");
-}
-
-int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_export* exports,
-                                       int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
-    static const char* entry = "ts2d_ensemble_predict_tiled_export";
-    int todo = 0;
-    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
-    if (!todo) return TS2D_OK;
-    return predict_tiled_impl(engines, n_engines, images, exports, false, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
-                              true, true, entry);
-}
-
-int ts2d_ensemble_predict_tiled_labelmap(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_labelmap* labelmaps,
-                                         int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
-    static const char* entry = "ts2d_ensemble_predict_tiled_labelmap";
-    int todo = 0;
-    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
-    if (!todo) return TS2D_OK;
-    if (!labelmaps) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
-    std::vector<ts2d_tiled_export> ex((size_t)n_images);      // the geometry of an export, ONE uint8 output
+// the descriptors of a label-map or region call as the geometry of an export with ONE uint8 output
+std::vector<ts2d_tiled_export> one_plane_exports(const ts2d_tiled_labelmap* maps, int n_images) {
+    std::vector<ts2d_tiled_export> ex((size_t)n_images);
     for (int i = 0; i < n_images; ++i) {
-        const ts2d_tiled_labelmap& lm = labelmaps[i];
+        const ts2d_tiled_labelmap& lm = maps[i];
         ex[i] = ts2d_tiled_export{lm.src_y, lm.src_x, lm.src_h, lm.src_w, lm.out_h, lm.out_w, lm.label_u8, nullptr};
     }
-    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, n_images, ph, pw, mirror_mask, gaussian_f16,
-                              full_batch ? kFullBatch : kBySize, true, true, entry);
+    return ex;
 }
 
-int ts2d_labelmap_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
-                              uint8_t* label_u8) {
-    static const char* entry = "ts2d_labelmap_from_logits";
-    if (!logits_f16 || !rect || !label_u8) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
+// ts2d_labelmap_from_logits and ts2d_regions_from_logits: the one-image kernel call on half planes of the caller's.
+// class_order null: sw_labelmap; else sw_regions with its K class values.
+int one_plane_from_logits(const char* entry, const char* what, int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4],
+                          int out_h, int out_w, const uint8_t* class_order, uint8_t* label_u8) {
     if (K < 1 || K > 256) return fail(TS2D_ERR_INVALID, "%s: %d heads outside 1 ... 256", entry, K);
     if (H < 1 || W < 1 || (long long)K * H * W >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: bad extent %d x %d x %d (2^31 elements at most)", entry, K, H, W);
     const ts2d_tiled_export ex{rect[0], rect[1], rect[2], rect[3], out_h, out_w, label_u8, nullptr};
@@ -234,21 +191,117 @@ int ts2d_labelmap_from_logits(int device, const uint16_t* logits_f16, int K, int
     std::vector<RsSeg> segs; std::vector<RsTap> rtaps;
     long long blocks = 0, elems = 0;
     rs_plan_segment(true, K, H, W, ex, 0, &segs, &rtaps, &blocks, &elems);
-    if (blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the labelmap exceeds 2^31 blocks", entry);
+    if (blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the %s exceeds 2^31 blocks", entry, what);
     HIP_TRY(hipSetDevice(device));
-    // [segment | taps | half planes | label map]
+    // [segment | taps | class order | half planes | label map]
     const size_t n_src = (size_t)K * H * W, n_dst = (size_t)out_h * out_w;
-    const size_t o_taps = align_up(sizeof(RsSeg), 8), o_src = align_up(o_taps + rtaps.size() * sizeof(RsTap), 256), o_dst = align_up(o_src + n_src * 2, 256);
+    const size_t o_taps = align_up(sizeof(RsSeg), 8), o_order = o_taps + rtaps.size() * sizeof(RsTap);
+    const size_t o_src = align_up(o_order + (class_order ? (size_t)K : 0), 256), o_dst = align_up(o_src + n_src * 2, 256);
     DevMem d;
     HIP_TRY(d.alloc(o_dst + n_dst));
     HIP_TRY(hipMemcpy(d.as<char>(), segs.data(), sizeof(RsSeg), hipMemcpyHostToDevice));
     if (!rtaps.empty()) HIP_TRY(hipMemcpy(d.as<char>(o_taps), rtaps.data(), rtaps.size() * sizeof(RsTap), hipMemcpyHostToDevice));
+    if (class_order) HIP_TRY(hipMemcpy(d.as<char>(o_order), class_order, (size_t)K, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_src), logits_f16, n_src * 2, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sw_labelmap, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(), 1, K,
-                       d.as<const RsTap>(o_taps), d.as<uint8_t>(o_dst));
+    if (class_order)
+        hipLaunchKernelGGL(sw_regions, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(), 1, K,
+                           d.as<const RsTap>(o_taps), d.as<const uint8_t>(o_order), d.as<uint8_t>(o_dst), kSigmoidHalfThreshold);
+    else
+        hipLaunchKernelGGL(sw_labelmap, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(), 1, K,
+                           d.as<const RsTap>(o_taps), d.as<uint8_t>(o_dst));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(label_u8, d.as<uint8_t>(o_dst), n_dst, hipMemcpyDeviceToHost));
     return TS2D_OK;
+}
+
+}  // namespace
+#pragma GCC visibility pop
+
+extern "C" {
+
+int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp, int ph, int pw, int n_tiles,
+                              const int32_t* tile_y, const int32_t* tile_x, int mirror_mask, const uint16_t* gaussian_f16,
+                              uint16_t* logits_f16, uint8_t* seg_u8) {
+    if (!e || !image || !tile_y || !tile_x) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: null argument");
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
+    if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
+    ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
+    return predict_tiled_impl(&e, 1, &one, nullptr, false, nullptr, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
+}
+
+int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
+                                    const uint16_t* gaussian_f16) {
+    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: null engine");
+    if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
+    if (n_images == 0) return TS2D_OK;
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
+    return predict_tiled_impl(&e, 1, images, nullptr, false, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
+}
+
+int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
+                                     int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
+    if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: null engine");
+    if (n_images < 0 || (n_images > 0 && !(images && exports)))
+        return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: %d images at a null pointer", n_images);
+    if (n_images == 0) return TS2D_OK;
+    if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_export: weights not loaded");
+    return predict_tiled_impl(&e, 1, images, exports, false, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
+                              "ts2d_engine_predict_tiled_export");
+}
+
+int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_export* exports,
+                                       int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
+    static const char* entry = "ts2d_ensemble_predict_tiled_export";
+    int todo = 0;
+    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    if (!todo) return TS2D_OK;
+    return predict_tiled_impl(engines, n_engines, images, exports, false, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
+                              true, true, entry);
+}
+
+int ts2d_ensemble_predict_tiled_labelmap(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_labelmap* labelmaps,
+                                         int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
+    static const char* entry = "ts2d_ensemble_predict_tiled_labelmap";
+    int todo = 0;
+    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    if (!todo) return TS2D_OK;
+    if (!labelmaps) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
+    const std::vector<ts2d_tiled_export> ex = one_plane_exports(labelmaps, n_images);
+    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16,
+                              full_batch ? kFullBatch : kBySize, true, true, entry);
+}
+
+int ts2d_ensemble_predict_tiled_regions(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_labelmap* maps,
+                                        int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch,
+                                        const uint8_t* class_order, int n_order) {
+    static const char* entry = "ts2d_ensemble_predict_tiled_regions";
+    int todo = 0;
+    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    if (!todo) return TS2D_OK;
+    if (!maps) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
+    if (!class_order) return fail(TS2D_ERR_INVALID, "%s: regions: the class order is null", entry);
+    const int K = engines[0]->arch.num_classes;
+    if (n_order != K) return fail(TS2D_ERR_INVALID, "%s: regions: %d class values for a model of %d heads", entry, n_order, K);
+    if (K > 256) return fail(TS2D_ERR_INVALID, "%s: regions: %d heads outside 1 ... 256", entry, K);
+    const std::vector<ts2d_tiled_export> ex = one_plane_exports(maps, n_images);
+    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, class_order, n_images, ph, pw, mirror_mask, gaussian_f16,
+                              full_batch ? kFullBatch : kBySize, true, true, entry);
+}
+
+int ts2d_labelmap_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
+                              uint8_t* label_u8) {
+    static const char* entry = "ts2d_labelmap_from_logits";
+    if (!logits_f16 || !rect || !label_u8) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
+    return one_plane_from_logits(entry, "labelmap", device, logits_f16, K, H, W, rect, out_h, out_w, nullptr, label_u8);
+}
+
+int ts2d_regions_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
+                             const uint8_t* class_order, uint8_t* label_u8) {
+    static const char* entry = "ts2d_regions_from_logits";
+    if (!logits_f16 || !rect) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
+    if (!class_order) return fail(TS2D_ERR_INVALID, "%s: regions: the class order is null", entry);
+    if (!label_u8) return fail(TS2D_ERR_INVALID, "%s: regions: the output is null", entry);
+    return one_plane_from_logits(entry, "regions", device, logits_f16, K, H, W, rect, out_h, out_w, class_order, label_u8);
 }
 
 int ts2d_engine_tiled_inf_flag(const ts2d_engine* e) { return e ? (e->tiled_inf != 0) : 0; }

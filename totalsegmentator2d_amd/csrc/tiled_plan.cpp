@@ -32,11 +32,12 @@ void rs_axis_taps(int n_in, int n_out, int origin, RsTap* t) {
 }
 
 // every image (and its export descriptor) on its own; the totals that bound the tables
-// `labelmap`: the descriptors are those of a label-map call (ONE output plane per image: seg_u8 is its label_u8) and are named so
-int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, int n_images, int ph,
-                 int pw, bool name_images, const char* entry, SwPlan* pl) {
+// `labelmap`: the descriptors are those of a label-map call (ONE output plane per image: seg_u8 is its label_u8) and are named so;
+// `regions`: of a region call - the same descriptors under that name
+int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, bool regions, int n_images,
+                 int ph, int pw, bool name_images, const char* entry, SwPlan* pl) {
     long long n_taps_all = 0;
-    const char* what = labelmap ? "labelmap" : "export";
+    const char* what = regions ? "regions" : labelmap ? "labelmap" : "export";
     pl->any16 = F > 1;      // (the mean is taken over the half buffers)
     for (int i = 0; i < n_images; ++i) {
         const ts2d_tiled_image& im = images[i];
@@ -118,14 +119,14 @@ int pack_rows(int F, int C, int K, const ts2d_tiled_image* images, int n_images,
 
 // The export: one segment per image (its half logits are segs' out_off), the taps of its rows then of its columns.
 // rs_elems: elements of the resampled outputs.
-int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, int n_images, const char* entry,
-                SwPlan* pl, std::vector<RsTap>* rtaps, long long* rs_elems) {
+int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, bool regions, int n_images,
+                const char* entry, SwPlan* pl, std::vector<RsTap>* rtaps, long long* rs_elems) {
     long long oo = 0;
     for (int i = 0; i < n_images; ++i) {
         rs_plan_segment(labelmap, K, images[i].Hp, images[i].Wp, exports[i], oo, &pl->rsegs, rtaps, &pl->rs_blocks, rs_elems);
         oo += (long long)align_up((size_t)K * images[i].Hp * images[i].Wp, 256);
     }
-    if (pl->rs_blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the %s exceeds 2^31 blocks", entry, labelmap ? "labelmap" : "export");
+    if (pl->rs_blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the %s exceeds 2^31 blocks", entry, regions ? "regions" : labelmap ? "labelmap" : "export");
     return TS2D_OK;
 }
 
@@ -150,8 +151,8 @@ void rs_plan_segment(bool labelmap, int K, int Hp, int Wp, const ts2d_tiled_expo
     *rs_elems += (long long)align_up((size_t)planes * ex.out_h * ex.out_w, 256);
 }
 
-int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, int n_images,
-               int ph, int pw, int mirror_mask, bool name_images, const char* entry, SwPlan* pl) {
+int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap,
+               const uint8_t* class_order, int n_images, int ph, int pw, int mirror_mask, bool name_images, const char* entry, SwPlan* pl) {
     if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "%s: bad patch %dx%d", entry, ph, pw);
     const int C = e->arch.input_channels, K = e->arch.num_classes;
     int vflip[4] = {0, 0, 0, 0};
@@ -161,14 +162,17 @@ int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, cons
     pl->vflips = vflip[0] | (vflip[1] << 8) | (vflip[2] << 16) | (vflip[3] << 24);
     long long img_floats = 0, log_rows = 0, rs_elems = 0;
     std::vector<RsTap> rtaps;
-    TRY(check_images(F, C, K, images, exports, labelmap, n_images, ph, pw, name_images, entry, pl));
+    const bool regions = class_order != nullptr;
+    TRY(check_images(F, C, K, images, exports, labelmap, regions, n_images, ph, pw, name_images, entry, pl));
     TRY(pack_rows(F, C, K, images, n_images, ph, pw, entry, pl, &img_floats, &log_rows));
-    if (exports) TRY(plan_export(K, images, exports, labelmap, n_images, entry, pl, &rtaps, &rs_elems));
+    if (exports) TRY(plan_export(K, images, exports, labelmap, regions, n_images, entry, pl, &rtaps, &rs_elems));
     // ---- the descriptor table and every tile origin
     const size_t n_tiles = (size_t)pl->n_tiles_all;
     pl->tab_segs = pl->segs.size() * sizeof(SwSeg); pl->tab_rsegs = align_up(pl->tab_segs + 2 * n_tiles * 4, 8);
     pl->tab_rtaps = pl->tab_rsegs + pl->rsegs.size() * sizeof(RsSeg);
-    pl->tab.resize(pl->tab_rtaps + rtaps.size() * sizeof(RsTap));
+    pl->tab_order = pl->tab_rtaps + rtaps.size() * sizeof(RsTap);
+    pl->tab.resize(pl->tab_order + (regions ? (size_t)K : 0));
+    if (regions) memcpy(pl->tab.data() + pl->tab_order, class_order, (size_t)K);      // (K == n_order: the entry has checked it)
     memcpy(pl->tab.data(), pl->segs.data(), pl->tab_segs);
     if (exports) {
         memcpy(pl->tab.data() + pl->tab_rsegs, pl->rsegs.data(), pl->rsegs.size() * sizeof(RsSeg));

@@ -452,6 +452,55 @@ def labelmap_from_logits(logits_f16: np.ndarray, rect, out_hw, device: int = 0) 
     return out
 
 
+def _class_order_u8(class_order, what: str) -> np.ndarray:
+    """The class-order table of a region-based model as the K bytes the library takes; a value outside uint8 is refused here."""
+    order = [int(c) for c in class_order]
+    if any(c < 0 or c > 255 for c in order):
+        raise RuntimeError(f"{what}: a class value outside 0..255 does not fit the uint8 output plane: {order}")
+    return np.array(order, dtype=np.uint8)
+
+
+def predict_tiled_regions_ensemble(engines, images, patch, tiles, rects, class_order, mirror_axes=None, gaussian: Optional[np.ndarray] = None,
+                                   want_logits: bool = False, full_batch: bool = True):
+    """:func:`predict_tiled_labelmap_ensemble` for a REGION-BASED model (C-ABI ts2d_ensemble_predict_tiled_regions): the same sliding
+    window per fold, the same mean, the same descriptors, then per image the resample-back of the half logits, the export's predicate
+    ``sigmoid(float32 v) > 0.5`` per head and the painting in order on the device (csrc/kernels_regions.h).  ``class_order``: one class
+    value (0..255) per head, ``regions_class_order`` of the model's ``dataset.json``.  Returns ``(labels, logits)``: lists of uint8
+    [out_h,out_w] - ``export.regions_statement`` of the half logits, byte for byte - and of float16 [K,Hp,Wp] (None unless asked for)."""
+    engines = list(engines)
+    if not engines:
+        raise RuntimeError("predict_tiled_regions_ensemble: no engines")
+    if rects is None:
+        raise RuntimeError("predict_tiled_regions_ensemble: the maps need their rectangles and extents")
+    order = _class_order_u8(class_order, 'predict_tiled_regions_ensemble')
+    desc, lmd, mask, g, keep, outs = engines[0]._tiled_args('predict_tiled_regions_ensemble', images, tiles, rects, mirror_axes, gaussian,
+                                                            True, False, want_logits, False, labelmap=True)
+    handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
+    _lib.check(engines[0].lib.ts2d_ensemble_predict_tiled_regions(handles, len(engines), desc, lmd, len(images), int(patch[0]), int(patch[1]),
+                                                                  mask, g, int(bool(full_batch)), order.ctypes.data, int(order.size)),
+               'ts2d_ensemble_predict_tiled_regions')
+    _read_tiled_inf(engines, desc, len(images), engine_flags=True)
+    del keep
+    return outs[0], outs[2]
+
+
+def regions_from_logits(logits_f16: np.ndarray, rect, out_hw, class_order, device: int = 0) -> np.ndarray:
+    """The region kernel on half planes of the caller's (C-ABI ts2d_regions_from_logits): float16 [K,H,W], ``rect = (y, x, h, w)`` inside
+    it, resampled to ``out_hw``, thresholded per head and painted in order -> uint8 [out_h,out_w] = ``export.regions_statement``."""
+    lg = np.ascontiguousarray(logits_f16, dtype=np.float16)
+    if lg.ndim != 3:
+        raise RuntimeError(f"expected [K,H,W], found shape {lg.shape}")
+    order = _class_order_u8(class_order, 'regions_from_logits')
+    if order.size != lg.shape[0]:
+        raise RuntimeError(f"regions_from_logits: {order.size} class values for {lg.shape[0]} heads")
+    oh, ow = (int(v) for v in out_hw)
+    out = np.empty((max(oh, 0), max(ow, 0)), dtype=np.uint8)
+    r = (ctypes.c_int32 * 4)(*[int(v) for v in rect])
+    _lib.check(_lib.load().ts2d_regions_from_logits(int(device), lg.ctypes.data, lg.shape[0], lg.shape[1], lg.shape[2], ctypes.byref(r), oh, ow,
+                                                    order.ctypes.data, out.ctypes.data), 'ts2d_regions_from_logits')
+    return out
+
+
 def _read_tiled_inf(engines, desc, n_images, engine_flags: bool):
     """The inf flags a tiled call left behind (upstream's inf check, done on the device).  With descriptors, ``last_tiled_inf_per_image``
     of the first engine is their per-image flags; ``last_tiled_inf`` of every engine is its own flag in the library (the flat entry and

@@ -41,10 +41,41 @@ def labelmap_statement(logits_f16, rect, out_hw) -> np.ndarray:
     return lg.argmax(0).astype(np.uint8)
 
 
+def paint_regions(above, class_order) -> np.ndarray:
+    """nnU-Net's ``convert_probabilities_to_segmentation`` of a region-based model [UPSTREAM-RECALL], on the thresholded heads
+    ``above`` [K, ...] (bool: ``sigmoid(logit) > 0.5``): ``seg = 0; for i, c in enumerate(regions_class_order): seg[above[i]] = c`` -
+    the highest head above one half decides a pixel; class values may repeat and may be 0.  uint8 [...]."""
+    above = np.asarray(above)
+    if len(class_order) != above.shape[0]:
+        raise ValueError(f"regions_class_order has {len(class_order)} entries, the prediction {above.shape[0]} heads")
+    seg = np.zeros(above.shape[1:], dtype=np.uint8)
+    for i, c in enumerate(class_order):
+        seg[above[i]] = c
+    return seg
+
+
+def regions_statement(logits_f16, rect, out_hw, class_order) -> np.ndarray:
+    """The numpy statement of the device export of a REGION-BASED model (csrc/kernels_regions.h; C-ABI
+    ts2d_ensemble_predict_tiled_regions and ts2d_regions_from_logits): the rectangle ``rect = (y, x, h, w)`` of the aggregated half
+    logits [K, Hp, Wp] widened to float32, every plane resampled to ``out_hw`` by :func:`preprocess.resize_linear_f64` - NOT where
+    ``out_hw == (h, w)``, as in :func:`labelmap_statement` - then the export's predicate ``sigmoid(float32 v) > 0.5``, that is
+    ``v > SIGMOID_HALF_THRESHOLD`` (NaN is not above it, +inf is), and :func:`paint_regions` in ``class_order``.  uint8 [out_h, out_w]."""
+    from .preprocess import resize_linear_f64
+    y, x, h, w = (int(v) for v in rect)
+    out_hw = tuple(int(v) for v in out_hw)
+    lg = np.asarray(logits_f16)[:, y:y + h, x:x + w].astype(np.float32)
+    if out_hw != (h, w):
+        with np.errstate(invalid='ignore'):          # (a zero weight on an infinite sample: NaN, not painted)
+            lg = np.stack([resize_linear_f64(pl, out_hw) for pl in lg])
+    return paint_regions(lg > SIGMOID_HALF_THRESHOLD, class_order)
+
+
 def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties: dict, multilabel: bool = True,
-                                                                transpose_backward=(0, 1, 2)) -> np.ndarray:
+                                                                transpose_backward=(0, 1, 2), regions=None) -> np.ndarray:
     """[K, Z, H, W] logits (any float dtype) -> uint8 segmentation in the ORIGINAL (pre-crop) array shape:
-    multilabel: [K, Z0, H0, W0] of {0,1}; otherwise a label map [Z0, H0, W0] (argmax).  Upstream first resamples the logits back to
+    multilabel: [K, Z0, H0, W0] of {0,1}; otherwise a label map [Z0, H0, W0] - the argmax over the heads or, with ``regions`` (the
+    ``regions_class_order`` of a region-based model, one class value per head), ``sigmoid > 0.5`` per head painted in that order.
+    Upstream first resamples the logits back to
     ``properties['shape_after_cropping_and_before_resampling']`` (``resampling_fn_probabilities``: order 1, per slice for the 2-D
     configurations [UPSTREAM-RECALL]) - a no-op when the plan's spacing is the image's."""
     lg = np.asarray(logits)
@@ -69,10 +100,14 @@ def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properti
         out[(slice(None),) + sl] = seg
         return out.transpose([0] + [i + 1 for i in transpose_backward])
     if lg.dtype == np.uint8:
-        # already resampled and decided on the device (HIPnnUNetPredictor.predict_labelmap_from_preprocessed_data): ONE plane of labels
+        # already resampled and decided on the device (HIPnnUNetPredictor.predict_labelmap_from_preprocessed_data): ONE plane of labels,
+        # the argmax of a label-map model or the painted regions of a region-based one
         if lg.shape[0] != 1:
             raise ValueError(f"a uint8 prediction of a label-map model is one plane of labels, found {lg.shape[0]}")
         seg = lg[0]
+    elif regions is not None:
+        # [UPSTREAM-RECALL] the sigmoid in float32, > 0.5, the painting loop: on the host for whatever the device did not decide
+        seg = paint_regions(lg.astype(np.float32) > SIGMOID_HALF_THRESHOLD, regions)
     else:
         seg = lg.astype(np.float32).argmax(0).astype(np.uint8)
     out = np.zeros(shape0, dtype=np.uint8)
@@ -101,9 +136,11 @@ def segmentation_to_image(seg: np.ndarray, ref: nrrd.Image, multilabel: bool, la
 def export_prediction_from_logits(logits, properties: dict, configuration_manager, plans_manager, dataset_json: dict,
                                   ofile_truncated: str, save_probabilities: bool = False, ref_image: Optional[nrrd.Image] = None,
                                   labels: Optional[Dict[int, str]] = None, colors: Optional[dict] = None) -> nrrd.Image:
-    multilabel = bool(dataset_json.get('multilabel', dataset_json.get('multiclass', False)))
+    from .labels import label_convention
+    conv = label_convention(dataset_json)
+    multilabel = conv.kind == 'multilabel'
     tb = getattr(plans_manager, 'transpose_backward', [0, 1, 2])
-    seg = convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties, multilabel, tb)
+    seg = convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties, multilabel, tb, regions=conv.class_order)
     if ref_image is None:
         ref_image = nrrd.read(properties['sitk_stuff']['files'][0])
     img = segmentation_to_image(seg, ref_image, multilabel, labels, colors)

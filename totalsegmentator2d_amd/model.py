@@ -17,6 +17,7 @@ import numpy as np
 
 from . import nrrd
 from .export import export_prediction_from_logits, needs_logits
+from .labels import label_convention
 from .predictor import HIPnnUNetPredictor
 
 
@@ -40,6 +41,7 @@ class HIPModel:
         self._dataset_json: Optional[dict] = None
         self.device_threshold = True     # thresholded segmentation straight from the device where the export needs no logits (_run)
         self.device_labelmap = True      # a label-map (non-multilabel) model: resample-back and argmax on the device, ONE uint8 plane to the host (_run); the host route's bytes
+        self.device_regions = True       # a region-based model (label values are lists + regions_class_order): resample-back, sigmoid predicate and painting in class order on the device, ONE uint8 plane to the host (_run); the host route's bytes
         self.device_input_resample = True   # order-3 resample of an off-spacing case's input on the device: the same float32 values as scipy, bit for bit (preprocess.resize_cubic_f64)
         self.device_input_normalize = True  # crop box, z-score (and that resample) of a native 2-D input on device-resident planes: the same float32 values as numpy, bit for bit (preprocess.zscore_f32_statement)
         self.device_input_normalize_schemes = True  # the same for every other nnU-Net scheme (masked z-score, CT, Rescale, RGB, none): the cases device_input_normalize leaves to numpy, the same bits (preprocess.*_f32_statement)
@@ -61,8 +63,7 @@ class HIPModel:
             self._data_dir = os.path.join(root, task, trainer)
             with open(os.path.join(self._data_dir, 'dataset.json')) as f:
                 self._dataset_json = json.load(f)
-        lab = self._dataset_json.get('labels', {})
-        self.labels = {int(v): k for k, v in lab.items() if k != 'background'}
+        self.labels = label_convention(self._dataset_json).names      # (a region-based model: {class value: region name})
 
     @property
     def name(self):
@@ -258,7 +259,8 @@ class HIPModel:
         # plan's) joins with the extent it had before resampling: the device resamples the logits back (order 1) in front of the
         # threshold and the export step receives uint8 planes already in that extent.  The reference's seam
         # (predict_logits_from_preprocessed_data + export_prediction_from_logits) stays as it is and serves every other case
-        multilabel = bool(p.dataset_json.get('multilabel', p.dataset_json.get('multiclass', False)))
+        kind = label_convention(p.dataset_json).kind
+        multilabel = kind == 'multilabel'
         can_seg = self.device_threshold and multilabel and hasattr(p, 'predict_segmentation_from_preprocessed_data' + ('_batch' if batched else ''))
         # (a foreign predictor, or a double of the engine method, that knows the fast path but not its `out_shape(s)` keyword keeps
         #  the host route for resampled cases, as before the device export existed)
@@ -267,12 +269,14 @@ class HIPModel:
             and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, 'out_shapes'))
         # a label-map model (the ordinary nnU-Net head): the same two host steps - resample-back, then the argmax over the heads - on the
         # device, ONE uint8 plane per case to the host; the export step receives it as the decided label map.  Only a predictor that has
-        # the method (and, where it is a double of the engine method, its `labelmap` keyword) takes this route
+        # the method (and, where it is a double of the engine method, its `labelmap` keyword) takes this route.  A region-based model goes
+        # the same way under its own switch and keyword (`regions`: sigmoid predicate per head, painted in class order, kernels_regions.h)
         lm_name = 'predict_labelmap_from_preprocessed_data'
         lm_fn = getattr(p, lm_name + ('_batch' if batched else ''), None)
-        can_lm = getattr(self, 'device_labelmap', False) and not multilabel and lm_fn is not None \
+        switch, keyword = ('device_regions', 'regions') if kind == 'regions' else ('device_labelmap', 'labelmap')
+        can_lm = getattr(self, switch, False) and not multilabel and lm_fn is not None \
             and self._takes(lm_fn, 'out_shapes' if batched else 'out_shape') \
-            and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, 'labelmap'))
+            and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, keyword))
 
         def target(t):
             """The extent the device export resamples case `t` to: None = none needed, False = not a case for it (a stack, a 3-D plan,

@@ -109,6 +109,7 @@ class HIPnnUNetPredictor:
         self.allowed_mirroring_axes = None
         self.list_of_parameters: List[np.ndarray] = []
         self.label_manager = None
+        self.regions_class_order = None      # a region-based model (labels.label_convention): the class value each head paints; else None
 
     # ------------------------------------------------------------------ initialisation
     def manual_initialization(self, arch: UNetArch, fold_blobs: Sequence[np.ndarray], patch_size: Sequence[int],
@@ -123,6 +124,8 @@ class HIPnnUNetPredictor:
             'channel_names': {str(i): f'ch{i}' for i in range(arch.input_channels)},
             'labels': {'background': 0, **{f'label{i + 1}': i + 1 for i in range(arch.num_classes)}},
             'file_ending': '.nrrd', 'multilabel': True}
+        from .labels import label_convention
+        self.regions_class_order = label_convention(self.dataset_json).class_order
         self.plans_manager = SimpleNamespace(plans=plans or {}, transpose_forward=[0, 1, 2], transpose_backward=[0, 1, 2])
         self.configuration_manager = SimpleNamespace(
             patch_size=list(patch_size), spacing=list(spacing), preprocessor_class=DefaultPreprocessor,
@@ -143,10 +146,8 @@ class HIPnnUNetPredictor:
             use_folds = [use_folds]
         blobs, mirror, configuration = [], None, None
         n_in = len(dataset_json['channel_names'])
-        labels = dataset_json['labels']
-        multilabel = bool(dataset_json.get('multilabel', dataset_json.get('multiclass', False)))
-        n_fg = len([k for k, v in labels.items() if k != 'background' and v != 0])
-        n_heads = n_fg if multilabel else len(labels)
+        from .labels import label_convention
+        n_heads = label_convention(dataset_json).n_heads      # (a region-based model: one head per foreground region)
         for i, f in enumerate(use_folds):
             f = int(f) if f != 'all' else f
             sd, mirror_axes, init_args = W.load_checkpoint(os.path.join(model_training_output_dir, f'fold_{f}', checkpoint_name))
@@ -182,7 +183,7 @@ class HIPnnUNetPredictor:
                     'value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32')
 
     def _sliding_window_batch(self, list_of_data, fold: Optional[int] = 0, want_seg: bool = False, one_call: bool = True, out_shapes=None,
-                              labelmap: bool = False):
+                              labelmap: bool = False, regions=None):
         """One fold, N inputs [C,Z,H,W]: pad, tile, tiles x mirror variants through the engine, upstream's fp16 Gaussian aggregation
         on the device.  Every z slice of every input is one image.  ``one_call``: all images in ONE engine call (C-ABI
         ts2d_engine_predict_tiled_batch: the network takes the full-batch dispatch, an input's bytes do not depend on its batch-mates,
@@ -200,24 +201,30 @@ class HIPnnUNetPredictor:
         ``fold`` or, with None, every fold and their mean; the device resamples every input's logits to its extent of ``out_shapes``
         (None = its own: no resampling) and takes the argmax over the heads there (:func:`export.labelmap_statement`, byte for byte):
         uint8 [1,1,h,w] per input.
+        ``regions`` (a region-based model: its ``regions_class_order``, one class value per head; single-slice inputs): the same call
+        shape through C-ABI ts2d_ensemble_predict_tiled_regions - the device resamples as for ``labelmap``, thresholds every head with the
+        export's predicate and paints the regions in that order (:func:`export.regions_statement`, byte for byte): uint8 [1,1,h,w] per input.
         (The one method that touches the engine, under the name the test infrastructure overrides: tests/batch_util.py replaces it, and
         tests/host_predictor.py predict_sliding_window_return_logits, with the host restatement.)"""
         patch = tuple(self.configuration_manager.patch_size)
         ensemble = fold is None
-        images, tiles, owner, reverts, shapes = self._pad_and_tile(list_of_data, patch, single_slice=ensemble or labelmap)
+        images, tiles, owner, reverts, shapes = self._pad_and_tile(list_of_data, patch, single_slice=ensemble or labelmap or regions is not None)
         if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
             raise AssertionError('mirror_axes does not match the dimension of the input!')
         g = sw.compute_gaussian(patch) if self.use_gaussian else None
         axes = self.allowed_mirroring_axes if self.use_mirroring else None
         e = None if ensemble else self.engines[fold]
-        if labelmap:
-            from .engine import predict_tiled_labelmap_ensemble
+        if labelmap or regions is not None:
+            from .engine import predict_tiled_labelmap_ensemble, predict_tiled_regions_ensemble
             rects = self._export_rects(list_of_data, reverts, shapes, out_shapes if out_shapes is not None else [None] * len(list_of_data), True)
             engines = self.engines if ensemble else [e]
             planes, inf = [], []
             for grp in ([range(len(images))] if one_call else [[j] for j in range(len(images))]):
-                planes += predict_tiled_labelmap_ensemble(engines, [images[j] for j in grp], patch, [tiles[j] for j in grp], [rects[j] for j in grp],
-                                                          axes, g, full_batch=one_call)[0]
+                args = ([images[j] for j in grp], patch, [tiles[j] for j in grp], [rects[j] for j in grp])
+                if regions is not None:
+                    planes += predict_tiled_regions_ensemble(engines, *args, tuple(regions), axes, g, full_batch=one_call)[0]
+                else:
+                    planes += predict_tiled_labelmap_ensemble(engines, *args, axes, g, full_batch=one_call)[0]
                 inf += engines[0].last_tiled_inf_per_image
             self._raise_on_inf(inf, owner, one_call)
             return [p[None, None] for p in planes]
@@ -335,6 +342,12 @@ class HIPnnUNetPredictor:
         kw = {} if hw is None else {'out_shapes': [hw]}
         return self._sliding_window_batch([data], None if ensemble else 0, want_seg=True, one_call=False, **kw)[0]
 
+    def _decision(self) -> dict:
+        """The keyword of :meth:`_sliding_window_batch` that decides the map of this model: ``labelmap`` (argmax over the heads) or, for a
+        region-based model, ``regions`` (its class order)."""
+        order = getattr(self, 'regions_class_order', None)
+        return {'labelmap': True} if order is None else {'regions': tuple(order)}
+
     def predict_labelmap_from_preprocessed_data(self, data, out_shape=None):
         """The twin of :meth:`predict_segmentation_from_preprocessed_data` for a LABEL-MAP model (the ordinary nnU-Net head: one head per
         label, background at 0): the export's order-1 resample-back and the argmax over the heads ON THE DEVICE (kernels_labelmap.h), so
@@ -342,7 +355,10 @@ class HIPnnUNetPredictor:
         extent of ``out_shape`` (the case's ``shape_after_cropping_and_before_resampling``, (h, w) or (1, h, w); None: the preprocessed
         geometry) - or None when the case keeps the logits route (3-D stacks; a predictor without engines; a bad ``out_shape``).  A fold
         ensemble runs every fold in one engine call, the mean of the folds in front of the argmax.  The bytes are those of
-        :meth:`predict_logits_from_preprocessed_data` + the host export (``resample_data_to_shape(order=1)`` + ``argmax``)."""
+        :meth:`predict_logits_from_preprocessed_data` + the host export (``resample_data_to_shape(order=1)`` + ``argmax``).
+        A REGION-BASED model (``regions_class_order`` is set) takes the same route with its own decision: the sigmoid's predicate per
+        head and the painting in class order (kernels_regions.h) in the place of the argmax - the decided map of whatever non-multilabel
+        convention the model has."""
         data = _to_numpy(data)
         ensemble = self._device_ensemble()
         if not (ensemble or len(self.list_of_parameters) == len(self.engines) == 1) or data.ndim != 4 or data.shape[1] != 1:
@@ -350,7 +366,7 @@ class HIPnnUNetPredictor:
         hw = self._in_plane(out_shape, data)
         if hw is False:
             return None
-        return self._sliding_window_batch([data], None if ensemble else 0, one_call=False, out_shapes=[hw], labelmap=True)[0]
+        return self._sliding_window_batch([data], None if ensemble else 0, one_call=False, out_shapes=[hw], **self._decision())[0]
 
     def predict_labelmap_from_preprocessed_data_batch(self, list_of_data, out_shapes=None):
         """:meth:`predict_labelmap_from_preprocessed_data` for a list of inputs: uint8 [1,1,h,w] per input from ONE engine call (every
@@ -367,7 +383,7 @@ class HIPnnUNetPredictor:
         hws = [self._in_plane(s, d) for s, d in zip(out_shapes, datas)] if out_shapes is not None else [None] * len(datas)
         if any(hw is False for hw in hws):
             return None
-        return self._sliding_window_batch(datas, None if ensemble else 0, out_shapes=hws, labelmap=True)
+        return self._sliding_window_batch(datas, None if ensemble else 0, out_shapes=hws, **self._decision())
 
     def predict_logits_from_preprocessed_data(self, data):
         """Fold ensemble (upstream: sum over ``list_of_parameters`` then ``/= n``).  Accepts numpy or torch [C,1,H,W];
