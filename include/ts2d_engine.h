@@ -339,6 +339,65 @@ int ts2d_ensemble_predict_tiled_regions(ts2d_engine* const* engines, int n_engin
 int ts2d_regions_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
                              const uint8_t* class_order, uint8_t* label_u8);
 
+/* The PROBABILITIES of the export - `save_probabilities=True` of the reference's predictor (ts2d/core/inference/predictor.py:99-111, passed to
+ * export_prediction_from_logits, prediction_worker.py:215-221) - from the device, for every label convention, with the decided map of
+ * the same pass: upstream resamples the logits back (order 1), applies the inference non-linearity in float32 - the sigmoid per head for a
+ * multilabel or region-based model, the softmax over the heads for a label-map model - and reverts the crop on the probabilities: outside
+ * the crop box they are 0, except head 0 of a label-map model, which is 1 [UPSTREAM-RECALL: LabelManager.apply_inference_nonlin,
+ * revert_cropping_on_probabilities].  One kernel (csrc/kernels_prob.h) does all of it where the aggregation (or the mean of the folds)
+ * left the half logits and writes the planes of the PRE-CROP extent, fill included.
+ *   engines, images, full_batch, the fold mean, inf_flag: as in ts2d_ensemble_predict_tiled_labelmap.
+ *   mode           TS2D_PROB_MULTILABEL (sigmoid; decided_u8 [K, full_h, full_w]: value > 1.5 * 2^-24 per head), TS2D_PROB_LABELMAP
+ *                  (softmax; decided_u8 [full_h, full_w]: the label map of ts2d_ensemble_predict_tiled_labelmap) or TS2D_PROB_REGIONS
+ *                  (sigmoid; decided_u8 [full_h, full_w]: the painted regions of ts2d_ensemble_predict_tiled_regions, class_order and
+ *                  n_order as there; both are ignored in the other modes).
+ *   probabilities  n_images descriptors.  (src_y, src_x, src_h, src_w) and (out_h, out_w) mean what they mean in ts2d_tiled_export;
+ *                  (full_h, full_w): the extent before cropping; (box_y, box_x): where the [out_h, out_w] rectangle sits in it.
+ *                  prob_f32 [K, full_h, full_w], not NULL.  The value v per head is that of ts2d_tiled_export.logits_f32, bit for bit,
+ *                  except where (out_h, out_w) == (src_h, src_w): the widened half itself, as in the label-map entry.  Sigmoid:
+ *                  1 / (1 + exp(-v)); softmax: exp(v - max) / sum_k exp(v_k - max), the sum in head order; float32 with a correctly
+ *                  rounded add and division, exp the float64 function rounded once to float32.  A NaN logit gives a NaN probability; the
+ *                  softmax of a pixel with a +inf or NaN head is NaN in every head, a -inf head gives 0 (torch.softmax on the CPU).  Outside
+ *                  the box: 0, or 1 in head 0 of TS2D_PROB_LABELMAP.  Not bit for bit the host route's values (another exp): within a few
+ *                  float32 units of them (tests/test_gpu_probabilities.py); restated in numpy as export.probabilities_statement.
+ *                  decided_u8, or NULL: decided on the LOGIT value with the predicate / comparator of the entries named above, never on
+ *                  the probability - byte for byte what those entries write into the box - and 0 outside the box.
+ * Every argument is validated before any device work and nothing is written on an error: what the label-map and region entries refuse,
+ * in the same words with "probabilities:" where they say "labelmap:" / "regions:"; a rectangle that leaves the full extent; a NULL
+ * prob_f32 ("probabilities: the output is null"); an unknown mode; K x full_h x full_w of 2^31 or more; fewer than 1 or more than 256 heads, in
+ * every mode and in both entries ("probabilities: 300 heads outside 1 ... 256").  n_images == 0 returns TS2D_OK and does nothing.
+ * Device scratch, all held by engines[0]: that of ts2d_ensemble_predict_tiled_labelmap without its label maps plus, summed over the images,
+ * K x full_h x full_w x 4 bytes (the probabilities), full_h x full_w bytes (x K multilabel) where decided_u8 is asked for, 24 bytes per output
+ * row and column of an image that resamples + 72 per image, n_order bytes.
+ * Synchronous: ONE stream synchronise per call, then ts2d_engine_check for every fold; a failure is reported as "fold <f>: <message>".
+ * (Added under ABI 9: new symbols only, no existing signature or structure changes, so ts2d_abi_version() stays 9.) */
+#define TS2D_PROB_MULTILABEL 0
+#define TS2D_PROB_LABELMAP 1
+#define TS2D_PROB_REGIONS 2
+typedef struct {
+    int32_t  src_y, src_x, src_h, src_w;   /* rectangle of the aggregated [K, Hp, Wp] logits that is the prediction (un-padded) */
+    int32_t  out_h, out_w;                 /* extent after resampling back */
+    int32_t  full_h, full_w;               /* extent before cropping: what is written */
+    int32_t  box_y, box_x;                 /* origin of the [out_h, out_w] rectangle in it */
+    float*   prob_f32;                     /* host [K, full_h, full_w] */
+    uint8_t* decided_u8;                   /* host [full_h, full_w] (multilabel: [K, full_h, full_w]), or NULL */
+} ts2d_tiled_probabilities;
+
+int ts2d_ensemble_predict_tiled_probabilities(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images,
+                                              const ts2d_tiled_probabilities* probabilities, int n_images, int patch_h, int patch_w,
+                                              int mirror_mask, const uint16_t* gaussian_f16, int full_batch, int mode,
+                                              const uint8_t* class_order, int n_order);
+
+/* The kernel of ts2d_ensemble_predict_tiled_probabilities on half planes the CALLER supplies - the twin of ts2d_labelmap_from_logits and
+ * ts2d_regions_from_logits, with their arguments and their refusals ("probabilities:" in the place of "regions:"), plus the full extent, the
+ * box origin and the mode: logits_f16 host [K, H, W] half bits, rect = {src_y, src_x, src_h, src_w}, prob_f32 host [K, full_h, full_w] (not
+ * NULL), decided_u8 host as in the descriptor above (or NULL), class_order K class values (TS2D_PROB_REGIONS only; NULL there: "probabilities:
+ * the class order is null").  Same arithmetic, same fill, same identity rule.  Host pointers in and out, synchronous, scratch of the call's
+ * own, freed on every path.  (A new symbol of ABI 9: nothing that existed changed.) */
+int ts2d_probabilities_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
+                                   int full_h, int full_w, int box_y, int box_x, int mode, const uint8_t* class_order, float* prob_f32,
+                                   uint8_t* decided_u8);
+
 /* Blend order of ts2d_engine_predict_tiled (upstream `prediction *= gaussian; predicted_logits[sl] += prediction` with
  * float16 `predicted_logits`; reached from ts2d/core/inference/prediction_worker.py:209):
  *   TS2D_TILE_F32 (default) the reference's CPU path (nnu.py:161-163: device=cpu when torch.cuda.is_available() is false - no autocast): the tile prediction is

@@ -45,6 +45,17 @@ struct RsTap {
 };
 static_assert(sizeof(RsTap) == 24, "RsTap is copied to the device as bytes");
 
+// ---- the export's probabilities (kernels_prob.h): what a segment of sw_probabilities needs beside its RsSeg (same index).  The lanes of a
+// probabilities segment walk the FULL pre-crop extent, not the output extent: RsSeg::block0 counts blocks of full_h x ceil(full_w / 4) lanes
+enum ProbMode : int { kProbMultilabel = 0, kProbLabelmap = 1, kProbRegions = 2 };      // the TS2D_PROB_* of the C header
+struct ProbSeg {
+    long long prob_off;     // elements from the float outputs to this image's [K, full_h, full_w] (a multiple of 4)
+    long long dec_off;      // elements from the uint8 outputs to this image's decided map (a multiple of 4): [K, full_h, full_w] multilabel, else [full_h, full_w]
+    int full_h, full_w;     // the extent before cropping: what the kernel writes
+    int box_y, box_x;       // where the resampled [out_h, out_w] rectangle sits in it; everything else is the fill
+};
+static_assert(sizeof(ProbSeg) == 32, "ProbSeg is copied to the device as bytes");
+
 // ---- the order-3 input resample (kernels_resample_in.h)
 constexpr int kRsInPad = 12;            // scipy's _prepad_for_spline_filter for mode='nearest'
 constexpr int kRsInMaxExtent = 8192;    // preprocess.CUBIC_MAX_EXTENT

@@ -242,20 +242,28 @@ struct SwPlan {
     long long n_tiles_all = 0, out_elems = 0, rs_blocks = 0;
     bool any16 = false, anyseg = false, any_rs8 = false, any_rs32 = false;
     std::vector<SwSeg> segs; std::vector<SwChunk> chunks; std::vector<RsSeg> rsegs;
-    std::vector<char> tab;                  // [segments | tile_y | tile_x | export (or label-map) segments | their taps | class order]: one host blob, one copy
-    size_t tab_segs = 0, tab_rsegs = 0, tab_rtaps = 0, tab_order = 0;
-    // scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs x F | uint8 outputs | flags x F | resampled uint8 (or label maps) | resampled float]
-    size_t o_tab = 0, o_g = 0, o_imgs = 0, o_batch = 0, o_log = 0, o_o16 = 0, o_seg = 0, o_flag = 0, o_rs8 = 0, o_rs32 = 0, bytes = 0;
+    std::vector<ProbSeg> psegs; long long prob_elems = 0;      // a probabilities call: one per image beside its RsSeg; elements of the float outputs
+    std::vector<char> tab;                  // [segments | tile_y | tile_x | export (or label-map) segments | their taps | class order | probabilities segments]: one host blob, one copy
+    size_t tab_segs = 0, tab_rsegs = 0, tab_rtaps = 0, tab_order = 0, tab_psegs = 0;
+    // scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs x F | uint8 outputs | flags x F | resampled uint8 (or label maps, or decided maps) | resampled float | probabilities]
+    size_t o_tab = 0, o_g = 0, o_imgs = 0, o_batch = 0, o_log = 0, o_o16 = 0, o_seg = 0, o_flag = 0, o_rs8 = 0, o_rs32 = 0, o_prob = 0, bytes = 0;
 };
+// a probabilities call (ts2d_ensemble_predict_tiled_probabilities): its descriptors and its mode (ProbMode = TS2D_PROB_*)
+struct ProbCall { const ts2d_tiled_probabilities* descs; int mode; };
 // `labelmap`: `exports` describe a label-map call (ts2d_ensemble_predict_tiled_labelmap: seg_u8 = the image's label_u8, ONE output plane)
 // `class_order` (with `labelmap`; else null): a region call (ts2d_ensemble_predict_tiled_regions) - the same plan, its descriptors named
 // "regions:" in a message, and the num_classes class values appended to the table blob at tab_order
+// `prob` (else null): a probabilities call - `exports` carry its geometry with `labelmap` set (seg_u8 = the image's prob_f32), `class_order`
+// is that of its regions mode (else null); the descriptors are named "probabilities:" in a message, a segment's lanes walk the full extent
+// and the ProbSegs go behind the class order at tab_psegs
 int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap,
-               const uint8_t* class_order, int n_images, int ph, int pw, int mirror_mask, bool name_images, const char* entry, SwPlan* pl);
+               const uint8_t* class_order, const ProbCall* prob, int n_images, int ph, int pw, int mirror_mask, bool name_images,
+               const char* entry, SwPlan* pl);
 // One image's segment and taps of the export's resample (checked extents): appended to rsegs / rtaps, `blocks` and `rs_elems` advanced.
 // src_off: elements to the image's [K, Hp, Wp] half planes.  (Also what ts2d_labelmap_from_logits and ts2d_regions_from_logits plan their one image with.)
+// full_hw (a probabilities segment; else null): the lanes walk this extent, 4 X each, and rs_elems is left alone (it may be null).
 void rs_plan_segment(bool labelmap, int K, int Hp, int Wp, const ts2d_tiled_export& ex, long long src_off, std::vector<RsSeg>* rsegs,
-                     std::vector<RsTap>* rtaps, long long* blocks, long long* rs_elems);
+                     std::vector<RsTap>* rtaps, long long* blocks, long long* rs_elems, const int* full_hw);
 
 // ---- prep_plan.cpp: the host arithmetic of the input side, bit for bit numpy's / scipy's
 // The host tables of one (in_h, in_w) -> (out_h, out_w) order-3 zoom and the layout of the scratch they go to: [coefficients | powers | taps]

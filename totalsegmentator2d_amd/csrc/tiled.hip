@@ -1,12 +1,14 @@
 // The sliding window of libts2d_engine.so: tile gather, aggregation, the mean of an ensemble's folds and the export's resample-back, around
 // the engine's forward (engine.hip: reserve_checked, run_forward).  The C entries ts2d_engine_predict_tiled*, ts2d_ensemble_predict_tiled_export,
-// ts2d_ensemble_predict_tiled_labelmap, ts2d_ensemble_predict_tiled_regions, ts2d_labelmap_from_logits and ts2d_regions_from_logits.
+// ts2d_ensemble_predict_tiled_labelmap, ts2d_ensemble_predict_tiled_regions, ts2d_ensemble_predict_tiled_probabilities, ts2d_labelmap_from_logits,
+// ts2d_regions_from_logits and ts2d_probabilities_from_logits.
 #include "engine_internal.h"
 #include "kernels_sw.h"
 #include "kernels_fold.h"
 #include "kernels_resample.h"
 #include "kernels_labelmap.h"
 #include "kernels_regions.h"
+#include "kernels_prob.h"
 
 #include <string>
 #include <vector>
@@ -38,12 +40,15 @@ int name_fold(int rc, bool name_folds, int f) {
 // aggregate (or the mean) ONE sw_labelmap launch (kernels_labelmap.h) in the place of sw_resample_threshold: ONE uint8 plane per image.
 // `class_order` (ts2d_ensemble_predict_tiled_regions; with `labelmap`, else null): the num_classes class values of a region-based model -
 // the label-map plan, the table riding in the call's one table blob, and ONE sw_regions launch (kernels_regions.h) in sw_labelmap's place.
+// `prob` (ts2d_ensemble_predict_tiled_probabilities; with `labelmap`, else null): `exports` carry the geometry of its descriptors (seg_u8 =
+// prob_f32), `class_order` is set in its regions mode only - the label-map plan with lanes over the full extent, and ONE sw_probabilities
+// launch (kernels_prob.h) in sw_labelmap's place: K float planes (and the decided map) of the pre-crop extent per image.
 int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap,
-                       const uint8_t* class_order, int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, bool full,
-                       bool name_images, bool name_folds, const char* entry) {
+                       const uint8_t* class_order, const ProbCall* prob, int n_images, int ph, int pw, int mirror_mask,
+                       const uint16_t* gaussian_f16, bool full, bool name_images, bool name_folds, const char* entry) {
     ts2d_engine* e = engines[0];
     SwPlan pl;
-    TRY(plan_tiled(e, F, images, exports, labelmap, class_order, n_images, ph, pw, mirror_mask, name_images, entry, &pl));
+    TRY(plan_tiled(e, F, images, exports, labelmap, class_order, prob, n_images, ph, pw, mirror_mask, name_images, entry, &pl));
     const int C = e->arch.input_channels, K = e->arch.num_classes, V = pl.V;
     for (int f = 0; f < F; ++f) TRY(name_fold(reserve_checked(engines[f], pl.cap_rows, ph, pw, full), name_folds, f));
     HIP_TRY(hipSetDevice(e->device));
@@ -93,7 +98,20 @@ int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* ima
         HIP_TRY(hipGetLastError());
     }
     uint8_t* d_rs8 = pl.any_rs8 ? reinterpret_cast<uint8_t*>(b + pl.o_rs8) : nullptr; float* d_rs32 = pl.any_rs32 ? reinterpret_cast<float*>(b + pl.o_rs32) : nullptr;
-    if (labelmap) {
+    if (prob) {
+        float* d_prob = reinterpret_cast<float*>(b + pl.o_prob);
+        hipLaunchKernelGGL(sw_probabilities, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
+                           reinterpret_cast<const ProbSeg*>(b + pl.o_tab + pl.tab_psegs), n_images, K, reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps),
+                           prob->mode, class_order ? reinterpret_cast<const uint8_t*>(b + pl.o_tab + pl.tab_order) : nullptr, d_prob, d_rs8, kSigmoidHalfThreshold);
+        HIP_TRY(hipGetLastError());
+        for (int i = 0; i < n_images; ++i) {
+            const ts2d_tiled_probabilities& pd = prob->descs[i];
+            const size_t fplane = (size_t)pd.full_h * pd.full_w;
+            HIP_TRY(hipMemcpyAsync(pd.prob_f32, d_prob + pl.psegs[i].prob_off, (size_t)K * fplane * 4, hipMemcpyDeviceToHost, st));
+            if (pd.decided_u8)
+                HIP_TRY(hipMemcpyAsync(pd.decided_u8, d_rs8 + pl.psegs[i].dec_off, (prob->mode == kProbMultilabel ? (size_t)K : 1) * fplane, hipMemcpyDeviceToHost, st));
+        }
+    } else if (labelmap) {
         const RsSeg* d_rsegs = reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs);
         const RsTap* d_rtaps = reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps);
         if (class_order)
@@ -177,20 +195,26 @@ std::vector<ts2d_tiled_export> one_plane_exports(const ts2d_tiled_labelmap* maps
 
 // ts2d_labelmap_from_logits and ts2d_regions_from_logits: the one-image kernel call on half planes of the caller's.
 // class_order null: sw_labelmap; else sw_regions with its K class values.
-int one_plane_from_logits(const char* entry, const char* what, int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4],
-                          int out_h, int out_w, const uint8_t* class_order, uint8_t* label_u8) {
+// what the *_from_logits entries refuse alike of their planes, rectangle and output extent
+int check_from_logits(const char* entry, int K, int H, int W, const ts2d_tiled_export& ex) {
     if (K < 1 || K > 256) return fail(TS2D_ERR_INVALID, "%s: %d heads outside 1 ... 256", entry, K);
     if (H < 1 || W < 1 || (long long)K * H * W >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: bad extent %d x %d x %d (2^31 elements at most)", entry, K, H, W);
-    const ts2d_tiled_export ex{rect[0], rect[1], rect[2], rect[3], out_h, out_w, label_u8, nullptr};
     if (ex.src_h < 1 || ex.src_w < 1 || ex.src_y < 0 || ex.src_x < 0 || ex.src_h > H - ex.src_y || ex.src_w > W - ex.src_x)
         return fail(TS2D_ERR_INVALID, "%s: source rectangle %dx%d at (%d,%d) is empty or leaves the %dx%d image", entry, ex.src_h, ex.src_w, ex.src_y,
                     ex.src_x, H, W);
-    if (out_h < 1 || out_w < 1) return fail(TS2D_ERR_INVALID, "%s: bad output extent %dx%d", entry, out_h, out_w);
-    if ((long long)out_h * out_w >= (1LL << 31) || (long long)out_h + out_w >= (1LL << 26))
-        return fail(TS2D_ERR_INVALID, "%s: %dx%d exceeds 2^31 output elements or 2^26 output rows + columns", entry, out_h, out_w);
+    if (ex.out_h < 1 || ex.out_w < 1) return fail(TS2D_ERR_INVALID, "%s: bad output extent %dx%d", entry, ex.out_h, ex.out_w);
+    if ((long long)ex.out_h * ex.out_w >= (1LL << 31) || (long long)ex.out_h + ex.out_w >= (1LL << 26))
+        return fail(TS2D_ERR_INVALID, "%s: %dx%d exceeds 2^31 output elements or 2^26 output rows + columns", entry, ex.out_h, ex.out_w);
+    return TS2D_OK;
+}
+
+int one_plane_from_logits(const char* entry, const char* what, int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4],
+                          int out_h, int out_w, const uint8_t* class_order, uint8_t* label_u8) {
+    const ts2d_tiled_export ex{rect[0], rect[1], rect[2], rect[3], out_h, out_w, label_u8, nullptr};
+    TRY(check_from_logits(entry, K, H, W, ex));
     std::vector<RsSeg> segs; std::vector<RsTap> rtaps;
     long long blocks = 0, elems = 0;
-    rs_plan_segment(true, K, H, W, ex, 0, &segs, &rtaps, &blocks, &elems);
+    rs_plan_segment(true, K, H, W, ex, 0, &segs, &rtaps, &blocks, &elems, nullptr);
     if (blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the %s exceeds 2^31 blocks", entry, what);
     HIP_TRY(hipSetDevice(device));
     // [segment | taps | class order | half planes | label map]
@@ -214,6 +238,15 @@ int one_plane_from_logits(const char* entry, const char* what, int device, const
     return TS2D_OK;
 }
 
+// what both probabilities entries refuse of the mode and its class order
+int check_prob_mode(const char* entry, int mode, int K, const uint8_t* class_order) {
+    if (mode != kProbMultilabel && mode != kProbLabelmap && mode != kProbRegions)
+        return fail(TS2D_ERR_INVALID, "%s: probabilities: unknown mode %d", entry, mode);
+    if (mode == kProbRegions && !class_order) return fail(TS2D_ERR_INVALID, "%s: probabilities: the class order is null", entry);
+    if (K < 1 || K > 256) return fail(TS2D_ERR_INVALID, "%s: probabilities: %d heads outside 1 ... 256", entry, K);      // (every mode: the twin's limit)
+    return TS2D_OK;
+}
+
 }  // namespace
 #pragma GCC visibility pop
 
@@ -226,7 +259,7 @@ int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
     if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
     ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
-    return predict_tiled_impl(&e, 1, &one, nullptr, false, nullptr, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
+    return predict_tiled_impl(&e, 1, &one, nullptr, false, nullptr, nullptr, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
 }
 
 int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
@@ -235,7 +268,7 @@ int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, in
     if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
     if (n_images == 0) return TS2D_OK;
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
-    return predict_tiled_impl(&e, 1, images, nullptr, false, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
+    return predict_tiled_impl(&e, 1, images, nullptr, false, nullptr, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
 }
 
 int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
@@ -245,7 +278,7 @@ int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, c
         return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: %d images at a null pointer", n_images);
     if (n_images == 0) return TS2D_OK;
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_export: weights not loaded");
-    return predict_tiled_impl(&e, 1, images, exports, false, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
+    return predict_tiled_impl(&e, 1, images, exports, false, nullptr, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
                               "ts2d_engine_predict_tiled_export");
 }
 
@@ -255,7 +288,7 @@ int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engine
     int todo = 0;
     TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
     if (!todo) return TS2D_OK;
-    return predict_tiled_impl(engines, n_engines, images, exports, false, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
+    return predict_tiled_impl(engines, n_engines, images, exports, false, nullptr, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
                               true, true, entry);
 }
 
@@ -267,7 +300,7 @@ int ts2d_ensemble_predict_tiled_labelmap(ts2d_engine* const* engines, int n_engi
     if (!todo) return TS2D_OK;
     if (!labelmaps) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
     const std::vector<ts2d_tiled_export> ex = one_plane_exports(labelmaps, n_images);
-    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16,
+    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, nullptr, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16,
                               full_batch ? kFullBatch : kBySize, true, true, entry);
 }
 
@@ -284,7 +317,7 @@ int ts2d_ensemble_predict_tiled_regions(ts2d_engine* const* engines, int n_engin
     if (n_order != K) return fail(TS2D_ERR_INVALID, "%s: regions: %d class values for a model of %d heads", entry, n_order, K);
     if (K > 256) return fail(TS2D_ERR_INVALID, "%s: regions: %d heads outside 1 ... 256", entry, K);
     const std::vector<ts2d_tiled_export> ex = one_plane_exports(maps, n_images);
-    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, class_order, n_images, ph, pw, mirror_mask, gaussian_f16,
+    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, class_order, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16,
                               full_batch ? kFullBatch : kBySize, true, true, entry);
 }
 
@@ -302,6 +335,69 @@ int ts2d_regions_from_logits(int device, const uint16_t* logits_f16, int K, int 
     if (!class_order) return fail(TS2D_ERR_INVALID, "%s: regions: the class order is null", entry);
     if (!label_u8) return fail(TS2D_ERR_INVALID, "%s: regions: the output is null", entry);
     return one_plane_from_logits(entry, "regions", device, logits_f16, K, H, W, rect, out_h, out_w, class_order, label_u8);
+}
+
+int ts2d_ensemble_predict_tiled_probabilities(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images,
+                                              const ts2d_tiled_probabilities* probabilities, int n_images, int ph, int pw, int mirror_mask,
+                                              const uint16_t* gaussian_f16, int full_batch, int mode, const uint8_t* class_order, int n_order) {
+    static const char* entry = "ts2d_ensemble_predict_tiled_probabilities";
+    int todo = 0;
+    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    if (!todo) return TS2D_OK;
+    if (!probabilities) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
+    const int K = engines[0]->arch.num_classes;
+    TRY(check_prob_mode(entry, mode, K, class_order));
+    if (mode == kProbRegions && n_order != K) return fail(TS2D_ERR_INVALID, "%s: probabilities: %d class values for a model of %d heads", entry, n_order, K);
+    std::vector<ts2d_tiled_export> ex((size_t)n_images);      // the geometry of an export with ONE output: a null prob_f32 is "the output is null"
+    for (int i = 0; i < n_images; ++i) {
+        const ts2d_tiled_probabilities& pd = probabilities[i];
+        ex[i] = ts2d_tiled_export{pd.src_y, pd.src_x, pd.src_h, pd.src_w, pd.out_h, pd.out_w, reinterpret_cast<uint8_t*>(pd.prob_f32), nullptr};
+    }
+    const ProbCall prob{probabilities, mode};
+    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, mode == kProbRegions ? class_order : nullptr, &prob, n_images, ph, pw,
+                              mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, true, entry);
+}
+
+int ts2d_probabilities_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
+                                   int full_h, int full_w, int box_y, int box_x, int mode, const uint8_t* class_order, float* prob_f32,
+                                   uint8_t* decided_u8) {
+    static const char* entry = "ts2d_probabilities_from_logits";
+    if (!logits_f16 || !rect) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
+    if (!prob_f32) return fail(TS2D_ERR_INVALID, "%s: probabilities: the output is null", entry);
+    const ts2d_tiled_export ex{rect[0], rect[1], rect[2], rect[3], out_h, out_w, nullptr, nullptr};
+    TRY(check_prob_mode(entry, mode, K, class_order));
+    TRY(check_from_logits(entry, K, H, W, ex));
+    if (full_h < 1 || full_w < 1 || box_y < 0 || box_x < 0 || out_h > full_h - box_y || out_w > full_w - box_x)
+        return fail(TS2D_ERR_INVALID, "%s: probabilities: the %dx%d output at (%d,%d) leaves the full extent %dx%d", entry, out_h, out_w, box_y, box_x,
+                    full_h, full_w);
+    if ((long long)K * full_h * full_w >= (1LL << 31))
+        return fail(TS2D_ERR_INVALID, "%s: probabilities: %d x %dx%d exceeds 2^31 output elements", entry, K, full_h, full_w);
+    std::vector<RsSeg> segs; std::vector<RsTap> rtaps;
+    long long blocks = 0;
+    const int full_hw[2] = {full_h, full_w};
+    rs_plan_segment(true, K, H, W, ex, 0, &segs, &rtaps, &blocks, nullptr, full_hw);
+    if (blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the probabilities exceed 2^31 blocks", entry);
+    const bool regions = mode == kProbRegions;
+    const ProbSeg ps{0, 0, full_h, full_w, box_y, box_x};
+    HIP_TRY(hipSetDevice(device));
+    // [segment | probabilities segment | taps | class order | half planes | probabilities | decided map]
+    const size_t n_src = (size_t)K * H * W, n_prob = (size_t)K * full_h * full_w, n_dec = decided_u8 ? (mode == kProbMultilabel ? n_prob : n_prob / K) : 0;
+    const size_t o_ps = align_up(sizeof(RsSeg), 8), o_taps = o_ps + sizeof(ProbSeg), o_order = o_taps + rtaps.size() * sizeof(RsTap);
+    const size_t o_src = align_up(o_order + (regions ? (size_t)K : 0), 256), o_prob = align_up(o_src + n_src * 2, 256), o_dec = align_up(o_prob + n_prob * 4, 256);
+    DevMem d;
+    HIP_TRY(d.alloc(o_dec + n_dec));
+    HIP_TRY(hipMemcpy(d.as<char>(), segs.data(), sizeof(RsSeg), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_ps), &ps, sizeof(ProbSeg), hipMemcpyHostToDevice));
+    if (!rtaps.empty()) HIP_TRY(hipMemcpy(d.as<char>(o_taps), rtaps.data(), rtaps.size() * sizeof(RsTap), hipMemcpyHostToDevice));
+    if (regions) HIP_TRY(hipMemcpy(d.as<char>(o_order), class_order, (size_t)K, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_src), logits_f16, n_src * 2, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(sw_probabilities, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(), d.as<const ProbSeg>(o_ps), 1, K,
+                       d.as<const RsTap>(o_taps), mode, regions ? d.as<const uint8_t>(o_order) : nullptr, d.as<float>(o_prob),
+                       decided_u8 ? d.as<uint8_t>(o_dec) : nullptr, kSigmoidHalfThreshold);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(prob_f32, d.as<float>(o_prob), n_prob * 4, hipMemcpyDeviceToHost));
+    if (decided_u8) HIP_TRY(hipMemcpy(decided_u8, d.as<uint8_t>(o_dec), n_dec, hipMemcpyDeviceToHost));
+    return TS2D_OK;
 }
 
 int ts2d_engine_tiled_inf_flag(const ts2d_engine* e) { return e ? (e->tiled_inf != 0) : 0; }

@@ -33,11 +33,12 @@ void rs_axis_taps(int n_in, int n_out, int origin, RsTap* t) {
 
 // every image (and its export descriptor) on its own; the totals that bound the tables
 // `labelmap`: the descriptors are those of a label-map call (ONE output plane per image: seg_u8 is its label_u8) and are named so;
-// `regions`: of a region call - the same descriptors under that name
-int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, bool regions, int n_images,
-                 int ph, int pw, bool name_images, const char* entry, SwPlan* pl) {
+// `regions`: of a region call - the same descriptors under that name;  `prob`: of a probabilities call (seg_u8 is its prob_f32) - named
+// "probabilities", whatever its mode, and checked against the full extent too
+int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, bool regions,
+                 const ProbCall* prob, int n_images, int ph, int pw, bool name_images, const char* entry, SwPlan* pl) {
     long long n_taps_all = 0;
-    const char* what = regions ? "regions" : labelmap ? "labelmap" : "export";
+    const char* what = prob ? "probabilities" : regions ? "regions" : labelmap ? "labelmap" : "export";
     pl->any16 = F > 1;      // (the mean is taken over the half buffers)
     for (int i = 0; i < n_images; ++i) {
         const ts2d_tiled_image& im = images[i];
@@ -65,7 +66,15 @@ int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d
             return fail(TS2D_ERR_INVALID, "%s%s: %dx%d exceeds 2^31 output elements", pre, what, ex.out_h, ex.out_w);
         n_taps_all += (long long)ex.out_h + ex.out_w;         // (each < 2^31 by the check above; bounded before any table is allocated)
         if (n_taps_all >= (1LL << 26)) return fail(TS2D_ERR_INVALID, "%s%s: more than 2^26 output rows + columns in one call", pre, what);
-        pl->any16 = true; pl->any_rs8 |= ex.seg_u8 != nullptr; pl->any_rs32 |= ex.logits_f32 != nullptr;
+        pl->any16 = true;
+        if (!prob) { pl->any_rs8 |= ex.seg_u8 != nullptr; pl->any_rs32 |= ex.logits_f32 != nullptr; continue; }
+        const ts2d_tiled_probabilities& pd = prob->descs[i];
+        if (pd.full_h < 1 || pd.full_w < 1 || pd.box_y < 0 || pd.box_x < 0 || ex.out_h > pd.full_h - pd.box_y || ex.out_w > pd.full_w - pd.box_x)
+            return fail(TS2D_ERR_INVALID, "%s%s: the %dx%d output at (%d,%d) leaves the full extent %dx%d", pre, what, ex.out_h, ex.out_w, pd.box_y,
+                        pd.box_x, pd.full_h, pd.full_w);
+        if ((long long)K * pd.full_h * pd.full_w >= (1LL << 31))
+            return fail(TS2D_ERR_INVALID, "%s%s: %d x %dx%d exceeds 2^31 output elements", pre, what, K, pd.full_h, pd.full_w);
+        pl->any_rs8 |= pd.decided_u8 != nullptr;
     }
     if (pl->n_tiles_all * pl->V >= (1LL << 28)) return fail(TS2D_ERR_INVALID, "%s: %lld network rows in one call", entry, pl->n_tiles_all * pl->V);
     return TS2D_OK;
@@ -119,24 +128,37 @@ int pack_rows(int F, int C, int K, const ts2d_tiled_image* images, int n_images,
 
 // The export: one segment per image (its half logits are segs' out_off), the taps of its rows then of its columns.
 // rs_elems: elements of the resampled outputs.
-int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, bool regions, int n_images,
-                const char* entry, SwPlan* pl, std::vector<RsTap>* rtaps, long long* rs_elems) {
+// `prob`: a probabilities call - the lanes of a segment walk the full extent, and beside every RsSeg goes a ProbSeg with the image's places
+// in the float outputs (prob_elems) and in the decided maps (rs_elems)
+int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, bool regions, const ProbCall* prob,
+                int n_images, const char* entry, SwPlan* pl, std::vector<RsTap>* rtaps, long long* rs_elems) {
     long long oo = 0;
     for (int i = 0; i < n_images; ++i) {
-        rs_plan_segment(labelmap, K, images[i].Hp, images[i].Wp, exports[i], oo, &pl->rsegs, rtaps, &pl->rs_blocks, rs_elems);
+        if (prob) {
+            const ts2d_tiled_probabilities& pd = prob->descs[i];
+            const int full_hw[2] = {pd.full_h, pd.full_w};
+            const size_t fplane = (size_t)pd.full_h * pd.full_w;
+            pl->psegs.push_back(ProbSeg{pl->prob_elems, *rs_elems, pd.full_h, pd.full_w, pd.box_y, pd.box_x});
+            rs_plan_segment(true, K, images[i].Hp, images[i].Wp, exports[i], oo, &pl->rsegs, rtaps, &pl->rs_blocks, nullptr, full_hw);
+            pl->prob_elems += (long long)align_up((size_t)K * fplane, 256);
+            *rs_elems += (long long)align_up((prob->mode == kProbMultilabel ? (size_t)K : 1) * fplane, 256);
+        } else {
+            rs_plan_segment(labelmap, K, images[i].Hp, images[i].Wp, exports[i], oo, &pl->rsegs, rtaps, &pl->rs_blocks, rs_elems, nullptr);
+        }
         oo += (long long)align_up((size_t)K * images[i].Hp * images[i].Wp, 256);
     }
-    if (pl->rs_blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the %s exceeds 2^31 blocks", entry, regions ? "regions" : labelmap ? "labelmap" : "export");
+    if (pl->rs_blocks >= (1LL << 31))
+        return fail(TS2D_ERR_INVALID, "%s: the %s exceeds 2^31 blocks", entry, prob ? "probabilities" : regions ? "regions" : labelmap ? "labelmap" : "export");
     return TS2D_OK;
 }
 
 }  // namespace
 
 void rs_plan_segment(bool labelmap, int K, int Hp, int Wp, const ts2d_tiled_export& ex, long long src_off, std::vector<RsSeg>* rsegs,
-                     std::vector<RsTap>* rtaps, long long* blocks, long long* rs_elems) {
+                     std::vector<RsTap>* rtaps, long long* blocks, long long* rs_elems, const int* full_hw) {
     const int planes = labelmap ? 1 : K;          // of the output: the label map is ONE plane, its lanes walk the K source planes
     RsSeg rs{};
-    rs.src_off = src_off; rs.dst_off = *rs_elems; rs.Hp = Hp; rs.Wp = Wp; rs.out_h = ex.out_h; rs.out_w = ex.out_w;
+    rs.src_off = src_off; rs.dst_off = full_hw ? 0 : *rs_elems; rs.Hp = Hp; rs.Wp = Wp; rs.out_h = ex.out_h; rs.out_w = ex.out_w;
     rs.block0 = (unsigned)*blocks;
     if (labelmap && ex.out_h == ex.src_h && ex.out_w == ex.src_w) {      // the host route does not resample then: no taps, no weights
         rs.tap0 = -1; rs.src_off += (long long)ex.src_y * Wp + ex.src_x;
@@ -147,12 +169,14 @@ void rs_plan_segment(bool labelmap, int K, int Hp, int Wp, const ts2d_tiled_expo
         rs_axis_taps(ex.src_w, ex.out_w, ex.src_x, rtaps->data() + rs.tap0 + ex.out_h);
     }
     rsegs->push_back(rs);
+    if (full_hw) { *blocks += blocks_of((long long)full_hw[0] * ((full_hw[1] + 3) / 4)); return; }      // (its outputs: the caller's ProbSeg)
     *blocks += blocks_of((long long)planes * ex.out_h * ((ex.out_w + 3) / 4));
     *rs_elems += (long long)align_up((size_t)planes * ex.out_h * ex.out_w, 256);
 }
 
 int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap,
-               const uint8_t* class_order, int n_images, int ph, int pw, int mirror_mask, bool name_images, const char* entry, SwPlan* pl) {
+               const uint8_t* class_order, const ProbCall* prob, int n_images, int ph, int pw, int mirror_mask, bool name_images,
+               const char* entry, SwPlan* pl) {
     if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "%s: bad patch %dx%d", entry, ph, pw);
     const int C = e->arch.input_channels, K = e->arch.num_classes;
     int vflip[4] = {0, 0, 0, 0};
@@ -163,15 +187,17 @@ int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, cons
     long long img_floats = 0, log_rows = 0, rs_elems = 0;
     std::vector<RsTap> rtaps;
     const bool regions = class_order != nullptr;
-    TRY(check_images(F, C, K, images, exports, labelmap, regions, n_images, ph, pw, name_images, entry, pl));
+    TRY(check_images(F, C, K, images, exports, labelmap, regions, prob, n_images, ph, pw, name_images, entry, pl));
     TRY(pack_rows(F, C, K, images, n_images, ph, pw, entry, pl, &img_floats, &log_rows));
-    if (exports) TRY(plan_export(K, images, exports, labelmap, regions, n_images, entry, pl, &rtaps, &rs_elems));
+    if (exports) TRY(plan_export(K, images, exports, labelmap, regions, prob, n_images, entry, pl, &rtaps, &rs_elems));
     // ---- the descriptor table and every tile origin
     const size_t n_tiles = (size_t)pl->n_tiles_all;
     pl->tab_segs = pl->segs.size() * sizeof(SwSeg); pl->tab_rsegs = align_up(pl->tab_segs + 2 * n_tiles * 4, 8);
     pl->tab_rtaps = pl->tab_rsegs + pl->rsegs.size() * sizeof(RsSeg);
     pl->tab_order = pl->tab_rtaps + rtaps.size() * sizeof(RsTap);
-    pl->tab.resize(pl->tab_order + (regions ? (size_t)K : 0));
+    pl->tab_psegs = align_up(pl->tab_order + (regions ? (size_t)K : 0), 8);
+    pl->tab.resize(prob ? pl->tab_psegs + pl->psegs.size() * sizeof(ProbSeg) : pl->tab_order + (regions ? (size_t)K : 0));
+    if (prob) memcpy(pl->tab.data() + pl->tab_psegs, pl->psegs.data(), pl->psegs.size() * sizeof(ProbSeg));
     if (regions) memcpy(pl->tab.data() + pl->tab_order, class_order, (size_t)K);      // (K == n_order: the entry has checked it)
     memcpy(pl->tab.data(), pl->segs.data(), pl->tab_segs);
     if (exports) {
@@ -191,6 +217,7 @@ int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, cons
     pl->o_o16 = take(pl->any16 ? (size_t)F * pl->out_elems * 2 : 0); pl->o_seg = take(pl->anyseg ? (size_t)pl->out_elems : 0);
     pl->o_flag = take((size_t)F * n_images * 4);
     pl->o_rs8 = take(pl->any_rs8 ? (size_t)rs_elems : 0); pl->o_rs32 = take(pl->any_rs32 ? (size_t)rs_elems * 4 : 0);
+    pl->o_prob = take((size_t)pl->prob_elems * 4);
     pl->bytes = off;
     return TS2D_OK;
 }

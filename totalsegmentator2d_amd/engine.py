@@ -260,13 +260,16 @@ class Engine:
         return outs
 
     def _tiled_args(self, what, images, tiles, exports, mirror_axes, gaussian, want_seg, want_f32, want_logits, want_padded_seg,
-                    labelmap: bool = False):
+                    labelmap: bool = False, prob_mode: Optional[int] = None):
         """Argument preparation of every tiled call (`what` names the calling method in a message): the ``TiledImage`` array, the
         ``TiledExport`` array (None without ``exports``: no resample-back), the mirror mask, the address of the half gaussian (or None),
         the arrays all of these point into - they must outlive the call - and the output lists ``(seg, f32, logits, padded_seg)`` the
         call fills, each None unless asked for.  ``labelmap``: the descriptors are ``TiledLabelmap`` and ``seg`` holds ONE uint8 plane
         [out_h,out_w] per image, the label map.  ``what`` None is the one image of :meth:`predict_tiled`: its messages carry no
-        ``image i: `` and everything but the channel count is left to the library (or to the unpacking of the shape) to refuse."""
+        ``image i: `` and everything but the channel count is left to the library (or to the unpacking of the shape) to refuse.
+        ``prob_mode`` (a ``_lib.PROB_*``): the descriptors are ``TiledProbabilities`` from ``exports`` of ten numbers (the six, then
+        ``full_h, full_w, box_y, box_x``); ``f32`` holds the float32 probabilities [K,full_h,full_w] and ``seg`` the decided uint8 map
+        of the full extent ([K,full_h,full_w] multilabel, else [full_h,full_w])."""
         one = what is None
         if len(images) != len(tiles) or (exports is not None and len(exports) != len(images)):
             raise RuntimeError(f"{len(images)} images but {len(tiles)} tile lists" + ("" if exports is None else f" and {len(exports)} exports"))
@@ -280,7 +283,8 @@ class Engine:
         K = self.arch.num_classes
         keep = []                    # every array the descriptors point into stays alive until the call returns
         n = max(len(images), 1)
-        desc, exd = (_lib.TiledImage * n)(), (None if exports is None else ((_lib.TiledLabelmap if labelmap else _lib.TiledExport) * n)())
+        kind = _lib.TiledProbabilities if prob_mode is not None else _lib.TiledLabelmap if labelmap else _lib.TiledExport
+        desc, exd = (_lib.TiledImage * n)(), (None if exports is None else (kind * n)())
         seg, f32, out16, pseg = [], [], [], []
         for i, (image, tl) in enumerate(zip(images, tiles)):
             at = '' if one else f'image {i}: '
@@ -302,11 +306,20 @@ class Engine:
             d.seg_u8 = pseg[i].ctypes.data if want_padded_seg else None
             if exports is None:
                 continue
-            sy, sx, sh, sw_, oh, ow = (int(v) for v in exports[i])
+            sy, sx, sh, sw_, oh, ow = (int(v) for v in exports[i][:6])
+            x = exd[i]
+            if prob_mode is not None:
+                fh, fw, by, bx = (int(v) for v in exports[i][6:])
+                full = (max(fh, 0), max(fw, 0))                                    # (a bad extent is the library's to reject, by name)
+                f32.append(np.empty((K,) + full, dtype=np.float32))
+                seg.append(np.empty(((K,) if prob_mode == _lib.PROB_MULTILABEL else ()) + full, dtype=np.uint8) if want_seg else None)
+                x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w = sy, sx, sh, sw_, oh, ow
+                x.full_h, x.full_w, x.box_y, x.box_x = fh, fw, by, bx
+                x.prob_f32, x.decided_u8 = f32[i].ctypes.data, (seg[i].ctypes.data if want_seg else None)
+                continue
             shape = (() if labelmap else (K,)) + (max(oh, 0), max(ow, 0))          # (a bad extent is the library's to reject, by name)
             seg.append(np.empty(shape, dtype=np.uint8) if want_seg else None)
             f32.append(np.empty(shape, dtype=np.float32) if want_f32 else None)
-            x = exd[i]
             x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w = sy, sx, sh, sw_, oh, ow
             if labelmap:
                 x.label_u8 = seg[i].ctypes.data
@@ -499,6 +512,82 @@ def regions_from_logits(logits_f16: np.ndarray, rect, out_hw, class_order, devic
     _lib.check(_lib.load().ts2d_regions_from_logits(int(device), lg.ctypes.data, lg.shape[0], lg.shape[1], lg.shape[2], ctypes.byref(r), oh, ow,
                                                     order.ctypes.data, out.ctypes.data), 'ts2d_regions_from_logits')
     return out
+
+
+def _prob_mode(mode, class_order, what: str):
+    """``mode`` of ``export.PROBABILITY_MODES`` -> (TS2D_PROB_*, the class-order bytes of a regions call or None)."""
+    from .export import PROBABILITY_MODES
+    if mode not in PROBABILITY_MODES:
+        raise RuntimeError(f"{what}: mode must be one of {PROBABILITY_MODES}, found {mode!r}")
+    if mode != 'regions':
+        return PROBABILITY_MODES.index(mode), None
+    if class_order is None:
+        raise RuntimeError(f"{what}: the regions mode needs the class order")
+    return _lib.PROB_REGIONS, _class_order_u8(class_order, what)
+
+
+def _need_probabilities(lib, name: str):
+    if not hasattr(lib, name):
+        raise RuntimeError(f"{name}: this libts2d_engine.so was built before the probabilities entries; rebuild it, or keep the host route")
+    return getattr(lib, name)
+
+
+def has_probabilities() -> bool:
+    """Does the loaded library have the probabilities entries?  (A library built before them still loads: the callers keep the host route.)"""
+    return hasattr(_lib.load(), 'ts2d_ensemble_predict_tiled_probabilities')
+
+
+def predict_tiled_probabilities_ensemble(engines, images, patch, tiles, rects, mode, class_order=None, mirror_axes=None,
+                                         gaussian: Optional[np.ndarray] = None, want_decided: bool = True, want_logits: bool = False,
+                                         full_batch: bool = True):
+    """:func:`predict_tiled_labelmap_ensemble` with the export's PROBABILITIES (C-ABI ts2d_ensemble_predict_tiled_probabilities): the same
+    sliding window per fold and the same mean, then per image ONE kernel (csrc/kernels_prob.h) that resamples the half logits back,
+    applies the non-linearity of ``mode`` (``export.PROBABILITY_MODES``: sigmoid for 'multilabel' and 'regions', softmax for 'labelmap'),
+    writes the planes of the pre-crop extent with the fill around the box and decides the model's map on the logits in the same pass.
+    rects: one ``(src_y, src_x, src_h, src_w, out_h, out_w, full_h, full_w, box_y, box_x)`` per image; ``class_order``: the regions mode's.
+    Returns ``(probabilities, decided, logits)``: lists of float32 [K,full_h,full_w] - ``export.probabilities_statement`` of the half
+    logits to within a few float32 units - of uint8 [full_h,full_w] ([K,full_h,full_w] multilabel; None unless ``want_decided``) - inside
+    the box byte for byte what the label-map / regions / threshold routes give, 0 outside - and of float16 [K,Hp,Wp] (None unless asked)."""
+    what = 'predict_tiled_probabilities_ensemble'
+    engines = list(engines)
+    if not engines:
+        raise RuntimeError(f"{what}: no engines")
+    if rects is None:
+        raise RuntimeError(f"{what}: the probabilities need their rectangles and extents")
+    code, order = _prob_mode(mode, class_order, what)
+    fn = _need_probabilities(engines[0].lib, 'ts2d_ensemble_predict_tiled_probabilities')
+    desc, pd, mask, g, keep, outs = engines[0]._tiled_args(what, images, tiles, rects, mirror_axes, gaussian, bool(want_decided), True, want_logits,
+                                                           False, labelmap=True, prob_mode=code)
+    handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
+    _lib.check(fn(handles, len(engines), desc, pd, len(images), int(patch[0]), int(patch[1]), mask, g, int(bool(full_batch)), code,
+                  None if order is None else order.ctypes.data, 0 if order is None else int(order.size)), 'ts2d_ensemble_predict_tiled_probabilities')
+    _read_tiled_inf(engines, desc, len(images), engine_flags=True)
+    del keep
+    return outs[1], outs[0], outs[2]
+
+
+def probabilities_from_logits(logits_f16: np.ndarray, rect, out_hw, full_hw, box_yx, mode, class_order=None, want_decided: bool = True,
+                              device: int = 0):
+    """The probabilities kernel on half planes of the caller's (C-ABI ts2d_probabilities_from_logits): float16 [K,H,W], ``rect = (y, x, h, w)``
+    inside it, resampled to ``out_hw``, placed at ``box_yx`` of ``full_hw`` -> ``(float32 [K,full_h,full_w], decided uint8 or None)``."""
+    lg = np.ascontiguousarray(logits_f16, dtype=np.float16)
+    if lg.ndim != 3:
+        raise RuntimeError(f"expected [K,H,W], found shape {lg.shape}")
+    code, order = _prob_mode(mode, class_order, 'probabilities_from_logits')
+    if order is not None and order.size != lg.shape[0]:
+        raise RuntimeError(f"probabilities_from_logits: {order.size} class values for {lg.shape[0]} heads")
+    oh, ow = (int(v) for v in out_hw)
+    fh, fw = (int(v) for v in full_hw)
+    by, bx = (int(v) for v in box_yx)
+    full = (max(fh, 0), max(fw, 0))
+    prob = np.empty((lg.shape[0],) + full, dtype=np.float32)
+    dec = np.empty(((lg.shape[0],) if code == _lib.PROB_MULTILABEL else ()) + full, dtype=np.uint8) if want_decided else None
+    r = (ctypes.c_int32 * 4)(*[int(v) for v in rect])
+    fn = _need_probabilities(_lib.load(), 'ts2d_probabilities_from_logits')
+    _lib.check(fn(int(device), lg.ctypes.data, lg.shape[0], lg.shape[1], lg.shape[2], ctypes.byref(r), oh, ow, fh, fw, by, bx, code,
+                  None if order is None else order.ctypes.data, prob.ctypes.data, None if dec is None else dec.ctypes.data),
+               'ts2d_probabilities_from_logits')
+    return prob, dec
 
 
 def _read_tiled_inf(engines, desc, n_images, engine_flags: bool):

@@ -70,15 +70,85 @@ def regions_statement(logits_f16, rect, out_hw, class_order) -> np.ndarray:
     return paint_regions(lg > SIGMOID_HALF_THRESHOLD, class_order)
 
 
+PROBABILITY_MODES = ('multilabel', 'labelmap', 'regions')      # in the order of TS2D_PROB_* (include/ts2d_engine.h)
+
+
+def inference_nonlinearity(lg32, softmax: bool) -> np.ndarray:
+    """nnU-Net's inference non-linearity on float32 logits [K, ...] [UPSTREAM-RECALL: LabelManager.apply_inference_nonlin on
+    ``logits.float()``]: the softmax over the heads for a label-map model, else the sigmoid per head, in float32 numpy.  A NaN logit
+    gives NaN; the softmax of a pixel with a +inf or NaN head is NaN in every head (inf - inf) and a -inf head gives 0 - what
+    ``torch.softmax`` does on the CPU.  Every sum, difference and quotient is float32; ``exp`` is the float64 function rounded once to
+    float32, as on the device (csrc/kernels_prob.h: pr_exp): numpy's own float32 ``exp`` is a whole unit off on some arguments, enough
+    for ``sigmoid(2^-23) > 0.5`` to come out false, and the probabilities must never contradict the segmentation decided on the logit."""
+    v = np.asarray(lg32, dtype=np.float32)
+
+    def exp32(x):
+        return np.exp(x.astype(np.float64)).astype(np.float32)
+    with np.errstate(invalid='ignore', over='ignore', under='ignore'):
+        if softmax:
+            e = exp32(v - v.max(0, keepdims=True))
+            return (e / e.sum(0, keepdims=True, dtype=np.float32)).astype(np.float32)
+        return (np.float32(1) / (np.float32(1) + exp32(-v))).astype(np.float32)
+
+
+def fill_probabilities(prob, full_shape, slices, softmax: bool) -> np.ndarray:
+    """Upstream's ``revert_cropping_on_probabilities`` [UPSTREAM-RECALL]: ``prob`` [K, ...] placed at ``slices`` of a float32
+    [K, *full_shape] whose rest is 0 - except head 0 of a label-map model (``softmax``), which is 1: background is certain there."""
+    out = np.zeros((prob.shape[0],) + tuple(int(v) for v in full_shape), dtype=np.float32)
+    if softmax:
+        out[0] = 1
+    out[(slice(None),) + tuple(slices)] = prob
+    return out
+
+
+def probabilities_statement(logits_f16, rect, out_hw, full_hw, box_yx, mode) -> np.ndarray:
+    """The numpy statement of the device's probabilities (csrc/kernels_prob.h; C-ABI ts2d_ensemble_predict_tiled_probabilities and
+    ts2d_probabilities_from_logits): the rectangle ``rect = (y, x, h, w)`` of the aggregated half logits [K, Hp, Wp] widened to float32,
+    every plane resampled to ``out_hw`` by :func:`preprocess.resize_linear_f64` - NOT where ``out_hw == (h, w)``, as in
+    :func:`labelmap_statement` - then :func:`inference_nonlinearity` (``mode`` of :data:`PROBABILITY_MODES`: the softmax for 'labelmap',
+    else the sigmoid) and :func:`fill_probabilities` into ``full_hw`` with the rectangle at ``box_yx``.  float32 [K, full_h, full_w].
+    The resampled logits are the device's bit for bit; the probabilities are not (another ``exp``): both lie within a few float32 units
+    of the exact value (tests/test_probabilities_cpu.py, tests/test_gpu_probabilities.py)."""
+    from .preprocess import resize_linear_f64
+    if mode not in PROBABILITY_MODES:
+        raise ValueError(f"mode must be one of {PROBABILITY_MODES}, found {mode!r}")
+    y, x, h, w = (int(v) for v in rect)
+    out_hw = tuple(int(v) for v in out_hw)
+    by, bx = (int(v) for v in box_yx)
+    lg = np.asarray(logits_f16)[:, y:y + h, x:x + w].astype(np.float32)
+    if out_hw != (h, w):
+        with np.errstate(invalid='ignore'):          # (a zero weight on an infinite sample: NaN)
+            lg = np.stack([resize_linear_f64(pl, out_hw) for pl in lg])
+    softmax = mode == 'labelmap'
+    return fill_probabilities(inference_nonlinearity(lg, softmax), full_hw, (slice(by, by + out_hw[0]), slice(bx, bx + out_hw[1])), softmax)
+
+
 def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties: dict, multilabel: bool = True,
-                                                                transpose_backward=(0, 1, 2), regions=None) -> np.ndarray:
+                                                                transpose_backward=(0, 1, 2), regions=None,
+                                                                return_probabilities: bool = False, probabilities=None):
     """[K, Z, H, W] logits (any float dtype) -> uint8 segmentation in the ORIGINAL (pre-crop) array shape:
     multilabel: [K, Z0, H0, W0] of {0,1}; otherwise a label map [Z0, H0, W0] - the argmax over the heads or, with ``regions`` (the
     ``regions_class_order`` of a region-based model, one class value per head), ``sigmoid > 0.5`` per head painted in that order.
     Upstream first resamples the logits back to
     ``properties['shape_after_cropping_and_before_resampling']`` (``resampling_fn_probabilities``: order 1, per slice for the 2-D
-    configurations [UPSTREAM-RECALL]) - a no-op when the plan's spacing is the image's."""
+    configurations [UPSTREAM-RECALL]) - a no-op when the plan's spacing is the image's.
+    ``return_probabilities``: ``(segmentation, probabilities)`` - the host route of ``save_probabilities``: the inference non-linearity
+    in float32 on the resampled logits (:func:`inference_nonlinearity`: sigmoid, or softmax for a label-map model), the crop reverted
+    on them (:func:`fill_probabilities`) and ``transpose_backward`` applied: float32 [K, Z0, H0, W0] [UPSTREAM-RECALL].  It needs the
+    logits; the segmentation is decided on them exactly as without the flag.
+    ``probabilities`` (with ``return_probabilities``): the device has done all of it (HIPnnUNetPredictor.
+    predict_probabilities_from_preprocessed_data) - ``logits`` is then its decided uint8 map and ``probabilities`` its float32
+    [K, Z0, H0, W0], both already in the PRE-CROP shape: only ``transpose_backward`` is left."""
     lg = np.asarray(logits)
+    if probabilities is not None:
+        if not return_probabilities or lg.dtype != np.uint8:
+            raise ValueError("device probabilities come with return_probabilities and the decided uint8 map")
+        seg = lg if multilabel else lg[0]
+        tb = list(transpose_backward)
+        return ((seg.transpose([0] + [i + 1 for i in tb]) if multilabel else seg.transpose(tb)),
+                np.asarray(probabilities, dtype=np.float32).transpose([0] + [i + 1 for i in tb]))
+    if return_probabilities and lg.dtype == np.uint8:
+        raise ValueError("probabilities need the logits, found an already decided uint8 prediction")
     tgt = tuple(properties.get('shape_after_cropping_and_before_resampling', lg.shape[1:]))
     if tuple(lg.shape[1:]) != tgt:
         from .preprocess import resample_data_to_shape
@@ -98,7 +168,8 @@ def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properti
             seg = (lg.astype(np.float32) > SIGMOID_HALF_THRESHOLD).astype(np.uint8)
         out = np.zeros((lg.shape[0],) + shape0, dtype=np.uint8)
         out[(slice(None),) + sl] = seg
-        return out.transpose([0] + [i + 1 for i in transpose_backward])
+        out = out.transpose([0] + [i + 1 for i in transpose_backward])
+        return (out, _host_probabilities(lg, shape0, sl, False, transpose_backward)) if return_probabilities else out
     if lg.dtype == np.uint8:
         # already resampled and decided on the device (HIPnnUNetPredictor.predict_labelmap_from_preprocessed_data): ONE plane of labels,
         # the argmax of a label-map model or the painted regions of a region-based one
@@ -112,7 +183,15 @@ def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properti
         seg = lg.astype(np.float32).argmax(0).astype(np.uint8)
     out = np.zeros(shape0, dtype=np.uint8)
     out[sl] = seg
-    return out.transpose(list(transpose_backward))
+    out = out.transpose(list(transpose_backward))
+    return (out, _host_probabilities(lg, shape0, sl, regions is None, transpose_backward)) if return_probabilities else out
+
+
+def _host_probabilities(lg, shape0, sl, softmax: bool, transpose_backward) -> np.ndarray:
+    """The probabilities of the host route: the (resampled) logits ``lg`` [K, Z, H, W] in float32 through the non-linearity, the crop
+    reverted, ``transpose_backward`` applied."""
+    prob = fill_probabilities(inference_nonlinearity(lg.astype(np.float32), softmax), shape0, sl, softmax)
+    return prob.transpose([0] + [i + 1 for i in transpose_backward])
 
 
 def segmentation_to_image(seg: np.ndarray, ref: nrrd.Image, multilabel: bool, labels: Optional[Dict[int, str]] = None,
@@ -135,15 +214,32 @@ def segmentation_to_image(seg: np.ndarray, ref: nrrd.Image, multilabel: bool, la
 
 def export_prediction_from_logits(logits, properties: dict, configuration_manager, plans_manager, dataset_json: dict,
                                   ofile_truncated: str, save_probabilities: bool = False, ref_image: Optional[nrrd.Image] = None,
-                                  labels: Optional[Dict[int, str]] = None, colors: Optional[dict] = None) -> nrrd.Image:
+                                  labels: Optional[Dict[int, str]] = None, colors: Optional[dict] = None,
+                                  probabilities=None) -> nrrd.Image:
+    """``save_probabilities`` [UPSTREAM-RECALL: export_prediction_from_logits]: beside the segmentation ``<ofile>.npz``
+    (``np.savez_compressed``, key ``probabilities``: float32 [K, *original shape]) and ``<ofile>.pkl`` (the case's properties) are
+    written; the returned image carries the array as ``img.probabilities`` (the one thing a caller without an output file gets).
+    ``probabilities``: the device's array, ``logits`` then being its decided map (see :func:`convert_...`)."""
     from .labels import label_convention
     conv = label_convention(dataset_json)
     multilabel = conv.kind == 'multilabel'
     tb = getattr(plans_manager, 'transpose_backward', [0, 1, 2])
-    seg = convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties, multilabel, tb, regions=conv.class_order)
+    prob = None
+    if save_probabilities:
+        seg, prob = convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties, multilabel, tb, regions=conv.class_order,
+                                                                                return_probabilities=True, probabilities=probabilities)
+    else:
+        seg = convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties, multilabel, tb, regions=conv.class_order)
     if ref_image is None:
         ref_image = nrrd.read(properties['sitk_stuff']['files'][0])
     img = segmentation_to_image(seg, ref_image, multilabel, labels, colors)
+    if prob is not None:
+        img.probabilities = prob
     if ofile_truncated:
         nrrd.write(img, ofile_truncated + dataset_json.get('file_ending', '.nrrd'), True)
+        if prob is not None:
+            import pickle
+            np.savez_compressed(ofile_truncated + '.npz', probabilities=prob)
+            with open(ofile_truncated + '.pkl', 'wb') as f:
+                pickle.dump(properties, f)
     return img

@@ -43,7 +43,7 @@ def _enumerate_cases(src: str):
 
 
 def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fetch_remote: bool = True, collapse: bool = False,
-             visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1):
+             visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1, save_probabilities: bool = False):
     model = DEFAULT_MODEL if model is None else model
     content = 'all' if visualize else 'file'
     which = 'all' if save_all else 'final'
@@ -58,13 +58,16 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
                 group = cases[g0:g0 + batch_cases]
                 for i, (name, _) in enumerate(group):
                     log(f"[{g0 + i + 1}/{len(cases)}] Processing: {name}")
-                for (name, _), res in zip(group, ts.predict_many([path for _, path in group], collapse=collapse, max_cases=batch_cases)):
+                for (name, _), res in zip(group, ts.predict_many([path for _, path in group], collapse=collapse, max_cases=batch_cases,
+                                                                  probabilities=save_probabilities)):
                     res.save(dest=dest, name=name, models=which, content=content, targets=['segmentation', 'projection'])
+                    res.save_probabilities(dest, name)
             return
         for i, (name, path) in enumerate(cases):
             log(f"[{i + 1}/{len(cases)}] Processing: {name}")
-            res = ts.predict(path, collapse=collapse)
+            res = ts.predict(path, collapse=collapse, probabilities=save_probabilities)
             res.save(dest=dest, name=name, models=which, content=content, targets=['segmentation', 'projection'])
+            res.save_probabilities(dest, name)
 
 
 def ts2d_entry_point(argv=None):
@@ -81,11 +84,13 @@ def ts2d_entry_point(argv=None):
     p.add_argument("--silent", action="store_true", help="Hides any unnecessary output.")
     p.add_argument("--batch-cases", type=int, default=1, help="Cases of a directory that share one engine batch per sub-model (1: one case at a time). "
                    "A case's result does not depend on the other cases of its batch.")
+    p.add_argument("--save-probabilities", action="store_true", help="Also write the probabilities of every sub-model: one "
+                   "<case>-<group>.npz (key 'probabilities', float32 [K, *shape of the sub-model's 2-D input]) per sub-model.")
     a = p.parse_args(argv)
     if a.batch_cases < 1:
         p.error("--batch-cases must be at least 1")
     ts2d_run(src=a.src, dest=a.dest, model=a.model, use_remote=not a.no_remote, fetch_remote=not a.no_fetch, collapse=a.collapse,
-             visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases)
+             visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases, save_probabilities=a.save_probabilities)
 
 
 if __name__ == '__main__':

@@ -42,6 +42,7 @@ class HIPModel:
         self.device_threshold = True     # thresholded segmentation straight from the device where the export needs no logits (_run)
         self.device_labelmap = True      # a label-map (non-multilabel) model: resample-back and argmax on the device, ONE uint8 plane to the host (_run); the host route's bytes
         self.device_regions = True       # a region-based model (label values are lists + regions_class_order): resample-back, sigmoid predicate and painting in class order on the device, ONE uint8 plane to the host (_run); the host route's bytes
+        self.device_probabilities = True  # save_probabilities: resample-back, sigmoid / softmax, the fill around the crop box and the decision in one kernel, float32 planes of the pre-crop extent to the host (_run); the host route's segmentation bytes, its probabilities to a few float32 units
         self.device_input_resample = True   # order-3 resample of an off-spacing case's input on the device: the same float32 values as scipy, bit for bit (preprocess.resize_cubic_f64)
         self.device_input_normalize = True  # crop box, z-score (and that resample) of a native 2-D input on device-resident planes: the same float32 values as numpy, bit for bit (preprocess.zscore_f32_statement)
         self.device_input_normalize_schemes = True  # the same for every other nnU-Net scheme (masked z-score, CT, Rescale, RGB, none): the cases device_input_normalize leaves to numpy, the same bits (preprocess.*_f32_statement)
@@ -125,7 +126,12 @@ class HIPModel:
             self._predictor = None
 
     # ------------------------------------------------------------------ apply (reference nnu.py:169-241)
-    def apply(self, inputs: Union[str, nrrd.Image, List, Dict], result_dir: Optional[str] = None, override: bool = True):
+    def apply(self, inputs: Union[str, nrrd.Image, List, Dict], result_dir: Optional[str] = None, override: bool = True,
+              save_probabilities: bool = False):
+        """``save_probabilities`` (reference: ``ParallelPredictor.predict(..., save_probabilities=True)``, ts2d/core/inference/predictor.py:99-111):
+        with a ``result_dir`` ``<name>.npz`` (key ``probabilities``: float32 [K, *original shape]) and ``<name>.pkl`` (the case's
+        properties) appear beside ``<name>.nrrd``; without one the returned image carries the array as ``img.probabilities``.  The
+        segmentation is byte for byte that of the same call without the flag."""
         if self._predictor is None:
             raise RuntimeError("model is not started")
         single = isinstance(inputs, (str, nrrd.Image))
@@ -136,7 +142,7 @@ class HIPModel:
         results = {}
         for name, img in inputs.items():          # one input at a time through all four stages, as the reference's worker
             try:
-                results.update(self._run({name: img}, result_dir, override, batched=False, stamps={}))
+                results.update(self._run({name: img}, result_dir, override, batched=False, stamps={}, save_probabilities=save_probabilities))
             except Exception as ex:
                 raise RuntimeError(f"Prediction failed for: {name}: {ex}") from ex
         return next(iter(results.values())) if single else results
@@ -226,7 +232,27 @@ class HIPModel:
             out = [p.predict_logits_from_preprocessed_data(d) if o is None else o for d, o in zip(datas, out)]
         return [o.cpu().numpy() if hasattr(o, 'cpu') else o for o in out]
 
-    def _run(self, inputs: dict, result_dir, override, batched: bool, stamps: dict) -> dict:
+    def _predict_probabilities(self, group, batched: bool):
+        """Stage 2 of :meth:`_run` for cases that ask for probabilities and can have them from the device: per case ``(decided map,
+        probabilities)`` of the predictor's probabilities method - the extent before resampling, the extent before cropping and the crop
+        box's origin go with each case - or, where it answers None, the logits (:meth:`_predict`): the export then takes the host route."""
+        p = self._predictor
+        name = 'predict_probabilities_from_preprocessed_data'
+        datas = [t[3] for t in group]
+        outs = [tuple(t[4].get('shape_after_cropping_and_before_resampling', np.asarray(t[3]).shape[1:])) for t in group]
+        fulls = [tuple(t[4]['shape_before_cropping']) for t in group]
+        boxes = [tuple(int(b[0]) for b in t[4]['bbox_used_for_cropping']) for t in group]
+        if batched:
+            out = getattr(p, name + '_batch')(datas, out_shapes=outs, full_shapes=fulls, boxes=boxes)
+            out = list(out) if out is not None else [None] * len(group)
+        else:
+            out = [getattr(p, name)(d, out_shape=o, full_shape=f, box=b) for d, o, f, b in zip(datas, outs, fulls, boxes)]
+        rest = [i for i, o in enumerate(out) if o is None]
+        for i, lg in zip(rest, self._predict([datas[i] for i in rest], False, batched) if rest else []):
+            out[i] = lg
+        return out
+
+    def _run(self, inputs: dict, result_dir, override, batched: bool, stamps: dict, save_probabilities: bool = False) -> dict:
         """The reference worker's four stages (``prediction_worker.py:177-242``) over ``inputs``: output file, preprocessing of every
         input, prediction (:meth:`_predict`, per group of inputs that share the fast-path decision: at most two groups), export of each.
         Each stage fails under its own name - ``"<Stage> failed for <name>: <cause>"`` - so that a HIP error (``ts2d_last_error``)
@@ -243,7 +269,8 @@ class HIPModel:
                 if result_dir is not None:
                     os.makedirs(result_dir, exist_ok=True)
                     ofile = os.path.join(result_dir, name)
-                    if not override and os.path.exists(ofile + '.nrrd'):
+                    wanted = ('.nrrd', '.npz', '.pkl') if save_probabilities else ('.nrrd',)
+                    if not override and all(os.path.exists(ofile + ext) for ext in wanted):
                         results[name] = ofile + '.nrrd'
                         continue
             except Exception as ex:
@@ -278,6 +305,17 @@ class HIPModel:
             and self._takes(lm_fn, 'out_shapes' if batched else 'out_shape') \
             and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, keyword))
 
+        # save_probabilities: the decided maps alone cannot give them.  Either the device does everything in one kernel (resample-back, the
+        # non-linearity, the fill around the crop box, the decision on the logits: kernels_prob.h) and the export receives the decided map
+        # and the float32 planes of the pre-crop extent, or the logits travel and the export's host route computes both.  The guards are
+        # those of can_lm: the predictor has the method and, where it is a double of the engine method, the `probabilities` keyword
+        pr_fn = getattr(p, 'predict_probabilities_from_preprocessed_data' + ('_batch' if batched else ''), None)
+        can_prob = save_probabilities and getattr(self, 'device_probabilities', False) and pr_fn is not None \
+            and self._takes(pr_fn, 'full_shapes' if batched else 'full_shape') \
+            and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, 'probabilities'))
+        if save_probabilities:
+            can_seg = can_export = can_lm = False
+
         def target(t):
             """The extent the device export resamples case `t` to: None = none needed, False = not a case for it (a stack, a 3-D plan,
             a predictor without the export)."""
@@ -285,14 +323,17 @@ class HIPModel:
             if not needs_logits(t[4], shape):
                 return None
             tgt = tuple(t[4]['shape_after_cropping_and_before_resampling'])
-            return tgt if (can_export or can_lm) and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] == 1 else False
-        fast = [t for t in todo if (can_seg or can_lm) and target(t) is not False]
+            return tgt if (can_export or can_lm or can_prob) and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] == 1 else False
+        fast = [t for t in todo if (can_seg or can_lm or can_prob) and target(t) is not False and (not can_prob or np.asarray(t[3]).shape[1] == 1)]
         for group, use_seg in ((fast, True), ([t for t in todo if not any(t is f for f in fast)], False)):
             if not group:
                 continue
             try:
-                out = self._predict([t[3] for t in group], use_seg, batched, [target(t) for t in group] if use_seg else None,
-                                    **({'fast': lm_name} if can_lm else {}))
+                if use_seg and can_prob:
+                    out = self._predict_probabilities(group, batched)
+                else:
+                    out = self._predict([t[3] for t in group], use_seg, batched, [target(t) for t in group] if use_seg else None,
+                                        **({'fast': lm_name} if can_lm else {}))
             except Exception as ex:
                 names = ', '.join(t[0] for t in group)
                 m = re.match(r'input (\d+): ', str(ex))          # the predictor names the offending input of the batch by index
@@ -306,24 +347,30 @@ class HIPModel:
         for name, ofile, ref, data, props, logits in todo:
             ts = self.timestamps = stamps[name]
             try:
+                more = {}
+                if save_probabilities:           # (a pair: the device's decided map and its probabilities; else the logits for the host route)
+                    more = {'save_probabilities': True, 'probabilities': logits[1] if isinstance(logits, tuple) else None}
+                    logits = logits[0] if isinstance(logits, tuple) else logits
                 seg = export_prediction_from_logits(logits, props, p.configuration_manager, p.plans_manager, p.dataset_json, ofile,
                                                     ref_image=ref, labels=self.labels,
-                                                    colors=self.colors if isinstance(self.colors, dict) else None)
+                                                    colors=self.colors if isinstance(self.colors, dict) else None, **more)
                 ts['exported'] = ts['done'] = time.time()
             except Exception as ex:
                 raise RuntimeError(f"Export failed for {name}: {ex}") from ex
             results[name] = (ofile + '.nrrd') if result_dir is not None else seg
         return {name: results[name] for name in inputs}
 
-    def apply_batch(self, inputs: Union[List, Dict], result_dir: Optional[str] = None, override: bool = True) -> dict:
+    def apply_batch(self, inputs: Union[List, Dict], result_dir: Optional[str] = None, override: bool = True,
+                    save_probabilities: bool = False) -> dict:
         """:meth:`apply` for several inputs with ONE engine batch (the reference's ``apply`` submits every input to its worker pool before
         it waits, ``ts2d/core/inference/nnu.py:194-216``): the stages of :meth:`_run` over all inputs, the prediction one predictor
         batch call per fast-path group.  Inside the batched engine call the network always takes the full-batch dispatch, so an
         input's result does not depend on the other inputs of the call.  Errors: ``"<Stage> failed for <name>: <cause>"``.
-        ``batch_timestamps[name]`` holds the stamps per input; ``timestamps`` is left at the last input's values."""
+        ``batch_timestamps[name]`` holds the stamps per input; ``timestamps`` is left at the last input's values.
+        ``save_probabilities``: as in :meth:`apply`."""
         if self._predictor is None:
             raise RuntimeError("model is not started")
         if isinstance(inputs, (list, tuple)):
             inputs = {f'image{i + 1}': img for i, img in enumerate(inputs)}
         self.batch_timestamps = {}
-        return self._run(inputs, result_dir, override, batched=True, stamps=self.batch_timestamps)
+        return self._run(inputs, result_dir, override, batched=True, stamps=self.batch_timestamps, save_probabilities=save_probabilities)

@@ -183,7 +183,7 @@ class HIPnnUNetPredictor:
                     'value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32')
 
     def _sliding_window_batch(self, list_of_data, fold: Optional[int] = 0, want_seg: bool = False, one_call: bool = True, out_shapes=None,
-                              labelmap: bool = False, regions=None):
+                              labelmap: bool = False, regions=None, probabilities=None):
         """One fold, N inputs [C,Z,H,W]: pad, tile, tiles x mirror variants through the engine, upstream's fp16 Gaussian aggregation
         on the device.  Every z slice of every input is one image.  ``one_call``: all images in ONE engine call (C-ABI
         ts2d_engine_predict_tiled_batch: the network takes the full-batch dispatch, an input's bytes do not depend on its batch-mates,
@@ -204,16 +204,39 @@ class HIPnnUNetPredictor:
         ``regions`` (a region-based model: its ``regions_class_order``, one class value per head; single-slice inputs): the same call
         shape through C-ABI ts2d_ensemble_predict_tiled_regions - the device resamples as for ``labelmap``, thresholds every head with the
         export's predicate and paints the regions in that order (:func:`export.regions_statement`, byte for byte): uint8 [1,1,h,w] per input.
+        ``probabilities`` (single-slice inputs): one ``((full_h, full_w), (box_y, box_x))`` per input - the extent the case had before
+        cropping and where its rectangle sits in it.  ONE engine call (C-ABI ts2d_ensemble_predict_tiled_probabilities) over fold ``fold``
+        or every fold and their mean: the device resamples as above, applies the inference non-linearity of the model's convention
+        (``labelmap``: softmax; ``regions`` or neither: sigmoid), writes the float32 planes of the full extent with upstream's fill around
+        the rectangle and decides the map on the logits in the same pass (csrc/kernels_prob.h; :func:`export.probabilities_statement`):
+        ``(uint8 [1,1,full_h,full_w] - multilabel [K,1,full_h,full_w] -, float32 [K,1,full_h,full_w])`` per input.
         (The one method that touches the engine, under the name the test infrastructure overrides: tests/batch_util.py replaces it, and
         tests/host_predictor.py predict_sliding_window_return_logits, with the host restatement.)"""
         patch = tuple(self.configuration_manager.patch_size)
         ensemble = fold is None
-        images, tiles, owner, reverts, shapes = self._pad_and_tile(list_of_data, patch, single_slice=ensemble or labelmap or regions is not None)
+        images, tiles, owner, reverts, shapes = self._pad_and_tile(list_of_data, patch, single_slice=ensemble or labelmap or regions is not None or probabilities is not None)
         if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
             raise AssertionError('mirror_axes does not match the dimension of the input!')
         g = sw.compute_gaussian(patch) if self.use_gaussian else None
         axes = self.allowed_mirroring_axes if self.use_mirroring else None
         e = None if ensemble else self.engines[fold]
+        if probabilities is not None:
+            from .engine import predict_tiled_probabilities_ensemble
+            if len(probabilities) != len(list_of_data):
+                raise AssertionError('probabilities needs one (full extent, box origin) per input')
+            rects = self._export_rects(list_of_data, reverts, shapes, out_shapes if out_shapes is not None else [None] * len(list_of_data), True)
+            rects = [r + tuple(int(v) for v in full) + tuple(int(v) for v in box) for r, (full, box) in zip(rects, probabilities)]
+            mode = 'regions' if regions is not None else 'labelmap' if labelmap else 'multilabel'
+            engines = self.engines if ensemble else [e]
+            probs, maps, inf = [], [], []
+            for grp in ([range(len(images))] if one_call else [[j] for j in range(len(images))]):
+                pr, dc, _ = predict_tiled_probabilities_ensemble(engines, [images[j] for j in grp], patch, [tiles[j] for j in grp], [rects[j] for j in grp],
+                                                                 mode, regions, axes, g, full_batch=one_call)
+                probs += pr
+                maps += dc
+                inf += engines[0].last_tiled_inf_per_image
+            self._raise_on_inf(inf, owner, one_call)
+            return [((d[None, None] if d.ndim == 2 else d[:, None]), pr[:, None]) for d, pr in zip(maps, probs)]
         if labelmap or regions is not None:
             from .engine import predict_tiled_labelmap_ensemble, predict_tiled_regions_ensemble
             rects = self._export_rects(list_of_data, reverts, shapes, out_shapes if out_shapes is not None else [None] * len(list_of_data), True)
@@ -384,6 +407,62 @@ class HIPnnUNetPredictor:
         if any(hw is False for hw in hws):
             return None
         return self._sliding_window_batch(datas, None if ensemble else 0, out_shapes=hws, **self._decision())
+
+    def _probability_mode(self) -> dict:
+        """The keyword of :meth:`_sliding_window_batch` for this model's convention, as :meth:`_decision` - nothing for a multilabel model."""
+        from .labels import label_convention
+        return {} if label_convention(self.dataset_json).kind == 'multilabel' else self._decision()
+
+    @staticmethod
+    def _full_and_box(hw, data, full_shape, box):
+        """``full_shape`` ((h, w) or (1, h, w); None: the output extent) and ``box`` ((y, x) or (0, y, x); None: the origin) of the
+        probabilities methods -> ``((full_h, full_w), (box_y, box_x))``, or None where they describe no 2-D placement of the output."""
+        out = tuple(int(v) for v in (hw if hw is not None else data.shape[2:]))
+        full = out if full_shape is None else tuple(int(v) for v in full_shape)
+        at = (0, 0) if box is None else tuple(int(v) for v in box)
+        if len(full) == 3 and full[0] == 1:
+            full = full[1:]
+        if len(at) == 3 and at[0] == 0:
+            at = at[1:]
+        if len(full) != 2 or len(at) != 2 or min(at) < 0 or any(o + a > f for o, a, f in zip(out, at, full)):
+            return None
+        return full, at
+
+    def predict_probabilities_from_preprocessed_data(self, data, out_shape=None, full_shape=None, box=None):
+        """The export's PROBABILITIES from the device (``save_probabilities`` of the reference's predictor, predictor.py:99-111): the
+        twin of :meth:`predict_segmentation_from_preprocessed_data` / :meth:`predict_labelmap_from_preprocessed_data` that also returns
+        what the export computes in front of the decision.  ``out_shape`` as there; ``full_shape`` ((h, w) or (1, h, w)): the case's
+        ``shape_before_cropping``, ``box`` ((y, x) or (0, y, x)): where the crop box begins in it (None, None: the output is the whole).
+        Returns ``(decided uint8, float32 [K,1,full_h,full_w])`` - the decided map [1,1,full_h,full_w] of a label-map or region-based
+        model or the thresholded planes [K,1,full_h,full_w] of a multilabel one, in the PRE-CROP extent, 0 outside the box, inside it the
+        bytes of the sibling methods; the probabilities with upstream's fill (0; 1 in head 0 of a label-map model) - or None wherever the
+        siblings return None, and with a library built before the entry."""
+        out = self.predict_probabilities_from_preprocessed_data_batch([data], None if out_shape is None else [out_shape], [full_shape], [box],
+                                                                      one_call=False)
+        return None if out is None else out[0]
+
+    def predict_probabilities_from_preprocessed_data_batch(self, list_of_data, out_shapes=None, full_shapes=None, boxes=None, one_call: bool = True):
+        """:meth:`predict_probabilities_from_preprocessed_data` for a list of inputs: ``(decided, probabilities)`` per input from ONE
+        engine call (every fold of an ensemble in it), or None.  ``out_shapes`` / ``full_shapes`` / ``boxes``: one entry (or None) per input."""
+        from .engine import has_probabilities
+        datas = [_to_numpy(d) for d in list_of_data]
+        ensemble = self._device_ensemble()
+        if not (ensemble or len(self.list_of_parameters) == len(self.engines) == 1) or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
+            return None
+        if not has_probabilities():
+            return None
+        if not datas:
+            return []
+        n = len(datas)
+        if any(v is not None and len(v) != n for v in (out_shapes, full_shapes, boxes)):
+            return None
+        hws = [self._in_plane(s, d) for s, d in zip(out_shapes, datas)] if out_shapes is not None else [None] * n
+        if any(hw is False for hw in hws):
+            return None
+        place = [self._full_and_box(hw, d, f, b) for hw, d, f, b in zip(hws, datas, full_shapes or [None] * n, boxes or [None] * n)]
+        if any(pl is None for pl in place):
+            return None
+        return self._sliding_window_batch(datas, None if ensemble else 0, one_call=one_call, out_shapes=hws, probabilities=place, **self._probability_mode())
 
     def predict_logits_from_preprocessed_data(self, data):
         """Fold ensemble (upstream: sum over ``list_of_parameters`` then ``/= n``).  Accepts numpy or torch [C,1,H,W];

@@ -130,22 +130,26 @@ class TS2D:
             result['projections'] = cache['projections']
         return TS2D.Result(result)
 
-    def predict(self, input: Union[nrrd.Image, str], collapse: bool = False, merge: bool = True) -> "TS2D.Result":
+    def predict(self, input: Union[nrrd.Image, str], collapse: bool = False, merge: bool = True, probabilities: bool = False) -> "TS2D.Result":
+        """``probabilities``: every sub-model also returns the probabilities of its export (``HIPModel.apply(save_probabilities=True)``:
+        float32 [K, *shape of its 2-D input]), kept per sub-model and reachable through ``Result.get_probabilities(model)``.  There is no
+        merged array: the reference defines none.  The segmentations are byte for byte those of the call without the flag."""
         input = self._as_image(input)
         cache: dict = {}
         # input side per sub-model (projections are computed once and cached), then the networks
         prepared = {mid: self._prepare_model_input(mid, input, cache) for mid in sorted(self.models)}
-        done = self._fan_out(lambda mid: self._apply_model(mid, prepared[mid], collapse))
+        done = self._fan_out(lambda mid: self._apply_model(mid, prepared[mid], collapse, probabilities))
         return self._result(input, cache, done, merge)
 
-    def predict_many(self, inputs, collapse: bool = False, merge: bool = True, max_cases: int = 8) -> List["TS2D.Result"]:
+    def predict_many(self, inputs, collapse: bool = False, merge: bool = True, max_cases: int = 8, probabilities: bool = False) -> List["TS2D.Result"]:
         """:meth:`predict` for several cases: per sub-model ONE engine batch over groups of at most ``max_cases`` cases
         (``HIPModel.apply_batch``) instead of one small batch per case; the sub-models run concurrently on their own threads and streams as
         in :meth:`predict`.  Inside a batched engine call the network always takes the full-batch dispatch, so a case's result does not
         depend on which other cases travel with it, on their order or on ``max_cases``; against :meth:`predict` (small-batch dispatch)
         it agrees to fp32 summation order (a few float16 ulps at most on the aggregated logits: each rounding into the half buffer may flip).
         ``max_cases=8`` makes 64 network rows for the default case of 2 tiles x 4 mirror passes.  Host memory: every case of a group holds
-        its K result planes of Hp x Wp bytes per sub-model until the group is exported (float16 planes where an export resamples)."""
+        its K result planes of Hp x Wp bytes per sub-model until the group is exported (float16 planes where an export resamples).
+        ``probabilities``: as in :meth:`predict` (``HIPModel.apply_batch(save_probabilities=True)``)."""
         images = [self._as_image(inp) for inp in inputs]
         max_cases = max(1, int(max_cases))
         order = sorted(self.models)
@@ -155,7 +159,7 @@ class TS2D:
         def run_model(mid):
             out = []
             for g0 in range(0, len(images), max_cases):
-                out += self._apply_model_batch(mid, [pr[mid] for pr in prepared[g0:g0 + max_cases]], collapse, first=g0)
+                out += self._apply_model_batch(mid, [pr[mid] for pr in prepared[g0:g0 + max_cases]], collapse, first=g0, probabilities=probabilities)
             return out
         done = self._fan_out(run_model)
         return [self._result(img, cache, {mid: done[mid][i] for mid in order}, merge) for i, (img, cache) in enumerate(zip(images, caches))]
@@ -165,6 +169,8 @@ class TS2D:
         input, input2d, native_2d = prepared
         res = {'id': mid, 'revision': self.models[mid].revision}
         res['model'], res['group'] = decompose_model_key(mid)
+        if getattr(seg, 'probabilities', None) is not None:      # (asked for: the array rides on the image the export returned)
+            res['probabilities'] = seg.probabilities
         if not (collapse or native_2d):
             seg = restore_dimension(seg, input)
         res['input'] = input2d if collapse else input
@@ -172,16 +178,17 @@ class TS2D:
         res['timestamps'] = dict(timestamps)
         return res
 
-    def _apply_model(self, mid: str, prepared, collapse: bool) -> dict:
+    def _apply_model(self, mid: str, prepared, collapse: bool, probabilities: bool = False) -> dict:
         """Reference tool.py:172-174: ``model.apply`` + restoring the 3-D geometry."""
         model = self.models[mid]
-        return self._model_result(mid, prepared, collapse, model.apply(prepared[1]), model.timestamps)
+        more = {'save_probabilities': True} if probabilities else {}
+        return self._model_result(mid, prepared, collapse, model.apply(prepared[1], **more), model.timestamps)
 
-    def _apply_model_batch(self, mid: str, prepared: list, collapse: bool, first: int = 0) -> List[dict]:
+    def _apply_model_batch(self, mid: str, prepared: list, collapse: bool, first: int = 0, probabilities: bool = False) -> List[dict]:
         """:meth:`_apply_model` for a group of cases: one ``model.apply_batch``."""
         model = self.models[mid]
         names = [f'case{first + i + 1}' for i in range(len(prepared))]
-        segs = model.apply_batch({n: pr[1] for n, pr in zip(names, prepared)})
+        segs = model.apply_batch({n: pr[1] for n, pr in zip(names, prepared)}, **({'save_probabilities': True} if probabilities else {}))
         return [self._model_result(mid, pr, collapse, segs[n], model.batch_timestamps[n]) for n, pr in zip(names, prepared)]
 
     def _predict_model(self, mid: str, input: nrrd.Image, collapse: bool, cache: dict) -> dict:
@@ -239,6 +246,22 @@ class TS2D:
 
         def get_segmentation(self, model: Optional[str] = None):
             return self.data.get('models', {}).get(model, {}).get('segmentation') if model is not None else self.data.get('segmentation')
+
+        def get_probabilities(self, model: str):
+            """float32 [K, *shape of the sub-model's 2-D input] of sub-model ``model`` (``predict(..., probabilities=True)``), else None."""
+            return self.data.get('models', {}).get(model, {}).get('probabilities')
+
+        def save_probabilities(self, dest: str, name: str = 'result', naming: str = 'group') -> List[str]:
+            """One ``<name>-<group or model>.npz`` (``np.savez_compressed``, key ``probabilities``) per sub-model that has them."""
+            assert naming in {'group', 'model'}
+            os.makedirs(dest, exist_ok=True)
+            written = []
+            for key in self.models:
+                prob = self.get_probabilities(key)
+                if prob is not None:
+                    written.append(os.path.join(dest, f"{name}-{(decompose_model_key(key)[1] or key) if naming == 'group' else key}.npz"))
+                    np.savez_compressed(written[-1], probabilities=prob)
+            return written
 
         def get_projection(self, channel: Optional[str] = None):
             pr = self.data.get('projections', {})
