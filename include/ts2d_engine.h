@@ -78,6 +78,32 @@ typedef struct ts2d_engine ts2d_engine;
 int ts2d_engine_create(const ts2d_arch_desc* arch, const float* weights, size_t n_floats, int device,
                        ts2d_engine** out);
 
+/* nnU-Net's ResidualEncoderUNet (the nnUNetResEncUNet{M,L,XL}Plans presets; 2-D, `block` = BasicBlockD): what it adds to the descriptor.
+ * The encoder is a stem (Conv 3x3 stride 1 + bias, InstanceNorm, LeakyReLU: input_channels -> features[0]) and per stage s n_blocks[s]
+ * blocks out = lrelu(conv2(conv1(x)) + skip(x)): conv1 = Conv 3x3 (block 0: the stage's stride) + bias, norm, LeakyReLU; conv2 = Conv 3x3 +
+ * bias, norm, NO non-linearity; skip = the identity, or AvgPool2d(kernel = stride) where the block has a stride, followed by Conv 1x1
+ * WITHOUT bias + norm (no non-linearity) where the block changes the width.  Decoder and head are those of ts2d_arch_desc. */
+typedef struct {
+    int32_t n_blocks[TS2D_MAX_STAGES];      /* arch_kwargs['n_blocks_per_stage'], >= 1 each */
+    int32_t reserved[16];                   /* must be zero */
+} ts2d_residual_desc;
+
+/* ts2d_engine_create for a ResidualEncoderUNet.  `arch`: as above, its n_conv_enc is ignored.  Not supported (TS2D_ERR_INVALID):
+ * bottleneck blocks, squeeze-excitation, a stem width other than features[0], conv_bias = False - the descriptor cannot even name them;
+ * the caller (arch.py: UNetArch.from_plans) refuses such plans.
+ * Blob order (PyTorch layouts, n_floats must match exactly):
+ *   encoder.stem.convs.0.{conv.weight, conv.bias, norm.weight, norm.bias};
+ *   per stage s and block b: encoder.stages.{s}.blocks.{b}.conv1.{conv.weight, conv.bias, norm.weight, norm.bias}, then
+ *   ...conv2.{conv.weight, conv.bias, norm.weight, norm.bias}, then - only where features[s - 1] != features[s], b = 0 - the projection
+ *   ...skip.{i}.{conv.weight [Cout, Cin, 1, 1], norm.weight, norm.bias} (i = 1 behind an AvgPool2d, else 0);
+ *   then the decoder and the head exactly as for ts2d_engine_create.
+ * Every entry that takes an engine takes this one.  TS2D_PRECISION_F32_SPLIT_F16X3 and TS2D_PRECISION_F32_EXACT are supported;
+ * ts2d_engine_set_precision(e, TS2D_PRECISION_F16) returns TS2D_ERR_INVALID and leaves the mode unchanged.
+ * ts2d_engine_debug_tensor names: "stem", "enc{s}.b{b}.c1", "enc{s}.b{b}.c2" and "enc{s}.b{b}.proj" (normalised, NOT activated - as the
+ * join reads them) and "enc{s}.b{b}" (the block's output); the decoder's names are unchanged. */
+int ts2d_engine_create_residual(const ts2d_arch_desc* arch, const ts2d_residual_desc* residual, const float* weights, size_t n_floats,
+                                int device, ts2d_engine** out);
+
 /* Replace the weights of an existing engine (fold switch: `network.load_state_dict(params)` in
  * predict_logits_from_preprocessed_data, reference call site prediction_worker.py:209). */
 int ts2d_engine_load_weights(ts2d_engine* e, const float* weights, size_t n_floats);

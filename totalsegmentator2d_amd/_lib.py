@@ -26,6 +26,11 @@ class ArchDesc(ctypes.Structure):
                 ('strides', (ctypes.c_int32 * 2) * MAX_STAGES)]
 
 
+class ResidualDesc(ctypes.Structure):
+    """``ts2d_residual_desc``: what a ResidualEncoderUNet adds to ``ts2d_arch_desc``."""
+    _fields_ = [('n_blocks', ctypes.c_int32 * MAX_STAGES), ('reserved', ctypes.c_int32 * 16)]
+
+
 class TiledImage(ctypes.Structure):
     """``ts2d_tiled_image``: one image of ``ts2d_engine_predict_tiled_batch``."""
     _fields_ = [('image', ctypes.c_void_p), ('Hp', ctypes.c_int32), ('Wp', ctypes.c_int32), ('n_tiles', ctypes.c_int32),
@@ -65,6 +70,7 @@ SIGNATURES = {
     'ts2d_abi_version': (_I, []),                 # first: load() checks it before it looks up the rest
     'ts2d_last_error': (_S, []),
     'ts2d_engine_create': (_I, [ctypes.POINTER(ArchDesc), _P, _Z, _I, _PP]),
+    'ts2d_engine_create_residual': (_I, [ctypes.POINTER(ArchDesc), ctypes.POINTER(ResidualDesc), _P, _Z, _I, _PP]),
     'ts2d_engine_load_weights': (_I, [_P, _P, _Z]),
     'ts2d_engine_weight_buffer': (_I, [_P, _PP, ctypes.POINTER(_Z)]),
     'ts2d_engine_weights_ready': (_I, [_P]),
@@ -112,7 +118,8 @@ SIGNATURES = {
 SYMBOLS = tuple(SIGNATURES)
 # added under ABI 9 (the cubic resample; the device-resident planes of preprocess.DevicePlanes, ts2d_planes_crop_normalize after the others):
 # a library built before them lacks the symbols, still loads, and the callers keep the host route; the probabilities entries likewise
-OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n)
+# ... and the residual-encoder entry: without it a ResidualEncoderUNet cannot be created (Engine says so), a plain net is unaffected
+OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n or n == 'ts2d_engine_create_residual')
 
 
 class EngineLibraryError(RuntimeError):

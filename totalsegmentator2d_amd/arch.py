@@ -1,4 +1,4 @@
-"""Architecture descriptor for the 2-D nnU-Net ``PlainConvUNet`` hot path.
+"""Architecture descriptor for the 2-D nnU-Net ``PlainConvUNet`` / ``ResidualEncoderUNet`` hot path.
 
 The reference never builds the network itself: ``nnUNetPredictor.initialize_from_trained_model_folder``
 (reference call site ``ts2d/core/inference/nnu.py:164-165``) reads ``plans.json`` and instantiates
@@ -17,6 +17,8 @@ from typing import Dict, List, Sequence, Tuple
 OP_CONV3X3 = 0    # Conv2d 3x3 pad 1 (+bias) -> InstanceNorm2d(affine) -> LeakyReLU   (K1/K2/K3/K6)
 OP_CONVT2X2 = 1   # ConvTranspose2d k=2 s=2 (+bias), no norm / activation             (K5)
 OP_HEAD1X1 = 2    # seg_layers[-1]: Conv2d 1x1 (+bias) -> logits                       (K7)
+OP_PROJ1X1 = 3    # residual skip path: AvgPool2d(kernel = stride) -> Conv2d 1x1 (no bias) -> InstanceNorm2d(affine), no activation
+OP_JOIN = 4       # residual join: norm(conv2) + residual; the block's LeakyReLU is applied by whoever reads the tensor
 
 
 @dataclass
@@ -37,6 +39,10 @@ class UNetArch:
     norm_eps: float = 1e-5
     norm_affine: bool = True
     leaky_slope: float = 0.01
+    # 'plain': PlainConvUNet (n_conv_per_stage convs per encoder stage).  'residual': ResidualEncoderUNet - a stem conv block, then
+    # n_blocks_per_stage[s] BasicBlockD blocks per stage (n_conv_per_stage is ignored); decoder and head are the same.
+    encoder: str = 'plain'
+    n_blocks_per_stage: Sequence[int] = ()
 
     # ------------------------------------------------------------------ constructors
     @staticmethod
@@ -58,9 +64,24 @@ class UNetArch:
             cfg = plans['configurations'][cfg['inherits_from']]
         arch = cfg['architecture']
         cls = arch['network_class_name']
-        if not cls.endswith('PlainConvUNet'):
-            raise NotImplementedError(f"network class '{cls}' is not supported by the MI355X engine (PlainConvUNet only)")
+        residual = cls.endswith('ResidualEncoderUNet')
+        if not residual and not cls.endswith('PlainConvUNet'):
+            raise NotImplementedError(f"network class '{cls}' is not supported by the MI355X engine (PlainConvUNet and ResidualEncoderUNet only)")
         kw = arch['arch_kwargs']
+        if residual:
+            if 'n_blocks_per_stage' not in kw:
+                raise NotImplementedError(f"network class '{cls}': arch_kwargs name no n_blocks_per_stage - not a ResidualEncoderUNet plan this engine can read")
+            block = kw.get('block')
+            if block is not None and not str(block).endswith('BasicBlockD'):
+                raise NotImplementedError(f"ResidualEncoderUNet block '{block}' is not supported (BasicBlockD only)")
+            if kw.get('bottleneck_channels') is not None:
+                raise NotImplementedError(f"ResidualEncoderUNet bottleneck_channels = {kw['bottleneck_channels']} is not supported (BasicBlockD has none)")
+            feats0 = kw['features_per_stage'][0] if isinstance(kw['features_per_stage'], (list, tuple)) else kw['features_per_stage']
+            if kw.get('stem_channels') is not None and int(kw['stem_channels']) != int(feats0):
+                raise NotImplementedError(f"ResidualEncoderUNet stem_channels = {kw['stem_channels']} is not supported (only features_per_stage[0] = {feats0})")
+            for name in ('squeeze_excitation', 'stochastic_depth_p'):
+                if kw.get(name):
+                    raise NotImplementedError(f"ResidualEncoderUNet {name} = {kw[name]} is not supported")
         if not str(kw['conv_op']).endswith('Conv2d'):
             raise NotImplementedError(f"conv_op {kw['conv_op']} is not supported (2-D only)")
         if not str(kw['norm_op']).endswith('InstanceNorm2d'):
@@ -79,7 +100,9 @@ class UNetArch:
             features_per_stage=tuple(int(f) for f in _per_stage(kw['features_per_stage'], n_stages)),
             kernel_sizes=tuple(tuple(k) if isinstance(k, (list, tuple)) else (k, k) for k in kw['kernel_sizes']),
             strides=tuple(tuple(s) if isinstance(s, (list, tuple)) else (s, s) for s in kw['strides']),
-            n_conv_per_stage=tuple(int(n) for n in _per_stage(kw['n_conv_per_stage'], n_stages)),
+            n_conv_per_stage=tuple(int(n) for n in _per_stage(kw.get('n_conv_per_stage', 1) if residual else kw['n_conv_per_stage'], n_stages)),
+            encoder='residual' if residual else 'plain',
+            n_blocks_per_stage=tuple(int(n) for n in _per_stage(kw['n_blocks_per_stage'], n_stages)) if residual else (),
             n_conv_per_stage_decoder=tuple(int(n) for n in _per_stage(kw['n_conv_per_stage_decoder'], n_stages - 1)),
             conv_bias=bool(kw.get('conv_bias', True)),
             norm_eps=float(nk.get('eps', 1e-5)), norm_affine=bool(nk.get('affine', True)),
@@ -117,6 +140,13 @@ class UNetArch:
             raise NotImplementedError(f"features_per_stage[0] = {self.features_per_stage[0]}: the 1x1 head kernel supports at most 64 channels")
         if any(c < 1 for c in list(self.n_conv_per_stage) + list(self.n_conv_per_stage_decoder)):
             raise ValueError("n_conv_per_stage* must be >= 1")
+        if self.encoder not in ('plain', 'residual'):
+            raise NotImplementedError(f"encoder '{self.encoder}' is not supported ('plain' or 'residual')")
+        if self.encoder == 'residual':
+            if len(self.n_blocks_per_stage) != n:
+                raise ValueError(f"n_blocks_per_stage must have {n} entries, found {len(self.n_blocks_per_stage)}")
+            if any(int(b) < 1 for b in self.n_blocks_per_stage):
+                raise ValueError("n_blocks_per_stage must be >= 1")
 
     def level_shifts(self) -> List[Tuple[int, int]]:
         """(log2 of the cumulative stride along H, along W) of every stage: a level-s tensor of an H x W input has
@@ -151,16 +181,42 @@ class UNetArch:
         self.validate()
         ops: List[dict] = []
         cur, cin = 'input', self.input_channels
-        for s in range(self.n_stages):
-            f = self.features_per_stage[s]
-            for i in range(self.n_conv_per_stage[s]):
-                stride = tuple(int(v) for v in self.strides[s]) if (i == 0 and s > 0) else (1, 1)
-                dst = f'enc{s}.c{i}'
-                ops.append(dict(op=OP_CONV3X3, name=dst, src=cur, skip=None, cin=cin, cin_skip=0, cout=f,
-                                stride=stride, level=s, dst=dst,
-                                key=f'encoder.stages.{s}.0.convs.{i}'))
-                cur, cin = dst, f
-        skips = {s: f'enc{s}.c{self.n_conv_per_stage[s] - 1}' for s in range(self.n_stages)}
+        if self.encoder == 'residual':
+            # stem, then per block conv1, conv2 (normalised, not activated), the projection of the skip path where the widths differ, and the
+            # join ``enc{s}.b{b}`` (``res``: what it adds to conv2 - the block's input, average-pooled over ``stride``, or the projection)
+            def conv(name, src, ci, f, stride, s, key, linear=False):
+                ops.append(dict(op=OP_CONV3X3, name=name, src=src, skip=None, res=None, cin=ci, cin_skip=0, cout=f, stride=stride, level=s,
+                                dst=name, key=key, linear=linear))
+            f0 = self.features_per_stage[0]
+            conv('stem', cur, cin, f0, (1, 1), 0, 'encoder.stem.convs.0')
+            cur, cin = 'stem', f0
+            for s in range(self.n_stages):
+                f = self.features_per_stage[s]
+                for b in range(self.n_blocks_per_stage[s]):
+                    stride = tuple(int(v) for v in self.strides[s]) if (b == 0 and s > 0) else (1, 1)
+                    key, nm = f'encoder.stages.{s}.blocks.{b}', f'enc{s}.b{b}'
+                    conv(f'{nm}.c1', cur, cin, f, stride, s, f'{key}.conv1')
+                    conv(f'{nm}.c2', f'{nm}.c1', f, f, (1, 1), s, f'{key}.conv2', linear=True)
+                    res, pool = cur, stride
+                    if cin != f:
+                        ops.append(dict(op=OP_PROJ1X1, name=f'{nm}.proj', src=cur, skip=None, res=None, cin=cin, cin_skip=0, cout=f, stride=stride,
+                                        level=s, dst=f'{nm}.proj', key=f'{key}.skip.{1 if stride != (1, 1) else 0}', linear=True))
+                        res, pool = f'{nm}.proj', (1, 1)
+                    ops.append(dict(op=OP_JOIN, name=nm, src=f'{nm}.c2', skip=None, res=res, cin=f, cin_skip=0, cout=f, stride=pool, level=s,
+                                    dst=nm, key=None, linear=False))
+                    cur, cin = nm, f
+            skips = {s: f'enc{s}.b{self.n_blocks_per_stage[s] - 1}' for s in range(self.n_stages)}
+        else:
+            for s in range(self.n_stages):
+                f = self.features_per_stage[s]
+                for i in range(self.n_conv_per_stage[s]):
+                    stride = tuple(int(v) for v in self.strides[s]) if (i == 0 and s > 0) else (1, 1)
+                    dst = f'enc{s}.c{i}'
+                    ops.append(dict(op=OP_CONV3X3, name=dst, src=cur, skip=None, cin=cin, cin_skip=0, cout=f,
+                                    stride=stride, level=s, dst=dst,
+                                    key=f'encoder.stages.{s}.0.convs.{i}'))
+                    cur, cin = dst, f
+            skips = {s: f'enc{s}.c{self.n_conv_per_stage[s] - 1}' for s in range(self.n_stages)}
         for j in range(self.n_stages - 1):          # decoder stage j handles skip level n-2-j
             lvl = self.n_stages - 2 - j
             f = self.features_per_stage[lvl]
@@ -192,6 +248,10 @@ class UNetArch:
                           (f'{k}.norm.weight', (cout,)), (f'{k}.norm.bias', (cout,))]
             elif op['op'] == OP_CONVT2X2:
                 specs += [(f'{k}.weight', (cin, cout) + tuple(op['stride'])), (f'{k}.bias', (cout,))]
+            elif op['op'] == OP_PROJ1X1:       # no bias
+                specs += [(f'{k}.conv.weight', (cout, cin, 1, 1)), (f'{k}.norm.weight', (cout,)), (f'{k}.norm.bias', (cout,))]
+            elif op['op'] == OP_JOIN:
+                continue
             else:
                 specs += [(f'{k}.weight', (cout, cin, 1, 1)), (f'{k}.bias', (cout,))]
         return specs
@@ -223,6 +283,12 @@ class UNetArch:
             elif op['op'] == OP_CONVT2X2:
                 m = h * w * cout * cin          # each output pixel = one tap
                 rd, wr = (h // sy) * (w // sx) * cin * act_bytes, h * w * cout * act_bytes
+            elif op['op'] == OP_PROJ1X1:        # reads the block's input at the finer extent, pools it on the way
+                m = h * w * cout * cin
+                rd, wr = h * sy * w * sx * cin * act_bytes, h * w * cout * act_bytes
+            elif op['op'] == OP_JOIN:           # conv2 and the residual (pooled over the window on the way) in, the sum out
+                m = 0
+                rd, wr = (h * w + h * sy * w * sx) * cout * act_bytes, h * w * cout * act_bytes
             else:
                 m = h * w * cout * cin
                 rd, wr = h * w * cin * act_bytes, h * w * cout * 4

@@ -186,7 +186,8 @@ bool fuse0_applies(const ts2d_engine* e, int H, int W) {
     const Op& o0 = e->ops[0]; const Op& o1 = e->ops[1];
     if (!o0.first_direct || o0.cout != 32 || e->arch.input_channels > 2) return false;
     if (o1.type != OP_CONV || !o1.res_ok || o1.src != o0.dst || o1.skip >= 0) return false;
-    for (size_t i = 2; i < e->ops.size(); ++i) if (e->ops[i].src == o0.dst || e->ops[i].skip == o0.dst) return false;      // (a one-conv stage: the tensor is a skip)
+    for (size_t i = 2; i < e->ops.size(); ++i)       // (a one-conv stage: the tensor is a skip; a residual encoder: the first join adds the stem's output)
+        if (e->ops[i].src == o0.dst || e->ops[i].skip == o0.dst || e->ops[i].res == o0.dst) return false;
     if (H % 8 || W % 32) return false;
     return fits32((size_t)H * W * 32 * 4) && fits32((size_t)e->arch.input_channels * H * W * 4);
 }
@@ -235,6 +236,20 @@ Choice pick_kernel(const ts2d_engine* e, size_t oi, int B, int H, int W, bool fu
     const Op& op = e->ops[oi];
     Choice c;
     const bool f16 = e->precision == TS2D_PRECISION_F16, exact = e->precision == TS2D_PRECISION_F32_EXACT;
+    if (op.type == OP_PROJ || op.type == OP_JOIN) {
+        // Residual blocks (kernels_resblock.h), fp32 storage only: the 16-bit contract of a residual block is not defined (K_NONE; ts2d_engine_set_precision
+        // refuses the mode on such an engine before a forward gets here).  Per-pixel work: no pixel tiling, nothing that depends on B or on an option.
+        if (f16) return c;
+        c.k = op.type == OP_PROJ ? K_PROJ : K_JOIN;
+        c.bn = op.cout % 64 == 0 ? 64 : 32;
+        if (op.type == OP_PROJ) {       // tiles of 128 rows of the batch's pixels; partial statistics per tile where an image is a whole number of them
+            const int HW = (H >> op.ly) * (W >> op.lx);
+            c.fused_stats = HW % 128 == 0;
+            c.g.NIMG = 1; c.g.tiles_x = c.fused_stats ? HW / 128 : 1; c.g.tiles_y = 1;
+            c.g.n_mtiles = (int)(((long long)B * HW + 127) / 128);
+        }
+        return c;
+    }
     if (op.type == OP_HEAD) {
         const bool hm = op.split_ok && !exact && e->use_one && e->tensors[op.src].C == 32 && (H * W) % 32 == 0 && W % 32 == 0;
         c.k = hm ? K_HEAD_MFMA : K_HEAD_1X1;
@@ -394,6 +409,8 @@ const char* kernel_name(const Op& op, const Choice& c) {
     case K_UPC_H: return b64 ? "conv3x3_upc_h<64>" : "conv3x3_upc_h<32>";
     case K_UPC_H2: return "conv3x3_upc_h2";
     case K_HEAD_MFMA: case K_HEAD_1X1: return "head";
+    case K_PROJ: return "pool_proj1x1";
+    case K_JOIN: return "res_join";
     }
     return "";
 }
@@ -440,7 +457,7 @@ size_t part_floats_needed(const ts2d_engine* e, const std::vector<Choice>& plan,
     size_t mx = 0;
     for (size_t i = 0; i < e->ops.size(); ++i) {
         const Op& op = e->ops[i];
-        if (op.type != OP_CONV) continue;
+        if (op.type != OP_CONV && op.type != OP_PROJ) continue;
         const Choice& c = plan[i];
         if (c.fused_stats) mx = std::max(mx, (size_t)B * c.g.tiles_x * c.g.tiles_y * c.ppt * op.cout * 4);      // (S, Q, K, n) per (tile, channel)
         if (e->use_sbk) mx = std::max(mx, kSbkElems / 256 * 4);      // small-batch split-K (any smaller batch in this workspace): a partial per 256 pixels and channel
@@ -468,6 +485,7 @@ ActPlan plan_activations(const ts2d_engine* e, const std::vector<Choice>& plan, 
         if (op.type == OP_CONV && op.up_idx >= 0 && skipped[op.up_idx]) { reads[i] = {e->ops[op.up_idx].src, op.skip}; continue; }
         if (!(op.first_direct)) reads[i].push_back(op.src);
         if (op.skip >= 0) reads[i].push_back(op.skip);
+        if (op.res >= 0) reads[i].push_back(op.res);
     }
     std::vector<int> last(nt, -1);
     for (size_t i = 0; i < no; ++i) for (int t : reads[i]) last[t] = (int)i;

@@ -18,6 +18,7 @@
 #include "kernels_upq.h"
 #include "kernels_upc_h.h"
 #include "kernels_upc_h2.h"
+#include "kernels_resblock.h"
 
 #include <atomic>
 #include <cstdio>
@@ -44,7 +45,7 @@ int upload_weights(ts2d_engine* e, const float* blob, size_t n_floats) {
     std::vector<float> staging, wide;
     try {
         staging.resize(e->weight_floats);
-        if (e->padded) { expand_blob(e->user_arch, e->arch, blob, wide); blob = wide.data(); }
+        if (e->padded) { expand_blob(e->user_arch, e->arch, e->residual ? e->n_blocks : nullptr, blob, wide); blob = wide.data(); }
     } catch (...) { return fail(TS2D_ERR_NOMEM, "host staging allocation failed"); }
     pack_weights(e, blob, staging.data());
     HIP_TRY(hipSetDevice(e->device));
@@ -357,6 +358,42 @@ int launch_head(ts2d_engine* e, size_t oi, const Choice& c, const Run& r) {
     return TS2D_OK;
 }
 
+// ---- residual blocks (kernels_resblock.h): the skip path's pooled 1x1 projection and the join
+int launch_proj(ts2d_engine* e, size_t oi, const Choice& c, const Run& r) {
+    const Op& op = e->ops[oi];
+    const Tensor& src = e->tensors[op.src];
+    ProjArgs pa{};
+    pa.src = src.data; pa.sc = src.scale; pa.sh = src.shift; pa.w = e->d_weights + op.dev_w; pa.dst = e->tensors[op.dst].data;
+    pa.part = c.fused_stats ? e->d_part : nullptr;
+    pa.Cin = src.C; pa.Cout = op.cout; pa.sy = op.sy; pa.sx = op.sx;
+    pa.Wt = r.W >> op.lx; pa.HW = (r.H >> op.ly) * pa.Wt; pa.Win = r.W >> src.lx; pa.M = r.B * pa.HW;
+    pa.slope = e->arch.leaky_slope; pa.inv_n = 1.0f / (float)(op.sy * op.sx);
+    if (!src.normed || src.linear || src.C % 32 || op.cout % c.bn || (r.H >> src.ly) != (r.H >> op.ly) * op.sy || pa.Win != pa.Wt * op.sx)
+        return fail(TS2D_ERR_INVALID, "internal: op %s: source of the projection is not an activated tensor of %d x the output's extent", op.name.c_str(), op.sy * op.sx);
+    if (c.fused_stats && (pa.HW % kProjBM || c.g.tiles_x != pa.HW / kProjBM))
+        return fail(TS2D_ERR_INVALID, "internal: op %s: partial statistics on tiles that span images", op.name.c_str());
+    const dim3 grid((unsigned)((pa.M + kProjBM - 1) / kProjBM), op.cout / c.bn), block(256);
+    HIP_TRY(c.bn == 64 ? launch_kernel<pool_proj1x1<64>>(grid, block, 0, r.st, pa) : launch_kernel<pool_proj1x1<32>>(grid, block, 0, r.st, pa));
+    return TS2D_OK;
+}
+
+int launch_join(ts2d_engine* e, size_t oi, const Choice&, const Run& r) {
+    const Op& op = e->ops[oi];
+    const Tensor& c2 = e->tensors[op.src]; const Tensor& rs = e->tensors[op.res]; const Tensor& dst = e->tensors[op.dst];
+    JoinArgs ja{};
+    ja.raw2 = c2.data; ja.sc2 = c2.scale; ja.sh2 = c2.shift; ja.r = rs.data; ja.scr = rs.scale; ja.shr = rs.shift;
+    ja.dst = dst.data; ja.dsc = dst.scale; ja.dsh = dst.shift;
+    ja.linear = rs.linear ? 1 : 0; ja.sy = op.sy; ja.sx = op.sx;
+    ja.Wt = r.W >> op.lx; ja.HW = (r.H >> op.ly) * ja.Wt; ja.Win = r.W >> rs.lx; ja.C = op.cout; ja.npix = r.B * ja.HW;
+    ja.slope = e->arch.leaky_slope; ja.inv_n = 1.0f / (float)(op.sy * op.sx);
+    if (!c2.normed || !rs.normed || c2.C != op.cout || rs.C != op.cout || op.cout % 32 || (r.H >> rs.ly) != (r.H >> op.ly) * op.sy || ja.Win != ja.Wt * op.sx ||
+        (rs.linear && (op.sy != 1 || op.sx != 1)))
+        return fail(TS2D_ERR_INVALID, "internal: op %s: the join's sources do not match its output", op.name.c_str());
+    const dim3 grid((unsigned)((ja.npix + 31) / 32), op.cout / 32), block(256);
+    HIP_TRY(launch_kernel<res_join>(grid, block, 0, r.st, ja));
+    return TS2D_OK;
+}
+
 // ---- every kernel that takes ConvArgs
 // The generic implicit-GEMM kernel: the whole exact mode (fp32 storage), and - in every mode - the stages whose stride is neither
 // (1, 1) nor (2, 2) (f16 = fp16 storage with the 16-bit mode's operand rounding).
@@ -581,6 +618,8 @@ int launch_op(ts2d_engine* e, size_t oi, const Choice& c, const Run& r) {
     case K_UP0: case K_UPQ: case K_UPC: case K_UPC_H: case K_UPC_H2: return launch_composed(e, oi, c, r);
     case K_S1_RES32: case K_S1_RES32F: return launch_res32(e, oi, c, r);
     case K_HEAD_MFMA: case K_HEAD_1X1: return launch_head(e, oi, c, r);
+    case K_PROJ: return launch_proj(e, oi, c, r);
+    case K_JOIN: return launch_join(e, oi, c, r);
     default: return launch_conv_family(e, oi, c, r);
     }
 }
@@ -611,6 +650,8 @@ int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, flo
     for (size_t oi = 0; oi < e->ops.size(); ++oi) {
         const Op& op = e->ops[oi];
         const Choice& c = plan[oi];
+        if (c.k == K_NONE && e->residual)
+            return fail(TS2D_ERR_INVALID, "op %s: TS2D_PRECISION_F16 is not supported on a residual-encoder engine", op.name.c_str());
         if (c.k == K_NONE) return fail(TS2D_ERR_INVALID, "op %s has no fp16 kernel (channel counts must be multiples of 16)", op.name.c_str());
         if (c.k == K_FUSED_AWAY) { e->fused_away[oi] = 1; continue; }      // composed into the next block (kernels_upc.h): the upsampled tensor is never materialised
         TRY(prof_begin(e, op.name, "", st));
@@ -618,7 +659,7 @@ int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, flo
         if (c.ksplit > 1) prof_ksplit(e, c.ksplit);
         TRY(launch_op(e, oi, c, r));
         TRY(prof_end(e, st));
-        if (op.type == OP_CONV) TRY(launch_stats(e, oi, c, r));
+        if (op.type == OP_CONV || op.type == OP_PROJ) TRY(launch_stats(e, oi, c, r));
     }
     return TS2D_OK;
 }
@@ -683,15 +724,18 @@ int ts2d_abi_version(void) { return 9; }
 
 const char* ts2d_last_error(void) { return last_error(); }
 
-int ts2d_engine_create(const ts2d_arch_desc* arch, const float* weights, size_t n_floats, int device, ts2d_engine** out) {
-    if (!arch || !out) return fail(TS2D_ERR_INVALID, "ts2d_engine_create: null argument");
+static int create_engine(const char* entry, const ts2d_arch_desc* arch, const ts2d_residual_desc* res, const float* weights, size_t n_floats, int device,
+                         ts2d_engine** out) {
+    if (!arch || !out) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
     *out = nullptr;
+    if (res) for (int v : res->reserved) if (v) return fail(TS2D_ERR_INVALID, "%s: ts2d_residual_desc.reserved must be zero", entry);
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(TS2D_ERR_INVALID, "device %d out of range (%d HIP devices visible)", device, ndev);
     ts2d_engine* e = new (std::nothrow) ts2d_engine();
     if (!e) return fail(TS2D_ERR_NOMEM, "host allocation failed");
     e->user_arch = *arch; e->device = device;
+    if (res) { e->residual = true; for (int s = 0; s < TS2D_MAX_STAGES; ++s) e->n_blocks[s] = res->n_blocks[s]; }
     if (arch->n_stages >= 2 && arch->n_stages <= TS2D_MAX_STAGES) e->arch = pad_arch(*arch, e->padded); else e->arch = *arch;
     {
         hipDeviceProp_t prop;
@@ -721,6 +765,16 @@ int ts2d_engine_create(const ts2d_arch_desc* arch, const float* weights, size_t 
     return TS2D_OK;
 }
 
+int ts2d_engine_create(const ts2d_arch_desc* arch, const float* weights, size_t n_floats, int device, ts2d_engine** out) {
+    return create_engine("ts2d_engine_create", arch, nullptr, weights, n_floats, device, out);
+}
+
+int ts2d_engine_create_residual(const ts2d_arch_desc* arch, const ts2d_residual_desc* residual, const float* weights, size_t n_floats, int device,
+                                ts2d_engine** out) {
+    if (!residual) return fail(TS2D_ERR_INVALID, "ts2d_engine_create_residual: null argument");
+    return create_engine("ts2d_engine_create_residual", arch, residual, weights, n_floats, device, out);
+}
+
 int ts2d_engine_load_weights(ts2d_engine* e, const float* weights, size_t n_floats) {
     if (!e || !weights) return fail(TS2D_ERR_INVALID, "ts2d_engine_load_weights: null argument");
     HIP_TRY(hipSetDevice(e->device));
@@ -739,6 +793,9 @@ int ts2d_engine_set_precision(ts2d_engine* e, int mode) {
     if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_set_precision: null engine");
     if (mode != TS2D_PRECISION_F32_EXACT && mode != TS2D_PRECISION_F32_SPLIT_F16X3 && mode != TS2D_PRECISION_F16)
         return fail(TS2D_ERR_INVALID, "unknown precision mode %d", mode);
+    if (mode == TS2D_PRECISION_F16 && e->residual)      // (the 16-bit contract of a residual block - where the sum is rounded - is a definition of its own)
+        return fail(TS2D_ERR_INVALID, "TS2D_PRECISION_F16 is not supported on a residual-encoder engine (TS2D_PRECISION_F32_SPLIT_F16X3 and "
+                    "TS2D_PRECISION_F32_EXACT are); the mode is unchanged");
     e->precision = mode;
     return TS2D_OK;
 }
@@ -890,6 +947,7 @@ int ts2d_engine_check(ts2d_engine* e) {
             const size_t n = (size_t)B * (H >> t.ly) * (W >> t.lx) * t.C;
             const int f = has_nonfinite(t.data, n, e->last_f16);
             const int g = (f == 0 && t.normed) ? has_nonfinite(t.scale, (size_t)B * t.C, false) : 0;
+            // (a linear tensor - conv2 / projection of a residual block - and a join's sum are scanned as stored, like every other: no activation is applied here)
             if (f == 1 || g == 1) { where = "layer " + op.name + (f == 1 ? "" : " (InstanceNorm statistics)"); named = true; break; }
         }
     if (d_copy) {
@@ -1004,7 +1062,8 @@ int ts2d_engine_debug_tensor(ts2d_engine* e, const char* name, float* out, size_
         for (int p = 0; p < h * w; ++p)
             for (int c = 0; c < Cu; ++c) {
                 float v = raw[((size_t)b * h * w + p) * C + c];
-                if (t.normed) { v = v * sc[(size_t)b * C + c] + sh[(size_t)b * C + c]; v = v > 0.f ? v : v * e->arch.leaky_slope; }
+                if (t.linear) v = std::fmaf(sc[(size_t)b * C + c], v, sh[(size_t)b * C + c]);      // conv2 / projection of a residual block: normalised, not activated - the join's own fused form
+                else if (t.normed) { v = v * sc[(size_t)b * C + c] + sh[(size_t)b * C + c]; v = v > 0.f ? v : v * e->arch.leaky_slope; }
                 out[((size_t)b * Cu + c) * h * w + p] = v;
             }
     return TS2D_OK;

@@ -48,7 +48,9 @@ private:
 
 constexpr size_t kWsHeader = 256;         // bytes in front of the activation plan: [0] = token of the last run inside this memory
 
-enum OpType { OP_CONV = 0, OP_CONVT = 1, OP_HEAD = 2 };
+enum OpType { OP_CONV = 0, OP_CONVT = 1, OP_HEAD = 2,
+              OP_PROJ = 3,      // residual skip path: average pool over the block's stride + 1x1 conv (no bias) + statistics (kernels_resblock.h)
+              OP_JOIN = 4 };    // residual join: norm2(conv2) + residual, stored before the LeakyReLU with scale 1 / shift 0
 
 struct Tensor {            // an activation tensor of the program (NHWC fp32)
     std::string name;
@@ -56,6 +58,7 @@ struct Tensor {            // an activation tensor of the program (NHWC fp32)
     int Cu = 0;            // channels of the CALLER's architecture (C is the width the kernels run: rounded up to 32 - pad_arch)
     int ly = 0, lx = 0;    // log2 of the cumulative stride along H / W: extent (H >> ly, W >> lx) (per-axis strides, ABI 7)
     bool normed = false;   // raw conv output that carries InstanceNorm scale/shift
+    bool linear = false;   // normalised but never activated (conv2 and the projection of a residual block): only the join reads it
     float* data = nullptr; float* scale = nullptr; float* shift = nullptr;
     size_t bytes = 0;      // of its buffer in the workspace plan (0: none)
     bool resident = false; // its buffer still holds the values of the last run (no later tensor of the run was placed on it)
@@ -64,6 +67,7 @@ struct Tensor {            // an activation tensor of the program (NHWC fp32)
 struct Op {
     OpType type; std::string name;
     int src, skip, dst;           // tensor indices (skip = -1 if none)
+    int res = -1;                 // third source (-1 if none): the residual a join adds - the block's input, or its projection
     int cin, cin_skip, cout, stride, level;      // stride: 1 = (1, 1), 2 = (2, 2) - the dedicated kernels; 3 = anisotropic (generic kernel only)
     int sy = 1, sx = 1;           // stride along H / W (conv: of the conv; transposed conv: kernel = stride of the upsampling)
     int ly = 0, lx = 0;           // shifts of the op's level (= of its output tensor; the head: level 0)
@@ -104,7 +108,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 struct TileGeom { int TH, TW, NIMG, lgTH, lgTW, tiles_x, tiles_y, n_mtiles, PH, PW; };
 
 enum Kern { K_NONE = 0, K_FUSED_AWAY, K_FIRST, K_FIRST_STATS, K_EXACT, K_S1_GENERIC, K_S1_ONE, K_S1_QP, K_S1_H32, K_S1_H2, K_S1_RES32, K_S1_RES32F,
-            K_S2_V2, K_S2_ONE, K_S2_GENERIC, K_T_ONE, K_T_GENERIC, K_UP0, K_UPQ, K_UPC, K_UPC_H, K_UPC_H2, K_HEAD_MFMA, K_HEAD_1X1 };
+            K_S2_V2, K_S2_ONE, K_S2_GENERIC, K_T_ONE, K_T_GENERIC, K_UP0, K_UPQ, K_UPC, K_UPC_H, K_UPC_H2, K_HEAD_MFMA, K_HEAD_1X1, K_PROJ, K_JOIN };
 
 struct Choice {
     Kern k = K_NONE;
@@ -140,6 +144,8 @@ struct ts2d_engine {
     std::vector<ts2d::Op> ops;
     size_t blob_floats = 0;
     ts2d_arch_desc user_arch{};        // the descriptor the caller gave; `arch` is what the kernels run (pad_arch)
+    bool residual = false;             // ResidualEncoderUNet (ts2d_engine_create_residual): stem + BasicBlockD stages; n_conv_enc is ignored
+    int n_blocks[TS2D_MAX_STAGES] = {0};      // ... blocks per stage
     bool padded = false;
     size_t user_blob_floats = 0;       // floats of the caller's blob (== blob_floats unless padded)
     float* d_weights = nullptr; size_t weight_floats = 0;
@@ -203,7 +209,8 @@ namespace ts2d {
 
 // ---- program.cpp: the descriptor as a program of ops over tensors, and the device weight arena's layout
 ts2d_arch_desc pad_arch(const ts2d_arch_desc& a, bool& padded);
-void expand_blob(const ts2d_arch_desc& ua, const ts2d_arch_desc& pa, const float* ub, std::vector<float>& pb);
+// n_blocks: the blocks per stage of a residual encoder, or null for a plain one
+void expand_blob(const ts2d_arch_desc& ua, const ts2d_arch_desc& pa, const int* n_blocks, const float* ub, std::vector<float>& pb);
 int build_program(ts2d_engine* e);
 int tensor_index(ts2d_engine* e, const std::string& name);      // -1: no such tensor
 

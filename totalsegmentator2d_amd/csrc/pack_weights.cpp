@@ -251,6 +251,16 @@ void pack_weights(const ts2d_engine* e, const float* blob, float* out) {
     }
     for (const Op& op : e->ops) {
         const int ct = op.cin + op.cin_skip, co_n = op.cout;
+        if (op.type == OP_JOIN) continue;
+        if (op.type == OP_PROJ) {           // W[co][ci] -> [ci][co]; no bias
+            const float* w = blob + op.blob_w;
+            float* d = out + op.dev_w;
+            for (int co = 0; co < co_n; ++co)
+                for (int ci = 0; ci < ct; ++ci) d[(size_t)ci * co_n + co] = w[(size_t)co * ct + ci];
+            memcpy(out + op.dev_g, blob + op.blob_g, co_n * sizeof(float));
+            memcpy(out + op.dev_be, blob + op.blob_be, co_n * sizeof(float));
+            continue;
+        }
         if (op.type == OP_CONV) {           // W[co][ci][ky][kx] -> [chunk][tap][kk][co][8]
             const int ck = op.ck, kkn = ck / 8;
             const float* w = blob + op.blob_w;

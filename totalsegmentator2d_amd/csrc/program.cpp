@@ -1,4 +1,4 @@
-// The network descriptor as a program: tensors, ops in PlainConvUNet forward order, offsets into the caller's blob and into the device
+// The network descriptor as a program: tensors, ops in PlainConvUNet (or ResidualEncoderUNet) forward order, offsets into the caller's blob and into the device
 // weight arena (which packed weight images an op gets is decided here, by its channel counts).  Also the library's last-error slot.
 #include "engine_internal.h"
 
@@ -34,14 +34,29 @@ int add_tensor(ts2d_engine* e, const std::string& name, int C, int level, bool n
 
 // The parameter tensors of a descriptor in state-dict order, as (rows, columns of the first / second source, inner) blocks; vectors have inner 0.
 struct ParamSeg { int rows, ca, cb, inner; };
-std::vector<ParamSeg> param_segs(const ts2d_arch_desc& a) {
+// `ua`: the CALLER's descriptor - whether a residual block has a projection is a property of the caller's widths (40 and 48 channels both run
+// at 64, and the block still has its 1x1 conv); `n_blocks`: blocks per stage of a residual encoder, or null.
+std::vector<ParamSeg> param_segs(const ts2d_arch_desc& a, const ts2d_arch_desc& ua, const int* n_blocks) {
     std::vector<ParamSeg> v;
     auto stride_of = [&](int s, int ax) { const int y = a.strides[s][0], x = a.strides[s][1]; return (y == 0 && x == 0) ? (s ? 2 : 1) : (ax ? x : y); };
+    auto block3x3 = [&](int f, int cin) { v.push_back({f, cin, 0, 9}); v.push_back({f, 0, 0, 0}); v.push_back({f, 0, 0, 0}); v.push_back({f, 0, 0, 0}); };
     int cin = a.input_channels;
+    if (n_blocks) {       // stem; per stage and block conv1, conv2, then the projection (w, gamma, beta) where the widths differ
+        block3x3(a.features[0], cin);
+        cin = a.features[0];
+        for (int s = 0; s < a.n_stages; ++s)
+            for (int b = 0; b < n_blocks[s]; ++b) {
+                const int f = a.features[s];
+                const bool proj = b == 0 && s > 0 && ua.features[s - 1] != ua.features[s];
+                block3x3(f, cin); block3x3(f, f);
+                if (proj) { v.push_back({f, cin, 0, 1}); v.push_back({f, 0, 0, 0}); v.push_back({f, 0, 0, 0}); }
+                cin = f;
+            }
+    } else
     for (int s = 0; s < a.n_stages; ++s)
         for (int i = 0; i < a.n_conv_enc[s]; ++i) {
             const int f = a.features[s];
-            v.push_back({f, cin, 0, 9}); v.push_back({f, 0, 0, 0}); v.push_back({f, 0, 0, 0}); v.push_back({f, 0, 0, 0});
+            block3x3(f, cin);
             cin = f;
         }
     for (int j = 0; j < a.n_stages - 1; ++j) {
@@ -82,8 +97,8 @@ ts2d_arch_desc pad_arch(const ts2d_arch_desc& a, bool& padded) {
 
 // caller-layout blob -> the blob of the padded architecture (zeros in every added row / column; the second source of a decoder block's
 // first conv - the skip half of cat((up, skip), 1) - starts at the PADDED width of the first)
-void expand_blob(const ts2d_arch_desc& ua, const ts2d_arch_desc& pa, const float* ub, std::vector<float>& pb) {
-    const std::vector<ParamSeg> us = param_segs(ua), ps = param_segs(pa);
+void expand_blob(const ts2d_arch_desc& ua, const ts2d_arch_desc& pa, const int* n_blocks, const float* ub, std::vector<float>& pb) {
+    const std::vector<ParamSeg> us = param_segs(ua, ua, n_blocks), ps = param_segs(pa, ua, n_blocks);
     pb.assign(segs_floats(ps), 0.f);
     size_t uo = 0, po = 0;
     for (size_t k = 0; k < us.size(); ++k) {
@@ -103,7 +118,11 @@ void expand_blob(const ts2d_arch_desc& ua, const ts2d_arch_desc& pa, const float
     }
 }
 
-// Mirror of UNetArch.program() (totalsegmentator2d_amd/arch.py): PlainConvUNet forward order.
+// Mirror of UNetArch.program() (totalsegmentator2d_amd/arch.py): PlainConvUNet forward order, or - `e->residual` - ResidualEncoderUNet's:
+// stem, then per stage and block conv1 (3x3, the block's stride), conv2 (3x3, normalised, NOT activated), the projection of the skip path where
+// the widths differ (average pool over the stride + 1x1 conv without bias + norm, not activated) and the join.  The join stores
+// t = norm2(conv2) + residual BEFORE the block's LeakyReLU with scale 1 / shift 0: every consumer applies lrelu(1 * t + 0) = lrelu(t) as it
+// loads (exact in fp32), so no convolution kernel knows about residual blocks.
 int build_program(ts2d_engine* e) {
     const ts2d_arch_desc& a = e->arch;
     if (a.n_stages < 2 || a.n_stages > TS2D_MAX_STAGES) return fail(TS2D_ERR_INVALID, "n_stages %d out of range [2,%d]", a.n_stages, TS2D_MAX_STAGES);
@@ -111,7 +130,8 @@ int build_program(ts2d_engine* e) {
     if (a.num_classes > 256) return fail(TS2D_ERR_INVALID, "num_classes %d > 256 is not supported", a.num_classes);
     for (int s = 0; s < a.n_stages; ++s) {
         if (e->user_arch.features[s] < 1) return fail(TS2D_ERR_INVALID, "features[%d] = %d must be positive", s, e->user_arch.features[s]);
-        if (a.n_conv_enc[s] < 1) return fail(TS2D_ERR_INVALID, "n_conv_enc[%d] must be >= 1", s);
+        if (!e->residual && a.n_conv_enc[s] < 1) return fail(TS2D_ERR_INVALID, "n_conv_enc[%d] must be >= 1", s);
+        if (e->residual && e->n_blocks[s] < 1) return fail(TS2D_ERR_INVALID, "n_blocks[%d] must be >= 1", s);
         if (s < a.n_stages - 1 && a.n_conv_dec[s] < 1) return fail(TS2D_ERR_INVALID, "n_conv_dec[%d] must be >= 1", s);
     }
     if (a.features[0] != 32 && a.features[0] != 64) return fail(TS2D_ERR_INVALID, "features[0] = %d: the head kernel supports at most 64 channels", e->user_arch.features[0]);
@@ -131,6 +151,53 @@ int build_program(ts2d_engine* e) {
     int cur = add_tensor(e, "input", e->cin_pad, 0, false), cin = a.input_channels;
     std::vector<int> skips(a.n_stages);
     char nm[64];
+    if (e->residual) {
+        auto conv3x3 = [&](const char* name, int src, int ci, int f, int s, int sy, int sx, bool linear) {
+            Op op{}; op.type = OP_CONV; op.name = name; op.src = src; op.skip = -1;
+            op.cin = ci; op.cin_skip = 0; op.cout = f; op.level = s; op.ly = e->lvl_y[s]; op.lx = e->lvl_x[s];
+            op.sy = sy; op.sx = sx; op.stride = stride_code(sy, sx);
+            op.dst = add_tensor(e, name, f, s, true);
+            e->tensors[op.dst].linear = linear;
+            op.blob_w = bo; bo += (size_t)f * ci * 9; op.blob_b = bo; bo += f; op.blob_g = bo; bo += f; op.blob_be = bo; bo += f;
+            e->ops.push_back(op);
+            return op.dst;
+        };
+        cur = conv3x3("stem", cur, cin, a.features[0], 0, 1, 1, false);
+        cin = a.features[0];
+        for (int s = 0; s < a.n_stages; ++s) {
+            const int f = a.features[s];
+            for (int b = 0; b < e->n_blocks[s]; ++b) {
+                const bool first = b == 0 && s > 0;
+                const int sy = first ? st[s][0] : 1, sx = first ? st[s][1] : 1;
+                const bool proj = first && e->user_arch.features[s - 1] != e->user_arch.features[s];
+                snprintf(nm, sizeof(nm), "enc%d.b%d.c1", s, b);
+                const int c1 = conv3x3(nm, cur, cin, f, s, sy, sx, false);
+                snprintf(nm, sizeof(nm), "enc%d.b%d.c2", s, b);
+                const int c2 = conv3x3(nm, c1, f, f, s, 1, 1, true);
+                int res = cur;
+                if (proj) {
+                    snprintf(nm, sizeof(nm), "enc%d.b%d.proj", s, b);
+                    Op op{}; op.type = OP_PROJ; op.name = nm; op.src = cur; op.skip = -1;
+                    op.cin = cin; op.cin_skip = 0; op.cout = f; op.level = s; op.ly = e->lvl_y[s]; op.lx = e->lvl_x[s];
+                    op.sy = sy; op.sx = sx; op.stride = stride_code(sy, sx);
+                    op.dst = add_tensor(e, nm, f, s, true);
+                    e->tensors[op.dst].linear = true;
+                    op.blob_w = bo; bo += (size_t)f * cin; op.blob_g = bo; bo += f; op.blob_be = bo; bo += f;      // (no bias)
+                    e->ops.push_back(op);
+                    res = op.dst;
+                }
+                snprintf(nm, sizeof(nm), "enc%d.b%d", s, b);
+                Op jn{}; jn.type = OP_JOIN; jn.name = nm; jn.src = c2; jn.skip = -1; jn.res = res;
+                jn.cin = f; jn.cin_skip = 0; jn.cout = f; jn.level = s; jn.ly = e->lvl_y[s]; jn.lx = e->lvl_x[s];
+                jn.sy = proj ? 1 : sy; jn.sx = proj ? 1 : sx;      // the window the join itself pools over (a projection has pooled already)
+                jn.stride = stride_code(jn.sy, jn.sx);
+                jn.dst = add_tensor(e, nm, f, s, true);           // "normed": the kernel writes scale 1 / shift 0
+                e->ops.push_back(jn);
+                cur = jn.dst; cin = f;
+            }
+            skips[s] = cur;
+        }
+    } else
     for (int s = 0; s < a.n_stages; ++s) {
         const int f = a.features[s];
         for (int i = 0; i < a.n_conv_enc[s]; ++i) {
@@ -175,11 +242,18 @@ int build_program(ts2d_engine* e) {
         e->ops.push_back(hd);
     }
     e->blob_floats = bo;
-    e->user_blob_floats = e->padded ? segs_floats(param_segs(e->user_arch)) : bo;
+    e->user_blob_floats = e->padded ? segs_floats(param_segs(e->user_arch, e->user_arch, e->residual ? e->n_blocks : nullptr)) : bo;
     // device weight arena layout
     size_t wo = 0;
     for (Op& op : e->ops) {
         const int ct = op.cin + op.cin_skip;
+        if (op.type == OP_JOIN) continue;                                // (no parameters)
+        if (op.type == OP_PROJ) {                                        // W[co][ci] -> [ci][co] (pool_proj1x1 stages rows of it), gamma, beta; no bias
+            op.ck = 0; op.dev_w_floats = (size_t)ct * op.cout;
+            op.dev_w = wo; wo = align_up(wo + op.dev_w_floats, 64);
+            op.dev_g = wo; wo = align_up(wo + op.cout, 64); op.dev_be = wo; wo = align_up(wo + op.cout, 64);
+            continue;
+        }
         if (op.type == OP_CONV) {
             const int ctp = (op.src == 0) ? e->cin_pad : ct;             // first conv reads the zero-padded input
             op.ck = (op.stride != 1 || ctp % 16) ? 8 : 16;

@@ -23,7 +23,7 @@ def _desc(arch: UNetArch) -> _lib.ArchDesc:
     d.input_channels, d.num_classes, d.n_stages = arch.input_channels, arch.num_classes, arch.n_stages
     for i, f in enumerate(arch.features_per_stage):
         d.features[i] = int(f)
-    for i, c in enumerate(arch.n_conv_per_stage):
+    for i, c in enumerate(arch.n_conv_per_stage):       # (ignored by ts2d_engine_create_residual)
         d.n_conv_enc[i] = int(c)
     for i, c in enumerate(arch.n_conv_per_stage_decoder):
         d.n_conv_dec[i] = int(c)
@@ -31,6 +31,13 @@ def _desc(arch: UNetArch) -> _lib.ArchDesc:
     for i, st in enumerate(arch.strides):
         d.strides[i][0], d.strides[i][1] = int(st[0]), int(st[1])
     return d
+
+
+def _residual_desc(arch: UNetArch) -> _lib.ResidualDesc:
+    r = _lib.ResidualDesc()
+    for i, b in enumerate(arch.n_blocks_per_stage):
+        r.n_blocks[i] = int(b)
+    return r
 
 
 def _is_torch(x) -> bool:
@@ -57,11 +64,15 @@ class Engine:
         d = _desc(arch)
         if blob is not None:
             blob = np.ascontiguousarray(blob, dtype=np.float32)
-            _lib.check(self.lib.ts2d_engine_create(ctypes.byref(d), blob.ctypes.data, blob.size, self.device,
-                                                   ctypes.byref(self._h)), 'ts2d_engine_create')
+        ptr, n = (blob.ctypes.data, blob.size) if blob is not None else (None, 0)
+        if arch.encoder == 'residual':
+            if not hasattr(self.lib, 'ts2d_engine_create_residual'):
+                raise RuntimeError(f"{_lib.LIB_PATH} was built before ts2d_engine_create_residual: rebuild it to run a ResidualEncoderUNet")
+            r = _residual_desc(arch)
+            _lib.check(self.lib.ts2d_engine_create_residual(ctypes.byref(d), ctypes.byref(r), ptr, n, self.device, ctypes.byref(self._h)),
+                       'ts2d_engine_create_residual')
         else:
-            _lib.check(self.lib.ts2d_engine_create(ctypes.byref(d), None, 0, self.device, ctypes.byref(self._h)),
-                       'ts2d_engine_create')
+            _lib.check(self.lib.ts2d_engine_create(ctypes.byref(d), ptr, n, self.device, ctypes.byref(self._h)), 'ts2d_engine_create')
         for k, v in {**Engine.default_options, **(options or {})}.items():
             self.set_option(k, v)
 
@@ -99,7 +110,8 @@ class Engine:
 
     def set_precision(self, mode):
         """'exact' (fp32 MFMA), 'split' (fp16 hi/lo x3 MFMA, fp32-equivalent accuracy; the default) or 'f16' (fp16 storage,
-        one fp16 MFMA product, fp32 accumulate/statistics: BASELINE configs 3/5, outside the fp32 parity tolerance)."""
+        one fp16 MFMA product, fp32 accumulate/statistics: BASELINE configs 3/5, outside the fp32 parity tolerance).  A residual-encoder
+        engine refuses 'f16' (RuntimeError naming the mode) and keeps the mode it had."""
         m = {'exact': _lib.PRECISION_F32_EXACT, 'split': _lib.PRECISION_F32_SPLIT_F16X3, 'f16': _lib.PRECISION_F16}.get(mode, mode)
         _lib.check(self.lib.ts2d_engine_set_precision(self._h, int(m)), 'ts2d_engine_set_precision')
         self._ws_need.clear()
