@@ -556,6 +556,39 @@ int ts2d_planes_crop_zscore(ts2d_planes* p, int32_t box[4], float* stats, int* n
 int ts2d_planes_crop_normalize(ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask, int32_t box[4],
                                float* stats, int* status);
 
+/* A STACK on the handle: a 3-D volume that a 2-D plan takes slice by slice (run_case, prediction_worker.py:194-199, fed a volume - what
+ * `nnUNetv2_predict -c 2d` does with a CT).  Upload src [channels][slices][h][w] float32; the handle then holds channels x slices planes, and
+ * ts2d_planes_resample_cubic, ts2d_planes_extent, ts2d_planes_download and ts2d_planes_destroy treat every slice as a plane.  The two crop
+ * entries above refuse such a handle (TS2D_ERR_INVALID); ts2d_planes_crop_normalize_stack is its own.
+ * TS2D_ERR_INVALID, by name, before any device work: null pointers, channels or slices below 1, more than 65535 planes, an extent outside
+ * 1 ... 8192, more than 2^28 samples.  (A new symbol of ABI 9: nothing that existed changed.) */
+int ts2d_planes_create_stack(int device, const float* src, int channels, int slices, int h, int w, ts2d_planes** out);
+
+/* crop_to_nonzero and the normalisation of a stack (run_case on [C, Z, H, W] with Z > 1), in place on the handle:
+ *   box       {first slice, one past the last slice, first row, one past the last row, first column, one past the last column} of the voxels
+ *             that are non-zero in ANY channel (`!= 0` as numpy has it: a NaN is not zero, -0.0 is; a volume of zeros keeps its whole
+ *             extent) = preprocess.crop_box3_statement = crop_to_nonzero's box: the holes nnU-Net fills in the mask of a volume lie inside
+ *             the box of the unfilled one.  The volume is compacted to it, dense [channels][Z'][h'][w']: the handle then holds channels x Z'
+ *             planes of h' x w'.
+ *   schemes, params   per CHANNEL, as in ts2d_planes_crop_normalize.
+ *   use_mask  [channels]: must be zero for every TS2D_NORM_ZSCORE channel - the mask of a volume is hole-filled in 3-D, which stays on the
+ *             host; ignored for the other schemes, as nnU-Net ignores it.
+ *   stats     [channels][2], as in ts2d_planes_crop_normalize.
+ * Arithmetic contract = the statements of ts2d_planes_crop_normalize applied to each channel's WHOLE cropped volume, flattened in C order, which
+ * is what numpy reduces (normalize_channel copies the cropped view into a dense array): the z-score sums run over N = Z' h' w' samples, their
+ * chunks of 8192 crossing the slice boundaries, mean and variance fl32(f64(sum) / N) (numpy's, beyond 2^24 samples too); Rescale takes the
+ * minimum and maximum of the whole channel.  Each sample is then normalised by its CHANNEL's parameters.  The clip bounds kept for
+ * ts2d_planes_resample_cubic are the float32 minimum and maximum of each resulting SLICE: nnU-Net's resize clips every 2-D slice to its own.
+ *   status    0, or TS2D_PLANES_NONFINITE, TS2D_PLANES_RGB_RANGE, TS2D_PLANES_ZERO_SIGN with their meaning above: the volume is then cropped
+ *             but NOT a result the caller may use; it drops the handle and runs numpy.
+ * TS2D_ERR_INVALID, by name, before any device work and with nothing written: null pointers, a scheme outside TS2D_NORM_*, a masked z-score
+ * channel, a non-finite CT parameter.
+ * Device scratch of the call's own, freed on every path: 16 bytes per slice, 32 per channel, and per channel 4 bytes per 8192 samples of the
+ * uncropped volume + 640 (the chunk and leaf sums); the compaction holds the cropped copy beside the volume until it has been made.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+int ts2d_planes_crop_normalize_stack(ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask, int32_t box[6],
+                                     float* stats, int* status);
+
 /* The order-3 resample of run_case (prediction_worker.py:194-199, a case whose spacing is not the plan's) of every plane of the handle to
  * out_h x out_w, clipped to the bounds ts2d_planes_crop_zscore left: the arithmetic, the limits and the messages of ts2d_resample_cubic.
  * The handle's extent becomes out_h x out_w and its clip bounds are used up (TS2D_ERR_STATE without them). */

@@ -1,11 +1,13 @@
 // The input side of libts2d_engine.so, none of which needs an engine: coronal projection + z-score of a volume, the order-3 resample to the
-// plan spacing, and the ts2d_planes handle (crop box, every normalisation scheme of nnU-Net and resample of native 2-D inputs where they lie on the device).
+// plan spacing, and the ts2d_planes handle (crop box, every normalisation scheme of nnU-Net and resample of native 2-D inputs, and of the slice stacks
+// of a volume under a 2-D plan, where they lie on the device).
 // The host arithmetic behind them is prep_plan.cpp; every device buffer of a call is a DevMem, so HIP_TRY may return wherever it fails.
 #include "engine_internal.h"
 #include "kernels_project.h"
 #include "kernels_resample_in.h"
 #include "kernels_prep.h"
 #include "kernels_prep_schemes.h"
+#include "kernels_prep_stack.h"
 
 #include <algorithm>
 #include <cmath>
@@ -19,6 +21,7 @@ using namespace ts2d;
 struct ts2d_planes {
     int device = 0;
     int n = 0, h = 0, w = 0;
+    int z = 1;                  // slices per channel: 1, or those of a stack (ts2d_planes_create_stack), whose n = channels * z planes are its slices
     DevMem d;                   // float [n][h][w]
     DevMem d_lh;                // float [n][2]: float32 minimum and maximum of each plane, valid while has_bounds
     bool has_bounds = false;
@@ -110,6 +113,27 @@ int rsin_run(const RsInPlan& pl, char* d_scratch, const float* d_src, const floa
     hipLaunchKernelGGL(rsin_interp_clip, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, 0,
                        d_coef, n_planes, pl.Hp, pl.Wp, out_h, out_w, d_taps, d_lh, d_dst);
     HIP_TRY(hipGetLastError());
+    return TS2D_OK;
+}
+
+// Both create entries: n_planes planes of h x w, `slices` of them per channel, uploaded to a new handle.
+int planes_create(const char* entry, int device, const float* src, int n_planes, int slices, int h, int w, ts2d_planes** out) {
+    if (!src || !out) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
+    *out = nullptr;
+    if (n_planes < 1 || n_planes > kPrepMaxPlanes) return fail(TS2D_ERR_INVALID, "%s: %d planes outside 1 ... %d", entry, n_planes, kPrepMaxPlanes);
+    if (h < 1 || w < 1 || h > kRsInMaxExtent || w > kRsInMaxExtent)
+        return fail(TS2D_ERR_INVALID, "%s: extents %d x %d outside 1 ... %d", entry, h, w, kRsInMaxExtent);
+    if ((long long)n_planes * h * w > kPrepMaxSamples)
+        return fail(TS2D_ERR_INVALID, "%s: %d planes of %d x %d are more than one handle takes (2^28 samples)", entry, n_planes, h, w);
+    HIP_TRY(hipSetDevice(device));
+    const size_t bytes = (size_t)n_planes * h * w * sizeof(float);
+    DevMem d, d_lh;
+    HIP_TRY(d.alloc(bytes));
+    HIP_TRY(d_lh.alloc((size_t)n_planes * 2 * sizeof(float)));
+    HIP_TRY(hipMemcpy(d.as<float>(), src, bytes, hipMemcpyHostToDevice));
+    ts2d_planes* p = new ts2d_planes();
+    p->device = device; p->n = n_planes; p->z = slices; p->h = h; p->w = w; p->d = std::move(d); p->d_lh = std::move(d_lh);
+    *out = p;
     return TS2D_OK;
 }
 
@@ -228,28 +252,21 @@ int ts2d_resample_cubic(int device, const float* src, int n_planes, int in_h, in
 
 // ---------------------------------------------------------------------------------------------------------------- ts2d_planes
 int ts2d_planes_create(int device, const float* src, int n_planes, int h, int w, ts2d_planes** out) {
-    if (!src || !out) return fail(TS2D_ERR_INVALID, "ts2d_planes_create: null argument");
-    *out = nullptr;
-    if (n_planes < 1 || n_planes > kPrepMaxPlanes) return fail(TS2D_ERR_INVALID, "ts2d_planes_create: %d planes outside 1 ... %d", n_planes, kPrepMaxPlanes);
-    if (h < 1 || w < 1 || h > kRsInMaxExtent || w > kRsInMaxExtent)
-        return fail(TS2D_ERR_INVALID, "ts2d_planes_create: extents %d x %d outside 1 ... %d", h, w, kRsInMaxExtent);
-    if ((long long)n_planes * h * w > kPrepMaxSamples)
-        return fail(TS2D_ERR_INVALID, "ts2d_planes_create: %d planes of %d x %d are more than one handle takes (2^28 samples)", n_planes, h, w);
-    HIP_TRY(hipSetDevice(device));
-    const size_t bytes = (size_t)n_planes * h * w * sizeof(float);
-    DevMem d, d_lh;
-    HIP_TRY(d.alloc(bytes));
-    HIP_TRY(d_lh.alloc((size_t)n_planes * 2 * sizeof(float)));
-    HIP_TRY(hipMemcpy(d.as<float>(), src, bytes, hipMemcpyHostToDevice));
-    ts2d_planes* p = new ts2d_planes();
-    p->device = device; p->n = n_planes; p->h = h; p->w = w; p->d = std::move(d); p->d_lh = std::move(d_lh);
-    *out = p;
-    return TS2D_OK;
+    return planes_create("ts2d_planes_create", device, src, n_planes, 1, h, w, out);
+}
+
+int ts2d_planes_create_stack(int device, const float* src, int channels, int slices, int h, int w, ts2d_planes** out) {
+    const char* const entry = "ts2d_planes_create_stack";
+    if (out) *out = nullptr;
+    if (channels < 1 || slices < 1 || (long long)channels * slices > kPrepMaxPlanes)
+        return fail(TS2D_ERR_INVALID, "%s: %d channels of %d slices outside 1 ... %d planes", entry, channels, slices, kPrepMaxPlanes);
+    return planes_create(entry, device, src, channels * slices, slices, h, w, out);
 }
 
 int ts2d_planes_crop_zscore(ts2d_planes* p, int32_t box[4], float* stats, int* nonfinite) {
     if (!p || !box || !stats || !nonfinite) return fail(TS2D_ERR_INVALID, "ts2d_planes_crop_zscore: null argument");
     *nonfinite = 0;
+    if (p->z != 1) return fail(TS2D_ERR_INVALID, "ts2d_planes_crop_zscore: the handle is a stack of %d slices per channel (ts2d_planes_crop_normalize_stack crops and normalises one)", p->z);
     HIP_TRY(hipSetDevice(p->device));
     const int n = p->n;
     // scratch, sized for the uncropped extent: [box | min / max keys | mean, divisor | leaves of the partial chunk | chunk and leaf sums]
@@ -285,6 +302,7 @@ int ts2d_planes_crop_normalize(ts2d_planes* p, const int32_t* schemes, const flo
     const char* const entry = "ts2d_planes_crop_normalize";
     if (!p || !schemes || !params || !use_mask || !box || !stats || !status) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
     *status = 0;
+    if (p->z != 1) return fail(TS2D_ERR_INVALID, "%s: the handle is a stack of %d slices per channel (ts2d_planes_crop_normalize_stack crops and normalises one)", entry, p->z);
     const int n = p->n;
     bool any_plain = false, any_masked = false, any_rescale = false;
     for (int c = 0; c < n; ++c) {
@@ -383,6 +401,117 @@ int ts2d_planes_crop_normalize(ts2d_planes* p, const int32_t* schemes, const flo
     HIP_TRY(hipMemcpy(status, d_status, sizeof(int), hipMemcpyDeviceToHost));
     if (bad) *status |= TS2D_PLANES_NONFINITE;                     // (a quotient overflowed, or a plane that is not normalised holds a non-finite sample)
     if (*status) p->has_bounds = false;                            // (an RGB sample out of range: the planes are no result, nothing resamples them)
+    return TS2D_OK;
+}
+
+int ts2d_planes_crop_normalize_stack(ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask, int32_t box[6], float* stats,
+                                     int* status) {
+    const char* const entry = "ts2d_planes_crop_normalize_stack";
+    if (!p || !schemes || !params || !use_mask || !box || !stats || !status) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
+    *status = 0;
+    const int C = p->n / p->z;
+    bool any_zscore = false, any_rescale = false;
+    for (int c = 0; c < C; ++c) {
+        if (schemes[c] < TS2D_NORM_ZSCORE || schemes[c] > TS2D_NORM_NONE) return fail(TS2D_ERR_INVALID, "%s: channel %d has the unknown scheme %d", entry, c, (int)schemes[c]);
+        if (schemes[c] == TS2D_NORM_ZSCORE && use_mask[c])
+            return fail(TS2D_ERR_INVALID, "%s: channel %d is normalised inside the non-zero mask, which nnU-Net fills in 3-D for a volume: that stays on the host", entry, c);
+        if (schemes[c] == TS2D_NORM_CT)
+            for (int k = 0; k < 4; ++k)
+                if (!std::isfinite(params[4 * c + k]))
+                    return fail(TS2D_ERR_INVALID, "%s: channel %d has the non-finite CT parameter %g at [%d] (mean, divisor, lower bound, upper bound)", entry, c, (double)params[4 * c + k], k);
+        any_zscore |= schemes[c] == TS2D_NORM_ZSCORE; any_rescale |= schemes[c] == TS2D_NORM_RESCALE01;
+    }
+    HIP_TRY(hipSetDevice(p->device));
+    // scratch, sized for the uncropped extent: [box, -, status | min / max keys of every slice, of the result and of the input | mean, divisor |
+    //                                           scheme table | leaves of the partial chunk | chunk and leaf sums of every channel]
+    const int n0 = p->n;
+    const size_t per_channel = (size_t)((long long)p->z * p->h * p->w / kPrepChunk) + kPrepMaxTailLeaves;
+    const size_t o_keys = 256, o_norm = align_up(o_keys + (size_t)n0 * 4 * sizeof(int), 256), o_table = align_up(o_norm + (size_t)C * sizeof(PrepNorm), 256);
+    const size_t o_leaves = align_up(o_table + (size_t)C * sizeof(PrepScheme), 256), o_sums = align_up(o_leaves + kPrepMaxTailLeaves * sizeof(PrepLeaf), 256);
+    DevMem d;
+    HIP_TRY(d.alloc(o_sums + (size_t)C * per_channel * sizeof(float)));
+    int* d_box = d.as<int>(); int* d_status = d.as<int>(7 * sizeof(int));
+    int* d_keys = d.as<int>(o_keys);
+    PrepNorm* d_norm = d.as<PrepNorm>(o_norm); PrepScheme* d_table = d.as<PrepScheme>(o_table);
+    // 1. crop_to_nonzero's box over all channels and all three axes (the holes nnU-Net fills in the mask lie inside it: the box is that of the raw mask)
+    int hb[6] = {p->z, -1, p->h, -1, p->w, -1};
+    const int zero = 0;
+    HIP_TRY(hipMemcpy(d_box, hb, sizeof(hb), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_status, &zero, sizeof(int), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(prep_nonzero_box3, dim3((unsigned)(((long long)p->z * p->h * p->w + 255) / 256)), dim3(256), 0, 0, p->d.as<float>(), C, p->z, p->h, p->w, d_box);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(hb, d_box, sizeof(hb), hipMemcpyDeviceToHost));
+    if (hb[1] < 0) { hb[0] = 0; hb[1] = p->z - 1; hb[2] = 0; hb[3] = p->h - 1; hb[4] = 0; hb[5] = p->w - 1; }      // nothing but zeros: the whole extent stays
+    const int ext[3] = {p->z, p->h, p->w};
+    for (int a = 0; a < 3; ++a)
+        if (hb[2 * a] < 0 || hb[2 * a + 1] >= ext[a] || hb[2 * a] > hb[2 * a + 1])
+            return fail(TS2D_ERR_HIP, "%s: the device returned the box %d ... %d on axis %d of extent %d", entry, hb[2 * a], hb[2 * a + 1], a, ext[a]);
+    const int bz = hb[1] - hb[0] + 1, bh = hb[3] - hb[2] + 1, bw = hb[5] - hb[4] + 1;
+    // 2. compaction: the flattened index of the dense [C][bz][bh][bw] buffer is numpy's
+    if (bz != p->z || bh != p->h || bw != p->w) {
+        DevMem d_new;
+        HIP_TRY(d_new.alloc((size_t)C * bz * bh * bw * sizeof(float)));
+        hipLaunchKernelGGL(prep_compact_box3, dim3((unsigned)((bh * bw + 255) / 256), (unsigned)bz, (unsigned)C), dim3(256), 0, 0,
+                           p->d.as<const float>(), p->z, p->h, p->w, hb[0], hb[2], hb[4], bh, bw, d_new.as<float>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+        p->d = std::move(d_new); p->z = bz; p->h = bh; p->w = bw; p->n = C * bz;
+    }
+    p->has_bounds = false;
+    for (int a = 0; a < 3; ++a) { box[2 * a] = hb[2 * a]; box[2 * a + 1] = hb[2 * a + 1] + 1; }
+    const int n = p->n;
+    float* const x = p->d.as<float>();
+    const long long n_plane = (long long)bh * bw, N = n_plane * bz;
+    const dim3 grid_apply((unsigned)((n_plane + 256 * kPrepNormPerLane - 1) / (256 * kPrepNormPerLane)), (unsigned)n);
+    int* d_keys_in = d_keys + 2 * (size_t)n;
+    std::vector<int> keys((size_t)n * 4);
+    for (size_t i = 0; i < keys.size(); i += 2) { keys[i] = 0x7FFFFFFF; keys[i + 1] = (int)0x80000000; }
+    HIP_TRY(hipMemcpy(d_keys, keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice));
+    // 3. the parameters of every channel, over its WHOLE cropped volume: the z-score statistics of a run of N = bz bh bw samples (numpy's chunks
+    //    cross the slices), the minimum and maximum behind Rescale folded over the channel's slices, the caller's for CT
+    std::vector<PrepNorm> norm((size_t)C, PrepNorm{0.f, 1.f});
+    bool bad = false;
+    if (any_zscore) {
+        std::vector<uint8_t> want((size_t)C);
+        for (int c = 0; c < C; ++c) want[c] = schemes[c] == TS2D_NORM_ZSCORE;
+        TRY(planes_stats(entry, x, N, C, want.data(), d_norm, d.as<PrepLeaf>(o_leaves), d.as<float>(o_sums), norm.data(), stats, &bad));
+    }
+    if (any_rescale && !bad) {
+        hipLaunchKernelGGL(prep_apply_schemes_stack<false>, grid_apply, dim3(256), 0, 0, x, n_plane, bz, nullptr, d_keys_in, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(keys.data() + 2 * (size_t)n, d_keys_in, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    std::vector<PrepScheme> table((size_t)C);
+    for (int c = 0; c < C && !bad; ++c) {
+        PrepScheme& s = table[c];
+        s = PrepScheme{(int)schemes[c], 0, 0.f, 1.f, 0.f, 0.f};
+        if (s.id == kPrepZScore) { s.sub = norm[c].mean; s.div = norm[c].div; continue; }      // (stats: mean and std, written above)
+        if (s.id == kPrepCT) { s.sub = params[4 * c]; s.div = params[4 * c + 1]; s.lo = params[4 * c + 2]; s.hi = params[4 * c + 3]; }
+        if (s.id == kPrepRGB01) s.div = 255.f;
+        if (s.id == kPrepRescale01) {
+            int klo = 0x7FFFFFFF, khi = (int)0x80000000;
+            for (int k = 0; k < bz; ++k) {
+                const int* kk = keys.data() + 2 * (size_t)n + 2 * ((size_t)c * bz + k);
+                klo = std::min(klo, kk[0]); khi = std::max(khi, kk[1]);
+            }
+            const float mn = prep_unkey(klo), mx = prep_unkey(khi);
+            if (!std::isfinite(mn) || !std::isfinite(mx)) { bad = true; break; }
+            // numpy's min() of a volume that holds zeros of both signs and nothing below them returns either: not decided here
+            if (mn == 0.f && std::signbit(mn)) *status |= TS2D_PLANES_ZERO_SIGN;
+            s.sub = mn; s.div = prep_rescale_div(mn, mx);
+        }
+        stats[2 * c] = s.sub; stats[2 * c + 1] = s.div;
+    }
+    if (bad) *status |= TS2D_PLANES_NONFINITE;                     // a non-finite sample (or an overflowing sum)
+    if (*status) return TS2D_OK;                                   // nothing is normalised
+    // 4. normalise in place by the channel's row; the minimum and maximum of each resulting SLICE are the clip bounds of the resample
+    HIP_TRY(hipMemcpy(d_table, table.data(), table.size() * sizeof(PrepScheme), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(prep_apply_schemes_stack<true>, grid_apply, dim3(256), 0, 0, x, n_plane, bz, d_table, d_keys, d_status);
+    HIP_TRY(hipGetLastError());
+    TRY(planes_keep_bounds(p, d_keys, &keys, &bad));
+    HIP_TRY(hipMemcpy(status, d_status, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad) *status |= TS2D_PLANES_NONFINITE;                     // (a quotient overflowed, or a channel that is not normalised holds a non-finite sample)
+    if (*status) p->has_bounds = false;                            // (an RGB sample out of range: the slices are no result, nothing resamples them)
     return TS2D_OK;
 }
 

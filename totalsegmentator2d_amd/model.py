@@ -46,6 +46,8 @@ class HIPModel:
         self.device_input_resample = True   # order-3 resample of an off-spacing case's input on the device: the same float32 values as scipy, bit for bit (preprocess.resize_cubic_f64)
         self.device_input_normalize = True  # crop box, z-score (and that resample) of a native 2-D input on device-resident planes: the same float32 values as numpy, bit for bit (preprocess.zscore_f32_statement)
         self.device_input_normalize_schemes = True  # the same for every other nnU-Net scheme (masked z-score, CT, Rescale, RGB, none): the cases device_input_normalize leaves to numpy, the same bits (preprocess.*_f32_statement)
+        self.device_input_stack = True   # a stack [C, Z, H, W] under a 2-D plan: crop box over three axes, unmasked normalisation with the statistics of the whole volume (and the per-slice resample) on device-resident planes; numpy's bits (preprocess.crop_box3_statement and the *_f32_statement of the flattened channel)
+        self.device_stack = True         # ... and its decided map from the device, every slice one image of the convention's own entry (_run; needs that convention's switch too); the host route's bytes
         self._discover()
 
     # ------------------------------------------------------------------ configuration (reference wrapper.py:113-162)
@@ -152,7 +154,7 @@ class HIPModel:
         """Everything DefaultPreprocessor.run_case_npy reads besides the image itself: two sub-models with the same key preprocess identically."""
         cm, pm = p.configuration_manager, p.plans_manager
         dz = props.get('device_zscore')
-        return repr((props.get('device_resample'), props.get('device_normalize'), props.get('device_normalize_schemes')) + (list(getattr(pm, 'transpose_forward', [0, 1, 2])), list(cm.spacing), list(getattr(cm, 'normalization_schemes', None) or []),
+        return repr((props.get('device_resample'), props.get('device_normalize'), props.get('device_normalize_schemes'), props.get('device_normalize_stack')) + (list(getattr(pm, 'transpose_forward', [0, 1, 2])), list(cm.spacing), list(getattr(cm, 'normalization_schemes', None) or []),
                      list(getattr(cm, 'use_mask_for_norm', None) or []), sorted((p.dataset_json.get('channel_names') or {}).items()),
                      (getattr(pm, 'plans', None) or {}).get('foreground_intensity_properties_per_channel', {}),
                      None if dz is None else tuple(dz.get('order', ()))))
@@ -189,6 +191,8 @@ class HIPModel:
             props['device_normalize'] = self._normalize_device()  # a native 2-D input is cropped and z-scored on the device, on planes that stay there for the resample (preprocess.py)
         if self._input_device(getattr(self, 'device_input_normalize_schemes', False)) is not None:
             props['device_normalize_schemes'] = self._input_device(self.device_input_normalize_schemes)   # ... and normalised there by any other scheme of the plan
+        if self._input_device(getattr(self, 'device_input_stack', False)) is not None:
+            props['device_normalize_stack'] = self._input_device(self.device_input_stack)   # ... and a stack of slices under a 2-D plan is cropped and normalised there as a volume
         pre = p.configuration_manager.preprocessor_class(verbose=p.verbose)
         shared = getattr(ref, 'preprocess_cache', None)      # set by TS2D.predict: the sub-models of one case mostly share channels and plan
         if shared is None:
@@ -247,6 +251,23 @@ class HIPModel:
             out = list(out) if out is not None else [None] * len(group)
         else:
             out = [getattr(p, name)(d, out_shape=o, full_shape=f, box=b) for d, o, f, b in zip(datas, outs, fulls, boxes)]
+        rest = [i for i, o in enumerate(out) if o is None]
+        for i, lg in zip(rest, self._predict([datas[i] for i in rest], False, batched) if rest else []):
+            out[i] = lg
+        return out
+
+    def _predict_stacks(self, group, batched: bool):
+        """Stage 2 of :meth:`_run` for stacks (3-D volumes under a 2-D plan): per case the decided map of the predictor's stack method - the
+        extent before resampling goes with each case - or, where it answers None, the logits (:meth:`_predict`): the export then takes the host route."""
+        p = self._predictor
+        name = 'predict_stack_from_preprocessed_data'
+        datas = [t[3] for t in group]
+        outs = [tuple(t[4].get('shape_after_cropping_and_before_resampling', np.asarray(t[3]).shape[1:])) for t in group]
+        if batched:
+            out = getattr(p, name + '_batch')(datas, out_shapes=outs)
+            out = list(out) if out is not None else [None] * len(group)
+        else:
+            out = [getattr(p, name)(d, out_shape=o) for d, o in zip(datas, outs)]
         rest = [i for i, o in enumerate(out) if o is None]
         for i, lg in zip(rest, self._predict([datas[i] for i in rest], False, batched) if rest else []):
             out[i] = lg
@@ -324,12 +345,26 @@ class HIPModel:
                 return None
             tgt = tuple(t[4]['shape_after_cropping_and_before_resampling'])
             return tgt if (can_export or can_lm or can_prob) and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] == 1 else False
-        fast = [t for t in todo if (can_seg or can_lm or can_prob) and target(t) is not False and (not can_prob or np.asarray(t[3]).shape[1] == 1)]
-        for group, use_seg in ((fast, True), ([t for t in todo if not any(t is f for f in fast)], False)):
+        # a stack - a 3-D volume under a 2-D plan, more than one slice left after cropping - gets the decided map of its convention from the
+        # device too, every slice one image of the same entries (the predictor's stack methods); its slice count never changes.  Only a predictor
+        # that has the methods takes this route, and only with the convention's own switch on; probabilities of a stack keep the host route
+        st_fn = getattr(p, 'predict_stack_from_preprocessed_data' + ('_batch' if batched else ''), None)
+        can_stack = getattr(self, 'device_stack', False) and not save_probabilities and st_fn is not None \
+            and len(p.configuration_manager.patch_size) == 2 and bool(self.device_threshold if multilabel else getattr(self, switch, False))
+
+        def is_stack(t):
+            shape = tuple(np.asarray(t[3]).shape[1:])
+            tgt = tuple(t[4].get('shape_after_cropping_and_before_resampling', shape))
+            return can_stack and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] > 1
+        stacks = [t for t in todo if is_stack(t)]
+        fast = [t for t in todo if (can_seg or can_lm or can_prob) and not is_stack(t) and target(t) is not False and (not can_prob or np.asarray(t[3]).shape[1] == 1)]
+        for group, use_seg in ((stacks, True), (fast, True), ([t for t in todo if not any(t is f for f in fast + stacks)], False)):
             if not group:
                 continue
             try:
-                if use_seg and can_prob:
+                if group is stacks:
+                    out = self._predict_stacks(group, batched)
+                elif use_seg and can_prob:
                     out = self._predict_probabilities(group, batched)
                 else:
                     out = self._predict([t[3] for t in group], use_seg, batched, [target(t) for t in group] if use_seg else None,

@@ -464,6 +464,114 @@ class HIPnnUNetPredictor:
             return None
         return self._sliding_window_batch(datas, None if ensemble else 0, one_call=one_call, out_shapes=hws, probabilities=place, **self._probability_mode())
 
+    # ------------------------------------------------------------------ stacks: a 3-D volume through a 2-D model, slice by slice
+    stack_call_bytes = 1 << 30       # device bytes of inputs and outputs one engine call of the stack batch method may hold (see _stack_calls)
+
+    @staticmethod
+    def _stack_extent(out_shape, data):
+        """``out_shape`` of the stack methods, ``(Z, h, w)`` with the stack's own Z -> the in-plane ``(h, w)`` every slice is resampled to (None: the
+        slices' own), or False where it describes no such extent."""
+        if out_shape is None:
+            return tuple(int(v) for v in data.shape[2:])
+        s = tuple(int(v) for v in out_shape)
+        if len(s) != 3 or s[0] != data.shape[1] or min(s) < 1:
+            return False
+        return s[1:]
+
+    @staticmethod
+    def _stack_rects(datas, reverts, hws):
+        """One ``(src_y, src_x, src_h, src_w, out_h, out_w)`` per SLICE of every input, in image order: the rectangle of the padded prediction that
+        is the slice - the same for all slices of an input - and the extent it is resampled to."""
+        rects = []
+        for data, revert, hw in zip(datas, reverts, hws):
+            H, W = data.shape[2:]
+            rects += [(revert[2].start, revert[3].start, H, W, int(hw[0]), int(hw[1]))] * data.shape[1]
+        return rects
+
+    def _stack_calls(self, images, rects, multilabel: bool):
+        """The images of the stack batch method split into engine calls, in order, by a byte budget (``stack_call_bytes``) on what the header's
+        scratch formula sums over the images of a call: the inputs C x Hp x Wp x 4, the half outputs folds x K x Hp x Wp x 2, the export's outputs
+        out_h x out_w (x K for a multilabel model).  At least one image per call.  Where the calls split does not show in the bytes: inside a
+        full-batch call an image's result does not depend on its call-mates."""
+        K, F, budget = self.arch.num_classes, max(1, len(self.engines)), int(self.stack_call_bytes)
+        calls, used = [[]], 0
+        for j, (image, r) in enumerate(zip(images, rects)):
+            C, Hp, Wp = image.shape
+            need = C * Hp * Wp * 4 + F * K * Hp * Wp * 2 + r[4] * r[5] * (K if multilabel else 1)
+            if calls[-1] and used + need > budget:
+                calls.append([])
+                used = 0
+            calls[-1].append(j)
+            used += need
+        return calls
+
+    def _stack_window(self, datas, hws, full_batch: bool):
+        """Inputs [C,Z,H,W] -> the decided uint8 maps of every slice from the device, stacked per input: [1,Z,h,w] of a label-map or region-based
+        model, [K,Z,h,w] of a multilabel one.  Every slice is one image of the ensemble entries (ts2d_ensemble_predict_tiled_labelmap / _regions /
+        _export: one engine is the single-model case), with its input's tile list, rectangle and out extent.  ``full_batch`` False: one call per
+        slice with the size-dependent dispatch - the bytes of :meth:`predict_logits_from_preprocessed_data` + the host export; True: calls of
+        :meth:`_stack_calls` with the full-batch dispatch - the bytes of :meth:`predict_logits_from_preprocessed_data_batch` + the host export."""
+        from .engine import predict_tiled_export_ensemble, predict_tiled_labelmap_ensemble, predict_tiled_regions_ensemble
+        from .labels import label_convention
+        patch = tuple(self.configuration_manager.patch_size)
+        images, tiles, owner, reverts, _ = self._pad_and_tile(datas, patch, single_slice=False)
+        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
+            raise AssertionError('mirror_axes does not match the dimension of the input!')
+        g = sw.compute_gaussian(patch) if self.use_gaussian else None
+        axes = self.allowed_mirroring_axes if self.use_mirroring else None
+        rects = self._stack_rects(datas, reverts, hws)
+        multilabel = label_convention(self.dataset_json).kind == 'multilabel'
+        decision = {} if multilabel else self._decision()
+        planes, inf = [], []
+        for grp in (self._stack_calls(images, rects, multilabel) if full_batch else [[j] for j in range(len(images))]):
+            args = (self.engines, [images[j] for j in grp], patch, [tiles[j] for j in grp], [rects[j] for j in grp])
+            if multilabel:
+                planes += predict_tiled_export_ensemble(*args, axes, g, want_seg=True, full_batch=full_batch)[0]
+            elif 'regions' in decision:
+                planes += predict_tiled_regions_ensemble(*args, decision['regions'], axes, g, full_batch=full_batch)[0]
+            else:
+                planes += predict_tiled_labelmap_ensemble(*args, axes, g, full_batch=full_batch)[0]
+            inf += self.engines[0].last_tiled_inf_per_image
+        self._raise_on_inf(inf, owner, full_batch)
+        out, j = [], 0
+        for data in datas:
+            Z = data.shape[1]
+            out.append(np.stack(planes[j:j + Z], axis=1) if multilabel else np.stack(planes[j:j + Z])[None])
+            j += Z
+        return out
+
+    def _serves_stacks(self) -> bool:
+        """Can the device decide the maps?  One real engine per fold (the host doubles of the tests have none: they keep the logits route) and a 2-D plan."""
+        from .engine import Engine
+        return len(self.engines) == len(self.list_of_parameters) >= 1 and all(isinstance(e, Engine) for e in self.engines) \
+            and len(self.configuration_manager.patch_size) == 2
+
+    def predict_stack_from_preprocessed_data(self, data, out_shape=None):
+        """The decided map of a STACK [C,Z,H,W] - a 3-D volume that this 2-D model takes slice by slice - from the device, in the model's own
+        convention: uint8 [1,Z,h,w] of a label-map model (argmax) or a region-based one (painted regions), uint8 [K,Z,h,w] of a multilabel one
+        (thresholded heads).  ``out_shape``: the case's ``shape_after_cropping_and_before_resampling`` ``(Z, h, w)`` - Z the stack's own, (h, w) the
+        extent every slice is resampled back to (order 1) in front of the decision; None: the preprocessed geometry.  One engine call per slice with
+        the size-dependent dispatch, every fold of an ensemble in it: the bytes are those of :meth:`predict_logits_from_preprocessed_data` + the host
+        export.  None where the device cannot serve (a predictor without engines, a 3-D plan, a bad ``out_shape``): the caller keeps the logits."""
+        data = _to_numpy(data)
+        if not self._serves_stacks() or data.ndim != 4:
+            return None
+        hw = self._stack_extent(out_shape, data)
+        return None if hw is False else self._stack_window([data], [hw], full_batch=False)[0]
+
+    def predict_stack_from_preprocessed_data_batch(self, list_of_data, out_shapes=None):
+        """:meth:`predict_stack_from_preprocessed_data` for a list of inputs - stacks and single-slice cases may be mixed: the slices of all inputs packed
+        into engine calls with the full-batch dispatch, as many per call as ``stack_call_bytes`` allows, so that a stack's bytes depend neither on that
+        budget nor on its batch-mates; they are those of :meth:`predict_logits_from_preprocessed_data_batch` + the host export.  ``out_shapes``: one
+        ``out_shape`` (or None) per input.  None where the single-case method returns None for some input."""
+        datas = [_to_numpy(d) for d in list_of_data]
+        if not self._serves_stacks() or any(d.ndim != 4 for d in datas) or (out_shapes is not None and len(out_shapes) != len(datas)):
+            return None
+        if not datas:
+            return []
+        hws = [self._stack_extent(s, d) for s, d in zip(out_shapes if out_shapes is not None else [None] * len(datas), datas)]
+        return None if any(hw is False for hw in hws) else self._stack_window(datas, hws, full_batch=True)
+
     def predict_logits_from_preprocessed_data(self, data):
         """Fold ensemble (upstream: sum over ``list_of_parameters`` then ``/= n``).  Accepts numpy or torch [C,1,H,W];
         returns a torch CPU tensor (float16) when torch is importable so that the caller's ``.cpu()`` works."""

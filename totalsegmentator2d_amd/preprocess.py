@@ -316,7 +316,7 @@ def resample_planes_cubic_device(data: np.ndarray, new_hw, device: int) -> Optio
     c, z, h, w = data.shape
     oh, ow = int(new_hw[0]), int(new_hw[1])
     if isinstance(data, DevicePlanes):          # normalised on the device: resampled there, with the clip bounds it kept, and downloaded once
-        if min(h, w, oh, ow) < 2 or max(h, w, oh, ow) > CUBIC_MAX_EXTENT or c * (h + 2 * CUBIC_PAD) * (w + 2 * CUBIC_PAD) > 1 << 28 or c * oh * ow > 1 << 28:
+        if min(h, w, oh, ow) < 2 or max(h, w, oh, ow) > CUBIC_MAX_EXTENT or c * z * (h + 2 * CUBIC_PAD) * (w + 2 * CUBIC_PAD) > 1 << 28 or c * z * oh * ow > 1 << 28:
             return None
         return data.resample((oh, ow)).download()
     entry = cubic_device_entry()
@@ -360,6 +360,7 @@ def resample_data_to_shape(data: np.ndarray, new_shape, order: int = 3, device: 
 SUM_CHUNK = 8192             # numpy's default buffer size in elements (np.getbufsize()): the run add.reduce hands to its pairwise sum
 SUM_LEAF = 128               # numpy's PW_BLOCKSIZE: the longest run summed in eight strided accumulators
 PLANES_MAX_SAMPLES = 1 << 28  # samples one device handle takes (ts2d_planes_create)
+PLANES_MAX_PLANES = 65535     # ... and planes: the channels x slices of a stack (ts2d_planes_create_stack)
 
 
 def pairwise_leaves(n: int):
@@ -475,6 +476,21 @@ def crop_box_statement(data: np.ndarray):
     return [[0, 1], [int(rows[0]), int(rows[-1]) + 1], [int(cols[0]), int(cols[-1]) + 1]]
 
 
+def crop_box3_statement(data: np.ndarray):
+    """:func:`crop_to_nonzero`'s box for a stack ``[C, Z, H, W]``: ``[[z0, z1], [r0, r1], [c0, c1]]``, half open, over the voxels that are non-zero in
+    any channel (``!= 0``: a NaN counts, ``-0.0`` does not); an all-zero volume keeps its whole extent.  Upstream fills the holes of the mask before it
+    takes the box; a hole is enclosed by the mask, so the box of the filled mask is that of the raw one and no filling is needed for it
+    (tests/test_stack_cpu.py).  The device entry ts2d_planes_crop_normalize_stack returns ``(z0, z1, r0, r1, c0, c1)``."""
+    nz = (np.asarray(data) != 0).any(axis=0)
+    if nz.ndim != 3:
+        raise ValueError(f"crop_box3_statement: [C, Z, H, W] is needed, got {np.shape(data)}")
+    box = []
+    for ax in range(3):
+        idx = np.flatnonzero(nz.any(axis=tuple(i for i in range(3) if i != ax)))
+        box.append([int(idx[0]), int(idx[-1]) + 1] if len(idx) else [0, int(nz.shape[ax])])
+    return box
+
+
 # nnU-Net's default_normalization_schemes -> the TS2D_NORM_* of include/ts2d_engine.h, and the TS2D_PLANES_* status bits of ts2d_planes_crop_normalize
 NORM_SCHEME_IDS = {'ZScoreNormalization': 0, 'CTNormalization': 1, 'RescaleTo01Normalization': 2, 'RGBTo01Normalization': 3, 'NoNormalization': 4}
 PLANES_NONFINITE, PLANES_RGB_RANGE, PLANES_EMPTY_MASK, PLANES_ZERO_SIGN = 1, 2, 4, 8
@@ -565,24 +581,30 @@ def planes_device_entries():
 
 
 class DevicePlanes:
-    """The planes ``[C, 1, h, w]`` float32 of one native 2-D case on the device, behind a ``ts2d_planes`` handle: uploaded once here, cropped
+    """The planes ``[C, 1, h, w]`` float32 of one native 2-D case - with ``stack``, the slices ``[C, Z, h, w]`` of a volume that a 2-D plan takes slice
+    by slice (:meth:`crop_normalize_stack` is then the one crop entry) - on the device, behind a ``ts2d_planes`` handle: uploaded once here, cropped
     and normalised (:meth:`crop_zscore`, or :meth:`crop_normalize` for the other schemes) and resampled (:meth:`resample`) where they lie, downloaded once (:meth:`download`).  Every float32
     that comes back is the host route's, bit for bit (:func:`zscore_f32_statement` and the statements of the other schemes, :func:`resize_cubic_f64`).  A context manager;
     :meth:`close` destroys the handle and may be called twice."""
 
-    def __init__(self, data: np.ndarray, device: int, lib=None):
+    def __init__(self, data: np.ndarray, device: int, lib=None, stack: bool = False):
         import ctypes
         self._lib = lib if lib is not None else planes_device_entries()
         if self._lib is None:
             raise RuntimeError("DevicePlanes: the engine library has no ts2d_planes_* entries")
         data = np.asarray(data)
-        if data.ndim != 4 or data.shape[1] != 1 or data.dtype != np.float32:
+        if data.ndim != 4 or (data.shape[1] != 1 and not stack) or data.dtype != np.float32:
             raise ValueError(f"DevicePlanes: float32 [C, 1, H, W] is needed, got {data.dtype} {data.shape}")
         src = np.ascontiguousarray(data)
         self.device, self.channels = int(device), int(data.shape[0])
+        self.slices = int(data.shape[1])                    # 1, or the slices per channel of a stack (crop_normalize_stack may drop some)
         self.stats = None                                   # [C, 2] float32 (mean, std) after crop_zscore; what crop_normalize used per channel
         self.status = 0                                     # PLANES_* bits of the last crop_normalize
         self._h = ctypes.c_void_p()
+        if stack:
+            self._check(self._lib.ts2d_planes_create_stack(self.device, src.ctypes.data, self.channels, self.slices, int(data.shape[2]), int(data.shape[3]),
+                                                           ctypes.byref(self._h)), 'ts2d_planes_create_stack')
+            return
         self._check(self._lib.ts2d_planes_create(self.device, src.ctypes.data, self.channels, int(data.shape[2]), int(data.shape[3]),
                                                  ctypes.byref(self._h)), 'ts2d_planes_create')
 
@@ -596,7 +618,7 @@ class DevicePlanes:
         import ctypes
         h, w = ctypes.c_int(), ctypes.c_int()
         self._check(self._lib.ts2d_planes_extent(self._h, ctypes.byref(h), ctypes.byref(w)), 'ts2d_planes_extent')
-        return (self.channels, 1, h.value, w.value)
+        return (self.channels, self.slices, h.value, w.value)
 
     def crop_zscore(self):
         """crop_to_nonzero and the per-channel z-score on the device.  Returns the box ``[[0, 1], [r0, r1], [c0, c1]]`` the planes now span, or None
@@ -629,6 +651,26 @@ class DevicePlanes:
             return None
         self.stats = stats
         return [[0, 1], [int(box[0]), int(box[1])], [int(box[2]), int(box[3])]]
+
+    def crop_normalize_stack(self, schemes, use_mask, fip):
+        """:meth:`crop_normalize` for a stack (ts2d_planes_crop_normalize_stack): the box over all three axes, each channel normalised with the
+        parameters of its WHOLE cropped volume, no masked scheme.  Returns the box ``[[z0, z1], [r0, r1], [c0, c1]]`` the slices now span, or None with
+        the PLANES_* bits in ``self.status``."""
+        import ctypes
+        ids = np.array([NORM_SCHEME_IDS[s] for s in schemes[:self.channels]], np.int32)
+        params = np.zeros((self.channels, 4), np.float32)
+        for c in np.flatnonzero(ids == NORM_SCHEME_IDS['CTNormalization']):
+            params[c] = ct_f32_parameters(fip[str(c)])
+        masked = np.array([bool(c < len(use_mask) and use_mask[c]) for c in range(self.channels)], np.uint8)
+        box, status = (ctypes.c_int32 * 6)(), ctypes.c_int(0)
+        stats = np.zeros((self.channels, 2), np.float32)
+        self._check(self._lib.ts2d_planes_crop_normalize_stack(self._h, ids.ctypes.data, params.ctypes.data, masked.ctypes.data, ctypes.byref(box),
+                                                               stats.ctypes.data, ctypes.byref(status)), 'ts2d_planes_crop_normalize_stack')
+        self.status = int(status.value)
+        if self.status:
+            return None
+        self.stats, self.slices = stats, int(box[1]) - int(box[0])
+        return [[int(box[0]), int(box[1])], [int(box[2]), int(box[3])], [int(box[4]), int(box[5])]]
 
     def resample(self, hw):
         """Order-3 resample of every plane to ``hw`` on the device, clipped to the bounds :meth:`crop_zscore` left."""
@@ -677,6 +719,39 @@ def _device_normalize_applies(data, tf, schemes, use_mask, dz) -> bool:
             and planes_device_entries() is not None)
 
 
+def _ct_parameters_usable(schemes, fip, c) -> bool:
+    """Are the plan's intensity properties there for every CT channel of the first ``c``, as Python numbers that are finite in float32?"""
+    for i in range(c):
+        if schemes[i] == 'CTNormalization':
+            props = (fip or {}).get(str(i))
+            keys = ('mean', 'std', 'percentile_00_5', 'percentile_99_5')
+            if not props or not all(type(props.get(k)) in (int, float) for k in keys):
+                return False
+            try:
+                if not np.isfinite(ct_f32_parameters(props)).all():
+                    return False
+            except OverflowError:
+                return False
+    return True
+
+
+def _device_stack_applies(data, tf, schemes, use_mask, fip) -> bool:
+    """The cases ts2d_planes_crop_normalize_stack computes: a stack (more than one slice per channel) under the identity transpose, every scheme one of
+    nnU-Net's five and none of them masked (the mask of a volume is hole-filled in 3-D: that stays on the host), usable CT parameters, extents,
+    plane and sample counts inside the handle's limits (and above the size from which it pays), the two stack entries present."""
+    c, z, h, w = data.shape
+    if not (list(tf) == [0, 1, 2] and z > 1 and c >= 1 and len(schemes) >= c and all(s in NORM_SCHEME_IDS for s in schemes[:c])):
+        return False
+    if any(schemes[i] == 'ZScoreNormalization' and i < len(use_mask) and use_mask[i] for i in range(c)):
+        return False
+    if not _ct_parameters_usable(schemes, fip, c):
+        return False
+    lib = planes_device_entries()
+    return (1 <= min(h, w) and max(h, w) <= CUBIC_MAX_EXTENT and c * z <= PLANES_MAX_PLANES
+            and DEVICE_NORMALIZE_MIN_SAMPLES <= c * z * h * w <= PLANES_MAX_SAMPLES
+            and lib is not None and hasattr(lib, 'ts2d_planes_create_stack') and hasattr(lib, 'ts2d_planes_crop_normalize_stack'))
+
+
 def _device_schemes_apply(data, tf, schemes, use_mask, fip) -> bool:
     """The cases :func:`_device_normalize_applies` refuses for their schemes and ts2d_planes_crop_normalize computes: identity transpose, one slice
     per channel, every scheme one of nnU-Net's five and not all of them the plain z-score (that case belongs to the other predicate, its z-score
@@ -689,17 +764,8 @@ def _device_schemes_apply(data, tf, schemes, use_mask, fip) -> bool:
     masked = [bool(i < len(use_mask) and use_mask[i]) for i in range(c)]
     if all(s == 'ZScoreNormalization' for s in schemes[:c]) and not any(masked):
         return False
-    for i in range(c):
-        if schemes[i] == 'CTNormalization':
-            props = (fip or {}).get(str(i))
-            keys = ('mean', 'std', 'percentile_00_5', 'percentile_99_5')
-            if not props or not all(type(props.get(k)) in (int, float) for k in keys):
-                return False
-            try:
-                if not np.isfinite(ct_f32_parameters(props)).all():
-                    return False
-            except OverflowError:
-                return False
+    if not _ct_parameters_usable(schemes, fip, c):
+        return False
     lib = planes_device_entries()
     return (1 <= min(h, w) and max(h, w) <= CUBIC_MAX_EXTENT and DEVICE_NORMALIZE_MIN_SAMPLES <= c * h * w <= PLANES_MAX_SAMPLES
             and lib is not None and hasattr(lib, 'ts2d_planes_crop_normalize'))
@@ -731,6 +797,7 @@ class DefaultPreprocessor:
         device_resample = properties.pop('device_resample', None)     # GPU index for the order-3 resample below (HIPModel sets it), None: host
         device_normalize = properties.pop('device_normalize', None)   # GPU index for crop box + z-score (+ that resample) on device-resident planes
         device_schemes = properties.pop('device_normalize_schemes', None)   # the same for the cases that route refuses for their schemes: masked z-score, CT, Rescale, RGB, none
+        device_stack = properties.pop('device_normalize_stack', None)       # the same for a stack [C, Z, H, W], Z > 1, under a 2-D plan: box over three axes, statistics of the whole volume, no masked scheme
         target_spacing = list(configuration_manager.spacing)
         if len(target_spacing) < len(data.shape[1:]):
             target_spacing = [original_spacing[0]] + target_spacing
@@ -740,6 +807,16 @@ class DefaultPreprocessor:
             planes_device, plain = device_normalize, True
         elif device_schemes is not None and _device_schemes_apply(data, tf, schemes, use_mask, fip):
             planes_device, plain = device_schemes, False
+        if device_stack is not None and len(configuration_manager.spacing) == 2 and _device_stack_applies(data, tf, schemes, use_mask, fip):
+            with DevicePlanes(data, device_stack, stack=True) as planes:
+                bbox = planes.crop_normalize_stack(schemes, use_mask, fip)
+                if bbox is not None:            # (None: a status bit - numpy below computes, or raises, what numpy does)
+                    properties['bbox_used_for_cropping'] = bbox
+                    shape = properties['shape_after_cropping_and_before_resampling'] = planes.shape[1:]
+                    new_shape = [int(round(i / j * k)) for i, j, k in zip(original_spacing, target_spacing, shape)]
+                    if list(new_shape) != list(shape):
+                        return resample_data_to_shape(planes, new_shape, order=3, device=device_resample), None, properties
+                    return planes.download(), None, properties
         if planes_device is not None:
             with DevicePlanes(data, planes_device) as planes:
                 bbox = planes.crop_zscore() if plain else planes.crop_normalize(schemes, use_mask, fip)
