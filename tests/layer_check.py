@@ -4,7 +4,17 @@ front of it or behind it.  The engine must have run its forward with ``keep_acti
 
 Split / exact mode: the reference block is evaluated in float64 (``layer_forward(dtype=torch.float64)``), so its own rounding is no
 part of the bound; the engine's inputs are fp32 values and enter the reference exactly.  16-bit mode: the 16-bit oracle block in its
-storage view and the bounds of tests/test_gpu_parity.py (``_f16_layer_ok``)."""
+storage view and the bounds of tests/test_gpu_parity.py (``_f16_layer_ok``).
+
+Residual encoders (``arch.encoder == 'residual'``, split / exact mode only): the graph comes from the ``src`` / ``skip`` / ``res`` / ``key`` /
+``linear`` fields of ``arch.program()``, the float64 blocks from tests/resenc_util.py (``conv_norm``: stem, ``.c1``, ``.c2`` with slope 1;
+``pool_proj``: ``.proj``).  A join is judged by a derived rule (:func:`join_reference`).  The other blocks of such a net - ``.c2`` and
+``.proj`` are normalised but not activated - are judged under ``max(SPLIT_LAYER_TOL, 2 E_op)``, ``E_op`` = the error of the float32 torch
+block against the float64 block on the same inputs (:func:`reference_error`): the reference sets the bound, the engine never does.  ``E_op``
+stays at or below 3.5e-6 for every conv block of the cases of tests/resenc_util.py, so SPLIT_LAYER_TOL is their bound.  The second term is
+the active one in ONE place: ``enc4.b0.proj`` of ``res_deep`` (a 256 -> 512 projection over 8 x 8 pixels whose un-activated outputs reach 40:
+E_op 4.9e-6 on one host, 5.6e-6 ... 6.4e-6 on another - torch's summation order follows the thread count - so the bound there is up to 1.3e-5;
+the engine measures 5.6e-6 ... 6.6e-6).  The plain-net paths are untouched."""
 from __future__ import annotations
 
 import numpy as np
@@ -22,9 +32,83 @@ F16_UP_RTOL = 2e-3
 HEAD_RTOL = {'split': 1e-6, 'exact': 1e-6, 'f16': 1.5e-3}          # (worst 3.0e-7 split, 2.9e-7 exact, 4.5e-4 16-bit mode)
 
 
+OP_CONV3X3, OP_CONVT2X2, OP_HEAD1X1, OP_PROJ1X1, OP_JOIN = 0, 1, 2, 3, 4          # totalsegmentator2d_amd/arch.py (asserted in _program)
+JOIN_UNITS = 4           # a join: |out - lrelu(c2 + r)| <= JOIN_UNITS * 2^-23 * max(1, |c2|, |r|) element-wise (:func:`join_reference`)
+
+
+def _residual(arch):
+    return getattr(arch, 'encoder', 'plain') == 'residual'
+
+
+_programs = {}
+
+
+def _program(arch):
+    """{op name: op} of ``arch.program()``, made once per arch."""
+    key = repr(arch)
+    if key not in _programs:
+        from totalsegmentator2d_amd import arch as A
+        assert (A.OP_CONV3X3, A.OP_CONVT2X2, A.OP_HEAD1X1, A.OP_PROJ1X1, A.OP_JOIN) == (OP_CONV3X3, OP_CONVT2X2, OP_HEAD1X1, OP_PROJ1X1, OP_JOIN)
+        _programs[key] = {o['name']: o for o in arch.program()}
+    return _programs[key]
+
+
+def _res_sources(arch, name):
+    """:func:`op_sources` of a residual net, from the program's fields: (src,) for stem / ``.c1`` / ``.c2`` / ``.proj`` / ``.up`` / head,
+    (conv2, what the join adds) for a join ``encS.bB``, (coarse, skip) for ``decL.c0`` - the skip is the last JOIN of level L."""
+    prog = _program(arch)
+    o = prog[name]
+    if o['op'] == OP_JOIN:
+        return (o['src'], o['res'])
+    if o['skip'] is not None:
+        up = prog[o['src']]
+        assert up['op'] == OP_CONVT2X2, (name, up['name'])
+        return (up['src'], o['skip'])
+    return (o['src'],)
+
+
+def join_reference(arch, c2, res, pool):
+    """(want, bound) of a join, float64, from the values the accessor shows: ``lrelu(c2 + r)``; r = `res` itself (the projection, or the
+    block's input) or - `pool` != (1, 1) - ATen's float32 average of `res` over the window.  Element-wise bound
+    ``JOIN_UNITS * 2^-23 * max(1, |c2|, |r|)``: one unit for each input's accessor rounding against the kernel's fused form, one for the
+    sum, one for the slope product - derived, not measured."""
+    import torch
+    c2 = np.asarray(c2, np.float32)
+    r = np.asarray(res, np.float32)
+    if tuple(pool) != (1, 1):
+        r = torch.nn.functional.avg_pool2d(torch.from_numpy(np.ascontiguousarray(r)), tuple(pool), tuple(pool)).numpy()
+    r = r.astype(np.float64)
+    t = c2.astype(np.float64) + r
+    want = np.where(t > 0, t, t * np.float64(np.float32(arch.leaky_slope)))
+    return want, JOIN_UNITS * 2.0 ** -23 * np.maximum(1.0, np.maximum(np.abs(c2), np.abs(r)))
+
+
+def _res_block(arch, sd, name, srcs, dtype):
+    """Block `name` of a residual net from `srcs` in `dtype` (None: torch's float32), as a tensor; None for the ops whose reference has one
+    form only (join, transposed conv, head)."""
+    from oracle import torch_oracle as O
+    from tests import resenc_util as R
+    o = _program(arch)[name]
+    if o['op'] == OP_PROJ1X1:
+        return R.pool_proj(sd, o['key'], srcs[0], o['stride'], arch.norm_eps, dtype)
+    if o['op'] != OP_CONV3X3:
+        return None
+    if o['key'].startswith('decoder.'):                            # the decoder is the plain net's: the oracle's own block
+        return O.layer_forward(arch, sd, name, srcs[0], srcs[1] if len(srcs) > 1 else None, dtype=dtype)
+    return R.conv_norm(sd, o['key'], srcs[0], tuple(o['stride']), arch.norm_eps, 1.0 if o['linear'] else arch.leaky_slope, dtype)
+
+
+def reference_error(arch, sd, name, srcs, want):
+    """``E_op`` of a normalised block of a residual net: max |float32 torch block - `want`| on the same inputs (None: the op has no such term)."""
+    got = _res_block(arch, sd, name, srcs, None)
+    return None if got is None else float(np.abs(got.numpy().astype(np.float64) - want).max())
+
+
 def op_sources(arch, name):
     """Names of the tensors block `name` reads: (src,) for a plain block, (coarse, skip) for ``decL.c0``, (coarse,) for ``decL.up``;
-    ``'input'`` (the network input) for ``enc0.c0``; the last block of level 0 for ``head``."""
+    ``'input'`` (the network input) for ``enc0.c0``; the last block of level 0 for ``head``.  Residual nets: :func:`_res_sources`."""
+    if _residual(arch):
+        return _res_sources(arch, name)
     if name == 'head':
         return (f'dec0.c{arch.n_conv_per_stage_decoder[-1] - 1}',)
     if name == 'enc0.c0':
@@ -52,6 +136,14 @@ def reference_block(arch, sd, name, srcs, mode, from_input=False):
     import torch
     from oracle import torch_oracle as O
     f16 = mode == 'f16'
+    if _residual(arch):
+        assert not f16 and not from_input, (name, mode)                     # (the 16-bit mode is refused for such nets; no fused first block)
+        o = _program(arch)[name]
+        if o['op'] == OP_JOIN:
+            return join_reference(arch, srcs[0], srcs[1], o['stride'])[0]
+        y = _res_block(arch, sd, name, srcs, torch.float64)
+        if y is not None:
+            return y.numpy()
     if from_input:
         assert name == 'enc0.c1' and not f16, (name, mode)
         t = {k: O._t(v).double() for k, v in sd.items() if k.startswith('encoder.stages.0.0.convs.')}
@@ -92,18 +184,25 @@ def _capacity(e, arch, n, x):
     """Floats of tensor `n` for the batch of `x` (0 without `x`: the accessor's default capacity serves)."""
     if x is None:
         return 0
-    lvl = int(n[3:n.index('.')])
+    lvl = _program(arch)[n]['level'] if _residual(arch) else int(n[3:n.index('.')])
     h, w = arch.extent(lvl, x.shape[2], x.shape[3])
     return x.shape[0] * arch.features_per_stage[lvl] * h * w
 
 
-def layer_error(name, got, want, mode):
-    """(ok, worst, text): the comparison of one block under the bound of its mode."""
+def layer_error(name, got, want, mode, bound=None, e_op=None):
+    """(ok, worst, text): the comparison of one block under the bound of its mode.  Residual nets: `bound` - the element-wise bound of a
+    join (worst: in units of it); `e_op` - ``E_op`` of a normalised block, judged under ``max(SPLIT_LAYER_TOL, 2 E_op)``."""
     got = np.asarray(got, np.float64)
-    d = got - want
-    mx, rms = float(np.abs(d).max()), float(np.sqrt((d ** 2).mean()))
     if got.shape != want.shape or not np.isfinite(got).all():
         return False, float('inf'), f'{name}: shape {got.shape} vs {want.shape}, finite {bool(np.isfinite(got).all())}'
+    d = got - want
+    mx, rms = float(np.abs(d).max()), float(np.sqrt((d ** 2).mean()))
+    if bound is not None:
+        ratio = float((np.abs(d) / bound).max())
+        return ratio <= 1.0, ratio, f'{name}: join {ratio:.3f} of its bound (max {mx:.3e})'
+    if e_op is not None:
+        tol = max(SPLIT_LAYER_TOL, 2 * e_op)
+        return mx <= tol, mx, f'{name}: max {mx:.3e} rms {rms:.3e} (E_op {e_op:.2e}, bound {tol:.1e})'
     if name.endswith('.up') or name == 'head':
         rel = mx / max(float(np.abs(want).max()), 1e-30)
         tol = HEAD_RTOL[mode] if name == 'head' else (F16_UP_RTOL if mode == 'f16' else SPLIT_UP_RTOL)
@@ -114,14 +213,24 @@ def layer_error(name, got, want, mode):
     return mx <= SPLIT_LAYER_TOL, mx, f'{name}: max {mx:.3e} rms {rms:.3e}'
 
 
-def check_layers(e, arch, sd, mode, names, rows=None, x=None, logits=None, exempt=(), memo=None):
+def _res_terms(arch, sd, name, srcs, want):
+    """(bound, e_op) of :func:`layer_error` for op `name` of a residual net."""
+    o = _program(arch)[name]
+    if o['op'] == OP_JOIN:
+        return join_reference(arch, srcs[0], srcs[1], o['stride'])[1], None
+    return None, reference_error(arch, sd, name, srcs, want)
+
+
+def check_layers(e, arch, sd, mode, names, rows=None, x=None, logits=None, exempt=(), memo=None, e_ops=None):
     """Every block in `names` of the engine's last forward against the oracle block on the engine's own inputs.  `rows`: batch rows to
     compare (default all).  `x`, `logits`: the input and the logits of that forward (all rows), needed for ``enc0.c0`` / ``head``; a
     first block that was not materialised is judged through ``enc0.c1`` from `x` (:func:`reference_block`, ``from_input``).  `exempt`:
     names whose value is measured and returned but not asserted.  `memo`: a dict that keeps reference blocks by the bytes of their inputs
     (forwards that differ in one kernel share every block in front of it).  Asserts the bound of `mode`; returns {name: worst value} (absolute;
-    relative for ``.up`` and ``head``)."""
+    relative for ``.up`` and ``head``; a join of a residual net: in units of its bound).  `e_ops`: a dict that receives {name: E_op} of the
+    normalised blocks of a residual net."""
     cache, worst, bad = {}, {}, []
+    res = _residual(arch)
     fused_first = None
 
     def tensor(n):
@@ -143,10 +252,18 @@ def check_layers(e, arch, sd, mode, names, rows=None, x=None, logits=None, exemp
         key = None if memo is None else (id(sd), name, mode, from_input) + tuple(_digest(t) for t in ins)
         if key is None or key not in memo:
             want = reference_block(arch, sd, name, ins, mode, from_input=from_input)
+            if res:
+                want = (want,) + _res_terms(arch, sd, name, ins, want)
             if key is not None:
                 memo[key] = want
         want = want if key is None else memo[key]
-        ok, w, text = layer_error(name, tensor(name), want, mode)
+        if res:
+            want, bound, e_op = want
+            if e_ops is not None and e_op is not None:
+                e_ops[name] = e_op
+            ok, w, text = layer_error(name, tensor(name), want, mode, bound=bound, e_op=e_op)
+        else:
+            ok, w, text = layer_error(name, tensor(name), want, mode)
         ok = ok or name in exempt
         worst[name] = w
         if not ok:

@@ -50,12 +50,20 @@ RES_CASES = {
     'res_pad': (resunet((24, 40, 72), (1, 2, 1), 26, cin=1), 1, 48, 80, 36),
     # K = 256 -> 512 projection; the 16 x 32-tile and the composed kernels read join outputs
     'res_deep': (resunet((32, 64, 128, 256, 512), (1, 2, 2, 2, 2), 18, nconv_dec=1), 2, 128, 128, 37),
+    # projection tiles that span images: level 1 is 8 x 24 = 192 pixels (M = 576: 4.5 tiles of 128 rows, the image seams inside tiles, a partial
+    # last tile, 64 columns, pooled), level 2 is 4 x 12 = 48 pixels (M = 144: two tiles, 32 columns); statistics by stats_direct
+    'res_span': (resunet((32, 64, 96), (1, 1, 1), 4), 3, 16, 48, 41),
+    # per-axis windows at B = 3: a pool-only join behind a (1, 2) window, a projection behind a (2, 1) window, a pool-only (2, 2) join
+    'res_win12': (resunet((32, 32, 64, 64), (1, 1, 1, 1), 5, strides=((1, 1), (1, 2), (2, 1), (2, 2))), 3, 32, 64, 42),
+    # ... the other way round at B = 2: pool-only (2, 1), a projection behind (1, 2), identity joins inside a (2, 1) stage
+    'res_win21': (resunet((32, 32, 64, 64), (1, 2, 1, 1), 5, strides=((1, 1), (2, 1), (1, 2), (2, 2))), 2, 32, 64, 43),
 }
 
 
-def case_input(name):
-    arch, B, H, W, seed = RES_CASES[name]
-    return cases.make_input(arch, B, H, W, seed)
+def case_input(name, B=None):
+    """The input of a case; `B`: at another batch size (the same PRNG stream, so that the first rows agree)."""
+    arch, B0, H, W, seed = RES_CASES[name]
+    return cases.make_input(arch, B0 if B is None else B, H, W, seed)
 
 
 def block_keys(s, b):
@@ -71,6 +79,33 @@ def skip_layout(arch, s, b):
     return stride, pool, proj
 
 
+def conv_norm(sd, key, x, stride, eps, slope, dtype=None):
+    """``ConvDropoutNormReLU`` under state-dict prefix `key` from its (activated) input: Conv 3x3 (stride) + bias -> InstanceNorm ->
+    LeakyReLU(slope); slope 1.0: no non-linearity (a LeakyReLU of slope 1 is the identity, bit for bit).  ``dtype=torch.float64``: every
+    operation in double precision."""
+    import torch
+    from oracle import torch_oracle as O
+    t = lambda k: O._t(sd[k]) if dtype is None else O._t(sd[k]).to(dtype)
+    x = O._t(x) if dtype is None else O._t(x).to(dtype)
+    with torch.no_grad():
+        return O.conv_block(x, t(f'{key}.conv.weight'), t(f'{key}.conv.bias'), t(f'{key}.norm.weight'), t(f'{key}.norm.bias'), stride, eps, slope)
+
+
+def pool_proj(sd, key, x, pool, eps, dtype=None):
+    """The skip path where the widths differ, from the block's (activated) input: ``AvgPool2d(pool)`` (None or (1, 1): no pool) -> Conv 1x1
+    without bias under prefix `key` -> InstanceNorm, no non-linearity."""
+    import torch
+    import torch.nn.functional as F
+    from oracle import torch_oracle as O
+    t = lambda k: O._t(sd[k]) if dtype is None else O._t(sd[k]).to(dtype)
+    r = O._t(x) if dtype is None else O._t(x).to(dtype)
+    with torch.no_grad():
+        if pool and tuple(pool) != (1, 1):
+            r = F.avg_pool2d(r, tuple(pool), tuple(pool))
+        p = F.conv2d(r, t(f'{key}.conv.weight'))
+        return F.instance_norm(p, None, None, t(f'{key}.norm.weight'), t(f'{key}.norm.bias'), use_input_stats=True, momentum=0.1, eps=eps)
+
+
 def block_forward(arch, sd, s, b, x, dtype=None):
     """One BasicBlockD from its (activated) input: dict with c1 (activated), c2 and proj (normalised, not activated; proj None without a
     projection), r (what the join adds) and out.  ``dtype=torch.float64``: every operation in double precision."""
@@ -79,22 +114,17 @@ def block_forward(arch, sd, s, b, x, dtype=None):
     from oracle import torch_oracle as O
     k = block_keys(s, b)
     stride, pool, proj = skip_layout(arch, s, b)
-    t = lambda key: O._t(sd[key]) if dtype is None else O._t(sd[key]).to(dtype)
     x = O._t(x) if dtype is None else O._t(x).to(dtype)
     eps, slope = arch.norm_eps, arch.leaky_slope
     with torch.no_grad():
-        c1 = O.conv_block(x, t(f'{k}.conv1.conv.weight'), t(f'{k}.conv1.conv.bias'), t(f'{k}.conv1.norm.weight'), t(f'{k}.conv1.norm.bias'),
-                          stride, eps, slope)
-        # (no non-linearity: a LeakyReLU of slope 1 is the identity, bit for bit)
-        c2 = O.conv_block(c1, t(f'{k}.conv2.conv.weight'), t(f'{k}.conv2.conv.bias'), t(f'{k}.conv2.norm.weight'), t(f'{k}.conv2.norm.bias'),
-                          1, eps, 1.0)
+        c1 = conv_norm(sd, f'{k}.conv1', x, stride, eps, slope, dtype)
+        c2 = conv_norm(sd, f'{k}.conv2', c1, 1, eps, 1.0, dtype)
         r = x
         if pool:
             r = F.avg_pool2d(r, pool, pool)
         p = None
         if proj:
-            p = F.conv2d(r, t(f'{proj}.conv.weight'))
-            p = F.instance_norm(p, None, None, t(f'{proj}.norm.weight'), t(f'{proj}.norm.bias'), use_input_stats=True, momentum=0.1, eps=eps)
+            p = pool_proj(sd, proj, x, pool, eps, dtype)
             r = p
         out = F.leaky_relu(c2 + r, slope)
     return dict(c1=c1, c2=c2, proj=p, r=r, out=out)
