@@ -117,7 +117,8 @@ int ts2d_engine_set_precision(ts2d_engine* e, int mode);
  * never changes results beyond fp32 summation order (every switch has a parity test on each of its sides).  Names (value 0 / 1 unless noted):
  *   "upc" composed decoder entry | "up0" dedicated level-0 composed kernel | "u0seg" (int) its tiles per workgroup segment, 0 = automatic | "q" persistent 16x32-tile stride-1 kernel |
  *   "one" one-image-tile kernels | "res" resident-weight 32 -> 32 kernel | "fuse0" first block recomputed inside the second |
- *   "s2v2" 512-thread stride-2 kernel | "h2", "uh2", "s2k32": the 16-bit mode's variants | "flex" the composed decoder
+ *   "s2v2" 512-thread stride-2 kernel | "s2p" its pipelined split-mode instance at 128 output columns (two patch buffers, weights from L2;
+ *   0: the single-buffered instance, bit-identical - test scaffolding) | "h2", "uh2", "s2k32": the 16-bit mode's variants | "flex" the composed decoder
  *   entry on tiles that follow the level's extent where it is no multiple of 8 x 32 pixels (0: transposed conv + conv there) |
  *   "flex2" (int) the 512-thread stride-2 kernel on tiles that divide such a level (0: off, 1: 16-bit mode only, 2: every mode) |
  *   "first_split" the first block's K = 9 C contraction as one fp16 hi / lo split product (0: exact fp32 MFMA) |

@@ -198,6 +198,9 @@ void s2v2_variant(const ts2d_engine* e, const Op& op, Choice& c) {
     // 16-bit mode: chunks of 32 channels (the second part of the LDS images = channels 16-31 instead of the split mode's lo parts; K32)
     c.k32 = f16 && e->use_s2k32 && op.cin % 32 == 0;
     c.npp = (f16 && !c.k32) ? 1 : 2; c.nch = op.cin / (c.k32 ? 32 : 16);
+    // split mode, 128 columns, fixed tile, weights not resident (two chunks or more): the pipelined instance (kernels_s2v2p.h).  Its conversion is
+    // branch-free, so it takes normalised sources only - every stride-2 conv of the supported nets reads one
+    c.s2p = e->precision == TS2D_PRECISION_F32_SPLIT_F16X3 && c.bn == 128 && !c.flex && !s2v2_resident(c) && e->use_s2p && e->tensors[op.src].normed;
 }
 
 // The decoder block `op` (3x3 conv over cat(up, skip)) as ONE kernel together with its transposed conv (kernels_upc.h ...), or K_NONE.

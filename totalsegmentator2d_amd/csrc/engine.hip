@@ -13,6 +13,7 @@
 #include "kernels_first.h"
 #include "kernels_res32.h"
 #include "kernels_s2v2.h"
+#include "kernels_s2v2p.h"
 #include "kernels_upc.h"
 #include "kernels_up0.h"
 #include "kernels_upq.h"
@@ -450,10 +451,11 @@ hipError_t launch_tiled(Kern k, bool f16, int bn, int P, const ConvArgs& a, int 
 
 // conv3x3s2_v2 (kernels_s2v2.h): persistent, one workgroup per CU walks its tiles; every chunk's weights resident in LDS when they fit beside the patch
 hipError_t launch_s2v2(const ts2d_engine* e, const Choice& c, bool f16, const ConvArgs& ca, int grid_x, hipStream_t st) {
-    const size_t wchunk = (size_t)9 * c.npp * 2 * c.bn * 16;
-    const bool resw = (size_t)c.npp * 2 * kS2Plane + (size_t)c.nch * wchunk <= (size_t)160 * 1024;
+    const size_t wchunk = s2v2_wchunk(c);
+    const bool resw = s2v2_resident(c);
     const dim3 grid(std::min(grid_x, 8 * ca.n_ctiles * std::max(1, e->num_cus / (8 * ca.n_ctiles)))), block(kS2Threads);
     const size_t smem = (size_t)c.npp * 2 * kS2Plane + (resw ? (size_t)c.nch : 1) * wchunk;
+    if (c.s2p) return launch_max_lds<conv3x3s2_v2p>(grid, block, kS2pLds, st, ca);      // two patch buffers, weights from L2 (dispatch.cpp: s2v2_variant)
     auto inst = [&](auto bn_, auto s, auto k32_) {
         using S = decltype(s); using ST = typename S::type;
         constexpr int BN = decltype(bn_)::value; constexpr bool K32 = decltype(k32_)::value;
@@ -805,7 +807,7 @@ int ts2d_engine_set_option(ts2d_engine* e, const char* name, int value) {
     struct B { const char* n; bool* p; };
     struct I { const char* n; int* p; int lo, hi; };
     const B bools[] = {{"one", &e->use_one}, {"s2v2", &e->use_s2v2}, {"q", &e->use_q}, {"h2", &e->use_h2},  {"uh2", &e->use_uh2},
-                       {"first_split", &e->use_first_split}, {"sbk", &e->use_sbk}, {"s2k32", &e->use_s2k32}, {"up0", &e->use_up0}, {"upc", &e->use_upc}, {"res", &e->use_res}, {"fuse0", &e->use_fuse0}, {"flex", &e->use_flex}};
+                       {"first_split", &e->use_first_split}, {"sbk", &e->use_sbk}, {"s2k32", &e->use_s2k32}, {"s2p", &e->use_s2p}, {"up0", &e->use_up0}, {"upc", &e->use_upc}, {"res", &e->use_res}, {"fuse0", &e->use_fuse0}, {"flex", &e->use_flex}};
     const I ints[] = {{"u0seg", &e->u0seg, 0, 1 << 20}, {"flex2", &e->use_flex2, 0, 2}};
     bool found = false;
     for (const B& b : bools) if (!strcmp(name, b.n)) { *b.p = value != 0; found = true; }
@@ -813,7 +815,7 @@ int ts2d_engine_set_option(ts2d_engine* e, const char* name, int value) {
         if (value < i.lo || value > i.hi) return fail(TS2D_ERR_INVALID, "option %s = %d out of range [%d, %d]", name, value, i.lo, i.hi);
         *i.p = value; found = true;
     }
-    if (!found) return fail(TS2D_ERR_INVALID, "unknown option '%s' (one s2v2 q h2 uh2 up0 u0seg upc res fuse0 flex flex2 first_split sbk s2k32)", name);
+    if (!found) return fail(TS2D_ERR_INVALID, "unknown option '%s' (one s2v2 q h2 uh2 up0 u0seg upc res fuse0 flex flex2 first_split sbk s2k32 s2p)", name);
     e->ws_precision = -1;         // which ops compose (and with it the activation plan) depends on the options: re-plan at the next reserve / forward
     ++e->opt_gen;
     return TS2D_OK;

@@ -7,6 +7,7 @@
 #include "../../include/ts2d_engine.h"
 #include <hip/hip_runtime_api.h>
 #include "device_tables.h"
+#include "tile_dims.h"
 
 #include <atomic>
 #include <cstddef>
@@ -122,6 +123,7 @@ struct Choice {
     bool first_split = false;   // (K_FIRST*) the K = 9 C contraction as one fp16 hi / lo split product (kernels_first.h SPLIT; else the exact fp32 MFMA)
     bool k32 = false;           // (K_S2_V2) 16-bit mode: chunks of 32 channels (kernels_s2v2.h K32)
     int npp = 0, nch = 0;       // (K_S2_V2) LDS planes per (tap, k half), channel chunks
+    bool s2p = false;           // (K_S2_V2) the pipelined split-mode instance conv3x3s2_v2p (kernels_s2v2p.h); same reported name, same bits
     int seg = 0;                // (K_UP0 / K_S1_RES32*) tiles per workgroup segment (segment_tiles)
     int ks = 0;                 // (K_UPC_H / K_UPC_H2) coarse k-steps per staged chunk
     const char* name = "";      // what ts2d_engine_op_kernel reports for the op (tests and scripts/pmc_traffic.py key on these strings)
@@ -130,6 +132,9 @@ struct Choice {
 inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 inline int ct_total(const Op& op) { return op.cin + op.cin_skip; }
+// (K_S2_V2) every chunk's weight block of the column tile stays in LDS beside the patch
+inline size_t s2v2_wchunk(const Choice& c) { return (size_t)9 * c.npp * 2 * c.bn * 16; }
+inline bool s2v2_resident(const Choice& c) { return (size_t)c.npp * 2 * kS2PlaneBytes + (size_t)c.nch * s2v2_wchunk(c) <= (size_t)kS2LdsMax; }
 
 }  // namespace ts2d
 
@@ -163,6 +168,7 @@ struct ts2d_engine {
     bool use_h2 = true;           // "h2": 16-bit plain C -> C blocks on 16 x 32 tiles (0: conv3x3_h32)
     bool use_uh2 = true;          // "uh2": 16-bit composed block on 16 x 32 tiles (0: conv3x3_upc_h)
     bool use_s2k32 = true;        // "s2k32": 16-bit mode - the 512-thread stride-2 kernel on 32-channel chunks (0: 16-channel chunks)
+    bool use_s2p = true;          // "s2p": split mode - the pipelined instance of the 512-thread stride-2 kernel at 128 columns (0: conv3x3s2_v2<128> itself, its bit-identical twin)
     bool use_sbk = true;          // "sbk": small batches - split-K (and the two-kernel decoder entry) where the preferred kernel would leave most CUs idle (fill_ksplit)
     bool use_first_split = true;  // "first_split": the first block's contraction as one fp16 hi / lo split product (kernels_first.h SPLIT; 0: exact fp32 MFMA)
     bool use_up0 = true;          // "up0": dedicated persistent kernel of the level-0 composed block (0: conv3x3_upc<32>)
