@@ -554,13 +554,15 @@ int ts2d_planes_crop_zscore(ts2d_planes* p, int32_t box[4], float* stats, int* n
 #define TS2D_PLANES_EMPTY_MASK 4    /* use_mask on an image of zeros: there is nothing to take a mean of */
 #define TS2D_PLANES_ZERO_SIGN 8     /* a TS2D_NORM_RESCALE01 plane whose minimum is -0.0: if it holds +0.0 too, numpy's min() may return
                                      * either, and the sign of every resulting zero hangs on it */
+#define TS2D_PLANES_FILL_ROUNDS 16  /* ts2d_planes_crop_normalize_stack_masked only: the 3-D hole filling of the mask was still adding voxels after
+                                     * its 64 rounds (a corridor that winds through the volume): the fill is left to the host */
 int ts2d_planes_crop_normalize(ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask, int32_t box[4],
                                float* stats, int* status);
 
 /* A STACK on the handle: a 3-D volume that a 2-D plan takes slice by slice (run_case, prediction_worker.py:194-199, fed a volume - what
  * `nnUNetv2_predict -c 2d` does with a CT).  Upload src [channels][slices][h][w] float32; the handle then holds channels x slices planes, and
  * ts2d_planes_resample_cubic, ts2d_planes_extent, ts2d_planes_download and ts2d_planes_destroy treat every slice as a plane.  The two crop
- * entries above refuse such a handle (TS2D_ERR_INVALID); ts2d_planes_crop_normalize_stack is its own.
+ * entries above refuse such a handle (TS2D_ERR_INVALID); ts2d_planes_crop_normalize_stack and ts2d_planes_crop_normalize_stack_masked are its own.
  * TS2D_ERR_INVALID, by name, before any device work: null pointers, channels or slices below 1, more than 65535 planes, an extent outside
  * 1 ... 8192, more than 2^28 samples.  (A new symbol of ABI 9: nothing that existed changed.) */
 int ts2d_planes_create_stack(int device, const float* src, int channels, int slices, int h, int w, ts2d_planes** out);
@@ -572,8 +574,8 @@ int ts2d_planes_create_stack(int device, const float* src, int channels, int sli
  *             the box of the unfilled one.  The volume is compacted to it, dense [channels][Z'][h'][w']: the handle then holds channels x Z'
  *             planes of h' x w'.
  *   schemes, params   per CHANNEL, as in ts2d_planes_crop_normalize.
- *   use_mask  [channels]: must be zero for every TS2D_NORM_ZSCORE channel - the mask of a volume is hole-filled in 3-D, which stays on the
- *             host; ignored for the other schemes, as nnU-Net ignores it.
+ *   use_mask  [channels]: must be zero for every TS2D_NORM_ZSCORE channel - the mask of a volume is hole-filled in 3-D, which
+ *             ts2d_planes_crop_normalize_stack_masked does; ignored for the other schemes, as nnU-Net ignores it.
  *   stats     [channels][2], as in ts2d_planes_crop_normalize.
  * Arithmetic contract = the statements of ts2d_planes_crop_normalize applied to each channel's WHOLE cropped volume, flattened in C order, which
  * is what numpy reduces (normalize_channel copies the cropped view into a dense array): the z-score sums run over N = Z' h' w' samples, their
@@ -589,6 +591,28 @@ int ts2d_planes_create_stack(int device, const float* src, int channels, int sli
  * (A new symbol of ABI 9: nothing that existed changed.) */
 int ts2d_planes_crop_normalize_stack(ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask, int32_t box[6],
                                      float* stats, int* status);
+
+/* ts2d_planes_crop_normalize_stack that TAKES a masked z-score channel (use_mask_for_norm of an MR plan): the same arguments, box, limits and
+ * messages under its own name, and for the channels that are not masked the same bytes.
+ *   use_mask  [channels]: non-zero = a TS2D_NORM_ZSCORE channel takes its statistics over, and is normalised only inside, the non-zero mask of
+ *             the cropped volume with its holes filled in 3-D: "non-zero in ANY channel" (`!= 0`: a NaN counts, -0.0 does not) plus every zero
+ *             voxel that is not 6-connected through zero voxels to a face of the box = scipy.ndimage.binary_fill_holes of the mask of the whole
+ *             array (default cross structure), cropped - what nnU-Net's create_nonzero_mask computes of a volume; every voxel outside the box is
+ *             zero and reaches the array's border in a straight line, so the faces of the box stand in for that border.  Ignored for the other
+ *             schemes.  The fill runs only when a channel is masked.
+ *   stats     (mean, std) of a masked channel are those of its masked samples.
+ * Arithmetic contract of a masked channel = preprocess.masked_zscore_stack_statement: masked_zscore_f32_statement over the flattened channel - the
+ * masked samples in index order are ONE run of n_m elements, so numpy's chunks of 8192 cross the slices as `img[mask]` does; inside the mask
+ * fl32(fl32(x - mean) / max(std, 1e-8)), outside it the sample itself.  The mask itself = preprocess.fill_holes_sweeps_statement: rounds of six
+ * directional sweeps (z up, z down, y up, y down, x up, x down) from the background voxels on the faces until a round adds nothing.
+ *   status    the bits of ts2d_planes_crop_normalize_stack, and
+ *             TS2D_PLANES_EMPTY_MASK   a masked channel in a volume of zeros;
+ *             TS2D_PLANES_FILL_ROUNDS  64 rounds each still added a voxel: nothing is normalised, no retry; the caller runs numpy.
+ * Device scratch beside that of ts2d_planes_crop_normalize_stack, only with a masked channel and freed on every path: two bit planes of the
+ * cropped volume (a quarter of a byte per voxel), one byte per voxel for the mask, 4 bytes per 2048 voxels twice, and the masked samples of
+ * every channel (4 bytes each).  (A new symbol of ABI 9: nothing that existed changed.) */
+int ts2d_planes_crop_normalize_stack_masked(ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask, int32_t box[6],
+                                            float* stats, int* status);
 
 /* The order-3 resample of run_case (prediction_worker.py:194-199, a case whose spacing is not the plan's) of every plane of the handle to
  * out_h x out_w, clipped to the bounds ts2d_planes_crop_zscore left: the arithmetic, the limits and the messages of ts2d_resample_cubic.

@@ -94,6 +94,7 @@ SIGNATURES = {
     'ts2d_planes_crop_normalize': (_I, [_P, _P, _P, _P, ctypes.POINTER(ctypes.c_int32 * 4), _P, ctypes.POINTER(_I)]),
     'ts2d_planes_create_stack': (_I, [_I, _P, _I, _I, _I, _I, _PP]),
     'ts2d_planes_crop_normalize_stack': (_I, [_P, _P, _P, _P, ctypes.POINTER(ctypes.c_int32 * 6), _P, ctypes.POINTER(_I)]),
+    'ts2d_planes_crop_normalize_stack_masked': (_I, [_P, _P, _P, _P, ctypes.POINTER(ctypes.c_int32 * 6), _P, ctypes.POINTER(_I)]),
     'ts2d_planes_resample_cubic': (_I, [_P, _I, _I]),
     'ts2d_planes_extent': (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     'ts2d_planes_download': (_I, [_P, _P]),
@@ -118,7 +119,7 @@ SIGNATURES = {
     'ts2d_engine_destroy': (_I, [_P]),
 }
 SYMBOLS = tuple(SIGNATURES)
-# added under ABI 9 (the cubic resample; the device-resident planes of preprocess.DevicePlanes, ts2d_planes_crop_normalize after the others, the two *_stack entries last):
+# added under ABI 9 (the cubic resample; the device-resident planes of preprocess.DevicePlanes, ts2d_planes_crop_normalize after the others, the two *_stack entries, then ts2d_planes_crop_normalize_stack_masked last):
 # a library built before them lacks the symbols, still loads, and the callers keep the host route; the probabilities entries likewise
 # ... and the residual-encoder entry: without it a ResidualEncoderUNet cannot be created (Engine says so), a plain net is unaffected
 OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n or n == 'ts2d_engine_create_residual')

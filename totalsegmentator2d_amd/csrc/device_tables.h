@@ -85,7 +85,7 @@ static_assert(sizeof(PrepNorm) == 8, "PrepNorm is copied to the device as bytes"
 
 // ---- every normalisation scheme on those planes (kernels_prep_schemes.h); the ids and status bits are the TS2D_NORM_* / TS2D_PLANES_* of the C header
 enum PrepSchemeId : int { kPrepZScore = 0, kPrepCT = 1, kPrepRescale01 = 2, kPrepRGB01 = 3, kPrepNone = 4 };
-enum PrepStatus : int { kPrepStatusNonfinite = 1, kPrepStatusRgbRange = 2, kPrepStatusEmptyMask = 4, kPrepStatusZeroSign = 8 };
+enum PrepStatus : int { kPrepStatusNonfinite = 1, kPrepStatusRgbRange = 2, kPrepStatusEmptyMask = 4, kPrepStatusZeroSign = 8, kPrepStatusFillRounds = 16 };
 constexpr int kPrepMaskBlock = 2048;    // pixels per workgroup of the mask kernels: 8 rows of 256 lanes
 
 // per plane: x <- fl32(fl32(clip(x) - sub) / div); the clip to [lo, hi] for kPrepCT only, nothing at all for kPrepNone, and with `masked`

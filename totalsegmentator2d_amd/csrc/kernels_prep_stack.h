@@ -4,10 +4,11 @@
 // follows is per slice, clipped to each slice's own minimum and maximum.  Three kernels behind ts2d_planes_crop_normalize_stack (prep.hip):
 //     prep_nonzero_box3          the box {z0, z1, r0, r1, c0, c1} of the voxels that are non-zero in ANY channel (integer atomics, one pass)
 //     prep_compact_box3          the box of every channel copied into a dense [C][Z'][h'][w'] buffer: its flattened index is numpy's
-//     prep_apply_schemes_stack<A> prep_apply_schemes of kernels_prep_schemes.h with the scheme row of plane / Z' and no mask: A = true normalises
+//     prep_apply_schemes_stack<A, M> prep_apply_schemes of kernels_prep_schemes.h with the scheme row of plane / Z': A = true normalises
 //                                every slice in place by its CHANNEL's row and leaves the float32 minimum and maximum of each SLICE as integer
 //                                keys; A = false leaves the keys of the slices as they are (the minimum and maximum behind Rescale: the host
-//                                folds them over a channel's slices, integers again)
+//                                folds them over a channel's slices, integers again).  M = false reads no mask; M = true normalises a masked row
+//                                only inside the volume's hole-filled mask (kernels_prep_fill.h), behind ts2d_planes_crop_normalize_stack_masked
 // The sums of the z-score are prep_chunk_sums<0 / 1> of kernels_prep.h, unchanged, over C runs of N = Z' h' w' elements: numpy copies the cropped
 // view of a channel into a dense C-ordered array and reduces that, so its chunks of 8192 cross the slice boundaries exactly as these do
 // (tests/test_stack_cpu.py).  Arithmetic = the statements of preprocess.py applied to the flattened channel, bit for bit; every subtraction and
@@ -46,17 +47,19 @@ __global__ __launch_bounds__(256) void prep_compact_box3(const float* __restrict
     dst[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * bh * bw + i] = src[from];
 }
 
-// prep_apply_schemes for the slices x [channels * slices][n] of a stack: slice `plane` is normalised by schemes[plane / slices] (no row is masked);
+// prep_apply_schemes for the slices x [channels * slices][n] of a stack: slice `plane` is normalised by schemes[plane / slices] - with MASKED a masked
+// row only where mask [slices][n], the mask of the volume that all channels share, is set, the sample itself elsewhere; without it mask is not read;
 // lo_hi [channels * slices][2] receives prep_key of each SLICE's minimum and maximum, preset to {INT_MAX, INT_MIN} by the host; *status as there.
 // Not APPLY: schemes and status are not read and x is not written.  grid = (ceil(n / 2048), channels * slices), 256 lanes.
-template <bool APPLY>
+template <bool APPLY, bool MASKED>
 __global__ __launch_bounds__(256) void prep_apply_schemes_stack(float* __restrict__ x, long long n, int slices, const PrepScheme* __restrict__ schemes,
-                                                                int* __restrict__ lo_hi, int* __restrict__ status) {
+                                                                const uint8_t* __restrict__ mask, int* __restrict__ lo_hi, int* __restrict__ status) {
 #pragma clang fp contract(off)
     const int plane = blockIdx.y;
     PrepScheme s{kPrepNone, 0, 0.f, 1.f, 0.f, 0.f};
     if (APPLY) s = schemes[plane / slices];
     float* p = x + (size_t)plane * n;
+    const uint8_t* m = MASKED ? mask + (size_t)(plane % slices) * n : nullptr;
     const long long i0 = (long long)blockIdx.x * (256 * kPrepNormPerLane) + threadIdx.x;
     int lo = 0x7FFFFFFF, hi = (int)0x80000000;
     bool outside = false;
@@ -70,7 +73,7 @@ __global__ __launch_bounds__(256) void prep_apply_schemes_stack(float* __restric
                 v = v > s.hi ? s.hi : v;
             }
             if (s.id == kPrepRGB01) outside |= v < 0.f || v > 255.f;
-            if (s.id != kPrepNone) {
+            if (s.id != kPrepNone && (!MASKED || !s.masked || m[i] != 0)) {
                 const float d = v - s.sub;
                 v = d / s.div;
                 p[i] = v;

@@ -8,6 +8,7 @@
 #include "kernels_prep.h"
 #include "kernels_prep_schemes.h"
 #include "kernels_prep_stack.h"
+#include "kernels_prep_fill.h"
 
 #include <algorithm>
 #include <cmath>
@@ -32,7 +33,8 @@ namespace {
 constexpr int kPrepMaxPlanes = 65535;           // (a grid dimension)
 constexpr long long kPrepMaxSamples = 1ll << 28;
 static_assert(kPrepZScore == TS2D_NORM_ZSCORE && kPrepCT == TS2D_NORM_CT && kPrepRescale01 == TS2D_NORM_RESCALE01 && kPrepRGB01 == TS2D_NORM_RGB01 &&
-              kPrepNone == TS2D_NORM_NONE && kPrepStatusRgbRange == TS2D_PLANES_RGB_RANGE, "the scheme table speaks the C header's numbers");
+              kPrepNone == TS2D_NORM_NONE && kPrepStatusRgbRange == TS2D_PLANES_RGB_RANGE && kPrepStatusFillRounds == TS2D_PLANES_FILL_ROUNDS,
+              "the scheme table speaks the C header's numbers");
 
 int project_coronal_impl(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz,
                          long long sy, long long sx, long long base, float* out_max, float* out_mean, float* out_norm, double* out_stats, int* out_box) {
@@ -206,6 +208,170 @@ int planes_keep_bounds(ts2d_planes* p, const int* d_keys, std::vector<int>* keys
     if (*bad) return TS2D_OK;
     HIP_TRY(hipMemcpy(p->d_lh.as<float>(), lh.data(), m * sizeof(float), hipMemcpyHostToDevice));
     p->has_bounds = true;
+    return TS2D_OK;
+}
+
+// Both crop entries of a stack.  take_masked: a z-score channel with use_mask is normalised inside the hole-filled mask of the volume
+// (kernels_prep_fill.h); without it such a channel is refused by name.
+int planes_crop_normalize_stack(const char* entry, bool take_masked, ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask,
+                                int32_t box[6], float* stats, int* status) {
+    if (!p || !schemes || !params || !use_mask || !box || !stats || !status) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
+    *status = 0;
+    const int C = p->n / p->z;
+    bool any_plain = false, any_masked = false, any_rescale = false;
+    for (int c = 0; c < C; ++c) {
+        if (schemes[c] < TS2D_NORM_ZSCORE || schemes[c] > TS2D_NORM_NONE) return fail(TS2D_ERR_INVALID, "%s: channel %d has the unknown scheme %d", entry, c, (int)schemes[c]);
+        const bool masked = schemes[c] == TS2D_NORM_ZSCORE && use_mask[c];
+        if (masked && !take_masked)
+            return fail(TS2D_ERR_INVALID, "%s: channel %d is normalised inside the non-zero mask, which nnU-Net fills in 3-D for a volume: that stays on the host", entry, c);
+        if (schemes[c] == TS2D_NORM_CT)
+            for (int k = 0; k < 4; ++k)
+                if (!std::isfinite(params[4 * c + k]))
+                    return fail(TS2D_ERR_INVALID, "%s: channel %d has the non-finite CT parameter %g at [%d] (mean, divisor, lower bound, upper bound)", entry, c, (double)params[4 * c + k], k);
+        any_masked |= masked; any_plain |= schemes[c] == TS2D_NORM_ZSCORE && !masked; any_rescale |= schemes[c] == TS2D_NORM_RESCALE01;
+    }
+    HIP_TRY(hipSetDevice(p->device));
+    // scratch, sized for the uncropped extent: [box, -, status, n_m, "a sweep added a bit" | min / max keys of every slice, of the result and of the input | mean, divisor |
+    //                                           scheme table | leaves of the partial chunk | chunk and leaf sums of every channel]
+    const int n0 = p->n;
+    const size_t per_channel = (size_t)((long long)p->z * p->h * p->w / kPrepChunk) + kPrepMaxTailLeaves;
+    const size_t o_keys = 256, o_norm = align_up(o_keys + (size_t)n0 * 4 * sizeof(int), 256), o_table = align_up(o_norm + (size_t)C * sizeof(PrepNorm), 256);
+    const size_t o_leaves = align_up(o_table + (size_t)C * sizeof(PrepScheme), 256), o_sums = align_up(o_leaves + kPrepMaxTailLeaves * sizeof(PrepLeaf), 256);
+    DevMem d;
+    HIP_TRY(d.alloc(o_sums + (size_t)C * per_channel * sizeof(float)));
+    int* d_box = d.as<int>(); int* d_status = d.as<int>(7 * sizeof(int)); int* d_total = d_status + 1; int* d_added = d_status + 2;
+    int* d_keys = d.as<int>(o_keys);
+    PrepNorm* d_norm = d.as<PrepNorm>(o_norm); PrepScheme* d_table = d.as<PrepScheme>(o_table);
+    // 1. crop_to_nonzero's box over all channels and all three axes (the holes nnU-Net fills in the mask lie inside it: the box is that of the raw mask)
+    int hb[6] = {p->z, -1, p->h, -1, p->w, -1};
+    const int zero = 0;
+    HIP_TRY(hipMemcpy(d_box, hb, sizeof(hb), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_status, &zero, sizeof(int), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(prep_nonzero_box3, dim3((unsigned)(((long long)p->z * p->h * p->w + 255) / 256)), dim3(256), 0, 0, p->d.as<float>(), C, p->z, p->h, p->w, d_box);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(hb, d_box, sizeof(hb), hipMemcpyDeviceToHost));
+    if (hb[1] < 0) { hb[0] = 0; hb[1] = p->z - 1; hb[2] = 0; hb[3] = p->h - 1; hb[4] = 0; hb[5] = p->w - 1; }      // nothing but zeros: the whole extent stays
+    const int ext[3] = {p->z, p->h, p->w};
+    for (int a = 0; a < 3; ++a)
+        if (hb[2 * a] < 0 || hb[2 * a + 1] >= ext[a] || hb[2 * a] > hb[2 * a + 1])
+            return fail(TS2D_ERR_HIP, "%s: the device returned the box %d ... %d on axis %d of extent %d", entry, hb[2 * a], hb[2 * a + 1], a, ext[a]);
+    const int bz = hb[1] - hb[0] + 1, bh = hb[3] - hb[2] + 1, bw = hb[5] - hb[4] + 1;
+    // 2. compaction: the flattened index of the dense [C][bz][bh][bw] buffer is numpy's
+    if (bz != p->z || bh != p->h || bw != p->w) {
+        DevMem d_new;
+        HIP_TRY(d_new.alloc((size_t)C * bz * bh * bw * sizeof(float)));
+        hipLaunchKernelGGL(prep_compact_box3, dim3((unsigned)((bh * bw + 255) / 256), (unsigned)bz, (unsigned)C), dim3(256), 0, 0,
+                           p->d.as<const float>(), p->z, p->h, p->w, hb[0], hb[2], hb[4], bh, bw, d_new.as<float>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+        p->d = std::move(d_new); p->z = bz; p->h = bh; p->w = bw; p->n = C * bz;
+    }
+    p->has_bounds = false;
+    for (int a = 0; a < 3; ++a) { box[2 * a] = hb[2 * a]; box[2 * a + 1] = hb[2 * a + 1] + 1; }
+    const int n = p->n;
+    float* const x = p->d.as<float>();
+    const long long n_plane = (long long)bh * bw, N = n_plane * bz;
+    const dim3 grid_apply((unsigned)((n_plane + 256 * kPrepNormPerLane - 1) / (256 * kPrepNormPerLane)), (unsigned)n);
+    int* d_keys_in = d_keys + 2 * (size_t)n;
+    std::vector<int> keys((size_t)n * 4);
+    for (size_t i = 0; i < keys.size(); i += 2) { keys[i] = 0x7FFFFFFF; keys[i + 1] = (int)0x80000000; }
+    HIP_TRY(hipMemcpy(d_keys, keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice));
+    // 3. with a masked channel: the non-zero mask of the volume with its holes filled in 3-D, shared by all channels - rounds of six sweeps over two
+    //    bit planes until one adds nothing - and the masked samples of every channel in index order: numpy's `img[m]`, across the slices
+    long long n_m = 0;
+    const uint8_t* mask = nullptr;
+    DevMem d_bits, d_mask, d_dense;
+    if (any_masked) {
+        const int ww = (bw + 63) / 64;
+        const long long rows = (long long)bz * bh, words = rows * ww;
+        HIP_TRY(d_bits.alloc(2 * (size_t)words * sizeof(prep_word)));
+        prep_word* const d_bg = d_bits.as<prep_word>(); prep_word* const d_out = d_bg + words;
+        hipLaunchKernelGGL(prep_fill_planes, dim3((unsigned)((words + 3) / 4)), dim3(256), 0, 0, x, C, bz, bh, bw, d_bg, d_out);
+        HIP_TRY(hipGetLastError());
+        const long long lines_z = (long long)bh * ww, lines_y = (long long)bz * ww;
+        const dim3 grid_z((unsigned)((lines_z + 63) / 64)), grid_y((unsigned)((lines_y + 63) / 64)), grid_x((unsigned)((rows + 63) / 64));
+        int round = 0;
+        for (; round < kPrepFillMaxRounds; ++round) {
+            int added = 0;
+            HIP_TRY(hipMemcpy(d_added, &added, sizeof(int), hipMemcpyHostToDevice));
+            for (int dir = 1; dir >= -1; dir -= 2)
+                hipLaunchKernelGGL(prep_fill_sweep_words, grid_z, dim3(64), 0, 0, d_bg, d_out, lines_z, lines_z, 0ll, lines_z, bz, dir, d_added);
+            for (int dir = 1; dir >= -1; dir -= 2)
+                hipLaunchKernelGGL(prep_fill_sweep_words, grid_y, dim3(64), 0, 0, d_bg, d_out, lines_y, (long long)ww, lines_z, (long long)ww, bh, dir, d_added);
+            hipLaunchKernelGGL(prep_fill_sweep_rows<true>, grid_x, dim3(64), 0, 0, d_bg, d_out, rows, ww, d_added);
+            hipLaunchKernelGGL(prep_fill_sweep_rows<false>, grid_x, dim3(64), 0, 0, d_bg, d_out, rows, ww, d_added);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(&added, d_added, sizeof(int), hipMemcpyDeviceToHost));
+            if (!added) break;
+        }
+        if (round == kPrepFillMaxRounds) { *status = TS2D_PLANES_FILL_ROUNDS; return TS2D_OK; }      // every round still added something: numpy's turn
+        const int nb = (int)((N + kPrepMaskBlock - 1) / kPrepMaskBlock);
+        const size_t o_counts = align_up((size_t)N, 256), o_offs = align_up(o_counts + (size_t)nb * sizeof(int), 256);
+        HIP_TRY(d_mask.alloc(o_offs + (size_t)nb * sizeof(int)));
+        mask = d_mask.as<uint8_t>();
+        hipLaunchKernelGGL(prep_fill_mask_counts, dim3((unsigned)nb), dim3(256), 0, 0, d_out, bw, N, d_mask.as<uint8_t>(), d_mask.as<int>(o_counts));
+        hipLaunchKernelGGL(prep_mask_scan, dim3(1), dim3(1024), 0, 0, d_mask.as<int>(o_counts), nb, d_mask.as<int>(o_offs), d_total);
+        HIP_TRY(hipGetLastError());
+        int total = 0;
+        HIP_TRY(hipMemcpy(&total, d_total, sizeof(int), hipMemcpyDeviceToHost));
+        if (total < 0 || total > N) return fail(TS2D_ERR_HIP, "%s: the device counted %d masked voxels of %lld", entry, total, N);
+        if (total == 0) { *status = TS2D_PLANES_EMPTY_MASK; return TS2D_OK; }      // a volume of zeros: numpy takes the mean of nothing
+        n_m = total;
+        HIP_TRY(d_dense.alloc((size_t)C * n_m * sizeof(float)));
+        hipLaunchKernelGGL(prep_mask_scatter, dim3((unsigned)nb, (unsigned)C), dim3(256), 0, 0, x, N, mask, d_mask.as<int>(o_offs), n_m, d_dense.as<float>());
+        HIP_TRY(hipGetLastError());
+    }
+    // 4. the parameters of every channel, over its WHOLE cropped volume: the z-score statistics of a run of N = bz bh bw samples (numpy's chunks
+    //    cross the slices) - of the n_m masked ones for a masked channel -, the minimum and maximum behind Rescale folded over the channel's
+    //    slices, the caller's for CT
+    std::vector<PrepNorm> norm((size_t)C, PrepNorm{0.f, 1.f});
+    std::vector<uint8_t> want((size_t)C);
+    bool bad = false;
+    if (any_plain) {
+        for (int c = 0; c < C; ++c) want[c] = schemes[c] == TS2D_NORM_ZSCORE && !use_mask[c];
+        TRY(planes_stats(entry, x, N, C, want.data(), d_norm, d.as<PrepLeaf>(o_leaves), d.as<float>(o_sums), norm.data(), stats, &bad));
+    }
+    if (any_masked && !bad) {
+        for (int c = 0; c < C; ++c) want[c] = schemes[c] == TS2D_NORM_ZSCORE && use_mask[c];
+        TRY(planes_stats(entry, d_dense.as<float>(), n_m, C, want.data(), d_norm, d.as<PrepLeaf>(o_leaves), d.as<float>(o_sums), norm.data(), stats, &bad));
+    }
+    if (any_rescale && !bad) {
+        hipLaunchKernelGGL((prep_apply_schemes_stack<false, false>), grid_apply, dim3(256), 0, 0, x, n_plane, bz, nullptr, nullptr, d_keys_in, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(keys.data() + 2 * (size_t)n, d_keys_in, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    std::vector<PrepScheme> table((size_t)C);
+    for (int c = 0; c < C && !bad; ++c) {
+        PrepScheme& s = table[c];
+        s = PrepScheme{(int)schemes[c], 0, 0.f, 1.f, 0.f, 0.f};
+        if (s.id == kPrepZScore) { s.masked = use_mask[c] ? 1 : 0; s.sub = norm[c].mean; s.div = norm[c].div; continue; }      // (stats: mean and std, written above)
+        if (s.id == kPrepCT) { s.sub = params[4 * c]; s.div = params[4 * c + 1]; s.lo = params[4 * c + 2]; s.hi = params[4 * c + 3]; }
+        if (s.id == kPrepRGB01) s.div = 255.f;
+        if (s.id == kPrepRescale01) {
+            int klo = 0x7FFFFFFF, khi = (int)0x80000000;
+            for (int k = 0; k < bz; ++k) {
+                const int* kk = keys.data() + 2 * (size_t)n + 2 * ((size_t)c * bz + k);
+                klo = std::min(klo, kk[0]); khi = std::max(khi, kk[1]);
+            }
+            const float mn = prep_unkey(klo), mx = prep_unkey(khi);
+            if (!std::isfinite(mn) || !std::isfinite(mx)) { bad = true; break; }
+            // numpy's min() of a volume that holds zeros of both signs and nothing below them returns either: not decided here
+            if (mn == 0.f && std::signbit(mn)) *status |= TS2D_PLANES_ZERO_SIGN;
+            s.sub = mn; s.div = prep_rescale_div(mn, mx);
+        }
+        stats[2 * c] = s.sub; stats[2 * c + 1] = s.div;
+    }
+    if (bad) *status |= TS2D_PLANES_NONFINITE;                     // a non-finite sample (or an overflowing sum)
+    if (*status) return TS2D_OK;                                   // nothing is normalised
+    // 5. normalise in place by the channel's row (a masked one inside the mask only); the minimum and maximum of each resulting SLICE are the clip bounds of the resample
+    HIP_TRY(hipMemcpy(d_table, table.data(), table.size() * sizeof(PrepScheme), hipMemcpyHostToDevice));
+    if (any_masked) hipLaunchKernelGGL((prep_apply_schemes_stack<true, true>), grid_apply, dim3(256), 0, 0, x, n_plane, bz, d_table, mask, d_keys, d_status);
+    else hipLaunchKernelGGL((prep_apply_schemes_stack<true, false>), grid_apply, dim3(256), 0, 0, x, n_plane, bz, d_table, nullptr, d_keys, d_status);
+    HIP_TRY(hipGetLastError());
+    TRY(planes_keep_bounds(p, d_keys, &keys, &bad));
+    HIP_TRY(hipMemcpy(status, d_status, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad) *status |= TS2D_PLANES_NONFINITE;                     // (a quotient overflowed, or a channel that is not normalised holds a non-finite sample)
+    if (*status) p->has_bounds = false;                            // (an RGB sample out of range: the slices are no result, nothing resamples them)
     return TS2D_OK;
 }
 
@@ -406,113 +572,12 @@ int ts2d_planes_crop_normalize(ts2d_planes* p, const int32_t* schemes, const flo
 
 int ts2d_planes_crop_normalize_stack(ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask, int32_t box[6], float* stats,
                                      int* status) {
-    const char* const entry = "ts2d_planes_crop_normalize_stack";
-    if (!p || !schemes || !params || !use_mask || !box || !stats || !status) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
-    *status = 0;
-    const int C = p->n / p->z;
-    bool any_zscore = false, any_rescale = false;
-    for (int c = 0; c < C; ++c) {
-        if (schemes[c] < TS2D_NORM_ZSCORE || schemes[c] > TS2D_NORM_NONE) return fail(TS2D_ERR_INVALID, "%s: channel %d has the unknown scheme %d", entry, c, (int)schemes[c]);
-        if (schemes[c] == TS2D_NORM_ZSCORE && use_mask[c])
-            return fail(TS2D_ERR_INVALID, "%s: channel %d is normalised inside the non-zero mask, which nnU-Net fills in 3-D for a volume: that stays on the host", entry, c);
-        if (schemes[c] == TS2D_NORM_CT)
-            for (int k = 0; k < 4; ++k)
-                if (!std::isfinite(params[4 * c + k]))
-                    return fail(TS2D_ERR_INVALID, "%s: channel %d has the non-finite CT parameter %g at [%d] (mean, divisor, lower bound, upper bound)", entry, c, (double)params[4 * c + k], k);
-        any_zscore |= schemes[c] == TS2D_NORM_ZSCORE; any_rescale |= schemes[c] == TS2D_NORM_RESCALE01;
-    }
-    HIP_TRY(hipSetDevice(p->device));
-    // scratch, sized for the uncropped extent: [box, -, status | min / max keys of every slice, of the result and of the input | mean, divisor |
-    //                                           scheme table | leaves of the partial chunk | chunk and leaf sums of every channel]
-    const int n0 = p->n;
-    const size_t per_channel = (size_t)((long long)p->z * p->h * p->w / kPrepChunk) + kPrepMaxTailLeaves;
-    const size_t o_keys = 256, o_norm = align_up(o_keys + (size_t)n0 * 4 * sizeof(int), 256), o_table = align_up(o_norm + (size_t)C * sizeof(PrepNorm), 256);
-    const size_t o_leaves = align_up(o_table + (size_t)C * sizeof(PrepScheme), 256), o_sums = align_up(o_leaves + kPrepMaxTailLeaves * sizeof(PrepLeaf), 256);
-    DevMem d;
-    HIP_TRY(d.alloc(o_sums + (size_t)C * per_channel * sizeof(float)));
-    int* d_box = d.as<int>(); int* d_status = d.as<int>(7 * sizeof(int));
-    int* d_keys = d.as<int>(o_keys);
-    PrepNorm* d_norm = d.as<PrepNorm>(o_norm); PrepScheme* d_table = d.as<PrepScheme>(o_table);
-    // 1. crop_to_nonzero's box over all channels and all three axes (the holes nnU-Net fills in the mask lie inside it: the box is that of the raw mask)
-    int hb[6] = {p->z, -1, p->h, -1, p->w, -1};
-    const int zero = 0;
-    HIP_TRY(hipMemcpy(d_box, hb, sizeof(hb), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_status, &zero, sizeof(int), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(prep_nonzero_box3, dim3((unsigned)(((long long)p->z * p->h * p->w + 255) / 256)), dim3(256), 0, 0, p->d.as<float>(), C, p->z, p->h, p->w, d_box);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(hb, d_box, sizeof(hb), hipMemcpyDeviceToHost));
-    if (hb[1] < 0) { hb[0] = 0; hb[1] = p->z - 1; hb[2] = 0; hb[3] = p->h - 1; hb[4] = 0; hb[5] = p->w - 1; }      // nothing but zeros: the whole extent stays
-    const int ext[3] = {p->z, p->h, p->w};
-    for (int a = 0; a < 3; ++a)
-        if (hb[2 * a] < 0 || hb[2 * a + 1] >= ext[a] || hb[2 * a] > hb[2 * a + 1])
-            return fail(TS2D_ERR_HIP, "%s: the device returned the box %d ... %d on axis %d of extent %d", entry, hb[2 * a], hb[2 * a + 1], a, ext[a]);
-    const int bz = hb[1] - hb[0] + 1, bh = hb[3] - hb[2] + 1, bw = hb[5] - hb[4] + 1;
-    // 2. compaction: the flattened index of the dense [C][bz][bh][bw] buffer is numpy's
-    if (bz != p->z || bh != p->h || bw != p->w) {
-        DevMem d_new;
-        HIP_TRY(d_new.alloc((size_t)C * bz * bh * bw * sizeof(float)));
-        hipLaunchKernelGGL(prep_compact_box3, dim3((unsigned)((bh * bw + 255) / 256), (unsigned)bz, (unsigned)C), dim3(256), 0, 0,
-                           p->d.as<const float>(), p->z, p->h, p->w, hb[0], hb[2], hb[4], bh, bw, d_new.as<float>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipDeviceSynchronize());
-        p->d = std::move(d_new); p->z = bz; p->h = bh; p->w = bw; p->n = C * bz;
-    }
-    p->has_bounds = false;
-    for (int a = 0; a < 3; ++a) { box[2 * a] = hb[2 * a]; box[2 * a + 1] = hb[2 * a + 1] + 1; }
-    const int n = p->n;
-    float* const x = p->d.as<float>();
-    const long long n_plane = (long long)bh * bw, N = n_plane * bz;
-    const dim3 grid_apply((unsigned)((n_plane + 256 * kPrepNormPerLane - 1) / (256 * kPrepNormPerLane)), (unsigned)n);
-    int* d_keys_in = d_keys + 2 * (size_t)n;
-    std::vector<int> keys((size_t)n * 4);
-    for (size_t i = 0; i < keys.size(); i += 2) { keys[i] = 0x7FFFFFFF; keys[i + 1] = (int)0x80000000; }
-    HIP_TRY(hipMemcpy(d_keys, keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice));
-    // 3. the parameters of every channel, over its WHOLE cropped volume: the z-score statistics of a run of N = bz bh bw samples (numpy's chunks
-    //    cross the slices), the minimum and maximum behind Rescale folded over the channel's slices, the caller's for CT
-    std::vector<PrepNorm> norm((size_t)C, PrepNorm{0.f, 1.f});
-    bool bad = false;
-    if (any_zscore) {
-        std::vector<uint8_t> want((size_t)C);
-        for (int c = 0; c < C; ++c) want[c] = schemes[c] == TS2D_NORM_ZSCORE;
-        TRY(planes_stats(entry, x, N, C, want.data(), d_norm, d.as<PrepLeaf>(o_leaves), d.as<float>(o_sums), norm.data(), stats, &bad));
-    }
-    if (any_rescale && !bad) {
-        hipLaunchKernelGGL(prep_apply_schemes_stack<false>, grid_apply, dim3(256), 0, 0, x, n_plane, bz, nullptr, d_keys_in, nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(keys.data() + 2 * (size_t)n, d_keys_in, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    std::vector<PrepScheme> table((size_t)C);
-    for (int c = 0; c < C && !bad; ++c) {
-        PrepScheme& s = table[c];
-        s = PrepScheme{(int)schemes[c], 0, 0.f, 1.f, 0.f, 0.f};
-        if (s.id == kPrepZScore) { s.sub = norm[c].mean; s.div = norm[c].div; continue; }      // (stats: mean and std, written above)
-        if (s.id == kPrepCT) { s.sub = params[4 * c]; s.div = params[4 * c + 1]; s.lo = params[4 * c + 2]; s.hi = params[4 * c + 3]; }
-        if (s.id == kPrepRGB01) s.div = 255.f;
-        if (s.id == kPrepRescale01) {
-            int klo = 0x7FFFFFFF, khi = (int)0x80000000;
-            for (int k = 0; k < bz; ++k) {
-                const int* kk = keys.data() + 2 * (size_t)n + 2 * ((size_t)c * bz + k);
-                klo = std::min(klo, kk[0]); khi = std::max(khi, kk[1]);
-            }
-            const float mn = prep_unkey(klo), mx = prep_unkey(khi);
-            if (!std::isfinite(mn) || !std::isfinite(mx)) { bad = true; break; }
-            // numpy's min() of a volume that holds zeros of both signs and nothing below them returns either: not decided here
-            if (mn == 0.f && std::signbit(mn)) *status |= TS2D_PLANES_ZERO_SIGN;
-            s.sub = mn; s.div = prep_rescale_div(mn, mx);
-        }
-        stats[2 * c] = s.sub; stats[2 * c + 1] = s.div;
-    }
-    if (bad) *status |= TS2D_PLANES_NONFINITE;                     // a non-finite sample (or an overflowing sum)
-    if (*status) return TS2D_OK;                                   // nothing is normalised
-    // 4. normalise in place by the channel's row; the minimum and maximum of each resulting SLICE are the clip bounds of the resample
-    HIP_TRY(hipMemcpy(d_table, table.data(), table.size() * sizeof(PrepScheme), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(prep_apply_schemes_stack<true>, grid_apply, dim3(256), 0, 0, x, n_plane, bz, d_table, d_keys, d_status);
-    HIP_TRY(hipGetLastError());
-    TRY(planes_keep_bounds(p, d_keys, &keys, &bad));
-    HIP_TRY(hipMemcpy(status, d_status, sizeof(int), hipMemcpyDeviceToHost));
-    if (bad) *status |= TS2D_PLANES_NONFINITE;                     // (a quotient overflowed, or a channel that is not normalised holds a non-finite sample)
-    if (*status) p->has_bounds = false;                            // (an RGB sample out of range: the slices are no result, nothing resamples them)
-    return TS2D_OK;
+    return planes_crop_normalize_stack("ts2d_planes_crop_normalize_stack", false, p, schemes, params, use_mask, box, stats, status);
+}
+
+int ts2d_planes_crop_normalize_stack_masked(ts2d_planes* p, const int32_t* schemes, const float* params, const uint8_t* use_mask, int32_t box[6],
+                                            float* stats, int* status) {
+    return planes_crop_normalize_stack("ts2d_planes_crop_normalize_stack_masked", true, p, schemes, params, use_mask, box, stats, status);
 }
 
 int ts2d_planes_resample_cubic(ts2d_planes* p, int out_h, int out_w) {

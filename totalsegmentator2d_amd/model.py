@@ -47,6 +47,7 @@ class HIPModel:
         self.device_input_normalize = True  # crop box, z-score (and that resample) of a native 2-D input on device-resident planes: the same float32 values as numpy, bit for bit (preprocess.zscore_f32_statement)
         self.device_input_normalize_schemes = True  # the same for every other nnU-Net scheme (masked z-score, CT, Rescale, RGB, none): the cases device_input_normalize leaves to numpy, the same bits (preprocess.*_f32_statement)
         self.device_input_stack = True   # a stack [C, Z, H, W] under a 2-D plan: crop box over three axes, unmasked normalisation with the statistics of the whole volume (and the per-slice resample) on device-resident planes; numpy's bits (preprocess.crop_box3_statement and the *_f32_statement of the flattened channel)
+        self.device_input_stack_masked = True   # ... and a stack whose plan has use_mask_for_norm on a z-score channel (the MR plans): the 3-D hole filling of the non-zero mask, the statistics of the masked samples and the normalisation inside the mask on those planes; numpy's and scipy's bits (preprocess.fill_holes_sweeps_statement, masked_zscore_stack_statement)
         self.device_stack = True         # ... and its decided map from the device, every slice one image of the convention's own entry (_run; needs that convention's switch too); the host route's bytes
         self._discover()
 
@@ -154,7 +155,7 @@ class HIPModel:
         """Everything DefaultPreprocessor.run_case_npy reads besides the image itself: two sub-models with the same key preprocess identically."""
         cm, pm = p.configuration_manager, p.plans_manager
         dz = props.get('device_zscore')
-        return repr((props.get('device_resample'), props.get('device_normalize'), props.get('device_normalize_schemes'), props.get('device_normalize_stack')) + (list(getattr(pm, 'transpose_forward', [0, 1, 2])), list(cm.spacing), list(getattr(cm, 'normalization_schemes', None) or []),
+        return repr((props.get('device_resample'), props.get('device_normalize'), props.get('device_normalize_schemes'), props.get('device_normalize_stack'), props.get('device_normalize_stack_masked')) + (list(getattr(pm, 'transpose_forward', [0, 1, 2])), list(cm.spacing), list(getattr(cm, 'normalization_schemes', None) or []),
                      list(getattr(cm, 'use_mask_for_norm', None) or []), sorted((p.dataset_json.get('channel_names') or {}).items()),
                      (getattr(pm, 'plans', None) or {}).get('foreground_intensity_properties_per_channel', {}),
                      None if dz is None else tuple(dz.get('order', ()))))
@@ -193,6 +194,8 @@ class HIPModel:
             props['device_normalize_schemes'] = self._input_device(self.device_input_normalize_schemes)   # ... and normalised there by any other scheme of the plan
         if self._input_device(getattr(self, 'device_input_stack', False)) is not None:
             props['device_normalize_stack'] = self._input_device(self.device_input_stack)   # ... and a stack of slices under a 2-D plan is cropped and normalised there as a volume
+        if self._input_device(getattr(self, 'device_input_stack_masked', False)) is not None:
+            props['device_normalize_stack_masked'] = self._input_device(self.device_input_stack_masked)   # ... with the 3-D hole filling of the mask where a channel is normalised inside it
         pre = p.configuration_manager.preprocessor_class(verbose=p.verbose)
         shared = getattr(ref, 'preprocess_cache', None)      # set by TS2D.predict: the sub-models of one case mostly share channels and plan
         if shared is None:

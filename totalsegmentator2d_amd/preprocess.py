@@ -494,6 +494,8 @@ def crop_box3_statement(data: np.ndarray):
 # nnU-Net's default_normalization_schemes -> the TS2D_NORM_* of include/ts2d_engine.h, and the TS2D_PLANES_* status bits of ts2d_planes_crop_normalize
 NORM_SCHEME_IDS = {'ZScoreNormalization': 0, 'CTNormalization': 1, 'RescaleTo01Normalization': 2, 'RGBTo01Normalization': 3, 'NoNormalization': 4}
 PLANES_NONFINITE, PLANES_RGB_RANGE, PLANES_EMPTY_MASK, PLANES_ZERO_SIGN = 1, 2, 4, 8
+PLANES_FILL_ROUNDS = 16      # ts2d_planes_crop_normalize_stack_masked: the hole filling was still adding voxels after FILL_MAX_ROUNDS rounds
+FILL_MAX_ROUNDS = 64         # kPrepFillMaxRounds of csrc/kernels_prep_fill.h
 RGB_RANGE_MESSAGE = "RGB images are uint 8, for whatever reason I found pixel values outside [0, 255]"
 
 
@@ -569,6 +571,49 @@ def masked_zscore_f32_statement(plane: np.ndarray, mask: np.ndarray) -> np.ndarr
     return x
 
 
+def fill_holes_sweeps_statement(mask: np.ndarray):
+    """``scipy.ndimage.binary_fill_holes(mask)`` (default cross structure) of a boolean volume ``[Z, H, W]`` as the device computes it
+    (csrc/kernels_prep_fill.h), ``(filled, rounds)``: ``bg = ~mask``; ``out`` starts as the background voxels on the six faces; a ROUND is six
+    directional sweeps in fixed order - z up, z down, y up, y down, x up, x down - each ``out[i] |= bg[i] & out[i -+ 1]`` walked along its axis, each
+    seeing the one before; a round that adds nothing ends the loop and is counted.  ``filled = ~out``.  The result does not depend on the order: a
+    background voxel stays outside the mask iff it is 6-connected through background to a face, which is scipy's definition, so the bytes are
+    scipy's (tests/test_stack_masked_cpu.py) - only ``rounds`` belongs to this order, and they are the device's rounds: 2 ... 7 on head-like masks,
+    ``(H - 1) // 2 + 1`` on a one-voxel serpentine corridor of height H.  Applied to the mask INSIDE crop_to_nonzero's box it gives the filled mask of the
+    whole array, cropped: every voxel outside the box is background and reaches the array's border in a straight line."""
+    mask = np.asarray(mask).astype(bool)
+    if mask.ndim != 3:
+        raise ValueError(f"fill_holes_sweeps_statement: [Z, H, W] is needed, got {mask.shape}")
+    bg = ~mask
+    out = np.zeros_like(bg)
+    for ax in range(3):
+        for at in (0, -1):
+            sl = [slice(None)] * 3
+            sl[ax] = at
+            out[tuple(sl)] = bg[tuple(sl)]
+    o, b = [np.moveaxis(out, ax, 0) for ax in range(3)], [np.moveaxis(bg, ax, 0) for ax in range(3)]     # views: axis `ax` first
+    rounds = 0
+    while True:
+        rounds += 1
+        before = int(out.sum())
+        for ax in range(3):
+            n = mask.shape[ax]
+            for i in range(1, n):                       # up
+                o[ax][i] |= b[ax][i] & o[ax][i - 1]
+            for i in range(n - 2, -1, -1):              # down
+                o[ax][i] |= b[ax][i] & o[ax][i + 1]
+        if int(out.sum()) == before:
+            return ~out, rounds
+
+
+def masked_zscore_stack_statement(vol: np.ndarray, mask: np.ndarray) -> np.ndarray:
+    """``ZScoreNormalization.run`` with ``use_mask_for_norm`` of one channel's cropped volume ``[Z, h, w]``: :func:`masked_zscore_f32_statement` over the
+    flattened, C-ordered channel - ``img[mask]`` is ONE run of the masked samples in index order, so numpy's chunks of 8192 cross the slices.
+    ``mask``: the volume's hole-filled non-zero mask (:func:`fill_holes_sweeps_statement` inside the crop box = :func:`crop_to_nonzero`'s).  This is
+    the statement the device entry ts2d_planes_crop_normalize_stack_masked reproduces bit for bit."""
+    flat = np.ascontiguousarray(vol, np.float32).reshape(1, -1)
+    return masked_zscore_f32_statement(flat, np.asarray(mask).reshape(1, -1)).reshape(np.shape(vol))
+
+
 def planes_device_entries():
     """The engine library when it has the ``ts2d_planes_*`` entries, or None (no library built, or one built before they existed): the callers
     then keep the host route, silently - the result is the same."""
@@ -582,7 +627,7 @@ def planes_device_entries():
 
 class DevicePlanes:
     """The planes ``[C, 1, h, w]`` float32 of one native 2-D case - with ``stack``, the slices ``[C, Z, h, w]`` of a volume that a 2-D plan takes slice
-    by slice (:meth:`crop_normalize_stack` is then the one crop entry) - on the device, behind a ``ts2d_planes`` handle: uploaded once here, cropped
+    by slice (:meth:`crop_normalize_stack`, or :meth:`crop_normalize_stack_masked` with a masked z-score channel, is then the crop entry) - on the device, behind a ``ts2d_planes`` handle: uploaded once here, cropped
     and normalised (:meth:`crop_zscore`, or :meth:`crop_normalize` for the other schemes) and resampled (:meth:`resample`) where they lie, downloaded once (:meth:`download`).  Every float32
     that comes back is the host route's, bit for bit (:func:`zscore_f32_statement` and the statements of the other schemes, :func:`resize_cubic_f64`).  A context manager;
     :meth:`close` destroys the handle and may be called twice."""
@@ -652,10 +697,10 @@ class DevicePlanes:
         self.stats = stats
         return [[0, 1], [int(box[0]), int(box[1])], [int(box[2]), int(box[3])]]
 
-    def crop_normalize_stack(self, schemes, use_mask, fip):
+    def crop_normalize_stack(self, schemes, use_mask, fip, entry='ts2d_planes_crop_normalize_stack'):
         """:meth:`crop_normalize` for a stack (ts2d_planes_crop_normalize_stack): the box over all three axes, each channel normalised with the
         parameters of its WHOLE cropped volume, no masked scheme.  Returns the box ``[[z0, z1], [r0, r1], [c0, c1]]`` the slices now span, or None with
-        the PLANES_* bits in ``self.status``."""
+        the PLANES_* bits in ``self.status``.  ``entry``: the symbol to call - :meth:`crop_normalize_stack_masked` passes its own, same arguments."""
         import ctypes
         ids = np.array([NORM_SCHEME_IDS[s] for s in schemes[:self.channels]], np.int32)
         params = np.zeros((self.channels, 4), np.float32)
@@ -664,13 +709,20 @@ class DevicePlanes:
         masked = np.array([bool(c < len(use_mask) and use_mask[c]) for c in range(self.channels)], np.uint8)
         box, status = (ctypes.c_int32 * 6)(), ctypes.c_int(0)
         stats = np.zeros((self.channels, 2), np.float32)
-        self._check(self._lib.ts2d_planes_crop_normalize_stack(self._h, ids.ctypes.data, params.ctypes.data, masked.ctypes.data, ctypes.byref(box),
-                                                               stats.ctypes.data, ctypes.byref(status)), 'ts2d_planes_crop_normalize_stack')
+        self._check(getattr(self._lib, entry)(self._h, ids.ctypes.data, params.ctypes.data, masked.ctypes.data, ctypes.byref(box),
+                                              stats.ctypes.data, ctypes.byref(status)), entry)
         self.status = int(status.value)
         if self.status:
             return None
         self.stats, self.slices = stats, int(box[1]) - int(box[0])
         return [[int(box[0]), int(box[1])], [int(box[2]), int(box[3])], [int(box[4]), int(box[5])]]
+
+    def crop_normalize_stack_masked(self, schemes, use_mask, fip):
+        """:meth:`crop_normalize_stack` that takes a masked z-score channel (ts2d_planes_crop_normalize_stack_masked): the non-zero mask of the cropped
+        volume is hole-filled in 3-D on the device (:func:`fill_holes_sweeps_statement`) and the channel normalised inside it with the statistics of its
+        masked samples (:func:`masked_zscore_stack_statement`).  None with the PLANES_* bits in ``self.status`` - PLANES_EMPTY_MASK and
+        PLANES_FILL_ROUNDS among them - as there."""
+        return self.crop_normalize_stack(schemes, use_mask, fip, entry='ts2d_planes_crop_normalize_stack_masked')
 
     def resample(self, hw):
         """Order-3 resample of every plane to ``hw`` on the device, clipped to the bounds :meth:`crop_zscore` left."""
@@ -737,7 +789,7 @@ def _ct_parameters_usable(schemes, fip, c) -> bool:
 
 def _device_stack_applies(data, tf, schemes, use_mask, fip) -> bool:
     """The cases ts2d_planes_crop_normalize_stack computes: a stack (more than one slice per channel) under the identity transpose, every scheme one of
-    nnU-Net's five and none of them masked (the mask of a volume is hole-filled in 3-D: that stays on the host), usable CT parameters, extents,
+    nnU-Net's five and none of them masked (the mask of a volume is hole-filled in 3-D: :func:`_device_stack_masked_applies` and its entry take that), usable CT parameters, extents,
     plane and sample counts inside the handle's limits (and above the size from which it pays), the two stack entries present."""
     c, z, h, w = data.shape
     if not (list(tf) == [0, 1, 2] and z > 1 and c >= 1 and len(schemes) >= c and all(s in NORM_SCHEME_IDS for s in schemes[:c])):
@@ -750,6 +802,23 @@ def _device_stack_applies(data, tf, schemes, use_mask, fip) -> bool:
     return (1 <= min(h, w) and max(h, w) <= CUBIC_MAX_EXTENT and c * z <= PLANES_MAX_PLANES
             and DEVICE_NORMALIZE_MIN_SAMPLES <= c * z * h * w <= PLANES_MAX_SAMPLES
             and lib is not None and hasattr(lib, 'ts2d_planes_create_stack') and hasattr(lib, 'ts2d_planes_crop_normalize_stack'))
+
+
+def _device_stack_masked_applies(data, tf, schemes, use_mask, fip) -> bool:
+    """The cases :func:`_device_stack_applies` refuses for a masked channel and ts2d_planes_crop_normalize_stack_masked computes: its other conditions,
+    at least one ZScoreNormalization channel with ``use_mask_for_norm``, and that entry present.  Ungated beyond DEVICE_NORMALIZE_MIN_SAMPLES: the
+    device route wins at every size measured, 16 x 128 x 128 included (profiles/r22_stack_masked_case.txt)."""
+    c, z, h, w = data.shape
+    if not (list(tf) == [0, 1, 2] and z > 1 and c >= 1 and len(schemes) >= c and all(s in NORM_SCHEME_IDS for s in schemes[:c])):
+        return False
+    if not any(schemes[i] == 'ZScoreNormalization' and i < len(use_mask) and use_mask[i] for i in range(c)):
+        return False
+    if not _ct_parameters_usable(schemes, fip, c):
+        return False
+    lib = planes_device_entries()
+    return (1 <= min(h, w) and max(h, w) <= CUBIC_MAX_EXTENT and c * z <= PLANES_MAX_PLANES
+            and DEVICE_NORMALIZE_MIN_SAMPLES <= c * z * h * w <= PLANES_MAX_SAMPLES
+            and lib is not None and hasattr(lib, 'ts2d_planes_create_stack') and hasattr(lib, 'ts2d_planes_crop_normalize_stack_masked'))
 
 
 def _device_schemes_apply(data, tf, schemes, use_mask, fip) -> bool:
@@ -798,6 +867,7 @@ class DefaultPreprocessor:
         device_normalize = properties.pop('device_normalize', None)   # GPU index for crop box + z-score (+ that resample) on device-resident planes
         device_schemes = properties.pop('device_normalize_schemes', None)   # the same for the cases that route refuses for their schemes: masked z-score, CT, Rescale, RGB, none
         device_stack = properties.pop('device_normalize_stack', None)       # the same for a stack [C, Z, H, W], Z > 1, under a 2-D plan: box over three axes, statistics of the whole volume, no masked scheme
+        device_stack_masked = properties.pop('device_normalize_stack_masked', None)   # ... and for a stack with a masked z-score channel: the 3-D hole filling of the mask, the statistics of the masked samples
         target_spacing = list(configuration_manager.spacing)
         if len(target_spacing) < len(data.shape[1:]):
             target_spacing = [original_spacing[0]] + target_spacing
@@ -807,9 +877,14 @@ class DefaultPreprocessor:
             planes_device, plain = device_normalize, True
         elif device_schemes is not None and _device_schemes_apply(data, tf, schemes, use_mask, fip):
             planes_device, plain = device_schemes, False
+        stack_device = None
         if device_stack is not None and len(configuration_manager.spacing) == 2 and _device_stack_applies(data, tf, schemes, use_mask, fip):
-            with DevicePlanes(data, device_stack, stack=True) as planes:
-                bbox = planes.crop_normalize_stack(schemes, use_mask, fip)
+            stack_device, stack_masked = device_stack, False
+        elif device_stack_masked is not None and len(configuration_manager.spacing) == 2 and _device_stack_masked_applies(data, tf, schemes, use_mask, fip):
+            stack_device, stack_masked = device_stack_masked, True
+        if stack_device is not None:
+            with DevicePlanes(data, stack_device, stack=True) as planes:
+                bbox = planes.crop_normalize_stack_masked(schemes, use_mask, fip) if stack_masked else planes.crop_normalize_stack(schemes, use_mask, fip)
                 if bbox is not None:            # (None: a status bit - numpy below computes, or raises, what numpy does)
                     properties['bbox_used_for_cropping'] = bbox
                     shape = properties['shape_after_cropping_and_before_resampling'] = planes.shape[1:]
