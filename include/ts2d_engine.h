@@ -415,6 +415,51 @@ int ts2d_ensemble_predict_tiled_probabilities(ts2d_engine* const* engines, int n
                                               int mirror_mask, const uint16_t* gaussian_f16, int full_batch, int mode,
                                               const uint8_t* class_order, int n_order);
 
+/* ts2d_ensemble_predict_tiled_probabilities for SLICE STACKS - a 3-D volume [C, Z, H, W] that a 2-D model takes slice by slice, whose
+ * probabilities are ONE array [K, Z0, full_h, full_w]: the outputs are described per RUN, not per image.  A run is n_slices consecutive
+ * images of the call, images[first_image ... first_image + n_slices), that share one geometry - the ten numbers of
+ * ts2d_tiled_probabilities and the padded extent (Hp, Wp) - and are consecutive slices of one volume:
+ *   prob_f32       host, head 0 of the run's first slice.  Head k of slice s lies at prob_f32 + k * prob_head_stride + s * full_h * full_w
+ *                  (elements): with prob_head_stride = Z0 * full_h * full_w the run writes slices [z, z + n_slices) of the caller's
+ *                  [K, Z0, full_h, full_w] where prob_f32 points at [0, z].  prob_head_stride >= n_slices * full_h * full_w.  Not NULL.
+ *   decided_u8     host or NULL, the same scheme: slice s of the decided map at decided_u8 + s * full_h * full_w, multilabel head k at
+ *                  + k * decided_head_stride (>= n_slices * full_h * full_w there; ignored in the other modes: one plane per slice).
+ * The runs of a call cover its images exactly once, in order: run 0 begins at image 0, every run where the one before it ended, the last
+ * ends at n_images.  A volume that is split over several calls contributes one run to each, at different slice offsets of the same arrays;
+ * slices outside every run (those outside the crop box along z) are the caller's to fill.
+ * Everything else - engines, images, full_batch and its determinism rule, the fold mean, inf_flag, mode, class_order, the arithmetic, the
+ * fill around the box, the identity rule, the decision - is the sibling entry's: a run of one slice with prob_head_stride = full_h * full_w
+ * writes that entry's bytes.  On the device the outputs of a run live as [K][n_slices][full_h][full_w], so a run is downloaded in K
+ * contiguous copies (+ K, or 1, for the decided map), and the taps of a run that resamples are built and uploaded once, not per slice
+ * (csrc/kernels_prob.h: sw_probabilities<ProbStackSeg>, the sibling's lanes with a head stride).
+ * Every argument is validated before any device work and nothing is written on an error: everything the sibling entry refuses, in its
+ * words with the run named ("run 1: image 3: probabilities: bad output extent 0x5"); runs at a NULL pointer or n_runs < 1 for n_images
+ * > 0; a run of fewer than 1 slices; a run that begins behind the end of the one before it ("run 1: probabilities: begins at image 3
+ * and leaves a gap behind image 2"), before it ("... begins at image 1 and overlaps the run before it, which ends at image 2"), or leaves the
+ * call's images; runs that end before n_images; a NULL prob_f32 ("run 0: probabilities: the output is null"); a head stride below
+ * n_slices * full_h * full_w ("run 0: probabilities: head stride 100 is below 3 slices of 6x7"; "decided head stride" likewise); an
+ * image of a run whose padded extent differs from the run's first.  n_images == 0 returns TS2D_OK and does nothing.
+ * Device scratch, all held by engines[0]: that of the sibling entry, with the outputs summed over the RUNS - K x n_slices x full_h x full_w
+ * x 4 bytes, n_slices x full_h x full_w bytes (x K multilabel) where decided_u8 is asked for, each rounded up to 256 elements - 24 bytes per
+ * output row and column of a RUN that resamples + 88 per image, n_order bytes.
+ * (Added under ABI 9: new symbols only, no existing signature or structure changes, so ts2d_abi_version() stays 9.) */
+typedef struct {
+    int32_t  src_y, src_x, src_h, src_w;   /* as in ts2d_tiled_probabilities, for every slice of the run */
+    int32_t  out_h, out_w;
+    int32_t  full_h, full_w;
+    int32_t  box_y, box_x;
+    int32_t  first_image, n_slices;        /* images[first_image ... first_image + n_slices) */
+    float*   prob_f32;                     /* host: head 0 of the run's first slice */
+    int64_t  prob_head_stride;             /* elements between the heads of a slice */
+    uint8_t* decided_u8;                   /* host: the run's first slice of the decided map, or NULL */
+    int64_t  decided_head_stride;          /* multilabel: elements between the heads of a slice; else ignored */
+} ts2d_tiled_probabilities_run;
+
+int ts2d_ensemble_predict_tiled_probabilities_stack(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, int n_images,
+                                                    const ts2d_tiled_probabilities_run* runs, int n_runs, int patch_h, int patch_w,
+                                                    int mirror_mask, const uint16_t* gaussian_f16, int full_batch, int mode,
+                                                    const uint8_t* class_order, int n_order);
+
 /* The kernel of ts2d_ensemble_predict_tiled_probabilities on half planes the CALLER supplies - the twin of ts2d_labelmap_from_logits and
  * ts2d_regions_from_logits, with their arguments and their refusals ("probabilities:" in the place of "regions:"), plus the full extent, the
  * box origin and the mode: logits_f16 host [K, H, W] half bits, rect = {src_y, src_x, src_h, src_w}, prob_f32 host [K, full_h, full_w] (not

@@ -57,12 +57,22 @@ class TiledProbabilities(ctypes.Structure):
                 ('box_y', ctypes.c_int32), ('box_x', ctypes.c_int32), ('prob_f32', ctypes.c_void_p), ('decided_u8', ctypes.c_void_p)]
 
 
+class TiledProbabilitiesRun(ctypes.Structure):
+    """``ts2d_tiled_probabilities_run``: the outputs of ``n_slices`` consecutive images of ``ts2d_ensemble_predict_tiled_probabilities_stack`` - slices of
+    one volume with one geometry - as a pointer and a head stride into the caller's [K, Z0, full_h, full_w]."""
+    _fields_ = [('src_y', ctypes.c_int32), ('src_x', ctypes.c_int32), ('src_h', ctypes.c_int32), ('src_w', ctypes.c_int32),
+                ('out_h', ctypes.c_int32), ('out_w', ctypes.c_int32), ('full_h', ctypes.c_int32), ('full_w', ctypes.c_int32),
+                ('box_y', ctypes.c_int32), ('box_x', ctypes.c_int32), ('first_image', ctypes.c_int32), ('n_slices', ctypes.c_int32),
+                ('prob_f32', ctypes.c_void_p), ('prob_head_stride', ctypes.c_int64), ('decided_u8', ctypes.c_void_p),
+                ('decided_head_stride', ctypes.c_int64)]
+
+
 PROB_MULTILABEL, PROB_LABELMAP, PROB_REGIONS = 0, 1, 2      # TS2D_PROB_*
 
 # shorthands of the table below: int, void *, size_t, long long, unsigned long long, char *; pointers to a void * and to the three descriptors
 _I, _P, _Z, _LL, _ULL, _S = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_char_p
 _PP, _TI, _TE, _TL = ctypes.POINTER(_P), ctypes.POINTER(TiledImage), ctypes.POINTER(TiledExport), ctypes.POINTER(TiledLabelmap)
-_TP = ctypes.POINTER(TiledProbabilities)
+_TP, _TPR = ctypes.POINTER(TiledProbabilities), ctypes.POINTER(TiledProbabilitiesRun)
 _PROJECT = [_I, _P, _Z, _I, _I, _I, _I, _LL, _LL, _LL, _LL, _P, _P]
 
 # every symbol include/ts2d_engine.h declares: name -> (restype, argtypes)
@@ -85,6 +95,7 @@ SIGNATURES = {
     'ts2d_ensemble_predict_tiled_regions': (_I, [_PP, _I, _TI, _TL, _I, _I, _I, _I, _P, _I, _P, _I]),
     'ts2d_regions_from_logits': (_I, [_I, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32 * 4), _I, _I, _P, _P]),
     'ts2d_ensemble_predict_tiled_probabilities': (_I, [_PP, _I, _TI, _TP, _I, _I, _I, _I, _P, _I, _I, _P, _I]),
+    'ts2d_ensemble_predict_tiled_probabilities_stack': (_I, [_PP, _I, _TI, _I, _TPR, _I, _I, _I, _I, _P, _I, _I, _P, _I]),
     'ts2d_probabilities_from_logits': (_I, [_I, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32 * 4), _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     'ts2d_project_coronal': (_I, _PROJECT),
     'ts2d_project_coronal_zscore': (_I, _PROJECT + [_P, _P, _P]),
@@ -120,7 +131,7 @@ SIGNATURES = {
 }
 SYMBOLS = tuple(SIGNATURES)
 # added under ABI 9 (the cubic resample; the device-resident planes of preprocess.DevicePlanes, ts2d_planes_crop_normalize after the others, the two *_stack entries, then ts2d_planes_crop_normalize_stack_masked last):
-# a library built before them lacks the symbols, still loads, and the callers keep the host route; the probabilities entries likewise
+# a library built before them lacks the symbols, still loads, and the callers keep the host route; the probabilities entries likewise (the one for stacks came after the other two: each is looked up on its own)
 # ... and the residual-encoder entry: without it a ResidualEncoderUNet cannot be created (Engine says so), a plain net is unaffected
 OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n or n == 'ts2d_engine_create_residual')
 

@@ -56,6 +56,19 @@ struct ProbSeg {
 };
 static_assert(sizeof(ProbSeg) == 32, "ProbSeg is copied to the device as bytes");
 
+// ... and of sw_probabilities<ProbStackSeg>: the image is slice s of a RUN of n_slices images whose outputs lie head-major, [K][n_slices][full_h][full_w],
+// so that a head of the whole run is one contiguous piece; head k of the slice is at prob_off + k * prob_stride.  Every field is a multiple of 4
+// where full_w is (the vector stores' condition)
+struct ProbStackSeg {
+    long long prob_off;     // elements from the float outputs to head 0 of this slice: the run's first element + s * full_h * full_w
+    long long dec_off;      // ... from the uint8 outputs to this slice of the decided map ([K][n_slices] planes multilabel, else [n_slices] planes)
+    long long prob_stride;  // elements between the heads of a slice: n_slices * full_h * full_w
+    long long dec_stride;   // ... of the decided map (multilabel; else unused: its one plane is head 0)
+    int full_h, full_w;
+    int box_y, box_x;
+};
+static_assert(sizeof(ProbStackSeg) == 48, "ProbStackSeg is copied to the device as bytes");
+
 // ---- the order-3 input resample (kernels_resample_in.h)
 constexpr int kRsInPad = 12;            // scipy's _prepad_for_spline_filter for mode='nearest'
 constexpr int kRsInMaxExtent = 8192;    // preprocess.CUBIC_MAX_EXTENT

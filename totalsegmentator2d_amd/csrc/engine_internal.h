@@ -256,13 +256,20 @@ struct SwPlan {
     bool any16 = false, anyseg = false, any_rs8 = false, any_rs32 = false;
     std::vector<SwSeg> segs; std::vector<SwChunk> chunks; std::vector<RsSeg> rsegs;
     std::vector<ProbSeg> psegs; long long prob_elems = 0;      // a probabilities call: one per image beside its RsSeg; elements of the float outputs
-    std::vector<char> tab;                  // [segments | tile_y | tile_x | export (or label-map) segments | their taps | class order | probabilities segments]: one host blob, one copy
+    std::vector<ProbStackSeg> pssegs;       // ... of runs (ts2d_ensemble_predict_tiled_probabilities_stack): these in the place of psegs, at tab_psegs too
+    std::vector<char> tab;                  // [segments | tile_y | tile_x | export (or label-map) segments | their taps | class order | probabilities segments (ProbSeg, or ProbStackSeg of runs)]: one host blob, one copy
     size_t tab_segs = 0, tab_rsegs = 0, tab_rtaps = 0, tab_order = 0, tab_psegs = 0;
     // scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs x F | uint8 outputs | flags x F | resampled uint8 (or label maps, or decided maps) | resampled float | probabilities]
     size_t o_tab = 0, o_g = 0, o_imgs = 0, o_batch = 0, o_log = 0, o_o16 = 0, o_seg = 0, o_flag = 0, o_rs8 = 0, o_rs32 = 0, o_prob = 0, bytes = 0;
 };
 // a probabilities call (ts2d_ensemble_predict_tiled_probabilities): its descriptors and its mode (ProbMode = TS2D_PROB_*)
-struct ProbCall { const ts2d_tiled_probabilities* descs; int mode; };
+// `runs` (ts2d_ensemble_predict_tiled_probabilities_stack; else null): the outputs are those of the runs - `descs` is then the entry's own
+// per-image expansion of them (the geometry and the slice's place in the caller's arrays), run_of[i] the run of image i (named in a message);
+// the entry has checked that the runs cover the images once, in order, and that a run's images share (Hp, Wp)
+struct ProbCall {
+    const ts2d_tiled_probabilities* descs; int mode;
+    const ts2d_tiled_probabilities_run* runs = nullptr; int n_runs = 0; const int* run_of = nullptr;
+};
 // `labelmap`: `exports` describe a label-map call (ts2d_ensemble_predict_tiled_labelmap: seg_u8 = the image's label_u8, ONE output plane)
 // `class_order` (with `labelmap`; else null): a region call (ts2d_ensemble_predict_tiled_regions) - the same plan, its descriptors named
 // "regions:" in a message, and the num_classes class values appended to the table blob at tab_order

@@ -83,15 +83,24 @@ __device__ __forceinline__ void pr_store4(uint8_t* __restrict__ o, const unsigne
     }
 }
 
+// elements between the heads of an image's outputs: the dense block of ProbSeg, the run's stride of ProbStackSeg
+__device__ __forceinline__ size_t pr_prob_stride(const ProbSeg& ps) { return (size_t)ps.full_h * ps.full_w; }
+__device__ __forceinline__ size_t pr_dec_stride(const ProbSeg& ps) { return (size_t)ps.full_h * ps.full_w; }
+__device__ __forceinline__ size_t pr_prob_stride(const ProbStackSeg& ps) { return (size_t)ps.prob_stride; }
+__device__ __forceinline__ size_t pr_dec_stride(const ProbStackSeg& ps) { return (size_t)ps.dec_stride; }
+
 // one lane per 4 consecutive X of one row Y of one image's FULL extent; mode: ProbMode; order: K class values (kProbRegions only);
-// prob: [K, full_h, full_w] per image at ProbSeg::prob_off; dec (or null): the decided map at ProbSeg::dec_off
+// Seg = ProbSeg: prob [K, full_h, full_w] per image at ProbSeg::prob_off; dec (or null): the decided map at ProbSeg::dec_off
+// Seg = ProbStackSeg (ts2d_ensemble_predict_tiled_probabilities_stack): the image is a slice of a run whose outputs are [K][n_slices][full_h][full_w] -
+// head k at prob_off + k * prob_stride (dec likewise): the ONE difference between the two instantiations; all offsets are 64-bit
+template <class Seg>
 __global__ __launch_bounds__(256) void sw_probabilities(const __half* __restrict__ src16, const RsSeg* __restrict__ segs,
-                                                        const ProbSeg* __restrict__ psegs, int n_segs, int K, const RsTap* __restrict__ taps,
+                                                        const Seg* __restrict__ psegs, int n_segs, int K, const RsTap* __restrict__ taps,
                                                         int mode, const uint8_t* __restrict__ order, float* __restrict__ prob,
                                                         uint8_t* __restrict__ dec, float thr) {
     const int si = rs_find_seg(segs, n_segs, blockIdx.x);
     const RsSeg sg = segs[si];
-    const ProbSeg ps = psegs[si];
+    const Seg ps = psegs[si];
     const int Wq = (ps.full_w + 3) >> 2;
     const long long l = (long long)(blockIdx.x - sg.block0) * 256 + threadIdx.x;
     if (l >= (long long)ps.full_h * Wq) return;
@@ -99,7 +108,7 @@ __global__ __launch_bounds__(256) void sw_probabilities(const __half* __restrict
     const int nx = ps.full_w - X0 < 4 ? ps.full_w - X0 : 4;     // (the last quad of a row whose extent is no multiple of 4)
     const bool softmax = mode == kProbLabelmap;
     const bool vec = (ps.full_w & 3) == 0;                      // (block-uniform) every quad is whole and 16 / 4 bytes aligned: the offsets are multiples of 4
-    const size_t fplane = (size_t)ps.full_h * ps.full_w;
+    const size_t pstride = pr_prob_stride(ps), dstride = pr_dec_stride(ps);
     const size_t at = (size_t)Y * ps.full_w + X0;
     float* po = prob + ps.prob_off + at;
     uint8_t* dk = dec ? dec + ps.dec_off + at : nullptr;
@@ -115,8 +124,8 @@ __global__ __launch_bounds__(256) void sw_probabilities(const __half* __restrict
         const float zero[4] = {0.f, 0.f, 0.f, 0.f}, one[4] = {1.f, 1.f, 1.f, 1.f};
         const unsigned none[4] = {0u, 0u, 0u, 0u};
         for (int k = 0; k < K; ++k) {
-            pr_store4(po + k * fplane, softmax && k == 0 ? one : zero, nx, vec);
-            if (dk && (mode == kProbMultilabel || k == 0)) pr_store4(dk + k * fplane, none, nx, vec);
+            pr_store4(po + k * pstride, softmax && k == 0 ? one : zero, nx, vec);
+            if (dk && (mode == kProbMultilabel || k == 0)) pr_store4(dk + k * dstride, none, nx, vec);
         }
         return;
     }
@@ -150,8 +159,8 @@ __global__ __launch_bounds__(256) void sw_probabilities(const __half* __restrict
                 ab[j] = above ? 1u : 0u;
                 if (above) head[j] = k + 1;
             }
-            pr_store4(po + k * fplane, pr, nx, vec);
-            if (dk && mode == kProbMultilabel) pr_store4(dk + k * fplane, ab, nx, vec);
+            pr_store4(po + k * pstride, pr, nx, vec);
+            if (dk && mode == kProbMultilabel) pr_store4(dk + k * dstride, ab, nx, vec);
         }
         if (dk && mode == kProbRegions) {
             unsigned lab[4];
@@ -182,7 +191,7 @@ __global__ __launch_bounds__(256) void sw_probabilities(const __half* __restrict
             const float e = pr_exp(pr_value(p, q, j) - best[j]) / sum[j];
             pr[j] = in[j] ? e : k == 0 ? 1.f : 0.f;
         }
-        pr_store4(po + k * fplane, pr, nx, vec);
+        pr_store4(po + k * pstride, pr, nx, vec);
     }
     if (dk) {
         for (int j = 0; j < 4; ++j)

@@ -1,7 +1,7 @@
 // The sliding window of libts2d_engine.so: tile gather, aggregation, the mean of an ensemble's folds and the export's resample-back, around
 // the engine's forward (engine.hip: reserve_checked, run_forward).  The C entries ts2d_engine_predict_tiled*, ts2d_ensemble_predict_tiled_export,
-// ts2d_ensemble_predict_tiled_labelmap, ts2d_ensemble_predict_tiled_regions, ts2d_ensemble_predict_tiled_probabilities, ts2d_labelmap_from_logits,
-// ts2d_regions_from_logits and ts2d_probabilities_from_logits.
+// ts2d_ensemble_predict_tiled_labelmap, ts2d_ensemble_predict_tiled_regions, ts2d_ensemble_predict_tiled_probabilities (and its _stack twin),
+// ts2d_labelmap_from_logits, ts2d_regions_from_logits and ts2d_probabilities_from_logits.
 #include "engine_internal.h"
 #include "kernels_sw.h"
 #include "kernels_fold.h"
@@ -43,6 +43,8 @@ int name_fold(int rc, bool name_folds, int f) {
 // `prob` (ts2d_ensemble_predict_tiled_probabilities; with `labelmap`, else null): `exports` carry the geometry of its descriptors (seg_u8 =
 // prob_f32), `class_order` is set in its regions mode only - the label-map plan with lanes over the full extent, and ONE sw_probabilities
 // launch (kernels_prob.h) in sw_labelmap's place: K float planes (and the decided map) of the pre-crop extent per image.
+// `prob->runs` (ts2d_ensemble_predict_tiled_probabilities_stack): the outputs are those of runs of slices - sw_probabilities<ProbStackSeg> writes a run's
+// planes head-major, and every head of a run travels to the host in one copy, to its place in the caller's strided volume.
 int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap,
                        const uint8_t* class_order, const ProbCall* prob, int n_images, int ph, int pw, int mirror_mask,
                        const uint16_t* gaussian_f16, bool full, bool name_images, bool name_folds, const char* entry) {
@@ -98,9 +100,24 @@ int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* ima
         HIP_TRY(hipGetLastError());
     }
     uint8_t* d_rs8 = pl.any_rs8 ? reinterpret_cast<uint8_t*>(b + pl.o_rs8) : nullptr; float* d_rs32 = pl.any_rs32 ? reinterpret_cast<float*>(b + pl.o_rs32) : nullptr;
-    if (prob) {
+    if (prob && prob->runs) {
         float* d_prob = reinterpret_cast<float*>(b + pl.o_prob);
-        hipLaunchKernelGGL(sw_probabilities, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
+        hipLaunchKernelGGL(sw_probabilities<ProbStackSeg>, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
+                           reinterpret_cast<const ProbStackSeg*>(b + pl.o_tab + pl.tab_psegs), n_images, K, reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps),
+                           prob->mode, class_order ? reinterpret_cast<const uint8_t*>(b + pl.o_tab + pl.tab_order) : nullptr, d_prob, d_rs8, kSigmoidHalfThreshold);
+        HIP_TRY(hipGetLastError());
+        for (int r = 0; r < prob->n_runs; ++r) {              // a head of a run is one piece on both sides
+            const ts2d_tiled_probabilities_run& rn = prob->runs[r];
+            const ProbStackSeg& ps = pl.pssegs[(size_t)rn.first_image];
+            const size_t run_plane = (size_t)ps.prob_stride;
+            for (int k = 0; k < K; ++k)
+                HIP_TRY(hipMemcpyAsync(rn.prob_f32 + (long long)k * rn.prob_head_stride, d_prob + ps.prob_off + (size_t)k * run_plane, run_plane * 4, hipMemcpyDeviceToHost, st));
+            for (int k = 0; rn.decided_u8 && k < (prob->mode == kProbMultilabel ? K : 1); ++k)
+                HIP_TRY(hipMemcpyAsync(rn.decided_u8 + (long long)k * rn.decided_head_stride, d_rs8 + ps.dec_off + (size_t)k * run_plane, run_plane, hipMemcpyDeviceToHost, st));
+        }
+    } else if (prob) {
+        float* d_prob = reinterpret_cast<float*>(b + pl.o_prob);
+        hipLaunchKernelGGL(sw_probabilities<ProbSeg>, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
                            reinterpret_cast<const ProbSeg*>(b + pl.o_tab + pl.tab_psegs), n_images, K, reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps),
                            prob->mode, class_order ? reinterpret_cast<const uint8_t*>(b + pl.o_tab + pl.tab_order) : nullptr, d_prob, d_rs8, kSigmoidHalfThreshold);
         HIP_TRY(hipGetLastError());
@@ -358,6 +375,59 @@ int ts2d_ensemble_predict_tiled_probabilities(ts2d_engine* const* engines, int n
                               mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, true, entry);
 }
 
+int ts2d_ensemble_predict_tiled_probabilities_stack(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, int n_images,
+                                                    const ts2d_tiled_probabilities_run* runs, int n_runs, int ph, int pw, int mirror_mask,
+                                                    const uint16_t* gaussian_f16, int full_batch, int mode, const uint8_t* class_order, int n_order) {
+    static const char* entry = "ts2d_ensemble_predict_tiled_probabilities_stack";
+    int todo = 0;
+    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    if (!todo) return TS2D_OK;
+    if (!runs || n_runs < 1) return fail(TS2D_ERR_INVALID, "%s: %d runs at a null pointer", entry, n_runs);
+    const int K = engines[0]->arch.num_classes;
+    TRY(check_prob_mode(entry, mode, K, class_order));
+    if (mode == kProbRegions && n_order != K) return fail(TS2D_ERR_INVALID, "%s: probabilities: %d class values for a model of %d heads", entry, n_order, K);
+    // the runs cover the images once, in order; every image gets the descriptor of the sibling entry: its run's geometry, its own slice of the outputs
+    std::vector<ts2d_tiled_probabilities> descs((size_t)n_images);
+    std::vector<ts2d_tiled_export> ex((size_t)n_images);
+    std::vector<int> run_of((size_t)n_images);
+    int next = 0;
+    for (int r = 0; r < n_runs; ++r) {
+        const ts2d_tiled_probabilities_run& rn = runs[r];
+        if (rn.n_slices < 1) return fail(TS2D_ERR_INVALID, "%s: run %d: probabilities: %d slices", entry, r, rn.n_slices);
+        if (rn.first_image > next)
+            return fail(TS2D_ERR_INVALID, "%s: run %d: probabilities: begins at image %d and leaves a gap behind image %d", entry, r, rn.first_image, next - 1);
+        if (rn.first_image < next)
+            return fail(TS2D_ERR_INVALID, "%s: run %d: probabilities: begins at image %d and overlaps the run before it, which ends at image %d", entry, r,
+                        rn.first_image, next - 1);
+        if (rn.n_slices > n_images - next)
+            return fail(TS2D_ERR_INVALID, "%s: run %d: probabilities: %d slices from image %d leave the call's %d images", entry, r, rn.n_slices, rn.first_image, n_images);
+        if (!rn.prob_f32) return fail(TS2D_ERR_INVALID, "%s: run %d: probabilities: the output is null", entry, r);
+        const bool extent = rn.full_h >= 1 && rn.full_w >= 1;         // (a bad one is refused below, with the image named, in the sibling's words)
+        const long long fplane = extent ? (long long)rn.full_h * rn.full_w : 0;
+        if (extent && rn.prob_head_stride < fplane * rn.n_slices)
+            return fail(TS2D_ERR_INVALID, "%s: run %d: probabilities: head stride %lld is below %d slices of %dx%d", entry, r, (long long)rn.prob_head_stride,
+                        rn.n_slices, rn.full_h, rn.full_w);
+        if (extent && rn.decided_u8 && mode == kProbMultilabel && rn.decided_head_stride < fplane * rn.n_slices)
+            return fail(TS2D_ERR_INVALID, "%s: run %d: probabilities: decided head stride %lld is below %d slices of %dx%d", entry, r,
+                        (long long)rn.decided_head_stride, rn.n_slices, rn.full_h, rn.full_w);
+        for (int s = 0; s < rn.n_slices; ++s) {
+            const int i = next + s;
+            if (images[i].Hp != images[next].Hp || images[i].Wp != images[next].Wp)
+                return fail(TS2D_ERR_INVALID, "%s: run %d: image %d: probabilities: the padded extent %dx%d differs from %dx%d of the run's first image", entry, r, i,
+                            images[i].Hp, images[i].Wp, images[next].Hp, images[next].Wp);
+            descs[i] = ts2d_tiled_probabilities{rn.src_y, rn.src_x, rn.src_h, rn.src_w, rn.out_h, rn.out_w, rn.full_h, rn.full_w, rn.box_y, rn.box_x,
+                                                rn.prob_f32 + s * fplane, rn.decided_u8 ? rn.decided_u8 + s * fplane : nullptr};
+            ex[i] = ts2d_tiled_export{rn.src_y, rn.src_x, rn.src_h, rn.src_w, rn.out_h, rn.out_w, reinterpret_cast<uint8_t*>(rn.prob_f32), nullptr};
+            run_of[i] = r;
+        }
+        next += rn.n_slices;
+    }
+    if (next != n_images) return fail(TS2D_ERR_INVALID, "%s: probabilities: the %d runs end at image %d and leave a gap to the call's %d images", entry, n_runs, next - 1, n_images);
+    const ProbCall prob{descs.data(), mode, runs, n_runs, run_of.data()};
+    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, mode == kProbRegions ? class_order : nullptr, &prob, n_images, ph, pw,
+                              mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, true, entry);
+}
+
 int ts2d_probabilities_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
                                    int full_h, int full_w, int box_y, int box_x, int mode, const uint8_t* class_order, float* prob_f32,
                                    uint8_t* decided_u8) {
@@ -391,7 +461,7 @@ int ts2d_probabilities_from_logits(int device, const uint16_t* logits_f16, int K
     if (!rtaps.empty()) HIP_TRY(hipMemcpy(d.as<char>(o_taps), rtaps.data(), rtaps.size() * sizeof(RsTap), hipMemcpyHostToDevice));
     if (regions) HIP_TRY(hipMemcpy(d.as<char>(o_order), class_order, (size_t)K, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_src), logits_f16, n_src * 2, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sw_probabilities, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(), d.as<const ProbSeg>(o_ps), 1, K,
+    hipLaunchKernelGGL(sw_probabilities<ProbSeg>, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(), d.as<const ProbSeg>(o_ps), 1, K,
                        d.as<const RsTap>(o_taps), mode, regions ? d.as<const uint8_t>(o_order) : nullptr, d.as<float>(o_prob),
                        decided_u8 ? d.as<uint8_t>(o_dec) : nullptr, kSigmoidHalfThreshold);
     HIP_TRY(hipGetLastError());

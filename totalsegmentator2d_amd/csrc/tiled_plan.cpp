@@ -42,8 +42,9 @@ int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d
     pl->any16 = F > 1;      // (the mean is taken over the half buffers)
     for (int i = 0; i < n_images; ++i) {
         const ts2d_tiled_image& im = images[i];
-        char pre[24] = "";
-        if (name_images) snprintf(pre, sizeof(pre), "image %d: ", i);
+        char pre[48] = "";
+        if (name_images && prob && prob->runs) snprintf(pre, sizeof(pre), "run %d: image %d: ", prob->run_of[i], i);
+        else if (name_images) snprintf(pre, sizeof(pre), "image %d: ", i);
         if (!im.image || !im.tile_y || !im.tile_x) return fail(TS2D_ERR_INVALID, "%snull image or tile pointer", pre);
         if (!exports && !im.logits_f16 && !im.seg_u8) return fail(TS2D_ERR_INVALID, "%sboth outputs are null", pre);
         if (im.n_tiles < 1 || im.n_tiles > (1 << 20) || im.Hp < 1 || im.Wp < 1 || ph > im.Hp || pw > im.Wp)
@@ -129,11 +130,35 @@ int pack_rows(int F, int C, int K, const ts2d_tiled_image* images, int n_images,
 // The export: one segment per image (its half logits are segs' out_off), the taps of its rows then of its columns.
 // rs_elems: elements of the resampled outputs.
 // `prob`: a probabilities call - the lanes of a segment walk the full extent, and beside every RsSeg goes a ProbSeg with the image's places
-// in the float outputs (prob_elems) and in the decided maps (rs_elems)
+// in the float outputs (prob_elems) and in the decided maps (rs_elems); with `prob->runs` a ProbStackSeg, the places being those of the image's slice in its run
 int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, bool regions, const ProbCall* prob,
                 int n_images, const char* entry, SwPlan* pl, std::vector<RsTap>* rtaps, long long* rs_elems) {
     long long oo = 0;
-    for (int i = 0; i < n_images; ++i) {
+    // runs: the outputs of a run are [K][n_slices][full_h][full_w] (one contiguous piece per head), its taps are planned with its first slice
+    // and every other slice's segment is that one at its own half planes and blocks
+    for (int r = 0; prob && r < prob->n_runs; ++r) {
+        const ts2d_tiled_probabilities_run& rn = prob->runs[r];
+        const int full_hw[2] = {rn.full_h, rn.full_w};
+        const long long fplane = (long long)rn.full_h * rn.full_w, run_plane = fplane * rn.n_slices;
+        const size_t first = pl->rsegs.size();
+        const long long oo_first = oo;
+        for (int s = 0; s < rn.n_slices; ++s) {
+            const int i = rn.first_image + s;
+            pl->pssegs.push_back(ProbStackSeg{pl->prob_elems + s * fplane, *rs_elems + s * fplane, run_plane, run_plane, rn.full_h, rn.full_w, rn.box_y, rn.box_x});
+            if (s == 0) {
+                rs_plan_segment(true, K, images[i].Hp, images[i].Wp, exports[i], oo, &pl->rsegs, rtaps, &pl->rs_blocks, nullptr, full_hw);
+            } else {
+                RsSeg rs = pl->rsegs[first];
+                rs.src_off += oo - oo_first; rs.block0 = (unsigned)pl->rs_blocks;
+                pl->rsegs.push_back(rs);
+                pl->rs_blocks += blocks_of((long long)rn.full_h * ((rn.full_w + 3) / 4));
+            }
+            oo += (long long)align_up((size_t)K * images[i].Hp * images[i].Wp, 256);
+        }
+        pl->prob_elems += (long long)align_up((size_t)K * run_plane, 256);
+        *rs_elems += (long long)align_up((size_t)(prob->mode == kProbMultilabel ? K : 1) * run_plane, 256);
+    }
+    for (int i = 0; i < n_images && !(prob && prob->runs); ++i) {
         if (prob) {
             const ts2d_tiled_probabilities& pd = prob->descs[i];
             const int full_hw[2] = {pd.full_h, pd.full_w};
@@ -196,8 +221,9 @@ int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, cons
     pl->tab_rtaps = pl->tab_rsegs + pl->rsegs.size() * sizeof(RsSeg);
     pl->tab_order = pl->tab_rtaps + rtaps.size() * sizeof(RsTap);
     pl->tab_psegs = align_up(pl->tab_order + (regions ? (size_t)K : 0), 8);
-    pl->tab.resize(prob ? pl->tab_psegs + pl->psegs.size() * sizeof(ProbSeg) : pl->tab_order + (regions ? (size_t)K : 0));
-    if (prob) memcpy(pl->tab.data() + pl->tab_psegs, pl->psegs.data(), pl->psegs.size() * sizeof(ProbSeg));
+    pl->tab.resize(prob ? pl->tab_psegs + pl->psegs.size() * sizeof(ProbSeg) + pl->pssegs.size() * sizeof(ProbStackSeg) : pl->tab_order + (regions ? (size_t)K : 0));
+    if (prob && prob->runs) memcpy(pl->tab.data() + pl->tab_psegs, pl->pssegs.data(), pl->pssegs.size() * sizeof(ProbStackSeg));
+    else if (prob) memcpy(pl->tab.data() + pl->tab_psegs, pl->psegs.data(), pl->psegs.size() * sizeof(ProbSeg));
     if (regions) memcpy(pl->tab.data() + pl->tab_order, class_order, (size_t)K);      // (K == n_order: the entry has checked it)
     memcpy(pl->tab.data(), pl->segs.data(), pl->tab_segs);
     if (exports) {

@@ -272,7 +272,7 @@ class Engine:
         return outs
 
     def _tiled_args(self, what, images, tiles, exports, mirror_axes, gaussian, want_seg, want_f32, want_logits, want_padded_seg,
-                    labelmap: bool = False, prob_mode: Optional[int] = None):
+                    labelmap: bool = False, prob_mode: Optional[int] = None, runs: bool = False):
         """Argument preparation of every tiled call (`what` names the calling method in a message): the ``TiledImage`` array, the
         ``TiledExport`` array (None without ``exports``: no resample-back), the mirror mask, the address of the half gaussian (or None),
         the arrays all of these point into - they must outlive the call - and the output lists ``(seg, f32, logits, padded_seg)`` the
@@ -281,14 +281,15 @@ class Engine:
         ``image i: `` and everything but the channel count is left to the library (or to the unpacking of the shape) to refuse.
         ``prob_mode`` (a ``_lib.PROB_*``): the descriptors are ``TiledProbabilities`` from ``exports`` of ten numbers (the six, then
         ``full_h, full_w, box_y, box_x``); ``f32`` holds the float32 probabilities [K,full_h,full_w] and ``seg`` the decided uint8 map
-        of the full extent ([K,full_h,full_w] multilabel, else [full_h,full_w])."""
+        of the full extent ([K,full_h,full_w] multilabel, else [full_h,full_w]).  ``runs``: the outputs are described apart from the
+        images (:func:`predict_tiled_probabilities_stack_ensemble`): no ``exports``, and no output of these lists need be asked for."""
         one = what is None
         if len(images) != len(tiles) or (exports is not None and len(exports) != len(images)):
             raise RuntimeError(f"{len(images)} images but {len(tiles)} tile lists" + ("" if exports is None else f" and {len(exports)} exports"))
         if exports is None:
             if want_seg or want_f32:
                 raise RuntimeError(f"{what}: the resampled outputs need exports")
-            if not (want_logits or want_padded_seg or one):
+            if not (want_logits or want_padded_seg or one or runs):
                 raise RuntimeError(f"{what}: neither logits nor segmentation requested")
         elif not (want_seg or want_f32):
             raise RuntimeError(f"{what}: neither the resampled segmentation nor the resampled logits requested")
@@ -576,6 +577,54 @@ def predict_tiled_probabilities_ensemble(engines, images, patch, tiles, rects, m
     _read_tiled_inf(engines, desc, len(images), engine_flags=True)
     del keep
     return outs[1], outs[0], outs[2]
+
+
+def has_stack_probabilities() -> bool:
+    """Does the loaded library have the probabilities entry for slice stacks?  (One built before it still loads: the callers keep the host route.)"""
+    return hasattr(_lib.load(), 'ts2d_ensemble_predict_tiled_probabilities_stack')
+
+
+def predict_tiled_probabilities_stack_ensemble(engines, images, patch, tiles, runs, mode, class_order=None, mirror_axes=None,
+                                               gaussian: Optional[np.ndarray] = None, want_logits: bool = False, full_batch: bool = True):
+    """:func:`predict_tiled_probabilities_ensemble` for SLICE STACKS (C-ABI ts2d_ensemble_predict_tiled_probabilities_stack): the outputs are
+    described per RUN - consecutive images that are consecutive slices of one volume and share one geometry - and are written IN PLACE into
+    arrays of the caller's.  runs: one ``(first_image, n_slices, rect, prob, decided)`` each, covering the images once and in order;
+    ``rect`` the ten numbers of that function; ``prob`` a float32 view [K, n_slices, full_h, full_w] of the caller's [K, Z0, full_h, full_w]
+    (``volume[:, z:z + n_slices]``: any stride between the heads, dense below it); ``decided`` the like uint8 view, [K, n_slices, ...] of a
+    multilabel model and [n_slices, ...] otherwise, or None.  Every slice gets the bytes the per-image function gives it.  Returns the list
+    of float16 [K,Hp,Wp] logits (None unless ``want_logits``).  Sets the inf flags as :func:`predict_tiled_export_ensemble` does."""
+    what = 'predict_tiled_probabilities_stack_ensemble'
+    engines = list(engines)
+    if not engines:
+        raise RuntimeError(f"{what}: no engines")
+    code, order = _prob_mode(mode, class_order, what)
+    fn = _need_probabilities(engines[0].lib, 'ts2d_ensemble_predict_tiled_probabilities_stack')
+    desc, _, mask, g, keep, outs = engines[0]._tiled_args(what, images, tiles, None, mirror_axes, gaussian, False, False, want_logits, False, runs=True)
+    K = engines[0].arch.num_classes
+    rd = (_lib.TiledProbabilitiesRun * max(len(runs), 1))()
+    for r, (first, n, rect, prob, dec) in enumerate(runs):
+        x = rd[r]
+        (x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w, x.full_h, x.full_w, x.box_y, x.box_x) = (int(v) for v in rect)
+        x.first_image, x.n_slices = int(first), int(n)
+        for name, a, dt, heads in (('prob', prob, np.float32, True), ('decided', dec, np.uint8, code == _lib.PROB_MULTILABEL)):
+            if a is None and name == 'decided':
+                continue
+            tail = (int(n), max(x.full_h, 0), max(x.full_w, 0))              # (a bad extent is the library's to reject, by name)
+            if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != ((K,) if heads else ()) + tail or not a.flags.writeable \
+                    or not a[0 if heads else slice(None)].flags.c_contiguous or (heads and a.strides[0] % a.itemsize):
+                raise RuntimeError(f"{what}: run {r}: {name} must be a writeable {np.dtype(dt).name} view {((K,) if heads else ()) + tail}, dense below the heads")
+            stride = a.strides[0] // a.itemsize if heads else 0
+            if name == 'prob':
+                x.prob_f32, x.prob_head_stride = a.ctypes.data, stride
+            else:
+                x.decided_u8, x.decided_head_stride = a.ctypes.data, stride
+            keep.append(a)
+    handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
+    _lib.check(fn(handles, len(engines), desc, len(images), rd, len(runs), int(patch[0]), int(patch[1]), mask, g, int(bool(full_batch)), code,
+                  None if order is None else order.ctypes.data, 0 if order is None else int(order.size)), 'ts2d_ensemble_predict_tiled_probabilities_stack')
+    _read_tiled_inf(engines, desc, len(images), engine_flags=True)
+    del keep
+    return outs[2]
 
 
 def probabilities_from_logits(logits_f16: np.ndarray, rect, out_hw, full_hw, box_yx, mode, class_order=None, want_decided: bool = True,

@@ -123,6 +123,19 @@ def probabilities_statement(logits_f16, rect, out_hw, full_hw, box_yx, mode) -> 
     return fill_probabilities(inference_nonlinearity(lg, softmax), full_hw, (slice(by, by + out_hw[0]), slice(bx, bx + out_hw[1])), softmax)
 
 
+def stack_probabilities_statement(logits_f16, rect, out_hw, full_shape, box, mode) -> np.ndarray:
+    """The numpy statement of the device's probabilities of a SLICE STACK (C-ABI ts2d_ensemble_predict_tiled_probabilities_stack under
+    HIPnnUNetPredictor.predict_stack_probabilities_from_preprocessed_data): ``logits_f16`` [K, Z, Hp, Wp], :func:`probabilities_statement`
+    of every slice - ``rect``, ``out_hw`` and the in-plane part of ``full_shape`` = (Z0, H0, W0) and ``box`` = (z0, y0, x0) are the same
+    for all of them - placed at slice ``z0 + z`` of a float32 [K, Z0, H0, W0] whose other slices hold the fill of
+    :func:`fill_probabilities`.  Bit for bit the host route of a stack (``convert_...(return_probabilities=True)``, which resamples per
+    slice: tests/test_stack_probabilities_cpu.py)."""
+    lg = np.asarray(logits_f16)
+    Z0, z0 = int(full_shape[0]), int(box[0])
+    planes = np.stack([probabilities_statement(lg[:, z], rect, out_hw, full_shape[1:], box[1:], mode) for z in range(lg.shape[1])], axis=1)
+    return fill_probabilities(planes, (Z0,) + planes.shape[2:], (slice(z0, z0 + lg.shape[1]), slice(None), slice(None)), mode == 'labelmap')
+
+
 def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties: dict, multilabel: bool = True,
                                                                 transpose_backward=(0, 1, 2), regions=None,
                                                                 return_probabilities: bool = False, probabilities=None):

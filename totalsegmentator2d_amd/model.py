@@ -49,6 +49,7 @@ class HIPModel:
         self.device_input_stack = True   # a stack [C, Z, H, W] under a 2-D plan: crop box over three axes, unmasked normalisation with the statistics of the whole volume (and the per-slice resample) on device-resident planes; numpy's bits (preprocess.crop_box3_statement and the *_f32_statement of the flattened channel)
         self.device_input_stack_masked = True   # ... and a stack whose plan has use_mask_for_norm on a z-score channel (the MR plans): the 3-D hole filling of the non-zero mask, the statistics of the masked samples and the normalisation inside the mask on those planes; numpy's and scipy's bits (preprocess.fill_holes_sweeps_statement, masked_zscore_stack_statement)
         self.device_stack = True         # ... and its decided map from the device, every slice one image of the convention's own entry (_run; needs that convention's switch too); the host route's bytes
+        self.device_stack_probabilities = True   # ... and, with save_probabilities, its probabilities: every slice through the kernel of device_probabilities, written in place into ONE float32 [K, Z0, H0, W0] (_run; needs device_stack and the convention's switch, and an untransposed plan); the host route's segmentation bytes, its probabilities to a few float32 units
         self._discover()
 
     # ------------------------------------------------------------------ configuration (reference wrapper.py:113-162)
@@ -276,6 +277,26 @@ class HIPModel:
             out[i] = lg
         return out
 
+    def _predict_stack_probabilities(self, group, batched: bool):
+        """Stage 2 of :meth:`_run` for stacks that ask for probabilities: per case ``(decided map, probabilities)`` of the predictor's stack
+        probabilities method - the extent before resampling, the extent before cropping and the origin of the three-axis crop box go with each
+        case - or, where it answers None, the logits (:meth:`_predict`): the export then takes the host route."""
+        p = self._predictor
+        name = 'predict_stack_probabilities_from_preprocessed_data'
+        datas = [t[3] for t in group]
+        outs = [tuple(t[4].get('shape_after_cropping_and_before_resampling', np.asarray(t[3]).shape[1:])) for t in group]
+        fulls = [tuple(t[4]['shape_before_cropping']) for t in group]
+        boxes = [tuple(int(b[0]) for b in t[4]['bbox_used_for_cropping']) for t in group]
+        if batched:
+            out = getattr(p, name + '_batch')(datas, out_shapes=outs, full_shapes=fulls, boxes=boxes)
+            out = list(out) if out is not None else [None] * len(group)
+        else:
+            out = [getattr(p, name)(d, out_shape=o, full_shape=f, box=b) for d, o, f, b in zip(datas, outs, fulls, boxes)]
+        rest = [i for i, o in enumerate(out) if o is None]
+        for i, lg in zip(rest, self._predict([datas[i] for i in rest], False, batched) if rest else []):
+            out[i] = lg
+        return out
+
     def _run(self, inputs: dict, result_dir, override, batched: bool, stamps: dict, save_probabilities: bool = False) -> dict:
         """The reference worker's four stages (``prediction_worker.py:177-242``) over ``inputs``: output file, preprocessing of every
         input, prediction (:meth:`_predict`, per group of inputs that share the fast-path decision: at most two groups), export of each.
@@ -350,10 +371,16 @@ class HIPModel:
             return tgt if (can_export or can_lm or can_prob) and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] == 1 else False
         # a stack - a 3-D volume under a 2-D plan, more than one slice left after cropping - gets the decided map of its convention from the
         # device too, every slice one image of the same entries (the predictor's stack methods); its slice count never changes.  Only a predictor
-        # that has the methods takes this route, and only with the convention's own switch on; probabilities of a stack keep the host route
-        st_fn = getattr(p, 'predict_stack_from_preprocessed_data' + ('_batch' if batched else ''), None)
-        can_stack = getattr(self, 'device_stack', False) and not save_probabilities and st_fn is not None \
+        # that has the methods takes this route, and only with the convention's own switch on.  With save_probabilities the stack takes the
+        # predictor's stack probabilities methods instead - the kernel of can_prob per slice, written in place into one [K, Z0, H0, W0] - under a
+        # switch of their own, and only for an untransposed plan (the slice axis must be the volume's first)
+        name = 'predict_stack_probabilities_from_preprocessed_data' if save_probabilities else 'predict_stack_from_preprocessed_data'
+        st_fn = getattr(p, name + ('_batch' if batched else ''), None)
+        can_stack = getattr(self, 'device_stack', False) and st_fn is not None \
             and len(p.configuration_manager.patch_size) == 2 and bool(self.device_threshold if multilabel else getattr(self, switch, False))
+        if save_probabilities:
+            can_stack = can_stack and getattr(self, 'device_stack_probabilities', False) \
+                and list(getattr(p.plans_manager, 'transpose_forward', [0, 1, 2])) == [0, 1, 2]
 
         def is_stack(t):
             shape = tuple(np.asarray(t[3]).shape[1:])
@@ -366,7 +393,7 @@ class HIPModel:
                 continue
             try:
                 if group is stacks:
-                    out = self._predict_stacks(group, batched)
+                    out = (self._predict_stack_probabilities if save_probabilities else self._predict_stacks)(group, batched)
                 elif use_seg and can_prob:
                     out = self._predict_probabilities(group, batched)
                 else:

@@ -488,16 +488,19 @@ class HIPnnUNetPredictor:
             rects += [(revert[2].start, revert[3].start, H, W, int(hw[0]), int(hw[1]))] * data.shape[1]
         return rects
 
-    def _stack_calls(self, images, rects, multilabel: bool):
+    def _stack_calls(self, images, rects, multilabel: bool, fulls=None):
         """The images of the stack batch method split into engine calls, in order, by a byte budget (``stack_call_bytes``) on what the header's
         scratch formula sums over the images of a call: the inputs C x Hp x Wp x 4, the half outputs folds x K x Hp x Wp x 2, the export's outputs
         out_h x out_w (x K for a multilabel model).  At least one image per call.  Where the calls split does not show in the bytes: inside a
-        full-batch call an image's result does not depend on its call-mates."""
+        full-batch call an image's result does not depend on its call-mates.  ``fulls`` (the probabilities of stacks): one ``(full_h, full_w)`` per
+        image - its outputs are then the planes of that extent, K x full_h x full_w x 4 of probabilities and the decided planes beside them."""
         K, F, budget = self.arch.num_classes, max(1, len(self.engines)), int(self.stack_call_bytes)
         calls, used = [[]], 0
         for j, (image, r) in enumerate(zip(images, rects)):
             C, Hp, Wp = image.shape
             need = C * Hp * Wp * 4 + F * K * Hp * Wp * 2 + r[4] * r[5] * (K if multilabel else 1)
+            if fulls is not None:
+                need = C * Hp * Wp * 4 + F * K * Hp * Wp * 2 + fulls[j][0] * fulls[j][1] * (K * 4 + (K if multilabel else 1))
             if calls[-1] and used + need > budget:
                 calls.append([])
                 used = 0
@@ -571,6 +574,116 @@ class HIPnnUNetPredictor:
             return []
         hws = [self._stack_extent(s, d) for s, d in zip(out_shapes if out_shapes is not None else [None] * len(datas), datas)]
         return None if any(hw is False for hw in hws) else self._stack_window(datas, hws, full_batch=True)
+
+    # ------------------------------------------------------------------ ... and their probabilities: one strided volume per stack
+    @staticmethod
+    def _stack_place(hw, data, full_shape, box):
+        """``full_shape`` ((Z0, H0, W0); None: the output's own extent) and ``box`` ((z0, y0, x0); None: the origin) of the stack probabilities
+        methods -> ``((Z0, H0, W0), (z0, y0, x0))``, or None where the [Z, h, w] output does not lie inside that extent at that place."""
+        out = (int(data.shape[1]),) + tuple(int(v) for v in hw)
+        full = out if full_shape is None else tuple(int(v) for v in full_shape)
+        at = (0, 0, 0) if box is None else tuple(int(v) for v in box)
+        if len(full) != 3 or len(at) != 3 or min(at) < 0 or any(o + a > f for o, a, f in zip(out, at, full)):
+            return None
+        return full, at
+
+    @staticmethod
+    def _stack_runs(grp, owner, first_image, rects, places, probs, decs, multilabel: bool):
+        """The run descriptors of ONE engine call of the stack probabilities (``engine.predict_tiled_probabilities_stack_ensemble``).  ``grp``: the
+        call's images, consecutive indices into the image list; ``owner[j]`` the input of image j, ``first_image[i]`` the index of input i's first
+        slice.  Consecutive images of one input are one run ``(first image in the call, n_slices, the ten numbers, probabilities view, decided
+        view)``: the views are slices ``[z0 + s, z0 + s + n_slices)`` along axis 1 of that input's arrays - [K, Z0, H0, W0] float32 and
+        [K or 1, Z0, H0, W0] uint8 (the one plane per slice of a non-multilabel model is passed without its leading axis) - so a volume that a call
+        boundary splits contributes one run to each call, at different slice offsets of the same arrays."""
+        runs, a = [], 0
+        while a < len(grp):
+            i = owner[grp[a]]
+            b = a
+            while b < len(grp) and owner[grp[b]] == i:
+                b += 1
+            (full, at), n = places[i], b - a
+            z = at[0] + grp[a] - first_image[i]
+            dec = decs[i][:, z:z + n] if multilabel else decs[i][0, z:z + n]
+            runs.append((a, n, tuple(rects[grp[a]]) + tuple(full[1:]) + tuple(at[1:]), probs[i][:, z:z + n], dec))
+            a = b
+        return runs
+
+    def _stack_probabilities_window(self, datas, hws, places, full_batch: bool):
+        """:meth:`_stack_window` with the export's probabilities: per input ``(decided uint8 [1 or K, Z0, H0, W0], float32 [K, Z0, H0, W0])``, both
+        allocated ONCE in their final layout.  The slabs outside the z range of the box are filled here with upstream's fill (0; 1 in head 0 of a
+        label-map model); every slice inside it - its in-plane fill included - is written in place by the engine, a run of slices per call and input
+        (C-ABI ts2d_ensemble_predict_tiled_probabilities_stack).  ``full_batch`` as in :meth:`_stack_window`."""
+        from .engine import predict_tiled_probabilities_stack_ensemble
+        from .labels import label_convention
+        patch = tuple(self.configuration_manager.patch_size)
+        images, tiles, owner, reverts, _ = self._pad_and_tile(datas, patch, single_slice=False)
+        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
+            raise AssertionError('mirror_axes does not match the dimension of the input!')
+        g = sw.compute_gaussian(patch) if self.use_gaussian else None
+        axes = self.allowed_mirroring_axes if self.use_mirroring else None
+        rects = self._stack_rects(datas, reverts, hws)
+        kind = label_convention(self.dataset_json).kind
+        multilabel = kind == 'multilabel'
+        mode = 'multilabel' if multilabel else 'regions' if 'regions' in self._decision() else 'labelmap'
+        K = self.arch.num_classes
+        probs, decs, first_image = [], [], []
+        for data, (full, at) in zip(datas, places):
+            first_image.append(sum(d.shape[1] for d in datas[:len(first_image)]))
+            prob, dec = np.empty((K,) + full, dtype=np.float32), np.empty((K if multilabel else 1,) + full, dtype=np.uint8)
+            for slab in (slice(0, at[0]), slice(at[0] + data.shape[1], full[0])):
+                prob[:, slab] = 0
+                if mode == 'labelmap':
+                    prob[0, slab] = 1
+                dec[:, slab] = 0
+            probs.append(prob)
+            decs.append(dec)
+        fulls = [places[i][0][1:] for i in owner]
+        inf = []
+        for grp in (self._stack_calls(images, rects, multilabel, fulls) if full_batch else [[j] for j in range(len(images))]):
+            runs = self._stack_runs(grp, owner, first_image, rects, places, probs, decs, multilabel)
+            predict_tiled_probabilities_stack_ensemble(self.engines, [images[j] for j in grp], patch, [tiles[j] for j in grp], runs, mode,
+                                                       self._decision().get('regions'), axes, g, full_batch=full_batch)
+            inf += self.engines[0].last_tiled_inf_per_image
+        self._raise_on_inf(inf, owner, full_batch)
+        return list(zip(decs, probs))
+
+    def predict_stack_probabilities_from_preprocessed_data(self, data, out_shape=None, full_shape=None, box=None):
+        """:meth:`predict_stack_from_preprocessed_data` with the export's PROBABILITIES (``save_probabilities`` for a 3-D volume under a 2-D plan):
+        ``data`` [C,Z,H,W], ``out_shape`` ``(Z, h, w)`` as there, ``full_shape`` ``(Z0, H0, W0)`` the case's ``shape_before_cropping`` and ``box``
+        ``(z0, y0, x0)`` where the crop box begins in it (None, None: the output is the whole).  Returns ``(decided uint8, float32 [K,Z0,H0,W0])`` -
+        the decided map [1,Z0,H0,W0] of a label-map or region-based model, [K,Z0,H0,W0] of a multilabel one, 0 outside the box and inside it the
+        bytes of :meth:`predict_stack_from_preprocessed_data`; the probabilities of :meth:`predict_probabilities_from_preprocessed_data` per slice
+        with upstream's fill (0; 1 in head 0 of a label-map model) everywhere else, the slices outside the box along z included.  One engine call
+        per slice with the size-dependent dispatch.  None where the stack methods or the probabilities methods return None: a predictor without
+        engines, a 3-D plan, a bad shape, a box that leaves the full extent, a library built before the entry."""
+        out = self._stack_probabilities([data], None if out_shape is None else [out_shape], [full_shape], [box], full_batch=False)
+        return None if out is None else out[0]
+
+    def predict_stack_probabilities_from_preprocessed_data_batch(self, list_of_data, out_shapes=None, full_shapes=None, boxes=None):
+        """:meth:`predict_stack_probabilities_from_preprocessed_data` for a list of inputs - stacks and single-slice cases may be mixed: the slices of
+        all inputs packed into full-batch engine calls by ``stack_call_bytes`` (:meth:`_stack_calls`; a call boundary may fall inside a volume), so
+        that the bytes depend neither on that budget nor on the batch-mates: every slice has those of
+        :meth:`predict_probabilities_from_preprocessed_data_batch`.  One entry (or None) per input in each list.  None where the single-case
+        method returns None for some input."""
+        return self._stack_probabilities(list_of_data, out_shapes, full_shapes, boxes, full_batch=True)
+
+    def _stack_probabilities(self, list_of_data, out_shapes, full_shapes, boxes, full_batch: bool):
+        from .engine import has_stack_probabilities
+        datas = [_to_numpy(d) for d in list_of_data]
+        n = len(datas)
+        if not self._serves_stacks() or any(d.ndim != 4 for d in datas) or any(v is not None and len(v) != n for v in (out_shapes, full_shapes, boxes)):
+            return None
+        if not has_stack_probabilities():
+            return None
+        if not datas:
+            return []
+        hws = [self._stack_extent(s, d) for s, d in zip(out_shapes if out_shapes is not None else [None] * n, datas)]
+        if any(hw is False for hw in hws):
+            return None
+        places = [self._stack_place(hw, d, f, b) for hw, d, f, b in zip(hws, datas, full_shapes or [None] * n, boxes or [None] * n)]
+        if any(pl is None for pl in places):
+            return None
+        return self._stack_probabilities_window(datas, hws, places, full_batch)
 
     def predict_logits_from_preprocessed_data(self, data):
         """Fold ensemble (upstream: sum over ``list_of_parameters`` then ``/= n``).  Accepts numpy or torch [C,1,H,W];
