@@ -62,7 +62,17 @@ typedef struct {
 #define TS2D_PRECISION_F32_SPLIT_F16X3 1
 /*   TS2D_PRECISION_F16  "mixed fp16" (BASELINE configs 3 and 5): activations stored as fp16 in HBM (half the traffic), weights
  *       rounded to fp16, ONE fp16 MFMA product per MAC, fp32 accumulation and fp32 InstanceNorm statistics; logits are
- *       still returned as fp32.  NOT within the fp32 parity tolerance (logit error ~1e-2); selected explicitly. */
+ *       still returned as fp32.  NOT within the fp32 parity tolerance (logit error ~1e-2); selected explicitly.
+ *   Residual blocks under TS2D_PRECISION_F16 (ts2d_engine_create_residual; opt-in: option "resf16").  h(.) rounds to IEEE half and back,
+ *   act16(y) = max(y, h(y * h(slope))) for a half y - what every 16-bit consumer does at load time.
+ *     stem, conv1, decoder blocks: as every plain block of the mode (the stem's weights are not rounded, like the first block of a plain
+ *       net); the operand the next op multiplies is a = act16(h(scale * stored + shift)).
+ *     conv2: stored y2 = h(conv(a, h(w)) + b); statistics in fp32 over the stored values; n2 = fma(scale, y2, shift) stays fp32 in the join.
+ *     residual r, fp32: the identity skip r = a (the half conv1 multiplies); a pooled skip the fp32 sum of the window's a in row-major
+ *       order, times 1 / n; a projection p = h(conv1x1(h(pool(a)), h(w))) (no bias), statistics in fp32 over the stored p,
+ *       r = fma(scale_p, p, shift_p), not rounded.
+ *     join: t = h(n2 + r) - ONE rounding, on the store - kept as half with scale 1 / shift 0, so that every consumer's load gives act16(t).
+ *     ts2d_engine_debug_tensor shows the storage view of a join as of every tensor: leaky_relu(t) in fp32. */
 #define TS2D_PRECISION_F16 2
 
 typedef struct ts2d_engine ts2d_engine;
@@ -98,7 +108,8 @@ typedef struct {
  *   ...skip.{i}.{conv.weight [Cout, Cin, 1, 1], norm.weight, norm.bias} (i = 1 behind an AvgPool2d, else 0);
  *   then the decoder and the head exactly as for ts2d_engine_create.
  * Every entry that takes an engine takes this one.  TS2D_PRECISION_F32_SPLIT_F16X3 and TS2D_PRECISION_F32_EXACT are supported;
- * ts2d_engine_set_precision(e, TS2D_PRECISION_F16) returns TS2D_ERR_INVALID and leaves the mode unchanged.
+ * ts2d_engine_set_precision(e, TS2D_PRECISION_F16) returns TS2D_ERR_INVALID and leaves the mode unchanged unless the option "resf16" is
+ * set on the handle (ts2d_engine_set_option; the contract of a residual block in that mode: TS2D_PRECISION_F16 above).
  * ts2d_engine_debug_tensor names: "stem", "enc{s}.b{b}.c1", "enc{s}.b{b}.c2" and "enc{s}.b{b}.proj" (normalised, NOT activated - as the
  * join reads them) and "enc{s}.b{b}" (the block's output); the decoder's names are unchanged. */
 int ts2d_engine_create_residual(const ts2d_arch_desc* arch, const ts2d_residual_desc* residual, const float* weights, size_t n_floats,
@@ -127,6 +138,10 @@ int ts2d_engine_set_precision(ts2d_engine* e, int mode);
  *   (deterministic two-phase reduction) and a composed decoder entry runs as transposed conv + conv.  With "sbk" on (the default) a
  *   slice's result is bit-identical between two batches only if both take the same path (e.g. any two batches >= 32 of the canonical
  *   net); across paths it agrees to fp32 summation order (3e-5 on the logits).  The same batch always reproduces its bits.
+ *   "resf16" (default 0) the 16-bit mode on a residual-encoder engine: with 1, ts2d_engine_set_precision(e, TS2D_PRECISION_F16) succeeds there
+ *   and the residual blocks run their fp16-storage kernels (res_join<_Float16>, pool_proj1x1_h).  Cleared while such an engine is in the
+ *   16-bit mode, the next forward fails (the mode is never changed silently).  No effect on a plain engine.  Not test scaffolding: the opt-in
+ *   of a mode whose results differ from the fp32 modes'.
  * Most of these have had one measured winner for rounds ("q", "res", "one", "s2v2", "up0" ...): they are test scaffolding -
  * the way the parity suite reaches the second kernel of an op - not tuning knobs of the product.
  * Unknown names and out-of-range values return TS2D_ERR_INVALID.  The reference has no counterpart (one code path through torch:

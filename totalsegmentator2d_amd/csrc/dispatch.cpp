@@ -240,9 +240,11 @@ Choice pick_kernel(const ts2d_engine* e, size_t oi, int B, int H, int W, bool fu
     Choice c;
     const bool f16 = e->precision == TS2D_PRECISION_F16, exact = e->precision == TS2D_PRECISION_F32_EXACT;
     if (op.type == OP_PROJ || op.type == OP_JOIN) {
-        // Residual blocks (kernels_resblock.h), fp32 storage only: the 16-bit contract of a residual block is not defined (K_NONE; ts2d_engine_set_precision
-        // refuses the mode on such an engine before a forward gets here).  Per-pixel work: no pixel tiling, nothing that depends on B or on an option.
-        if (f16) return c;
+        // Residual blocks (kernels_resblock.h).  The 16-bit mode is opt-in (option "resf16"; without it K_NONE: ts2d_engine_set_precision refuses the
+        // mode on such an engine before a forward gets here, and a forward after the option was cleared fails).  Per-pixel work: no pixel tiling,
+        // nothing that depends on B or on another option.
+        if (f16 && !e->use_resf16) return c;
+        c.half = f16;
         c.k = op.type == OP_PROJ ? K_PROJ : K_JOIN;
         c.bn = op.cout % 64 == 0 ? 64 : 32;
         if (op.type == OP_PROJ) {       // tiles of 128 rows of the batch's pixels; partial statistics per tile where an image is a whole number of them
@@ -412,8 +414,8 @@ const char* kernel_name(const Op& op, const Choice& c) {
     case K_UPC_H: return b64 ? "conv3x3_upc_h<64>" : "conv3x3_upc_h<32>";
     case K_UPC_H2: return "conv3x3_upc_h2";
     case K_HEAD_MFMA: case K_HEAD_1X1: return "head";
-    case K_PROJ: return "pool_proj1x1";
-    case K_JOIN: return "res_join";
+    case K_PROJ: return c.half ? "pool_proj1x1_h" : "pool_proj1x1";
+    case K_JOIN: return c.half ? "res_join_h" : "res_join";
     }
     return "";
 }

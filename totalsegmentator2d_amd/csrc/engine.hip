@@ -364,7 +364,7 @@ int launch_proj(ts2d_engine* e, size_t oi, const Choice& c, const Run& r) {
     const Op& op = e->ops[oi];
     const Tensor& src = e->tensors[op.src];
     ProjArgs pa{};
-    pa.src = src.data; pa.sc = src.scale; pa.sh = src.shift; pa.w = e->d_weights + op.dev_w; pa.dst = e->tensors[op.dst].data;
+    pa.src = src.data; pa.sc = src.scale; pa.sh = src.shift; pa.w = e->d_weights + op.dev_w; pa.wh = e->d_weights + op.dev_wh; pa.dst = e->tensors[op.dst].data;
     pa.part = c.fused_stats ? e->d_part : nullptr;
     pa.Cin = src.C; pa.Cout = op.cout; pa.sy = op.sy; pa.sx = op.sx;
     pa.Wt = r.W >> op.lx; pa.HW = (r.H >> op.ly) * pa.Wt; pa.Win = r.W >> src.lx; pa.M = r.B * pa.HW;
@@ -374,11 +374,13 @@ int launch_proj(ts2d_engine* e, size_t oi, const Choice& c, const Run& r) {
     if (c.fused_stats && (pa.HW % kProjBM || c.g.tiles_x != pa.HW / kProjBM))
         return fail(TS2D_ERR_INVALID, "internal: op %s: partial statistics on tiles that span images", op.name.c_str());
     const dim3 grid((unsigned)((pa.M + kProjBM - 1) / kProjBM), op.cout / c.bn), block(256);
-    HIP_TRY(c.bn == 64 ? launch_kernel<pool_proj1x1<64>>(grid, block, 0, r.st, pa) : launch_kernel<pool_proj1x1<32>>(grid, block, 0, r.st, pa));
+    if (c.half != r.f16) return fail(TS2D_ERR_INVALID, "internal: op %s: the plan's storage is not the run's", op.name.c_str());
+    if (r.f16) HIP_TRY(c.bn == 64 ? launch_kernel<pool_proj1x1_h<64>>(grid, block, 0, r.st, pa) : launch_kernel<pool_proj1x1_h<32>>(grid, block, 0, r.st, pa));
+    else HIP_TRY(c.bn == 64 ? launch_kernel<pool_proj1x1<64>>(grid, block, 0, r.st, pa) : launch_kernel<pool_proj1x1<32>>(grid, block, 0, r.st, pa));
     return TS2D_OK;
 }
 
-int launch_join(ts2d_engine* e, size_t oi, const Choice&, const Run& r) {
+int launch_join(ts2d_engine* e, size_t oi, const Choice& c, const Run& r) {
     const Op& op = e->ops[oi];
     const Tensor& c2 = e->tensors[op.src]; const Tensor& rs = e->tensors[op.res]; const Tensor& dst = e->tensors[op.dst];
     JoinArgs ja{};
@@ -390,8 +392,12 @@ int launch_join(ts2d_engine* e, size_t oi, const Choice&, const Run& r) {
     if (!c2.normed || !rs.normed || c2.C != op.cout || rs.C != op.cout || op.cout % 32 || (r.H >> rs.ly) != (r.H >> op.ly) * op.sy || ja.Win != ja.Wt * op.sx ||
         (rs.linear && (op.sy != 1 || op.sx != 1)))
         return fail(TS2D_ERR_INVALID, "internal: op %s: the join's sources do not match its output", op.name.c_str());
-    const dim3 grid((unsigned)((ja.npix + 31) / 32), op.cout / 32), block(256);
-    HIP_TRY(launch_kernel<res_join>(grid, block, 0, r.st, ja));
+    if (c.half != r.f16) return fail(TS2D_ERR_INVALID, "internal: op %s: the plan's storage is not the run's", op.name.c_str());
+    if (r.f16 && op.cout > 2048) return fail(TS2D_ERR_INVALID, "op %s: the 16-bit join serves at most 2048 channels", op.name.c_str());
+    // fp32 storage: 32 pixels x 32 channels per block; fp16 storage: 256 / (C / 8) whole pixels per block (a lane owns 16 bytes of a pixel)
+    const int ppb = r.f16 ? 256 / (op.cout / 8) : 32;
+    const dim3 grid((unsigned)((ja.npix + ppb - 1) / ppb), r.f16 ? 1 : op.cout / 32), block(256);
+    HIP_TRY(with_storage(r.f16, [&](auto s) { return launch_kernel<res_join<typename decltype(s)::type>>(grid, block, 0, r.st, ja); }));
     return TS2D_OK;
 }
 
@@ -652,7 +658,7 @@ int run_forward_impl(ts2d_engine* e, const float* d_in, int B, int H, int W, flo
     for (size_t oi = 0; oi < e->ops.size(); ++oi) {
         const Op& op = e->ops[oi];
         const Choice& c = plan[oi];
-        if (c.k == K_NONE && e->residual)
+        if (c.k == K_NONE && e->residual && !e->use_resf16)      // (the option was cleared with the mode still set: no silent change of mode)
             return fail(TS2D_ERR_INVALID, "op %s: TS2D_PRECISION_F16 is not supported on a residual-encoder engine", op.name.c_str());
         if (c.k == K_NONE) return fail(TS2D_ERR_INVALID, "op %s has no fp16 kernel (channel counts must be multiples of 16)", op.name.c_str());
         if (c.k == K_FUSED_AWAY) { e->fused_away[oi] = 1; continue; }      // composed into the next block (kernels_upc.h): the upsampled tensor is never materialised
@@ -795,7 +801,7 @@ int ts2d_engine_set_precision(ts2d_engine* e, int mode) {
     if (!e) return fail(TS2D_ERR_INVALID, "ts2d_engine_set_precision: null engine");
     if (mode != TS2D_PRECISION_F32_EXACT && mode != TS2D_PRECISION_F32_SPLIT_F16X3 && mode != TS2D_PRECISION_F16)
         return fail(TS2D_ERR_INVALID, "unknown precision mode %d", mode);
-    if (mode == TS2D_PRECISION_F16 && e->residual)      // (the 16-bit contract of a residual block - where the sum is rounded - is a definition of its own)
+    if (mode == TS2D_PRECISION_F16 && e->residual && !e->use_resf16)      // (opt-in, option "resf16": the contract of a residual block is a definition of its own - ts2d_engine.h)
         return fail(TS2D_ERR_INVALID, "TS2D_PRECISION_F16 is not supported on a residual-encoder engine (TS2D_PRECISION_F32_SPLIT_F16X3 and "
                     "TS2D_PRECISION_F32_EXACT are); the mode is unchanged");
     e->precision = mode;
@@ -807,7 +813,7 @@ int ts2d_engine_set_option(ts2d_engine* e, const char* name, int value) {
     struct B { const char* n; bool* p; };
     struct I { const char* n; int* p; int lo, hi; };
     const B bools[] = {{"one", &e->use_one}, {"s2v2", &e->use_s2v2}, {"q", &e->use_q}, {"h2", &e->use_h2},  {"uh2", &e->use_uh2},
-                       {"first_split", &e->use_first_split}, {"sbk", &e->use_sbk}, {"s2k32", &e->use_s2k32}, {"s2p", &e->use_s2p}, {"up0", &e->use_up0}, {"upc", &e->use_upc}, {"res", &e->use_res}, {"fuse0", &e->use_fuse0}, {"flex", &e->use_flex}};
+                       {"first_split", &e->use_first_split}, {"sbk", &e->use_sbk}, {"s2k32", &e->use_s2k32}, {"s2p", &e->use_s2p}, {"up0", &e->use_up0}, {"upc", &e->use_upc}, {"res", &e->use_res}, {"fuse0", &e->use_fuse0}, {"flex", &e->use_flex}, {"resf16", &e->use_resf16}};
     const I ints[] = {{"u0seg", &e->u0seg, 0, 1 << 20}, {"flex2", &e->use_flex2, 0, 2}};
     bool found = false;
     for (const B& b : bools) if (!strcmp(name, b.n)) { *b.p = value != 0; found = true; }
@@ -815,7 +821,7 @@ int ts2d_engine_set_option(ts2d_engine* e, const char* name, int value) {
         if (value < i.lo || value > i.hi) return fail(TS2D_ERR_INVALID, "option %s = %d out of range [%d, %d]", name, value, i.lo, i.hi);
         *i.p = value; found = true;
     }
-    if (!found) return fail(TS2D_ERR_INVALID, "unknown option '%s' (one s2v2 q h2 uh2 up0 u0seg upc res fuse0 flex flex2 first_split sbk s2k32 s2p)", name);
+    if (!found) return fail(TS2D_ERR_INVALID, "unknown option '%s' (one s2v2 q h2 uh2 up0 u0seg upc res fuse0 flex flex2 first_split sbk s2k32 s2p resf16)", name);
     e->ws_precision = -1;         // which ops compose (and with it the activation plan) depends on the options: re-plan at the next reserve / forward
     ++e->opt_gen;
     return TS2D_OK;

@@ -126,6 +126,7 @@ struct Choice {
     bool s2p = false;           // (K_S2_V2) the pipelined split-mode instance conv3x3s2_v2p (kernels_s2v2p.h); same reported name, same bits
     int seg = 0;                // (K_UP0 / K_S1_RES32*) tiles per workgroup segment (segment_tiles)
     int ks = 0;                 // (K_UPC_H / K_UPC_H2) coarse k-steps per staged chunk
+    bool half = false;          // (K_PROJ / K_JOIN) the fp16-storage instance (16-bit mode, option "resf16")
     const char* name = "";      // what ts2d_engine_op_kernel reports for the op (tests and scripts/pmc_traffic.py key on these strings)
 };
 
@@ -178,6 +179,7 @@ struct ts2d_engine {
     bool use_fuse0 = true;        // "fuse0": first block recomputed inside the second (statistics-only pre-pass + conv3x3_res32 fused variant)
     bool diagnosing = false;      // the re-run of ts2d_engine_check: the first block as its own kernel whatever "fuse0" says (its output can be scanned and named)
     int use_flex2 = 2;            // "flex2": conv3x3s2_v2 on level-dividing tiles where the level is no multiple of 8 x 32 (0: off, 1: 16-bit mode only, 2: both)
+    bool use_resf16 = false;      // "resf16": the 16-bit mode on a residual-encoder engine (opt-in: 0 refuses TS2D_PRECISION_F16 there, as before the mode existed)
     bool use_flex = true;         // "flex": the composed decoder entry on extent-following tiles at levels that are no multiple of 8 x 32 (0: two kernels there)
     int dbg = 0;                  // TS2D_DBG (the one environment switch left): timing ablations / in-kernel phase stamps of diagnostic runs
     unsigned long long* d_prof = nullptr;     // TS2D_DBG=256: in-kernel phase counters, 8 per op (diagnostic)

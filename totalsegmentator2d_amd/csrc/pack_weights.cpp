@@ -257,6 +257,11 @@ void pack_weights(const ts2d_engine* e, const float* blob, float* out) {
             float* d = out + op.dev_w;
             for (int co = 0; co < co_n; ++co)
                 for (int ci = 0; ci < ct; ++ci) d[(size_t)ci * co_n + co] = w[(size_t)co * ct + ci];
+            if (ct % 32 == 0) {             // the 16-bit mode's copy: h(w), [chunk32][co][32 halves]
+                uint16_t* dh = reinterpret_cast<uint16_t*>(out + op.dev_wh);
+                for (int co = 0; co < co_n; ++co)
+                    for (int ci = 0; ci < ct; ++ci) dh[((size_t)(ci / 32) * co_n + co) * 32 + ci % 32] = f32_to_f16(w[(size_t)co * ct + ci]);
+            }
             memcpy(out + op.dev_g, blob + op.blob_g, co_n * sizeof(float));
             memcpy(out + op.dev_be, blob + op.blob_be, co_n * sizeof(float));
             continue;

@@ -252,6 +252,7 @@ int build_program(ts2d_engine* e) {
             op.ck = 0; op.dev_w_floats = (size_t)ct * op.cout;
             op.dev_w = wo; wo = align_up(wo + op.dev_w_floats, 64);
             op.dev_g = wo; wo = align_up(wo + op.cout, 64); op.dev_be = wo; wo = align_up(wo + op.cout, 64);
+            op.dev_wh = wo; wo = align_up(wo + op.dev_w_floats / 2, 64);     // rounded to half, [chunk32][Cout][32 halves] (pool_proj1x1_h; Cin % 32 == 0: pad_arch)
             continue;
         }
         if (op.type == OP_CONV) {

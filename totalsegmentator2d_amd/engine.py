@@ -44,6 +44,19 @@ def _is_torch(x) -> bool:
     return type(x).__module__.startswith('torch') and hasattr(x, 'data_ptr')
 
 
+def set_precision_opted_in(e: 'Engine', mode):
+    """``e.set_precision(mode)`` for a caller who has NAMED the mode (``HIPnnUNetPredictor(precision=...)``, ``SubModelSet(precision=...)``):
+    the 16-bit mode of a residual-encoder engine is opt-in at the C-ABI (option ``"resf16"``), and naming ``'f16'`` is the opt-in."""
+    if mode in ('f16', _lib.PRECISION_F16) and e.arch.encoder == 'residual':
+        try:
+            e.set_option('resf16', 1)
+        except RuntimeError as err:
+            if 'unknown option' not in str(err):
+                raise
+            raise RuntimeError(f"{_lib.LIB_PATH} was built before the option 'resf16': rebuild it to run a ResidualEncoderUNet in the 16-bit mode") from err
+    e.set_precision(mode)
+
+
 class Engine:
     default_options: Dict[str, int] = {}     # dispatch options every new handle starts with (empty in the product; test modules that address
                                              # the large-batch kernels at small B set {'sbk': 0})
@@ -111,7 +124,8 @@ class Engine:
     def set_precision(self, mode):
         """'exact' (fp32 MFMA), 'split' (fp16 hi/lo x3 MFMA, fp32-equivalent accuracy; the default) or 'f16' (fp16 storage,
         one fp16 MFMA product, fp32 accumulate/statistics: BASELINE configs 3/5, outside the fp32 parity tolerance).  A residual-encoder
-        engine refuses 'f16' (RuntimeError naming the mode) and keeps the mode it had."""
+        engine refuses 'f16' (RuntimeError naming the mode) and keeps the mode it had, unless its option ``'resf16'`` is set
+        (:func:`set_precision_opted_in` does both)."""
         m = {'exact': _lib.PRECISION_F32_EXACT, 'split': _lib.PRECISION_F32_SPLIT_F16X3, 'f16': _lib.PRECISION_F16}.get(mode, mode)
         _lib.check(self.lib.ts2d_engine_set_precision(self._h, int(m)), 'ts2d_engine_set_precision')
         self._ws_need.clear()

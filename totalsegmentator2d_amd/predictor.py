@@ -165,12 +165,12 @@ class HIPnnUNetPredictor:
         self.configuration_manager.use_mask_for_norm = cfg.get('use_mask_for_norm', self.configuration_manager.use_mask_for_norm)
 
     def _create_engines(self):
-        from .engine import Engine            # raises loudly if libts2d_engine.so is missing - no fallback
+        from .engine import Engine, set_precision_opted_in            # raises loudly if libts2d_engine.so is missing - no fallback
         for e in self.engines:
             e.close()
         self.engines = [Engine(self.arch, blob, self.device.index) for blob in self.list_of_parameters]
         for e in self.engines:
-            e.set_precision(self.precision)
+            set_precision_opted_in(e, self.precision)      # (precision='f16' on a ResidualEncoderUNet: the user has named the mode)
             e.set_tile_dtype(self.tile_dtype)
 
     def close(self):

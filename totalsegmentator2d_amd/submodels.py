@@ -11,7 +11,7 @@ from __future__ import annotations
 from typing import Dict, List, Optional, Sequence, Tuple
 
 from .arch import UNetArch
-from .engine import Engine
+from .engine import Engine, set_precision_opted_in
 
 TS2D_V2_HEADS: Dict[str, int] = {'cardiac': 18, 'muscles': 23, 'organs': 24, 'ribs': 26, 'vertebrae': 26}
 
@@ -23,7 +23,7 @@ class SubModelSet:
         self.engines: List[Engine] = []
         for mid, arch, blob in sorted(models, key=lambda m: m[0]):
             e = Engine(arch, blob, device=device)
-            e.set_precision(precision)
+            set_precision_opted_in(e, precision)        # (a residual member runs the 16-bit mode too: naming it is the opt-in)
             self.ids.append(mid)
             self.engines.append(e)
         self.channels = [e.arch.num_classes for e in self.engines]
@@ -41,7 +41,7 @@ class SubModelSet:
     def set_precision(self, mode: str):
         """Arithmetic mode of every sub-model; the shared workspace is re-sized at the next forward (a mode's activation plan differs)."""
         for e in self.engines:
-            e.set_precision(mode)
+            set_precision_opted_in(e, mode)
         self._reserved = None
 
     def reserve(self, B: int, H: int, W: int):
