@@ -15,7 +15,10 @@ without a GPU, which seeded defects these bounds catch.
   d. small nets that reach the names the canonical net never reports (32-column instances, the exact kernels on a (2, 1) stage, widths
      that are no multiples of 32), transposed-conv bias x 40 on the composed-block net.
   e. 16-bit mode, B = 64: rows 0, 37, 63 bit-identical to those rows alone.
-  f. (last) every name ``kernel_name()`` of csrc/dispatch.cpp can return was seen above, per storage.
+  f. (last) every name ``kernel_name()`` of csrc/dispatch.cpp can return was seen above, per storage.  The name ``head`` covers TWO kernels:
+     ``head_mfma32`` (K <= 32 at width 32: nearly every case here) and ``head_1x1`` (csrc/kernels.h: the exact mode, the ``one`` = 0 twin - and
+     every model with more than 32 heads or a level-0 width of 64), so "seen" says little about the second one.  It is judged, pinned by the
+     construction of its cases, in tests/test_gpu_many_heads.py (K up to 256, C = 32 and 64).
 
 Measured worst per-layer values (MI355X, 256 CUs; printed by every case and, per kernel name, by the last test: read them with ``pytest -s``).
 Every op of every case stayed under the FIXED bounds of tests/layer_check.py (8e-6 block, 2e-6 / 2e-3 transposed conv, ``_f16_layer_ok``):

@@ -91,9 +91,10 @@ def _crafted(K, seed):
     return lg
 
 
-@pytest.mark.parametrize('K', [1, 2, 3, 18])
+@pytest.mark.parametrize('K', [1, 2, 3, 18, 33, 256])
 def test_kernel_on_crafted_planes(K):
-    """13 x 10 planes, the rectangle (1, 3, 11, 6) with an odd src_x (the unaligned read path); identity and 17 x 7 (a width that is no multiple
+    """(K = 33 and 256: the passes over the heads at the head counts of label-map models - tests/test_gpu_many_heads.py has the engine entry.)
+    13 x 10 planes, the rectangle (1, 3, 11, 6) with an odd src_x (the unaligned read path); identity and 17 x 7 (a width that is no multiple
     of 4); in a 20 x 9 extent at (2, 1) (scalar stores, the fill on every side) and with the output as the whole extent."""
     rect = (1, 3, 11, 6)
     order = tuple(int(c) for c in np.random.default_rng(K).integers(0, 256, K))

@@ -33,6 +33,30 @@ The narrowest per-layer margin is ``eps_out`` (2.0e-5 against 8e-6, a factor 2.4
 defect vanishes to first order (sqrt(v + eps) - sqrt(v) - eps = eps (1 / (2 sigma) - 1)), so it is caught on the block as a whole and
 not on every channel of it.
 
+MANY-CLASS HEADS.  What tests/test_gpu_many_heads.py can see of a defective HEAD kernel (its checks a. and b.): two-stage nets of that module - K = 118 at
+C = 32 and K = 40 at C = 64, weights and inputs seeded 300 + K - B = 3 of 16 x 32; ``nextimg`` on B = 3 of 4 x 32, the input whose first
+256-pixel block holds the pixels of two images (that input is judged per layer only on the GPU).  ``got`` = the float32 torch head with ONE
+seeded defect, on the float32 chain's own ``dec0.c0``; per layer against ``layer_check.reference_block('head')`` under ``HEAD_RTOL``, all
+rows; end to end against the clean chain's logits at ``TOL`` (16-bit defect: ``F16E_MAX`` / ``F16E_RMS`` against the 16-bit oracle).
+
+  defect                                                             net         per layer (of the largest logit)    end to end (max | rms)
+  cols32   heads >= 32 computed with the weights of head k - 32      K=118 C=32  1.7e+0   caught                     1.1e+1 | 1.2e+0   caught
+           (what a 32-column kernel would do)                        K=40  C=64  1.3e+0   caught                     6.0e+0 | 5.6e-1   caught
+  bias32   the bias read at k mod 32                                 K=118 C=32  7.7e-3   caught                     4.7e-2 | 1.3e-2   caught
+                                                                     K=40  C=64  1.8e-3   caught                     8.0e-3 | 2.4e-3   caught
+  chan56   the last 8 of 64 channels left out                        K=40  C=64  5.7e-1   caught                     2.6e+0 | 3.8e-1   caught
+  nextimg  image 0's scale and shift for the pixels of image 1,      K=118 C=32  1.1e-1   caught                     5.7e-1 | 5.8e-2   caught
+           4 x 32: the block that holds both                         K=40  C=64  1.0e-1   caught                     4.9e-1 | 6.4e-2   caught
+  trunc16  16-bit mode: the fp16 operand cut off, not rounded        K=118 C=32  6.0e-4   NOT caught (1.5e-3)        3.7e-3 | 5.0e-4   PASSES (0.1 | 0.012)
+                                                                     K=40  C=64  6.4e-4   NOT caught (1.5e-3)        2.9e-3 | 4.9e-4   PASSES (0.1 | 0.012)
+
+The first four are caught per layer with a margin of 1.8e3 (bias32 at K = 40) to 1.7e6 over HEAD_RTOL = 1e-6 (the clean float32 head: 2.0e-7
+... 3.3e-7), and end to end as well: a defect of the LAST op reaches the logits undamped.  The fifth is NOT caught, per layer or end to end,
+and is recorded as found: a truncated fp16 operand moves a logit by 6.0e-4 ... 6.4e-4 of the largest one - 32 or 64 terms of half an fp16 unit
+each, whose signs follow the weights' and cancel - which is the size of a CORRECT kernel's distance from the 16-bit oracle (head_1x1 keeps fp32
+weights and operands there: 3.2e-4 ... 4.7e-4 on the MI355X, tests/test_gpu_many_heads.py) and 0.4 of HEAD_RTOL['f16'] = 1.5e-3.  A check
+that separates rounding from truncation of the head's operand would have to compare operands, not logits.
+
 The numbers above are asserted as classifications (caught / passes), not as values; each case prints its figures (``pytest -s``)."""
 import numpy as np
 import pytest
@@ -283,3 +307,111 @@ def test_op_sources_agrees_with_the_program(which):
         else:
             want = (o['src'],)
         assert LC.op_sources(arch, n) == want, (n, LC.op_sources(arch, n), want)
+
+
+# ------------------------------------------------------------------------------------------------------------------ many-class heads
+# (the table of these defects is in the module docstring: MANY-CLASS HEADS)
+HEAD_NETS = {'K118_C32': ((32, 32), 118), 'K40_C64': ((64, 64), 40)}
+# defect -> (mode, extent of the input, nets, caught per layer?, stays under the end-to-end bound?)
+HEAD_DEFECTS = {
+    'cols32': ('split', (16, 32), ('K118_C32', 'K40_C64'), True, False),
+    'bias32': ('split', (16, 32), ('K118_C32', 'K40_C64'), True, False),
+    'chan56': ('split', (16, 32), ('K40_C64',), True, False),
+    'nextimg': ('split', (4, 32), ('K118_C32', 'K40_C64'), True, False),
+    'trunc16': ('f16', (16, 32), ('K118_C32', 'K40_C64'), False, True),
+}
+_head_cases = {}
+
+
+def _head_case(net, hw):
+    """(arch, sd, x, the float32 chain's tensors, the 16-bit chain's tensors) of a head net on B = 3 of `hw`, made once."""
+    if (net, hw) not in _head_cases:
+        feats, K = HEAD_NETS[net]
+        arch = cases.unet(2, feats, K, nconv=1)
+        sd = weights.synthetic_state_dict(arch, 300 + K)
+        x = cases.make_input(arch, 3, hw[0], hw[1], 300 + K)
+        out = []
+        for emulate in (None, 'f16'):
+            lg, inter = O.unet_forward(arch, sd, x, return_intermediates=True, emulate=emulate)
+            inter = {k: v.numpy() for k, v in inter.items()}
+            inter['head'] = lg.numpy()
+            out.append(inter)
+        _head_cases[(net, hw)] = (arch, sd, x, out[0], out[1])
+    return _head_cases[(net, hw)]
+
+
+def _trunc16(t):
+    """float32 -> fp16 cut off towards zero (the defect ``trunc`` above, on an operand) -> float32."""
+    h = t.to(torch.float16)
+    over = h.float().abs() > t.abs()
+    return torch.where(over, (h.view(torch.int16) - 1).view(torch.float16), h).float()
+
+
+def head32(arch, sd, inter, defect=None, f16=False):
+    """The head in float32 from the chain's tensors, written out so that a defect can be seeded: ``dec0.c0`` = conv -> statistics ->
+    scale / shift -> LeakyReLU (what the head kernels apply on load), then the 1x1 conv.  `f16`: fp16 weights and operand, fp32 sums - from
+    the storage view of ``dec0.c0``, as ``layer_check`` feeds the 16-bit head."""
+    t = {k: O._t(v) for k, v in sd.items()}
+    w, b = t['decoder.seg_layers.0.weight'].clone(), t['decoder.seg_layers.0.bias'].clone()
+    K = w.shape[0]
+    with torch.no_grad():
+        if defect == 'nextimg':                              # dec0.c0 once more with image 0's statistics for image 1
+            k = 'decoder.stages.0.convs.0'
+            up = F.conv_transpose2d(O._t(inter['enc1.c0']), t['decoder.transpconvs.0.weight'], t['decoder.transpconvs.0.bias'], stride=tuple(arch.strides[1]))
+            y = F.conv2d(torch.cat((up, O._t(inter['enc0.c0'])), 1), t[f'{k}.conv.weight'], t[f'{k}.conv.bias'], padding=1)
+            mean = y.mean((2, 3), keepdim=True)
+            rstd = 1.0 / (((y - mean) ** 2).mean((2, 3), keepdim=True) + arch.norm_eps).sqrt()
+            clean = F.leaky_relu((y - mean) * rstd * t[f'{k}.norm.weight'][None, :, None, None] + t[f'{k}.norm.bias'][None, :, None, None], arch.leaky_slope)
+            assert float((clean - O._t(inter['dec0.c0'])).abs().max()) <= 2e-6            # the written-out block is torch's block
+            mean, rstd = mean.clone(), rstd.clone()
+            mean[1], rstd[1] = mean[0], rstd[0]
+            xin = F.leaky_relu((y - mean) * rstd * t[f'{k}.norm.weight'][None, :, None, None] + t[f'{k}.norm.bias'][None, :, None, None], arch.leaky_slope)
+        else:
+            xin = O._t(inter['dec0.c0']).float()
+        if defect == 'cols32':
+            w[32:] = t['decoder.seg_layers.0.weight'][:K - 32]
+        if defect == 'bias32':
+            b = b[torch.arange(K) % 32]
+        if defect == 'chan56':
+            assert w.shape[1] == 64
+            w[:, 56:] = 0
+        if f16:
+            xin, w = (_trunc16(xin) if defect == 'trunc16' else O._h(xin)), O._h(w)
+        return F.conv2d(xin, w, b).numpy()
+
+
+def test_the_head_nets_are_those_of_the_gpu_module():
+    for net, (feats, K) in HEAD_NETS.items():
+        arch = _head_case(net, (16, 32))[0]
+        assert arch.features_per_stage == tuple(feats) and arch.num_classes == K > 32 and [o['name'] for o in arch.program()][-2:] == ['dec0.c0', 'head']
+    assert _head_case('K118_C32', (4, 32))[2].shape == (3, 2, 4, 32)               # 384 pixels: the first 256-pixel block holds images 0 and 1
+
+
+@pytest.mark.parametrize('defect,net', [(d, n) for d, v in HEAD_DEFECTS.items() for n in v[2]])
+def test_seeded_head_defect(defect, net):
+    mode, hw, _, caught, passes_e2e = HEAD_DEFECTS[defect]
+    f16 = mode == 'f16'
+    arch, sd, x, inter32, inter16 = _head_case(net, hw)
+    inter = inter16 if f16 else inter32
+    src = inter['dec0.c0']
+    if f16:                                                  # what the accessor shows: the stored fp16 conv output normalised and activated in fp32
+        src = O.layer_forward(arch, sd, 'dec0.c0', inter['enc1.c0'], inter['enc0.c0'], emulate='f16', storage_view=True).numpy()
+    want = LC.reference_block(arch, sd, 'head', [src], mode)
+    feed = dict(inter, **{'dec0.c0': src})
+    clean = head32(arch, sd, feed, None, f16)
+    ok0, w0, text0 = LC.layer_error('head', clean, want, mode)
+    assert ok0, ('the clean head must pass', text0)
+    got = head32(arch, sd, feed, defect, f16)
+    assert not np.array_equal(got, clean), 'the defect changed nothing'
+    ok, w, text = LC.layer_error('head', got, want, mode)
+    d = got - inter['head']                                  # the head is the last op: its output IS the logits of the defective chain
+    e2e, e2e_rms = float(np.abs(d).max()), float(np.sqrt((d.astype(np.float64) ** 2).mean()))
+    under = (e2e <= F16E_MAX and e2e_rms <= F16E_RMS) if f16 else e2e <= TOL
+    print(f'[layer-check-cpu] head {defect} {net} {hw}: per layer {text} (clean {w0:.2e}, bound {LC.HEAD_RTOL[mode]:.1e}) -> '
+          f'{"caught" if not ok else "NOT caught"}; logits max {e2e:.2e} rms {e2e_rms:.2e} -> {"passes" if under else "caught"} end to end')
+    assert (not ok) == caught, text
+    assert under == passes_e2e, (e2e, e2e_rms)
+
+
+def test_the_first_four_head_defects_are_caught_per_layer():
+    assert [d for d, v in HEAD_DEFECTS.items() if not v[3]] == ['trunc16'] and len(HEAD_DEFECTS) == 5

@@ -34,6 +34,22 @@ def test_c_oracle_matches_goldens(name):
     assert np.abs(C.unet_forward(arch, blob, x, acc64=True) - g).max() <= tol
 
 
+@pytest.mark.parametrize('feats,K', [((64, 64), 40), ((32, 32), 118)])
+def test_c_oracle_matches_the_torch_oracle_at_many_heads(feats, K):
+    """More heads than any golden has (the largest is 26): the two-stage nets of tests/test_gpu_many_heads.py, B = 3 of 16 x 32 and B = 5 of
+    6 x 20.  The two restatements share no code; the tolerance is that of the goldens above."""
+    arch = cases.unet(2, feats, K, nconv=1)
+    sd, blob = blob_for(arch, 300 + K)
+    for B, H, W in ((3, 16, 32), (5, 6, 20)):
+        x = cases.make_input(arch, B, H, W, 300 + K)
+        ref = O.unet_forward(arch, sd, x).numpy()
+        assert ref.shape == (B, K, H, W)
+        for acc64 in (False, True):
+            assert np.abs(C.unet_forward(arch, blob, x, acc64=acc64) - ref).max() <= 1e-4, (B, H, W, acc64)
+        assert np.array_equal(C.logits_to_mask(ref), O.logits_to_mask(ref).numpy())
+        assert len(np.unique(ref.argmax(1))) > 32                 # heads beyond 32 win pixels: a restatement that dropped them would differ
+
+
 def test_anisotropic_strides_follow_plain_torch_modules():
     """Per-axis strides (nnU-Net pools every axis separately; the plan is whatever the model folder holds: reference
     ts2d/core/inference/nnu.py:164-165): the oracle's functional restatement equals a network assembled from plain torch.nn modules
