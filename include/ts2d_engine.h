@@ -688,6 +688,28 @@ int ts2d_planes_download(const ts2d_planes* p, float* dst);
 /* Free the handle and its device memory (NULL is fine).  Reference: the preprocessed array going out of scope (prediction_worker.py:194-199). */
 int ts2d_planes_destroy(ts2d_planes* p);
 
+/* nnU-Net's postprocessing of a decided label map, the plan nnUNetv2_find_best_configuration stores beside a model: the steps of
+ * remove_all_but_largest_component_from_segmentation, one after the other on the device (kernels_post_cc.h).  The reference has no counterpart
+ * (its models are multilabel and carry no such plan); the contract is postprocess.keep_largest_components_statement, byte for byte.
+ *   seg       host uint8 [Z][H][W], changed IN PLACE; a 2-D case is Z = 1.  One upload, every step on the device, one download.
+ *   steps     [n_steps], applied in order, each to the result of the one before.  A step: `member` - 1 at every label value it names, label or
+ *             region alike (the union) - and `background`.  mask = member[seg]; its components under FULL connectivity (26 neighbours, 8 at
+ *             Z = 1) are sized; every mask voxel of a component smaller than the largest becomes `background`; components that tie for the
+ *             largest all stay; an empty mask changes nothing.
+ *   stats     NULL, or int64 [n_steps][4]: mask voxels, components, largest size, voxels removed.
+ *   status    0, or TS2D_CC_GIVE_UP: a bounded loop of the labelling reached its hard cap (32768 steps of one find chain, 1024 lost races of one
+ *             union - neither has been seen).  The call returns TS2D_OK with seg and stats as the caller passed them; no retry, the caller takes the
+ *             host route.
+ * The result does not depend on the order in which the lanes arrive: the partition, the integer sizes and their maximum are unique and ties are kept.
+ * TS2D_ERR_INVALID, by name, before any device work: null seg or status, null steps with n_steps > 0, a non-positive extent, more than 2^31 - 1
+ * voxels (the indices are int32), n_steps < 0.  n_steps = 0 does nothing.  On any error the host buffer is untouched.
+ * Device scratch of the call's own, freed on every path: 9 1/8 bytes per voxel (the map, its bit words, parent and count), 257 bytes and four
+ * counters per step.  (A new symbol of ABI 9: nothing that existed changed.) */
+typedef struct { uint8_t member[256]; uint8_t background; } ts2d_cc_step;
+#define TS2D_CC_GIVE_UP 1   /* a bounded loop reached its cap: seg is unchanged, the caller takes the host route */
+int ts2d_keep_largest_components(int device, uint8_t* seg /* host [Z][H][W], in place */, int Z, int H, int W,
+                                 const ts2d_cc_step* steps, int n_steps, int64_t* stats /* [n_steps][4] or NULL */, int* status);
+
 /* Synthetic slice stream on the device (BASELINE config 4: "synthetic 10k-slice stream", generated per rank from (seed, slice
  * index) so that no host transfer skews the timing).  Writes n_elements fp32 values, approximately N(0,1), to device memory:
  * element i of the call = element (first_element + i) of the stream identified by `key`; a value depends on (key, element index)

@@ -69,6 +69,14 @@ class TiledProbabilitiesRun(ctypes.Structure):
 
 PROB_MULTILABEL, PROB_LABELMAP, PROB_REGIONS = 0, 1, 2      # TS2D_PROB_*
 
+
+class CcStep(ctypes.Structure):
+    """``ts2d_cc_step``: one step of ``ts2d_keep_largest_components`` - the membership table of its labels and its background byte."""
+    _fields_ = [('member', ctypes.c_uint8 * 256), ('background', ctypes.c_uint8)]
+
+
+CC_GIVE_UP = 1                                              # TS2D_CC_GIVE_UP
+
 # shorthands of the table below: int, void *, size_t, long long, unsigned long long, char *; pointers to a void * and to the three descriptors
 _I, _P, _Z, _LL, _ULL, _S = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_char_p
 _PP, _TI, _TE, _TL = ctypes.POINTER(_P), ctypes.POINTER(TiledImage), ctypes.POINTER(TiledExport), ctypes.POINTER(TiledLabelmap)
@@ -110,6 +118,7 @@ SIGNATURES = {
     'ts2d_planes_extent': (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     'ts2d_planes_download': (_I, [_P, _P]),
     'ts2d_planes_destroy': (_I, [_P]),
+    'ts2d_keep_largest_components': (_I, [_I, _P, _I, _I, _I, _P, _I, _P, ctypes.POINTER(_I)]),
     'ts2d_synth_slices': (_I, [_I, _ULL, _ULL, _ULL, _P, _P]),
     'ts2d_engine_reserve': (_I, [_P, _I, _I, _I]),
     'ts2d_engine_workspace_bytes': (_I, [_P, _I, _I, _I, ctypes.POINTER(_Z)]),
@@ -133,7 +142,9 @@ SYMBOLS = tuple(SIGNATURES)
 # added under ABI 9 (the cubic resample; the device-resident planes of preprocess.DevicePlanes, ts2d_planes_crop_normalize after the others, the two *_stack entries, then ts2d_planes_crop_normalize_stack_masked last):
 # a library built before them lacks the symbols, still loads, and the callers keep the host route; the probabilities entries likewise (the one for stacks came after the other two: each is looked up on its own)
 # ... and the residual-encoder entry: without it a ResidualEncoderUNet cannot be created (Engine says so), a plain net is unaffected
-OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n or n == 'ts2d_engine_create_residual')
+# ... and the largest-component postprocessing: without it postprocess.apply_postprocessing keeps the host route
+OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n
+                     or n in ('ts2d_engine_create_residual', 'ts2d_keep_largest_components'))
 
 
 class EngineLibraryError(RuntimeError):

@@ -665,6 +665,46 @@ def probabilities_from_logits(logits_f16: np.ndarray, rect, out_hw, full_hw, box
     return prob, dec
 
 
+def has_keep_largest_components() -> bool:
+    """Does the engine library have ``ts2d_keep_largest_components``?  False with no library built, one that does not load, or one built
+    before the entry: the callers keep the host route (postprocess.apply_postprocessing)."""
+    try:
+        return hasattr(_lib.load(), 'ts2d_keep_largest_components')
+    except _lib.EngineLibraryError:
+        return False
+
+
+def keep_largest_components(seg: np.ndarray, tables, backgrounds, device: int = 0):
+    """nnU-Net's largest-component postprocessing on the device (C-ABI ts2d_keep_largest_components, csrc/kernels_post_cc.h): uint8
+    [Z,H,W] (or [H,W]: Z = 1), per step a 256-byte membership table and a background byte (``PostprocessingPlan.compiled``).  Returns
+    ``(seg_out, stats, status)``: a new array - ``postprocess.keep_largest_components_statement`` byte for byte - the int64
+    [n_steps, 4] counters (mask voxels, components, largest size, voxels removed) and 0; or ``(None, None, CC_GIVE_UP)`` where a bounded
+    loop of the labelling reached its cap: the caller takes the host route."""
+    src = np.asarray(seg)
+    if src.dtype != np.uint8 or src.ndim not in (2, 3):
+        raise RuntimeError(f"keep_largest_components: expected uint8 [Z,H,W] or [H,W], found {src.dtype} {src.shape}")
+    lib = _lib.load()
+    if not hasattr(lib, 'ts2d_keep_largest_components'):
+        raise RuntimeError("ts2d_keep_largest_components: this libts2d_engine.so was built before the entry; rebuild it, or keep the host route")
+    out = np.array(src, dtype=np.uint8, order='C')            # (a copy: the entry works in place)
+    z, h, w = ((1,) + out.shape)[-3:]
+    n = len(tables)
+    steps = (_lib.CcStep * max(n, 1))()
+    for k in range(n):
+        t = np.ascontiguousarray(tables[k], dtype=np.uint8)
+        if t.shape != (256,):
+            raise RuntimeError(f"keep_largest_components: step {k}: the membership table has shape {t.shape}, not (256,)")
+        ctypes.memmove(steps[k].member, t.ctypes.data, 256)
+        steps[k].background = int(backgrounds[k])
+    stats = np.zeros((n, 4), dtype=np.int64)
+    status = ctypes.c_int(0)
+    _lib.check(lib.ts2d_keep_largest_components(int(device), out.ctypes.data, z, h, w, ctypes.cast(steps, ctypes.c_void_p), n, stats.ctypes.data,
+                                                ctypes.byref(status)), 'ts2d_keep_largest_components')
+    if status.value:
+        return None, None, int(status.value)
+    return out, stats, 0
+
+
 def _read_tiled_inf(engines, desc, n_images, engine_flags: bool):
     """The inf flags a tiled call left behind (upstream's inf check, done on the device).  With descriptors, ``last_tiled_inf_per_image``
     of the first engine is their per-image flags; ``last_tiled_inf`` of every engine is its own flag in the library (the flat entry and

@@ -228,8 +228,12 @@ def segmentation_to_image(seg: np.ndarray, ref: nrrd.Image, multilabel: bool, la
 def export_prediction_from_logits(logits, properties: dict, configuration_manager, plans_manager, dataset_json: dict,
                                   ofile_truncated: str, save_probabilities: bool = False, ref_image: Optional[nrrd.Image] = None,
                                   labels: Optional[Dict[int, str]] = None, colors: Optional[dict] = None,
-                                  probabilities=None) -> nrrd.Image:
-    """``save_probabilities`` [UPSTREAM-RECALL: export_prediction_from_logits]: beside the segmentation ``<ofile>.npz``
+                                  probabilities=None, postprocess=None) -> nrrd.Image:
+    """``postprocess``: None, or a callable ``seg -> (seg, stats, route)`` (a closure over ``postprocess.apply_postprocessing``, HIPModel._run)
+    applied to the decided label map in its ORIGINAL extent, after the crop has been reverted and ``transpose_backward`` applied and before it
+    becomes an image [UPSTREAM-RECALL: the stored postprocessing runs on the written label maps]; the probabilities stay as they are.  The
+    returned image then carries ``img.postprocessing = {'route': ..., 'stats': ..., 'seconds': the span of the step alone}``.  A multilabel model has no such step (ValueError).
+    ``save_probabilities`` [UPSTREAM-RECALL: export_prediction_from_logits]: beside the segmentation ``<ofile>.npz``
     (``np.savez_compressed``, key ``probabilities``: float32 [K, *original shape]) and ``<ofile>.pkl`` (the case's properties) are
     written; the returned image carries the array as ``img.probabilities`` (the one thing a caller without an output file gets).
     ``probabilities``: the device's array, ``logits`` then being its decided map (see :func:`convert_...`)."""
@@ -243,11 +247,21 @@ def export_prediction_from_logits(logits, properties: dict, configuration_manage
                                                                                 return_probabilities=True, probabilities=probabilities)
     else:
         seg = convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties, multilabel, tb, regions=conv.class_order)
+    post = None
+    if postprocess is not None:
+        if multilabel:
+            raise ValueError("postprocessing is defined for label-map and region-based models, not for a multilabel model")
+        import time
+        t0 = time.perf_counter()
+        seg, stats, route = postprocess(seg)
+        post = {'route': route, 'stats': stats, 'seconds': time.perf_counter() - t0}
     if ref_image is None:
         ref_image = nrrd.read(properties['sitk_stuff']['files'][0])
     img = segmentation_to_image(seg, ref_image, multilabel, labels, colors)
     if prob is not None:
         img.probabilities = prob
+    if post is not None:
+        img.postprocessing = post
     if ofile_truncated:
         nrrd.write(img, ofile_truncated + dataset_json.get('file_ending', '.nrrd'), True)
         if prob is not None:

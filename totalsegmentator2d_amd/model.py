@@ -50,7 +50,35 @@ class HIPModel:
         self.device_input_stack_masked = True   # ... and a stack whose plan has use_mask_for_norm on a z-score channel (the MR plans): the 3-D hole filling of the non-zero mask, the statistics of the masked samples and the normalisation inside the mask on those planes; numpy's and scipy's bits (preprocess.fill_holes_sweeps_statement, masked_zscore_stack_statement)
         self.device_stack = True         # ... and its decided map from the device, every slice one image of the convention's own entry (_run; needs that convention's switch too); the host route's bytes
         self.device_stack_probabilities = True   # ... and, with save_probabilities, its probabilities: every slice through the kernel of device_probabilities, written in place into ONE float32 [K, Z0, H0, W0] (_run; needs device_stack and the convention's switch, and an untransposed plan); the host route's segmentation bytes, its probabilities to a few float32 units
+        self.device_postprocessing = True   # a model with a postprocessing plan (set_postprocessing): 26-connected labelling of the final uint8 map, component sizes and the removal of all but the largest on the device, every step of the plan between one upload and one download (_run); the host route's bytes (postprocess.keep_largest_components_statement)
+        self._postprocessing = None      # the plan (postprocess.PostprocessingPlan); None - the default - leaves the export exactly as it is
         self._discover()
+        plan = self._param.get('nnu.postprocessing')               # a postprocessing.json or a folder that holds one; True: the model's own folder
+        if plan is None or plan is False:
+            plan = (self._config.get('synthetic') or {}).get('postprocessing')      # ... or a plan list stated beside synthetic weights
+        elif plan is True:
+            if self._data_dir is None:
+                raise ValueError("nnu.postprocessing = True looks in the trained-model folder; a synthetic model has none")
+            plan = self._data_dir
+        self.set_postprocessing(plan)
+
+    def set_postprocessing(self, plan):
+        """The model's postprocessing plan: None (none), a ``postprocess.PostprocessingPlan``, a list of ``(labels_or_regions,
+        background_label)`` steps, or the path of a ``postprocessing.json`` / of a trained-model folder (``postprocess.load_postprocessing``).
+        Defined for label-map and region-based models; a multilabel model is refused here."""
+        if plan is None:
+            self._postprocessing = None
+            return
+        kind = label_convention(self._dataset_json).kind
+        if kind == 'multilabel':
+            raise ValueError(f"a postprocessing plan was given for the {kind} model {self.name!r}: the largest-component step is defined for "
+                             "label-map and region-based models only")
+        from .postprocess import load_postprocessing
+        self._postprocessing = load_postprocessing(plan)
+
+    @property
+    def postprocessing(self):
+        return self._postprocessing
 
     # ------------------------------------------------------------------ configuration (reference wrapper.py:113-162)
     def _discover(self):
@@ -409,6 +437,10 @@ class HIPModel:
             for t, o in zip(group, out):
                 t[5] = o
                 stamps[t[0]]['predicted'] = now
+        # the model's postprocessing plan, if it has one: the export applies it to the final map (export_prediction_from_logits) - on the device
+        # of the predictor's engines under `device_postprocessing`, on the host (the same bytes) with the switch off or no engine of this library
+        post = getattr(self, '_postprocessing', None)
+        post_device = self._input_device(getattr(self, 'device_postprocessing', False)) if post is not None else None
         for name, ofile, ref, data, props, logits in todo:
             ts = self.timestamps = stamps[name]
             try:
@@ -416,6 +448,8 @@ class HIPModel:
                 if save_probabilities:           # (a pair: the device's decided map and its probabilities; else the logits for the host route)
                     more = {'save_probabilities': True, 'probabilities': logits[1] if isinstance(logits, tuple) else None}
                     logits = logits[0] if isinstance(logits, tuple) else logits
+                if post is not None:             # (no plan: the export is called exactly as before)
+                    more['postprocess'] = lambda s, ts=ts: self._postprocess(s, post, post_device, ts)
                 seg = export_prediction_from_logits(logits, props, p.configuration_manager, p.plans_manager, p.dataset_json, ofile,
                                                     ref_image=ref, labels=self.labels,
                                                     colors=self.colors if isinstance(self.colors, dict) else None, **more)
@@ -424,6 +458,14 @@ class HIPModel:
                 raise RuntimeError(f"Export failed for {name}: {ex}") from ex
             results[name] = (ofile + '.nrrd') if result_dir is not None else seg
         return {name: results[name] for name in inputs}
+
+    @staticmethod
+    def _postprocess(seg, plan, device, ts: dict):
+        """The closure :meth:`_run` hands to the export: ``postprocess.apply_postprocessing`` of the final map, stamped ``postprocessed``."""
+        from .postprocess import apply_postprocessing
+        out = apply_postprocessing(seg, plan, device=device)
+        ts['postprocessed'] = time.time()
+        return out
 
     def apply_batch(self, inputs: Union[List, Dict], result_dir: Optional[str] = None, override: bool = True,
                     save_probabilities: bool = False) -> dict:
