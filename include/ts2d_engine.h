@@ -533,6 +533,44 @@ int ts2d_project_coronal_zscore(int device, const void* volume, size_t n_elems, 
                                 long long sy, long long sx, long long base, float* out_max, float* out_mean, float* out_norm,
                                 double* out_stats, int32_t* out_box);
 
+/* Every projection mode of the reference's project() along the coronal axis (ts2d/core/util/image.py:46-101; a TS2D sub-model's channel NAMES are
+ * projection modes, ts2d/tool.py:156-158), on the device, with the addressing of ts2d_project_coronal (volume ... base as there).
+ *   modes        [n_modes] TS2D_PROJECT_* codes, 1 <= n_modes <= TS2D_PROJECT_MAX_MODES; a code may occur more than once
+ *   slice_index  [n_modes]: for a TS2D_PROJECT_SLICE entry the index along y, in [0, ny); ignored for the other codes (never null)
+ *   out_planes   host [n_modes][nz][nx] float32, plane m in mode modes[m].  What a plane holds is stated by totalsegmentator2d_amd.image.project,
+ *                followed by its cast to float32:
+ *                  MAX, MEAN   bit for bit the planes of ts2d_project_coronal
+ *                  MIN         the minimum
+ *                  MEDIAN      the value at index ny / 2 of the sorted ray (the upper median: no averaging), picked in the input type
+ *                  STD         sqrt(sum((v - mean)^2) / (ny - 1)): float64, two passes in index order, multiply and add rounded separately,
+ *                              correctly rounded divide and square root, one rounding to float32; needs ny >= 2
+ *                  FIRST       the first sample != 0 in index order, the sample at index 0 when there is none
+ *                  SLICE       the sample at slice_index[m]
+ *   out_norm     host [n_modes][nz][nx] float32, or NULL: every plane z-scored by itself, as behind ts2d_project_coronal_zscore
+ *   out_stats    host [n_modes][2] float64 {mean, std} of each plane, or NULL (needs out_norm)
+ *   out_box      host [n_modes][4] {first, last non-zero row, first, last non-zero column} of EACH plane ({nz, -1, nx, -1} for a plane of
+ *                zeros), or NULL (needs out_norm): the caller forms the union over the planes that make up one network input
+ *   status       a bit word, 0 when the outputs are the result.  TS2D_PROJECT_NONFINITE: a float32 volume holds a NaN or an infinity;
+ *                TS2D_PROJECT_RAY_TOO_LONG: ny > TS2D_PROJECT_RAY_CAP (nothing was launched).  With a bit set the call still returns TS2D_OK,
+ *                the outputs are unspecified and the caller must not use them: it takes the host route.
+ * Every argument is checked before any device work and refused by name with TS2D_ERR_INVALID: a null pointer, an unknown mode, a slice index
+ * outside [0, ny), n_modes outside its range, an extent below 1, a view that leaves the buffer.  Nothing is written then.
+ * Host pointers in and out; synchronous; the call owns its device scratch and frees it on every path.  (ABI 9, optional symbol) */
+#define TS2D_PROJECT_MAX 0
+#define TS2D_PROJECT_MIN 1
+#define TS2D_PROJECT_MEAN 2
+#define TS2D_PROJECT_MEDIAN 3
+#define TS2D_PROJECT_STD 4
+#define TS2D_PROJECT_FIRST 5
+#define TS2D_PROJECT_SLICE 6
+#define TS2D_PROJECT_MAX_MODES 16
+#define TS2D_PROJECT_RAY_CAP 8192
+#define TS2D_PROJECT_NONFINITE 1
+#define TS2D_PROJECT_RAY_TOO_LONG 2
+int ts2d_project_coronal_modes(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy,
+                               long long sx, long long base, const int32_t* modes, const int32_t* slice_index, int n_modes, float* out_planes,
+                               float* out_norm, double* out_stats, int32_t* out_box, int32_t* status);
+
 /* nnU-Net's input resample for the 2-D configurations on the device: every plane of src [n_planes][in_h][in_w] float32 resampled to
  * dst [n_planes][out_h][out_w] float32 as skimage.transform.resize(plane, (out_h, out_w), order=3, mode='edge', anti_aliasing=False,
  * clip=True) does it (reference flow DefaultPreprocessor.run_case, ts2d/core/inference/prediction_worker.py:194-199, for a case whose

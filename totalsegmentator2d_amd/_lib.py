@@ -76,6 +76,9 @@ class CcStep(ctypes.Structure):
 
 
 CC_GIVE_UP = 1                                              # TS2D_CC_GIVE_UP
+PROJECT_MODES = {'max': 0, 'min': 1, 'mean': 2, 'median': 3, 'std': 4, 'first': 5, 'slice': 6}      # TS2D_PROJECT_*
+PROJECT_MAX_MODES, PROJECT_RAY_CAP = 16, 8192               # TS2D_PROJECT_MAX_MODES, TS2D_PROJECT_RAY_CAP
+PROJECT_NONFINITE, PROJECT_RAY_TOO_LONG = 1, 2              # TS2D_PROJECT_NONFINITE, TS2D_PROJECT_RAY_TOO_LONG
 
 # shorthands of the table below: int, void *, size_t, long long, unsigned long long, char *; pointers to a void * and to the three descriptors
 _I, _P, _Z, _LL, _ULL, _S = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_char_p
@@ -107,6 +110,7 @@ SIGNATURES = {
     'ts2d_probabilities_from_logits': (_I, [_I, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32 * 4), _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     'ts2d_project_coronal': (_I, _PROJECT),
     'ts2d_project_coronal_zscore': (_I, _PROJECT + [_P, _P, _P]),
+    'ts2d_project_coronal_modes': (_I, _PROJECT[:-2] + [_P, _P, _I, _P, _P, _P, _P, _P]),
     'ts2d_resample_cubic': (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),
     'ts2d_planes_create': (_I, [_I, _P, _I, _I, _I, _PP]),
     'ts2d_planes_crop_zscore': (_I, [_P, ctypes.POINTER(ctypes.c_int32 * 4), _P, ctypes.POINTER(_I)]),
@@ -143,8 +147,9 @@ SYMBOLS = tuple(SIGNATURES)
 # a library built before them lacks the symbols, still loads, and the callers keep the host route; the probabilities entries likewise (the one for stacks came after the other two: each is looked up on its own)
 # ... and the residual-encoder entry: without it a ResidualEncoderUNet cannot be created (Engine says so), a plain net is unaffected
 # ... and the largest-component postprocessing: without it postprocess.apply_postprocessing keeps the host route
+# ... and the projection modes: without the entry TS2D keeps the host route for a channel name beyond max / mean
 OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n
-                     or n in ('ts2d_engine_create_residual', 'ts2d_keep_largest_components'))
+                     or n in ('ts2d_engine_create_residual', 'ts2d_keep_largest_components', 'ts2d_project_coronal_modes'))
 
 
 class EngineLibraryError(RuntimeError):

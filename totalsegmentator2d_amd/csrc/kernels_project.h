@@ -1,8 +1,10 @@
 // Coronal maximum / mean projection of a CT volume (the step right before the hot path: reference ts2d/tool.py:152-160 ->
 // ts2d/core/util/image.py:46-101, sitk Max/MeanProjectionImageFilter along axis 1).  One thread per output pixel (z, x);
 // the volume is addressed through signed element strides, so the axis permutation / flips of `reorient_image` (DICOMOrient
-// 'RAI') cost nothing.  Pure HBM streaming.  Mean of integer volumes follows ITK: exact sum, truncated back to the
-// integer type [UPSTREAM-RECALL], then cast to float (reference tool.py:182-185).
+// 'RAI') cost nothing.  Pure HBM streaming.  The mean is REAL-valued for every input type, as include/ts2d_engine.h and
+// image.project state it and the reference's pre-projected sample assets pin it: the sum in index order (exact for an integer
+// volume) divided in double, rounded once to float (the reference's cast to Float32, tool.py:182-185).  The other modes of the
+// reference's project(): kernels_project_modes.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

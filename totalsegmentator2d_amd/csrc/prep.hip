@@ -4,6 +4,7 @@
 // The host arithmetic behind them is prep_plan.cpp; every device buffer of a call is a DevMem, so HIP_TRY may return wherever it fails.
 #include "engine_internal.h"
 #include "kernels_project.h"
+#include "kernels_project_modes.h"
 #include "kernels_resample_in.h"
 #include "kernels_prep.h"
 #include "kernels_prep_schemes.h"
@@ -85,6 +86,126 @@ int project_coronal_impl(int device, const void* volume, size_t n_elems, int dty
     }
     HIP_TRY(hipMemcpy(out_max, d_max, obytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_mean, d_mean, obytes, hipMemcpyDeviceToHost));
+    return TS2D_OK;
+}
+
+static_assert(kPmMax == TS2D_PROJECT_MAX && kPmMin == TS2D_PROJECT_MIN && kPmMean == TS2D_PROJECT_MEAN && kPmMedian == TS2D_PROJECT_MEDIAN &&
+              kPmStd == TS2D_PROJECT_STD && kPmFirst == TS2D_PROJECT_FIRST && kPmSlice == TS2D_PROJECT_SLICE && kPmMaxModes == TS2D_PROJECT_MAX_MODES &&
+              kPmStatusNonFinite == TS2D_PROJECT_NONFINITE && kPmStatusRayTooLong == TS2D_PROJECT_RAY_TOO_LONG && kPmRayCap == TS2D_PROJECT_RAY_CAP,
+              "the projection modes speak the C header's numbers");
+
+// The launches of ts2d_project_coronal_modes for one sample type.  d_first[kind]: the first plane asked for of that kind (null: none).
+template <typename T>
+int project_modes_launch(const T* d_vol, int nz, int ny, int nx, long long sz, long long sy, long long sx, long long base, bool stream,
+                         const PmStreamArgs& sa, float* d_median, int* d_status) {
+    const long long n = (long long)nz * nx;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (stream) hipLaunchKernelGGL(project_modes_stream<T>, dim3(grid), dim3(256), 0, 0, d_vol, nz, ny, nx, sz, sy, sx, base, sa, d_status);
+    if (d_median) {
+        const int tile_x = pm_tile_x(ny, (int)sizeof(T));
+        if (tile_x) {
+            int lg = 4;
+            while ((1 << lg) < tile_x) ++lg;
+            const int tiles_x = (nx + tile_x - 1) / tile_x, n_full = ny * tile_x / kPmThreads;
+            const size_t smem = kPmLdsCountBytes + align_up((size_t)ny * tile_x * sizeof(T), 16);
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(project_median_lds<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            hipLaunchKernelGGL(project_median_lds<T>, dim3((unsigned)((long long)tiles_x * nz)), dim3(kPmThreads), smem, 0, d_vol, nz, ny, nx, sz, sy, sx,
+                               base, lg, tiles_x, n_full, d_median);
+        } else {
+            hipLaunchKernelGGL(project_median_global<T>, dim3(grid), dim3(256), 0, 0, d_vol, nz, ny, nx, sz, sy, sx, base, d_median);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return TS2D_OK;
+}
+
+int project_coronal_modes_impl(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy,
+                               long long sx, long long base, const int* modes, const int* slice_index, int n_modes, float* out_planes,
+                               float* out_norm, double* out_stats, int* out_box, int* status) {
+    const char* const E = "ts2d_project_coronal_modes";
+    if (!volume) return fail(TS2D_ERR_INVALID, "%s: volume is null", E);
+    if (!modes) return fail(TS2D_ERR_INVALID, "%s: modes is null", E);
+    if (!slice_index) return fail(TS2D_ERR_INVALID, "%s: slice_index is null", E);
+    if (!out_planes) return fail(TS2D_ERR_INVALID, "%s: out_planes is null", E);
+    if (!status) return fail(TS2D_ERR_INVALID, "%s: status is null", E);
+    if (!out_norm && (out_stats || out_box)) return fail(TS2D_ERR_INVALID, "%s: out_stats / out_box without out_norm", E);
+    static const int esize[5] = {2, 1, 4, 2, 4};
+    if (dtype < 0 || dtype > 4) return fail(TS2D_ERR_INVALID, "%s: dtype %d unknown", E, dtype);
+    if (n_modes < 1 || n_modes > kPmMaxModes) return fail(TS2D_ERR_INVALID, "%s: n_modes %d outside 1 ... %d", E, n_modes, kPmMaxModes);
+    if (nz < 1 || ny < 1 || nx < 1) return fail(TS2D_ERR_INVALID, "%s: extents nz %d, ny %d, nx %d below 1", E, nz, ny, nx);
+    if ((long long)nz * nx * n_modes > kPrepMaxSamples)
+        return fail(TS2D_ERR_INVALID, "%s: n_modes %d planes of nz %d x nx %d are more than one call takes (2^28 samples)", E, n_modes, nz, nx);
+    bool want[kPmKinds] = {};
+    for (int m = 0; m < n_modes; ++m) {
+        if (modes[m] < 0 || modes[m] >= kPmKinds) return fail(TS2D_ERR_INVALID, "%s: modes[%d] = %d is an unknown mode", E, m, modes[m]);
+        if (modes[m] == kPmSlice && (slice_index[m] < 0 || slice_index[m] >= ny))
+            return fail(TS2D_ERR_INVALID, "%s: slice_index[%d] = %d outside [0, ny = %d)", E, m, slice_index[m], ny);
+        want[modes[m]] = true;
+    }
+    if (want[kPmStd] && ny < 2) return fail(TS2D_ERR_INVALID, "%s: the std mode needs ny >= 2, found ny %d", E, ny);
+    {   // every element the view can touch must lie inside the buffer
+        long long lo = base, hi = base;
+        const long long ext[3] = {(long long)(nz - 1) * sz, (long long)(ny - 1) * sy, (long long)(nx - 1) * sx};
+        for (int k = 0; k < 3; ++k) { if (ext[k] < 0) lo += ext[k]; else hi += ext[k]; }
+        if (lo < 0 || hi >= (long long)n_elems) return fail(TS2D_ERR_INVALID, "%s: the strided view (base, sz, sy, sx) leaves the buffer of n_elems %zu", E, n_elems);
+    }
+    *status = 0;
+    if (ny > kPmRayCap) { *status = kPmStatusRayTooLong; return TS2D_OK; }     // nothing is launched, nothing is written
+    HIP_TRY(hipSetDevice(device));
+    const long long n = (long long)nz * nx;
+    const size_t vbytes = n_elems * esize[dtype], obytes = (size_t)n * sizeof(float);
+    // [volume | planes x n_modes | normalised x n_modes | partial sums | stats | boxes | status]
+    const size_t o_proj = align_up(vbytes, 256), o_norm = align_up(o_proj + n_modes * obytes, 256), o_part = align_up(o_norm + n_modes * obytes, 256);
+    const size_t o_stats = o_part + (size_t)n_modes * kZBlocks * sizeof(double), o_box = o_stats + (size_t)n_modes * 2 * sizeof(double);
+    const size_t o_status = o_box + (size_t)n_modes * 4 * sizeof(int);
+    DevMem d;
+    HIP_TRY(d.alloc(o_status + sizeof(int)));
+    float* d_planes = d.as<float>(o_proj);
+    int* d_status = d.as<int>(o_status);
+    HIP_TRY(hipMemcpy(d.as<char>(), volume, vbytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_status, 0, sizeof(int)));
+    // a kind asked for twice is computed once, into its first plane, and copied to the others
+    PmStreamArgs sa = {};
+    float* d_first[kPmKinds] = {};
+    for (int m = 0; m < n_modes; ++m) {
+        float* plane = d_planes + (size_t)m * n;
+        if (modes[m] == kPmSlice) { sa.slice_y[sa.n_slices] = slice_index[m]; sa.slice_out[sa.n_slices++] = plane; }
+        else if (!d_first[modes[m]]) d_first[modes[m]] = plane;
+    }
+    for (int k = 0; k < kPmKinds; ++k) sa.out[k] = (k == kPmMedian || k == kPmSlice) ? nullptr : d_first[k];
+    // a float volume is always streamed: that pass is what finds a non-finite sample
+    const bool stream = dtype == 2 || sa.n_slices > 0 || want[kPmMax] || want[kPmMin] || want[kPmMean] || want[kPmStd] || want[kPmFirst];
+    switch (dtype) {
+        case 0: TRY(project_modes_launch(d.as<const int16_t>(), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status)); break;
+        case 1: TRY(project_modes_launch(d.as<const uint8_t>(), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status)); break;
+        case 2: TRY(project_modes_launch(d.as<const float>(), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status)); break;
+        case 3: TRY(project_modes_launch(d.as<const uint16_t>(), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status)); break;
+        default: TRY(project_modes_launch(d.as<const int32_t>(), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status)); break;
+    }
+    for (int m = 0; m < n_modes; ++m) {
+        float* plane = d_planes + (size_t)m * n;
+        if (modes[m] != kPmSlice && d_first[modes[m]] != plane) HIP_TRY(hipMemcpy(plane, d_first[modes[m]], obytes, hipMemcpyDeviceToDevice));
+    }
+    HIP_TRY(hipMemcpy(status, d_status, sizeof(int), hipMemcpyDeviceToHost));
+    if (*status) return TS2D_OK;                                   // a non-finite sample: the planes are no result, the caller takes the host route
+    if (out_norm) {          // per-plane z-score as behind ts2d_project_coronal_zscore, the non-zero box per plane
+        float* d_norm = d.as<float>(o_norm);
+        double* d_part = d.as<double>(o_part); double* d_stats = d.as<double>(o_stats);
+        int* d_box = d.as<int>(o_box);
+        int box0[4 * kPmMaxModes];
+        for (int m = 0; m < n_modes; ++m) { box0[4 * m] = nz; box0[4 * m + 1] = -1; box0[4 * m + 2] = nx; box0[4 * m + 3] = -1; }
+        HIP_TRY(hipMemcpy(d_box, box0, (size_t)n_modes * 4 * sizeof(int), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(zs_partial<0>, dim3(kZBlocks, n_modes), dim3(256), 0, 0, d_planes, n, d_stats, d_part);
+        hipLaunchKernelGGL(zs_combine<0>, dim3(1), dim3(n_modes), 0, 0, d_part, n, d_stats);
+        hipLaunchKernelGGL(zs_partial<1>, dim3(kZBlocks, n_modes), dim3(256), 0, 0, d_planes, n, d_stats, d_part);
+        hipLaunchKernelGGL(zs_combine<1>, dim3(1), dim3(n_modes), 0, 0, d_part, n, d_stats);
+        hipLaunchKernelGGL(zs_apply_planes, dim3((unsigned)((n + 255) / 256), n_modes), dim3(256), 0, 0, d_planes, n, nx, d_stats, d_norm, d_box);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(out_norm, d_norm, n_modes * obytes, hipMemcpyDeviceToHost));
+        if (out_stats) HIP_TRY(hipMemcpy(out_stats, d_stats, (size_t)n_modes * 2 * sizeof(double), hipMemcpyDeviceToHost));
+        if (out_box) HIP_TRY(hipMemcpy(out_box, d_box, (size_t)n_modes * 4 * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(hipMemcpy(out_planes, d_planes, n_modes * obytes, hipMemcpyDeviceToHost));
     return TS2D_OK;
 }
 
@@ -390,6 +511,13 @@ int ts2d_project_coronal_zscore(int device, const void* volume, size_t n_elems, 
                                 double* out_stats, int32_t* out_box) {
     if (!out_norm) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal_zscore: null argument");
     return project_coronal_impl(device, volume, n_elems, dtype, nz, ny, nx, sz, sy, sx, base, out_max, out_mean, out_norm, out_stats, out_box);
+}
+
+int ts2d_project_coronal_modes(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy,
+                               long long sx, long long base, const int32_t* modes, const int32_t* slice_index, int n_modes, float* out_planes,
+                               float* out_norm, double* out_stats, int32_t* out_box, int32_t* status) {
+    return project_coronal_modes_impl(device, volume, n_elems, dtype, nz, ny, nx, sz, sy, sx, base, modes, slice_index, n_modes, out_planes, out_norm,
+                                      out_stats, out_box, status);
 }
 
 int ts2d_resample_cubic(int device, const float* src, int n_planes, int in_h, int in_w, int out_h, int out_w, const float* lo_hi, float* dst) {

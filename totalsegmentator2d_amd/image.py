@@ -1,7 +1,7 @@
 """Image operations either side of the hot path, on :class:`nrrd.Image` (the stand-in for ``sitk.Image``).
 
 Mirrors the subset of the reference's ``ts2d/core/util/image.py`` and ``ts2d/core/util/meta.py`` that ``TS2D.predict`` /
-``Result.save`` use: ``reorient_image`` (:32-43), ``project`` (:46-101, modes max/mip/min/mean/avg), ``reduce_dimensions``
+``Result.save`` use: ``reorient_image`` (:32-43), ``project`` (:46-101, every mode but multiclass), ``reduce_dimensions``
 (:241-258), ``combine_segmentations`` (:490-510), ``split_channels`` (:512-520), ``get_label_mask`` (meta.py:51-62),
 ``set_annotation_meta`` / ``get_annotation_labels`` (meta.py:172-240,289-330).  SimpleITK is not installed here, so the ITK
 filters are restated in numpy; where ITK behaviour could not be verified offline the docstring says [UPSTREAM-RECALL].
@@ -63,31 +63,94 @@ def reorient_image(img: Image, orient: str = 'RAI') -> Image:
     return out
 
 
+_SLICE_POSITIONS = {'first': 0.0, 'middle': 0.5, 'last': 1.0}
+
+
+def parse_projection_mode(mode) -> tuple:
+    """A projection mode as the reference reads it (image.py:58-62): lower-case, stripped, split at the first ``:`` into a name and an
+    optional parameter (``'slice:0.25'`` -> ``('slice', '0.25')``, ``'max'`` -> ``('max', None)``)."""
+    name, _, param = str(mode).lower().strip().partition(':')
+    return name.strip(), (param.strip() if param else None)
+
+
+def slice_projection_index(param, n: int) -> int:
+    """Index along a ray of ``n`` samples of ``slice:<param>``: ``param`` is a float or first = 0, middle = 0.5, last = 1; the index is
+    ``int(clip(np.round(n * pos), 0, n))`` (``np.round``: half to even).  An index equal to n is outside the ray and raises, as it does in the
+    reference - so ``slice:last`` raises."""
+    if param in _SLICE_POSITIONS:
+        pos = _SLICE_POSITIONS[param]
+    else:
+        try:
+            pos = float(param)
+        except (TypeError, ValueError):
+            raise RuntimeError(f"Unsupported slice position: {param!r} (a number, or one of {sorted(_SLICE_POSITIONS)})") from None
+        if not np.isfinite(pos):
+            raise RuntimeError(f"Unsupported slice position: {param!r} (not finite)")
+    idx = int(np.clip(np.round(n * pos), 0, n))
+    if not 0 <= idx < n:
+        raise RuntimeError(f"Slice index {idx} (position {pos}) is outside the valid range [0, {n}) of the projection axis")
+    return idx
+
+
 def project(img: Image, mode: str = 'max', axis=-1) -> Image:
-    """``sitk.{Maximum,Minimum,Mean}ProjectionImageFilter`` along ``axis``: the projected axis keeps size 1 and its
-    origin (reference image.py:97-100).  The mean is REAL-valued (float64: ITK accumulates and divides in double), also for
-    integer volumes - pinned by the reference's own pre-projected assets (``sample_s0332`` / ``sample_s0616``: channel 0 is
-    exactly ``double(sum) / n``; tests/test_oracle.py); the reference casts to Float32 afterwards (tool.py:182-185)."""
+    """The reference's ``project`` (image.py:46-101) along ``axis``: the projected axis keeps size 1 and its origin (:97-100).  The mode is
+    a name with an optional parameter (:func:`parse_projection_mode`); n is the length of a ray.
+
+    ``max`` / ``mip``, ``min``: ``sitk.{Maximum,Minimum}ProjectionImageFilter``, in the input type.
+    ``avg`` / ``mean``: the mean is REAL-valued (float64: ITK accumulates and divides in double), also for integer volumes - pinned by the
+    reference's own pre-projected assets (``sample_s0332`` / ``sample_s0616``: channel 0 is exactly ``double(sum) / n``; tests/test_oracle.py);
+    the reference casts to Float32 afterwards (tool.py:182-185).
+    ``median``: the value at index ``n // 2`` of the sorted ray - the upper median, no averaging of two values - in the input type
+    [UPSTREAM-RECALL: ITK's MedianAccumulator runs ``std::nth_element`` at ``size / 2``].  The sign of a float zero is unspecified.
+    ``std``: ``sqrt(sum((v - mean)**2) / (n - 1))`` in float64, two passes: the mean as for ``mean``, the squares added in index order, no
+    fused multiply-add [UPSTREAM-RECALL: ITK's StandardDeviationAccumulator divides by ``size - 1``].  n >= 2.
+    ``first`` / ``depth``: the first sample ``!= 0`` in index order along the ray, the sample at index 0 when there is none (the reference's
+    ``argmax(arr != 0)`` and ``take_along_axis``), in the input type.
+    ``slice:<pos>``: the sample at :func:`slice_projection_index`, in the input type.
+    ``multiclass:*``, ``xr`` and unknown names raise ``Unsupported filter mode`` (multiclass is a label-volume mode with a vector result)."""
     ax = axis_name_to_index(axis) if isinstance(axis, str) else list(range(img.dimension))[axis]
-    mode = str(mode).lower().strip()
+    name, param = parse_projection_mode(mode)
     npax = _np_axis(img, ax)
     a = img.array
-    if mode in ('max', 'mip'):
+    n = a.shape[npax]
+    if param is not None and name != 'slice':
+        raise RuntimeError(f"Unsupported filter mode: {str(mode).lower().strip()}")
+    if name in ('max', 'mip'):
         r = a.max(axis=npax, keepdims=True)
-    elif mode == 'min':
+    elif name == 'min':
         r = a.min(axis=npax, keepdims=True)
-    elif mode in ('avg', 'mean'):
-        if np.issubdtype(a.dtype, np.integer):      # exact integer sum (15x faster than a float64 copy of a CT volume)
-            r = a.sum(axis=npax, keepdims=True, dtype=np.int64).astype(np.float64) / np.float64(a.shape[npax])
-        else:                                       # ITK's accumulator: slices added in index order, in double
-            v = np.moveaxis(a, npax, 0)
-            acc = np.zeros(v.shape[1:], np.float64)
-            for k in range(v.shape[0]):
-                acc += v[k]
-            r = np.expand_dims(acc / np.float64(v.shape[0]), npax)
+    elif name in ('avg', 'mean'):
+        r = _ray_mean64(a, npax)
+    elif name == 'median':
+        r = np.take(np.partition(a, n // 2, axis=npax), [n // 2], axis=npax)
+    elif name == 'std':
+        mean = _ray_mean64(a, npax)
+        v = np.moveaxis(a, npax, 0)
+        m0 = np.squeeze(mean, npax)
+        acc = np.zeros(v.shape[1:], np.float64)
+        for k in range(n):                          # squares in index order, each product rounded before it is added
+            d = v[k].astype(np.float64) - m0
+            acc += d * d
+        with np.errstate(divide='ignore', invalid='ignore'):
+            r = np.expand_dims(np.sqrt(acc / np.float64(n - 1)), npax)
+    elif name in ('first', 'depth'):
+        r = np.take_along_axis(a, np.expand_dims(np.argmax(a != 0, axis=npax), npax), axis=npax)
+    elif name == 'slice':
+        r = np.take(a, [slice_projection_index(param, n)], axis=npax)
     else:
-        raise RuntimeError(f"Unsupported filter mode: {mode}")
+        raise RuntimeError(f"Unsupported filter mode: {str(mode).lower().strip()}")
     return Image(np.ascontiguousarray(r), img.spacing, img.origin, img.direction, img.components, dict(img.meta), img.space)
+
+
+def _ray_mean64(a: np.ndarray, npax: int) -> np.ndarray:
+    """float64 mean along ``npax`` (kept with size 1): exact integer sum, or ITK's accumulator for a float volume."""
+    if np.issubdtype(a.dtype, np.integer):          # exact integer sum (15x faster than a float64 copy of a CT volume)
+        return a.sum(axis=npax, keepdims=True, dtype=np.int64).astype(np.float64) / np.float64(a.shape[npax])
+    v = np.moveaxis(a, npax, 0)                     # ITK's accumulator: slices added in index order, in double
+    acc = np.zeros(v.shape[1:], np.float64)
+    for k in range(v.shape[0]):
+        acc += v[k]
+    return np.expand_dims(acc / np.float64(v.shape[0]), npax)
 
 
 _GPU_DTYPES = {'int16': 0, 'uint8': 1, 'float32': 2, 'uint16': 3, 'int32': 4}
@@ -103,7 +166,47 @@ def _reorient_plan(img: Image):
     return perm, flips
 
 
-def project_coronal_gpu(img: Image, device: int = 0, zscore: bool = False):
+class ProjectionDeviceRefused(RuntimeError):
+    """``ts2d_project_coronal_modes`` set a status bit (``.status``): a non-finite sample in a float volume, or a ray above the cap.  Its outputs
+    were not used; the caller takes the host route (:func:`project` behind :func:`reorient_image`)."""
+    def __init__(self, status: int):
+        from . import _lib
+        why = [t for bit, t in ((_lib.PROJECT_NONFINITE, 'the volume holds a non-finite sample'),
+                                (_lib.PROJECT_RAY_TOO_LONG, f'the rays are longer than {_lib.PROJECT_RAY_CAP} samples')) if status & bit]
+        super().__init__(f"the device projection refused the volume (status {status}): " + '; '.join(why or ['unknown status bit']))
+        self.status = int(status)
+
+
+def device_projection_mode(mode, n: int):
+    """(TS2D_PROJECT_* code, slice index) of a projection mode the device entry serves for rays of ``n`` samples, else None - an unknown name,
+    ``multiclass`` / ``xr``, or a slice that :func:`project` refuses: those keep the host route, which raises what it raises."""
+    from . import _lib
+    name, param = parse_projection_mode(mode)
+    name = {'mip': 'max', 'avg': 'mean', 'depth': 'first'}.get(name, name)
+    if name == 'slice':
+        try:
+            return _lib.PROJECT_MODES['slice'], slice_projection_index(param, n)
+        except RuntimeError:
+            return None
+    if param is not None or name not in _lib.PROJECT_MODES or (name == 'std' and n < 2):
+        return None
+    return _lib.PROJECT_MODES[name], 0
+
+
+def _coronal_view(img: Image):
+    """The volume's buffer and the reoriented view [z][y][x] over it as (array, (nz, ny, nx), (sz, sy, sx), base) in elements, plus the plan."""
+    perm, flips = _reorient_plan(img)
+    a = np.ascontiguousarray(img.array)
+    view = np.transpose(a, [2 - perm[2 - k] for k in range(3)])          # numpy axis k = sitk axis 2 - k
+    for k in range(3):
+        if flips[k]:
+            view = np.flip(view, axis=2 - k)
+    it = a.dtype.itemsize
+    base = (view.__array_interface__['data'][0] - a.__array_interface__['data'][0]) // it
+    return a, view.shape, tuple(s // it for s in view.strides), base, perm, flips
+
+
+def project_coronal_gpu(img: Image, device: int = 0, zscore: bool = False, modes=None):
     """max and mean coronal projections of a 3-D volume on the MI355X (C-ABI ``ts2d_project_coronal``): equals
     ``project(reorient_image(img), mode, 'coronal')`` for mode in (max, mean), as float32 images, without the host-side
     reorientation copy.  Returns {'max': Image, 'mean': Image} with size (nx, 1, nz).
@@ -111,22 +214,45 @@ def project_coronal_gpu(img: Image, device: int = 0, zscore: bool = False):
     ``zscore=True`` (C-ABI ``ts2d_project_coronal_zscore``) also normalises both projections on the device - nnU-Net's
     ZScoreNormalization, float64 statistics - and returns them under ``'zscore'``: ``{'norm': [2, nz, nx] float32 in
     (max, mean) order, 'stats': (mean, std) x 2, 'box': non-zero bounding box}``; ``DefaultPreprocessor.run_case_npy`` uses it
-    in place of its host pass when nnU-Net's crop-to-nonzero is the identity (``preprocess.py``)."""
+    in place of its host pass when nnU-Net's crop-to-nonzero is the identity (``preprocess.py``).
+
+    ``modes``: a list of projection mode names (at most 16 distinct ones, each served by :func:`device_projection_mode`) takes the C-ABI
+    ``ts2d_project_coronal_modes`` instead and returns ``{name: Image}`` under the names as given - each equal to
+    ``cast(project(reorient_image(img), name, 'coronal'), float32)`` - and with ``zscore=True`` ``'zscore'`` =
+    ``{name: {'norm': [nz, nx] float32, 'stats': (mean, std), 'box': that plane's own non-zero box, 'shape': (nz, nx)}}``.  Raises
+    :class:`ProjectionDeviceRefused` when the entry sets a status bit."""
     from . import _lib
     if img.dimension != 3 or img.components != 1 or img.array.dtype.name not in _GPU_DTYPES:
         raise RuntimeError(f"GPU projection needs a scalar 3-D volume of type {sorted(_GPU_DTYPES)}, found {img.array.dtype}")
-    perm, flips = _reorient_plan(img)
-    a = np.ascontiguousarray(img.array)
-    view = np.transpose(a, [2 - perm[2 - k] for k in range(3)])          # numpy axis k = sitk axis 2 - k
-    for k in range(3):
-        if flips[k]:
-            view = np.flip(view, axis=2 - k)
-    nz, ny, nx = view.shape
-    it = a.dtype.itemsize
-    base = (view.__array_interface__['data'][0] - a.__array_interface__['data'][0]) // it
-    sz, sy, sx = (s // it for s in view.strides)
-    omax = np.empty((nz, nx), np.float32); omean = np.empty((nz, nx), np.float32)
+    a, (nz, ny, nx), (sz, sy, sx), base, perm, flips = _coronal_view(img)
     lib = _lib.load()
+    sp = tuple(img.spacing[ax] for ax in perm)
+    geo = _reoriented_geometry(img, perm, flips)
+    if modes is not None:
+        names = list(dict.fromkeys(modes))
+        plan = [device_projection_mode(m, ny) for m in names]
+        if not names or any(p is None for p in plan):
+            raise RuntimeError(f"GPU projection does not serve the modes {[m for m, p in zip(names, plan) if p is None] or names}")
+        if not hasattr(lib, 'ts2d_project_coronal_modes'):
+            raise RuntimeError("ts2d_project_coronal_modes is missing from the engine library (built before the projection modes)")
+        codes = np.array([p[0] for p in plan], np.int32); sidx = np.array([p[1] for p in plan], np.int32)
+        M = len(names)
+        planes = np.empty((M, nz, nx), np.float32); status = np.zeros(1, np.int32)
+        norm = np.empty((M, nz, nx), np.float32) if zscore else None
+        stats = np.empty((M, 2), np.float64) if zscore else None
+        box = np.empty((M, 4), np.int32) if zscore else None
+        _lib.check(lib.ts2d_project_coronal_modes(int(device), a.ctypes.data, a.size, _GPU_DTYPES[a.dtype.name], nz, ny, nx, sz, sy, sx, base,
+                                                  codes.ctypes.data, sidx.ctypes.data, M, planes.ctypes.data,
+                                                  norm.ctypes.data if zscore else None, stats.ctypes.data if zscore else None,
+                                                  box.ctypes.data if zscore else None, status.ctypes.data), 'ts2d_project_coronal_modes')
+        if int(status[0]):
+            raise ProjectionDeviceRefused(int(status[0]))
+        out = {m: Image(planes[k].reshape(nz, 1, nx), sp, geo[0], geo[1], 1, dict(img.meta), img.space) for k, m in enumerate(names)}
+        if zscore:
+            out['zscore'] = {m: {'norm': norm[k], 'stats': (float(stats[k, 0]), float(stats[k, 1])), 'box': tuple(int(v) for v in box[k]),
+                                 'shape': (nz, nx)} for k, m in enumerate(names)}
+        return out
+    omax = np.empty((nz, nx), np.float32); omean = np.empty((nz, nx), np.float32)
     zs = None
     if zscore:
         norm = np.empty((2, nz, nx), np.float32); stats = np.empty(4, np.float64); box = np.empty(4, np.int32)
@@ -137,8 +263,6 @@ def project_coronal_gpu(img: Image, device: int = 0, zscore: bool = False):
     else:
         _lib.check(lib.ts2d_project_coronal(int(device), a.ctypes.data, a.size, _GPU_DTYPES[a.dtype.name], nz, ny, nx, sz, sy, sx, base,
                                             omax.ctypes.data, omean.ctypes.data), 'ts2d_project_coronal')
-    sp = tuple(img.spacing[ax] for ax in perm)
-    geo = _reoriented_geometry(img, perm, flips)
     out = {m: Image(arr.reshape(nz, 1, nx), sp, geo[0], geo[1], 1, dict(img.meta), img.space) for m, arr in (('max', omax), ('mean', omean))}
     if zs is not None:
         out['zscore'] = zs

@@ -201,14 +201,16 @@ class TS2D:
         projections = cache.setdefault('projections', {})
         if get_actual_dimension(input) > 2:
             need = [n for _, n in channels if n not in projections]
-            if need and self._gpu_projection and input.components == 1 and input.array.dtype.name in ('int16', 'uint8', 'float32', 'uint16', 'int32') \
-                    and all(n.lower() in ('max', 'mip', 'mean', 'avg') for n in need):
+            on_device = self._gpu_projection and input.components == 1 and input.array.dtype.name in ('int16', 'uint8', 'float32', 'uint16', 'int32')
+            if need and on_device and all(n.lower() in ('max', 'mip', 'mean', 'avg') for n in need):
                 # product path: both projections in one pass over the volume on the GPU, reorientation folded into the strides
                 from .image import project_coronal_gpu
                 pr = project_coronal_gpu(input, getattr(model._predictor.device, 'index', 0) or 0, zscore=True)
                 for n in need:
                     projections[n] = pr['max' if n.lower() in ('max', 'mip') else 'mean']
                 cache['device_zscore'] = pr['zscore']      # both projections normalised on the device (preprocess.py uses it)
+            elif on_device and not self._max_mean_only(channels) and self._project_modes_on_device(model, input, channels, cache):
+                pass                                       # every channel of this sub-model projected and normalised by ts2d_project_coronal_modes
             else:
                 input = reorient_image(input, 'RAI')
             chs = []
@@ -228,10 +230,48 @@ class TS2D:
         if dz is not None and not native_2d and all(n.lower() in ('max', 'mip', 'mean', 'avg') for _, n in channels):
             # channel order of THIS model over the (max, mean) planes the device normalised
             input2d.device_zscore = dict(dz, order=tuple(0 if n.lower() in ('max', 'mip') else 1 for _, n in channels))
+        zp = cache.get('device_zscore_planes', {})
+        if not native_2d and not self._max_mean_only(channels) and all(n in zp for _, n in channels):
+            # this model's own channel set over the planes ts2d_project_coronal_modes normalised one by one: stacked in its channel order,
+            # the non-zero box the union of its planes' boxes - the shape preprocess.py reads
+            mine = [zp[n] for _, n in channels]
+            input2d.device_zscore = {'norm': np.stack([p['norm'] for p in mine]), 'order': tuple(range(len(mine))),
+                                     'stats': tuple(v for p in mine for v in p['stats']), 'shape': mine[0]['shape'],
+                                     'box': (min(p['box'][0] for p in mine), max(p['box'][1] for p in mine),
+                                             min(p['box'][2] for p in mine), max(p['box'][3] for p in mine))}
         # one preprocessing per distinct (channels, plan) of the case, shared by the sub-models (they run on threads: model.py takes the lock)
         import threading
         input2d.preprocess_cache = cache.setdefault('preprocessed', {'lock': threading.Lock(), 'items': {}})
         return input, input2d, native_2d
+
+    @staticmethod
+    def _max_mean_only(channels) -> bool:
+        return all(n.lower() in ('max', 'mip', 'mean', 'avg') for _, n in channels)
+
+    def _project_modes_on_device(self, model, input: nrrd.Image, channels, cache: dict) -> bool:
+        """A sub-model with a channel name beyond max / mean: ONE call of ``ts2d_project_coronal_modes`` for those of its names that the case
+        has no device-normalised plane of yet (``cache['device_zscore_planes']``, shared by name across the sub-models like the projections).
+        False - nothing taken - when a name is no device mode, the entry is missing, or it refused the volume (a non-finite sample, rays above
+        the cap): the whole case then stays on the host branch."""
+        from . import _lib
+        from .image import ProjectionDeviceRefused, _reorient_plan, device_projection_mode, project_coronal_gpu
+        if cache.get('host_projection') or not hasattr(_lib.load(), 'ts2d_project_coronal_modes') or input.dimension != 3:
+            return False
+        planes = cache.setdefault('device_zscore_planes', {})
+        want = list(dict.fromkeys(n for _, n in channels if n not in planes))
+        ny = input.size[_reorient_plan(input)[0][1]]
+        if len(want) > _lib.PROJECT_MAX_MODES or any(device_projection_mode(n, ny) is None for _, n in channels):
+            return False
+        if want:
+            try:
+                pr = project_coronal_gpu(input, getattr(model._predictor.device, 'index', 0) or 0, zscore=True, modes=want)
+            except ProjectionDeviceRefused:
+                cache['host_projection'] = True
+                return False
+            for n in want:
+                cache['projections'].setdefault(n, pr[n])
+                planes[n] = pr['zscore'][n]
+        return True
 
     class Result:
         def __init__(self, data: dict):
