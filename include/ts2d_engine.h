@@ -748,6 +748,34 @@ typedef struct { uint8_t member[256]; uint8_t background; } ts2d_cc_step;
 int ts2d_keep_largest_components(int device, uint8_t* seg /* host [Z][H][W], in place */, int Z, int H, int W,
                                  const ts2d_cc_step* steps, int n_steps, int64_t* stats /* [n_steps][4] or NULL */, int* status);
 
+/* PNG visuals of a result on the device: the reference's create_visual (ts2d/core/util/image.py:383-453), which Result.save calls for every file
+ * it writes (ts2d/tool.py:272-311).  The statement is totalsegmentator2d_amd/visual.py (numpy float64); both entries reproduce it byte for byte.
+ * Host pointers in and out, synchronous, scratch of the call's own, freed on every path.  Geometry of both: a plane of H x W samples at spacing
+ * spacing_h x spacing_w is resampled to the smaller spacing m; per axis of N samples at spacing s the output has M = int(0.5 + N*s/m) samples,
+ * output index j reads the continuous source index x_j = (N/2) + (j - M/2) * (m/s) (float64, in that order) and is inside iff
+ * -0.5 <= x_j < N - 0.5; outside pixels are 0.  out_h x out_w must be those extents (the caller sizes its buffer by them).  A plane that needs no
+ * resample is handed over with spacing 1 x 1.
+ *
+ * ts2d_visual_labels: planes [K][H][W] uint8; K = 1 is a label map, K > 1 is flattened to 1 + the index of the LAST non-zero plane (0: none).
+ * Nearest sample floor(x + 0.5); rgb [out_h][out_w][3] = palette[v % n_palette] for v > 0, black for 0 and outside.  palette [n_palette][3].
+ *
+ * ts2d_visual_grey: one plane of `dtype` (the codes of ts2d_project_coronal: 0 int16, 1 uint8, 2 float32, 3 uint16, 4 int32).  cubic = 0: the
+ * nearest sample; cubic = 1 (not for uint8; extents of at least 2): the order-3 B-spline with mirror boundaries in float64 - prefilter along both
+ * axes, 16 taps - cast back to the pixel type (float32: one rounding; an integer type: clamped, truncated toward zero).  The window maps lo ... hi
+ * to 0 ... 255 (below lo 0, above hi 255, hi == lo: an all-zero plane); auto_lo / auto_hi != 0 take the minimum / maximum of the RESAMPLED plane
+ * in place of lo / hi.  grey [out_h][out_w]; window_used[2] receives lo and hi as used.
+ *   status    0, or TS2D_VISUAL_NONFINITE: a float32 sample is NaN or infinite; grey and window_used are not written, the caller takes the host
+ *             route.  The call returns TS2D_OK.
+ * TS2D_ERR_INVALID, by name, before any device work: a null pointer, K outside 1 ... 255, n_palette outside 1 ... 256, an unknown dtype, cubic
+ * outside {0, 1} or with uint8 or with an extent below 2, a non-finite window bound that is not automatic, an extent outside 1 ... 8192, a spacing
+ * that is not finite and positive, output extents above 32768 per axis or 2^28 pixels, out_h x out_w that are not the resample's.
+ * (New symbols of ABI 9: nothing that existed changed.) */
+#define TS2D_VISUAL_NONFINITE 1
+int ts2d_visual_labels(int device, const uint8_t* planes, int K, int H, int W, double spacing_h, double spacing_w, const uint8_t* palette,
+                       int n_palette, int out_h, int out_w, uint8_t* rgb);
+int ts2d_visual_grey(int device, const void* plane, int dtype, int H, int W, double spacing_h, double spacing_w, int cubic, double lo, double hi,
+                     int auto_lo, int auto_hi, int out_h, int out_w, uint8_t* grey, double* window_used, int* status);
+
 /* Synthetic slice stream on the device (BASELINE config 4: "synthetic 10k-slice stream", generated per rank from (seed, slice
  * index) so that no host transfer skews the timing).  Writes n_elements fp32 values, approximately N(0,1), to device memory:
  * element i of the call = element (first_element + i) of the stream identified by `key`; a value depends on (key, element index)

@@ -705,6 +705,52 @@ def keep_largest_components(seg: np.ndarray, tables, backgrounds, device: int = 
     return out, stats, 0
 
 
+def _visual_entry(name: str):
+    lib = _lib.load()
+    if not hasattr(lib, name):
+        raise RuntimeError(f"{name}: this libts2d_engine.so was built before the entry; rebuild it, or keep the host route")
+    return getattr(lib, name)
+
+
+def visual_labels(planes: np.ndarray, spacing_hw, palette: np.ndarray, out_hw, device: int = 0) -> np.ndarray:
+    """The label visual on the device (C-ABI ts2d_visual_labels, csrc/kernels_visual.h): uint8 planes [K, H, W] (K = 1: a label map; K > 1:
+    flattened to 1 + the index of the last non-zero plane), nearest resample to the smaller of ``spacing_hw``, colour ``palette[v % n]`` (uint8
+    [n, 3]), 0 and outside black.  ``out_hw``: the output extents (``visual.uniform_extent`` per axis).  Returns uint8 [h, w, 3] -
+    ``visual.label_rgb`` of the statement byte for byte."""
+    src = np.ascontiguousarray(planes, dtype=np.uint8)
+    pal = np.ascontiguousarray(palette, dtype=np.uint8)
+    if src.ndim != 3 or pal.ndim != 2 or pal.shape[1] != 3:
+        raise RuntimeError(f"visual_labels: expected uint8 planes [K,H,W] and a palette [n,3], found {src.shape} and {pal.shape}")
+    k, h, w = src.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    out = np.empty((max(oh, 0), max(ow, 0), 3), np.uint8)
+    _lib.check(_visual_entry('ts2d_visual_labels')(int(device), src.ctypes.data, k, h, w, float(spacing_hw[0]), float(spacing_hw[1]), pal.ctypes.data,
+                                                  pal.shape[0], oh, ow, out.ctypes.data), 'ts2d_visual_labels')
+    return out
+
+
+def visual_grey(plane: np.ndarray, spacing_hw, cubic: bool, lo, hi, out_hw, device: int = 0):
+    """The grey visual on the device (C-ABI ts2d_visual_grey): one plane [H, W] of type uint8, int16, uint16, int32 or float32, nearest or
+    order-3 resample to the smaller of ``spacing_hw``, window ``lo ... hi`` to 0 ... 255 (None: the minimum / maximum of the resampled plane).
+    Returns ``(uint8 [h, w], (lo, hi) as used)`` - ``visual.window_u8`` of the statement byte for byte - or None where the entry set a status bit
+    (a non-finite float32 sample): the caller takes the host route."""
+    from .visual import DEVICE_DTYPES
+    src = np.ascontiguousarray(plane)
+    if src.ndim != 2 or src.dtype.name not in DEVICE_DTYPES:
+        raise RuntimeError(f"visual_grey: expected a plane [H,W] of type {sorted(DEVICE_DTYPES)}, found {src.dtype} {src.shape}")
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    out = np.empty((max(oh, 0), max(ow, 0)), np.uint8)
+    used = np.zeros(2, np.float64)
+    status = ctypes.c_int(0)
+    _lib.check(_visual_entry('ts2d_visual_grey')(int(device), src.ctypes.data, DEVICE_DTYPES[src.dtype.name], src.shape[0], src.shape[1],
+                                                float(spacing_hw[0]), float(spacing_hw[1]), 1 if cubic else 0, 0.0 if lo is None else float(lo),
+                                                0.0 if hi is None else float(hi), int(lo is None), int(hi is None), oh, ow, out.ctypes.data,
+                                                used.ctypes.data, ctypes.byref(status)), 'ts2d_visual_grey')
+    if status.value:
+        return None
+    return out, (float(used[0]), float(used[1]))
+
+
 def _read_tiled_inf(engines, desc, n_images, engine_flags: bool):
     """The inf flags a tiled call left behind (upstream's inf check, done on the device).  With descriptors, ``last_tiled_inf_per_image``
     of the first engine is their per-image flags; ``last_tiled_inf`` of every engine is its own flag in the library (the flat entry and

@@ -434,3 +434,6 @@ def combine_segmentations(segs: Sequence[Image]) -> Image:
         out = Image(np.moveaxis(planes, 0, -1), first.spacing, first.origin, first.direction, n, {}, first.space)
     set_annotation_meta(out, names=names, colors=colors)
     return out
+
+
+from .visual import create_visual  # noqa: E402,F401  (reference image.py:383-453; the statement and its device route live in visual.py)

@@ -79,7 +79,7 @@ def ts2d_entry_point(argv=None):
     p.add_argument("--no-remote", action="store_true", help="Disable remote model download (always the case here).")
     p.add_argument("--no-fetch", action="store_true", help="Do not fetch model URLs (always the case here).")
     p.add_argument("--collapse", action="store_true", help="Collapse projected images to 2D.")
-    p.add_argument("--visualize", action="store_true", help="Visualize the results as PNG images (not implemented).")
+    p.add_argument("--visualize", action="store_true", help="Visualize the results as PNG images.")
     p.add_argument("--save-all", action="store_true", help="Also save results for each individual model.")
     p.add_argument("--silent", action="store_true", help="Hides any unnecessary output.")
     p.add_argument("--batch-cases", type=int, default=1, help="Cases of a directory that share one engine batch per sub-model (1: one case at a time). "

@@ -5,8 +5,9 @@ Same constructor, ``predict(input, collapse, merge) -> TS2D.Result`` and ``Resul
 test/test_030_cli.py:46-50).  Differences: models run in-process (no worker pool, no temp files); the sub-models of one case
 run CONCURRENTLY (one host thread per sub-model, each engine on its own HIP stream: a case is 2 tiles x 4 mirror passes = 8 slices
 per sub-model, which leaves most of the GPU idle when the five are driven one after the other as the reference does,
-tool.py:110-112; ``concurrent_models=False`` restores that order - the results are identical); PNG visualisation is not
-implemented (``content='visual'`` is skipped with a warning; SURVEY.md marks rendering out of scope).
+tool.py:110-112; ``concurrent_models=False`` restores that order - the results are identical); the PNG twins of ``Result.save``
+(``content='visual'`` / ``'all'``, reference tool.py:272-311) are ``image.create_visual`` written by ``png.write`` - rendered on the device of
+the engines (C-ABI ``ts2d_visual_labels`` / ``ts2d_visual_grey``), from the host statement in visual.py without one: the bytes are the same.
 """
 from __future__ import annotations
 
@@ -16,8 +17,8 @@ from typing import Dict, List, Optional, Union
 
 import numpy as np
 
-from . import nrrd
-from .image import (cast, combine_segmentations, compose, get_actual_dimension, project, reduce_dimensions, reorient_image,
+from . import nrrd, png
+from .image import (cast, combine_segmentations, compose, create_visual, get_actual_dimension, project, reduce_dimensions, reorient_image,
                     restore_dimension, split_channels)
 from .model import HIPModel
 from .zoo import LocalZoo, decompose_model_key, get_label_colors
@@ -139,7 +140,14 @@ class TS2D:
         # input side per sub-model (projections are computed once and cached), then the networks
         prepared = {mid: self._prepare_model_input(mid, input, cache) for mid in sorted(self.models)}
         done = self._fan_out(lambda mid: self._apply_model(mid, prepared[mid], collapse, probabilities))
-        return self._result(input, cache, done, merge)
+        return self._on_device(self._result(input, cache, done, merge))
+
+    def _on_device(self, result: "TS2D.Result") -> "TS2D.Result":
+        """Hand the result the device of the engines (its PNG visuals are rendered there); None where the models are not backed by HIP engines."""
+        if self._gpu_projection and self.models:
+            first = self.models[sorted(self.models)[0]]
+            result.device = getattr(first._predictor.device, 'index', 0) or 0
+        return result
 
     def predict_many(self, inputs, collapse: bool = False, merge: bool = True, max_cases: int = 8, probabilities: bool = False) -> List["TS2D.Result"]:
         """:meth:`predict` for several cases: per sub-model ONE engine batch over groups of at most ``max_cases`` cases
@@ -162,7 +170,7 @@ class TS2D:
                 out += self._apply_model_batch(mid, [pr[mid] for pr in prepared[g0:g0 + max_cases]], collapse, first=g0, probabilities=probabilities)
             return out
         done = self._fan_out(run_model)
-        return [self._result(img, cache, {mid: done[mid][i] for mid in order}, merge) for i, (img, cache) in enumerate(zip(images, caches))]
+        return [self._on_device(self._result(img, cache, {mid: done[mid][i] for mid in order}, merge)) for i, (img, cache) in enumerate(zip(images, caches))]
 
     def _model_result(self, mid: str, prepared, collapse: bool, seg, timestamps: dict) -> dict:
         """What one sub-model contributes to a ``Result``: the segmentation ``model.apply`` returned for ``prepared``, its 3-D geometry restored."""
@@ -274,8 +282,9 @@ class TS2D:
         return True
 
     class Result:
-        def __init__(self, data: dict):
+        def __init__(self, data: dict, device: Optional[int] = None):
             self.data = data
+            self.device = device          # where save() renders the PNG visuals: a device index, or None for the host statement
 
         @property
         def models(self) -> List[str]:
@@ -310,9 +319,11 @@ class TS2D:
         def save(self, dest: str, name: str = 'result', ext: str = 'nrrd', models='final', targets='all', content: str = 'all',
                  naming: str = 'group'):
             assert ext.lower() != 'png', "PNG is not a valid export format for the 'file' content type."
+            """Reference tool.py:235-311.  ``content``: 'file' writes ``<base>.<ext>``, ``<base>.seg.<ext>`` and ``<name>_<channel>.<ext>``;
+            'visual' their PNG twins (``<base>.png`` - ``<base>-ch<i>.png`` per channel of a multi-channel input -, ``<base>.seg.png``,
+            ``<name>_<channel>.png``: ``create_visual`` along the coronal axis, on ``self.device``); 'all' both.  Returns every path written."""
             assert naming in {'group', 'model'} and content in {'file', 'visual', 'all'}
-            if content in ('visual', 'all'):
-                warnings.warn("PNG visualisation is not implemented in the MI355X build; only files are written.")
+            kinds = {'file', 'visual'} if content == 'all' else {content}
             mset = {str(t).strip().lower() for t in _as_list(models)}
             keys: set = set()
             if 'all' in mset:
@@ -329,20 +340,36 @@ class TS2D:
 
             os.makedirs(dest, exist_ok=True)
             written = []
+
+            def write_file(img, stem):
+                if 'file' in kinds:
+                    written.append(os.path.join(dest, f"{stem}.{ext}"))
+                    nrrd.write(img, written[-1], True)
+
+            def write_visual(img, stem, **how):
+                written.append(os.path.join(dest, f"{stem}.png"))
+                png.write(create_visual(img, device=self.device, **how), written[-1])
+
             if {'all', 'input'} & tset:
                 for key in keys:
                     img = self.get_input(key)
                     if img is not None:
-                        written.append(os.path.join(dest, f"{fname(name, key)}.{ext}"))
-                        nrrd.write(img, written[-1], True)
+                        base = fname(name, key)
+                        write_file(img, base)
+                        if 'visual' in kinds:
+                            chs = split_channels(img)
+                            for i, ch in enumerate(chs):
+                                write_visual(ch, base if len(chs) == 1 else f"{base}-ch{i}", labels=False, axis='coronal')
             if {'all', 'segmentation'} & tset:
                 for key in keys:
                     img = self.get_segmentation(key)
                     if img is not None:
-                        written.append(os.path.join(dest, f"{fname(name, key)}.seg.{ext}"))
-                        nrrd.write(img, written[-1], True)
+                        write_file(img, f"{fname(name, key)}.seg")
+                        if 'visual' in kinds:
+                            write_visual(img, f"{fname(name, key)}.seg", labels=True, axis='coronal')
             if {'all', 'projection'} & tset:
                 for channel, img in self.get_projection().items():
-                    written.append(os.path.join(dest, f"{name}_{channel}.{ext}"))
-                    nrrd.write(img, written[-1], True)
+                    write_file(img, f"{name}_{channel}")
+                    if 'visual' in kinds:
+                        write_visual(img, f"{name}_{channel}")
             return written
