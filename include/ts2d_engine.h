@@ -776,6 +776,40 @@ int ts2d_visual_labels(int device, const uint8_t* planes, int K, int H, int W, d
 int ts2d_visual_grey(int device, const void* plane, int dtype, int H, int W, double spacing_h, double spacing_w, int cubic, double lo, double hi,
                      int auto_lo, int auto_hi, int out_h, int out_w, uint8_t* grey, double* window_used, int* status);
 
+/* Per-label statistics of a segmentation on the device: is a structure there, how large is it, where is it, how bright is the image under it
+ * (the reference's get_labels_voxels / get_voxel_mm, ts2d/core/util/meta.py:64-80, and beyond them box, centroid sums and intensity moments).
+ * The statement is totalsegmentator2d_amd/statistics.py (label_statistics_statement, numpy); the entry reproduces it bit for bit, the float64
+ * sums included.  Host pointers in and out, synchronous: ONE upload, every label on the device, ONE download; scratch of the call's own, freed
+ * on every path.  A volume is Z x H x W samples (a 2-D image: Z = 1), addressed as R = Z * H rows of W samples.
+ *   seg, kind  TS2D_STATS_PLANES: uint8 [K][Z][H][W], label k is plane k > 0.  TS2D_STATS_LABELMAP: ONE uint8 [Z][H][W] and values[K] (each
+ *              1 ... 255), label k is seg == values[k].  values may be NULL for planes.
+ *   intensities  float32 [C][Z][H][W]; NULL with C = 0: counts, boxes and index sums only (out_f64 may then be NULL too).
+ *   max_scratch_bytes  bound of the row partials (20 + 16 C bytes per label and row); the labels are processed in chunks that stay below it;
+ *              0: 256 MiB.  The result does not depend on the chunking.
+ *   out_int    int64 [K][TS2D_STATS_INTS]: count; the sum of the z, y and x indices of the label's samples; min z, max z, min y, max y,
+ *              min x, max x (inclusive).  An empty label: count 0, sums 0, minima Z, H, W, maxima -1.
+ *   out_f64    float64 [K][C][TS2D_STATS_F64S]: sum, ssq, mean, std, min, max.  sum: the float64 sum of the samples under the label; mean =
+ *              sum / count; ssq: the sum of (x - mean)^2, difference, product and sum each rounded on its own; std = sqrt(ssq / count); IEEE
+ *              divide and square root; min and max: the float32 extremes on the order-preserving keys of csrc/ray_select.h (-0.0 < +0.0),
+ *              widened exactly.  An empty label: all six +0.0.
+ *              Both sums are added in ONE fixed order (csrc/stats_tree.h): per row, lane l of 64 adds the terms at x = l, l + 64, ... in
+ *              increasing x from +0.0 (a sample outside the label is the term +0.0) and the 64 lane values are halved, v[l] + v[l + 32], then
+ *              + 16 ... + 1; per label the row partials meet the same way over the rows l, l + 64, ...  The order is a function of (Z * H, W).
+ *   status     0, or TS2D_STATS_NONFINITE: an intensity under a label is NaN or infinite; out_int and out_f64 are not written, the caller takes
+ *              the host route.  The call returns TS2D_OK.
+ * TS2D_ERR_INVALID, by name, before any device work: a null pointer, an unknown kind, K outside 1 ... 255, an extent below 1 or more than
+ * 2^31 - 1 voxels, C outside 0 ... TS2D_STATS_MAX_CHANNELS, C > 0 without intensities or out_f64, a label map without values or with a value 0,
+ * row partials of ONE label above max_scratch_bytes.  On any error the outputs are untouched.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+#define TS2D_STATS_PLANES 0
+#define TS2D_STATS_LABELMAP 1
+#define TS2D_STATS_NONFINITE 1
+#define TS2D_STATS_INTS 10
+#define TS2D_STATS_F64S 6
+#define TS2D_STATS_MAX_CHANNELS 64
+int ts2d_label_statistics(int device, const uint8_t* seg, int kind, const uint8_t* values, int K, int Z, int H, int W, const float* intensities,
+                          int C, size_t max_scratch_bytes, int64_t* out_int, double* out_f64, int* status);
+
 /* Synthetic slice stream on the device (BASELINE config 4: "synthetic 10k-slice stream", generated per rank from (seed, slice
  * index) so that no host transfer skews the timing).  Writes n_elements fp32 values, approximately N(0,1), to device memory:
  * element i of the call = element (first_element + i) of the stream identified by `key`; a value depends on (key, element index)

@@ -751,6 +751,44 @@ def visual_grey(plane: np.ndarray, spacing_hw, cubic: bool, lo, hi, out_hw, devi
     return out, (float(used[0]), float(used[1]))
 
 
+def label_statistics(seg: np.ndarray, kind: int, values, shape_zhw, intensities: Optional[np.ndarray] = None, max_scratch_bytes: int = 0,
+                     device: int = 0):
+    """The per-label statistics on the device (C-ABI ts2d_label_statistics, csrc/kernels_stats.h).  ``seg``: C-contiguous uint8, planes
+    [K, Z, H, W] (``kind`` = ``_lib.STATS_PLANES``) or one label map [Z, H, W] with ``values`` [K] (``_lib.STATS_LABELMAP``); ``intensities``:
+    float32 [C, Z, H, W] or None.  Returns ``(int64 [K, 10], float64 [K, C, 6])`` in the layout of include/ts2d_engine.h - the statement's
+    numbers bit for bit - or None where the entry set a status bit (a non-finite intensity under a label): the caller takes the host route."""
+    lib = _lib.load()
+    if not hasattr(lib, 'ts2d_label_statistics'):
+        raise RuntimeError("ts2d_label_statistics: this libts2d_engine.so was built before the entry; rebuild it, or keep the host route")
+    z, h, w = (int(v) for v in shape_zhw)
+    if seg.dtype != np.uint8 or not seg.flags['C_CONTIGUOUS']:
+        raise RuntimeError(f"label_statistics: expected a C-contiguous uint8 segmentation, found {seg.dtype} {seg.shape}")
+    if kind == _lib.STATS_LABELMAP:
+        vals = np.ascontiguousarray(values, dtype=np.uint8)
+        k = int(vals.size)
+        if seg.size != z * h * w:
+            raise RuntimeError(f"label_statistics: a label map of {seg.size} samples for {z} x {h} x {w}")
+    else:
+        vals = None
+        k = int(seg.shape[0])
+        if seg.size != k * z * h * w:
+            raise RuntimeError(f"label_statistics: planes of {seg.size} samples for {k} x {z} x {h} x {w}")
+    c = 0
+    if intensities is not None:
+        if intensities.dtype != np.float32 or not intensities.flags['C_CONTIGUOUS'] or intensities.size % (z * h * w):
+            raise RuntimeError(f"label_statistics: expected C-contiguous float32 intensities [C, {z}, {h}, {w}], found {intensities.dtype} {intensities.shape}")
+        c = intensities.size // (z * h * w)
+    out_int = np.zeros((k, _lib.STATS_INTS), np.int64)
+    out_f64 = np.zeros((k, c, _lib.STATS_F64S), np.float64)
+    status = ctypes.c_int(0)
+    _lib.check(lib.ts2d_label_statistics(int(device), seg.ctypes.data, int(kind), vals.ctypes.data if vals is not None else None, k, z, h, w,
+                                         intensities.ctypes.data if c else None, c, int(max_scratch_bytes), out_int.ctypes.data,
+                                         out_f64.ctypes.data if c else None, ctypes.byref(status)), 'ts2d_label_statistics')
+    if status.value:
+        return None
+    return out_int, out_f64
+
+
 def _read_tiled_inf(engines, desc, n_images, engine_flags: bool):
     """The inf flags a tiled call left behind (upstream's inf check, done on the device).  With descriptors, ``last_tiled_inf_per_image``
     of the first engine is their per-image flags; ``last_tiled_inf`` of every engine is its own flag in the library (the flat entry and

@@ -367,8 +367,19 @@ def set_annotation_meta(seg: Image, names: Optional[Dict[int, str]] = None, colo
     seg.meta = meta
 
 
-def get_annotation_labels(seg: Image) -> Dict[str, dict]:
-    """name -> {value, color?} from the ``Segment*`` keys (reference meta.py:289-330); multilabel value = Layer + 1."""
+def get_annotation_labels(seg: Image, fetch: bool = False, counts: bool = False) -> Dict[str, dict]:
+    """name -> {value, color?} from the ``Segment*`` keys (reference meta.py:289-330); multilabel value = Layer + 1.  ``fetch=True`` adds
+    ``exists`` (does the label have a sample?), ``counts=True`` adds ``count`` and ``mm = count * prod(spacing)`` (the reference's
+    ``get_labels_voxels`` and ``get_voxel_mm``, meta.py:64-80, :315-320) - both from ``statistics.label_statistics`` without intensities."""
+    if fetch or counts:
+        from .statistics import label_statistics
+        out = get_annotation_labels(seg)
+        for name, st in label_statistics(seg).items():
+            if fetch:
+                out[name]['exists'] = st['exists']
+            if counts:
+                out[name]['count'], out[name]['mm'] = st['count'], st['mm']
+        return out
     out: Dict[str, dict] = {}
     i = 0
     while f'Segment{i}_ID' in seg.meta or f'Segment{i}_Name' in seg.meta:

@@ -43,7 +43,8 @@ def _enumerate_cases(src: str):
 
 
 def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fetch_remote: bool = True, collapse: bool = False,
-             visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1, save_probabilities: bool = False):
+             visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1, save_probabilities: bool = False,
+             statistics: bool = False):
     model = DEFAULT_MODEL if model is None else model
     content = 'all' if visualize else 'file'
     which = 'all' if save_all else 'final'
@@ -62,12 +63,16 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
                                                                   probabilities=save_probabilities)):
                     res.save(dest=dest, name=name, models=which, content=content, targets=['segmentation', 'projection'])
                     res.save_probabilities(dest, name)
+                    if statistics:
+                        res.save_statistics(dest, name, models=which)
             return
         for i, (name, path) in enumerate(cases):
             log(f"[{i + 1}/{len(cases)}] Processing: {name}")
             res = ts.predict(path, collapse=collapse, probabilities=save_probabilities)
             res.save(dest=dest, name=name, models=which, content=content, targets=['segmentation', 'projection'])
             res.save_probabilities(dest, name)
+            if statistics:
+                res.save_statistics(dest, name, models=which)
 
 
 def ts2d_entry_point(argv=None):
@@ -86,11 +91,14 @@ def ts2d_entry_point(argv=None):
                    "A case's result does not depend on the other cases of its batch.")
     p.add_argument("--save-probabilities", action="store_true", help="Also write the probabilities of every sub-model: one "
                    "<case>-<group>.npz (key 'probabilities', float32 [K, *shape of the sub-model's 2-D input]) per sub-model.")
+    p.add_argument("--statistics", action="store_true", help="Also write <case>.statistics.json: per label count, mm, bounding box, centroid and "
+                   "min / max / mean / std of every projection under it (with --save-all one <case>-<group>.statistics.json per sub-model too).")
     a = p.parse_args(argv)
     if a.batch_cases < 1:
         p.error("--batch-cases must be at least 1")
     ts2d_run(src=a.src, dest=a.dest, model=a.model, use_remote=not a.no_remote, fetch_remote=not a.no_fetch, collapse=a.collapse,
-             visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases, save_probabilities=a.save_probabilities)
+             visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases, save_probabilities=a.save_probabilities,
+             statistics=a.statistics)
 
 
 if __name__ == '__main__':

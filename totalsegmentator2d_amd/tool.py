@@ -21,6 +21,7 @@ from . import nrrd, png
 from .image import (cast, combine_segmentations, compose, create_visual, get_actual_dimension, project, reduce_dimensions, reorient_image,
                     restore_dimension, split_channels)
 from .model import HIPModel
+from .statistics import dump_statistics, label_statistics
 from .zoo import LocalZoo, decompose_model_key, get_label_colors
 
 
@@ -315,6 +316,44 @@ class TS2D:
         def get_projection(self, channel: Optional[str] = None):
             pr = self.data.get('projections', {})
             return pr.get(channel) if channel is not None else pr
+
+        def statistics(self, model: Optional[str] = None, channels='all') -> Dict[str, dict]:
+            """Per-label statistics (``statistics.label_statistics``: count, mm, box, centroid, and min / max / mean / std of the intensity
+            under the label) of the merged segmentation (``model=None``) or of sub-model ``model``'s, against the projections of
+            :meth:`get_projection` - all of them, or the channel names in ``channels``.  Computed on ``self.device`` (C-ABI
+            ``ts2d_label_statistics``), from the host statement without one: the numbers are the same bit for bit."""
+            seg = self.get_segmentation(model)
+            if seg is None:
+                raise ValueError(f"no segmentation for model {model!r}")
+            pr = self.get_projection()
+            want = list(pr) if isinstance(channels, str) and channels.strip().lower() == 'all' else [str(c) for c in _as_list(channels)]
+            missing = [c for c in want if c not in pr]
+            if missing:
+                raise ValueError(f"no projection named {missing}; the result has {sorted(pr)}")
+            spatial = tuple(seg.array.shape[:seg.dimension])
+            images = {}
+            for c in want:
+                a = pr[c].array
+                if a.shape != spatial and int(a.size) == int(np.prod(spatial)) and [s for s in a.shape if s > 1] == [s for s in spatial if s > 1]:
+                    a = a.reshape(spatial)          # a collapsed segmentation against a projection that kept its unit axis
+                images[c] = a
+            return label_statistics(seg, images, device=self.device)
+
+        def save_statistics(self, dest: str, name: str = 'result', models='final', naming: str = 'group') -> List[str]:
+            """``<name>.statistics.json`` for the merged segmentation and ``<name>-<group or model>.statistics.json`` per sub-model, selected
+            by ``models`` as in :meth:`save`: ``json.dump`` of :meth:`statistics` with sorted keys (None of an empty label is ``null``)."""
+            assert naming in {'group', 'model'}
+            mset = {str(t).strip().lower() for t in _as_list(models)}
+            keys = []
+            if {'all', 'final'} & mset and self.get_segmentation() is not None:
+                keys.append(None)
+            keys += [m for m in self.models if ('all' in mset or m.lower() in mset) and self.get_segmentation(m) is not None]
+            os.makedirs(dest, exist_ok=True)
+            written = []
+            for key in keys:
+                stem = name if key is None else f"{name}-{(decompose_model_key(key)[1] or key) if naming == 'group' else key}"
+                written.append(dump_statistics(self.statistics(key), os.path.join(dest, f"{stem}.statistics.json")))
+            return written
 
         def save(self, dest: str, name: str = 'result', ext: str = 'nrrd', models='final', targets='all', content: str = 'all',
                  naming: str = 'group'):
