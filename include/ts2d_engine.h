@@ -810,6 +810,47 @@ int ts2d_visual_grey(int device, const void* plane, int dtype, int H, int W, dou
 int ts2d_label_statistics(int device, const uint8_t* seg, int kind, const uint8_t* values, int K, int Z, int H, int W, const float* intensities,
                           int C, size_t max_scratch_bytes, int64_t* out_int, double* out_f64, int* status);
 
+/* Scoring a segmentation against a reference on the device.  The statements are totalsegmentator2d_amd/evaluate.py (project_labels,
+ * overlap_statement, surface_statement; numpy); the three entries reproduce them byte for byte and bit for bit.  Host pointers in and out,
+ * synchronous; each input is uploaded once, the result downloaded once; scratch of the call's own, freed on every path.
+ *
+ * ts2d_project_labels_coronal: the reference's project(..., 'multiclass:<num>') along the coronal axis (ts2d/core/util/image.py:164-194) of a
+ * scalar INTEGER label volume, through the strided view of ts2d_project_coronal_modes (volume, n_elems, dtype, extents, element strides and base
+ * as there; dtype 2, float, is refused).  planes_u8 [num][nz][nx]: plane k is 1 where any sample of the ray equals k + 1, else 0.  One pass over
+ * the volume whatever num (1 ... 255) is.
+ *   status     0, or TS2D_LABELS_RANGE: a sample lies outside 0 ... num; planes_u8 is not written, and the caller raises (there is no other route
+ *              that would give a result).  The call returns TS2D_OK.
+ *
+ * ts2d_label_overlap: per label the samples on side a, on side b and on both.  a, kind_a and b, kind_b: each as seg, kind of
+ * ts2d_label_statistics (TS2D_STATS_PLANES: uint8 [K][Z][H][W], label k is plane k > 0; TS2D_STATS_LABELMAP: ONE uint8 [Z][H][W], label k is
+ * == values[k]); the two kinds may be mixed; values may be NULL where both are planes.  out_i64 [K][3] = n_a, n_b, n_both.
+ *
+ * ts2d_surface_distances: the boundary distances of 2-D planes [H][W] (a and b as above with Z = 1; H, W at most TS2D_EVAL_MAX_EXTENT).
+ * A border pixel of a mask is a foreground pixel with at least one of its four neighbours background, outside the image being background.
+ * For a border pixel p of one side, d2(p) = min over the border pixels q of the other side of
+ * ((|py - qy| * spacing_h) * (|py - qy| * spacing_h) + (|px - qx| * spacing_w) * (|px - qx| * spacing_w)) in float64, every product and the sum
+ * rounded on their own, +inf where the other side has no border - computed by the exact two-pass decomposition of csrc/surface_dist.h.
+ *   tol_sq     [T] float64, T at most TS2D_EVAL_MAX_TOLERANCES: the SQUARES of the tolerances (the caller squares once)
+ *   max_scratch_bytes  bound of the scratch (6 bytes per label and pixel); the labels are processed in chunks that stay below it; 0: 256 MiB.
+ *              The result does not depend on the chunking.
+ *   out_i64    [K][2][1 + T], direction 0: a against b, direction 1: b against a: the border pixels of the direction's own side, then per
+ *              tolerance those of them with d2 <= tol_sq[t]
+ *   out_f64    [K][2]: the largest d2 of the direction; -inf for an empty border, +inf where only the other side's is empty
+ * TS2D_ERR_INVALID, by name, before any device work: a null pointer, an unknown kind or dtype, K or num outside 1 ... 255, an extent below 1 or
+ * above its limit, a view that leaves the buffer, a label map without values or with a value 0, T outside its range, a negative tol_sq, a spacing
+ * that is not finite and positive, scratch of ONE label above max_scratch_bytes.  On any error the outputs are untouched.
+ * (New symbols of ABI 9: nothing that existed changed.) */
+#define TS2D_LABELS_RANGE 1
+#define TS2D_EVAL_MAX_TOLERANCES 8
+#define TS2D_EVAL_MAX_EXTENT 32767
+int ts2d_project_labels_coronal(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy,
+                                long long sx, long long base, int num, uint8_t* planes_u8, int32_t* status);
+int ts2d_label_overlap(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int Z, int H, int W,
+                       int64_t* out_i64);
+int ts2d_surface_distances(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int H, int W,
+                           double spacing_h, double spacing_w, const double* tol_sq, int T, size_t max_scratch_bytes, int64_t* out_i64,
+                           double* out_f64);
+
 /* Synthetic slice stream on the device (BASELINE config 4: "synthetic 10k-slice stream", generated per rank from (seed, slice
  * index) so that no host transfer skews the timing).  Writes n_elements fp32 values, approximately N(0,1), to device memory:
  * element i of the call = element (first_element + i) of the stream identified by `key`; a value depends on (key, element index)

@@ -1,0 +1,184 @@
+// Scoring a segmentation against a reference, none of which needs an engine: ts2d_project_labels_coronal, ts2d_label_overlap and
+// ts2d_surface_distances (kernels_evaluate.h; the arithmetic of the distances: surface_dist.h; the statements: totalsegmentator2d_amd/evaluate.py).
+// Host pointers in and out; a call uploads each input once, works on the device and downloads once; every device buffer of a call is one DevMem,
+// so HIP_TRY may return wherever it fails.
+#include "engine_internal.h"
+#include "kernels_evaluate.h"
+
+#include <cstring>
+#include <vector>
+
+using namespace ts2d;
+
+static_assert(kSdPlanes == TS2D_STATS_PLANES && kSdLabelMap == TS2D_STATS_LABELMAP, "the kinds speak the C header's numbers");
+static_assert(kPlStatusRange == TS2D_LABELS_RANGE && kSdMaxTolerances == TS2D_EVAL_MAX_TOLERANCES && kSdMaxExtent == TS2D_EVAL_MAX_EXTENT,
+              "the status bit and the limits speak the C header's numbers");
+
+#pragma GCC visibility push(hidden)
+namespace {
+
+template <typename T>
+void project_labels_launch(const T* d_vol, int nz, int ny, int nx, long long sz, long long sy, long long sx, long long base, int num, uint8_t* d_out,
+                           int* d_status) {
+    const long long N = (long long)nz * nx, quads = (N + 3) / 4;
+    const dim3 grid((unsigned)((quads + kPlThreads - 1) / kPlThreads)), block(kPlThreads);
+    const int vec = N % 4 == 0 ? 1 : 0;
+    if (num <= 32) hipLaunchKernelGGL((project_labels_stream<T, 1>), grid, block, 0, 0, d_vol, nz, ny, nx, sz, sy, sx, base, num, vec, d_out, d_status);
+    else if (num <= 64) hipLaunchKernelGGL((project_labels_stream<T, 2>), grid, block, 0, 0, d_vol, nz, ny, nx, sz, sy, sx, base, num, vec, d_out, d_status);
+    else if (num <= 128) hipLaunchKernelGGL((project_labels_stream<T, 4>), grid, block, 0, 0, d_vol, nz, ny, nx, sz, sy, sx, base, num, vec, d_out, d_status);
+    else hipLaunchKernelGGL((project_labels_stream<T, 8>), grid, block, 0, 0, d_vol, nz, ny, nx, sz, sy, sx, base, num, vec, d_out, d_status);
+}
+
+// the checks the two scoring entries share; *seg_a, *seg_b: the bytes of either input
+int check_sides(const char* entry, const void* a, int kind_a, const void* b, int kind_b, const uint8_t* values, int K, size_t n, size_t* seg_a,
+                size_t* seg_b) {
+    if (!a || !b) return fail(TS2D_ERR_INVALID, "%s: null segmentation", entry);
+    if ((kind_a != kSdPlanes && kind_a != kSdLabelMap) || (kind_b != kSdPlanes && kind_b != kSdLabelMap))
+        return fail(TS2D_ERR_INVALID, "%s: kinds %d, %d are not planes (0) or label map (1)", entry, kind_a, kind_b);
+    if (K < 1 || K > 255) return fail(TS2D_ERR_INVALID, "%s: K = %d labels outside 1 ... 255", entry, K);
+    if (kind_a == kSdLabelMap || kind_b == kSdLabelMap) {
+        if (!values) return fail(TS2D_ERR_INVALID, "%s: a label map needs the values of its K labels", entry);
+        for (int k = 0; k < K; ++k)
+            if (values[k] == 0) return fail(TS2D_ERR_INVALID, "%s: values[%d] = 0 is the background, not a label", entry, k);
+    }
+    *seg_a = kind_a == kSdPlanes ? (size_t)K * n : n;
+    *seg_b = kind_b == kSdPlanes ? (size_t)K * n : n;
+    return TS2D_OK;
+}
+
+}  // namespace
+#pragma GCC visibility pop
+
+extern "C" {
+
+int ts2d_project_labels_coronal(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy,
+                                long long sx, long long base, int num, uint8_t* planes_u8, int32_t* status) {
+    const char* const E = "ts2d_project_labels_coronal";
+    if (!volume || !planes_u8 || !status) return fail(TS2D_ERR_INVALID, "%s: null argument", E);
+    static const int esize[5] = {2, 1, 4, 2, 4};
+    if (dtype < 0 || dtype > 4 || dtype == 2) return fail(TS2D_ERR_INVALID, "%s: dtype %d is not an integer type (int16 0, uint8 1, uint16 3, int32 4)", E, dtype);
+    if (num < 1 || num > 255) return fail(TS2D_ERR_INVALID, "%s: num = %d outside 1 ... 255", E, num);
+    if (nz < 1 || ny < 1 || nx < 1) return fail(TS2D_ERR_INVALID, "%s: extents nz %d, ny %d, nx %d below 1", E, nz, ny, nx);
+    if ((long long)nz * nx * num > 0x7FFFFFFFll) return fail(TS2D_ERR_INVALID, "%s: %d planes of nz %d x nx %d are more than 2^31 - 1 bytes", E, num, nz, nx);
+    {   // every element the view can touch must lie inside the buffer
+        long long lo = base, hi = base;
+        const long long ext[3] = {(long long)(nz - 1) * sz, (long long)(ny - 1) * sy, (long long)(nx - 1) * sx};
+        for (int k = 0; k < 3; ++k) { if (ext[k] < 0) lo += ext[k]; else hi += ext[k]; }
+        if (lo < 0 || hi >= (long long)n_elems) return fail(TS2D_ERR_INVALID, "%s: the strided view (base, sz, sy, sx) leaves the buffer of n_elems %zu", E, n_elems);
+    }
+    *status = 0;
+    HIP_TRY(hipSetDevice(device));
+    const size_t vbytes = n_elems * esize[dtype], obytes = (size_t)nz * nx * num;
+    // [status | volume | planes]
+    const size_t o_vol = 256, o_out = align_up(o_vol + vbytes, 256);
+    DevMem d;
+    HIP_TRY(d.alloc(o_out + obytes));
+    int* d_status = d.as<int>();
+    uint8_t* d_out = d.as<uint8_t>(o_out);
+    HIP_TRY(hipMemset(d_status, 0, sizeof(int)));
+    HIP_TRY(hipMemcpy(d.as<char>(o_vol), volume, vbytes, hipMemcpyHostToDevice));
+    switch (dtype) {
+        case 0: project_labels_launch(d.as<const int16_t>(o_vol), nz, ny, nx, sz, sy, sx, base, num, d_out, d_status); break;
+        case 1: project_labels_launch(d.as<const uint8_t>(o_vol), nz, ny, nx, sz, sy, sx, base, num, d_out, d_status); break;
+        case 3: project_labels_launch(d.as<const uint16_t>(o_vol), nz, ny, nx, sz, sy, sx, base, num, d_out, d_status); break;
+        default: project_labels_launch(d.as<const int32_t>(o_vol), nz, ny, nx, sz, sy, sx, base, num, d_out, d_status); break;
+    }
+    HIP_TRY(hipGetLastError());
+    int st = 0;
+    HIP_TRY(hipMemcpy(&st, d_status, sizeof(st), hipMemcpyDeviceToHost));       // (waits for the launch: the default stream orders them)
+    if (st) { *status = st; return TS2D_OK; }                                     // a sample outside 0 ... num: the planes are no result
+    HIP_TRY(hipMemcpy(planes_u8, d_out, obytes, hipMemcpyDeviceToHost));
+    return TS2D_OK;
+}
+
+int ts2d_label_overlap(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int Z, int H, int W,
+                       int64_t* out_i64) {
+    const char* const E = "ts2d_label_overlap";
+    if (!out_i64) return fail(TS2D_ERR_INVALID, "%s: out_i64 is null", E);
+    if (Z < 1 || H < 1 || W < 1 || (long long)Z * H > 0x7FFFFFFFll || (long long)Z * H * W > 0x7FFFFFFFll)
+        return fail(TS2D_ERR_INVALID, "%s: %d x %d x %d is empty or more than 2^31 - 1 samples", E, Z, H, W);
+    const size_t n = (size_t)Z * H * W;
+    size_t bytes_a = 0, bytes_b = 0;
+    TRY(check_sides(E, a, kind_a, b, kind_b, values, K, n, &bytes_a, &bytes_b));
+    HIP_TRY(hipSetDevice(device));
+    // [counts | values | a | b]
+    const size_t o_val = align_up((size_t)K * 3 * sizeof(unsigned long long), 256), o_a = o_val + 256, o_b = align_up(o_a + bytes_a, 256);
+    DevMem d;
+    HIP_TRY(d.alloc(o_b + bytes_b));
+    HIP_TRY(hipMemset(d.as<char>(), 0, o_a));
+    if (values) HIP_TRY(hipMemcpy(d.as<char>(o_val), values, (size_t)K, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_a), a, bytes_a, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_b), b, bytes_b, hipMemcpyHostToDevice));
+    const int vec = n % 16 == 0 ? 1 : 0;
+    const size_t units = vec ? n / 16 : n;
+    size_t blocks = (units + kOvThreads - 1) / kOvThreads;
+    if (blocks > (size_t)kOvMaxBlocks) blocks = kOvMaxBlocks;
+    hipLaunchKernelGGL(overlap_count, dim3((unsigned)blocks, (unsigned)K), dim3(kOvThreads), 0, 0, d.as<const uint8_t>(o_a), kind_a,
+                       d.as<const uint8_t>(o_b), kind_b, d.as<const uint8_t>(o_val), (long long)n, vec, d.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out_i64, d.as<char>(), (size_t)K * 3 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return TS2D_OK;
+}
+
+int ts2d_surface_distances(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int H, int W,
+                           double spacing_h, double spacing_w, const double* tol_sq, int T, size_t max_scratch_bytes, int64_t* out_i64,
+                           double* out_f64) {
+    const char* const E = "ts2d_surface_distances";
+    if (!out_i64 || !out_f64) return fail(TS2D_ERR_INVALID, "%s: null output", E);
+    if (H < 1 || W < 1 || H > kSdMaxExtent || W > kSdMaxExtent) return fail(TS2D_ERR_INVALID, "%s: %d x %d outside 1 ... %d per axis", E, H, W, kSdMaxExtent);
+    if (T < 0 || T > kSdMaxTolerances || (T > 0 && !tol_sq)) return fail(TS2D_ERR_INVALID, "%s: T = %d tolerances outside 0 ... %d, or without tol_sq", E, T, kSdMaxTolerances);
+    if (!(spacing_h > 0.0 && spacing_h < 1e300 && spacing_w > 0.0 && spacing_w < 1e300))
+        return fail(TS2D_ERR_INVALID, "%s: spacing %g x %g is not finite and positive", E, spacing_h, spacing_w);
+    SdTolerances tol = {};
+    for (int t = 0; t < T; ++t) {
+        if (!(tol_sq[t] >= 0.0)) return fail(TS2D_ERR_INVALID, "%s: tol_sq[%d] = %g is negative or not a number", E, t, tol_sq[t]);
+        tol.sq[t] = tol_sq[t];
+    }
+    const size_t n = (size_t)H * W;
+    size_t bytes_a = 0, bytes_b = 0;
+    TRY(check_sides(E, a, kind_a, b, kind_b, values, K, n, &bytes_a, &bytes_b));
+    // a label's scratch: the border bytes and the uint16 row distances of both sides
+    const size_t per_label = n * 2 * (1 + sizeof(uint16_t));
+    const size_t budget = max_scratch_bytes ? max_scratch_bytes : ((size_t)256 << 20);
+    size_t L = budget / per_label;
+    if (L < 1)
+        return fail(TS2D_ERR_INVALID, "%s: the scratch of ONE label (%d x %d) takes %zu bytes, above max_scratch_bytes = %zu", E, H, W, per_label, budget);
+    if (L > (size_t)K) L = (size_t)K;
+    HIP_TRY(hipSetDevice(device));
+    // [counts | keys | values | a | b | border of a chunk | g of a chunk]
+    const size_t n_cnt = (size_t)K * 2 * (1 + T);
+    const size_t o_key = align_up(n_cnt * sizeof(unsigned long long), 256), o_val = align_up(o_key + (size_t)K * 2 * sizeof(unsigned long long), 256);
+    const size_t o_a = o_val + 256, o_b = align_up(o_a + bytes_a, 256), o_border = align_up(o_b + bytes_b, 256);
+    const size_t o_g = align_up(o_border + L * 2 * n, 256), total = o_g + L * 2 * n * sizeof(uint16_t);
+    DevMem d;
+    HIP_TRY(d.alloc(total));
+    HIP_TRY(hipMemset(d.as<char>(), 0, o_a));
+    if (values) HIP_TRY(hipMemcpy(d.as<char>(o_val), values, (size_t)K, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_a), a, bytes_a, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_b), b, bytes_b, hipMemcpyHostToDevice));
+    unsigned long long* const d_cnt = d.as<unsigned long long>();
+    unsigned long long* const d_key = d.as<unsigned long long>(o_key);
+    for (int k0 = 0; k0 < K; k0 += (int)L) {
+        const unsigned labels = (unsigned)(K - k0 < (int)L ? K - k0 : (int)L);
+        hipLaunchKernelGGL(sd_columns, dim3((unsigned)((W + 63) / 64), 2, labels), dim3(64), 0, 0, d.as<const uint8_t>(o_a), kind_a,
+                           d.as<const uint8_t>(o_b), kind_b, d.as<const uint8_t>(o_val), k0, H, W, d.as<uint8_t>(o_border), d.as<uint16_t>(o_g));
+        hipLaunchKernelGGL(sd_rows, dim3((unsigned)H, 2, labels), dim3(64), 0, 0, d.as<const uint8_t>(o_border), d.as<const uint16_t>(o_g), k0, H, W,
+                           spacing_h, spacing_w, tol, T, d_cnt, d_key);
+        HIP_TRY(hipGetLastError());
+    }
+    // one download: the counts and the keys lie next to each other (the gap of the alignment goes along)
+    std::vector<char> host(o_val);
+    HIP_TRY(hipMemcpy(host.data(), d.as<char>(), host.size(), hipMemcpyDeviceToHost));
+    memcpy(out_i64, host.data(), n_cnt * sizeof(int64_t));
+    for (int i = 0; i < K * 2; ++i) {
+        long long border;
+        uint64_t key;
+        memcpy(&border, host.data() + (size_t)i * (1 + T) * sizeof(int64_t), sizeof(border));
+        memcpy(&key, host.data() + o_key + (size_t)i * sizeof(uint64_t), sizeof(key));
+        if (border == 0) key = 0xFFF0000000000000ull;                              // an empty border: -inf
+        memcpy(out_f64 + i, &key, sizeof(key));
+    }
+    return TS2D_OK;
+}
+
+}  // extern "C"

@@ -789,6 +789,74 @@ def label_statistics(seg: np.ndarray, kind: int, values, shape_zhw, intensities:
     return out_int, out_f64
 
 
+def _evaluate_entry(name: str):
+    lib = _lib.load()
+    if not hasattr(lib, name):
+        raise RuntimeError(f"{name}: this libts2d_engine.so was built before the entry; rebuild it, or keep the host route")
+    return getattr(lib, name)
+
+
+def project_labels_coronal(buffer: np.ndarray, extents, strides, base: int, num: int, device: int = 0):
+    """The label projection on the device (C-ABI ts2d_project_labels_coronal, csrc/kernels_evaluate.h).  ``buffer``: the volume's C-contiguous
+    integer samples; ``extents`` (nz, ny, nx), ``strides`` (sz, sy, sx) and ``base`` in elements: the reoriented view of
+    ``image._coronal_view``.  Returns ``(uint8 [num, nz, nx], status)``; with a status bit (``_lib.LABELS_RANGE``) the planes are no result."""
+    from .image import _GPU_DTYPES
+    fn = _evaluate_entry('ts2d_project_labels_coronal')
+    if buffer.dtype.name not in _GPU_DTYPES or not np.issubdtype(buffer.dtype, np.integer) or not buffer.flags['C_CONTIGUOUS']:
+        raise RuntimeError(f"project_labels_coronal: expected a C-contiguous int16, uint8, uint16 or int32 volume, found {buffer.dtype}")
+    nz, ny, nx = (int(v) for v in extents)
+    sz, sy, sx = (int(v) for v in strides)
+    planes = np.zeros((int(num), nz, nx), np.uint8)
+    status = np.zeros(1, np.int32)
+    _lib.check(fn(int(device), buffer.ctypes.data, buffer.size, _GPU_DTYPES[buffer.dtype.name], nz, ny, nx, sz, sy, sx, int(base), int(num),
+                  planes.ctypes.data, status.ctypes.data), 'ts2d_project_labels_coronal')
+    return planes, int(status[0])
+
+
+def _evaluate_sides(what: str, a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, n: int):
+    """(K, values as uint8 or None) of the two sides of a scoring entry: C-contiguous uint8, planes [K, n samples] or one label map."""
+    for x in (a, b):
+        if x.dtype != np.uint8 or not x.flags['C_CONTIGUOUS']:
+            raise RuntimeError(f"{what}: expected C-contiguous uint8 segmentations, found {x.dtype} {x.shape}")
+    vals = None if values is None else np.ascontiguousarray(values, dtype=np.uint8)
+    ks = [int(x.shape[0]) for x, kind in ((a, kind_a), (b, kind_b)) if kind == _lib.STATS_PLANES] + ([int(vals.size)] if vals is not None else [])
+    if not ks or len(set(ks)) != 1:
+        raise RuntimeError(f"{what}: the sides and the values differ in their number of labels: {ks}")
+    for x, kind in ((a, kind_a), (b, kind_b)):
+        if x.size != (ks[0] if kind == _lib.STATS_PLANES else 1) * n:
+            raise RuntimeError(f"{what}: a segmentation of {x.size} samples for {ks[0] if kind == _lib.STATS_PLANES else 1} x {n}")
+    return ks[0], vals
+
+
+def label_overlap(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, shape_zhw, device: int = 0) -> np.ndarray:
+    """The overlap counts on the device (C-ABI ts2d_label_overlap).  ``a``, ``b``: C-contiguous uint8, each planes [K, Z, H, W]
+    (``_lib.STATS_PLANES``) or one label map [Z, H, W] with ``values`` [K] (``_lib.STATS_LABELMAP``).  Returns int64 [K, 3] = n_a, n_b, n_both."""
+    fn = _evaluate_entry('ts2d_label_overlap')
+    z, h, w = (int(v) for v in shape_zhw)
+    k, vals = _evaluate_sides('label_overlap', a, kind_a, b, kind_b, values, z * h * w)
+    out = np.zeros((k, 3), np.int64)
+    _lib.check(fn(int(device), a.ctypes.data, int(kind_a), b.ctypes.data, int(kind_b), vals.ctypes.data if vals is not None else None, k, z, h, w,
+                  out.ctypes.data), 'ts2d_label_overlap')
+    return out
+
+
+def surface_distances(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, shape_hw, spacing_hw, tol_sq, max_scratch_bytes: int = 0,
+                      device: int = 0):
+    """The boundary distances of 2-D planes on the device (C-ABI ts2d_surface_distances).  ``a``, ``b`` as in :func:`label_overlap` with Z = 1;
+    ``tol_sq``: the squared tolerances, float64 [T].  Returns ``(int64 [K, 2, 1 + T], float64 [K, 2])`` in the layout of include/ts2d_engine.h."""
+    fn = _evaluate_entry('ts2d_surface_distances')
+    h, w = (int(v) for v in shape_hw)
+    k, vals = _evaluate_sides('surface_distances', a, kind_a, b, kind_b, values, h * w)
+    tol = np.ascontiguousarray(tol_sq, dtype=np.float64)
+    t = int(tol.size)
+    out_i = np.zeros((k, 2, 1 + t), np.int64)
+    out_f = np.zeros((k, 2), np.float64)
+    _lib.check(fn(int(device), a.ctypes.data, int(kind_a), b.ctypes.data, int(kind_b), vals.ctypes.data if vals is not None else None, k, h, w,
+                  float(spacing_hw[0]), float(spacing_hw[1]), tol.ctypes.data if t else None, t, int(max_scratch_bytes), out_i.ctypes.data,
+                  out_f.ctypes.data), 'ts2d_surface_distances')
+    return out_i, out_f
+
+
 def _read_tiled_inf(engines, desc, n_images, engine_flags: bool):
     """The inf flags a tiled call left behind (upstream's inf check, done on the device).  With descriptors, ``last_tiled_inf_per_image``
     of the first engine is their per-image flags; ``last_tiled_inf`` of every engine is its own flag in the library (the flat entry and

@@ -1,0 +1,360 @@
+"""Score a segmentation against a reference: the label projection of a 3-D label volume, overlap counts (Dice, IoU, precision, recall) and, for
+2-D planes, boundary distances (surface Dice, Hausdorff distance).
+
+The functions ``*_statement`` and :func:`project_labels` are the project's definition - written in numpy, they are the host route and the
+oracle of the device route (C-ABI ``ts2d_project_labels_coronal``, ``ts2d_label_overlap``, ``ts2d_surface_distances``;
+``csrc/kernels_evaluate.h``), which reproduces them bit for bit, as ``statistics.py``, ``visual.py`` and ``postprocess.py`` are for their entries.
+
+LABEL PROJECTION.  TotalSegmentator 2D is trained and evaluated on 3-D label volumes projected into one binary plane per label: the reference's
+``project(..., 'multiclass:<num>')`` (``ts2d/core/util/image.py:164-194``, ``_project_multiclass``).  :func:`project_labels` restates it.  Its
+result is a vector image, so it has a function of its own: ``image.project`` keeps refusing the mode.
+
+KINDS.  A segmentation is handed over as planes ``[K, *spatial]`` (label ``k`` is ``planes[k] > 0``) or as a label map ``[*spatial]`` with
+``values[K]`` (label ``k`` is ``map == values[k]``) - the two kinds of ``ts2d_label_statistics`` -, and the two sides may be mixed.
+
+BORDER AND DISTANCE (2-D).  A border pixel of a mask is a foreground pixel with at least one of its four neighbours background; outside the image
+counts as background (``mask & ~scipy.ndimage.binary_erosion(mask)``).  For a border pixel ``p`` of A
+
+    d2(p) = min over border pixels q of B of ((|py - qy| * sy) * (|py - qy| * sy) + (|px - qx| * sx) * (|px - qx| * sx))
+
+in float64, every product and the sum rounded on their own (no fused multiply-add), ``+inf`` where B has no border.  The minimum of a set does
+not depend on order, so the bits are a function of the input alone.  The statement computes it by the exact two-pass decomposition the kernels use
+(``csrc/surface_dist.h`` has the argument): per column the integer row distance ``g`` to the nearest border pixel of B, then per border pixel the
+minimum over the columns ``x'`` of the formula with ``|py - qy| = g(py, x')``.  tests/test_evaluate_cpu.py holds it against the brute force over
+all border pairs, bit for bit.
+"""
+from __future__ import annotations
+
+import json
+import math
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+
+from .nrrd import Image
+
+PLANES, LABELMAP = 0, 1          # _lib.STATS_PLANES, _lib.STATS_LABELMAP: the kinds of ts2d_label_statistics
+MAX_TOLERANCES = 8               # _lib.EVAL_MAX_TOLERANCES
+_AXES = {'a': 2, 'ax': 2, 'axial': 2, 's': 0, 'sag': 0, 'sagittal': 0, 'c': 1, 'cor': 1, 'coronal': 1}
+# No size gate: the device route lost at no measured size, the small end included - 117 labels at 53 x 133 take 0.17 ms (overlap) and 0.56 ms
+# (distances) there against 0.38 ms and 25.6 ms for the statements; the narrowest win is the overlap of 18 labels at 600 x 512, 0.56 ms against
+# 0.69 ... 0.87 ms (scripts/gpu_evaluate_case.py, profiles/r29_evaluate_case.txt).
+
+
+# ------------------------------------------------------------------------------------------------------------------ label projection
+def project_labels(img: Image, num: int, axis='coronal') -> Image:
+    """The reference's ``project(img, 'multiclass:<num>', axis)`` (``_project_multiclass``, image.py:164-194).
+
+    Scalar integer volume (:166-188): the result has ``num`` uint8 components; component ``k`` is 1 where any sample of the ray along ``axis``
+    equals ``k + 1`` (:177-181: the non-zero samples scatter a 1 into plane ``value - 1``), else 0.  The projected axis keeps size 1 and its
+    origin, as in ``image.project`` (:97-100).  Multi-component input (:189-193): the per-component maximum along the axis, in the input type.
+
+    The result has the layout of a multilabel segmentation as ``TS2D`` returns it (plane-major memory behind the ``[..., label]`` view; a scalar
+    image for ``num = 1``), so it goes straight to ``statistics.label_statistics`` and to :func:`evaluate`.
+
+    A sample outside ``0 ... num`` raises ``ValueError``.  (The reference raises ``IndexError`` for a sample above ``num`` and silently WRAPS a
+    negative one: ``-1 - 1`` indexes plane ``num - 2`` from the end.  Neither is a result.)  ``num`` runs from 1 to 255; a float volume raises
+    ``ValueError``."""
+    ax = _AXES[axis.lower()] if isinstance(axis, str) else list(range(img.dimension))[axis]
+    npax = img.dimension - 1 - ax
+    a = img.array
+    if img.components > 1:
+        r = a.max(axis=npax, keepdims=True)
+        return Image(np.ascontiguousarray(r), img.spacing, img.origin, img.direction, img.components, dict(img.meta), img.space)
+    num = _check_num(num)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"project_labels: a label volume has an integer type, found {a.dtype}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) > num):
+        raise ValueError(f"project_labels: the volume holds samples outside 0 ... {num} (minimum {int(a.min())}, maximum {int(a.max())})")
+    moved = np.moveaxis(a, npax, 0)                                          # the ray first, as the reference has it (:175)
+    idx = np.nonzero(moved)
+    planes = np.zeros((num, 1) + moved.shape[1:], np.uint8)
+    planes[(moved[idx].astype(np.intp) - 1, 0) + idx[1:]] = 1                # (:177-181; every sample is inside 1 ... num here)
+    return _planes_image(np.moveaxis(planes, 1, npax + 1), img)
+
+
+def _check_num(num) -> int:
+    n = int(num)
+    if not 1 <= n <= 255:
+        raise ValueError(f"project_labels: num = {num} outside 1 ... 255")
+    return n
+
+
+def _planes_image(planes: np.ndarray, like: Image, spacing=None, origin=None, direction=None) -> Image:
+    num = planes.shape[0]
+    arr = planes[0] if num == 1 else np.moveaxis(planes, 0, -1)
+    return Image(arr, like.spacing if spacing is None else spacing, like.origin if origin is None else origin,
+                 like.direction if direction is None else direction, num, dict(like.meta), like.space)
+
+
+def device_projects(img: Image) -> bool:
+    """Does ``ts2d_project_labels_coronal`` serve the volume?  A scalar 3-D volume of an integer type of the device projection, and a library that
+    has the symbol."""
+    from . import _lib
+    from .image import _GPU_DTYPES
+    if img.dimension != 3 or img.components != 1 or img.array.dtype.name not in _GPU_DTYPES or not np.issubdtype(img.array.dtype, np.integer):
+        return False
+    try:
+        return hasattr(_lib.load(), 'ts2d_project_labels_coronal')
+    except Exception:
+        return False
+
+
+def project_labels_coronal_gpu(img: Image, num: int, device: int = 0) -> Image:
+    """``project_labels(reorient_image(img), num, 'coronal')`` on the device (C-ABI ``ts2d_project_labels_coronal``), without the host
+    reorientation copy: the entry reads the reoriented strided view of ``image._coronal_view``.  One pass over the volume whatever ``num`` is.
+    A sample outside ``0 ... num`` is a status bit of the entry and raises the statement's ``ValueError``: there is no silent fall-back."""
+    from . import _lib, engine
+    from .image import _coronal_view, _reoriented_geometry
+    num = _check_num(num)
+    if not device_projects(img):
+        raise RuntimeError(f"project_labels_coronal_gpu needs a scalar 3-D volume of type int16, uint8, uint16 or int32 and a library with "
+                           f"ts2d_project_labels_coronal, found {img.array.dtype} with {img.components} components in {img.dimension}-D")
+    a, (nz, ny, nx), strides, base, perm, flips = _coronal_view(img)
+    planes, status = engine.project_labels_coronal(a, (nz, ny, nx), strides, base, num, device)
+    if status & _lib.LABELS_RANGE:
+        raise ValueError(f"project_labels: the volume holds samples outside 0 ... {num}")
+    geo = _reoriented_geometry(img, perm, flips)
+    return _planes_image(planes.reshape(num, nz, 1, nx), img, tuple(img.spacing[ax] for ax in perm), geo[0], geo[1])
+
+
+# ------------------------------------------------------------------------------------------------------------------ the statements
+def _sides(a, kind_a, b, kind_b, values):
+    a, b = np.asarray(a), np.asarray(b)
+    for kind in (kind_a, kind_b):
+        if kind not in (PLANES, LABELMAP):
+            raise ValueError(f"kind {kind} is neither planes ({PLANES}) nor label map ({LABELMAP})")
+    if LABELMAP in (kind_a, kind_b) and values is None:
+        raise ValueError("a label map needs the values of its labels")
+    sa = a.shape[1:] if kind_a == PLANES else a.shape
+    sb = b.shape[1:] if kind_b == PLANES else b.shape
+    if tuple(sa) != tuple(sb):
+        raise ValueError(f"the two segmentations differ in shape: {tuple(sa)} and {tuple(sb)}")
+    ks = [x.shape[0] for x, kind in ((a, kind_a), (b, kind_b)) if kind == PLANES] + ([len(values)] if values is not None else [])
+    if len(set(ks)) != 1:
+        raise ValueError(f"the two segmentations and the values differ in their number of labels: {ks}")
+    return a, b, tuple(sa), ks[0]
+
+
+def _mask(x: np.ndarray, kind: int, values, k: int) -> np.ndarray:
+    return (x[k] > 0) if kind == PLANES else (x == values[k])
+
+
+def overlap_statement(a, kind_a: int, b, kind_b: int, values=None) -> dict:
+    """THE DEFINITION of the overlap counts.  ``a`` and ``b``: each plane-major ``[K, *spatial]`` (kind ``PLANES``) or a label map ``[*spatial]``
+    with ``values[K]`` (kind ``LABELMAP``), of one spatial shape.  Returns int64 arrays over the K labels: ``n_a``, ``n_b`` (the samples of the
+    label on either side) and ``n_both`` (the samples of the label on both)."""
+    a, b, _, K = _sides(a, kind_a, b, kind_b, values)
+    out = {f: np.zeros(K, np.int64) for f in ('n_a', 'n_b', 'n_both')}
+    for k in range(K):
+        ma, mb = _mask(a, kind_a, values, k), _mask(b, kind_b, values, k)
+        out['n_a'][k], out['n_b'][k], out['n_both'][k] = np.count_nonzero(ma), np.count_nonzero(mb), np.count_nonzero(ma & mb)
+    return out
+
+
+def border_of(mask: np.ndarray) -> np.ndarray:
+    """The border pixels of a 2-D mask: foreground with at least one of the four neighbours background, outside the image being background."""
+    m = np.asarray(mask, bool)
+    p = np.pad(m, 1)
+    return m & ~(p[:-2, 1:-1] & p[2:, 1:-1] & p[1:-1, :-2] & p[1:-1, 2:])
+
+
+def row_distance(border: np.ndarray) -> np.ndarray:
+    """Pass 1: int64 [H, W], per pixel the row distance ``|y - y'|`` to the nearest border pixel of its COLUMN (a downward and an upward scan);
+    -1 where the column has none."""
+    H, W = border.shape
+    big = np.int64(1) << 40
+    y = np.arange(H, dtype=np.int64)[:, None]
+    above = np.maximum.accumulate(np.where(border, y, -big), axis=0)                     # the nearest border row at or above
+    below = np.minimum.accumulate(np.where(border, y, big)[::-1], axis=0)[::-1]          # ... at or below
+    g = np.minimum(y - above, below - y)
+    return np.where(g >= H, -1, g)
+
+
+def d2_from_rows(border_a: np.ndarray, g_b: np.ndarray, spacing_hw) -> np.ndarray:
+    """Pass 2: float64 d2 of every border pixel of A (in ``np.nonzero`` order) from the row distances of B's border."""
+    sy, sx = np.float64(spacing_hw[0]), np.float64(spacing_hw[1])
+    H, W = border_a.shape
+    ys, xs = np.nonzero(border_a)
+    with np.errstate(invalid='ignore'):
+        ry = np.where(g_b < 0, np.inf, g_b.astype(np.float64)) * sy
+        dy2 = ry * ry                                                                    # [H, W]: (g * sy) * (g * sy), +inf without a border
+    rx = np.abs(np.arange(W, dtype=np.int64)[:, None] - np.arange(W, dtype=np.int64)[None, :]).astype(np.float64) * sx
+    dx2 = rx * rx                                                                        # [W, W]: (|x - x'| * sx) * (|x - x'| * sx)
+    out = np.empty(len(ys), np.float64)
+    step = max(1, (1 << 22) // max(W, 1))
+    for i in range(0, len(ys), step):
+        out[i:i + step] = (dy2[ys[i:i + step]] + dx2[xs[i:i + step]]).min(axis=1)
+    return out
+
+
+def surface_statement(a, kind_a: int, b, kind_b: int, values, spacing_hw, tolerances: Sequence[float]) -> dict:
+    """THE DEFINITION of the boundary distances of 2-D planes (module docstring).  ``a``, ``b``: planes ``[K, 1, H, W]`` / ``[K, H, W]`` or label
+    maps ``[1, H, W]`` / ``[H, W]``; a volume (``Z > 1``) raises ``ValueError``.  ``spacing_hw``: (mm per row, mm per column).
+
+    Returns over the K labels and the two directions (0: A to B, 1: B to A): ``border`` int64 [K, 2] (the border pixels of the direction's own
+    side), ``d2_max`` float64 [K, 2] (``-inf`` for an empty border, ``+inf`` where the other side has none) and ``within`` int64 [K, 2, T]: per
+    tolerance ``t`` (mm) the border pixels with ``d2 <= t * t``, the square taken once in float64."""
+    a, b, spatial, K = _sides(a, kind_a, b, kind_b, values)
+    if len(spatial) == 3 and spatial[0] == 1:
+        spatial = spatial[1:]
+        a = a.reshape((K,) + spatial if kind_a == PLANES else spatial)
+        b = b.reshape((K,) + spatial if kind_b == PLANES else spatial)
+    if len(spatial) != 2:
+        raise ValueError(f"surface_statement: boundary distances are defined for 2-D planes, found the extent {tuple(spatial)}")
+    tol = np.asarray(list(tolerances), np.float64)
+    tol_sq = tol * tol
+    T = len(tol)
+    out = {'border': np.zeros((K, 2), np.int64), 'd2_max': np.full((K, 2), -np.inf, np.float64), 'within': np.zeros((K, 2, T), np.int64)}
+    for k in range(K):
+        ba, bb = border_of(_mask(a, kind_a, values, k)), border_of(_mask(b, kind_b, values, k))
+        for d, (own, other) in enumerate(((ba, bb), (bb, ba))):
+            n = int(np.count_nonzero(own))
+            out['border'][k, d] = n
+            if n == 0:
+                continue
+            d2 = d2_from_rows(own, row_distance(other), spacing_hw)
+            out['d2_max'][k, d] = d2.max()
+            for t in range(T):
+                out['within'][k, d, t] = np.count_nonzero(d2 <= tol_sq[t])
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ the device route
+def device_serves(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, spatial, K: int) -> bool:
+    """Do ``ts2d_label_overlap`` and ``ts2d_surface_distances`` serve the case?  uint8 samples, 1 ... 255 labels (label-map values 1 ... 255), at
+    most 2^31 - 1 samples, and a library that has the symbols."""
+    from . import _lib
+    if a.dtype != np.uint8 or b.dtype != np.uint8 or not 1 <= K <= 255:
+        return False
+    if min(spatial, default=0) < 1 or int(np.prod(spatial, dtype=np.int64)) > 2 ** 31 - 1:
+        return False
+    if LABELMAP in (kind_a, kind_b) and not all(1 <= int(v) <= 255 for v in values):
+        return False
+    try:
+        lib = _lib.load()
+        return hasattr(lib, 'ts2d_label_overlap') and hasattr(lib, 'ts2d_surface_distances')
+    except Exception:
+        return False
+
+
+def _device_overlap(a, kind_a, b, kind_b, values, spatial, device: int) -> dict:
+    from . import engine
+    zhw = (1,) * (3 - len(spatial)) + tuple(int(v) for v in spatial)
+    o = engine.label_overlap(np.ascontiguousarray(a), kind_a, np.ascontiguousarray(b), kind_b, values, zhw, device)
+    return {'n_a': o[:, 0].copy(), 'n_b': o[:, 1].copy(), 'n_both': o[:, 2].copy()}
+
+
+def _device_surface(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, device: int, max_scratch_bytes: int = 0) -> dict:
+    from . import engine
+    tol = np.asarray(list(tolerances), np.float64)
+    oi, of = engine.surface_distances(np.ascontiguousarray(a), kind_a, np.ascontiguousarray(b), kind_b, values, hw, spacing_hw, tol * tol,
+                                      max_scratch_bytes, device)
+    return {'border': oi[:, :, 0].copy(), 'd2_max': of, 'within': oi[:, :, 1:].copy()}
+
+
+# ------------------------------------------------------------------------------------------------------------------ evaluate
+def _plane_axes(img: Image):
+    """The (array axes, (spacing_h, spacing_w)) of a 2-D input: a 2-D image as it is, a 3-D image with an axis of size 1 without that axis (the
+    coronal one first: what ``TS2D`` leaves behind); None for a volume."""
+    nd = img.dimension
+    shape = img.array.shape[:nd]
+    if nd == 2:
+        keep = [0, 1]
+    elif nd == 3 and 1 in shape:
+        drop = 1 if shape[1] == 1 else list(shape).index(1)
+        keep = [k for k in range(3) if k != drop]
+    else:
+        return None
+    return keep, tuple(float(img.spacing[nd - 1 - k]) for k in keep)
+
+
+def _side(seg: Image, vals, who: str):
+    """(array, kind) of one side for the labels ``vals``: the planes ``vals[k] - 1`` of a multi-component image, plane-major, or its label map."""
+    if seg.components > 1:
+        bad = [v for v in vals if not 1 <= v <= seg.components]
+        if bad:
+            raise ValueError(f"evaluate: labels {bad} name a component beyond the {who}'s {seg.components}")
+        planes = np.moveaxis(seg.array, -1, 0)
+        idx = [v - 1 for v in vals]
+        planes = planes[idx[0]:idx[0] + len(idx)] if idx == list(range(idx[0], idx[0] + len(idx))) else planes[idx]
+        return (planes if planes.flags['C_CONTIGUOUS'] else np.ascontiguousarray(planes)), PLANES
+    return np.ascontiguousarray(seg.array), LABELMAP
+
+
+def _ratio(n, d):
+    return None if d == 0 else float(np.float64(n) / np.float64(d))
+
+
+def tolerance_key(t) -> str:
+    """The key of a tolerance in ``surface_dice``: ``repr`` of the float, so a dumped evaluation reads back to the dict."""
+    return repr(float(t))
+
+
+def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: Sequence[float] = (2.0,)) -> Dict[str, dict]:
+    """name -> scores of ``pred`` against ``ref`` for every named label of ``pred`` (``image.get_annotation_labels(pred)``).
+
+    ``pred``, ``ref``: each a multi-component segmentation (label ``v`` is component ``v - 1`` > 0) or a label map (label ``v`` is ``seg == v``),
+    of one spatial shape (else ``ValueError`` with both extents).
+
+    Per label: ``value``, ``count_pred``, ``count_ref``, ``count_both``, ``dice = 2 both / (pred + ref)``, ``iou = both / (pred + ref - both)``,
+    ``precision = both / pred``, ``recall = both / ref`` (float64 quotients of integers), ``mm_pred`` / ``mm_ref`` = count * prod(spacing), and
+    for 2-D inputs (:func:`_plane_axes`) ``surface_dice[tolerance_key(t)] = (within_ab + within_ba) / (border_a + border_b)`` and
+    ``hausdorff = sqrt(max(d2_max_ab, d2_max_ba))`` in mm.  A ratio with a zero denominator is None; a mask that is empty on one side only gives
+    ``hausdorff = inf``; empty on both, None.  For a volume ``surface_dice`` and ``hausdorff`` are absent.
+
+    Route: ``ts2d_label_overlap`` and ``ts2d_surface_distances`` where ``device`` is given, the library has the symbols and the case is served
+    (:func:`device_serves`), else the statements.  The numbers are the same bit for bit either way."""
+    from .image import get_annotation_labels
+    names = get_annotation_labels(pred)
+    sp_pred, sp_ref = tuple(pred.array.shape[:pred.dimension]), tuple(ref.array.shape[:ref.dimension])
+    if sp_pred != sp_ref:
+        raise ValueError(f"evaluate: the segmentation has the extent {sp_pred}, the reference {sp_ref}")
+    tolerances = [float(t) for t in tolerances]
+    if len(tolerances) > MAX_TOLERANCES or any(not (t >= 0.0 and math.isfinite(t)) for t in tolerances):
+        raise ValueError(f"evaluate: at most {MAX_TOLERANCES} tolerances, each finite and not negative, found {tolerances}")
+    out: Dict[str, dict] = {}
+    if not names:
+        return out
+    vals = [int(i['value']) for i in names.values()]
+    a, kind_a = _side(pred, vals, 'segmentation')
+    b, kind_b = _side(ref, vals, 'reference')
+    K = len(vals)
+    flat = _plane_axes(pred)
+    hw = tuple(sp_pred[k] for k in flat[0]) if flat else None
+    on_device = device is not None and device_serves(a, kind_a, b, kind_b, vals, sp_pred, K)
+    if on_device:
+        ov = _device_overlap(a, kind_a, b, kind_b, vals, sp_pred, int(device))
+    else:
+        ov = overlap_statement(a, kind_a, b, kind_b, vals)
+    sf = None
+    if flat:
+        a2 = a.reshape(((K,) if kind_a == PLANES else ()) + hw)
+        b2 = b.reshape(((K,) if kind_b == PLANES else ()) + hw)
+        if on_device:
+            sf = _device_surface(a2, kind_a, b2, kind_b, vals, hw, flat[1], tolerances, int(device))
+        else:
+            sf = surface_statement(a2, kind_a, b2, kind_b, vals, flat[1], tolerances)
+    mm = np.float64(np.prod(np.asarray(pred.spacing, dtype=np.float64)))
+    mm_ref = np.float64(np.prod(np.asarray(ref.spacing, dtype=np.float64)))
+    for k, (name, info) in enumerate(names.items()):
+        na, nb, both = int(ov['n_a'][k]), int(ov['n_b'][k]), int(ov['n_both'][k])
+        e = {'value': int(info['value']), 'count_pred': na, 'count_ref': nb, 'count_both': both, 'dice': _ratio(2 * both, na + nb),
+             'iou': _ratio(both, na + nb - both), 'precision': _ratio(both, na), 'recall': _ratio(both, nb),
+             'mm_pred': float(np.float64(na) * mm), 'mm_ref': float(np.float64(nb) * mm_ref)}
+        if sf is not None:
+            ba, bb = int(sf['border'][k, 0]), int(sf['border'][k, 1])
+            e['surface_dice'] = {tolerance_key(t): _ratio(int(sf['within'][k, 0, i]) + int(sf['within'][k, 1, i]), ba + bb)
+                                 for i, t in enumerate(tolerances)}
+            top = max(float(sf['d2_max'][k, 0]), float(sf['d2_max'][k, 1]))
+            e['hausdorff'] = None if ba + bb == 0 else float(np.sqrt(np.float64(top)))
+        out[name] = e
+    return out
+
+
+def dump_evaluation(result: dict, path: str) -> str:
+    """``json.dump`` with sorted keys; Python floats, so the file reads back to the dict (None is ``null``, an infinite distance ``Infinity``)."""
+    with open(path, 'w') as f:
+        json.dump(result, f, sort_keys=True, indent=1)
+        f.write('\n')
+    return path

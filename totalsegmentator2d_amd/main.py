@@ -42,9 +42,28 @@ def _enumerate_cases(src: str):
     return cases
 
 
+def _references(reference, cases, src_is_dir: bool) -> dict:
+    """case name -> reference file of ``--reference``: a file serves a single input; in a directory the reference of case ``<case>.nrrd`` is the
+    file of the same name, and a case without one is an error that names it (before anything is predicted)."""
+    if reference is None:
+        return {}
+    if os.path.isdir(reference):
+        found = {name: os.path.join(reference, os.path.basename(path)) for name, path in cases}
+        missing = [name for name, ref in found.items() if not os.path.isfile(ref)]
+        if missing:
+            raise FileNotFoundError(f"No reference for case{'s' if len(missing) != 1 else ''} {', '.join(missing)} in {reference} "
+                                    f"(expected {', '.join(os.path.basename(found[n]) for n in missing)})")
+        return found
+    if not os.path.isfile(reference):
+        raise FileNotFoundError(f"Reference does not exist: {reference}")
+    if src_is_dir or len(cases) != 1:
+        raise ValueError(f"A reference file serves a single input; for the {len(cases)} cases of a directory give a directory of references")
+    return {cases[0][0]: reference}
+
+
 def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fetch_remote: bool = True, collapse: bool = False,
              visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1, save_probabilities: bool = False,
-             statistics: bool = False):
+             statistics: bool = False, reference: str = None):
     model = DEFAULT_MODEL if model is None else model
     content = 'all' if visualize else 'file'
     which = 'all' if save_all else 'final'
@@ -52,6 +71,7 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
     log("TS2D is a research tool. It is NOT validated for clinical use and should NOT be used for medical diagnosis or treatment.")
     with TS2D(key=model, use_remote=use_remote, fetch_remote=fetch_remote, models=models) as ts:
         cases = list(_enumerate_cases(src))
+        references = _references(reference, cases, os.path.isdir(src))
         log(f"Predicting {len(cases)} case{'s' if len(cases) != 1 else ''}")
         if batch_cases > 1:
             # groups of `batch_cases` cases share one engine batch per sub-model (TS2D.predict_many); same files, same log lines per case
@@ -65,6 +85,8 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
                     res.save_probabilities(dest, name)
                     if statistics:
                         res.save_statistics(dest, name, models=which)
+                    if references:
+                        res.save_evaluation(dest, name, references[name])
             return
         for i, (name, path) in enumerate(cases):
             log(f"[{i + 1}/{len(cases)}] Processing: {name}")
@@ -73,6 +95,8 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
             res.save_probabilities(dest, name)
             if statistics:
                 res.save_statistics(dest, name, models=which)
+            if references:
+                res.save_evaluation(dest, name, references[name])
 
 
 def ts2d_entry_point(argv=None):
@@ -93,12 +117,15 @@ def ts2d_entry_point(argv=None):
                    "<case>-<group>.npz (key 'probabilities', float32 [K, *shape of the sub-model's 2-D input]) per sub-model.")
     p.add_argument("--statistics", action="store_true", help="Also write <case>.statistics.json: per label count, mm, bounding box, centroid and "
                    "min / max / mean / std of every projection under it (with --save-all one <case>-<group>.statistics.json per sub-model too).")
+    p.add_argument("--reference", type=str, default=None, help="Score every result against a reference and write <case>.evaluation.json (per label "
+                   "Dice, IoU, precision, recall, surface Dice at 2 mm, Hausdorff distance): a 3-D label volume (label v = segment v) or a 2-D "
+                   "segmentation; a file for a single input, or a directory that holds a file of the same name for every case.")
     a = p.parse_args(argv)
     if a.batch_cases < 1:
         p.error("--batch-cases must be at least 1")
     ts2d_run(src=a.src, dest=a.dest, model=a.model, use_remote=not a.no_remote, fetch_remote=not a.no_fetch, collapse=a.collapse,
              visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases, save_probabilities=a.save_probabilities,
-             statistics=a.statistics)
+             statistics=a.statistics, reference=a.reference)
 
 
 if __name__ == '__main__':

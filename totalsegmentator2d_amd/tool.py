@@ -355,6 +355,54 @@ class TS2D:
                 written.append(dump_statistics(self.statistics(key), os.path.join(dest, f"{stem}.statistics.json")))
             return written
 
+        def evaluate(self, reference, model: Optional[str] = None, tolerances=(2.0,)) -> Dict[str, dict]:
+            """Scores of the merged segmentation (``model=None``) or of sub-model ``model``'s against ``reference`` (``evaluate.evaluate``:
+            per label the counts, Dice, IoU, precision, recall and, for a 2-D result, surface Dice per tolerance in mm and the Hausdorff distance).
+
+            ``reference`` (an image or a path) is one of two things.  A 3-D label volume: it is reoriented and projected along the coronal axis
+            with ``evaluate.project_labels`` (``num`` = the number of labels of that segmentation) - on ``self.device`` where the result has one
+            and the entry serves the volume (C-ABI ``ts2d_project_labels_coronal``) - and collapsed as the result's segmentation is; label ``v``
+            of the volume is component ``v - 1``, the convention ``statistics.label_statistics`` documents.  Or an already-2-D segmentation of
+            the result's extent.  A shape or spacing mismatch raises ``ValueError`` with both extents.  Computed on ``self.device``, from the
+            host statements without one: the numbers are the same bit for bit."""
+            from . import evaluate as ev
+            seg = self.get_segmentation(model)
+            if seg is None:
+                raise ValueError(f"no segmentation for model {model!r}")
+            ref = TS2D._as_image(reference)
+            if ref.components == 1 and get_actual_dimension(ref) > 2 and get_actual_dimension(seg) <= 2:
+                from .image import get_annotation_labels
+                num = seg.components if seg.components > 1 else max([int(i['value']) for i in get_annotation_labels(seg).values()] or [1])
+                if self.device is not None and ev.device_projects(ref):
+                    ref = ev.project_labels_coronal_gpu(ref, num, self.device)
+                else:
+                    ref = ev.project_labels(reorient_image(ref, 'RAI'), num, 'coronal')
+                if seg.dimension < 3:
+                    ref = reduce_dimensions(ref)
+            e_seg, e_ref = tuple(seg.array.shape[:seg.dimension]), tuple(ref.array.shape[:ref.dimension])
+            if e_seg != e_ref or not np.allclose(seg.spacing, ref.spacing, rtol=1e-5, atol=1e-8):
+                raise ValueError(f"the reference does not lie on the segmentation's grid: extent {e_ref} with spacing {tuple(ref.spacing)} against "
+                                 f"extent {e_seg} with spacing {tuple(seg.spacing)}")
+            return ev.evaluate(seg, ref, device=self.device, tolerances=tolerances)
+
+        def save_evaluation(self, dest: str, name: str, reference, models='final', naming: str = 'group', tolerances=(2.0,)) -> List[str]:
+            """``<name>.evaluation.json`` for the merged segmentation and ``<name>-<group or model>.evaluation.json`` per sub-model, selected by
+            ``models`` and named as in :meth:`save_statistics`: ``json.dump`` of :meth:`evaluate` against ``reference`` with sorted keys."""
+            from .evaluate import dump_evaluation
+            assert naming in {'group', 'model'}
+            mset = {str(t).strip().lower() for t in _as_list(models)}
+            keys = []
+            if {'all', 'final'} & mset and self.get_segmentation() is not None:
+                keys.append(None)
+            keys += [m for m in self.models if ('all' in mset or m.lower() in mset) and self.get_segmentation(m) is not None]
+            ref = TS2D._as_image(reference)
+            os.makedirs(dest, exist_ok=True)
+            written = []
+            for key in keys:
+                stem = name if key is None else f"{name}-{(decompose_model_key(key)[1] or key) if naming == 'group' else key}"
+                written.append(dump_evaluation(self.evaluate(ref, key, tolerances), os.path.join(dest, f"{stem}.evaluation.json")))
+            return written
+
         def save(self, dest: str, name: str = 'result', ext: str = 'nrrd', models='final', targets='all', content: str = 'all',
                  naming: str = 'group'):
             assert ext.lower() != 'png', "PNG is not a valid export format for the 'file' content type."
