@@ -851,6 +851,33 @@ int ts2d_surface_distances(int device, const uint8_t* a, int kind_a, const uint8
                            double spacing_h, double spacing_w, const double* tol_sq, int T, size_t max_scratch_bytes, int64_t* out_i64,
                            double* out_f64);
 
+/* ts2d_surface_distance_profile: ts2d_surface_distances and, from the same pass over the border pixels, per (label, direction) the SUM of the
+ * boundary distances and their exact ORDER STATISTICS at requested percentiles - what the average surface distances and the percentile Hausdorff
+ * distance (HD95) are made of.  The statement is evaluate.distance_profile_statement; the entry reproduces it bit for bit.  Every argument of
+ * ts2d_surface_distances means what it means there, out_i64 and out_f64 are filled exactly as there, and one call serves a whole evaluation.
+ *   percentiles  [P] float64, P at most TS2D_EVAL_MAX_PERCENTILES (0: none), each in 0 ... 100
+ *   want_sum     not 0: out_sum_f64 is filled
+ *   max_scratch_bytes  as above; per label and pixel 6 bytes, and with percentiles 16 more (the float64 bits of d2 of both directions, kept
+ *                dense: a pixel's key lies at the pixel's place) besides 4 KiB of bins per label and percentile; with the sum 16 bytes per
+ *                label and row.  The result does not depend on the chunking.
+ *   out_sum_f64  [K][2] (want_sum): the sum of sqrt(d2) over the border pixels of the direction's own side, the correctly rounded root, added in
+ *                the ONE fixed order of csrc/stats_tree.h over (H, W) with the term +0.0 for every other pixel (see ts2d_label_statistics).
+ *                +0.0 for an empty border, +inf where only the other side's is empty.
+ *   out_rank_f64 [K][2][P][2] (P > 0): with n border pixels, h = (n - 1) * (percentiles[p] / 100), i = min(floor(h), n - 1) and
+ *                j = min(i + 1, n - 1) in IEEE float64 arithmetic, the d2 at the sorted positions i and j (from 0; ties are repeated values) -
+ *                selected on the integer bits of d2, which order as the values do.  Both -inf for an empty border.
+ *   out_weight_f64  [K][2][P] (P > 0): h - i, the weight of position j in the linear interpolation between the two ROOTS, which the caller
+ *                forms (evaluate.percentile_of_ranks).  +0.0 for an empty border.
+ * TS2D_ERR_INVALID, by name, before any device work: what ts2d_surface_distances refuses, P outside 0 ... TS2D_EVAL_MAX_PERCENTILES or without
+ * percentiles, a percentile that is not a number or lies outside 0 ... 100, a null output that is asked for (out_sum_f64 with want_sum,
+ * out_rank_f64 or out_weight_f64 with P > 0).  On any error the outputs are untouched.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+#define TS2D_EVAL_MAX_PERCENTILES 8
+int ts2d_surface_distance_profile(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int H,
+                                  int W, double spacing_h, double spacing_w, const double* tol_sq, int T, const double* percentiles, int P,
+                                  int want_sum, size_t max_scratch_bytes, int64_t* out_i64, double* out_f64, double* out_sum_f64,
+                                  double* out_rank_f64, double* out_weight_f64);
+
 /* Synthetic slice stream on the device (BASELINE config 4: "synthetic 10k-slice stream", generated per rank from (seed, slice
  * index) so that no host transfer skews the timing).  Writes n_elements fp32 values, approximately N(0,1), to device memory:
  * element i of the call = element (first_element + i) of the stream identified by `key`; a value depends on (key, element index)

@@ -83,6 +83,7 @@ VISUAL_NONFINITE = 1                                        # TS2D_VISUAL_NONFIN
 STATS_PLANES, STATS_LABELMAP, STATS_NONFINITE = 0, 1, 1     # TS2D_STATS_PLANES, TS2D_STATS_LABELMAP, TS2D_STATS_NONFINITE
 STATS_INTS, STATS_F64S, STATS_MAX_CHANNELS = 10, 6, 64      # TS2D_STATS_INTS, TS2D_STATS_F64S, TS2D_STATS_MAX_CHANNELS
 LABELS_RANGE, EVAL_MAX_TOLERANCES, EVAL_MAX_EXTENT = 1, 8, 32767      # TS2D_LABELS_RANGE, TS2D_EVAL_MAX_TOLERANCES, TS2D_EVAL_MAX_EXTENT
+EVAL_MAX_PERCENTILES = 8                                    # TS2D_EVAL_MAX_PERCENTILES
 
 # shorthands of the table below: int, void *, size_t, long long, unsigned long long, char *; pointers to a void * and to the three descriptors
 _I, _P, _Z, _LL, _ULL, _S = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_char_p
@@ -134,6 +135,7 @@ SIGNATURES = {
     'ts2d_project_labels_coronal': (_I, _PROJECT[:-2] + [_I, _P, _P]),
     'ts2d_label_overlap': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     'ts2d_surface_distances': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _D, _D, _P, _I, _Z, _P, _P]),
+    'ts2d_surface_distance_profile': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _D, _D, _P, _I, _P, _I, _I, _Z, _P, _P, _P, _P, _P]),
     'ts2d_synth_slices': (_I, [_I, _ULL, _ULL, _ULL, _P, _P]),
     'ts2d_engine_reserve': (_I, [_P, _I, _I, _I]),
     'ts2d_engine_workspace_bytes': (_I, [_P, _I, _I, _I, ctypes.POINTER(_Z)]),
@@ -162,10 +164,11 @@ SYMBOLS = tuple(SIGNATURES)
 # ... and the two entries of the PNG visuals: without them visual.create_visual returns the statement's bytes from the host
 # ... and the per-label statistics: without the entry statistics.label_statistics keeps the host route (its statement)
 # ... and the three entries of the evaluation: without them evaluate.evaluate and Result.evaluate keep the host route (the statements)
+# ... and the distance profile: without the entry evaluate.evaluate takes percentiles and average distances from its statement
 OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n
                      or n.startswith('ts2d_visual_')
                      or n in ('ts2d_engine_create_residual', 'ts2d_keep_largest_components', 'ts2d_project_coronal_modes', 'ts2d_label_statistics',
-                              'ts2d_project_labels_coronal', 'ts2d_label_overlap', 'ts2d_surface_distances'))
+                              'ts2d_project_labels_coronal', 'ts2d_label_overlap', 'ts2d_surface_distances', 'ts2d_surface_distance_profile'))
 
 
 class EngineLibraryError(RuntimeError):

@@ -1,9 +1,11 @@
-// Scoring a segmentation against a reference, none of which needs an engine: ts2d_project_labels_coronal, ts2d_label_overlap and
-// ts2d_surface_distances (kernels_evaluate.h; the arithmetic of the distances: surface_dist.h; the statements: totalsegmentator2d_amd/evaluate.py).
+// Scoring a segmentation against a reference, none of which needs an engine: ts2d_project_labels_coronal, ts2d_label_overlap,
+// ts2d_surface_distances (kernels_evaluate.h) and ts2d_surface_distance_profile (kernels_evaluate_profile.h); the arithmetic of the distances:
+// surface_dist.h; the statements: totalsegmentator2d_amd/evaluate.py.
 // Host pointers in and out; a call uploads each input once, works on the device and downloads once; every device buffer of a call is one DevMem,
 // so HIP_TRY may return wherever it fails.
 #include "engine_internal.h"
 #include "kernels_evaluate.h"
+#include "kernels_evaluate_profile.h"
 
 #include <cstring>
 #include <vector>
@@ -13,6 +15,7 @@ using namespace ts2d;
 static_assert(kSdPlanes == TS2D_STATS_PLANES && kSdLabelMap == TS2D_STATS_LABELMAP, "the kinds speak the C header's numbers");
 static_assert(kPlStatusRange == TS2D_LABELS_RANGE && kSdMaxTolerances == TS2D_EVAL_MAX_TOLERANCES && kSdMaxExtent == TS2D_EVAL_MAX_EXTENT,
               "the status bit and the limits speak the C header's numbers");
+static_assert(kSdMaxPercentiles == TS2D_EVAL_MAX_PERCENTILES, "the limits speak the C header's numbers");
 
 #pragma GCC visibility push(hidden)
 namespace {
@@ -178,6 +181,108 @@ int ts2d_surface_distances(int device, const uint8_t* a, int kind_a, const uint8
         if (border == 0) key = 0xFFF0000000000000ull;                              // an empty border: -inf
         memcpy(out_f64 + i, &key, sizeof(key));
     }
+    return TS2D_OK;
+}
+
+int ts2d_surface_distance_profile(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int H,
+                                  int W, double spacing_h, double spacing_w, const double* tol_sq, int T, const double* percentiles, int P,
+                                  int want_sum, size_t max_scratch_bytes, int64_t* out_i64, double* out_f64, double* out_sum_f64,
+                                  double* out_rank_f64, double* out_weight_f64) {
+    const char* const E = "ts2d_surface_distance_profile";
+    if (!out_i64 || !out_f64) return fail(TS2D_ERR_INVALID, "%s: null output", E);
+    if (H < 1 || W < 1 || H > kSdMaxExtent || W > kSdMaxExtent) return fail(TS2D_ERR_INVALID, "%s: %d x %d outside 1 ... %d per axis", E, H, W, kSdMaxExtent);
+    if (T < 0 || T > kSdMaxTolerances || (T > 0 && !tol_sq)) return fail(TS2D_ERR_INVALID, "%s: T = %d tolerances outside 0 ... %d, or without tol_sq", E, T, kSdMaxTolerances);
+    if (!(spacing_h > 0.0 && spacing_h < 1e300 && spacing_w > 0.0 && spacing_w < 1e300))
+        return fail(TS2D_ERR_INVALID, "%s: spacing %g x %g is not finite and positive", E, spacing_h, spacing_w);
+    SdTolerances tol = {};
+    for (int t = 0; t < T; ++t) {
+        if (!(tol_sq[t] >= 0.0)) return fail(TS2D_ERR_INVALID, "%s: tol_sq[%d] = %g is negative or not a number", E, t, tol_sq[t]);
+        tol.sq[t] = tol_sq[t];
+    }
+    if (P < 0 || P > kSdMaxPercentiles || (P > 0 && !percentiles))
+        return fail(TS2D_ERR_INVALID, "%s: P = %d percentiles outside 0 ... %d, or without percentiles", E, P, kSdMaxPercentiles);
+    SdPercentiles pc = {};
+    for (int p = 0; p < P; ++p) {
+        if (!(percentiles[p] >= 0.0 && percentiles[p] <= 100.0)) return fail(TS2D_ERR_INVALID, "%s: percentiles[%d] = %g outside 0 ... 100", E, p, percentiles[p]);
+        pc.q[p] = percentiles[p];
+    }
+    if ((P > 0 && (!out_rank_f64 || !out_weight_f64)) || (want_sum && !out_sum_f64))
+        return fail(TS2D_ERR_INVALID, "%s: null output for the %s", E, want_sum && !out_sum_f64 ? "sum" : "percentiles");
+    const size_t n = (size_t)H * W;
+    size_t bytes_a = 0, bytes_b = 0;
+    TRY(check_sides(E, a, kind_a, b, kind_b, values, K, n, &bytes_a, &bytes_b));
+    // a label's scratch: the border bytes and the uint16 row distances of both sides; with percentiles the keys of both directions and the bins
+    // of its 2 * 2 P selections; with the sum the row partials of both directions
+    const int R = 2 * P;
+    const size_t bins_label = (size_t)2 * R * kSdDigits * sizeof(uint32_t);
+    const size_t per_label = n * 2 * (1 + sizeof(uint16_t)) + (P ? n * 2 * sizeof(uint64_t) + bins_label : 0) + (want_sum ? (size_t)H * 2 * sizeof(double) : 0);
+    const size_t budget = max_scratch_bytes ? max_scratch_bytes : ((size_t)256 << 20);
+    size_t L = budget / per_label;
+    if (L < 1)
+        return fail(TS2D_ERR_INVALID, "%s: the scratch of ONE label (%d x %d) takes %zu bytes, above max_scratch_bytes = %zu", E, H, W, per_label, budget);
+    if (L > (size_t)K) L = (size_t)K;
+    HIP_TRY(hipSetDevice(device));
+    // [counts | keys | sums | prefixes | weights || ranks | bins of a chunk | values | a | b | border of a chunk | g | key buffer | row partials]
+    const size_t n_cnt = (size_t)K * 2 * (1 + T), n_sel = (size_t)K * 2 * R;
+    const size_t o_key = align_up(n_cnt * sizeof(unsigned long long), 256), o_sum = align_up(o_key + (size_t)K * 2 * sizeof(unsigned long long), 256);
+    const size_t o_pre = align_up(o_sum + (size_t)K * 2 * sizeof(double), 256), o_wgt = align_up(o_pre + n_sel * sizeof(uint64_t), 256);
+    const size_t o_rank = align_up(o_wgt + (size_t)K * 2 * P * sizeof(double), 256), o_bins = align_up(o_rank + n_sel * sizeof(long long), 256);
+    const size_t o_val = align_up(o_bins + (P ? L * bins_label : 0), 256);
+    const size_t o_a = o_val + 256, o_b = align_up(o_a + bytes_a, 256), o_border = align_up(o_b + bytes_b, 256);
+    const size_t o_g = align_up(o_border + L * 2 * n, 256), o_kbuf = align_up(o_g + L * 2 * n * sizeof(uint16_t), 256);
+    const size_t o_rows = align_up(o_kbuf + (P ? L * 2 * n * sizeof(uint64_t) : 0), 256), total = o_rows + (want_sum ? L * 2 * (size_t)H * sizeof(double) : 0);
+    DevMem d;
+    HIP_TRY(d.alloc(total));
+    HIP_TRY(hipMemset(d.as<char>(), 0, o_a));
+    if (values) HIP_TRY(hipMemcpy(d.as<char>(o_val), values, (size_t)K, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_a), a, bytes_a, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_b), b, bytes_b, hipMemcpyHostToDevice));
+    unsigned long long* const d_cnt = d.as<unsigned long long>();
+    unsigned long long* const d_key = d.as<unsigned long long>(o_key);
+    long long* const d_rank = d.as<long long>(o_rank);
+    uint64_t* const d_pre = d.as<uint64_t>(o_pre);
+    uint32_t* const d_bins = d.as<uint32_t>(o_bins);
+    uint64_t* const d_kbuf = P ? d.as<uint64_t>(o_kbuf) : nullptr;
+    double* const d_rows = want_sum ? d.as<double>(o_rows) : nullptr;
+    size_t hist_blocks = (n + 1023) / 1024;                                          // 16 keys per lane, up to the cap
+    if (hist_blocks > (size_t)kSpHistMaxBlocks) hist_blocks = kSpHistMaxBlocks;
+    for (int k0 = 0; k0 < K; k0 += (int)L) {
+        const unsigned labels = (unsigned)(K - k0 < (int)L ? K - k0 : (int)L);
+        hipLaunchKernelGGL(sd_columns, dim3((unsigned)((W + 63) / 64), 2, labels), dim3(64), 0, 0, d.as<const uint8_t>(o_a), kind_a,
+                           d.as<const uint8_t>(o_b), kind_b, d.as<const uint8_t>(o_val), k0, H, W, d.as<uint8_t>(o_border), d.as<uint16_t>(o_g));
+        hipLaunchKernelGGL(sd_rows_profile, dim3((unsigned)H, 2, labels), dim3(64), 0, 0, d.as<const uint8_t>(o_border), d.as<const uint16_t>(o_g), k0,
+                           H, W, spacing_h, spacing_w, tol, T, d_cnt, d_key, d_kbuf, d_rows);
+        if (want_sum) hipLaunchKernelGGL(sd_profile_combine, dim3(2, labels), dim3(64), 0, 0, d_rows, k0, H, d.as<double>(o_sum));
+        if (P) {
+            hipLaunchKernelGGL(sd_select_init, dim3(labels), dim3(64), 0, 0, d_cnt, k0, T, pc, P, d_rank, d_pre, d.as<double>(o_wgt));
+            for (int rnd = 0; rnd < kSdRounds; ++rnd) {
+                hipLaunchKernelGGL(sd_select_hist, dim3((unsigned)hist_blocks, 2, labels), dim3(64), 0, 0, d_kbuf, k0, (long long)n, R, rnd, d_rank,
+                                   d_pre, d_bins);
+                hipLaunchKernelGGL(sd_select_decide, dim3((unsigned)R, 2, labels), dim3(64), 0, 0, k0, R, rnd, d_rank, d_pre, d_bins);
+            }
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    // one download: counts, keys, sums, prefixes and weights lie next to each other (the gaps of the alignment go along)
+    std::vector<char> host(o_rank);
+    HIP_TRY(hipMemcpy(host.data(), d.as<char>(), host.size(), hipMemcpyDeviceToHost));
+    memcpy(out_i64, host.data(), n_cnt * sizeof(int64_t));
+    const uint64_t minus_inf = 0xFFF0000000000000ull;
+    for (int i = 0; i < K * 2; ++i) {
+        long long border;
+        uint64_t key;
+        memcpy(&border, host.data() + (size_t)i * (1 + T) * sizeof(int64_t), sizeof(border));
+        memcpy(&key, host.data() + o_key + (size_t)i * sizeof(uint64_t), sizeof(key));
+        if (border == 0) key = minus_inf;                                          // an empty border: -inf
+        memcpy(out_f64 + i, &key, sizeof(key));
+        for (int r = 0; r < R; ++r) {
+            memcpy(&key, host.data() + o_pre + ((size_t)i * R + r) * sizeof(uint64_t), sizeof(key));
+            if (border == 0) key = minus_inf;
+            memcpy(out_rank_f64 + (size_t)i * R + r, &key, sizeof(key));
+        }
+    }
+    if (want_sum) memcpy(out_sum_f64, host.data() + o_sum, (size_t)K * 2 * sizeof(double));
+    if (P) memcpy(out_weight_f64, host.data() + o_wgt, (size_t)K * 2 * P * sizeof(double));
     return TS2D_OK;
 }
 

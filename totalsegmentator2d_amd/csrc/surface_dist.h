@@ -19,9 +19,23 @@
 //   pass 1, per column    g(y, x') = min |y - y'| over the border rows y' of column x': a downward scan (nearest at or above) and an upward
 //                         scan (nearest at or below); kSdNone where the column has no border pixel
 //   pass 2, per border pixel of the row    the minimum over x' of sd_candidate(g(py, x'), |px - x'|)
+//
+// The distance profile (ts2d_surface_distance_profile; the statement: evaluate.distance_profile_statement) keeps every border pixel's d2.
+//   Sum.  The term of pixel (y, x) is sd_sqrt(d2) where it is a border pixel of the direction's own side, +0.0 elsewhere, and the terms meet in
+//   the tree of stats_tree.h over (H, W): per row lane l of 64 adds the terms at x = l, l + 64, ... in increasing x from +0.0, the lanes are
+//   halved, and the row partials meet the same way.  No term is negative, so an infinite term makes the sum +inf and never a NaN.
+//   Order statistics.  The root is monotone, so the distance at sorted position r is the root of the d2 at sorted position r, and d2 >= +0.0 orders
+//   as its key (sd_key) does.  The key at position r is built from its top digit down, eight rounds of eight bits (rs_decide of ray_select.h
+//   generalised to a digit): with the digits above decided (`prefix`), a round counts per digit value the candidates - the keys that agree with
+//   the prefix on those digits -; the digit is the first whose running count passes r, and the count below it is taken off r.  Integers only.
+//   Ranks.  For percentile q among n >= 1 sorted values: h = (n - 1) * (q / 100), i = min(floor(h), n - 1), j = min(i + 1, n - 1), t = h - i, each
+//   operation an IEEE float64 one (sd_percentile_ranks); the caller interpolates between the roots of the two selected d2.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
+
+#include "stats_tree.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define TS2D_SD_HD __host__ __device__ __forceinline__
@@ -35,6 +49,10 @@ enum { kSdPlanes = 0, kSdLabelMap = 1 };      // TS2D_STATS_PLANES, TS2D_STATS_L
 constexpr uint16_t kSdNone = 0xFFFFu;          // g of a column without a border pixel (H <= kSdMaxExtent keeps every real g below it)
 constexpr int kSdMaxExtent = 32767;
 constexpr int kSdMaxTolerances = 8;            // TS2D_EVAL_MAX_TOLERANCES
+constexpr int kSdMaxPercentiles = 8;           // TS2D_EVAL_MAX_PERCENTILES
+constexpr int kSdMaxRanks = 2 * kSdMaxPercentiles;      // a percentile selects two sorted positions
+constexpr uint64_t kSdNoKey = ~0ull;           // in a key buffer: not a border pixel (the bits of a NaN: no d2 has them)
+constexpr int kSdRounds = 8, kSdDigits = 256;  // a 64-bit key in 8-bit digits, the top one first
 
 // does a segmentation sample belong to the label?  planes: the label's own plane > 0; label map: the sample equals the label's value
 TS2D_SD_HD bool sd_masked(uint8_t s, int kind, uint8_t value) { return kind == kSdLabelMap ? s == value : s > 0; }
@@ -72,6 +90,52 @@ TS2D_SD_HD uint64_t sd_key(double d2) {
     uint64_t u;
     memcpy(&u, &d2, sizeof(u));
     return u;
+}
+
+TS2D_SD_HD double sd_unkey(uint64_t key) {
+    double d;
+    memcpy(&d, &key, sizeof(d));
+    return d;
+}
+
+// the distance of a d2: the correctly rounded root, np.sqrt's bits (IEEE on the host; the device's double sqrt is correctly rounded without
+// fast-math, and tests/test_gpu_evaluate_profile.py holds it against np.sqrt on the values the distances take)
+TS2D_SD_HD double sd_sqrt(double d2) { return sqrt(d2); }
+
+// the sorted positions i <= j and the weight t of percentile q (0 ... 100) among n >= 1 values
+TS2D_SD_HD void sd_percentile_ranks(long long n, double q, long long* i, long long* j, double* t) {
+#pragma clang fp contract(off)
+    const double f = q / 100.0;
+    const double h = (double)(n - 1) * f;
+    long long lo = (long long)floor(h);
+    lo = lo < n - 1 ? lo : n - 1;
+    *i = lo;
+    *j = lo + 1 < n - 1 ? lo + 1 : n - 1;
+    *t = h - (double)lo;
+}
+
+// round rnd (0 ... 7) looks at the bits [shift, shift + 8) of a key
+TS2D_SD_HD int sd_round_shift(int rnd) { return 8 * (kSdRounds - 1 - rnd); }
+// does a key agree with the prefix on the digits decided before round rnd?
+TS2D_SD_HD bool sd_digit_candidate(uint64_t key, uint64_t prefix, int rnd) {
+    return rnd == 0 || (key >> (sd_round_shift(rnd) + 8)) == (prefix >> (sd_round_shift(rnd) + 8));
+}
+TS2D_SD_HD int sd_digit(uint64_t key, int rnd) { return (int)((key >> sd_round_shift(rnd)) & 0xFFu); }
+
+// One decision over FOUR adjacent digit values d0 ... d0 + 3 with c[] candidates each, `below` candidates under d0: where sorted position *rank
+// falls among them, the digit goes into the prefix, the candidates under it come off the rank, and the result is true.
+TS2D_SD_HD bool sd_decide_quad(const uint32_t* c, int d0, long long below, int rnd, long long* rank, uint64_t* prefix) {
+    long long r = *rank - below;
+    if (r < 0) return false;
+    for (int j = 0; j < 4; ++j) {
+        if (r < (long long)c[j]) {
+            *rank = r;
+            *prefix |= (uint64_t)(d0 + j) << sd_round_shift(rnd);
+            return true;
+        }
+        r -= (long long)c[j];
+    }
+    return false;
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -116,6 +180,71 @@ inline long long sd_label(const uint8_t* own, int kind_own, const uint8_t* other
             *key_max = key > *key_max ? key : *key_max;
             for (int t = 0; t < T; ++t) within[t] += d2 <= tol_sq[t] ? 1 : 0;
         }
+    return n;
+}
+
+// The key at sorted position rank (0 <= rank < the number of keys other than kSdNoKey) of keys[0 ... n - 1]: what sd_select_hist and
+// sd_select_decide compute together.
+inline uint64_t sd_select_rank(const uint64_t* keys, size_t n, long long rank) {
+    uint64_t prefix = 0;
+    for (int rnd = 0; rnd < kSdRounds; ++rnd) {
+        uint32_t bins[kSdDigits] = {0};
+        for (size_t i = 0; i < n; ++i)
+            if (keys[i] != kSdNoKey && sd_digit_candidate(keys[i], prefix, rnd)) ++bins[sd_digit(keys[i], rnd)];
+        long long below = 0;
+        for (int d0 = 0; d0 < kSdDigits; d0 += 4) {
+            if (sd_decide_quad(bins + d0, d0, below, rnd, &rank, &prefix)) break;
+            below += (long long)bins[d0] + bins[d0 + 1] + bins[d0 + 2] + bins[d0 + 3];
+        }
+    }
+    return prefix;
+}
+
+// sd_label with the profile, what sd_columns, sd_rows_profile, sd_profile_combine and the selection kernels compute together: also the sum of
+// the distances in the tree over (H, W) and per percentile q[p] the keys at the two sorted positions (rank_keys [P][2]) and the weight
+// (weights [P]); an empty border leaves rank_keys and weights alone and gives the sum +0.0.  keys: H * W, partial: H of scratch.
+inline long long sd_label_profile(const uint8_t* own, int kind_own, const uint8_t* other, int kind_other, uint8_t value, int H, int W, double sy,
+                                  double sx, const double* tol_sq, int T, const double* q, int P, uint8_t* border_own, uint8_t* border_other,
+                                  uint16_t* g, uint64_t* keys, double* partial, uint64_t* key_max, long long* within, double* dist_sum,
+                                  uint64_t* rank_keys, double* weights) {
+#pragma clang fp contract(off)
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            border_own[(size_t)y * W + x] = sd_border(own, kind_own, value, H, W, y, x) ? 1 : 0;
+            border_other[(size_t)y * W + x] = sd_border(other, kind_other, value, H, W, y, x) ? 1 : 0;
+        }
+    for (int x = 0; x < W; ++x) sd_column(border_other, H, W, x, g);
+    long long n = 0;
+    *key_max = 0;
+    for (int t = 0; t < T; ++t) within[t] = 0;
+    double v[kStLanes];
+    for (int y = 0; y < H; ++y) {
+        for (int l = 0; l < kStLanes; ++l) v[l] = 0.0;
+        for (int x = 0; x < W; ++x) {
+            keys[(size_t)y * W + x] = kSdNoKey;
+            if (!border_own[(size_t)y * W + x]) continue;
+            double d2 = sd_inf();
+            for (int xo = 0; xo < W; ++xo) {
+                const double c = sd_candidate(g[(size_t)y * W + xo], xo > x ? xo - x : x - xo, sy, sx);
+                d2 = c < d2 ? c : d2;
+            }
+            ++n;
+            const uint64_t key = sd_key(d2);
+            keys[(size_t)y * W + x] = key;
+            *key_max = key > *key_max ? key : *key_max;
+            for (int t = 0; t < T; ++t) within[t] += d2 <= tol_sq[t] ? 1 : 0;
+            v[x % kStLanes] = v[x % kStLanes] + sd_sqrt(d2);          // increasing x: lane x % 64 meets its terms in order
+        }
+        partial[y] = st_halve(v);
+    }
+    for (int l = 0; l < kStLanes; ++l) v[l] = st_lane_rows(partial, H, l);
+    *dist_sum = st_halve(v);
+    for (int p = 0; p < P && n > 0; ++p) {
+        long long i, j;
+        sd_percentile_ranks(n, q[p], &i, &j, weights + p);
+        rank_keys[2 * p] = sd_select_rank(keys, (size_t)H * W, i);
+        rank_keys[2 * p + 1] = sd_select_rank(keys, (size_t)H * W, j);
+    }
     return n;
 }
 #endif

@@ -857,6 +857,37 @@ def surface_distances(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, va
     return out_i, out_f
 
 
+def surface_profile_scratch_per_label(shape_hw, n_percentiles: int, want_sum: bool) -> int:
+    """The scratch bytes ts2d_surface_distance_profile needs per label (include/ts2d_engine.h): what ``max_scratch_bytes`` is divided by."""
+    h, w = (int(v) for v in shape_hw)
+    p = int(n_percentiles)
+    return 6 * h * w + (16 * h * w + 4096 * p if p else 0) + (16 * h if want_sum else 0)
+
+
+def surface_distance_profile(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, shape_hw, spacing_hw, tol_sq, percentiles,
+                             want_sum: bool, max_scratch_bytes: int = 0, device: int = 0):
+    """:func:`surface_distances` and the distance profile in one call (C-ABI ts2d_surface_distance_profile).  ``percentiles``: float64 [P] in
+    0 ... 100.  Returns ``(int64 [K, 2, 1 + T], float64 [K, 2], sums float64 [K, 2] or None, ranks float64 [K, 2, P, 2], weights float64
+    [K, 2, P])`` in the layout of include/ts2d_engine.h."""
+    fn = _evaluate_entry('ts2d_surface_distance_profile')
+    h, w = (int(v) for v in shape_hw)
+    k, vals = _evaluate_sides('surface_distance_profile', a, kind_a, b, kind_b, values, h * w)
+    tol = np.ascontiguousarray(tol_sq, dtype=np.float64)
+    pct = np.ascontiguousarray(percentiles, dtype=np.float64)
+    t, p = int(tol.size), int(pct.size)
+    out_i = np.zeros((k, 2, 1 + t), np.int64)
+    out_f = np.zeros((k, 2), np.float64)
+    out_sum = np.zeros((k, 2), np.float64) if want_sum else None
+    out_rank = np.zeros((k, 2, p, 2), np.float64)
+    out_weight = np.zeros((k, 2, p), np.float64)
+    _lib.check(fn(int(device), a.ctypes.data, int(kind_a), b.ctypes.data, int(kind_b), vals.ctypes.data if vals is not None else None, k, h, w,
+                  float(spacing_hw[0]), float(spacing_hw[1]), tol.ctypes.data if t else None, t, pct.ctypes.data if p else None, p,
+                  1 if want_sum else 0, int(max_scratch_bytes), out_i.ctypes.data, out_f.ctypes.data,
+                  out_sum.ctypes.data if want_sum else None, out_rank.ctypes.data if p else None, out_weight.ctypes.data if p else None),
+               'ts2d_surface_distance_profile')
+    return out_i, out_f, out_sum, out_rank, out_weight
+
+
 def _read_tiled_inf(engines, desc, n_images, engine_flags: bool):
     """The inf flags a tiled call left behind (upstream's inf check, done on the device).  With descriptors, ``last_tiled_inf_per_image``
     of the first engine is their per-image flags; ``last_tiled_inf`` of every engine is its own flag in the library (the flat entry and

@@ -1,9 +1,10 @@
 """Score a segmentation against a reference: the label projection of a 3-D label volume, overlap counts (Dice, IoU, precision, recall) and, for
-2-D planes, boundary distances (surface Dice, Hausdorff distance).
+2-D planes, boundary distances (surface Dice, Hausdorff distance; on request its percentiles - HD95 - and the average surface distances).
 
 The functions ``*_statement`` and :func:`project_labels` are the project's definition - written in numpy, they are the host route and the
-oracle of the device route (C-ABI ``ts2d_project_labels_coronal``, ``ts2d_label_overlap``, ``ts2d_surface_distances``;
-``csrc/kernels_evaluate.h``), which reproduces them bit for bit, as ``statistics.py``, ``visual.py`` and ``postprocess.py`` are for their entries.
+oracle of the device route (C-ABI ``ts2d_project_labels_coronal``, ``ts2d_label_overlap``, ``ts2d_surface_distances``,
+``ts2d_surface_distance_profile``; ``csrc/kernels_evaluate.h``, ``csrc/kernels_evaluate_profile.h``), which reproduces them bit for bit, as
+``statistics.py``, ``visual.py`` and ``postprocess.py`` are for their entries.
 
 LABEL PROJECTION.  TotalSegmentator 2D is trained and evaluated on 3-D label volumes projected into one binary plane per label: the reference's
 ``project(..., 'multiclass:<num>')`` (``ts2d/core/util/image.py:164-194``, ``_project_multiclass``).  :func:`project_labels` restates it.  Its
@@ -35,10 +36,12 @@ from .nrrd import Image
 
 PLANES, LABELMAP = 0, 1          # _lib.STATS_PLANES, _lib.STATS_LABELMAP: the kinds of ts2d_label_statistics
 MAX_TOLERANCES = 8               # _lib.EVAL_MAX_TOLERANCES
+MAX_PERCENTILES = 8              # _lib.EVAL_MAX_PERCENTILES
 _AXES = {'a': 2, 'ax': 2, 'axial': 2, 's': 0, 'sag': 0, 'sagittal': 0, 'c': 1, 'cor': 1, 'coronal': 1}
 # No size gate: the device route lost at no measured size, the small end included - 117 labels at 53 x 133 take 0.17 ms (overlap) and 0.56 ms
 # (distances) there against 0.38 ms and 25.6 ms for the statements; the narrowest win is the overlap of 18 labels at 600 x 512, 0.56 ms against
-# 0.69 ... 0.87 ms (scripts/gpu_evaluate_case.py, profiles/r29_evaluate_case.txt).
+# 0.69 ... 0.87 ms (scripts/gpu_evaluate_case.py, profiles/r29_evaluate_case.txt).  The distance profile likewise: 0.65 ... 0.70 ms against 32 ms
+# there, 4.7 ms against 990 ms for 117 labels at 644 x 337 (scripts/gpu_evaluate_profile_case.py, profiles/r30_distance_profile_case.txt).
 
 
 # ------------------------------------------------------------------------------------------------------------------ label projection
@@ -220,6 +223,83 @@ def surface_statement(a, kind_a: int, b, kind_b: int, values, spacing_hw, tolera
     return out
 
 
+def _percentiles(percentiles, who: str) -> list:
+    qs = [float(q) for q in percentiles]
+    if len(qs) > MAX_PERCENTILES or any(not (math.isfinite(q) and 0.0 <= q <= 100.0) for q in qs):
+        raise ValueError(f"{who}: at most {MAX_PERCENTILES} percentiles, each finite and in 0 ... 100, found {qs}")
+    return qs
+
+
+def percentile_ranks(n: int, q: float):
+    """``(i, j, t)``: the sorted positions and the weight of percentile ``q`` among ``n >= 1`` values - ``h = (n - 1) * (q / 100)`` in float64,
+    ``i = min(floor(h), n - 1)``, ``j = min(i + 1, n - 1)``, ``t = h - i`` (``sd_percentile_ranks`` of csrc/surface_dist.h)."""
+    h = np.float64(n - 1) * (np.float64(q) / np.float64(100))
+    i = min(int(np.floor(h)), n - 1)
+    return i, min(i + 1, n - 1), np.float64(h - np.float64(i))
+
+
+def percentile_of_ranks(d2_i, d2_j, t) -> np.float64:
+    """The percentile of the DISTANCES from the two selected squared distances and the weight (:func:`percentile_ranks`): numpy's linear method
+    spelled out, every operation rounded on its own.  ``lo = sqrt(d2_i)``, ``hi = sqrt(d2_j)``; ``lo`` where ``t == 0`` or ``hi == lo``, else
+    ``lo + (hi - lo) * t`` for ``t < 0.5`` and ``hi - (hi - lo) * (1 - t)`` from there.  Infinite distances give ``inf`` (``np.percentile`` gives
+    NaN as soon as one is in the set), and the index arithmetic does not depend on the numpy at hand."""
+    lo, hi, t = np.sqrt(np.float64(d2_i)), np.sqrt(np.float64(d2_j)), np.float64(t)
+    if t == 0 or hi == lo:
+        return lo
+    if t < 0.5:
+        return lo + (hi - lo) * t
+    return hi - (hi - lo) * (np.float64(1) - t)
+
+
+def distance_profile_statement(a, kind_a: int, b, kind_b: int, values, spacing_hw, tolerances: Sequence[float], percentiles: Sequence[float]) -> dict:
+    """THE DEFINITION of the distance profile: the inputs, the refusals and the results of :func:`surface_statement` (the same bits), and over
+    the K labels and the two directions
+
+    ``dist_sum`` float64 [K, 2]: ``statistics.tree_sum`` over terms [H, W] - ``np.sqrt(d2)`` at a border pixel of the direction's own side,
+    ``+0.0`` elsewhere; ``+0.0`` for an empty border, ``+inf`` where only the other side's is empty (no term is negative: never a NaN).
+    ``d2_rank`` float64 [K, 2, P, 2]: per percentile the ``d2`` at the sorted positions ``i`` and ``j`` of :func:`percentile_ranks` - exact
+    bits, ties being repeated values; both ``-inf`` for an empty border.
+    ``rank_weight`` float64 [K, 2, P]: its ``t``; ``+0.0`` for an empty border.
+
+    The root is monotone, so the order statistics of the distances are the roots of those of ``d2``: :func:`percentile_of_ranks` makes the
+    percentile of the two."""
+    from .statistics import tree_sum
+    qs = _percentiles(percentiles, 'distance_profile_statement')
+    a, b, spatial, K = _sides(a, kind_a, b, kind_b, values)
+    if len(spatial) == 3 and spatial[0] == 1:
+        spatial = spatial[1:]
+        a = a.reshape((K,) + spatial if kind_a == PLANES else spatial)
+        b = b.reshape((K,) + spatial if kind_b == PLANES else spatial)
+    if len(spatial) != 2:
+        raise ValueError(f"distance_profile_statement: boundary distances are defined for 2-D planes, found the extent {tuple(spatial)}")
+    tol = np.asarray(list(tolerances), np.float64)
+    tol_sq = tol * tol
+    T, P = len(tol), len(qs)
+    out = {'border': np.zeros((K, 2), np.int64), 'd2_max': np.full((K, 2), -np.inf, np.float64), 'within': np.zeros((K, 2, T), np.int64),
+           'dist_sum': np.zeros((K, 2), np.float64), 'd2_rank': np.full((K, 2, P, 2), -np.inf, np.float64),
+           'rank_weight': np.zeros((K, 2, P), np.float64)}
+    for k in range(K):
+        ba, bb = border_of(_mask(a, kind_a, values, k)), border_of(_mask(b, kind_b, values, k))
+        for d, (own, other) in enumerate(((ba, bb), (bb, ba))):
+            n = int(np.count_nonzero(own))
+            out['border'][k, d] = n
+            if n == 0:
+                continue
+            d2 = d2_from_rows(own, row_distance(other), spacing_hw)                      # (the walk of surface_statement up to here)
+            out['d2_max'][k, d] = d2.max()
+            for t in range(T):
+                out['within'][k, d, t] = np.count_nonzero(d2 <= tol_sq[t])
+            terms = np.zeros(spatial, np.float64)
+            terms[own] = np.sqrt(d2)                                                     # (np.nonzero order on both sides)
+            out['dist_sum'][k, d] = tree_sum(terms)
+            ordered = np.sort(d2)
+            for p, q in enumerate(qs):
+                i, j, t = percentile_ranks(n, q)
+                out['d2_rank'][k, d, p] = ordered[i], ordered[j]
+                out['rank_weight'][k, d, p] = t
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------ the device route
 def device_serves(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, spatial, K: int) -> bool:
     """Do ``ts2d_label_overlap`` and ``ts2d_surface_distances`` serve the case?  uint8 samples, 1 ... 255 labels (label-map values 1 ... 255), at
@@ -251,6 +331,28 @@ def _device_surface(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, de
     oi, of = engine.surface_distances(np.ascontiguousarray(a), kind_a, np.ascontiguousarray(b), kind_b, values, hw, spacing_hw, tol * tol,
                                       max_scratch_bytes, device)
     return {'border': oi[:, :, 0].copy(), 'd2_max': of, 'within': oi[:, :, 1:].copy()}
+
+
+def device_profiles() -> bool:
+    """Does the library have ``ts2d_surface_distance_profile``?  (It serves what :func:`device_serves` serves.)"""
+    from . import _lib
+    try:
+        return hasattr(_lib.load(), 'ts2d_surface_distance_profile')
+    except Exception:
+        return False
+
+
+def _device_profile(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, percentiles, want_sum: bool, device: int,
+                    max_scratch_bytes: int = 0) -> dict:
+    """:func:`distance_profile_statement` on the device; ``dist_sum`` only with ``want_sum``."""
+    from . import engine
+    tol = np.asarray(list(tolerances), np.float64)
+    oi, of, osum, orank, oweight = engine.surface_distance_profile(np.ascontiguousarray(a), kind_a, np.ascontiguousarray(b), kind_b, values, hw,
+                                                                   spacing_hw, tol * tol, list(percentiles), want_sum, max_scratch_bytes, device)
+    out = {'border': oi[:, :, 0].copy(), 'd2_max': of, 'within': oi[:, :, 1:].copy(), 'd2_rank': orank, 'rank_weight': oweight}
+    if want_sum:
+        out['dist_sum'] = osum
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------ evaluate
@@ -291,7 +393,13 @@ def tolerance_key(t) -> str:
     return repr(float(t))
 
 
-def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: Sequence[float] = (2.0,)) -> Dict[str, dict]:
+def percentile_key(q) -> str:
+    """The key of a percentile in ``hausdorff_percentile``: ``repr`` of the float, as :func:`tolerance_key`."""
+    return repr(float(q))
+
+
+def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: Sequence[float] = (2.0,), percentiles: Sequence[float] = (),
+             average_distance: bool = False) -> Dict[str, dict]:
     """name -> scores of ``pred`` against ``ref`` for every named label of ``pred`` (``image.get_annotation_labels(pred)``).
 
     ``pred``, ``ref``: each a multi-component segmentation (label ``v`` is component ``v - 1`` > 0) or a label map (label ``v`` is ``seg == v``),
@@ -303,8 +411,19 @@ def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: 
     ``hausdorff = sqrt(max(d2_max_ab, d2_max_ba))`` in mm.  A ratio with a zero denominator is None; a mask that is empty on one side only gives
     ``hausdorff = inf``; empty on both, None.  For a volume ``surface_dice`` and ``hausdorff`` are absent.
 
+    On request, for 2-D inputs too (absent for a volume, and absent without the request: the default call returns what it always did):
+    ``percentiles`` (at most ``MAX_PERCENTILES``, each finite and in 0 ... 100, else ``ValueError``) adds
+    ``hausdorff_percentile[percentile_key(q)]``, the robust Hausdorff distance as Metrics Reloaded and MONAI define HD95 for ``q = 95``: the
+    larger of the two directed ``q``-th percentiles of the boundary distances (numpy's linear method, :func:`percentile_of_ranks`), taken over the
+    directions that have a border; None where both borders are empty, ``inf`` where exactly one is.  ``average_distance=True`` adds
+    ``asd_pred_to_ref`` and ``asd_ref_to_pred`` (the mean distance of a side's border pixels to the other border: the float64 sum of the
+    distances in the fixed order of ``statistics.tree_sum`` over the border count), ``assd`` (both sums over both counts) and ``masd`` (the mean
+    of the two directed averages; None if either is).  A zero denominator gives None, a border on one side only ``inf``.
+
     Route: ``ts2d_label_overlap`` and ``ts2d_surface_distances`` where ``device`` is given, the library has the symbols and the case is served
-    (:func:`device_serves`), else the statements.  The numbers are the same bit for bit either way."""
+    (:func:`device_serves`), else the statements; with ``percentiles`` or ``average_distance`` the ONE call ``ts2d_surface_distance_profile``
+    (:func:`device_profiles`) in the place of ``ts2d_surface_distances``, else :func:`distance_profile_statement`.  The numbers are the same bit
+    for bit either way."""
     from .image import get_annotation_labels
     names = get_annotation_labels(pred)
     sp_pred, sp_ref = tuple(pred.array.shape[:pred.dimension]), tuple(ref.array.shape[:ref.dimension])
@@ -313,6 +432,8 @@ def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: 
     tolerances = [float(t) for t in tolerances]
     if len(tolerances) > MAX_TOLERANCES or any(not (t >= 0.0 and math.isfinite(t)) for t in tolerances):
         raise ValueError(f"evaluate: at most {MAX_TOLERANCES} tolerances, each finite and not negative, found {tolerances}")
+    percentiles = _percentiles(percentiles, 'evaluate')
+    profile = bool(percentiles) or bool(average_distance)
     out: Dict[str, dict] = {}
     if not names:
         return out
@@ -331,7 +452,11 @@ def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: 
     if flat:
         a2 = a.reshape(((K,) if kind_a == PLANES else ()) + hw)
         b2 = b.reshape(((K,) if kind_b == PLANES else ()) + hw)
-        if on_device:
+        if profile and on_device and device_profiles():
+            sf = _device_profile(a2, kind_a, b2, kind_b, vals, hw, flat[1], tolerances, percentiles, bool(average_distance), int(device))
+        elif profile:
+            sf = distance_profile_statement(a2, kind_a, b2, kind_b, vals, flat[1], tolerances, percentiles)
+        elif on_device:
             sf = _device_surface(a2, kind_a, b2, kind_b, vals, hw, flat[1], tolerances, int(device))
         else:
             sf = surface_statement(a2, kind_a, b2, kind_b, vals, flat[1], tolerances)
@@ -348,6 +473,16 @@ def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: 
                                  for i, t in enumerate(tolerances)}
             top = max(float(sf['d2_max'][k, 0]), float(sf['d2_max'][k, 1]))
             e['hausdorff'] = None if ba + bb == 0 else float(np.sqrt(np.float64(top)))
+            if percentiles:
+                e['hausdorff_percentile'] = {}
+                for p, q in enumerate(percentiles):
+                    directed = [percentile_of_ranks(sf['d2_rank'][k, d, p, 0], sf['d2_rank'][k, d, p, 1], sf['rank_weight'][k, d, p])
+                                for d, n in enumerate((ba, bb)) if n > 0]
+                    e['hausdorff_percentile'][percentile_key(q)] = float(max(directed)) if directed else None
+            if average_distance:
+                s0, s1 = np.float64(sf['dist_sum'][k, 0]), np.float64(sf['dist_sum'][k, 1])
+                e['asd_pred_to_ref'], e['asd_ref_to_pred'], e['assd'] = _ratio(s0, ba), _ratio(s1, bb), _ratio(s0 + s1, ba + bb)
+                e['masd'] = None if ba == 0 or bb == 0 else float((np.float64(e['asd_pred_to_ref']) + np.float64(e['asd_ref_to_pred'])) / np.float64(2))
         out[name] = e
     return out
 

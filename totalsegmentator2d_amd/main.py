@@ -63,7 +63,7 @@ def _references(reference, cases, src_is_dir: bool) -> dict:
 
 def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fetch_remote: bool = True, collapse: bool = False,
              visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1, save_probabilities: bool = False,
-             statistics: bool = False, reference: str = None):
+             statistics: bool = False, reference: str = None, hausdorff_percentiles=(), average_distance: bool = False):
     model = DEFAULT_MODEL if model is None else model
     content = 'all' if visualize else 'file'
     which = 'all' if save_all else 'final'
@@ -86,7 +86,7 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
                     if statistics:
                         res.save_statistics(dest, name, models=which)
                     if references:
-                        res.save_evaluation(dest, name, references[name])
+                        res.save_evaluation(dest, name, references[name], percentiles=hausdorff_percentiles, average_distance=average_distance)
             return
         for i, (name, path) in enumerate(cases):
             log(f"[{i + 1}/{len(cases)}] Processing: {name}")
@@ -96,7 +96,7 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
             if statistics:
                 res.save_statistics(dest, name, models=which)
             if references:
-                res.save_evaluation(dest, name, references[name])
+                res.save_evaluation(dest, name, references[name], percentiles=hausdorff_percentiles, average_distance=average_distance)
 
 
 def ts2d_entry_point(argv=None):
@@ -120,12 +120,19 @@ def ts2d_entry_point(argv=None):
     p.add_argument("--reference", type=str, default=None, help="Score every result against a reference and write <case>.evaluation.json (per label "
                    "Dice, IoU, precision, recall, surface Dice at 2 mm, Hausdorff distance): a 3-D label volume (label v = segment v) or a 2-D "
                    "segmentation; a file for a single input, or a directory that holds a file of the same name for every case.")
+    p.add_argument("--hausdorff-percentile", type=float, action="append", default=None, metavar="Q", help="With --reference: also write per label "
+                   "hausdorff_percentile[Q], the Q-th percentile Hausdorff distance in mm (95: HD95), Q in 0 ... 100; may be given up to 8 times.")
+    p.add_argument("--average-distance", action="store_true", help="With --reference: also write per label the average surface distances in mm: "
+                   "asd_pred_to_ref, asd_ref_to_pred, assd (both borders pooled) and masd (the mean of the two).")
     a = p.parse_args(argv)
     if a.batch_cases < 1:
         p.error("--batch-cases must be at least 1")
+    if (a.hausdorff_percentile or a.average_distance) and a.reference is None:
+        p.error("--hausdorff-percentile and --average-distance score against a reference: give --reference")
     ts2d_run(src=a.src, dest=a.dest, model=a.model, use_remote=not a.no_remote, fetch_remote=not a.no_fetch, collapse=a.collapse,
              visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases, save_probabilities=a.save_probabilities,
-             statistics=a.statistics, reference=a.reference)
+             statistics=a.statistics, reference=a.reference, hausdorff_percentiles=tuple(a.hausdorff_percentile or ()),
+             average_distance=a.average_distance)
 
 
 if __name__ == '__main__':

@@ -355,9 +355,12 @@ class TS2D:
                 written.append(dump_statistics(self.statistics(key), os.path.join(dest, f"{stem}.statistics.json")))
             return written
 
-        def evaluate(self, reference, model: Optional[str] = None, tolerances=(2.0,)) -> Dict[str, dict]:
+        def evaluate(self, reference, model: Optional[str] = None, tolerances=(2.0,), percentiles=(), average_distance: bool = False) -> Dict[str, dict]:
             """Scores of the merged segmentation (``model=None``) or of sub-model ``model``'s against ``reference`` (``evaluate.evaluate``:
             per label the counts, Dice, IoU, precision, recall and, for a 2-D result, surface Dice per tolerance in mm and the Hausdorff distance).
+            On request, for a 2-D result: ``percentiles`` (0 ... 100, at most 8) adds ``hausdorff_percentile[repr(float(q))]``, the percentile
+            Hausdorff distance (HD95 for 95), and ``average_distance=True`` adds ``asd_pred_to_ref``, ``asd_ref_to_pred``, ``assd`` and ``masd``,
+            the average surface distances in mm; without them the result is what it always was.
 
             ``reference`` (an image or a path) is one of two things.  A 3-D label volume: it is reoriented and projected along the coronal axis
             with ``evaluate.project_labels`` (``num`` = the number of labels of that segmentation) - on ``self.device`` where the result has one
@@ -383,11 +386,14 @@ class TS2D:
             if e_seg != e_ref or not np.allclose(seg.spacing, ref.spacing, rtol=1e-5, atol=1e-8):
                 raise ValueError(f"the reference does not lie on the segmentation's grid: extent {e_ref} with spacing {tuple(ref.spacing)} against "
                                  f"extent {e_seg} with spacing {tuple(seg.spacing)}")
-            return ev.evaluate(seg, ref, device=self.device, tolerances=tolerances)
+            return ev.evaluate(seg, ref, device=self.device, tolerances=tolerances, percentiles=percentiles, average_distance=average_distance)
 
-        def save_evaluation(self, dest: str, name: str, reference, models='final', naming: str = 'group', tolerances=(2.0,)) -> List[str]:
+        def save_evaluation(self, dest: str, name: str, reference, models='final', naming: str = 'group', tolerances=(2.0,), percentiles=(),
+                            average_distance: bool = False) -> List[str]:
             """``<name>.evaluation.json`` for the merged segmentation and ``<name>-<group or model>.evaluation.json`` per sub-model, selected by
-            ``models`` and named as in :meth:`save_statistics`: ``json.dump`` of :meth:`evaluate` against ``reference`` with sorted keys."""
+            ``models`` and named as in :meth:`save_statistics`: ``json.dump`` of :meth:`evaluate` against ``reference`` with sorted keys.
+            ``percentiles`` and ``average_distance`` as in :meth:`evaluate`: the keys ``hausdorff_percentile``, ``asd_pred_to_ref``,
+            ``asd_ref_to_pred``, ``assd`` and ``masd`` appear in the files only on request."""
             from .evaluate import dump_evaluation
             assert naming in {'group', 'model'}
             mset = {str(t).strip().lower() for t in _as_list(models)}
@@ -400,7 +406,7 @@ class TS2D:
             written = []
             for key in keys:
                 stem = name if key is None else f"{name}-{(decompose_model_key(key)[1] or key) if naming == 'group' else key}"
-                written.append(dump_evaluation(self.evaluate(ref, key, tolerances), os.path.join(dest, f"{stem}.evaluation.json")))
+                written.append(dump_evaluation(self.evaluate(ref, key, tolerances, percentiles, average_distance), os.path.join(dest, f"{stem}.evaluation.json")))
             return written
 
         def save(self, dest: str, name: str = 'result', ext: str = 'nrrd', models='final', targets='all', content: str = 'all',
