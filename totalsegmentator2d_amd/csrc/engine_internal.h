@@ -1,6 +1,7 @@
 // Host-side internals of libts2d_engine.so, shared by the plain C++ files (program.cpp, pack_weights.cpp, dispatch.cpp, tiled_plan.cpp,
 // prep_plan.cpp) and the seven device units: the program (tensors, ops), the kernel choice of an op, the workspace layout, the engine
 // handle, the plans of the sliding window and of the input side.  Not installed, not part of the ABI (include/ts2d_engine.h is).
+// (What the entries that need no engine share of their call scaffolding is entry_util.h beside it.)
 // No device code here or in the .cpp files: they build without an offload pass.  Kernels live in engine.hip (the network), tiled.hip
 // (the sliding window, fold mean and export), prep.hip (projection, input resample, native 2-D planes), post.hip (largest-component
 // postprocessing), visual.hip (the PNG visuals; its host tables, visual_plan.cpp, have a header of their own), stats.hip (the per-label

@@ -1,18 +1,21 @@
-// Scoring a segmentation against a reference, none of which needs an engine: ts2d_project_labels_coronal, ts2d_label_overlap,
-// ts2d_surface_distances (kernels_evaluate.h) and ts2d_surface_distance_profile (kernels_evaluate_profile.h); the arithmetic of the distances:
-// surface_dist.h; the statements: totalsegmentator2d_amd/evaluate.py.
-// Host pointers in and out; a call uploads each input once, works on the device and downloads once; every device buffer of a call is one DevMem,
-// so HIP_TRY may return wherever it fails.
+// Scoring a segmentation against a reference, none of which needs an engine: ts2d_project_labels_coronal, ts2d_label_overlap and the boundary
+// distances (kernels_evaluate.h; what their profile adds: kernels_evaluate_profile.h).  ts2d_surface_distances and ts2d_surface_distance_profile
+// are ONE implementation, surface_distances_impl: the first is the second without percentiles and without the sum.  The arithmetic of the
+// distances: surface_dist.h; the statements: totalsegmentator2d_amd/evaluate.py.
+// Host pointers in and out; a call uploads each input once, works on the device and downloads once; every device buffer of a call is one DevMem
+// laid out by an ArenaLayout (entry_util.h), so HIP_TRY may return wherever it fails.
 #include "engine_internal.h"
+#include "entry_util.h"
 #include "kernels_evaluate.h"
 #include "kernels_evaluate_profile.h"
 
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 using namespace ts2d;
 
-static_assert(kSdPlanes == TS2D_STATS_PLANES && kSdLabelMap == TS2D_STATS_LABELMAP, "the kinds speak the C header's numbers");
+static_assert(kStPlanes == TS2D_STATS_PLANES && kStLabelMap == TS2D_STATS_LABELMAP, "the kinds speak the C header's numbers");
 static_assert(kPlStatusRange == TS2D_LABELS_RANGE && kSdMaxTolerances == TS2D_EVAL_MAX_TOLERANCES && kSdMaxExtent == TS2D_EVAL_MAX_EXTENT,
               "the status bit and the limits speak the C header's numbers");
 static_assert(kSdMaxPercentiles == TS2D_EVAL_MAX_PERCENTILES, "the limits speak the C header's numbers");
@@ -36,159 +39,20 @@ void project_labels_launch(const T* d_vol, int nz, int ny, int nx, long long sz,
 int check_sides(const char* entry, const void* a, int kind_a, const void* b, int kind_b, const uint8_t* values, int K, size_t n, size_t* seg_a,
                 size_t* seg_b) {
     if (!a || !b) return fail(TS2D_ERR_INVALID, "%s: null segmentation", entry);
-    if ((kind_a != kSdPlanes && kind_a != kSdLabelMap) || (kind_b != kSdPlanes && kind_b != kSdLabelMap))
+    if (!label_kind(kind_a) || !label_kind(kind_b))
         return fail(TS2D_ERR_INVALID, "%s: kinds %d, %d are not planes (0) or label map (1)", entry, kind_a, kind_b);
-    if (K < 1 || K > 255) return fail(TS2D_ERR_INVALID, "%s: K = %d labels outside 1 ... 255", entry, K);
-    if (kind_a == kSdLabelMap || kind_b == kSdLabelMap) {
-        if (!values) return fail(TS2D_ERR_INVALID, "%s: a label map needs the values of its K labels", entry);
-        for (int k = 0; k < K; ++k)
-            if (values[k] == 0) return fail(TS2D_ERR_INVALID, "%s: values[%d] = 0 is the background, not a label", entry, k);
-    }
-    *seg_a = kind_a == kSdPlanes ? (size_t)K * n : n;
-    *seg_b = kind_b == kSdPlanes ? (size_t)K * n : n;
+    TRY(check_label_count(entry, K));
+    if (kind_a == kStLabelMap || kind_b == kStLabelMap) TRY(check_label_values(entry, values, K));
+    *seg_a = kind_a == kStPlanes ? (size_t)K * n : n;
+    *seg_b = kind_b == kStPlanes ? (size_t)K * n : n;
     return TS2D_OK;
 }
 
-}  // namespace
-#pragma GCC visibility pop
-
-extern "C" {
-
-int ts2d_project_labels_coronal(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy,
-                                long long sx, long long base, int num, uint8_t* planes_u8, int32_t* status) {
-    const char* const E = "ts2d_project_labels_coronal";
-    if (!volume || !planes_u8 || !status) return fail(TS2D_ERR_INVALID, "%s: null argument", E);
-    static const int esize[5] = {2, 1, 4, 2, 4};
-    if (dtype < 0 || dtype > 4 || dtype == 2) return fail(TS2D_ERR_INVALID, "%s: dtype %d is not an integer type (int16 0, uint8 1, uint16 3, int32 4)", E, dtype);
-    if (num < 1 || num > 255) return fail(TS2D_ERR_INVALID, "%s: num = %d outside 1 ... 255", E, num);
-    if (nz < 1 || ny < 1 || nx < 1) return fail(TS2D_ERR_INVALID, "%s: extents nz %d, ny %d, nx %d below 1", E, nz, ny, nx);
-    if ((long long)nz * nx * num > 0x7FFFFFFFll) return fail(TS2D_ERR_INVALID, "%s: %d planes of nz %d x nx %d are more than 2^31 - 1 bytes", E, num, nz, nx);
-    {   // every element the view can touch must lie inside the buffer
-        long long lo = base, hi = base;
-        const long long ext[3] = {(long long)(nz - 1) * sz, (long long)(ny - 1) * sy, (long long)(nx - 1) * sx};
-        for (int k = 0; k < 3; ++k) { if (ext[k] < 0) lo += ext[k]; else hi += ext[k]; }
-        if (lo < 0 || hi >= (long long)n_elems) return fail(TS2D_ERR_INVALID, "%s: the strided view (base, sz, sy, sx) leaves the buffer of n_elems %zu", E, n_elems);
-    }
-    *status = 0;
-    HIP_TRY(hipSetDevice(device));
-    const size_t vbytes = n_elems * esize[dtype], obytes = (size_t)nz * nx * num;
-    // [status | volume | planes]
-    const size_t o_vol = 256, o_out = align_up(o_vol + vbytes, 256);
-    DevMem d;
-    HIP_TRY(d.alloc(o_out + obytes));
-    int* d_status = d.as<int>();
-    uint8_t* d_out = d.as<uint8_t>(o_out);
-    HIP_TRY(hipMemset(d_status, 0, sizeof(int)));
-    HIP_TRY(hipMemcpy(d.as<char>(o_vol), volume, vbytes, hipMemcpyHostToDevice));
-    switch (dtype) {
-        case 0: project_labels_launch(d.as<const int16_t>(o_vol), nz, ny, nx, sz, sy, sx, base, num, d_out, d_status); break;
-        case 1: project_labels_launch(d.as<const uint8_t>(o_vol), nz, ny, nx, sz, sy, sx, base, num, d_out, d_status); break;
-        case 3: project_labels_launch(d.as<const uint16_t>(o_vol), nz, ny, nx, sz, sy, sx, base, num, d_out, d_status); break;
-        default: project_labels_launch(d.as<const int32_t>(o_vol), nz, ny, nx, sz, sy, sx, base, num, d_out, d_status); break;
-    }
-    HIP_TRY(hipGetLastError());
-    int st = 0;
-    HIP_TRY(hipMemcpy(&st, d_status, sizeof(st), hipMemcpyDeviceToHost));       // (waits for the launch: the default stream orders them)
-    if (st) { *status = st; return TS2D_OK; }                                     // a sample outside 0 ... num: the planes are no result
-    HIP_TRY(hipMemcpy(planes_u8, d_out, obytes, hipMemcpyDeviceToHost));
-    return TS2D_OK;
-}
-
-int ts2d_label_overlap(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int Z, int H, int W,
-                       int64_t* out_i64) {
-    const char* const E = "ts2d_label_overlap";
-    if (!out_i64) return fail(TS2D_ERR_INVALID, "%s: out_i64 is null", E);
-    if (Z < 1 || H < 1 || W < 1 || (long long)Z * H > 0x7FFFFFFFll || (long long)Z * H * W > 0x7FFFFFFFll)
-        return fail(TS2D_ERR_INVALID, "%s: %d x %d x %d is empty or more than 2^31 - 1 samples", E, Z, H, W);
-    const size_t n = (size_t)Z * H * W;
-    size_t bytes_a = 0, bytes_b = 0;
-    TRY(check_sides(E, a, kind_a, b, kind_b, values, K, n, &bytes_a, &bytes_b));
-    HIP_TRY(hipSetDevice(device));
-    // [counts | values | a | b]
-    const size_t o_val = align_up((size_t)K * 3 * sizeof(unsigned long long), 256), o_a = o_val + 256, o_b = align_up(o_a + bytes_a, 256);
-    DevMem d;
-    HIP_TRY(d.alloc(o_b + bytes_b));
-    HIP_TRY(hipMemset(d.as<char>(), 0, o_a));
-    if (values) HIP_TRY(hipMemcpy(d.as<char>(o_val), values, (size_t)K, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.as<char>(o_a), a, bytes_a, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.as<char>(o_b), b, bytes_b, hipMemcpyHostToDevice));
-    const int vec = n % 16 == 0 ? 1 : 0;
-    const size_t units = vec ? n / 16 : n;
-    size_t blocks = (units + kOvThreads - 1) / kOvThreads;
-    if (blocks > (size_t)kOvMaxBlocks) blocks = kOvMaxBlocks;
-    hipLaunchKernelGGL(overlap_count, dim3((unsigned)blocks, (unsigned)K), dim3(kOvThreads), 0, 0, d.as<const uint8_t>(o_a), kind_a,
-                       d.as<const uint8_t>(o_b), kind_b, d.as<const uint8_t>(o_val), (long long)n, vec, d.as<unsigned long long>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out_i64, d.as<char>(), (size_t)K * 3 * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return TS2D_OK;
-}
-
-int ts2d_surface_distances(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int H, int W,
-                           double spacing_h, double spacing_w, const double* tol_sq, int T, size_t max_scratch_bytes, int64_t* out_i64,
-                           double* out_f64) {
-    const char* const E = "ts2d_surface_distances";
-    if (!out_i64 || !out_f64) return fail(TS2D_ERR_INVALID, "%s: null output", E);
-    if (H < 1 || W < 1 || H > kSdMaxExtent || W > kSdMaxExtent) return fail(TS2D_ERR_INVALID, "%s: %d x %d outside 1 ... %d per axis", E, H, W, kSdMaxExtent);
-    if (T < 0 || T > kSdMaxTolerances || (T > 0 && !tol_sq)) return fail(TS2D_ERR_INVALID, "%s: T = %d tolerances outside 0 ... %d, or without tol_sq", E, T, kSdMaxTolerances);
-    if (!(spacing_h > 0.0 && spacing_h < 1e300 && spacing_w > 0.0 && spacing_w < 1e300))
-        return fail(TS2D_ERR_INVALID, "%s: spacing %g x %g is not finite and positive", E, spacing_h, spacing_w);
-    SdTolerances tol = {};
-    for (int t = 0; t < T; ++t) {
-        if (!(tol_sq[t] >= 0.0)) return fail(TS2D_ERR_INVALID, "%s: tol_sq[%d] = %g is negative or not a number", E, t, tol_sq[t]);
-        tol.sq[t] = tol_sq[t];
-    }
-    const size_t n = (size_t)H * W;
-    size_t bytes_a = 0, bytes_b = 0;
-    TRY(check_sides(E, a, kind_a, b, kind_b, values, K, n, &bytes_a, &bytes_b));
-    // a label's scratch: the border bytes and the uint16 row distances of both sides
-    const size_t per_label = n * 2 * (1 + sizeof(uint16_t));
-    const size_t budget = max_scratch_bytes ? max_scratch_bytes : ((size_t)256 << 20);
-    size_t L = budget / per_label;
-    if (L < 1)
-        return fail(TS2D_ERR_INVALID, "%s: the scratch of ONE label (%d x %d) takes %zu bytes, above max_scratch_bytes = %zu", E, H, W, per_label, budget);
-    if (L > (size_t)K) L = (size_t)K;
-    HIP_TRY(hipSetDevice(device));
-    // [counts | keys | values | a | b | border of a chunk | g of a chunk]
-    const size_t n_cnt = (size_t)K * 2 * (1 + T);
-    const size_t o_key = align_up(n_cnt * sizeof(unsigned long long), 256), o_val = align_up(o_key + (size_t)K * 2 * sizeof(unsigned long long), 256);
-    const size_t o_a = o_val + 256, o_b = align_up(o_a + bytes_a, 256), o_border = align_up(o_b + bytes_b, 256);
-    const size_t o_g = align_up(o_border + L * 2 * n, 256), total = o_g + L * 2 * n * sizeof(uint16_t);
-    DevMem d;
-    HIP_TRY(d.alloc(total));
-    HIP_TRY(hipMemset(d.as<char>(), 0, o_a));
-    if (values) HIP_TRY(hipMemcpy(d.as<char>(o_val), values, (size_t)K, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.as<char>(o_a), a, bytes_a, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.as<char>(o_b), b, bytes_b, hipMemcpyHostToDevice));
-    unsigned long long* const d_cnt = d.as<unsigned long long>();
-    unsigned long long* const d_key = d.as<unsigned long long>(o_key);
-    for (int k0 = 0; k0 < K; k0 += (int)L) {
-        const unsigned labels = (unsigned)(K - k0 < (int)L ? K - k0 : (int)L);
-        hipLaunchKernelGGL(sd_columns, dim3((unsigned)((W + 63) / 64), 2, labels), dim3(64), 0, 0, d.as<const uint8_t>(o_a), kind_a,
-                           d.as<const uint8_t>(o_b), kind_b, d.as<const uint8_t>(o_val), k0, H, W, d.as<uint8_t>(o_border), d.as<uint16_t>(o_g));
-        hipLaunchKernelGGL(sd_rows, dim3((unsigned)H, 2, labels), dim3(64), 0, 0, d.as<const uint8_t>(o_border), d.as<const uint16_t>(o_g), k0, H, W,
-                           spacing_h, spacing_w, tol, T, d_cnt, d_key);
-        HIP_TRY(hipGetLastError());
-    }
-    // one download: the counts and the keys lie next to each other (the gap of the alignment goes along)
-    std::vector<char> host(o_val);
-    HIP_TRY(hipMemcpy(host.data(), d.as<char>(), host.size(), hipMemcpyDeviceToHost));
-    memcpy(out_i64, host.data(), n_cnt * sizeof(int64_t));
-    for (int i = 0; i < K * 2; ++i) {
-        long long border;
-        uint64_t key;
-        memcpy(&border, host.data() + (size_t)i * (1 + T) * sizeof(int64_t), sizeof(border));
-        memcpy(&key, host.data() + o_key + (size_t)i * sizeof(uint64_t), sizeof(key));
-        if (border == 0) key = 0xFFF0000000000000ull;                              // an empty border: -inf
-        memcpy(out_f64 + i, &key, sizeof(key));
-    }
-    return TS2D_OK;
-}
-
-int ts2d_surface_distance_profile(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int H,
-                                  int W, double spacing_h, double spacing_w, const double* tol_sq, int T, const double* percentiles, int P,
-                                  int want_sum, size_t max_scratch_bytes, int64_t* out_i64, double* out_f64, double* out_sum_f64,
-                                  double* out_rank_f64, double* out_weight_f64) {
-    const char* const E = "ts2d_surface_distance_profile";
+// ts2d_surface_distances (E names it; P = 0, want_sum = 0, the three outputs of the profile null) and ts2d_surface_distance_profile.
+int surface_distances_impl(const char* E, int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int H,
+                           int W, double spacing_h, double spacing_w, const double* tol_sq, int T, const double* percentiles, int P, int want_sum,
+                           size_t max_scratch_bytes, int64_t* out_i64, double* out_f64, double* out_sum_f64, double* out_rank_f64,
+                           double* out_weight_f64) {
     if (!out_i64 || !out_f64) return fail(TS2D_ERR_INVALID, "%s: null output", E);
     if (H < 1 || W < 1 || H > kSdMaxExtent || W > kSdMaxExtent) return fail(TS2D_ERR_INVALID, "%s: %d x %d outside 1 ... %d per axis", E, H, W, kSdMaxExtent);
     if (T < 0 || T > kSdMaxTolerances || (T > 0 && !tol_sq)) return fail(TS2D_ERR_INVALID, "%s: T = %d tolerances outside 0 ... %d, or without tol_sq", E, T, kSdMaxTolerances);
@@ -216,42 +80,44 @@ int ts2d_surface_distance_profile(int device, const uint8_t* a, int kind_a, cons
     const int R = 2 * P;
     const size_t bins_label = (size_t)2 * R * kSdDigits * sizeof(uint32_t);
     const size_t per_label = n * 2 * (1 + sizeof(uint16_t)) + (P ? n * 2 * sizeof(uint64_t) + bins_label : 0) + (want_sum ? (size_t)H * 2 * sizeof(double) : 0);
-    const size_t budget = max_scratch_bytes ? max_scratch_bytes : ((size_t)256 << 20);
-    size_t L = budget / per_label;
+    size_t budget = 0;
+    const size_t L = labels_per_chunk(max_scratch_bytes, per_label, K, &budget);
     if (L < 1)
         return fail(TS2D_ERR_INVALID, "%s: the scratch of ONE label (%d x %d) takes %zu bytes, above max_scratch_bytes = %zu", E, H, W, per_label, budget);
-    if (L > (size_t)K) L = (size_t)K;
     HIP_TRY(hipSetDevice(device));
-    // [counts | keys | sums | prefixes | weights || ranks | bins of a chunk | values | a | b | border of a chunk | g | key buffer | row partials]
-    const size_t n_cnt = (size_t)K * 2 * (1 + T), n_sel = (size_t)K * 2 * R;
-    const size_t o_key = align_up(n_cnt * sizeof(unsigned long long), 256), o_sum = align_up(o_key + (size_t)K * 2 * sizeof(unsigned long long), 256);
-    const size_t o_pre = align_up(o_sum + (size_t)K * 2 * sizeof(double), 256), o_wgt = align_up(o_pre + n_sel * sizeof(uint64_t), 256);
-    const size_t o_rank = align_up(o_wgt + (size_t)K * 2 * P * sizeof(double), 256), o_bins = align_up(o_rank + n_sel * sizeof(long long), 256);
-    const size_t o_val = align_up(o_bins + (P ? L * bins_label : 0), 256);
-    const size_t o_a = o_val + 256, o_b = align_up(o_a + bytes_a, 256), o_border = align_up(o_b + bytes_b, 256);
-    const size_t o_g = align_up(o_border + L * 2 * n, 256), o_kbuf = align_up(o_g + L * 2 * n * sizeof(uint16_t), 256);
-    const size_t o_rows = align_up(o_kbuf + (P ? L * 2 * n * sizeof(uint64_t) : 0), 256), total = o_rows + (want_sum ? L * 2 * (size_t)H * sizeof(double) : 0);
+    // [counts | keys | sums | prefixes | weights || ranks | bins of a chunk | values || a | b | border of a chunk | g | key buffer | row partials]:
+    // what is downloaded, then what more starts as zero, then the rest
+    const size_t n_cnt = (size_t)K * 2 * (1 + T), n_sel = (size_t)K * 2 * R, pairs = (size_t)K * 2;
+    ArenaLayout lay;
+    const size_t o_cnt = lay.add(n_cnt * sizeof(unsigned long long)), o_key = lay.add(pairs * sizeof(unsigned long long));
+    const size_t o_sum = lay.add(want_sum ? pairs * sizeof(double) : 0), o_pre = lay.add(n_sel * sizeof(uint64_t));
+    const size_t o_wgt = lay.add(pairs * P * sizeof(double)), down_bytes = lay.total();
+    const size_t o_rank = lay.add(n_sel * sizeof(long long)), o_bins = lay.add(P ? L * bins_label : 0), o_val = lay.add((size_t)K);
+    const size_t zero_bytes = lay.total();
+    const size_t o_a = lay.add(bytes_a), o_b = lay.add(bytes_b), o_border = lay.add(L * 2 * n), o_g = lay.add(L * 2 * n * sizeof(uint16_t));
+    const size_t o_kbuf = lay.add(P ? L * 2 * n * sizeof(uint64_t) : 0), o_rows = lay.add(want_sum ? L * 2 * (size_t)H * sizeof(double) : 0);
     DevMem d;
-    HIP_TRY(d.alloc(total));
-    HIP_TRY(hipMemset(d.as<char>(), 0, o_a));
+    HIP_TRY(d.alloc(lay.total()));
+    HIP_TRY(hipMemset(d.as<char>(), 0, zero_bytes));
     if (values) HIP_TRY(hipMemcpy(d.as<char>(o_val), values, (size_t)K, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_a), a, bytes_a, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_b), b, bytes_b, hipMemcpyHostToDevice));
-    unsigned long long* const d_cnt = d.as<unsigned long long>();
+    unsigned long long* const d_cnt = d.as<unsigned long long>(o_cnt);
     unsigned long long* const d_key = d.as<unsigned long long>(o_key);
     long long* const d_rank = d.as<long long>(o_rank);
     uint64_t* const d_pre = d.as<uint64_t>(o_pre);
     uint32_t* const d_bins = d.as<uint32_t>(o_bins);
     uint64_t* const d_kbuf = P ? d.as<uint64_t>(o_kbuf) : nullptr;
     double* const d_rows = want_sum ? d.as<double>(o_rows) : nullptr;
+    const bool profile = P > 0 || want_sum;
     size_t hist_blocks = (n + 1023) / 1024;                                          // 16 keys per lane, up to the cap
     if (hist_blocks > (size_t)kSpHistMaxBlocks) hist_blocks = kSpHistMaxBlocks;
     for (int k0 = 0; k0 < K; k0 += (int)L) {
         const unsigned labels = (unsigned)(K - k0 < (int)L ? K - k0 : (int)L);
         hipLaunchKernelGGL(sd_columns, dim3((unsigned)((W + 63) / 64), 2, labels), dim3(64), 0, 0, d.as<const uint8_t>(o_a), kind_a,
                            d.as<const uint8_t>(o_b), kind_b, d.as<const uint8_t>(o_val), k0, H, W, d.as<uint8_t>(o_border), d.as<uint16_t>(o_g));
-        hipLaunchKernelGGL(sd_rows_profile, dim3((unsigned)H, 2, labels), dim3(64), 0, 0, d.as<const uint8_t>(o_border), d.as<const uint16_t>(o_g), k0,
-                           H, W, spacing_h, spacing_w, tol, T, d_cnt, d_key, d_kbuf, d_rows);
+        hipLaunchKernelGGL(profile ? sd_rows<true> : sd_rows<false>, dim3((unsigned)H, 2, labels), dim3(64), 0, 0, d.as<const uint8_t>(o_border),
+                           d.as<const uint16_t>(o_g), k0, H, W, spacing_h, spacing_w, tol, T, d_cnt, d_key, d_kbuf, d_rows);
         if (want_sum) hipLaunchKernelGGL(sd_profile_combine, dim3(2, labels), dim3(64), 0, 0, d_rows, k0, H, d.as<double>(o_sum));
         if (P) {
             hipLaunchKernelGGL(sd_select_init, dim3(labels), dim3(64), 0, 0, d_cnt, k0, T, pc, P, d_rank, d_pre, d.as<double>(o_wgt));
@@ -264,26 +130,109 @@ int ts2d_surface_distance_profile(int device, const uint8_t* a, int kind_a, cons
         HIP_TRY(hipGetLastError());
     }
     // one download: counts, keys, sums, prefixes and weights lie next to each other (the gaps of the alignment go along)
-    std::vector<char> host(o_rank);
+    std::vector<char> host(down_bytes);
     HIP_TRY(hipMemcpy(host.data(), d.as<char>(), host.size(), hipMemcpyDeviceToHost));
-    memcpy(out_i64, host.data(), n_cnt * sizeof(int64_t));
+    memcpy(out_i64, host.data() + o_cnt, n_cnt * sizeof(int64_t));
     const uint64_t minus_inf = 0xFFF0000000000000ull;
-    for (int i = 0; i < K * 2; ++i) {
+    for (size_t i = 0; i < pairs; ++i) {
         long long border;
         uint64_t key;
-        memcpy(&border, host.data() + (size_t)i * (1 + T) * sizeof(int64_t), sizeof(border));
-        memcpy(&key, host.data() + o_key + (size_t)i * sizeof(uint64_t), sizeof(key));
+        memcpy(&border, host.data() + o_cnt + i * (1 + T) * sizeof(int64_t), sizeof(border));
+        memcpy(&key, host.data() + o_key + i * sizeof(uint64_t), sizeof(key));
         if (border == 0) key = minus_inf;                                          // an empty border: -inf
         memcpy(out_f64 + i, &key, sizeof(key));
         for (int r = 0; r < R; ++r) {
-            memcpy(&key, host.data() + o_pre + ((size_t)i * R + r) * sizeof(uint64_t), sizeof(key));
+            memcpy(&key, host.data() + o_pre + (i * R + r) * sizeof(uint64_t), sizeof(key));
             if (border == 0) key = minus_inf;
-            memcpy(out_rank_f64 + (size_t)i * R + r, &key, sizeof(key));
+            memcpy(out_rank_f64 + i * R + r, &key, sizeof(key));
         }
     }
-    if (want_sum) memcpy(out_sum_f64, host.data() + o_sum, (size_t)K * 2 * sizeof(double));
-    if (P) memcpy(out_weight_f64, host.data() + o_wgt, (size_t)K * 2 * P * sizeof(double));
+    if (want_sum) memcpy(out_sum_f64, host.data() + o_sum, pairs * sizeof(double));
+    if (P) memcpy(out_weight_f64, host.data() + o_wgt, pairs * P * sizeof(double));
     return TS2D_OK;
+}
+
+}  // namespace
+#pragma GCC visibility pop
+
+extern "C" {
+
+int ts2d_project_labels_coronal(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy,
+                                long long sx, long long base, int num, uint8_t* planes_u8, int32_t* status) {
+    const char* const E = "ts2d_project_labels_coronal";
+    if (!volume || !planes_u8 || !status) return fail(TS2D_ERR_INVALID, "%s: null argument", E);
+    if (dtype < 0 || dtype > 4 || dtype == 2) return fail(TS2D_ERR_INVALID, "%s: dtype %d is not an integer type (int16 0, uint8 1, uint16 3, int32 4)", E, dtype);
+    if (num < 1 || num > 255) return fail(TS2D_ERR_INVALID, "%s: num = %d outside 1 ... 255", E, num);
+    if (nz < 1 || ny < 1 || nx < 1) return fail(TS2D_ERR_INVALID, "%s: extents nz %d, ny %d, nx %d below 1", E, nz, ny, nx);
+    if ((long long)nz * nx * num > 0x7FFFFFFFll) return fail(TS2D_ERR_INVALID, "%s: %d planes of nz %d x nx %d are more than 2^31 - 1 bytes", E, num, nz, nx);
+    TRY(check_strided_view(E, n_elems, base, {nz, ny, nx}, {sz, sy, sx}));
+    *status = 0;
+    HIP_TRY(hipSetDevice(device));
+    const size_t vbytes = n_elems * sample_size(dtype), obytes = (size_t)nz * nx * num;
+    ArenaLayout lay;
+    const size_t o_status = lay.add(sizeof(int)), o_vol = lay.add(vbytes), o_out = lay.add(obytes);
+    DevMem d;
+    HIP_TRY(d.alloc(lay.total()));
+    int* d_status = d.as<int>(o_status);
+    uint8_t* d_out = d.as<uint8_t>(o_out);
+    HIP_TRY(hipMemset(d_status, 0, sizeof(int)));
+    HIP_TRY(hipMemcpy(d.as<char>(o_vol), volume, vbytes, hipMemcpyHostToDevice));
+    by_sample_type(dtype, [&](auto t) {
+        using S = typename decltype(t)::type;
+        if constexpr (std::is_integral<S>::value)                  // (float32 was refused above: no kernel of it is built)
+            project_labels_launch(d.as<const S>(o_vol), nz, ny, nx, sz, sy, sx, base, num, d_out, d_status);
+    });
+    HIP_TRY(hipGetLastError());
+    int st = 0;
+    HIP_TRY(hipMemcpy(&st, d_status, sizeof(st), hipMemcpyDeviceToHost));       // (waits for the launch: the default stream orders them)
+    if (st) { *status = st; return TS2D_OK; }                                     // a sample outside 0 ... num: the planes are no result
+    HIP_TRY(hipMemcpy(planes_u8, d_out, obytes, hipMemcpyDeviceToHost));
+    return TS2D_OK;
+}
+
+int ts2d_label_overlap(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int Z, int H, int W,
+                       int64_t* out_i64) {
+    const char* const E = "ts2d_label_overlap";
+    if (!out_i64) return fail(TS2D_ERR_INVALID, "%s: out_i64 is null", E);
+    if (!volume_fits_int32(Z, H, W)) return fail(TS2D_ERR_INVALID, "%s: %d x %d x %d is empty or more than 2^31 - 1 samples", E, Z, H, W);
+    const size_t n = (size_t)Z * H * W;
+    size_t bytes_a = 0, bytes_b = 0;
+    TRY(check_sides(E, a, kind_a, b, kind_b, values, K, n, &bytes_a, &bytes_b));
+    HIP_TRY(hipSetDevice(device));
+    ArenaLayout lay;
+    const size_t o_cnt = lay.add((size_t)K * 3 * sizeof(unsigned long long)), o_val = lay.add((size_t)K);
+    const size_t o_a = lay.add(bytes_a), o_b = lay.add(bytes_b);
+    DevMem d;
+    HIP_TRY(d.alloc(lay.total()));
+    HIP_TRY(hipMemset(d.as<char>(), 0, o_a));                      // the counts and the values
+    if (values) HIP_TRY(hipMemcpy(d.as<char>(o_val), values, (size_t)K, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_a), a, bytes_a, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_b), b, bytes_b, hipMemcpyHostToDevice));
+    const int vec = n % 16 == 0 ? 1 : 0;
+    const size_t units = vec ? n / 16 : n;
+    size_t blocks = (units + kOvThreads - 1) / kOvThreads;
+    if (blocks > (size_t)kOvMaxBlocks) blocks = kOvMaxBlocks;
+    hipLaunchKernelGGL(overlap_count, dim3((unsigned)blocks, (unsigned)K), dim3(kOvThreads), 0, 0, d.as<const uint8_t>(o_a), kind_a,
+                       d.as<const uint8_t>(o_b), kind_b, d.as<const uint8_t>(o_val), (long long)n, vec, d.as<unsigned long long>(o_cnt));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out_i64, d.as<char>(o_cnt), (size_t)K * 3 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return TS2D_OK;
+}
+
+
+int ts2d_surface_distances(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int H, int W,
+                           double spacing_h, double spacing_w, const double* tol_sq, int T, size_t max_scratch_bytes, int64_t* out_i64,
+                           double* out_f64) {
+    return surface_distances_impl("ts2d_surface_distances", device, a, kind_a, b, kind_b, values, K, H, W, spacing_h, spacing_w, tol_sq, T, nullptr, 0, 0,
+                                  max_scratch_bytes, out_i64, out_f64, nullptr, nullptr, nullptr);
+}
+
+int ts2d_surface_distance_profile(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int H,
+                                  int W, double spacing_h, double spacing_w, const double* tol_sq, int T, const double* percentiles, int P,
+                                  int want_sum, size_t max_scratch_bytes, int64_t* out_i64, double* out_f64, double* out_sum_f64,
+                                  double* out_rank_f64, double* out_weight_f64) {
+    return surface_distances_impl("ts2d_surface_distance_profile", device, a, kind_a, b, kind_b, values, K, H, W, spacing_h, spacing_w, tol_sq, T,
+                                  percentiles, P, want_sum, max_scratch_bytes, out_i64, out_f64, out_sum_f64, out_rank_f64, out_weight_f64);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
-// Scoring a segmentation against a reference, behind ts2d_project_labels_coronal, ts2d_label_overlap and ts2d_surface_distances.  The statements
-// are totalsegmentator2d_amd.evaluate.project_labels, overlap_statement and surface_statement; tests/test_gpu_evaluate.py holds these kernels
-// against them byte for byte and bit for bit, the float64 bits of the largest squared distance included.
+// Scoring a segmentation against a reference, behind ts2d_project_labels_coronal, ts2d_label_overlap and the two passes of the boundary
+// distances of ts2d_surface_distances and ts2d_surface_distance_profile (what the profile adds behind them: kernels_evaluate_profile.h).  The
+// statements are totalsegmentator2d_amd.evaluate.project_labels, overlap_statement, surface_statement and distance_profile_statement;
+// tests/test_gpu_evaluate.py and tests/test_gpu_evaluate_profile.py hold these kernels against them byte for byte and bit for bit, the float64
+// bits of the largest squared distance included.
 //
 //   project_labels_stream  the reference's project(..., 'multiclass:<num>') along the coronal axis (ts2d/core/util/image.py:164-194) in ONE pass
 //                          over the volume whatever num is.  The volume is addressed as project_modes_stream (kernels_project_modes.h) addresses
@@ -19,12 +21,23 @@
 //                          ballot), and for each of them its lanes stride the columns x' of the other side's g, take the minimum of
 //                          sd_candidate in registers and meet across the wave.  Lane 0 counts the border pixels, those within each tolerance, and
 //                          keeps the largest d2 as its key; per wave one integer add per counter and one integer max.
+//                          ONE body in two compile-time forms.  sd_rows<false> (ts2d_surface_distances) is that and no more.  sd_rows<true>
+//                          (ts2d_surface_distance_profile) keeps every border pixel's d2: the minimum of border pixel px goes to every lane,
+//                          and lane px - x0 keeps it.  After the 64 columns of a chunk every lane stores its key to the key buffer (kSdNoKey
+//                          where it has no border pixel: one coalesced store per chunk) and adds sd_sqrt of its d2 to its own float64 sum -
+//                          one root per lane and chunk, all lanes at once.  The chunks come in increasing x0, so lane l adds the terms at
+//                          x = l, l + 64, ... in increasing x from +0.0: level 1 of the tree of stats_tree.h.  At the end of the row the lanes
+//                          are halved (st_wave_halve, kernels_stats.h) and lane 0 stores the row's partial.  Compile-time, not a null check
+//                          at run time: the plain form then carries no broadcast, no per-lane key and no sum, and keeps its 35 registers
+//                          (the profile form needs 46) without anyone having to measure that a branch on null costs nothing.
 // Integer atomics only (sums and a maximum of non-negative keys: the result does not depend on their order), no flags, nothing waits for another
-// wave; every loop bound is a kernel argument, 64 or a constant.  Indices into a plane are int32 or long long as the entry's limits need.
+// wave (a workgroup of sd_columns and sd_rows is ONE wave); contraction off; every loop bound is a kernel argument, the grid's extent, 64 or a
+// constant.  Indices into a plane are int32 or long long as the entry's limits need.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels_stats.h"
 #include "surface_dist.h"
 
 namespace ts2d {
@@ -86,9 +99,9 @@ __global__ __launch_bounds__(kPlThreads) void project_labels_stream(const T* __r
 
 // the high bit of every byte of x that belongs to the label: planes - the byte is not 0; label map - the byte equals the value (v4: it in all four bytes)
 __device__ __forceinline__ uint32_t ov_bytes(uint32_t x, int kind, uint32_t v4) {
-    const uint32_t y = kind == kSdLabelMap ? x ^ v4 : x;
+    const uint32_t y = kind == kStLabelMap ? x ^ v4 : x;
     const uint32_t nonzero = (((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y) & 0x80808080u;
-    return kind == kSdLabelMap ? nonzero ^ 0x80808080u : nonzero;
+    return kind == kStLabelMap ? nonzero ^ 0x80808080u : nonzero;
 }
 
 // grid = (blocks, K), block = kOvThreads.  a, b: planes [K][n] or one label map [n]; values [K]; out: [K][3] = n_a, n_b, n_both, zero before the launch.
@@ -96,8 +109,8 @@ __global__ __launch_bounds__(kOvThreads) void overlap_count(const uint8_t* __res
                                                             const uint8_t* __restrict__ values, long long n, int vec,
                                                             unsigned long long* __restrict__ out) {
     const int k = (int)blockIdx.y;
-    const uint8_t* pa = a + (kind_a == kSdPlanes ? (long long)k * n : 0ll);
-    const uint8_t* pb = b + (kind_b == kSdPlanes ? (long long)k * n : 0ll);
+    const uint8_t* pa = a + (kind_a == kStPlanes ? (long long)k * n : 0ll);
+    const uint8_t* pb = b + (kind_b == kStPlanes ? (long long)k * n : 0ll);
     const uint8_t value = values[k];
     const long long first = (long long)blockIdx.x * kOvThreads + threadIdx.x, step = (long long)gridDim.x * kOvThreads;
     int ca = 0, cb = 0, cab = 0;
@@ -117,7 +130,7 @@ __global__ __launch_bounds__(kOvThreads) void overlap_count(const uint8_t* __res
         }
     } else {
         for (long long i = first; i < n; i += step) {
-            const bool ma = sd_masked(pa[i], kind_a, value), mb = sd_masked(pb[i], kind_b, value);
+            const bool ma = st_masked(pa[i], kind_a, value), mb = st_masked(pb[i], kind_b, value);
             ca += ma ? 1 : 0; cb += mb ? 1 : 0; cab += (ma && mb) ? 1 : 0;
         }
     }
@@ -142,7 +155,7 @@ __global__ __launch_bounds__(64) void sd_columns(const uint8_t* __restrict__ a, 
     const int side = (int)blockIdx.y, l = (int)blockIdx.z, k = k0 + l;
     const long long HW = (long long)H * W;
     const int kind = side == 0 ? kind_a : kind_b;
-    const uint8_t* m = (side == 0 ? a : b) + (kind == kSdPlanes ? (long long)k * HW : 0ll);
+    const uint8_t* m = (side == 0 ? a : b) + (kind == kStPlanes ? (long long)k * HW : 0ll);
     const uint8_t value = values[k];
     uint8_t* bo = border + ((long long)l * 2 + side) * HW;
     uint16_t* go = g + ((long long)l * 2 + side) * HW;
@@ -165,10 +178,13 @@ __global__ __launch_bounds__(64) void sd_columns(const uint8_t* __restrict__ a, 
 struct SdTolerances { double sq[kSdMaxTolerances]; };
 
 // grid = (H, 2, L), block = 64.  Direction 0: the border pixels of A against g of B; direction 1: the other way.  counts: [K][2][1 + T] (border
-// pixels, then those within each tolerance), keys: [K][2] (the largest d2 as sd_key), both zero before the first launch.
+// pixels, then those within each tolerance), keys: [K][2] (the largest d2 as sd_key), both zero before the first launch.  PROFILE: also key_buf
+// uint64 [L][2][H * W] (null: no keys are kept) and row_sum float64 [L][2][H] (null: no sum); the plain form reads neither argument.
+template <bool PROFILE>
 __global__ __launch_bounds__(64) void sd_rows(const uint8_t* __restrict__ border, const uint16_t* __restrict__ g, int k0, int H, int W, double sy,
                                               double sx, SdTolerances tol, int T, unsigned long long* __restrict__ counts,
-                                              unsigned long long* __restrict__ keys) {
+                                              unsigned long long* __restrict__ keys, uint64_t* __restrict__ key_buf, double* __restrict__ row_sum) {
+#pragma clang fp contract(off)
     const int y = (int)blockIdx.x, dir = (int)blockIdx.y, l = (int)blockIdx.z, k = k0 + l, lane = (int)threadIdx.x;
     const long long HW = (long long)H * W;
     const uint8_t* bo = border + ((long long)l * 2 + dir) * HW + (long long)y * W;
@@ -178,11 +194,13 @@ __global__ __launch_bounds__(64) void sd_rows(const uint8_t* __restrict__ border
 #pragma unroll
     for (int t = 0; t < kSdMaxTolerances; ++t) within[t] = 0;
     uint64_t key_max = 0;
+    double acc = 0.0;                                              // (PROFILE)
     for (int x0 = 0; x0 < W; x0 += 64) {
         const int x = x0 + lane;
         unsigned long long todo = __ballot(x < W && bo[x] != 0);
+        uint64_t mine = kSdNoKey;                                  // (PROFILE)
         while (todo) {                                             // at most 64 rounds; the mask is the same in every lane
-            const int px = x0 + (__ffsll((long long)todo) - 1);
+            const int src = __ffsll((long long)todo) - 1, px = x0 + src;
             todo &= todo - 1;
             double best = sd_inf();
             for (int xo = lane; xo < W; xo += 64) {
@@ -190,11 +208,23 @@ __global__ __launch_bounds__(64) void sd_rows(const uint8_t* __restrict__ border
                 best = c < best ? c : best;
             }
             for (int off = 32; off >= 1; off >>= 1) { const double o = __shfl_down(best, off, 64); best = o < best ? o : best; }
-            ++cnt;                                                 // (lane 0 holds the minimum; the other lanes' tallies are not used)
+            if constexpr (PROFILE) best = __shfl(best, 0, 64);     // lane 0 holds the minimum: now every lane does
+            ++cnt;                                                 // (plain: the other lanes' tallies are not used)
             const uint64_t key = sd_key(best);
             key_max = key > key_max ? key : key_max;
 #pragma unroll
             for (int t = 0; t < kSdMaxTolerances; ++t) within[t] += (t < T && best <= tol.sq[t]) ? 1 : 0;
+            if constexpr (PROFILE) mine = lane == src ? key : mine;
+        }
+        if constexpr (PROFILE) {
+            if (key_buf && x < W) key_buf[((long long)l * 2 + dir) * HW + (long long)y * W + x] = mine;
+            if (row_sum) acc = acc + (mine != kSdNoKey ? sd_sqrt(sd_unkey(mine)) : 0.0);      // (+0.0 for no border pixel: the sum stays as it is)
+        }
+    }
+    if constexpr (PROFILE) {
+        if (row_sum) {
+            acc = st_wave_halve(acc);
+            if (lane == 0) row_sum[((long long)l * 2 + dir) * H + y] = acc;
         }
     }
     if (lane == 0 && cnt) {

@@ -1,16 +1,11 @@
-// The distance profile behind ts2d_surface_distance_profile: what ts2d_surface_distances computes, and with it per (label, direction) the sum
-// of the boundary distances in the fixed tree and their exact order statistics at requested percentiles.  The statement is
+// What the distance profile of ts2d_surface_distance_profile adds behind the two passes of the boundary distances: per (label, direction) the sum
+// of the distances in the fixed tree and their exact order statistics at requested percentiles.  The statement is
 // totalsegmentator2d_amd.evaluate.distance_profile_statement; tests/test_gpu_evaluate_profile.py holds these kernels against it bit for bit.
-// The arithmetic - root, ranks, digits, decision - is surface_dist.h; pass 1 is sd_columns of kernels_evaluate.h as it is.
+// The arithmetic - root, ranks, digits, decision - is surface_dist.h.  The passes themselves, sd_columns and sd_rows<true> - which leaves the key
+// buffer and the row partials these kernels read - are kernels_evaluate.h: there is ONE walk over the border pixels.
 //
-//   sd_rows_profile     pass 2, one wave per (label, direction, row), the ballot walk of sd_rows with the same tallies.  The minimum d2 of border
-//                       pixel px goes to every lane, and lane px - x0 keeps it.  After the 64 columns of a chunk every lane stores its key to the
-//                       key buffer (kSdNoKey where it has no border pixel: one coalesced store per chunk) and adds sd_sqrt of its d2 to its own
-//                       float64 sum - one root per lane and chunk, all lanes at once.  The chunks come in increasing x0, so lane l adds the
-//                       terms at x = l, l + 64, ... in increasing x from +0.0: level 1 of the tree of stats_tree.h.  At the end of the row the
-//                       lanes are halved (sd_wave_halve = st_wave_halve) and lane 0 stores the row's partial.
 //   sd_profile_combine  one wave per (label, direction): level 2 over the H row partials (st_lane_rows, then the halving).
-//   sd_select_init      per (label, direction, percentile) the two sorted positions and the weight from the border count that sd_rows_profile has
+//   sd_select_init      per (label, direction, percentile) the two sorted positions and the weight from the border count that sd_rows has
 //                       just left behind (sd_percentile_ranks); an empty border gets position -1: nothing is selected.
 //   sd_select_hist      one round of the selection: a wave per slice of a (label, direction)'s key buffer counts, per selection, the digit of the
 //                       keys that agree with the selection's prefix - into an LDS histogram with integer atomics, then its non-zero bins into the
@@ -40,72 +35,10 @@ constexpr int kSpHistMaxBlocks = 256;
 
 struct SdPercentiles { double q[kSdMaxPercentiles]; };
 
-// st_wave_halve of kernels_stats.h: v[l] + v[l + 32], then 16 ... 1
-__device__ __forceinline__ double sd_wave_halve(double v) {
-#pragma clang fp contract(off)
-    for (int off = kStLanes / 2; off >= 1; off >>= 1) v = v + __shfl_down(v, off, kStLanes);
-    return v;
-}
-
-// grid = (H, 2, L), block = 64.  As sd_rows, and: key_buf uint64 [L][2][H * W] (null: no keys are kept), row_sum float64 [L][2][H] (null: no sum).
-__global__ __launch_bounds__(64) void sd_rows_profile(const uint8_t* __restrict__ border, const uint16_t* __restrict__ g, int k0, int H, int W,
-                                                      double sy, double sx, SdTolerances tol, int T, unsigned long long* __restrict__ counts,
-                                                      unsigned long long* __restrict__ keys, uint64_t* __restrict__ key_buf,
-                                                      double* __restrict__ row_sum) {
-#pragma clang fp contract(off)
-    const int y = (int)blockIdx.x, dir = (int)blockIdx.y, l = (int)blockIdx.z, k = k0 + l, lane = (int)threadIdx.x;
-    const long long HW = (long long)H * W;
-    const uint8_t* bo = border + ((long long)l * 2 + dir) * HW + (long long)y * W;
-    const uint16_t* go = g + ((long long)l * 2 + (1 - dir)) * HW + (long long)y * W;
-    uint64_t* kb = key_buf ? key_buf + ((long long)l * 2 + dir) * HW + (long long)y * W : nullptr;
-    int cnt = 0;
-    int within[kSdMaxTolerances];
-#pragma unroll
-    for (int t = 0; t < kSdMaxTolerances; ++t) within[t] = 0;
-    uint64_t key_max = 0;
-    double acc = 0.0;
-    for (int x0 = 0; x0 < W; x0 += 64) {
-        const int x = x0 + lane;
-        unsigned long long todo = __ballot(x < W && bo[x] != 0);
-        uint64_t mine = kSdNoKey;
-        while (todo) {                                             // at most 64 rounds; the mask is the same in every lane
-            const int src = __ffsll((long long)todo) - 1, px = x0 + src;
-            todo &= todo - 1;
-            double best = sd_inf();
-            for (int xo = lane; xo < W; xo += 64) {
-                const double c = sd_candidate(go[xo], xo > px ? xo - px : px - xo, sy, sx);
-                best = c < best ? c : best;
-            }
-            for (int off = 32; off >= 1; off >>= 1) { const double o = __shfl_down(best, off, 64); best = o < best ? o : best; }
-            best = __shfl(best, 0, 64);                            // lane 0 holds the minimum: now every lane does
-            ++cnt;
-            const uint64_t key = sd_key(best);
-            key_max = key > key_max ? key : key_max;
-#pragma unroll
-            for (int t = 0; t < kSdMaxTolerances; ++t) within[t] += (t < T && best <= tol.sq[t]) ? 1 : 0;
-            mine = lane == src ? key : mine;
-        }
-        if (kb && x < W) kb[x] = mine;
-        if (row_sum) acc = acc + (mine != kSdNoKey ? sd_sqrt(sd_unkey(mine)) : 0.0);      // (+0.0 for no border pixel: the sum stays as it is)
-    }
-    if (row_sum) {
-        acc = sd_wave_halve(acc);
-        if (lane == 0) row_sum[((long long)l * 2 + dir) * H + y] = acc;
-    }
-    if (lane == 0 && cnt) {
-        unsigned long long* c = counts + ((long long)k * 2 + dir) * (1 + T);
-        atomicAdd(c, (unsigned long long)cnt);
-#pragma unroll
-        for (int t = 0; t < kSdMaxTolerances; ++t)
-            if (t < T && within[t]) atomicAdd(c + 1 + t, (unsigned long long)within[t]);
-        atomicMax(keys + (long long)k * 2 + dir, (unsigned long long)key_max);
-    }
-}
-
 // grid = (2, L), block = 64.  row_sum [L][2][H] -> sums [K][2].
 __global__ __launch_bounds__(64) void sd_profile_combine(const double* __restrict__ row_sum, int k0, int H, double* __restrict__ sums) {
     const int dir = (int)blockIdx.x, l = (int)blockIdx.y, lane = (int)threadIdx.x;
-    const double v = sd_wave_halve(st_lane_rows(row_sum + ((long long)l * 2 + dir) * H, H, lane));
+    const double v = st_wave_halve(st_lane_rows(row_sum + ((long long)l * 2 + dir) * H, H, lane));
     if (lane == 0) sums[(long long)(k0 + l) * 2 + dir] = v;
 }
 

@@ -2,6 +2,7 @@
 // (kernels_post_cc.h).  One upload, every step on the device, one download; every device buffer of the call is a DevMem, so HIP_TRY may return
 // wherever it fails.
 #include "engine_internal.h"
+#include "entry_util.h"
 #include "kernels_post_cc.h"
 
 #include <vector>
@@ -16,7 +17,7 @@ int ts2d_keep_largest_components(int device, uint8_t* seg, int Z, int H, int W, 
     if (!seg || !status || (!steps && n_steps > 0)) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
     *status = 0;
     if (Z < 1 || H < 1 || W < 1) return fail(TS2D_ERR_INVALID, "%s: extents %d x %d x %d must be positive", entry, Z, H, W);
-    if ((long long)Z * H > 0x7FFFFFFFll || (long long)Z * H * W > 0x7FFFFFFFll)
+    if (!volume_fits_int32(Z, H, W))
         return fail(TS2D_ERR_INVALID, "%s: %d x %d x %d are more voxels than one call takes (2^31 - 1: the indices are int32)", entry, Z, H, W);
     if (n_steps < 0) return fail(TS2D_ERR_INVALID, "%s: %d steps", entry, n_steps);
     if (n_steps == 0) return TS2D_OK;
@@ -26,12 +27,12 @@ int ts2d_keep_largest_components(int device, uint8_t* seg, int Z, int H, int W, 
     const long long words = (long long)Z * H * ww;
     // [status, counters of every step | the steps | seg | bit words | parent | count]
     const size_t ctr_ints = 1 + (size_t)n_steps * kCcCounters;
-    const size_t o_steps = align_up(ctr_ints * sizeof(int), 256), o_seg = align_up(o_steps + (size_t)n_steps * sizeof(ts2d_cc_step), 256);
-    const size_t o_bits = align_up(o_seg + n, 256), o_parent = align_up(o_bits + (size_t)words * sizeof(cc_word), 256);
-    const size_t o_count = align_up(o_parent + n * sizeof(int), 256);
+    ArenaLayout lay;
+    const size_t o_ctr = lay.add(ctr_ints * sizeof(int)), o_steps = lay.add((size_t)n_steps * sizeof(ts2d_cc_step)), o_seg = lay.add(n);
+    const size_t o_bits = lay.add((size_t)words * sizeof(cc_word)), o_parent = lay.add(n * sizeof(int)), o_count = lay.add(n * sizeof(int));
     DevMem d;
-    HIP_TRY(d.alloc(o_count + n * sizeof(int)));
-    int* const d_status = d.as<int>();
+    HIP_TRY(d.alloc(lay.total()));
+    int* const d_status = d.as<int>(o_ctr);
     uint8_t* const d_seg = d.as<uint8_t>(o_seg);
     cc_word* const d_bits = d.as<cc_word>(o_bits);
     int* const d_parent = d.as<int>(o_parent);

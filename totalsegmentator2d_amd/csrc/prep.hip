@@ -3,6 +3,7 @@
 // of a volume under a 2-D plan, where they lie on the device).
 // The host arithmetic behind them is prep_plan.cpp; every device buffer of a call is a DevMem, so HIP_TRY may return wherever it fails.
 #include "engine_internal.h"
+#include "entry_util.h"
 #include "kernels_project.h"
 #include "kernels_project_modes.h"
 #include "kernels_resample_in.h"
@@ -40,32 +41,24 @@ static_assert(kPrepZScore == TS2D_NORM_ZSCORE && kPrepCT == TS2D_NORM_CT && kPre
 int project_coronal_impl(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz,
                          long long sy, long long sx, long long base, float* out_max, float* out_mean, float* out_norm, double* out_stats, int* out_box) {
     if (!volume || !out_max || !out_mean) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal: null argument");
-    static const int esize[5] = {2, 1, 4, 2, 4};
     if (dtype < 0 || dtype > 4 || nz < 1 || ny < 1 || nx < 1) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal: bad dtype / extents");
-    {   // every element the view can touch must lie inside the buffer
-        long long lo = base, hi = base;
-        const long long ext[3] = {(long long)(nz - 1) * sz, (long long)(ny - 1) * sy, (long long)(nx - 1) * sx};
-        for (int k = 0; k < 3; ++k) { if (ext[k] < 0) lo += ext[k]; else hi += ext[k]; }
-        if (lo < 0 || hi >= (long long)n_elems) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal: the strided view leaves the buffer");
-    }
+    TRY(check_strided_view("ts2d_project_coronal", n_elems, base, {nz, ny, nx}, {sz, sy, sx}, false));
     HIP_TRY(hipSetDevice(device));
-    const size_t vbytes = n_elems * esize[dtype], obytes = (size_t)nz * nx * sizeof(float);
-    // [volume | max | mean (contiguous: the two channels of the z-score) | normalised x 2 | partial sums | stats | box]
-    const size_t o_proj = align_up(vbytes, 256), o_norm = align_up(o_proj + 2 * obytes, 256), o_part = align_up(o_norm + 2 * obytes, 256);
-    const size_t o_stats = o_part + 2 * kZBlocks * sizeof(double), o_box = o_stats + 4 * sizeof(double);
+    const size_t vbytes = n_elems * sample_size(dtype), obytes = (size_t)nz * nx * sizeof(float);
+    ArenaLayout lay;
+    const size_t o_vol = lay.add(vbytes), o_proj = lay.add(2 * obytes);      // max | mean, contiguous: the two channels of the z-score
+    const size_t o_norm = lay.add(2 * obytes), o_part = lay.add(2 * kZBlocks * sizeof(double)), o_stats = lay.add(4 * sizeof(double));
+    const size_t o_box = lay.add(4 * sizeof(int));
     DevMem d;
-    HIP_TRY(d.alloc(o_box + 4 * sizeof(int)));
+    HIP_TRY(d.alloc(lay.total()));
     float* d_max = d.as<float>(o_proj);
     float* d_mean = d_max + (size_t)nz * nx;
-    HIP_TRY(hipMemcpy(d.as<char>(), volume, vbytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_vol), volume, vbytes, hipMemcpyHostToDevice));
     const unsigned grid = (unsigned)(((long long)nz * nx + 255) / 256);
-    switch (dtype) {
-        case 0: hipLaunchKernelGGL(project_coronal<int16_t>, dim3(grid), dim3(256), 0, 0, d.as<const int16_t>(), nz, ny, nx, sz, sy, sx, base, d_max, d_mean); break;
-        case 1: hipLaunchKernelGGL(project_coronal<uint8_t>, dim3(grid), dim3(256), 0, 0, d.as<const uint8_t>(), nz, ny, nx, sz, sy, sx, base, d_max, d_mean); break;
-        case 2: hipLaunchKernelGGL(project_coronal<float>, dim3(grid), dim3(256), 0, 0, d.as<const float>(), nz, ny, nx, sz, sy, sx, base, d_max, d_mean); break;
-        case 3: hipLaunchKernelGGL(project_coronal<uint16_t>, dim3(grid), dim3(256), 0, 0, d.as<const uint16_t>(), nz, ny, nx, sz, sy, sx, base, d_max, d_mean); break;
-        default: hipLaunchKernelGGL(project_coronal<int32_t>, dim3(grid), dim3(256), 0, 0, d.as<const int32_t>(), nz, ny, nx, sz, sy, sx, base, d_max, d_mean); break;
-    }
+    by_sample_type(dtype, [&](auto t) {
+        using S = typename decltype(t)::type;
+        hipLaunchKernelGGL(project_coronal<S>, dim3(grid), dim3(256), 0, 0, d.as<const S>(o_vol), nz, ny, nx, sz, sy, sx, base, d_max, d_mean);
+    });
     HIP_TRY(hipGetLastError());
     if (out_norm) {          // per-channel z-score of (max, mean): float64 two-pass statistics, deterministic
         const long long n = (long long)nz * nx;
@@ -129,7 +122,6 @@ int project_coronal_modes_impl(int device, const void* volume, size_t n_elems, i
     if (!out_planes) return fail(TS2D_ERR_INVALID, "%s: out_planes is null", E);
     if (!status) return fail(TS2D_ERR_INVALID, "%s: status is null", E);
     if (!out_norm && (out_stats || out_box)) return fail(TS2D_ERR_INVALID, "%s: out_stats / out_box without out_norm", E);
-    static const int esize[5] = {2, 1, 4, 2, 4};
     if (dtype < 0 || dtype > 4) return fail(TS2D_ERR_INVALID, "%s: dtype %d unknown", E, dtype);
     if (n_modes < 1 || n_modes > kPmMaxModes) return fail(TS2D_ERR_INVALID, "%s: n_modes %d outside 1 ... %d", E, n_modes, kPmMaxModes);
     if (nz < 1 || ny < 1 || nx < 1) return fail(TS2D_ERR_INVALID, "%s: extents nz %d, ny %d, nx %d below 1", E, nz, ny, nx);
@@ -143,26 +135,21 @@ int project_coronal_modes_impl(int device, const void* volume, size_t n_elems, i
         want[modes[m]] = true;
     }
     if (want[kPmStd] && ny < 2) return fail(TS2D_ERR_INVALID, "%s: the std mode needs ny >= 2, found ny %d", E, ny);
-    {   // every element the view can touch must lie inside the buffer
-        long long lo = base, hi = base;
-        const long long ext[3] = {(long long)(nz - 1) * sz, (long long)(ny - 1) * sy, (long long)(nx - 1) * sx};
-        for (int k = 0; k < 3; ++k) { if (ext[k] < 0) lo += ext[k]; else hi += ext[k]; }
-        if (lo < 0 || hi >= (long long)n_elems) return fail(TS2D_ERR_INVALID, "%s: the strided view (base, sz, sy, sx) leaves the buffer of n_elems %zu", E, n_elems);
-    }
+    TRY(check_strided_view(E, n_elems, base, {nz, ny, nx}, {sz, sy, sx}));
     *status = 0;
     if (ny > kPmRayCap) { *status = kPmStatusRayTooLong; return TS2D_OK; }     // nothing is launched, nothing is written
     HIP_TRY(hipSetDevice(device));
     const long long n = (long long)nz * nx;
-    const size_t vbytes = n_elems * esize[dtype], obytes = (size_t)n * sizeof(float);
-    // [volume | planes x n_modes | normalised x n_modes | partial sums | stats | boxes | status]
-    const size_t o_proj = align_up(vbytes, 256), o_norm = align_up(o_proj + n_modes * obytes, 256), o_part = align_up(o_norm + n_modes * obytes, 256);
-    const size_t o_stats = o_part + (size_t)n_modes * kZBlocks * sizeof(double), o_box = o_stats + (size_t)n_modes * 2 * sizeof(double);
-    const size_t o_status = o_box + (size_t)n_modes * 4 * sizeof(int);
+    const size_t vbytes = n_elems * sample_size(dtype), obytes = (size_t)n * sizeof(float);
+    ArenaLayout lay;
+    const size_t o_vol = lay.add(vbytes), o_proj = lay.add(n_modes * obytes), o_norm = lay.add(n_modes * obytes);
+    const size_t o_part = lay.add((size_t)n_modes * kZBlocks * sizeof(double)), o_stats = lay.add((size_t)n_modes * 2 * sizeof(double));
+    const size_t o_box = lay.add((size_t)n_modes * 4 * sizeof(int)), o_status = lay.add(sizeof(int));
     DevMem d;
-    HIP_TRY(d.alloc(o_status + sizeof(int)));
+    HIP_TRY(d.alloc(lay.total()));
     float* d_planes = d.as<float>(o_proj);
     int* d_status = d.as<int>(o_status);
-    HIP_TRY(hipMemcpy(d.as<char>(), volume, vbytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_vol), volume, vbytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(d_status, 0, sizeof(int)));
     // a kind asked for twice is computed once, into its first plane, and copied to the others
     PmStreamArgs sa = {};
@@ -175,13 +162,9 @@ int project_coronal_modes_impl(int device, const void* volume, size_t n_elems, i
     for (int k = 0; k < kPmKinds; ++k) sa.out[k] = (k == kPmMedian || k == kPmSlice) ? nullptr : d_first[k];
     // a float volume is always streamed: that pass is what finds a non-finite sample
     const bool stream = dtype == 2 || sa.n_slices > 0 || want[kPmMax] || want[kPmMin] || want[kPmMean] || want[kPmStd] || want[kPmFirst];
-    switch (dtype) {
-        case 0: TRY(project_modes_launch(d.as<const int16_t>(), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status)); break;
-        case 1: TRY(project_modes_launch(d.as<const uint8_t>(), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status)); break;
-        case 2: TRY(project_modes_launch(d.as<const float>(), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status)); break;
-        case 3: TRY(project_modes_launch(d.as<const uint16_t>(), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status)); break;
-        default: TRY(project_modes_launch(d.as<const int32_t>(), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status)); break;
-    }
+    TRY(by_sample_type(dtype, [&](auto t) {
+        return project_modes_launch(d.as<const typename decltype(t)::type>(o_vol), nz, ny, nx, sz, sy, sx, base, stream, sa, d_first[kPmMedian], d_status);
+    }));
     for (int m = 0; m < n_modes; ++m) {
         float* plane = d_planes + (size_t)m * n;
         if (modes[m] != kPmSlice && d_first[modes[m]] != plane) HIP_TRY(hipMemcpy(plane, d_first[modes[m]], obytes, hipMemcpyDeviceToDevice));

@@ -3,6 +3,7 @@
 // device in chunks of labels whose row partials stay below max_scratch_bytes, one download; every device buffer of the call is one DevMem,
 // so HIP_TRY may return wherever it fails.
 #include "engine_internal.h"
+#include "entry_util.h"
 #include "kernels_stats.h"
 
 #include <cstring>
@@ -19,46 +20,40 @@ int ts2d_label_statistics(int device, const uint8_t* seg, int kind, const uint8_
     const char* const entry = "ts2d_label_statistics";
     if (!seg || !out_int || !status) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
     *status = 0;
-    if (kind != kStPlanes && kind != kStLabelMap) return fail(TS2D_ERR_INVALID, "%s: kind %d is neither planes (0) nor label map (1)", entry, kind);
-    if (K < 1 || K > 255) return fail(TS2D_ERR_INVALID, "%s: K = %d labels outside 1 ... 255", entry, K);
-    if (Z < 1 || H < 1 || W < 1 || (long long)Z * H > 0x7FFFFFFFll || (long long)Z * H * W > 0x7FFFFFFFll)
-        return fail(TS2D_ERR_INVALID, "%s: %d x %d x %d is empty or more than 2^31 - 1 voxels", entry, Z, H, W);
+    if (!label_kind(kind)) return fail(TS2D_ERR_INVALID, "%s: kind %d is neither planes (0) nor label map (1)", entry, kind);
+    TRY(check_label_count(entry, K));
+    if (!volume_fits_int32(Z, H, W)) return fail(TS2D_ERR_INVALID, "%s: %d x %d x %d is empty or more than 2^31 - 1 voxels", entry, Z, H, W);
     if (C < 0 || C > TS2D_STATS_MAX_CHANNELS) return fail(TS2D_ERR_INVALID, "%s: C = %d channels outside 0 ... %d", entry, C, TS2D_STATS_MAX_CHANNELS);
     if (C > 0 && (!intensities || !out_f64)) return fail(TS2D_ERR_INVALID, "%s: C = %d channels without intensities or out_f64", entry, C);
-    if (kind == kStLabelMap) {
-        if (!values) return fail(TS2D_ERR_INVALID, "%s: a label map needs the values of its K labels", entry);
-        for (int k = 0; k < K; ++k)
-            if (values[k] == 0) return fail(TS2D_ERR_INVALID, "%s: values[%d] = 0 is the background, not a label", entry, k);
-    }
+    if (kind == kStLabelMap) TRY(check_label_values(entry, values, K));
     const size_t n = (size_t)Z * H * W, R = (size_t)Z * H;
     // a label's row partials: count, min x, max x (int32), sum x (int64), and per channel one float64 and two keys
     const size_t per_label = R * (20 + 16 * (size_t)C);
-    const size_t budget = max_scratch_bytes ? max_scratch_bytes : ((size_t)256 << 20);
-    size_t L = budget / per_label;
+    size_t budget = 0;
+    size_t L = labels_per_chunk(max_scratch_bytes, per_label, K, &budget);
     if (L < 1)
         return fail(TS2D_ERR_INVALID, "%s: the row partials of ONE label (%zu rows, %d channels) take %zu bytes, above max_scratch_bytes = %zu", entry,
                     R, C, per_label, budget);
     const size_t slot_cap = (size_t)0x7FFFFFFF / (R * (size_t)(C > 0 ? C : 1));       // int32 slots: L * C * R stays below 2^31
     if (slot_cap < 1) return fail(TS2D_ERR_INVALID, "%s: %zu rows x %d channels are more partial slots than an int32 index reaches", entry, R, C);
     if (L > slot_cap) L = slot_cap;
-    if (L > (size_t)K) L = (size_t)K;
 
     HIP_TRY(hipSetDevice(device));
     const size_t seg_bytes = kind == kStPlanes ? (size_t)K * n : n;
-    // [status | values | out_int | out_f64 | segmentation | intensities | partials of a chunk]
-    const size_t o_val = 256, o_int = o_val + 256, o_f64 = align_up(o_int + (size_t)K * kStInts * sizeof(long long), 256);
-    const size_t o_seg = align_up(o_f64 + (size_t)K * C * kStF64s * sizeof(double), 256), o_x = align_up(o_seg + seg_bytes, 256);
-    const size_t o_cnt = align_up(o_x + (size_t)C * n * sizeof(float), 256), o_minx = align_up(o_cnt + L * R * 4, 256);
-    const size_t o_maxx = align_up(o_minx + L * R * 4, 256), o_sumx = align_up(o_maxx + L * R * 4, 256);
-    const size_t o_fsum = align_up(o_sumx + L * R * 8, 256), o_kmin = align_up(o_fsum + L * C * R * 8, 256);
-    const size_t o_kmax = align_up(o_kmin + L * C * R * 4, 256), total = align_up(o_kmax + L * C * R * 4, 256);
+    // [status | values || out_int | out_f64 || segmentation | intensities | partials of a chunk]: what starts as zero, what is downloaded, the rest
+    ArenaLayout lay;
+    const size_t o_status = lay.add(sizeof(int)), o_val = lay.add((size_t)K);
+    const size_t o_int = lay.add((size_t)K * kStInts * sizeof(long long)), o_f64 = lay.add((size_t)K * C * kStF64s * sizeof(double));
+    const size_t o_seg = lay.add(seg_bytes), o_x = lay.add((size_t)C * n * sizeof(float));
+    const size_t o_cnt = lay.add(L * R * 4), o_minx = lay.add(L * R * 4), o_maxx = lay.add(L * R * 4), o_sumx = lay.add(L * R * 8);
+    const size_t o_fsum = lay.add(L * C * R * 8), o_kmin = lay.add(L * C * R * 4), o_kmax = lay.add(L * C * R * 4);
     DevMem d;
-    HIP_TRY(d.alloc(total));
+    HIP_TRY(d.alloc(lay.total()));
     HIP_TRY(hipMemset(d.as<char>(), 0, o_int));
     if (kind == kStLabelMap) HIP_TRY(hipMemcpy(d.as<char>(o_val), values, (size_t)K, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_seg), seg, seg_bytes, hipMemcpyHostToDevice));
     if (C > 0) HIP_TRY(hipMemcpy(d.as<char>(o_x), intensities, (size_t)C * n * sizeof(float), hipMemcpyHostToDevice));
-    int* const d_status = d.as<int>();
+    int* const d_status = d.as<int>(o_status);
     const uint8_t* const d_values = d.as<const uint8_t>(o_val);
     long long* const d_int = d.as<long long>(o_int);
     double* const d_f64 = d.as<double>(o_f64);

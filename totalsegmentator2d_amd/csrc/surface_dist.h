@@ -1,6 +1,8 @@
-// The arithmetic of the boundary distances (kernels_evaluate.h) that the statement, totalsegmentator2d_amd/evaluate.py, fixes bit for bit: which
-// samples belong to a label, which of them are border pixels, and the squared distance of a border pixel of one mask to the border of the other.
-// Its own header, host and device: tests/test_evaluate_cpu.py compiles it into a stand-alone program and holds sd_label against the statement.
+// The arithmetic of the boundary distances and their profile (kernels_evaluate.h, kernels_evaluate_profile.h) that the statements of
+// totalsegmentator2d_amd/evaluate.py fix bit for bit: which samples are border pixels, the squared distance of a border pixel of one mask to the
+// border of the other, and the sum and the order statistics of those distances.  Its own header, host and device: tests/test_evaluate_cpu.py and
+// tests/test_evaluate_profile_cpu.py compile it into stand-alone programs and hold its ONE host walk, sd_label_profile (sd_label: the call of it
+// without the profile), against the statements.
 //
 // Border.  A border pixel of a mask is a foreground pixel with at least one of its four neighbours background; outside the image is background.
 //
@@ -45,7 +47,6 @@
 
 namespace ts2d {
 
-enum { kSdPlanes = 0, kSdLabelMap = 1 };      // TS2D_STATS_PLANES, TS2D_STATS_LABELMAP
 constexpr uint16_t kSdNone = 0xFFFFu;          // g of a column without a border pixel (H <= kSdMaxExtent keeps every real g below it)
 constexpr int kSdMaxExtent = 32767;
 constexpr int kSdMaxTolerances = 8;            // TS2D_EVAL_MAX_TOLERANCES
@@ -54,16 +55,13 @@ constexpr int kSdMaxRanks = 2 * kSdMaxPercentiles;      // a percentile selects 
 constexpr uint64_t kSdNoKey = ~0ull;           // in a key buffer: not a border pixel (the bits of a NaN: no d2 has them)
 constexpr int kSdRounds = 8, kSdDigits = 256;  // a 64-bit key in 8-bit digits, the top one first
 
-// does a segmentation sample belong to the label?  planes: the label's own plane > 0; label map: the sample equals the label's value
-TS2D_SD_HD bool sd_masked(uint8_t s, int kind, uint8_t value) { return kind == kSdLabelMap ? s == value : s > 0; }
-
-// is (y, x) a border pixel of the label's mask m [H][W]?
+// is (y, x) a border pixel of the label's mask m [H][W]?  (the kinds and st_masked, who belongs to the label: stats_tree.h)
 TS2D_SD_HD bool sd_border(const uint8_t* m, int kind, uint8_t value, int H, int W, int y, int x) {
-    if (!sd_masked(m[(long long)y * W + x], kind, value)) return false;
-    const bool up = y > 0 && sd_masked(m[(long long)(y - 1) * W + x], kind, value);
-    const bool down = y + 1 < H && sd_masked(m[(long long)(y + 1) * W + x], kind, value);
-    const bool left = x > 0 && sd_masked(m[(long long)y * W + x - 1], kind, value);
-    const bool right = x + 1 < W && sd_masked(m[(long long)y * W + x + 1], kind, value);
+    if (!st_masked(m[(long long)y * W + x], kind, value)) return false;
+    const bool up = y > 0 && st_masked(m[(long long)(y - 1) * W + x], kind, value);
+    const bool down = y + 1 < H && st_masked(m[(long long)(y + 1) * W + x], kind, value);
+    const bool left = x > 0 && st_masked(m[(long long)y * W + x - 1], kind, value);
+    const bool right = x + 1 < W && st_masked(m[(long long)y * W + x + 1], kind, value);
     return !(up && down && left && right);
 }
 
@@ -153,36 +151,6 @@ inline void sd_column(const uint8_t* border, int H, int W, int x, uint16_t* g) {
     }
 }
 
-// One label and one direction on the host, what the kernels compute together: the border count of `own`, the largest d2 as a key (0 for an empty
-// border: the caller reports -inf) and per tolerance the border pixels with d2 <= tol_sq[t].  border_own, border_other: H * W bytes of scratch
-// each; g: H * W.
-inline long long sd_label(const uint8_t* own, int kind_own, const uint8_t* other, int kind_other, uint8_t value, int H, int W, double sy, double sx,
-                          const double* tol_sq, int T, uint8_t* border_own, uint8_t* border_other, uint16_t* g, uint64_t* key_max, long long* within) {
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            border_own[(size_t)y * W + x] = sd_border(own, kind_own, value, H, W, y, x) ? 1 : 0;
-            border_other[(size_t)y * W + x] = sd_border(other, kind_other, value, H, W, y, x) ? 1 : 0;
-        }
-    for (int x = 0; x < W; ++x) sd_column(border_other, H, W, x, g);
-    long long n = 0;
-    *key_max = 0;
-    for (int t = 0; t < T; ++t) within[t] = 0;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            if (!border_own[(size_t)y * W + x]) continue;
-            double d2 = sd_inf();
-            for (int xo = 0; xo < W; ++xo) {
-                const double c = sd_candidate(g[(size_t)y * W + xo], xo > x ? xo - x : x - xo, sy, sx);
-                d2 = c < d2 ? c : d2;
-            }
-            ++n;
-            const uint64_t key = sd_key(d2);
-            *key_max = key > *key_max ? key : *key_max;
-            for (int t = 0; t < T; ++t) within[t] += d2 <= tol_sq[t] ? 1 : 0;
-        }
-    return n;
-}
-
 // The key at sorted position rank (0 <= rank < the number of keys other than kSdNoKey) of keys[0 ... n - 1]: what sd_select_hist and
 // sd_select_decide compute together.
 inline uint64_t sd_select_rank(const uint64_t* keys, size_t n, long long rank) {
@@ -200,9 +168,11 @@ inline uint64_t sd_select_rank(const uint64_t* keys, size_t n, long long rank) {
     return prefix;
 }
 
-// sd_label with the profile, what sd_columns, sd_rows_profile, sd_profile_combine and the selection kernels compute together: also the sum of
-// the distances in the tree over (H, W) and per percentile q[p] the keys at the two sorted positions (rank_keys [P][2]) and the weight
-// (weights [P]); an empty border leaves rank_keys and weights alone and gives the sum +0.0.  keys: H * W, partial: H of scratch.
+// One label and one direction on the host, what sd_columns, sd_rows, sd_profile_combine and the selection kernels compute together: the border
+// count of `own`, the largest d2 as a key (0 for an empty border: the caller reports -inf), per tolerance the border pixels with d2 <= tol_sq[t];
+// with `partial` (H of scratch; else null) the sum of the distances in the tree over (H, W), +0.0 for an empty border; with `keys` (H * W of
+// scratch; else null, and P = 0) per percentile q[p] the keys at the two sorted positions (rank_keys [P][2]) and the weight (weights [P]), which
+// an empty border leaves alone.  border_own, border_other: H * W bytes of scratch each; g: H * W.
 inline long long sd_label_profile(const uint8_t* own, int kind_own, const uint8_t* other, int kind_other, uint8_t value, int H, int W, double sy,
                                   double sx, const double* tol_sq, int T, const double* q, int P, uint8_t* border_own, uint8_t* border_other,
                                   uint16_t* g, uint64_t* keys, double* partial, uint64_t* key_max, long long* within, double* dist_sum,
@@ -221,7 +191,7 @@ inline long long sd_label_profile(const uint8_t* own, int kind_own, const uint8_
     for (int y = 0; y < H; ++y) {
         for (int l = 0; l < kStLanes; ++l) v[l] = 0.0;
         for (int x = 0; x < W; ++x) {
-            keys[(size_t)y * W + x] = kSdNoKey;
+            if (keys) keys[(size_t)y * W + x] = kSdNoKey;
             if (!border_own[(size_t)y * W + x]) continue;
             double d2 = sd_inf();
             for (int xo = 0; xo < W; ++xo) {
@@ -230,15 +200,17 @@ inline long long sd_label_profile(const uint8_t* own, int kind_own, const uint8_
             }
             ++n;
             const uint64_t key = sd_key(d2);
-            keys[(size_t)y * W + x] = key;
+            if (keys) keys[(size_t)y * W + x] = key;
             *key_max = key > *key_max ? key : *key_max;
             for (int t = 0; t < T; ++t) within[t] += d2 <= tol_sq[t] ? 1 : 0;
-            v[x % kStLanes] = v[x % kStLanes] + sd_sqrt(d2);          // increasing x: lane x % 64 meets its terms in order
+            if (partial) v[x % kStLanes] = v[x % kStLanes] + sd_sqrt(d2);          // increasing x: lane x % 64 meets its terms in order
         }
-        partial[y] = st_halve(v);
+        if (partial) partial[y] = st_halve(v);
     }
-    for (int l = 0; l < kStLanes; ++l) v[l] = st_lane_rows(partial, H, l);
-    *dist_sum = st_halve(v);
+    if (partial) {
+        for (int l = 0; l < kStLanes; ++l) v[l] = st_lane_rows(partial, H, l);
+        *dist_sum = st_halve(v);
+    }
     for (int p = 0; p < P && n > 0; ++p) {
         long long i, j;
         sd_percentile_ranks(n, q[p], &i, &j, weights + p);
@@ -246,6 +218,13 @@ inline long long sd_label_profile(const uint8_t* own, int kind_own, const uint8_
         rank_keys[2 * p + 1] = sd_select_rank(keys, (size_t)H * W, j);
     }
     return n;
+}
+
+// ... without the profile: what ts2d_surface_distances reports
+inline long long sd_label(const uint8_t* own, int kind_own, const uint8_t* other, int kind_other, uint8_t value, int H, int W, double sy, double sx,
+                          const double* tol_sq, int T, uint8_t* border_own, uint8_t* border_other, uint16_t* g, uint64_t* key_max, long long* within) {
+    return sd_label_profile(own, kind_own, other, kind_other, value, H, W, sy, sx, tol_sq, T, nullptr, 0, border_own, border_other, g, nullptr, nullptr,
+                            key_max, within, nullptr, nullptr, nullptr);
 }
 #endif
 

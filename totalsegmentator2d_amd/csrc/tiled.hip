@@ -3,6 +3,7 @@
 // ts2d_ensemble_predict_tiled_labelmap, ts2d_ensemble_predict_tiled_regions, ts2d_ensemble_predict_tiled_probabilities (and its _stack twin),
 // ts2d_labelmap_from_logits, ts2d_regions_from_logits and ts2d_probabilities_from_logits.
 #include "engine_internal.h"
+#include "entry_util.h"
 #include "kernels_sw.h"
 #include "kernels_fold.h"
 #include "kernels_resample.h"
@@ -450,18 +451,18 @@ int ts2d_probabilities_from_logits(int device, const uint16_t* logits_f16, int K
     const bool regions = mode == kProbRegions;
     const ProbSeg ps{0, 0, full_h, full_w, box_y, box_x};
     HIP_TRY(hipSetDevice(device));
-    // [segment | probabilities segment | taps | class order | half planes | probabilities | decided map]
     const size_t n_src = (size_t)K * H * W, n_prob = (size_t)K * full_h * full_w, n_dec = decided_u8 ? (mode == kProbMultilabel ? n_prob : n_prob / K) : 0;
-    const size_t o_ps = align_up(sizeof(RsSeg), 8), o_taps = o_ps + sizeof(ProbSeg), o_order = o_taps + rtaps.size() * sizeof(RsTap);
-    const size_t o_src = align_up(o_order + (regions ? (size_t)K : 0), 256), o_prob = align_up(o_src + n_src * 2, 256), o_dec = align_up(o_prob + n_prob * 4, 256);
+    ArenaLayout lay;
+    const size_t o_seg = lay.add(sizeof(RsSeg)), o_ps = lay.add(sizeof(ProbSeg)), o_taps = lay.add(rtaps.size() * sizeof(RsTap));
+    const size_t o_order = lay.add(regions ? (size_t)K : 0), o_src = lay.add(n_src * 2), o_prob = lay.add(n_prob * 4), o_dec = lay.add(n_dec);
     DevMem d;
-    HIP_TRY(d.alloc(o_dec + n_dec));
-    HIP_TRY(hipMemcpy(d.as<char>(), segs.data(), sizeof(RsSeg), hipMemcpyHostToDevice));
+    HIP_TRY(d.alloc(lay.total()));
+    HIP_TRY(hipMemcpy(d.as<char>(o_seg), segs.data(), sizeof(RsSeg), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_ps), &ps, sizeof(ProbSeg), hipMemcpyHostToDevice));
     if (!rtaps.empty()) HIP_TRY(hipMemcpy(d.as<char>(o_taps), rtaps.data(), rtaps.size() * sizeof(RsTap), hipMemcpyHostToDevice));
     if (regions) HIP_TRY(hipMemcpy(d.as<char>(o_order), class_order, (size_t)K, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_src), logits_f16, n_src * 2, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sw_probabilities<ProbSeg>, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(), d.as<const ProbSeg>(o_ps), 1, K,
+    hipLaunchKernelGGL(sw_probabilities<ProbSeg>, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(o_seg), d.as<const ProbSeg>(o_ps), 1, K,
                        d.as<const RsTap>(o_taps), mode, regions ? d.as<const uint8_t>(o_order) : nullptr, d.as<float>(o_prob),
                        decided_u8 ? d.as<uint8_t>(o_dec) : nullptr, kSigmoidHalfThreshold);
     HIP_TRY(hipGetLastError());

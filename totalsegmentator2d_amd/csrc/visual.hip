@@ -3,6 +3,7 @@
 // out, one call = uploads, a few launches on the default stream, downloads; every device buffer of a call is a DevMem, so HIP_TRY may return
 // wherever it fails.
 #include "engine_internal.h"
+#include "entry_util.h"
 #include "kernels_visual.h"
 
 #include <cmath>
@@ -68,12 +69,12 @@ int ts2d_visual_labels(int device, const uint8_t* planes, int K, int H, int W, d
     visual_color_lut(palette, n_palette, lut);
     HIP_TRY(hipSetDevice(device));
     const size_t n = (size_t)H * W, stride = align_up(n, 16), n_out = (size_t)out_h * out_w;
-    // [colour table | axis tables | index map | rgb | the planes at a stride of a multiple of 16 (K > 1)]
-    const size_t o_taps = align_up(sizeof(lut), 256), o_idx = align_up(o_taps + taps.size() * sizeof(VisTap), 256);
-    const size_t o_rgb = align_up(o_idx + stride, 256), o_planes = align_up(o_rgb + 3 * n_out, 256);
+    ArenaLayout lay;
+    const size_t o_lut = lay.add(sizeof(lut)), o_taps = lay.add(taps.size() * sizeof(VisTap)), o_idx = lay.add(stride), o_rgb = lay.add(3 * n_out);
+    const size_t o_planes = lay.add(K > 1 ? (size_t)K * stride : 0);          // at a stride of a multiple of 16
     DevMem d;
-    HIP_TRY(d.alloc(o_planes + (K > 1 ? (size_t)K * stride : 0)));
-    HIP_TRY(hipMemcpy(d.as<char>(), lut, sizeof(lut), hipMemcpyHostToDevice));
+    HIP_TRY(d.alloc(lay.total()));
+    HIP_TRY(hipMemcpy(d.as<char>(o_lut), lut, sizeof(lut), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_taps), taps.data(), taps.size() * sizeof(VisTap), hipMemcpyHostToDevice));
     uint8_t* const d_idx = d.as<uint8_t>(o_idx);
     if (K > 1) {
@@ -84,7 +85,7 @@ int ts2d_visual_labels(int device, const uint8_t* planes, int K, int H, int W, d
         HIP_TRY(hipMemcpy(d_idx, planes, n, hipMemcpyHostToDevice));      // K = 1 is a label map: it is its own index map
     }
     hipLaunchKernelGGL(visual_label_rgb, dim3((unsigned)((out_w + 255) / 256), (unsigned)out_h), dim3(64), 0, 0, d_idx, W, out_h, out_w,
-                       d.as<const VisTap>(o_taps), d.as<const uint32_t>(), d.as<uint8_t>(o_rgb));
+                       d.as<const VisTap>(o_taps), d.as<const uint32_t>(o_lut), d.as<uint8_t>(o_rgb));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(rgb, d.as<char>(o_rgb), 3 * n_out, hipMemcpyDeviceToHost));
     return TS2D_OK;
@@ -93,7 +94,6 @@ int ts2d_visual_labels(int device, const uint8_t* planes, int K, int H, int W, d
 int ts2d_visual_grey(int device, const void* plane, int dtype, int H, int W, double spacing_h, double spacing_w, int cubic, double lo, double hi,
                      int auto_lo, int auto_hi, int out_h, int out_w, uint8_t* grey, double* window_used, int* status) {
     const char* const entry = "ts2d_visual_grey";
-    static const size_t esize[5] = {2, 1, 4, 2, 4};
     if (!plane || !grey || !window_used || !status) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
     *status = 0;
     if (dtype < 0 || dtype > 4) return fail(TS2D_ERR_INVALID, "%s: dtype %d unknown (0 int16, 1 uint8, 2 float32, 3 uint16, 4 int32)", entry, dtype);
@@ -110,30 +110,26 @@ int ts2d_visual_grey(int device, const void* plane, int dtype, int H, int W, dou
     const VisAxis ax_h = visual_axis_constants(H), ax_w = visual_axis_constants(W);
     HIP_TRY(hipSetDevice(device));
     const size_t n = (size_t)H * W, n_out = (size_t)out_h * out_w;
-    // [control words | axis tables | pole powers | source plane | resampled words | grey | coefficients (cubic)]
-    const size_t o_taps = 256, o_pow = align_up(o_taps + taps.size() * sizeof(VisTap), 256), o_src = align_up(o_pow + zpow.size() * sizeof(double), 256);
-    const size_t o_res = align_up(o_src + n * esize[dtype], 256), o_grey = align_up(o_res + n_out * sizeof(int), 256);
-    const size_t o_coef = align_up(o_grey + n_out, 256);
+    ArenaLayout lay;
+    const size_t o_ctl = lay.add(sizeof(VisCtl)), o_taps = lay.add(taps.size() * sizeof(VisTap)), o_pow = lay.add(zpow.size() * sizeof(double));
+    const size_t o_src = lay.add(n * sample_size(dtype)), o_res = lay.add(n_out * sizeof(int)), o_grey = lay.add(n_out);
+    const size_t o_coef = lay.add(cubic ? n * sizeof(double) : 0);
     DevMem d;
-    HIP_TRY(d.alloc(o_coef + (cubic ? n * sizeof(double) : 0)));
+    HIP_TRY(d.alloc(lay.total()));
     VisCtl ctl = {0, 0x7FFFFFFF, (int)0x80000000, 0};
-    VisCtl* const d_ctl = d.as<VisCtl>();
+    VisCtl* const d_ctl = d.as<VisCtl>(o_ctl);
     HIP_TRY(hipMemcpy(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_taps), taps.data(), taps.size() * sizeof(VisTap), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_pow), zpow.data(), zpow.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.as<char>(o_src), plane, n * esize[dtype], hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_src), plane, n * sample_size(dtype), hipMemcpyHostToDevice));
     const void* d_src = d.as<const char>(o_src);
     const VisTap* d_taps = d.as<const VisTap>(o_taps);
     const double* d_zpow = d.as<const double>(o_pow);
     double* d_coef = d.as<double>(o_coef);
     int* d_res = d.as<int>(o_res);
-    switch (dtype) {
-        case 0: launch_grey_resample<0>(cubic, d_src, H, W, out_h, out_w, ax_h, ax_w, d_zpow, d_coef, d_taps, d_res, d_ctl); break;
-        case 1: launch_grey_resample<1>(cubic, d_src, H, W, out_h, out_w, ax_h, ax_w, d_zpow, d_coef, d_taps, d_res, d_ctl); break;
-        case 2: launch_grey_resample<2>(cubic, d_src, H, W, out_h, out_w, ax_h, ax_w, d_zpow, d_coef, d_taps, d_res, d_ctl); break;
-        case 3: launch_grey_resample<3>(cubic, d_src, H, W, out_h, out_w, ax_h, ax_w, d_zpow, d_coef, d_taps, d_res, d_ctl); break;
-        default: launch_grey_resample<4>(cubic, d_src, H, W, out_h, out_w, ax_h, ax_w, d_zpow, d_coef, d_taps, d_res, d_ctl); break;
-    }
+    by_sample_type(dtype, [&](auto t) {
+        launch_grey_resample<decltype(t)::dtype>(cubic, d_src, H, W, out_h, out_w, ax_h, ax_w, d_zpow, d_coef, d_taps, d_res, d_ctl);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost));      // (waits for the launches: the default stream orders them)
     if (ctl.status) { *status = ctl.status; return TS2D_OK; }                   // a non-finite sample: nothing is written, the caller takes the host route

@@ -553,15 +553,29 @@ def _prob_mode(mode, class_order, what: str):
     return _lib.PROB_REGIONS, _class_order_u8(class_order, what)
 
 
-def _need_probabilities(lib, name: str):
+def has_entry(*names: str, tolerant: bool = True) -> bool:
+    """Does the engine library have every one of these entries?  The ONE lookup behind the ``has_*`` / ``device_*`` probes of the package: a
+    library built before an optional entry (``_lib.OPTIONAL``) still loads, and the callers keep the host route.  ``tolerant``: no library built,
+    or one that does not load, is False too (else that is ``_lib.load``'s error)."""
+    try:
+        return all(hasattr(_lib.load(), n) for n in names)
+    except Exception:
+        if tolerant:
+            return False
+        raise
+
+
+def _entry(name: str, lib=None):
+    """The entry ``name`` of the library (``lib``: an engine's own handle of it), or the error that says what to do about a library without it."""
+    lib = _lib.load() if lib is None else lib
     if not hasattr(lib, name):
-        raise RuntimeError(f"{name}: this libts2d_engine.so was built before the probabilities entries; rebuild it, or keep the host route")
+        raise RuntimeError(f"{name}: this libts2d_engine.so was built before the entry; rebuild it, or keep the host route")
     return getattr(lib, name)
 
 
 def has_probabilities() -> bool:
     """Does the loaded library have the probabilities entries?  (A library built before them still loads: the callers keep the host route.)"""
-    return hasattr(_lib.load(), 'ts2d_ensemble_predict_tiled_probabilities')
+    return has_entry('ts2d_ensemble_predict_tiled_probabilities', tolerant=False)
 
 
 def predict_tiled_probabilities_ensemble(engines, images, patch, tiles, rects, mode, class_order=None, mirror_axes=None,
@@ -582,7 +596,7 @@ def predict_tiled_probabilities_ensemble(engines, images, patch, tiles, rects, m
     if rects is None:
         raise RuntimeError(f"{what}: the probabilities need their rectangles and extents")
     code, order = _prob_mode(mode, class_order, what)
-    fn = _need_probabilities(engines[0].lib, 'ts2d_ensemble_predict_tiled_probabilities')
+    fn = _entry('ts2d_ensemble_predict_tiled_probabilities', engines[0].lib)
     desc, pd, mask, g, keep, outs = engines[0]._tiled_args(what, images, tiles, rects, mirror_axes, gaussian, bool(want_decided), True, want_logits,
                                                            False, labelmap=True, prob_mode=code)
     handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
@@ -595,7 +609,7 @@ def predict_tiled_probabilities_ensemble(engines, images, patch, tiles, rects, m
 
 def has_stack_probabilities() -> bool:
     """Does the loaded library have the probabilities entry for slice stacks?  (One built before it still loads: the callers keep the host route.)"""
-    return hasattr(_lib.load(), 'ts2d_ensemble_predict_tiled_probabilities_stack')
+    return has_entry('ts2d_ensemble_predict_tiled_probabilities_stack', tolerant=False)
 
 
 def predict_tiled_probabilities_stack_ensemble(engines, images, patch, tiles, runs, mode, class_order=None, mirror_axes=None,
@@ -612,7 +626,7 @@ def predict_tiled_probabilities_stack_ensemble(engines, images, patch, tiles, ru
     if not engines:
         raise RuntimeError(f"{what}: no engines")
     code, order = _prob_mode(mode, class_order, what)
-    fn = _need_probabilities(engines[0].lib, 'ts2d_ensemble_predict_tiled_probabilities_stack')
+    fn = _entry('ts2d_ensemble_predict_tiled_probabilities_stack', engines[0].lib)
     desc, _, mask, g, keep, outs = engines[0]._tiled_args(what, images, tiles, None, mirror_axes, gaussian, False, False, want_logits, False, runs=True)
     K = engines[0].arch.num_classes
     rd = (_lib.TiledProbabilitiesRun * max(len(runs), 1))()
@@ -658,7 +672,7 @@ def probabilities_from_logits(logits_f16: np.ndarray, rect, out_hw, full_hw, box
     prob = np.empty((lg.shape[0],) + full, dtype=np.float32)
     dec = np.empty(((lg.shape[0],) if code == _lib.PROB_MULTILABEL else ()) + full, dtype=np.uint8) if want_decided else None
     r = (ctypes.c_int32 * 4)(*[int(v) for v in rect])
-    fn = _need_probabilities(_lib.load(), 'ts2d_probabilities_from_logits')
+    fn = _entry('ts2d_probabilities_from_logits')
     _lib.check(fn(int(device), lg.ctypes.data, lg.shape[0], lg.shape[1], lg.shape[2], ctypes.byref(r), oh, ow, fh, fw, by, bx, code,
                   None if order is None else order.ctypes.data, prob.ctypes.data, None if dec is None else dec.ctypes.data),
                'ts2d_probabilities_from_logits')
@@ -668,10 +682,7 @@ def probabilities_from_logits(logits_f16: np.ndarray, rect, out_hw, full_hw, box
 def has_keep_largest_components() -> bool:
     """Does the engine library have ``ts2d_keep_largest_components``?  False with no library built, one that does not load, or one built
     before the entry: the callers keep the host route (postprocess.apply_postprocessing)."""
-    try:
-        return hasattr(_lib.load(), 'ts2d_keep_largest_components')
-    except _lib.EngineLibraryError:
-        return False
+    return has_entry('ts2d_keep_largest_components')
 
 
 def keep_largest_components(seg: np.ndarray, tables, backgrounds, device: int = 0):
@@ -683,9 +694,7 @@ def keep_largest_components(seg: np.ndarray, tables, backgrounds, device: int = 
     src = np.asarray(seg)
     if src.dtype != np.uint8 or src.ndim not in (2, 3):
         raise RuntimeError(f"keep_largest_components: expected uint8 [Z,H,W] or [H,W], found {src.dtype} {src.shape}")
-    lib = _lib.load()
-    if not hasattr(lib, 'ts2d_keep_largest_components'):
-        raise RuntimeError("ts2d_keep_largest_components: this libts2d_engine.so was built before the entry; rebuild it, or keep the host route")
+    fn = _entry('ts2d_keep_largest_components')
     out = np.array(src, dtype=np.uint8, order='C')            # (a copy: the entry works in place)
     z, h, w = ((1,) + out.shape)[-3:]
     n = len(tables)
@@ -698,18 +707,11 @@ def keep_largest_components(seg: np.ndarray, tables, backgrounds, device: int = 
         steps[k].background = int(backgrounds[k])
     stats = np.zeros((n, 4), dtype=np.int64)
     status = ctypes.c_int(0)
-    _lib.check(lib.ts2d_keep_largest_components(int(device), out.ctypes.data, z, h, w, ctypes.cast(steps, ctypes.c_void_p), n, stats.ctypes.data,
+    _lib.check(fn(int(device), out.ctypes.data, z, h, w, ctypes.cast(steps, ctypes.c_void_p), n, stats.ctypes.data,
                                                 ctypes.byref(status)), 'ts2d_keep_largest_components')
     if status.value:
         return None, None, int(status.value)
     return out, stats, 0
-
-
-def _visual_entry(name: str):
-    lib = _lib.load()
-    if not hasattr(lib, name):
-        raise RuntimeError(f"{name}: this libts2d_engine.so was built before the entry; rebuild it, or keep the host route")
-    return getattr(lib, name)
 
 
 def visual_labels(planes: np.ndarray, spacing_hw, palette: np.ndarray, out_hw, device: int = 0) -> np.ndarray:
@@ -724,7 +726,7 @@ def visual_labels(planes: np.ndarray, spacing_hw, palette: np.ndarray, out_hw, d
     k, h, w = src.shape
     oh, ow = int(out_hw[0]), int(out_hw[1])
     out = np.empty((max(oh, 0), max(ow, 0), 3), np.uint8)
-    _lib.check(_visual_entry('ts2d_visual_labels')(int(device), src.ctypes.data, k, h, w, float(spacing_hw[0]), float(spacing_hw[1]), pal.ctypes.data,
+    _lib.check(_entry('ts2d_visual_labels')(int(device), src.ctypes.data, k, h, w, float(spacing_hw[0]), float(spacing_hw[1]), pal.ctypes.data,
                                                   pal.shape[0], oh, ow, out.ctypes.data), 'ts2d_visual_labels')
     return out
 
@@ -742,7 +744,7 @@ def visual_grey(plane: np.ndarray, spacing_hw, cubic: bool, lo, hi, out_hw, devi
     out = np.empty((max(oh, 0), max(ow, 0)), np.uint8)
     used = np.zeros(2, np.float64)
     status = ctypes.c_int(0)
-    _lib.check(_visual_entry('ts2d_visual_grey')(int(device), src.ctypes.data, DEVICE_DTYPES[src.dtype.name], src.shape[0], src.shape[1],
+    _lib.check(_entry('ts2d_visual_grey')(int(device), src.ctypes.data, DEVICE_DTYPES[src.dtype.name], src.shape[0], src.shape[1],
                                                 float(spacing_hw[0]), float(spacing_hw[1]), 1 if cubic else 0, 0.0 if lo is None else float(lo),
                                                 0.0 if hi is None else float(hi), int(lo is None), int(hi is None), oh, ow, out.ctypes.data,
                                                 used.ctypes.data, ctypes.byref(status)), 'ts2d_visual_grey')
@@ -757,9 +759,7 @@ def label_statistics(seg: np.ndarray, kind: int, values, shape_zhw, intensities:
     [K, Z, H, W] (``kind`` = ``_lib.STATS_PLANES``) or one label map [Z, H, W] with ``values`` [K] (``_lib.STATS_LABELMAP``); ``intensities``:
     float32 [C, Z, H, W] or None.  Returns ``(int64 [K, 10], float64 [K, C, 6])`` in the layout of include/ts2d_engine.h - the statement's
     numbers bit for bit - or None where the entry set a status bit (a non-finite intensity under a label): the caller takes the host route."""
-    lib = _lib.load()
-    if not hasattr(lib, 'ts2d_label_statistics'):
-        raise RuntimeError("ts2d_label_statistics: this libts2d_engine.so was built before the entry; rebuild it, or keep the host route")
+    fn = _entry('ts2d_label_statistics')
     z, h, w = (int(v) for v in shape_zhw)
     if seg.dtype != np.uint8 or not seg.flags['C_CONTIGUOUS']:
         raise RuntimeError(f"label_statistics: expected a C-contiguous uint8 segmentation, found {seg.dtype} {seg.shape}")
@@ -781,7 +781,7 @@ def label_statistics(seg: np.ndarray, kind: int, values, shape_zhw, intensities:
     out_int = np.zeros((k, _lib.STATS_INTS), np.int64)
     out_f64 = np.zeros((k, c, _lib.STATS_F64S), np.float64)
     status = ctypes.c_int(0)
-    _lib.check(lib.ts2d_label_statistics(int(device), seg.ctypes.data, int(kind), vals.ctypes.data if vals is not None else None, k, z, h, w,
+    _lib.check(fn(int(device), seg.ctypes.data, int(kind), vals.ctypes.data if vals is not None else None, k, z, h, w,
                                          intensities.ctypes.data if c else None, c, int(max_scratch_bytes), out_int.ctypes.data,
                                          out_f64.ctypes.data if c else None, ctypes.byref(status)), 'ts2d_label_statistics')
     if status.value:
@@ -789,19 +789,12 @@ def label_statistics(seg: np.ndarray, kind: int, values, shape_zhw, intensities:
     return out_int, out_f64
 
 
-def _evaluate_entry(name: str):
-    lib = _lib.load()
-    if not hasattr(lib, name):
-        raise RuntimeError(f"{name}: this libts2d_engine.so was built before the entry; rebuild it, or keep the host route")
-    return getattr(lib, name)
-
-
 def project_labels_coronal(buffer: np.ndarray, extents, strides, base: int, num: int, device: int = 0):
     """The label projection on the device (C-ABI ts2d_project_labels_coronal, csrc/kernels_evaluate.h).  ``buffer``: the volume's C-contiguous
     integer samples; ``extents`` (nz, ny, nx), ``strides`` (sz, sy, sx) and ``base`` in elements: the reoriented view of
     ``image._coronal_view``.  Returns ``(uint8 [num, nz, nx], status)``; with a status bit (``_lib.LABELS_RANGE``) the planes are no result."""
     from .image import _GPU_DTYPES
-    fn = _evaluate_entry('ts2d_project_labels_coronal')
+    fn = _entry('ts2d_project_labels_coronal')
     if buffer.dtype.name not in _GPU_DTYPES or not np.issubdtype(buffer.dtype, np.integer) or not buffer.flags['C_CONTIGUOUS']:
         raise RuntimeError(f"project_labels_coronal: expected a C-contiguous int16, uint8, uint16 or int32 volume, found {buffer.dtype}")
     nz, ny, nx = (int(v) for v in extents)
@@ -831,7 +824,7 @@ def _evaluate_sides(what: str, a: np.ndarray, kind_a: int, b: np.ndarray, kind_b
 def label_overlap(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, shape_zhw, device: int = 0) -> np.ndarray:
     """The overlap counts on the device (C-ABI ts2d_label_overlap).  ``a``, ``b``: C-contiguous uint8, each planes [K, Z, H, W]
     (``_lib.STATS_PLANES``) or one label map [Z, H, W] with ``values`` [K] (``_lib.STATS_LABELMAP``).  Returns int64 [K, 3] = n_a, n_b, n_both."""
-    fn = _evaluate_entry('ts2d_label_overlap')
+    fn = _entry('ts2d_label_overlap')
     z, h, w = (int(v) for v in shape_zhw)
     k, vals = _evaluate_sides('label_overlap', a, kind_a, b, kind_b, values, z * h * w)
     out = np.zeros((k, 3), np.int64)
@@ -840,20 +833,28 @@ def label_overlap(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values
     return out
 
 
-def surface_distances(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, shape_hw, spacing_hw, tol_sq, max_scratch_bytes: int = 0,
-                      device: int = 0):
-    """The boundary distances of 2-D planes on the device (C-ABI ts2d_surface_distances).  ``a``, ``b`` as in :func:`label_overlap` with Z = 1;
-    ``tol_sq``: the squared tolerances, float64 [T].  Returns ``(int64 [K, 2, 1 + T], float64 [K, 2])`` in the layout of include/ts2d_engine.h."""
-    fn = _evaluate_entry('ts2d_surface_distances')
+def _surface_call(what: str, a, kind_a, b, kind_b, values, shape_hw, spacing_hw, tol_sq, device):
+    """What the two boundary-distance wrappers prepare alike for the entry ``ts2d_<what>``: ``(entry, its arguments up to T, K, out_i, out_f,
+    the arrays those arguments point into)``."""
+    fn = _entry('ts2d_' + what)
     h, w = (int(v) for v in shape_hw)
-    k, vals = _evaluate_sides('surface_distances', a, kind_a, b, kind_b, values, h * w)
+    k, vals = _evaluate_sides(what, a, kind_a, b, kind_b, values, h * w)
     tol = np.ascontiguousarray(tol_sq, dtype=np.float64)
     t = int(tol.size)
     out_i = np.zeros((k, 2, 1 + t), np.int64)
     out_f = np.zeros((k, 2), np.float64)
-    _lib.check(fn(int(device), a.ctypes.data, int(kind_a), b.ctypes.data, int(kind_b), vals.ctypes.data if vals is not None else None, k, h, w,
-                  float(spacing_hw[0]), float(spacing_hw[1]), tol.ctypes.data if t else None, t, int(max_scratch_bytes), out_i.ctypes.data,
-                  out_f.ctypes.data), 'ts2d_surface_distances')
+    head = (int(device), a.ctypes.data, int(kind_a), b.ctypes.data, int(kind_b), vals.ctypes.data if vals is not None else None, k, h, w,
+            float(spacing_hw[0]), float(spacing_hw[1]), tol.ctypes.data if t else None, t)
+    return fn, head, k, out_i, out_f, (vals, tol)
+
+
+def surface_distances(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, shape_hw, spacing_hw, tol_sq, max_scratch_bytes: int = 0,
+                      device: int = 0):
+    """The boundary distances of 2-D planes on the device (C-ABI ts2d_surface_distances).  ``a``, ``b`` as in :func:`label_overlap` with Z = 1;
+    ``tol_sq``: the squared tolerances, float64 [T].  Returns ``(int64 [K, 2, 1 + T], float64 [K, 2])`` in the layout of include/ts2d_engine.h."""
+    fn, head, _, out_i, out_f, keep = _surface_call('surface_distances', a, kind_a, b, kind_b, values, shape_hw, spacing_hw, tol_sq, device)
+    _lib.check(fn(*head, int(max_scratch_bytes), out_i.ctypes.data, out_f.ctypes.data), 'ts2d_surface_distances')
+    del keep
     return out_i, out_f
 
 
@@ -869,22 +870,16 @@ def surface_distance_profile(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: 
     """:func:`surface_distances` and the distance profile in one call (C-ABI ts2d_surface_distance_profile).  ``percentiles``: float64 [P] in
     0 ... 100.  Returns ``(int64 [K, 2, 1 + T], float64 [K, 2], sums float64 [K, 2] or None, ranks float64 [K, 2, P, 2], weights float64
     [K, 2, P])`` in the layout of include/ts2d_engine.h."""
-    fn = _evaluate_entry('ts2d_surface_distance_profile')
-    h, w = (int(v) for v in shape_hw)
-    k, vals = _evaluate_sides('surface_distance_profile', a, kind_a, b, kind_b, values, h * w)
-    tol = np.ascontiguousarray(tol_sq, dtype=np.float64)
+    fn, head, k, out_i, out_f, keep = _surface_call('surface_distance_profile', a, kind_a, b, kind_b, values, shape_hw, spacing_hw, tol_sq, device)
     pct = np.ascontiguousarray(percentiles, dtype=np.float64)
-    t, p = int(tol.size), int(pct.size)
-    out_i = np.zeros((k, 2, 1 + t), np.int64)
-    out_f = np.zeros((k, 2), np.float64)
+    p = int(pct.size)
     out_sum = np.zeros((k, 2), np.float64) if want_sum else None
     out_rank = np.zeros((k, 2, p, 2), np.float64)
     out_weight = np.zeros((k, 2, p), np.float64)
-    _lib.check(fn(int(device), a.ctypes.data, int(kind_a), b.ctypes.data, int(kind_b), vals.ctypes.data if vals is not None else None, k, h, w,
-                  float(spacing_hw[0]), float(spacing_hw[1]), tol.ctypes.data if t else None, t, pct.ctypes.data if p else None, p,
-                  1 if want_sum else 0, int(max_scratch_bytes), out_i.ctypes.data, out_f.ctypes.data,
+    _lib.check(fn(*head, pct.ctypes.data if p else None, p, 1 if want_sum else 0, int(max_scratch_bytes), out_i.ctypes.data, out_f.ctypes.data,
                   out_sum.ctypes.data if want_sum else None, out_rank.ctypes.data if p else None, out_weight.ctypes.data if p else None),
                'ts2d_surface_distance_profile')
+    del keep
     return out_i, out_f, out_sum, out_rank, out_weight
 
 

@@ -3,7 +3,8 @@
 
 The functions ``*_statement`` and :func:`project_labels` are the project's definition - written in numpy, they are the host route and the
 oracle of the device route (C-ABI ``ts2d_project_labels_coronal``, ``ts2d_label_overlap``, ``ts2d_surface_distances``,
-``ts2d_surface_distance_profile``; ``csrc/kernels_evaluate.h``, ``csrc/kernels_evaluate_profile.h``), which reproduces them bit for bit, as
+``ts2d_surface_distance_profile`` - the two are one path, the first the second without its extras -; ``csrc/kernels_evaluate.h``,
+``csrc/kernels_evaluate_profile.h``), which reproduces them bit for bit, as
 ``statistics.py``, ``visual.py`` and ``postprocess.py`` are for their entries.
 
 LABEL PROJECTION.  TotalSegmentator 2D is trained and evaluated on 3-D label volumes projected into one binary plane per label: the reference's
@@ -93,14 +94,11 @@ def _planes_image(planes: np.ndarray, like: Image, spacing=None, origin=None, di
 def device_projects(img: Image) -> bool:
     """Does ``ts2d_project_labels_coronal`` serve the volume?  A scalar 3-D volume of an integer type of the device projection, and a library that
     has the symbol."""
-    from . import _lib
+    from . import engine
     from .image import _GPU_DTYPES
     if img.dimension != 3 or img.components != 1 or img.array.dtype.name not in _GPU_DTYPES or not np.issubdtype(img.array.dtype, np.integer):
         return False
-    try:
-        return hasattr(_lib.load(), 'ts2d_project_labels_coronal')
-    except Exception:
-        return False
+    return engine.has_entry('ts2d_project_labels_coronal')
 
 
 def project_labels_coronal_gpu(img: Image, num: int, device: int = 0) -> Image:
@@ -191,38 +189,6 @@ def d2_from_rows(border_a: np.ndarray, g_b: np.ndarray, spacing_hw) -> np.ndarra
     return out
 
 
-def surface_statement(a, kind_a: int, b, kind_b: int, values, spacing_hw, tolerances: Sequence[float]) -> dict:
-    """THE DEFINITION of the boundary distances of 2-D planes (module docstring).  ``a``, ``b``: planes ``[K, 1, H, W]`` / ``[K, H, W]`` or label
-    maps ``[1, H, W]`` / ``[H, W]``; a volume (``Z > 1``) raises ``ValueError``.  ``spacing_hw``: (mm per row, mm per column).
-
-    Returns over the K labels and the two directions (0: A to B, 1: B to A): ``border`` int64 [K, 2] (the border pixels of the direction's own
-    side), ``d2_max`` float64 [K, 2] (``-inf`` for an empty border, ``+inf`` where the other side has none) and ``within`` int64 [K, 2, T]: per
-    tolerance ``t`` (mm) the border pixels with ``d2 <= t * t``, the square taken once in float64."""
-    a, b, spatial, K = _sides(a, kind_a, b, kind_b, values)
-    if len(spatial) == 3 and spatial[0] == 1:
-        spatial = spatial[1:]
-        a = a.reshape((K,) + spatial if kind_a == PLANES else spatial)
-        b = b.reshape((K,) + spatial if kind_b == PLANES else spatial)
-    if len(spatial) != 2:
-        raise ValueError(f"surface_statement: boundary distances are defined for 2-D planes, found the extent {tuple(spatial)}")
-    tol = np.asarray(list(tolerances), np.float64)
-    tol_sq = tol * tol
-    T = len(tol)
-    out = {'border': np.zeros((K, 2), np.int64), 'd2_max': np.full((K, 2), -np.inf, np.float64), 'within': np.zeros((K, 2, T), np.int64)}
-    for k in range(K):
-        ba, bb = border_of(_mask(a, kind_a, values, k)), border_of(_mask(b, kind_b, values, k))
-        for d, (own, other) in enumerate(((ba, bb), (bb, ba))):
-            n = int(np.count_nonzero(own))
-            out['border'][k, d] = n
-            if n == 0:
-                continue
-            d2 = d2_from_rows(own, row_distance(other), spacing_hw)
-            out['d2_max'][k, d] = d2.max()
-            for t in range(T):
-                out['within'][k, d, t] = np.count_nonzero(d2 <= tol_sq[t])
-    return out
-
-
 def _percentiles(percentiles, who: str) -> list:
     qs = [float(q) for q in percentiles]
     if len(qs) > MAX_PERCENTILES or any(not (math.isfinite(q) and 0.0 <= q <= 100.0) for q in qs):
@@ -251,6 +217,59 @@ def percentile_of_ranks(d2_i, d2_j, t) -> np.float64:
     return hi - (hi - lo) * (np.float64(1) - t)
 
 
+def _distance_walk(who: str, a, kind_a: int, b, kind_b: int, values, spacing_hw, tolerances: Sequence[float], qs: Optional[list]) -> dict:
+    """The ONE walk over the labels and the two directions behind :func:`surface_statement` (``qs`` None: border, d2_max, within, and neither a
+    root nor a sort is taken) and :func:`distance_profile_statement` (``qs`` the checked percentiles: also dist_sum, d2_rank, rank_weight)."""
+    a, b, spatial, K = _sides(a, kind_a, b, kind_b, values)
+    if len(spatial) == 3 and spatial[0] == 1:
+        spatial = spatial[1:]
+        a = a.reshape((K,) + spatial if kind_a == PLANES else spatial)
+        b = b.reshape((K,) + spatial if kind_b == PLANES else spatial)
+    if len(spatial) != 2:
+        raise ValueError(f"{who}: boundary distances are defined for 2-D planes, found the extent {tuple(spatial)}")
+    tol = np.asarray(list(tolerances), np.float64)
+    tol_sq = tol * tol
+    T = len(tol)
+    out = {'border': np.zeros((K, 2), np.int64), 'd2_max': np.full((K, 2), -np.inf, np.float64), 'within': np.zeros((K, 2, T), np.int64)}
+    if qs is not None:
+        from .statistics import tree_sum
+        P = len(qs)
+        out.update(dist_sum=np.zeros((K, 2), np.float64), d2_rank=np.full((K, 2, P, 2), -np.inf, np.float64),
+                   rank_weight=np.zeros((K, 2, P), np.float64))
+    for k in range(K):
+        ba, bb = border_of(_mask(a, kind_a, values, k)), border_of(_mask(b, kind_b, values, k))
+        for d, (own, other) in enumerate(((ba, bb), (bb, ba))):
+            n = int(np.count_nonzero(own))
+            out['border'][k, d] = n
+            if n == 0:
+                continue
+            d2 = d2_from_rows(own, row_distance(other), spacing_hw)
+            out['d2_max'][k, d] = d2.max()
+            for t in range(T):
+                out['within'][k, d, t] = np.count_nonzero(d2 <= tol_sq[t])
+            if qs is None:
+                continue
+            terms = np.zeros(spatial, np.float64)
+            terms[own] = np.sqrt(d2)                                                     # (np.nonzero order on both sides)
+            out['dist_sum'][k, d] = tree_sum(terms)
+            ordered = np.sort(d2)
+            for p, q in enumerate(qs):
+                i, j, t = percentile_ranks(n, q)
+                out['d2_rank'][k, d, p] = ordered[i], ordered[j]
+                out['rank_weight'][k, d, p] = t
+    return out
+
+
+def surface_statement(a, kind_a: int, b, kind_b: int, values, spacing_hw, tolerances: Sequence[float]) -> dict:
+    """THE DEFINITION of the boundary distances of 2-D planes (module docstring).  ``a``, ``b``: planes ``[K, 1, H, W]`` / ``[K, H, W]`` or label
+    maps ``[1, H, W]`` / ``[H, W]``; a volume (``Z > 1``) raises ``ValueError``.  ``spacing_hw``: (mm per row, mm per column).
+
+    Returns over the K labels and the two directions (0: A to B, 1: B to A): ``border`` int64 [K, 2] (the border pixels of the direction's own
+    side), ``d2_max`` float64 [K, 2] (``-inf`` for an empty border, ``+inf`` where the other side has none) and ``within`` int64 [K, 2, T]: per
+    tolerance ``t`` (mm) the border pixels with ``d2 <= t * t``, the square taken once in float64."""
+    return _distance_walk('surface_statement', a, kind_a, b, kind_b, values, spacing_hw, tolerances, None)
+
+
 def distance_profile_statement(a, kind_a: int, b, kind_b: int, values, spacing_hw, tolerances: Sequence[float], percentiles: Sequence[float]) -> dict:
     """THE DEFINITION of the distance profile: the inputs, the refusals and the results of :func:`surface_statement` (the same bits), and over
     the K labels and the two directions
@@ -263,59 +282,22 @@ def distance_profile_statement(a, kind_a: int, b, kind_b: int, values, spacing_h
 
     The root is monotone, so the order statistics of the distances are the roots of those of ``d2``: :func:`percentile_of_ranks` makes the
     percentile of the two."""
-    from .statistics import tree_sum
-    qs = _percentiles(percentiles, 'distance_profile_statement')
-    a, b, spatial, K = _sides(a, kind_a, b, kind_b, values)
-    if len(spatial) == 3 and spatial[0] == 1:
-        spatial = spatial[1:]
-        a = a.reshape((K,) + spatial if kind_a == PLANES else spatial)
-        b = b.reshape((K,) + spatial if kind_b == PLANES else spatial)
-    if len(spatial) != 2:
-        raise ValueError(f"distance_profile_statement: boundary distances are defined for 2-D planes, found the extent {tuple(spatial)}")
-    tol = np.asarray(list(tolerances), np.float64)
-    tol_sq = tol * tol
-    T, P = len(tol), len(qs)
-    out = {'border': np.zeros((K, 2), np.int64), 'd2_max': np.full((K, 2), -np.inf, np.float64), 'within': np.zeros((K, 2, T), np.int64),
-           'dist_sum': np.zeros((K, 2), np.float64), 'd2_rank': np.full((K, 2, P, 2), -np.inf, np.float64),
-           'rank_weight': np.zeros((K, 2, P), np.float64)}
-    for k in range(K):
-        ba, bb = border_of(_mask(a, kind_a, values, k)), border_of(_mask(b, kind_b, values, k))
-        for d, (own, other) in enumerate(((ba, bb), (bb, ba))):
-            n = int(np.count_nonzero(own))
-            out['border'][k, d] = n
-            if n == 0:
-                continue
-            d2 = d2_from_rows(own, row_distance(other), spacing_hw)                      # (the walk of surface_statement up to here)
-            out['d2_max'][k, d] = d2.max()
-            for t in range(T):
-                out['within'][k, d, t] = np.count_nonzero(d2 <= tol_sq[t])
-            terms = np.zeros(spatial, np.float64)
-            terms[own] = np.sqrt(d2)                                                     # (np.nonzero order on both sides)
-            out['dist_sum'][k, d] = tree_sum(terms)
-            ordered = np.sort(d2)
-            for p, q in enumerate(qs):
-                i, j, t = percentile_ranks(n, q)
-                out['d2_rank'][k, d, p] = ordered[i], ordered[j]
-                out['rank_weight'][k, d, p] = t
-    return out
+    return _distance_walk('distance_profile_statement', a, kind_a, b, kind_b, values, spacing_hw, tolerances,
+                          _percentiles(percentiles, 'distance_profile_statement'))
 
 
 # ------------------------------------------------------------------------------------------------------------------ the device route
 def device_serves(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, spatial, K: int) -> bool:
     """Do ``ts2d_label_overlap`` and ``ts2d_surface_distances`` serve the case?  uint8 samples, 1 ... 255 labels (label-map values 1 ... 255), at
     most 2^31 - 1 samples, and a library that has the symbols."""
-    from . import _lib
+    from . import engine
     if a.dtype != np.uint8 or b.dtype != np.uint8 or not 1 <= K <= 255:
         return False
     if min(spatial, default=0) < 1 or int(np.prod(spatial, dtype=np.int64)) > 2 ** 31 - 1:
         return False
     if LABELMAP in (kind_a, kind_b) and not all(1 <= int(v) <= 255 for v in values):
         return False
-    try:
-        lib = _lib.load()
-        return hasattr(lib, 'ts2d_label_overlap') and hasattr(lib, 'ts2d_surface_distances')
-    except Exception:
-        return False
+    return engine.has_entry('ts2d_label_overlap', 'ts2d_surface_distances')
 
 
 def _device_overlap(a, kind_a, b, kind_b, values, spatial, device: int) -> dict:
@@ -325,34 +307,37 @@ def _device_overlap(a, kind_a, b, kind_b, values, spatial, device: int) -> dict:
     return {'n_a': o[:, 0].copy(), 'n_b': o[:, 1].copy(), 'n_both': o[:, 2].copy()}
 
 
-def _device_surface(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, device: int, max_scratch_bytes: int = 0) -> dict:
-    from . import engine
-    tol = np.asarray(list(tolerances), np.float64)
-    oi, of = engine.surface_distances(np.ascontiguousarray(a), kind_a, np.ascontiguousarray(b), kind_b, values, hw, spacing_hw, tol * tol,
-                                      max_scratch_bytes, device)
-    return {'border': oi[:, :, 0].copy(), 'd2_max': of, 'within': oi[:, :, 1:].copy()}
-
-
 def device_profiles() -> bool:
     """Does the library have ``ts2d_surface_distance_profile``?  (It serves what :func:`device_serves` serves.)"""
-    from . import _lib
-    try:
-        return hasattr(_lib.load(), 'ts2d_surface_distance_profile')
-    except Exception:
-        return False
+    from . import engine
+    return engine.has_entry('ts2d_surface_distance_profile')
+
+
+def _device_distances(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, percentiles, want_sum: bool, device: int,
+                      max_scratch_bytes: int = 0) -> dict:
+    """The statements on the device, as :func:`_distance_walk` has them: ``percentiles`` None - :func:`surface_statement` by
+    ``ts2d_surface_distances``; a list - :func:`distance_profile_statement` by ``ts2d_surface_distance_profile``, ``dist_sum`` only with
+    ``want_sum``."""
+    from . import engine
+    tol = np.asarray(list(tolerances), np.float64)
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if percentiles is None:
+        oi, of = engine.surface_distances(a, kind_a, b, kind_b, values, hw, spacing_hw, tol * tol, max_scratch_bytes, device)
+        extras = {}
+    else:
+        oi, of, osum, orank, oweight = engine.surface_distance_profile(a, kind_a, b, kind_b, values, hw, spacing_hw, tol * tol, list(percentiles),
+                                                                       want_sum, max_scratch_bytes, device)
+        extras = dict({'d2_rank': orank, 'rank_weight': oweight}, **({'dist_sum': osum} if want_sum else {}))
+    return dict({'border': oi[:, :, 0].copy(), 'd2_max': of, 'within': oi[:, :, 1:].copy()}, **extras)
+
+
+def _device_surface(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, device: int, max_scratch_bytes: int = 0) -> dict:
+    return _device_distances(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, None, False, device, max_scratch_bytes)
 
 
 def _device_profile(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, percentiles, want_sum: bool, device: int,
                     max_scratch_bytes: int = 0) -> dict:
-    """:func:`distance_profile_statement` on the device; ``dist_sum`` only with ``want_sum``."""
-    from . import engine
-    tol = np.asarray(list(tolerances), np.float64)
-    oi, of, osum, orank, oweight = engine.surface_distance_profile(np.ascontiguousarray(a), kind_a, np.ascontiguousarray(b), kind_b, values, hw,
-                                                                   spacing_hw, tol * tol, list(percentiles), want_sum, max_scratch_bytes, device)
-    out = {'border': oi[:, :, 0].copy(), 'd2_max': of, 'within': oi[:, :, 1:].copy(), 'd2_rank': orank, 'rank_weight': oweight}
-    if want_sum:
-        out['dist_sum'] = osum
-    return out
+    return _device_distances(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, list(percentiles), want_sum, device, max_scratch_bytes)
 
 
 # ------------------------------------------------------------------------------------------------------------------ evaluate
@@ -452,14 +437,11 @@ def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: 
     if flat:
         a2 = a.reshape(((K,) if kind_a == PLANES else ()) + hw)
         b2 = b.reshape(((K,) if kind_b == PLANES else ()) + hw)
-        if profile and on_device and device_profiles():
-            sf = _device_profile(a2, kind_a, b2, kind_b, vals, hw, flat[1], tolerances, percentiles, bool(average_distance), int(device))
-        elif profile:
-            sf = distance_profile_statement(a2, kind_a, b2, kind_b, vals, flat[1], tolerances, percentiles)
-        elif on_device:
-            sf = _device_surface(a2, kind_a, b2, kind_b, vals, hw, flat[1], tolerances, int(device))
+        qs = percentiles if profile else None                                            # the ONE decision "profile or not", for either route
+        if on_device and (qs is None or device_profiles()):
+            sf = _device_distances(a2, kind_a, b2, kind_b, vals, hw, flat[1], tolerances, qs, bool(average_distance), int(device))
         else:
-            sf = surface_statement(a2, kind_a, b2, kind_b, vals, flat[1], tolerances)
+            sf = _distance_walk('evaluate', a2, kind_a, b2, kind_b, vals, flat[1], tolerances, qs)
     mm = np.float64(np.prod(np.asarray(pred.spacing, dtype=np.float64)))
     mm_ref = np.float64(np.prod(np.asarray(ref.spacing, dtype=np.float64)))
     for k, (name, info) in enumerate(names.items()):

@@ -221,7 +221,7 @@ def project_coronal_gpu(img: Image, device: int = 0, zscore: bool = False, modes
     ``cast(project(reorient_image(img), name, 'coronal'), float32)`` - and with ``zscore=True`` ``'zscore'`` =
     ``{name: {'norm': [nz, nx] float32, 'stats': (mean, std), 'box': that plane's own non-zero box, 'shape': (nz, nx)}}``.  Raises
     :class:`ProjectionDeviceRefused` when the entry sets a status bit."""
-    from . import _lib
+    from . import _lib, engine
     if img.dimension != 3 or img.components != 1 or img.array.dtype.name not in _GPU_DTYPES:
         raise RuntimeError(f"GPU projection needs a scalar 3-D volume of type {sorted(_GPU_DTYPES)}, found {img.array.dtype}")
     a, (nz, ny, nx), (sz, sy, sx), base, perm, flips = _coronal_view(img)
@@ -233,7 +233,7 @@ def project_coronal_gpu(img: Image, device: int = 0, zscore: bool = False, modes
         plan = [device_projection_mode(m, ny) for m in names]
         if not names or any(p is None for p in plan):
             raise RuntimeError(f"GPU projection does not serve the modes {[m for m, p in zip(names, plan) if p is None] or names}")
-        if not hasattr(lib, 'ts2d_project_coronal_modes'):
+        if not engine.has_entry('ts2d_project_coronal_modes'):
             raise RuntimeError("ts2d_project_coronal_modes is missing from the engine library (built before the projection modes)")
         codes = np.array([p[0] for p in plan], np.int32); sidx = np.array([p[1] for p in plan], np.int32)
         M = len(names)

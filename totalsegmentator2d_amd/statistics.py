@@ -177,10 +177,8 @@ def device_serves(planes: np.ndarray, values, spatial, C: int) -> bool:
         return False
     if values is not None and not all(1 <= int(v) <= 255 for v in values):
         return False
-    try:
-        return hasattr(_lib.load(), 'ts2d_label_statistics')
-    except Exception:
-        return False
+    from . import engine
+    return engine.has_entry('ts2d_label_statistics')
 
 
 def _array_of(img) -> np.ndarray:

@@ -262,9 +262,9 @@ class TS2D:
         has no device-normalised plane of yet (``cache['device_zscore_planes']``, shared by name across the sub-models like the projections).
         False - nothing taken - when a name is no device mode, the entry is missing, or it refused the volume (a non-finite sample, rays above
         the cap): the whole case then stays on the host branch."""
-        from . import _lib
+        from . import _lib, engine
         from .image import ProjectionDeviceRefused, _reorient_plan, device_projection_mode, project_coronal_gpu
-        if cache.get('host_projection') or not hasattr(_lib.load(), 'ts2d_project_coronal_modes') or input.dimension != 3:
+        if cache.get('host_projection') or not engine.has_entry('ts2d_project_coronal_modes', tolerant=False) or input.dimension != 3:
             return False
         planes = cache.setdefault('device_zscore_planes', {})
         want = list(dict.fromkeys(n for _, n in channels if n not in planes))

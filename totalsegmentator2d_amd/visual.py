@@ -292,12 +292,8 @@ def _grey_statement(plane: np.ndarray, spacing_hw, window) -> np.ndarray:
 
 
 def _device_entries():
-    from . import _lib
-    try:
-        lib = _lib.load()
-    except _lib.EngineLibraryError:
-        return None
-    return lib if hasattr(lib, 'ts2d_visual_labels') and hasattr(lib, 'ts2d_visual_grey') else None
+    from . import _lib, engine
+    return _lib.load() if engine.has_entry('ts2d_visual_labels', 'ts2d_visual_grey') else None
 
 
 def _device_geometry(shape, spacing_hw):
