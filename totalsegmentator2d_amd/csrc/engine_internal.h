@@ -267,28 +267,50 @@ struct SwPlan {
     // scratch: [table | gaussian | images | one chunk's batch | tile logits | half outputs x F | uint8 outputs | flags x F | resampled uint8 (or label maps, or decided maps) | resampled float | probabilities]
     size_t o_tab = 0, o_g = 0, o_imgs = 0, o_batch = 0, o_log = 0, o_o16 = 0, o_seg = 0, o_flag = 0, o_rs8 = 0, o_rs32 = 0, o_prob = 0, bytes = 0;
 };
-// a probabilities call (ts2d_ensemble_predict_tiled_probabilities): its descriptors and its mode (ProbMode = TS2D_PROB_*)
-// `runs` (ts2d_ensemble_predict_tiled_probabilities_stack; else null): the outputs are those of the runs - `descs` is then the entry's own
-// per-image expansion of them (the geometry and the slice's place in the caller's arrays), run_of[i] the run of image i (named in a message);
-// the entry has checked that the runs cover the images once, in order, and that a run's images share (Hp, Wp)
-struct ProbCall {
-    const ts2d_tiled_probabilities* descs; int mode;
-    const ts2d_tiled_probabilities_run* runs = nullptr; int n_runs = 0; const int* run_of = nullptr;
+// The TAIL of a sliding-window call: what becomes of the aggregated half logits (the mean's, of an ensemble) behind the last sw_aggregate
+// or sw_fold_mean.  One kernel per kind, then that kind's device-to-host copies (tiled.hip: run_tail):
+//   kNone        nothing: the padded outputs of the images are the call's results
+//   kExport      sw_resample_threshold: K uint8 and / or K float planes [out_h, out_w] per image (u8 = seg_u8, f32 = logits_f32)
+//   kLabelmap    sw_labelmap: ONE uint8 plane per image (u8 = label_u8)
+//   kRegions     sw_regions: the same plan and plane, painted by `class_order`, which rides in the table blob at tab_order
+//   kProb        sw_probabilities<ProbSeg>: K float planes of the pre-crop extent per image (f32 = prob_f32), the decided map beside them (u8 =
+//                decided_u8, or null); `mode` is a ProbMode = TS2D_PROB_* and `class_order` that of its regions mode (else null); a segment's
+//                lanes walk the full extent and the ProbSegs go behind the class order at tab_psegs
+//   kProbRuns    sw_probabilities<ProbStackSeg>: the outputs are those of `runs` of slices, head-major in the caller's strided volumes; `images`
+//                is the entry's per-image expansion of them (a run's geometry, the slice's place in the caller's arrays) and run_of[i] the run of
+//                image i.  The entry has checked that the runs cover the images once, in order, and that a run's images share (Hp, Wp).
+struct SwTail {
+    enum Kind { kNone, kExport, kLabelmap, kRegions, kProb, kProbRuns };
+    struct Image { int src_y, src_x, src_h, src_w, out_h, out_w, full_h, full_w, box_y, box_x; uint8_t* u8; float* f32; };
+    Kind kind = kNone;
+    std::vector<Image> images;              // one per image of the call (kNone: none)
+    int mode = 0; const uint8_t* class_order = nullptr;
+    const ts2d_tiled_probabilities_run* runs = nullptr; int n_runs = 0; std::vector<int> run_of;
+
+    SwTail() = default;
+    SwTail(Kind k, int n_images) : kind(k), images((size_t)n_images, Image{}) {}
+    bool prob() const { return kind == kProb || kind == kProbRuns; }
+    const char* what() const { return prob() ? "probabilities" : kind == kRegions ? "regions" : kind == kLabelmap ? "labelmap" : "export"; }      // in a message
+    int planes(int K) const { return kind == kExport ? K : 1; }         // of an image's resampled uint8 output
+    int decided_planes(int K) const { return mode == kProbMultilabel ? K : 1; }      // ... of its decided map (prob())
+    bool no_output(const Image& t) const { return kind == kExport ? !t.u8 && !t.f32 : prob() ? !t.f32 : !t.u8; }
+    // the six numbers every descriptor begins with (ts2d_tiled_export, _labelmap, _probabilities, _probabilities_run)
+    template <class D> static Image rect_of(const D& d, uint8_t* u8, float* f32) {
+        return Image{d.src_y, d.src_x, d.src_h, d.src_w, d.out_h, d.out_w, 0, 0, 0, 0, u8, f32};
+    }
+    template <class D> static Image full_of(const D& d, uint8_t* u8, float* f32) {      // ... and the four of a probabilities descriptor
+        Image t = rect_of(d, u8, f32);
+        t.full_h = d.full_h; t.full_w = d.full_w; t.box_y = d.box_y; t.box_x = d.box_x;
+        return t;
+    }
 };
-// `labelmap`: `exports` describe a label-map call (ts2d_ensemble_predict_tiled_labelmap: seg_u8 = the image's label_u8, ONE output plane)
-// `class_order` (with `labelmap`; else null): a region call (ts2d_ensemble_predict_tiled_regions) - the same plan, its descriptors named
-// "regions:" in a message, and the num_classes class values appended to the table blob at tab_order
-// `prob` (else null): a probabilities call - `exports` carry its geometry with `labelmap` set (seg_u8 = the image's prob_f32), `class_order`
-// is that of its regions mode (else null); the descriptors are named "probabilities:" in a message, a segment's lanes walk the full extent
-// and the ProbSegs go behind the class order at tab_psegs
-int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap,
-               const uint8_t* class_order, const ProbCall* prob, int n_images, int ph, int pw, int mirror_mask, bool name_images,
-               const char* entry, SwPlan* pl);
-// One image's segment and taps of the export's resample (checked extents): appended to rsegs / rtaps, `blocks` and `rs_elems` advanced.
-// src_off: elements to the image's [K, Hp, Wp] half planes.  (Also what ts2d_labelmap_from_logits and ts2d_regions_from_logits plan their one image with.)
-// full_hw (a probabilities segment; else null): the lanes walk this extent, 4 X each, and rs_elems is left alone (it may be null).
-void rs_plan_segment(bool labelmap, int K, int Hp, int Wp, const ts2d_tiled_export& ex, long long src_off, std::vector<RsSeg>* rsegs,
-                     std::vector<RsTap>* rtaps, long long* blocks, long long* rs_elems, const int* full_hw);
+int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const SwTail& tail, int n_images, int ph, int pw, int mirror_mask,
+               bool name_images, const char* entry, SwPlan* pl);
+// Image i's segment and taps of the tail's resample (checked extents): appended to rsegs / rtaps, `blocks` and `rs_elems` advanced.
+// src_off: elements to the image's [K, Hp, Wp] half planes.  (Also what the ts2d_*_from_logits entries plan their one image with.)
+// A probabilities segment: the lanes walk the full extent, 4 X each, and rs_elems is left alone (it may be null).
+void rs_plan_segment(const SwTail& tail, int i, int K, int Hp, int Wp, long long src_off, std::vector<RsSeg>* rsegs, std::vector<RsTap>* rtaps,
+                     long long* blocks, long long* rs_elems);
 
 // ---- prep_plan.cpp: the host arithmetic of the input side, bit for bit numpy's / scipy's
 // The host tables of one (in_h, in_w) -> (out_h, out_w) order-3 zoom and the layout of the scratch they go to: [coefficients | powers | taps]

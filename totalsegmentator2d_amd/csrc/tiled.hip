@@ -1,7 +1,8 @@
-// The sliding window of libts2d_engine.so: tile gather, aggregation, the mean of an ensemble's folds and the export's resample-back, around
-// the engine's forward (engine.hip: reserve_checked, run_forward).  The C entries ts2d_engine_predict_tiled*, ts2d_ensemble_predict_tiled_export,
-// ts2d_ensemble_predict_tiled_labelmap, ts2d_ensemble_predict_tiled_regions, ts2d_ensemble_predict_tiled_probabilities (and its _stack twin),
-// ts2d_labelmap_from_logits, ts2d_regions_from_logits and ts2d_probabilities_from_logits.
+// The sliding window of libts2d_engine.so: tile gather, aggregation, the mean of an ensemble's folds and the TAIL of a call (SwTail,
+// engine_internal.h: what becomes of the aggregated half logits - the export's resample-back, a label map, regions, probabilities), around
+// the engine's forward (engine.hip: reserve_checked, run_forward).  The C entries ts2d_engine_predict_tiled*, ts2d_ensemble_predict_tiled_*
+// (predict_tiled_impl, which runs the tail once: run_tail) and ts2d_{labelmap,regions,probabilities}_from_logits (tail_from_logits: the same
+// run_tail on half planes of the caller's).
 #include "engine_internal.h"
 #include "entry_util.h"
 #include "kernels_sw.h"
@@ -25,33 +26,77 @@ int name_fold(int rc, bool name_folds, int f) {
     return fail(rc, "fold %d: %s", f, msg.c_str());
 }
 
+// Where the tables and the outputs of a tail lie on the device, and the host's copy of the segments (the places of the outputs).
+struct TailTables {
+    const RsSeg* d_rsegs; const RsTap* d_rtaps; const uint8_t* d_order; const void* d_psegs;       // d_order: null without a class order
+    uint8_t* d_rs8; float* d_rs32; float* d_prob;                                                  // d_rs8 / d_rs32: null where no image asks
+    long long blocks;
+    const RsSeg* rsegs; const ProbSeg* psegs; const ProbStackSeg* pssegs;
+};
+
+// THE tail: the one kernel of the tail's kind on the half logits d_o16, then that kind's device-to-host copies, all enqueued on `st`.
+int run_tail(const SwTail& t, int K, const TailTables& tt, const __half* d_o16, hipStream_t st) {
+    const int n = (int)t.images.size();
+    const dim3 grid((unsigned)tt.blocks), block(256);
+    switch (t.kind) {
+    case SwTail::kNone: return TS2D_OK;
+    case SwTail::kExport:
+        hipLaunchKernelGGL(sw_resample_threshold, grid, block, 0, st, d_o16, tt.d_rsegs, n, K, tt.d_rtaps, tt.d_rs8, tt.d_rs32, kSigmoidHalfThreshold);
+        break;
+    case SwTail::kLabelmap: hipLaunchKernelGGL(sw_labelmap, grid, block, 0, st, d_o16, tt.d_rsegs, n, K, tt.d_rtaps, tt.d_rs8); break;
+    case SwTail::kRegions:
+        hipLaunchKernelGGL(sw_regions, grid, block, 0, st, d_o16, tt.d_rsegs, n, K, tt.d_rtaps, tt.d_order, tt.d_rs8, kSigmoidHalfThreshold);
+        break;
+    case SwTail::kProbRuns:                                   // (named before kProb: the order of the two instantiations in the code object)
+        hipLaunchKernelGGL(sw_probabilities<ProbStackSeg>, grid, block, 0, st, d_o16, tt.d_rsegs, static_cast<const ProbStackSeg*>(tt.d_psegs), n, K,
+                           tt.d_rtaps, t.mode, tt.d_order, tt.d_prob, tt.d_rs8, kSigmoidHalfThreshold);
+        break;
+    case SwTail::kProb:
+        hipLaunchKernelGGL(sw_probabilities<ProbSeg>, grid, block, 0, st, d_o16, tt.d_rsegs, static_cast<const ProbSeg*>(tt.d_psegs), n, K, tt.d_rtaps,
+                           t.mode, tt.d_order, tt.d_prob, tt.d_rs8, kSigmoidHalfThreshold);
+        break;
+    }
+    HIP_TRY(hipGetLastError());
+    const size_t D = (size_t)t.decided_planes(K);
+    for (int r = 0; r < t.n_runs; ++r) {                      // (kProbRuns) a head of a run is one piece on both sides
+        const ts2d_tiled_probabilities_run& rn = t.runs[r];
+        const ProbStackSeg& ps = tt.pssegs[(size_t)rn.first_image];
+        const size_t run_plane = (size_t)ps.prob_stride;
+        for (int k = 0; k < K; ++k)
+            HIP_TRY(hipMemcpyAsync(rn.prob_f32 + (long long)k * rn.prob_head_stride, tt.d_prob + ps.prob_off + (size_t)k * run_plane, run_plane * 4, hipMemcpyDeviceToHost, st));
+        for (size_t k = 0; rn.decided_u8 && k < D; ++k)
+            HIP_TRY(hipMemcpyAsync(rn.decided_u8 + (long long)k * rn.decided_head_stride, tt.d_rs8 + ps.dec_off + k * run_plane, run_plane, hipMemcpyDeviceToHost, st));
+    }
+    for (int i = 0; i < n && t.kind != SwTail::kProbRuns; ++i) {
+        const SwTail::Image& ti = t.images[(size_t)i];
+        if (t.kind == SwTail::kProb) {
+            const size_t fplane = (size_t)ti.full_h * ti.full_w;
+            HIP_TRY(hipMemcpyAsync(ti.f32, tt.d_prob + tt.psegs[i].prob_off, (size_t)K * fplane * 4, hipMemcpyDeviceToHost, st));
+            if (ti.u8) HIP_TRY(hipMemcpyAsync(ti.u8, tt.d_rs8 + tt.psegs[i].dec_off, D * fplane, hipMemcpyDeviceToHost, st));
+            continue;
+        }
+        const size_t ne = (size_t)t.planes(K) * ti.out_h * ti.out_w;
+        if (ti.u8) HIP_TRY(hipMemcpyAsync(ti.u8, tt.d_rs8 + tt.rsegs[i].dst_off, ne, hipMemcpyDeviceToHost, st));
+        if (ti.f32) HIP_TRY(hipMemcpyAsync(ti.f32, tt.d_rs32 + tt.rsegs[i].dst_off, ne * 4, hipMemcpyDeviceToHost, st));
+    }
+    return TS2D_OK;
+}
+
 // The sliding window of every C entry (include/ts2d_engine.h): N images as ONE engine batch; ts2d_engine_predict_tiled is N = 1.
 // plan_tiled (tiled_plan.cpp) validates everything, packs the rows (tile x mirror variant) of the images into chunks of at most
 // kSwChunkRows and lays the scratch out; here every host-to-device copy is enqueued, then per chunk one sw_gather, one forward and
-// (where an image ends in the chunk) one sw_aggregate, then every device-to-host copy, ONE stream synchronise and the result check.
+// (where an image ends in the chunk) one sw_aggregate, then the tail and every device-to-host copy, ONE stream synchronise and the result check.
 // `full` is the whole difference between the entries' results: the batch entry asks for the full-batch dispatch (a row's bits must not
 // depend on its batch-mates), the single-image entry for the size-dependent one.  `name_images`: a message names the image it is about.
-// `exports` (ts2d_engine_predict_tiled_export; else null): one descriptor per image - behind the last aggregate ONE sw_resample_threshold
-// launch resamples every image's half logits to its export extent where they lie in the scratch.
-// `engines[0 .. F)` (ts2d_ensemble_predict_tiled_export; the other entries are F = 1): the folds of an ensemble, one after the other on
+// `engines[0 .. F)` (the ts2d_ensemble_* entries; the others are F = 1): the folds of an ensemble, one after the other on
 // the FIRST engine's stream and in its scratch - the chunk loop once per fold, sw_aggregate into the fold's own half slot and inf
-// flags, then ONE sw_fold_mean (kernels_fold.h) into slot 0, on which the tail below runs as it does on a single fold's logits.  Only
+// flags, then ONE sw_fold_mean (kernels_fold.h) into slot 0, on which the tail runs as it does on a single fold's logits.  Only
 // the half slots and the flags exist F times.  `name_folds`: a fold's failed reserve or result check is reported as "fold <f>: ...".
-// `labelmap` (ts2d_ensemble_predict_tiled_labelmap): `exports` carry the label-map descriptors (seg_u8 = label_u8) - behind the last
-// aggregate (or the mean) ONE sw_labelmap launch (kernels_labelmap.h) in the place of sw_resample_threshold: ONE uint8 plane per image.
-// `class_order` (ts2d_ensemble_predict_tiled_regions; with `labelmap`, else null): the num_classes class values of a region-based model -
-// the label-map plan, the table riding in the call's one table blob, and ONE sw_regions launch (kernels_regions.h) in sw_labelmap's place.
-// `prob` (ts2d_ensemble_predict_tiled_probabilities; with `labelmap`, else null): `exports` carry the geometry of its descriptors (seg_u8 =
-// prob_f32), `class_order` is set in its regions mode only - the label-map plan with lanes over the full extent, and ONE sw_probabilities
-// launch (kernels_prob.h) in sw_labelmap's place: K float planes (and the decided map) of the pre-crop extent per image.
-// `prob->runs` (ts2d_ensemble_predict_tiled_probabilities_stack): the outputs are those of runs of slices - sw_probabilities<ProbStackSeg> writes a run's
-// planes head-major, and every head of a run travels to the host in one copy, to its place in the caller's strided volume.
-int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap,
-                       const uint8_t* class_order, const ProbCall* prob, int n_images, int ph, int pw, int mirror_mask,
+int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* images, const SwTail& tail, int n_images, int ph, int pw, int mirror_mask,
                        const uint16_t* gaussian_f16, bool full, bool name_images, bool name_folds, const char* entry) {
     ts2d_engine* e = engines[0];
     SwPlan pl;
-    TRY(plan_tiled(e, F, images, exports, labelmap, class_order, prob, n_images, ph, pw, mirror_mask, name_images, entry, &pl));
+    TRY(plan_tiled(e, F, images, tail, n_images, ph, pw, mirror_mask, name_images, entry, &pl));
     const int C = e->arch.input_channels, K = e->arch.num_classes, V = pl.V;
     for (int f = 0; f < F; ++f) TRY(name_fold(reserve_checked(engines[f], pl.cap_rows, ph, pw, full), name_folds, f));
     HIP_TRY(hipSetDevice(e->device));
@@ -100,56 +145,12 @@ int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* ima
                            d_seg, kSigmoidHalfThreshold);
         HIP_TRY(hipGetLastError());
     }
-    uint8_t* d_rs8 = pl.any_rs8 ? reinterpret_cast<uint8_t*>(b + pl.o_rs8) : nullptr; float* d_rs32 = pl.any_rs32 ? reinterpret_cast<float*>(b + pl.o_rs32) : nullptr;
-    if (prob && prob->runs) {
-        float* d_prob = reinterpret_cast<float*>(b + pl.o_prob);
-        hipLaunchKernelGGL(sw_probabilities<ProbStackSeg>, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
-                           reinterpret_cast<const ProbStackSeg*>(b + pl.o_tab + pl.tab_psegs), n_images, K, reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps),
-                           prob->mode, class_order ? reinterpret_cast<const uint8_t*>(b + pl.o_tab + pl.tab_order) : nullptr, d_prob, d_rs8, kSigmoidHalfThreshold);
-        HIP_TRY(hipGetLastError());
-        for (int r = 0; r < prob->n_runs; ++r) {              // a head of a run is one piece on both sides
-            const ts2d_tiled_probabilities_run& rn = prob->runs[r];
-            const ProbStackSeg& ps = pl.pssegs[(size_t)rn.first_image];
-            const size_t run_plane = (size_t)ps.prob_stride;
-            for (int k = 0; k < K; ++k)
-                HIP_TRY(hipMemcpyAsync(rn.prob_f32 + (long long)k * rn.prob_head_stride, d_prob + ps.prob_off + (size_t)k * run_plane, run_plane * 4, hipMemcpyDeviceToHost, st));
-            for (int k = 0; rn.decided_u8 && k < (prob->mode == kProbMultilabel ? K : 1); ++k)
-                HIP_TRY(hipMemcpyAsync(rn.decided_u8 + (long long)k * rn.decided_head_stride, d_rs8 + ps.dec_off + (size_t)k * run_plane, run_plane, hipMemcpyDeviceToHost, st));
-        }
-    } else if (prob) {
-        float* d_prob = reinterpret_cast<float*>(b + pl.o_prob);
-        hipLaunchKernelGGL(sw_probabilities<ProbSeg>, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
-                           reinterpret_cast<const ProbSeg*>(b + pl.o_tab + pl.tab_psegs), n_images, K, reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps),
-                           prob->mode, class_order ? reinterpret_cast<const uint8_t*>(b + pl.o_tab + pl.tab_order) : nullptr, d_prob, d_rs8, kSigmoidHalfThreshold);
-        HIP_TRY(hipGetLastError());
-        for (int i = 0; i < n_images; ++i) {
-            const ts2d_tiled_probabilities& pd = prob->descs[i];
-            const size_t fplane = (size_t)pd.full_h * pd.full_w;
-            HIP_TRY(hipMemcpyAsync(pd.prob_f32, d_prob + pl.psegs[i].prob_off, (size_t)K * fplane * 4, hipMemcpyDeviceToHost, st));
-            if (pd.decided_u8)
-                HIP_TRY(hipMemcpyAsync(pd.decided_u8, d_rs8 + pl.psegs[i].dec_off, (prob->mode == kProbMultilabel ? (size_t)K : 1) * fplane, hipMemcpyDeviceToHost, st));
-        }
-    } else if (labelmap) {
-        const RsSeg* d_rsegs = reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs);
-        const RsTap* d_rtaps = reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps);
-        if (class_order)
-            hipLaunchKernelGGL(sw_regions, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, d_rsegs, n_images, K, d_rtaps,
-                               reinterpret_cast<const uint8_t*>(b + pl.o_tab + pl.tab_order), d_rs8, kSigmoidHalfThreshold);
-        else
-            hipLaunchKernelGGL(sw_labelmap, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, d_rsegs, n_images, K, d_rtaps, d_rs8);
-        HIP_TRY(hipGetLastError());
-        for (int i = 0; i < n_images; ++i)
-            HIP_TRY(hipMemcpyAsync(exports[i].seg_u8, d_rs8 + pl.rsegs[i].dst_off, (size_t)exports[i].out_h * exports[i].out_w, hipMemcpyDeviceToHost, st));
-    } else if (exports) {
-        hipLaunchKernelGGL(sw_resample_threshold, dim3((unsigned)pl.rs_blocks), dim3(256), 0, st, d_o16, reinterpret_cast<const RsSeg*>(b + pl.o_tab + pl.tab_rsegs),
-                           n_images, K, reinterpret_cast<const RsTap*>(b + pl.o_tab + pl.tab_rtaps), d_rs8, d_rs32, kSigmoidHalfThreshold);
-        HIP_TRY(hipGetLastError());
-        for (int i = 0; i < n_images; ++i) {
-            const size_t ne = (size_t)K * exports[i].out_h * exports[i].out_w;
-            if (exports[i].seg_u8) HIP_TRY(hipMemcpyAsync(exports[i].seg_u8, d_rs8 + pl.rsegs[i].dst_off, ne, hipMemcpyDeviceToHost, st));
-            if (exports[i].logits_f32) HIP_TRY(hipMemcpyAsync(exports[i].logits_f32, d_rs32 + pl.rsegs[i].dst_off, ne * 4, hipMemcpyDeviceToHost, st));
-        }
-    }
+    const char* tab = b + pl.o_tab;
+    TRY(run_tail(tail, K, TailTables{reinterpret_cast<const RsSeg*>(tab + pl.tab_rsegs), reinterpret_cast<const RsTap*>(tab + pl.tab_rtaps),
+                                     tail.class_order ? reinterpret_cast<const uint8_t*>(tab + pl.tab_order) : nullptr, tab + pl.tab_psegs,
+                                     pl.any_rs8 ? reinterpret_cast<uint8_t*>(b + pl.o_rs8) : nullptr, pl.any_rs32 ? reinterpret_cast<float*>(b + pl.o_rs32) : nullptr,
+                                     reinterpret_cast<float*>(b + pl.o_prob), pl.rs_blocks, pl.rsegs.data(), pl.psegs.data(), pl.pssegs.data()},
+                 d_o16, st));
     std::vector<int> flags((size_t)F * n_images, 0);
     HIP_TRY(hipMemcpyAsync(flags.data(), d_flag, (size_t)F * n_images * 4, hipMemcpyDeviceToHost, st));
     {
@@ -174,9 +175,9 @@ int predict_tiled_impl(ts2d_engine* const* engines, int F, ts2d_tiled_image* ima
     return TS2D_OK;
 }
 
-// what the ensemble entries refuse alike before any device work: the handles, the image array, folds that differ where they must agree.
-// *todo: the images to run (0: the call returns TS2D_OK and does nothing)
-int check_folds(const char* entry, ts2d_engine* const* engines, int n_engines, const ts2d_tiled_image* images, int n_images, int* todo) {
+// The prologue of every ensemble entry, before any device work: the handles, the image array, folds that differ where they must agree, the
+// entry's own per-image descriptor array (`no_descs`: it is null).  *todo: the images to run (0: the call returns TS2D_OK and does nothing)
+int check_folds(const char* entry, ts2d_engine* const* engines, int n_engines, const ts2d_tiled_image* images, int n_images, bool no_descs, int* todo) {
     if (!engines) return fail(TS2D_ERR_INVALID, "%s: %d engines at a null pointer", entry, n_engines);
     if (n_engines < 1 || n_engines > kMaxFolds) return fail(TS2D_ERR_INVALID, "%s: n_engines = %d is outside 1..%d", entry, n_engines, kMaxFolds);
     for (int f = 0; f < n_engines; ++f)
@@ -198,23 +199,27 @@ int check_folds(const char* entry, ts2d_engine* const* engines, int n_engines, c
         if (e->tile_half != e0->tile_half)
             return fail(TS2D_ERR_INVALID, "%s: fold %d blends with tile dtype %d, fold 0 with %d", entry, f, e->tile_half, e0->tile_half);
     }
+    if (no_descs) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
     return TS2D_OK;
 }
 
-// the descriptors of a label-map or region call as the geometry of an export with ONE uint8 output
-std::vector<ts2d_tiled_export> one_plane_exports(const ts2d_tiled_labelmap* maps, int n_images) {
-    std::vector<ts2d_tiled_export> ex((size_t)n_images);
-    for (int i = 0; i < n_images; ++i) {
-        const ts2d_tiled_labelmap& lm = maps[i];
-        ex[i] = ts2d_tiled_export{lm.src_y, lm.src_x, lm.src_h, lm.src_w, lm.out_h, lm.out_w, lm.label_u8, nullptr};
-    }
-    return ex;
+// the tail of an export call (null: a call without one)
+SwTail export_tail(const ts2d_tiled_export* exports, int n_images) {
+    SwTail t(exports ? SwTail::kExport : SwTail::kNone, exports ? n_images : 0);
+    for (size_t i = 0; i < t.images.size(); ++i) t.images[i] = SwTail::rect_of(exports[i], exports[i].seg_u8, exports[i].logits_f32);
+    return t;
 }
 
-// ts2d_labelmap_from_logits and ts2d_regions_from_logits: the one-image kernel call on half planes of the caller's.
-// class_order null: sw_labelmap; else sw_regions with its K class values.
+// the tail of a label-map or region call: ONE uint8 plane per image
+SwTail one_plane_tail(SwTail::Kind kind, const ts2d_tiled_labelmap* maps, int n_images, const uint8_t* class_order) {
+    SwTail t(kind, n_images);
+    t.class_order = class_order;
+    for (int i = 0; i < n_images; ++i) t.images[(size_t)i] = SwTail::rect_of(maps[i], maps[i].label_u8, nullptr);
+    return t;
+}
+
 // what the *_from_logits entries refuse alike of their planes, rectangle and output extent
-int check_from_logits(const char* entry, int K, int H, int W, const ts2d_tiled_export& ex) {
+int check_from_logits(const char* entry, int K, int H, int W, const SwTail::Image& ex) {
     if (K < 1 || K > 256) return fail(TS2D_ERR_INVALID, "%s: %d heads outside 1 ... 256", entry, K);
     if (H < 1 || W < 1 || (long long)K * H * W >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: bad extent %d x %d x %d (2^31 elements at most)", entry, K, H, W);
     if (ex.src_h < 1 || ex.src_w < 1 || ex.src_y < 0 || ex.src_x < 0 || ex.src_h > H - ex.src_y || ex.src_w > W - ex.src_x)
@@ -226,42 +231,50 @@ int check_from_logits(const char* entry, int K, int H, int W, const ts2d_tiled_e
     return TS2D_OK;
 }
 
-int one_plane_from_logits(const char* entry, const char* what, int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4],
-                          int out_h, int out_w, const uint8_t* class_order, uint8_t* label_u8) {
-    const ts2d_tiled_export ex{rect[0], rect[1], rect[2], rect[3], out_h, out_w, label_u8, nullptr};
-    TRY(check_from_logits(entry, K, H, W, ex));
+// The ts2d_*_from_logits entries: the tail of ONE image (t.images[0]; the entry has refused its null pointers) on half planes of the caller's.
+int tail_from_logits(const char* entry, int device, const uint16_t* logits_f16, int K, int H, int W, const SwTail& t) {
+    const SwTail::Image& ti = t.images[0];
+    TRY(check_from_logits(entry, K, H, W, ti));
+    if (t.prob()) {
+        if (ti.full_h < 1 || ti.full_w < 1 || ti.box_y < 0 || ti.box_x < 0 || ti.out_h > ti.full_h - ti.box_y || ti.out_w > ti.full_w - ti.box_x)
+            return fail(TS2D_ERR_INVALID, "%s: probabilities: the %dx%d output at (%d,%d) leaves the full extent %dx%d", entry, ti.out_h, ti.out_w, ti.box_y,
+                        ti.box_x, ti.full_h, ti.full_w);
+        if ((long long)K * ti.full_h * ti.full_w >= (1LL << 31))
+            return fail(TS2D_ERR_INVALID, "%s: probabilities: %d x %dx%d exceeds 2^31 output elements", entry, K, ti.full_h, ti.full_w);
+    }
     std::vector<RsSeg> segs; std::vector<RsTap> rtaps;
     long long blocks = 0, elems = 0;
-    rs_plan_segment(true, K, H, W, ex, 0, &segs, &rtaps, &blocks, &elems, nullptr);
-    if (blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the %s exceeds 2^31 blocks", entry, what);
+    rs_plan_segment(t, 0, K, H, W, 0, &segs, &rtaps, &blocks, &elems);
+    if (blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, t.prob() ? "%s: the %s exceed 2^31 blocks" : "%s: the %s exceeds 2^31 blocks", entry, t.what());
+    const ProbSeg ps{0, 0, ti.full_h, ti.full_w, ti.box_y, ti.box_x};
     HIP_TRY(hipSetDevice(device));
-    // [segment | taps | class order | half planes | label map]
-    const size_t n_src = (size_t)K * H * W, n_dst = (size_t)out_h * out_w;
-    const size_t o_taps = align_up(sizeof(RsSeg), 8), o_order = o_taps + rtaps.size() * sizeof(RsTap);
-    const size_t o_src = align_up(o_order + (class_order ? (size_t)K : 0), 256), o_dst = align_up(o_src + n_src * 2, 256);
+    const size_t n_src = (size_t)K * H * W, n_prob = t.prob() ? (size_t)K * ti.full_h * ti.full_w : 0;
+    const size_t n_u8 = !ti.u8 ? 0 : t.prob() ? (size_t)t.decided_planes(K) * ti.full_h * ti.full_w : (size_t)elems;
+    ArenaLayout lay;
+    const size_t o_seg = lay.add(sizeof(RsSeg)), o_ps = lay.add(t.prob() ? sizeof(ProbSeg) : 0), o_taps = lay.add(rtaps.size() * sizeof(RsTap));
+    const size_t o_order = lay.add(t.class_order ? (size_t)K : 0), o_src = lay.add(n_src * 2), o_prob = lay.add(n_prob * 4), o_u8 = lay.add(n_u8);
     DevMem d;
-    HIP_TRY(d.alloc(o_dst + n_dst));
-    HIP_TRY(hipMemcpy(d.as<char>(), segs.data(), sizeof(RsSeg), hipMemcpyHostToDevice));
+    HIP_TRY(d.alloc(lay.total()));
+    HIP_TRY(hipMemcpy(d.as<char>(o_seg), segs.data(), sizeof(RsSeg), hipMemcpyHostToDevice));
+    if (t.prob()) HIP_TRY(hipMemcpy(d.as<char>(o_ps), &ps, sizeof(ProbSeg), hipMemcpyHostToDevice));
     if (!rtaps.empty()) HIP_TRY(hipMemcpy(d.as<char>(o_taps), rtaps.data(), rtaps.size() * sizeof(RsTap), hipMemcpyHostToDevice));
-    if (class_order) HIP_TRY(hipMemcpy(d.as<char>(o_order), class_order, (size_t)K, hipMemcpyHostToDevice));
+    if (t.class_order) HIP_TRY(hipMemcpy(d.as<char>(o_order), t.class_order, (size_t)K, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.as<char>(o_src), logits_f16, n_src * 2, hipMemcpyHostToDevice));
-    if (class_order)
-        hipLaunchKernelGGL(sw_regions, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(), 1, K,
-                           d.as<const RsTap>(o_taps), d.as<const uint8_t>(o_order), d.as<uint8_t>(o_dst), kSigmoidHalfThreshold);
-    else
-        hipLaunchKernelGGL(sw_labelmap, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(), 1, K,
-                           d.as<const RsTap>(o_taps), d.as<uint8_t>(o_dst));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(label_u8, d.as<uint8_t>(o_dst), n_dst, hipMemcpyDeviceToHost));
+    TRY(run_tail(t, K, TailTables{d.as<const RsSeg>(o_seg), d.as<const RsTap>(o_taps), t.class_order ? d.as<const uint8_t>(o_order) : nullptr,
+                                  d.as<const char>(o_ps), ti.u8 ? d.as<uint8_t>(o_u8) : nullptr, nullptr, d.as<float>(o_prob), blocks, segs.data(), &ps, nullptr},
+                 d.as<const __half>(o_src), 0));
+    HIP_TRY(hipStreamSynchronize(0));         // the outputs are the caller's (and `d` goes) when the entry returns
     return TS2D_OK;
 }
 
-// what both probabilities entries refuse of the mode and its class order
-int check_prob_mode(const char* entry, int mode, int K, const uint8_t* class_order) {
+// what the probabilities entries refuse of the mode and its class order (n_order: of an engine's call; the from_logits entry has none to check)
+int check_prob_mode(const char* entry, int mode, int K, const uint8_t* class_order, const int* n_order = nullptr) {
     if (mode != kProbMultilabel && mode != kProbLabelmap && mode != kProbRegions)
         return fail(TS2D_ERR_INVALID, "%s: probabilities: unknown mode %d", entry, mode);
     if (mode == kProbRegions && !class_order) return fail(TS2D_ERR_INVALID, "%s: probabilities: the class order is null", entry);
     if (K < 1 || K > 256) return fail(TS2D_ERR_INVALID, "%s: probabilities: %d heads outside 1 ... 256", entry, K);      // (every mode: the twin's limit)
+    if (n_order && mode == kProbRegions && *n_order != K)
+        return fail(TS2D_ERR_INVALID, "%s: probabilities: %d class values for a model of %d heads", entry, *n_order, K);
     return TS2D_OK;
 }
 
@@ -277,7 +290,7 @@ int ts2d_engine_predict_tiled(ts2d_engine* e, const float* image, int Hp, int Wp
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled: weights not loaded");
     if (!logits_f16 && !seg_u8) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled: both outputs are null");
     ts2d_tiled_image one{image, Hp, Wp, n_tiles, tile_y, tile_x, logits_f16, seg_u8, 0};
-    return predict_tiled_impl(&e, 1, &one, nullptr, false, nullptr, nullptr, 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
+    return predict_tiled_impl(&e, 1, &one, SwTail(), 1, ph, pw, mirror_mask, gaussian_f16, kBySize, false, false, "ts2d_engine_predict_tiled");
 }
 
 int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, int n_images, int ph, int pw, int mirror_mask,
@@ -286,7 +299,7 @@ int ts2d_engine_predict_tiled_batch(ts2d_engine* e, ts2d_tiled_image* images, in
     if (n_images < 0 || (n_images > 0 && !images)) return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_batch: %d images at a null pointer", n_images);
     if (n_images == 0) return TS2D_OK;
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_batch: weights not loaded");
-    return predict_tiled_impl(&e, 1, images, nullptr, false, nullptr, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
+    return predict_tiled_impl(&e, 1, images, SwTail(), n_images, ph, pw, mirror_mask, gaussian_f16, kFullBatch, true, false, "ts2d_engine_predict_tiled_batch");
 }
 
 int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, const ts2d_tiled_export* exports, int n_images, int ph, int pw,
@@ -296,7 +309,7 @@ int ts2d_engine_predict_tiled_export(ts2d_engine* e, ts2d_tiled_image* images, c
         return fail(TS2D_ERR_INVALID, "ts2d_engine_predict_tiled_export: %d images at a null pointer", n_images);
     if (n_images == 0) return TS2D_OK;
     if (!e->weights_ready) return fail(TS2D_ERR_STATE, "ts2d_engine_predict_tiled_export: weights not loaded");
-    return predict_tiled_impl(&e, 1, images, exports, false, nullptr, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
+    return predict_tiled_impl(&e, 1, images, export_tail(exports, n_images), n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, false,
                               "ts2d_engine_predict_tiled_export");
 }
 
@@ -304,9 +317,9 @@ int ts2d_ensemble_predict_tiled_export(ts2d_engine* const* engines, int n_engine
                                        int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
     static const char* entry = "ts2d_ensemble_predict_tiled_export";
     int todo = 0;
-    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    TRY(check_folds(entry, engines, n_engines, images, n_images, false, &todo));
     if (!todo) return TS2D_OK;
-    return predict_tiled_impl(engines, n_engines, images, exports, false, nullptr, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
+    return predict_tiled_impl(engines, n_engines, images, export_tail(exports, n_images), n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize,
                               true, true, entry);
 }
 
@@ -314,12 +327,10 @@ int ts2d_ensemble_predict_tiled_labelmap(ts2d_engine* const* engines, int n_engi
                                          int n_images, int ph, int pw, int mirror_mask, const uint16_t* gaussian_f16, int full_batch) {
     static const char* entry = "ts2d_ensemble_predict_tiled_labelmap";
     int todo = 0;
-    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    TRY(check_folds(entry, engines, n_engines, images, n_images, !labelmaps, &todo));
     if (!todo) return TS2D_OK;
-    if (!labelmaps) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
-    const std::vector<ts2d_tiled_export> ex = one_plane_exports(labelmaps, n_images);
-    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, nullptr, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16,
-                              full_batch ? kFullBatch : kBySize, true, true, entry);
+    return predict_tiled_impl(engines, n_engines, images, one_plane_tail(SwTail::kLabelmap, labelmaps, n_images, nullptr), n_images, ph, pw, mirror_mask,
+                              gaussian_f16, full_batch ? kFullBatch : kBySize, true, true, entry);
 }
 
 int ts2d_ensemble_predict_tiled_regions(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, const ts2d_tiled_labelmap* maps,
@@ -327,23 +338,23 @@ int ts2d_ensemble_predict_tiled_regions(ts2d_engine* const* engines, int n_engin
                                         const uint8_t* class_order, int n_order) {
     static const char* entry = "ts2d_ensemble_predict_tiled_regions";
     int todo = 0;
-    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    TRY(check_folds(entry, engines, n_engines, images, n_images, !maps, &todo));
     if (!todo) return TS2D_OK;
-    if (!maps) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
     if (!class_order) return fail(TS2D_ERR_INVALID, "%s: regions: the class order is null", entry);
     const int K = engines[0]->arch.num_classes;
     if (n_order != K) return fail(TS2D_ERR_INVALID, "%s: regions: %d class values for a model of %d heads", entry, n_order, K);
     if (K > 256) return fail(TS2D_ERR_INVALID, "%s: regions: %d heads outside 1 ... 256", entry, K);
-    const std::vector<ts2d_tiled_export> ex = one_plane_exports(maps, n_images);
-    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, class_order, nullptr, n_images, ph, pw, mirror_mask, gaussian_f16,
-                              full_batch ? kFullBatch : kBySize, true, true, entry);
+    return predict_tiled_impl(engines, n_engines, images, one_plane_tail(SwTail::kRegions, maps, n_images, class_order), n_images, ph, pw, mirror_mask,
+                              gaussian_f16, full_batch ? kFullBatch : kBySize, true, true, entry);
 }
 
 int ts2d_labelmap_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
                               uint8_t* label_u8) {
     static const char* entry = "ts2d_labelmap_from_logits";
     if (!logits_f16 || !rect || !label_u8) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
-    return one_plane_from_logits(entry, "labelmap", device, logits_f16, K, H, W, rect, out_h, out_w, nullptr, label_u8);
+    SwTail t(SwTail::kLabelmap, 1);
+    t.images[0] = SwTail::Image{rect[0], rect[1], rect[2], rect[3], out_h, out_w, 0, 0, 0, 0, label_u8, nullptr};
+    return tail_from_logits(entry, device, logits_f16, K, H, W, t);
 }
 
 int ts2d_regions_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
@@ -352,7 +363,10 @@ int ts2d_regions_from_logits(int device, const uint16_t* logits_f16, int K, int 
     if (!logits_f16 || !rect) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
     if (!class_order) return fail(TS2D_ERR_INVALID, "%s: regions: the class order is null", entry);
     if (!label_u8) return fail(TS2D_ERR_INVALID, "%s: regions: the output is null", entry);
-    return one_plane_from_logits(entry, "regions", device, logits_f16, K, H, W, rect, out_h, out_w, class_order, label_u8);
+    SwTail t(SwTail::kRegions, 1);
+    t.class_order = class_order;
+    t.images[0] = SwTail::Image{rect[0], rect[1], rect[2], rect[3], out_h, out_w, 0, 0, 0, 0, label_u8, nullptr};
+    return tail_from_logits(entry, device, logits_f16, K, H, W, t);
 }
 
 int ts2d_ensemble_predict_tiled_probabilities(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images,
@@ -360,20 +374,13 @@ int ts2d_ensemble_predict_tiled_probabilities(ts2d_engine* const* engines, int n
                                               const uint16_t* gaussian_f16, int full_batch, int mode, const uint8_t* class_order, int n_order) {
     static const char* entry = "ts2d_ensemble_predict_tiled_probabilities";
     int todo = 0;
-    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    TRY(check_folds(entry, engines, n_engines, images, n_images, !probabilities, &todo));
     if (!todo) return TS2D_OK;
-    if (!probabilities) return fail(TS2D_ERR_INVALID, "%s: %d images at a null pointer", entry, n_images);
-    const int K = engines[0]->arch.num_classes;
-    TRY(check_prob_mode(entry, mode, K, class_order));
-    if (mode == kProbRegions && n_order != K) return fail(TS2D_ERR_INVALID, "%s: probabilities: %d class values for a model of %d heads", entry, n_order, K);
-    std::vector<ts2d_tiled_export> ex((size_t)n_images);      // the geometry of an export with ONE output: a null prob_f32 is "the output is null"
-    for (int i = 0; i < n_images; ++i) {
-        const ts2d_tiled_probabilities& pd = probabilities[i];
-        ex[i] = ts2d_tiled_export{pd.src_y, pd.src_x, pd.src_h, pd.src_w, pd.out_h, pd.out_w, reinterpret_cast<uint8_t*>(pd.prob_f32), nullptr};
-    }
-    const ProbCall prob{probabilities, mode};
-    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, mode == kProbRegions ? class_order : nullptr, &prob, n_images, ph, pw,
-                              mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, true, entry);
+    TRY(check_prob_mode(entry, mode, engines[0]->arch.num_classes, class_order, &n_order));
+    SwTail t(SwTail::kProb, n_images);
+    t.mode = mode; t.class_order = mode == kProbRegions ? class_order : nullptr;
+    for (int i = 0; i < n_images; ++i) t.images[(size_t)i] = SwTail::full_of(probabilities[i], probabilities[i].decided_u8, probabilities[i].prob_f32);
+    return predict_tiled_impl(engines, n_engines, images, t, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, true, entry);
 }
 
 int ts2d_ensemble_predict_tiled_probabilities_stack(ts2d_engine* const* engines, int n_engines, ts2d_tiled_image* images, int n_images,
@@ -381,16 +388,13 @@ int ts2d_ensemble_predict_tiled_probabilities_stack(ts2d_engine* const* engines,
                                                     const uint16_t* gaussian_f16, int full_batch, int mode, const uint8_t* class_order, int n_order) {
     static const char* entry = "ts2d_ensemble_predict_tiled_probabilities_stack";
     int todo = 0;
-    TRY(check_folds(entry, engines, n_engines, images, n_images, &todo));
+    TRY(check_folds(entry, engines, n_engines, images, n_images, false, &todo));
     if (!todo) return TS2D_OK;
     if (!runs || n_runs < 1) return fail(TS2D_ERR_INVALID, "%s: %d runs at a null pointer", entry, n_runs);
-    const int K = engines[0]->arch.num_classes;
-    TRY(check_prob_mode(entry, mode, K, class_order));
-    if (mode == kProbRegions && n_order != K) return fail(TS2D_ERR_INVALID, "%s: probabilities: %d class values for a model of %d heads", entry, n_order, K);
-    // the runs cover the images once, in order; every image gets the descriptor of the sibling entry: its run's geometry, its own slice of the outputs
-    std::vector<ts2d_tiled_probabilities> descs((size_t)n_images);
-    std::vector<ts2d_tiled_export> ex((size_t)n_images);
-    std::vector<int> run_of((size_t)n_images);
+    TRY(check_prob_mode(entry, mode, engines[0]->arch.num_classes, class_order, &n_order));
+    // the runs cover the images once, in order; every image gets what the sibling entry's descriptor holds: its run's geometry, its own slice of the outputs
+    SwTail t(SwTail::kProbRuns, n_images);
+    t.mode = mode; t.class_order = mode == kProbRegions ? class_order : nullptr; t.runs = runs; t.n_runs = n_runs; t.run_of.resize((size_t)n_images);
     int next = 0;
     for (int r = 0; r < n_runs; ++r) {
         const ts2d_tiled_probabilities_run& rn = runs[r];
@@ -416,17 +420,13 @@ int ts2d_ensemble_predict_tiled_probabilities_stack(ts2d_engine* const* engines,
             if (images[i].Hp != images[next].Hp || images[i].Wp != images[next].Wp)
                 return fail(TS2D_ERR_INVALID, "%s: run %d: image %d: probabilities: the padded extent %dx%d differs from %dx%d of the run's first image", entry, r, i,
                             images[i].Hp, images[i].Wp, images[next].Hp, images[next].Wp);
-            descs[i] = ts2d_tiled_probabilities{rn.src_y, rn.src_x, rn.src_h, rn.src_w, rn.out_h, rn.out_w, rn.full_h, rn.full_w, rn.box_y, rn.box_x,
-                                                rn.prob_f32 + s * fplane, rn.decided_u8 ? rn.decided_u8 + s * fplane : nullptr};
-            ex[i] = ts2d_tiled_export{rn.src_y, rn.src_x, rn.src_h, rn.src_w, rn.out_h, rn.out_w, reinterpret_cast<uint8_t*>(rn.prob_f32), nullptr};
-            run_of[i] = r;
+            t.images[(size_t)i] = SwTail::full_of(rn, rn.decided_u8 ? rn.decided_u8 + s * fplane : nullptr, rn.prob_f32 + s * fplane);
+            t.run_of[(size_t)i] = r;
         }
         next += rn.n_slices;
     }
     if (next != n_images) return fail(TS2D_ERR_INVALID, "%s: probabilities: the %d runs end at image %d and leave a gap to the call's %d images", entry, n_runs, next - 1, n_images);
-    const ProbCall prob{descs.data(), mode, runs, n_runs, run_of.data()};
-    return predict_tiled_impl(engines, n_engines, images, ex.data(), true, mode == kProbRegions ? class_order : nullptr, &prob, n_images, ph, pw,
-                              mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, true, entry);
+    return predict_tiled_impl(engines, n_engines, images, t, n_images, ph, pw, mirror_mask, gaussian_f16, full_batch ? kFullBatch : kBySize, true, true, entry);
 }
 
 int ts2d_probabilities_from_logits(int device, const uint16_t* logits_f16, int K, int H, int W, const int32_t rect[4], int out_h, int out_w,
@@ -435,40 +435,11 @@ int ts2d_probabilities_from_logits(int device, const uint16_t* logits_f16, int K
     static const char* entry = "ts2d_probabilities_from_logits";
     if (!logits_f16 || !rect) return fail(TS2D_ERR_INVALID, "%s: null argument", entry);
     if (!prob_f32) return fail(TS2D_ERR_INVALID, "%s: probabilities: the output is null", entry);
-    const ts2d_tiled_export ex{rect[0], rect[1], rect[2], rect[3], out_h, out_w, nullptr, nullptr};
     TRY(check_prob_mode(entry, mode, K, class_order));
-    TRY(check_from_logits(entry, K, H, W, ex));
-    if (full_h < 1 || full_w < 1 || box_y < 0 || box_x < 0 || out_h > full_h - box_y || out_w > full_w - box_x)
-        return fail(TS2D_ERR_INVALID, "%s: probabilities: the %dx%d output at (%d,%d) leaves the full extent %dx%d", entry, out_h, out_w, box_y, box_x,
-                    full_h, full_w);
-    if ((long long)K * full_h * full_w >= (1LL << 31))
-        return fail(TS2D_ERR_INVALID, "%s: probabilities: %d x %dx%d exceeds 2^31 output elements", entry, K, full_h, full_w);
-    std::vector<RsSeg> segs; std::vector<RsTap> rtaps;
-    long long blocks = 0;
-    const int full_hw[2] = {full_h, full_w};
-    rs_plan_segment(true, K, H, W, ex, 0, &segs, &rtaps, &blocks, nullptr, full_hw);
-    if (blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the probabilities exceed 2^31 blocks", entry);
-    const bool regions = mode == kProbRegions;
-    const ProbSeg ps{0, 0, full_h, full_w, box_y, box_x};
-    HIP_TRY(hipSetDevice(device));
-    const size_t n_src = (size_t)K * H * W, n_prob = (size_t)K * full_h * full_w, n_dec = decided_u8 ? (mode == kProbMultilabel ? n_prob : n_prob / K) : 0;
-    ArenaLayout lay;
-    const size_t o_seg = lay.add(sizeof(RsSeg)), o_ps = lay.add(sizeof(ProbSeg)), o_taps = lay.add(rtaps.size() * sizeof(RsTap));
-    const size_t o_order = lay.add(regions ? (size_t)K : 0), o_src = lay.add(n_src * 2), o_prob = lay.add(n_prob * 4), o_dec = lay.add(n_dec);
-    DevMem d;
-    HIP_TRY(d.alloc(lay.total()));
-    HIP_TRY(hipMemcpy(d.as<char>(o_seg), segs.data(), sizeof(RsSeg), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.as<char>(o_ps), &ps, sizeof(ProbSeg), hipMemcpyHostToDevice));
-    if (!rtaps.empty()) HIP_TRY(hipMemcpy(d.as<char>(o_taps), rtaps.data(), rtaps.size() * sizeof(RsTap), hipMemcpyHostToDevice));
-    if (regions) HIP_TRY(hipMemcpy(d.as<char>(o_order), class_order, (size_t)K, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.as<char>(o_src), logits_f16, n_src * 2, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sw_probabilities<ProbSeg>, dim3((unsigned)blocks), dim3(256), 0, 0, d.as<const __half>(o_src), d.as<const RsSeg>(o_seg), d.as<const ProbSeg>(o_ps), 1, K,
-                       d.as<const RsTap>(o_taps), mode, regions ? d.as<const uint8_t>(o_order) : nullptr, d.as<float>(o_prob),
-                       decided_u8 ? d.as<uint8_t>(o_dec) : nullptr, kSigmoidHalfThreshold);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(prob_f32, d.as<float>(o_prob), n_prob * 4, hipMemcpyDeviceToHost));
-    if (decided_u8) HIP_TRY(hipMemcpy(decided_u8, d.as<uint8_t>(o_dec), n_dec, hipMemcpyDeviceToHost));
-    return TS2D_OK;
+    SwTail t(SwTail::kProb, 1);
+    t.mode = mode; t.class_order = mode == kProbRegions ? class_order : nullptr;
+    t.images[0] = SwTail::Image{rect[0], rect[1], rect[2], rect[3], out_h, out_w, full_h, full_w, box_y, box_x, decided_u8, prob_f32};
+    return tail_from_logits(entry, device, logits_f16, K, H, W, t);
 }
 
 int ts2d_engine_tiled_inf_flag(const ts2d_engine* e) { return e ? (e->tiled_inf != 0) : 0; }

@@ -31,22 +31,19 @@ void rs_axis_taps(int n_in, int n_out, int origin, RsTap* t) {
     }
 }
 
-// every image (and its export descriptor) on its own; the totals that bound the tables
-// `labelmap`: the descriptors are those of a label-map call (ONE output plane per image: seg_u8 is its label_u8) and are named so;
-// `regions`: of a region call - the same descriptors under that name;  `prob`: of a probabilities call (seg_u8 is its prob_f32) - named
-// "probabilities", whatever its mode, and checked against the full extent too
-int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, bool regions,
-                 const ProbCall* prob, int n_images, int ph, int pw, bool name_images, const char* entry, SwPlan* pl) {
+// every image (and its part of the tail, under the tail's name) on its own; the totals that bound the tables
+int check_images(int F, int C, int K, const ts2d_tiled_image* images, const SwTail& tail, int n_images, int ph, int pw, bool name_images,
+                 const char* entry, SwPlan* pl) {
     long long n_taps_all = 0;
-    const char* what = prob ? "probabilities" : regions ? "regions" : labelmap ? "labelmap" : "export";
+    const char* what = tail.what();
     pl->any16 = F > 1;      // (the mean is taken over the half buffers)
     for (int i = 0; i < n_images; ++i) {
         const ts2d_tiled_image& im = images[i];
         char pre[48] = "";
-        if (name_images && prob && prob->runs) snprintf(pre, sizeof(pre), "run %d: image %d: ", prob->run_of[i], i);
+        if (name_images && tail.kind == SwTail::kProbRuns) snprintf(pre, sizeof(pre), "run %d: image %d: ", tail.run_of[i], i);
         else if (name_images) snprintf(pre, sizeof(pre), "image %d: ", i);
         if (!im.image || !im.tile_y || !im.tile_x) return fail(TS2D_ERR_INVALID, "%snull image or tile pointer", pre);
-        if (!exports && !im.logits_f16 && !im.seg_u8) return fail(TS2D_ERR_INVALID, "%sboth outputs are null", pre);
+        if (tail.kind == SwTail::kNone && !im.logits_f16 && !im.seg_u8) return fail(TS2D_ERR_INVALID, "%sboth outputs are null", pre);
         if (im.n_tiles < 1 || im.n_tiles > (1 << 20) || im.Hp < 1 || im.Wp < 1 || ph > im.Hp || pw > im.Wp)
             return fail(TS2D_ERR_INVALID, "%sbad tiling: %d tiles of %dx%d on %dx%d", pre, im.n_tiles, ph, pw, im.Hp, im.Wp);
         if ((long long)K * im.Hp * im.Wp >= (1LL << 31) || (long long)C * im.Hp * im.Wp >= (1LL << 31))
@@ -56,26 +53,25 @@ int check_images(int F, int C, int K, const ts2d_tiled_image* images, const ts2d
                 return fail(TS2D_ERR_INVALID, "%stile %d at (%d,%d) leaves the %dx%d image", pre, t, im.tile_y[t], im.tile_x[t], im.Hp, im.Wp);
         pl->n_tiles_all += im.n_tiles;
         pl->any16 |= im.logits_f16 != nullptr; pl->anyseg |= im.seg_u8 != nullptr;
-        if (!exports) continue;
-        const ts2d_tiled_export& ex = exports[i];
-        if (!ex.seg_u8 && !ex.logits_f32) return fail(TS2D_ERR_INVALID, labelmap ? "%s%s: the output is null" : "%s%s: both outputs are null", pre, what);
+        if (tail.kind == SwTail::kNone) continue;
+        const SwTail::Image& ex = tail.images[i];
+        if (tail.no_output(ex)) return fail(TS2D_ERR_INVALID, tail.kind == SwTail::kExport ? "%s%s: both outputs are null" : "%s%s: the output is null", pre, what);
         if (ex.src_h < 1 || ex.src_w < 1 || ex.src_y < 0 || ex.src_x < 0 || ex.src_h > im.Hp - ex.src_y || ex.src_w > im.Wp - ex.src_x)
             return fail(TS2D_ERR_INVALID, "%s%s: source rectangle %dx%d at (%d,%d) is empty or leaves the %dx%d image", pre, what, ex.src_h, ex.src_w,
                         ex.src_y, ex.src_x, im.Hp, im.Wp);
         if (ex.out_h < 1 || ex.out_w < 1) return fail(TS2D_ERR_INVALID, "%s%s: bad output extent %dx%d", pre, what, ex.out_h, ex.out_w);
-        if ((long long)(labelmap ? 1 : K) * ex.out_h * ex.out_w >= (1LL << 31))
+        if ((long long)tail.planes(K) * ex.out_h * ex.out_w >= (1LL << 31))
             return fail(TS2D_ERR_INVALID, "%s%s: %dx%d exceeds 2^31 output elements", pre, what, ex.out_h, ex.out_w);
         n_taps_all += (long long)ex.out_h + ex.out_w;         // (each < 2^31 by the check above; bounded before any table is allocated)
         if (n_taps_all >= (1LL << 26)) return fail(TS2D_ERR_INVALID, "%s%s: more than 2^26 output rows + columns in one call", pre, what);
         pl->any16 = true;
-        if (!prob) { pl->any_rs8 |= ex.seg_u8 != nullptr; pl->any_rs32 |= ex.logits_f32 != nullptr; continue; }
-        const ts2d_tiled_probabilities& pd = prob->descs[i];
-        if (pd.full_h < 1 || pd.full_w < 1 || pd.box_y < 0 || pd.box_x < 0 || ex.out_h > pd.full_h - pd.box_y || ex.out_w > pd.full_w - pd.box_x)
-            return fail(TS2D_ERR_INVALID, "%s%s: the %dx%d output at (%d,%d) leaves the full extent %dx%d", pre, what, ex.out_h, ex.out_w, pd.box_y,
-                        pd.box_x, pd.full_h, pd.full_w);
-        if ((long long)K * pd.full_h * pd.full_w >= (1LL << 31))
-            return fail(TS2D_ERR_INVALID, "%s%s: %d x %dx%d exceeds 2^31 output elements", pre, what, K, pd.full_h, pd.full_w);
-        pl->any_rs8 |= pd.decided_u8 != nullptr;
+        pl->any_rs8 |= ex.u8 != nullptr;
+        if (!tail.prob()) { pl->any_rs32 |= ex.f32 != nullptr; continue; }
+        if (ex.full_h < 1 || ex.full_w < 1 || ex.box_y < 0 || ex.box_x < 0 || ex.out_h > ex.full_h - ex.box_y || ex.out_w > ex.full_w - ex.box_x)
+            return fail(TS2D_ERR_INVALID, "%s%s: the %dx%d output at (%d,%d) leaves the full extent %dx%d", pre, what, ex.out_h, ex.out_w, ex.box_y,
+                        ex.box_x, ex.full_h, ex.full_w);
+        if ((long long)K * ex.full_h * ex.full_w >= (1LL << 31))
+            return fail(TS2D_ERR_INVALID, "%s%s: %d x %dx%d exceeds 2^31 output elements", pre, what, K, ex.full_h, ex.full_w);
     }
     if (pl->n_tiles_all * pl->V >= (1LL << 28)) return fail(TS2D_ERR_INVALID, "%s: %lld network rows in one call", entry, pl->n_tiles_all * pl->V);
     return TS2D_OK;
@@ -127,18 +123,18 @@ int pack_rows(int F, int C, int K, const ts2d_tiled_image* images, int n_images,
     return TS2D_OK;
 }
 
-// The export: one segment per image (its half logits are segs' out_off), the taps of its rows then of its columns.
-// rs_elems: elements of the resampled outputs.
-// `prob`: a probabilities call - the lanes of a segment walk the full extent, and beside every RsSeg goes a ProbSeg with the image's places
-// in the float outputs (prob_elems) and in the decided maps (rs_elems); with `prob->runs` a ProbStackSeg, the places being those of the image's slice in its run
-int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap, bool regions, const ProbCall* prob,
-                int n_images, const char* entry, SwPlan* pl, std::vector<RsTap>* rtaps, long long* rs_elems) {
+// The tail: one segment per image (its half logits are segs' out_off), the taps of its rows then of its columns.
+// rs_elems: elements of the resampled uint8 outputs (the decided maps of a probabilities tail).
+// A probabilities tail: beside every RsSeg goes a ProbSeg with the image's places in the float outputs (prob_elems) and in the decided maps
+// (rs_elems); of runs a ProbStackSeg, the places being those of the image's slice in its run.
+int plan_export(int K, const ts2d_tiled_image* images, const SwTail& tail, int n_images, const char* entry, SwPlan* pl, std::vector<RsTap>* rtaps,
+                long long* rs_elems) {
     long long oo = 0;
+    const int D = tail.decided_planes(K);
     // runs: the outputs of a run are [K][n_slices][full_h][full_w] (one contiguous piece per head), its taps are planned with its first slice
     // and every other slice's segment is that one at its own half planes and blocks
-    for (int r = 0; prob && r < prob->n_runs; ++r) {
-        const ts2d_tiled_probabilities_run& rn = prob->runs[r];
-        const int full_hw[2] = {rn.full_h, rn.full_w};
+    for (int r = 0; r < tail.n_runs; ++r) {
+        const ts2d_tiled_probabilities_run& rn = tail.runs[r];
         const long long fplane = (long long)rn.full_h * rn.full_w, run_plane = fplane * rn.n_slices;
         const size_t first = pl->rsegs.size();
         const long long oo_first = oo;
@@ -146,7 +142,7 @@ int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* 
             const int i = rn.first_image + s;
             pl->pssegs.push_back(ProbStackSeg{pl->prob_elems + s * fplane, *rs_elems + s * fplane, run_plane, run_plane, rn.full_h, rn.full_w, rn.box_y, rn.box_x});
             if (s == 0) {
-                rs_plan_segment(true, K, images[i].Hp, images[i].Wp, exports[i], oo, &pl->rsegs, rtaps, &pl->rs_blocks, nullptr, full_hw);
+                rs_plan_segment(tail, i, K, images[i].Hp, images[i].Wp, oo, &pl->rsegs, rtaps, &pl->rs_blocks, nullptr);
             } else {
                 RsSeg rs = pl->rsegs[first];
                 rs.src_off += oo - oo_first; rs.block0 = (unsigned)pl->rs_blocks;
@@ -156,34 +152,32 @@ int plan_export(int K, const ts2d_tiled_image* images, const ts2d_tiled_export* 
             oo += (long long)align_up((size_t)K * images[i].Hp * images[i].Wp, 256);
         }
         pl->prob_elems += (long long)align_up((size_t)K * run_plane, 256);
-        *rs_elems += (long long)align_up((size_t)(prob->mode == kProbMultilabel ? K : 1) * run_plane, 256);
+        *rs_elems += (long long)align_up((size_t)D * run_plane, 256);
     }
-    for (int i = 0; i < n_images && !(prob && prob->runs); ++i) {
-        if (prob) {
-            const ts2d_tiled_probabilities& pd = prob->descs[i];
-            const int full_hw[2] = {pd.full_h, pd.full_w};
+    for (int i = 0; i < n_images && tail.kind != SwTail::kProbRuns; ++i) {
+        rs_plan_segment(tail, i, K, images[i].Hp, images[i].Wp, oo, &pl->rsegs, rtaps, &pl->rs_blocks, rs_elems);
+        if (tail.prob()) {
+            const SwTail::Image& pd = tail.images[i];
             const size_t fplane = (size_t)pd.full_h * pd.full_w;
             pl->psegs.push_back(ProbSeg{pl->prob_elems, *rs_elems, pd.full_h, pd.full_w, pd.box_y, pd.box_x});
-            rs_plan_segment(true, K, images[i].Hp, images[i].Wp, exports[i], oo, &pl->rsegs, rtaps, &pl->rs_blocks, nullptr, full_hw);
             pl->prob_elems += (long long)align_up((size_t)K * fplane, 256);
-            *rs_elems += (long long)align_up((prob->mode == kProbMultilabel ? (size_t)K : 1) * fplane, 256);
-        } else {
-            rs_plan_segment(labelmap, K, images[i].Hp, images[i].Wp, exports[i], oo, &pl->rsegs, rtaps, &pl->rs_blocks, rs_elems, nullptr);
+            *rs_elems += (long long)align_up((size_t)D * fplane, 256);
         }
         oo += (long long)align_up((size_t)K * images[i].Hp * images[i].Wp, 256);
     }
-    if (pl->rs_blocks >= (1LL << 31))
-        return fail(TS2D_ERR_INVALID, "%s: the %s exceeds 2^31 blocks", entry, prob ? "probabilities" : regions ? "regions" : labelmap ? "labelmap" : "export");
+    if (pl->rs_blocks >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "%s: the %s exceeds 2^31 blocks", entry, tail.what());
     return TS2D_OK;
 }
 
 }  // namespace
 
-void rs_plan_segment(bool labelmap, int K, int Hp, int Wp, const ts2d_tiled_export& ex, long long src_off, std::vector<RsSeg>* rsegs,
-                     std::vector<RsTap>* rtaps, long long* blocks, long long* rs_elems, const int* full_hw) {
-    const int planes = labelmap ? 1 : K;          // of the output: the label map is ONE plane, its lanes walk the K source planes
+void rs_plan_segment(const SwTail& tail, int i, int K, int Hp, int Wp, long long src_off, std::vector<RsSeg>* rsegs, std::vector<RsTap>* rtaps,
+                     long long* blocks, long long* rs_elems) {
+    const SwTail::Image& ex = tail.images[(size_t)i];
+    const bool labelmap = tail.kind != SwTail::kExport, full = tail.prob();
+    const int planes = tail.planes(K);          // of the output: the label map is ONE plane, its lanes walk the K source planes
     RsSeg rs{};
-    rs.src_off = src_off; rs.dst_off = full_hw ? 0 : *rs_elems; rs.Hp = Hp; rs.Wp = Wp; rs.out_h = ex.out_h; rs.out_w = ex.out_w;
+    rs.src_off = src_off; rs.dst_off = full ? 0 : *rs_elems; rs.Hp = Hp; rs.Wp = Wp; rs.out_h = ex.out_h; rs.out_w = ex.out_w;
     rs.block0 = (unsigned)*blocks;
     if (labelmap && ex.out_h == ex.src_h && ex.out_w == ex.src_w) {      // the host route does not resample then: no taps, no weights
         rs.tap0 = -1; rs.src_off += (long long)ex.src_y * Wp + ex.src_x;
@@ -194,14 +188,13 @@ void rs_plan_segment(bool labelmap, int K, int Hp, int Wp, const ts2d_tiled_expo
         rs_axis_taps(ex.src_w, ex.out_w, ex.src_x, rtaps->data() + rs.tap0 + ex.out_h);
     }
     rsegs->push_back(rs);
-    if (full_hw) { *blocks += blocks_of((long long)full_hw[0] * ((full_hw[1] + 3) / 4)); return; }      // (its outputs: the caller's ProbSeg)
+    if (full) { *blocks += blocks_of((long long)ex.full_h * ((ex.full_w + 3) / 4)); return; }      // (its outputs: the caller's ProbSeg)
     *blocks += blocks_of((long long)planes * ex.out_h * ((ex.out_w + 3) / 4));
     *rs_elems += (long long)align_up((size_t)planes * ex.out_h * ex.out_w, 256);
 }
 
-int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const ts2d_tiled_export* exports, bool labelmap,
-               const uint8_t* class_order, const ProbCall* prob, int n_images, int ph, int pw, int mirror_mask, bool name_images,
-               const char* entry, SwPlan* pl) {
+int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, const SwTail& tail, int n_images, int ph, int pw, int mirror_mask,
+               bool name_images, const char* entry, SwPlan* pl) {
     if (ph < 1 || pw < 1) return fail(TS2D_ERR_INVALID, "%s: bad patch %dx%d", entry, ph, pw);
     const int C = e->arch.input_channels, K = e->arch.num_classes;
     int vflip[4] = {0, 0, 0, 0};
@@ -211,24 +204,24 @@ int plan_tiled(const ts2d_engine* e, int F, const ts2d_tiled_image* images, cons
     pl->vflips = vflip[0] | (vflip[1] << 8) | (vflip[2] << 16) | (vflip[3] << 24);
     long long img_floats = 0, log_rows = 0, rs_elems = 0;
     std::vector<RsTap> rtaps;
-    const bool regions = class_order != nullptr;
-    TRY(check_images(F, C, K, images, exports, labelmap, regions, prob, n_images, ph, pw, name_images, entry, pl));
+    const bool regions = tail.class_order != nullptr, exports = tail.kind != SwTail::kNone;
+    TRY(check_images(F, C, K, images, tail, n_images, ph, pw, name_images, entry, pl));
     TRY(pack_rows(F, C, K, images, n_images, ph, pw, entry, pl, &img_floats, &log_rows));
-    if (exports) TRY(plan_export(K, images, exports, labelmap, regions, prob, n_images, entry, pl, &rtaps, &rs_elems));
+    if (exports) TRY(plan_export(K, images, tail, n_images, entry, pl, &rtaps, &rs_elems));
     // ---- the descriptor table and every tile origin
     const size_t n_tiles = (size_t)pl->n_tiles_all;
     pl->tab_segs = pl->segs.size() * sizeof(SwSeg); pl->tab_rsegs = align_up(pl->tab_segs + 2 * n_tiles * 4, 8);
     pl->tab_rtaps = pl->tab_rsegs + pl->rsegs.size() * sizeof(RsSeg);
     pl->tab_order = pl->tab_rtaps + rtaps.size() * sizeof(RsTap);
     pl->tab_psegs = align_up(pl->tab_order + (regions ? (size_t)K : 0), 8);
-    pl->tab.resize(prob ? pl->tab_psegs + pl->psegs.size() * sizeof(ProbSeg) + pl->pssegs.size() * sizeof(ProbStackSeg) : pl->tab_order + (regions ? (size_t)K : 0));
-    if (prob && prob->runs) memcpy(pl->tab.data() + pl->tab_psegs, pl->pssegs.data(), pl->pssegs.size() * sizeof(ProbStackSeg));
-    else if (prob) memcpy(pl->tab.data() + pl->tab_psegs, pl->psegs.data(), pl->psegs.size() * sizeof(ProbSeg));
-    if (regions) memcpy(pl->tab.data() + pl->tab_order, class_order, (size_t)K);      // (K == n_order: the entry has checked it)
+    pl->tab.resize(tail.prob() ? pl->tab_psegs + pl->psegs.size() * sizeof(ProbSeg) + pl->pssegs.size() * sizeof(ProbStackSeg) : pl->tab_order + (regions ? (size_t)K : 0));
+    if (tail.kind == SwTail::kProbRuns) memcpy(pl->tab.data() + pl->tab_psegs, pl->pssegs.data(), pl->pssegs.size() * sizeof(ProbStackSeg));
+    else if (tail.prob()) memcpy(pl->tab.data() + pl->tab_psegs, pl->psegs.data(), pl->psegs.size() * sizeof(ProbSeg));
+    if (regions) memcpy(pl->tab.data() + pl->tab_order, tail.class_order, (size_t)K);      // (K == n_order: the entry has checked it)
     memcpy(pl->tab.data(), pl->segs.data(), pl->tab_segs);
     if (exports) {
         memcpy(pl->tab.data() + pl->tab_rsegs, pl->rsegs.data(), pl->rsegs.size() * sizeof(RsSeg));
-        memcpy(pl->tab.data() + pl->tab_rtaps, rtaps.data(), rtaps.size() * sizeof(RsTap));
+        if (!rtaps.empty()) memcpy(pl->tab.data() + pl->tab_rtaps, rtaps.data(), rtaps.size() * sizeof(RsTap));      // (no taps: no pointer to copy from)
     }
     int32_t* ty = reinterpret_cast<int32_t*>(pl->tab.data() + pl->tab_segs); int32_t* tx = ty + n_tiles;
     for (int i = 0; i < n_images; ++i) {

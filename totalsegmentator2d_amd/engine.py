@@ -243,7 +243,7 @@ class Engine:
         tiles: [(y, x), ...] in upstream order; gaussian: float16 [ph,pw] or None.  Returns (float16 [K,Hp,Wp] or None,
         uint8 [K,Hp,Wp] or None)."""
         desc, _, mask, g, keep, outs = self._tiled_args(None, [image], [tiles], None, mirror_axes, gaussian, False, False, want_logits, want_seg)
-        d = desc[0]
+        d = desc[0]                  # (the one entry without descriptors: it makes its own call, _tiled_call serves the others)
         _lib.check(self.lib.ts2d_engine_predict_tiled(self._h, d.image, d.Hp, d.Wp, int(patch[0]), int(patch[1]), d.n_tiles, d.tile_y, d.tile_x,
                                                       mask, g, d.logits_f16, d.seg_u8), 'ts2d_engine_predict_tiled')
         _read_tiled_inf([self], None, 0, engine_flags=True)                          # upstream's inf check, done on the device
@@ -258,12 +258,8 @@ class Engine:
         The network takes the full-batch dispatch whatever the batch: an image's bytes do not depend on its batch-mates, its position
         or the batch size, and equal :meth:`predict_tiled` on an engine with ``options={'sbk': 0}`` bit for bit.
         Sets ``last_tiled_inf`` (the OR over the images) and ``last_tiled_inf_per_image``."""
-        desc, _, mask, g, keep, outs = self._tiled_args('predict_tiled_batch', images, tiles, None, mirror_axes, gaussian,
-                                                        False, False, want_logits, want_seg)
-        _lib.check(self.lib.ts2d_engine_predict_tiled_batch(self._h, desc, len(images), int(patch[0]), int(patch[1]), mask, g),
-                   'ts2d_engine_predict_tiled_batch')
-        _read_tiled_inf([self], desc, len(images), engine_flags=False)
-        del keep
+        outs = _tiled_call('predict_tiled_batch', 'ts2d_engine_predict_tiled_batch', [self], False, images, patch, tiles, None, mirror_axes, gaussian,
+                           (False, False, want_logits, want_seg), spell=lambda desc, n, common, keep: (desc, n) + common)
         return outs[2], outs[3]
 
     def predict_tiled_export(self, images, patch, tiles, exports, mirror_axes=None, gaussian: Optional[np.ndarray] = None,
@@ -277,41 +273,35 @@ class Engine:
         ``full_batch``: the full-batch dispatch of :meth:`predict_tiled_batch` (an image's bytes do not depend on its batch-mates);
         False: the size-dependent dispatch of :meth:`predict_tiled`.  The resampled values equal
         ``preprocess.resize_linear_f64`` of the float16 logits bit for bit.  Sets ``last_tiled_inf`` / ``last_tiled_inf_per_image``."""
-        desc, exd, mask, g, keep, outs = self._tiled_args('predict_tiled_export', images, tiles, exports, mirror_axes, gaussian,
-                                                          want_seg, want_f32, want_logits, want_padded_seg)
-        _lib.check(self.lib.ts2d_engine_predict_tiled_export(self._h, desc, exd, len(images), int(patch[0]), int(patch[1]), mask, g,
-                                                             int(bool(full_batch))), 'ts2d_engine_predict_tiled_export')
-        _read_tiled_inf([self], desc, len(images), engine_flags=False)
-        del keep
-        return outs
+        return _tiled_call('predict_tiled_export', 'ts2d_engine_predict_tiled_export', [self], False, images, patch, tiles, exports, mirror_axes,
+                           gaussian, (want_seg, want_f32, want_logits, want_padded_seg), full_batch=full_batch)
 
-    def _tiled_args(self, what, images, tiles, exports, mirror_axes, gaussian, want_seg, want_f32, want_logits, want_padded_seg,
-                    labelmap: bool = False, prob_mode: Optional[int] = None, runs: bool = False):
+    def _tiled_args(self, what, images, tiles, exports, mirror_axes, gaussian, want_seg, want_f32, want_logits, want_padded_seg, kind: str = 'export'):
         """Argument preparation of every tiled call (`what` names the calling method in a message): the ``TiledImage`` array, the
-        ``TiledExport`` array (None without ``exports``: no resample-back), the mirror mask, the address of the half gaussian (or None),
-        the arrays all of these point into - they must outlive the call - and the output lists ``(seg, f32, logits, padded_seg)`` the
-        call fills, each None unless asked for.  ``labelmap``: the descriptors are ``TiledLabelmap`` and ``seg`` holds ONE uint8 plane
-        [out_h,out_w] per image, the label map.  ``what`` None is the one image of :meth:`predict_tiled`: its messages carry no
-        ``image i: `` and everything but the channel count is left to the library (or to the unpacking of the shape) to refuse.
-        ``prob_mode`` (a ``_lib.PROB_*``): the descriptors are ``TiledProbabilities`` from ``exports`` of ten numbers (the six, then
-        ``full_h, full_w, box_y, box_x``); ``f32`` holds the float32 probabilities [K,full_h,full_w] and ``seg`` the decided uint8 map
-        of the full extent ([K,full_h,full_w] multilabel, else [full_h,full_w]).  ``runs``: the outputs are described apart from the
-        images (:func:`predict_tiled_probabilities_stack_ensemble`): no ``exports``, and no output of these lists need be asked for."""
+        descriptor array of the tail ``kind`` (``_TAILS``; None without ``exports``: no resample-back), the mirror mask, the address of the
+        half gaussian (or None), the arrays all of these point into - they must outlive the call - and the output lists ``(seg, f32,
+        logits, padded_seg)`` the call fills, each None unless asked for.  ``seg`` / ``f32`` are the uint8 / float32 output of the kind:
+        'export' [K,out_h,out_w] both; 'labelmap' ONE uint8 plane [out_h,out_w], the label map; 'probabilities' (``exports`` of ten
+        numbers: the six, then ``full_h, full_w, box_y, box_x``) the float32 probabilities [K,full_h,full_w] and the decided uint8 map
+        [full_h,full_w] - [K,full_h,full_w] of 'probabilities_multilabel'.  'runs': the outputs are described apart from the images
+        (:func:`predict_tiled_probabilities_stack_ensemble`): no ``exports``, and no output of these lists need be asked for.
+        ``what`` None is the one image of :meth:`predict_tiled`: its messages carry no ``image i: `` and everything but the channel
+        count is left to the library (or to the unpacking of the shape) to refuse."""
+        struct, u8_field, f32_field, u8_heads, full_extent = _TAILS[kind]
         one = what is None
         if len(images) != len(tiles) or (exports is not None and len(exports) != len(images)):
             raise RuntimeError(f"{len(images)} images but {len(tiles)} tile lists" + ("" if exports is None else f" and {len(exports)} exports"))
         if exports is None:
             if want_seg or want_f32:
                 raise RuntimeError(f"{what}: the resampled outputs need exports")
-            if not (want_logits or want_padded_seg or one or runs):
+            if not (want_logits or want_padded_seg or one or kind == 'runs'):
                 raise RuntimeError(f"{what}: neither logits nor segmentation requested")
         elif not (want_seg or want_f32):
             raise RuntimeError(f"{what}: neither the resampled segmentation nor the resampled logits requested")
         K = self.arch.num_classes
         keep = []                    # every array the descriptors point into stays alive until the call returns
         n = max(len(images), 1)
-        kind = _lib.TiledProbabilities if prob_mode is not None else _lib.TiledLabelmap if labelmap else _lib.TiledExport
-        desc, exd = (_lib.TiledImage * n)(), (None if exports is None else (kind * n)())
+        desc, exd = (_lib.TiledImage * n)(), (None if exports is None else (struct * n)())
         seg, f32, out16, pseg = [], [], [], []
         for i, (image, tl) in enumerate(zip(images, tiles)):
             at = '' if one else f'image {i}: '
@@ -333,26 +323,18 @@ class Engine:
             d.seg_u8 = pseg[i].ctypes.data if want_padded_seg else None
             if exports is None:
                 continue
-            sy, sx, sh, sw_, oh, ow = (int(v) for v in exports[i][:6])
             x = exd[i]
-            if prob_mode is not None:
-                fh, fw, by, bx = (int(v) for v in exports[i][6:])
-                full = (max(fh, 0), max(fw, 0))                                    # (a bad extent is the library's to reject, by name)
-                f32.append(np.empty((K,) + full, dtype=np.float32))
-                seg.append(np.empty(((K,) if prob_mode == _lib.PROB_MULTILABEL else ()) + full, dtype=np.uint8) if want_seg else None)
-                x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w = sy, sx, sh, sw_, oh, ow
-                x.full_h, x.full_w, x.box_y, x.box_x = fh, fw, by, bx
-                x.prob_f32, x.decided_u8 = f32[i].ctypes.data, (seg[i].ctypes.data if want_seg else None)
-                continue
-            shape = (() if labelmap else (K,)) + (max(oh, 0), max(ow, 0))          # (a bad extent is the library's to reject, by name)
-            seg.append(np.empty(shape, dtype=np.uint8) if want_seg else None)
-            f32.append(np.empty(shape, dtype=np.float32) if want_f32 else None)
-            x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w = sy, sx, sh, sw_, oh, ow
-            if labelmap:
-                x.label_u8 = seg[i].ctypes.data
-                continue
-            x.seg_u8 = seg[i].ctypes.data if want_seg else None
-            x.logits_f32 = f32[i].ctypes.data if want_f32 else None
+            x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w = six = tuple(int(v) for v in exports[i][:6])
+            extent = six[4:]
+            if full_extent:
+                x.full_h, x.full_w, x.box_y, x.box_x = four = tuple(int(v) for v in exports[i][6:])
+                extent = four[:2]
+            extent = tuple(max(v, 0) for v in extent)                              # (a bad extent is the library's to reject, by name)
+            seg.append(np.empty(((K,) if u8_heads else ()) + extent, dtype=np.uint8) if want_seg else None)
+            f32.append(np.empty((K,) + extent, dtype=np.float32) if want_f32 else None)
+            setattr(x, u8_field, seg[i].ctypes.data if want_seg else None)
+            if f32_field:
+                setattr(x, f32_field, f32[i].ctypes.data if want_f32 else None)
         mask = 0
         for a in (mirror_axes or ()):
             mask |= 1 << int(a)
@@ -433,6 +415,76 @@ class Engine:
         return int(self.lib.ts2d_engine_device_bytes(self._h))
 
 
+# The tails of a tiled call by kind: the descriptor struct of an image (None: none), its uint8 and its float32 output field, whether the uint8
+# output has the K heads in front (the float32 one always has), whether both are of the full extent (the descriptor then has ten numbers).
+_TAILS = {'export': (_lib.TiledExport, 'seg_u8', 'logits_f32', True, False),
+          'labelmap': (_lib.TiledLabelmap, 'label_u8', None, False, False),
+          'probabilities': (_lib.TiledProbabilities, 'decided_u8', 'prob_f32', False, True),
+          'probabilities_multilabel': (_lib.TiledProbabilities, 'decided_u8', 'prob_f32', True, True),
+          'runs': (None, None, None, False, False)}
+
+
+def _tiled_call(what, name, engines, ensemble: bool, images, patch, tiles, exports, mirror_axes, gaussian, wants, kind: str = 'export',
+                full_batch=None, need: Optional[str] = None, extra=None, spell=None):
+    """THE call of every tiled entry ``name`` that takes descriptors, for the method ``what``: the engines check, what the method needs of ``exports`` (``need``: the
+    words of the refusal where they are None), its trailing arguments (``extra()`` -> ``(arguments, what they point into)``), the entry,
+    :meth:`Engine._tiled_args` with ``wants = (seg, f32, logits, padded_seg)`` and ``kind``, the fold handles of an ``ensemble`` entry (else the
+    one engine's), the call, the inf flags and the keep-alive.  The arguments between the handles and the trailing ones are ``desc, exd, n, ph, pw,
+    mask, g`` and ``full_batch`` unless None, or what ``spell(desc, n, (ph, pw, mask, g), keep)`` returns.  Returns the four output lists."""
+    engines = list(engines)
+    if not engines:
+        raise RuntimeError(f"{what}: no engines")
+    if need is not None and exports is None:
+        raise RuntimeError(f"{what}: {need}")
+    tail, keep_tail = extra() if extra else ((), None)
+    fn = _entry(name, engines[0].lib)
+    desc, exd, mask, g, keep, outs = engines[0]._tiled_args(what, images, tiles, exports, mirror_axes, gaussian, *wants, kind=kind)
+    n, common = len(images), (int(patch[0]), int(patch[1]), mask, g)
+    head = ((ctypes.c_void_p * len(engines))(*[e._h for e in engines]), len(engines)) if ensemble else (engines[0]._h,)
+    args = spell(desc, n, common, keep) if spell else (desc, exd, n) + common + (() if full_batch is None else (int(bool(full_batch)),))
+    _lib.check(fn(*head, *args, *tail), name)
+    _read_tiled_inf(engines, desc, n, engine_flags=ensemble)
+    del keep, keep_tail
+    return outs
+
+
+def _order_args(order):
+    """The trailing ``class_order, n_order`` of an entry -> ``(arguments, the array they point into)``."""
+    return ((None, 0) if order is None else (order.ctypes.data, int(order.size))), order
+
+
+def _from_logits(kind, logits_f16, rect, out_hw, device, class_order=None, prob=None):
+    """The marshalling of the three ``<kind>_from_logits`` wrappers (C-ABI ``ts2d_<kind>_from_logits``), ``kind`` 'labelmap', 'regions' (with its
+    ``class_order``) or 'probabilities' (with ``prob = (mode, full_hw, box_yx, want_decided)``, and the ``class_order`` of its regions mode).
+    Returns the label map, or ``(probabilities, decided)``."""
+    what = kind + '_from_logits'
+    lg = np.ascontiguousarray(logits_f16, dtype=np.float16)
+    if lg.ndim != 3:
+        raise RuntimeError(f"expected [K,H,W], found shape {lg.shape}")
+    K, code, order = lg.shape[0], None, None
+    if prob is not None:
+        code, order = _prob_mode(prob[0], class_order, what)
+    elif kind == 'regions':
+        order = _class_order_u8(class_order, what)
+    if order is not None and order.size != K:
+        raise RuntimeError(f"{what}: {order.size} class values for {K} heads")
+    oh, ow = (int(v) for v in out_hw)
+    if prob is None:
+        out = result = np.empty((max(oh, 0), max(ow, 0)), dtype=np.uint8)
+        tail = (() if order is None else (order.ctypes.data,)) + (out.ctypes.data,)
+    else:
+        fh, fw = (int(v) for v in prob[1])
+        by, bx = (int(v) for v in prob[2])
+        full = (max(fh, 0), max(fw, 0))
+        out = np.empty((K,) + full, dtype=np.float32)
+        dec = np.empty(((K,) if code == _lib.PROB_MULTILABEL else ()) + full, dtype=np.uint8) if prob[3] else None
+        tail = (fh, fw, by, bx, code, None if order is None else order.ctypes.data, out.ctypes.data, None if dec is None else dec.ctypes.data)
+        result = (out, dec)
+    r = (ctypes.c_int32 * 4)(*[int(v) for v in rect])
+    _lib.check(_entry('ts2d_' + what)(int(device), lg.ctypes.data, K, lg.shape[1], lg.shape[2], ctypes.byref(r), oh, ow, *tail), 'ts2d_' + what)
+    return result
+
+
 def predict_tiled_export_ensemble(engines, images, patch, tiles, exports, mirror_axes=None, gaussian: Optional[np.ndarray] = None,
                                   want_seg: bool = True, want_f32: bool = False, want_logits: bool = False, want_padded_seg: bool = False,
                                   full_batch: bool = True):
@@ -443,17 +495,8 @@ def predict_tiled_export_ensemble(engines, images, patch, tiles, exports, mirror
     resample-back: ``want_seg`` / ``want_f32`` must be off and ``want_logits`` or ``want_padded_seg`` on).  One engine: that method's
     bytes.  Sets ``last_tiled_inf_per_image`` on the first engine (per image the OR over the folds: upstream checks every fold's
     array) and ``last_tiled_inf`` on every engine (that fold's own)."""
-    engines = list(engines)
-    if not engines:
-        raise RuntimeError("predict_tiled_export_ensemble: no engines")
-    desc, exd, mask, g, keep, outs = engines[0]._tiled_args('predict_tiled_export_ensemble', images, tiles, exports, mirror_axes, gaussian,
-                                                            want_seg, want_f32, want_logits, want_padded_seg)
-    handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
-    _lib.check(engines[0].lib.ts2d_ensemble_predict_tiled_export(handles, len(engines), desc, exd, len(images), int(patch[0]), int(patch[1]),
-                                                                 mask, g, int(bool(full_batch))), 'ts2d_ensemble_predict_tiled_export')
-    _read_tiled_inf(engines, desc, len(images), engine_flags=True)
-    del keep
-    return outs
+    return _tiled_call('predict_tiled_export_ensemble', 'ts2d_ensemble_predict_tiled_export', engines, True, images, patch, tiles, exports, mirror_axes,
+                       gaussian, (want_seg, want_f32, want_logits, want_padded_seg), full_batch=full_batch)
 
 
 def predict_tiled_labelmap_ensemble(engines, images, patch, tiles, rects, mirror_axes=None, gaussian: Optional[np.ndarray] = None,
@@ -463,33 +506,15 @@ def predict_tiled_labelmap_ensemble(engines, images, patch, tiles, rects, mirror
     over the heads on the device (csrc/kernels_labelmap.h).  rects: one ``(src_y, src_x, src_h, src_w, out_h, out_w)`` per image.
     Returns ``(labels, logits)``: lists of uint8 [out_h,out_w] - ``export.labelmap_statement`` of the half logits, byte for byte - and
     of float16 [K,Hp,Wp] (those logits; None unless asked for).  Sets the inf flags as :func:`predict_tiled_export_ensemble` does."""
-    engines = list(engines)
-    if not engines:
-        raise RuntimeError("predict_tiled_labelmap_ensemble: no engines")
-    if rects is None:
-        raise RuntimeError("predict_tiled_labelmap_ensemble: the label maps need their rectangles and extents")
-    desc, lmd, mask, g, keep, outs = engines[0]._tiled_args('predict_tiled_labelmap_ensemble', images, tiles, rects, mirror_axes, gaussian,
-                                                            True, False, want_logits, False, labelmap=True)
-    handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
-    _lib.check(engines[0].lib.ts2d_ensemble_predict_tiled_labelmap(handles, len(engines), desc, lmd, len(images), int(patch[0]), int(patch[1]),
-                                                                   mask, g, int(bool(full_batch))), 'ts2d_ensemble_predict_tiled_labelmap')
-    _read_tiled_inf(engines, desc, len(images), engine_flags=True)
-    del keep
+    outs = _tiled_call('predict_tiled_labelmap_ensemble', 'ts2d_ensemble_predict_tiled_labelmap', engines, True, images, patch, tiles, rects, mirror_axes,
+                       gaussian, (True, False, want_logits, False), 'labelmap', full_batch, need='the label maps need their rectangles and extents')
     return outs[0], outs[2]
 
 
 def labelmap_from_logits(logits_f16: np.ndarray, rect, out_hw, device: int = 0) -> np.ndarray:
     """The label-map kernel on half planes of the caller's (C-ABI ts2d_labelmap_from_logits): float16 [K,H,W], ``rect = (y, x, h, w)``
     inside it, resampled to ``out_hw`` and decided over the heads -> uint8 [out_h,out_w] = ``export.labelmap_statement``."""
-    lg = np.ascontiguousarray(logits_f16, dtype=np.float16)
-    if lg.ndim != 3:
-        raise RuntimeError(f"expected [K,H,W], found shape {lg.shape}")
-    oh, ow = (int(v) for v in out_hw)
-    out = np.empty((max(oh, 0), max(ow, 0)), dtype=np.uint8)
-    r = (ctypes.c_int32 * 4)(*[int(v) for v in rect])
-    _lib.check(_lib.load().ts2d_labelmap_from_logits(int(device), lg.ctypes.data, lg.shape[0], lg.shape[1], lg.shape[2], ctypes.byref(r), oh, ow,
-                                                     out.ctypes.data), 'ts2d_labelmap_from_logits')
-    return out
+    return _from_logits('labelmap', logits_f16, rect, out_hw, device)
 
 
 def _class_order_u8(class_order, what: str) -> np.ndarray:
@@ -507,38 +532,17 @@ def predict_tiled_regions_ensemble(engines, images, patch, tiles, rects, class_o
     ``sigmoid(float32 v) > 0.5`` per head and the painting in order on the device (csrc/kernels_regions.h).  ``class_order``: one class
     value (0..255) per head, ``regions_class_order`` of the model's ``dataset.json``.  Returns ``(labels, logits)``: lists of uint8
     [out_h,out_w] - ``export.regions_statement`` of the half logits, byte for byte - and of float16 [K,Hp,Wp] (None unless asked for)."""
-    engines = list(engines)
-    if not engines:
-        raise RuntimeError("predict_tiled_regions_ensemble: no engines")
-    if rects is None:
-        raise RuntimeError("predict_tiled_regions_ensemble: the maps need their rectangles and extents")
-    order = _class_order_u8(class_order, 'predict_tiled_regions_ensemble')
-    desc, lmd, mask, g, keep, outs = engines[0]._tiled_args('predict_tiled_regions_ensemble', images, tiles, rects, mirror_axes, gaussian,
-                                                            True, False, want_logits, False, labelmap=True)
-    handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
-    _lib.check(engines[0].lib.ts2d_ensemble_predict_tiled_regions(handles, len(engines), desc, lmd, len(images), int(patch[0]), int(patch[1]),
-                                                                  mask, g, int(bool(full_batch)), order.ctypes.data, int(order.size)),
-               'ts2d_ensemble_predict_tiled_regions')
-    _read_tiled_inf(engines, desc, len(images), engine_flags=True)
-    del keep
+    what = 'predict_tiled_regions_ensemble'
+    outs = _tiled_call(what, 'ts2d_ensemble_predict_tiled_regions', engines, True, images, patch, tiles, rects, mirror_axes, gaussian,
+                       (True, False, want_logits, False), 'labelmap', full_batch, need='the maps need their rectangles and extents',
+                       extra=lambda: _order_args(_class_order_u8(class_order, what)))
     return outs[0], outs[2]
 
 
 def regions_from_logits(logits_f16: np.ndarray, rect, out_hw, class_order, device: int = 0) -> np.ndarray:
     """The region kernel on half planes of the caller's (C-ABI ts2d_regions_from_logits): float16 [K,H,W], ``rect = (y, x, h, w)`` inside
     it, resampled to ``out_hw``, thresholded per head and painted in order -> uint8 [out_h,out_w] = ``export.regions_statement``."""
-    lg = np.ascontiguousarray(logits_f16, dtype=np.float16)
-    if lg.ndim != 3:
-        raise RuntimeError(f"expected [K,H,W], found shape {lg.shape}")
-    order = _class_order_u8(class_order, 'regions_from_logits')
-    if order.size != lg.shape[0]:
-        raise RuntimeError(f"regions_from_logits: {order.size} class values for {lg.shape[0]} heads")
-    oh, ow = (int(v) for v in out_hw)
-    out = np.empty((max(oh, 0), max(ow, 0)), dtype=np.uint8)
-    r = (ctypes.c_int32 * 4)(*[int(v) for v in rect])
-    _lib.check(_lib.load().ts2d_regions_from_logits(int(device), lg.ctypes.data, lg.shape[0], lg.shape[1], lg.shape[2], ctypes.byref(r), oh, ow,
-                                                    order.ctypes.data, out.ctypes.data), 'ts2d_regions_from_logits')
-    return out
+    return _from_logits('regions', logits_f16, rect, out_hw, device, class_order)
 
 
 def _prob_mode(mode, class_order, what: str):
@@ -590,20 +594,13 @@ def predict_tiled_probabilities_ensemble(engines, images, patch, tiles, rects, m
     logits to within a few float32 units - of uint8 [full_h,full_w] ([K,full_h,full_w] multilabel; None unless ``want_decided``) - inside
     the box byte for byte what the label-map / regions / threshold routes give, 0 outside - and of float16 [K,Hp,Wp] (None unless asked)."""
     what = 'predict_tiled_probabilities_ensemble'
-    engines = list(engines)
-    if not engines:
-        raise RuntimeError(f"{what}: no engines")
-    if rects is None:
-        raise RuntimeError(f"{what}: the probabilities need their rectangles and extents")
-    code, order = _prob_mode(mode, class_order, what)
-    fn = _entry('ts2d_ensemble_predict_tiled_probabilities', engines[0].lib)
-    desc, pd, mask, g, keep, outs = engines[0]._tiled_args(what, images, tiles, rects, mirror_axes, gaussian, bool(want_decided), True, want_logits,
-                                                           False, labelmap=True, prob_mode=code)
-    handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
-    _lib.check(fn(handles, len(engines), desc, pd, len(images), int(patch[0]), int(patch[1]), mask, g, int(bool(full_batch)), code,
-                  None if order is None else order.ctypes.data, 0 if order is None else int(order.size)), 'ts2d_ensemble_predict_tiled_probabilities')
-    _read_tiled_inf(engines, desc, len(images), engine_flags=True)
-    del keep
+
+    def extra():
+        code, order = _prob_mode(mode, class_order, what)
+        return (code,) + _order_args(order)[0], order
+    outs = _tiled_call(what, 'ts2d_ensemble_predict_tiled_probabilities', engines, True, images, patch, tiles, rects, mirror_axes, gaussian,
+                       (bool(want_decided), True, want_logits, False), 'probabilities_multilabel' if mode == 'multilabel' else 'probabilities',
+                       full_batch, need='the probabilities need their rectangles and extents', extra=extra)
     return outs[1], outs[0], outs[2]
 
 
@@ -623,60 +620,42 @@ def predict_tiled_probabilities_stack_ensemble(engines, images, patch, tiles, ru
     of float16 [K,Hp,Wp] logits (None unless ``want_logits``).  Sets the inf flags as :func:`predict_tiled_export_ensemble` does."""
     what = 'predict_tiled_probabilities_stack_ensemble'
     engines = list(engines)
-    if not engines:
-        raise RuntimeError(f"{what}: no engines")
-    code, order = _prob_mode(mode, class_order, what)
-    fn = _entry('ts2d_ensemble_predict_tiled_probabilities_stack', engines[0].lib)
-    desc, _, mask, g, keep, outs = engines[0]._tiled_args(what, images, tiles, None, mirror_axes, gaussian, False, False, want_logits, False, runs=True)
-    K = engines[0].arch.num_classes
-    rd = (_lib.TiledProbabilitiesRun * max(len(runs), 1))()
-    for r, (first, n, rect, prob, dec) in enumerate(runs):
-        x = rd[r]
-        (x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w, x.full_h, x.full_w, x.box_y, x.box_x) = (int(v) for v in rect)
-        x.first_image, x.n_slices = int(first), int(n)
-        for name, a, dt, heads in (('prob', prob, np.float32, True), ('decided', dec, np.uint8, code == _lib.PROB_MULTILABEL)):
-            if a is None and name == 'decided':
-                continue
-            tail = (int(n), max(x.full_h, 0), max(x.full_w, 0))              # (a bad extent is the library's to reject, by name)
-            if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != ((K,) if heads else ()) + tail or not a.flags.writeable \
-                    or not a[0 if heads else slice(None)].flags.c_contiguous or (heads and a.strides[0] % a.itemsize):
-                raise RuntimeError(f"{what}: run {r}: {name} must be a writeable {np.dtype(dt).name} view {((K,) if heads else ()) + tail}, dense below the heads")
-            stride = a.strides[0] // a.itemsize if heads else 0
-            if name == 'prob':
-                x.prob_f32, x.prob_head_stride = a.ctypes.data, stride
-            else:
-                x.decided_u8, x.decided_head_stride = a.ctypes.data, stride
-            keep.append(a)
-    handles = (ctypes.c_void_p * len(engines))(*[e._h for e in engines])
-    _lib.check(fn(handles, len(engines), desc, len(images), rd, len(runs), int(patch[0]), int(patch[1]), mask, g, int(bool(full_batch)), code,
-                  None if order is None else order.ctypes.data, 0 if order is None else int(order.size)), 'ts2d_ensemble_predict_tiled_probabilities_stack')
-    _read_tiled_inf(engines, desc, len(images), engine_flags=True)
-    del keep
-    return outs[2]
+
+    def extra():
+        code, order = _prob_mode(mode, class_order, what)
+        return (code,) + _order_args(order)[0], order
+
+    def spell(desc, n_images, common, keep):           # the run descriptors go between the images and the patch
+        K = engines[0].arch.num_classes
+        rd = (_lib.TiledProbabilitiesRun * max(len(runs), 1))()
+        for r, (first, n, rect, prob, dec) in enumerate(runs):
+            x = rd[r]
+            (x.src_y, x.src_x, x.src_h, x.src_w, x.out_h, x.out_w, x.full_h, x.full_w, x.box_y, x.box_x) = (int(v) for v in rect)
+            x.first_image, x.n_slices = int(first), int(n)
+            for name, a, dt, heads in (('prob', prob, np.float32, True), ('decided', dec, np.uint8, mode == 'multilabel')):
+                if a is None and name == 'decided':
+                    continue
+                tail = (int(n), max(x.full_h, 0), max(x.full_w, 0))              # (a bad extent is the library's to reject, by name)
+                if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != ((K,) if heads else ()) + tail or not a.flags.writeable \
+                        or not a[0 if heads else slice(None)].flags.c_contiguous or (heads and a.strides[0] % a.itemsize):
+                    raise RuntimeError(f"{what}: run {r}: {name} must be a writeable {np.dtype(dt).name} view {((K,) if heads else ()) + tail}, dense below the heads")
+                stride = a.strides[0] // a.itemsize if heads else 0
+                if name == 'prob':
+                    x.prob_f32, x.prob_head_stride = a.ctypes.data, stride
+                else:
+                    x.decided_u8, x.decided_head_stride = a.ctypes.data, stride
+                keep.append(a)
+        keep.append(rd)
+        return (desc, n_images, rd, len(runs)) + common + (int(bool(full_batch)),)
+    return _tiled_call(what, 'ts2d_ensemble_predict_tiled_probabilities_stack', engines, True, images, patch, tiles, None, mirror_axes, gaussian,
+                       (False, False, want_logits, False), 'runs', extra=extra, spell=spell)[2]
 
 
 def probabilities_from_logits(logits_f16: np.ndarray, rect, out_hw, full_hw, box_yx, mode, class_order=None, want_decided: bool = True,
                               device: int = 0):
     """The probabilities kernel on half planes of the caller's (C-ABI ts2d_probabilities_from_logits): float16 [K,H,W], ``rect = (y, x, h, w)``
     inside it, resampled to ``out_hw``, placed at ``box_yx`` of ``full_hw`` -> ``(float32 [K,full_h,full_w], decided uint8 or None)``."""
-    lg = np.ascontiguousarray(logits_f16, dtype=np.float16)
-    if lg.ndim != 3:
-        raise RuntimeError(f"expected [K,H,W], found shape {lg.shape}")
-    code, order = _prob_mode(mode, class_order, 'probabilities_from_logits')
-    if order is not None and order.size != lg.shape[0]:
-        raise RuntimeError(f"probabilities_from_logits: {order.size} class values for {lg.shape[0]} heads")
-    oh, ow = (int(v) for v in out_hw)
-    fh, fw = (int(v) for v in full_hw)
-    by, bx = (int(v) for v in box_yx)
-    full = (max(fh, 0), max(fw, 0))
-    prob = np.empty((lg.shape[0],) + full, dtype=np.float32)
-    dec = np.empty(((lg.shape[0],) if code == _lib.PROB_MULTILABEL else ()) + full, dtype=np.uint8) if want_decided else None
-    r = (ctypes.c_int32 * 4)(*[int(v) for v in rect])
-    fn = _entry('ts2d_probabilities_from_logits')
-    _lib.check(fn(int(device), lg.ctypes.data, lg.shape[0], lg.shape[1], lg.shape[2], ctypes.byref(r), oh, ow, fh, fw, by, bx, code,
-                  None if order is None else order.ctypes.data, prob.ctypes.data, None if dec is None else dec.ctypes.data),
-               'ts2d_probabilities_from_logits')
-    return prob, dec
+    return _from_logits('probabilities', logits_f16, rect, out_hw, device, class_order, (mode, full_hw, box_yx, want_decided))
 
 
 def has_keep_largest_components() -> bool:

@@ -268,66 +268,102 @@ class HIPModel:
             out = [p.predict_logits_from_preprocessed_data(d) if o is None else o for d, o in zip(datas, out)]
         return [o.cpu().numpy() if hasattr(o, 'cpu') else o for o in out]
 
-    def _predict_probabilities(self, group, batched: bool):
-        """Stage 2 of :meth:`_run` for cases that ask for probabilities and can have them from the device: per case ``(decided map,
-        probabilities)`` of the predictor's probabilities method - the extent before resampling, the extent before cropping and the crop
-        box's origin go with each case - or, where it answers None, the logits (:meth:`_predict`): the export then takes the host route."""
+    def _predict_device(self, group, batched: bool, name: str, placed: bool):
+        """Stage 2 of :meth:`_run` for cases whose map the device decides beyond :meth:`_predict`'s reach: per case what the predictor's method
+        ``name`` answers - the decided map of a stack (``predict_stack_...``), or ``(decided map, probabilities)`` (``predict_probabilities_...``,
+        ``predict_stack_probabilities_...``) - or, where it answers None, the logits (:meth:`_predict`): the export then takes the host route.
+        The extent before resampling goes with each case and, with ``placed``, the extent before cropping and the origin of the crop box."""
         p = self._predictor
-        name = 'predict_probabilities_from_preprocessed_data'
         datas = [t[3] for t in group]
-        outs = [tuple(t[4].get('shape_after_cropping_and_before_resampling', np.asarray(t[3]).shape[1:])) for t in group]
-        fulls = [tuple(t[4]['shape_before_cropping']) for t in group]
-        boxes = [tuple(int(b[0]) for b in t[4]['bbox_used_for_cropping']) for t in group]
+        kw = {'out_shape': [tuple(t[4].get('shape_after_cropping_and_before_resampling', np.asarray(t[3]).shape[1:])) for t in group]}
+        if placed:
+            kw['full_shape'] = [tuple(t[4]['shape_before_cropping']) for t in group]
+            kw['box'] = [tuple(int(b[0]) for b in t[4]['bbox_used_for_cropping']) for t in group]
         if batched:
-            out = getattr(p, name + '_batch')(datas, out_shapes=outs, full_shapes=fulls, boxes=boxes)
+            out = getattr(p, name + '_batch')(datas, **{'boxes' if k == 'box' else k + 's': v for k, v in kw.items()})
             out = list(out) if out is not None else [None] * len(group)
         else:
-            out = [getattr(p, name)(d, out_shape=o, full_shape=f, box=b) for d, o, f, b in zip(datas, outs, fulls, boxes)]
+            out = [getattr(p, name)(d, **{k: v[i] for k, v in kw.items()}) for i, d in enumerate(datas)]
         rest = [i for i, o in enumerate(out) if o is None]
         for i, lg in zip(rest, self._predict([datas[i] for i in rest], False, batched) if rest else []):
             out[i] = lg
         return out
 
-    def _predict_stacks(self, group, batched: bool):
-        """Stage 2 of :meth:`_run` for stacks (3-D volumes under a 2-D plan): per case the decided map of the predictor's stack method - the
-        extent before resampling goes with each case - or, where it answers None, the logits (:meth:`_predict`): the export then takes the host route."""
+    def _routes(self, todo, batched: bool, save_probabilities: bool):
+        """The route decision of :meth:`_run`: the preprocessed cases ``todo`` in at most three groups - stacks, fast, rest - each with the call
+        that predicts it, ``[(group, predict), ...]``; ``predict()`` returns one result per case of its group."""
         p = self._predictor
-        name = 'predict_stack_from_preprocessed_data'
-        datas = [t[3] for t in group]
-        outs = [tuple(t[4].get('shape_after_cropping_and_before_resampling', np.asarray(t[3]).shape[1:])) for t in group]
-        if batched:
-            out = getattr(p, name + '_batch')(datas, out_shapes=outs)
-            out = list(out) if out is not None else [None] * len(group)
-        else:
-            out = [getattr(p, name)(d, out_shape=o) for d, o in zip(datas, outs)]
-        rest = [i for i, o in enumerate(out) if o is None]
-        for i, lg in zip(rest, self._predict([datas[i] for i in rest], False, batched) if rest else []):
-            out[i] = lg
-        return out
+        method = lambda name: getattr(p, name + ('_batch' if batched else ''), None)
+        window_takes = lambda keyword: not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, keyword)
+        # product fast path: a multilabel 2-D case gets its segmentation thresholded on the device (K uint8 planes to the host instead
+        # of K float16 ones; the predicate is the export step's, bit for bit).  A case whose export resamples (its spacing is not the
+        # plan's) joins with the extent it had before resampling: the device resamples the logits back (order 1) in front of the
+        # threshold and the export step receives uint8 planes already in that extent.  The reference's seam
+        # (predict_logits_from_preprocessed_data + export_prediction_from_logits) stays as it is and serves every other case
+        kind = label_convention(p.dataset_json).kind
+        multilabel = kind == 'multilabel'
+        fast_fn = method('predict_segmentation_from_preprocessed_data')
+        can_seg = self.device_threshold and multilabel and fast_fn is not None
+        # (a foreign predictor, or a double of the engine method, that knows the fast path but not its `out_shape(s)` keyword keeps
+        #  the host route for resampled cases, as before the device export existed)
+        can_export = can_seg and self._takes(fast_fn, 'out_shapes' if batched else 'out_shape') and window_takes('out_shapes')
+        # a label-map model (the ordinary nnU-Net head): the same two host steps - resample-back, then the argmax over the heads - on the
+        # device, ONE uint8 plane per case to the host; the export step receives it as the decided label map.  Only a predictor that has
+        # the method (and, where it is a double of the engine method, its `labelmap` keyword) takes this route.  A region-based model goes
+        # the same way under its own switch and keyword (`regions`: sigmoid predicate per head, painted in class order, kernels_regions.h)
+        lm_name = 'predict_labelmap_from_preprocessed_data'
+        lm_fn = method(lm_name)
+        switch, keyword = ('device_regions', 'regions') if kind == 'regions' else ('device_labelmap', 'labelmap')
+        can_lm = getattr(self, switch, False) and not multilabel and lm_fn is not None \
+            and self._takes(lm_fn, 'out_shapes' if batched else 'out_shape') and window_takes(keyword)
 
-    def _predict_stack_probabilities(self, group, batched: bool):
-        """Stage 2 of :meth:`_run` for stacks that ask for probabilities: per case ``(decided map, probabilities)`` of the predictor's stack
-        probabilities method - the extent before resampling, the extent before cropping and the origin of the three-axis crop box go with each
-        case - or, where it answers None, the logits (:meth:`_predict`): the export then takes the host route."""
-        p = self._predictor
-        name = 'predict_stack_probabilities_from_preprocessed_data'
-        datas = [t[3] for t in group]
-        outs = [tuple(t[4].get('shape_after_cropping_and_before_resampling', np.asarray(t[3]).shape[1:])) for t in group]
-        fulls = [tuple(t[4]['shape_before_cropping']) for t in group]
-        boxes = [tuple(int(b[0]) for b in t[4]['bbox_used_for_cropping']) for t in group]
-        if batched:
-            out = getattr(p, name + '_batch')(datas, out_shapes=outs, full_shapes=fulls, boxes=boxes)
-            out = list(out) if out is not None else [None] * len(group)
-        else:
-            out = [getattr(p, name)(d, out_shape=o, full_shape=f, box=b) for d, o, f, b in zip(datas, outs, fulls, boxes)]
-        rest = [i for i, o in enumerate(out) if o is None]
-        for i, lg in zip(rest, self._predict([datas[i] for i in rest], False, batched) if rest else []):
-            out[i] = lg
-        return out
+        # save_probabilities: the decided maps alone cannot give them.  Either the device does everything in one kernel (resample-back, the
+        # non-linearity, the fill around the crop box, the decision on the logits: kernels_prob.h) and the export receives the decided map
+        # and the float32 planes of the pre-crop extent, or the logits travel and the export's host route computes both.  The guards are
+        # those of can_lm: the predictor has the method and, where it is a double of the engine method, the `probabilities` keyword
+        pr_name = 'predict_probabilities_from_preprocessed_data'
+        pr_fn = method(pr_name)
+        can_prob = save_probabilities and getattr(self, 'device_probabilities', False) and pr_fn is not None \
+            and self._takes(pr_fn, 'full_shapes' if batched else 'full_shape') and window_takes('probabilities')
+        if save_probabilities:
+            can_seg = can_export = can_lm = False
+
+        def target(t):
+            """The extent the device export resamples case `t` to: None = none needed, False = not a case for it (a stack, a 3-D plan,
+            a predictor without the export)."""
+            shape = tuple(np.asarray(t[3]).shape[1:])
+            if not needs_logits(t[4], shape):
+                return None
+            tgt = tuple(t[4]['shape_after_cropping_and_before_resampling'])
+            return tgt if (can_export or can_lm or can_prob) and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] == 1 else False
+        # a stack - a 3-D volume under a 2-D plan, more than one slice left after cropping - gets the decided map of its convention from the
+        # device too, every slice one image of the same entries (the predictor's stack methods); its slice count never changes.  Only a predictor
+        # that has the methods takes this route, and only with the convention's own switch on.  With save_probabilities the stack takes the
+        # predictor's stack probabilities methods instead - the kernel of can_prob per slice, written in place into one [K, Z0, H0, W0] - under a
+        # switch of their own, and only for an untransposed plan (the slice axis must be the volume's first)
+        st_name = 'predict_stack_probabilities_from_preprocessed_data' if save_probabilities else 'predict_stack_from_preprocessed_data'
+        can_stack = getattr(self, 'device_stack', False) and method(st_name) is not None \
+            and len(p.configuration_manager.patch_size) == 2 and bool(self.device_threshold if multilabel else getattr(self, switch, False))
+        if save_probabilities:
+            can_stack = can_stack and getattr(self, 'device_stack_probabilities', False) \
+                and list(getattr(p.plans_manager, 'transpose_forward', [0, 1, 2])) == [0, 1, 2]
+
+        def is_stack(t):
+            shape = tuple(np.asarray(t[3]).shape[1:])
+            tgt = tuple(t[4].get('shape_after_cropping_and_before_resampling', shape))
+            return can_stack and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] > 1
+        stacks = [t for t in todo if is_stack(t)]
+        fast = [t for t in todo if (can_seg or can_lm or can_prob) and not is_stack(t) and target(t) is not False and (not can_prob or np.asarray(t[3]).shape[1] == 1)]
+        rest = [t for t in todo if not any(t is f for f in fast + stacks)]
+        lm = {'fast': lm_name} if can_lm else {}
+        return [(stacks, lambda: self._predict_device(stacks, batched, st_name, placed=save_probabilities)),
+                (fast, (lambda: self._predict_device(fast, batched, pr_name, placed=True)) if can_prob else
+                 (lambda: self._predict([t[3] for t in fast], True, batched, [target(t) for t in fast], **lm))),
+                (rest, lambda: self._predict([t[3] for t in rest], False, batched, None, **lm))]
 
     def _run(self, inputs: dict, result_dir, override, batched: bool, stamps: dict, save_probabilities: bool = False) -> dict:
         """The reference worker's four stages (``prediction_worker.py:177-242``) over ``inputs``: output file, preprocessing of every
-        input, prediction (:meth:`_predict`, per group of inputs that share the fast-path decision: at most two groups), export of each.
+        input, prediction (per group of :meth:`_routes`: the inputs that share the fast-path decision), export of each.
         Each stage fails under its own name - ``"<Stage> failed for <name>: <cause>"`` - so that a HIP error (``ts2d_last_error``)
         tells which stage raised it.  ``stamps[name]`` receives ``start / preprocessed / predicted / exported / done`` per input (the
         inputs of one group share ``predicted``); ``timestamps`` follows the input at work.  ``override=False`` skips existing outputs
@@ -354,79 +390,11 @@ class HIPModel:
             except Exception as ex:
                 raise RuntimeError(f"Preprocessing failed for {name}: {ex}") from ex
             todo.append([name, ofile, ref, data, props, None])
-        # product fast path: a multilabel 2-D case gets its segmentation thresholded on the device (K uint8 planes to the host instead
-        # of K float16 ones; the predicate is the export step's, bit for bit).  A case whose export resamples (its spacing is not the
-        # plan's) joins with the extent it had before resampling: the device resamples the logits back (order 1) in front of the
-        # threshold and the export step receives uint8 planes already in that extent.  The reference's seam
-        # (predict_logits_from_preprocessed_data + export_prediction_from_logits) stays as it is and serves every other case
-        kind = label_convention(p.dataset_json).kind
-        multilabel = kind == 'multilabel'
-        can_seg = self.device_threshold and multilabel and hasattr(p, 'predict_segmentation_from_preprocessed_data' + ('_batch' if batched else ''))
-        # (a foreign predictor, or a double of the engine method, that knows the fast path but not its `out_shape(s)` keyword keeps
-        #  the host route for resampled cases, as before the device export existed)
-        fast_fn = getattr(p, 'predict_segmentation_from_preprocessed_data' + ('_batch' if batched else ''), None)
-        can_export = can_seg and self._takes(fast_fn, 'out_shapes' if batched else 'out_shape') \
-            and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, 'out_shapes'))
-        # a label-map model (the ordinary nnU-Net head): the same two host steps - resample-back, then the argmax over the heads - on the
-        # device, ONE uint8 plane per case to the host; the export step receives it as the decided label map.  Only a predictor that has
-        # the method (and, where it is a double of the engine method, its `labelmap` keyword) takes this route.  A region-based model goes
-        # the same way under its own switch and keyword (`regions`: sigmoid predicate per head, painted in class order, kernels_regions.h)
-        lm_name = 'predict_labelmap_from_preprocessed_data'
-        lm_fn = getattr(p, lm_name + ('_batch' if batched else ''), None)
-        switch, keyword = ('device_regions', 'regions') if kind == 'regions' else ('device_labelmap', 'labelmap')
-        can_lm = getattr(self, switch, False) and not multilabel and lm_fn is not None \
-            and self._takes(lm_fn, 'out_shapes' if batched else 'out_shape') \
-            and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, keyword))
-
-        # save_probabilities: the decided maps alone cannot give them.  Either the device does everything in one kernel (resample-back, the
-        # non-linearity, the fill around the crop box, the decision on the logits: kernels_prob.h) and the export receives the decided map
-        # and the float32 planes of the pre-crop extent, or the logits travel and the export's host route computes both.  The guards are
-        # those of can_lm: the predictor has the method and, where it is a double of the engine method, the `probabilities` keyword
-        pr_fn = getattr(p, 'predict_probabilities_from_preprocessed_data' + ('_batch' if batched else ''), None)
-        can_prob = save_probabilities and getattr(self, 'device_probabilities', False) and pr_fn is not None \
-            and self._takes(pr_fn, 'full_shapes' if batched else 'full_shape') \
-            and (not hasattr(p, '_sliding_window_batch') or self._takes(p._sliding_window_batch, 'probabilities'))
-        if save_probabilities:
-            can_seg = can_export = can_lm = False
-
-        def target(t):
-            """The extent the device export resamples case `t` to: None = none needed, False = not a case for it (a stack, a 3-D plan,
-            a predictor without the export)."""
-            shape = tuple(np.asarray(t[3]).shape[1:])
-            if not needs_logits(t[4], shape):
-                return None
-            tgt = tuple(t[4]['shape_after_cropping_and_before_resampling'])
-            return tgt if (can_export or can_lm or can_prob) and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] == 1 else False
-        # a stack - a 3-D volume under a 2-D plan, more than one slice left after cropping - gets the decided map of its convention from the
-        # device too, every slice one image of the same entries (the predictor's stack methods); its slice count never changes.  Only a predictor
-        # that has the methods takes this route, and only with the convention's own switch on.  With save_probabilities the stack takes the
-        # predictor's stack probabilities methods instead - the kernel of can_prob per slice, written in place into one [K, Z0, H0, W0] - under a
-        # switch of their own, and only for an untransposed plan (the slice axis must be the volume's first)
-        name = 'predict_stack_probabilities_from_preprocessed_data' if save_probabilities else 'predict_stack_from_preprocessed_data'
-        st_fn = getattr(p, name + ('_batch' if batched else ''), None)
-        can_stack = getattr(self, 'device_stack', False) and st_fn is not None \
-            and len(p.configuration_manager.patch_size) == 2 and bool(self.device_threshold if multilabel else getattr(self, switch, False))
-        if save_probabilities:
-            can_stack = can_stack and getattr(self, 'device_stack_probabilities', False) \
-                and list(getattr(p.plans_manager, 'transpose_forward', [0, 1, 2])) == [0, 1, 2]
-
-        def is_stack(t):
-            shape = tuple(np.asarray(t[3]).shape[1:])
-            tgt = tuple(t[4].get('shape_after_cropping_and_before_resampling', shape))
-            return can_stack and len(tgt) == len(shape) == 3 and tgt[0] == shape[0] > 1
-        stacks = [t for t in todo if is_stack(t)]
-        fast = [t for t in todo if (can_seg or can_lm or can_prob) and not is_stack(t) and target(t) is not False and (not can_prob or np.asarray(t[3]).shape[1] == 1)]
-        for group, use_seg in ((stacks, True), (fast, True), ([t for t in todo if not any(t is f for f in fast + stacks)], False)):
+        for group, predict in self._routes(todo, batched, save_probabilities):
             if not group:
                 continue
             try:
-                if group is stacks:
-                    out = (self._predict_stack_probabilities if save_probabilities else self._predict_stacks)(group, batched)
-                elif use_seg and can_prob:
-                    out = self._predict_probabilities(group, batched)
-                else:
-                    out = self._predict([t[3] for t in group], use_seg, batched, [target(t) for t in group] if use_seg else None,
-                                        **({'fast': lm_name} if can_lm else {}))
+                out = predict()
             except Exception as ex:
                 names = ', '.join(t[0] for t in group)
                 m = re.match(r'input (\d+): ', str(ex))          # the predictor names the offending input of the batch by index

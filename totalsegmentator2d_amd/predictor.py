@@ -212,75 +212,86 @@ class HIPnnUNetPredictor:
         ``(uint8 [1,1,full_h,full_w] - multilabel [K,1,full_h,full_w] -, float32 [K,1,full_h,full_w])`` per input.
         (The one method that touches the engine, under the name the test infrastructure overrides: tests/batch_util.py replaces it, and
         tests/host_predictor.py predict_sliding_window_return_logits, with the host restatement.)"""
-        patch = tuple(self.configuration_manager.patch_size)
-        ensemble = fold is None
-        images, tiles, owner, reverts, shapes = self._pad_and_tile(list_of_data, patch, single_slice=ensemble or labelmap or regions is not None or probabilities is not None)
-        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
-            raise AssertionError('mirror_axes does not match the dimension of the input!')
-        g = sw.compute_gaussian(patch) if self.use_gaussian else None
-        axes = self.allowed_mirroring_axes if self.use_mirroring else None
+        ensemble, n = fold is None, len(list_of_data)
+        w = self._window(list_of_data, single_slice=ensemble or labelmap or regions is not None or probabilities is not None)
+        patch, images, tiles, axes, g = w.patch, w.images, w.tiles, w.axes, w.g
         e = None if ensemble else self.engines[fold]
-        if probabilities is not None:
-            from .engine import predict_tiled_probabilities_ensemble
-            if len(probabilities) != len(list_of_data):
+        engines = self.engines if ensemble else [e]
+        per_image = [range(len(images))] if one_call else [[j] for j in range(len(images))]
+        if probabilities is not None or labelmap or regions is not None:
+            if probabilities is not None and len(probabilities) != n:
                 raise AssertionError('probabilities needs one (full extent, box origin) per input')
-            rects = self._export_rects(list_of_data, reverts, shapes, out_shapes if out_shapes is not None else [None] * len(list_of_data), True)
+            rects = self._export_rects(list_of_data, w.reverts, w.shapes, out_shapes if out_shapes is not None else [None] * n, True)
+            decision = {'regions': tuple(regions)} if regions is not None else {'labelmap': True} if labelmap else {}
+            if probabilities is None:
+                entry = self._decided_entry(decision)
+                planes = self._calls(w, per_image, one_call, lambda im, tl, grp: entry(engines, im, patch, tl, [rects[j] for j in grp], axes, g, one_call), engines[0])
+                return [p[None, None] for p in planes]
+            from .engine import predict_tiled_probabilities_ensemble
             rects = [r + tuple(int(v) for v in full) + tuple(int(v) for v in box) for r, (full, box) in zip(rects, probabilities)]
             mode = 'regions' if regions is not None else 'labelmap' if labelmap else 'multilabel'
-            engines = self.engines if ensemble else [e]
-            probs, maps, inf = [], [], []
-            for grp in ([range(len(images))] if one_call else [[j] for j in range(len(images))]):
-                pr, dc, _ = predict_tiled_probabilities_ensemble(engines, [images[j] for j in grp], patch, [tiles[j] for j in grp], [rects[j] for j in grp],
-                                                                 mode, regions, axes, g, full_batch=one_call)
-                probs += pr
-                maps += dc
-                inf += engines[0].last_tiled_inf_per_image
-            self._raise_on_inf(inf, owner, one_call)
-            return [((d[None, None] if d.ndim == 2 else d[:, None]), pr[:, None]) for d, pr in zip(maps, probs)]
-        if labelmap or regions is not None:
-            from .engine import predict_tiled_labelmap_ensemble, predict_tiled_regions_ensemble
-            rects = self._export_rects(list_of_data, reverts, shapes, out_shapes if out_shapes is not None else [None] * len(list_of_data), True)
-            engines = self.engines if ensemble else [e]
-            planes, inf = [], []
-            for grp in ([range(len(images))] if one_call else [[j] for j in range(len(images))]):
-                args = ([images[j] for j in grp], patch, [tiles[j] for j in grp], [rects[j] for j in grp])
-                if regions is not None:
-                    planes += predict_tiled_regions_ensemble(engines, *args, tuple(regions), axes, g, full_batch=one_call)[0]
-                else:
-                    planes += predict_tiled_labelmap_ensemble(engines, *args, axes, g, full_batch=one_call)[0]
-                inf += engines[0].last_tiled_inf_per_image
-            self._raise_on_inf(inf, owner, one_call)
-            return [p[None, None] for p in planes]
+
+            def call(im, tl, grp):
+                pr, dc, _ = predict_tiled_probabilities_ensemble(engines, im, patch, tl, [rects[j] for j in grp], mode, regions, axes, g, full_batch=one_call)
+                return list(zip(dc, pr))
+            return [((d[None, None] if d.ndim == 2 else d[:, None]), pr[:, None]) for d, pr in self._calls(w, per_image, one_call, call, engines[0])]
         if ensemble and want_seg and out_shapes is None:
-            out_shapes = [None] * len(list_of_data)
-        exports = None if out_shapes is None else self._export_rects(list_of_data, reverts, shapes, out_shapes, want_seg)
+            out_shapes = [None] * n
+        exports = None if out_shapes is None else self._export_rects(list_of_data, w.reverts, w.shapes, out_shapes, want_seg)
         want = dict(want_logits=not want_seg, want_seg=want_seg)
         if ensemble:
             from .engine import predict_tiled_export_ensemble
-            planes = predict_tiled_export_ensemble(self.engines, images, patch, tiles, exports, axes, g, **want, full_batch=one_call)[0 if want_seg else 2]
-            inf = self.engines[0].last_tiled_inf_per_image
+            planes = self._calls(w, [range(len(images))], one_call, lambda im, tl, grp: predict_tiled_export_ensemble(
+                self.engines, im, patch, tl, exports, axes, g, **want, full_batch=one_call)[0 if want_seg else 2])
         elif exports is not None:
-            planes, inf = [], []
-            for grp in ([range(len(images))] if one_call else [[j] for j in range(len(images))]):
-                planes += e.predict_tiled_export([images[j] for j in grp], patch, [tiles[j] for j in grp], [exports[j] for j in grp], axes, g,
-                                                 full_batch=one_call)[0]
-                inf += e.last_tiled_inf_per_image
+            planes = self._calls(w, per_image, one_call, lambda im, tl, grp: e.predict_tiled_export(
+                im, patch, tl, [exports[j] for j in grp], axes, g, full_batch=one_call)[0], e)
         elif one_call:
-            planes, inf = e.predict_tiled_batch(images, patch, tiles, axes, g, **want)[want_seg], e.last_tiled_inf_per_image
+            planes = self._calls(w, per_image, one_call, lambda im, tl, grp: e.predict_tiled_batch(im, patch, tl, axes, g, **want)[want_seg], e)
         else:
-            planes, inf = [], []
-            for image, tl in zip(images, tiles):
-                planes.append(e.predict_tiled(image, patch, tl, axes, g, **want)[want_seg])
-                inf.append(e.last_tiled_inf)
-        self._raise_on_inf(inf, owner, one_call)
+            planes = self._calls(w, per_image, one_call, lambda im, tl, grp: [e.predict_tiled(im[0], patch, tl[0], axes, g, **want)[want_seg]], e,
+                                 flags=lambda: [e.last_tiled_inf])
         if exports is not None:              # resampled on the device: already the case's own rectangle, one plane per input
             return [p[:, None] for p in planes]
         results, j = [], 0
-        for (Z, H, W), revert in zip(shapes, reverts):
+        for (Z, H, W), revert in zip(w.shapes, w.reverts):
             full = np.stack(planes[j:j + Z], axis=1) if Z != 1 else planes[j][:, None]
             j += Z
             results.append(full[(slice(None),) + revert[1:]])
         return results
+
+    def _window(self, list_of_data, single_slice: bool):
+        """The set-up every sliding window shares: the padded images with their tiles (:meth:`_pad_and_tile`), the mirror assertion, the gaussian
+        and the mirror axes - as one namespace ``patch, images, tiles, owner, reverts, shapes, g, axes``."""
+        patch = tuple(self.configuration_manager.patch_size)
+        images, tiles, owner, reverts, shapes = self._pad_and_tile(list_of_data, patch, single_slice=single_slice)
+        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
+            raise AssertionError('mirror_axes does not match the dimension of the input!')
+        return SimpleNamespace(patch=patch, images=images, tiles=tiles, owner=owner, reverts=reverts, shapes=shapes,
+                               g=sw.compute_gaussian(patch) if self.use_gaussian else None,
+                               axes=self.allowed_mirroring_axes if self.use_mirroring else None)
+
+    def _calls(self, w, groups, named: bool, call, engine=None, flags=None):
+        """One engine call per group of images of the window ``w``: ``call(images, tiles, group)`` returns one result per image; they are
+        collected in image order with the inf flags each call left (``flags()``; else the per-image flags of ``engine``, else of the first
+        engine), and :meth:`_raise_on_inf` is applied (``named``: the calls carry several inputs)."""
+        engine = self.engines[0] if engine is None else engine
+        out, inf = [], []
+        for grp in groups:
+            out += call([w.images[j] for j in grp], [w.tiles[j] for j in grp], grp)
+            inf += flags() if flags else engine.last_tiled_inf_per_image
+        self._raise_on_inf(inf, w.owner, named)
+        return out
+
+    def _decided_entry(self, decision: dict):
+        """The engine function that decides the maps of a model by its convention (``decision``: :meth:`_decision`, or {} for a multilabel model),
+        as ``(engines, images, patch, tiles, rects, axes, g, full_batch) -> one uint8 array per image``."""
+        from .engine import predict_tiled_export_ensemble, predict_tiled_labelmap_ensemble, predict_tiled_regions_ensemble
+        if 'regions' in decision:
+            return lambda eng, im, patch, tl, rc, axes, g, full: predict_tiled_regions_ensemble(eng, im, patch, tl, rc, decision['regions'], axes, g, full_batch=full)[0]
+        if decision:
+            return lambda eng, im, patch, tl, rc, axes, g, full: predict_tiled_labelmap_ensemble(eng, im, patch, tl, rc, axes, g, full_batch=full)[0]
+        return lambda eng, im, patch, tl, rc, axes, g, full: predict_tiled_export_ensemble(eng, im, patch, tl, rc, axes, g, want_seg=True, full_batch=full)[0]
 
     def _pad_and_tile(self, list_of_data, patch, single_slice: bool):
         """Inputs [C,Z,H,W] -> every z slice of every input, padded up to the patch, as one image with its tile list (upstream order),
@@ -355,15 +366,45 @@ class HIPnnUNetPredictor:
         ``out_shape`` (the case's ``shape_after_cropping_and_before_resampling``, (h, w) or (1, h, w)): the export's order-1
         resample-back runs on the device in front of the threshold (kernels_resample.h; bit for bit the host route's
         ``resample_data_to_shape(order=1)`` + threshold) and the result is uint8 [K, 1, h, w] in THAT extent."""
-        data = _to_numpy(data)
-        ensemble = self._device_ensemble()
-        if not (ensemble or len(self.list_of_parameters) == len(self.engines) == 1) or data.ndim != 4 or data.shape[1] != 1:
+        out = self._segmentation([data], None if out_shape is None else [out_shape], one_call=False, compare_engines=True)
+        return None if out is None else out[0]
+
+    def _fast_inputs(self, list_of_data, per_input, stack: bool = False, probe=None, compare_engines: bool = True, convert_first: bool = False):
+        """THE guard of the fast-path methods: the inputs as float32 arrays and the in-plane extent each is resampled to (None: its own),
+        ``(datas, hws)`` - or ``[]`` for no inputs, or None where the predictor keeps the logits route.  ``per_input``: the per-input
+        lists of the method, ``out_shapes`` first, each None or of one entry per input.  ``stack``: the stack methods (:meth:`_serves_stacks`,
+        any Z, ``out_shapes`` of ``(Z, h, w)``, and a list of the wrong length is refused before an empty call is answered); else the
+        single-slice methods: a device ensemble, or one fold on - ``compare_engines`` - one engine.  ``probe``: the ``engine.has_*`` of an
+        optional entry.  ``convert_first`` (the segmentation methods): the entries of ``out_shapes`` are converted, as far as the inputs go,
+        before the length of the list is looked at - a malformed entry raises even in a list of the wrong length."""
+        datas = [_to_numpy(d) for d in list_of_data]
+        n = len(datas)
+        lengths = all(v is None or len(v) == n for v in per_input)
+        if stack:
+            if not self._serves_stacks() or any(d.ndim != 4 for d in datas) or not lengths:
+                return None
+        elif not (self._device_ensemble() or (len(self.list_of_parameters) == 1 and (len(self.engines) == 1 or not compare_engines))) \
+                or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
             return None
-        hw = self._in_plane(out_shape, data)
-        if hw is False:
+        if probe is not None and not probe():
             return None
-        kw = {} if hw is None else {'out_shapes': [hw]}
-        return self._sliding_window_batch([data], None if ensemble else 0, want_seg=True, one_call=False, **kw)[0]
+        if not datas:
+            return []
+        if not lengths and not convert_first:
+            return None
+        extent = self._stack_extent if stack else self._in_plane
+        hws = [extent(s, d) for s, d in zip(per_input[0] if per_input[0] is not None else [None] * n, datas)]
+        return None if not lengths or any(hw is False for hw in hws) else (datas, hws)
+
+    @staticmethod
+    def _per_image(one_call: bool) -> dict:
+        """``one_call`` as a keyword of :meth:`_sliding_window_batch` only where it is not the default: the doubles of the tests that override
+        the method for the batch route need not know it."""
+        return {} if one_call else {'one_call': False}
+
+    def _fold(self):
+        """The ``fold`` of :meth:`_sliding_window_batch` for the fast paths: every fold of a device ensemble, else the one there is."""
+        return None if self._device_ensemble() else 0
 
     def _decision(self) -> dict:
         """The keyword of :meth:`_sliding_window_batch` that decides the map of this model: ``labelmap`` (argmax over the heads) or, for a
@@ -382,31 +423,18 @@ class HIPnnUNetPredictor:
         A REGION-BASED model (``regions_class_order`` is set) takes the same route with its own decision: the sigmoid's predicate per
         head and the painting in class order (kernels_regions.h) in the place of the argmax - the decided map of whatever non-multilabel
         convention the model has."""
-        data = _to_numpy(data)
-        ensemble = self._device_ensemble()
-        if not (ensemble or len(self.list_of_parameters) == len(self.engines) == 1) or data.ndim != 4 or data.shape[1] != 1:
-            return None
-        hw = self._in_plane(out_shape, data)
-        if hw is False:
-            return None
-        return self._sliding_window_batch([data], None if ensemble else 0, one_call=False, out_shapes=[hw], **self._decision())[0]
+        out = self._labelmaps([data], None if out_shape is None else [out_shape], one_call=False)
+        return None if out is None else out[0]
 
     def predict_labelmap_from_preprocessed_data_batch(self, list_of_data, out_shapes=None):
         """:meth:`predict_labelmap_from_preprocessed_data` for a list of inputs: uint8 [1,1,h,w] per input from ONE engine call (every
         fold of an ensemble in it), or None when the predictor keeps the logits route (a fold ensemble without engines), an input is no
         single z slice or an ``out_shapes`` entry is bad.  ``out_shapes``: one ``out_shape`` (or None) per input."""
-        datas = [_to_numpy(d) for d in list_of_data]
-        ensemble = self._device_ensemble()
-        if not (ensemble or len(self.list_of_parameters) == len(self.engines) == 1) or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
-            return None
-        if not datas:
-            return []
-        if out_shapes is not None and len(out_shapes) != len(datas):
-            return None
-        hws = [self._in_plane(s, d) for s, d in zip(out_shapes, datas)] if out_shapes is not None else [None] * len(datas)
-        if any(hw is False for hw in hws):
-            return None
-        return self._sliding_window_batch(datas, None if ensemble else 0, out_shapes=hws, **self._decision())
+        return self._labelmaps(list_of_data, out_shapes, one_call=True)
+
+    def _labelmaps(self, list_of_data, out_shapes, one_call: bool):
+        ok = self._fast_inputs(list_of_data, (out_shapes,))
+        return ok if not ok else self._sliding_window_batch(ok[0], self._fold(), out_shapes=ok[1], **self._per_image(one_call), **self._decision())
 
     def _probability_mode(self) -> dict:
         """The keyword of :meth:`_sliding_window_batch` for this model's convention, as :meth:`_decision` - nothing for a multilabel model."""
@@ -445,24 +473,14 @@ class HIPnnUNetPredictor:
         """:meth:`predict_probabilities_from_preprocessed_data` for a list of inputs: ``(decided, probabilities)`` per input from ONE
         engine call (every fold of an ensemble in it), or None.  ``out_shapes`` / ``full_shapes`` / ``boxes``: one entry (or None) per input."""
         from .engine import has_probabilities
-        datas = [_to_numpy(d) for d in list_of_data]
-        ensemble = self._device_ensemble()
-        if not (ensemble or len(self.list_of_parameters) == len(self.engines) == 1) or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
-            return None
-        if not has_probabilities():
-            return None
-        if not datas:
-            return []
-        n = len(datas)
-        if any(v is not None and len(v) != n for v in (out_shapes, full_shapes, boxes)):
-            return None
-        hws = [self._in_plane(s, d) for s, d in zip(out_shapes, datas)] if out_shapes is not None else [None] * n
-        if any(hw is False for hw in hws):
-            return None
+        ok = self._fast_inputs(list_of_data, (out_shapes, full_shapes, boxes), probe=has_probabilities)
+        if not ok:
+            return ok
+        (datas, hws), n = ok, len(ok[0])
         place = [self._full_and_box(hw, d, f, b) for hw, d, f, b in zip(hws, datas, full_shapes or [None] * n, boxes or [None] * n)]
         if any(pl is None for pl in place):
             return None
-        return self._sliding_window_batch(datas, None if ensemble else 0, one_call=one_call, out_shapes=hws, probabilities=place, **self._probability_mode())
+        return self._sliding_window_batch(datas, self._fold(), one_call=one_call, out_shapes=hws, probabilities=place, **self._probability_mode())
 
     # ------------------------------------------------------------------ stacks: a 3-D volume through a 2-D model, slice by slice
     stack_call_bytes = 1 << 30       # device bytes of inputs and outputs one engine call of the stack batch method may hold (see _stack_calls)
@@ -514,28 +532,13 @@ class HIPnnUNetPredictor:
         _export: one engine is the single-model case), with its input's tile list, rectangle and out extent.  ``full_batch`` False: one call per
         slice with the size-dependent dispatch - the bytes of :meth:`predict_logits_from_preprocessed_data` + the host export; True: calls of
         :meth:`_stack_calls` with the full-batch dispatch - the bytes of :meth:`predict_logits_from_preprocessed_data_batch` + the host export."""
-        from .engine import predict_tiled_export_ensemble, predict_tiled_labelmap_ensemble, predict_tiled_regions_ensemble
         from .labels import label_convention
-        patch = tuple(self.configuration_manager.patch_size)
-        images, tiles, owner, reverts, _ = self._pad_and_tile(datas, patch, single_slice=False)
-        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
-            raise AssertionError('mirror_axes does not match the dimension of the input!')
-        g = sw.compute_gaussian(patch) if self.use_gaussian else None
-        axes = self.allowed_mirroring_axes if self.use_mirroring else None
-        rects = self._stack_rects(datas, reverts, hws)
+        w = self._window(datas, single_slice=False)
+        rects = self._stack_rects(datas, w.reverts, hws)
         multilabel = label_convention(self.dataset_json).kind == 'multilabel'
-        decision = {} if multilabel else self._decision()
-        planes, inf = [], []
-        for grp in (self._stack_calls(images, rects, multilabel) if full_batch else [[j] for j in range(len(images))]):
-            args = (self.engines, [images[j] for j in grp], patch, [tiles[j] for j in grp], [rects[j] for j in grp])
-            if multilabel:
-                planes += predict_tiled_export_ensemble(*args, axes, g, want_seg=True, full_batch=full_batch)[0]
-            elif 'regions' in decision:
-                planes += predict_tiled_regions_ensemble(*args, decision['regions'], axes, g, full_batch=full_batch)[0]
-            else:
-                planes += predict_tiled_labelmap_ensemble(*args, axes, g, full_batch=full_batch)[0]
-            inf += self.engines[0].last_tiled_inf_per_image
-        self._raise_on_inf(inf, owner, full_batch)
+        entry = self._decided_entry({} if multilabel else self._decision())
+        groups = self._stack_calls(w.images, rects, multilabel) if full_batch else [[j] for j in range(len(w.images))]
+        planes = self._calls(w, groups, full_batch, lambda im, tl, grp: entry(self.engines, im, w.patch, tl, [rects[j] for j in grp], w.axes, w.g, full_batch))
         out, j = [], 0
         for data in datas:
             Z = data.shape[1]
@@ -556,24 +559,19 @@ class HIPnnUNetPredictor:
         extent every slice is resampled back to (order 1) in front of the decision; None: the preprocessed geometry.  One engine call per slice with
         the size-dependent dispatch, every fold of an ensemble in it: the bytes are those of :meth:`predict_logits_from_preprocessed_data` + the host
         export.  None where the device cannot serve (a predictor without engines, a 3-D plan, a bad ``out_shape``): the caller keeps the logits."""
-        data = _to_numpy(data)
-        if not self._serves_stacks() or data.ndim != 4:
-            return None
-        hw = self._stack_extent(out_shape, data)
-        return None if hw is False else self._stack_window([data], [hw], full_batch=False)[0]
+        out = self._stacks([data], None if out_shape is None else [out_shape], full_batch=False)
+        return None if out is None else out[0]
 
     def predict_stack_from_preprocessed_data_batch(self, list_of_data, out_shapes=None):
         """:meth:`predict_stack_from_preprocessed_data` for a list of inputs - stacks and single-slice cases may be mixed: the slices of all inputs packed
         into engine calls with the full-batch dispatch, as many per call as ``stack_call_bytes`` allows, so that a stack's bytes depend neither on that
         budget nor on its batch-mates; they are those of :meth:`predict_logits_from_preprocessed_data_batch` + the host export.  ``out_shapes``: one
         ``out_shape`` (or None) per input.  None where the single-case method returns None for some input."""
-        datas = [_to_numpy(d) for d in list_of_data]
-        if not self._serves_stacks() or any(d.ndim != 4 for d in datas) or (out_shapes is not None and len(out_shapes) != len(datas)):
-            return None
-        if not datas:
-            return []
-        hws = [self._stack_extent(s, d) for s, d in zip(out_shapes if out_shapes is not None else [None] * len(datas), datas)]
-        return None if any(hw is False for hw in hws) else self._stack_window(datas, hws, full_batch=True)
+        return self._stacks(list_of_data, out_shapes, full_batch=True)
+
+    def _stacks(self, list_of_data, out_shapes, full_batch: bool):
+        ok = self._fast_inputs(list_of_data, (out_shapes,), stack=True)
+        return ok if not ok else self._stack_window(*ok, full_batch=full_batch)
 
     # ------------------------------------------------------------------ ... and their probabilities: one strided volume per stack
     @staticmethod
@@ -615,13 +613,9 @@ class HIPnnUNetPredictor:
         (C-ABI ts2d_ensemble_predict_tiled_probabilities_stack).  ``full_batch`` as in :meth:`_stack_window`."""
         from .engine import predict_tiled_probabilities_stack_ensemble
         from .labels import label_convention
-        patch = tuple(self.configuration_manager.patch_size)
-        images, tiles, owner, reverts, _ = self._pad_and_tile(datas, patch, single_slice=False)
-        if self.use_mirroring and self.allowed_mirroring_axes and max(self.allowed_mirroring_axes) > 1:
-            raise AssertionError('mirror_axes does not match the dimension of the input!')
-        g = sw.compute_gaussian(patch) if self.use_gaussian else None
-        axes = self.allowed_mirroring_axes if self.use_mirroring else None
-        rects = self._stack_rects(datas, reverts, hws)
+        w = self._window(datas, single_slice=False)
+        images, owner = w.images, w.owner
+        rects = self._stack_rects(datas, w.reverts, hws)
         kind = label_convention(self.dataset_json).kind
         multilabel = kind == 'multilabel'
         mode = 'multilabel' if multilabel else 'regions' if 'regions' in self._decision() else 'labelmap'
@@ -638,13 +632,13 @@ class HIPnnUNetPredictor:
             probs.append(prob)
             decs.append(dec)
         fulls = [places[i][0][1:] for i in owner]
-        inf = []
-        for grp in (self._stack_calls(images, rects, multilabel, fulls) if full_batch else [[j] for j in range(len(images))]):
+
+        def call(im, tl, grp):
             runs = self._stack_runs(grp, owner, first_image, rects, places, probs, decs, multilabel)
-            predict_tiled_probabilities_stack_ensemble(self.engines, [images[j] for j in grp], patch, [tiles[j] for j in grp], runs, mode,
-                                                       self._decision().get('regions'), axes, g, full_batch=full_batch)
-            inf += self.engines[0].last_tiled_inf_per_image
-        self._raise_on_inf(inf, owner, full_batch)
+            predict_tiled_probabilities_stack_ensemble(self.engines, im, w.patch, tl, runs, mode, self._decision().get('regions'), w.axes, w.g,
+                                                       full_batch=full_batch)
+            return []
+        self._calls(w, self._stack_calls(images, rects, multilabel, fulls) if full_batch else [[j] for j in range(len(images))], full_batch, call)
         return list(zip(decs, probs))
 
     def predict_stack_probabilities_from_preprocessed_data(self, data, out_shape=None, full_shape=None, box=None):
@@ -669,17 +663,10 @@ class HIPnnUNetPredictor:
 
     def _stack_probabilities(self, list_of_data, out_shapes, full_shapes, boxes, full_batch: bool):
         from .engine import has_stack_probabilities
-        datas = [_to_numpy(d) for d in list_of_data]
-        n = len(datas)
-        if not self._serves_stacks() or any(d.ndim != 4 for d in datas) or any(v is not None and len(v) != n for v in (out_shapes, full_shapes, boxes)):
-            return None
-        if not has_stack_probabilities():
-            return None
-        if not datas:
-            return []
-        hws = [self._stack_extent(s, d) for s, d in zip(out_shapes if out_shapes is not None else [None] * n, datas)]
-        if any(hw is False for hw in hws):
-            return None
+        ok = self._fast_inputs(list_of_data, (out_shapes, full_shapes, boxes), stack=True, probe=has_stack_probabilities)
+        if not ok:
+            return ok
+        (datas, hws), n = ok, len(ok[0])
         places = [self._stack_place(hw, d, f, b) for hw, d, f, b in zip(hws, datas, full_shapes or [None] * n, boxes or [None] * n)]
         if any(pl is None for pl in places):
             return None
@@ -708,14 +695,13 @@ class HIPnnUNetPredictor:
         or None when the predictor needs the logits (a fold ensemble without engines) or an input is no single z slice.  ``out_shapes``:
         one ``out_shape`` (or None) per input; inputs that resample and inputs that do not travel in the same call.  A fold ensemble:
         every fold and every input in ONE engine call, the mean of the folds on the device (:meth:`_sliding_window_batch` with ``fold=None``)."""
-        datas = [_to_numpy(d) for d in list_of_data]
-        ensemble = self._device_ensemble()
-        if not (ensemble or len(self.list_of_parameters) == 1) or any(d.ndim != 4 or d.shape[1] != 1 for d in datas):
-            return None
-        if not datas:
-            return []
-        hws = [self._in_plane(s, d) for s, d in zip(out_shapes, datas)] if out_shapes is not None else [None] * len(datas)
-        if (out_shapes is not None and len(out_shapes) != len(datas)) or any(hw is False for hw in hws):
-            return None
-        kw = {} if all(hw is None for hw in hws) else {'out_shapes': hws}
-        return self._sliding_window_batch(datas, None if ensemble else 0, want_seg=True, **kw)
+        return self._segmentation(list_of_data, out_shapes, one_call=True, compare_engines=False)
+
+    def _segmentation(self, list_of_data, out_shapes, one_call: bool, compare_engines: bool):
+        """The two segmentation methods.  ``compare_engines``: the single-case method wants its one fold on ONE engine; the batch method
+        does not look (and goes through the export entry only where some input resamples)."""
+        ok = self._fast_inputs(list_of_data, (out_shapes,), compare_engines=compare_engines, convert_first=True)
+        if not ok:
+            return ok
+        kw = {} if all(hw is None for hw in ok[1]) else {'out_shapes': ok[1]}
+        return self._sliding_window_batch(ok[0], self._fold(), want_seg=True, **self._per_image(one_call), **kw)
