@@ -41,13 +41,15 @@ TileGeom tile_geom_pow2(int B, int Ht, int Wt, int sy, int sx, int taps) {
 // shape depends on (Ht, Wt, stride) only - never on B or on the mode, so the statistics partials are laid out the same everywhere).
 TileGeom tile_geom(int B, int Ht, int Wt, int sy, int sx, int taps) {
     TileGeom g = tile_geom_pow2(B, Ht, Wt, sy, sx, taps);
-    if (g.NIMG == 1 ? (Ht % g.TH == 0 && Wt % g.TW == 0) : (g.TH == Ht && g.TW == Wt)) return g;
     const int halo = (taps == 9) ? 3 : 1;
     auto patch = [&](int th, int tw) { return ((th - 1) * sy + halo) * ((tw - 1) * sx + halo); };
     const bool s1 = sy == 1 && sx == 1;
     // staging budgets (patch pixels): conv_mfma_f32 576 / 1296 (ConvCfg::MAXP), conv3x3_f16x3 640, conv3x3s2_f16x3 1536; preferred (one-image
     // kernels): conv3x3_f16x3_one / conv3x3_h32 384, conv3x3s2_f16x3_one 1280
     const int hard = taps == 1 ? (1 << 30) : (s1 ? 576 : 1296), soft = taps == 1 ? (1 << 30) : (s1 ? 384 : 1280);
+    // (the power-of-two tile too must fit the budget: 16 images of 2 x 8 are 640 patch pixels, 8 of 1 x 32 are 816 - the kernels stage no more than
+    //  their budget and the last images of such a tile read LDS nobody wrote.  tests/test_workspace_plan_cpu.py, W4, found it and holds every tile to it)
+    if ((g.NIMG == 1 ? (Ht % g.TH == 0 && Wt % g.TW == 0) : (g.TH == Ht && g.TW == Wt)) && g.NIMG * patch(g.TH, g.TW) <= hard) return g;
     if (Ht * Wt * 2 <= kBM) {
         int n = std::min(16, kBM / (Ht * Wt));
         while (n > 1 && n * patch(Ht, Wt) > hard) --n;
@@ -126,7 +128,8 @@ TileGeom tile_fixed(int B, int Ht, int Wt, int th, int tw, int sy, int sx) {
 // Split-K factor for a split-fp16 conv whose grid would leave most CUs idle (8x8 / 4x4 bottleneck levels).
 int choose_ksplit(const Op& op, const TileGeom& g) {
     if (op.type != OP_CONV || !op.split_ok || op.first_direct) return 1;
-    // The factor depends on the layer geometry only (never on B), so a slice computes bit-identically alone or in a batch:
+    // The factor depends on the layer geometry only (never on B), so a slice computes bit-identically alone or in a batch
+    // (the whole Choice of the full dispatch, as a property over batches: tests/test_workspace_plan_cpu.py, W5):
     // tiles that hold >= 4 whole images (<= 8x8 pixels per image) leave most CUs idle -> split K as far as 4 chunks/slice.
     if (g.NIMG < 4) return 1;
     const int nchunks = (op.cin + op.cin_skip) / (op.stride == 1 ? 16 : 8);
@@ -454,6 +457,7 @@ size_t partial_floats_needed(const ts2d_engine* e, const std::vector<Choice>& pl
         if (plan[i].ksplit > 1) mx = std::max(mx, (size_t)plan[i].ksplit * B * (H >> op.ly) * (W >> op.lx) * op.cout);
     }
     // a workspace sized for B also serves every smaller batch, whose ops may split K further (fill_ksplit): the bound of that rule
+    // (asserted, not only argued: tests/test_workspace_plan_cpu.py, W3, takes every admitted (layout, run) pair of its sweep)
     if (e->use_sbk) mx = std::max(mx, kSbkElems);
     return mx;
 }
@@ -475,6 +479,7 @@ size_t part_floats_needed(const ts2d_engine* e, const std::vector<Choice>& plan,
 // simulating the program.  Canonical net: 340 -> ~110 MB per slice.  A composed decoder entry (kernels_upc.h) reads the COARSE tensor
 // and never materialises `decN.up`, so the plan depends on the precision mode - it is remade when that changes.
 // keep_activations: no reuse (every tensor keeps its own buffer for ts2d_engine_debug_tensor / the non-finite diagnosis).
+// That no run admitted into a layout writes over a tensor it still reads is tests/test_workspace_plan_cpu.py, W2.
 ActPlan plan_activations(const ts2d_engine* e, const std::vector<Choice>& plan, int B, int H, int W, bool keep) {
     const size_t nt = e->tensors.size(), no = e->ops.size();
     ActPlan p; p.off.assign(nt, 0); p.size.assign(nt, 0); p.used.assign(nt, 0); p.reused.assign(nt, 0);
@@ -570,6 +575,7 @@ WsLayout workspace_layout(const ts2d_engine* e, int B, int H, int W, bool full) 
     L.o_part = off; off = align_up(off + part_floats_needed(e, plan, B) * sizeof(float) + 256, 256);
     L.o_pk = off; off = align_up(off + partial_floats_needed(e, plan, B, H, W) * sizeof(float) + 256, 256);   // split-K partials
     // one upsampled tensor of a small batch's two-kernel decoder entry (composed_kernel): the plan above is the reserved batch's, where that entry is composed
+    // (one tenant at a time, read by the next op only, never above the region: tests/test_workspace_plan_cpu.py, W1 and W2)
     L.has_up = e->use_sbk;
     L.o_up = off; if (L.has_up) off = align_up(off + kSbkElems / 2 * sizeof(float) + 256, 256);
     L.bytes = off;

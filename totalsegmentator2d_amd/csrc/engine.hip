@@ -61,6 +61,9 @@ int upload_weights(ts2d_engine* e, const float* blob, size_t n_floats) {
 // memory when it fits (checked below, never assumed).  The reverse holds: a full-dispatch layout serves every "sbk" run of the same or a
 // smaller batch (the upsampled tensor of its two-kernel entries goes to the d_up scratch, as for any batch below the reserved one), so
 // the layout stays and a following predict_tiled / forward finds it unchanged.
+// What this reuse rests on - a buffer for every output, no live tensor overwritten, side regions that hold what their kernels touch - is
+// checked for every admitted (layout, run) pair of a sweep on the CPU (tests/test_workspace_plan_cpu.py, W1-W3) and run at a few pairs on
+// the card (tests/test_gpu_workspace_reuse.py).
 int ensure_workspace(ts2d_engine* e, int B, int H, int W, bool full) {
     const bool keep = e->keep_activations;
     if (e->d_ws && e->wsB >= B && e->wsH == H && e->wsW == W && e->ws_precision == e->precision && e->ws_keep == keep && (e->ws_full || !full)) return TS2D_OK;

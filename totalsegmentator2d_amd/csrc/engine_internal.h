@@ -230,7 +230,8 @@ void pack_weights(const ts2d_engine* e, const float* blob, float* out);
 float f16_to_f32(uint16_t hb);
 
 // ---- dispatch.cpp: which kernel serves an op, and the workspace that follows from it
-// Small-batch split-K (fill_ksplit): S x B x HW x Cout of any op the rule splits (n_wgs S < 2 x 256 CUs, <= 256 pixels x 64 columns each)
+// Small-batch split-K (fill_ksplit): S x B x HW x Cout of any op the rule splits (n_wgs S < 2 x 256 CUs, <= 256 pixels x 64 columns each).
+// The bound is asserted against every split op of a sweep of nets, extents and batches: tests/test_workspace_plan_cpu.py, W3.
 constexpr size_t kSbkElems = (size_t)2 * 256 * 256 * 64;
 // `full`: the run asks for the full-batch dispatch whatever its size (ts2d_engine_predict_tiled_batch: a row's bits must not depend on its batch).
 // No default anywhere: every caller names the dispatch it means.

@@ -1,6 +1,7 @@
 // The device-free front of the sliding window (tiled.hip: predict_tiled_impl): argument checks, the rows (tile x mirror variant) of the
 // images packed into chunks of at most kSwChunkRows, the export's segments and taps, the table blob and the scratch layout.  Plain C++:
-// the taps must match numpy bit for bit, so this arithmetic is not compiled as HIP code.
+// the taps must match numpy bit for bit, so this arithmetic is not compiled as HIP code.  (Every plan of a scenario table, its rows, regions,
+// lane addresses and taps: tests/test_tiled_plan_cpu.py.)
 #include "engine_internal.h"
 
 #include <algorithm>
