@@ -878,6 +878,29 @@ int ts2d_surface_distance_profile(int device, const uint8_t* a, int kind_a, cons
                                   int want_sum, size_t max_scratch_bytes, int64_t* out_i64, double* out_f64, double* out_sum_f64,
                                   double* out_rank_f64, double* out_weight_f64);
 
+/* ts2d_volume_surface_distances: the boundary distances of VOLUMES [Z][H][W] and, on request, their profile - ts2d_surface_distance_profile
+ * with one more axis.  The statements are evaluate.volume_surface_statement and evaluate.volume_distance_profile_statement; the entry reproduces
+ * them bit for bit.  a, kind_a, b, kind_b, values, K as in ts2d_label_overlap; each extent 1 ... TS2D_EVAL_MAX_EXTENT and Z * H * W at most
+ * 2^31 - 1.  A border voxel of a mask is a foreground voxel with at least one of its SIX face neighbours background, outside the volume being
+ * background (so with Z = 1 every foreground voxel is one: that is not the 2-D border of ts2d_surface_distances).  For a border voxel p of one
+ * side, d2(p) = min over the border voxels q of the other side of ((f(|pz - qz|, spacing_z) + f(|py - qy|, spacing_h)) + f(|px - qx|, spacing_w))
+ * with f(n, s) = (n * s) * (n * s), in float64, that association, every operation rounded on its own, +inf where the other side has no border -
+ * computed by the exact three-pass decomposition of csrc/surface_dist.h inside each label's joint bounding box (csrc/kernels_evaluate_volume.h).
+ * P = 0 and want_sum = 0 is the plain form: out_sum_f64, out_rank_f64 and out_weight_f64 may then be NULL.  tol_sq, T, percentiles, P, want_sum
+ * and the five outputs mean what they mean in ts2d_surface_distance_profile, with the same layouts; the sum meets in the tree of
+ * csrc/stats_tree.h over (Z * H, W).
+ *   max_scratch_bytes  bound of the scratch that labels working at once take together; 0: 4 GiB.  Per label and voxel OF ITS BOX (the inclusive
+ *              box of the label over both sides) 22 bytes - 2 of border, 4 of line distances, 16 of the float64 second pass -, with percentiles 16
+ *              more, and with the sum 16 per box row (z, y); a label that is empty on both sides takes none.  The labels are packed into chunks
+ *              that stay below the bound, in their order.  The result does not depend on the chunking.
+ * TS2D_ERR_INVALID, by name: what ts2d_surface_distance_profile refuses (before any device work) and, once the boxes are known, scratch of ONE
+ * label above max_scratch_bytes.  On any error the outputs are untouched.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+int ts2d_volume_surface_distances(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int Z,
+                                  int H, int W, double spacing_z, double spacing_h, double spacing_w, const double* tol_sq, int T,
+                                  const double* percentiles, int P, int want_sum, size_t max_scratch_bytes, int64_t* out_i64, double* out_f64,
+                                  double* out_sum_f64, double* out_rank_f64, double* out_weight_f64);
+
 /* Synthetic slice stream on the device (BASELINE config 4: "synthetic 10k-slice stream", generated per rank from (seed, slice
  * index) so that no host transfer skews the timing).  Writes n_elements fp32 values, approximately N(0,1), to device memory:
  * element i of the call = element (first_element + i) of the stream identified by `key`; a value depends on (key, element index)

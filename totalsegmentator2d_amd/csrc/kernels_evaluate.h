@@ -30,6 +30,7 @@
 //                          are halved (st_wave_halve, kernels_stats.h) and lane 0 stores the row's partial.  Compile-time, not a null check
 //                          at run time: the plain form then carries no broadcast, no per-lane key and no sum, and keeps its 35 registers
 //                          (the profile form needs 46) without anyone having to measure that a branch on null costs nothing.
+//                          The body is sd_row_walk, which the rows of a volume's boxes share (sdv_rows, kernels_evaluate_volume.h).
 // Integer atomics only (sums and a maximum of non-negative keys: the result does not depend on their order), no flags, nothing waits for another
 // wave (a workgroup of sd_columns and sd_rows is ONE wave); contraction off; every loop bound is a kernel argument, the grid's extent, 64 or a
 // constant.  Indices into a plane are int32 or long long as the entry's limits need.
@@ -177,34 +178,40 @@ __global__ __launch_bounds__(64) void sd_columns(const uint8_t* __restrict__ a, 
 
 struct SdTolerances { double sq[kSdMaxTolerances]; };
 
-// grid = (H, 2, L), block = 64.  Direction 0: the border pixels of A against g of B; direction 1: the other way.  counts: [K][2][1 + T] (border
-// pixels, then those within each tolerance), keys: [K][2] (the largest d2 as sd_key), both zero before the first launch.  PROFILE: also key_buf
-// uint64 [L][2][H * W] (null: no keys are kept) and row_sum float64 [L][2][H] (null: no sum); the plain form reads neither argument.
-template <bool PROFILE>
-__global__ __launch_bounds__(64) void sd_rows(const uint8_t* __restrict__ border, const uint16_t* __restrict__ g, int k0, int H, int W, double sy,
-                                              double sx, SdTolerances tol, int T, unsigned long long* __restrict__ counts,
-                                              unsigned long long* __restrict__ keys, uint64_t* __restrict__ key_buf, double* __restrict__ row_sum) {
+// The ONE walk over the border pixels of a row, behind sd_rows (2-D planes) and sdv_rows (volumes: kernels_evaluate_volume.h), in compile-time
+// forms: PROFILE as above; VOLUME chooses the candidate of column x' - sd_candidate(go[x'], dx) from the row distances of the other side, or
+// sd_candidate_h(ho[x'], dx) from pass 2 of a volume - and where the row starts: a volume's row is a row of the label's BOX, whose column 0 is
+// column x_first of the full extent, and the sum's lane of a term is its FULL-extent x % 64 (stats_tree.h over (Z * H, W)), so the chunks of 64
+// start at `first` = -(x_first % 64) and lane l walks the box columns first + l, first + l + 64, ...: the terms of full-extent lane
+// (x_first + x) % 64 = l in increasing x.  The columns a row skips that way, and those outside the box, have the term +0.0, which leaves the
+// bits of a non-negative sum as they are.  The ballot, the broadcast, the key store, the per-lane root sums and the counters exist once.
+// bo: the border bytes of the row (W of them); go / ho: g or h of the other side's row; counts: the (label, direction)'s [1 + T]; key_top: its
+// largest key; key_row: the row's W keys (null: none kept); row_slot: the row's partial (null: no sum).
+template <bool PROFILE, bool VOLUME>
+__device__ __forceinline__ void sd_row_walk(const uint8_t* __restrict__ bo, const uint16_t* __restrict__ go, const double* __restrict__ ho, int first,
+                                            int W, double sy, double sx, const SdTolerances& tol, int T, unsigned long long* __restrict__ counts,
+                                            unsigned long long* __restrict__ key_top, uint64_t* __restrict__ key_row, double* __restrict__ row_slot,
+                                            int lane) {
 #pragma clang fp contract(off)
-    const int y = (int)blockIdx.x, dir = (int)blockIdx.y, l = (int)blockIdx.z, k = k0 + l, lane = (int)threadIdx.x;
-    const long long HW = (long long)H * W;
-    const uint8_t* bo = border + ((long long)l * 2 + dir) * HW + (long long)y * W;
-    const uint16_t* go = g + ((long long)l * 2 + (1 - dir)) * HW + (long long)y * W;
     int cnt = 0;
     int within[kSdMaxTolerances];
 #pragma unroll
     for (int t = 0; t < kSdMaxTolerances; ++t) within[t] = 0;
     uint64_t key_max = 0;
     double acc = 0.0;                                              // (PROFILE)
-    for (int x0 = 0; x0 < W; x0 += 64) {
+    for (int x0 = VOLUME ? first : 0; x0 < W; x0 += 64) {
         const int x = x0 + lane;
-        unsigned long long todo = __ballot(x < W && bo[x] != 0);
+        const bool in = VOLUME ? (x >= 0 && x < W) : x < W;
+        unsigned long long todo = __ballot(in && bo[x] != 0);
         uint64_t mine = kSdNoKey;                                  // (PROFILE)
         while (todo) {                                             // at most 64 rounds; the mask is the same in every lane
             const int src = __ffsll((long long)todo) - 1, px = x0 + src;
             todo &= todo - 1;
             double best = sd_inf();
             for (int xo = lane; xo < W; xo += 64) {
-                const double c = sd_candidate(go[xo], xo > px ? xo - px : px - xo, sy, sx);
+                double c;
+                if constexpr (VOLUME) c = sd_candidate_h(ho[xo], xo > px ? xo - px : px - xo, sx);
+                else c = sd_candidate(go[xo], xo > px ? xo - px : px - xo, sy, sx);
                 best = c < best ? c : best;
             }
             for (int off = 32; off >= 1; off >>= 1) { const double o = __shfl_down(best, off, 64); best = o < best ? o : best; }
@@ -217,24 +224,39 @@ __global__ __launch_bounds__(64) void sd_rows(const uint8_t* __restrict__ border
             if constexpr (PROFILE) mine = lane == src ? key : mine;
         }
         if constexpr (PROFILE) {
-            if (key_buf && x < W) key_buf[((long long)l * 2 + dir) * HW + (long long)y * W + x] = mine;
-            if (row_sum) acc = acc + (mine != kSdNoKey ? sd_sqrt(sd_unkey(mine)) : 0.0);      // (+0.0 for no border pixel: the sum stays as it is)
+            if (key_row && in) key_row[x] = mine;
+            if (row_slot) acc = acc + (mine != kSdNoKey ? sd_sqrt(sd_unkey(mine)) : 0.0);      // (+0.0 for no border pixel: the sum stays as it is)
         }
     }
     if constexpr (PROFILE) {
-        if (row_sum) {
+        if (row_slot) {
             acc = st_wave_halve(acc);
-            if (lane == 0) row_sum[((long long)l * 2 + dir) * H + y] = acc;
+            if (lane == 0) *row_slot = acc;
         }
     }
     if (lane == 0 && cnt) {
-        unsigned long long* c = counts + ((long long)k * 2 + dir) * (1 + T);
-        atomicAdd(c, (unsigned long long)cnt);
+        atomicAdd(counts, (unsigned long long)cnt);
 #pragma unroll
         for (int t = 0; t < kSdMaxTolerances; ++t)
-            if (t < T && within[t]) atomicAdd(c + 1 + t, (unsigned long long)within[t]);
-        atomicMax(keys + (long long)k * 2 + dir, (unsigned long long)key_max);
+            if (t < T && within[t]) atomicAdd(counts + 1 + t, (unsigned long long)within[t]);
+        atomicMax(key_top, (unsigned long long)key_max);
     }
+}
+
+// grid = (H, 2, L), block = 64.  Direction 0: the border pixels of A against g of B; direction 1: the other way.  counts: [K][2][1 + T] (border
+// pixels, then those within each tolerance), keys: [K][2] (the largest d2 as sd_key), both zero before the first launch.  PROFILE: also key_buf
+// uint64 [L][2][H * W] (null: no keys are kept) and row_sum float64 [L][2][H] (null: no sum); the plain form reads neither argument.
+template <bool PROFILE>
+__global__ __launch_bounds__(64) void sd_rows(const uint8_t* __restrict__ border, const uint16_t* __restrict__ g, int k0, int H, int W, double sy,
+                                              double sx, SdTolerances tol, int T, unsigned long long* __restrict__ counts,
+                                              unsigned long long* __restrict__ keys, uint64_t* __restrict__ key_buf, double* __restrict__ row_sum) {
+    const int y = (int)blockIdx.x, dir = (int)blockIdx.y, l = (int)blockIdx.z, k = k0 + l, lane = (int)threadIdx.x;
+    const long long HW = (long long)H * W;
+    const long long own = ((long long)l * 2 + dir) * HW + (long long)y * W;
+    sd_row_walk<PROFILE, false>(border + own, g + ((long long)l * 2 + (1 - dir)) * HW + (long long)y * W, nullptr, 0, W, sy, sx, tol, T,
+                                counts + ((long long)k * 2 + dir) * (1 + T), keys + (long long)k * 2 + dir,
+                                PROFILE && key_buf ? key_buf + own : nullptr, PROFILE && row_sum ? row_sum + ((long long)l * 2 + dir) * H + y : nullptr,
+                                lane);
 }
 
 }  // namespace ts2d

@@ -32,6 +32,24 @@
 //   the prefix on those digits -; the digit is the first whose running count passes r, and the count below it is taken off r.  Integers only.
 //   Ranks.  For percentile q among n >= 1 sorted values: h = (n - 1) * (q / 100), i = min(floor(h), n - 1), j = min(i + 1, n - 1), t = h - i, each
 //   operation an IEEE float64 one (sd_percentile_ranks); the caller interpolates between the roots of the two selected d2.
+//
+// VOLUMES (ts2d_volume_surface_distances, kernels_evaluate_volume.h; the statements: evaluate.volume_surface_statement and
+// evaluate.volume_distance_profile_statement; the host walk: sd_volume_label_profile, held against them by tests/test_evaluate_volume_cpu.py).
+// Border (sd_border3).  A border voxel of a mask [Z][H][W] is a foreground voxel with at least one of its SIX face neighbours background; outside
+// the volume is background.  (With Z = 1 every foreground voxel is one: that is this definition, not the 2-D border.)
+// Distance.  For a border voxel p of A,
+//     d2(p) = min over border voxels q of B of ((f(|pz - qz|, sz) + f(|py - qy|, sy)) + f(|px - qx|, sx))
+// in float64, that association, every operation rounded on its own, +inf where B has no border.
+// The three passes and why they are exact.  f(n, s) is monotone in n and u -> fl(u + v) is monotone in u (above).
+//   pass 1, per line (y', x') along z    the integer g(z, y', x') = min |z - z'| over the border voxels of the line (two scans), or kSdNone
+//   pass 2, per (z, y, x')               h(z, y, x') = min over y' of (f(g(z, y', x'), sz) + f(|y - y'|, sy)), +inf without a candidate
+//   pass 3, per border voxel p of A      d2(p) = min over x' of (h(pz, py, x') + f(|px - x'|, sx))      (sd_candidate_h)
+// Fix a line (y', x') of B.  Its candidates for p differ in the z term alone, f(|pz - z'|, sz), and (u + f(dy)) + f(dx) is monotone in u by two
+// applications of the second fact: the line's NEAREST voxel gives its smallest candidate.  Fix x'.  The candidates of its lines are
+// u(y') + f(|px - x'|, sx) with u(y') = f(g, sz) + f(|py - y'|, sy), monotone in u: the smallest u - that is h - gives the smallest candidate,
+// so the minimum over y' commutes with adding the x term.  The three passes therefore take the same set minimum over fewer candidates: equal
+// to the brute force over all border pairs bit for bit, whatever the order in which lines and columns are met.
+// The sum of a volume's profile meets in the tree of stats_tree.h over (Z * H, W): row z * H + y, lane x % 64.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -65,6 +83,19 @@ TS2D_SD_HD bool sd_border(const uint8_t* m, int kind, uint8_t value, int H, int 
     return !(up && down && left && right);
 }
 
+// is (z, y, x) a border voxel of the label's mask m [Z][H][W]?  (six face neighbours)
+TS2D_SD_HD bool sd_border3(const uint8_t* m, int kind, uint8_t value, int Z, int H, int W, int z, int y, int x) {
+    const long long HW = (long long)H * W, i = (long long)z * HW + (long long)y * W + x;
+    if (!st_masked(m[i], kind, value)) return false;
+    const bool before = z > 0 && st_masked(m[i - HW], kind, value);
+    const bool after = z + 1 < Z && st_masked(m[i + HW], kind, value);
+    const bool up = y > 0 && st_masked(m[i - W], kind, value);
+    const bool down = y + 1 < H && st_masked(m[i + W], kind, value);
+    const bool left = x > 0 && st_masked(m[i - 1], kind, value);
+    const bool right = x + 1 < W && st_masked(m[i + 1], kind, value);
+    return !(before && after && up && down && left && right);
+}
+
 TS2D_SD_HD double sd_inf() {
     const uint64_t u = 0x7FF0000000000000ull;
     double d;
@@ -81,6 +112,29 @@ TS2D_SD_HD double sd_candidate(uint16_t g, int dx, double sy, double sx) {
     const double rx = (double)dx * sx;
     const double rx2 = rx * rx;
     return ry2 + rx2;
+}
+
+// f(n, s) = (n * s) * (n * s), its two roundings
+TS2D_SD_HD double sd_f(int n, double s) {
+#pragma clang fp contract(off)
+    const double r = (double)n * s;
+    return r * r;
+}
+
+// volumes, pass 2: the candidate of line (y', x') for the voxels of row y at its z - line distance g (kSdNone: no border on the line)
+TS2D_SD_HD double sd_candidate_line(uint16_t g, int dy, double sz, double sy) {
+#pragma clang fp contract(off)
+    if (g == kSdNone) return sd_inf();
+    const double a = sd_f((int)g, sz);
+    const double b = sd_f(dy, sy);
+    return a + b;
+}
+
+// volumes, pass 3: the candidate of column x' for a border voxel - h of the column at the voxel's (z, y) (+inf: no candidate), column distance dx
+TS2D_SD_HD double sd_candidate_h(double h, int dx, double sx) {
+#pragma clang fp contract(off)
+    const double c = sd_f(dx, sx);
+    return h + c;
 }
 
 // d2 >= +0.0 or +inf: the bit pattern of such a float64, read as an unsigned integer, orders as the values do
@@ -225,6 +279,91 @@ inline long long sd_label(const uint8_t* own, int kind_own, const uint8_t* other
                           const double* tol_sq, int T, uint8_t* border_own, uint8_t* border_other, uint16_t* g, uint64_t* key_max, long long* within) {
     return sd_label_profile(own, kind_own, other, kind_other, value, H, W, sy, sx, tol_sq, T, nullptr, 0, border_own, border_other, g, nullptr, nullptr,
                             key_max, within, nullptr, nullptr, nullptr);
+}
+// Pass 1 of one line (y, x) along z on the host: g[z * H * W + i] for z = 0 ... Z - 1 from the border bytes of the line (i = y * W + x).
+inline void sd_line(const uint8_t* border, int Z, size_t HW, size_t i, uint16_t* g) {
+    int last = -1;
+    for (int z = 0; z < Z; ++z) {
+        if (border[(size_t)z * HW + i]) last = z;
+        g[(size_t)z * HW + i] = last < 0 ? kSdNone : (uint16_t)(z - last);
+    }
+    last = -1;
+    for (int z = Z - 1; z >= 0; --z) {
+        if (border[(size_t)z * HW + i]) last = z;
+        if (last >= 0 && (uint16_t)(last - z) < g[(size_t)z * HW + i]) g[(size_t)z * HW + i] = (uint16_t)(last - z);
+    }
+}
+
+// One label and one direction of a VOLUME on the host, what sdv_lines, sdv_planes, sdv_rows, sdv_profile_combine and the selection kernels
+// compute together (they inside the label's box, this over the whole extent: outside the box everything is background).  The results and the
+// optional parts as sd_label_profile has them; the tree of the sum is over (Z * H, W).  border_own, border_other: Z * H * W bytes of scratch
+// each; g: Z * H * W; h: Z * H * W; keys: Z * H * W or null; partial: Z * H or null.
+inline long long sd_volume_label_profile(const uint8_t* own, int kind_own, const uint8_t* other, int kind_other, uint8_t value, int Z, int H, int W,
+                                         double sz, double sy, double sx, const double* tol_sq, int T, const double* q, int P, uint8_t* border_own,
+                                         uint8_t* border_other, uint16_t* g, double* h, uint64_t* keys, double* partial, uint64_t* key_max,
+                                         long long* within, double* dist_sum, uint64_t* rank_keys, double* weights) {
+#pragma clang fp contract(off)
+    const size_t HW = (size_t)H * W, n_all = (size_t)Z * HW;
+    for (int z = 0; z < Z; ++z)
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x) {
+                const size_t i = (size_t)z * HW + (size_t)y * W + x;
+                border_own[i] = sd_border3(own, kind_own, value, Z, H, W, z, y, x) ? 1 : 0;
+                border_other[i] = sd_border3(other, kind_other, value, Z, H, W, z, y, x) ? 1 : 0;
+            }
+    for (size_t i = 0; i < HW; ++i) sd_line(border_other, Z, HW, i, g);
+    for (int z = 0; z < Z; ++z)
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x) {
+                double best = sd_inf();
+                for (int yo = 0; yo < H; ++yo) {
+                    const double c = sd_candidate_line(g[(size_t)z * HW + (size_t)yo * W + x], yo > y ? yo - y : y - yo, sz, sy);
+                    best = c < best ? c : best;
+                }
+                h[(size_t)z * HW + (size_t)y * W + x] = best;
+            }
+    long long n = 0;
+    *key_max = 0;
+    for (int t = 0; t < T; ++t) within[t] = 0;
+    double v[kStLanes];
+    for (size_t r = 0; r < (size_t)Z * H; ++r) {                    // row r = z * H + y
+        for (int l = 0; l < kStLanes; ++l) v[l] = 0.0;
+        for (int x = 0; x < W; ++x) {
+            if (keys) keys[r * W + x] = kSdNoKey;
+            if (!border_own[r * W + x]) continue;
+            double d2 = sd_inf();
+            for (int xo = 0; xo < W; ++xo) {
+                const double c = sd_candidate_h(h[r * W + xo], xo > x ? xo - x : x - xo, sx);
+                d2 = c < d2 ? c : d2;
+            }
+            ++n;
+            const uint64_t key = sd_key(d2);
+            if (keys) keys[r * W + x] = key;
+            *key_max = key > *key_max ? key : *key_max;
+            for (int t = 0; t < T; ++t) within[t] += d2 <= tol_sq[t] ? 1 : 0;
+            if (partial) v[x % kStLanes] = v[x % kStLanes] + sd_sqrt(d2);
+        }
+        if (partial) partial[r] = st_halve(v);
+    }
+    if (partial) {
+        for (int l = 0; l < kStLanes; ++l) v[l] = st_lane_rows(partial, Z * H, l);
+        *dist_sum = st_halve(v);
+    }
+    for (int p = 0; p < P && n > 0; ++p) {
+        long long i, j;
+        sd_percentile_ranks(n, q[p], &i, &j, weights + p);
+        rank_keys[2 * p] = sd_select_rank(keys, n_all, i);
+        rank_keys[2 * p + 1] = sd_select_rank(keys, n_all, j);
+    }
+    return n;
+}
+
+// ... without the profile: the plain form of ts2d_volume_surface_distances
+inline long long sd_volume_label(const uint8_t* own, int kind_own, const uint8_t* other, int kind_other, uint8_t value, int Z, int H, int W, double sz,
+                                 double sy, double sx, const double* tol_sq, int T, uint8_t* border_own, uint8_t* border_other, uint16_t* g, double* h,
+                                 uint64_t* key_max, long long* within) {
+    return sd_volume_label_profile(own, kind_own, other, kind_other, value, Z, H, W, sz, sy, sx, tol_sq, T, nullptr, 0, border_own, border_other, g, h,
+                                   nullptr, nullptr, key_max, within, nullptr, nullptr, nullptr);
 }
 #endif
 

@@ -862,6 +862,38 @@ def surface_distance_profile(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: 
     return out_i, out_f, out_sum, out_rank, out_weight
 
 
+def volume_scratch_per_label(box_zhw, n_percentiles: int, want_sum: bool) -> int:
+    """The scratch bytes ts2d_volume_surface_distances needs for a label whose joint box has the extents ``box_zhw`` (include/ts2d_engine.h):
+    what ``max_scratch_bytes`` bounds per chunk of labels."""
+    z, h, w = (int(v) for v in box_zhw)
+    return z * h * w * (22 + (16 if n_percentiles else 0)) + (16 * z * h if want_sum else 0)
+
+
+def volume_surface_distances(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, shape_zhw, spacing_zhw, tol_sq, percentiles=(),
+                             want_sum: bool = False, max_scratch_bytes: int = 0, device: int = 0):
+    """The boundary distances of volumes on the device, with their profile on request (C-ABI ts2d_volume_surface_distances).  ``a``, ``b`` as in
+    :func:`label_overlap`; ``tol_sq``: the squared tolerances, float64 [T]; ``percentiles``: float64 [P] in 0 ... 100 (none, and no
+    ``want_sum``: the plain form).  Returns ``(int64 [K, 2, 1 + T], float64 [K, 2], sums float64 [K, 2] or None, ranks float64 [K, 2, P, 2],
+    weights float64 [K, 2, P])`` in the layout of include/ts2d_engine.h."""
+    fn = _entry('ts2d_volume_surface_distances')
+    z, h, w = (int(v) for v in shape_zhw)
+    k, vals = _evaluate_sides('volume_surface_distances', a, kind_a, b, kind_b, values, z * h * w)
+    tol = np.ascontiguousarray(tol_sq, dtype=np.float64)
+    pct = np.ascontiguousarray(percentiles, dtype=np.float64)
+    t, p = int(tol.size), int(pct.size)
+    out_i = np.zeros((k, 2, 1 + t), np.int64)
+    out_f = np.zeros((k, 2), np.float64)
+    out_sum = np.zeros((k, 2), np.float64) if want_sum else None
+    out_rank = np.zeros((k, 2, p, 2), np.float64)
+    out_weight = np.zeros((k, 2, p), np.float64)
+    _lib.check(fn(int(device), a.ctypes.data, int(kind_a), b.ctypes.data, int(kind_b), vals.ctypes.data if vals is not None else None, k, z, h, w,
+                  float(spacing_zhw[0]), float(spacing_zhw[1]), float(spacing_zhw[2]), tol.ctypes.data if t else None, t,
+                  pct.ctypes.data if p else None, p, 1 if want_sum else 0, int(max_scratch_bytes), out_i.ctypes.data, out_f.ctypes.data,
+                  out_sum.ctypes.data if want_sum else None, out_rank.ctypes.data if p else None, out_weight.ctypes.data if p else None),
+               'ts2d_volume_surface_distances')
+    return out_i, out_f, out_sum, out_rank, out_weight
+
+
 def _read_tiled_inf(engines, desc, n_images, engine_flags: bool):
     """The inf flags a tiled call left behind (upstream's inf check, done on the device).  With descriptors, ``last_tiled_inf_per_image``
     of the first engine is their per-image flags; ``last_tiled_inf`` of every engine is its own flag in the library (the flat entry and

@@ -24,6 +24,23 @@ not depend on order, so the bits are a function of the input alone.  The stateme
 (``csrc/surface_dist.h`` has the argument): per column the integer row distance ``g`` to the nearest border pixel of B, then per border pixel the
 minimum over the columns ``x'`` of the formula with ``|py - qy| = g(py, x')``.  tests/test_evaluate_cpu.py holds it against the brute force over
 all border pairs, bit for bit.
+
+BORDER AND DISTANCE (3-D; on request: ``evaluate(..., volume_distances=True)``, :func:`volume_surface_statement`,
+:func:`volume_distance_profile_statement`; device route C-ABI ``ts2d_volume_surface_distances``, ``csrc/kernels_evaluate_volume.h``).  A border
+voxel of a mask ``[Z, H, W]`` is a foreground voxel with at least one of its SIX face neighbours background, outside the volume being background
+(``mask & ~scipy.ndimage.binary_erosion(mask)`` with the default 3-D cross; :func:`border_of_volume`).  With ``Z == 1`` every foreground voxel is
+therefore a border voxel: that is what the definition says, it is not the 2-D border, and :func:`evaluate` never sends a unit-axis image there.
+With ``f(n, s) = (n * s) * (n * s)`` (two roundings), for a border voxel ``p`` of A
+
+    d2(p) = min over border voxels q of B of ((f(|pz - qz|, sz) + f(|py - qy|, sy)) + f(|px - qx|, sx))
+
+in float64, that association, every operation rounded on its own, ``+inf`` where B has no border.  Three exact passes (``csrc/surface_dist.h``
+has the argument: ``f`` is monotone in ``n`` and ``u -> fl(u + v)`` is monotone in ``u``, so a line's nearest voxel gives the line's smallest
+candidate and the minimum over ``y'`` commutes with adding the x term): per line ``(y', x')`` along z the integer ``g(z, y', x')`` to the
+nearest border voxel of B on the line (:func:`line_distance`); per ``(z, y, x')`` the float64
+``h = min over y' of (f(g(z, y', x'), sz) + f(|y - y'|, sy))`` (:func:`plane_distance`); per border voxel of A
+``d2 = min over x' of (h(pz, py, x') + f(|px - x'|, sx))`` (:func:`d2_from_planes`).  tests/test_evaluate_volume_cpu.py holds them against the
+brute force over all border pairs, bit for bit.  The sum of a volume's profile is ``statistics.tree_sum`` over the terms as ``[Z * H, W]``.
 """
 from __future__ import annotations
 
@@ -189,6 +206,53 @@ def d2_from_rows(border_a: np.ndarray, g_b: np.ndarray, spacing_hw) -> np.ndarra
     return out
 
 
+def border_of_volume(mask: np.ndarray) -> np.ndarray:
+    """The border voxels of a 3-D mask: foreground with at least one of the six face neighbours background, outside the volume being background."""
+    m = np.asarray(mask, bool)
+    if m.ndim != 3:
+        raise ValueError(f"border_of_volume: a mask [Z, H, W], found the extent {m.shape}")
+    p = np.pad(m, 1)
+    return m & ~(p[:-2, 1:-1, 1:-1] & p[2:, 1:-1, 1:-1] & p[1:-1, :-2, 1:-1] & p[1:-1, 2:, 1:-1] & p[1:-1, 1:-1, :-2] & p[1:-1, 1:-1, 2:])
+
+
+def line_distance(border: np.ndarray) -> np.ndarray:
+    """Pass 1 of a volume: int64 [Z, H, W], per voxel ``|z - z'|`` to the nearest border voxel of its LINE along z (:func:`row_distance` with the
+    lines as its columns); -1 where the line has none."""
+    Z, H, W = border.shape
+    return row_distance(border.reshape(Z, H * W)).reshape(Z, H, W)
+
+
+def plane_distance(g: np.ndarray, sz, sy, chunk_bytes: int = 1 << 25) -> np.ndarray:
+    """Pass 2 of a volume: float64 [Z, H, W], ``h(z, y, x') = min over y' of (f(g(z, y', x'), sz) + f(|y - y'|, sy))``, ``+inf`` without a
+    candidate.  Chunked over z, so no ``[Z, H, H, W]`` is allocated at once."""
+    sz, sy = np.float64(sz), np.float64(sy)
+    Z, H, W = g.shape
+    with np.errstate(invalid='ignore'):
+        rz = np.where(g < 0, np.inf, g.astype(np.float64)) * sz
+        fz = rz * rz                                                                     # [Z, H(y'), W]
+    ry = np.abs(np.arange(H, dtype=np.int64)[:, None] - np.arange(H, dtype=np.int64)[None, :]).astype(np.float64) * sy
+    fy = ry * ry                                                                         # [H(y), H(y')]
+    h = np.empty((Z, H, W), np.float64)
+    step = max(1, chunk_bytes // max(8 * H * H * W, 1))
+    for z in range(0, Z, step):
+        h[z:z + step] = (fz[z:z + step, None, :, :] + fy[None, :, :, None]).min(axis=2)
+    return h
+
+
+def d2_from_planes(border_a: np.ndarray, h_b: np.ndarray, sx) -> np.ndarray:
+    """Pass 3 of a volume: float64 d2 of every border voxel of A (in ``np.nonzero`` order) from pass 2 of B's border."""
+    sx = np.float64(sx)
+    W = border_a.shape[2]
+    zs, ys, xs = np.nonzero(border_a)
+    rx = np.abs(np.arange(W, dtype=np.int64)[:, None] - np.arange(W, dtype=np.int64)[None, :]).astype(np.float64) * sx
+    dx2 = rx * rx
+    out = np.empty(len(zs), np.float64)
+    step = max(1, (1 << 22) // max(W, 1))
+    for i in range(0, len(zs), step):
+        out[i:i + step] = (h_b[zs[i:i + step], ys[i:i + step]] + dx2[xs[i:i + step]]).min(axis=1)
+    return out
+
+
 def _percentiles(percentiles, who: str) -> list:
     qs = [float(q) for q in percentiles]
     if len(qs) > MAX_PERCENTILES or any(not (math.isfinite(q) and 0.0 <= q <= 100.0) for q in qs):
@@ -217,16 +281,32 @@ def percentile_of_ranks(d2_i, d2_j, t) -> np.float64:
     return hi - (hi - lo) * (np.float64(1) - t)
 
 
-def _distance_walk(who: str, a, kind_a: int, b, kind_b: int, values, spacing_hw, tolerances: Sequence[float], qs: Optional[list]) -> dict:
+def _distance_walk(who: str, a, kind_a: int, b, kind_b: int, values, spacing, tolerances: Sequence[float], qs: Optional[list],
+                   volume: bool = False) -> dict:
     """The ONE walk over the labels and the two directions behind :func:`surface_statement` (``qs`` None: border, d2_max, within, and neither a
-    root nor a sort is taken) and :func:`distance_profile_statement` (``qs`` the checked percentiles: also dist_sum, d2_rank, rank_weight)."""
+    root nor a sort is taken) and :func:`distance_profile_statement` (``qs`` the checked percentiles: also dist_sum, d2_rank, rank_weight), and
+    with ``volume`` behind :func:`volume_surface_statement` and :func:`volume_distance_profile_statement`: the dimension chooses the border, the
+    passes of ``d2`` and the rows of the sum's tree, and nothing else."""
     a, b, spatial, K = _sides(a, kind_a, b, kind_b, values)
-    if len(spatial) == 3 and spatial[0] == 1:
-        spatial = spatial[1:]
-        a = a.reshape((K,) + spatial if kind_a == PLANES else spatial)
-        b = b.reshape((K,) + spatial if kind_b == PLANES else spatial)
-    if len(spatial) != 2:
-        raise ValueError(f"{who}: boundary distances are defined for 2-D planes, found the extent {tuple(spatial)}")
+    if volume:
+        if len(spatial) != 3 or min(spatial) < 1:
+            raise ValueError(f"{who}: boundary distances of volumes are defined for [Z, H, W], found the extent {tuple(spatial)}")
+        sz, sy, sx = spacing
+        border, rows = border_of_volume, (spatial[0] * spatial[1], spatial[2])
+
+        def d2_of(own, other):
+            return d2_from_planes(own, plane_distance(line_distance(other), sz, sy), sx)
+    else:
+        if len(spatial) == 3 and spatial[0] == 1:
+            spatial = spatial[1:]
+            a = a.reshape((K,) + spatial if kind_a == PLANES else spatial)
+            b = b.reshape((K,) + spatial if kind_b == PLANES else spatial)
+        if len(spatial) != 2:
+            raise ValueError(f"{who}: boundary distances are defined for 2-D planes, found the extent {tuple(spatial)}")
+        border, rows = border_of, spatial
+
+        def d2_of(own, other):
+            return d2_from_rows(own, row_distance(other), spacing)
     tol = np.asarray(list(tolerances), np.float64)
     tol_sq = tol * tol
     T = len(tol)
@@ -237,13 +317,13 @@ def _distance_walk(who: str, a, kind_a: int, b, kind_b: int, values, spacing_hw,
         out.update(dist_sum=np.zeros((K, 2), np.float64), d2_rank=np.full((K, 2, P, 2), -np.inf, np.float64),
                    rank_weight=np.zeros((K, 2, P), np.float64))
     for k in range(K):
-        ba, bb = border_of(_mask(a, kind_a, values, k)), border_of(_mask(b, kind_b, values, k))
+        ba, bb = border(_mask(a, kind_a, values, k)), border(_mask(b, kind_b, values, k))
         for d, (own, other) in enumerate(((ba, bb), (bb, ba))):
             n = int(np.count_nonzero(own))
             out['border'][k, d] = n
             if n == 0:
                 continue
-            d2 = d2_from_rows(own, row_distance(other), spacing_hw)
+            d2 = d2_of(own, other)
             out['d2_max'][k, d] = d2.max()
             for t in range(T):
                 out['within'][k, d, t] = np.count_nonzero(d2 <= tol_sq[t])
@@ -251,7 +331,7 @@ def _distance_walk(who: str, a, kind_a: int, b, kind_b: int, values, spacing_hw,
                 continue
             terms = np.zeros(spatial, np.float64)
             terms[own] = np.sqrt(d2)                                                     # (np.nonzero order on both sides)
-            out['dist_sum'][k, d] = tree_sum(terms)
+            out['dist_sum'][k, d] = tree_sum(terms.reshape(rows))
             ordered = np.sort(d2)
             for p, q in enumerate(qs):
                 i, j, t = percentile_ranks(n, q)
@@ -284,6 +364,21 @@ def distance_profile_statement(a, kind_a: int, b, kind_b: int, values, spacing_h
     percentile of the two."""
     return _distance_walk('distance_profile_statement', a, kind_a, b, kind_b, values, spacing_hw, tolerances,
                           _percentiles(percentiles, 'distance_profile_statement'))
+
+
+def volume_surface_statement(a, kind_a: int, b, kind_b: int, values, spacing_zhw, tolerances: Sequence[float]) -> dict:
+    """THE DEFINITION of the boundary distances of volumes (module docstring): :func:`surface_statement` with one more axis.  ``a``, ``b``: planes
+    ``[K, Z, H, W]`` or label maps ``[Z, H, W]``, and nothing else (``ValueError``); ``Z == 1`` is a volume of one slice, whose every foreground
+    voxel is a border voxel.  ``spacing_zhw``: mm per array axis.  The same kinds, refusals and result keys: ``border``, ``d2_max``, ``within``."""
+    return _distance_walk('volume_surface_statement', a, kind_a, b, kind_b, values, spacing_zhw, tolerances, None, volume=True)
+
+
+def volume_distance_profile_statement(a, kind_a: int, b, kind_b: int, values, spacing_zhw, tolerances: Sequence[float],
+                                      percentiles: Sequence[float]) -> dict:
+    """THE DEFINITION of the distance profile of volumes: :func:`volume_surface_statement` (the same bits) and ``dist_sum``, ``d2_rank``,
+    ``rank_weight`` as :func:`distance_profile_statement` has them, the terms of the sum meeting in ``statistics.tree_sum`` as ``[Z * H, W]``."""
+    return _distance_walk('volume_distance_profile_statement', a, kind_a, b, kind_b, values, spacing_zhw, tolerances,
+                          _percentiles(percentiles, 'volume_distance_profile_statement'), volume=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the device route
@@ -340,6 +435,38 @@ def _device_profile(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, pe
     return _device_distances(a, kind_a, b, kind_b, values, hw, spacing_hw, tolerances, list(percentiles), want_sum, device, max_scratch_bytes)
 
 
+VOLUME_SCRATCH_BYTES = 4 << 30       # the default bound of ts2d_volume_surface_distances: what ONE label's box may take at the most
+# No size gate for the volume route either: 18 labels at 16 x 128 x 128 take 0.98 ms (plain) and 2.3 ms (95th percentile and sum) against 35 ... 40 ms
+# for scipy's EDT inside the joint boxes and 1.7 ... 2.2 s for the statements; at 64 x 512 x 512, 7.8 and 12.4 ms against 2.27 s
+# (scripts/gpu_evaluate_volume_case.py, profiles/r34_volume_distances_case.txt).
+
+
+def device_serves_volume(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, spatial, K: int) -> bool:
+    """Does ``ts2d_volume_surface_distances`` serve the case?  What :func:`device_serves` asks, three extents of at most
+    ``_lib.EVAL_MAX_EXTENT`` each, a label filling the whole volume within the default scratch bound, and a library that has the symbol."""
+    from . import _lib, engine
+    if len(spatial) != 3 or max(spatial) > _lib.EVAL_MAX_EXTENT or not device_serves(a, kind_a, b, kind_b, values, spatial, K):
+        return False
+    if engine.volume_scratch_per_label(spatial, 1, True) > VOLUME_SCRATCH_BYTES:
+        return False
+    return engine.has_entry('ts2d_volume_surface_distances')
+
+
+def _device_volume_distances(a, kind_a, b, kind_b, values, zhw, spacing_zhw, tolerances, percentiles, want_sum: bool, device: int,
+                             max_scratch_bytes: int = 0) -> dict:
+    """The volume statements on the device by ``ts2d_volume_surface_distances``: ``percentiles`` None - :func:`volume_surface_statement` (the
+    plain form of the entry); a list - :func:`volume_distance_profile_statement`, ``dist_sum`` only with ``want_sum``."""
+    from . import engine
+    tol = np.asarray(list(tolerances), np.float64)
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    plain = percentiles is None
+    oi, of, osum, orank, oweight = engine.volume_surface_distances(a, kind_a, b, kind_b, values, zhw, spacing_zhw, tol * tol,
+                                                                   [] if plain else list(percentiles), bool(want_sum) and not plain,
+                                                                   max_scratch_bytes, device)
+    extras = {} if plain else dict({'d2_rank': orank, 'rank_weight': oweight}, **({'dist_sum': osum} if want_sum else {}))
+    return dict({'border': oi[:, :, 0].copy(), 'd2_max': of, 'within': oi[:, :, 1:].copy()}, **extras)
+
+
 # ------------------------------------------------------------------------------------------------------------------ evaluate
 def _plane_axes(img: Image):
     """The (array axes, (spacing_h, spacing_w)) of a 2-D input: a 2-D image as it is, a 3-D image with an axis of size 1 without that axis (the
@@ -384,7 +511,7 @@ def percentile_key(q) -> str:
 
 
 def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: Sequence[float] = (2.0,), percentiles: Sequence[float] = (),
-             average_distance: bool = False) -> Dict[str, dict]:
+             average_distance: bool = False, volume_distances: bool = False) -> Dict[str, dict]:
     """name -> scores of ``pred`` against ``ref`` for every named label of ``pred`` (``image.get_annotation_labels(pred)``).
 
     ``pred``, ``ref``: each a multi-component segmentation (label ``v`` is component ``v - 1`` > 0) or a label map (label ``v`` is ``seg == v``),
@@ -394,7 +521,11 @@ def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: 
     ``precision = both / pred``, ``recall = both / ref`` (float64 quotients of integers), ``mm_pred`` / ``mm_ref`` = count * prod(spacing), and
     for 2-D inputs (:func:`_plane_axes`) ``surface_dice[tolerance_key(t)] = (within_ab + within_ba) / (border_a + border_b)`` and
     ``hausdorff = sqrt(max(d2_max_ab, d2_max_ba))`` in mm.  A ratio with a zero denominator is None; a mask that is empty on one side only gives
-    ``hausdorff = inf``; empty on both, None.  For a volume ``surface_dice`` and ``hausdorff`` are absent.
+    ``hausdorff = inf``; empty on both, None.  For a volume ``surface_dice`` and ``hausdorff`` are absent - unless ``volume_distances=True``
+    asks for them: a volume (three spatial axes, all above 1) then gains exactly the keys of the 2-D case, those on request included, with the
+    same formulas and the same None / ``inf`` rules, from the 3-D border and distance of the module docstring
+    (:func:`volume_surface_statement`, :func:`volume_distance_profile_statement`; the spacing of array axis ``k`` is ``spacing[2 - k]``).  On a
+    2-D input the flag changes nothing.
 
     On request, for 2-D inputs too (absent for a volume, and absent without the request: the default call returns what it always did):
     ``percentiles`` (at most ``MAX_PERCENTILES``, each finite and in 0 ... 100, else ``ValueError``) adds
@@ -408,7 +539,8 @@ def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: 
     Route: ``ts2d_label_overlap`` and ``ts2d_surface_distances`` where ``device`` is given, the library has the symbols and the case is served
     (:func:`device_serves`), else the statements; with ``percentiles`` or ``average_distance`` the ONE call ``ts2d_surface_distance_profile``
     (:func:`device_profiles`) in the place of ``ts2d_surface_distances``, else :func:`distance_profile_statement`.  The numbers are the same bit
-    for bit either way."""
+    for bit either way.  A volume's distances: ``ts2d_volume_surface_distances`` where ``device`` is given and :func:`device_serves_volume`
+    holds, else the statements."""
     from .image import get_annotation_labels
     names = get_annotation_labels(pred)
     sp_pred, sp_ref = tuple(pred.array.shape[:pred.dimension]), tuple(ref.array.shape[:ref.dimension])
@@ -442,6 +574,15 @@ def evaluate(pred: Image, ref: Image, device: Optional[int] = None, tolerances: 
             sf = _device_distances(a2, kind_a, b2, kind_b, vals, hw, flat[1], tolerances, qs, bool(average_distance), int(device))
         else:
             sf = _distance_walk('evaluate', a2, kind_a, b2, kind_b, vals, flat[1], tolerances, qs)
+    elif volume_distances and pred.dimension == 3 and min(sp_pred) > 1:
+        a3 = a.reshape(((K,) if kind_a == PLANES else ()) + sp_pred)
+        b3 = b.reshape(((K,) if kind_b == PLANES else ()) + sp_pred)
+        spacing_zhw = tuple(float(pred.spacing[2 - k]) for k in range(3))
+        qs = percentiles if profile else None
+        if device is not None and device_serves_volume(a, kind_a, b, kind_b, vals, sp_pred, K):
+            sf = _device_volume_distances(a3, kind_a, b3, kind_b, vals, sp_pred, spacing_zhw, tolerances, qs, bool(average_distance), int(device))
+        else:
+            sf = _distance_walk('evaluate', a3, kind_a, b3, kind_b, vals, spacing_zhw, tolerances, qs, volume=True)
     mm = np.float64(np.prod(np.asarray(pred.spacing, dtype=np.float64)))
     mm_ref = np.float64(np.prod(np.asarray(ref.spacing, dtype=np.float64)))
     for k, (name, info) in enumerate(names.items()):
