@@ -164,7 +164,16 @@ int ts2d_engine_weights_ready(ts2d_engine* e);
  *                when mask_packed != NULL
  *   on_device    nonzero: input/logits/mask_packed are device pointers; zero: host pointers (staged by the engine)
  *   stream       hipStream_t as void* (NULL = the engine's own stream).  The call is asynchronous when on_device
- *                != 0 (caller synchronises the stream) and synchronous otherwise. */
+ *                != 0 (caller synchronises the stream) and synchronous otherwise.
+ * Size limits, both refused by name with TS2D_ERR_INVALID before any workspace is allocated (ts2d_engine_reserve and the sliding-window
+ * entries, whose forwards run on the patch extent, inherit them):
+ *   per call     B * H * W < 2^31 pixels; on a residual-encoder engine B * H * W <= 2^29 - 32 (the join launches 256 threads per 32 pixels).
+ *   per image    no plane of ONE image may pass 2^31 - 1 bytes, counted at four bytes per element in every precision mode: the widest
+ *                activation tensor, (H >> ly) * (W >> lx) * C * 4 over the levels of the net with C the stage's width rounded up to a
+ *                multiple of 32, and the input, C_in * H * W * 4.  For a net whose widest plane is level 0 at width 32 that is
+ *                H * W <= 16 777 215 pixels (4094 x 4096 passes, 4096 x 4096 is refused); (32, 512) on two stages is bound by level 1:
+ *                H * W <= 4 194 303.  Reason: the kernels address an image through 32-bit byte offsets ("32-bit
+ *                quantities of the forward path"). */
 int ts2d_engine_forward(ts2d_engine* e, const float* input, int B, int H, int W, float* logits,
                         uint32_t* mask_packed, int on_device, void* stream);
 

@@ -314,11 +314,12 @@ void run_sweep(Sweep& sw) {
         std::map<size_t, std::tuple<int, int, int>> geom;      // op -> tile of the tile_geom family, over every mode and batch of this extent
         for (int mode : sw.modes) {
             e->precision = mode;
+            if (!image_extent_ok(e, H, W)) { std::printf("skip %s %dx%d mode=%s: above the per-image limit of reserve_checked\n", sw.net.c_str(), H, W, kMode[mode]); continue; }
             std::map<std::pair<int, int>, WsLayout> layouts;
             std::map<std::pair<int, int>, std::vector<Choice>> plans;
             std::vector<int> ok_b;
             for (int b : bs) {
-                if ((long long)b * H * W >= (1LL << 31)) continue;                          // engine.hip:727
+                if ((long long)b * H * W >= call_pixel_limit(e)) continue;                   // engine.hip: reserve_checked
                 ok_b.push_back(b);
                 for (int f = 0; f < 2; ++f) {
                     layouts[{b, f}] = workspace_layout(e, b, H, W, f != 0);
@@ -452,6 +453,46 @@ int main_ws(const char* path) {
             for (size_t i = 0; i < plan.size(); ++i)
                 std::printf("show %s %s S=%d tile %dx%dx%d tiles %dx%d\n", e->ops[i].name.c_str(), plan[i].k == K_FUSED_AWAY ? "(composed away)" : plan[i].name, plan[i].ksplit,
                             plan[i].g.NIMG, plan[i].g.TH, plan[i].g.TW, plan[i].g.tiles_y, plan[i].g.tiles_x);
+        } else if (w == "limit") {     // limit MODE H W: the per-image predicate of reserve_checked (engine.hip; program.cpp image_extent_ok) at one extent
+            int mode, H, W;
+            f >> mode >> H >> W;
+            std::unique_ptr<ts2d_engine> e = make_engine(arch, residual ? n_blocks : nullptr);
+            if (!e) return 4;
+            for (auto& o : opts) set_option(e.get(), o.first, o.second);
+            e->precision = mode;
+            int t = -1;
+            const long long bytes = image_plane_bytes(e.get(), H, W, &t);
+            std::printf("limit %s mode=%d H=%d W=%d bytes=%lld widest=%s C=%d ok=%d call=%lld\n", sw.net.c_str(), mode, H, W, bytes, t >= 0 ? e->tensors[t].name.c_str() : "input",
+                        t >= 0 ? e->tensors[t].C : e->arch.input_channels, (int)image_extent_ok(e.get(), H, W), call_pixel_limit(e.get()));
+        } else if (w == "limits") {    // limits MODE: L1 - along W at many heights, the predicate flips once, exactly where the restated plane passes 2^31 - 1 bytes
+            int mode;
+            f >> mode;
+            std::unique_ptr<ts2d_engine> e = make_engine(arch, residual ? n_blocks : nullptr);
+            if (!e) return 4;
+            e->precision = mode;
+            const int divy = 1 << e->lvl_y[e->arch.n_stages - 1], divx = 1 << e->lvl_x[e->arch.n_stages - 1];
+            // restated from the consumers, not asked of program.cpp: a record count (int)(pixels * C * sizeof(ST)) per activation tensor (kernels_f16x3.h:218
+            // and its siblings), handed an op only under fits32(pixels * C * 4) in every mode (dispatch.cpp:165, 229-233, 271, 292, 320, 349);
+            // (int)(C0 * H * W * 4) for the network input (kernels_res32.h:144-145, dispatch.cpp:195)
+            auto plane = [&](long long H, long long W) {
+                unsigned __int128 worst = (unsigned __int128)H * W * e->arch.input_channels * 4;
+                for (const Tensor& x : e->tensors) worst = std::max(worst, (unsigned __int128)(H >> x.ly) * (W >> x.lx) * x.C * 4);
+                return worst;
+            };
+            long long n = 0;
+            for (long long H = divy; H <= (1LL << 30); H = H * 3 / 2 / divy * divy + divy) {
+                g_rep.where = fmt("%s mode=%d H=%lld", sw.net.c_str(), mode, H);
+                long long lo = 0, hi = ((1LL << 31) - 1) / H / divx + 1;      // in units of divx: ok(lo) (or lo = 0), not ok(hi) - there H * W reaches 2^31 pixels
+                if (image_extent_ok(e.get(), (int)H, (int)std::min(hi * divx, (long long)INT32_MAX / divx * divx))) g_rep.viol("L1", "accepted at 2^31 pixels");
+                while (hi - lo > 1) { const long long mid = (lo + hi) / 2; (image_extent_ok(e.get(), (int)H, (int)(mid * divx)) ? lo : hi) = mid; }
+                for (long long k = std::max(1LL, lo - 3); k <= std::min(hi + 3, ((1LL << 31) - 1) / divx); ++k) {
+                    const bool ok = image_extent_ok(e.get(), (int)H, (int)(k * divx)), want = (unsigned __int128)H * (k * divx) < ((unsigned __int128)1 << 31) && plane(H, k * divx) <= (unsigned __int128)kImagePlaneMax;
+                    if (ok != want) g_rep.viol("L1", fmt("W=%lld: the predicate says %d, the restated plane %d", k * divx, (int)ok, (int)want));
+                    ++n;
+                }
+                if (lo >= 1 && plane(H, lo * divx) > (unsigned __int128)kImagePlaneMax) g_rep.viol("L1", fmt("W=%lld accepted with a plane above the limit", lo * divx));
+            }
+            std::printf("limits %s mode=%d checked=%lld viol=%lld\n", sw.net.c_str(), mode, n, g_rep.n["L1"]);
         } else { std::fprintf(stderr, "unknown word %s\n", w.c_str()); return 6; }
     }
     std::printf("tally");

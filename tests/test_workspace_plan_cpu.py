@@ -213,6 +213,43 @@ def test_tiles_of_several_tiny_images_fit_what_the_kernels_stage(driver, tmp_pat
     assert all(v == 0 for v in _tally(out).values())
 
 
+# ------------------------------------------------------------------------------------------------------------------ the per-image limit
+# reserve_checked (csrc/engine.hip) refuses an extent whose widest per-image plane - the widest activation tensor or the NCHW input, at four bytes
+# per element in every mode - passes 2^31 - 1 bytes (csrc/program.cpp: image_extent_ok; DESIGN.md, "32-bit quantities of the forward path").
+# (name, net, mode, H, bytes per level-0 pixel of the widest plane): W = limit is the largest multiple of the divisor with H * W * bytes <= 2^31 - 1.
+LIMIT_CASES = (('w32', cases.unet(2, (32, 32), 1, cin=1, nconv=1), 'split', 4096, 32 * 4),          # widths of 32, float32 storage
+               ('w32-exact', cases.unet(2, (32, 32), 1, cin=1, nconv=1), 'exact', 4096, 32 * 4),
+               ('w24', cases.unet(2, (24, 24), 1, cin=1, nconv=1), 'split', 4096, 32 * 4),          # a width the engine pads to 32: the plane is the padded one
+               # half storage: the SAME limit - the dispatch guards every per-image kernel with fits32(pixels * C * 4) whatever the mode stores
+               # (csrc/dispatch.cpp), and the workspace plan sizes every buffer for floats
+               ('w32-half', cases.unet(2, (32, 32), 1, cin=1, nconv=1), 'f16', 4096, 32 * 4),
+               ('deep512', cases.unet(2, (32, 512), 2, cin=1, nconv=1), 'split', 2048, 512 * 4 // 4),   # level 1 is the widest: 512 channels on a quarter of the pixels
+               ('cin64', cases.unet(2, (32, 32), 1, cin=64, nconv=1), 'f16', 2048, 64 * 4))         # the float32 NCHW input is the widest
+
+
+@pytest.mark.parametrize('name,arch,mode,H,per_px', LIMIT_CASES, ids=[c[0] for c in LIMIT_CASES])
+def test_the_per_image_limit_at_below_and_above(driver, tmp_path, name, arch, mode, H, per_px):
+    limit = (2 ** 31 - 1) // (H * per_px) // 2 * 2                    # W is a multiple of the divisor 2
+    assert H * limit * per_px <= 2 ** 31 - 1 < H * (limit + 2) * per_px
+    lines = [PD.net_words(name, arch)] + [f'limit {PD.MODE_ID[mode]} {H} {w}' for w in (limit - 2, limit, limit + 2)] + [f'limits {PD.MODE_ID[mode]}']
+    out = _run(driver, tmp_path, lines, f'limit {name}')
+    got = [dict(w.split('=') for w in line.split()[2:]) for line in out if line.startswith('limit ')]
+    assert [(int(g['W']), int(g['ok']), int(g['bytes'])) for g in got] == [(w, int(w <= limit), H * w * per_px) for w in (limit - 2, limit, limit + 2)], got
+    assert all(int(g['call']) == 2 ** 31 for g in got)                # pixels per call: 2^31 on a plain encoder ...
+    sweep =[line for line in out if line.startswith('limits ')]
+    assert len(sweep) == 1 and sweep[0].endswith('viol=0') and int(sweep[0].split()[3].split('=')[1]) > 100, (sweep, [line for line in out if line.startswith('viol ')])
+
+
+def test_the_per_call_pixel_limit_of_a_residual_encoder(driver, tmp_path):
+    """... and 2^29 - 32 on a residual encoder: res_join launches 256 threads per 32 pixels of a level (csrc/engine.hip launch_join, float32 storage)
+    and a launch holds fewer than 2^32 threads."""
+    ppb, threads, most = 32, 256, 2 ** 29 - 32
+    assert (most + ppb - 1) // ppb * threads < 2 ** 32 <= (most + 1 + ppb - 1) // ppb * threads
+    out = _run(driver, tmp_path, [PD.net_words('res_min', RES_CASES['res_min'][0]), f'limit {PD.MODE_ID["split"]} 256 256'], 'call limit')
+    got = [dict(w.split('=') for w in line.split()[2:]) for line in out if line.startswith('limit ')]
+    assert len(got) == 1 and int(got[0]['call']) == most + 1 and int(got[0]['ok']) == 1, got
+
+
 # ------------------------------------------------------------------------------------------------------------------ the proof that it bites
 # The named case: the EDGE net on 96 x 160 (ragged deep levels), split mode, a layout reserved for 5 slices under the full dispatch, a run of
 # one slice under the by-size dispatch - split-K convs, an un-composed decoder entry in the scratch region, extent-following tiles.

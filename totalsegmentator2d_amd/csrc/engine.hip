@@ -725,6 +725,18 @@ int ts2d::reserve_checked(ts2d_engine* e, int B, int H, int W, bool full) {
     if ((H / divy) * (W / divx) <= 1)   // torch InstanceNorm2d raises "Expected more than 1 spatial element" here too
         return fail(TS2D_ERR_INVALID, "shape %dx%d leaves a single bottleneck pixel: InstanceNorm needs more than 1 spatial element", H, W);
     if ((long long)B * H * W >= (1LL << 31)) return fail(TS2D_ERR_INVALID, "B*H*W = %lld exceeds 2^31 pixels per call", (long long)B * H * W);
+    if ((long long)B * H * W >= call_pixel_limit(e))
+        return fail(TS2D_ERR_INVALID, "B*H*W = %lld exceeds the 2^29 - 32 pixels per call of a residual-encoder engine (res_join launches 8 threads per pixel)", (long long)B * H * W);
+    // one image: every plane the kernels address through a per-image buffer resource stays below 2^31 bytes (program.cpp: image_plane_bytes)
+    if (!image_extent_ok(e, H, W)) {
+        int t = -1;
+        const long long bytes = image_plane_bytes(e, H, W, &t);
+        const int C = t >= 0 ? e->tensors[t].C : e->arch.input_channels;
+        const int ly = t >= 0 ? e->tensors[t].ly : 0, lx = t >= 0 ? e->tensors[t].lx : 0;
+        return fail(TS2D_ERR_INVALID, "image extent %dx%d exceeds the per-image limit: %s holds %lld bytes per image (%d channels of 4 bytes at %dx%d), the limit is "
+                    "%lld bytes (2^31 - 1), %lld pixels at that width", H, W, t >= 0 ? e->tensors[t].name.c_str() : "the input", bytes, C, H >> ly, W >> lx,
+                    kImagePlaneMax, kImagePlaneMax / ((long long)C * 4));
+    }
     return ensure_workspace(e, B, H, W, full);
 }
 

@@ -224,6 +224,13 @@ ts2d_arch_desc pad_arch(const ts2d_arch_desc& a, bool& padded);
 void expand_blob(const ts2d_arch_desc& ua, const ts2d_arch_desc& pa, const int* n_blocks, const float* ub, std::vector<float>& pb);
 int build_program(ts2d_engine* e);
 int tensor_index(ts2d_engine* e, const std::string& name);      // -1: no such tensor
+// The per-image limit of a forward (reserve_checked refuses beyond it): bytes of the largest plane one image occupies - the widest activation tensor
+// or the NCHW input, at four bytes per element in every mode - and the bound the kernels' per-image buffer resources and 32-bit in-image byte
+// offsets set for it.  `widest`: index of that tensor (-1: the input).  Host arithmetic only: swept on the CPU by tests/plan_driver.cpp.
+constexpr long long kImagePlaneMax = (1LL << 31) - 1;
+long long image_plane_bytes(const ts2d_engine* e, int H, int W, int* widest);
+bool image_extent_ok(const ts2d_engine* e, int H, int W);
+long long call_pixel_limit(const ts2d_engine* e);      // B * H * W of a call stays below it: 2^31, or 2^29 - 31 on a residual encoder (res_join's launch)
 
 // ---- pack_weights.cpp: PyTorch-layout blob -> packed device layouts (host staging buffer `out`, weight_floats long)
 void pack_weights(const ts2d_engine* e, const float* blob, float* out);

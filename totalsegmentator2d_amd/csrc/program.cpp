@@ -323,4 +323,28 @@ int build_program(ts2d_engine* e) {
     return TS2D_OK;
 }
 
+// The largest plane ONE image of an H x W forward occupies: the widest activation tensor, or the NCHW input, counted as floats in EVERY mode.  The
+// kernels of the dedicated families address an image through a buffer resource whose record count is (int)plane_bytes and whose lane and scalar
+// offsets are 32-bit byte offsets ("32-bit quantities of the forward path"); dispatch.cpp hands them an op only while fits32() holds for
+// the op's planes at four bytes per element - the 16-bit mode included, whose buffers the workspace plan sizes for floats too - and beyond that
+// falls back to the generic kernels, which no test has ever run at such a size.  reserve_checked therefore refuses where the first plane reaches
+// 2^31 bytes: inside the limit fits32() holds for every op, and every accepted extent runs the kernels the suite judges.
+// Extents whose pixel count alone reaches 2^31 are answered with that count (no product here leaves 64 bits).
+long long image_plane_bytes(const ts2d_engine* e, int H, int W, int* widest) {
+    if (widest) *widest = -1;
+    if (H < 1 || W < 1 || (long long)H * W >= (1LL << 31)) return (long long)H * W;
+    const long long elt = 4;
+    long long worst = (long long)H * W * e->arch.input_channels * 4;
+    for (size_t t = 0; t < e->tensors.size(); ++t) {
+        const Tensor& x = e->tensors[t];
+        const long long b = (long long)(H >> x.ly) * (W >> x.lx) * x.C * elt;
+        if (b > worst) { worst = b; if (widest) *widest = (int)t; }
+    }
+    return worst;
+}
+// Pixels B * H * W one call may hold (exclusive).  2^31: the pixel index of the generic staging loops is an int.  A residual encoder: res_join (fp32
+// storage) launches 256 threads per 32 pixels of a level - 8 per pixel - and a launch holds fewer than 2^32 threads, so its level-0 join ends where ceil(pixels / 32) * 256 would reach 2^32: at most 2^29 - 32 pixels.
+long long call_pixel_limit(const ts2d_engine* e) { return e->residual ? (1LL << 29) - 31 : (1LL << 31); }
+bool image_extent_ok(const ts2d_engine* e, int H, int W) { return H >= 1 && W >= 1 && (long long)H * W < (1LL << 31) && image_plane_bytes(e, H, W, nullptr) <= kImagePlaneMax; }
+
 }  // namespace ts2d
