@@ -819,6 +819,36 @@ int ts2d_visual_grey(int device, const void* plane, int dtype, int H, int W, dou
 int ts2d_label_statistics(int device, const uint8_t* seg, int kind, const uint8_t* values, int K, int Z, int H, int W, const float* intensities,
                           int C, size_t max_scratch_bytes, int64_t* out_int, double* out_f64, int* status);
 
+/* Percentiles of the intensities under a label on the device: per (label, channel, percentile) the two float32 samples numpy's linear
+ * percentile interpolates between, and the weight.  The statement is totalsegmentator2d_amd/statistics.py (label_percentiles_statement, numpy);
+ * the entry reproduces counts, rank values and weights bit for bit, and the caller interpolates on the host (statistics.percentile_of_values).
+ * Host pointers in and out, synchronous: ONE upload, every label on the device, ONE download; scratch of the call's own, freed on every path.
+ *   seg, kind, values, K, Z, H, W   as ts2d_label_statistics has them, with its limits.
+ *   intensities  float32 [C][Z][H][W], C in 1 ... TS2D_STATS_MAX_CHANNELS.
+ *   percentiles  float64 [P], P in 1 ... TS2D_STATS_MAX_PERCENTILES, each finite and in 0 ... 100.
+ *   max_scratch_bytes  bound of the device state of the labels that work at once: per label and channel 2 P selections of a rank (int64), a
+ *              prefix (uint64) and 256 bins (uint32), and per label the row partials of the counting pass (20 bytes per row); the labels are
+ *              processed in chunks that stay below it; 0: 256 MiB.  The result does not depend on the chunking.
+ *   out_count  int64 [K]: the label's samples, n.
+ *   out_rank_f32  float32 [K][C][P][2]: the channel's samples under the label at the sorted positions i and j of percentile q among n:
+ *              h = (n - 1) * (q / 100), i = min(floor(h), n - 1), j = min(i + 1, n - 1), each operation an IEEE float64 one.  The order is
+ *              that of the order-preserving keys of csrc/ray_select.h: -0.0 right below +0.0, equal values repeated.
+ *   out_weight_f64  float64 [K][P]: t = h - i.  It does not depend on the channel.
+ *              An empty label: count 0, rank values +0.0, weights +0.0.
+ *   status     0, or TS2D_STATS_NONFINITE: an intensity under a label is NaN or infinite; the outputs are not written, the caller takes the
+ *              host route.  The call returns TS2D_OK.  A non-finite sample under no label is of no consequence.
+ * The selection runs straight over (segmentation, intensity) pairs inside the label's bounding box - four rounds of one 8-bit digit of the key
+ * each, no key buffer; the boxes are read on the device, none is downloaded (csrc/kernels_stats_select.h).
+ * TS2D_ERR_INVALID, by name, before any device work: a null pointer, an unknown kind, K outside 1 ... 255, an extent below 1 or more than
+ * 2^31 - 1 voxels, C outside 1 ... TS2D_STATS_MAX_CHANNELS, P outside 1 ... TS2D_STATS_MAX_PERCENTILES, a percentile that is not finite or
+ * outside 0 ... 100, a label map without values or with a value 0, the state of ONE label above max_scratch_bytes.  On any error the outputs
+ * are untouched.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+#define TS2D_STATS_MAX_PERCENTILES 8
+int ts2d_label_percentiles(int device, const uint8_t* seg, int kind, const uint8_t* values, int K, int Z, int H, int W, const float* intensities,
+                           int C, const double* percentiles, int P, size_t max_scratch_bytes, int64_t* out_count, float* out_rank_f32,
+                           double* out_weight_f64, int* status);
+
 /* Scoring a segmentation against a reference on the device.  The statements are totalsegmentator2d_amd/evaluate.py (project_labels,
  * overlap_statement, surface_statement; numpy); the three entries reproduce them byte for byte and bit for bit.  Host pointers in and out,
  * synchronous; each input is uploaded once, the result downloaded once; scratch of the call's own, freed on every path.

@@ -1,0 +1,65 @@
+// TEST INFRASTRUCTURE (never linked into the product): the host walk of csrc/label_select.h and the chunk planner of csrc/stats_plan.cpp
+// behind a main of their own.  Built by tests/test_statistics_percentiles_cpu.py under the address and undefined-behaviour sanitizers; touches
+// no device and is never loaded into Python.
+//
+//     label_select_driver walk FILE     FILE: cases of (int32 kind, value, n, P; float64 q[P]; uint8 m[n]; float32 x[n]).  Per case one line:
+//                                       count bad, then per percentile the bits of the two rank values and of the weight.
+//     label_select_driver plan FILE     FILE: text lines "K C P rows max_scratch_bytes".  Per line: rc need budget, then the chunks k0:k1.
+#include "../totalsegmentator2d_amd/csrc/label_select.h"
+#include "../totalsegmentator2d_amd/csrc/stats_plan.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+static int walk(const char* path) {
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return 2;
+    int head[4];
+    while (std::fread(head, sizeof(int), 4, f) == 4) {
+        const int kind = head[0], value = head[1], P = head[3];
+        const size_t n = (size_t)head[2];
+        std::vector<double> q((size_t)P), w((size_t)P);
+        std::vector<uint8_t> m(n);
+        std::vector<float> x(n), rv(2 * (size_t)P);
+        if (std::fread(q.data(), 8, (size_t)P, f) != (size_t)P || std::fread(m.data(), 1, n, f) != n || std::fread(x.data(), 4, n, f) != n) return 3;
+        int bad = 0;
+        const long long count = ts2d::ls_label_percentiles(m.data(), kind, (uint8_t)value, x.data(), n, q.data(), P, rv.data(), w.data(), &bad);
+        std::printf("%lld %d", count, bad);
+        for (int p = 0; p < P; ++p) {
+            unsigned lo, hi;
+            unsigned long long t;
+            std::memcpy(&lo, &rv[2 * (size_t)p], 4); std::memcpy(&hi, &rv[2 * (size_t)p + 1], 4); std::memcpy(&t, &w[(size_t)p], 8);
+            std::printf(" %u %u %llu", lo, hi, t);
+        }
+        std::printf("\n");
+    }
+    std::fclose(f);
+    return 0;
+}
+
+static int plan(const char* path) {
+    FILE* f = std::fopen(path, "r");
+    if (!f) return 2;
+    int K, C, P;
+    long long rows;
+    unsigned long long bound;
+    while (std::fscanf(f, "%d %d %d %lld %llu", &K, &C, &P, &rows, &bound) == 5) {
+        std::vector<ts2d::LsChunk> chunks;
+        size_t need = 0, budget = 0;
+        const int rc = ts2d::ls_plan(K, C, P, rows, (size_t)bound, &chunks, &need, &budget);
+        std::printf("%d %zu %zu", rc, need, budget);
+        for (const ts2d::LsChunk& c : chunks) std::printf(" %d:%d", c.k0, c.k1);
+        std::printf("\n");
+    }
+    std::fclose(f);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc != 3) return 1;
+    if (!std::strcmp(argv[1], "walk")) return walk(argv[2]);
+    if (!std::strcmp(argv[1], "plan")) return plan(argv[2]);
+    return 1;
+}

@@ -82,6 +82,7 @@ PROJECT_NONFINITE, PROJECT_RAY_TOO_LONG = 1, 2              # TS2D_PROJECT_NONFI
 VISUAL_NONFINITE = 1                                        # TS2D_VISUAL_NONFINITE
 STATS_PLANES, STATS_LABELMAP, STATS_NONFINITE = 0, 1, 1     # TS2D_STATS_PLANES, TS2D_STATS_LABELMAP, TS2D_STATS_NONFINITE
 STATS_INTS, STATS_F64S, STATS_MAX_CHANNELS = 10, 6, 64      # TS2D_STATS_INTS, TS2D_STATS_F64S, TS2D_STATS_MAX_CHANNELS
+STATS_MAX_PERCENTILES = 8                                   # TS2D_STATS_MAX_PERCENTILES
 LABELS_RANGE, EVAL_MAX_TOLERANCES, EVAL_MAX_EXTENT = 1, 8, 32767      # TS2D_LABELS_RANGE, TS2D_EVAL_MAX_TOLERANCES, TS2D_EVAL_MAX_EXTENT
 EVAL_MAX_PERCENTILES = 8                                    # TS2D_EVAL_MAX_PERCENTILES
 
@@ -132,6 +133,7 @@ SIGNATURES = {
     'ts2d_visual_labels': (_I, [_I, _P, _I, _I, _I, _D, _D, _P, _I, _I, _I, _P]),
     'ts2d_visual_grey': (_I, [_I, _P, _I, _I, _I, _D, _D, _I, _D, _D, _I, _I, _I, _I, _P, _P, ctypes.POINTER(_I)]),
     'ts2d_label_statistics': (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _Z, _P, _P, ctypes.POINTER(_I)]),
+    'ts2d_label_percentiles': (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _Z, _P, _P, _P, ctypes.POINTER(_I)]),
     'ts2d_project_labels_coronal': (_I, _PROJECT[:-2] + [_I, _P, _P]),
     'ts2d_label_overlap': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     'ts2d_surface_distances': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _D, _D, _P, _I, _Z, _P, _P]),
@@ -164,12 +166,13 @@ SYMBOLS = tuple(SIGNATURES)
 # ... and the projection modes: without the entry TS2D keeps the host route for a channel name beyond max / mean
 # ... and the two entries of the PNG visuals: without them visual.create_visual returns the statement's bytes from the host
 # ... and the per-label statistics: without the entry statistics.label_statistics keeps the host route (its statement)
+# ... and the percentiles under a label: without the entry statistics.label_statistics takes them from its statement
 # ... and the three entries of the evaluation: without them evaluate.evaluate and Result.evaluate keep the host route (the statements)
 # ... and the distance profile: without the entry evaluate.evaluate takes percentiles and average distances from its statement
 # ... and the boundary distances of volumes: without the entry evaluate.evaluate(volume_distances=True) keeps its statement
 OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n
                      or n.startswith('ts2d_visual_')
-                     or n in ('ts2d_engine_create_residual', 'ts2d_keep_largest_components', 'ts2d_project_coronal_modes', 'ts2d_label_statistics',
+                     or n in ('ts2d_engine_create_residual', 'ts2d_keep_largest_components', 'ts2d_project_coronal_modes', 'ts2d_label_statistics', 'ts2d_label_percentiles',
                               'ts2d_project_labels_coronal', 'ts2d_label_overlap', 'ts2d_surface_distances', 'ts2d_surface_distance_profile',
                               'ts2d_volume_surface_distances'))
 

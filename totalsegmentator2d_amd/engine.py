@@ -732,6 +732,22 @@ def visual_grey(plane: np.ndarray, spacing_hw, cubic: bool, lo, hi, out_hw, devi
     return out, (float(used[0]), float(used[1]))
 
 
+def _label_side(who: str, seg: np.ndarray, kind: int, values, z: int, h: int, w: int):
+    """``(values as uint8 or None, K)`` of the label side of a statistics call: C-contiguous uint8 planes [K, Z, H, W] or one label map
+    [Z, H, W] with ``values`` [K]."""
+    if seg.dtype != np.uint8 or not seg.flags['C_CONTIGUOUS']:
+        raise RuntimeError(f"{who}: expected a C-contiguous uint8 segmentation, found {seg.dtype} {seg.shape}")
+    if kind == _lib.STATS_LABELMAP:
+        vals = np.ascontiguousarray(values, dtype=np.uint8)
+        if seg.size != z * h * w:
+            raise RuntimeError(f"{who}: a label map of {seg.size} samples for {z} x {h} x {w}")
+        return vals, int(vals.size)
+    k = int(seg.shape[0])
+    if seg.size != k * z * h * w:
+        raise RuntimeError(f"{who}: planes of {seg.size} samples for {k} x {z} x {h} x {w}")
+    return None, k
+
+
 def label_statistics(seg: np.ndarray, kind: int, values, shape_zhw, intensities: Optional[np.ndarray] = None, max_scratch_bytes: int = 0,
                      device: int = 0):
     """The per-label statistics on the device (C-ABI ts2d_label_statistics, csrc/kernels_stats.h).  ``seg``: C-contiguous uint8, planes
@@ -740,18 +756,7 @@ def label_statistics(seg: np.ndarray, kind: int, values, shape_zhw, intensities:
     numbers bit for bit - or None where the entry set a status bit (a non-finite intensity under a label): the caller takes the host route."""
     fn = _entry('ts2d_label_statistics')
     z, h, w = (int(v) for v in shape_zhw)
-    if seg.dtype != np.uint8 or not seg.flags['C_CONTIGUOUS']:
-        raise RuntimeError(f"label_statistics: expected a C-contiguous uint8 segmentation, found {seg.dtype} {seg.shape}")
-    if kind == _lib.STATS_LABELMAP:
-        vals = np.ascontiguousarray(values, dtype=np.uint8)
-        k = int(vals.size)
-        if seg.size != z * h * w:
-            raise RuntimeError(f"label_statistics: a label map of {seg.size} samples for {z} x {h} x {w}")
-    else:
-        vals = None
-        k = int(seg.shape[0])
-        if seg.size != k * z * h * w:
-            raise RuntimeError(f"label_statistics: planes of {seg.size} samples for {k} x {z} x {h} x {w}")
+    vals, k = _label_side('label_statistics', seg, kind, values, z, h, w)
     c = 0
     if intensities is not None:
         if intensities.dtype != np.float32 or not intensities.flags['C_CONTIGUOUS'] or intensities.size % (z * h * w):
@@ -766,6 +771,33 @@ def label_statistics(seg: np.ndarray, kind: int, values, shape_zhw, intensities:
     if status.value:
         return None
     return out_int, out_f64
+
+
+def label_percentiles(seg: np.ndarray, kind: int, values, shape_zhw, intensities: np.ndarray, percentiles, max_scratch_bytes: int = 0,
+                      device: int = 0):
+    """The samples under every label at the sorted positions of percentiles, on the device (C-ABI ts2d_label_percentiles,
+    csrc/kernels_stats_select.h).  ``seg``, ``kind``, ``values``, ``shape_zhw``: as :func:`label_statistics`; ``intensities``: float32
+    [C, Z, H, W], C >= 1; ``percentiles``: 1 ... 8 floats in 0 ... 100.  Returns ``(count int64 [K], rank_value float32 [K, C, P, 2],
+    rank_weight float64 [K, P])`` - ``statistics.label_percentiles_statement``'s bit for bit - or None where the entry set a status bit (a
+    non-finite intensity under a label): the caller takes the host route."""
+    fn = _entry('ts2d_label_percentiles')
+    z, h, w = (int(v) for v in shape_zhw)
+    vals, k = _label_side('label_percentiles', seg, kind, values, z, h, w)
+    if intensities is None or intensities.dtype != np.float32 or not intensities.flags['C_CONTIGUOUS'] or intensities.size % (z * h * w):
+        raise RuntimeError(f"label_percentiles: expected C-contiguous float32 intensities [C, {z}, {h}, {w}]")
+    c = intensities.size // (z * h * w)
+    qs = np.ascontiguousarray(percentiles, dtype=np.float64).reshape(-1)
+    p = int(qs.size)
+    count = np.zeros(k, np.int64)
+    rank_value = np.zeros((k, c, p, 2), np.float32)
+    rank_weight = np.zeros((k, p), np.float64)
+    status = ctypes.c_int(0)
+    _lib.check(fn(int(device), seg.ctypes.data, int(kind), vals.ctypes.data if vals is not None else None, k, z, h, w, intensities.ctypes.data, c,
+                  qs.ctypes.data, p, int(max_scratch_bytes), count.ctypes.data, rank_value.ctypes.data, rank_weight.ctypes.data,
+                  ctypes.byref(status)), 'ts2d_label_percentiles')
+    if status.value:
+        return None
+    return count, rank_value, rank_weight
 
 
 def project_labels_coronal(buffer: np.ndarray, extents, strides, base: int, num: int, device: int = 0):

@@ -1,6 +1,7 @@
 """``ts2d`` command line (reference ``ts2d/main.py:10-115``): same flags, same output file names."""
 from __future__ import annotations
 
+import math
 import os
 from glob import glob
 
@@ -63,12 +64,14 @@ def _references(reference, cases, src_is_dir: bool) -> dict:
 
 def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fetch_remote: bool = True, collapse: bool = False,
              visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1, save_probabilities: bool = False,
-             statistics: bool = False, reference: str = None, hausdorff_percentiles=(), average_distance: bool = False):
+             statistics: bool = False, reference: str = None, hausdorff_percentiles=(), average_distance: bool = False,
+             statistics_percentiles=()):
     model = DEFAULT_MODEL if model is None else model
     content = 'all' if visualize else 'file'
     which = 'all' if save_all else 'final'
     log = (lambda *a: None) if silent else print
     log("TS2D is a research tool. It is NOT validated for clinical use and should NOT be used for medical diagnosis or treatment.")
+    stat_kw = {'percentiles': tuple(statistics_percentiles)} if len(statistics_percentiles) else {}      # without them: the call of before
     with TS2D(key=model, use_remote=use_remote, fetch_remote=fetch_remote, models=models) as ts:
         cases = list(_enumerate_cases(src))
         references = _references(reference, cases, os.path.isdir(src))
@@ -84,7 +87,7 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
                     res.save(dest=dest, name=name, models=which, content=content, targets=['segmentation', 'projection'])
                     res.save_probabilities(dest, name)
                     if statistics:
-                        res.save_statistics(dest, name, models=which)
+                        res.save_statistics(dest, name, models=which, **stat_kw)
                     if references:
                         res.save_evaluation(dest, name, references[name], percentiles=hausdorff_percentiles, average_distance=average_distance)
             return
@@ -94,7 +97,7 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
             res.save(dest=dest, name=name, models=which, content=content, targets=['segmentation', 'projection'])
             res.save_probabilities(dest, name)
             if statistics:
-                res.save_statistics(dest, name, models=which)
+                res.save_statistics(dest, name, models=which, **stat_kw)
             if references:
                 res.save_evaluation(dest, name, references[name], percentiles=hausdorff_percentiles, average_distance=average_distance)
 
@@ -117,6 +120,9 @@ def ts2d_entry_point(argv=None):
                    "<case>-<group>.npz (key 'probabilities', float32 [K, *shape of the sub-model's 2-D input]) per sub-model.")
     p.add_argument("--statistics", action="store_true", help="Also write <case>.statistics.json: per label count, mm, bounding box, centroid and "
                    "min / max / mean / std of every projection under it (with --save-all one <case>-<group>.statistics.json per sub-model too).")
+    p.add_argument("--statistics-percentile", type=float, action="append", default=None, metavar="Q", help="With --statistics: also write per label "
+                   "and projection percentile[Q], the Q-th percentile of the projection under the label (50: the median), Q in 0 ... 100; may be "
+                   "given up to 8 times.")
     p.add_argument("--reference", type=str, default=None, help="Score every result against a reference and write <case>.evaluation.json (per label "
                    "Dice, IoU, precision, recall, surface Dice at 2 mm, Hausdorff distance): a 3-D label volume (label v = segment v) or a 2-D "
                    "segmentation; a file for a single input, or a directory that holds a file of the same name for every case.")
@@ -129,10 +135,14 @@ def ts2d_entry_point(argv=None):
         p.error("--batch-cases must be at least 1")
     if (a.hausdorff_percentile or a.average_distance) and a.reference is None:
         p.error("--hausdorff-percentile and --average-distance score against a reference: give --reference")
+    if a.statistics_percentile and not a.statistics:
+        p.error("--statistics-percentile adds to the statistics: give --statistics")
+    if a.statistics_percentile and (len(a.statistics_percentile) > 8 or any(not (math.isfinite(q) and 0.0 <= q <= 100.0) for q in a.statistics_percentile)):
+        p.error("--statistics-percentile: at most 8 values, each in 0 ... 100")
     ts2d_run(src=a.src, dest=a.dest, model=a.model, use_remote=not a.no_remote, fetch_remote=not a.no_fetch, collapse=a.collapse,
              visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases, save_probabilities=a.save_probabilities,
              statistics=a.statistics, reference=a.reference, hausdorff_percentiles=tuple(a.hausdorff_percentile or ()),
-             average_distance=a.average_distance)
+             average_distance=a.average_distance, **({'statistics_percentiles': tuple(a.statistics_percentile)} if a.statistics_percentile else {}))
 
 
 if __name__ == '__main__':

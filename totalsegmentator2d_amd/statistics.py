@@ -24,6 +24,14 @@ starts at ``+0.0`` never becomes ``-0.0``.
 
 A non-finite intensity under a label is a status at the device entry (it writes nothing); the statement computes what numpy computes (NaN or
 inf), and :func:`label_statistics` hands such a case to it.
+
+PERCENTILES.  On request (``percentiles``: at most 8, each in 0 ... 100) the median and any other percentile of every intensity channel under
+every label - numpy's linear method.  :func:`label_percentiles_statement` is the definition: the samples of a channel under a label are ordered
+by their keys (``-0.0`` right below ``+0.0``, equal values repeated), percentile ``q`` among ``n`` samples selects the sorted positions ``i`` and
+``j`` and the weight ``t`` of ``evaluate.percentile_ranks``, and :func:`percentile_of_values` interpolates between the two samples in float64.
+The device route (C-ABI ``ts2d_label_percentiles``, ``csrc/kernels_stats_select.h``) SELECTS only - a most-significant-digit-first radix
+selection straight over (segmentation, intensity) pairs inside the label's box, the counts, the two samples and the weight bit for bit -; the
+interpolation runs on the host on both routes, so the percentiles are the same bits either way.
 """
 from __future__ import annotations
 
@@ -34,9 +42,13 @@ import numpy as np
 
 from .nrrd import Image
 
+from .evaluate import _percentiles, percentile_key, percentile_ranks
+
 LANES = 64
 # No size gate: the device route lost at no measured size, the small end included - 117 labels at 53 x 133 with 2 channels take 1.05 ms there
 # against 15.8 ms for the statement and 5.8 ms for plain per-label numpy (scripts/gpu_statistics_case.py, profiles/r28_statistics_case.txt).
+# No size gate for the percentiles either: at the same small end q = (5, 50, 95) take 1.44 ms on the device against 11.1 ms for the statement and
+# 14.4 ms for np.percentile per label and channel (scripts/gpu_statistics_percentiles_case.py, profiles/r35_statistics_percentiles_case.txt).
 
 
 def float_keys(x: np.ndarray) -> np.ndarray:
@@ -166,6 +178,96 @@ def _device_statistics(planes, values, spatial, x, spacing, device: int, max_scr
     return out
 
 
+def percentile_of_values(lo, hi, t) -> np.float64:
+    """The percentile from the two selected samples and the weight (``evaluate.percentile_ranks``): numpy's linear method on the two values
+    widened exactly to float64, every operation rounded on its own.  ``lo`` where ``t == 0`` or ``hi == lo``, else ``lo + (hi - lo) * t`` for
+    ``t < 0.5`` and ``hi - (hi - lo) * (1 - t)`` from there (``evaluate.percentile_of_ranks`` without the roots).  Infinite samples give what
+    IEEE gives."""
+    lo, hi, t = np.float64(lo), np.float64(hi), np.float64(t)
+    if t == 0 or hi == lo:
+        return lo
+    with np.errstate(invalid='ignore', over='ignore'):
+        if t < 0.5:
+            return lo + (hi - lo) * t
+        return hi - (hi - lo) * (np.float64(1) - t)
+
+
+def _percentiles_of_ranks(count: np.ndarray, rank_value: np.ndarray, rank_weight: np.ndarray) -> np.ndarray:
+    """float64 [K, C, P]: :func:`percentile_of_values` of every selected pair; zeros for an empty label."""
+    K, C, P = rank_value.shape[:3]
+    out = np.zeros((K, C, P), np.float64)
+    for k in range(K):
+        if count[k] > 0:
+            for c in range(C):
+                for p in range(P):
+                    out[k, c, p] = percentile_of_values(rank_value[k, c, p, 0], rank_value[k, c, p, 1], rank_weight[k, p])
+    return out
+
+
+def label_percentiles_statement(seg: np.ndarray, intensities: np.ndarray, percentiles: Sequence[float], values: Optional[Sequence[int]] = None) -> dict:
+    """THE DEFINITION of the percentiles under a label.  ``seg``, ``values``: as in :func:`label_statistics_statement`; ``intensities``:
+    ``[C, *spatial]`` float32, C >= 1; ``percentiles``: at most 8, each finite and in 0 ... 100 (``evaluate``'s check), else ``ValueError``.
+
+    For label ``k`` with ``n > 0`` samples and percentile ``q``, ``(i, j, t) = evaluate.percentile_ranks(n, q)``; the samples of channel ``c``
+    under the label are ordered by their keys (:func:`float_keys`).  Returns ``count`` int64 [K]; ``rank_value`` float32 [K, C, P, 2], the
+    samples at the sorted positions ``i`` and ``j``; ``rank_weight`` float64 [K, P] = ``t``; ``percentile`` float64 [K, C, P] =
+    :func:`percentile_of_values` of them.  An empty label: zeros everywhere (the callers report None).  A NaN under the label makes every
+    percentile of that (label, channel) NaN, as ``np.percentile`` does; infinities are ordinary keys.  The definition is the sorted order; the
+    two positions are taken with ``np.partition``."""
+    qs = _percentiles(percentiles, 'label_percentiles_statement')
+    seg = np.asarray(seg)
+    if values is None:
+        spatial, K = seg.shape[1:], seg.shape[0]
+    else:
+        spatial, K = seg.shape, len(values)
+    if len(spatial) < 1:
+        raise ValueError("label_percentiles_statement: the segmentation has no spatial axis")
+    x = np.asarray(intensities)
+    if x.ndim != len(spatial) + 1 or x.shape[0] < 1 or x.shape[1:] != tuple(spatial):
+        raise ValueError(f"label_percentiles_statement: intensities {x.shape} are not [C >= 1, *{tuple(spatial)}]")
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    C, P = x.shape[0], len(qs)
+    keys = [float_keys(x[c]) for c in range(C)]
+    out = {'count': np.zeros(K, np.int64), 'rank_value': np.zeros((K, C, P, 2), np.float32), 'rank_weight': np.zeros((K, P), np.float64)}
+    nan = np.zeros((K, C), bool)
+    for k in range(K):
+        mask = (seg[k] > 0) if values is None else (seg == values[k])
+        n = int(np.count_nonzero(mask))
+        out['count'][k] = n
+        if n == 0 or P == 0:
+            continue
+        ranks = [percentile_ranks(n, q) for q in qs]
+        at = sorted({r for i, j, _ in ranks for r in (i, j)})
+        out['rank_weight'][k] = [t for _, _, t in ranks]
+        for c in range(C):
+            kk = np.partition(keys[c][mask], at)
+            nan[k, c] = bool(np.isnan(x[c][mask]).any())
+            for p, (i, j, _) in enumerate(ranks):
+                out['rank_value'][k, c, p] = float_unkeys(kk[[i, j]])
+    out['percentile'] = _percentiles_of_ranks(out['count'], out['rank_value'], out['rank_weight'])
+    out['percentile'][nan] = np.nan
+    return out
+
+
+def _device_percentiles(planes, values, spatial, x, qs, device: int, max_scratch_bytes: int = 0) -> Optional[dict]:
+    """The statement's dict from ``ts2d_label_percentiles`` (the interpolation on the host); None where the entry set a status bit."""
+    from . import _lib, engine
+    nd = len(spatial)
+    zhw = (1,) * (3 - nd) + tuple(int(v) for v in spatial)
+    got = engine.label_percentiles(planes, _lib.STATS_PLANES if values is None else _lib.STATS_LABELMAP, values, zhw, x, qs, max_scratch_bytes, device)
+    if got is None:
+        return None
+    count, rank_value, rank_weight = got
+    return {'count': count, 'rank_value': rank_value, 'rank_weight': rank_weight, 'percentile': _percentiles_of_ranks(count, rank_value, rank_weight)}
+
+
+def device_serves_percentiles(planes: np.ndarray, values, spatial, C: int, P: int) -> bool:
+    """Does ``ts2d_label_percentiles`` serve the case?  What :func:`device_serves` asks, at least one channel and one percentile, and a library
+    that has the symbol."""
+    from . import engine
+    return C >= 1 and P >= 1 and device_serves(planes, values, spatial, C) and engine.has_entry('ts2d_label_percentiles')
+
+
 def device_serves(planes: np.ndarray, values, spatial, C: int) -> bool:
     """Does ``ts2d_label_statistics`` serve the case?  uint8 samples, 2 or 3 spatial axes, at most 2^31 - 1 voxels, 1 ... 255 labels with values
     1 ... 255, at most 64 channels, and a library that has the symbol."""
@@ -189,7 +291,7 @@ def _array_of(img) -> np.ndarray:
     return np.asarray(img)
 
 
-def label_statistics(seg: Image, intensities: Optional[dict] = None, device: Optional[int] = None) -> Dict[str, dict]:
+def label_statistics(seg: Image, intensities: Optional[dict] = None, device: Optional[int] = None, percentiles: Sequence[float] = ()) -> Dict[str, dict]:
     """name -> statistics for every named label of ``seg`` (the names and values of ``image.get_annotation_labels``).
 
     ``seg``: a multi-component segmentation (label ``v`` is component ``v - 1`` > 0) or a label map (label ``v`` is ``seg == v``).
@@ -203,8 +305,16 @@ def label_statistics(seg: Image, intensities: Optional[dict] = None, device: Opt
     Route: ``ts2d_label_statistics`` where ``device`` is given, the library has the symbol and the entry serves the case
     (:func:`device_serves`), else :func:`label_statistics_statement`; a status bit of the entry (a non-finite intensity under a label) sends
     the case to the statement too.  The numbers are the same bit for bit.  A plane-major multi-component segmentation (the merged result,
-    what ``export.py`` builds) is handed over without a copy; an interleaved one (a file read back) is made plane-major first."""
+    what ``export.py`` builds) is handed over without a copy; an interleaved one (a file read back) is made plane-major first.
+
+    ``percentiles`` (at most 8, each finite and in 0 ... 100, else ``ValueError``) adds to every ``intensity[channel]`` the key
+    ``'percentile'``: ``{evaluate.percentile_key(q): value}``, numpy's linear percentile of the channel's samples under the label (50: the
+    median); an empty label gets None for every ``q``.  Route: ``ts2d_label_percentiles`` under the conditions above and with at least one
+    channel (:func:`device_serves_percentiles`), else :func:`label_percentiles_statement`; a status bit sends the case to the statement.  The
+    device selects, the host interpolates (:func:`percentile_of_values`) on both routes: the same bits.  With ``percentiles=()`` the dict and
+    the device calls are those of before."""
     from .image import get_annotation_labels
+    qs = _percentiles(percentiles, 'label_statistics')
     names = get_annotation_labels(seg)
     multi = seg.components > 1
     spatial = tuple(seg.array.shape[:seg.dimension])
@@ -234,6 +344,12 @@ def label_statistics(seg: Image, intensities: Optional[dict] = None, device: Opt
         raw = _device_statistics(planes, values, spatial, x, seg.spacing, int(device))
     if raw is None:
         raw = label_statistics_statement(planes, x, seg.spacing, values) if names else None
+    pct = None
+    if qs and names and chans:
+        if device is not None and device_serves_percentiles(planes, values, spatial, len(chans), len(qs)):
+            pct = _device_percentiles(planes, values, spatial, x, qs, int(device))
+        if pct is None:
+            pct = label_percentiles_statement(planes, x, qs, values)
     nd = len(spatial)
     origin = np.asarray(seg.origin, np.float64)
     D = np.asarray(seg.direction, np.float64).reshape(nd, nd)
@@ -244,6 +360,9 @@ def label_statistics(seg: Image, intensities: Optional[dict] = None, device: Opt
         n = int(raw['count'][j])
         e = {'value': int(info['value']), 'exists': n > 0, 'count': n, 'mm': float(raw['mm'][j]), 'bbox': None, 'centroid_index': None,
              'centroid_physical': None, 'intensity': {c: {'min': None, 'max': None, 'mean': None, 'std': None} for c in chans}}
+        if qs:
+            for c in chans:
+                e['intensity'][c]['percentile'] = {percentile_key(q): None for q in qs}
         if n > 0:
             e['bbox'] = [[int(v) for v in raw['bbox_min'][j]], [int(v) for v in raw['bbox_max'][j]]]
             ci = raw['index_sum'][j].astype(np.float64) / np.float64(n)
@@ -252,6 +371,8 @@ def label_statistics(seg: Image, intensities: Optional[dict] = None, device: Opt
             for i, c in enumerate(chans):
                 e['intensity'][c] = {'min': float(raw['min'][j, i]), 'max': float(raw['max'][j, i]), 'mean': float(raw['mean'][j, i]),
                                      'std': float(raw['std'][j, i])}
+                if qs:
+                    e['intensity'][c]['percentile'] = {percentile_key(q): float(pct['percentile'][j, i, p]) for p, q in enumerate(qs)}
         out[name] = e
     return out
 

@@ -317,11 +317,13 @@ class TS2D:
             pr = self.data.get('projections', {})
             return pr.get(channel) if channel is not None else pr
 
-        def statistics(self, model: Optional[str] = None, channels='all') -> Dict[str, dict]:
+        def statistics(self, model: Optional[str] = None, channels='all', percentiles=()) -> Dict[str, dict]:
             """Per-label statistics (``statistics.label_statistics``: count, mm, box, centroid, and min / max / mean / std of the intensity
             under the label) of the merged segmentation (``model=None``) or of sub-model ``model``'s, against the projections of
             :meth:`get_projection` - all of them, or the channel names in ``channels``.  Computed on ``self.device`` (C-ABI
-            ``ts2d_label_statistics``), from the host statement without one: the numbers are the same bit for bit."""
+            ``ts2d_label_statistics``), from the host statement without one: the numbers are the same bit for bit.  ``percentiles`` (0 ... 100,
+            at most 8) adds ``intensity[channel]['percentile'][repr(float(q))]``, the percentile of the channel under the label (50: the
+            median; on the device by ``ts2d_label_percentiles``)."""
             seg = self.get_segmentation(model)
             if seg is None:
                 raise ValueError(f"no segmentation for model {model!r}")
@@ -337,11 +339,14 @@ class TS2D:
                 if a.shape != spatial and int(a.size) == int(np.prod(spatial)) and [s for s in a.shape if s > 1] == [s for s in spatial if s > 1]:
                     a = a.reshape(spatial)          # a collapsed segmentation against a projection that kept its unit axis
                 images[c] = a
-            return label_statistics(seg, images, device=self.device)
+            if not len(percentiles):
+                return label_statistics(seg, images, device=self.device)
+            return label_statistics(seg, images, device=self.device, percentiles=percentiles)
 
-        def save_statistics(self, dest: str, name: str = 'result', models='final', naming: str = 'group') -> List[str]:
+        def save_statistics(self, dest: str, name: str = 'result', models='final', naming: str = 'group', percentiles=()) -> List[str]:
             """``<name>.statistics.json`` for the merged segmentation and ``<name>-<group or model>.statistics.json`` per sub-model, selected
-            by ``models`` as in :meth:`save`: ``json.dump`` of :meth:`statistics` with sorted keys (None of an empty label is ``null``)."""
+            by ``models`` as in :meth:`save`: ``json.dump`` of :meth:`statistics` (with ``percentiles``) with sorted keys (None of an empty
+            label is ``null``)."""
             assert naming in {'group', 'model'}
             mset = {str(t).strip().lower() for t in _as_list(models)}
             keys = []
@@ -352,7 +357,8 @@ class TS2D:
             written = []
             for key in keys:
                 stem = name if key is None else f"{name}-{(decompose_model_key(key)[1] or key) if naming == 'group' else key}"
-                written.append(dump_statistics(self.statistics(key), os.path.join(dest, f"{stem}.statistics.json")))
+                stats = self.statistics(key, percentiles=percentiles) if len(percentiles) else self.statistics(key)
+                written.append(dump_statistics(stats, os.path.join(dest, f"{stem}.statistics.json")))
             return written
 
         def evaluate(self, reference, model: Optional[str] = None, tolerances=(2.0,), percentiles=(), average_distance: bool = False) -> Dict[str, dict]:
