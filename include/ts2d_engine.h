@@ -849,6 +849,48 @@ int ts2d_label_percentiles(int device, const uint8_t* seg, int kind, const uint8
                            int C, const double* percentiles, int P, size_t max_scratch_bytes, int64_t* out_count, float* out_rank_f32,
                            double* out_weight_f64, int* status);
 
+/* The connected components of EVERY label of a segmentation at once on the device: per label how many pieces it has and how large they are, and a
+ * clean-up rule - keep the largest piece, drop every piece below a size - for all labels in the same six or seven launches, whatever K is
+ * (csrc/kernels_components.h; ts2d_keep_largest_components above takes one union of labels per step and six launches per step).  The statement is
+ * totalsegmentator2d_amd/components.py (label_components_statement: scipy.ndimage.label per label); the entry reproduces it byte for byte.
+ * Host pointers in and out, synchronous: ONE upload, every label on the device, ONE download; scratch of the call's own, freed on every path.
+ *   seg, kind, values, K, Z, H, W   as ts2d_label_statistics has them, with its limits; a 2-D case is Z = 1.  The values of a label map are distinct.
+ *   connectivity  TS2D_COMP_FULL: 26 neighbours (8 at Z = 1), what ts2d_keep_largest_components uses; TS2D_COMP_FACES: 6 (4 at Z = 1), scipy's default.
+ *              The components are those of each label's mask ON ITS OWN: two labels that touch in a label map never join, nor do plane k and
+ *              plane k + 1.
+ *   keep_largest, min_voxels  the rule: a component of size s of label k is REMOVED iff (keep_largest != 0 and s < the largest size of label k) or
+ *              s < min_voxels[k].  Components that tie for the largest all stay; s == min_voxels[k] stays; min_voxels NULL: zeros.  Removed voxels
+ *              become 0: the background of a label map, that plane's voxel of planes.
+ *   max_scratch_bytes  bound of the labelling state that works at once: 9 1/8 bytes per voxel (class 1, parent 4, count 4, one bit of run structure) -
+ *              ONCE for a label map, whatever K is, and per label for planes, whose labels are processed in chunks that stay below the bound;
+ *              0: 1 GiB.  The result does not depend on the chunking.  (The segmentation itself and the list lie beside it.)
+ *   out_seg    NULL, or the cleaned segmentation, of the shape of seg.
+ *   out_counters  int64 [K][TS2D_COMP_COUNTERS]: voxels, components, largest size, voxels removed, components removed.  An absent label: zeros.
+ *   out_components, capacity  NULL with capacity 0, or int64 [capacity][3]: per component of the INPUT (label index k, first, size), first the smallest
+ *              linear index of the component inside [Z][H][W]; sorted by (k, size descending, first), so the order in which the lanes arrive does
+ *              not show.  out_n_components receives their number N, whatever the capacity is; the first N rows are written.
+ *   status     0, or a union of
+ *              TS2D_COMP_GIVE_UP    a bounded loop of the labelling reached its hard cap (those of ts2d_keep_largest_components; neither has been
+ *                                   seen).  NO output is written; no retry, the caller takes the host route.
+ *              TS2D_COMP_LIST_FULL  N > capacity.  out_seg, out_counters and out_n_components are valid, out_components is not written; a caller
+ *                                   that wants the list calls again with a capacity of N.  (With capacity 0 that is every call that finds a
+ *                                   component: a caller that wants no list ignores the bit.)
+ *              The call returns TS2D_OK.
+ * TS2D_ERR_INVALID, by name, before any device work: a null seg, out_counters, out_n_components or status, an unknown kind or connectivity, K outside
+ * 1 ... 255, an extent below 1 or more than 2^31 - 1 voxels, a label map without values, with a value 0 or with a repeated value, a negative min_voxels
+ * or capacity, capacity > 0 without out_components, the state of ONE label above max_scratch_bytes.  On any error the outputs are untouched.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+#define TS2D_COMP_FULL 0
+#define TS2D_COMP_FACES 1
+#define TS2D_COMP_GIVE_UP 1
+#define TS2D_COMP_LIST_FULL 2
+#define TS2D_COMP_COUNTERS 5
+int ts2d_label_components(int device, const uint8_t* seg, int kind /* TS2D_STATS_PLANES | TS2D_STATS_LABELMAP */, const uint8_t* values, int K,
+                          int Z, int H, int W, int connectivity, int keep_largest, const int64_t* min_voxels /* [K] or NULL */,
+                          size_t max_scratch_bytes, uint8_t* out_seg /* cleaned, same shape; NULL: not wanted */,
+                          int64_t* out_counters /* [K][5] */, int64_t* out_components /* [capacity][3] or NULL */, int64_t capacity,
+                          int64_t* out_n_components, int* status);
+
 /* Scoring a segmentation against a reference on the device.  The statements are totalsegmentator2d_amd/evaluate.py (project_labels,
  * overlap_statement, surface_statement; numpy); the three entries reproduce them byte for byte and bit for bit.  Host pointers in and out,
  * synchronous; each input is uploaded once, the result downloaded once; scratch of the call's own, freed on every path.

@@ -85,6 +85,7 @@ STATS_INTS, STATS_F64S, STATS_MAX_CHANNELS = 10, 6, 64      # TS2D_STATS_INTS, T
 STATS_MAX_PERCENTILES = 8                                   # TS2D_STATS_MAX_PERCENTILES
 LABELS_RANGE, EVAL_MAX_TOLERANCES, EVAL_MAX_EXTENT = 1, 8, 32767      # TS2D_LABELS_RANGE, TS2D_EVAL_MAX_TOLERANCES, TS2D_EVAL_MAX_EXTENT
 EVAL_MAX_PERCENTILES = 8                                    # TS2D_EVAL_MAX_PERCENTILES
+COMP_FULL, COMP_FACES, COMP_GIVE_UP, COMP_LIST_FULL, COMP_COUNTERS = 0, 1, 1, 2, 5      # TS2D_COMP_*
 
 # shorthands of the table below: int, void *, size_t, long long, unsigned long long, char *; pointers to a void * and to the three descriptors
 _I, _P, _Z, _LL, _ULL, _S = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_char_p
@@ -134,6 +135,7 @@ SIGNATURES = {
     'ts2d_visual_grey': (_I, [_I, _P, _I, _I, _I, _D, _D, _I, _D, _D, _I, _I, _I, _I, _P, _P, ctypes.POINTER(_I)]),
     'ts2d_label_statistics': (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _Z, _P, _P, ctypes.POINTER(_I)]),
     'ts2d_label_percentiles': (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _Z, _P, _P, _P, ctypes.POINTER(_I)]),
+    'ts2d_label_components': (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, ctypes.c_int64, _P, ctypes.POINTER(_I)]),
     'ts2d_project_labels_coronal': (_I, _PROJECT[:-2] + [_I, _P, _P]),
     'ts2d_label_overlap': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     'ts2d_surface_distances': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _D, _D, _P, _I, _Z, _P, _P]),
@@ -170,11 +172,12 @@ SYMBOLS = tuple(SIGNATURES)
 # ... and the three entries of the evaluation: without them evaluate.evaluate and Result.evaluate keep the host route (the statements)
 # ... and the distance profile: without the entry evaluate.evaluate takes percentiles and average distances from its statement
 # ... and the boundary distances of volumes: without the entry evaluate.evaluate(volume_distances=True) keeps its statement
+# ... and the components of every label at once: without the entry components.label_components and clean_components keep the host route (their statement)
 OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n
                      or n.startswith('ts2d_visual_')
                      or n in ('ts2d_engine_create_residual', 'ts2d_keep_largest_components', 'ts2d_project_coronal_modes', 'ts2d_label_statistics', 'ts2d_label_percentiles',
                               'ts2d_project_labels_coronal', 'ts2d_label_overlap', 'ts2d_surface_distances', 'ts2d_surface_distance_profile',
-                              'ts2d_volume_surface_distances'))
+                              'ts2d_volume_surface_distances', 'ts2d_label_components'))
 
 
 class EngineLibraryError(RuntimeError):

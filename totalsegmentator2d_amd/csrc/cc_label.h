@@ -118,4 +118,46 @@ TS2D_CC_HD void cc_link_voxel(int* parent, const cc_word* bits, int H, int W, in
     }
 }
 
+// ---- every label at once (kernels_components.h): the same forest, linked by CLASS EQUALITY in place of mask membership.
+// cls [Z H W] holds 0 outside every label and the voxel's class (1 ... 255) inside; two voxels may join iff their classes are equal and not 0.
+// "Has my class" is an equivalence on a row, so a row falls into maximal runs of equal class exactly as a mask falls into runs of ones, and every
+// rule of cc_link_voxel holds with "is in the mask" read as "has my class".
+
+// does voxel x of the row `row` have the non-zero class c?  Outside 0 ... W - 1: no.
+TS2D_CC_HD bool cc_same(const uint8_t* row, int W, int x, uint8_t c) { return x >= 0 && x < W && row[x] == c; }
+
+// eq: bit l is set iff voxel l of the word has a non-zero class AND voxel l - 1 of the SAME word has the same one (bit 0 is never set).  The voxel at
+// `lane` has a class: the first voxel of its run of equal class inside the word, and how many voxels the run has from `lane` on (itself included).
+TS2D_CC_HD int cc_class_run_start(cc_word eq, int lane) { return (eq >> lane & 1) ? cc_run_start(eq, lane) - 1 : lane; }
+TS2D_CC_HD int cc_class_run_length(cc_word eq, int lane) { return lane < 63 ? 1 + cc_run_length(eq, lane + 1) : 1; }
+
+// The links of voxel (z, y, x), of class cls[.] != 0, to the earlier neighbours of its own class.  The initial parent of a voxel is the start of its run
+// of equal class inside its 64-voxel word (cc_class_run_start), so along x only a run that crosses a word end needs a link.
+//     faces == 0  the 13 earlier neighbours of full connectivity, with the three de-duplication rules of cc_link_voxel
+//     faces != 0  x - 1 (at a word start), (y - 1, x) and (z - 1, y, x) only; of the rules only "straight, and the left neighbour has my class with one
+//                 of my class below it too" applies - the two runs overlap further left and the first voxel of the overlap links
+TS2D_CC_HD void cc_link_voxel_classes(int* parent, const uint8_t* cls, int H, int W, int z, int y, int x, int faces, int find_cap, int union_cap,
+                                      int* gave_up) {
+    const long long row = (long long)z * H + y;
+    const uint8_t* me = cls + row * W;
+    const uint8_t c = me[x];
+    const int i = (int)(row * W + x);
+    const bool left = cc_same(me, W, x - 1, c), right = cc_same(me, W, x + 1, c);
+    if (left && (x & 63) == 0) cc_union(parent, i, i - 1, find_cap, union_cap, gave_up);
+    for (int k = 0; k < 4; ++k) {
+        if (faces && (k & 1)) continue;          // (dz, dy) = (-1, -1) and (-1, +1) are no face neighbours
+        const int zz = z - (k > 0), yy = y + (k == 0 ? -1 : k - 2);
+        if (zz < 0 || yy < 0 || yy >= H) continue;
+        const long long nrow = (long long)zz * H + yy;
+        const uint8_t* nb = cls + nrow * W;
+        const int j = (int)(nrow * W + x);
+        if (cc_same(nb, W, x, c)) {
+            if (!(left && cc_same(nb, W, x - 1, c))) cc_union(parent, i, j, find_cap, union_cap, gave_up);
+        } else if (!faces) {
+            if (!left && cc_same(nb, W, x - 1, c)) cc_union(parent, i, j - 1, find_cap, union_cap, gave_up);
+            if (!right && cc_same(nb, W, x + 1, c)) cc_union(parent, i, j + 1, find_cap, union_cap, gave_up);
+        }
+    }
+}
+
 }  // namespace ts2d

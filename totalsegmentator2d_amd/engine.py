@@ -800,6 +800,52 @@ def label_percentiles(seg: np.ndarray, kind: int, values, shape_zhw, intensities
     return count, rank_value, rank_weight
 
 
+COMPONENTS_FIRST_CAPACITY = 65536      # rows of the list on the first call of label_components; more components than that cost one more call
+
+
+def components_state_bytes(shape_zhw) -> int:
+    """The labelling state of ONE label of ``ts2d_label_components`` (of a whole label map): class, parent, count and the run words."""
+    z, h, w = (int(v) for v in shape_zhw)
+    return 9 * z * h * w + 8 * z * h * ((w + 63) // 64)
+
+
+def label_components(seg: np.ndarray, kind: int, values, shape_zhw, connectivity: int = 0, keep_largest: bool = False, min_voxels=None,
+                     want_seg: bool = True, want_list: bool = True, max_scratch_bytes: int = 0, device: int = 0, capacity: Optional[int] = None):
+    """The components of every label at once on the device (C-ABI ts2d_label_components, csrc/kernels_components.h).  ``seg``, ``kind``,
+    ``values``, ``shape_zhw``: as :func:`label_statistics`; ``connectivity``: ``_lib.COMP_FULL`` or ``_lib.COMP_FACES``; ``min_voxels``: None
+    or K non-negative integers.  Returns ``(cleaned or None, counters int64 [K, 5], components int64 [N, 3] or None)`` -
+    ``components.label_components_statement``'s byte for byte - or None where the entry gave up (TS2D_COMP_GIVE_UP): the caller takes the host
+    route.  The list is asked for with ``capacity`` rows (default :data:`COMPONENTS_FIRST_CAPACITY`); where there are more components the entry
+    is called once more with their exact number, never a third time."""
+    fn = _entry('ts2d_label_components')
+    z, h, w = (int(v) for v in shape_zhw)
+    vals, k = _label_side('label_components', seg, kind, values, z, h, w)
+    mv = None
+    if min_voxels is not None:
+        mv = np.ascontiguousarray([min(int(v), 2 ** 63 - 1) for v in min_voxels], dtype=np.int64)
+        if mv.shape != (k,):
+            raise RuntimeError(f"label_components: min_voxels has {mv.size} entries for {k} labels")
+    counters = np.zeros((k, _lib.COMP_COUNTERS), np.int64)
+    cap = (COMPONENTS_FIRST_CAPACITY if capacity is None else int(capacity)) if want_list else 0
+    for _ in range(2):
+        out = np.empty_like(seg) if want_seg else None
+        rows = np.zeros((cap, 3), np.int64) if want_list else None
+        total = ctypes.c_int64(0)
+        status = ctypes.c_int(0)
+        _lib.check(fn(int(device), seg.ctypes.data, int(kind), vals.ctypes.data if vals is not None else None, k, z, h, w, int(connectivity),
+                      int(bool(keep_largest)), mv.ctypes.data if mv is not None else None, int(max_scratch_bytes),
+                      out.ctypes.data if want_seg else None, counters.ctypes.data, rows.ctypes.data if want_list else None, cap,
+                      ctypes.byref(total), ctypes.byref(status)), 'ts2d_label_components')
+        if status.value & _lib.COMP_GIVE_UP:
+            return None
+        if not want_list:
+            return out, counters, None
+        if not status.value & _lib.COMP_LIST_FULL:
+            return out, counters, rows[:total.value].copy()
+        cap = int(total.value)
+    raise RuntimeError(f"ts2d_label_components: {total.value} components did not fit a list of as many rows")
+
+
 def project_labels_coronal(buffer: np.ndarray, extents, strides, base: int, num: int, device: int = 0):
     """The label projection on the device (C-ABI ts2d_project_labels_coronal, csrc/kernels_evaluate.h).  ``buffer``: the volume's C-contiguous
     integer samples; ``extents`` (nz, ny, nx), ``strides`` (sz, sy, sx) and ``base`` in elements: the reoriented view of

@@ -65,13 +65,19 @@ def _references(reference, cases, src_is_dir: bool) -> dict:
 def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fetch_remote: bool = True, collapse: bool = False,
              visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1, save_probabilities: bool = False,
              statistics: bool = False, reference: str = None, hausdorff_percentiles=(), average_distance: bool = False,
-             statistics_percentiles=()):
+             statistics_percentiles=(), keep_largest: bool = False, min_component_mm: float = 0.0, components: bool = False,
+             component_connectivity: str = 'full'):
     model = DEFAULT_MODEL if model is None else model
     content = 'all' if visualize else 'file'
     which = 'all' if save_all else 'final'
     log = (lambda *a: None) if silent else print
     log("TS2D is a research tool. It is NOT validated for clinical use and should NOT be used for medical diagnosis or treatment.")
     stat_kw = {'percentiles': tuple(statistics_percentiles)} if len(statistics_percentiles) else {}      # without them: the call of before
+
+    def tidy(res):          # the clean-up comes before a result is saved, measured or scored; without its flags the result is the one predicted
+        if keep_largest or min_component_mm > 0:
+            res = res.cleaned(keep_largest=keep_largest, min_size_mm=min_component_mm, connectivity=component_connectivity)
+        return res
     with TS2D(key=model, use_remote=use_remote, fetch_remote=fetch_remote, models=models) as ts:
         cases = list(_enumerate_cases(src))
         references = _references(reference, cases, os.path.isdir(src))
@@ -84,20 +90,25 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
                     log(f"[{g0 + i + 1}/{len(cases)}] Processing: {name}")
                 for (name, _), res in zip(group, ts.predict_many([path for _, path in group], collapse=collapse, max_cases=batch_cases,
                                                                   probabilities=save_probabilities)):
+                    res = tidy(res)
                     res.save(dest=dest, name=name, models=which, content=content, targets=['segmentation', 'projection'])
                     res.save_probabilities(dest, name)
                     if statistics:
                         res.save_statistics(dest, name, models=which, **stat_kw)
+                    if components:
+                        res.save_components(dest, name, models=which, connectivity=component_connectivity)
                     if references:
                         res.save_evaluation(dest, name, references[name], percentiles=hausdorff_percentiles, average_distance=average_distance)
             return
         for i, (name, path) in enumerate(cases):
             log(f"[{i + 1}/{len(cases)}] Processing: {name}")
-            res = ts.predict(path, collapse=collapse, probabilities=save_probabilities)
+            res = tidy(ts.predict(path, collapse=collapse, probabilities=save_probabilities))
             res.save(dest=dest, name=name, models=which, content=content, targets=['segmentation', 'projection'])
             res.save_probabilities(dest, name)
             if statistics:
                 res.save_statistics(dest, name, models=which, **stat_kw)
+            if components:
+                res.save_components(dest, name, models=which, connectivity=component_connectivity)
             if references:
                 res.save_evaluation(dest, name, references[name], percentiles=hausdorff_percentiles, average_distance=average_distance)
 
@@ -130,6 +141,14 @@ def ts2d_entry_point(argv=None):
                    "hausdorff_percentile[Q], the Q-th percentile Hausdorff distance in mm (95: HD95), Q in 0 ... 100; may be given up to 8 times.")
     p.add_argument("--average-distance", action="store_true", help="With --reference: also write per label the average surface distances in mm: "
                    "asd_pred_to_ref, asd_ref_to_pred, assd (both borders pooled) and masd (the mean of the two).")
+    p.add_argument("--keep-largest", action="store_true", help="Clean the result before it is saved, measured or scored: of every label only the "
+                   "connected components of the largest size stay.")
+    p.add_argument("--min-component-mm", type=float, default=0.0, metavar="A", help="Clean the result before it is saved, measured or scored: every "
+                   "connected component of a label below A (an area or volume in the unit of mm of the statistics) is removed; A >= 0.")
+    p.add_argument("--components", action="store_true", help="Also write <case>.components.json: per label how many connected components it has, "
+                   "their sizes and where each starts (with --save-all one <case>-<group>.components.json per sub-model too).")
+    p.add_argument("--component-connectivity", choices=("full", "faces"), default=None, help="With --keep-largest, --min-component-mm or --components: "
+                   "which neighbours connect, full (8 / 26, the default) or faces (4 / 6).")
     a = p.parse_args(argv)
     if a.batch_cases < 1:
         p.error("--batch-cases must be at least 1")
@@ -139,10 +158,18 @@ def ts2d_entry_point(argv=None):
         p.error("--statistics-percentile adds to the statistics: give --statistics")
     if a.statistics_percentile and (len(a.statistics_percentile) > 8 or any(not (math.isfinite(q) and 0.0 <= q <= 100.0) for q in a.statistics_percentile)):
         p.error("--statistics-percentile: at most 8 values, each in 0 ... 100")
+    if not (math.isfinite(a.min_component_mm) and a.min_component_mm >= 0.0):
+        p.error("--min-component-mm must be a number >= 0")
+    clean_kw = {}
+    if a.keep_largest or a.min_component_mm > 0 or a.components:          # without the flags: the call of before
+        clean_kw = {'keep_largest': a.keep_largest, 'min_component_mm': a.min_component_mm, 'components': a.components,
+                    'component_connectivity': a.component_connectivity or 'full'}
+    elif a.component_connectivity is not None:
+        p.error("--component-connectivity chooses how components connect: give --keep-largest, --min-component-mm or --components")
     ts2d_run(src=a.src, dest=a.dest, model=a.model, use_remote=not a.no_remote, fetch_remote=not a.no_fetch, collapse=a.collapse,
              visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases, save_probabilities=a.save_probabilities,
              statistics=a.statistics, reference=a.reference, hausdorff_percentiles=tuple(a.hausdorff_percentile or ()),
-             average_distance=a.average_distance, **({'statistics_percentiles': tuple(a.statistics_percentile)} if a.statistics_percentile else {}))
+             average_distance=a.average_distance, **({'statistics_percentiles': tuple(a.statistics_percentile)} if a.statistics_percentile else {}), **clean_kw)
 
 
 if __name__ == '__main__':

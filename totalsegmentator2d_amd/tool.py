@@ -361,6 +361,52 @@ class TS2D:
                 written.append(dump_statistics(stats, os.path.join(dest, f"{stem}.statistics.json")))
             return written
 
+        def components(self, model: Optional[str] = None, connectivity: str = 'full') -> Dict[str, dict]:
+            """Per label its connected components (``components.label_components``: count, mm, how many pieces, the largest, every size and
+            where each piece starts) of the merged segmentation (``model=None``) or of sub-model ``model``'s.  Computed on ``self.device``
+            (C-ABI ``ts2d_label_components``), from the host statement without one: the numbers are the same."""
+            from .components import label_components
+            seg = self.get_segmentation(model)
+            if seg is None:
+                raise ValueError(f"no segmentation for model {model!r}")
+            return label_components(seg, device=self.device, connectivity=connectivity)
+
+        def cleaned(self, keep_largest: bool = False, min_size_mm: float = 0.0, connectivity: str = 'full', models='all') -> "TS2D.Result":
+            """A NEW result whose segmentations are cleaned (``components.clean_components``: per label, ``keep_largest`` keeps the pieces
+            of the largest size only, ``min_size_mm`` drops every piece below that area or volume): the merged segmentation and that of every
+            sub-model ``models`` selects ('all', or model keys).  Input and projections are shared with this result, which stays untouched;
+            with the defaults the new result holds equal bytes."""
+            from .components import clean_components
+            mset = {str(t).strip().lower() for t in _as_list(models)}
+
+            def clean(seg):
+                return clean_components(seg, device=self.device, connectivity=connectivity, keep_largest=keep_largest, min_size_mm=min_size_mm)[0]
+            data = dict(self.data)
+            if self.get_segmentation() is not None:
+                data['segmentation'] = clean(self.get_segmentation())
+            data['models'] = {m: dict(d) for m, d in self.data.get('models', {}).items()}
+            for m, d in data['models'].items():
+                if ('all' in mset or m.lower() in mset) and d.get('segmentation') is not None:
+                    d['segmentation'] = clean(d['segmentation'])
+            return type(self)(data, self.device)
+
+        def save_components(self, dest: str, name: str = 'result', models='final', naming: str = 'group', connectivity: str = 'full') -> List[str]:
+            """``<name>.components.json`` for the merged segmentation and ``<name>-<group or model>.components.json`` per sub-model, selected
+            by ``models`` and named as in :meth:`save_statistics`: ``json.dump`` of :meth:`components` with sorted keys."""
+            from .components import dump_components
+            assert naming in {'group', 'model'}
+            mset = {str(t).strip().lower() for t in _as_list(models)}
+            keys = []
+            if {'all', 'final'} & mset and self.get_segmentation() is not None:
+                keys.append(None)
+            keys += [m for m in self.models if ('all' in mset or m.lower() in mset) and self.get_segmentation(m) is not None]
+            os.makedirs(dest, exist_ok=True)
+            written = []
+            for key in keys:
+                stem = name if key is None else f"{name}-{(decompose_model_key(key)[1] or key) if naming == 'group' else key}"
+                written.append(dump_components(self.components(key, connectivity), os.path.join(dest, f"{stem}.components.json")))
+            return written
+
         def evaluate(self, reference, model: Optional[str] = None, tolerances=(2.0,), percentiles=(), average_distance: bool = False) -> Dict[str, dict]:
             """Scores of the merged segmentation (``model=None``) or of sub-model ``model``'s against ``reference`` (``evaluate.evaluate``:
             per label the counts, Dice, IoU, precision, recall and, for a 2-D result, surface Dice per tolerance in mm and the Hausdorff distance).
