@@ -527,7 +527,9 @@ int ts2d_engine_tiled_inf_flag(const ts2d_engine* e);
  *   out_max, out_mean  host [nz][nx] float32: projections along y.  The mean is real-valued for every input type: the sum in index
  *              order (exact for integer volumes) divided in double, rounded once to float - ITK's MeanProjectionImageFilter followed by
  *              the reference's Cast to Float32 (ts2d/tool.py:182-185); the reference's pre-projected sample assets pin it
- *              (oracle/input_oracle.py).  Synchronous. */
+ *              (oracle/input_oracle.py).  Synchronous.
+ * TS2D_ERR_INVALID, by name: nz * nx above 2^31 - 1 output pixels (one lane per pixel: a launch past 2^32 lanes is not refused by the runtime
+ * but cut short), and a view that leaves the buffer. */
 int ts2d_project_coronal(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz,
                          long long sy, long long sx, long long base, float* out_max, float* out_mean);
 
@@ -975,7 +977,8 @@ int ts2d_surface_distance_profile(int device, const uint8_t* a, int kind_a, cons
  *              more, and with the sum 16 per box row (z, y); a label that is empty on both sides takes none.  The labels are packed into chunks
  *              that stay below the bound, in their order.  The result does not depend on the chunking.
  * TS2D_ERR_INVALID, by name: what ts2d_surface_distance_profile refuses (before any device work) and, once the boxes are known, scratch of ONE
- * label above max_scratch_bytes.  On any error the outputs are untouched.
+ * label above max_scratch_bytes, or a label whose box has more than 2^26 - 1 = 67 108 863 rows (z, y) - one wave works per box row, and the
+ * runtime cuts a launch of 2^32 lanes or more short instead of refusing it; W < 32 at such a box.  On any error the outputs are untouched.
  * (A new symbol of ABI 9: nothing that existed changed.) */
 int ts2d_volume_surface_distances(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int Z,
                                   int H, int W, double spacing_z, double spacing_h, double spacing_w, const double* tol_sq, int T,

@@ -5,6 +5,7 @@
 //     label_select_driver walk FILE     FILE: cases of (int32 kind, value, n, P; float64 q[P]; uint8 m[n]; float32 x[n]).  Per case one line:
 //                                       count bad, then per percentile the bits of the two rank values and of the weight.
 //     label_select_driver plan FILE     FILE: text lines "K C P rows max_scratch_bytes".  Per line: rc need budget, then the chunks k0:k1.
+//     label_select_driver chunk FILE    FILE: text lines "K C rows max_scratch_bytes" (C >= 0).  Per line: rc labels need budget of st_plan.
 #include "../totalsegmentator2d_amd/csrc/label_select.h"
 #include "../totalsegmentator2d_amd/csrc/stats_plan.h"
 
@@ -57,9 +58,25 @@ static int plan(const char* path) {
     return 0;
 }
 
+static int chunk(const char* path) {
+    FILE* f = std::fopen(path, "r");
+    if (!f) return 2;
+    int K, C;
+    long long rows;
+    unsigned long long bound;
+    while (std::fscanf(f, "%d %d %lld %llu", &K, &C, &rows, &bound) == 4) {
+        size_t labels = 0, need = 0, budget = 0;
+        const int rc = ts2d::st_plan(K, C, rows, (size_t)bound, &labels, &need, &budget);
+        std::printf("%d %zu %zu %zu\n", rc, labels, need, budget);
+    }
+    std::fclose(f);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc != 3) return 1;
     if (!std::strcmp(argv[1], "walk")) return walk(argv[2]);
     if (!std::strcmp(argv[1], "plan")) return plan(argv[2]);
+    if (!std::strcmp(argv[1], "chunk")) return chunk(argv[2]);
     return 1;
 }

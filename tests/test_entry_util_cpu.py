@@ -1,5 +1,5 @@
 """csrc/entry_util.h - the call scaffolding the engine-free entries share - as plain C++ behind a main of its own: the arena layout, the
-strided-view check against its definition, the sample types and the chunk of labels.  Enumerated cases; the expected verdicts are computed here."""
+strided-view check against its definition, the sample types, the chunk of labels and the folded grid.  Enumerated cases; the expected verdicts are computed here."""
 import itertools
 import os
 import shutil
@@ -66,6 +66,12 @@ int main(int argc, char** argv) {
             int z, h, w;
             if (std::fscanf(f, "%d %d %d", &z, &h, &w) != 3) return 3;
             std::printf("%d\n", ts2d::volume_fits_int32(z, h, w) ? 1 : 0);
+        } else if (!std::strcmp(what, "fold")) {                             // blocks, threads -> x and fold of the folded grid
+            long long blocks;
+            int threads;
+            if (std::fscanf(f, "%lld %d", &blocks, &threads) != 2) return 3;
+            const ts2d::FoldedGrid g = ts2d::fold_grid(blocks, threads);
+            std::printf("%u %u\n", g.x, g.fold);
         } else {
             return 4;
         }
@@ -168,3 +174,18 @@ def test_the_sample_types_the_chunk_and_the_extent(util_program, tmp_path):
         assert line == f'{min(budget // per, K)} {budget}', (cap, per, K)
     for (z, h, w), line in zip(volumes, out[5 + len(chunks):]):
         assert line == str(int(min(z, h, w) >= 1 and z * h <= 2 ** 31 - 1 and z * h * w <= 2 ** 31 - 1)), (z, h, w)
+
+
+def test_a_folded_grid_covers_every_block_and_no_axis_passes_2_32_work_items(util_program, tmp_path):
+    """Up to 2^32 - 1 work-items along x the grid is the plain one (fold 1: the launch of before); beyond, x * threads stays below 2^32, x * fold
+    covers the blocks with less than one fold to spare, and the fold stays far below the 65535 of a grid's other axes."""
+    cases = [(b, t) for t in (64, 256) for b in (1, 2, 1000, 2 ** 32 // t - 1, (2 ** 32 - 1) // t, 2 ** 32 // t, 2 ** 32 // t + 1, 67117056 // (t // 64),
+                                                 2 ** 29, 2 ** 31 - 1)]
+    out = _run(util_program, tmp_path, ['fold %d %d' % c for c in cases])
+    folded = 0
+    for (blocks, threads), line in zip(cases, out):
+        x, fold = (int(v) for v in line.split())
+        assert x * threads <= 2 ** 32 - 1 and x * fold >= blocks and x * (fold - 1) < blocks and 1 <= fold <= 129, (blocks, threads, x, fold)
+        assert (fold == 1) == (blocks * threads <= 2 ** 32 - 1) and (fold > 1 or x == blocks), (blocks, threads, x, fold)
+        folded += fold > 1
+    assert folded >= 8

@@ -70,6 +70,20 @@ inline bool volume_fits_int32(int Z, int H, int W) {
     return Z >= 1 && H >= 1 && W >= 1 && (long long)Z * H <= 0x7FFFFFFFll && (long long)Z * H * W <= 0x7FFFFFFFll;
 }
 
+// One axis of a dispatch counts its work-items in 32 bits, and the runtime does not refuse a launch beyond them: the count wraps and only a part of
+// the grid runs.  `blocks` workgroups of `threads` lanes along x are therefore FOLDED: x workgroups along x (x * threads < 2^32), `fold` times along
+// an axis the kernel does not use otherwise; the workgroup's number is fold index * gridDim.x + blockIdx.x, and a kernel leaves where that number
+// reaches `blocks` (x * fold >= blocks).  fold == 1 and x == blocks wherever blocks * threads < 2^32: the launch of before.
+struct FoldedGrid {
+    unsigned x, fold;
+};
+inline FoldedGrid fold_grid(long long blocks, int threads) {
+    const long long cap = 0xFFFFFFFFll / threads;
+    if (blocks <= cap) return {(unsigned)blocks, 1u};
+    const long long fold = (blocks + cap - 1) / cap;
+    return {(unsigned)((blocks + fold - 1) / fold), (unsigned)fold};
+}
+
 // The labels of one chunk: as many as have their scratch of per_label bytes under max_scratch_bytes (0: 256 MiB; *budget: what was used), at
 // most K.  0: ONE label does not fit - the entry refuses in its own words.
 inline size_t labels_per_chunk(size_t max_scratch_bytes, size_t per_label, int K, size_t* budget) {

@@ -237,6 +237,15 @@ int volume_distances_impl(const char* E, int device, const uint8_t* a, int kind_
         return fail(TS2D_ERR_INVALID, "%s: the scratch of ONE label (label %d, its box %d x %d x %d) takes %zu bytes, above max_scratch_bytes = %zu", E,
                     over, box[(size_t)over * 6 + 3] - box[(size_t)over * 6] + 1, box[(size_t)over * 6 + 4] - box[(size_t)over * 6 + 1] + 1,
                     box[(size_t)over * 6 + 5] - box[(size_t)over * 6 + 2] + 1, need, budget);
+    // sdv_planes and sdv_rows run one wave per (group of) box row(s): a box of more than 2^26 - 1 rows (W < 32 at the largest extents) would be a
+    // launch of more than 2^32 - 1 threads, which the runtime does not refuse but cuts short
+    for (int k = 0; k < K; ++k) {
+        const SdvLabel& l = labels[(size_t)k];
+        const long long pl = (long long)((l.bx + 63) / 64) * ((l.by + kSdvRows - 1) / kSdvRows) * l.bz, rw = (long long)l.bz * l.by;
+        if ((pl > rw ? pl : rw) * 64 > 0xFFFFFFFFll)
+            return fail(TS2D_ERR_INVALID, "%s: label %d: its box %d x %d x %d has %lld rows, above the 67108863 rows one launch takes", E, k, l.bz, l.by,
+                        l.bx, rw);
+    }
     long long max_vox = 0, max_rows = 0;
     for (const SdvChunk& c : chunks) {
         max_vox = c.vox > max_vox ? c.vox : max_vox;

@@ -17,7 +17,8 @@
 //     lc_apply     a component of size s of label k goes iff (keep_largest and s < largest_k) or s < min_voxels[k]: its voxels become 0 in the
 //                  segmentation; voxels removed (one add per run) and components removed (by the root lanes) are counted per label
 //     lc_list      every root appends (label, root, count) through ONE integer cursor, and writes only while its slot is below the capacity
-// Every kernel runs one WAVE per 64-voxel word with CcLane's addressing (kernels_post_cc.h): grid = (ceil(Z H ceil(W / 64) / 4), sets), 256 lanes.
+// Every kernel runs one WAVE per 64-voxel word with CcLane's addressing (kernels_post_cc.h): grid = (ceil(Z H ceil(W / 64) / 4), sets), 256 lanes,
+// folded along z where it passes 2^32 threads.
 //
 // Termination and order: the arguments of kernels_post_cc.h hold unchanged.  The only loops are cc_find and cc_union, bounded by monotonicity AND a hard
 // cap; a lane at a cap ORs kLcStatusGiveUp into the status, lc_apply and lc_list write nothing once it is set, and the entry leaves the caller's

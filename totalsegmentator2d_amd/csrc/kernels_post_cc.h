@@ -10,7 +10,8 @@
 //     cc_count       count[root] += the voxels of every run of a word, one integer atomicAdd per run (the lanes of a run share their root)
 //     cc_max         the largest count: an integer atomicMax per wave over its roots
 //     cc_apply       seg[i] <- background where i is in the mask and count[parent[i]] is below the maximum; the voxels removed
-// Every kernel runs one WAVE per 64-bit word, lane k on voxel 64 w + k of the row (lanes past W idle): grid = ceil(Z H ceil(W / 64) / 4), 256 lanes.
+// Every kernel runs one WAVE per 64-bit word, lane k on voxel 64 w + k of the row (lanes past W idle): grid = ceil(Z H ceil(W / 64) / 4), 256 lanes;
+// from 2^26 - 3 words on (W < 32 at the largest volumes) that grid passes 2^32 threads and folds along z (entry_util.h: fold_grid).
 // All indices are int32: the entry refuses more than 2^31 - 1 voxels.  parent holds -1 or an index below Z H W, count is indexed by a parent that is
 // >= 0 only, the tables have 256 entries and are indexed by a byte: no access can leave its array whatever the arrival order.
 //
@@ -43,7 +44,7 @@ struct CcLane {
 };
 __device__ __forceinline__ bool cc_lane(long long words, int ww, CcLane* l) {
     l->lane = threadIdx.x & 63;
-    l->word = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    l->word = ((long long)blockIdx.z * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6);      // (a folded grid: entry_util.h, fold_grid)
     if (l->word >= words) return false;                          // (the whole wave leaves together)
     l->row = l->word / ww;
     l->x = (int)(l->word - l->row * ww) * 64 + l->lane;

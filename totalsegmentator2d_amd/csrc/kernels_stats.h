@@ -62,13 +62,16 @@ __device__ __forceinline__ uint32_t st_wave_umax(uint32_t v) {
     return v;
 }
 
-// grid = (R, L), block = 64.  seg: planes [K][n] or one label map [n] with values [K]; label k0 + blockIdx.y; x: [C][n] float32;
+// grid = (R, L), block = 64; where R * 64 passes 2^32 the rows fold along z (entry_util.h: fold_grid), row = blockIdx.z * gridDim.x + blockIdx.x.
+// seg: planes [K][n] or one label map [n] with values [K]; label k0 + blockIdx.y; x: [C][n] float32;
 // result: the labels' out_f64 (PASS 2 reads the mean there).
 template <int PASS>
 __global__ __launch_bounds__(64) void stats_rows(const uint8_t* __restrict__ seg, int kind, const uint8_t* __restrict__ values, int k0, int R, int W,
                                                  long long n, const float* __restrict__ x, int C, StScratch s, const double* __restrict__ result,
                                                  int* __restrict__ status) {
-    const int r = (int)blockIdx.x, l = (int)blockIdx.y, k = k0 + l, lane = (int)threadIdx.x;
+    const long long row = (long long)blockIdx.z * gridDim.x + blockIdx.x;
+    if (row >= R) return;                                          // (the whole wave: the last fold of a folded grid)
+    const int r = (int)row, l = (int)blockIdx.y, k = k0 + l, lane = (int)threadIdx.x;
     const uint8_t* m = seg + (kind == kStPlanes ? (long long)k * n : 0ll) + (long long)r * W;
     const uint8_t value = kind == kStLabelMap ? values[k] : (uint8_t)0;
     const int slot = l * R + r;

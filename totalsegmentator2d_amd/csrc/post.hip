@@ -42,7 +42,8 @@ int ts2d_keep_largest_components(int device, uint8_t* seg, int Z, int H, int W, 
     HIP_TRY(hipMemset(d_status, 0, ctr_ints * sizeof(int)));
     HIP_TRY(hipMemcpy(d.as<char>(o_steps), steps, (size_t)n_steps * sizeof(ts2d_cc_step), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_seg, seg, n, hipMemcpyHostToDevice));
-    const dim3 grid((unsigned)((words + 3) / 4)), block(256);
+    const FoldedGrid fg = fold_grid((words + 3) / 4, 256);
+    const dim3 grid(fg.x, 1, fg.fold), block(256);
     for (int s = 0; s < n_steps; ++s) {          // each launch sees the one before it: the default stream orders them
         const uint8_t* member = d.as<const uint8_t>(o_steps + (size_t)s * sizeof(ts2d_cc_step));
         int* ctr = d_status + 1 + (size_t)s * kCcCounters;
@@ -126,9 +127,10 @@ int ts2d_label_components(int device, const uint8_t* seg, int kind, const uint8_
     HIP_TRY(hipMemcpy(d_seg, seg, seg_bytes, hipMemcpyHostToDevice));
     LcState s = {d.as<uint8_t>(o_cls), d.as<cc_word>(o_eq), d.as<int>(o_parent), d.as<int>(o_count), (long long)n, words, W, kind, 0};
     const dim3 block(256);
+    const FoldedGrid fg = fold_grid((words + 3) / 4, 256);
     for (int k0 = 0; k0 < (int)n_sets; k0 += sets) {               // each launch sees the one before it: the default stream orders them
         const unsigned now = (unsigned)((int)n_sets - k0 < sets ? (int)n_sets - k0 : sets);
-        const dim3 grid((unsigned)((words + 3) / 4), now);
+        const dim3 grid(fg.x, now, fg.fold);
         s.k0 = k0;
         hipLaunchKernelGGL(lc_init, grid, block, 0, 0, d_seg, d.as<const uint8_t>(o_table), s, d_ctr);
         hipLaunchKernelGGL(lc_link, grid, block, 0, 0, s, H, connectivity, d_status);

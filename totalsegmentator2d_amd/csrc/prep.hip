@@ -42,6 +42,8 @@ int project_coronal_impl(int device, const void* volume, size_t n_elems, int dty
                          long long sy, long long sx, long long base, float* out_max, float* out_mean, float* out_norm, double* out_stats, int* out_box) {
     if (!volume || !out_max || !out_mean) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal: null argument");
     if (dtype < 0 || dtype > 4 || nz < 1 || ny < 1 || nx < 1) return fail(TS2D_ERR_INVALID, "ts2d_project_coronal: bad dtype / extents");
+    if ((long long)nz * nx > 0x7FFFFFFFll)          // one lane per output pixel: a launch past 2^32 lanes is cut short, not refused, by the runtime
+        return fail(TS2D_ERR_INVALID, "ts2d_project_coronal: planes of nz %d x nx %d are more than 2^31 - 1 pixels", nz, nx);
     TRY(check_strided_view("ts2d_project_coronal", n_elems, base, {nz, ny, nx}, {sz, sy, sx}, false));
     HIP_TRY(hipSetDevice(device));
     const size_t vbytes = n_elems * sample_size(dtype), obytes = (size_t)nz * nx * sizeof(float);

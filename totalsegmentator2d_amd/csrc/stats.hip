@@ -30,16 +30,13 @@ int ts2d_label_statistics(int device, const uint8_t* seg, int kind, const uint8_
     if (C > 0 && (!intensities || !out_f64)) return fail(TS2D_ERR_INVALID, "%s: C = %d channels without intensities or out_f64", entry, C);
     if (kind == kStLabelMap) TRY(check_label_values(entry, values, K));
     const size_t n = (size_t)Z * H * W, R = (size_t)Z * H;
-    // a label's row partials: count, min x, max x (int32), sum x (int64), and per channel one float64 and two keys
-    const size_t per_label = R * (20 + 16 * (size_t)C);
-    size_t budget = 0;
-    size_t L = labels_per_chunk(max_scratch_bytes, per_label, K, &budget);
-    if (L < 1)
+    // a label's row partials and the labels of a chunk: stats_plan.cpp
+    size_t L = 0, per_label = 0, budget = 0;
+    const int planned = st_plan(K, C, (long long)R, max_scratch_bytes, &L, &per_label, &budget);
+    if (planned == -1)
         return fail(TS2D_ERR_INVALID, "%s: the row partials of ONE label (%zu rows, %d channels) take %zu bytes, above max_scratch_bytes = %zu", entry,
                     R, C, per_label, budget);
-    const size_t slot_cap = (size_t)0x7FFFFFFF / (R * (size_t)(C > 0 ? C : 1));       // int32 slots: L * C * R stays below 2^31
-    if (slot_cap < 1) return fail(TS2D_ERR_INVALID, "%s: %zu rows x %d channels are more partial slots than an int32 index reaches", entry, R, C);
-    if (L > slot_cap) L = slot_cap;
+    if (planned != 0) return fail(TS2D_ERR_INVALID, "%s: %zu rows x %d channels are more partial slots than an int32 index reaches", entry, R, C);
 
     HIP_TRY(hipSetDevice(device));
     const size_t seg_bytes = kind == kStPlanes ? (size_t)K * n : n;
@@ -66,7 +63,8 @@ int ts2d_label_statistics(int device, const uint8_t* seg, int kind, const uint8_
                          d.as<double>(o_fsum), d.as<uint32_t>(o_kmin), d.as<uint32_t>(o_kmax)};
     for (int k0 = 0; k0 < K; k0 += (int)L) {
         const unsigned labels = (unsigned)(K - k0 < (int)L ? K - k0 : (int)L);
-        const dim3 rows((unsigned)R, labels), block(kStLanes);
+        const FoldedGrid fg = fold_grid((long long)R, kStLanes);      // (R * 64 threads pass 2^32 from R = 2^26 on)
+        const dim3 rows(fg.x, labels, fg.fold), block(kStLanes);
         hipLaunchKernelGGL(stats_rows<1>, rows, block, 0, 0, d_seg, kind, d_values, k0, (int)R, W, (long long)n, d_x, C, s, d_f64, d_status);
         hipLaunchKernelGGL(stats_combine<1>, dim3(labels), block, 0, 0, k0, (int)R, H, Z, W, C, s, d_int, d_f64);
         if (C > 0) {
@@ -149,8 +147,9 @@ int ts2d_label_percentiles(int device, const uint8_t* seg, int kind, const uint8
     for (const LsChunk& ch : chunks) {
         const unsigned labels = (unsigned)(ch.k1 - ch.k0);
         const dim3 block(kStLanes);
+        const FoldedGrid fg = fold_grid((long long)rows, kStLanes);
         // counts and boxes: the counting pass of ts2d_label_statistics without a channel
-        hipLaunchKernelGGL(stats_rows<1>, dim3((unsigned)rows, labels), block, 0, 0, d_seg, kind, d_values, ch.k0, (int)rows, W, (long long)n,
+        hipLaunchKernelGGL(stats_rows<1>, dim3(fg.x, labels, fg.fold), block, 0, 0, d_seg, kind, d_values, ch.k0, (int)rows, W, (long long)n,
                            (const float*)nullptr, 0, s, (const double*)nullptr, d_status);
         hipLaunchKernelGGL(stats_combine<1>, dim3(labels), block, 0, 0, ch.k0, (int)rows, H, Z, W, 0, s, d_int, (double*)nullptr);
         hipLaunchKernelGGL(ls_select_init, dim3(labels), block, 0, 0, d_int, ch.k0, C, pc, P, d_sel, d_pre, d.as<double>(o_wgt));

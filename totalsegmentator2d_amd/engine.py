@@ -809,6 +809,27 @@ def components_state_bytes(shape_zhw) -> int:
     return 9 * z * h * w + 8 * z * h * ((w + 63) // 64)
 
 
+def statistics_chunk_labels(shape_zhw, n_labels: int, n_channels: int, max_scratch_bytes: int = 0):
+    """``(labels per chunk, what set it)`` of ``ts2d_label_statistics`` (csrc/stats_plan.cpp: ``st_plan``, spelled again): ``'budget'`` - the row
+    partials of a chunk, ``rows * (20 + 16 C)`` bytes a label, stay at or below ``max_scratch_bytes`` (0: 256 MiB); ``'slot_cap'`` - a channel
+    partial's slot is an int32, so a chunk has at most ``(2^31 - 1) // (rows * max(C, 1))`` labels; ``'labels'`` - all K fit.  0 labels: the entry
+    refuses."""
+    z, h, _ = (int(v) for v in shape_zhw)
+    rows, c = z * h, int(n_channels)
+    by_budget = (int(max_scratch_bytes) or 256 << 20) // (rows * (20 + 16 * c))
+    by_slots = (2 ** 31 - 1) // (rows * max(c, 1))
+    return min((by_budget, 'budget'), (by_slots, 'slot_cap'), (int(n_labels), 'labels'), key=lambda t: t[0])
+
+
+def percentiles_chunk_labels(shape_zhw, n_labels: int, n_channels: int, n_percentiles: int, max_scratch_bytes: int = 0):
+    """:func:`statistics_chunk_labels` for ``ts2d_label_percentiles`` (``ls_plan``): a label's state is ``C * 2 P * 1040 + rows * 20`` bytes and
+    the slot of a row partial, ``label * rows + row``, is an int32."""
+    z, h, _ = (int(v) for v in shape_zhw)
+    rows = z * h
+    by_budget = (int(max_scratch_bytes) or 256 << 20) // (int(n_channels) * 2 * int(n_percentiles) * 1040 + rows * 20)
+    return min((by_budget, 'budget'), ((2 ** 31 - 1) // rows, 'slot_cap'), (int(n_labels), 'labels'), key=lambda t: t[0])
+
+
 def label_components(seg: np.ndarray, kind: int, values, shape_zhw, connectivity: int = 0, keep_largest: bool = False, min_voxels=None,
                      want_seg: bool = True, want_list: bool = True, max_scratch_bytes: int = 0, device: int = 0, capacity: Optional[int] = None):
     """The components of every label at once on the device (C-ABI ts2d_label_components, csrc/kernels_components.h).  ``seg``, ``kind``,
