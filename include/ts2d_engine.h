@@ -985,6 +985,24 @@ int ts2d_volume_surface_distances(int device, const uint8_t* a, int kind_a, cons
                                   const double* percentiles, int P, int want_sum, size_t max_scratch_bytes, int64_t* out_i64, double* out_f64,
                                   double* out_sum_f64, double* out_rank_f64, double* out_weight_f64);
 
+/* ts2d_label_confusion: the confusion (co-occurrence) matrix of two segmentations - for every pair of labels (i of a, j of b) the samples that
+ * are in both - in ONE integer matrix product on the device (csrc/kernels_confusion.h: v_mfma_i32_32x32x32_i8 over 0 / 1 bytes, exact in int32).
+ * The statement is evaluate.confusion_statement; the entry reproduces it integer for integer.  a, kind_a, b, kind_b, values, K, Z, H, W as in
+ * ts2d_label_overlap, with its contract: host pointers, synchronous, each input uploaded once (a == b, the same pointer with the same kind, is
+ * allowed and uploaded once), one download, scratch of the call's own (one byte per sample and side), freed on every path.
+ *   out_i64    [K + 2][K + 2], row = side a, column = side b.  Either side has K + 2 indicator rows over the N = Z * H * W samples: row 0 "none
+ *              of the K labels" (planes: every plane is 0 there; label map: the byte is not among values), row 1 + k the mask of label k, row
+ *              K + 1 every sample.  out[i][j] counts the samples in row i of a and in row j of b, so out[1 + k][1 + k], out[1 + k][K + 1] and
+ *              out[K + 1][1 + k] are n_both, n_a and n_b of ts2d_label_overlap, and out[K + 1][K + 1] = N.  With a planes side a sample may be in
+ *              several rows.
+ * Limits: K 1 ... 255; every extent at least 1; N at most 2^31 - 1 samples (an int32 accumulator of the product counts samples, so none can
+ * overflow); a planes side is K * N bytes, up to 2^39, and every byte offset is 64-bit.
+ * TS2D_ERR_INVALID, by name, before any device work: a null pointer, an unknown kind, K outside 1 ... 255, an extent below 1, more than
+ * 2^31 - 1 samples, a label map without values or with a value 0.  On any error the output is untouched.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+int ts2d_label_confusion(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int Z, int H, int W,
+                         int64_t* out_i64 /* [K + 2][K + 2], row = side a */);
+
 /* Synthetic slice stream on the device (BASELINE config 4: "synthetic 10k-slice stream", generated per rank from (seed, slice
  * index) so that no host transfer skews the timing).  Writes n_elements fp32 values, approximately N(0,1), to device memory:
  * element i of the call = element (first_element + i) of the stream identified by `key`; a value depends on (key, element index)

@@ -141,6 +141,7 @@ SIGNATURES = {
     'ts2d_surface_distances': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _D, _D, _P, _I, _Z, _P, _P]),
     'ts2d_surface_distance_profile': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _D, _D, _P, _I, _P, _I, _I, _Z, _P, _P, _P, _P, _P]),
     'ts2d_volume_surface_distances': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _D, _D, _D, _P, _I, _P, _I, _I, _Z, _P, _P, _P, _P, _P]),
+    'ts2d_label_confusion': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     'ts2d_synth_slices': (_I, [_I, _ULL, _ULL, _ULL, _P, _P]),
     'ts2d_engine_reserve': (_I, [_P, _I, _I, _I]),
     'ts2d_engine_workspace_bytes': (_I, [_P, _I, _I, _I, ctypes.POINTER(_Z)]),
@@ -173,11 +174,12 @@ SYMBOLS = tuple(SIGNATURES)
 # ... and the distance profile: without the entry evaluate.evaluate takes percentiles and average distances from its statement
 # ... and the boundary distances of volumes: without the entry evaluate.evaluate(volume_distances=True) keeps its statement
 # ... and the components of every label at once: without the entry components.label_components and clean_components keep the host route (their statement)
+# ... and the confusion matrix: without the entry evaluate.confusion keeps the host route (its statement)
 OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n
                      or n.startswith('ts2d_visual_')
                      or n in ('ts2d_engine_create_residual', 'ts2d_keep_largest_components', 'ts2d_project_coronal_modes', 'ts2d_label_statistics', 'ts2d_label_percentiles',
                               'ts2d_project_labels_coronal', 'ts2d_label_overlap', 'ts2d_surface_distances', 'ts2d_surface_distance_profile',
-                              'ts2d_volume_surface_distances', 'ts2d_label_components'))
+                              'ts2d_volume_surface_distances', 'ts2d_label_components', 'ts2d_label_confusion'))
 
 
 class EngineLibraryError(RuntimeError):

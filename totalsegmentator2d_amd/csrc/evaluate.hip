@@ -3,11 +3,13 @@
 // are ONE implementation, surface_distances_impl: the first is the second without percentiles and without the sum.
 // ts2d_volume_surface_distances is their counterpart for volumes (kernels_evaluate_volume.h; the plan of its scratch: evaluate_plan.h): the same
 // checks (check_distance_request), the same counters, selections and download (DistanceResults).  The arithmetic of the
-// distances: surface_dist.h; the statements: totalsegmentator2d_amd/evaluate.py.
+// distances: surface_dist.h; the statements: totalsegmentator2d_amd/evaluate.py.  ts2d_label_confusion stands beside ts2d_label_overlap: the
+// matrix of all label pairs as one integer matrix product (kernels_confusion.h; what a row is as operand bytes: confusion.h).
 // Host pointers in and out; a call uploads each input once, works on the device and downloads once; every device buffer of a call is one DevMem
 // laid out by an ArenaLayout (entry_util.h), so HIP_TRY may return wherever it fails.
 #include "engine_internal.h"
 #include "entry_util.h"
+#include "kernels_confusion.h"
 #include "kernels_evaluate.h"
 #include "kernels_evaluate_profile.h"
 #include "kernels_evaluate_volume.h"
@@ -22,6 +24,8 @@ static_assert(kStPlanes == TS2D_STATS_PLANES && kStLabelMap == TS2D_STATS_LABELM
 static_assert(kPlStatusRange == TS2D_LABELS_RANGE && kSdMaxTolerances == TS2D_EVAL_MAX_TOLERANCES && kSdMaxExtent == TS2D_EVAL_MAX_EXTENT,
               "the status bit and the limits speak the C header's numbers");
 static_assert(kSdMaxPercentiles == TS2D_EVAL_MAX_PERCENTILES, "the limits speak the C header's numbers");
+static_assert(kCfPlanes == TS2D_STATS_PLANES && kCfLabelMap == TS2D_STATS_LABELMAP, "confusion.h speaks the C header's kinds");
+static_assert(kCfChunkMin % 128 == 0 && kCfChunkMin % kCfStep == 0 && kCfStep == 2 * kCfLoad, "a chunk is whole lines and whole steps");
 
 #pragma GCC visibility push(hidden)
 namespace {
@@ -361,6 +365,54 @@ int ts2d_label_overlap(int device, const uint8_t* a, int kind_a, const uint8_t* 
                        d.as<const uint8_t>(o_b), kind_b, d.as<const uint8_t>(o_val), (long long)n, vec, d.as<unsigned long long>(o_cnt));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out_i64, d.as<char>(o_cnt), (size_t)K * 3 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return TS2D_OK;
+}
+
+int ts2d_label_confusion(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int Z, int H, int W,
+                         int64_t* out_i64) {
+    const char* const E = "ts2d_label_confusion";
+    if (!out_i64) return fail(TS2D_ERR_INVALID, "%s: out_i64 is null", E);
+    if (!volume_fits_int32(Z, H, W)) return fail(TS2D_ERR_INVALID, "%s: %d x %d x %d is empty or more than 2^31 - 1 samples", E, Z, H, W);
+    const size_t n = (size_t)Z * H * W;
+    size_t bytes_a = 0, bytes_b = 0;
+    TRY(check_sides(E, a, kind_a, b, kind_b, values, K, n, &bytes_a, &bytes_b));
+    const bool same = a == b && kind_a == kind_b;                  // ONE array on both sides: one upload, one none plane
+    const bool any_map = kind_a == kStLabelMap || kind_b == kStLabelMap;
+    uint32_t set[8] = {};
+    if (any_map) cf_set_build(values, K, set);
+    HIP_TRY(hipSetDevice(device));
+    // [the matrix | values | the set of the values || a | b | none of a | none of b]
+    const size_t rows = (size_t)K + 2, cnt_bytes = rows * rows * sizeof(unsigned long long);
+    ArenaLayout lay;
+    const size_t o_cnt = lay.add(cnt_bytes), o_val = lay.add((size_t)K), o_set = lay.add(sizeof(set));
+    const size_t o_a = lay.add(bytes_a), o_b = same ? o_a : lay.add(bytes_b), o_na = lay.add(n), o_nb = same ? o_na : lay.add(n);
+    DevMem d;
+    HIP_TRY(d.alloc(lay.total()));
+    HIP_TRY(hipMemset(d.as<char>(), 0, o_set));                    // the matrix and the values
+    if (values) HIP_TRY(hipMemcpy(d.as<char>(o_val), values, (size_t)K, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_set), set, sizeof(set), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.as<char>(o_a), a, bytes_a, hipMemcpyHostToDevice));
+    if (!same) HIP_TRY(hipMemcpy(d.as<char>(o_b), b, bytes_b, hipMemcpyHostToDevice));
+    const int aligned = n % kCfLoad == 0 ? 1 : 0;                  // every region starts on a 256-byte boundary: plane k on one of 16 iff n is a multiple
+    // Neither launch comes near the 2^32 lanes of one axis, where a grid would have to be folded (entry_util.h, fold_grid): n <= 2^31 - 1, a lane
+    // of cf_none takes 16 samples (at most 2^27 lanes along x) and a wave of cf_product at least kCfChunkMin = 1024 (at most 2^21 waves, 2^27 lanes;
+    // along y the at most 81 tile pairs).
+    const unsigned none_blocks = (unsigned)(((n + kCfLoad - 1) / kCfLoad + kCfNoneThreads - 1) / kCfNoneThreads);
+    hipLaunchKernelGGL(cf_none, dim3(none_blocks), dim3(kCfNoneThreads), 0, 0, d.as<const uint8_t>(o_a), kind_a, K, (long long)n, aligned,
+                       d.as<const uint32_t>(o_set), d.as<uint8_t>(o_na));
+    if (!same)
+        hipLaunchKernelGGL(cf_none, dim3(none_blocks), dim3(kCfNoneThreads), 0, 0, d.as<const uint8_t>(o_b), kind_b, K, (long long)n, aligned,
+                           d.as<const uint32_t>(o_set), d.as<uint8_t>(o_nb));
+    HIP_TRY(hipGetLastError());
+    const int tiles = (int)((rows + kCfTile - 1) / kCfTile), pairs = tiles * tiles;
+    const long long per_pair = kCfWavesAim / pairs > 0 ? kCfWavesAim / pairs : 1;
+    long long chunk = ((long long)n + per_pair - 1) / per_pair;
+    chunk = chunk < kCfChunkMin ? kCfChunkMin : (chunk + 127) / 128 * 128;
+    hipLaunchKernelGGL(cf_product, dim3((unsigned)(((long long)n + chunk - 1) / chunk), (unsigned)pairs), dim3(64), 0, 0, d.as<const uint8_t>(o_a), kind_a, d.as<const uint8_t>(o_na),
+                       d.as<const uint8_t>(o_b), kind_b, d.as<const uint8_t>(o_nb), d.as<const uint8_t>(o_val), K, (long long)n, chunk, tiles, aligned,
+                       aligned, d.as<unsigned long long>(o_cnt));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out_i64, d.as<char>(o_cnt), cnt_bytes, hipMemcpyDeviceToHost));
     return TS2D_OK;
 }
 

@@ -911,6 +911,19 @@ def label_overlap(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values
     return out
 
 
+def label_confusion(a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, shape_zhw, device: int = 0) -> np.ndarray:
+    """The confusion matrix on the device (C-ABI ts2d_label_confusion, csrc/kernels_confusion.h).  ``a``, ``b``, ``values`` as in
+    :func:`label_overlap`; ``a`` and ``b`` may be the same array.  Returns int64 [K + 2, K + 2], row = side a, column = side b: row 0 "none of
+    the labels", row 1 + k label k, row K + 1 every sample (``evaluate.confusion_statement``)."""
+    fn = _entry('ts2d_label_confusion')
+    z, h, w = (int(v) for v in shape_zhw)
+    k, vals = _evaluate_sides('label_confusion', a, kind_a, b, kind_b, values, z * h * w)
+    out = np.zeros((k + 2, k + 2), np.int64)
+    _lib.check(fn(int(device), a.ctypes.data, int(kind_a), b.ctypes.data, int(kind_b), vals.ctypes.data if vals is not None else None, k, z, h, w,
+                  out.ctypes.data), 'ts2d_label_confusion')
+    return out
+
+
 def _surface_call(what: str, a, kind_a, b, kind_b, values, shape_hw, spacing_hw, tol_sq, device):
     """What the two boundary-distance wrappers prepare alike for the entry ``ts2d_<what>``: ``(entry, its arguments up to T, K, out_i, out_f,
     the arrays those arguments point into)``."""

@@ -66,7 +66,7 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
              visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1, save_probabilities: bool = False,
              statistics: bool = False, reference: str = None, hausdorff_percentiles=(), average_distance: bool = False,
              statistics_percentiles=(), keep_largest: bool = False, min_component_mm: float = 0.0, components: bool = False,
-             component_connectivity: str = 'full'):
+             component_connectivity: str = 'full', confusion: bool = False):
     model = DEFAULT_MODEL if model is None else model
     content = 'all' if visualize else 'file'
     which = 'all' if save_all else 'final'
@@ -99,6 +99,8 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
                         res.save_components(dest, name, models=which, connectivity=component_connectivity)
                     if references:
                         res.save_evaluation(dest, name, references[name], percentiles=hausdorff_percentiles, average_distance=average_distance)
+                        if confusion:
+                            res.save_confusion(dest, name, references[name])
             return
         for i, (name, path) in enumerate(cases):
             log(f"[{i + 1}/{len(cases)}] Processing: {name}")
@@ -111,6 +113,8 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
                 res.save_components(dest, name, models=which, connectivity=component_connectivity)
             if references:
                 res.save_evaluation(dest, name, references[name], percentiles=hausdorff_percentiles, average_distance=average_distance)
+                if confusion:
+                    res.save_confusion(dest, name, references[name])
 
 
 def ts2d_entry_point(argv=None):
@@ -141,6 +145,8 @@ def ts2d_entry_point(argv=None):
                    "hausdorff_percentile[Q], the Q-th percentile Hausdorff distance in mm (95: HD95), Q in 0 ... 100; may be given up to 8 times.")
     p.add_argument("--average-distance", action="store_true", help="With --reference: also write per label the average surface distances in mm: "
                    "asd_pred_to_ref, asd_ref_to_pred, assd (both borders pooled) and masd (the mean of the two).")
+    p.add_argument("--confusion", action="store_true", help="With --reference: also write <case>.confusion.json, the confusion matrix of the result "
+                   "against the reference (rows the reference, columns the prediction; per label what it was predicted as and predicted from).")
     p.add_argument("--keep-largest", action="store_true", help="Clean the result before it is saved, measured or scored: of every label only the "
                    "connected components of the largest size stay.")
     p.add_argument("--min-component-mm", type=float, default=0.0, metavar="A", help="Clean the result before it is saved, measured or scored: every "
@@ -154,6 +160,8 @@ def ts2d_entry_point(argv=None):
         p.error("--batch-cases must be at least 1")
     if (a.hausdorff_percentile or a.average_distance) and a.reference is None:
         p.error("--hausdorff-percentile and --average-distance score against a reference: give --reference")
+    if a.confusion and a.reference is None:
+        p.error("--confusion compares against a reference: give --reference")
     if a.statistics_percentile and not a.statistics:
         p.error("--statistics-percentile adds to the statistics: give --statistics")
     if a.statistics_percentile and (len(a.statistics_percentile) > 8 or any(not (math.isfinite(q) and 0.0 <= q <= 100.0) for q in a.statistics_percentile)):
@@ -169,7 +177,8 @@ def ts2d_entry_point(argv=None):
     ts2d_run(src=a.src, dest=a.dest, model=a.model, use_remote=not a.no_remote, fetch_remote=not a.no_fetch, collapse=a.collapse,
              visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases, save_probabilities=a.save_probabilities,
              statistics=a.statistics, reference=a.reference, hausdorff_percentiles=tuple(a.hausdorff_percentile or ()),
-             average_distance=a.average_distance, **({'statistics_percentiles': tuple(a.statistics_percentile)} if a.statistics_percentile else {}), **clean_kw)
+             average_distance=a.average_distance, **({'statistics_percentiles': tuple(a.statistics_percentile)} if a.statistics_percentile else {}), **clean_kw,
+             **({'confusion': True} if a.confusion else {}))          # without the flag: the call of before
 
 
 if __name__ == '__main__':

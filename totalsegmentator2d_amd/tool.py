@@ -407,19 +407,10 @@ class TS2D:
                 written.append(dump_components(self.components(key, connectivity), os.path.join(dest, f"{stem}.components.json")))
             return written
 
-        def evaluate(self, reference, model: Optional[str] = None, tolerances=(2.0,), percentiles=(), average_distance: bool = False) -> Dict[str, dict]:
-            """Scores of the merged segmentation (``model=None``) or of sub-model ``model``'s against ``reference`` (``evaluate.evaluate``:
-            per label the counts, Dice, IoU, precision, recall and, for a 2-D result, surface Dice per tolerance in mm and the Hausdorff distance).
-            On request, for a 2-D result: ``percentiles`` (0 ... 100, at most 8) adds ``hausdorff_percentile[repr(float(q))]``, the percentile
-            Hausdorff distance (HD95 for 95), and ``average_distance=True`` adds ``asd_pred_to_ref``, ``asd_ref_to_pred``, ``assd`` and ``masd``,
-            the average surface distances in mm; without them the result is what it always was.
-
-            ``reference`` (an image or a path) is one of two things.  A 3-D label volume: it is reoriented and projected along the coronal axis
-            with ``evaluate.project_labels`` (``num`` = the number of labels of that segmentation) - on ``self.device`` where the result has one
-            and the entry serves the volume (C-ABI ``ts2d_project_labels_coronal``) - and collapsed as the result's segmentation is; label ``v``
-            of the volume is component ``v - 1``, the convention ``statistics.label_statistics`` documents.  Or an already-2-D segmentation of
-            the result's extent.  A shape or spacing mismatch raises ``ValueError`` with both extents.  Computed on ``self.device``, from the
-            host statements without one: the numbers are the same bit for bit."""
+        def _scored_pair(self, reference, model: Optional[str] = None):
+            """(segmentation, reference on its grid) as :meth:`evaluate` and :meth:`confusion` score them: a 3-D label volume is reoriented,
+            projected along the coronal axis and collapsed as the segmentation is, an already-2-D segmentation is taken as it is, and a
+            reference that does not lie on the segmentation's grid raises ``ValueError`` with both extents."""
             from . import evaluate as ev
             seg = self.get_segmentation(model)
             if seg is None:
@@ -438,6 +429,23 @@ class TS2D:
             if e_seg != e_ref or not np.allclose(seg.spacing, ref.spacing, rtol=1e-5, atol=1e-8):
                 raise ValueError(f"the reference does not lie on the segmentation's grid: extent {e_ref} with spacing {tuple(ref.spacing)} against "
                                  f"extent {e_seg} with spacing {tuple(seg.spacing)}")
+            return seg, ref
+
+        def evaluate(self, reference, model: Optional[str] = None, tolerances=(2.0,), percentiles=(), average_distance: bool = False) -> Dict[str, dict]:
+            """Scores of the merged segmentation (``model=None``) or of sub-model ``model``'s against ``reference`` (``evaluate.evaluate``:
+            per label the counts, Dice, IoU, precision, recall and, for a 2-D result, surface Dice per tolerance in mm and the Hausdorff distance).
+            On request, for a 2-D result: ``percentiles`` (0 ... 100, at most 8) adds ``hausdorff_percentile[repr(float(q))]``, the percentile
+            Hausdorff distance (HD95 for 95), and ``average_distance=True`` adds ``asd_pred_to_ref``, ``asd_ref_to_pred``, ``assd`` and ``masd``,
+            the average surface distances in mm; without them the result is what it always was.
+
+            ``reference`` (an image or a path) is one of two things.  A 3-D label volume: it is reoriented and projected along the coronal axis
+            with ``evaluate.project_labels`` (``num`` = the number of labels of that segmentation) - on ``self.device`` where the result has one
+            and the entry serves the volume (C-ABI ``ts2d_project_labels_coronal``) - and collapsed as the result's segmentation is; label ``v``
+            of the volume is component ``v - 1``, the convention ``statistics.label_statistics`` documents.  Or an already-2-D segmentation of
+            the result's extent.  A shape or spacing mismatch raises ``ValueError`` with both extents.  Computed on ``self.device``, from the
+            host statements without one: the numbers are the same bit for bit."""
+            from . import evaluate as ev
+            seg, ref = self._scored_pair(reference, model)
             return ev.evaluate(seg, ref, device=self.device, tolerances=tolerances, percentiles=percentiles, average_distance=average_distance)
 
         def save_evaluation(self, dest: str, name: str, reference, models='final', naming: str = 'group', tolerances=(2.0,), percentiles=(),
@@ -459,6 +467,34 @@ class TS2D:
             for key in keys:
                 stem = name if key is None else f"{name}-{(decompose_model_key(key)[1] or key) if naming == 'group' else key}"
                 written.append(dump_evaluation(self.evaluate(ref, key, tolerances, percentiles, average_distance), os.path.join(dest, f"{stem}.evaluation.json")))
+            return written
+
+        def confusion(self, reference, model: Optional[str] = None, top: int = 3) -> dict:
+            """The confusion matrix of the merged segmentation (``model=None``) or of sub-model ``model``'s against ``reference``
+            (``evaluate.confusion``: what every structure of the reference was taken for - rows the reference, columns the prediction, the
+            margins, per label the ``top`` classes it was predicted as and predicted from).  ``reference`` is prepared exactly as in
+            :meth:`evaluate`.  Computed on ``self.device`` (C-ABI ``ts2d_label_confusion``), from the host statement without one: the integers
+            are the same."""
+            from . import evaluate as ev
+            seg, ref = self._scored_pair(reference, model)
+            return ev.confusion(seg, ref, device=self.device, top=top)
+
+        def save_confusion(self, dest: str, name: str, reference, models='final', naming: str = 'group', top: int = 3) -> List[str]:
+            """``<name>.confusion.json`` for the merged segmentation and ``<name>-<group or model>.confusion.json`` per sub-model, selected by
+            ``models`` and named as in :meth:`save_evaluation`: ``json.dump`` of :meth:`confusion` against ``reference`` with sorted keys."""
+            from .evaluate import dump_evaluation
+            assert naming in {'group', 'model'}
+            mset = {str(t).strip().lower() for t in _as_list(models)}
+            keys = []
+            if {'all', 'final'} & mset and self.get_segmentation() is not None:
+                keys.append(None)
+            keys += [m for m in self.models if ('all' in mset or m.lower() in mset) and self.get_segmentation(m) is not None]
+            ref = TS2D._as_image(reference)
+            os.makedirs(dest, exist_ok=True)
+            written = []
+            for key in keys:
+                stem = name if key is None else f"{name}-{(decompose_model_key(key)[1] or key) if naming == 'group' else key}"
+                written.append(dump_evaluation(self.confusion(ref, key, top), os.path.join(dest, f"{stem}.confusion.json")))
             return written
 
         def save(self, dest: str, name: str = 'result', ext: str = 'nrrd', models='final', targets='all', content: str = 'all',
