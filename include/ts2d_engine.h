@@ -582,6 +582,48 @@ int ts2d_project_coronal_modes(int device, const void* volume, size_t n_elems, i
                                long long sx, long long base, const int32_t* modes, const int32_t* slice_index, int n_modes, float* out_planes,
                                float* out_norm, double* out_stats, int32_t* out_box, int32_t* status);
 
+/* The synthetic radiograph of a CT volume, and the projection of a 3-D label volume along the radiograph's rays, on the device.  The statements
+ * are totalsegmentator2d_amd/xray.py (xr_tables, synthetic_xr_statement, project_labels_xr_statement; numpy); the two entries reproduce them bit
+ * for bit and byte for byte.  Both take the strided view of ts2d_project_coronal_modes (volume, n_elems, dtype, extents, element strides and base
+ * as there) and then the geometry as plain numbers:
+ *   spacing_x, spacing_y, spacing_z   the spacings of the view's x, y and z in mm
+ *   source_detector_mm, source_center_mm   sdd and sod: the source's distance to the detector and to the centre of the volume
+ *   view_pa      0: 'ap', the source in front of the patient (at y below the volume); 1: 'pa', behind it.  Rows and columns keep their directions.
+ *   parallel     1: parallel rays (then nu = nx, nv = nz, du = spacing_x, dv = spacing_z are required); 0: a cone beam
+ *   du, dv, nu, nv   the detector's pixel spacings in mm and its size; pixel (k, i) of [nv][nu] sits at Cx + (i - (nu - 1) / 2) du,
+ *                Cz + (k - (nv - 1) / 2) dv, C the centre ((nx - 1) spacing_x / 2, (ny - 1) spacing_y / 2, (nz - 1) spacing_z / 2)
+ * Rays run along y; every ray has one sample per plane y = j, taken in index order for both views.
+ *
+ * ts2d_project_xr: the five sample types.  The density of a sample v is max((double(v) - air) * (1 / (water - air)), 0), then min(., density_max)
+ * where clip is 1; each sample of a ray is the bilinear interpolation of the plane's density (+0.0 outside the plane), in float64, every
+ * operation rounded on its own.
+ *   out_sum_f64  host [nv][nu] float64, the sums of the rays, or NULL
+ *   out_xr_f32   host [nv][nu] float32 = float32(sum * step), step the ray's length between two planes in mm: the line integral of the density
+ *                in millimetres of water (no exponential is applied); or NULL.  Not both NULL.
+ *   status       0, or TS2D_XR_NONFINITE: a float32 volume holds a NaN or an infinity; the outputs are not written, and the caller raises.
+ *                The call returns TS2D_OK.
+ *
+ * ts2d_project_labels_xr: integer sample types (dtype 2, float, is refused).  planes_u8 [num][nv][nu]: plane k is 1 where any sample of the ray
+ * - the NEAREST voxel floor(x + 0.5), floor(z + 0.5); a sample outside the volume is skipped - equals k + 1, else 0; num 1 ... 255.
+ *   status       0, or TS2D_LABELS_RANGE: a sample of the volume (met by a ray or not) lies outside 0 ... num; planes_u8 is not written, and
+ *                the caller raises.  The call returns TS2D_OK.
+ *
+ * Every argument is checked before any device work and refused by name with TS2D_ERR_INVALID, the outputs untouched: a null pointer, an unknown
+ * dtype, an extent below 1, a view that leaves the buffer, nz * nx above 2^31 - 1; a spacing or distance that is not finite and positive;
+ * source_center_mm <= (ny - 1) spacing_y / 2 (the source inside the slab of plane centres); source_detector_mm - source_center_mm below that half
+ * depth (the detector inside the slab); nu or nv below 1, nu * nv above 2^31 - 1 (num * nu * nv for the planes); view_pa, parallel or clip other
+ * than 0 or 1; water == air, either not finite; a density_max that is not a number >= 0; num outside 1 ... 255.
+ * Host pointers in and out; synchronous; the call owns its device scratch and frees it on every path.  (ABI 9, optional symbols) */
+#define TS2D_XR_NONFINITE 1
+int ts2d_project_xr(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy, long long sx,
+                    long long base, double spacing_x, double spacing_y, double spacing_z, double source_detector_mm, double source_center_mm,
+                    int view_pa, int parallel, double du, double dv, int nu, int nv, double air, double water, int clip, double density_max,
+                    double* out_sum_f64, float* out_xr_f32, int32_t* status);
+int ts2d_project_labels_xr(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy,
+                           long long sx, long long base, double spacing_x, double spacing_y, double spacing_z, double source_detector_mm,
+                           double source_center_mm, int view_pa, int parallel, double du, double dv, int nu, int nv, int num, uint8_t* planes_u8,
+                           int32_t* status);
+
 /* nnU-Net's input resample for the 2-D configurations on the device: every plane of src [n_planes][in_h][in_w] float32 resampled to
  * dst [n_planes][out_h][out_w] float32 as skimage.transform.resize(plane, (out_h, out_w), order=3, mode='edge', anti_aliasing=False,
  * clip=True) does it (reference flow DefaultPreprocessor.run_case, ts2d/core/inference/prediction_worker.py:194-199, for a case whose

@@ -79,6 +79,7 @@ CC_GIVE_UP = 1                                              # TS2D_CC_GIVE_UP
 PROJECT_MODES = {'max': 0, 'min': 1, 'mean': 2, 'median': 3, 'std': 4, 'first': 5, 'slice': 6}      # TS2D_PROJECT_*
 PROJECT_MAX_MODES, PROJECT_RAY_CAP = 16, 8192               # TS2D_PROJECT_MAX_MODES, TS2D_PROJECT_RAY_CAP
 PROJECT_NONFINITE, PROJECT_RAY_TOO_LONG = 1, 2              # TS2D_PROJECT_NONFINITE, TS2D_PROJECT_RAY_TOO_LONG
+XR_NONFINITE = 1                                            # TS2D_XR_NONFINITE
 VISUAL_NONFINITE = 1                                        # TS2D_VISUAL_NONFINITE
 STATS_PLANES, STATS_LABELMAP, STATS_NONFINITE = 0, 1, 1     # TS2D_STATS_PLANES, TS2D_STATS_LABELMAP, TS2D_STATS_NONFINITE
 STATS_INTS, STATS_F64S, STATS_MAX_CHANNELS = 10, 6, 64      # TS2D_STATS_INTS, TS2D_STATS_F64S, TS2D_STATS_MAX_CHANNELS
@@ -93,6 +94,7 @@ _PP, _TI, _TE, _TL = ctypes.POINTER(_P), ctypes.POINTER(TiledImage), ctypes.POIN
 _TP, _TPR = ctypes.POINTER(TiledProbabilities), ctypes.POINTER(TiledProbabilitiesRun)
 _PROJECT = [_I, _P, _Z, _I, _I, _I, _I, _LL, _LL, _LL, _LL, _P, _P]
 _D = ctypes.c_double
+_XR_GEOMETRY = [_D, _D, _D, _D, _D, _I, _I, _D, _D, _I, _I]      # spacing_x, _y, _z, sdd, sod, view_pa, parallel, du, dv, nu, nv
 
 # every symbol include/ts2d_engine.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -119,6 +121,8 @@ SIGNATURES = {
     'ts2d_project_coronal': (_I, _PROJECT),
     'ts2d_project_coronal_zscore': (_I, _PROJECT + [_P, _P, _P]),
     'ts2d_project_coronal_modes': (_I, _PROJECT[:-2] + [_P, _P, _I, _P, _P, _P, _P, _P]),
+    'ts2d_project_xr': (_I, _PROJECT[:-2] + _XR_GEOMETRY + [_D, _D, _I, _D, _P, _P, _P]),
+    'ts2d_project_labels_xr': (_I, _PROJECT[:-2] + _XR_GEOMETRY + [_I, _P, _P]),
     'ts2d_resample_cubic': (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),
     'ts2d_planes_create': (_I, [_I, _P, _I, _I, _I, _PP]),
     'ts2d_planes_crop_zscore': (_I, [_P, ctypes.POINTER(ctypes.c_int32 * 4), _P, ctypes.POINTER(_I)]),
@@ -175,11 +179,12 @@ SYMBOLS = tuple(SIGNATURES)
 # ... and the boundary distances of volumes: without the entry evaluate.evaluate(volume_distances=True) keeps its statement
 # ... and the components of every label at once: without the entry components.label_components and clean_components keep the host route (their statement)
 # ... and the confusion matrix: without the entry evaluate.confusion keeps the host route (its statement)
+# ... and the two entries of the synthetic radiograph: without them xray.synthetic_xr and xray.project_labels_xr keep the host route (their statements)
 OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n
                      or n.startswith('ts2d_visual_')
                      or n in ('ts2d_engine_create_residual', 'ts2d_keep_largest_components', 'ts2d_project_coronal_modes', 'ts2d_label_statistics', 'ts2d_label_percentiles',
                               'ts2d_project_labels_coronal', 'ts2d_label_overlap', 'ts2d_surface_distances', 'ts2d_surface_distance_profile',
-                              'ts2d_volume_surface_distances', 'ts2d_label_components', 'ts2d_label_confusion'))
+                              'ts2d_volume_surface_distances', 'ts2d_label_components', 'ts2d_label_confusion', 'ts2d_project_xr', 'ts2d_project_labels_xr'))
 
 
 class EngineLibraryError(RuntimeError):

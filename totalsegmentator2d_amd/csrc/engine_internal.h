@@ -334,6 +334,18 @@ void prep_leaves(int off, int n, std::vector<PrepLeaf>* out);
 float prep_plane_sum(const float* sums, long long n);
 float prep_rescale_div(float mn, float mx);
 float prep_unkey(int key);
+// The geometry of a synthetic radiograph as its two entries take it, and the float64 ray tables made of it (xray.xr_tables in numpy): sample j of
+// ray (k, i) lies at x = cx[i] + t[j] * a[i], z = cz[k] + t[j] * b[k]; p and q give the ray's step length (xr_step).
+struct XrGeometry {
+    int nz, ny, nx; double sx, sy, sz, sdd, sod; int pa, parallel; double du, dv; int nu, nv;
+};
+struct XrPlan {
+    std::vector<double> t, a, cx, p, b, cz, q;      // t [ny]; a, cx, p [nu]; b, cz, q [nv]
+    double sy = 0.0; bool parallel = false; int nu = 0, nv = 0;
+};
+int xr_plan(const char* entry, const XrGeometry& g, XrPlan* pl);      // refuses, by name, what xray.XRGeometry.resolve refuses
+double xr_step(const XrPlan& pl, int k, int i);
+void xr_finish(const XrPlan& pl, const double* sum, float* out);       // out [nv][nu] = float32(sum * step)
 
 }  // namespace ts2d
 #pragma GCC visibility pop

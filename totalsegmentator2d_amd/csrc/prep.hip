@@ -1,4 +1,5 @@
-// The input side of libts2d_engine.so, none of which needs an engine: coronal projection + z-score of a volume, the order-3 resample to the
+// The input side of libts2d_engine.so, none of which needs an engine: coronal projection + z-score of a volume, its synthetic radiograph and the
+// label projection along the radiograph's rays, the order-3 resample to the
 // plan spacing, and the ts2d_planes handle (crop box, every normalisation scheme of nnU-Net and resample of native 2-D inputs, and of the slice stacks
 // of a volume under a 2-D plan, where they lie on the device).
 // The host arithmetic behind them is prep_plan.cpp; every device buffer of a call is a DevMem, so HIP_TRY may return wherever it fails.
@@ -6,6 +7,7 @@
 #include "entry_util.h"
 #include "kernels_project.h"
 #include "kernels_project_modes.h"
+#include "kernels_project_xr.h"
 #include "kernels_resample_in.h"
 #include "kernels_prep.h"
 #include "kernels_prep_schemes.h"
@@ -14,6 +16,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 using namespace ts2d;
@@ -481,6 +484,132 @@ int planes_crop_normalize_stack(const char* entry, bool take_masked, ts2d_planes
     return TS2D_OK;
 }
 
+static_assert(kXrStatusNonFinite == TS2D_XR_NONFINITE && kXrStatusRange == TS2D_LABELS_RANGE, "the radiograph entries speak the C header's numbers");
+
+// What ts2d_project_xr and ts2d_project_labels_xr share.  xr_check: every refusal of the view and the geometry, and the ray tables; nothing of the
+// device is touched.  xr_upload: the call's one allocation - status word, volume, tables, `out_bytes` of output - with the volume and the tables
+// uploaded and the status word cleared.
+struct XrCall {
+    XrPlan plan;
+    XrView view;
+    XrTables tb;
+    DevMem d;
+    int* d_status = nullptr;
+    size_t o_vol = 0, o_out = 0;
+};
+
+int xr_check(const char* E, const void* volume, size_t n_elems, const XrGeometry& g, long long sz, long long sy, long long sx, long long base, XrCall* c) {
+    if (!volume) return fail(TS2D_ERR_INVALID, "%s: volume is null", E);
+    TRY(xr_plan(E, g, &c->plan));
+    if ((long long)g.nz * g.nx > 0x7FFFFFFFll)          // (the scan: one lane per (z, x) column)
+        return fail(TS2D_ERR_INVALID, "%s: planes of nz %d x nx %d are more than 2^31 - 1 samples", E, g.nz, g.nx);
+    TRY(check_strided_view(E, n_elems, base, {g.nz, g.ny, g.nx}, {sz, sy, sx}));
+    c->view = XrView{g.nz, g.ny, g.nx, sz, sy, sx, base};
+    return TS2D_OK;
+}
+
+int xr_upload(int device, const void* volume, size_t vbytes, size_t out_bytes, XrCall* c) {
+    const XrPlan& pl = c->plan;
+    HIP_TRY(hipSetDevice(device));
+    ArenaLayout lay;
+    const size_t o_status = lay.add(sizeof(int));
+    c->o_vol = lay.add(vbytes);
+    const size_t nt = pl.t.size(), nu = pl.a.size(), nv = pl.b.size();
+    const size_t o_t = lay.add(nt * sizeof(double)), o_a = lay.add(nu * sizeof(double)), o_cx = lay.add(nu * sizeof(double));
+    const size_t o_b = lay.add(nv * sizeof(double)), o_cz = lay.add(nv * sizeof(double));
+    c->o_out = lay.add(out_bytes);
+    HIP_TRY(c->d.alloc(lay.total()));
+    c->d_status = c->d.as<int>(o_status);
+    HIP_TRY(hipMemset(c->d_status, 0, sizeof(int)));
+    HIP_TRY(hipMemcpy(c->d.as<char>(c->o_vol), volume, vbytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d.as<char>(o_t), pl.t.data(), nt * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d.as<char>(o_a), pl.a.data(), nu * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d.as<char>(o_cx), pl.cx.data(), nu * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d.as<char>(o_b), pl.b.data(), nv * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d.as<char>(o_cz), pl.cz.data(), nv * sizeof(double), hipMemcpyHostToDevice));
+    c->tb = XrTables{c->d.as<const double>(o_t), c->d.as<const double>(o_a), c->d.as<const double>(o_cx), c->d.as<const double>(o_b),
+                     c->d.as<const double>(o_cz), pl.nu, pl.nv};
+    return TS2D_OK;
+}
+
+int project_xr_impl(int device, const void* volume, size_t n_elems, int dtype, const XrGeometry& g, long long sz, long long sy, long long sx,
+                    long long base, double air, double water, int clip, double density_max, double* out_sum, float* out_xr, int* status) {
+    const char* const E = "ts2d_project_xr";
+    if (!status) return fail(TS2D_ERR_INVALID, "%s: status is null", E);
+    if (!out_sum && !out_xr) return fail(TS2D_ERR_INVALID, "%s: out_sum_f64 and out_xr_f32 are both null", E);
+    if (dtype < 0 || dtype > 4) return fail(TS2D_ERR_INVALID, "%s: dtype %d unknown", E, dtype);
+    if (!(std::isfinite(air) && std::isfinite(water))) return fail(TS2D_ERR_INVALID, "%s: air = %g, water = %g are not finite", E, air, water);
+    if (water == air) return fail(TS2D_ERR_INVALID, "%s: water == air = %g: no sample value has density 1", E, air);
+    if (clip != 0 && clip != 1) return fail(TS2D_ERR_INVALID, "%s: clip %d is neither 0 nor 1", E, clip);
+    if (clip && !(density_max >= 0.0)) return fail(TS2D_ERR_INVALID, "%s: density_max = %g is not a number >= 0", E, density_max);
+    XrCall c;
+    TRY(xr_check(E, volume, n_elems, g, sz, sy, sx, base, &c));
+    *status = 0;
+    const long long n = (long long)g.nu * g.nv;
+    TRY(xr_upload(device, volume, n_elems * sample_size(dtype), (size_t)n * sizeof(double), &c));
+    const XrDensity dn = {air, 1.0 / (water - air), clip ? density_max : 0.0, clip};
+    double* d_sum = c.d.as<double>(c.o_out);
+    by_sample_type(dtype, [&](auto t) {
+        using S = typename decltype(t)::type;
+        const S* d_vol = c.d.as<const S>(c.o_vol);
+        if constexpr (!std::is_integral<S>::value)       // the streaming pre-pass of a float volume: a non-finite sample is a status, not a result
+            hipLaunchKernelGGL(xr_scan<S>, dim3((unsigned)(((long long)g.nz * g.nx + kXrThreads - 1) / kXrThreads)), dim3(kXrThreads), 0, 0, d_vol, c.view,
+                               -1, c.d_status);
+        hipLaunchKernelGGL(project_xr_rays<S>, dim3((unsigned)((n + kXrThreads - 1) / kXrThreads)), dim3(kXrThreads), 0, 0, d_vol, c.view, dn, c.tb, d_sum);
+    });
+    HIP_TRY(hipGetLastError());
+    int st = 0;
+    HIP_TRY(hipMemcpy(&st, c.d_status, sizeof(st), hipMemcpyDeviceToHost));       // (waits for the launches: the default stream orders them)
+    if (st) { *status = kXrStatusNonFinite; return TS2D_OK; }                      // the sums are no result: the outputs stay untouched
+    std::vector<double> own;
+    double* sum = out_sum;
+    if (!sum) { own.resize((size_t)n); sum = own.data(); }
+    HIP_TRY(hipMemcpy(sum, d_sum, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_xr) xr_finish(c.plan, sum, out_xr);
+    return TS2D_OK;
+}
+
+template <typename T>
+void project_labels_xr_launch(const T* d_vol, const XrCall& c, int num, uint8_t* d_out) {
+    const long long n = (long long)c.tb.nu * c.tb.nv;
+    const dim3 grid((unsigned)((n + kXrThreads - 1) / kXrThreads)), block(kXrThreads);
+    hipLaunchKernelGGL(xr_scan<T>, dim3((unsigned)(((long long)c.view.nz * c.view.nx + kXrThreads - 1) / kXrThreads)), block, 0, 0, d_vol, c.view, num,
+                       c.d_status);
+    if (num <= 32) hipLaunchKernelGGL((project_labels_xr_rays<T, 1>), grid, block, 0, 0, d_vol, c.view, c.tb, num, d_out);
+    else if (num <= 64) hipLaunchKernelGGL((project_labels_xr_rays<T, 2>), grid, block, 0, 0, d_vol, c.view, c.tb, num, d_out);
+    else if (num <= 128) hipLaunchKernelGGL((project_labels_xr_rays<T, 4>), grid, block, 0, 0, d_vol, c.view, c.tb, num, d_out);
+    else hipLaunchKernelGGL((project_labels_xr_rays<T, 8>), grid, block, 0, 0, d_vol, c.view, c.tb, num, d_out);
+}
+
+int project_labels_xr_impl(int device, const void* volume, size_t n_elems, int dtype, const XrGeometry& g, long long sz, long long sy, long long sx,
+                           long long base, int num, uint8_t* planes, int* status) {
+    const char* const E = "ts2d_project_labels_xr";
+    if (!planes) return fail(TS2D_ERR_INVALID, "%s: planes_u8 is null", E);
+    if (!status) return fail(TS2D_ERR_INVALID, "%s: status is null", E);
+    if (dtype < 0 || dtype > 4 || dtype == 2)
+        return fail(TS2D_ERR_INVALID, "%s: dtype %d is not an integer type (int16 0, uint8 1, uint16 3, int32 4)", E, dtype);
+    if (num < 1 || num > 255) return fail(TS2D_ERR_INVALID, "%s: num = %d outside 1 ... 255", E, num);
+    XrCall c;
+    TRY(xr_check(E, volume, n_elems, g, sz, sy, sx, base, &c));
+    const long long n = (long long)g.nu * g.nv;
+    if (n * num > 0x7FFFFFFFll) return fail(TS2D_ERR_INVALID, "%s: %d planes of nv %d x nu %d are more than 2^31 - 1 bytes", E, num, g.nv, g.nu);
+    *status = 0;
+    const size_t obytes = (size_t)n * num;
+    TRY(xr_upload(device, volume, n_elems * sample_size(dtype), obytes, &c));
+    uint8_t* d_out = c.d.as<uint8_t>(c.o_out);
+    by_sample_type(dtype, [&](auto t) {
+        using S = typename decltype(t)::type;
+        if constexpr (std::is_integral<S>::value)                  // (float32 was refused above: no kernel of it is built)
+            project_labels_xr_launch(c.d.as<const S>(c.o_vol), c, num, d_out);
+    });
+    HIP_TRY(hipGetLastError());
+    int st = 0;
+    HIP_TRY(hipMemcpy(&st, c.d_status, sizeof(st), hipMemcpyDeviceToHost));
+    if (st) { *status = kXrStatusRange; return TS2D_OK; }                         // a sample outside 0 ... num: no plane is written
+    HIP_TRY(hipMemcpy(planes, d_out, obytes, hipMemcpyDeviceToHost));
+    return TS2D_OK;
+}
+
 }  // namespace
 #pragma GCC visibility pop
 
@@ -503,6 +632,22 @@ int ts2d_project_coronal_modes(int device, const void* volume, size_t n_elems, i
                                float* out_norm, double* out_stats, int32_t* out_box, int32_t* status) {
     return project_coronal_modes_impl(device, volume, n_elems, dtype, nz, ny, nx, sz, sy, sx, base, modes, slice_index, n_modes, out_planes, out_norm,
                                       out_stats, out_box, status);
+}
+
+int ts2d_project_xr(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy, long long sx,
+                    long long base, double spacing_x, double spacing_y, double spacing_z, double source_detector_mm, double source_center_mm,
+                    int view_pa, int parallel, double du, double dv, int nu, int nv, double air, double water, int clip, double density_max,
+                    double* out_sum_f64, float* out_xr_f32, int32_t* status) {
+    const XrGeometry g = {nz, ny, nx, spacing_x, spacing_y, spacing_z, source_detector_mm, source_center_mm, view_pa, parallel, du, dv, nu, nv};
+    return project_xr_impl(device, volume, n_elems, dtype, g, sz, sy, sx, base, air, water, clip, density_max, out_sum_f64, out_xr_f32, status);
+}
+
+int ts2d_project_labels_xr(int device, const void* volume, size_t n_elems, int dtype, int nz, int ny, int nx, long long sz, long long sy,
+                           long long sx, long long base, double spacing_x, double spacing_y, double spacing_z, double source_detector_mm,
+                           double source_center_mm, int view_pa, int parallel, double du, double dv, int nu, int nv, int num, uint8_t* planes_u8,
+                           int32_t* status) {
+    const XrGeometry g = {nz, ny, nx, spacing_x, spacing_y, spacing_z, source_detector_mm, source_center_mm, view_pa, parallel, du, dv, nu, nv};
+    return project_labels_xr_impl(device, volume, n_elems, dtype, g, sz, sy, sx, base, num, planes_u8, status);
 }
 
 int ts2d_resample_cubic(int device, const float* src, int n_planes, int in_h, int in_w, int out_h, int out_w, const float* lo_hi, float* dst) {

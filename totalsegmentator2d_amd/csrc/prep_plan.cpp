@@ -1,5 +1,5 @@
-// Host arithmetic of the input side (prep.hip): the taps and prefilter constants of the order-3 resample, and the fold of numpy's pairwise
-// sum behind the z-score.  Plain C++: every statement here must match scipy / numpy bit for bit, so none of it is compiled as HIP code.
+// Host arithmetic of the input side (prep.hip): the taps and prefilter constants of the order-3 resample, the fold of numpy's pairwise
+// sum behind the z-score, and the ray tables, step lengths and final cast of the synthetic radiograph.  Plain C++: every statement here must match scipy / numpy bit for bit, so none of it is compiled as HIP code.
 #include "engine_internal.h"
 
 #include <algorithm>
@@ -114,5 +114,71 @@ float prep_rescale_div(float mn, float mx) {
 }
 
 float prep_unkey(int key) { const int b = key < 0 ? key ^ 0x7FFFFFFF : key; float f; std::memcpy(&f, &b, 4); return f; }
+
+// The ray tables of a synthetic radiograph (totalsegmentator2d_amd/xray.py: xr_tables is the same statement in numpy), one rounding per
+// operation.  Refuses, by name, what XRGeometry.resolve refuses; on a refusal the plan is not to be used.
+int xr_plan(const char* entry, const XrGeometry& g, XrPlan* pl) {
+#pragma clang fp contract(off)
+    if (g.nz < 1 || g.ny < 1 || g.nx < 1) return fail(TS2D_ERR_INVALID, "%s: extents nz %d, ny %d, nx %d below 1", entry, g.nz, g.ny, g.nx);
+    if (g.pa != 0 && g.pa != 1) return fail(TS2D_ERR_INVALID, "%s: view %d is neither 0 (ap) nor 1 (pa)", entry, g.pa);
+    if (g.parallel != 0 && g.parallel != 1) return fail(TS2D_ERR_INVALID, "%s: parallel %d is neither 0 nor 1", entry, g.parallel);
+    const struct { const char* name; double v; } positive[] = {{"spacing_x", g.sx}, {"spacing_y", g.sy}, {"spacing_z", g.sz},
+        {"source_detector_mm", g.sdd}, {"source_center_mm", g.sod}, {"du", g.du}, {"dv", g.dv}};
+    for (const auto& c : positive)
+        if (!(std::isfinite(c.v) && c.v > 0.0)) return fail(TS2D_ERR_INVALID, "%s: %s = %g is not finite and positive", entry, c.name, c.v);
+    const double half = (double)(g.ny - 1) * g.sy / 2.0;
+    if (!(g.sod > half))
+        return fail(TS2D_ERR_INVALID, "%s: source_center_mm = %g puts the source inside the slab of plane centres (half depth %g mm)", entry, g.sod, half);
+    if (g.sdd - g.sod < half)
+        return fail(TS2D_ERR_INVALID, "%s: source_detector_mm - source_center_mm = %g puts the detector inside the slab of plane centres (half depth %g mm)",
+                    entry, g.sdd - g.sod, half);
+    if (g.nu < 1 || g.nv < 1) return fail(TS2D_ERR_INVALID, "%s: detector size nu %d, nv %d below 1", entry, g.nu, g.nv);
+    if ((long long)g.nu * g.nv > 0x7FFFFFFFll)
+        return fail(TS2D_ERR_INVALID, "%s: detector size nu %d x nv %d is more than 2^31 - 1 pixels", entry, g.nu, g.nv);
+    if (g.parallel && (g.nu != g.nx || g.nv != g.nz || g.du != g.sx || g.dv != g.sz))
+        return fail(TS2D_ERR_INVALID, "%s: parallel rays fix the detector to nu = nx, nv = nz, du = spacing_x, dv = spacing_z", entry);
+    const double Cx = (double)(g.nx - 1) * g.sx / 2.0, Cy = (double)(g.ny - 1) * g.sy / 2.0, Cz = (double)(g.nz - 1) * g.sz / 2.0;
+    const double sign = g.pa ? -1.0 : 1.0;
+    const double Sy = Cy - sign * g.sod;
+    const double Yd = Sy + sign * g.sdd;
+    const double den = Yd - Sy;
+    const double hu = (double)(g.nu - 1) / 2.0, hv = (double)(g.nv - 1) / 2.0;
+    pl->parallel = g.parallel != 0; pl->sy = g.sy; pl->nu = g.nu; pl->nv = g.nv;
+    pl->t.resize((size_t)g.ny);
+    pl->a.resize((size_t)g.nu); pl->cx.resize((size_t)g.nu); pl->p.resize((size_t)g.nu);
+    pl->b.resize((size_t)g.nv); pl->cz.resize((size_t)g.nv); pl->q.resize((size_t)g.nv);
+    for (int j = 0; j < g.ny; ++j) pl->t[(size_t)j] = g.parallel ? 0.0 : ((double)j * g.sy - Sy) / den;
+    const double cx = Cx / g.sx, cz = Cz / g.sz;
+    for (int i = 0; i < g.nu; ++i) {
+        const double U = Cx + ((double)i - hu) * g.du, off = U - Cx;
+        pl->a[(size_t)i] = off / g.sx; pl->p[(size_t)i] = off / den; pl->cx[(size_t)i] = g.parallel ? (double)i : cx;
+    }
+    for (int k = 0; k < g.nv; ++k) {
+        const double V = Cz + ((double)k - hv) * g.dv, off = V - Cz;
+        pl->b[(size_t)k] = off / g.sz; pl->q[(size_t)k] = off / den; pl->cz[(size_t)k] = g.parallel ? (double)k : cz;
+    }
+    return TS2D_OK;
+}
+
+// the step length of ray (k, i): sy * sqrt((1 + p_i p_i) + q_k q_k), sy for parallel rays
+double xr_step(const XrPlan& pl, int k, int i) {
+#pragma clang fp contract(off)
+    if (pl.parallel) return pl.sy;
+    const double p = pl.p[(size_t)i], q = pl.q[(size_t)k];
+    const double pp = p * p, qq = q * q;
+    const double s = (1.0 + pp) + qq;
+    return pl.sy * std::sqrt(s);
+}
+
+// the radiograph from the downloaded sums: float32(sum * step)
+void xr_finish(const XrPlan& pl, const double* sum, float* out) {
+#pragma clang fp contract(off)
+    for (int k = 0; k < pl.nv; ++k)
+        for (int i = 0; i < pl.nu; ++i) {
+            const size_t at = (size_t)k * pl.nu + i;
+            const double v = sum[at] * xr_step(pl, k, i);
+            out[at] = (float)v;
+        }
+}
 
 }  // namespace ts2d

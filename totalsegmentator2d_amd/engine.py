@@ -884,6 +884,46 @@ def project_labels_coronal(buffer: np.ndarray, extents, strides, base: int, num:
     return planes, int(status[0])
 
 
+def _xr_args(what: str, buffer: np.ndarray, extents, strides, base: int, g: dict, device: int, integer: bool):
+    """The view and the geometry of the two radiograph entries as their leading arguments.  ``g``: ``xray.XRGeometry.resolve``."""
+    from .image import _GPU_DTYPES
+    if buffer.dtype.name not in _GPU_DTYPES or (integer and not np.issubdtype(buffer.dtype, np.integer)) or not buffer.flags['C_CONTIGUOUS']:
+        raise RuntimeError(f"{what}: expected a C-contiguous {'int16, uint8, uint16 or int32' if integer else 'int16, uint8, float32, uint16 or int32'} "
+                           f"volume, found {buffer.dtype}")
+    nz, ny, nx = (int(v) for v in extents)
+    sz, sy, sx = (int(v) for v in strides)
+    return [int(device), buffer.ctypes.data, buffer.size, _GPU_DTYPES[buffer.dtype.name], nz, ny, nx, sz, sy, sx, int(base),
+            float(g['spacing'][0]), float(g['spacing'][1]), float(g['spacing'][2]), float(g['sdd']), float(g['sod']), int(g['pa']), int(g['parallel']),
+            float(g['du']), float(g['dv']), int(g['nu']), int(g['nv'])]
+
+
+def project_xr(buffer: np.ndarray, extents, strides, base: int, g: dict, device: int = 0, want_sum: bool = True, want_xr: bool = True):
+    """The synthetic radiograph on the device (C-ABI ts2d_project_xr, csrc/kernels_project_xr.h).  ``buffer``, ``extents``, ``strides``, ``base``:
+    the reoriented view of ``image._coronal_view``; ``g``: the resolved geometry (``xray.XRGeometry.resolve``).  Returns ``(float64 [nv, nu] sums or
+    None, float32 [nv, nu] radiograph or None, status)``; with a status bit (``_lib.XR_NONFINITE``) the arrays are no result."""
+    fn = _entry('ts2d_project_xr')
+    args = _xr_args('project_xr', buffer, extents, strides, base, g, device, integer=False)
+    nu, nv = int(g['nu']), int(g['nv'])
+    out_sum = np.zeros((nv, nu), np.float64) if want_sum else None
+    out_xr = np.zeros((nv, nu), np.float32) if want_xr else None
+    status = np.zeros(1, np.int32)
+    clip = g['density_max'] is not None
+    _lib.check(fn(*args, float(g['air']), float(g['water']), int(clip), float(g['density_max']) if clip else 0.0,
+                  out_sum.ctypes.data if want_sum else None, out_xr.ctypes.data if want_xr else None, status.ctypes.data), 'ts2d_project_xr')
+    return out_sum, out_xr, int(status[0])
+
+
+def project_labels_xr(buffer: np.ndarray, extents, strides, base: int, num: int, g: dict, device: int = 0):
+    """The label projection along the radiograph's rays on the device (C-ABI ts2d_project_labels_xr).  Arguments as :func:`project_xr`.  Returns
+    ``(uint8 [num, nv, nu], status)``; with a status bit (``_lib.LABELS_RANGE``) the planes are no result."""
+    fn = _entry('ts2d_project_labels_xr')
+    args = _xr_args('project_labels_xr', buffer, extents, strides, base, g, device, integer=True)
+    planes = np.zeros((int(num), int(g['nv']), int(g['nu'])), np.uint8)
+    status = np.zeros(1, np.int32)
+    _lib.check(fn(*args, int(num), planes.ctypes.data, status.ctypes.data), 'ts2d_project_labels_xr')
+    return planes, int(status[0])
+
+
 def _evaluate_sides(what: str, a: np.ndarray, kind_a: int, b: np.ndarray, kind_b: int, values, n: int):
     """(K, values as uint8 or None) of the two sides of a scoring entry: C-contiguous uint8, planes [K, n samples] or one label map."""
     for x in (a, b):

@@ -66,7 +66,8 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
              visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1, save_probabilities: bool = False,
              statistics: bool = False, reference: str = None, hausdorff_percentiles=(), average_distance: bool = False,
              statistics_percentiles=(), keep_largest: bool = False, min_component_mm: float = 0.0, components: bool = False,
-             component_connectivity: str = 'full', confusion: bool = False):
+             component_connectivity: str = 'full', confusion: bool = False, synthetic_xr=None):
+    """``synthetic_xr``: an ``xray.XRGeometry`` (or True) switches the synthetic radiograph of ``TS2D`` on; None: the call of before."""
     model = DEFAULT_MODEL if model is None else model
     content = 'all' if visualize else 'file'
     which = 'all' if save_all else 'final'
@@ -78,7 +79,8 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
         if keep_largest or min_component_mm > 0:
             res = res.cleaned(keep_largest=keep_largest, min_size_mm=min_component_mm, connectivity=component_connectivity)
         return res
-    with TS2D(key=model, use_remote=use_remote, fetch_remote=fetch_remote, models=models) as ts:
+    xr_kw = {} if synthetic_xr is None else {'synthetic_xr': synthetic_xr}
+    with TS2D(key=model, use_remote=use_remote, fetch_remote=fetch_remote, models=models, **xr_kw) as ts:
         cases = list(_enumerate_cases(src))
         references = _references(reference, cases, os.path.isdir(src))
         log(f"Predicting {len(cases)} case{'s' if len(cases) != 1 else ''}")
@@ -155,7 +157,23 @@ def ts2d_entry_point(argv=None):
                    "their sizes and where each starts (with --save-all one <case>-<group>.components.json per sub-model too).")
     p.add_argument("--component-connectivity", choices=("full", "faces"), default=None, help="With --keep-largest, --min-component-mm or --components: "
                    "which neighbours connect, full (8 / 26, the default) or faces (4 / 6).")
+    p.add_argument("--synthetic-xr", action="store_true", help="Render a synthetic radiograph of a 3-D input for every model channel named xr, xray "
+                   "or x-ray (a cone beam along the coronal axis; the line integral of the density in mm of water), and score a 3-D --reference "
+                   "through the same rays.")
+    p.add_argument("--xr-source-detector", type=float, default=None, metavar="MM", help="With --synthetic-xr: source-to-detector distance (1800).")
+    p.add_argument("--xr-source-center", type=float, default=None, metavar="MM", help="With --synthetic-xr: source-to-volume-centre distance (1500).")
+    p.add_argument("--xr-view", choices=("ap", "pa"), default=None, help="With --synthetic-xr: the source in front of the patient (ap, the default) "
+                   "or behind (pa).")
+    p.add_argument("--xr-parallel", action="store_true", help="With --synthetic-xr: parallel rays instead of a cone beam.")
     a = p.parse_args(argv)
+    xr_kw = {}
+    if a.synthetic_xr:
+        from .xray import XRGeometry
+        given = {'source_detector_mm': a.xr_source_detector, 'source_center_mm': a.xr_source_center, 'view': a.xr_view,
+                 'parallel': True if a.xr_parallel else None}
+        xr_kw = {'synthetic_xr': XRGeometry(**{k: v for k, v in given.items() if v is not None})}
+    elif a.xr_source_detector is not None or a.xr_source_center is not None or a.xr_view is not None or a.xr_parallel:
+        p.error("--xr-source-detector, --xr-source-center, --xr-view and --xr-parallel shape the synthetic radiograph: give --synthetic-xr")
     if a.batch_cases < 1:
         p.error("--batch-cases must be at least 1")
     if (a.hausdorff_percentile or a.average_distance) and a.reference is None:
@@ -178,7 +196,7 @@ def ts2d_entry_point(argv=None):
              visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases, save_probabilities=a.save_probabilities,
              statistics=a.statistics, reference=a.reference, hausdorff_percentiles=tuple(a.hausdorff_percentile or ()),
              average_distance=a.average_distance, **({'statistics_percentiles': tuple(a.statistics_percentile)} if a.statistics_percentile else {}), **clean_kw,
-             **({'confusion': True} if a.confusion else {}))          # without the flag: the call of before
+             **({'confusion': True} if a.confusion else {}), **xr_kw)          # without the flags: the call of before
 
 
 if __name__ == '__main__':

@@ -32,11 +32,21 @@ def _as_list(v):
 class TS2D:
     def __init__(self, key: str = "ts2d", use_remote: bool = True, fetch_remote: bool = True,
                  models: Optional[Dict[str, HIPModel]] = None, zoo_root: Optional[str] = None, device=None,
-                 concurrent_models: bool = True):
+                 concurrent_models: bool = True, synthetic_xr=None, synthetic_xr_channels=('xr', 'xray', 'x-ray')):
         """``models``: pre-built ``{id: HIPModel}`` (synthetic-weight models in tests / bench); otherwise `key` is resolved
-        against the local zoo.  ``use_remote`` / ``fetch_remote`` are accepted for signature compatibility (no network)."""
+        against the local zoo.  ``use_remote`` / ``fetch_remote`` are accepted for signature compatibility (no network).
+
+        ``synthetic_xr``: an ``xray.XRGeometry``, or True for its defaults, switches the synthetic radiograph on: for a 3-D input, a channel
+        whose name is one of ``synthetic_xr_channels`` is rendered from the volume (``xray.synthetic_xr``, on the engines' device) where
+        ``image.project`` would refuse the name, and a 3-D reference is scored through the same rays (``Result._scored_pair``).  Unset (None or
+        False), nothing changes: such a channel name on a 3-D input raises what it always raised."""
         self.models: Dict[str, HIPModel] = {}
         self.concurrent_models = bool(concurrent_models)
+        self.synthetic_xr = None
+        if synthetic_xr is not None and synthetic_xr is not False:
+            from .xray import _geometry
+            self.synthetic_xr = _geometry(synthetic_xr)
+        self.synthetic_xr_channels = tuple(str(c).lower().strip() for c in synthetic_xr_channels)
         if models is None:
             self.zoo = LocalZoo(zoo_root)
             ids = self.zoo.resolve(key, unique_model=True)
@@ -126,11 +136,34 @@ class TS2D:
         result: dict = {'models': models}
         if merge:
             segs = [r['segmentation'] for _, r in sorted(models.items())]
+            drawn = sorted(m for m, r in models.items() if r.get('xr_geometry') is not None)
+            if drawn and len(drawn) != len(models) and any(s.size != segs[0].size for s in segs[1:]):
+                raise RuntimeError(f"the sub-models on synthetic radiographs ({', '.join(drawn)}) and those on projections "
+                                   f"({', '.join(sorted(set(models) - set(drawn)))}) have different grids: there is no merged segmentation, "
+                                   f"predict with merge=False")
             result['segmentation'] = segs[0] if len(segs) == 1 else combine_segmentations(segs)
         result['input'] = input
         if cache.get('projections'):
             result['projections'] = cache['projections']
         return TS2D.Result(result)
+
+    def _is_xr_channel(self, name: str) -> bool:
+        from .image import parse_projection_mode
+        return self.synthetic_xr is not None and parse_projection_mode(name)[0] in self.synthetic_xr_channels
+
+    def _render_xr_channels(self, mid: str, input: nrrd.Image, channels, projections: dict) -> bool:
+        """The channels of sub-model ``mid`` that are synthetic radiographs, rendered once per case under their names (``xray.synthetic_xr`` on
+        the engines' device, its host statement without one).  True when the sub-model has one; a sub-model that mixes a radiograph with
+        projected channels needs them on one grid (parallel rays), which :meth:`_prepare_model_input` checks."""
+        mine = [n for _, n in channels if self._is_xr_channel(n)]
+        if mine and input.components != 1:
+            raise RuntimeError(f"Model {mid}: a synthetic radiograph needs a scalar volume, found {input.components} components")
+        for n in mine:
+            if n not in projections:
+                from .xray import synthetic_xr
+                dev = (getattr(self.models[mid]._predictor.device, 'index', 0) or 0) if self._gpu_projection else None
+                projections[n] = synthetic_xr(input, self.synthetic_xr, device=dev)
+        return bool(mine)
 
     def predict(self, input: Union[nrrd.Image, str], collapse: bool = False, merge: bool = True, probabilities: bool = False) -> "TS2D.Result":
         """``probabilities``: every sub-model also returns the probabilities of its export (``HIPModel.apply(save_probabilities=True)``:
@@ -177,6 +210,8 @@ class TS2D:
         """What one sub-model contributes to a ``Result``: the segmentation ``model.apply`` returned for ``prepared``, its 3-D geometry restored."""
         input, input2d, native_2d = prepared
         res = {'id': mid, 'revision': self.models[mid].revision}
+        if getattr(input2d, 'xr_geometry', None) is not None:      # (a rendered sub-model: a 3-D reference is scored through the same rays)
+            res['xr_geometry'] = input2d.xr_geometry
         res['model'], res['group'] = decompose_model_key(mid)
         if getattr(seg, 'probabilities', None) is not None:      # (asked for: the array rides on the image the export returned)
             res['probabilities'] = seg.probabilities
@@ -208,7 +243,9 @@ class TS2D:
         model = self.models[mid]
         channels = sorted(model.channels.items())
         projections = cache.setdefault('projections', {})
+        rendered = False
         if get_actual_dimension(input) > 2:
+            rendered = self.synthetic_xr is not None and self._render_xr_channels(mid, input, channels, projections)
             need = [n for _, n in channels if n not in projections]
             on_device = self._gpu_projection and input.components == 1 and input.array.dtype.name in ('int16', 'uint8', 'float32', 'uint16', 'int32')
             if need and on_device and all(n.lower() in ('max', 'mip', 'mean', 'avg') for n in need):
@@ -220,13 +257,17 @@ class TS2D:
                 cache['device_zscore'] = pr['zscore']      # both projections normalised on the device (preprocess.py uses it)
             elif on_device and not self._max_mean_only(channels) and self._project_modes_on_device(model, input, channels, cache):
                 pass                                       # every channel of this sub-model projected and normalised by ts2d_project_coronal_modes
-            else:
+            elif need or not rendered:                     # (a sub-model of radiographs alone has nothing left to project: no reorientation copy)
                 input = reorient_image(input, 'RAI')
             chs = []
             for _, ch_name in channels:                      # channel NAME = projection mode (reference tool.py:156-158)
                 if ch_name not in projections:
                     projections[ch_name] = cast(project(input, mode=ch_name, axis='coronal'), np.float32)
                 chs.append(projections[ch_name])
+            if rendered and any(c.size != chs[0].size or not np.allclose(c.spacing, chs[0].spacing, rtol=1e-5, atol=1e-8) for c in chs[1:]):
+                raise RuntimeError(f"Model {mid} mixes synthetic radiographs and projections on different grids: "
+                                   + ', '.join(f"{n}: size {c.size}, spacing {tuple(c.spacing)}" for (_, n), c in zip(channels, chs))
+                                   + " (parallel rays put them on one grid)")
             input = compose(chs) if len(chs) > 1 else chs[0]
         else:
             if len(channels) != input.components:
@@ -251,6 +292,8 @@ class TS2D:
         # one preprocessing per distinct (channels, plan) of the case, shared by the sub-models (they run on threads: model.py takes the lock)
         import threading
         input2d.preprocess_cache = cache.setdefault('preprocessed', {'lock': threading.Lock(), 'items': {}})
+        if rendered:
+            input2d.xr_geometry = self.synthetic_xr
         return input, input2d, native_2d
 
     @staticmethod
@@ -407,6 +450,22 @@ class TS2D:
                 written.append(dump_components(self.components(key, connectivity), os.path.join(dest, f"{stem}.components.json")))
             return written
 
+        def _xr_geometry(self, model: Optional[str] = None):
+            """The ``xray.XRGeometry`` sub-model ``model`` was rendered under, None for a projected one.  The merged segmentation
+            (``model=None``) has one when every sub-model has that one; a mix of rendered and projected sub-models has no grid of its own and is
+            refused by name: score its sub-models one by one."""
+            models = self.data.get('models', {})
+            if model is not None:
+                return models.get(model, {}).get('xr_geometry')
+            found = {m: d.get('xr_geometry') for m, d in models.items()}
+            with_xr = sorted(m for m, g in found.items() if g is not None)
+            if not with_xr:
+                return None
+            if len(with_xr) != len(found) or any(found[m] != found[with_xr[0]] for m in with_xr):
+                raise ValueError(f"the merged segmentation mixes sub-models on synthetic radiographs ({', '.join(with_xr)}) and on projections "
+                                 f"({', '.join(sorted(set(found) - set(with_xr)))}): score each sub-model with model=<key>")
+            return found[with_xr[0]]
+
         def _scored_pair(self, reference, model: Optional[str] = None):
             """(segmentation, reference on its grid) as :meth:`evaluate` and :meth:`confusion` score them: a 3-D label volume is reoriented,
             projected along the coronal axis and collapsed as the segmentation is, an already-2-D segmentation is taken as it is, and a
@@ -419,7 +478,11 @@ class TS2D:
             if ref.components == 1 and get_actual_dimension(ref) > 2 and get_actual_dimension(seg) <= 2:
                 from .image import get_annotation_labels
                 num = seg.components if seg.components > 1 else max([int(i['value']) for i in get_annotation_labels(seg).values()] or [1])
-                if self.device is not None and ev.device_projects(ref):
+                geometry = self._xr_geometry(model)
+                if geometry is not None:                   # a result on a synthetic radiograph: the reference goes through the same rays
+                    from .xray import project_labels_xr
+                    ref = project_labels_xr(ref, num, geometry, device=self.device)
+                elif self.device is not None and ev.device_projects(ref):
                     ref = ev.project_labels_coronal_gpu(ref, num, self.device)
                 else:
                     ref = ev.project_labels(reorient_image(ref, 'RAI'), num, 'coronal')
