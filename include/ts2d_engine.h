@@ -1045,6 +1045,38 @@ int ts2d_volume_surface_distances(int device, const uint8_t* a, int kind_a, cons
 int ts2d_label_confusion(int device, const uint8_t* a, int kind_a, const uint8_t* b, int kind_b, const uint8_t* values, int K, int Z, int H, int W,
                          int64_t* out_i64 /* [K + 2][K + 2], row = side a */);
 
+/* ts2d_label_morphology: grow (dilate), shrink (erode), open or close every label of a 2-D segmentation by a radius in the unit of the spacing, with
+ * an exact Euclidean disc: offset (dy, dx) belongs iff (|dy| * sy)^2 + (|dx| * sx)^2 <= radius * radius in float64, every operation rounded on its
+ * own (csrc/morph.h; a pixel exactly on the circle belongs).  Erosion is the dual INSIDE the image, E(M) = ~D(~M): outside the image is neither
+ * background nor foreground, so a mask that touches an edge is not eaten from that edge.  open = D(E(M)), close = E(D(M)).  The statement is
+ * morphology.label_morphology_statement; the entry reproduces it byte for byte, counters included.  The float64 comparison is decided on the host,
+ * in a table of at most H integers; the kernels (csrc/kernels_morph.h) hold no floating-point number, and every loop is bounded by an extent: there
+ * is no give-up status.
+ *   seg, kind, values, K   as in ts2d_label_statistics with Z = 1: TS2D_STATS_PLANES, uint8 [K][H][W], label k is plane k > 0;
+ *                 TS2D_STATS_LABELMAP, ONE uint8 [H][W] and values[K], each 1 ... 255 and distinct, label k is seg == values[k].
+ *   sy, sx        the spacing of a row step and of a column step; radius in the same unit, 0 allowed (the output equals the input)
+ *   select        NULL (every label) or K bytes: label k is worked iff select[k] != 0.  An unselected label is returned untouched.
+ *   out_seg       the layout of seg.  Planes: every label on its own; a pixel that stays set keeps its byte, a cleared one becomes 0, a new one 1.
+ *                 Label map: each selected label's result is computed on its own mask (everything else counts as outside it).  erode and open
+ *                 clear the pixels of label k that its result does not hold.  dilate and close paint samples equal to 0 only, in the order of
+ *                 values (the first label wins); a non-zero sample, named or not, is never overwritten.
+ *   out_counters  int64 [K][TS2D_MORPH_COUNTERS]: pixels before, pixels after, added, removed (of a label map: counted after painting).
+ *   max_scratch_bytes   bounds the device scratch of the labels that work at once (0: 256 MiB): per label and pixel 2 bytes, + 1 for open and
+ *                 close, + 1 for a label map.  The two copies of the segmentation are not counted.
+ * Host pointers in and out; synchronous; the call owns its device scratch and frees it on every path.
+ * TS2D_ERR_INVALID, by name, before any device work and with the outputs untouched: a null seg, out_seg or out_counters, an unknown kind or op, K
+ * outside 1 ... 255, an extent below 1 or above TS2D_EVAL_MAX_EXTENT, more than 2^31 - 1 pixels, a radius that is negative or not finite, a
+ * spacing that is not positive and finite, a label map without values, with a value 0 or a repeated one, a bound below the scratch of one label.
+ * (A new symbol of ABI 9: nothing that existed changed.) */
+#define TS2D_MORPH_DILATE 0
+#define TS2D_MORPH_ERODE 1
+#define TS2D_MORPH_OPEN 2
+#define TS2D_MORPH_CLOSE 3
+#define TS2D_MORPH_COUNTERS 4
+int ts2d_label_morphology(int device, const uint8_t* seg, int kind /* TS2D_STATS_PLANES | TS2D_STATS_LABELMAP */, const uint8_t* values, int K,
+                          int H, int W, double sy, double sx, int op /* TS2D_MORPH_* */, double radius, const uint8_t* select /* K or NULL */,
+                          uint64_t max_scratch_bytes, uint8_t* out_seg, int64_t* out_counters /* [K][TS2D_MORPH_COUNTERS] */);
+
 /* Synthetic slice stream on the device (BASELINE config 4: "synthetic 10k-slice stream", generated per rank from (seed, slice
  * index) so that no host transfer skews the timing).  Writes n_elements fp32 values, approximately N(0,1), to device memory:
  * element i of the call = element (first_element + i) of the stream identified by `key`; a value depends on (key, element index)

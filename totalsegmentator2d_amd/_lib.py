@@ -87,6 +87,7 @@ STATS_MAX_PERCENTILES = 8                                   # TS2D_STATS_MAX_PER
 LABELS_RANGE, EVAL_MAX_TOLERANCES, EVAL_MAX_EXTENT = 1, 8, 32767      # TS2D_LABELS_RANGE, TS2D_EVAL_MAX_TOLERANCES, TS2D_EVAL_MAX_EXTENT
 EVAL_MAX_PERCENTILES = 8                                    # TS2D_EVAL_MAX_PERCENTILES
 COMP_FULL, COMP_FACES, COMP_GIVE_UP, COMP_LIST_FULL, COMP_COUNTERS = 0, 1, 1, 2, 5      # TS2D_COMP_*
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE, MORPH_COUNTERS = 0, 1, 2, 3, 4     # TS2D_MORPH_*
 
 # shorthands of the table below: int, void *, size_t, long long, unsigned long long, char *; pointers to a void * and to the three descriptors
 _I, _P, _Z, _LL, _ULL, _S = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_char_p
@@ -146,6 +147,7 @@ SIGNATURES = {
     'ts2d_surface_distance_profile': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _D, _D, _P, _I, _P, _I, _I, _Z, _P, _P, _P, _P, _P]),
     'ts2d_volume_surface_distances': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _D, _D, _D, _P, _I, _P, _I, _I, _Z, _P, _P, _P, _P, _P]),
     'ts2d_label_confusion': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'ts2d_label_morphology': (_I, [_I, _P, _I, _P, _I, _I, _I, _D, _D, _I, _D, _P, ctypes.c_uint64, _P, _P]),
     'ts2d_synth_slices': (_I, [_I, _ULL, _ULL, _ULL, _P, _P]),
     'ts2d_engine_reserve': (_I, [_P, _I, _I, _I]),
     'ts2d_engine_workspace_bytes': (_I, [_P, _I, _I, _I, ctypes.POINTER(_Z)]),
@@ -179,12 +181,13 @@ SYMBOLS = tuple(SIGNATURES)
 # ... and the boundary distances of volumes: without the entry evaluate.evaluate(volume_distances=True) keeps its statement
 # ... and the components of every label at once: without the entry components.label_components and clean_components keep the host route (their statement)
 # ... and the confusion matrix: without the entry evaluate.confusion keeps the host route (its statement)
+# ... and the label morphology: without the entry morphology.label_morphology keeps the host route (its statement)
 # ... and the two entries of the synthetic radiograph: without them xray.synthetic_xr and xray.project_labels_xr keep the host route (their statements)
 OPTIONAL = frozenset(n for n in SIGNATURES if n == 'ts2d_resample_cubic' or n.startswith('ts2d_planes_') or 'probabilities' in n
                      or n.startswith('ts2d_visual_')
                      or n in ('ts2d_engine_create_residual', 'ts2d_keep_largest_components', 'ts2d_project_coronal_modes', 'ts2d_label_statistics', 'ts2d_label_percentiles',
                               'ts2d_project_labels_coronal', 'ts2d_label_overlap', 'ts2d_surface_distances', 'ts2d_surface_distance_profile',
-                              'ts2d_volume_surface_distances', 'ts2d_label_components', 'ts2d_label_confusion', 'ts2d_project_xr', 'ts2d_project_labels_xr'))
+                              'ts2d_volume_surface_distances', 'ts2d_label_components', 'ts2d_label_confusion', 'ts2d_project_xr', 'ts2d_project_labels_xr', 'ts2d_label_morphology'))
 
 
 class EngineLibraryError(RuntimeError):

@@ -5,7 +5,8 @@
 // No device code here or in the .cpp files: they build without an offload pass.  Kernels live in engine.hip (the network), tiled.hip
 // (the sliding window, fold mean and export), prep.hip (projection, input resample, native 2-D planes), post.hip (largest-component
 // postprocessing), visual.hip (the PNG visuals; its host tables, visual_plan.cpp, have a header of their own), stats.hip (the per-label
-// statistics of a segmentation) and evaluate.hip (scoring a segmentation against a reference), each kernel in exactly one.
+// statistics of a segmentation), evaluate.hip (scoring a segmentation against a reference) and morph.hip (grow, shrink, open and close every
+// label by a radius in mm), each kernel in exactly one.
 #pragma once
 #include "../../include/ts2d_engine.h"
 #include <hip/hip_runtime_api.h>

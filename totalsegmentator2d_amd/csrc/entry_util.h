@@ -1,4 +1,4 @@
-// What the entries that need no engine (prep.hip, post.hip, visual.hip, stats.hip, evaluate.hip, ts2d_probabilities_from_logits) share of
+// What the entries that need no engine (prep.hip, post.hip, visual.hip, stats.hip, evaluate.hip, morph.hip, ts2d_probabilities_from_logits) share of
 // their call scaffolding: the layout of a call's one DevMem, the strided-view check, the sample types, the label side of a call and the size of
 // a chunk of labels.  Host only and free of HIP: plain C++ includes it, and tests/test_entry_util_cpu.py compiles it behind a main of its own.
 #pragma once

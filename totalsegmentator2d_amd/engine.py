@@ -867,6 +867,28 @@ def label_components(seg: np.ndarray, kind: int, values, shape_zhw, connectivity
     raise RuntimeError(f"ts2d_label_components: {total.value} components did not fit a list of as many rows")
 
 
+def label_morphology(seg: np.ndarray, kind: int, values, shape_hw, spacing_hw, op: int, radius: float, select=None, max_scratch_bytes: int = 0,
+                     device: int = 0):
+    """Grow, shrink, open or close every label on the device (C-ABI ts2d_label_morphology, csrc/kernels_morph.h).  ``seg``: C-contiguous uint8,
+    planes [K, H, W] (``kind`` = ``_lib.STATS_PLANES``) or one label map [H, W] with ``values`` [K] (``_lib.STATS_LABELMAP``); ``spacing_hw``:
+    the spacings of a row step and a column step; ``op``: ``_lib.MORPH_*``; ``radius`` in the unit of the spacing; ``select``: None or K
+    booleans.  Returns ``(out of the shape of seg, counters int64 [K, 4])`` - ``morphology.label_morphology_statement``'s byte for byte."""
+    fn = _entry('ts2d_label_morphology')
+    h, w = (int(v) for v in shape_hw)
+    vals, k = _label_side('label_morphology', seg, kind, values, 1, h, w)
+    sel = None
+    if select is not None:
+        sel = np.ascontiguousarray([1 if s else 0 for s in select], dtype=np.uint8)
+        if sel.shape != (k,):
+            raise RuntimeError(f"label_morphology: select has {sel.size} entries for {k} labels")
+    out = np.empty_like(seg)
+    counters = np.zeros((k, _lib.MORPH_COUNTERS), np.int64)
+    _lib.check(fn(int(device), seg.ctypes.data, int(kind), vals.ctypes.data if vals is not None else None, k, h, w, float(spacing_hw[0]),
+                  float(spacing_hw[1]), int(op), float(radius), sel.ctypes.data if sel is not None else None, int(max_scratch_bytes),
+                  out.ctypes.data, counters.ctypes.data), 'ts2d_label_morphology')
+    return out, counters
+
+
 def project_labels_coronal(buffer: np.ndarray, extents, strides, base: int, num: int, device: int = 0):
     """The label projection on the device (C-ABI ts2d_project_labels_coronal, csrc/kernels_evaluate.h).  ``buffer``: the volume's C-contiguous
     integer samples; ``extents`` (nz, ny, nx), ``strides`` (sz, sy, sx) and ``base`` in elements: the reoriented view of

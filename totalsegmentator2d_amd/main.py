@@ -66,8 +66,9 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
              visualize: bool = True, save_all: bool = False, silent: bool = False, models=None, batch_cases: int = 1, save_probabilities: bool = False,
              statistics: bool = False, reference: str = None, hausdorff_percentiles=(), average_distance: bool = False,
              statistics_percentiles=(), keep_largest: bool = False, min_component_mm: float = 0.0, components: bool = False,
-             component_connectivity: str = 'full', confusion: bool = False, synthetic_xr=None):
-    """``synthetic_xr``: an ``xray.XRGeometry`` (or True) switches the synthetic radiograph of ``TS2D`` on; None: the call of before."""
+             component_connectivity: str = 'full', confusion: bool = False, synthetic_xr=None, morphology=None, morphology_labels='all'):
+    """``morphology``: None, or ``(op, radius_mm)`` with op 'dilate', 'erode', 'open' or 'close' - ``Result.morphology`` of every result, on
+    ``morphology_labels``, BEFORE the component clean-up.  ``synthetic_xr``: an ``xray.XRGeometry`` (or True) switches the synthetic radiograph of ``TS2D`` on; None: the call of before."""
     model = DEFAULT_MODEL if model is None else model
     content = 'all' if visualize else 'file'
     which = 'all' if save_all else 'final'
@@ -75,7 +76,9 @@ def ts2d_run(src: str, dest: str, model: str = None, use_remote: bool = True, fe
     log("TS2D is a research tool. It is NOT validated for clinical use and should NOT be used for medical diagnosis or treatment.")
     stat_kw = {'percentiles': tuple(statistics_percentiles)} if len(statistics_percentiles) else {}      # without them: the call of before
 
-    def tidy(res):          # the clean-up comes before a result is saved, measured or scored; without its flags the result is the one predicted
+    def tidy(res):          # morphology, then the clean-up, both before a result is saved, measured or scored; without their flags the result is the one predicted
+        if morphology is not None:
+            res = res.morphology(morphology[0], morphology[1], labels=morphology_labels)
         if keep_largest or min_component_mm > 0:
             res = res.cleaned(keep_largest=keep_largest, min_size_mm=min_component_mm, connectivity=component_connectivity)
         return res
@@ -157,6 +160,14 @@ def ts2d_entry_point(argv=None):
                    "their sizes and where each starts (with --save-all one <case>-<group>.components.json per sub-model too).")
     p.add_argument("--component-connectivity", choices=("full", "faces"), default=None, help="With --keep-largest, --min-component-mm or --components: "
                    "which neighbours connect, full (8 / 26, the default) or faces (4 / 6).")
+    p.add_argument("--grow", type=float, default=None, metavar="MM", help="Grow every label by MM (an exact Euclidean disc in the spacing of the "
+                   "result) before the component clean-up and before the result is saved, measured or scored.  At most one of --grow, --shrink, "
+                   "--open and --close.")
+    p.add_argument("--shrink", type=float, default=None, metavar="MM", help="Shrink every label by MM (a label at the image edge is not eaten from that edge).")
+    p.add_argument("--open", type=float, default=None, metavar="MM", help="Open every label by MM: shrink, then grow - thin bridges and specks go.")
+    p.add_argument("--close", type=float, default=None, metavar="MM", help="Close every label by MM: grow, then shrink - pin-holes and gaps fill.")
+    p.add_argument("--morphology-labels", type=str, default=None, metavar="NAME[,NAME...]", help="With --grow, --shrink, --open or --close: only "
+                   "these labels are changed; the others stay as they are (in a label map: obstacles).")
     p.add_argument("--synthetic-xr", action="store_true", help="Render a synthetic radiograph of a 3-D input for every model channel named xr, xray "
                    "or x-ray (a cone beam along the coronal axis; the line integral of the density in mm of water), and score a 3-D --reference "
                    "through the same rays.")
@@ -192,11 +203,26 @@ def ts2d_entry_point(argv=None):
                     'component_connectivity': a.component_connectivity or 'full'}
     elif a.component_connectivity is not None:
         p.error("--component-connectivity chooses how components connect: give --keep-largest, --min-component-mm or --components")
+    morph_kw = {}
+    given = [(op, mm) for op, mm in (('dilate', a.grow), ('erode', a.shrink), ('open', a.open), ('close', a.close)) if mm is not None]
+    if len(given) > 1:
+        p.error("--grow, --shrink, --open and --close: at most one per run")
+    if given:
+        if not (math.isfinite(given[0][1]) and given[0][1] >= 0.0):
+            p.error("--grow, --shrink, --open and --close take a number of mm >= 0")
+        morph_kw = {'morphology': given[0]}
+        if a.morphology_labels is not None:
+            names = [n.strip() for n in a.morphology_labels.split(',') if n.strip()]
+            if not names:
+                p.error("--morphology-labels names no label")
+            morph_kw['morphology_labels'] = names
+    elif a.morphology_labels is not None:
+        p.error("--morphology-labels chooses the labels of a morphology step: give --grow, --shrink, --open or --close")
     ts2d_run(src=a.src, dest=a.dest, model=a.model, use_remote=not a.no_remote, fetch_remote=not a.no_fetch, collapse=a.collapse,
              visualize=a.visualize, save_all=a.save_all, silent=a.silent, batch_cases=a.batch_cases, save_probabilities=a.save_probabilities,
              statistics=a.statistics, reference=a.reference, hausdorff_percentiles=tuple(a.hausdorff_percentile or ()),
              average_distance=a.average_distance, **({'statistics_percentiles': tuple(a.statistics_percentile)} if a.statistics_percentile else {}), **clean_kw,
-             **({'confusion': True} if a.confusion else {}), **xr_kw)          # without the flags: the call of before
+             **({'confusion': True} if a.confusion else {}), **xr_kw, **morph_kw)          # without the flags: the call of before
 
 
 if __name__ == '__main__':

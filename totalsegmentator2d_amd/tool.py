@@ -433,6 +433,35 @@ class TS2D:
                     d['segmentation'] = clean(d['segmentation'])
             return type(self)(data, self.device)
 
+        def morphology(self, op: str, radius_mm: float, labels='all', models='all') -> "TS2D.Result":
+            """A NEW result whose segmentations are grown ('dilate'), shrunk ('erode'), opened or closed by ``radius_mm`` with an exact
+            Euclidean disc (``morphology.label_morphology``; ``labels``: 'all' or label names - a segmentation is asked for those of them it
+            has): the merged segmentation and that of every sub-model ``models`` selects ('all', or model keys).  Input and projections are
+            shared with this result, which stays untouched; with ``radius_mm = 0`` the new result holds equal bytes."""
+            from .image import get_annotation_labels
+            from .morphology import label_morphology
+            mset = {str(t).strip().lower() for t in _as_list(models)}
+            wanted = None if (isinstance(labels, str) and labels == 'all') else {str(n) for n in _as_list(labels)}
+
+            def work(seg):
+                mine = 'all' if wanted is None else sorted(wanted & set(get_annotation_labels(seg)))
+                return label_morphology(seg, op, radius_mm, device=self.device, labels=mine)[0]
+            if wanted is not None:
+                known = set()
+                for seg in [self.get_segmentation()] + [d.get('segmentation') for d in self.data.get('models', {}).values()]:
+                    if seg is not None:
+                        known |= set(get_annotation_labels(seg))
+                if wanted - known:
+                    raise ValueError(f"morphology: labels {sorted(wanted - known)} are in no segmentation of this result")
+            data = dict(self.data)
+            if self.get_segmentation() is not None:
+                data['segmentation'] = work(self.get_segmentation())
+            data['models'] = {m: dict(d) for m, d in self.data.get('models', {}).items()}
+            for m, d in data['models'].items():
+                if ('all' in mset or m.lower() in mset) and d.get('segmentation') is not None:
+                    d['segmentation'] = work(d['segmentation'])
+            return type(self)(data, self.device)
+
         def save_components(self, dest: str, name: str = 'result', models='final', naming: str = 'group', connectivity: str = 'full') -> List[str]:
             """``<name>.components.json`` for the merged segmentation and ``<name>-<group or model>.components.json`` per sub-model, selected
             by ``models`` and named as in :meth:`save_statistics`: ``json.dump`` of :meth:`components` with sorted keys."""
